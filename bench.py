@@ -11,6 +11,11 @@ is an RCCL all_gather of the caption ids (int64 [16, 21] per rank) at the end of
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs the W warm-up steps and the K timed steps on the timed path, writes the caption ids of
+the last timed step if --dump-outputs DIR is given, and prints the JSON result line.  --full adds everything else
+the benchmark reports: the pipelined == serial screen, the latency frontier, the serial point, the roofline and
+per-kernel breakdown, the other BASELINE configurations, host-fed inputs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -379,17 +384,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is repeated; the median repeat is reported")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip configs[1] / configs[4] / one-clip (reported beside the headline)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event instrumented pass")
-    ap.add_argument("--plain", action="store_true", help="only warm-up + the timed region (for rocprofv3 runs: every pass in the trace is one full step)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is repeated; the median repeat is reported (default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (without it: warm-up + the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the caption ids of the last timed step to DIR/caption_ids.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip configs[1] / configs[4] / one-clip / host-fed (reported beside the headline)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event instrumented pass")
     ap.add_argument("--serial", action="store_true", help="one batch at a time (no cross-batch pipelining)")
     ap.add_argument("--inflight", type=int, default=3, choices=(2, 3, 4),
                     help="submissions in flight when pipelined (3: same throughput as 4, lower latency)")
     ap.add_argument("--coalesce", type=int, default=1, choices=(1, 2, 4),
                     help="dynamic batching: run this many consecutive 16-clip batches as one pass")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -463,29 +477,29 @@ def main():
             ring.fence()                                   # every gather issued so far has completed, then barrier
         torch.cuda.synchronize(dev)
 
-    for i in range(args.warmup):
-        step(i)
-    fence()
     # K steps = K batches.  Default: three batches in flight (one image pass overlaps the token loops of
     # the batches before it, on the library's streams); every batch is submitted AND completed (ids gathered)
     # inside the timed region.  --serial runs one batch at a time.  The region (barrier + synchronize on both sides,
     # max over ranks) is repeated --repeats times and the median repeat is reported.
-    def timed_region(inflight=None, serial_mode=None):
+    last_ids = [None]                                      # what the region's last step returned to its caller
+
+    def timed_region(inflight=None, serial_mode=None, steps=None):
         inflight = args.inflight if inflight is None else inflight
         serial_mode = args.serial if serial_mode is None else serial_mode
-        ev_sub = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-        ev_done = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        steps = args.steps if steps is None else steps
+        ev_sub = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
+        ev_done = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
         out = None
         fence()
         t0 = time.perf_counter()
         if serial_mode:
-            for i in range(args.steps):
+            for i in range(steps):
                 ev_sub[i].record()
                 out = step(i)
                 ev_done[i].record()
         else:
             pending = []
-            for i in range(args.steps):
+            for i in range(steps):
                 ev_sub[i].record()
                 pending.append((i, model.greedy_decode_async(inputs[i % NIN], max_len=TOKENS, stop="never", coalesce=args.coalesce)))
                 if len(pending) == inflight * args.coalesce:
@@ -497,26 +511,33 @@ def main():
                 ev_done[j].record()
         fence()
         el = time.perf_counter() - t0
-        lat = sorted(ev_sub[i].elapsed_time(ev_done[i]) for i in range(args.steps))   # submit -> ids ready, per batch
+        lat = sorted(ev_sub[i].elapsed_time(ev_done[i]) for i in range(steps))   # submit -> ids ready, per batch
         p = lat[len(lat) // 2]
         if use_dist:
             t = torch.tensor([el, p], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el, p = float(t[0]), float(t[1])
         assert out.shape == (world * CLIPS_PER_GPU, TOKENS + 1)
+        last_ids[0] = out
         return el, p
 
+    if args.warmup > 0:                                    # the warm-up runs the timed path, so its first use is not timed
+        timed_region(steps=args.warmup)
     note("warm-up done")
     regions = sorted(timed_region() for _ in range(max(1, args.repeats)))
     note("timed regions done")
     elapsed, p50 = regions[len(regions) // 2]
     region_ms = [round(r[0] * 1e3, 3) for r in regions]
+    if args.dump_outputs and rank == 0:
+        # a view into the library's submission buffers (or the gather ring): copied before anything else runs
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "caption_ids.npy"), last_ids[0].cpu().numpy().astype(np.float64))
 
     # ---- correctness screen of the path just timed (outside the timed region): clips are independent (model.py:765), so
     # the ids of every rotating input must be BITWISE the same pipelined (the library's streams, --inflight in flight,
     # --coalesce) as one batch at a time on the caller's stream ----
     pipelined_equals_serial = None
-    if not args.plain:
+    if args.full:
         fence()
         want = [model.greedy_decode(x, max_len=TOKENS, stop="never").clone() for x in inputs]
         ok, pend = True, []
@@ -535,7 +556,7 @@ def main():
     # ---- the latency / throughput frontier (BASELINE.json metric: "captions/sec + p50 latency"): the same K-step region with
     # one batch at a time, two and three (four) batches in flight; the headline is one of these points ----
     frontier = None
-    if not args.plain and not args.serial:
+    if args.full and not args.serial:
         frontier = []
         for nf in (1, 2, 3, 4):
             if nf == args.inflight:
@@ -548,7 +569,7 @@ def main():
         note("latency frontier done")
     # ---- unpipelined reference point: one batch at a time (what a single real-time caller sees) ----
     serial = None
-    if not args.serial and not args.plain:
+    if args.full and not args.serial:
         ns = min(args.steps, 10)
         es = [torch.cuda.Event(enable_timing=True) for _ in range(ns + 1)]
         fence()
@@ -574,7 +595,7 @@ def main():
         ts = sorted(ts[2:])
         return ts[len(ts) // 2]
     decode = None
-    if not args.plain:
+    if args.full:
         fence()
         t_full, t_one = timed_greedy(TOKENS), timed_greedy(1)
         loop_ms = (t_full - t_one) * TOKENS / (TOKENS - 1)
@@ -587,7 +608,7 @@ def main():
 
     # ---- per-kernel-class timing: HIP events recorded by the library on its launch stream ----
     roofline, breakdown = None, None
-    if not args.no_profile and not args.plain:
+    if args.full and not args.no_profile:
         # The brackets need one batch at a time (synchronous calls); the kernels are those of the pipelined path.
         model.profile(True)
         nprof = min(args.steps, 5)
@@ -662,14 +683,14 @@ def main():
         roofline["attn_full_mfma_frac"] = roofline["classes"]["attn_full"]["frac"]
 
     others = None
-    if rank == 0 and world == 1 and not args.plain and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_other_configs:
         hf = host_fed(model, cfg, dev, note, args.steps, args.inflight, world * CLIPS_PER_GPU * args.steps / elapsed)
         del model
         others = other_configs(dev, note)
         others["host_fed"] = hf
     note("GPU measurements done")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, weights)
 
     if rank == 0:

@@ -5,7 +5,7 @@ ROUNDS=${ROUNDS:-2}
 for r in $(seq $ROUNDS); do
   for cfg in "" "$@"; do
     for mode in "" "--serial"; do
-      out=$(env $cfg python bench.py --no-cpu-baseline --plain $mode 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['p50_latency_ms'])")
+      out=$(env $cfg python bench.py --repeats 5 $mode 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['p50_latency_ms'])")
       echo "round $r  [${cfg:-default}] ${mode:-pipelined}: $out"
     done
   done
