@@ -294,7 +294,7 @@ int gitcap_profile_read(gitcap_t* h, int cls, double* ms_total, int64_t* launche
  * 4 bias->f32); A [M][K] bf16, W [N][K] bf16; tile = 64, 128 or 256 (square tiles: M, N multiples of the tile). */
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out,
                     int M, int N, int K, int epi, int tile, void* stream);
-/* The fp8 tile kernel (csrc/gemm_f8.hip): A8 [M][K] and W8 [N][K] OCP e4m3 codes (M, N multiples of 256, K of 128), out = acc * ascale *
+/* The fp8 tile kernel (csrc/gemm256.hip): A8 [M][K] and W8 [N][K] OCP e4m3 codes (M, N multiples of 256, K of 128), out = acc * ascale *
  * wscale[n] + bias; epi 4 -> fp32 [M][N], 0 -> bf16, 8 / 9 -> e4m3 codes of quick_gelu / erf_gelu (.) * out8_inv. */
 int gitcap_dbg_gemm_f8(const void* A8, const void* W8, const float* wscale, float ascale, const float* bias, void* out,
                        int M, int N, int K, int epi, float out8_inv, void* stream);

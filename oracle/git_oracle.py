@@ -55,7 +55,7 @@ def _q8(x: torch.Tensor) -> torch.Tensor:
 def _q8_static(x: torch.Tensor, scale: float) -> torch.Tensor:
     """OCP e4m3 with ONE static power-of-two scale, straight from the fp32 value, saturating at +-448 x scale: what the
     device's `compute="fp8_ffn"` epilogues write for the activation operand of the two FFN GEMMs (csrc/common.h:
-    pack_fp8x4; csrc/gemm_f8.hip)."""
+    pack_fp8x4; csrc/gemm256.hip)."""
     return (x / scale).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).to(torch.float32) * scale
 
 

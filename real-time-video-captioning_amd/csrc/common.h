@@ -114,3 +114,16 @@ __device__ __forceinline__ float erf_gelu(float x) {
     const float hx = 0.5f * x;
     return __builtin_fmaf(hx, fast_erf(x * 0.70710678118654752f), hx);
 }
+
+// Host: raises KERNEL's dynamic-LDS limit to `bytes` on its first launch on each device (the attribute belongs to the
+// device's code object).
+template <auto KERNEL>
+inline hipError_t set_dynamic_lds_once(int bytes) {
+    static bool done[64] = {false};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (done[dev & 63]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done[dev & 63] = (e == hipSuccess);
+    return e;
+}

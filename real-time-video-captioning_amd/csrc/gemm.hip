@@ -179,16 +179,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs a) {
 template <int EPI, int BM, int BN, int NST>
 hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
     constexpr int LDS_BYTES = NST * (BM + BN) * BK * 2;
-    static bool attr_done[64] = {false};            // per device: the attribute belongs to the device's code object
-    int dev_ = 0;
-    (void)hipGetDevice(&dev_);
-    bool& attr_set = attr_done[dev_ & 63];
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<EPI, BM, BN, NST>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    const hipError_t e = set_dynamic_lds_once<gemm_bf16_kernel<EPI, BM, BN, NST>>(LDS_BYTES);
+    if (e != hipSuccess) return e;
     const int grid = (a.M / BM) * (a.N / BN);
     hipLaunchKernelGGL((gemm_bf16_kernel<EPI, BM, BN, NST>), dim3(grid), dim3(256), LDS_BYTES, s, a);
     return hipGetLastError();

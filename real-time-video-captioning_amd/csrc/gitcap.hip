@@ -17,10 +17,6 @@
 #include <sched.h>
 
 #define GITCAP_ABI_VERSION 1
-// (tools/build_diag.py redefines this to reach the experimental tile kernels of tools/experiments/)
-#ifndef GITCAP_DBG_GEMM_DISPATCH
-#define GITCAP_DBG_GEMM_DISPATCH(tile, a, epi, s) ((tile) == 256 ? launch_gemm256(a, epi, s) : (tile) == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s))
-#endif
 
 // Speed-only switches (results do not depend on them: tests/test_parity_gpu.py).  Process-wide, set once from the
 // environment; gitcap_dbg_config (a test hook) may flip them at run time, so they are atomics: an entry point running on
@@ -105,7 +101,7 @@ struct gitcap {
     ExchangeHealth xh;                  // host_logic.h: once raised, the handle runs GEMM + row kernel for good
     int cus = 256;                      // compute units of the handle's device
     int nslab_max = 16;                 // fp32 split-K slabs per text row the workspace holds
-    // opt-in fp8 MFMA compute of the image rows' FFN GEMMs (gitcap_set_compute; gemm_f8.hip): e4m3 activation operands
+    // opt-in fp8 MFMA compute of the image rows' FFN GEMMs (gitcap_set_compute; gemm256.hip): e4m3 activation operands
     bool f8ffn = false;
     float f8_scale = 1.0f / 16.0f;                   // static power-of-two scale of the e4m3 activation codes (gitcap_set_fp8_scale)
     unsigned long long* f8_sat = nullptr;            // device counter: codes of valid rows the producing epilogues clamped at +-448
@@ -373,7 +369,7 @@ int gemm(gitcap* h, hipStream_t s, int epi, const bf16_t* A, int lda, const WRef
 
 std::atomic<bool> g_fuse_ln{!env_flag("GITCAP_NO_GEMM_LN")};
 
-// compute = fp8_ffn: FC1 and FC2 of the image rows on v_mfma_f32_16x16x128_f8f6f4 (gemm_f8.hip).  Their activation operands
+// compute = fp8_ffn: FC1 and FC2 of the image rows on v_mfma_f32_16x16x128_f8f6f4 (gemm256.hip).  Their activation operands
 // (the LayerNorm output in front of FC1, the GELU output in front of FC2) are written as e4m3 codes of value / f8_scale by the
 // producing epilogues -- one static power-of-two scale per handle (default 1/16: codes cover +-28), saturating, every clamped
 // code of a valid row counted (gitcap_fp8_saturations) --, the weights are the e4m3 codes of
@@ -415,7 +411,7 @@ int gemm_ln(gitcap* h, hipStream_t s, bool post, const bf16_t* A, int lda, const
     a.ln_out8 = ln8; a.ld_ln8 = N; a.ln_out8_inv = 1.0f / h->f8_scale; a.f8_sat = h->f8_sat;
     if (f8in) { a.W = (const bf16_t*)W.p; a.wscale = W.scale; a.ascale = h->f8_scale; }
     const bool force_fused = ln8 != nullptr || f8in;
-    // the e4m3 LayerNorm copy of the fp8-operand kernel exists for the PRE form only (gemm_f8.hip: LN8 = EPI_RESID_LN_PRE)
+    // the e4m3 LayerNorm copy of the fp8-operand kernel exists for the PRE form only (gemm256.hip: gemm256f8_kernel, LN8 = EPI_RESID_LN_PRE)
     if (f8in && ln8 && post) return fail(h, GITCAP_ERR_STATE, "fp8 compute: no e4m3 LayerNorm copy in the post-LN form of the fp8-operand GEMM");
     a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = eps; a.ln_out = ln_out; a.ld_ln = N; a.ln_stats = h->ln_stats; a.ln_cnt = h->ln_cnt;
     a.ln_stats_rows = h->Mi;
@@ -1418,11 +1414,12 @@ int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float
     a.out = out; a.ldo = N; a.resid = resid; a.ldr = N;
     if (epi < 0 || epi > EPI_BIAS_F32) return GITCAP_ERR_ARG;
     if (tile != 64 && tile != 128 && tile != 256) return GITCAP_ERR_ARG;
-    hipError_t e = GITCAP_DBG_GEMM_DISPATCH(tile, a, epi, (hipStream_t)stream);
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
     return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
 }
 
-// fp8 tile kernel (gemm_f8.hip) on caller-owned buffers: A8 [M][K], W8 [N][K] e4m3 codes, wscale [N], acc * ascale * wscale[n] + bias;
+// fp8 tile kernel (gemm256.hip) on caller-owned buffers: A8 [M][K], W8 [N][K] e4m3 codes, wscale [N], acc * ascale * wscale[n] + bias;
 // epi 4 -> out fp32 [M][N]; epi 0 -> bf16; epi 8 / 9 -> e4m3 codes of gelu(.) * out8_inv
 int gitcap_dbg_gemm_f8(const void* A8, const void* W8, const float* wscale, float ascale, const float* bias, void* out, int M, int N,
                        int K, int epi, float out8_inv, void* stream) {
@@ -1449,7 +1446,8 @@ int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const fl
         float* xo = out_f32;
         float* tmp = nullptr;
         if (post) { if (hipMalloc(&tmp, (size_t)M * N * 4) != hipSuccess) return GITCAP_ERR_NOMEM; xo = tmp; a.out = tmp; }
-        hipError_t e = GITCAP_DBG_GEMM_DISPATCH(tile, a, resid ? EPI_BIAS_RESID_F32 : EPI_BIAS_F32, s);
+        const int epi = resid ? EPI_BIAS_RESID_F32 : EPI_BIAS_F32;
+        hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
         if (e == hipSuccess) {
             LnArgs l{xo, N, gamma, beta, eps, M, N, post ? out_f32 : nullptr, N, (bf16_t*)out_bf16, N, nullptr, 1, 1, nullptr, nullptr, 0.f};
             e = launch_layernorm(l, s);

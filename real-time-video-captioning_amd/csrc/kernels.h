@@ -16,7 +16,7 @@ enum GemmEpi {
     // and each normalises its own columns -> the LayerNorm launch behind the GEMM and its re-read disappear.
     EPI_RESID_LN_PRE = 6,     // x = acc + bias + resid: out f32 = x (nullable), ln_out bf16 = LayerNorm(x) [+ ln_add] (pre-LN ViT block; ln_post)
     EPI_RESID_LN_POST = 7,    // x = acc + bias [+ resid]: out f32 = LayerNorm(x), ln_out bf16 = the same (post-LN decoder)
-    // fp8 kernel only (gemm_f8.hip): the GELU output as OCP e4m3 codes of y * out8_inv -- the activation operand of the next fp8 GEMM
+    // fp8 kernel only (gemm256.hip: gemm256f8_kernel): the GELU output as OCP e4m3 codes of y * out8_inv -- the activation operand of the next fp8 GEMM
     EPI_BIAS_QGELU_F8 = 8,    // out e4m3 = quick_gelu(acc + bias)
     EPI_BIAS_GELU_F8 = 9      // out e4m3 = erf_gelu(acc + bias)
 };
@@ -39,7 +39,7 @@ struct GemmArgs {
     unsigned* ln_cnt;             // [row blocks][2] per row block {arrivals, generation}: zero before the first launch, self-resetting
     int ln_stats_rows;            // rows of ln_stats (>= M)
     int ln_rowblock_map;          // set by the launcher: workgroup -> tile map hands every XCD whole row blocks (host_logic.h)
-    // fp8 compute (gemm_f8.hip): A and W point at e4m3 codes; the accumulators are multiplied by ascale * wscale[n]
+    // fp8 compute (gemm256.hip: gemm256f8_kernel): A and W point at e4m3 codes; the accumulators are multiplied by ascale * wscale[n]
     const float* wscale; float ascale;
     float out8_inv;               // EPI_BIAS_*GELU_F8: 1 / (static scale of the e4m3 output)
     unsigned char* ln_out8; int ld_ln8; float ln_out8_inv;   // nullable (EPI_RESID_LN_*): e4m3 copy of the LayerNorm output * ln_out8_inv
@@ -58,7 +58,7 @@ bool gemm256_ok(const GemmArgs& a);
 hipError_t launch_gemm256(const GemmArgs& a, int epi, hipStream_t s);   // 256x256 tile, 8-wave ping-pong
 bool gemm256_ln_ok(const GemmArgs& a);                                   // shape the EPI_RESID_LN_* epilogues accept
 bool gemm256f8_ok(const GemmArgs& a);                                    // fp8 operands: K % 128 == 0, wscale / ascale set
-hipError_t launch_gemm256f8(const GemmArgs& a, int epi, hipStream_t s);  // the same tile kernel on e4m3 operands (gemm_f8.hip)
+hipError_t launch_gemm256f8(const GemmArgs& a, int epi, hipStream_t s);  // the same tile kernel on e4m3 operands (gemm256.hip)
 
 // ---- skinny GEMMs (text rows; M = a few 16-row tiles): weight streaming, one wave per tile ----
 enum SkinnyEpi { SK_BIAS_BF16 = 0, SK_BIAS_GELU_BF16 = 1, SK_BIAS_RELU_BF16 = 2, SK_BIAS_F32 = 3 };

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 # csrc/Makefile (tools/isa_waits.py: product_flags), so what is linted is what is shipped.
 EXPECTED_HIPCC = "7.2"
 LINTED = (("ffn_txt.hip", "ffn_txt_kernelILi24ELb0"), ("ffn_txt.hip", "ffn_txt_kernelILi24ELb1"), ("gemm256.hip", "gemm256_kernelILi6E"),
-          ("gemm_f8.hip", "gemm256f8_kernelILi6E"), ("skinny.hip", "skinny_head_kernelILi24ELb0"), ("skinny.hip", "skinny_rows3_kernelILi24ELi0"))
+          ("gemm256.hip", "gemm256f8_kernelILi6E"), ("skinny.hip", "skinny_head_kernelILi24ELb0"), ("skinny.hip", "skinny_rows3_kernelILi24ELi0"))
 
 
 def _hipcc_state():
@@ -42,7 +42,7 @@ elif _state == "other":
 # (ILi6ELb1 / ILi7ELb1: the opt-in fp8-compute instantiations that also write and count the e4m3 copy of the LayerNorm output)
 SCRATCH_ALLOWED = {"gemm256_kernelILi6ELb1E": 80, "gemm256_kernelILi7ELb1E": 32,
                    "gemm256f8_kernelILi6E": 40, "gemm256f8_kernelILi7E": 32}
-FILES = ["attention.hip", "ffn_txt.hip", "gemm.hip", "gemm256.hip", "gemm_f8.hip", "preproc.hip", "rowops.hip",
+FILES = ["attention.hip", "ffn_txt.hip", "gemm.hip", "gemm256.hip", "preproc.hip", "rowops.hip",
          "skinny.hip", "student.hip", "txtblock.hip"]
 
 
@@ -111,7 +111,7 @@ def test_gemm_ln_epilogue_keeps_its_spills_out_of_the_row_loops(listings):
     followed by vmcnt(0) in front of every row's store (round 5: +15 % per launch when a kernarg-layout change moved them there).
     Property: no scratch traffic in the two row loops between the end of the K loop and the statistics publish (the first buffer
     store), and the x stores of both half-blocks are waited for with counted waits (16 stores, first wait vmcnt(15))."""
-    for f, pat in (("gemm256.hip", "gemm256_kernelILi6E"), ("gemm_f8.hip", "gemm256f8_kernelILi6E")):
+    for f, pat in (("gemm256.hip", "gemm256_kernelILi6E"), ("gemm256.hip", "gemm256f8_kernelILi6E")):
         pres = [r for r in listings[f] if pat in r[0]]
         assert 1 <= len(pres) <= 2, [r[0] for r in pres]              # the pre-LN instantiation(s) of the tile kernel (gemm256: both K-loop forms)
         for name, _, _, toks in pres:

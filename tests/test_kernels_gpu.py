@@ -163,7 +163,7 @@ def test_layernorm_vs_reference(lib, rows, D):
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (512, 1024, 1024), (768, 4096, 1024), (512, 1024, 4096), (256, 768, 3072)])
 def test_gemm_fp8_vs_fp32_reference(lib, M, N, K):
-    """gemm_f8.hip (v_mfma_f32_16x16x128_f8f6f4): e4m3 codes in, exact products, fp32 accumulation -- against the fp32
+    """gemm256f8_kernel, gemm256.hip (v_mfma_f32_16x16x128_f8f6f4): e4m3 codes in, exact products, fp32 accumulation -- against the fp32
     matmul of the dequantised operands; then the e4m3-output GELU epilogues against the same reference rounded to e4m3."""
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a_f = (torch.randn(M, K, device="cuda", generator=g) * 1.5).clamp(-27, 27)

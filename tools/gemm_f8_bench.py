@@ -1,4 +1,4 @@
-# fp8 tile kernel (gemm_f8.hip) against the bf16 one (gemm256.hip) on the same shapes, through the C-ABI debug hooks,
+# fp8 tile kernel (gemm256f8_kernel) against the bf16 one (gemm256_kernel), both in gemm256.hip, on the same shapes, through the C-ABI debug hooks,
 # interleaved rounds in one process.  Shapes: BASELINE configs[4] (GIT-large, 10 240 image rows) and the headline.
 import sys, ctypes, torch
 sys.path.insert(0, 'real-time-video-captioning_amd')
