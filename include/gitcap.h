@@ -249,6 +249,45 @@ int gitcap_beam_search_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, in
                                   int beams, int max_steps, float length_penalty, int per_node_beam_size,
                                   int64_t* decoded_out, float* logprobs_out, float* step_logits_out, void* stream, int* ticket);
 
+/* Sliding frame window for live captioning (the reference's loop, src/real_time_inference.py:44-57, collects six sampled frames,
+ * captions them and clears its list: one caption per six new frames, each re-encoding frames it has never seen).  A caption of the
+ * last F frames after every new one would encode each frame F times through gitcap_greedy.  The ViT encodes every frame on its own,
+ * and the temporal embedding is added after ln_post: so the handle keeps a ring of the fp32 ln_post rows (embedding NOT added) of
+ * the last F frames of B clips that advance in lockstep, a push encodes only the new frames, and a window call adds each frame's
+ * embedding at its current position and runs the decoder's image prefix (which does depend on the whole window) and the token loop.
+ *
+ * gitcap_window_reset: B = 0 releases the ring.  Otherwise (re)allocates it for B <= max_batch clips and F <= max_frames (and
+ * <= num_frames when num_frames > 0) frames, and empties it.  Set-up call: may synchronise.
+ * gitcap_window_push: encode n (1 <= n <= F) new frames per clip and append them to the ring.  frames: device [B][n][3][S][S] fp32
+ * (as gitcap_encode); gitcap_window_push_raw: raw uint8 BGR [B][n][H][W][3] (as gitcap_encode_raw).  Frame j of a push is older
+ * than frame j + 1.
+ * gitcap_window_greedy / _beam_search: caption the current window (the last F frames pushed, oldest = temporal embedding 0);
+ * outputs as gitcap_greedy / gitcap_beam_search, visual_out (nullable, 16-byte aligned) as gitcap_encode's.
+ *
+ * Results: window_greedy's ids and steps are bitwise those of gitcap_greedy on the window's F frames, in the same weight-storage,
+ * compute and KV-cache mode; visual_out is bitwise gitcap_encode's; window_beam_search is bitwise gitcap_beam_search; the _raw push
+ * is bitwise gitcap_preprocess followed by gitcap_window_push.
+ * Isolation: a push writes only encoder workspace and the ring -- not slot 0's image K/V, the text cache or the current image, so a
+ * gitcap_text_forward after a push continues against the previous image.  A window call leaves slot 0 exactly as gitcap_greedy
+ * would.  Other synchronous calls and pipelined submissions made between pushes do not disturb the ring; pushes order themselves
+ * behind submissions in flight like every other synchronous entry point.  Pushes and window calls may be issued on different
+ * streams: each push waits for an event recorded behind the last window call's image prefix, each window call for one recorded
+ * behind the last ring write (no device synchronisation).
+ * Errors: GITCAP_ERR_ARG when B differs from the reset's, n < 1, n > F, or a pointer is null or misaligned; GITCAP_ERR_STATE for a
+ * push before any reset and a window call before F frames have been pushed since the reset; GITCAP_ERR_EXCHANGE (gitcap_poll_errors
+ * semantics): the ring's rows are undefined, so the window is emptied (as after a reset) and the error is returned once -- push the
+ * last F frames again.
+ * Workspace: gitcap_workspace_bytes counts the ring while it is allocated, B * F * N * enc_width * 4 bytes (58 MB at 16 clips x 6
+ * frames of GIT-base); the push stages its rows in the image pass's own q|k|v buffer.  A handle that never resets a window
+ * allocates nothing. */
+int gitcap_window_reset(gitcap_t* h, int B, int F);
+int gitcap_window_push(gitcap_t* h, const float* frames, int B, int n, void* stream);
+int gitcap_window_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int n, int H, int W, void* stream);
+int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out,
+                         int64_t* ids_out, int32_t* steps_out, void* stream);
+int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
+                              float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream);
+
 /* Host-side staging copy for host-fed callers (no reference counterpart): bytes from pageable memory (a DataLoader batch without
  * pin_memory, OpenCV frames) into a page-locked staging buffer, split over up to 8 threads -- as many as the process may really use
  * (affinity mask, cgroup CPU quota; GITCAP_HOST_COPY_THREADS overrides).  Plain memcpy semantics, blocking, no device work.

@@ -164,6 +164,17 @@ struct gitcap {
     int n_txt = NSLOT;
     bool pipelined = false; // the launches being issued belong to a gitcap_greedy_submit (other batches share the chip)
 
+    // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
+    // last win_F frames of win_B clips, clip-major [B][F][N][Dv].  win_head = the slot the next frame goes to (= the oldest frame
+    // once the window is full); win_count = frames pushed since the reset, capped at F.  A push orders itself behind the last
+    // window call's image prefix (ev_read: it rewrites the encoder workspace, hb included) and a window call behind the last
+    // push (ev_ring), whichever streams they were issued on.
+    float* win_ring = nullptr;
+    int64_t win_bytes = 0;
+    int win_B = 0, win_F = 0, win_head = 0, win_count = 0;
+    hipEvent_t win_ev_ring = nullptr, win_ev_read = nullptr;
+    bool win_ring_rec = false, win_read_rec = false;
+
     // instrumentation (bench.py): HIP-event brackets per kernel class, on the launch stream
     bool prof_on = false;
     struct ProfRec { hipEvent_t a, b; double flops, bytes; };
@@ -235,6 +246,7 @@ int poll_exchange(gitcap* h) {
     h->poison_upto = poison_mark(h->next_ticket);   // every submission made so far may hold undefined rows: its wait says so, every time
     *(volatile unsigned*)h->ln_fail = 0;
     if (h->ln_cnt) (void)hipMemset(h->ln_cnt, 0, h->ln_cnt_words * sizeof(unsigned));
+    h->win_count = 0;       // the frame window's rows may be undefined too: it is emptied, the caller pushes its frames again
     return fail(h, GITCAP_ERR_EXCHANGE, "a GEMM + LayerNorm launch timed out waiting for its sibling tiles (CUs held by another "
                 "process or a CU-masked stream?): results since the last call are undefined -- re-run them; this handle now uses "
                 "separate LayerNorm launches");
@@ -862,6 +874,9 @@ void gitcap_destroy(gitcap_t* h) {
     for (auto& t : h->txt_streams)
         if (t) (void)hipStreamDestroy(t);
     if (h->s_enc) (void)hipStreamDestroy(h->s_enc);
+    if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
+    if (h->win_ev_read) (void)hipEventDestroy(h->win_ev_read);
+    if (h->win_ring) (void)hipFree(h->win_ring);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
     for (auto& kv : h->w)
@@ -1032,14 +1047,16 @@ int gitcap_encode(gitcap_t* h, const float* frames, int B, int F, float* visual_
     return encode_impl(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
 }
 
-static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream) {
-    int rc = src.u8 ? check_frames(h, src.u8, B, F, true) : check_frames(h, src.f32, B, F);
-    if (rc) return rc;
+// The encoder half of the image pass: B x F frames (checked by the caller) through patch gather, the ViT blocks and ln_post.
+// Its output: the bf16 rows in h->hb (the decoder input) and, when ln_f32 != nullptr, the fp32 rows [B*F*N][Dv] there; addv
+// (nullable) = the temporal embedding, added to both inside the ln_post epilogue (frame = (row / N) % F).  Touches the encoder
+// workspace only (not the image K/V, the text rows or have_image).  taps: gitcap_dbg_enc_tap may copy the residual stream.
+static int encode_frames(gitcap* h, FrameSrc src, int B, int F, float* ln_f32, const float* addv, bool taps, hipStream_t stream) {
+    int rc;
     hipStream_t s = stream;
     const gitcap_config& c = h->c;
     const int Dv = h->Dv, N = h->N, nf = B * F, rows = nf * N, Mp = pad_to(rows, 256);
     const int P = nf * h->G * h->G, Pp = pad_to(P, 256);
-    h->have_image = false;
     h->n_staged = 0;             // nothing staged yet in this pass (a stale entry could match a recycled address)
 
     // patchify (conv k = stride = p, no bias) + CLS + position embedding, then ln_pre
@@ -1080,7 +1097,7 @@ static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
 
     // gitcap_dbg_enc_tap (synchronous calls only): the residual stream entering block e
     auto tap = [&](int e) -> hipError_t {
-        return (h->enc_tap && h->cur_slot == 0 && !h->pipelined && e < c.enc_layers)
+        return (taps && h->enc_tap && h->cur_slot == 0 && !h->pipelined && e < c.enc_layers)
                    ? hipMemcpyAsync(h->enc_tap + (size_t)e * rows * Dv, h->x, (size_t)rows * Dv * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
     };
     HIP_OK(h, tap(0));
@@ -1117,12 +1134,19 @@ static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
             // already adjacent rows, so the concat along tokens (model.py:382) is the identity on this layout.  x itself is
             // not needed any more.  The fp32 visual features (58 MB at B=16, F=6) are written straight into the caller's
             // buffer and only when asked for; the decoder consumes the bf16 copy.
-            const float* addv = c.num_frames > 0 ? h->temporal : nullptr;
             if ((rc = gemm_ln(h, s, false, fc2_in, c.enc_ffn, L.fc2w, L.fc2b, Mp, Dv, c.enc_ffn, nullptr, h->x, h->ln_post_w, h->ln_post_b,
-                              c.enc_ln_eps, rows, h->hb, nullptr, addv, N, F, visual_out, nullptr, f8))) return rc;
+                              c.enc_ln_eps, rows, h->hb, nullptr, addv, N, F, ln_f32, nullptr, f8))) return rc;
         }
     }
-    return image_prefix(h, B, F * N, s);
+    return 0;
+}
+
+static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream) {
+    int rc = src.u8 ? check_frames(h, src.u8, B, F, true) : check_frames(h, src.f32, B, F);
+    if (rc) return rc;
+    h->have_image = false;
+    if ((rc = encode_frames(h, src, B, F, visual_out, h->c.num_frames > 0 ? h->temporal : nullptr, true, stream))) return rc;
+    return image_prefix(h, B, F * h->N, stream);
 }
 
 int gitcap_set_visual(gitcap_t* h, const float* visual, int B, int S_img, void* stream) {
@@ -1342,6 +1366,122 @@ int gitcap_beam_search_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, in
     return submit_common(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream, ticket, [&](hipStream_t s) {
         return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
     });
+}
+
+// ---- frame window ------------------------------------------------------------------------------------------------------------
+// A ViT frame is encoded on its own (attention stays inside the frame, every GEMM and row kernel is batch invariant), and the only
+// step between the encoder and the decoder that depends on a frame's position in the clip is the temporal embedding, added after
+// ln_post in fp32.  So the ring keeps each frame's fp32 ln_post rows once, and a caption of the window adds the embedding of each
+// frame's current position (window_assemble_kernel: the add of the fused epilogue) and runs the decoder's image prefix.
+
+int gitcap_window_reset(gitcap_t* h, int B, int F) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "window_reset: null handle");
+    GUARD(h);
+    if (B < 0 || (B > 0 && (B > h->c.max_batch || F < 1 || F > h->c.max_frames || (h->c.num_frames > 0 && F > h->c.num_frames))))
+        return fail(h, GITCAP_ERR_ARG, "window_reset: B / F outside the sizes the handle was created for");
+    const int64_t bytes = B > 0 ? (int64_t)B * F * h->N * h->Dv * 4 : 0;
+    if (h->win_ring && bytes != h->win_bytes) {
+        HIP_OK(h, hipDeviceSynchronize());        // pushes or window calls in flight may still use the ring
+        HIP_OK(h, hipFree(h->win_ring));
+        h->win_ring = nullptr; h->win_bytes = 0;
+    }
+    h->win_B = h->win_F = h->win_head = h->win_count = 0;
+    if (B == 0) return 0;
+    if (!h->win_ev_ring) {
+        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
+        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
+    }
+    if (!h->win_ring) {
+        hipError_t e = hipMalloc(&h->win_ring, (size_t)bytes);
+        if (e != hipSuccess) { h->win_ring = nullptr; return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc frame window: ") + hipGetErrorString(e)); }
+        h->win_bytes = bytes;
+    }
+    h->win_B = B; h->win_F = F;
+    return 0;
+}
+
+// encode n new frames of each clip and append them to the ring: fp32 ln_post rows -> staging -> ring slots
+static int window_push(gitcap* h, FrameSrc src, int B, int n, hipStream_t s) {
+    if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "window_push: no frame window (gitcap_window_reset first)");
+    if (B != h->win_B || n < 1 || n > h->win_F) return fail(h, GITCAP_ERR_ARG, "window_push: B differs from the reset's, or n outside [1, F]");
+    int rc = src.u8 ? check_raw(h, src.u8, B, n, src.H, src.W) : check_frames(h, src.f32, B, n);
+    if (rc) return rc;
+    select_slot(h, 0);
+    HIP_OK(h, join_async(h, s));
+    if (h->win_read_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
+    if (h->win_ring_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    // staging: the q|k|v buffer of the image rows (bf16 [Mi][3 Dv], 1.5x the bytes of fp32 [Mi][Dv]) is dead once the last block's
+    // attention has read it, and only the final FC2 + ln_post launch and the scatter run after that
+    float* stage = (float*)h->qkv;
+    if ((rc = encode_frames(h, src, B, n, stage, nullptr, false, s))) return rc;
+    {
+        ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, 8.0 * B * n * (double)h->N * h->Dv);
+        HIP_OK(h, launch_window_scatter(stage, h->win_ring, B, n, h->win_F, h->win_head, h->N, h->Dv, s));
+    }
+    HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
+    h->win_ring_rec = true;
+    h->win_head = (h->win_head + n) % h->win_F;
+    h->win_count = std::min(h->win_count + n, h->win_F);
+    return 0;
+}
+
+int gitcap_window_push(gitcap_t* h, const float* frames, int B, int n, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "window_push: null handle");
+    GUARD(h);
+    POLL(h);
+    return window_push(h, FrameSrc{frames, nullptr, 0, 0}, B, n, (hipStream_t)stream);
+}
+
+int gitcap_window_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int n, int H, int W, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "window_push_raw: null handle");
+    GUARD(h);
+    POLL(h);
+    return window_push(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, n, (hipStream_t)stream);
+}
+
+// the current window -> decoder input (+ visual features) -> image prefix on slot 0
+static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
+    if (!h->win_ring || h->win_count < h->win_F) return fail(h, GITCAP_ERR_STATE, "window: fewer than F frames pushed since the reset");
+    if (((uintptr_t)visual_out & 15) != 0) return fail(h, GITCAP_ERR_ARG, "window: visual_out must be 16-byte aligned");
+    const int B = h->win_B, F = h->win_F, N = h->N, Dv = h->Dv;
+    const float* temporal = h->c.num_frames > 0 ? h->temporal : nullptr;
+    select_slot(h, 0);
+    HIP_OK(h, join_async(h, s));
+    HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    h->have_image = false;
+    {
+        const double rows = (double)B * F * N;
+        ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, rows * Dv * (4.0 + 2.0 + (visual_out ? 4.0 : 0.0)));
+        HIP_OK(h, launch_window_assemble(h->win_ring, temporal, h->hb, visual_out, B, F, h->win_head, N, Dv, s));
+    }
+    int rc = image_prefix(h, B, F * N, s);
+    if (rc) return rc;
+    HIP_OK(h, hipEventRecord(h->win_ev_read, s));
+    h->win_read_rec = true;
+    return 0;
+}
+
+int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, int64_t* ids_out, int32_t* steps_out, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "window_greedy: null handle");
+    GUARD(h);
+    POLL(h);
+    int rc = greedy_check(h, max_len, stop, ids_out);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = window_prefix(h, visual_out, s))) return rc;
+    return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
+}
+
+int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
+                              float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "window_beam_search: null handle");
+    GUARD(h);
+    POLL(h);
+    int rc = beam_check(h, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = window_prefix(h, visual_out, s))) return rc;
+    return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
 }
 
 int gitcap_reorder_rows(gitcap_t* h, const int32_t* src_rows, int rows, int t_len, void* stream) {
@@ -1681,7 +1821,7 @@ int gitcap_weight_bytes(const gitcap_t* h, int64_t* bytes) {
 
 int gitcap_workspace_bytes(const gitcap_t* h, int64_t* bytes) {
     if (!h || !bytes) return GITCAP_ERR_ARG;
-    *bytes = h->ws_bytes;
+    *bytes = h->ws_bytes + h->win_bytes;
     return 0;
 }
 

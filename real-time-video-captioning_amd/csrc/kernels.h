@@ -205,6 +205,13 @@ hipError_t launch_gather_hidden(const float* img, const float* txt, float* out, 
                                 size_t img_entry_stride, size_t txt_entry_stride, hipStream_t s);
 // V slice of kv [rows][3D] (bf16) -> e4m3 codes v8 [H][pitch][64] + power-of-two scales vs [H][pitch] per (row, head), head-major
 hipError_t launch_kv_quant_v(const bf16_t* kv, unsigned char* v8, float* vs, int rows, int D, int H, int64_t pitch, hipStream_t s);
+// frame window (gitcap_window_*): ring = fp32 ln_post rows of the last F frames of B clips, [B][F][rows_per_frame][D] (no temporal
+// embedding).  scatter: src [B][n][rows_per_frame][D] (contiguous) -> ring slot (head + j) % F of clip b, frame j of the push.
+hipError_t launch_window_scatter(const float* src, float* ring, int B, int n, int F, int head, int rows_per_frame, int D, hipStream_t s);
+// assemble: window position f of clip b = ring slot (head + f) % F (head = the oldest frame) + temporal[f] (nullable) -> out bf16
+// [B*F*N][D] (the decoder input) and vis fp32 (nullable); the same bits as the ln_post epilogue that adds the embedding itself
+hipError_t launch_window_assemble(const float* ring, const float* temporal, bf16_t* out, float* vis, int B, int F, int head, int N, int D,
+                                  hipStream_t s);
 // f32 -> bf16 copy
 hipError_t launch_cast_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t s);
 // e4m3 weight rows [rows][K] (+ per-row power-of-two scale) -> bf16 [rows][K] (exact); K % 16 == 0

@@ -175,6 +175,41 @@ __global__ __launch_bounds__(256) void gather_hidden_kernel(const float* __restr
     for (int c = threadIdx.x * 4; c < D; c += 1024) *(f32x4*)(out + row * D + c) = *(const f32x4*)(src + c);
 }
 
+// ---- frame window (gitcap_window_*) ----------------------------------------------------------
+// push: the ln_post rows of B x n new frames ([B][n][rows_per_frame][D], contiguous) -> ring slots (head + j) % F of their
+// clip ([B][F][rows_per_frame][D]).  A plain copy, 16 B per lane; blockIdx.y = frame (b, j).
+__global__ __launch_bounds__(256) void window_scatter_kernel(const float* __restrict__ src, float* __restrict__ ring, int n, int F,
+                                                             int head, int64_t frame4) {
+    const int fr = blockIdx.y, b = fr / n, j = fr % n;
+    const float* s = src + (size_t)fr * frame4 * 4;
+    float* d = ring + ((size_t)b * F + (head + j) % F) * frame4 * 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < frame4; i += (int64_t)gridDim.x * 256)
+        *(f32x4*)(d + i * 4) = *(const f32x4*)(s + i * 4);
+}
+
+// caption: row (b, f, tok) of the decoder input = bf16(ring[b][(head + f) % F][tok] + temporal[f]), optionally also the fp32 sum
+// (visual features).  One wave per row, lane = 4 consecutive columns, as layernorm_kernel; the add is the one the fused ln_post
+// epilogue makes (a lone fp32 add, compiled without contraction) and the rounding its pack_bf2, so the bits are gitcap_encode's.
+__global__ __launch_bounds__(256) void window_assemble_kernel(const float* __restrict__ ring, const float* __restrict__ temporal,
+                                                              bf16_t* __restrict__ out, float* __restrict__ vis, int rows, int F,
+                                                              int head, int N, int D) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int tok = row % N, f = (row / N) % F, b = row / (N * F);
+    const float* src = ring + (((size_t)b * F + (head + f) % F) * N + tok) * D;
+    const float* t = temporal ? temporal + (size_t)f * D : nullptr;
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 y = *(const f32x4*)(src + c);
+        if (t) y += *(const f32x4*)(t + c);
+        if (vis) *(f32x4*)(vis + (size_t)row * D + c) = y;
+        uint2 o;
+        o.x = pack_bf2(y[0], y[1]);
+        o.y = pack_bf2(y[2], y[3]);
+        *(uint2*)(out + (size_t)row * D + c) = o;
+    }
+}
+
 // e4m3 weight panel -> bf16 staging panel for the big-tile GEMMs (16 values per thread: 16-B read, 32-B write)
 __global__ __launch_bounds__(256) void dequant_fp8_kernel(const unsigned char* __restrict__ w8, const float* __restrict__ scale,
                                                           bf16_t* __restrict__ out, int K, int64_t n16) {
@@ -811,6 +846,23 @@ hipError_t launch_gather_hidden(const float* img, const float* txt, float* out, 
     const size_t rows = (size_t)B * n_entries * (S_img + T);
     hipLaunchKernelGGL(gather_hidden_kernel, dim3((unsigned)rows), dim3(256), 0, s, img, txt, out, n_entries, S_img, T, D,
                        img_entry_stride, txt_entry_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_scatter(const float* src, float* ring, int B, int n, int F, int head, int rows_per_frame, int D, hipStream_t s) {
+    if (B <= 0 || n <= 0 || n > F || head < 0 || head >= F || rows_per_frame <= 0 || D % 4) return hipErrorInvalidValue;
+    const int64_t frame4 = (int64_t)rows_per_frame * D / 4;
+    const unsigned gx = (unsigned)std::min<int64_t>((frame4 + 255) / 256, 64);
+    hipLaunchKernelGGL(window_scatter_kernel, dim3(gx, (unsigned)(B * n)), dim3(256), 0, s, src, ring, n, F, head, frame4);
+    return hipGetLastError();
+}
+
+hipError_t launch_window_assemble(const float* ring, const float* temporal, bf16_t* out, float* vis, int B, int F, int head, int N, int D,
+                                  hipStream_t s) {
+    if (B <= 0 || F <= 0 || head < 0 || head >= F || N <= 0 || D % 4 || D > 1024) return hipErrorInvalidValue;
+    const int rows = B * F * N;
+    hipLaunchKernelGGL(window_assemble_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ring, temporal, out, vis, rows, F,
+                       head, N, D);
     return hipGetLastError();
 }
 

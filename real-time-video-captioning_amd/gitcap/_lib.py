@@ -41,6 +41,11 @@ SYMBOLS = {
                                          POINTER(c_int)]),
     "gitcap_beam_search_raw_submit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int,
                                               c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "gitcap_window_reset": (c_int, [c_void_p, c_int, c_int]),
+    "gitcap_window_push": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gitcap_window_push_raw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_window_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gitcap_window_beam_search": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_enc_tap": (c_int, [c_void_p, c_void_p]),
     "gitcap_host_copy": (c_int, [c_void_p, c_void_p, c_int64]),
     "gitcap_poll_errors": (c_int, [c_void_p]),

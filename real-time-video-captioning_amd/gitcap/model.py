@@ -29,6 +29,7 @@ from torch import nn
 from . import _lib
 from .config import CGitCapConfig, GitCapConfig, git_base
 from . import weights as W
+from .window import WindowSchedule
 
 STOP_NEVER, STOP_ALL_SEP = 0, 1
 
@@ -247,6 +248,120 @@ class InferFuture(_Future):
         return self._done
 
 
+class CaptionStream:
+    """Live captioning over a sliding window of frames (GitCaptioner.caption_stream; include/gitcap.h: gitcap_window_*).  Every
+    frame is encoded once, when it is pushed; a caption of the last `window` frames re-runs only the decoder's image prefix and the
+    token loop.  Captions are bitwise those of greedy_decode (or of infer's device search) on the window's frames."""
+
+    def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features):
+        self._m = model
+        self._sched = WindowSchedule(batch, window, hop)
+        self._max_len, self._mode = max_len, mode
+        self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
+        self._kept = []                  # the last `window` frames per push order, [B, ...] each: what a recovery pushes again
+        self._kind = None                # (raw, device) of the frames since the reset
+        self._token = object()
+        model._window_owner = self._token
+        with torch.cuda.device(model._dev):
+            model._call("gitcap_window_reset", batch, window)
+
+    def _check_live(self):
+        if self._m._window_owner is not self._token:
+            raise _lib.GitcapError("this CaptionStream was invalidated (another caption_stream() was opened, or the model was moved)")
+
+    def reset(self):
+        """Empty the window: the next caption needs `window` new frames."""
+        self._check_live()
+        with torch.cuda.device(self._m._dev):
+            self._m._call("gitcap_window_reset", self._sched.batch, self._sched.window)
+        self._sched.reset()
+        self._kept, self._kind = [], None
+
+    def _shape(self, frames):
+        """[B,H,W,3] uint8 / [B,3,S,S] fp32 (one frame per clip) or [B,n,...] -> (5-D view, raw)."""
+        if frames.dim() == 4:
+            frames = frames.unsqueeze(1)
+        return self._m._check_frames(frames)
+
+    def _push_lib(self, x, raw):
+        m = self._m
+        fr = m._to_device(x)
+        B, n = fr.shape[:2]
+        with torch.cuda.device(m._dev):
+            if raw:
+                m._call("gitcap_window_push_raw", ctypes.c_void_p(fr.data_ptr()), B, n, fr.shape[2], fr.shape[3], m._stream())
+            else:
+                m._call("gitcap_window_push", ctypes.c_void_p(fr.data_ptr()), B, n, m._stream())
+
+    def _repush(self):
+        """After a failed statistics exchange the library emptied the ring: push the frames it held again (one push)."""
+        self._push_lib(torch.stack(self._kept, 1), self._kind[0])
+
+    def push(self, frames: torch.Tensor):
+        """Append one frame per clip ([B,H,W,3] uint8 camera frames or [B,3,S,S] transformed frames) or n of them ([B,n,...]), on
+        the CPU or the device.  -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in
+        greedy_decode), or with beam_size the dict infer returns.  CPU frames in: the result is on the CPU and vouched for."""
+        self._check_live()
+        m = self._m
+        x, raw = self._shape(frames)
+        B, n = x.shape[:2]
+        self._sched.check(B, n)
+        kind = (raw, x.device)
+        if self._kind is not None and kind != self._kind:
+            raise ValueError(f"frames of one window must keep their kind and device ({self._kind} then {kind}); reset() first")
+        m._drain()
+        failed = False
+        try:
+            self._push_lib(x, raw)
+        except _lib.GitcapExchangeTimeout:
+            failed = True
+        self._kind = kind
+        self._kept = (self._kept + [x[:, i] for i in range(n)])[-self._sched.window:]
+        due = self._sched.push(B, n)
+        if failed:
+            self._repush()
+        if not due:
+            return None
+        on_cpu = x.device.type == "cpu"
+        try:
+            out = self._caption(on_cpu)
+            if on_cpu:
+                m.poll_errors()
+            return out
+        except _lib.GitcapExchangeTimeout:        # reported once: the handle has switched to the unfused launches
+            self._repush()
+            out = self._caption(on_cpu)
+            if on_cpu:
+                m.poll_errors()
+            return out
+
+    def _caption(self, on_cpu):
+        m = self._m
+        B = self._sched.batch
+        vis = None
+        if self._vis:
+            vis = torch.empty((B, self._sched.window * m.cfg.tokens_per_frame, m.cfg.enc_width), dtype=torch.float32, device=m._dev)
+        vp = ctypes.c_void_p(vis.data_ptr() if vis is not None else None)
+        with torch.cuda.device(m._dev):
+            if self._beam is None:
+                ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
+                steps = torch.zeros((1,), dtype=torch.int32, device=m._dev)
+                m._call("gitcap_window_greedy", self._max_len, self._mode, vp, ctypes.c_void_p(ids.data_ptr()),
+                        ctypes.c_void_p(steps.data_ptr()), m._stream())
+            else:
+                decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
+                logprobs = torch.empty((B,), dtype=torch.float32, device=m._dev)
+                m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, vp,
+                        ctypes.c_void_p(decoded.data_ptr()), ctypes.c_void_p(logprobs.data_ptr()), m._stream())
+        m._last_memory = None
+        mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
+        if self._beam is not None:
+            return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]), "logits_dict": [], "visual_features": mv(vis)}
+        if self._mode == STOP_ALL_SEP:
+            ids = ids[:, :1 + int(steps.item())]
+        return mv(ids)
+
+
 def _rebuild(cfg_dict, weights, kwargs):
     return GitCaptioner(GitCapConfig(**cfg_dict), weights, **kwargs)
 
@@ -299,6 +414,7 @@ class GitCaptioner(nn.Module):
         self._inflight = []                             # submissions whose wait has not been enqueued yet (<= 4)
         self._undelivered = set()                       # waited for, but a future has still to hand out (or re-run) its rows
         self._ring = None                               # _StagingRing, made when the first CPU tensor arrives
+        self._window_owner = None                       # token of the one live CaptionStream (the handle has one frame window)
         self._copy_stream = os.environ.get("GITCAP_COPY_STREAM", "caller")  # "caller" | "own" (A/B switch; see _StagingRing)
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
         self._create()
@@ -422,6 +538,7 @@ class GitCaptioner(nn.Module):
 
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, *args, **kwargs):
+        self._window_owner = None                       # a CaptionStream does not follow the model
         dev = kwargs.get("device", args[0] if args else None)
         if isinstance(dev, (str, torch.device)):
             dev = torch.device(dev)
@@ -952,6 +1069,32 @@ class GitCaptioner(nn.Module):
             entry["sub"] = sub
         self._inflight.append(sub)
         return InferFuture(self, sub, kw, src.device, save_logits)
+
+    def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
+                       beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
+                       visual_features: bool = False) -> CaptionStream:
+        """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
+        frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
+        window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
+        default (ids as greedy_decode(max_len, stop)); with beam_size the dict of infer's device search (max_len = its
+        max_steps; visual_features adds the window's features).  One live stream per model: opening another one, or .to() /
+        .cuda(), invalidates this one."""
+        window = int(window or max(1, self.cfg.num_frames))
+        if batch > self.max_batch or window > self.max_frames or (self.cfg.num_frames > 0 and window > self.cfg.num_frames):
+            raise ValueError(f"batch {batch} / window {window} exceed max_batch={self.max_batch} / max_frames={self.max_frames} "
+                             f"/ num_frames={self.cfg.num_frames}")
+        if max_len > self.max_text_len:
+            raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
+        mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        if beam_size is None:
+            if visual_features:
+                raise ValueError("visual_features come with the beam-search dict (beam_size=...)")
+        else:
+            per_node_beam_size = 2 if per_node_beam_size is None else per_node_beam_size
+            self._check_device_search(beam_size, per_node_beam_size, 1)
+            if beam_size > self.max_beams:
+                raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
+        return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip
