@@ -382,7 +382,7 @@ int gitcap_abi_version(void);
  * PAD tokens masked as keys; model.py:134-136, src/utils/masking.py) with cross-attention over
  * `memory` = one token per frame (model.py:124), embedding + positional table / sqrt(d_model)
  * (model.py:140-144, :320-340) and a Linear vocabulary head (model.py:152).  The TinyViT image encoder
- * (timm, model.py:38) is NOT behind this ABI: the caller supplies memory [B][mem_tokens][d_model].
+ * (timm, model.py:38) has its own handle below (gitcap_tinyvit_*); the decoder takes memory [B][mem_tokens][d_model].
  * Tensor names are the reference's state_dict keys (embed.weight, pos_enc.pe,
  * decoder.layers.{i}.self_attn.in_proj_weight, ..., linear.weight, linear.bias); same ownership, error
  * and threading rules as the gitcap_* entry points above.
@@ -420,6 +420,33 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
  * (device), k beams (rows b * k + i; B * k <= max_rows, k <= 16), no end-of-sequence handling (as the reference);
  * ids_out [B][max_len] = the best beam of every clip, CLS first (model.py:317). */
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with
+ * features_only=True (src/models/model.py:35-47, :108-126) -- conv stem, MBConv stage 0, three stages of
+ * PatchMerging + windowed-attention blocks -- on bf16 activations (csrc/tinyvit.hip; rounding points in DESIGN.md).
+ * Tensor names are the canonical checkpoint keys without the image_encoder.model. prefix (patch_embed.conv1.*,
+ * stages_{i}.blocks.{j}.attn.qkv.weight, ...), with every Conv2d + BatchNorm2d pair folded by the caller into
+ * <prefix>.weight / <prefix>.bias.  Same ownership, error and threading rules as the gitcap_student_* entry points.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct gitcap_tinyvit gitcap_tinyvit_t;
+struct gitcap_tinyvit_config {
+    int32_t img_size, embed_dims[4], depths[4], num_heads[4], window_sizes[4],
+            merge_strides[4] /* [0] unused */, max_frames;
+    float ln_eps;                                    /* 1e-5 */
+};
+/* refuses, before touching the device, head_dim != 32, widths not multiples of 32, stage maps not divisible by their
+ * windows, windows above 14 and merge strides other than 1 or 2 */
+int gitcap_tinyvit_create(const struct gitcap_tinyvit_config* cfg, int device, gitcap_tinyvit_t** out);
+void gitcap_tinyvit_destroy(gitcap_tinyvit_t* h);
+const char* gitcap_tinyvit_last_error(const gitcap_tinyvit_t* h);
+/* host fp32 data, logical shape (conv weights [Cout][Cin/groups][k][k]); GEMM weights are stored as bf16 */
+int gitcap_tinyvit_load_tensor(gitcap_tinyvit_t* h, const char* name, const float* data, const int64_t* shape, int rank);
+int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h);
+/* frames: device fp32 [n][3][img][img] (normalised, as model.py:117 receives them) -> memory device fp32 [n][C3] (the mean
+ * of the stage-3 map, model.py:124); fmaps: nullable array of 4 nullable device fp32 NCHW outputs [n][Ci][Hi][Wi].
+ * n <= max_frames. */
+int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float* memory, float* const* fmaps, void* stream);
 
 #ifdef __cplusplus
 }

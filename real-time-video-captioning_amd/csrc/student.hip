@@ -1,7 +1,7 @@
 // Student caption decoder (SURVEY.md par. 8 row f.2): the reference's StudentCandidateV1 decoder
 // (src/models/model.py:50-187 -- nn.TransformerDecoder, post-LN, ReLU, causal + key-padding mask,
 // cross-attention over one memory token per frame) with an exact KV cache, behind the C ABI declared in
-// include/gitcap.h ("student decoder" section).  The TinyViT image encoder is outside this path.
+// include/gitcap.h ("student decoder" section).  The TinyViT image encoder is in tinyvit.hip.
 //
 // Everything here is the decode-loop regime of the GIT text path: M = rows x T is a handful of rows, so
 // the dense layers are the weight-streaming skinny GEMMs (skinny.hip), the LayerNorms are fused with the

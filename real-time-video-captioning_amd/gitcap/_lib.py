@@ -8,6 +8,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
 
 from .config import CGitCapConfig
 from .student_config import CStudentConfig
+from .tinyvit_config import CTinyViTConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgitcap.so")
@@ -77,6 +78,13 @@ SYMBOLS = {
     "gitcap_student_forward_decoder": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gitcap_student_greedy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_student_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # student image encoder (gitcap/tinyvit.py)
+    "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
+    "gitcap_tinyvit_destroy": (None, [c_void_p]),
+    "gitcap_tinyvit_last_error": (c_char_p, [c_void_p]),
+    "gitcap_tinyvit_load_tensor": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
+    "gitcap_tinyvit_finalize": (c_int, [c_void_p]),
+    "gitcap_tinyvit_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,10 +6,12 @@ Same constructor keywords (model.py:55-57), ``forward`` / ``forward_image_enc`` 
 ``forward_decoder`` / ``greedy_decode`` with the reference's argument meaning, ``state_dict`` keys of
 the reference.  The decoder (embedding, positional table, 2 x (self-attention, cross-attention over the
 frame tokens, FFN), vocabulary head, greedy loop with the all-rows-SEP stop rule) runs in HIP kernels
-with an exact KV cache.  The TinyViT image encoder is ``timm`` code that is absent from this image: it
-is NOT rebuilt here.  A caller who has it passes it as ``image_encoder`` (any module mapping
-``[B*F,3,H,W]`` to the list of feature maps, model.py:117); ``greedy_decode`` also accepts the frame
-features ``memory [B, F, d_model]`` directly.  There is no CPU or PyTorch fallback for the decoder.
+with an exact KV cache.  The TinyViT image encoder runs on the HIP kernels of csrc/tinyvit.hip
+(``gitcap.tinyvit.TinyViTEncoder``): ``image_encoder="native"`` builds it from ``image_enc_name``, or the caller
+passes a ``TinyViTEncoder``; then frames ``[B,F,3,H,W]`` go to a caption on the device, the encoder's memory never
+leaving it.  Any other module mapping ``[B*F,3,H,W]`` to the list of feature maps (model.py:117) is still accepted as
+``image_encoder``; ``greedy_decode`` also accepts the frame features ``memory [B, F, d_model]`` directly.  There is no
+CPU or PyTorch fallback for the decoder or the native encoder.
 """
 from __future__ import annotations
 
@@ -22,19 +24,22 @@ from torch import nn
 
 from . import _lib
 from .student_config import (CStudentConfig, StudentConfig, check_student_shapes, positional_table, student_shapes)
+from .tinyvit import TinyViTEncoder, tinyvit_config
+
+ENC_PREFIX = "image_encoder.model."
 
 STOP_NEVER, STOP_ALL_SEP = 0, 1
 
 
-def _rebuild_student(cfg_dict, weights, kwargs):
-    return StudentCaptioner(cfg=StudentConfig(**cfg_dict), weights=weights, **kwargs)
+def _rebuild_student(cfg_dict, weights, kwargs, encoder=None):
+    return StudentCaptioner(cfg=StudentConfig(**cfg_dict), weights=weights, image_encoder=encoder, **kwargs)
 
 
 class StudentCaptioner(nn.Module):
     def __init__(self, image_enc_name: Optional[str] = None, d_model: int = 576, n_head: int = 8, d_ffn: int = 1024,
                  dropout: float = 0.0, num_decoder_layers: int = 2, vocab_length: int = 30522, cls_token_id: int = 101,
                  sep_token_id: int = 102, *, cfg: Optional[StudentConfig] = None,
-                 weights: Optional[Mapping[str, np.ndarray]] = None, image_encoder: Optional[nn.Module] = None,
+                 weights: Optional[Mapping[str, np.ndarray]] = None, image_encoder=None,
                  device: str | torch.device = "cuda:0", max_batch: int = 16, max_text_len: int = 32,
                  mem_tokens: int = 6, stop: str = "all_sep"):
         super().__init__()
@@ -44,12 +49,19 @@ class StudentCaptioner(nn.Module):
                                 mem_tokens=mem_tokens)
         cfg.validate()
         self.cfg = cfg
-        self.image_enc_name = image_enc_name            # kept for callers that log it; no encoder is built from it
+        self.image_enc_name = image_enc_name
+        self._kw = dict(max_batch=int(max_batch), max_text_len=int(max_text_len), stop=stop)
+        if isinstance(image_encoder, str):
+            if image_encoder != "native":
+                raise ValueError(f"image_encoder={image_encoder!r}: only 'native' (or a module) is accepted")
+            image_encoder = TinyViTEncoder(tinyvit_config(image_enc_name or "tiny_vit_21m_224"), device=device,
+                                           max_frames=int(max_batch) * cfg.mem_tokens)
+        if isinstance(image_encoder, TinyViTEncoder) and image_encoder.out_dim != cfg.d_model:
+            raise ValueError(f"the TinyViT encoder's last width {image_encoder.out_dim} != d_model {cfg.d_model}")
         self.image_encoder = image_encoder
         self.cls_token_id, self.sep_token_id = cfg.cls_token_id, cfg.sep_token_id
         self.n_head = cfg.n_head
         self.stop = stop
-        self._kw = dict(max_batch=int(max_batch), max_text_len=int(max_text_len), stop=stop)
         self._dev = torch.device(device)
         self._handle = None
         self._weights: Optional[Dict[str, np.ndarray]] = None
@@ -110,13 +122,27 @@ class StudentCaptioner(nn.Module):
                 self.image_encoder.to(self._dev)
         return self
 
+    def _native(self) -> bool:
+        return isinstance(self.image_encoder, TinyViTEncoder)
+
     def state_dict(self, *a, **k):
-        return {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
+        sd = {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
+        if self._native():
+            sd.update({ENC_PREFIX + n: v for n, v in self.image_encoder.state_dict().items()})
+        return sd
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Takes the reference's checkpoint keys as they are (src/inference.py:38).  Keys outside the decoder
         (image_encoder.*, projectors.*, upsample, project, project_decoder, the unused template
-        ``decoder_layer.*``) are ignored; a missing ``pos_enc.pe`` buffer is rebuilt from model.py:324-335."""
+        ``decoder_layer.*``) are ignored; a missing ``pos_enc.pe`` buffer is rebuilt from model.py:324-335.
+        With a native TinyViT encoder the ``image_encoder.model.*`` keys load into it: a missing encoder key is an
+        error, unless the checkpoint has no encoder key at all and the encoder already holds weights."""
+        if self._native():
+            enc = {k[len(ENC_PREFIX):]: v for k, v in state_dict.items() if k.startswith(ENC_PREFIX)}
+            if enc or not self.image_encoder.loaded:
+                if not enc:
+                    raise KeyError(f"missing TinyViT encoder weights ({ENC_PREFIX}*) for image_encoder='native'")
+                self.image_encoder.load_state_dict(enc)
         w = {}
         for name, shape in student_shapes(self.cfg).items():
             if name not in state_dict:
@@ -140,12 +166,13 @@ class StudentCaptioner(nn.Module):
             self._call("gitcap_student_finalize")
 
     def __reduce__(self):
-        if self.image_encoder is not None:
-            raise TypeError("pickle the image encoder separately; StudentCaptioner pickles its decoder only")
+        if self.image_encoder is not None and not self._native():
+            raise TypeError("pickle the image encoder separately; StudentCaptioner pickles its decoder and a native encoder only")
         from dataclasses import asdict
         kw = dict(self._kw)
         kw["device"] = str(self._dev)
-        return _rebuild_student, (asdict(self.cfg), self._weights, kw)
+        kw["image_enc_name"] = self.image_enc_name
+        return _rebuild_student, (asdict(self.cfg), self._weights, kw, self.image_encoder)
 
     # ------------------------------------------------------------------ reference API
     def _memory(self, memory: torch.Tensor) -> torch.Tensor:
@@ -155,12 +182,20 @@ class StudentCaptioner(nn.Module):
             raise ValueError(f"batch {memory.shape[0]} outside 1..max_batch={self.max_batch}")
         return memory.to(device=self._dev, dtype=torch.float32).contiguous()
 
+    def _frames_memory(self, src: torch.Tensor) -> torch.Tensor:
+        """frames [B,F,C,H,W] -> memory [B,F,D]; the native encoder writes no feature maps and does not sync."""
+        if self._native():
+            return self.image_encoder.memory(src)
+        return self.forward_image_enc(src)[1]
+
     @torch.no_grad()
     def forward_image_enc(self, x: torch.Tensor):
-        """model.py:108-126: frames [B,F,C,H,W] -> (feature maps, memory [B,F,De]) through the caller's encoder."""
+        """model.py:108-126: frames [B,F,C,H,W] -> (feature maps, memory [B,F,De]) through the image encoder."""
+        if self._native():
+            return self.image_encoder.forward_with_memory(x)
         if self.image_encoder is None:
-            raise _lib.GitcapError("StudentCaptioner was built without an image_encoder: the TinyViT encoder (timm) is not "
-                                   "part of libgitcap; pass image_encoder=... or call the decoder with memory [B,F,d_model]")
+            raise _lib.GitcapError("StudentCaptioner was built without an image_encoder: pass image_encoder='native' (the "
+                                   "TinyViT encoder of libgitcap) or a module, or call the decoder with memory [B,F,d_model]")
         s = x.shape
         fmaps = self.image_encoder(x.to(self._dev).view(s[0] * s[1], *s[2:]))
         memory = torch.mean(fmaps[-1], dim=[2, 3]).view(s[0], s[1], -1)
@@ -190,10 +225,11 @@ class StudentCaptioner(nn.Module):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None) -> torch.Tensor:
-        """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``) or memory [B,F,D].
+        """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
+        device) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device."""
         out_dev = src.device
-        memory = self.forward_image_enc(src)[1] if src.dim() == 5 else src
+        memory = self._frames_memory(src) if src.dim() == 5 else src
         mem = self._memory(memory)
         if max_len < 1 or max_len > self.max_text_len:
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
@@ -217,7 +253,7 @@ class StudentCaptioner(nn.Module):
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams."""
         out_dev = src.device
-        memory = self.forward_image_enc(src)[1] if src.dim() == 5 else src
+        memory = self._frames_memory(src) if src.dim() == 5 else src
         mem = self._memory(memory)
         B = mem.shape[0]
         if B * k > self.max_batch:
@@ -237,7 +273,7 @@ class StudentCaptioner(nn.Module):
         """The same search driven from the host the way the reference writes it (every step recomputes the whole prefix
         through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests."""
         out_dev = src.device
-        memory = self.forward_image_enc(src)[1] if src.dim() == 5 else src
+        memory = self._frames_memory(src) if src.dim() == 5 else src
         mem = self._memory(memory)
         B = mem.shape[0]
         if B * k > self.max_batch:

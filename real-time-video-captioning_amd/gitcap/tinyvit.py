@@ -1,0 +1,186 @@
+"""``TinyViTEncoder``: the student captioner's TinyViT image encoder (timm ``TinyVit``, ``features_only=True``,
+the reference's src/models/model.py:35-47, :108-126) on the HIP kernels of csrc/tinyvit.hip through the
+``gitcap_tinyvit_*`` entry points (include/gitcap.h).
+
+``forward(x [N,3,H,W])`` returns the four feature maps (fp32 NCHW, as the reference's ``image_enc_fmaps``);
+``memory(x [B,F,3,H,W])`` returns the mean of the stage-3 map, ``[B,F,C3]`` fp32 (model.py:124), without writing the
+feature maps.  Everything runs on the caller's current stream with no host synchronisation.  There is no CPU path."""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import asdict
+from typing import Dict, Mapping, Optional
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from .tinyvit_config import (CTinyViTConfig, TinyViTConfig, canonical_key, check_tinyvit_shapes, fold_convnorm,  # noqa: F401
+                             folded_tensors, normalise_keys, tinyvit_config, tinyvit_shapes, tinyvit_synthetic_weights,
+                             tinyvit_tiny)
+
+
+def _rebuild_tinyvit(cfg_dict, weights, kwargs):
+    cfg_dict = dict(cfg_dict)
+    for k in ("embed_dims", "depths", "num_heads", "window_sizes", "merge_strides"):
+        cfg_dict[k] = tuple(cfg_dict[k])
+    return TinyViTEncoder(TinyViTConfig(**cfg_dict), weights=weights, **kwargs)
+
+
+class TinyViTEncoder(nn.Module):
+    def __init__(self, cfg: TinyViTConfig, weights: Optional[Mapping[str, object]] = None,
+                 device: str | torch.device = "cuda:0", max_frames: int = 96):
+        super().__init__()
+        cfg.validate()
+        self.cfg = cfg
+        self.max_frames = int(max_frames)
+        self._dev = torch.device(device)
+        self._handle = None
+        self._weights: Optional[Dict[str, np.ndarray]] = None
+        self._lib = _lib.load()
+        self._create()
+        if weights is not None:
+            self.load_state_dict(weights)
+
+    # ------------------------------------------------------------------ handle management
+    def _create(self):
+        if self._dev.type != "cuda":
+            raise _lib.GitcapError("gitcap runs on an AMD GPU only (no CPU path); got device %s" % self._dev)
+        if not torch.cuda.is_available():
+            raise _lib.GitcapError("no HIP device visible: gitcap has no CPU fallback")
+        idx = self._dev.index if self._dev.index is not None else torch.cuda.current_device()
+        self._dev = torch.device("cuda", idx)
+        cc = CTinyViTConfig.from_config(self.cfg, self.max_frames)
+        h = ctypes.c_void_p()
+        rc = self._lib.gitcap_tinyvit_create(ctypes.byref(cc), idx, ctypes.byref(h))
+        self._check(None, rc, "gitcap_tinyvit_create")
+        self._handle = h
+
+    def _check(self, handle, rc, what):
+        if rc != 0:
+            msg = self._lib.gitcap_tinyvit_last_error(handle)
+            raise _lib.GitcapError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
+
+    def _call(self, name, *args):
+        self._check(self._handle, getattr(self._lib, name)(self._handle, *args), name)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None):
+                self._lib.gitcap_tinyvit_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    @property
+    def device(self) -> torch.device:
+        return self._dev
+
+    @property
+    def out_dim(self) -> int:
+        return self.cfg.embed_dims[3]
+
+    def to(self, *args, **kwargs):
+        dev = kwargs.get("device", args[0] if args else None)
+        if isinstance(dev, (str, torch.device)):
+            dev = torch.device(dev)
+            if dev.type != "cuda":
+                raise _lib.GitcapError("gitcap has no CPU path; .to(%s) refused" % dev)
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            if idx != self._dev.index:
+                self._lib.gitcap_tinyvit_destroy(self._handle)
+                self._handle = None
+                self._dev = torch.device("cuda", idx)
+                self._create()
+                if self._weights is not None:
+                    self._upload(self._weights)
+        return self
+
+    def cpu(self):
+        raise _lib.GitcapError("gitcap has no CPU path; .cpu() refused")
+
+    # ------------------------------------------------------------------ weights
+    @property
+    def loaded(self) -> bool:
+        return self._weights is not None
+
+    def state_dict(self, *a, **k):
+        """Canonical keys (``stages_i`` form, no prefix), BatchNorms unfolded, as loaded."""
+        return {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """Takes the keys with the prefix ``image_encoder.model.``, ``model.`` or none, and ``stages_i`` or ``stages.i``;
+        ``num_batches_tracked`` and ``attention_bias_idxs`` are ignored (the index table is rebuilt).  Every key of
+        ``tinyvit_shapes`` must be present."""
+        state = normalise_keys(state_dict)
+        w = {}
+        for name in tinyvit_shapes(self.cfg):
+            if name not in state:
+                raise KeyError(f"missing TinyViT weight {name}")
+            v = state[name]
+            w[name] = np.ascontiguousarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+        if strict:
+            extra = sorted(set(state) - set(w))
+            if extra:
+                raise KeyError(f"unexpected TinyViT keys: {extra[:5]}")
+        check_tinyvit_shapes(self.cfg, w)
+        self._upload(w)
+        self._weights = w
+        return self
+
+    def _upload(self, w):
+        with torch.cuda.device(self._dev):
+            for name, arr in folded_tensors(self.cfg, w).items():
+                arr = np.ascontiguousarray(arr, dtype=np.float32)
+                shape = (ctypes.c_int64 * arr.ndim)(*arr.shape)
+                self._call("gitcap_tinyvit_load_tensor", name.encode(), arr.ctypes.data_as(ctypes.c_void_p), shape, arr.ndim)
+            self._call("gitcap_tinyvit_finalize")
+
+    def __reduce__(self):
+        return _rebuild_tinyvit, (asdict(self.cfg), self._weights, dict(device=str(self._dev), max_frames=self.max_frames))
+
+    # ------------------------------------------------------------------ encode
+    def _frames(self, x: torch.Tensor) -> torch.Tensor:
+        s = self.cfg.img_size
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != s or x.shape[3] != s:
+            raise ValueError(f"expected frames [N,3,{s},{s}], got {tuple(x.shape)}")
+        if x.shape[0] < 1 or x.shape[0] > self.max_frames:
+            raise ValueError(f"{x.shape[0]} frames outside 1..max_frames={self.max_frames}")
+        return x.to(device=self._dev, dtype=torch.float32).contiguous()
+
+    def _encode(self, x: torch.Tensor, want_fmaps: bool):
+        n = x.shape[0]
+        mem = torch.empty((n, self.out_dim), dtype=torch.float32, device=self._dev)
+        fmaps = []
+        arr = None
+        if want_fmaps:
+            for C, m in zip(self.cfg.embed_dims, self.cfg.stage_maps()):
+                fmaps.append(torch.empty((n, C, m, m), dtype=torch.float32, device=self._dev))
+            ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in fmaps])
+            arr = ctypes.cast(ptrs, ctypes.c_void_p)
+        with torch.cuda.device(self._dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+            self._call("gitcap_tinyvit_encode", ctypes.c_void_p(x.data_ptr()), n, ctypes.c_void_p(mem.data_ptr()),
+                       arr, stream)
+        return fmaps, mem
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor):
+        """x [N,3,H,W] (normalised) -> list of the four stage feature maps, fp32 NCHW on the device."""
+        return self._encode(self._frames(x), True)[0]
+
+    @torch.no_grad()
+    def forward_with_memory(self, x: torch.Tensor):
+        """x [B,F,3,H,W] -> (four feature maps [B*F,Ci,Hi,Wi], memory [B,F,C3]) from one encode."""
+        B, F = x.shape[:2]
+        fmaps, mem = self._encode(self._frames(x.reshape(B * F, *x.shape[2:])), True)
+        return fmaps, mem.view(B, F, -1)
+
+    @torch.no_grad()
+    def memory(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B,F,3,H,W] -> mean of the stage-3 map [B,F,C3] fp32 (model.py:124); no feature maps are written."""
+        if x.dim() != 5:
+            raise ValueError(f"expected frames [B,F,3,H,W], got {tuple(x.shape)}")
+        B, F = x.shape[:2]
+        return self._encode(self._frames(x.reshape(B * F, *x.shape[2:])), False)[1].view(B, F, -1)
