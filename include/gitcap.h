@@ -421,6 +421,33 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
  * ids_out [B][max_len] = the best beam of every clip, CLS first (model.py:317). */
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream);
 
+/* Memory-token window: the live loop of the reference (src/real_time_inference.py:30-57 collects six transformed frames, calls
+ * greedy_decode on all six, clears the list) as a sliding window that computes everything belonging to a frame once.  A memory
+ * token is one frame's own stage-3 mean (model.py:124) and its cross-attention K | V rows in every decoder layer are
+ * W_kv . token + b with no positional term, so a push computes them for the n new tokens only -- set_memory's GEMM on B * n rows
+ * instead of B * mem_tokens -- and keeps them in a ring of mem_tokens slots per clip; a window call copies the ring's rows, oldest
+ * first, to where set_memory would have written them and runs the token loop of the full call (the same captured graph).
+ * Contract: gitcap_student_window_greedy / _beam_search return bit for bit what gitcap_student_greedy / _beam_search return on the
+ * window's mem_tokens tokens in push order (a K | V row has the same bits whichever launch computed it: one MFMA chain per row).
+ *   reset  B clips (<= max_rows) advance in lockstep; allocates the ring (bf16 [num_layers][B][mem_tokens][2 d_model]) and a
+ *          staging buffer of B * mem_tokens rows, empties the window; B = 0 releases both (so does destroy).  A handle that never
+ *          resets a window allocates nothing.  Changing B waits for the device before the old ring is freed.
+ *   push   memory: device fp32 [B][n][d_model], 1 <= n <= mem_tokens, token j older than token j + 1 -- the `memory` output of
+ *          gitcap_tinyvit_encode(_raw).  Writes the ring and the staging buffer only: not the memory K | V of the decoder, not the
+ *          self-attention cache, not the current row count, so a gitcap_student_forward_decoder after a push still sees the
+ *          previous memory.
+ *   window calls  need mem_tokens tokens pushed since the reset; leave the handle as the full call would (a forward_decoder
+ *          after one sees the window; for beam search with B * k rows).  Arguments as the full calls without memory / B.
+ * Pushes and window calls may be issued on different streams: two events order a push behind the last window call's copy and
+ * the last push, and a window call behind the last push; there is no device synchronisation on the data path.
+ * Errors: GITCAP_ERR_ARG for a null handle or pointer, B different from the reset's, n outside [1, mem_tokens], B > max_rows at
+ * reset, B * k > max_rows, and the length / stop-rule checks of the full calls; GITCAP_ERR_STATE for a push before any reset, a
+ * window call before mem_tokens tokens have been pushed since the reset, and weights not finalized. */
+int gitcap_student_window_reset(gitcap_student_t* h, int B);
+int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream);
+int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream);
+int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with
  * features_only=True (src/models/model.py:35-47, :108-126) -- conv stem, MBConv stage 0, three stages of
@@ -447,6 +474,15 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h);
  * of the stage-3 map, model.py:124); fmaps: nullable array of 4 nullable device fp32 NCHW outputs [n][Ci][Hi][Wi].
  * n <= max_frames. */
 int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float* memory, float* const* fmaps, void* stream);
+/* The same from camera frames: frames_hwc_bgr device uint8 [n][H][W][3] (OpenCV layout, src/real_time_inference.py:39), the input
+ * of gitcap_preprocess.  Replaces the reference's per-frame host transform (real_time_inference.py:16-28: ToTensor, bicubic
+ * Resize of the shorter side to img_size, CenterCrop(img_size), BGR -> RGB, CLIP Normalize) AND the gather of the first stem
+ * convolution: one kernel writes the convolution's bf16 im2col rows straight from the uint8 frames, no fp32 frame tensor exists.
+ * Contract: memory and all four fmaps equal, bit for bit, gitcap_preprocess(crop = img_size) followed by gitcap_tinyvit_encode.
+ * GITCAP_ERR_ARG: null handle / frames / memory, n < 1, n > max_frames, H or W < 1 or a size whose resized frame is smaller
+ * than img_size.  No workspace beyond gitcap_tinyvit_encode's. */
+int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr, int n, int H, int W, float* memory,
+                              float* const* fmaps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,9 @@ hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_score
 hipError_t launch_preprocess(const unsigned char* in, float* out, int nf, int H, int W, int crop, hipStream_t s);
 // the same transform fused with the patch gather: -> bf16 patch rows [nf*G*G][Kp] (layout of launch_im2col)
 hipError_t launch_preprocess_patches(const unsigned char* in, bf16_t* patches, int nf, int H, int W, int crop, int p, int Kp, hipStream_t s);
+// the same transform fused with the gather of a 3x3 stride-2 pad-1 convolution over the cropped frame (TinyViT's first stem conv):
+// -> bf16 im2col rows [nf*(crop/2)^2][32], k = ci*9 + ky*3 + kx, every column written (zero at outside taps and k >= 27); crop even
+hipError_t launch_preprocess_stem(const unsigned char* in, bf16_t* col, int nf, int H, int W, int crop, hipStream_t s);
 // device-resident beam search state + one bookkeeping step per decoder step (rowops.hip)
 struct BeamBuffers {
     int64_t *ids0, *ids1, *words, *hyp_ids;

@@ -138,6 +138,33 @@ __global__ void student_beam_finish_kernel(const int64_t* __restrict__ ids, int6
     for (int i = threadIdx.x; i < max_len; i += 64) out[(size_t)b * max_len + i] = ids[(size_t)b * k * ld + i];
 }
 
+// ---- memory-token window (gitcap_student_window_*) -------------------------------------------------------------------------
+// push: fp32 tokens [B][n][D] -> bf16 staging rows as two contiguous segments, the n1 tokens per clip that fill the ring up to its
+// end ([B][n1][D]) and the n - n1 that wrap to slot 0 ([B][n - n1][D]): each segment is the X of one K|V GEMM whose output rows
+// are ring slots (sk_full's T / row_stride / row_off).  f2bf as launch_cast_bf16: the bf16 rows set_memory's GEMM reads.
+__global__ __launch_bounds__(256) void student_window_stage_kernel(const float* __restrict__ mem, bf16_t* __restrict__ stage, int B, int n,
+                                                                   int n1, int D4) {
+    const int64_t total = (int64_t)B * n * D4;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int c = (int)(e % D4), j = (int)((e / D4) % n), b = (int)(e / ((int64_t)D4 * n));
+        const int64_t row = j < n1 ? (int64_t)b * n1 + j : (int64_t)B * n1 + (int64_t)b * (n - n1) + (j - n1);
+        const f32x4 v = ((const f32x4*)mem)[e];
+        uint2 o;
+        o.x = pack_bf2(v[0], v[1]);
+        o.y = pack_bf2(v[2], v[3]);
+        ((uint2*)stage)[row * D4 + c] = o;
+    }
+}
+// window call: K|V rows of the ring [L][B][F slots][2D], oldest slot = head, -> memkv [L][R][F][2D] in window order; decoder row r
+// takes clip r / k (k beams per clip share its tokens).  blockIdx.x = (r, f), blockIdx.y = layer; n8 = 2D / 8 16-byte pieces per row.
+__global__ __launch_bounds__(64) void student_window_gather_kernel(const bf16_t* __restrict__ ring, bf16_t* __restrict__ memkv, int F, int head,
+                                                                   int k, int n8, size_t ring_layer, size_t mem_layer) {
+    const int r = blockIdx.x / F, f = blockIdx.x % F, l = blockIdx.y;
+    const uint4* src = (const uint4*)(ring + l * ring_layer) + ((size_t)(r / k) * F + (head + f) % F) * n8;
+    uint4* dst = (uint4*)(memkv + l * mem_layer) + ((size_t)r * F + f) * n8;
+    for (int i = threadIdx.x; i < n8; i += 64) dst[i] = src[i];
+}
+
 struct gitcap_student {
     gitcap_student_config c;
     int device = 0;
@@ -166,6 +193,14 @@ struct gitcap_student {
         int64_t *ids0 = nullptr, *ids1 = nullptr;
         bf16_t* kvs2 = nullptr; char* topk_scratch = nullptr;
     } bw;
+    // memory-token window (gitcap_student_window_*), allocated by window_reset: ring = the cross-attention K|V rows of the last F
+    // tokens of win_B clips, bf16 [L][win_B][F slots][2D]; win_head = the slot the next token goes to (the oldest token once the
+    // ring is full); win_count = tokens per clip pushed since the reset, capped at F.  A push orders itself behind the last window
+    // call's gather (win_ev_read) and the last push (win_ev_ring: they share the staging rows); a window call behind the last push.
+    bf16_t *win_ring = nullptr, *win_stage = nullptr;
+    int win_B = 0, win_head = 0, win_count = 0;
+    hipEvent_t win_ev_ring = nullptr, win_ev_read = nullptr;
+    bool win_ring_rec = false, win_read_rec = false;
     // resolved weights
     const float *embed = nullptr, *pe = nullptr, *head_b = nullptr;
     const bf16_t* head_w = nullptr;
@@ -382,6 +417,10 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->win_ring) (void)hipFree(h->win_ring);
+    if (h->win_stage) (void)hipFree(h->win_stage);
+    if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
+    if (h->win_ev_read) (void)hipEventDestroy(h->win_ev_read);
     delete h;
 }
 
@@ -470,16 +509,21 @@ int gitcap_student_forward_decoder(gitcap_student_t* h, const int64_t* ids, int 
     return text_forward(h, ids, ld_ids, B, 0, T, logits, nullptr, 0, nullptr, 0, (hipStream_t)stream);
 }
 
-int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
-                          int32_t* steps_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
-    if (!ids_out || max_len <= 0) return sfail(h, GITCAP_ERR_ARG, "student_greedy: bad arguments");
-    if (max_len + 1 > h->Tmax) return sfail(h, GITCAP_ERR_ARG, "student_greedy: max_len exceeds max_text_len");
-    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return sfail(h, GITCAP_ERR_ARG, "student_greedy: unknown stop rule");
-    S_GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = set_memory(h, memory, B, s);           // reads the caller's buffer: outside the graph
-    if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// argument checks shared by gitcap_student_greedy and gitcap_student_window_greedy
+int greedy_check(gitcap_student* h, const char* who, int max_len, int stop, const int64_t* ids_out) {
+    if (!ids_out || max_len <= 0) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
+    if (max_len + 1 > h->Tmax) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len");
+    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": unknown stop rule");
+    return 0;
+}
+
+// the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
+int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
+    int rc;
     const int ld = max_len + 1;
     // The token loop is launch-latency bound (26 kernels per token): it is captured once per (B, max_len, stop)
     // and replayed.  GITCAP_STUDENT_GRAPH=0 launches it kernel by kernel (same kernels, same results).
@@ -520,41 +564,40 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
     return 0;
 }
 
-// StudentCandidateV1.beam_search (model.py:189-318) on the device with the exact KV cache: k beams per clip as rows
-// b * k + i, no end-of-sequence handling (as the reference), no host round trip.  The reference lets every beam propose its
-// top k and keeps the k best of the k * k candidates; the k best of ALL beams x vocabulary candidates are the same set (a
-// candidate among the global k best is among its own beam's k best), which is what beam_topk ranks (log_softmax + beam
-// score, best first, ties to the smaller beam-major index).  Before the first step only beam 0 is live (score 0, the others
-// -1e9), so the k rows start as the top k of the single prefix [CLS] (model.py:221-227).  After every step the self-attention
-// K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
-int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
-    if (!memory || !ids_out || B <= 0 || k <= 0 || max_len < 2) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
-    if (k > 16) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: at most 16 beams");
-    if ((int64_t)B * k > h->R) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: B * k exceeds max_rows");
-    if (max_len > h->Tmax) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: max_len exceeds max_text_len + 1");
-    S_GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
+// argument checks shared by gitcap_student_beam_search and gitcap_student_window_beam_search
+int beam_check(gitcap_student* h, const char* who, int B, int k, int max_len, const int64_t* ids_out) {
+    if (!ids_out || B <= 0 || k <= 0 || max_len < 2) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
+    if (k > 16) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": at most 16 beams");
+    if ((int64_t)B * k > h->R) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": B * k exceeds max_rows");
+    if (max_len > h->Tmax) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len + 1");
+    return 0;
+}
+
+int beam_workspace(gitcap_student* h) {
+    gitcap_student::BeamWs& w = h->bw;
+    if (w.memrep) return 0;
+    const size_t R = h->R, ld = (size_t)h->Tmax + 1;
+    const int D = h->D, V = h->V;
+    int rc = 0;
+    rc = rc ? rc : s_alloc(h, &w.memrep, R * h->F * D);
+    rc = rc ? rc : s_alloc(h, &w.scores, R);
+    rc = rc ? rc : s_alloc(h, &w.cand_scores, R);
+    rc = rc ? rc : s_alloc(h, &w.cand_idx, R);
+    rc = rc ? rc : s_alloc(h, &w.src_rows, R);
+    rc = rc ? rc : s_alloc(h, &w.ids0, R * ld);
+    rc = rc ? rc : s_alloc(h, &w.ids1, R * ld);
+    rc = rc ? rc : s_alloc(h, &w.logits, R * (size_t)V);
+    rc = rc ? rc : s_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
+    rc = rc ? rc : s_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
+    if (rc) w = gitcap_student::BeamWs{};
+    return rc;
+}
+
+// the token loop of beam_search against the memory K|V of B * k rows in h->memkv (set_memory of the repeated rows, or the window's gather)
+int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s) {
     const int rows = B * k, D = h->D, V = h->V, ld = h->Tmax + 1;
     int rc = 0;
     gitcap_student::BeamWs& w = h->bw;
-    if (!w.memrep) {
-        const size_t R = h->R;
-        rc = rc ? rc : s_alloc(h, &w.memrep, R * h->F * D);
-        rc = rc ? rc : s_alloc(h, &w.scores, R);
-        rc = rc ? rc : s_alloc(h, &w.cand_scores, R);
-        rc = rc ? rc : s_alloc(h, &w.cand_idx, R);
-        rc = rc ? rc : s_alloc(h, &w.src_rows, R);
-        rc = rc ? rc : s_alloc(h, &w.ids0, R * (size_t)ld);
-        rc = rc ? rc : s_alloc(h, &w.ids1, R * (size_t)ld);
-        rc = rc ? rc : s_alloc(h, &w.logits, R * (size_t)V);
-        rc = rc ? rc : s_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
-        rc = rc ? rc : s_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
-        if (rc) { w = gitcap_student::BeamWs{}; return rc; }
-    }
-    hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, w.memrep, k, h->F * D / 4);
-    S_HIP_OK(h, hipGetLastError());
-    if ((rc = set_memory(h, w.memrep, rows, s))) return rc;
     S_HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
     hipLaunchKernelGGL(beam_scores_init_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, w.scores, rows, k);
     S_HIP_OK(h, hipGetLastError());
@@ -581,6 +624,153 @@ int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, 
     hipLaunchKernelGGL(student_beam_finish_kernel, dim3(B), dim3(64), 0, s, cur, ids_out, k, ld, max_len);
     S_HIP_OK(h, hipGetLastError());
     return 0;
+}
+
+// ---- memory-token window -----------------------------------------------------------------------------------------------------
+// A memory token is one frame's own stage-3 mean and its cross-attention K|V rows are W_kv . token + b, no positional term, from a
+// GEMM whose output rows do not depend on each other: everything per frame is computed once, at the push, and a caption of the
+// window only orders the F rows (student_window_gather_kernel) in front of the token loop of the full call.
+int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s) {
+    if (!h->win_ring || h->win_count < h->F)
+        return sfail(h, GITCAP_ERR_STATE, std::string(who) + ": fewer than mem_tokens tokens pushed since the reset");
+    const int rows = h->win_B * k, D = h->D;
+    S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    h->have_memory = false;
+    hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * h->F, h->L), dim3(64), 0, s, h->win_ring, h->memkv, h->F, h->win_head, k,
+                       2 * D / 8, (size_t)h->win_B * h->F * 2 * D, (size_t)h->R * h->F * 2 * D);
+    S_HIP_OK(h, hipGetLastError());
+    S_HIP_OK(h, hipEventRecord(h->win_ev_read, s));
+    h->win_read_rec = true;
+    h->cur_B = rows;
+    h->have_memory = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
+                          int32_t* steps_out, void* stream) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
+    if (int bad = greedy_check(h, "student_greedy", max_len, stop, ids_out)) return bad;
+    S_GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = set_memory(h, memory, B, s);           // reads the caller's buffer: outside the graph
+    if (rc) return rc;
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s);
+}
+
+// StudentCandidateV1.beam_search (model.py:189-318) on the device with the exact KV cache: k beams per clip as rows
+// b * k + i, no end-of-sequence handling (as the reference), no host round trip.  The reference lets every beam propose its
+// top k and keeps the k best of the k * k candidates; the k best of ALL beams x vocabulary candidates are the same set (a
+// candidate among the global k best is among its own beam's k best), which is what beam_topk ranks (log_softmax + beam
+// score, best first, ties to the smaller beam-major index).  Before the first step only beam 0 is live (score 0, the others
+// -1e9), so the k rows start as the top k of the single prefix [CLS] (model.py:221-227).  After every step the self-attention
+// K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
+int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
+    if (!memory) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
+    if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
+    S_GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = beam_workspace(h);
+    if (rc) return rc;
+    const int rows = B * k;
+    hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
+    S_HIP_OK(h, hipGetLastError());
+    if ((rc = set_memory(h, h->bw.memrep, rows, s))) return rc;
+    return beam_loop(h, B, k, max_len, ids_out, s);
+}
+
+int gitcap_student_window_reset(gitcap_student_t* h, int B) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_reset: null handle");
+    if (B < 0 || B > h->R) return sfail(h, GITCAP_ERR_ARG, "student_window_reset: B outside 0..max_rows");
+    S_GUARD(h);
+    if (h->win_ring && B != h->win_B) {
+        S_HIP_OK(h, hipDeviceSynchronize());          // pushes or window calls in flight may still use the ring
+        (void)hipFree(h->win_ring); (void)hipFree(h->win_stage);
+        h->win_ring = h->win_stage = nullptr;
+    }
+    h->win_B = h->win_head = h->win_count = 0;
+    if (B == 0) return 0;
+    if (!h->win_ev_ring) {
+        S_HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
+        S_HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
+    }
+    if (!h->win_ring) {
+        const size_t rows = (size_t)B * h->F;
+        hipError_t e = hipMalloc((void**)&h->win_ring, (size_t)h->L * rows * 2 * h->D * sizeof(bf16_t));
+        if (e == hipSuccess && (e = hipMalloc((void**)&h->win_stage, rows * h->D * sizeof(bf16_t))) != hipSuccess) {
+            (void)hipFree(h->win_ring);
+            h->win_ring = nullptr;
+        }
+        if (e != hipSuccess) {
+            h->win_ring = h->win_stage = nullptr;
+            return sfail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc memory-token window: ") + hipGetErrorString(e));
+        }
+    }
+    h->win_B = B;
+    return 0;
+}
+
+int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_push: null handle");
+    if (!memory) return sfail(h, GITCAP_ERR_ARG, "student_window_push: null memory");
+    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_push: weights not finalized");
+    if (!h->win_ring) return sfail(h, GITCAP_ERR_STATE, "student_window_push: no window (gitcap_student_window_reset first)");
+    if (B != h->win_B || n < 1 || n > h->F) return sfail(h, GITCAP_ERR_ARG, "student_window_push: B differs from the reset's, or n outside [1, mem_tokens]");
+    S_GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->win_read_rec) S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
+    if (h->win_ring_rec) S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    const int D = h->D, F = h->F, n1 = std::min(n, F - h->win_head), n2 = n - n1;
+    const int64_t total = (int64_t)B * n * (D / 4);
+    hipLaunchKernelGGL(student_window_stage_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1024)), dim3(256), 0, s, memory,
+                       h->win_stage, B, n, n1, D / 4);
+    S_HIP_OK(h, hipGetLastError());
+    const size_t ring_layer = (size_t)B * F * 2 * D;
+    for (int l = 0; l < h->L; ++l) {
+        const StuLayer& Ly = h->layers[l];
+        // k | v of the new tokens: set_memory's GEMM (same launch form whatever M), its output rows the ring slots head .. head + n1 - 1
+        // of every clip and, wrapped, 0 .. n2 - 1
+        bf16_t* ring = h->win_ring + (size_t)l * ring_layer;
+        int rc = sk_full(h, s, SK_BIAS_BF16, h->win_stage, D, Ly.ca_in_w + (size_t)D * D, Ly.ca_in_b + D, B * n1, 2 * D, D, ring, 2 * D,
+                         n1, F, h->win_head);
+        if (!rc && n2)
+            rc = sk_full(h, s, SK_BIAS_BF16, h->win_stage + (size_t)B * n1 * D, D, Ly.ca_in_w + (size_t)D * D, Ly.ca_in_b + D, B * n2, 2 * D, D,
+                         ring, 2 * D, n2, F, 0);
+        if (rc) { h->win_count = 0; return rc; }      // some slots may be half written: the window is emptied
+    }
+    S_HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
+    h->win_ring_rec = true;
+    h->win_head = (h->win_head + n) % F;
+    h->win_count = std::min(h->win_count + n, F);
+    return 0;
+}
+
+int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_greedy: null handle");
+    if (int bad = greedy_check(h, "student_window_greedy", max_len, stop, ids_out)) return bad;
+    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_greedy: weights not finalized");
+    S_GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = window_memory(h, "student_window_greedy", 1, s);
+    if (rc) return rc;
+    return greedy_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
+}
+
+int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
+    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
+    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
+    if (!h->win_ring) return sfail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
+    if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;
+    S_GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = beam_workspace(h);
+    if (rc) return rc;
+    if ((rc = window_memory(h, "student_window_beam_search", k, s))) return rc;
+    return beam_loop(h, h->win_B, k, max_len, ids_out, s);
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 //               index math on the NHWC rows.
 //   tv_pool     mean of the stage-3 map over H*W -> fp32 memory, ascending pixel order.
 //   tv_to_nchw  bf16 NHWC rows -> fp32 NCHW feature map (only when the caller asks for feature maps).
+// gitcap_tinyvit_encode_raw takes uint8 camera frames: the first stem convolution's im2col rows then come from
+// preprocess_stem_kernel (preproc.hip: the frame transform fused with that gather) and everything behind them is shared.
 // No atomics: every output element is summed in an order fixed by its own row, so results do not depend on the batch.
 #include "../../include/gitcap.h"
 #include "kernels.h"
@@ -580,11 +582,12 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
     return 0;
 }
 
-int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float* memory, float* const* fmaps, void* stream) {
-    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: null handle");
-    if (!h->finalized) return tfail(h, GITCAP_ERR_STATE, "tinyvit_encode: weights not finalized");
-    if (!frames || !memory || n <= 0) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: bad arguments");
-    if (n > h->c.max_frames) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: n exceeds max_frames");
+}  // extern "C"
+
+// frames: fp32 [n][3][img][img] (normalised), or -- raw != nullptr -- uint8 [n][H][W][3] BGR camera frames whose transform is
+// fused with the gather of the first stem convolution (preproc.hip: preprocess_stem_kernel); everything behind that gather is shared
+static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t* raw, int rawH, int rawW, int n, float* memory,
+                          float* const* fmaps, void* stream) {
     DeviceGuard guard(h->device);
     if (!guard.ok) return tfail(h, GITCAP_ERR_HIP, "cannot select the handle's device");
     hipStream_t s = (hipStream_t)stream;
@@ -621,9 +624,16 @@ int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float
     };
     int rc;
     // stem (patch_embed): conv1 3 -> C0/2 (3x3 s2) + GELU, conv2 C0/2 -> C0 (3x3 s2)
-    hipLaunchKernelGGL(tv_im2col_kernel<true>, dim3(grid_for((int64_t)n * g1 * g1 * h->stem_k1)), dim3(256), 0, s, frames, h->col, n,
-                       img, img, 3, g1, g1, h->stem_k1);
-    T_HIP_OK(h, hipGetLastError());
+    if (raw) {
+        const hipError_t e = launch_preprocess_stem(raw, h->col, n, rawH, rawW, img, s);
+        if (e == hipErrorInvalidValue)
+            return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: frame size the transform refuses (empty, or resized below img_size)");
+        T_HIP_OK(h, e);
+    } else {
+        hipLaunchKernelGGL(tv_im2col_kernel<true>, dim3(grid_for((int64_t)n * g1 * g1 * h->stem_k1)), dim3(256), 0, s, frames, h->col, n,
+                           img, img, 3, g1, g1, h->stem_k1);
+        T_HIP_OK(h, hipGetLastError());
+    }
     if ((rc = gemm(h->col, h->stem_k1, h->stem1, n * g1 * g1, c0h, TV_GELU, h->s1, nullptr))) return rc;
     hipLaunchKernelGGL(tv_im2col_kernel<false>, dim3(grid_for((int64_t)n * g0 * g0 * h->stem_k2)), dim3(256), 0, s, h->s1, h->col, n,
                        g1, g1, c0h, g0, g0, h->stem_k2);
@@ -668,6 +678,26 @@ int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float
     hipLaunchKernelGGL(tv_pool_kernel, dim3(n), dim3(256), 0, s, x, memory, h->map[3] * h->map[3], h->C[3]);
     T_HIP_OK(h, hipGetLastError());
     return 0;
+}
+
+extern "C" {
+
+int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float* memory, float* const* fmaps, void* stream) {
+    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: null handle");
+    if (!h->finalized) return tfail(h, GITCAP_ERR_STATE, "tinyvit_encode: weights not finalized");
+    if (!frames || !memory || n <= 0) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: bad arguments");
+    if (n > h->c.max_frames) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: n exceeds max_frames");
+    return tinyvit_encode(h, frames, nullptr, 0, 0, n, memory, fmaps, stream);
+}
+
+int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr, int n, int H, int W, float* memory,
+                              float* const* fmaps, void* stream) {
+    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: null handle");
+    if (!h->finalized) return tfail(h, GITCAP_ERR_STATE, "tinyvit_encode_raw: weights not finalized");
+    if (!frames_hwc_bgr || !memory || n <= 0 || H <= 0 || W <= 0) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: bad arguments");
+    if (n > h->c.max_frames) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: n exceeds max_frames");
+    if ((int64_t)n * H * W * 3 > ((int64_t)1 << 40)) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: sizes overflow");
+    return tinyvit_encode(h, nullptr, frames_hwc_bgr, H, W, n, memory, fmaps, stream);
 }
 
 }  // extern "C"

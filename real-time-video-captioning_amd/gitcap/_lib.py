@@ -78,6 +78,10 @@ SYMBOLS = {
     "gitcap_student_forward_decoder": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gitcap_student_greedy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_student_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gitcap_student_window_reset": (c_int, [c_void_p, c_int]),
+    "gitcap_student_window_push": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gitcap_student_window_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gitcap_student_window_beam_search": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),
@@ -85,6 +89,7 @@ SYMBOLS = {
     "gitcap_tinyvit_load_tensor": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
     "gitcap_tinyvit_finalize": (c_int, [c_void_p]),
     "gitcap_tinyvit_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gitcap_tinyvit_encode_raw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

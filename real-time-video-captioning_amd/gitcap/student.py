@@ -10,8 +10,10 @@ with an exact KV cache.  The TinyViT image encoder runs on the HIP kernels of cs
 (``gitcap.tinyvit.TinyViTEncoder``): ``image_encoder="native"`` builds it from ``image_enc_name``, or the caller
 passes a ``TinyViTEncoder``; then frames ``[B,F,3,H,W]`` go to a caption on the device, the encoder's memory never
 leaving it.  Any other module mapping ``[B*F,3,H,W]`` to the list of feature maps (model.py:117) is still accepted as
-``image_encoder``; ``greedy_decode`` also accepts the frame features ``memory [B, F, d_model]`` directly.  There is no
-CPU or PyTorch fallback for the decoder or the native encoder.
+``image_encoder``; ``greedy_decode`` also accepts the frame features ``memory [B, F, d_model]`` directly.  With the
+native encoder every frame argument may also be uint8 BGR camera frames ``[B,F,H,W,3]`` (what the reference's webcam loop
+holds, src/real_time_inference.py:39), and ``caption_stream()`` captions a sliding window of live frames, encoding each
+frame once (``StudentCaptionStream``).  There is no CPU or PyTorch fallback for the decoder or the native encoder.
 """
 from __future__ import annotations
 
@@ -25,10 +27,79 @@ from torch import nn
 from . import _lib
 from .student_config import (CStudentConfig, StudentConfig, check_student_shapes, positional_table, student_shapes)
 from .tinyvit import TinyViTEncoder, tinyvit_config
+from .window import WindowSchedule
 
 ENC_PREFIX = "image_encoder.model."
 
 STOP_NEVER, STOP_ALL_SEP = 0, 1
+
+
+class StudentCaptionStream:
+    """Live captioning on the student over a sliding window of ``mem_tokens`` frames (StudentCaptioner.caption_stream;
+    include/gitcap.h: gitcap_student_window_*).  A frame is encoded once, when it is pushed, and its cross-attention K|V rows
+    are computed then; a caption of the window only orders those rows and runs the token loop.  Captions are bitwise those of
+    greedy_decode / beam_search on the window's frames."""
+
+    def __init__(self, model, batch, hop, max_len, mode, beams):
+        self._m = model
+        self._sched = WindowSchedule(batch, model.cfg.mem_tokens, hop)
+        self._max_len, self._mode, self._beams = max_len, mode, beams
+        self._token = object()
+        model._window_owner = self._token
+        with torch.cuda.device(model._dev):
+            model._call("gitcap_student_window_reset", batch)
+
+    def _check_live(self):
+        if self._m._window_owner is not self._token:
+            raise _lib.GitcapError("this StudentCaptionStream was invalidated (another caption_stream() was opened, or the model was moved)")
+
+    def reset(self):
+        """Empty the window: the next caption needs ``mem_tokens`` new frames."""
+        self._check_live()
+        with torch.cuda.device(self._m._dev):
+            self._m._call("gitcap_student_window_reset", self._sched.batch)
+        self._sched.reset()
+
+    def _tokens(self, frames: torch.Tensor) -> torch.Tensor:
+        """One frame per clip ([B,H,W,3] uint8 / [B,3,S,S] fp32), n of them ([B,n,...]) or memory tokens [B,n,d_model]
+        -> memory tokens [B,n,d_model] fp32 on the device."""
+        m = self._m
+        if frames.dtype != torch.uint8 and frames.dim() == 3:
+            if frames.shape[2] != m.cfg.d_model:
+                raise ValueError(f"expected memory tokens [B,n,{m.cfg.d_model}], got {tuple(frames.shape)}")
+            return frames.to(device=m._dev, dtype=torch.float32).contiguous()
+        if frames.dim() == 4:
+            frames = frames.unsqueeze(1)
+        if frames.dim() != 5:
+            raise ValueError(f"expected frames [B,H,W,3] uint8, [B,3,S,S] fp32, [B,n,...] or tokens [B,n,d_model], got {tuple(frames.shape)}")
+        self._sched.check(frames.shape[0], frames.shape[1])          # before any device work
+        return m.image_encoder.memory(frames).contiguous()
+
+    def push(self, frames: torch.Tensor):
+        """Append one frame per clip or n of them (see ``_tokens``), on the CPU or the device; only these frames are encoded.
+        -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in greedy_decode), or
+        with ``beams`` the best beam [B, max_len]; on the CPU when the frames were."""
+        self._check_live()
+        m = self._m
+        mem = self._tokens(frames)
+        B, n = mem.shape[:2]
+        self._sched.check(B, n)
+        with torch.cuda.device(m._dev):
+            m._call("gitcap_student_window_push", ctypes.c_void_p(mem.data_ptr()), B, n, m._stream())
+        if not self._sched.push(B, n):
+            return None
+        with torch.cuda.device(m._dev):
+            if self._beams is None:
+                ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
+                steps = torch.zeros(1, dtype=torch.int32, device=m._dev)
+                m._call("gitcap_student_window_greedy", self._max_len, self._mode, ctypes.c_void_p(ids.data_ptr()),
+                        ctypes.c_void_p(steps.data_ptr()), m._stream())
+                if self._mode == STOP_ALL_SEP:
+                    ids = ids[:, :1 + int(steps.item())]
+            else:
+                ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
+                m._call("gitcap_student_window_beam_search", self._beams, self._max_len, ctypes.c_void_p(ids.data_ptr()), m._stream())
+        return ids.cpu() if frames.device.type == "cpu" else ids
 
 
 def _rebuild_student(cfg_dict, weights, kwargs, encoder=None):
@@ -64,6 +135,7 @@ class StudentCaptioner(nn.Module):
         self.stop = stop
         self._dev = torch.device(device)
         self._handle = None
+        self._window_owner = None                       # token of the live StudentCaptionStream
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
         self._create()
@@ -114,6 +186,7 @@ class StudentCaptioner(nn.Module):
             idx = dev.index if dev.index is not None else torch.cuda.current_device()
             if idx != self._dev.index:
                 self._lib.gitcap_student_destroy(self._handle)
+                self._window_owner = None               # the window lived in the old handle
                 self._dev = torch.device("cuda", idx)
                 self._create()
                 if self._weights is not None:
@@ -183,16 +256,25 @@ class StudentCaptioner(nn.Module):
         return memory.to(device=self._dev, dtype=torch.float32).contiguous()
 
     def _frames_memory(self, src: torch.Tensor) -> torch.Tensor:
-        """frames [B,F,C,H,W] -> memory [B,F,D]; the native encoder writes no feature maps and does not sync."""
+        """frames [B,F,C,H,W] (or uint8 camera frames [B,F,H,W,3]) -> memory [B,F,D]; the native encoder writes no feature
+        maps and does not sync."""
         if self._native():
             return self.image_encoder.memory(src)
         return self.forward_image_enc(src)[1]
 
+    def _src_memory(self, src: torch.Tensor) -> torch.Tensor:
+        """The ``src`` of the decode calls: frames (5-D, or uint8 of either rank) go through the encoder, else memory."""
+        return self._frames_memory(src) if src.dim() == 5 or src.dtype == torch.uint8 else src
+
     @torch.no_grad()
     def forward_image_enc(self, x: torch.Tensor):
-        """model.py:108-126: frames [B,F,C,H,W] -> (feature maps, memory [B,F,De]) through the image encoder."""
+        """model.py:108-126: frames [B,F,C,H,W] -> (feature maps, memory [B,F,De]) through the image encoder.  The native
+        encoder also takes uint8 BGR camera frames [B,F,H,W,3]."""
         if self._native():
             return self.image_encoder.forward_with_memory(x)
+        if x.dtype == torch.uint8:
+            raise _lib.GitcapError("uint8 camera frames need the native TinyViT encoder (image_encoder='native'): the frame "
+                                   "transform runs inside its first convolution")
         if self.image_encoder is None:
             raise _lib.GitcapError("StudentCaptioner was built without an image_encoder: pass image_encoder='native' (the "
                                    "TinyViT encoder of libgitcap) or a module, or call the decoder with memory [B,F,d_model]")
@@ -226,10 +308,10 @@ class StudentCaptioner(nn.Module):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None) -> torch.Tensor:
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
-        device) or memory [B,F,D].
+        device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device."""
         out_dev = src.device
-        memory = self._frames_memory(src) if src.dim() == 5 else src
+        memory = self._src_memory(src)
         mem = self._memory(memory)
         if max_len < 1 or max_len > self.max_text_len:
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
@@ -253,7 +335,7 @@ class StudentCaptioner(nn.Module):
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams."""
         out_dev = src.device
-        memory = self._frames_memory(src) if src.dim() == 5 else src
+        memory = self._src_memory(src)
         mem = self._memory(memory)
         B = mem.shape[0]
         if B * k > self.max_batch:
@@ -268,12 +350,36 @@ class StudentCaptioner(nn.Module):
                        ctypes.c_void_p(best.data_ptr()), self._stream())
         return best.to(out_dev) if out_dev != best.device else best
 
+    def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
+                       beams: Optional[int] = None) -> StudentCaptionStream:
+        """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
+        frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
+        frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
+        (real_time_inference.py:44-57), hop = 1 a caption per new frame.  Greedy by default (ids as
+        greedy_decode(max_len, stop)); with ``beams`` the best beam of beam_search(max_len, k=beams).  Needs the native
+        encoder.  One live stream per model: opening another one, or moving the model, invalidates this one."""
+        if not self._native():
+            raise _lib.GitcapError("caption_stream needs the native TinyViT encoder (image_encoder='native'): frames are "
+                                   "encoded one at a time on the device")
+        if batch < 1 or batch > self.max_batch:
+            raise ValueError(f"batch {batch} outside 1..max_batch={self.max_batch}")
+        mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        if beams is None:
+            if max_len < 1 or max_len > self.max_text_len:
+                raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
+        else:
+            if batch * beams > self.max_batch:
+                raise ValueError(f"batch*beams={batch * beams} rows > max_batch={self.max_batch}")
+            if max_len < 2 or max_len - 1 > self.max_text_len or beams < 1 or beams > 16:
+                raise ValueError(f"beam search needs 2 <= max_len <= max_text_len+1={self.max_text_len + 1} and 1 <= beams <= 16")
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams)
+
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """The same search driven from the host the way the reference writes it (every step recomputes the whole prefix
         through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests."""
         out_dev = src.device
-        memory = self._frames_memory(src) if src.dim() == 5 else src
+        memory = self._src_memory(src)
         mem = self._memory(memory)
         B = mem.shape[0]
         if B * k > self.max_batch:

@@ -4,7 +4,10 @@ the reference's src/models/model.py:35-47, :108-126) on the HIP kernels of csrc/
 
 ``forward(x [N,3,H,W])`` returns the four feature maps (fp32 NCHW, as the reference's ``image_enc_fmaps``);
 ``memory(x [B,F,3,H,W])`` returns the mean of the stage-3 map, ``[B,F,C3]`` fp32 (model.py:124), without writing the
-feature maps.  Everything runs on the caller's current stream with no host synchronisation.  There is no CPU path."""
+feature maps.  Both also take uint8 BGR camera frames (``[N,H,W,3]`` / ``[B,F,H,W,3]``): the reference's frame transform
+then runs inside the first stem convolution's gather (``gitcap_tinyvit_encode_raw``), bitwise equal to
+``gitcap.preprocess.preprocess_frames`` followed by the fp32 call.  Everything runs on the caller's current stream with
+no host synchronisation.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes
@@ -142,12 +145,27 @@ class TinyViTEncoder(nn.Module):
 
     # ------------------------------------------------------------------ encode
     def _frames(self, x: torch.Tensor) -> torch.Tensor:
+        """[N,3,S,S] transformed frames, or uint8 BGR camera frames [N,H,W,3] (OpenCV layout, the reference's
+        real_time_inference.py:39; the dtype decides, as in GitCaptioner._check_frames) -> contiguous device tensor."""
         s = self.cfg.img_size
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != s or x.shape[3] != s:
+        raw = x.dtype == torch.uint8
+        if raw:
+            if x.dim() != 4 or x.shape[3] != 3 or min(x.shape[1], x.shape[2]) < 1:
+                raise ValueError(f"expected uint8 frames [N,H,W,3], got {tuple(x.shape)}")
+        elif x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != s or x.shape[3] != s:
             raise ValueError(f"expected frames [N,3,{s},{s}], got {tuple(x.shape)}")
         if x.shape[0] < 1 or x.shape[0] > self.max_frames:
             raise ValueError(f"{x.shape[0]} frames outside 1..max_frames={self.max_frames}")
-        return x.to(device=self._dev, dtype=torch.float32).contiguous()
+        return x.to(device=self._dev, dtype=torch.uint8 if raw else torch.float32).contiguous()
+
+    def _clips(self, x: torch.Tensor):
+        """[B,F,3,S,S], or uint8 [B,F,H,W,3] ([F,H,W,3] = one clip) -> (frames [B*F,...], B, F)."""
+        if x.dtype == torch.uint8 and x.dim() == 4:
+            x = x.unsqueeze(0)
+        if x.dim() != 5:
+            raise ValueError(f"expected frames [B,F,3,H,W] or uint8 [B,F,H,W,3], got {tuple(x.shape)}")
+        B, F = x.shape[:2]
+        return self._frames(x.reshape(B * F, *x.shape[2:])), B, F
 
     def _encode(self, x: torch.Tensor, want_fmaps: bool):
         n = x.shape[0]
@@ -161,26 +179,30 @@ class TinyViTEncoder(nn.Module):
             arr = ctypes.cast(ptrs, ctypes.c_void_p)
         with torch.cuda.device(self._dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-            self._call("gitcap_tinyvit_encode", ctypes.c_void_p(x.data_ptr()), n, ctypes.c_void_p(mem.data_ptr()),
-                       arr, stream)
+            if x.dtype == torch.uint8:       # the transform is fused with the first stem convolution's gather
+                self._call("gitcap_tinyvit_encode_raw", ctypes.c_void_p(x.data_ptr()), n, x.shape[1], x.shape[2],
+                           ctypes.c_void_p(mem.data_ptr()), arr, stream)
+            else:
+                self._call("gitcap_tinyvit_encode", ctypes.c_void_p(x.data_ptr()), n, ctypes.c_void_p(mem.data_ptr()),
+                           arr, stream)
         return fmaps, mem
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor):
-        """x [N,3,H,W] (normalised) -> list of the four stage feature maps, fp32 NCHW on the device."""
+        """x [N,3,H,W] (normalised) or uint8 camera frames [N,H,W,3] -> list of the four stage feature maps, fp32 NCHW on
+        the device."""
         return self._encode(self._frames(x), True)[0]
 
     @torch.no_grad()
     def forward_with_memory(self, x: torch.Tensor):
-        """x [B,F,3,H,W] -> (four feature maps [B*F,Ci,Hi,Wi], memory [B,F,C3]) from one encode."""
-        B, F = x.shape[:2]
-        fmaps, mem = self._encode(self._frames(x.reshape(B * F, *x.shape[2:])), True)
+        """x [B,F,3,H,W] or uint8 [B,F,H,W,3] -> (four feature maps [B*F,Ci,Hi,Wi], memory [B,F,C3]) from one encode."""
+        fr, B, F = self._clips(x)
+        fmaps, mem = self._encode(fr, True)
         return fmaps, mem.view(B, F, -1)
 
     @torch.no_grad()
     def memory(self, x: torch.Tensor) -> torch.Tensor:
-        """x [B,F,3,H,W] -> mean of the stage-3 map [B,F,C3] fp32 (model.py:124); no feature maps are written."""
-        if x.dim() != 5:
-            raise ValueError(f"expected frames [B,F,3,H,W], got {tuple(x.shape)}")
-        B, F = x.shape[:2]
-        return self._encode(self._frames(x.reshape(B * F, *x.shape[2:])), False)[1].view(B, F, -1)
+        """x [B,F,3,H,W] or uint8 [B,F,H,W,3] -> mean of the stage-3 map [B,F,C3] fp32 (model.py:124); no feature maps
+        are written."""
+        fr, B, F = self._clips(x)
+        return self._encode(fr, False)[1].view(B, F, -1)
