@@ -484,6 +484,24 @@ int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float
 int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr, int n, int H, int W, float* memory,
                               float* const* fmaps, void* stream);
 
+/* ---- scene-change gate for live frames (gitcap/framegate.py) -------------------------------------------------------------
+ * Replaces: the distances of frame_mse_difference_sampling / scene_change_detection_sampling
+ *                                                         src/utils/frame_sampling_methods.py:201-297
+ * How far B camera frames are from B reference frames (the last frames a caller kept), computed on the device in one pass over
+ * both: frames_hwc_bgr, ref_hwc_bgr device uint8 [B][H][W][3] (the layout of gitcap_tinyvit_encode_raw / gitcap_window_push_raw;
+ * any alignment).  All five outputs are device memory, each may be NULL:
+ *   ssd[B]              exact sum over the H*W*3 bytes of (frame - ref)^2, in integers (not the reference's uint8 arithmetic,
+ *                       which wraps modulo 256, :237)
+ *   hist_frame[B][256]  exact counts of the byte values of channel `channel` (0, 1 or 2 of the BGR triple; the reference
+ *   hist_ref[B][256]    histograms the red channel, :282-286, which is 2 here) of the frame / of the reference frame
+ *   mse[B]              (double)ssd / (H*W*3)
+ *   chisq[B]            sum over the bins i with hist_ref[i] > 0, in ascending i, of (hist_ref[i] - hist_frame[i])^2 / hist_ref[i]
+ *                       in fp64: OpenCV's HISTCMP_CHISQR with the reference frame as H1 (:284-288)
+ * Stateless (no handle): the partial sums live in a stream-ordered allocation of the call, so calls on different streams share
+ * nothing.  GITCAP_ERR_ARG: a null input, B, H or W < 1, channel outside 0..2, H*W*3 >= 2^31 or B >= 65536. */
+int gitcap_frame_change(const uint8_t* frames_hwc_bgr, const uint8_t* ref_hwc_bgr, int B, int H, int W, int channel,
+                        uint64_t* ssd, uint32_t* hist_frame, uint32_t* hist_ref, double* mse, double* chisq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

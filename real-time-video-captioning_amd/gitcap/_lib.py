@@ -90,6 +90,9 @@ SYMBOLS = {
     "gitcap_tinyvit_finalize": (c_int, [c_void_p]),
     "gitcap_tinyvit_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_tinyvit_encode_raw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # scene-change gate (gitcap/framegate.py)
+    "gitcap_frame_change": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
 }
 
 _lib = None

@@ -28,6 +28,7 @@ from torch import nn
 
 from . import _lib
 from .config import CGitCapConfig, GitCapConfig, git_base
+from .framegate import FrameGate, gated_frames
 from . import weights as W
 from .window import WindowSchedule
 
@@ -251,10 +252,13 @@ class InferFuture(_Future):
 class CaptionStream:
     """Live captioning over a sliding window of frames (GitCaptioner.caption_stream; include/gitcap.h: gitcap_window_*).  Every
     frame is encoded once, when it is pushed; a caption of the last `window` frames re-runs only the decoder's image prefix and the
-    token loop.  Captions are bitwise those of greedy_decode (or of infer's device search) on the window's frames."""
+    token loop.  Captions are bitwise those of greedy_decode (or of infer's device search) on the window's frames.  With a ``gate``
+    (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
-    def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features):
+    def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
+                 gate=None):
         self._m = model
+        self._gate = gate
         self._sched = WindowSchedule(batch, window, hop)
         self._max_len, self._mode = max_len, mode
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
@@ -276,6 +280,8 @@ class CaptionStream:
             self._m._call("gitcap_window_reset", self._sched.batch, self._sched.window)
         self._sched.reset()
         self._kept, self._kind = [], None
+        if self._gate is not None:
+            self._gate.reset()
 
     def _shape(self, frames):
         """[B,H,W,3] uint8 / [B,3,S,S] fp32 (one frame per clip) or [B,n,...] -> (5-D view, raw)."""
@@ -300,8 +306,16 @@ class CaptionStream:
     def push(self, frames: torch.Tensor):
         """Append one frame per clip ([B,H,W,3] uint8 camera frames or [B,3,S,S] transformed frames) or n of them ([B,n,...]), on
         the CPU or the device.  -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in
-        greedy_decode), or with beam_size the dict infer returns.  CPU frames in: the result is on the CPU and vouched for."""
+        greedy_decode), or with beam_size the dict infer returns.  CPU frames in: the result is on the CPU and vouched for.  A
+        gated stream takes uint8 camera frames only; the window and `hop` count the frames the gate admits, and a push with none
+        admitted returns None."""
         self._check_live()
+        if self._gate is None:
+            return self._push(frames, frames.device.type == "cpu")
+        admitted = gated_frames(self._gate, frames, self._sched, self._m._dev)
+        return None if admitted is None else self._push(admitted, frames.device.type == "cpu")
+
+    def _push(self, frames: torch.Tensor, on_cpu: bool):
         m = self._m
         x, raw = self._shape(frames)
         B, n = x.shape[:2]
@@ -322,7 +336,6 @@ class CaptionStream:
             self._repush()
         if not due:
             return None
-        on_cpu = x.device.type == "cpu"
         try:
             out = self._caption(on_cpu)
             if on_cpu:
@@ -1072,13 +1085,14 @@ class GitCaptioner(nn.Module):
 
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
-                       visual_features: bool = False) -> CaptionStream:
+                       visual_features: bool = False, gate=None) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
         default (ids as greedy_decode(max_len, stop)); with beam_size the dict of infer's device search (max_len = its
         max_steps; visual_features adds the window's features).  One live stream per model: opening another one, or .to() /
-        .cuda(), invalidates this one."""
+        .cuda(), invalidates this one.  ``gate``: a gitcap.framegate.FrameGate that decides on the device which pushed camera frames
+        are worth encoding (it is reset here); without one every pushed frame is."""
         window = int(window or max(1, self.cfg.num_frames))
         if batch > self.max_batch or window > self.max_frames or (self.cfg.num_frames > 0 and window > self.cfg.num_frames):
             raise ValueError(f"batch {batch} / window {window} exceed max_batch={self.max_batch} / max_frames={self.max_frames} "
@@ -1094,7 +1108,11 @@ class GitCaptioner(nn.Module):
             self._check_device_search(beam_size, per_node_beam_size, 1)
             if beam_size > self.max_beams:
                 raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
-        return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features)
+        if gate is not None:
+            if not isinstance(gate, FrameGate):
+                raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
+            gate.reset()
+        return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip

@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .framegate import FrameGate, gated_frames
 from .student_config import (CStudentConfig, StudentConfig, check_student_shapes, positional_table, student_shapes)
 from .tinyvit import TinyViTEncoder, tinyvit_config
 from .window import WindowSchedule
@@ -38,10 +39,12 @@ class StudentCaptionStream:
     """Live captioning on the student over a sliding window of ``mem_tokens`` frames (StudentCaptioner.caption_stream;
     include/gitcap.h: gitcap_student_window_*).  A frame is encoded once, when it is pushed, and its cross-attention K|V rows
     are computed then; a caption of the window only orders those rows and runs the token loop.  Captions are bitwise those of
-    greedy_decode / beam_search on the window's frames."""
+    greedy_decode / beam_search on the window's frames.  With a ``gate`` (gitcap.framegate.FrameGate) only the frames it admits
+    are encoded and counted; a push of camera frames with none admitted returns None and costs one distance launch."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None):
         self._m = model
+        self._gate = gate
         self._sched = WindowSchedule(batch, model.cfg.mem_tokens, hop)
         self._max_len, self._mode, self._beams = max_len, mode, beams
         self._token = object()
@@ -59,6 +62,8 @@ class StudentCaptionStream:
         with torch.cuda.device(self._m._dev):
             self._m._call("gitcap_student_window_reset", self._sched.batch)
         self._sched.reset()
+        if self._gate is not None:
+            self._gate.reset()
 
     def _tokens(self, frames: torch.Tensor) -> torch.Tensor:
         """One frame per clip ([B,H,W,3] uint8 / [B,3,S,S] fp32), n of them ([B,n,...]) or memory tokens [B,n,d_model]
@@ -78,8 +83,15 @@ class StudentCaptionStream:
     def push(self, frames: torch.Tensor):
         """Append one frame per clip or n of them (see ``_tokens``), on the CPU or the device; only these frames are encoded.
         -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in greedy_decode), or
-        with ``beams`` the best beam [B, max_len]; on the CPU when the frames were."""
+        with ``beams`` the best beam [B, max_len]; on the CPU when the frames were.  A gated stream takes uint8 camera frames
+        only, [B,H,W,3] or [B,n,H,W,3]; the window and `hop` count the frames the gate admits, and a push with none returns None."""
         self._check_live()
+        if self._gate is None:
+            return self._push(frames, frames.device.type == "cpu")
+        admitted = gated_frames(self._gate, frames, self._sched, self._m._dev)
+        return None if admitted is None else self._push(admitted, frames.device.type == "cpu")
+
+    def _push(self, frames: torch.Tensor, to_cpu: bool):
         m = self._m
         mem = self._tokens(frames)
         B, n = mem.shape[:2]
@@ -99,7 +111,7 @@ class StudentCaptionStream:
             else:
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 m._call("gitcap_student_window_beam_search", self._beams, self._max_len, ctypes.c_void_p(ids.data_ptr()), m._stream())
-        return ids.cpu() if frames.device.type == "cpu" else ids
+        return ids.cpu() if to_cpu else ids
 
 
 def _rebuild_student(cfg_dict, weights, kwargs, encoder=None):
@@ -351,13 +363,15 @@ class StudentCaptioner(nn.Module):
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
-                       beams: Optional[int] = None) -> StudentCaptionStream:
+                       beams: Optional[int] = None, gate: Optional[FrameGate] = None) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
         (real_time_inference.py:44-57), hop = 1 a caption per new frame.  Greedy by default (ids as
         greedy_decode(max_len, stop)); with ``beams`` the best beam of beam_search(max_len, k=beams).  Needs the native
-        encoder.  One live stream per model: opening another one, or moving the model, invalidates this one."""
+        encoder.  One live stream per model: opening another one, or moving the model, invalidates this one.
+        ``gate``: a FrameGate that decides on the device which pushed camera frames are worth encoding (it is reset here);
+        without one every pushed frame is."""
         if not self._native():
             raise _lib.GitcapError("caption_stream needs the native TinyViT encoder (image_encoder='native'): frames are "
                                    "encoded one at a time on the device")
@@ -372,7 +386,11 @@ class StudentCaptioner(nn.Module):
                 raise ValueError(f"batch*beams={batch * beams} rows > max_batch={self.max_batch}")
             if max_len < 2 or max_len - 1 > self.max_text_len or beams < 1 or beams > 16:
                 raise ValueError(f"beam search needs 2 <= max_len <= max_text_len+1={self.max_text_len + 1} and 1 <= beams <= 16")
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams)
+        if gate is not None:
+            if not isinstance(gate, FrameGate):
+                raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
+            gate.reset()
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
