@@ -65,10 +65,8 @@ struct DecLayer {
 
 }  // namespace
 
-struct gitcap {
+struct gitcap : HandleCore {
     gitcap_config c;
-    int device = 0;
-    mutable std::string err;
     std::map<std::string, DevTensor> w;
     std::map<std::string, float*> wscale;          // e4m3 storage: per-row scales of the GEMM weights
     std::map<std::string, std::pair<void*, size_t>> wpack;   // fragment-major copies of the text-path weights (name -> buffer, bytes)
@@ -89,8 +87,6 @@ struct gitcap {
     // derived sizes
     int N = 0, G = 0, Kp = 0, Dv = 0, D = 0, V = 0, Vp = 0;
     int Smax = 0, Mi = 0, Pp = 0, R = 0, Tmax = 0, Mt = 0;
-    int64_t ws_bytes = 0;
-    std::vector<void*> allocs;
 
     // workspace (image rows)
     float *x = nullptr, *tmp = nullptr;
@@ -106,22 +102,10 @@ struct gitcap {
     float f8_scale = 1.0f / 16.0f;                   // static power-of-two scale of the e4m3 activation codes (gitcap_set_fp8_scale)
     unsigned long long* f8_sat = nullptr;            // device counter: codes of valid rows the producing epilogues clamped at +-448
     unsigned char *hb8 = nullptr, *ffn8 = nullptr;   // [Mi][Dm] LayerNorm output / [Mi][Fm] GELU output as e4m3 codes of value * 16
-    bf16_t *hb = nullptr, *qkv = nullptr, *ctx = nullptr, *ffn = nullptr, *patches = nullptr, *kv_img = nullptr;
+    bf16_t *hb = nullptr, *qkv = nullptr, *ctx = nullptr, *ffn = nullptr, *patches = nullptr;
     // opt-in kv_cache = v_e4m3 (gitcap_set_kv_cache): V of the image prefix as e4m3 codes [layer][Mi][D] + power-of-two scales
     // [layer][Mi][H] per (token, head), written behind every decoder layer's q|k|v GEMM of the image rows, read by txt_block
-    bool kv_v8 = false;
-    unsigned char* v8_img = nullptr; float* vs_img = nullptr;       // views into the selected slot
-    // workspace (text rows)
-    float *xs = nullptr, *xs2 = nullptr, *slabs = nullptr, *part = nullptr, *amax_val = nullptr;
-    int* amax_idx = nullptr;
-    unsigned* row_cnt = nullptr;
-    bf16_t *xsb = nullptr, *fs = nullptr, *kv_txt = nullptr, *kv_txt2 = nullptr;
-    int32_t* sep_cnt = nullptr;
-    BeamBuffers beam{};                 // device-resident beam-search state (views into the selected slot)
-    float* beam_logits = nullptr;       // [R][V]
-    float* cand_scores = nullptr;       // [B][16]
-    int* cand_idx = nullptr;
-    char* topk_scratch = nullptr;       // beam_topk chunk statistics + per-chunk candidates (sized for max_batch x max_beams rows)
+    bool kv_v8 = false;             // (the codes and scales are the slots' v8_img / vs_img)
 
     // resolved weights
     WRef patch_w, vproj_w, head_w;
@@ -131,10 +115,6 @@ struct gitcap {
                 *head_b = nullptr;
     std::vector<EncLayer> enc;
     std::vector<DecLayer> dec;
-
-    // state of the selected image slot (views into slots[cur_slot]; see select_slot)
-    int cur_B = 0, cur_S = 0;
-    bool have_image = false;
 
     // Four slots (image-prefix K/V, text-row workspace, stop counters; two decode streams shared by the slots).  While one
     // batch's image pass (MFMA bound) runs on `s_enc`, the token loops of the batches submitted before
@@ -149,15 +129,20 @@ struct gitcap {
         unsigned* row_cnt = nullptr;
         bf16_t *xsb = nullptr, *fs = nullptr, *kv_txt = nullptr, *kv_txt2 = nullptr;
         // device-resident beam-search state of the slot (gitcap_beam_search / _submit)
-        BeamBuffers beam{}; float* beam_logits = nullptr; float* cand_scores = nullptr; int* cand_idx = nullptr; char* topk_scratch = nullptr;
-        int B = 0, S = 0; bool have = false, used = false;
+        BeamBuffers beam{};
+        float* beam_logits = nullptr;       // [R][V]
+        float* cand_scores = nullptr;       // [B][16]
+        int* cand_idx = nullptr;
+        char* topk_scratch = nullptr;       // beam_topk chunk statistics + per-chunk candidates (sized for max_batch x max_beams rows)
+        int B = 0, S = 0;                   // clips and image rows per clip of the image prefix the slot holds (have: it holds one)
+        bool have = false, used = false;
         int Mt = 0;             // text rows (rows x positions) the slot's row workspace holds
         hipEvent_t ev_in = nullptr, ev_enc = nullptr, ev_dec = nullptr;
         hipStream_t s_txt = nullptr;
     };
     static constexpr int NSLOT = 4;
     Slot slots[NSLOT];
-    int cur_slot = 0, next_ticket = 0;
+    int cur_slot = 0, next_ticket = 0;      // cur_slot: the slot the launches being issued work on (select_slot)
     int poison_upto = 0;    // tickets below this were in flight when the statistics exchange failed: their results are undefined
     hipStream_t s_enc = nullptr;
     hipStream_t txt_streams[NSLOT] = {nullptr, nullptr, nullptr, nullptr};   // owned; slot i decodes on txt_streams[i % n_txt]
@@ -184,7 +169,6 @@ struct gitcap {
 
 namespace {
 
-std::string g_create_err;
 // Number of decode streams the four slots share (slot i decodes on stream i % n).  HIP multiplexes streams onto
 // GPU_MAX_HW_QUEUES (default 4) hardware queues; with one stream per slot the throughput depended on which streams
 // happened to share a queue (1073-1723 captions/s over 1..8 queues, 1514 as soon as an RCCL communicator added its
@@ -204,23 +188,8 @@ std::atomic<int> g_tiny_tiles{getenv("GITCAP_GEMM_TINY_TILES") ? atoi(getenv("GI
 // ~30 s).  gitcap_dbg_config(6, n): a test forces the give-up path with n = 1.
 std::atomic<unsigned> g_ln_spin_limit{0};
 
-int fail(const gitcap* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_err = msg;
-    return code;
-}
-
-void select_slot(gitcap* h, int i) {
-    gitcap::Slot& o = h->slots[h->cur_slot];
-    o.B = h->cur_B; o.S = h->cur_S; o.have = h->have_image;
-    o.kv_txt = h->kv_txt; o.kv_txt2 = h->kv_txt2;        // reorder_rows swaps these two
-    gitcap::Slot& n = h->slots[i];
-    h->kv_img = n.kv_img; h->sep_cnt = n.sep_cnt; h->cur_B = n.B; h->cur_S = n.S; h->have_image = n.have;
-    h->v8_img = n.v8_img; h->vs_img = n.vs_img;
-    h->xs = n.xs; h->xs2 = n.xs2; h->slabs = n.slabs; h->part = n.part; h->row_cnt = n.row_cnt; h->amax_val = n.amax_val; h->amax_idx = n.amax_idx;
-    h->xsb = n.xsb; h->fs = n.fs; h->kv_txt = n.kv_txt; h->kv_txt2 = n.kv_txt2;
-    h->beam = n.beam; h->beam_logits = n.beam_logits; h->cand_scores = n.cand_scores; h->cand_idx = n.cand_idx; h->topk_scratch = n.topk_scratch;
-    h->cur_slot = i;
-}
+void select_slot(gitcap* h, int i) { h->cur_slot = i; }
+gitcap::Slot& cur(gitcap* h) { return h->slots[h->cur_slot]; }      // the selected slot: every use of slot state goes through here
 
 // Synchronous entry points (slot 0, caller's stream) share the image-row workspace with the submissions that
 // gitcap_greedy_submit put on the handle's own streams: before a synchronous call touches it, the caller's stream
@@ -253,15 +222,6 @@ int poll_exchange(gitcap* h) {
 }
 #define POLL(h) do { int rc_ = poll_exchange(h); if (rc_) return rc_; } while (0)
 
-#define HIP_OK(h, expr)                                                                               \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail(h, GITCAP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
-#define GUARD(h) DeviceGuard guard_((h)->device); if (!guard_.ok) return fail(h, GITCAP_ERR_HIP, "cannot select the handle's device")
-
 struct ProfScope {
     gitcap* h; hipStream_t s; gitcap::ProfRec* r = nullptr;
     ProfScope(gitcap* h_, int cls, hipStream_t s_, double flops, double bytes) : h(h_), s(s_) {
@@ -279,20 +239,6 @@ struct ProfScope {
     ~ProfScope() { if (r) (void)hipEventRecord(r->b, s); }
 };
 
-template <typename T>
-int ws_alloc(gitcap* h, T** p, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = count * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-    e = hipMemset(q, 0, bytes);
-    if (e != hipSuccess) return fail(h, GITCAP_ERR_HIP, std::string("hipMemset workspace: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    h->ws_bytes += (int64_t)bytes;
-    *p = (T*)q;
-    return 0;
-}
-
 int ln(gitcap* h, hipStream_t s, const float* x, int ldx, const float* g, const float* b, float eps, int rows, int D,
        float* of, int ldf, bf16_t* ob, int ldb, const float* addv = nullptr, int add_div = 1, int add_mod = 1) {
     ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, (double)rows * D * (4.0 + (of ? 4.0 : 0.0) + (ob ? 2.0 : 0.0)));
@@ -301,7 +247,7 @@ int ln(gitcap* h, hipStream_t s, const float* x, int ldx, const float* g, const 
     return 0;
 }
 
-// Tile kernel selection.  `rows` = the valid rows of the launch; a.M comes in as rows padded to 256.  Few 256x256 tiles
+// Tile kernel selection.  a.M comes in as the valid rows of the launch padded to 256.  Few 256x256 tiles
 // (small batches: one 6-frame clip is 5 x 3..12 tiles for 256 CUs) leave most of the chip idle: below g_small_tiles
 // tiles the 128x128 kernel (4x the workgroups, two per CU) is used (B=1: 7.7 -> 6.8 ms per caption), and below
 // g_tiny_tiles of THOSE the 64x64 kernel (16x, three per CU, 3-stage ring: the single-clip launches).  All tile kernels
@@ -328,9 +274,7 @@ hipError_t resolve_weight(gitcap* h, const WRef& W, int N, int K, hipStream_t s,
     return e;
 }
 
-// `rows` = the valid rows of the launch (a.M = rows padded to 256)
-hipError_t launch_gemm_auto(gitcap* h, GemmArgs a, int epi, hipStream_t s, int rows, int cap) {
-    (void)rows; (void)cap;
+hipError_t launch_gemm_auto(gitcap* h, GemmArgs a, int epi, hipStream_t s) {
     const bool ln = epi == EPI_RESID_LN_PRE || epi == EPI_RESID_LN_POST;
     if (ln) { a.ln_fail = h->ln_fail; a.ln_spin_limit = g_ln_spin_limit; }
     if (a.wscale) return launch_gemm256f8(a, epi, s);                 // e4m3 operands: one tile kernel, whatever the batch
@@ -375,7 +319,7 @@ int gemm(gitcap* h, hipStream_t s, int epi, const bf16_t* A, int lda, const WRef
     ProfScope ps(h, GITCAP_PROF_GEMM, s, 2.0 * R * N * K, 2.0 * R * K + 2.0 * N * K + R * N * (osz + (resid ? 4.0 : 0.0)));
     a.A = A; a.lda = lda; a.bias = bias; a.M = M; a.N = N; a.K = K; a.out = out; a.ldo = ldo;
     a.resid = resid; a.ldr = ldr;
-    HIP_OK(h, launch_gemm_auto(h, a, epi, s, rows, h->Mi));
+    HIP_OK(h, launch_gemm_auto(h, a, epi, s));
     return 0;
 }
 
@@ -400,9 +344,20 @@ int gemm_f8(gitcap* h, hipStream_t s, int epi, const unsigned char* A8, int lda,
     a.A = (const bf16_t*)A8; a.lda = lda; a.W = (const bf16_t*)W.p; a.wscale = W.scale; a.ascale = h->f8_scale; a.bias = bias;
     a.M = M; a.N = N; a.K = K; a.out = out8; a.ldo = ldo; a.out8_inv = 1.0f / h->f8_scale;
     a.valid_rows = rows; a.f8_sat = h->f8_sat;
-    HIP_OK(h, launch_gemm_auto(h, a, epi, s, rows, h->Mi));
+    HIP_OK(h, launch_gemm_auto(h, a, epi, s));
     return 0;
 }
+
+// what a caller of gemm_ln may ask for beyond the plain form
+struct LnOpts {
+    const float* addv = nullptr;    // nullable: LayerNorm output += addv[((row / add_div) % add_mod) * N + n] (temporal embedding)
+    int add_div = 1, add_mod = 1;
+    float* ln_f32 = nullptr;        // nullable: the LayerNorm output in fp32 as well
+    // ln8 (fp8 compute): also write the LayerNorm output as e4m3 codes (the next FC1's operand).  f8in: A is e4m3 codes
+    // [M][lda bytes] and W the e4m3 storage (FC2 in fp8 compute).  Both exist in the fused epilogue only.
+    unsigned char* ln8 = nullptr;
+    bool f8in = false;
+};
 
 // GEMM (+ bias [+ residual]) followed by LayerNorm of its output rows.
 //   post = false (pre-LN ViT block):   x = A W^T + bias + resid -> xout (fp32, may alias resid);  ln_b = bf16 LN(x)
@@ -411,13 +366,11 @@ int gemm_f8(gitcap* h, hipStream_t s, int epi, const unsigned char* A8, int lda,
 // statistics); small ones the 128x128 kernel + the row kernel.  Both give the same bits (ln_canon.h).
 // GITCAP_NO_GEMM_LN=1 (diagnosis / A-B only) keeps every LayerNorm a launch of its own; so does a handle whose exchange
 // ever timed out (poll_exchange).
-
 int gemm_ln(gitcap* h, hipStream_t s, bool post, const bf16_t* A, int lda, const WRef& W, const float* bias, int M, int N,
             int K, float* xout, const float* resid, const float* ln_g, const float* ln_b, float eps, int rows,
-            bf16_t* ln_out, float* scratch, const float* addv = nullptr, int add_div = 1, int add_mod = 1, float* ln_f32 = nullptr,
-            unsigned char* ln8 = nullptr, bool f8in = false) {
-    // ln8 (fp8 compute): also write the LayerNorm output as e4m3 codes (the next FC1's operand).  f8in: A is e4m3 codes
-    // [M][lda bytes] and W the e4m3 storage (FC2 in fp8 compute).  Both exist in the fused epilogue only.
+            bf16_t* ln_out, float* scratch, const LnOpts& o = {}) {
+    const float* const addv = o.addv; const int add_div = o.add_div, add_mod = o.add_mod;
+    float* const ln_f32 = o.ln_f32; unsigned char* const ln8 = o.ln8; const bool f8in = o.f8in;
     GemmArgs a{};
     a.A = A; a.lda = lda; a.bias = bias; a.M = M; a.N = N; a.K = K; a.out = xout; a.ldo = N; a.resid = resid; a.ldr = N;
     a.ln_out8 = ln8; a.ld_ln8 = N; a.ln_out8_inv = 1.0f / h->f8_scale; a.f8_sat = h->f8_sat;
@@ -438,7 +391,7 @@ int gemm_ln(gitcap* h, hipStream_t s, bool post, const bf16_t* A, int lda, const
         if (!f8in) HIP_OK(h, resolve_weight(h, W, N, K, s, &a.W));
         const double R = rows, esz = f8in ? 1.0 : 2.0;   // A + W + fp32 out + bf16 LayerNorm out (+ fp32 residual read)
         ProfScope ps(h, GITCAP_PROF_GEMM_LN, s, 2.0 * R * N * K, esz * R * K + esz * N * K + R * N * ((xout ? 4.0 : 0.0) + 2.0 + (ln_f32 ? 4.0 : 0.0) + (resid ? 4.0 : 0.0)));
-        HIP_OK(h, launch_gemm_auto(h, a, post ? EPI_RESID_LN_POST : EPI_RESID_LN_PRE, s, rows, h->Mi));
+        HIP_OK(h, launch_gemm_auto(h, a, post ? EPI_RESID_LN_POST : EPI_RESID_LN_PRE, s));
         return 0;
     }
     int rc;
@@ -475,6 +428,7 @@ int ln_reduce(gitcap* h, hipStream_t s, const float* slabs, int nslab, const flo
 // projected image tokens -> decoder layers over image rows only; fills kv_img (text independent)
 int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
     const gitcap_config& c = h->c;
+    gitcap::Slot& sl = cur(h);
     const int D = h->D, Dv = h->Dv, rows = B * S, Mp = pad_to(rows, 256);
     int rc;
     h->n_staged = 0;
@@ -492,12 +446,12 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
     auto quant_v = [&](int l, const bf16_t* kv) -> int {
         if (!h->kv_v8) return 0;
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, (double)rows * D * 3.0);
-        HIP_OK(h, launch_kv_quant_v(kv, h->v8_img + (size_t)l * h->Mi * D, h->vs_img + (size_t)l * h->Mi * c.dec_heads, rows, D, c.dec_heads, h->Mi, s));
+        HIP_OK(h, launch_kv_quant_v(kv, sl.v8_img + (size_t)l * h->Mi * D, sl.vs_img + (size_t)l * h->Mi * c.dec_heads, rows, D, c.dec_heads, h->Mi, s));
         return 0;
     };
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayer& L = h->dec[l];
-        bf16_t* kv = h->kv_img + (size_t)l * kv_layer;
+        bf16_t* kv = sl.kv_img + (size_t)l * kv_layer;
         if (l + 1 < c.dec_layers || hid) {
             {   // e4m3 storage: the layer's matrices -> bf16 staging, one launch (fp8 compute reads FC1 / FC2 as they are)
                 const WRef* ws[4] = {&L.qkvw, &L.aow, &L.fc1w, &L.fc2w};
@@ -510,13 +464,15 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
                 ProfScope ps(h, GITCAP_PROF_ATTN_FULL, s, 4.0 * B * c.dec_heads * (double)S * S * 64, 0.0);
                 HIP_OK(h, launch_attn_full(kv, h->ctx, B, S, c.dec_heads, s));
             }
+            LnOpts ao; ao.ln8 = f8 ? h->hb8 : nullptr;
             if ((rc = gemm_ln(h, s, true, h->ctx, D, L.aow, L.aob, Mp, D, D, h->x, h->x, L.ln1w, L.ln1b, c.dec_ln_eps, rows,
-                              h->hb, h->tmp, nullptr, 1, 1, nullptr, f8 ? h->hb8 : nullptr))) return rc;
+                              h->hb, h->tmp, ao))) return rc;
             if (f8) rc = gemm_f8(h, s, EPI_BIAS_GELU_F8, h->hb8, D, L.fc1w, L.fc1b, rows, Mp, c.dec_ffn, D, h->ffn8, c.dec_ffn);
             else rc = gemm(h, s, EPI_BIAS_GELU_BF16, h->hb, D, L.fc1w, L.fc1b, rows, Mp, c.dec_ffn, D, h->ffn, c.dec_ffn);
             if (rc) return rc;
+            LnOpts fc2; fc2.f8in = f8;
             if ((rc = gemm_ln(h, s, true, f8 ? (const bf16_t*)h->ffn8 : h->ffn, c.dec_ffn, L.fc2w, L.fc2b, Mp, D, c.dec_ffn, h->x, h->x, L.ln2w, L.ln2b,
-                              c.dec_ln_eps, rows, h->hb, h->tmp, nullptr, 1, 1, nullptr, nullptr, f8))) return rc;
+                              c.dec_ln_eps, rows, h->hb, h->tmp, fc2))) return rc;
             HIP_OK(h, keep(l + 1));
         } else {
             // last layer: image rows are only ever read as keys/values -> K,V projections only
@@ -524,7 +480,7 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
             if ((rc = quant_v(l, kv))) return rc;
         }
     }
-    h->cur_B = B; h->cur_S = S; h->have_image = true;
+    sl.B = B; sl.S = S; sl.have = true;
     return 0;
 }
 
@@ -547,15 +503,16 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
                  int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
                  bool pre_embedded = false, bool embed_next = false) {
     const gitcap_config& c = h->c;
+    gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
-    if (!h->have_image) return fail(h, GITCAP_ERR_STATE, "text_forward before encode/set_visual");
+    if (!sl.have) return fail(h, GITCAP_ERR_STATE, "text_forward before encode/set_visual");
     if (!ids || rows <= 0 || beams <= 0 || T <= 0 || t0 < 0) return fail(h, GITCAP_ERR_ARG, "text_forward: bad arguments");
-    if (rows != h->cur_B * beams) return fail(h, GITCAP_ERR_ARG, "text_forward: rows != encoded clips * beams");
+    if (rows != sl.B * beams) return fail(h, GITCAP_ERR_ARG, "text_forward: rows != encoded clips * beams");
     if (rows > h->R) return fail(h, GITCAP_ERR_ARG, "text_forward: rows exceed max_batch*max_beams");
     if (t0 + T > h->Tmax) return fail(h, GITCAP_ERR_ARG, "text_forward: t0+T exceeds max_text_len");
     if (t0 + T > c.max_text_pos) return fail(h, GITCAP_ERR_ARG, "text_forward: position exceeds max_text_pos");
     const int D = h->D, M = rows * T, H = c.dec_heads;
-    if (M > h->slots[h->cur_slot].Mt) return fail(h, GITCAP_ERR_STATE, "text_forward: more text rows than the slot's workspace holds");
+    if (M > sl.Mt) return fail(h, GITCAP_ERR_STATE, "text_forward: more text rows than the slot's workspace holds");
     int rc;
     const size_t kvi_layer = (size_t)h->Mi * 3 * D, kvt_layer = (size_t)h->R * h->Tmax * 3 * D;
     // FC1 -> GELU -> FC2 of the text rows: one launch over 64-wide hidden slices (ffn_txt.hip), leaving dec_ffn / 64 fp32
@@ -566,7 +523,7 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     const int ks_f = ffn_slices ? c.dec_ffn / 64 : skinny_ksplit(c.dec_ffn);
     const bool hid = h->want_hidden && h->cur_slot == 0 && !h->pipelined && t0 == 0;    // hidden-state export: a whole prefix, synchronous path
     auto keep_txt = [&](int entry) -> hipError_t {                       // xs = the text rows' input of layer `entry`
-        return hid ? hipMemcpyAsync(h->hid_txt + (size_t)entry * h->Mt * D, h->xs, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+        return hid ? hipMemcpyAsync(h->hid_txt + (size_t)entry * h->Mt * D, sl.xs, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
     };
     if (hid) h->hid_T = T;
     // Per layer 5 launches: [text embedding | reduce of the previous layer's FC2 slabs + LayerNorm], q|k|v projection
@@ -575,20 +532,20 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     // (skinny.hip "row prologue": every workgroup of the q|k|v launch computes the rows itself): 4 launches per layer.
     // The residual rows then alternate between two buffers (workgroup 0 writes them while the others still read the old).
     const bool rows_pro = g_row_prologue && !hid && skinny_row_prologue_ok(M, D, h->dec[0].qkvw.scale != nullptr);
-    float *xcur = h->xs, *xalt = h->xs2;
+    float *xcur = sl.xs, *xalt = sl.xs2;
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayer& L = h->dec[l];
-        bf16_t* kvt = h->kv_txt + (size_t)l * kvt_layer;
+        bf16_t* kvt = sl.kv_txt + (size_t)l * kvt_layer;
         if (rows_pro) {
             ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * M * 3 * D * D, 2.0 * 3 * D * D);
-            SkinnyArgs a{h->xsb, D, L.qkvw.p, nullptr, L.qkvb, M, 3 * D, D, kvt, 3 * D, T, h->Tmax, t0, nullptr, nullptr};
+            SkinnyArgs a{sl.xsb, D, L.qkvw.p, nullptr, L.qkvb, M, 3 * D, D, kvt, 3 * D, T, h->Tmax, t0, nullptr, nullptr};
             a.Wpk = L.qkvw.pk;
             if (l == 0) {
                 a.ln.kind = 2; a.ln.ids = ids; a.ln.ld_ids = ld_ids; a.ln.T = T; a.ln.t0 = t0; a.ln.vocab = c.vocab_size;
                 a.ln.word = h->word; a.ln.pos = h->tpos; a.ln.g = h->txt_lnw; a.ln.b = h->txt_lnb;
             } else {
                 const DecLayer& P = h->dec[l - 1];
-                a.ln.kind = 1; a.ln.slabs = h->slabs; a.ln.nslab = ks_f; a.ln.bias = P.fc2b; a.ln.resid = xcur; a.ln.g = P.ln2w; a.ln.b = P.ln2b;
+                a.ln.kind = 1; a.ln.slabs = sl.slabs; a.ln.nslab = ks_f; a.ln.bias = P.fc2b; a.ln.resid = xcur; a.ln.g = P.ln2w; a.ln.b = P.ln2b;
             }
             a.ln.eps = c.dec_ln_eps; a.ln.xf = xalt;
             HIP_OK(h, launch_skinny(a, SK_BIAS_BF16, s));
@@ -597,43 +554,43 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
             if (l == 0) {
                 if (!pre_embedded)
                     HIP_OK(h, launch_embed_text(ids, ld_ids, rows, T, t0, h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D,
-                                                c.vocab_size, xcur, h->xsb, s));
+                                                c.vocab_size, xcur, sl.xsb, s));
             } else {
                 const DecLayer& P = h->dec[l - 1];
-                if ((rc = ln_reduce(h, s, h->slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, h->xsb))) return rc;
+                if ((rc = ln_reduce(h, s, sl.slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, sl.xsb))) return rc;
             }
             HIP_OK(h, keep_txt(l));
-            if ((rc = skinny(h, s, SK_BIAS_BF16, h->xsb, D, L.qkvw, L.qkvb, M, 3 * D, D, kvt, 3 * D, T, h->Tmax, t0))) return rc;
+            if ((rc = skinny(h, s, SK_BIAS_BF16, sl.xsb, D, L.qkvw, L.qkvb, M, 3 * D, D, kvt, 3 * D, T, h->Tmax, t0))) return rc;
         }
         {
             TxtBlockArgs ta{};
-            ta.kv_img = h->kv_img + (size_t)l * kvi_layer; ta.kv_txt = kvt;
-            ta.rows = rows; ta.beams = beams; ta.t0 = t0; ta.T = T; ta.Tmax = h->Tmax; ta.S_img = h->cur_S; ta.H = H; ta.D = D;
+            ta.kv_img = sl.kv_img + (size_t)l * kvi_layer; ta.kv_txt = kvt;
+            ta.rows = rows; ta.beams = beams; ta.t0 = t0; ta.T = T; ta.Tmax = h->Tmax; ta.S_img = sl.S; ta.H = H; ta.D = D;
             ta.aow = L.aow.p; ta.aowpk = L.aow.scale ? nullptr : L.aow.pk; ta.aoscale = L.aow.scale; ta.aob = L.aob; ta.g1 = L.ln1w; ta.b1 = L.ln1b; ta.xin = xcur; ta.eps = c.dec_ln_eps;
-            ta.part = h->part; ta.cnt = h->row_cnt; ta.xs = xcur; ta.xsb = h->xsb;
-            if (h->kv_v8) { ta.v8_img = h->v8_img + (size_t)l * h->Mi * D; ta.vs_img = h->vs_img + (size_t)l * h->Mi * H; ta.v8_pitch = h->Mi; }
+            ta.part = sl.part; ta.cnt = sl.row_cnt; ta.xs = xcur; ta.xsb = sl.xsb;
+            if (h->kv_v8) { ta.v8_img = sl.v8_img + (size_t)l * h->Mi * D; ta.vs_img = sl.vs_img + (size_t)l * h->Mi * H; ta.v8_pitch = h->Mi; }
             // K/V of all layers that one token step streams: beyond what the 256 MiB Infinity Cache can keep next to the
             // 132 MB of decoder weights, the rows are loaded non-temporally (16 clips x 6 frames: 349 MB per step; measured
             // +0.6 % pipelined, -1 % serial step; one clip stays cached across steps and is 4 % faster with the default policy)
-            ta.nt_kv = (double)h->cur_B * c.dec_layers * 2.0 * h->cur_S * D * 2.0 > 128e6 ? 1 : 0;
+            ta.nt_kv = (double)sl.B * c.dec_layers * 2.0 * sl.S * D * 2.0 > 128e6 ? 1 : 0;
             double kvb = 0;
-            for (int j = 0; j < T; ++j) kvb += (double)rows * (h->cur_S + t0 + j + 1) * 2 * D * 2;
-            if (h->kv_v8) kvb -= (double)rows * T * h->cur_S * (D - 4.0 * H);          // image V: 1 byte per element + 4 per (key, head)
+            for (int j = 0; j < T; ++j) kvb += (double)rows * (sl.S + t0 + j + 1) * 2 * D * 2;
+            if (h->kv_v8) kvb -= (double)rows * T * sl.S * (D - 4.0 * H);          // image V: 1 byte per element + 4 per (key, head)
             ProfScope ps(h, GITCAP_PROF_ATTN_TEXT, s, 0.0, kvb + (L.aow.scale ? 1.0 : 2.0) * D * D);     // K/V read once + the output dense
             HIP_OK(h, launch_txt_block(ta, s));
         }
         if (ffn_fused) {
             ProfScope ps(h, GITCAP_PROF_SKINNY, s, 4.0 * M * c.dec_ffn * D, (L.fc1w.scale ? 1.0 : 2.0) * 2.0 * c.dec_ffn * D);
-            FfnTxtArgs fa{h->xsb, D, L.fc1w.pk, L.fc2w.pk, L.fc1w.scale, L.fc2w.scale, L.fc1b, M, D, c.dec_ffn, h->slabs};
+            FfnTxtArgs fa{sl.xsb, D, L.fc1w.pk, L.fc2w.pk, L.fc1w.scale, L.fc2w.scale, L.fc1b, M, D, c.dec_ffn, sl.slabs};
             HIP_OK(h, launch_ffn_txt(fa, s));
         } else {
-            if ((rc = skinny(h, s, SK_BIAS_GELU_BF16, h->xsb, D, L.fc1w, L.fc1b, M, c.dec_ffn, D, h->fs, c.dec_ffn))) return rc;
-            if ((rc = skinny_splitk(h, s, h->fs, c.dec_ffn, L.fc2w, M, D, c.dec_ffn, h->slabs, ffn_slices ? ks_f : 0))) return rc;
+            if ((rc = skinny(h, s, SK_BIAS_GELU_BF16, sl.xsb, D, L.fc1w, L.fc1b, M, c.dec_ffn, D, sl.fs, c.dec_ffn))) return rc;
+            if ((rc = skinny_splitk(h, s, sl.fs, c.dec_ffn, L.fc2w, M, D, c.dec_ffn, sl.slabs, ffn_slices ? ks_f : 0))) return rc;
         }
     }
     {   // the last layer's FC2 reduce + bias + residual + LayerNorm
         const DecLayer& P = h->dec[c.dec_layers - 1];
-        if ((rc = ln_reduce(h, s, h->slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, h->xsb))) return rc;
+        if ((rc = ln_reduce(h, s, sl.slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, sl.xsb))) return rc;
         HIP_OK(h, keep_txt(c.dec_layers));
     }
     if (!logits_out && !argmax_out) return 0;
@@ -643,19 +600,19 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     ha.W = h->head_w.p; ha.Wpk = h->head_w.pk; ha.wscale = h->head_w.scale; ha.bias = h->head_b; ha.N = V; ha.K = D; ha.ldo = V; ha.T = 1; ha.row_stride = 1; ha.row_off = 0;
     int am_stride = 1, am_off = 0;
     if (all_positions && logits_out) {
-        ha.X = h->xsb; ha.ldx = D; ha.M = M; ha.out = logits_out;
+        ha.X = sl.xsb; ha.ldx = D; ha.M = M; ha.out = logits_out;
         am_stride = T; am_off = T - 1;
     } else {
-        ha.X = h->xsb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows; ha.out = logits_out;
+        ha.X = sl.xsb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows; ha.out = logits_out;
     }
-    if (argmax_out) { ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx; }
+    if (argmax_out) { ha.amax_val = sl.amax_val; ha.amax_idx = sl.amax_idx; }
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
         HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     }
     if (argmax_out) {
-        const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, h->xs, h->xsb};
-        HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
+        const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
+        HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
                                       sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr));
     }
     return 0;
@@ -698,7 +655,7 @@ static int submit_common(gitcap* h, FrameSrc src, int B, int F, float* visual_ou
             if (hipEventRecord(sl.ev_enc, h->s_enc) == hipSuccess) (void)hipStreamWaitEvent(sl.s_txt, sl.ev_enc, 0);
             if (hipEventRecord(sl.ev_dec, sl.s_txt) == hipSuccess) sl.used = true;
             else (void)hipDeviceSynchronize();          // no event to order on: drain instead
-            h->have_image = false;
+            sl.have = false;
         }
         select_slot(h, 0);
         return rc;
@@ -732,31 +689,31 @@ extern "C" {
 
 int gitcap_abi_version(void) { return GITCAP_ABI_VERSION; }
 
-const char* gitcap_last_error(const gitcap_t* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+const char* gitcap_last_error(const gitcap_t* h) { return h ? h->err.c_str() : create_err<gitcap>().c_str(); }
 
 int gitcap_create(const gitcap_config* cfg, int device, gitcap_t** out) {
-    if (!cfg || !out) return fail(nullptr, GITCAP_ERR_ARG, "create: null argument");
+    if (!cfg || !out) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: null argument");
     *out = nullptr;
     const gitcap_config& c = *cfg;
-    if (c.patch_size <= 0 || c.image_size % c.patch_size) return fail(nullptr, GITCAP_ERR_ARG, "create: image_size % patch_size != 0");
+    if (c.patch_size <= 0 || c.image_size % c.patch_size) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: image_size % patch_size != 0");
     if (c.enc_heads * 64 != c.enc_width || c.dec_heads * 64 != c.dec_width)
-        return fail(nullptr, GITCAP_ERR_ARG, "create: head_dim must be 64");
+        return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: head_dim must be 64");
     for (int n : {c.enc_width, c.enc_ffn, c.dec_width, c.dec_ffn})
-        if (n % 128) return fail(nullptr, GITCAP_ERR_ARG, "create: widths must be multiples of 128");
-    if (c.enc_width > 1024) return fail(nullptr, GITCAP_ERR_ARG, "create: enc_width > 1024 unsupported");
-    if (!txt_block_ok(c.dec_width)) return fail(nullptr, GITCAP_ERR_ARG, "create: dec_width must be 768 (GIT) or 128 (test config)");
+        if (n % 128) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: widths must be multiples of 128");
+    if (c.enc_width > 1024) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: enc_width > 1024 unsupported");
+    if (!txt_block_ok(c.dec_width)) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: dec_width must be 768 (GIT) or 128 (test config)");
     if (c.max_batch <= 0 || c.max_frames <= 0 || c.max_text_len <= 0 || c.max_beams <= 0)
-        return fail(nullptr, GITCAP_ERR_ARG, "create: max_* must be positive");
-    if (c.patch_size % 2) return fail(nullptr, GITCAP_ERR_ARG, "create: odd patch_size unsupported");
+        return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: max_* must be positive");
+    if (c.patch_size % 2) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: odd patch_size unsupported");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, GITCAP_ERR_HIP, "create: no HIP device visible (libgitcap has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(nullptr, GITCAP_ERR_ARG, "create: bad device index");
+        return fail<gitcap>(nullptr, GITCAP_ERR_HIP, "create: no HIP device visible (libgitcap has no CPU path)");
+    if (device < 0 || device >= ndev) return fail<gitcap>(nullptr, GITCAP_ERR_ARG, "create: bad device index");
     hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(nullptr, GITCAP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail<gitcap>(nullptr, GITCAP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
 
     gitcap* h = new (std::nothrow) gitcap();
-    if (!h) return fail(nullptr, GITCAP_ERR_NOMEM, "create: out of host memory");
+    if (!h) return fail<gitcap>(nullptr, GITCAP_ERR_NOMEM, "create: out of host memory");
     h->c = c; h->device = device;
     h->G = c.image_size / c.patch_size; h->N = h->G * h->G + 1;
     h->Kp = pad_to(3 * c.patch_size * c.patch_size, 64);
@@ -771,66 +728,57 @@ int gitcap_create(const gitcap_config* cfg, int device, gitcap_t** out) {
     h->nslab_max = std::max(16, std::min(64, c.dec_ffn / 64));    // FC2 partial slabs per text row: dec_ffn / 64 hidden slices (ffn_txt.hip)
     int rc = 0;
     const size_t Mi = h->Mi;
-    rc = rc ? rc : ws_alloc(h, &h->x, Mi * Dm);
-    rc = rc ? rc : ws_alloc(h, &h->tmp, Mi * h->D);
-    rc = rc ? rc : ws_alloc(h, &h->ln_stats, Mi * 16);
+    rc = rc ? rc : dev_alloc(h, &h->x, Mi * Dm);
+    rc = rc ? rc : dev_alloc(h, &h->tmp, Mi * h->D);
+    rc = rc ? rc : dev_alloc(h, &h->ln_stats, Mi * 16);
     h->ln_cnt_words = 2 * (Mi / 224 + 2);
-    rc = rc ? rc : ws_alloc(h, &h->ln_cnt, h->ln_cnt_words);
+    rc = rc ? rc : dev_alloc(h, &h->ln_cnt, h->ln_cnt_words);
     if (!rc) {
         if (hipHostMalloc((void**)&h->ln_fail, 64, hipHostMallocMapped) != hipSuccess) rc = fail(h, GITCAP_ERR_NOMEM, "create: hipHostMalloc (exchange flag)");
         else memset(h->ln_fail, 0, 64);
     }
     h->cus = device_cus();
-    rc = rc ? rc : ws_alloc(h, &h->hb, Mi * Dm);
-    rc = rc ? rc : ws_alloc(h, &h->qkv, Mi * 3 * h->Dv);
-    rc = rc ? rc : ws_alloc(h, &h->ctx, Mi * Dm);
-    rc = rc ? rc : ws_alloc(h, &h->ffn, Mi * Fm);
-    rc = rc ? rc : ws_alloc(h, &h->patches, (size_t)h->Pp * h->Kp);
-    rc = rc ? rc : ws_alloc(h, &h->kv_img, (size_t)c.dec_layers * Mi * 3 * h->D);
+    rc = rc ? rc : dev_alloc(h, &h->hb, Mi * Dm);
+    rc = rc ? rc : dev_alloc(h, &h->qkv, Mi * 3 * h->Dv);
+    rc = rc ? rc : dev_alloc(h, &h->ctx, Mi * Dm);
+    rc = rc ? rc : dev_alloc(h, &h->ffn, Mi * Fm);
+    rc = rc ? rc : dev_alloc(h, &h->patches, (size_t)h->Pp * h->Kp);
     for (int i = 0; i < gitcap::NSLOT && !rc; ++i) {
         gitcap::Slot& sl = h->slots[i];
-        if (i == 0) sl.kv_img = h->kv_img;
-        else rc = rc ? rc : ws_alloc(h, &sl.kv_img, (size_t)c.dec_layers * Mi * 3 * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.sep_cnt, (size_t)h->Tmax + 1);
+        rc = rc ? rc : dev_alloc(h, &sl.kv_img, (size_t)c.dec_layers * Mi * 3 * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.sep_cnt, (size_t)h->Tmax + 1);
         // Text-row workspace (48 fp32 FC2 slabs + 12 per-head partials = 184 KB per row, the arg-max partials, ...): slot 0 also
         // serves the synchronous entry points, whose teacher-forced passes run rows x positions text rows at once; slots 1-3 only
         // ever run token loops of pipelined submissions -- one position per row and step -- and are sized for that.
         const size_t Mt = i == 0 ? (size_t)h->Mt : (size_t)pad_to(h->R, 16);
         sl.Mt = (int)Mt;
-        rc = rc ? rc : ws_alloc(h, &sl.xs, Mt * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.xs2, 2 * h->D);            // second copy of the residual rows for the one/two-row form
-        rc = rc ? rc : ws_alloc(h, &sl.slabs, (size_t)h->nslab_max * Mt * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.xsb, Mt * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.part, Mt * (size_t)c.dec_heads * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.row_cnt, Mt);
-        rc = rc ? rc : ws_alloc(h, &sl.fs, Mt * c.dec_ffn);
-        rc = rc ? rc : ws_alloc(h, &sl.amax_val, Mt * (size_t)((h->V + 15) / 16));
-        rc = rc ? rc : ws_alloc(h, &sl.amax_idx, Mt * (size_t)((h->V + 15) / 16));
-        rc = rc ? rc : ws_alloc(h, &sl.kv_txt, (size_t)c.dec_layers * h->R * h->Tmax * 3 * h->D);
-        rc = rc ? rc : ws_alloc(h, &sl.kv_txt2, (size_t)c.dec_layers * h->R * h->Tmax * 3 * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.xs, Mt * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.xs2, 2 * h->D);            // second copy of the residual rows for the one/two-row form
+        rc = rc ? rc : dev_alloc(h, &sl.slabs, (size_t)h->nslab_max * Mt * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.xsb, Mt * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.part, Mt * (size_t)c.dec_heads * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.row_cnt, Mt);
+        rc = rc ? rc : dev_alloc(h, &sl.fs, Mt * c.dec_ffn);
+        rc = rc ? rc : dev_alloc(h, &sl.amax_val, Mt * (size_t)((h->V + 15) / 16));
+        rc = rc ? rc : dev_alloc(h, &sl.amax_idx, Mt * (size_t)((h->V + 15) / 16));
+        rc = rc ? rc : dev_alloc(h, &sl.kv_txt, (size_t)c.dec_layers * h->R * h->Tmax * 3 * h->D);
+        rc = rc ? rc : dev_alloc(h, &sl.kv_txt2, (size_t)c.dec_layers * h->R * h->Tmax * 3 * h->D);
         {   // beam-search state: per slot, so that searches of different submissions may be in flight together
             const size_t R = h->R, T = (size_t)h->Tmax + 1, Bm = c.max_batch;
-            rc = rc ? rc : ws_alloc(h, &sl.beam.ids0, R * T);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.ids1, R * T);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.words, R);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.hyp_ids, Bm * T);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.beam_scores, R);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.hyp_score, Bm);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.src_rows, R);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.done, Bm);
-            rc = rc ? rc : ws_alloc(h, &sl.beam.hyp_len, Bm);
-            rc = rc ? rc : ws_alloc(h, &sl.beam_logits, R * (size_t)h->V);
-            rc = rc ? rc : ws_alloc(h, &sl.cand_scores, Bm * 16);
-            rc = rc ? rc : ws_alloc(h, &sl.cand_idx, Bm * 16);
-            rc = rc ? rc : ws_alloc(h, &sl.topk_scratch, beam_topk_scratch_bytes(c.max_batch, std::max(1, c.max_beams), h->V, 16));
+            rc = rc ? rc : dev_alloc(h, &sl.beam.ids0, R * T);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.ids1, R * T);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.words, R);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.hyp_ids, Bm * T);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.beam_scores, R);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.hyp_score, Bm);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.src_rows, R);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.done, Bm);
+            rc = rc ? rc : dev_alloc(h, &sl.beam.hyp_len, Bm);
+            rc = rc ? rc : dev_alloc(h, &sl.beam_logits, R * (size_t)h->V);
+            rc = rc ? rc : dev_alloc(h, &sl.cand_scores, Bm * 16);
+            rc = rc ? rc : dev_alloc(h, &sl.cand_idx, Bm * 16);
+            rc = rc ? rc : dev_alloc(h, &sl.topk_scratch, beam_topk_scratch_bytes(c.max_batch, std::max(1, c.max_beams), h->V, 16));
         }
-    }
-    if (!rc) {   // select slot 0
-        gitcap::Slot& n = h->slots[0];
-        h->sep_cnt = n.sep_cnt; h->xs = n.xs; h->xs2 = n.xs2; h->slabs = n.slabs; h->part = n.part; h->row_cnt = n.row_cnt;
-            h->amax_val = n.amax_val; h->amax_idx = n.amax_idx;
-        h->xsb = n.xsb; h->fs = n.fs; h->kv_txt = n.kv_txt; h->kv_txt2 = n.kv_txt2;
-        h->beam = n.beam; h->beam_logits = n.beam_logits; h->cand_scores = n.cand_scores; h->cand_idx = n.cand_idx; h->topk_scratch = n.topk_scratch;
     }
     if (!rc) {
         // plain non-blocking streams for the pipeline (stream priorities measured neutral and
@@ -846,7 +794,7 @@ int gitcap_create(const gitcap_config* cfg, int device, gitcap_t** out) {
         if (!ok) rc = fail(h, GITCAP_ERR_HIP, "create: stream/event creation failed");
     }
     if (rc) {
-        g_create_err = h->err;
+        create_err<gitcap>() = h->err;
         gitcap_destroy(h);
         return rc;
     }
@@ -855,7 +803,7 @@ int gitcap_create(const gitcap_config* cfg, int device, gitcap_t** out) {
     for (auto& kv : exp) {
         DevTensor t;
         t.shape = kv.second;
-        t.bf16 = is_gemm_weight(kv.first);
+        t.kind = is_gemm_weight(kv.first) ? 1 : 0;
         h->w[kv.first] = t;
     }
     *out = h;
@@ -877,7 +825,7 @@ void gitcap_destroy(gitcap_t* h) {
     if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
     if (h->win_ev_read) (void)hipEventDestroy(h->win_ev_read);
     if (h->win_ring) (void)hipFree(h->win_ring);
-    for (void* p : h->allocs) (void)hipFree(p);
+    free_allocs(*h);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
     for (auto& kv : h->w)
         if (kv.second.p) (void)hipFree(kv.second.p);
@@ -890,16 +838,14 @@ void gitcap_destroy(gitcap_t* h) {
 
 int gitcap_load_tensor(gitcap_t* h, const char* name, const float* data, const int64_t* shape, int rank) {
     if (!h || !name || !data || !shape) return fail(h, GITCAP_ERR_ARG, "load_tensor: null argument");
-    auto it = h->w.find(name);
-    if (it == h->w.end()) return fail(h, GITCAP_ERR_ARG, std::string("load_tensor: unknown tensor '") + name + "'");
+    std::string why;
+    DevTensor* tp = find_tensor(h->w, name, shape, rank, "load_tensor", why);
+    if (!tp) return fail(h, GITCAP_ERR_ARG, why);
     GUARD(h);
-    DevTensor& t = it->second;
-    if ((int)t.shape.size() != rank) return fail(h, GITCAP_ERR_ARG, std::string("load_tensor: rank mismatch for ") + name);
-    for (int i = 0; i < rank; ++i)
-        if (t.shape[i] != shape[i]) return fail(h, GITCAP_ERR_ARG, std::string("load_tensor: shape mismatch for ") + name);
+    DevTensor& t = *tp;
     const int64_t rows = rank == 2 ? shape[0] : 1, cols = rank == 2 ? shape[1] : shape[0];
     if (t.p) { (void)hipFree(t.p); t.p = nullptr; h->weight_bytes -= t.bytes; t.bytes = 0; }
-    if (t.bf16 && h->fp8) {
+    if (t.kind == 1 && h->fp8) {
         // e4m3 storage: one power-of-two scale per row (the smallest that maps the row's amax into +-448), values
         // must already BE e4m3 x 2^k (gitcap.weights.quantize_weights_fp8): this is a lossless re-encoding
         const int64_t prow = pad_to((int)rows, 16), pcol = (strcmp(name, "enc.patch_w") == 0) ? h->Kp : cols;
@@ -920,16 +866,10 @@ int gitcap_load_tensor(gitcap_t* h, const char* name, const float* data, const i
         t.bytes = (int64_t)(q.size() + sc.size() * 4);
         h->weight_bytes += t.bytes;
         HIP_OK(h, hipMemcpy(t.p, q.data(), q.size(), hipMemcpyHostToDevice));
-    } else if (t.bf16) {
+    } else if (t.kind == 1) {
         // GEMM weights: bf16, rows padded to 16 (zero rows), patch-embed K padded to a multiple of 64
-        const int64_t prow = pad_to((int)rows, 16), pcol = (strcmp(name, "enc.patch_w") == 0) ? h->Kp : cols;
-        std::vector<uint16_t> hb((size_t)prow * pcol, 0);
-        for (int64_t r = 0; r < rows; ++r)
-            for (int64_t k = 0; k < cols; ++k) hb[(size_t)r * pcol + k] = host_f2bf(data[(size_t)r * cols + k]);
-        HIP_OK(h, hipMalloc(&t.p, hb.size() * 2));
-        t.bytes = (int64_t)hb.size() * 2;
+        if (int rc = upload_bf16_panel(h, t, data, rows, cols, 16, (strcmp(name, "enc.patch_w") == 0) ? h->Kp : cols)) return rc;
         h->weight_bytes += t.bytes;
-        HIP_OK(h, hipMemcpy(t.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
     } else {
         const size_t bytes = (size_t)rows * cols * 4;
         HIP_OK(h, hipMalloc(&t.p, bytes));
@@ -957,23 +897,23 @@ int gitcap_finalize_weights(gitcap_t* h) {
     };
     if (h->fp8) {
         for (auto& kv : h->w)
-            if (kv.second.bf16 && !h->wscale.count(kv.first))
+            if (kv.second.kind == 1 && !h->wscale.count(kv.first))
                 return fail(h, GITCAP_ERR_STATE, "finalize: '" + kv.first + "' was loaded before gitcap_set_weight_storage(e4m3)");
         if (!h->wstage) {          // bf16 staging panel of the big-tile GEMMs: the largest weight matrix
             size_t mx = 0;
             for (auto& kv : h->w)
-                if (kv.second.bf16 && kv.first != "head.w") {
+                if (kv.second.kind == 1 && kv.first != "head.w") {
                     const size_t cols = kv.first == "enc.patch_w" ? (size_t)h->Kp : (size_t)kv.second.shape[1];
                     mx = std::max(mx, (size_t)pad_to((int)kv.second.shape[0], 16) * cols);
                 }
-            int rc = ws_alloc(h, &h->wstage, mx);
+            int rc = dev_alloc(h, &h->wstage, mx);
             if (rc) return rc;
             auto pe = [](int64_t r, int64_t k) { return (size_t)pad_to((int)r, 16) * (size_t)k; };
             const gitcap_config& c = h->c;
             const size_t enc_l = pe(3 * c.enc_width, c.enc_width) + pe(c.enc_width, c.enc_width) + 2 * pe(c.enc_ffn, c.enc_width);
             const size_t dec_l = pe(3 * c.dec_width, c.dec_width) + pe(c.dec_width, c.dec_width) + 2 * pe(c.dec_ffn, c.dec_width);
             h->lstage_elems = std::max(enc_l, dec_l);
-            if ((rc = ws_alloc(h, &h->lstage, h->lstage_elems))) return rc;
+            if ((rc = dev_alloc(h, &h->lstage, h->lstage_elems))) return rc;
         }
     }
     h->patch_w = Wt("enc.patch_w"); h->cls = F("enc.cls"); h->pos = F("enc.pos");
@@ -1050,7 +990,7 @@ int gitcap_encode(gitcap_t* h, const float* frames, int B, int F, float* visual_
 // The encoder half of the image pass: B x F frames (checked by the caller) through patch gather, the ViT blocks and ln_post.
 // Its output: the bf16 rows in h->hb (the decoder input) and, when ln_f32 != nullptr, the fp32 rows [B*F*N][Dv] there; addv
 // (nullable) = the temporal embedding, added to both inside the ln_post epilogue (frame = (row / N) % F).  Touches the encoder
-// workspace only (not the image K/V, the text rows or have_image).  taps: gitcap_dbg_enc_tap may copy the residual stream.
+// workspace only (not the image K/V, the text rows or the slot's `have`).  taps: gitcap_dbg_enc_tap may copy the residual stream.
 static int encode_frames(gitcap* h, FrameSrc src, int B, int F, float* ln_f32, const float* addv, bool taps, hipStream_t stream) {
     int rc;
     hipStream_t s = stream;
@@ -1073,7 +1013,7 @@ static int encode_frames(gitcap* h, FrameSrc src, int B, int F, float* ln_f32, c
         ProfScope ps(h, GITCAP_PROF_GEMM, s, 2.0 * P * Dv * (3.0 * c.patch_size * c.patch_size), 2.0 * P * h->Kp + 2.0 * Dv * h->Kp + 4.0 * P * Dv);
         a.A = h->patches; a.lda = h->Kp; a.bias = nullptr; a.M = Pp; a.N = Dv; a.K = h->Kp;
         a.out = h->x; a.ldo = Dv; a.pos = h->pos; a.tokens_per_frame = N; a.patches_per_frame = h->G * h->G; a.valid_rows = P;
-        HIP_OK(h, launch_gemm_auto(h, a, EPI_PATCH_F32, s, P, h->Pp));
+        HIP_OK(h, launch_gemm_auto(h, a, EPI_PATCH_F32, s));
     }
     // ln_pre (fp32, in place: the residual stream) and the first block's LN1 (bf16: the first q|k|v operand) in one pass;
     // the same pass supplies the CLS rows (cls + pos[0], row frame * N) that the patch GEMM does not write
@@ -1117,25 +1057,28 @@ static int encode_frames(gitcap* h, FrameSrc src, int B, int F, float* ln_f32, c
             ProfScope ps(h, GITCAP_PROF_ATTN_FULL, s, 4.0 * nf * c.enc_heads * (double)N * N * 64, 0.0);
             HIP_OK(h, launch_attn_full(h->qkv, h->ctx, nf, N, c.enc_heads, s));
         }
+        LnOpts proj; proj.ln8 = f8 ? h->hb8 : nullptr;
         if ((rc = gemm_ln(h, s, false, h->ctx, Dv, L.projw, L.projb, Mp, Dv, Dv, h->x, h->x, L.ln2w, L.ln2b, c.enc_ln_eps, rows,
-                          h->hb, nullptr, nullptr, 1, 1, nullptr, f8 ? h->hb8 : nullptr))) return rc;
+                          h->hb, nullptr, proj))) return rc;
         // FC1 + QuickGELU, FC2 (+ the next LayerNorm): bf16, or (compute = fp8_ffn) on e4m3 operands at twice the MFMA rate
         const bf16_t* fc2_in = f8 ? (const bf16_t*)h->ffn8 : h->ffn;
         if (f8) rc = gemm_f8(h, s, EPI_BIAS_QGELU_F8, h->hb8, Dv, L.fc1w, L.fc1b, rows, Mp, c.enc_ffn, Dv, h->ffn8, c.enc_ffn);
         else rc = gemm(h, s, EPI_BIAS_QGELU_BF16, h->hb, Dv, L.fc1w, L.fc1b, rows, Mp, c.enc_ffn, Dv, h->ffn, c.enc_ffn);
         if (rc) return rc;
+        LnOpts fc2; fc2.f8in = f8;
         if (i + 1 < c.enc_layers) {
             const EncLayer& Nx = h->enc[i + 1];
             if ((rc = gemm_ln(h, s, false, fc2_in, c.enc_ffn, L.fc2w, L.fc2b, Mp, Dv, c.enc_ffn, h->x, h->x, Nx.ln1w, Nx.ln1b,
-                              c.enc_ln_eps, rows, h->hb, nullptr, nullptr, 1, 1, nullptr, nullptr, f8))) return rc;
+                              c.enc_ln_eps, rows, h->hb, nullptr, fc2))) return rc;
             HIP_OK(h, tap(i + 1));
         } else {
             // the last block's FC2 is followed by ln_post (+ per-frame temporal embedding, model.py:380); frames of a clip are
             // already adjacent rows, so the concat along tokens (model.py:382) is the identity on this layout.  x itself is
             // not needed any more.  The fp32 visual features (58 MB at B=16, F=6) are written straight into the caller's
             // buffer and only when asked for; the decoder consumes the bf16 copy.
+            fc2.addv = addv; fc2.add_div = N; fc2.add_mod = F; fc2.ln_f32 = ln_f32;
             if ((rc = gemm_ln(h, s, false, fc2_in, c.enc_ffn, L.fc2w, L.fc2b, Mp, Dv, c.enc_ffn, nullptr, h->x, h->ln_post_w, h->ln_post_b,
-                              c.enc_ln_eps, rows, h->hb, nullptr, addv, N, F, ln_f32, nullptr, f8))) return rc;
+                              c.enc_ln_eps, rows, h->hb, nullptr, fc2))) return rc;
         }
     }
     return 0;
@@ -1144,7 +1087,7 @@ static int encode_frames(gitcap* h, FrameSrc src, int B, int F, float* ln_f32, c
 static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream) {
     int rc = src.u8 ? check_frames(h, src.u8, B, F, true) : check_frames(h, src.f32, B, F);
     if (rc) return rc;
-    h->have_image = false;
+    cur(h).have = false;
     if ((rc = encode_frames(h, src, B, F, visual_out, h->c.num_frames > 0 ? h->temporal : nullptr, true, stream))) return rc;
     return image_prefix(h, B, F * h->N, stream);
 }
@@ -1159,7 +1102,7 @@ int gitcap_set_visual(gitcap_t* h, const float* visual, int B, int S_img, void* 
     if (B > h->c.max_batch || S_img > h->Smax) return fail(h, GITCAP_ERR_ARG, "set_visual: B/S_img exceed the sizes the handle was created for");
     if (((uintptr_t)visual & 15) != 0) return fail(h, GITCAP_ERR_ARG, "set_visual: visual must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    h->have_image = false;
+    cur(h).have = false;
     HIP_OK(h, join_async(h, s));
     HIP_OK(h, launch_cast_bf16(visual, h->hb, (int64_t)B * S_img * h->Dv, s));
     return image_prefix(h, B, S_img, s);
@@ -1176,7 +1119,7 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
                         (hipStream_t)stream);
 }
 
-// token steps 0 .. max_len-1 of `rows` text rows (the image K/V of their clips at h->kv_img), ids at ids_out (row pitch ld)
+// token steps 0 .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
 static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s) {
     const bool chain = text_chain_ok(h, rows, 1);
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
@@ -1185,7 +1128,7 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
     for (int t = 0; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
         const bool next = chain && t + 1 < max_len && t + 1 < h->c.max_text_pos;
-        const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, h->sep_cnt, t, s, have_rows, next);
+        const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next);
         if (rc) return rc;
         have_rows = next;
     }
@@ -1198,12 +1141,13 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
 // different streams do not overlap each other the way one chain overlaps an image pass.  Removed.)
 static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
     const int ld = max_len + 1;
+    gitcap::Slot& sl = cur(h);
     int rc;
     // CLS start tokens [B,1] (model.py:171)
     HIP_OK(h, launch_fill_i64(ids_out, ld, B, h->c.cls_token_id, s));
-    HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
+    HIP_OK(h, hipMemsetAsync(sl.sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
     if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s))) return rc;
-    if (steps_out) HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, steps_out, s));
+    if (steps_out) HIP_OK(h, launch_finish_steps(sl.sep_cnt, B, max_len, stop, steps_out, s));
     return 0;
 }
 
@@ -1303,25 +1247,26 @@ static int beam_check(gitcap* h, int beams, int max_steps, int per_node_beam_siz
 static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                      int64_t* decoded_out, float* logprobs_out, float* step_logits_out, hipStream_t s) {
     const int rows = B * beams, K = beams * per_node_beam_size, V = h->c.vocab_size, L = max_steps;
+    gitcap::Slot& sl = cur(h);
     int rc;
-    HIP_OK(h, launch_beam_init(h->beam, B, beams, L, h->c.cls_token_id, s));
+    HIP_OK(h, launch_beam_init(sl.beam, B, beams, L, h->c.cls_token_id, s));
     // while cur_len < max_length (model.py:518): the token at position cur_len-1 is decoded, candidates for
     // position cur_len are ranked, bookkept and the text K/V rows follow their beams -- no host round trip
     for (int cur_len = 1, cur = 0; cur_len < L; ++cur_len, cur ^= 1) {
         const int t = cur_len - 1;
         if (t > 0) {                                                         // rows continue beam src_rows[r]: all layers, one launch
-            HIP_OK(h, launch_gather_txt_rows(h->kv_txt, h->kv_txt2, h->beam.src_rows, rows, t, h->Tmax, 3 * h->D, h->c.dec_layers,
+            HIP_OK(h, launch_gather_txt_rows(sl.kv_txt, sl.kv_txt2, sl.beam.src_rows, rows, t, h->Tmax, 3 * h->D, h->c.dec_layers,
                                              (size_t)h->R * h->Tmax * 3 * h->D, s));
-            std::swap(h->kv_txt, h->kv_txt2);
+            std::swap(sl.kv_txt, sl.kv_txt2);
         }
-        float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : h->beam_logits;
-        rc = text_forward(h, h->beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
+        float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : sl.beam_logits;
+        rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
-        HIP_OK(h, launch_beam_topk(lg, V, h->beam.beam_scores, B, beams, V, K, h->cand_scores, h->cand_idx, h->topk_scratch, s));
-        HIP_OK(h, launch_beam_step(h->beam, h->cand_scores, h->cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
+        HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, B, beams, V, K, sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+        HIP_OK(h, launch_beam_step(sl.beam, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
                                    length_penalty, cur, s));
     }
-    HIP_OK(h, launch_beam_finish(h->beam, B, L, h->c.sep_token_id, decoded_out, logprobs_out, s));
+    HIP_OK(h, launch_beam_finish(sl.beam, B, L, h->c.sep_token_id, decoded_out, logprobs_out, s));
     return 0;
 }
 
@@ -1448,7 +1393,7 @@ static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
     select_slot(h, 0);
     HIP_OK(h, join_async(h, s));
     HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
-    h->have_image = false;
+    cur(h).have = false;
     {
         const double rows = (double)B * F * N;
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, rows * Dv * (4.0 + 2.0 + (visual_out ? 4.0 : 0.0)));
@@ -1491,10 +1436,11 @@ int gitcap_reorder_rows(gitcap_t* h, const int32_t* src_rows, int rows, int t_le
     if (!src_rows || rows <= 0 || rows > h->R || t_len < 0 || t_len > h->Tmax)
         return fail(h, GITCAP_ERR_ARG, "reorder_rows: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    gitcap::Slot& sl = cur(h);       // slot 0: every submission leaves it selected
     HIP_OK(h, join_async(h, s));
-    HIP_OK(h, launch_gather_txt_rows(h->kv_txt, h->kv_txt2, src_rows, rows, t_len, h->Tmax, 3 * h->D, h->c.dec_layers,
+    HIP_OK(h, launch_gather_txt_rows(sl.kv_txt, sl.kv_txt2, src_rows, rows, t_len, h->Tmax, 3 * h->D, h->c.dec_layers,
                                      (size_t)h->R * h->Tmax * 3 * h->D, s));
-    std::swap(h->kv_txt, h->kv_txt2);
+    std::swap(sl.kv_txt, sl.kv_txt2);
     return 0;
 }
 
@@ -1714,12 +1660,12 @@ int gitcap_hidden_states_enable(gitcap_t* h, int enable) {
     select_slot(h, 0);
     if (enable && !h->hid_img) {
         const size_t n = (size_t)h->c.dec_layers + 1;
-        int rc = ws_alloc(h, &h->hid_img, n * h->Mi * h->D);
-        rc = rc ? rc : ws_alloc(h, &h->hid_txt, n * h->Mt * h->D);
+        int rc = dev_alloc(h, &h->hid_img, n * h->Mi * h->D);
+        rc = rc ? rc : dev_alloc(h, &h->hid_txt, n * h->Mt * h->D);
         if (rc) return rc;
     }
     h->want_hidden = enable != 0;
-    h->have_image = false;          // the image rows of the last layer are only computed while this is on
+    cur(h).have = false;     // the image rows of the last layer are only computed while this is on
     return 0;
 }
 
@@ -1727,8 +1673,9 @@ int gitcap_hidden_states_read(gitcap_t* h, int B, int S_img, int T, float* out, 
     if (!h || !out) return fail(h, GITCAP_ERR_ARG, "hidden_states_read: null argument");
     GUARD(h);
     select_slot(h, 0);
-    if (!h->want_hidden || !h->have_image) return fail(h, GITCAP_ERR_STATE, "hidden_states_read: enable, encode and run a prefix (t0 = 0) first");
-    if (B != h->cur_B || S_img != h->cur_S || T != h->hid_T || T <= 0)
+    const gitcap::Slot& sl = cur(h);
+    if (!h->want_hidden || !sl.have) return fail(h, GITCAP_ERR_STATE, "hidden_states_read: enable, encode and run a prefix (t0 = 0) first");
+    if (B != sl.B || S_img != sl.S || T != h->hid_T || T <= 0)
         return fail(h, GITCAP_ERR_ARG, "hidden_states_read: B / S_img / T differ from the last encode + text_forward");
     HIP_OK(h, launch_gather_hidden(h->hid_img, h->hid_txt, out, h->c.dec_layers + 1, B, S_img, T, h->D, (size_t)h->Mi * h->D,
                                    (size_t)h->Mt * h->D, (hipStream_t)stream));
@@ -1739,7 +1686,7 @@ int gitcap_set_weight_storage(gitcap_t* h, int storage) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "set_weight_storage: null handle");
     if (storage != GITCAP_W_BF16 && storage != GITCAP_W_FP8_E4M3) return fail(h, GITCAP_ERR_ARG, "set_weight_storage: unknown storage");
     for (auto& kv : h->w)
-        if (kv.second.loaded && kv.second.bf16) return fail(h, GITCAP_ERR_STATE, "set_weight_storage: call it before the first gitcap_load_tensor");
+        if (kv.second.loaded && kv.second.kind == 1) return fail(h, GITCAP_ERR_STATE, "set_weight_storage: call it before the first gitcap_load_tensor");
     h->fp8 = storage == GITCAP_W_FP8_E4M3;
     return 0;
 }
@@ -1752,14 +1699,12 @@ int gitcap_set_kv_cache(gitcap_t* h, int mode) {
     select_slot(h, 0);
     if (mode == GITCAP_KV_V_E4M3 && !h->slots[0].v8_img) {
         for (auto& sl : h->slots) {
-            int rc = ws_alloc(h, &sl.v8_img, (size_t)h->c.dec_layers * h->Mi * h->D);
-            rc = rc ? rc : ws_alloc(h, &sl.vs_img, (size_t)h->c.dec_layers * h->Mi * h->c.dec_heads);
+            int rc = dev_alloc(h, &sl.v8_img, (size_t)h->c.dec_layers * h->Mi * h->D);
+            rc = rc ? rc : dev_alloc(h, &sl.vs_img, (size_t)h->c.dec_layers * h->Mi * h->c.dec_heads);
             if (rc) return rc;
         }
-        h->v8_img = h->slots[0].v8_img; h->vs_img = h->slots[0].vs_img;
     }
     h->kv_v8 = mode == GITCAP_KV_V_E4M3;
-    h->have_image = false;
     for (auto& sl : h->slots) sl.have = false;
     return 0;
 }
@@ -1776,15 +1721,15 @@ int gitcap_set_compute(gitcap_t* h, int compute) {
             return fail(h, GITCAP_ERR_ARG, "set_compute(fp8_ffn): widths must be 768 or 1024 and the FFN widths multiples of 256");
         if (!h->hb8) {
             const size_t Dm = std::max(h->Dv, h->D), Fm = std::max(c.enc_ffn, c.dec_ffn);
-            int rc = ws_alloc(h, &h->hb8, (size_t)h->Mi * Dm);
-            rc = rc ? rc : ws_alloc(h, &h->ffn8, (size_t)h->Mi * Fm);
-            rc = rc ? rc : ws_alloc(h, &h->f8_sat, 1);
+            int rc = dev_alloc(h, &h->hb8, (size_t)h->Mi * Dm);
+            rc = rc ? rc : dev_alloc(h, &h->ffn8, (size_t)h->Mi * Fm);
+            rc = rc ? rc : dev_alloc(h, &h->f8_sat, 1);
             if (rc) return rc;
         }
     }
     HIP_OK(h, hipDeviceSynchronize());          // not between the launches of a submission in flight
     h->f8ffn = compute == GITCAP_COMPUTE_FP8_FFN;
-    h->have_image = false;
+    cur(h).have = false;
     return 0;
 }
 
@@ -1796,7 +1741,7 @@ int gitcap_set_fp8_scale(gitcap_t* h, float scale) {
     GUARD(h);
     HIP_OK(h, hipDeviceSynchronize());          // not between the launches of a submission in flight
     h->f8_scale = scale;
-    h->have_image = false;
+    cur(h).have = false;
     return 0;
 }
 

@@ -55,6 +55,17 @@ int main() {
     CHECK(names.size() == shapes.size() && shapes.size() == 7 + 12 * 12 + 1 + 4 + 4 + 6 * 12 + 2);
     CHECK(gemm_w == 1 + 12 * 4 + 1 + 6 * 4 + 1);
     CHECK(!is_gemm_weight("enc.L0.qkv.b") && !is_gemm_weight("w") && is_gemm_weight("dec.L5.ao.w"));
+    // tensor lookup of the loaders: unknown name, rank mismatch, shape mismatch (each with the caller's prefix), and a hit
+    {
+        std::map<std::string, DevTensor> table;
+        for (auto& kv : shapes) table[kv.first].shape = kv.second;
+        std::string err;
+        const int64_t ok2[2] = {768, 768}, bad2[2] = {768, 767};
+        CHECK(!find_tensor(table, "dec.L9.ao.w", ok2, 2, "load_tensor", err) && err == "load_tensor: unknown tensor 'dec.L9.ao.w'");
+        CHECK(!find_tensor(table, "dec.L5.ao.w", ok2, 1, "student_load_tensor", err) && err == "student_load_tensor: rank mismatch for dec.L5.ao.w");
+        CHECK(!find_tensor(table, "dec.L5.ao.w", bad2, 2, "tinyvit_load_tensor", err) && err == "tinyvit_load_tensor: shape mismatch for dec.L5.ao.w");
+        CHECK(find_tensor(table, "dec.L5.ao.w", ok2, 2, "load_tensor", err) == &table["dec.L5.ao.w"]);
+    }
     // tickets: four slots, a ticket is waitable until its slot is handed on
     CHECK(ticket_slot(5, 4) == 1 && ticket_waitable(5, 6, 4) && ticket_waitable(2, 6, 4) && !ticket_waitable(1, 6, 4));
     CHECK(!ticket_waitable(6, 6, 4) && !ticket_waitable(-1, 6, 4));

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -119,6 +120,27 @@ inline bool is_gemm_weight(const std::string& n) {
     if (n == "enc.patch_w" || n == "vproj.w" || n == "head.w") return true;
     auto ends = [&](const char* s) { size_t l = strlen(s); return n.size() >= l && n.compare(n.size() - l, l, s) == 0; };
     return ends("qkv.w") || ends("proj.w") || ends("fc1.w") || ends("fc2.w") || ends("ao.w");
+}
+
+// One entry of a handle's weight table (GIT, student, TinyViT): what *_load_tensor expects and what it uploaded.
+struct DevTensor {
+    void* p = nullptr;
+    std::vector<int64_t> shape;   // logical (unpadded) shape
+    int kind = 0;                 // 0 fp32 as loaded, 1 GEMM weight (bf16 panel, or e4m3 + row scales), 2 depthwise [9][C] (TinyViT)
+    bool loaded = false;
+    int64_t bytes = 0;            // device bytes held (incl. row scales)
+};
+// The shared head of the three *_load_tensor entry points: the table's entry for `name` once rank and shape agree with it,
+// else nullptr and the message in `err`, led by the caller's prefix ("load_tensor", "student_load_tensor", ...).
+inline DevTensor* find_tensor(std::map<std::string, DevTensor>& table, const char* name, const int64_t* shape, int rank,
+                              const char* prefix, std::string& err) {
+    auto it = table.find(name);
+    if (it == table.end()) { err = std::string(prefix) + ": unknown tensor '" + name + "'"; return nullptr; }
+    DevTensor& t = it->second;
+    if ((int)t.shape.size() != rank) { err = std::string(prefix) + ": rank mismatch for " + name; return nullptr; }
+    for (int i = 0; i < rank; ++i)
+        if (t.shape[i] != shape[i]) { err = std::string(prefix) + ": shape mismatch for " + name; return nullptr; }
+    return &t;
 }
 
 // Pipeline bookkeeping (gitcap_greedy_submit / _wait): submission t uses slot t % nslot; a ticket can be waited for

@@ -1,4 +1,5 @@
-// Host-side helpers shared by the C-ABI translation units (gitcap.hip, student.hip).
+// Host-side helpers shared by the C-ABI translation units (gitcap.hip, student.hip, tinyvit.hip): the part of a handle the
+// three have in common and the plumbing that goes with it (error text, device selection, tracked allocations, weight upload).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,15 +7,37 @@
 
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
-struct DevTensor {
-    void* p = nullptr;
-    std::vector<int64_t> shape;   // logical (unpadded) shape
-    bool bf16 = false;            // a GEMM weight (stored as bf16, or as e4m3 + row scales)
-    bool loaded = false;
-    int64_t bytes = 0;            // device bytes held (incl. row scales)
+// What gitcap, gitcap_student and gitcap_tinyvit derive from.
+struct HandleCore {
+    int device = 0;
+    mutable std::string err;        // *_last_error(handle)
+    std::vector<void*> allocs;      // device buffers of dev_alloc, freed by free_allocs
+    int64_t ws_bytes = 0;           // their bytes
 };
+
+// *_last_error(NULL): the message of the last failed create or null-handle call of handle type H (one string per type)
+template <class H>
+std::string& create_err() {
+    static std::string s;
+    return s;
+}
+
+// Records the message on the handle, or (h == nullptr: spell the type, fail<gitcap>(nullptr, ...)) as H's create error.
+template <class H>
+int fail(const H* h, int code, const std::string& msg) {
+    (h ? h->err : create_err<H>()) = msg;
+    return code;
+}
+
+#define HIP_OK(h, expr)                                                                               \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess)                                                                         \
+            return fail(h, GITCAP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+    } while (0)
 
 // Makes a handle's device current for the duration of an entry point and restores the caller's.
 struct DeviceGuard {
@@ -26,3 +49,41 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+#define GUARD(h) DeviceGuard guard_((h)->device); if (!guard_.ok) return fail(h, GITCAP_ERR_HIP, "cannot select the handle's device")
+
+// A zero-filled device buffer of `count` T that lives as long as the handle.
+template <class H, typename T>
+int dev_alloc(H* h, T** p, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = count * sizeof(T);
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
+    e = hipMemset(q, 0, bytes);
+    if (e != hipSuccess) return fail(h, GITCAP_ERR_HIP, std::string("hipMemset workspace: ") + hipGetErrorString(e));
+    h->allocs.push_back(q);
+    h->ws_bytes += (int64_t)bytes;
+    *p = (T*)q;
+    return 0;
+}
+
+inline void free_allocs(HandleCore& c) {
+    for (void* p : c.allocs) (void)hipFree(p);
+    c.allocs.clear();
+}
+
+// A GEMM weight's upload: fp32 [rows][cols] -> t.p = bf16 [rows padded to a multiple of row_pad][pitch], zero padded
+// (pitch >= cols), t.bytes = its size.  On failure the tensor holds nothing (t.p null, not loaded, t.bytes untouched).
+template <class H>
+int upload_bf16_panel(H* h, DevTensor& t, const float* data, int64_t rows, int64_t cols, int row_pad, int64_t pitch) {
+    std::vector<uint16_t> hb((size_t)pad_to((int)rows, row_pad) * pitch, 0);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t k = 0; k < cols; ++k) hb[(size_t)(r * pitch + k)] = host_f2bf(data[r * cols + k]);
+    HIP_OK(h, hipMalloc(&t.p, hb.size() * 2));
+    const hipError_t e = hipMemcpy(t.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(t.p); t.p = nullptr; t.loaded = false;
+        return fail(h, GITCAP_ERR_HIP, std::string("hipMemcpy(t.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice): ") + hipGetErrorString(e));
+    }
+    t.bytes = (int64_t)hb.size() * 2;
+    return 0;
+}

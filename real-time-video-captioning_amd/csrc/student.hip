@@ -165,15 +165,11 @@ __global__ __launch_bounds__(64) void student_window_gather_kernel(const bf16_t*
     for (int i = threadIdx.x; i < n8; i += 64) dst[i] = src[i];
 }
 
-struct gitcap_student {
+struct gitcap_student : HandleCore {
     gitcap_student_config c;
-    int device = 0;
-    mutable std::string err;
     std::map<std::string, DevTensor> w;
     bool finalized = false, have_memory = false;
     int D = 0, H = 0, hd = 0, FF = 0, L = 0, V = 0, F = 0, R = 0, Tmax = 0, Mt = 0, cur_B = 0;
-    std::vector<void*> allocs;
-    int64_t ws_bytes = 0;
     // workspace: text rows
     float *xf = nullptr, *xf2 = nullptr, *slabs = nullptr, *amax_val = nullptr;
     int* amax_idx = nullptr;
@@ -209,21 +205,6 @@ struct gitcap_student {
 
 namespace {
 
-std::string g_student_create_err;
-
-int sfail(const gitcap_student* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_student_create_err = msg;
-    return code;
-}
-
-#define S_HIP_OK(h, expr)                                                                             \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return sfail(h, GITCAP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-    } while (0)
-#define S_GUARD(h) DeviceGuard guard_((h)->device); if (!guard_.ok) return sfail(h, GITCAP_ERR_HIP, "cannot select the handle's device")
-
 bool student_is_gemm_weight(const std::string& n) {
     auto ends = [&](const char* s) { size_t l = strlen(s); return n.size() >= l && n.compare(n.size() - l, l, s) == 0; };
     return n == "linear.weight" || ends("in_proj_weight") || ends("out_proj.weight") || ends("linear1.weight") || ends("linear2.weight");
@@ -249,26 +230,12 @@ void expected_shapes(const gitcap_student_config& c, std::vector<std::pair<std::
     add("linear.bias", {V});
 }
 
-template <typename T>
-int s_alloc(gitcap_student* h, T** p, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = count * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return sfail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-    e = hipMemset(q, 0, bytes);
-    if (e != hipSuccess) return sfail(h, GITCAP_ERR_HIP, std::string("hipMemset workspace: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    h->ws_bytes += (int64_t)bytes;
-    *p = (T*)q;
-    return 0;
-}
-
 int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx, const bf16_t* W, const float* bias, int M,
             int N, int K, void* out, int ldo, int T = 1, int row_stride = 1, int row_off = 0) {
     SkinnyArgs a{};
     a.X = X; a.ldx = ldx; a.W = W; a.bias = bias; a.M = M; a.N = N; a.K = K; a.out = out; a.ldo = ldo;
     a.T = T; a.row_stride = row_stride; a.row_off = row_off;
-    S_HIP_OK(h, launch_skinny(a, epi, s));
+    HIP_OK(h, launch_skinny(a, epi, s));
     return 0;
 }
 
@@ -276,15 +243,15 @@ int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx,
 int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int t0, int T, float* logits_out,
                  int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s) {
     const gitcap_student_config& c = h->c;
-    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student: weights not finalized");
-    if (!h->have_memory) return sfail(h, GITCAP_ERR_STATE, "student: decoder called before set_memory");
-    if (!ids || rows <= 0 || T <= 0 || t0 < 0) return sfail(h, GITCAP_ERR_ARG, "student: bad arguments");
-    if (rows != h->cur_B) return sfail(h, GITCAP_ERR_ARG, "student: rows != rows of the current memory");
-    if (t0 + T > h->Tmax) return sfail(h, GITCAP_ERR_ARG, "student: t0+T exceeds max_text_len+1");
-    if (t0 + T > c.max_pos) return sfail(h, GITCAP_ERR_ARG, "student: position exceeds the positional table");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
+    if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student: decoder called before set_memory");
+    if (!ids || rows <= 0 || T <= 0 || t0 < 0) return fail(h, GITCAP_ERR_ARG, "student: bad arguments");
+    if (rows != h->cur_B) return fail(h, GITCAP_ERR_ARG, "student: rows != rows of the current memory");
+    if (t0 + T > h->Tmax) return fail(h, GITCAP_ERR_ARG, "student: t0+T exceeds max_text_len+1");
+    if (t0 + T > c.max_pos) return fail(h, GITCAP_ERR_ARG, "student: position exceeds the positional table");
     const int D = h->D, M = rows * T;
     int rc;
-    S_HIP_OK(h, launch_student_embed(ids, ld_ids, rows, T, t0, h->embed, h->pe, D, h->V, h->xf, h->xb, s));
+    HIP_OK(h, launch_student_embed(ids, ld_ids, rows, T, t0, h->embed, h->pe, D, h->V, h->xf, h->xb, s));
     const size_t kvs_layer = (size_t)h->R * h->Tmax * 3 * D, mem_layer = (size_t)h->R * h->F * 2 * D;
     // Each post-LN sub-layer is split-K partial slabs -> sum + bias + residual + LayerNorm.  With one or two rows (the webcam
     // case) that row kernel is not launched: the projection that consumes its output computes the rows itself (skinny.hip
@@ -300,7 +267,7 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         a.T = Tq; a.row_stride = row_stride; a.row_off = row_off;
         a.ln.kind = 1; a.ln.slabs = h->slabs; a.ln.nslab = pend.nslab; a.ln.bias = pend.bias; a.ln.resid = xcur;
         a.ln.g = pend.g; a.ln.b = pend.b; a.ln.eps = h->c.ln_eps; a.ln.xf = xalt;
-        S_HIP_OK(h, launch_skinny(a, epi, s));
+        HIP_OK(h, launch_skinny(a, epi, s));
         std::swap(xcur, xalt);
         pend.on = false;
         return 0;
@@ -309,9 +276,9 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
     auto dense_ln = [&](const bf16_t* X, int K, const bf16_t* W, const float* bias, const float* g, const float* b, bool defer) -> int {
         SkinnyArgs a{};
         a.X = X; a.ldx = K; a.W = W; a.M = M; a.N = D; a.K = K; a.out = h->slabs; a.ldo = D; a.T = 1; a.row_stride = 1;
-        S_HIP_OK(h, launch_skinny_splitk(a, s));
+        HIP_OK(h, launch_skinny_splitk(a, s));
         if (rows_pro && defer) { pend = {true, bias, g, b, skinny_ksplit(K)}; return 0; }
-        S_HIP_OK(h, launch_ln_reduce(h->slabs, skinny_ksplit(K), bias, xcur, g, b, h->c.ln_eps, M, D, xcur, h->xb, s));
+        HIP_OK(h, launch_ln_reduce(h->slabs, skinny_ksplit(K), bias, xcur, g, b, h->c.ln_eps, M, D, xcur, h->xb, s));
         return 0;
     };
     for (int l = 0; l < h->L; ++l) {
@@ -321,13 +288,13 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         if ((rc = proj(SK_BIAS_BF16, Ly.sa_in_w, Ly.sa_in_b, 3 * D, kv, 3 * D, T, h->Tmax, t0))) return rc;
         SmallAttnArgs sa{kv, 3 * D, T, h->Tmax, t0, kv + D, kv + 2 * D, 3 * D, h->Tmax, 0, t0,
                          ids, ld_ids, c.pad_token_id, h->ctx, D, M, h->H, h->hd};
-        S_HIP_OK(h, launch_attn_small(sa, s));
+        HIP_OK(h, launch_attn_small(sa, s));
         if ((rc = dense_ln(h->ctx, D, Ly.sa_out_w, Ly.sa_out_b, Ly.n1w, Ly.n1b, true))) return rc;
         // cross-attention over the frame tokens (K/V precomputed by set_memory)
         if ((rc = proj(SK_BIAS_BF16, Ly.ca_in_w, Ly.ca_in_b, D, h->qc, D, 1, 1, 0))) return rc;
         const bf16_t* mkv = h->memkv + (size_t)l * mem_layer;
         SmallAttnArgs ca{h->qc, D, T, T, 0, mkv, mkv + D, 2 * D, h->F, h->F, 0, nullptr, 0, 0, h->ctx, D, M, h->H, h->hd};
-        S_HIP_OK(h, launch_attn_small(ca, s));
+        HIP_OK(h, launch_attn_small(ca, s));
         if ((rc = dense_ln(h->ctx, D, Ly.ca_out_w, Ly.ca_out_b, Ly.n2w, Ly.n2b, true))) return rc;
         // feed-forward (the last layer's LayerNorm is a launch: the vocabulary head reads its bf16 output)
         if ((rc = proj(SK_BIAS_RELU_BF16, Ly.l1w, Ly.l1b, h->FF, h->ffn, h->FF, 1, 1, 0))) return rc;
@@ -346,18 +313,18 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         ha.X = h->xb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows;
     }
     if (argmax_out) { ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx; }
-    S_HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
+    HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     if (argmax_out)
-        S_HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
+        HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
                                         sep_cnt, step, c.sep_token_id, s));
     return 0;
 }
 
 int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s) {
-    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student: weights not finalized");
-    if (!memory || B <= 0 || B > h->R) return sfail(h, GITCAP_ERR_ARG, "student: set_memory: bad arguments / B exceeds max_rows");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
+    if (!memory || B <= 0 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student: set_memory: bad arguments / B exceeds max_rows");
     const int D = h->D, Mm = B * h->F;
-    S_HIP_OK(h, launch_cast_bf16(memory, h->memb, (int64_t)Mm * D, s));
+    HIP_OK(h, launch_cast_bf16(memory, h->memb, (int64_t)Mm * D, s));
     const size_t mem_layer = (size_t)h->R * h->F * 2 * D;
     for (int l = 0; l < h->L; ++l) {
         const StuLayer& Ly = h->layers[l];
@@ -375,24 +342,24 @@ int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s) {
 
 extern "C" {
 
-const char* gitcap_student_last_error(const gitcap_student_t* h) { return h ? h->err.c_str() : g_student_create_err.c_str(); }
+const char* gitcap_student_last_error(const gitcap_student_t* h) { return h ? h->err.c_str() : create_err<gitcap_student>().c_str(); }
 
 int gitcap_student_create(const gitcap_student_config* cfg, int device, gitcap_student_t** out) {
-    if (!cfg || !out) return sfail(nullptr, GITCAP_ERR_ARG, "student_create: null argument");
+    if (!cfg || !out) return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: null argument");
     const gitcap_student_config& c = *cfg;
     if (c.d_model <= 0 || c.n_head <= 0 || c.d_model % c.n_head || c.d_model % 32 || c.d_ffn % 32 || c.d_model > 1024)
-        return sfail(nullptr, GITCAP_ERR_ARG, "student_create: d_model/d_ffn must be multiples of 32, d_model <= 1024 and divisible by n_head");
+        return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: d_model/d_ffn must be multiples of 32, d_model <= 1024 and divisible by n_head");
     const int hd = c.d_model / c.n_head;
-    if (hd % 8 || hd > 128) return sfail(nullptr, GITCAP_ERR_ARG, "student_create: head_dim must be a multiple of 8, <= 128");
+    if (hd % 8 || hd > 128) return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: head_dim must be a multiple of 8, <= 128");
     if (!skinny_full_ok(c.d_model) || !skinny_ksplit(c.d_model) || !skinny_ksplit(c.d_ffn))
-        return sfail(nullptr, GITCAP_ERR_ARG, "student_create: no skinny-GEMM instantiation for this d_model / d_ffn (d_model in {64,128,256,576,768,1024})");
+        return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: no skinny-GEMM instantiation for this d_model / d_ffn (d_model in {64,128,256,576,768,1024})");
     if (c.num_layers <= 0 || c.vocab_size <= 0 || c.mem_tokens <= 0 || c.mem_tokens > 64 || c.max_rows <= 0)
-        return sfail(nullptr, GITCAP_ERR_ARG, "student_create: bad layer / vocabulary / memory sizes (mem_tokens <= 64)");
+        return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: bad layer / vocabulary / memory sizes (mem_tokens <= 64)");
     if (c.max_text_len <= 0 || c.max_text_len + 1 > 64 || c.max_text_len + 1 > c.max_pos)
-        return sfail(nullptr, GITCAP_ERR_ARG, "student_create: max_text_len must be in 1..63 and fit the positional table");
+        return fail<gitcap_student>(nullptr, GITCAP_ERR_ARG, "student_create: max_text_len must be in 1..63 and fit the positional table");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return sfail(nullptr, GITCAP_ERR_HIP, "student_create: no such HIP device (libgitcap has no CPU fallback)");
+        return fail<gitcap_student>(nullptr, GITCAP_ERR_HIP, "student_create: no such HIP device (libgitcap has no CPU fallback)");
     gitcap_student* h = new gitcap_student();
     h->c = c; h->device = device;
     h->D = c.d_model; h->H = c.n_head; h->hd = hd; h->FF = c.d_ffn; h->L = c.num_layers; h->V = c.vocab_size;
@@ -402,7 +369,7 @@ int gitcap_student_create(const gitcap_student_config* cfg, int device, gitcap_s
     for (auto& kv : shapes) {
         DevTensor t;
         t.shape = kv.second;
-        t.bf16 = student_is_gemm_weight(kv.first);
+        t.kind = student_is_gemm_weight(kv.first) ? 1 : 0;
         h->w[kv.first] = t;
     }
     *out = h;
@@ -416,7 +383,7 @@ void gitcap_student_destroy(gitcap_student_t* h) {
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-    for (void* p : h->allocs) (void)hipFree(p);
+    free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
     if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
@@ -425,29 +392,22 @@ void gitcap_student_destroy(gitcap_student_t* h) {
 }
 
 int gitcap_student_load_tensor(gitcap_student_t* h, const char* name, const float* data, const int64_t* shape, int rank) {
-    if (!h || !name || !data || !shape) return sfail(h, GITCAP_ERR_ARG, "student_load_tensor: null argument");
-    auto it = h->w.find(name);
-    if (it == h->w.end()) return sfail(h, GITCAP_ERR_ARG, std::string("student_load_tensor: unknown tensor '") + name + "'");
-    S_GUARD(h);
-    DevTensor& t = it->second;
-    if ((int)t.shape.size() != rank) return sfail(h, GITCAP_ERR_ARG, std::string("student_load_tensor: rank mismatch for ") + name);
+    if (!h || !name || !data || !shape) return fail(h, GITCAP_ERR_ARG, "student_load_tensor: null argument");
+    std::string why;
+    DevTensor* tp = find_tensor(h->w, name, shape, rank, "student_load_tensor", why);
+    if (!tp) return fail(h, GITCAP_ERR_ARG, why);
+    GUARD(h);
+    DevTensor& t = *tp;
     int64_t rows = 1;
-    for (int i = 0; i < rank; ++i) {
-        if (t.shape[i] != shape[i]) return sfail(h, GITCAP_ERR_ARG, std::string("student_load_tensor: shape mismatch for ") + name);
-        if (i + 1 < rank) rows *= shape[i];
-    }
+    for (int i = 0; i + 1 < rank; ++i) rows *= shape[i];
     const int64_t cols = shape[rank - 1];
     if (t.p) { (void)hipFree(t.p); t.p = nullptr; }
-    if (t.bf16) {   // GEMM weights: bf16, rows padded to 16 (zero rows)
-        const int64_t prow = pad_to((int)rows, 16);
-        std::vector<uint16_t> hb((size_t)prow * cols, 0);
-        for (int64_t i = 0; i < rows * cols; ++i) hb[(size_t)i] = host_f2bf(data[i]);
-        S_HIP_OK(h, hipMalloc(&t.p, hb.size() * 2));
-        S_HIP_OK(h, hipMemcpy(t.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+    if (t.kind == 1) {   // GEMM weights: bf16, rows padded to 16 (zero rows)
+        if (int rc = upload_bf16_panel(h, t, data, rows, cols, 16, cols)) return rc;
     } else {
         const size_t bytes = (size_t)rows * cols * 4;
-        S_HIP_OK(h, hipMalloc(&t.p, bytes));
-        S_HIP_OK(h, hipMemcpy(t.p, data, bytes, hipMemcpyHostToDevice));
+        HIP_OK(h, hipMalloc(&t.p, bytes));
+        HIP_OK(h, hipMemcpy(t.p, data, bytes, hipMemcpyHostToDevice));
     }
     t.loaded = true;
     h->finalized = false;
@@ -455,10 +415,10 @@ int gitcap_student_load_tensor(gitcap_student_t* h, const char* name, const floa
 }
 
 int gitcap_student_finalize(gitcap_student_t* h) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_finalize: null handle");
-    S_GUARD(h);
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_finalize: null handle");
+    GUARD(h);
     for (auto& kv : h->w)
-        if (!kv.second.loaded) return sfail(h, GITCAP_ERR_STATE, "student_finalize: tensor '" + kv.first + "' was never loaded");
+        if (!kv.second.loaded) return fail(h, GITCAP_ERR_STATE, "student_finalize: tensor '" + kv.first + "' was never loaded");
     auto Fp = [&](const std::string& n) { return (const float*)h->w[n].p; };
     auto Wt = [&](const std::string& n) { return (const bf16_t*)h->w[n].p; };
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);     // weight pointers are baked into the nodes
@@ -483,13 +443,13 @@ int gitcap_student_finalize(gitcap_student_t* h) {
         const int ks = std::max(skinny_ksplit(h->D), skinny_ksplit(h->FF));
         const size_t ntiles = ((size_t)h->V + 15) / 16;
         int rc;
-        if ((rc = s_alloc(h, &h->xf2, 2 * D)) || (rc = s_alloc(h, &h->xf, Mt * D)) || (rc = s_alloc(h, &h->xb, Mt * D)) || (rc = s_alloc(h, &h->qc, Mt * D)) ||
-            (rc = s_alloc(h, &h->ctx, Mt * D)) || (rc = s_alloc(h, &h->ffn, Mt * h->FF)) ||
-            (rc = s_alloc(h, &h->slabs, (size_t)ks * Mt * D)) || (rc = s_alloc(h, &h->amax_val, Mt * ntiles)) ||
-            (rc = s_alloc(h, &h->amax_idx, Mt * ntiles)) || (rc = s_alloc(h, &h->kvs, (size_t)h->L * Mt * 3 * D)) ||
-            (rc = s_alloc(h, &h->memb, (size_t)h->R * h->F * D)) ||
-            (rc = s_alloc(h, &h->memkv, (size_t)h->L * h->R * h->F * 2 * D)) || (rc = s_alloc(h, &h->sep_cnt, (size_t)h->Tmax + 1)) ||
-            (rc = s_alloc(h, &h->g_ids, (size_t)h->R * h->Tmax)) || (rc = s_alloc(h, &h->g_steps, (size_t)1)))
+        if ((rc = dev_alloc(h, &h->xf2, 2 * D)) || (rc = dev_alloc(h, &h->xf, Mt * D)) || (rc = dev_alloc(h, &h->xb, Mt * D)) || (rc = dev_alloc(h, &h->qc, Mt * D)) ||
+            (rc = dev_alloc(h, &h->ctx, Mt * D)) || (rc = dev_alloc(h, &h->ffn, Mt * h->FF)) ||
+            (rc = dev_alloc(h, &h->slabs, (size_t)ks * Mt * D)) || (rc = dev_alloc(h, &h->amax_val, Mt * ntiles)) ||
+            (rc = dev_alloc(h, &h->amax_idx, Mt * ntiles)) || (rc = dev_alloc(h, &h->kvs, (size_t)h->L * Mt * 3 * D)) ||
+            (rc = dev_alloc(h, &h->memb, (size_t)h->R * h->F * D)) ||
+            (rc = dev_alloc(h, &h->memkv, (size_t)h->L * h->R * h->F * 2 * D)) || (rc = dev_alloc(h, &h->sep_cnt, (size_t)h->Tmax + 1)) ||
+            (rc = dev_alloc(h, &h->g_ids, (size_t)h->R * h->Tmax)) || (rc = dev_alloc(h, &h->g_steps, (size_t)1)))
             return rc;
     }
     h->finalized = true;
@@ -497,15 +457,15 @@ int gitcap_student_finalize(gitcap_student_t* h) {
 }
 
 int gitcap_student_set_memory(gitcap_student_t* h, const float* memory, int B, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_set_memory: null handle");
-    S_GUARD(h);
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_set_memory: null handle");
+    GUARD(h);
     return set_memory(h, memory, B, (hipStream_t)stream);
 }
 
 int gitcap_student_forward_decoder(gitcap_student_t* h, const int64_t* ids, int ld_ids, int B, int T, float* logits, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_forward_decoder: null handle");
-    if (!logits) return sfail(h, GITCAP_ERR_ARG, "student_forward_decoder: null logits");
-    S_GUARD(h);
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_forward_decoder: null handle");
+    if (!logits) return fail(h, GITCAP_ERR_ARG, "student_forward_decoder: null logits");
+    GUARD(h);
     return text_forward(h, ids, ld_ids, B, 0, T, logits, nullptr, 0, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -515,9 +475,9 @@ namespace {
 
 // argument checks shared by gitcap_student_greedy and gitcap_student_window_greedy
 int greedy_check(gitcap_student* h, const char* who, int max_len, int stop, const int64_t* ids_out) {
-    if (!ids_out || max_len <= 0) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
-    if (max_len + 1 > h->Tmax) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len");
-    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": unknown stop rule");
+    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
+    if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len");
+    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": unknown stop rule");
     return 0;
 }
 
@@ -529,13 +489,13 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
     // and replayed.  GITCAP_STUDENT_GRAPH=0 launches it kernel by kernel (same kernels, same results).
     static const bool use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
     auto enqueue_loop = [&](hipStream_t q) -> int {
-        S_HIP_OK(h, launch_fill_i64(h->g_ids, ld, B, h->c.cls_token_id, q));                 // model.py:171
-        S_HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
+        HIP_OK(h, launch_fill_i64(h->g_ids, ld, B, h->c.cls_token_id, q));                 // model.py:171
+        HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
         for (int t = 0; t < max_len; ++t) {                                                  // model.py:173-182
             int r = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q);
             if (r) return r;
         }
-        S_HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
+        HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
         return 0;
     };
     if (use_graph) {
@@ -544,32 +504,32 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
             if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share) exec = g.exec;
         if (!exec) {
             hipGraph_t graph = nullptr;
-            if (!h->cap_stream) S_HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-            S_HIP_OK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+            if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
+            HIP_OK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
             rc = enqueue_loop(h->cap_stream);
             hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            S_HIP_OK(h, e);
+            HIP_OK(h, e);
             e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
-            S_HIP_OK(h, e);
+            HIP_OK(h, e);
             h->graphs.push_back({B, max_len, stop, g_row_prologue, g_head_share, exec});
         }
-        S_HIP_OK(h, hipGraphLaunch(exec, s));
+        HIP_OK(h, hipGraphLaunch(exec, s));
     } else if ((rc = enqueue_loop(s))) {
         return rc;
     }
-    S_HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (steps_out) S_HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
 // argument checks shared by gitcap_student_beam_search and gitcap_student_window_beam_search
 int beam_check(gitcap_student* h, const char* who, int B, int k, int max_len, const int64_t* ids_out) {
-    if (!ids_out || B <= 0 || k <= 0 || max_len < 2) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
-    if (k > 16) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": at most 16 beams");
-    if ((int64_t)B * k > h->R) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": B * k exceeds max_rows");
-    if (max_len > h->Tmax) return sfail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len + 1");
+    if (!ids_out || B <= 0 || k <= 0 || max_len < 2) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
+    if (k > 16) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": at most 16 beams");
+    if ((int64_t)B * k > h->R) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": B * k exceeds max_rows");
+    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len + 1");
     return 0;
 }
 
@@ -579,16 +539,16 @@ int beam_workspace(gitcap_student* h) {
     const size_t R = h->R, ld = (size_t)h->Tmax + 1;
     const int D = h->D, V = h->V;
     int rc = 0;
-    rc = rc ? rc : s_alloc(h, &w.memrep, R * h->F * D);
-    rc = rc ? rc : s_alloc(h, &w.scores, R);
-    rc = rc ? rc : s_alloc(h, &w.cand_scores, R);
-    rc = rc ? rc : s_alloc(h, &w.cand_idx, R);
-    rc = rc ? rc : s_alloc(h, &w.src_rows, R);
-    rc = rc ? rc : s_alloc(h, &w.ids0, R * ld);
-    rc = rc ? rc : s_alloc(h, &w.ids1, R * ld);
-    rc = rc ? rc : s_alloc(h, &w.logits, R * (size_t)V);
-    rc = rc ? rc : s_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
-    rc = rc ? rc : s_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
+    rc = rc ? rc : dev_alloc(h, &w.memrep, R * h->F * D);
+    rc = rc ? rc : dev_alloc(h, &w.scores, R);
+    rc = rc ? rc : dev_alloc(h, &w.cand_scores, R);
+    rc = rc ? rc : dev_alloc(h, &w.cand_idx, R);
+    rc = rc ? rc : dev_alloc(h, &w.src_rows, R);
+    rc = rc ? rc : dev_alloc(h, &w.ids0, R * ld);
+    rc = rc ? rc : dev_alloc(h, &w.ids1, R * ld);
+    rc = rc ? rc : dev_alloc(h, &w.logits, R * (size_t)V);
+    rc = rc ? rc : dev_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
+    rc = rc ? rc : dev_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
     if (rc) w = gitcap_student::BeamWs{};
     return rc;
 }
@@ -598,9 +558,9 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
     const int rows = B * k, D = h->D, V = h->V, ld = h->Tmax + 1;
     int rc = 0;
     gitcap_student::BeamWs& w = h->bw;
-    S_HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
+    HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
     hipLaunchKernelGGL(beam_scores_init_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, w.scores, rows, k);
-    S_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     int64_t *cur = w.ids0, *nxt = w.ids1;
     bf16_t* const kvs_home = h->kvs;
     const size_t kv_layer = (size_t)h->R * h->Tmax * 3 * D;
@@ -608,21 +568,21 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
         if (t > 0) {                                                    // rows continue beam src_rows[r]: positions 0 .. t-1, all layers
             bf16_t* other = h->kvs == kvs_home ? w.kvs2 : kvs_home;
             const hipError_t eg = launch_gather_txt_rows(h->kvs, other, w.src_rows, rows, t, h->Tmax, 3 * D, h->L, kv_layer, s);
-            if (eg != hipSuccess) { rc = sfail(h, GITCAP_ERR_HIP, std::string("student_beam_search: gather_txt_rows: ") + hipGetErrorString(eg)); break; }   // (h->kvs is restored below on every path)
+            if (eg != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: gather_txt_rows: ") + hipGetErrorString(eg)); break; }   // (h->kvs is restored below on every path)
             h->kvs = other;
         }
         rc = text_forward(h, cur, ld, rows, t, 1, w.logits, nullptr, 0, nullptr, 0, s);
         if (rc) break;
         hipError_t e = launch_beam_topk(w.logits, V, w.scores, B, k, V, k, w.cand_scores, w.cand_idx, w.topk_scratch, s);
-        if (e != hipSuccess) { rc = sfail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
         hipLaunchKernelGGL(student_beam_step_kernel, dim3(B), dim3(64), 0, s, w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, k, V, t, ld);
-        if (hipGetLastError() != hipSuccess) { rc = sfail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
+        if (hipGetLastError() != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
         std::swap(cur, nxt);
     }
     h->kvs = kvs_home;                                                  // (the captured greedy graphs hold this pointer)
     if (rc) return rc;
     hipLaunchKernelGGL(student_beam_finish_kernel, dim3(B), dim3(64), 0, s, cur, ids_out, k, ld, max_len);
-    S_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     return 0;
 }
 
@@ -632,14 +592,14 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
 // window only orders the F rows (student_window_gather_kernel) in front of the token loop of the full call.
 int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s) {
     if (!h->win_ring || h->win_count < h->F)
-        return sfail(h, GITCAP_ERR_STATE, std::string(who) + ": fewer than mem_tokens tokens pushed since the reset");
+        return fail(h, GITCAP_ERR_STATE, std::string(who) + ": fewer than mem_tokens tokens pushed since the reset");
     const int rows = h->win_B * k, D = h->D;
-    S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
     h->have_memory = false;
     hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * h->F, h->L), dim3(64), 0, s, h->win_ring, h->memkv, h->F, h->win_head, k,
                        2 * D / 8, (size_t)h->win_B * h->F * 2 * D, (size_t)h->R * h->F * 2 * D);
-    S_HIP_OK(h, hipGetLastError());
-    S_HIP_OK(h, hipEventRecord(h->win_ev_read, s));
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipEventRecord(h->win_ev_read, s));
     h->win_read_rec = true;
     h->cur_B = rows;
     h->have_memory = true;
@@ -652,9 +612,9 @@ extern "C" {
 
 int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
                           int32_t* steps_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
     if (int bad = greedy_check(h, "student_greedy", max_len, stop, ids_out)) return bad;
-    S_GUARD(h);
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = set_memory(h, memory, B, s);           // reads the caller's buffer: outside the graph
     if (rc) return rc;
@@ -669,34 +629,34 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
 // -1e9), so the k rows start as the top k of the single prefix [CLS] (model.py:221-227).  After every step the self-attention
 // K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
-    if (!memory) return sfail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
+    if (!memory) return fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
     if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
-    S_GUARD(h);
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = beam_workspace(h);
     if (rc) return rc;
     const int rows = B * k;
     hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
-    S_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     if ((rc = set_memory(h, h->bw.memrep, rows, s))) return rc;
     return beam_loop(h, B, k, max_len, ids_out, s);
 }
 
 int gitcap_student_window_reset(gitcap_student_t* h, int B) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_reset: null handle");
-    if (B < 0 || B > h->R) return sfail(h, GITCAP_ERR_ARG, "student_window_reset: B outside 0..max_rows");
-    S_GUARD(h);
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_reset: null handle");
+    if (B < 0 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student_window_reset: B outside 0..max_rows");
+    GUARD(h);
     if (h->win_ring && B != h->win_B) {
-        S_HIP_OK(h, hipDeviceSynchronize());          // pushes or window calls in flight may still use the ring
+        HIP_OK(h, hipDeviceSynchronize());          // pushes or window calls in flight may still use the ring
         (void)hipFree(h->win_ring); (void)hipFree(h->win_stage);
         h->win_ring = h->win_stage = nullptr;
     }
     h->win_B = h->win_head = h->win_count = 0;
     if (B == 0) return 0;
     if (!h->win_ev_ring) {
-        S_HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
-        S_HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
+        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
+        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
     }
     if (!h->win_ring) {
         const size_t rows = (size_t)B * h->F;
@@ -707,7 +667,7 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B) {
         }
         if (e != hipSuccess) {
             h->win_ring = h->win_stage = nullptr;
-            return sfail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc memory-token window: ") + hipGetErrorString(e));
+            return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc memory-token window: ") + hipGetErrorString(e));
         }
     }
     h->win_B = B;
@@ -715,20 +675,20 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B) {
 }
 
 int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_push: null handle");
-    if (!memory) return sfail(h, GITCAP_ERR_ARG, "student_window_push: null memory");
-    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_push: weights not finalized");
-    if (!h->win_ring) return sfail(h, GITCAP_ERR_STATE, "student_window_push: no window (gitcap_student_window_reset first)");
-    if (B != h->win_B || n < 1 || n > h->F) return sfail(h, GITCAP_ERR_ARG, "student_window_push: B differs from the reset's, or n outside [1, mem_tokens]");
-    S_GUARD(h);
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_push: null handle");
+    if (!memory) return fail(h, GITCAP_ERR_ARG, "student_window_push: null memory");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_push: weights not finalized");
+    if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_push: no window (gitcap_student_window_reset first)");
+    if (B != h->win_B || n < 1 || n > h->F) return fail(h, GITCAP_ERR_ARG, "student_window_push: B differs from the reset's, or n outside [1, mem_tokens]");
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->win_read_rec) S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
-    if (h->win_ring_rec) S_HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    if (h->win_read_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
+    if (h->win_ring_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
     const int D = h->D, F = h->F, n1 = std::min(n, F - h->win_head), n2 = n - n1;
     const int64_t total = (int64_t)B * n * (D / 4);
     hipLaunchKernelGGL(student_window_stage_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1024)), dim3(256), 0, s, memory,
                        h->win_stage, B, n, n1, D / 4);
-    S_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     const size_t ring_layer = (size_t)B * F * 2 * D;
     for (int l = 0; l < h->L; ++l) {
         const StuLayer& Ly = h->layers[l];
@@ -742,7 +702,7 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
                          ring, 2 * D, n2, F, 0);
         if (rc) { h->win_count = 0; return rc; }      // some slots may be half written: the window is emptied
     }
-    S_HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
+    HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
     h->win_ring_rec = true;
     h->win_head = (h->win_head + n) % F;
     h->win_count = std::min(h->win_count + n, F);
@@ -750,10 +710,10 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
 }
 
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_greedy: null handle");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy: null handle");
     if (int bad = greedy_check(h, "student_window_greedy", max_len, stop, ids_out)) return bad;
-    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_greedy: weights not finalized");
-    S_GUARD(h);
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy: weights not finalized");
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = window_memory(h, "student_window_greedy", 1, s);
     if (rc) return rc;
@@ -761,11 +721,11 @@ int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int
 }
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
-    if (!h) return sfail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
-    if (!h->finalized) return sfail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
-    if (!h->win_ring) return sfail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
+    if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
     if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;
-    S_GUARD(h);
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = beam_workspace(h);
     if (rc) return rc;

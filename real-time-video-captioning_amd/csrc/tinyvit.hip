@@ -322,36 +322,18 @@ struct TvBlock {            // stage 0: MBConv (c1, c2 depthwise, c3); stages 1-
 
 }  // namespace
 
-struct gitcap_tinyvit {
+struct gitcap_tinyvit : HandleCore {
     gitcap_tinyvit_config c;
-    int device = 0;
-    mutable std::string err;
-    struct Tensor { DevTensor t; int kind = 0; };     // kind: 0 fp32 as loaded, 1 GEMM weight (bf16 [N][Kp]), 2 depthwise [9][C]
-    std::map<std::string, Tensor> w;
+    std::map<std::string, DevTensor> w;                  // kind 1: bf16 [N][Kp]; kind 2: depthwise, fp32 [9][C]
     bool finalized = false;
     int C[4] = {0, 0, 0, 0}, map[4] = {0, 0, 0, 0}, stem_k1 = 0, stem_k2 = 0;
     TvConv stem1, stem2, ds[4][3];
     std::vector<TvBlock> blocks[4];
     std::vector<float*> tables;                          // dense [heads][N][N] attention-bias tables (finalize)
-    std::vector<void*> allocs;
     bf16_t *col = nullptr, *s1 = nullptr, *x = nullptr, *y = nullptr, *xn = nullptr, *t1 = nullptr, *t2 = nullptr;
 };
 
 namespace {
-
-std::string g_tinyvit_create_err;
-
-int tfail(const gitcap_tinyvit* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_tinyvit_create_err = msg;
-    return code;
-}
-
-#define T_HIP_OK(h, expr)                                                                             \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return tfail(h, GITCAP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-    } while (0)
 
 // the checks of gitcap_tinyvit_create; fills the stage widths and maps.  Empty string = valid.
 std::string tinyvit_check(const gitcap_tinyvit_config& c, int C[4], int map[4]) {
@@ -377,30 +359,20 @@ std::string tinyvit_check(const gitcap_tinyvit_config& c, int C[4], int map[4]) 
     return "";
 }
 
-template <typename T>
-int t_alloc(gitcap_tinyvit* h, T** p, size_t count) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(T));
-    if (e != hipSuccess) return tfail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
-const char* gitcap_tinyvit_last_error(const gitcap_tinyvit_t* h) { return h ? h->err.c_str() : g_tinyvit_create_err.c_str(); }
+const char* gitcap_tinyvit_last_error(const gitcap_tinyvit_t* h) { return h ? h->err.c_str() : create_err<gitcap_tinyvit>().c_str(); }
 
 int gitcap_tinyvit_create(const gitcap_tinyvit_config* cfg, int device, gitcap_tinyvit_t** out) {
-    if (!cfg || !out) return tfail(nullptr, GITCAP_ERR_ARG, "tinyvit_create: null argument");
+    if (!cfg || !out) return fail<gitcap_tinyvit>(nullptr, GITCAP_ERR_ARG, "tinyvit_create: null argument");
     int C[4], map[4];
     const std::string bad = tinyvit_check(*cfg, C, map);
-    if (!bad.empty()) return tfail(nullptr, GITCAP_ERR_ARG, "tinyvit_create: " + bad);
+    if (!bad.empty()) return fail<gitcap_tinyvit>(nullptr, GITCAP_ERR_ARG, "tinyvit_create: " + bad);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return tfail(nullptr, GITCAP_ERR_HIP, "tinyvit_create: no such HIP device (libgitcap has no CPU fallback)");
+        return fail<gitcap_tinyvit>(nullptr, GITCAP_ERR_HIP, "tinyvit_create: no such HIP device (libgitcap has no CPU fallback)");
     gitcap_tinyvit* h = new gitcap_tinyvit();
     h->c = *cfg; h->device = device;
     for (int i = 0; i < 4; ++i) { h->C[i] = C[i]; h->map[i] = map[i]; }
@@ -408,8 +380,8 @@ int gitcap_tinyvit_create(const gitcap_tinyvit_config* cfg, int device, gitcap_t
     h->stem_k1 = pad_to(3 * 9, 32);
     h->stem_k2 = pad_to(c0h * 9, 32);
     auto add = [&](const std::string& n, std::vector<int64_t> shape, int kind) {
-        gitcap_tinyvit::Tensor t;
-        t.t.shape = std::move(shape);
+        DevTensor t;
+        t.shape = std::move(shape);
         t.kind = kind;
         h->w[n] = t;
     };
@@ -456,44 +428,35 @@ void gitcap_tinyvit_destroy(gitcap_tinyvit_t* h) {
     if (!h) return;
     DeviceGuard g(h->device);
     for (auto& kv : h->w)
-        if (kv.second.t.p) (void)hipFree(kv.second.t.p);
+        if (kv.second.p) (void)hipFree(kv.second.p);
     for (float* p : h->tables) (void)hipFree(p);
-    for (void* p : h->allocs) (void)hipFree(p);
+    free_allocs(*h);
     delete h;
 }
 
 int gitcap_tinyvit_load_tensor(gitcap_tinyvit_t* h, const char* name, const float* data, const int64_t* shape, int rank) {
-    if (!h || !name || !data || !shape) return tfail(h, GITCAP_ERR_ARG, "tinyvit_load_tensor: null argument");
-    auto it = h->w.find(name);
-    if (it == h->w.end()) return tfail(h, GITCAP_ERR_ARG, std::string("tinyvit_load_tensor: unknown tensor '") + name + "'");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return tfail(h, GITCAP_ERR_HIP, "cannot select the handle's device");
-    DevTensor& t = it->second.t;
-    if ((int)t.shape.size() != rank) return tfail(h, GITCAP_ERR_ARG, std::string("tinyvit_load_tensor: rank mismatch for ") + name);
+    if (!h || !name || !data || !shape) return fail(h, GITCAP_ERR_ARG, "tinyvit_load_tensor: null argument");
+    std::string why;
+    DevTensor* tp = find_tensor(h->w, name, shape, rank, "tinyvit_load_tensor", why);
+    if (!tp) return fail(h, GITCAP_ERR_ARG, why);
+    GUARD(h);
+    DevTensor& t = *tp;
     int64_t count = 1;
-    for (int i = 0; i < rank; ++i) {
-        if (t.shape[i] != shape[i]) return tfail(h, GITCAP_ERR_ARG, std::string("tinyvit_load_tensor: shape mismatch for ") + name);
-        count *= shape[i];
-    }
+    for (int i = 0; i < rank; ++i) count *= shape[i];
     if (t.p) { (void)hipFree(t.p); t.p = nullptr; }
-    const int kind = it->second.kind;
-    if (kind == 1) {            // GEMM weight: bf16 [N][Kp], K = everything after dim 0, zero-padded to a multiple of 32
-        const int64_t N = shape[0], K = count / N, Kp = pad_to((int)K, 32);
-        std::vector<uint16_t> hb((size_t)(N * Kp), 0);
-        for (int64_t r = 0; r < N; ++r)
-            for (int64_t k = 0; k < K; ++k) hb[(size_t)(r * Kp + k)] = host_f2bf(data[r * K + k]);
-        T_HIP_OK(h, hipMalloc(&t.p, hb.size() * 2));
-        T_HIP_OK(h, hipMemcpy(t.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-    } else if (kind == 2) {     // depthwise [C][1][3][3] -> fp32 [9][C]
+    if (t.kind == 1) {          // GEMM weight: bf16 [N][Kp], K = everything after dim 0, zero-padded to a multiple of 32
+        const int64_t N = shape[0], K = count / N;
+        if (int rc = upload_bf16_panel(h, t, data, N, K, 1, pad_to((int)K, 32))) return rc;
+    } else if (t.kind == 2) {     // depthwise [C][1][3][3] -> fp32 [9][C]
         const int64_t Cn = shape[0];
         std::vector<float> hf((size_t)(9 * Cn));
         for (int64_t c = 0; c < Cn; ++c)
             for (int tp = 0; tp < 9; ++tp) hf[(size_t)(tp * Cn + c)] = data[c * 9 + tp];
-        T_HIP_OK(h, hipMalloc(&t.p, hf.size() * 4));
-        T_HIP_OK(h, hipMemcpy(t.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
+        HIP_OK(h, hipMalloc(&t.p, hf.size() * 4));
+        HIP_OK(h, hipMemcpy(t.p, hf.data(), hf.size() * 4, hipMemcpyHostToDevice));
     } else {
-        T_HIP_OK(h, hipMalloc(&t.p, (size_t)count * 4));
-        T_HIP_OK(h, hipMemcpy(t.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
+        HIP_OK(h, hipMalloc(&t.p, (size_t)count * 4));
+        HIP_OK(h, hipMemcpy(t.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
     }
     t.loaded = true;
     h->finalized = false;
@@ -501,12 +464,11 @@ int gitcap_tinyvit_load_tensor(gitcap_tinyvit_t* h, const char* name, const floa
 }
 
 int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
-    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_finalize: null handle");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return tfail(h, GITCAP_ERR_HIP, "cannot select the handle's device");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "tinyvit_finalize: null handle");
+    GUARD(h);
     for (auto& kv : h->w)
-        if (!kv.second.t.loaded) return tfail(h, GITCAP_ERR_STATE, "tinyvit_finalize: tensor '" + kv.first + "' was never loaded");
-    auto P = [&](const std::string& n) { return h->w[n].t.p; };
+        if (!kv.second.loaded) return fail(h, GITCAP_ERR_STATE, "tinyvit_finalize: tensor '" + kv.first + "' was never loaded");
+    auto P = [&](const std::string& n) { return h->w[n].p; };
     auto conv = [&](const std::string& p) {
         TvConv c;
         if (h->w[p + ".weight"].kind == 2) c.dw = (const float*)P(p + ".weight"); else c.w = (const bf16_t*)P(p + ".weight");
@@ -548,14 +510,14 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
                     idx[(size_t)p * N + q] = id;
                 }
             std::vector<float> ab((size_t)heads * N);
-            T_HIP_OK(h, hipMemcpy(ab.data(), P(bp + "attn.attention_biases"), ab.size() * 4, hipMemcpyDeviceToHost));
+            HIP_OK(h, hipMemcpy(ab.data(), P(bp + "attn.attention_biases"), ab.size() * 4, hipMemcpyDeviceToHost));
             std::vector<float> dense((size_t)heads * N * N);
             for (int hh = 0; hh < heads; ++hh)
                 for (int e = 0; e < N * N; ++e) dense[(size_t)hh * N * N + e] = ab[(size_t)hh * N + idx[e]];
             float* dt = nullptr;
-            T_HIP_OK(h, hipMalloc(&dt, dense.size() * 4));
+            HIP_OK(h, hipMalloc(&dt, dense.size() * 4));
             h->tables.push_back(dt);
-            T_HIP_OK(h, hipMemcpy(dt, dense.data(), dense.size() * 4, hipMemcpyHostToDevice));
+            HIP_OK(h, hipMemcpy(dt, dense.data(), dense.size() * 4, hipMemcpyHostToDevice));
             b.bias_table = dt;
         }
     }
@@ -573,9 +535,9 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
         }
         const size_t col = std::max(m1 * h->stem_k1, m0 * h->stem_k2);
         int rc;
-        if ((rc = t_alloc(h, &h->col, col)) || (rc = t_alloc(h, &h->s1, m1 * (h->C[0] / 2))) || (rc = t_alloc(h, &h->x, act)) ||
-            (rc = t_alloc(h, &h->y, act)) || (rc = t_alloc(h, &h->xn, act)) || (rc = t_alloc(h, &h->t1, big)) ||
-            (rc = t_alloc(h, &h->t2, big)))
+        if ((rc = dev_alloc(h, &h->col, col)) || (rc = dev_alloc(h, &h->s1, m1 * (h->C[0] / 2))) || (rc = dev_alloc(h, &h->x, act)) ||
+            (rc = dev_alloc(h, &h->y, act)) || (rc = dev_alloc(h, &h->xn, act)) || (rc = dev_alloc(h, &h->t1, big)) ||
+            (rc = dev_alloc(h, &h->t2, big)))
             return rc;
     }
     h->finalized = true;
@@ -588,14 +550,13 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
 // fused with the gather of the first stem convolution (preproc.hip: preprocess_stem_kernel); everything behind that gather is shared
 static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t* raw, int rawH, int rawW, int n, float* memory,
                           float* const* fmaps, void* stream) {
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return tfail(h, GITCAP_ERR_HIP, "cannot select the handle's device");
+    GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     const gitcap_tinyvit_config& c = h->c;
     const int img = c.img_size, g1 = img / 2, g0 = img / 4, c0h = h->C[0] / 2;
     auto gemm = [&](const bf16_t* A, int K, const TvConv& cv, int M, int N, int epi, bf16_t* out, const bf16_t* res) -> int {
         TvGemmArgs a{A, K, cv.w, cv.b, res, N, out, N, M, N, K};
-        T_HIP_OK(h, tv_gemm(a, epi, s));
+        HIP_OK(h, tv_gemm(a, epi, s));
         return 0;
     };
     auto lin = [&](const bf16_t* A, int K, const bf16_t* W, const float* b, int M, int N, int epi, bf16_t* out, const bf16_t* res) -> int {
@@ -607,19 +568,19 @@ static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t*
         const int64_t total = (int64_t)n * Ho * Ho * (C / 8);
         if (gelu) hipLaunchKernelGGL(tv_dwconv_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in, cv.dw, cv.b, out, n, H, H, C, stride, Ho, Ho);
         else hipLaunchKernelGGL(tv_dwconv_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in, cv.dw, cv.b, out, n, H, H, C, stride, Ho, Ho);
-        T_HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipGetLastError());
         return 0;
     };
     auto ln = [&](const bf16_t* in, const float* g, const float* b, int M, int C, bf16_t* out) -> int {
         hipLaunchKernelGGL(tv_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, in, g, b, out, M, C, c.ln_eps);
-        T_HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipGetLastError());
         return 0;
     };
     auto emit = [&](int i, const bf16_t* x) -> int {
         if (!fmaps || !fmaps[i]) return 0;
         const int HW = h->map[i] * h->map[i];
         hipLaunchKernelGGL(tv_to_nchw_kernel, dim3(grid_for((int64_t)n * HW * h->C[i])), dim3(256), 0, s, x, fmaps[i], n, HW, h->C[i]);
-        T_HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipGetLastError());
         return 0;
     };
     int rc;
@@ -627,17 +588,17 @@ static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t*
     if (raw) {
         const hipError_t e = launch_preprocess_stem(raw, h->col, n, rawH, rawW, img, s);
         if (e == hipErrorInvalidValue)
-            return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: frame size the transform refuses (empty, or resized below img_size)");
-        T_HIP_OK(h, e);
+            return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: frame size the transform refuses (empty, or resized below img_size)");
+        HIP_OK(h, e);
     } else {
         hipLaunchKernelGGL(tv_im2col_kernel<true>, dim3(grid_for((int64_t)n * g1 * g1 * h->stem_k1)), dim3(256), 0, s, frames, h->col, n,
                            img, img, 3, g1, g1, h->stem_k1);
-        T_HIP_OK(h, hipGetLastError());
+        HIP_OK(h, hipGetLastError());
     }
     if ((rc = gemm(h->col, h->stem_k1, h->stem1, n * g1 * g1, c0h, TV_GELU, h->s1, nullptr))) return rc;
     hipLaunchKernelGGL(tv_im2col_kernel<false>, dim3(grid_for((int64_t)n * g0 * g0 * h->stem_k2)), dim3(256), 0, s, h->s1, h->col, n,
                        g1, g1, c0h, g0, g0, h->stem_k2);
-    T_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     bf16_t *x = h->x, *y = h->y;
     if ((rc = gemm(h->col, h->stem_k2, h->stem2, n * g0 * g0, h->C[0], 0, x, nullptr))) return rc;
     // stage 0: MBConv blocks, x = GELU(x + conv3(GELU(dw(GELU(conv1(x))))))
@@ -663,7 +624,7 @@ static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t*
             if ((rc = lin(h->xn, C, b.qkvw, b.qkvb, M, 3 * C, 0, h->t1, nullptr))) return rc;
             hipLaunchKernelGGL(tv_attn_kernel, dim3(n * (H / ws) * (H / ws), heads), dim3((ws * ws + 63) / 64 * 64), 0, s, h->t1,
                                b.bias_table, h->t2, H, H, C, ws, 0.17677669529663687f);
-            T_HIP_OK(h, hipGetLastError());
+            HIP_OK(h, hipGetLastError());
             if ((rc = lin(h->t2, C, b.projw, b.projb, M, C, TV_RES, x, x))) return rc;
             // x = local_conv(x): depthwise 3x3 + BN, no residual, no activation
             if ((rc = dw(x, b.local, H, C, 1, false, y))) return rc;
@@ -676,27 +637,27 @@ static int tinyvit_encode(gitcap_tinyvit* h, const float* frames, const uint8_t*
         if ((rc = emit(i, x))) return rc;
     }
     hipLaunchKernelGGL(tv_pool_kernel, dim3(n), dim3(256), 0, s, x, memory, h->map[3] * h->map[3], h->C[3]);
-    T_HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipGetLastError());
     return 0;
 }
 
 extern "C" {
 
 int gitcap_tinyvit_encode(gitcap_tinyvit_t* h, const float* frames, int n, float* memory, float* const* fmaps, void* stream) {
-    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: null handle");
-    if (!h->finalized) return tfail(h, GITCAP_ERR_STATE, "tinyvit_encode: weights not finalized");
-    if (!frames || !memory || n <= 0) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: bad arguments");
-    if (n > h->c.max_frames) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode: n exceeds max_frames");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "tinyvit_encode: weights not finalized");
+    if (!frames || !memory || n <= 0) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode: bad arguments");
+    if (n > h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode: n exceeds max_frames");
     return tinyvit_encode(h, frames, nullptr, 0, 0, n, memory, fmaps, stream);
 }
 
 int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr, int n, int H, int W, float* memory,
                               float* const* fmaps, void* stream) {
-    if (!h) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: null handle");
-    if (!h->finalized) return tfail(h, GITCAP_ERR_STATE, "tinyvit_encode_raw: weights not finalized");
-    if (!frames_hwc_bgr || !memory || n <= 0 || H <= 0 || W <= 0) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: bad arguments");
-    if (n > h->c.max_frames) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: n exceeds max_frames");
-    if ((int64_t)n * H * W * 3 > ((int64_t)1 << 40)) return tfail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: sizes overflow");
+    if (!h) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "tinyvit_encode_raw: weights not finalized");
+    if (!frames_hwc_bgr || !memory || n <= 0 || H <= 0 || W <= 0) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: bad arguments");
+    if (n > h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: n exceeds max_frames");
+    if ((int64_t)n * H * W * 3 > ((int64_t)1 << 40)) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: sizes overflow");
     return tinyvit_encode(h, nullptr, frames_hwc_bgr, H, W, n, memory, fmaps, stream);
 }
 
