@@ -15,7 +15,8 @@
  *   - work is enqueued on `stream` (a hipStream_t passed as void*; NULL = default stream) and is
  *     asynchronous; nothing on the data path synchronises the device -- only the set-up and diagnosis calls do
  *     (gitcap_load_tensor / _finalize_weights, gitcap_set_compute / _set_fp8_scale, gitcap_fp8_saturations, and gitcap_poll_errors
- *     when it has a failure to report);
+ *     when it has a failure to report).  One data-path call waits on the host without synchronising the device:
+ *     gitcap_student_greedy_draft / gitcap_student_window_greedy_draft wait for an event behind their own verify pass;
  *   - a handle is bound to one device and is not thread-safe.
  */
 #ifndef GITCAP_H
@@ -447,6 +448,36 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B);
 int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream);
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream);
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream);
+
+/* Greedy decoding that verifies a draft caption in one pass (self-speculative greedy; the reference has no counterpart: its live
+ * loop re-runs greedy_decode from [CLS] on every window, src/real_time_inference.py:56-61).  Two consecutive windows of a live stream
+ * share all but `hop` frames, so the previous caption is a good guess at the next.  The cached token loop equals one teacher-forced
+ * pass over its own output bit for bit and a row does not depend on the rows beside it, so one pass over the draft's n_draft
+ * positions -- the launches of one token step -- yields every token the loop would emit after each draft prefix: the leading draft
+ * tokens that equal them are accepted (all rows in lockstep: the minimum over the rows), the first position that differs already
+ * holds the loop's own token, and only the steps behind it are decoded one by one (replayed from per-step graphs captured at the
+ * first draft call of a (B, max_len, speed switches)).
+ *   draft_ids  device int64 [B][ld_draft]: column 0 is ignored and taken as CLS, columns 1..n_draft are the guessed tokens,
+ *              1 <= n_draft <= max_len, ld_draft >= n_draft + 1 (e.g. the ids_out of the previous call)
+ *   accepted_out  host int32 (nullable): the number of leading draft tokens accepted, 0..n_draft
+ *   the other arguments as gitcap_student_greedy / gitcap_student_window_greedy
+ * Contract: ids_out[:, :1 + steps] and *steps_out are bit for bit those of gitcap_student_greedy / _window_greedy with the same
+ * arguments, whatever the draft holds -- PAD, SEP, ids outside [0, vocab) and negative ids included: such an id is never used as an
+ * index (it is staged as "no word" on the device, its embedding lookup is clamped to the table) and can only mismatch, so the row is
+ * accepted up to that position at most.  Under GITCAP_STOP_NEVER steps = max_len and every column is defined; under
+ * GITCAP_STOP_ALL_SEP the columns beyond 1 + steps are unspecified.  The call leaves the handle as the full call would (a
+ * gitcap_student_forward_decoder after it sees the same memory) and does not touch the full loop's captured graphs.
+ * These are the only student data-path calls that wait on the host: for an event recorded behind the verify pass on `stream` (the
+ * accepted count decides which steps are enqueued), never for the device.
+ * Errors: GITCAP_ERR_ARG for a null handle, draft_ids or ids_out, n_draft < 1, n_draft > max_len, ld_draft < n_draft + 1, and the
+ * length / stop-rule / B / window-state errors of the calls they shadow (GITCAP_ERR_STATE for a window call before mem_tokens pushes).
+ * gitcap_student_draft_stats: host int64[4] = draft calls, draft tokens offered (n_draft summed), tokens accepted, tail steps
+ * enqueued, since the handle was created. */
+int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
+                                int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream);
+int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
+                                       int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream);
+int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4);
 
 /* ---------------------------------------------------------------------------------------------------
  * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with

@@ -130,6 +130,13 @@ struct NextEmbed { const float *word, *pos, *gamma, *beta; float eps; int D, voc
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride,
                                int row_off, int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s,
                                const NextEmbed* emb = nullptr);
+// Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
+// reduces them under launch_argmax_final's tie rule and compares with the draft tokens staged in ids [B][ld] (columns 1..n; -1 =
+// not a word).  a = the leading positions at which every row's token equals its draft token; ids columns 1..min(a + 1, n) and
+// sep_cnt[0 .. min(a + 1, n) - 1] become what the token loop would have written; host (page-locked int32[2]) = {a, all rows
+// emitted SEP in one of those steps}.  tok: int[B * n] scratch; ticket: one word, zero between launches.
+hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
+                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s);
 
 // ---- attention ---------------------------------------------------------------------------
 // Full (unmasked) self-attention over groups of S rows: qkv [G*S][3*W] bf16 (q | k | v, head h

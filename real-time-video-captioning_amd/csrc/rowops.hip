@@ -315,24 +315,15 @@ __global__ __launch_bounds__(256) void pack_frags_kernel(const T* __restrict__ s
 }
 
 // ---- final arg-max over the per-tile partials written by the vocabulary-head kernel ------------
-template <int NV>
-__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
-                                                           int ntiles, int row_stride, int row_off,
-                                                           int64_t* __restrict__ out, int ld_out,
-                                                           int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb) {
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    __shared__ int chosen;
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const size_t base = (size_t)(r * row_stride + row_off) * ntiles;
-    // gamma / beta of the next step's input row do not depend on the token chosen below: requested now (wave 0 uses them)
-    f32x4 gv[NV > 0 ? NV : 1], bv[NV > 0 ? NV : 1];
-    if (NV > 0) {
-        row_load_vec<(NV > 0 ? NV : 1)>(gv, emb.gamma, emb.D, tid & 63);
-        row_load_vec<(NV > 0 ? NV : 1)>(bv, emb.beta, emb.D, tid & 63);
-    }
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
+// The arg-max of one row's partials at val / idx + base by a 256-thread workgroup: the largest value, the smallest index among
+// equals, 0 for an all-NaN row.  In two parts, both called by argmax_final_kernel and draft_accept_kernel (the one statement of the
+// tie rule): argmax_partials_waves, by every thread, leaves each wave's candidate in sv / si (four words of LDS each) behind a
+// barrier and thread 0's own in best / bi; argmax_partials_pick, by thread 0 alone, returns the row's.
+__device__ __forceinline__ void argmax_partials_waves(const float* __restrict__ val, const int* __restrict__ idx, const size_t base,
+                                                      const int ntiles, float* sv, int* si, float& best, int& bi) {
+    const int tid = threadIdx.x;
+    best = -INFINITY;
+    bi = 0x7fffffff;
     // eight partials per thread and round trip (30 522 words = 1908 tiles: one round trip instead of eight); an index past the end
     // re-reads the last tile, which cannot change the result (max value, smallest index among equals: order does not matter)
     for (int i0 = tid; i0 < ntiles; i0 += 256 * 8) {
@@ -356,10 +347,35 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
     }
     if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
     __syncthreads();
+}
+__device__ __forceinline__ int argmax_partials_pick(const float* sv, const int* si, float best, int bi) {
+    for (int w = 1; w < 4; ++w)
+        if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    if (bi == 0x7fffffff) bi = 0;
+    return bi;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
+                                                           int ntiles, int row_stride, int row_off,
+                                                           int64_t* __restrict__ out, int ld_out,
+                                                           int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int chosen;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const size_t base = (size_t)(r * row_stride + row_off) * ntiles;
+    // gamma / beta of the next step's input row do not depend on the token chosen below: requested now (wave 0 uses them)
+    f32x4 gv[NV > 0 ? NV : 1], bv[NV > 0 ? NV : 1];
+    if (NV > 0) {
+        row_load_vec<(NV > 0 ? NV : 1)>(gv, emb.gamma, emb.D, tid & 63);
+        row_load_vec<(NV > 0 ? NV : 1)>(bv, emb.beta, emb.D, tid & 63);
+    }
+    float best;
+    int bi;
+    argmax_partials_waves(val, idx, base, ntiles, sv, si, best, bi);
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        if (bi == 0x7fffffff) bi = 0;
+        bi = argmax_partials_pick(sv, si, best, bi);
         out[(size_t)r * ld_out] = bi;
         if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
         chosen = bi;
@@ -373,6 +389,61 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
             row_store<(NV > 0 ? NV : 1)>(v, tid, emb.D, emb.xf + (size_t)r * emb.D, emb.xb + (size_t)r * emb.D);
         }
     }
+}
+
+// ---- draft verification of the student's greedy loop (student.hip: greedy_draft_core) -------------------------------------
+// The verify pass has left the arg-max partials of all rows x n positions (row m = r * n + j: what the model emits after the
+// draft's tokens 0..j of caption r).  One workgroup per (r, j) reduces its row with argmax_partials_waves / _pick -- the tie rule of the
+// token loop -- and hands the token to the last workgroup to arrive (txtblock.hip's hand-off: agent-scope store, vmcnt drain,
+// barrier, one ticket, agent-scope loads; the ticket word is zero between launches).  That workgroup's first wave, lane j =
+// position j, then does the bookkeeping of the covered steps:
+//   a_r = leading positions of row r whose token equals the draft's next token ids[r][j + 1] (an id outside the vocabulary was
+//         staged as -1 and equals no token); a = min over the rows -- the loop advances all rows in lockstep;
+//   covered = a + 1 steps when a < n (the token at position a is the model's own: the corrected token costs no step), else n;
+//   ids[r][1 .. covered] = the model's tokens (columns 1..a are the accepted draft tokens, the same values);
+//   sep_cnt[t] = rows whose token at step t < covered is SEP, counted from the model's tokens as the token loop counts them;
+//   host[0] = a, host[1] = 1 when all rows emitted SEP in one of the covered steps (page-locked host words).
+__global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restrict__ val, const int* __restrict__ idx, int ntiles, int B,
+                                                           int n, int64_t* ids, int ld, int* tok, unsigned* ticket,
+                                                           int32_t* __restrict__ sep_cnt, int sep_id, int32_t* host) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int last_flag;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    float best;
+    int bi;
+    argmax_partials_waves(val, idx, (size_t)m * ntiles, ntiles, sv, si, best, bi);
+    if (tid == 0) __hip_atomic_store(tok + m, argmax_partials_pick(sv, si, best, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = old == gridDim.x - 1;
+        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+        last_flag = last;
+    }
+    __syncthreads();
+    if (!last_flag || tid >= 64) return;
+    const int j = tid;                                                      // n <= 63: one lane per position
+    int a = n;
+    for (int r = 0; r < B; ++r) {
+        const int t = j < n ? __hip_atomic_load(tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+        const bool match = j < n && (int64_t)t == ids[(size_t)r * ld + j + 1];
+        const unsigned long long miss = __ballot(!match);                   // lanes >= n miss: never zero
+        a = min(a, (int)__ffsll((long long)miss) - 1);
+    }
+    const int covered = a < n ? a + 1 : n;
+    int seps = 0;
+    for (int r = 0; r < B; ++r) {
+        if (j < covered) {
+            const int t = __hip_atomic_load(tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ids[(size_t)r * ld + j + 1] = t;
+            seps += t == sep_id;
+        }
+    }
+    if (j < covered) sep_cnt[j] = seps;
+    const bool fired = __ballot(j < covered && seps == B) != 0ull;
+    if (j == 0) { host[0] = a; host[1] = fired ? 1 : 0; }
 }
 
 // ---- beam candidates: top-K of (log_softmax(logits[b*beams+j]) + beam_score[b*beams+j]) over j, v ----
@@ -724,6 +795,15 @@ hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int n
         default: AF_LAUNCH(4); break;
     }
 #undef AF_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
+                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s) {
+    if (B <= 0 || n < 1 || n > 63 || ld < n + 1 || ntiles <= 0 || !amax_val || !amax_idx || !ids || !tok || !ticket || !sep_cnt || !host)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(draft_accept_kernel, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt,
+                       sep_id, host);
     return hipGetLastError();
 }
 

@@ -44,6 +44,18 @@ __global__ __launch_bounds__(64) void student_embed_kernel(const int64_t* __rest
     }
 }
 
+// draft of gitcap_student_*_greedy_draft -> the handle's id rows: column 0 = CLS whatever the draft holds, columns 1..n the draft's
+// tokens, an id outside [0, vocab) as -1: the embedding clamps it to a table row, it equals no PAD key and no arg-max, so it can
+// only be rejected (draft_accept_kernel)
+__global__ void student_draft_stage_kernel(const int64_t* __restrict__ draft, int ld_draft, int n, int rows, int vocab, int64_t cls,
+                                           int64_t* __restrict__ ids, int ld) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * (n + 1)) return;
+    const int r = i / (n + 1), c = i % (n + 1);
+    const int64_t d = draft[(size_t)r * ld_draft + c];
+    ids[(size_t)r * ld + c] = c == 0 ? cls : (d >= 0 && d < vocab ? d : -1);
+}
+
 // one wave per (query, head); lane i owns key i for the scores and output column(s) lane, lane + 64 for P.V
 __global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a) {
     __shared__ float qs[128];
@@ -181,6 +193,16 @@ struct gitcap_student : HandleCore {
     int32_t* g_steps = nullptr;
     struct GreedyGraph { int B, max_len, stop; bool rows_pro, head_share; hipGraphExec_t exec; };
     std::vector<GreedyGraph> graphs;
+    // draft verification (gitcap_student_*_greedy_draft): the token steps t = 1 .. max_len - 1 of a (B, max_len, switches) as one
+    // graph each (step[t - 1]; the stop rule is not in a step), captured together at the first draft call with that key; acc_tok /
+    // acc_ticket = draft_accept_kernel's scratch, acc_host = its page-locked {accepted, stop rule fired}, read behind acc_ev
+    struct TailGraphs { int B, max_len; bool rows_pro, head_share; std::vector<hipGraphExec_t> step; };
+    std::vector<TailGraphs> tails;
+    int* acc_tok = nullptr;
+    unsigned* acc_ticket = nullptr;
+    int32_t* acc_host = nullptr;
+    hipEvent_t acc_ev = nullptr;
+    int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
     struct BeamWs {
@@ -204,6 +226,15 @@ struct gitcap_student : HandleCore {
 };
 
 namespace {
+
+// the captured token loops and token steps: weight pointers are baked into their nodes
+void destroy_graphs(gitcap_student* h) {
+    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+    h->graphs.clear();
+    for (auto& t : h->tails)
+        for (hipGraphExec_t e : t.step) (void)hipGraphExecDestroy(e);
+    h->tails.clear();
+}
 
 bool student_is_gemm_weight(const std::string& n) {
     auto ends = [&](const char* s) { size_t l = strlen(s); return n.size() >= l && n.compare(n.size() - l, l, s) == 0; };
@@ -381,8 +412,10 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     DeviceGuard g(h->device);
     for (auto& kv : h->w)
         if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+    destroy_graphs(h);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    if (h->acc_host) (void)hipHostFree(h->acc_host);
+    if (h->acc_ev) (void)hipEventDestroy(h->acc_ev);
     free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
@@ -421,8 +454,7 @@ int gitcap_student_finalize(gitcap_student_t* h) {
         if (!kv.second.loaded) return fail(h, GITCAP_ERR_STATE, "student_finalize: tensor '" + kv.first + "' was never loaded");
     auto Fp = [&](const std::string& n) { return (const float*)h->w[n].p; };
     auto Wt = [&](const std::string& n) { return (const bf16_t*)h->w[n].p; };
-    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);     // weight pointers are baked into the nodes
-    h->graphs.clear();
+    destroy_graphs(h);
     h->embed = Fp("embed.weight"); h->pe = Fp("pos_enc.pe"); h->head_w = Wt("linear.weight"); h->head_b = Fp("linear.bias");
     h->layers.resize(h->L);
     for (int i = 0; i < h->L; ++i) {
@@ -449,7 +481,8 @@ int gitcap_student_finalize(gitcap_student_t* h) {
             (rc = dev_alloc(h, &h->amax_idx, Mt * ntiles)) || (rc = dev_alloc(h, &h->kvs, (size_t)h->L * Mt * 3 * D)) ||
             (rc = dev_alloc(h, &h->memb, (size_t)h->R * h->F * D)) ||
             (rc = dev_alloc(h, &h->memkv, (size_t)h->L * h->R * h->F * 2 * D)) || (rc = dev_alloc(h, &h->sep_cnt, (size_t)h->Tmax + 1)) ||
-            (rc = dev_alloc(h, &h->g_ids, (size_t)h->R * h->Tmax)) || (rc = dev_alloc(h, &h->g_steps, (size_t)1)))
+            (rc = dev_alloc(h, &h->g_ids, (size_t)h->R * h->Tmax)) || (rc = dev_alloc(h, &h->g_steps, (size_t)1)) ||
+            (rc = dev_alloc(h, &h->acc_tok, Mt)) || (rc = dev_alloc(h, &h->acc_ticket, (size_t)4)))
             return rc;
     }
     h->finalized = true;
@@ -521,6 +554,99 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
     }
     HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// ---- greedy decoding that verifies a draft caption ------------------------------------------------------------------------
+// The cached token loop equals one teacher-forced pass over its own output bit for bit, and a row's result does not depend on the
+// rows beside it (tests/test_student.py: test_gpu_greedy_kv_cache_and_token_parity, test_gpu_student_batch_invariance_and_determinism).  So the tokens the loop would emit after
+// CLS, d_1, .., d_j are the head's arg-max at position j of ONE pass over the draft (T = n, the launches of one token step), and
+// every leading draft token that equals it is a token the loop would have produced: accepted, together with the K/V rows the pass
+// wrote for its position.  The first position that differs holds the loop's own token (the corrected one).  The steps behind it
+// are the loop's own launches, text_forward(t, 1).
+int draft_tail_graphs(gitcap_student* h, int B, int max_len, std::vector<hipGraphExec_t>** out) {
+    for (auto& t : h->tails)
+        if (t.B == B && t.max_len == max_len && t.rows_pro == g_row_prologue && t.head_share == g_head_share) { *out = &t.step; return 0; }
+    const int ld = max_len + 1;
+    gitcap_student::TailGraphs tg{B, max_len, g_row_prologue, g_head_share, {}};
+    if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
+    int rc = 0;
+    for (int t = 1; t < max_len && !rc; ++t) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipError_t e = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) {
+            rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, h->cap_stream);
+            e = hipStreamEndCapture(h->cap_stream, &graph);
+        }
+        if (!rc && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (!rc && e != hipSuccess) rc = fail(h, GITCAP_ERR_HIP, std::string("student draft: capturing a token step: ") + hipGetErrorString(e));
+        if (!rc) tg.step.push_back(exec);
+    }
+    if (rc) {
+        for (hipGraphExec_t e : tg.step) (void)hipGraphExecDestroy(e);
+        return rc;
+    }
+    h->tails.push_back(std::move(tg));
+    *out = &h->tails.back().step;
+    return 0;
+}
+
+// argument checks of the two draft calls (behind greedy_check)
+int draft_check(gitcap_student* h, const char* who, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len) {
+    if (!draft_ids) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": null draft_ids");
+    if (n_draft < 1 || n_draft > max_len || ld_draft < n_draft + 1)
+        return fail(h, GITCAP_ERR_ARG, std::string(who) + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
+    return 0;
+}
+
+// verify -> accept -> tail against the memory K|V in h->memkv; same results as greedy_loop(B, max_len, stop)
+int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_draft, int n, int max_len, int stop, int64_t* ids_out,
+                      int32_t* steps_out, int32_t* accepted_out, hipStream_t s) {
+    int rc;
+    const int ld = max_len + 1;
+    static const bool use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
+    if (!h->acc_host) {
+        HIP_OK(h, hipHostMalloc((void**)&h->acc_host, 16, hipHostMallocMapped));
+        HIP_OK(h, hipEventCreateWithFlags(&h->acc_ev, hipEventDisableTiming));
+    }
+    // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
+    std::vector<hipGraphExec_t>* steps = nullptr;
+    if (use_graph && (rc = draft_tail_graphs(h, B, max_len, &steps))) return rc;
+    // 1. verify: one pass over positions 0 .. n-1 of the staged draft (K/V rows of those positions -> the cache), then the
+    //    vocabulary head over all B * n rows, arg-max partials only
+    hipLaunchKernelGGL(student_draft_stage_kernel, dim3((B * (n + 1) + 255) / 256), dim3(256), 0, s, draft, ld_draft, n, B, h->V,
+                       (int64_t)h->c.cls_token_id, h->g_ids, ld);
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
+    if ((rc = text_forward(h, h->g_ids, ld, B, 0, n, nullptr, nullptr, 0, nullptr, 0, s))) return rc;
+    const int ntiles = (h->V + 15) / 16;
+    SkinnyArgs ha{};
+    ha.X = h->xb; ha.ldx = h->D; ha.W = h->head_w; ha.bias = h->head_b; ha.M = B * n; ha.N = h->V; ha.K = h->D; ha.ldo = h->V;
+    ha.T = 1; ha.row_stride = 1; ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx;
+    HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
+    // 2. accept
+    *(volatile int32_t*)h->acc_host = -1;
+    HIP_OK(h, launch_draft_accept(h->amax_val, h->amax_idx, ntiles, B, n, h->g_ids, ld, h->acc_tok, h->acc_ticket, h->sep_cnt,
+                                  h->c.sep_token_id, h->acc_host, s));
+    HIP_OK(h, hipEventRecord(h->acc_ev, s));
+    HIP_OK(h, hipEventSynchronize(h->acc_ev));
+    const int a = ((volatile int32_t*)h->acc_host)[0];
+    const bool fired = ((volatile int32_t*)h->acc_host)[1] != 0;
+    if (a < 0 || a > n) return fail(h, GITCAP_ERR_HIP, "student draft: the accept kernel published no count");
+    // 3. tail: the token steps the pass did not cover
+    const int t0 = a < n ? a + 1 : n;
+    const bool tail = t0 < max_len && !(stop == GITCAP_STOP_ALL_SEP && fired);
+    for (int t = t0; tail && t < max_len; ++t) {
+        if (use_graph) HIP_OK(h, hipGraphLaunch((*steps)[t - 1], s));
+        else if ((rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, s))) return rc;
+    }
+    HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, s));
+    HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (accepted_out) *accepted_out = a;
+    ++h->draft_calls; h->draft_offered += n; h->draft_accepted += a; h->draft_tail_steps += tail ? max_len - t0 : 0;
     return 0;
 }
 
@@ -718,6 +844,37 @@ int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int
     int rc = window_memory(h, "student_window_greedy", 1, s);
     if (rc) return rc;
     return greedy_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
+}
+
+int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
+                                int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy_draft: null handle");
+    if (int bad = greedy_check(h, "student_greedy_draft", max_len, stop, ids_out)) return bad;
+    if (int bad = draft_check(h, "student_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = set_memory(h, memory, B, s);
+    if (rc) return rc;
+    return greedy_draft_core(h, B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s);
+}
+
+int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
+                                       int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy_draft: null handle");
+    if (int bad = greedy_check(h, "student_window_greedy_draft", max_len, stop, ids_out)) return bad;
+    if (int bad = draft_check(h, "student_window_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy_draft: weights not finalized");
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = window_memory(h, "student_window_greedy_draft", 1, s);
+    if (rc) return rc;
+    return greedy_draft_core(h, h->win_B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s);
+}
+
+int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
+    if (!h || !out4) return fail(h, GITCAP_ERR_ARG, "student_draft_stats: null argument");
+    out4[0] = h->draft_calls; out4[1] = h->draft_offered; out4[2] = h->draft_accepted; out4[3] = h->draft_tail_steps;
+    return 0;
 }
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {

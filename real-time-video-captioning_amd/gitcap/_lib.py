@@ -82,6 +82,11 @@ SYMBOLS = {
     "gitcap_student_window_push": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gitcap_student_window_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_student_window_beam_search": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gitcap_student_greedy_draft": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            POINTER(c_int32), c_void_p]),
+    "gitcap_student_window_greedy_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                   POINTER(c_int32), c_void_p]),
+    "gitcap_student_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),

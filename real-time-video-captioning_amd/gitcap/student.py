@@ -40,11 +40,15 @@ class StudentCaptionStream:
     include/gitcap.h: gitcap_student_window_*).  A frame is encoded once, when it is pushed, and its cross-attention K|V rows
     are computed then; a caption of the window only orders those rows and runs the token loop.  Captions are bitwise those of
     greedy_decode / beam_search on the window's frames.  With a ``gate`` (gitcap.framegate.FrameGate) only the frames it admits
-    are encoded and counted; a push of camera frames with none admitted returns None and costs one distance launch."""
+    are encoded and counted; a push of camera frames with none admitted returns None and costs one distance launch.  With
+    ``carry`` a greedy stream offers its previous caption as the draft of the next window call
+    (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False):
         self._m = model
         self._gate = gate
+        self._carry, self._prev = bool(carry), None
+        self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
         self._sched = WindowSchedule(batch, model.cfg.mem_tokens, hop)
         self._max_len, self._mode, self._beams = max_len, mode, beams
         self._token = object()
@@ -62,8 +66,16 @@ class StudentCaptionStream:
         with torch.cuda.device(self._m._dev):
             self._m._call("gitcap_student_window_reset", self._sched.batch)
         self._sched.reset()
+        self._prev = None                                # the next caption is a plain call
         if self._gate is not None:
             self._gate.reset()
+
+    def stats(self) -> dict:
+        """Since the stream was opened: ``captions`` returned, ``draft_tokens`` offered to the verify pass (per clip; 0 for a
+        caption decoded by the plain call), ``accepted`` of them (the minimum over the clips, as the loop advances them in
+        lockstep), ``tail_steps`` decoded one by one behind a draft (a plain call's steps are not counted), and ``last`` = the
+        same three numbers of the latest caption.  A gate keeps its own statistics (FrameGate.stats)."""
+        return dict(self._stats)
 
     def _tokens(self, frames: torch.Tensor) -> torch.Tensor:
         """One frame per clip ([B,H,W,3] uint8 / [B,3,S,S] fp32), n of them ([B,n,...]) or memory tokens [B,n,d_model]
@@ -104,13 +116,23 @@ class StudentCaptionStream:
             if self._beams is None:
                 ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
                 steps = torch.zeros(1, dtype=torch.int32, device=m._dev)
-                m._call("gitcap_student_window_greedy", self._max_len, self._mode, ctypes.c_void_p(ids.data_ptr()),
-                        ctypes.c_void_p(steps.data_ptr()), m._stream())
+                last = dict(draft_tokens=0, accepted=0, tail_steps=0)
+                if self._carry and self._prev is not None:
+                    last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps)
+                else:
+                    m._call("gitcap_student_window_greedy", self._max_len, self._mode, ctypes.c_void_p(ids.data_ptr()),
+                            ctypes.c_void_p(steps.data_ptr()), m._stream())
                 if self._mode == STOP_ALL_SEP:
                     ids = ids[:, :1 + int(steps.item())]
+                if self._carry:
+                    self._prev = ids
+                for k, v in last.items():
+                    self._stats[k] += v
+                self._stats["last"] = last
             else:
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 m._call("gitcap_student_window_beam_search", self._beams, self._max_len, ctypes.c_void_p(ids.data_ptr()), m._stream())
+        self._stats["captions"] += 1
         return ids.cpu() if to_cpu else ids
 
 
@@ -148,6 +170,7 @@ class StudentCaptioner(nn.Module):
         self._dev = torch.device(device)
         self._handle = None
         self._window_owner = None                       # token of the live StudentCaptionStream
+        self.last_accepted: Optional[int] = None        # draft tokens the last greedy_decode(draft=...) accepted
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
         self._create()
@@ -317,11 +340,37 @@ class StudentCaptioner(nn.Module):
         fmaps, memory = self.forward_image_enc(x)
         return list(fmaps) + [self.forward_decoder(y, memory)]
 
+    def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor) -> dict:
+        """One of the two draft entry points (``head`` = the arguments in front of the draft's); ``draft`` int64 [B, 1+n] on
+        either device, trimmed to max_len columns beyond CLS.  -> what the call offered, accepted and decoded behind it."""
+        B = ids.shape[0]
+        if draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] < 2 or draft.dtype != torch.int64:
+            raise ValueError(f"draft must be int64 [{B}, 1+n] with n >= 1, got {draft.dtype} {tuple(draft.shape)}")
+        d = draft[:, :1 + max_len].to(self._dev).contiguous()
+        n = d.shape[1] - 1
+        acc = ctypes.c_int32(-1)
+        before = self._draft_stats()
+        self._call(name, *head, ctypes.c_void_p(d.data_ptr()), n + 1, n, max_len, mode, ctypes.c_void_p(ids.data_ptr()),
+                   ctypes.c_void_p(steps.data_ptr()), ctypes.byref(acc), self._stream())
+        self.last_accepted = int(acc.value)
+        return dict(draft_tokens=n, accepted=self.last_accepted, tail_steps=self._draft_stats()[3] - before[3])
+
+    def _draft_stats(self):
+        """gitcap_student_draft_stats: (draft calls, tokens offered, tokens accepted, tail steps) of this handle."""
+        out = (ctypes.c_int64 * 4)()
+        self._call("gitcap_student_draft_stats", out)
+        return tuple(int(v) for v in out)
+
     @torch.no_grad()
-    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None) -> torch.Tensor:
+    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
+                      draft: Optional[torch.Tensor] = None) -> torch.Tensor:
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
-        Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device."""
+        Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
+        ``draft``: int64 [B, 1+n], a guess at the result (e.g. the previous caption of a live stream; column 0 is taken as CLS,
+        any ids are allowed).  The result is the one without it, bit for bit: the draft is verified in one pass, the tokens the
+        loop would have produced anyway are accepted (``last_accepted`` = their number) and only the rest is decoded step by
+        step (include/gitcap.h: gitcap_student_greedy_draft).  The call waits on the host for the verify pass."""
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
@@ -332,8 +381,11 @@ class StudentCaptioner(nn.Module):
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
         with torch.cuda.device(self._dev):
-            self._call("gitcap_student_greedy", ctypes.c_void_p(mem.data_ptr()), B, max_len, mode,
-                       ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), self._stream())
+            if draft is not None:
+                self._draft_call("gitcap_student_greedy_draft", (ctypes.c_void_p(mem.data_ptr()), B), draft, max_len, mode, ids, steps)
+            else:
+                self._call("gitcap_student_greedy", ctypes.c_void_p(mem.data_ptr()), B, max_len, mode,
+                           ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
         return ids.to(out_dev) if out_dev != ids.device else ids
@@ -363,7 +415,7 @@ class StudentCaptioner(nn.Module):
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
-                       beams: Optional[int] = None, gate: Optional[FrameGate] = None) -> StudentCaptionStream:
+                       beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -371,7 +423,11 @@ class StudentCaptioner(nn.Module):
         greedy_decode(max_len, stop)); with ``beams`` the best beam of beam_search(max_len, k=beams).  Needs the native
         encoder.  One live stream per model: opening another one, or moving the model, invalidates this one.
         ``gate``: a FrameGate that decides on the device which pushed camera frames are worth encoding (it is reset here);
-        without one every pushed frame is."""
+        without one every pushed frame is.
+        ``carry``: a greedy stream passes its previous caption as the draft of the next window call (greedy_decode's ``draft``):
+        the same captions; ``stats()`` tells how much of the drafts was accepted.  Not with ``beams``."""
+        if carry and beams is not None:
+            raise ValueError("carry=True verifies the previous greedy caption: it cannot be combined with beams")
         if not self._native():
             raise _lib.GitcapError("caption_stream needs the native TinyViT encoder (image_encoder='native'): frames are "
                                    "encoded one at a time on the device")
@@ -390,7 +446,7 @@ class StudentCaptioner(nn.Module):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
