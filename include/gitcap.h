@@ -195,7 +195,8 @@ int gitcap_greedy_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, 
  *                                                         src/models/model.py:557-565
  * logits: device fp32 [B*beams][ld]; beam_scores: device fp32 [B*beams]; outputs: device
  * out_scores fp32 [B][K], out_idx int32 [B][K] (flat index beam*V + word), sorted descending,
- * ties by smaller flat index; K <= 16, beams <= 16.  Stateless (no handle). */
+ * ties by smaller flat index; K <= 16, beams <= 16, V <= 131072 (else GITCAP_ERR_ARG, nothing is launched).  Logits of -inf are
+ * no candidates; if a clip has fewer than K candidates its remaining slots hold score -inf, index 0x7fffffff.  Stateless (no handle). */
 int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
                      float* out_scores, int32_t* out_idx, void* stream);
 
@@ -361,6 +362,62 @@ int gitcap_dbg_attn_full(const void* qkv, void* ctx, int G, int S, int H, void* 
 /* layernorm: x fp32 [rows][D] -> out_f32 / out_bf16 (either may be NULL) */
 int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, float eps, int rows, int D,
                          float* out_f32, void* out_bf16, void* stream);
+
+/* Token-selection hooks (tests/test_selection_gpu.py; the restatement they are compared with is tests/selection_reference.py).
+ * Each runs ONE launcher of csrc/kernels.h on caller-owned device buffers; the selection rule everywhere: the largest value,
+ * the smallest index among equals.
+ *
+ * vocab_head: the vocabulary head of the token loops (launch_skinny, fp32-logits epilogue, identity row map).  X bf16 [M][ldx]
+ * (ldx >= K, a multiple of 8); W [Npad16][K] bf16 (Npad16 = N rounded up to 16; rows n >= N are read and must not be selected),
+ * or OCP e4m3 codes when wscale (fp32 [Npad16], powers of two) is non-NULL (K = 128 or 768 only); bias fp32 [N] or NULL;
+ * K in {64, 128, 256, 576, 768, 1024}.  logits: fp32 [M][N] or NULL.  amax_val fp32 / amax_idx int32 [M][ntiles], ntiles = Npad16 / 16
+ * (both or neither): per 16-column tile the largest logit of the row and the first column that holds it.  Honours
+ * gitcap_dbg_config(10, .): the four-tile workgroups that share X through LDS (N >= 64, K <= 768) or one wave per tile; same bits. */
+int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                          float* logits, float* amax_val, int32_t* amax_idx, void* stream);
+/* argmax_final: out[r * ld_out] = amax_idx of the best of the ntiles partials of row r * row_stride + row_off, r < rows (a row
+ * whose winner carries the empty-tile index 0x7fffffff, i.e. no logit above -inf: 0); sep_cnt (nullable): sep_cnt[step] += rows whose token is sep_id.  emb (nullable, all of
+ * its fields or none): the launch goes on to write row r of xf fp32 / xb bf16 [rows][D] = LayerNorm(word[token] + pos[position])
+ * (word [vocab][D], pos [>= position + 1][D], gamma / beta [D]; D a multiple of 4, <= 1024; a token outside [0, vocab) is
+ * clamped into the table). */
+typedef struct gitcap_dbg_next_embed {
+    const float *word, *pos, *gamma, *beta;
+    float eps;
+    int32_t D, vocab, position;
+    float* xf;
+    void* xb;
+} gitcap_dbg_next_embed;
+int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                            void* stream);
+/* draft_accept (the accept step of gitcap_student_greedy_draft): partials [B * n][ntiles] (row r * n + j = position j of caption
+ * r, n <= 63), ids int64 [B][ld] with the draft staged in columns 1..n (-1 = no word), ld >= n + 1.  a = the leading positions
+ * at which every row's token equals its draft token; covered = min(a + 1, n); ids columns 1..covered and sep_cnt[0..covered - 1]
+ * are rewritten from the model's tokens, nothing behind them is touched.  tok: int32 [B * n] scratch; ticket: one zero word,
+ * zero again when the launch has finished.  The call synchronises `stream` and writes host_out[0] = a, host_out[1] = 1 when all
+ * rows emitted sep_id in one of the covered steps, else 0 (host_out: HOST int32[2]). */
+int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                            int32_t* tok, uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream);
+/* The bookkeeping launches of the device-resident beam search over its nine state buffers (R = B * beams rows):
+ * ids0 / ids1 int64 [R][max_len] (double buffered prefixes), words int64 [R], hyp_ids int64 [B][max_len], beam_scores fp32 [R],
+ * hyp_score fp32 [B], src_rows int32 [R], done / hyp_len int32 [B].
+ *   beam_init:   ids0[r][0] = words[r] = cls, beam_scores = 0 for the first beam of a clip and -1e9 for the others (model.py:508-509),
+ *                src_rows[r] = r, done = hyp_len = 0.
+ *   beam_step:   one step of model.py:573-621 on the K <= 16 sorted candidates per clip that gitcap_beam_topk wrote (every
+ *                cand_idx must lie in [0, beams * V): the empty-slot sentinel of gitcap_beam_topk must not be passed on);
+ *                reads ids[cur], writes ids[cur ^ 1], words, src_rows, beam_scores and the best finished hypothesis.
+ *                1 <= cur_len < max_len.
+ *   beam_finish: decoded int64 [B][max_len] = the best hypothesis padded with eos, logprobs fp32 [B] = its score (-1e5: none). */
+typedef struct gitcap_dbg_beam_buffers {
+    int64_t *ids0, *ids1, *words, *hyp_ids;
+    float *beam_scores, *hyp_score;
+    int32_t *src_rows, *done, *hyp_len;
+} gitcap_dbg_beam_buffers;
+int gitcap_dbg_beam_init(const gitcap_dbg_beam_buffers* bb, int B, int beams, int max_len, int cls, void* stream);
+int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* bb, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                         int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
+int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* bb, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                           void* stream);
 
 /* Residual stream of the ViT per block (tests/test_stress_layers_gpu.py: single-block checks on the device's own inputs).
  * While `buf` is non-NULL every SYNCHRONOUS image pass (gitcap_encode / _greedy / _beam_search and their _raw forms) copies

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1595,6 +1596,83 @@ int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, 
                          float* out_f32, void* out_bf16, void* stream) {
     LnArgs a{x, D, gamma, beta, eps, rows, D, out_f32, D, (bf16_t*)out_bf16, D, nullptr, 1, 1, nullptr, nullptr, 0.f};
     return launch_layernorm(a, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+// ---- token selection (tests/test_selection_gpu.py): each hook is ONE launcher on caller-owned device buffers --------------
+static int dbg_rc(hipError_t e) { return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP); }
+
+// launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
+int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                          float* logits, float* amax_val, int32_t* amax_idx, void* stream) {
+    if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || (amax_val == nullptr) != (amax_idx == nullptr) ||
+        (!logits && !amax_val))
+        return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
+    a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
+    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr;
+    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream));
+}
+
+int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                            void* stream) {
+    if (!amax_val || !amax_idx || !out || ntiles <= 0 || rows <= 0 || row_stride <= 0 || row_off < 0 || ld_out <= 0 || step < 0)
+        return GITCAP_ERR_ARG;
+    NextEmbed ne{};
+    if (emb) {
+        if (emb->vocab <= 0 || emb->position < 0) return GITCAP_ERR_ARG;
+        ne = NextEmbed{emb->word, emb->pos, emb->gamma, emb->beta, emb->eps, emb->D, emb->vocab, emb->position, emb->xf, (bf16_t*)emb->xb};
+    }
+    return dbg_rc(launch_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id,
+                                      (hipStream_t)stream, emb ? &ne : nullptr));
+}
+
+// the two words the kernel publishes go through a page-locked int32[2] this hook owns (made once, kept for the process)
+int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream) {
+    static std::mutex mu;
+    static int32_t* host = nullptr;
+    if (!host_out) return GITCAP_ERR_ARG;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!host && hipHostMalloc((void**)&host, 16, hipHostMallocMapped) != hipSuccess) { host = nullptr; return GITCAP_ERR_NOMEM; }
+    const hipStream_t s = (hipStream_t)stream;
+    ((volatile int32_t*)host)[0] = -1;
+    ((volatile int32_t*)host)[1] = -1;
+    const hipError_t e = launch_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host, s);
+    if (e != hipSuccess) return dbg_rc(e);
+    if (hipStreamSynchronize(s) != hipSuccess) return GITCAP_ERR_HIP;
+    host_out[0] = ((volatile int32_t*)host)[0];
+    host_out[1] = ((volatile int32_t*)host)[1];
+    return 0;
+}
+
+static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) {
+    if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len)
+        return false;
+    bb = BeamBuffers{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
+    return true;
+}
+
+int gitcap_dbg_beam_init(const gitcap_dbg_beam_buffers* b, int B, int beams, int max_len, int cls, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb) || B <= 0 || beams <= 0 || beams > 16 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_init(bb, B, beams, max_len, cls, (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams, int K,
+                         int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || K <= 0 || V <= 0 || cur_len < 1 ||
+        cur_len >= max_len || (cur != 0 && cur != 1))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_step(bb, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_finish(bb, B, max_len, eos, decoded, logprobs, (hipStream_t)stream));
 }
 
 // Threads a host-side copy may use: the affinity mask capped by the cgroup CPU quota (a 1-GPU box gives the job a share of the

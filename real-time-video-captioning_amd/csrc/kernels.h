@@ -122,7 +122,8 @@ struct FfnTxtArgs {
 };
 bool ffn_txt_ok(int D, int F);
 hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
-// out[r*ld_out] = index of the max over the per-tile partials of row r*row_stride + row_off.
+// out[r*ld_out] = index of the max over the per-tile partials of row r*row_stride + row_off; lowest index wins ties (torch.argmax on
+// CPU), 0 when the winner is an empty tile's index 0x7fffffff (no logit above -inf in the row).  If sep_cnt != nullptr: sep_cnt[step] += 1 for every row whose token is sep_id (zero it per call).
 // emb (nullable; greedy loop, one position per row): the kernel goes on to embed the token it just chose at text position
 // emb->position -- word + position embedding -> LayerNorm -> xf / xb row r (rowln.h: the code of launch_embed_text) -- so
 // the next token step starts at its q|k|v projection.
@@ -230,15 +231,13 @@ hipError_t launch_dequant_fp8_batch(const DequantBatch& b, hipStream_t s);
 hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, int t0,
                              const float* word, const float* pos, const float* gamma, const float* beta,
                              float eps, int D, int vocab, float* x_f32, bf16_t* x_bf16, hipStream_t s);
-// argmax over [rows][V] (row stride ld) -> out[r*ld_out] (int64); lowest index wins ties.
-// If sep_cnt != nullptr: sep_cnt[step] += 1 for every row whose argmax is sep_id (zero it per call).
-hipError_t launch_argmax(const float* logits, int ld, int rows, int V, int64_t* out, int ld_out,
-                         int32_t* sep_flags, int step, int sep_id, hipStream_t s);
 hipError_t launch_finish_steps(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out, hipStream_t s);
 hipError_t launch_fill_i64(int64_t* p, int ld, int rows, int64_t v, hipStream_t s);
 hipError_t launch_gather_txt_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_rows, int rows,
                                   int t_len, int Tmax, int width, int layers, size_t layer_stride, hipStream_t s);
-// top-K over (beam, vocab) of log_softmax(logits) + beam_scores, one block per batch element
+// top-K over (beam, vocab) of log_softmax(logits) + beam_scores per batch element: sorted descending, ties by smaller flat index
+// j*V + v.  Logits of -inf are no candidates; where a clip has fewer than K candidates the remaining slots hold the sentinel
+// (score -inf, index 0x7fffffff) -- launch_beam_step divides the index by V and must never be handed one.
 size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scratch launch_beam_topk needs (V <= 131072)
 hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
                             float* out_scores, int* out_idx, void* scratch, hipStream_t s);

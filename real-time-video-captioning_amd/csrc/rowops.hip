@@ -1,5 +1,5 @@
 // HBM-bound row kernels: LayerNorm (one wave per row, 16-byte vector loads), patch gather
-// (im2col of NCHW fp32 frames, coalesced 16-B reads along W), text embedding, argmax.
+// (im2col of NCHW fp32 frames, coalesced 16-B reads along W), text embedding, token selection.
 #include "kernels.h"
 #include <algorithm>
 #include "ln_canon.h"
@@ -681,37 +681,6 @@ __global__ void beam_init_kernel(BeamState st, int B, int beams, int max_len, in
     if (r < B) { st.done[r] = 0; st.hyp_len[r] = 0; st.hyp_score[r] = 0.f; }
 }
 
-// ---- argmax: one block per row; lowest index wins ties (torch.argmax on CPU) -------------------
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int ld, int V,
-                                                     int64_t* __restrict__ out, int ld_out,
-                                                     int32_t* __restrict__ sep_cnt, int step, int sep_id) {
-    __shared__ float sv[4];
-    __shared__ int si[4];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const float* p = logits + (size_t)r * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += 256) {
-        const float v = p[i];
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(best, o);
-        const int i2 = __shfl_xor(bi, o);
-        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-    }
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        if (bi == 0x7fffffff) bi = 0;                               // all-NaN row: deterministic answer
-        out[(size_t)r * ld_out] = bi;
-        if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
-    }
-}
-
 // steps_out = number of generated columns that are valid under the stop rule
 __global__ void finish_steps_kernel(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out) {
     int steps = max_len;
@@ -973,12 +942,6 @@ hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, in
     else if (nv == 2) hipLaunchKernelGGL(embed_text_kernel<2>, dim3(grid), dim3(256), 0, s, ids, ld_ids, rows, T, t0, word, pos, gamma, beta, eps, D, vocab, x_f32, x_bf16);
     else if (nv == 3) hipLaunchKernelGGL(embed_text_kernel<3>, dim3(grid), dim3(256), 0, s, ids, ld_ids, rows, T, t0, word, pos, gamma, beta, eps, D, vocab, x_f32, x_bf16);
     else hipLaunchKernelGGL(embed_text_kernel<4>, dim3(grid), dim3(256), 0, s, ids, ld_ids, rows, T, t0, word, pos, gamma, beta, eps, D, vocab, x_f32, x_bf16);
-    return hipGetLastError();
-}
-
-hipError_t launch_argmax(const float* logits, int ld, int rows, int V, int64_t* out, int ld_out,
-                         int32_t* sep_flags, int step, int sep_id, hipStream_t s) {
-    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, out, ld_out, sep_flags, step, sep_id);
     return hipGetLastError();
 }
 

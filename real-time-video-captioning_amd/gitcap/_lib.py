@@ -13,6 +13,18 @@ from .tinyvit_config import CTinyViTConfig
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgitcap.so")
 
+class CDbgNextEmbed(ctypes.Structure):
+    """struct gitcap_dbg_next_embed (include/gitcap.h)."""
+    _fields_ = [("word", c_void_p), ("pos", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("eps", c_float),
+                ("D", c_int32), ("vocab", c_int32), ("position", c_int32), ("xf", c_void_p), ("xb", c_void_p)]
+
+
+class CDbgBeamBuffers(ctypes.Structure):
+    """struct gitcap_dbg_beam_buffers (include/gitcap.h): the nine device pointers of the beam search state."""
+    _fields_ = [("ids0", c_void_p), ("ids1", c_void_p), ("words", c_void_p), ("hyp_ids", c_void_p), ("beam_scores", c_void_p),
+                ("hyp_score", c_void_p), ("src_rows", c_void_p), ("done", c_void_p), ("hyp_len", c_void_p)]
+
+
 # every symbol include/gitcap.h declares (tests/test_cabi.py checks the list against the header)
 SYMBOLS = {
     "gitcap_abi_version": (c_int, []),
@@ -67,6 +79,17 @@ SYMBOLS = {
     "gitcap_dbg_config": (c_int, [c_int, c_int]),
     "gitcap_dbg_attn_full": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gitcap_dbg_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # token-selection hooks (tests/test_selection_gpu.py)
+    "gitcap_dbg_vocab_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "gitcap_dbg_argmax_final": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                        POINTER(CDbgNextEmbed), c_void_p]),
+    "gitcap_dbg_draft_accept": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                        POINTER(c_int32), c_void_p]),
+    "gitcap_dbg_beam_init": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_beam_step": (c_int, [POINTER(CDbgBeamBuffers), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_float, c_int, c_void_p]),
+    "gitcap_dbg_beam_finish": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
