@@ -290,6 +290,24 @@ int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out,
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream);
 
+/* Per-token log-probabilities of a greedy caption (no reference counterpart: the reference's greedy loop returns ids only).
+ * A ONE-SHOT attachment: it applies to the NEXT greedy-family call or submission on the handle -- gitcap_greedy, gitcap_greedy_raw,
+ * gitcap_greedy_submit, gitcap_greedy_raw_submit, gitcap_window_greedy -- and is consumed by it, whether that call succeeds or
+ * fails; any other entry point (encode, text_forward, beam search, pushes) leaves a pending attachment alone; logprobs_out == NULL
+ * detaches.  A pipelined submission captures the pointer: the buffer stays valid until the wait, like ids_out.
+ *   logprobs_out  device fp32 [B][ld], ld >= max_len of the consuming call: column t = log_softmax(logits of step t)[ids_out[b][t + 1]],
+ *                 the natural-log probability of the token the loop emitted at step t.  Columns < *steps_out are defined, later
+ *                 ones unspecified; columns >= max_len are not written.
+ * The values come out of the launches that choose the token (the vocabulary head leaves a third partial per 16-column tile, the
+ * sum of exp(logit - tile max); the arg-max launch merges them in a fixed order): no logits tensor, no extra launch, no host round
+ * trip, and bitwise independent of the batch size and of the entry point.  With or without an attachment every id is the same.
+ * Errors: GITCAP_ERR_ARG for ld < 1 or a pointer that is not 4-byte aligned; at the consuming call ld < max_len gives
+ * GITCAP_ERR_ARG with nothing launched (the attachment is consumed all the same).
+ * Memory: the first attach on a handle allocates the third partial beside the arg-max partials, one buffer per pipeline slot (a
+ * set-up step: it may synchronise; gitcap_workspace_bytes counts it from then on).  A handle that never attaches allocates
+ * nothing and runs exactly the launches it ran before. */
+int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld);
+
 /* Host-side staging copy for host-fed callers (no reference counterpart): bytes from pageable memory (a DataLoader batch without
  * pin_memory, OpenCV frames) into a page-locked staging buffer, split over up to 8 threads -- as many as the process may really use
  * (affinity mask, cgroup CPU quota; GITCAP_HOST_COPY_THREADS overrides).  Plain memcpy semantics, blocking, no device work.
@@ -375,6 +393,11 @@ int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, 
  * gitcap_dbg_config(10, .): the four-tile workgroups that share X through LDS (N >= 64, K <= 768) or one wave per tile; same bits. */
 int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
                           float* logits, float* amax_val, int32_t* amax_idx, void* stream);
+/* vocab_head_lse: the same launch with the third partial of the token log-probabilities: amax_sum fp32 [M][ntiles] (required, and
+ * with it amax_val / amax_idx) = the sum of exp(logit - amax_val) over the tile's valid columns, 0 for a tile whose amax_val is -inf.
+ * amax_val / amax_idx are bit for bit those of gitcap_dbg_vocab_head. */
+int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                              float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream);
 /* argmax_final: out[r * ld_out] = amax_idx of the best of the ntiles partials of row r * row_stride + row_off, r < rows (a row
  * whose winner carries the empty-tile index 0x7fffffff, i.e. no logit above -inf: 0); sep_cnt (nullable): sep_cnt[step] += rows whose token is sep_id.  emb (nullable, all of
  * its fields or none): the launch goes on to write row r of xf fp32 / xb bf16 [rows][D] = LayerNorm(word[token] + pos[position])
@@ -390,6 +413,13 @@ typedef struct gitcap_dbg_next_embed {
 int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                             int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
                             void* stream);
+/* argmax_final_lp: the same launch, and lp_out[r * ld_lp] = -log(sum_t amax_sum[t] * exp(amax_val[t] - M)), M = the row's largest
+ * partial: log_softmax(logits)[token] of the row (amax_sum fp32 [rows as amax_val][ntiles], both new arguments required).  Tiles
+ * with amax_val == -inf are skipped; a row with no logit above -inf gives -inf.  Summation order: thread tid of 256 takes tiles
+ * tid, tid + 256, .. ascending, a xor butterfly inside each wave, then waves 0..3 in order -- the same whatever `rows` is. */
+int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                               const float* amax_sum, float* lp_out, int ld_lp, void* stream);
 /* draft_accept (the accept step of gitcap_student_greedy_draft): partials [B * n][ntiles] (row r * n + j = position j of caption
  * r, n <= 63), ids int64 [B][ld] with the draft staged in columns 1..n (-1 = no word), ld >= n + 1.  a = the leading positions
  * at which every row's token equals its draft token; covered = min(a + 1, n); ids columns 1..covered and sep_cnt[0..covered - 1]
@@ -398,6 +428,11 @@ int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int 
  * rows emitted sep_id in one of the covered steps, else 0 (host_out: HOST int32[2]). */
 int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
                             int32_t* tok, uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream);
+/* draft_accept_lp: the same launch, and lp_out[r * ld_lp + j] (fp32 [B][ld_lp], ld_lp >= n) = argmax_final_lp's value of partial row
+ * r * n + j for the covered positions j < covered; nothing behind them is touched.  ids, sep_cnt and host_out as without _lp. */
+int gitcap_dbg_draft_accept_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                               int32_t* tok, uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out,
+                               const float* amax_sum, float* lp_out, int ld_lp, void* stream);
 /* The bookkeeping launches of the device-resident beam search over its nine state buffers (R = B * beams rows):
  * ids0 / ids1 int64 [R][max_len] (double buffered prefixes), words int64 [R], hyp_ids int64 [B][max_len], beam_scores fp32 [R],
  * hyp_score fp32 [B], src_rows int32 [R], done / hyp_len int32 [B].
@@ -535,6 +570,16 @@ int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B,
 int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
                                        int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream);
 int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4);
+/* Per-token log-probabilities of the student's greedy captions: gitcap_attach_token_logprobs for this handle.  One-shot; consumed
+ * by the next of gitcap_student_greedy, gitcap_student_window_greedy, gitcap_student_greedy_draft, gitcap_student_window_greedy_draft
+ * (success or failure); other entry points leave it pending; NULL detaches.  logprobs_out: device fp32 [B][ld], ld >= max_len,
+ * column t = the natural-log probability of ids_out[b][t + 1]; columns < *steps_out defined (the draft forms may stop on the
+ * host), columns >= max_len not written.  With a draft the covered positions come from the verify pass and the rest from the tail
+ * steps: by the exact-KV-cache property the values are bit for bit those of the plain call.  Needs finalized weights
+ * (GITCAP_ERR_STATE); GITCAP_ERR_ARG for ld < 1 or a misaligned pointer, and at the consuming call for ld < max_len (nothing
+ * launched, attachment consumed).  The first attach allocates the third partial (sized as the arg-max partials, which covers
+ * the verify pass's B * n_draft rows) and the handle's own [rows][max_len] staging the captured loops write. */
+int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld);
 
 /* ---------------------------------------------------------------------------------------------------
  * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with

@@ -127,6 +127,7 @@ struct gitcap : HandleCore {
         unsigned char* v8_img = nullptr; float* vs_img = nullptr;   // kv_cache = v_e4m3
         // text-row workspace of the slot (token loops of different slots may run concurrently)
         float *xs = nullptr, *xs2 = nullptr, *slabs = nullptr, *part = nullptr, *amax_val = nullptr; int* amax_idx = nullptr;
+        float* amax_sum = nullptr;          // third head partial, [Mt][ntiles] like amax_val: allocated by the first gitcap_attach_token_logprobs
         unsigned* row_cnt = nullptr;
         bf16_t *xsb = nullptr, *fs = nullptr, *kv_txt = nullptr, *kv_txt2 = nullptr;
         // device-resident beam-search state of the slot (gitcap_beam_search / _submit)
@@ -149,6 +150,9 @@ struct gitcap : HandleCore {
     hipStream_t txt_streams[NSLOT] = {nullptr, nullptr, nullptr, nullptr};   // owned; slot i decodes on txt_streams[i % n_txt]
     int n_txt = NSLOT;
     bool pipelined = false; // the launches being issued belong to a gitcap_greedy_submit (other batches share the chip)
+    // gitcap_attach_token_logprobs: the pending one-shot attachment (device fp32 [B][lp_ld]); taken by the next greedy-family call
+    float* lp_attach = nullptr;
+    int lp_ld = 0;
 
     // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
     // last win_F frames of win_B clips, clip-major [B][F][N][Dv].  win_head = the slot the next frame goes to (= the oldest frame
@@ -502,7 +506,7 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 
 int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams, int t0, int T, float* logits_out,
                  int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
-                 bool pre_embedded = false, bool embed_next = false) {
+                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0) {
     const gitcap_config& c = h->c;
     gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -607,6 +611,8 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
         ha.X = sl.xsb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows; ha.out = logits_out;
     }
     if (argmax_out) { ha.amax_val = sl.amax_val; ha.amax_idx = sl.amax_idx; }
+    if (lp_out && (!argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
+    if (lp_out) ha.amax_sum = sl.amax_sum;      // the head's third partial -> the chosen token's log-probability (argmax_final)
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
         HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
@@ -614,7 +620,8 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     if (argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
         HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
-                                      sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr));
+                                      sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr, lp_out ? sl.amax_sum : nullptr,
+                                      lp_out, ld_lp));
     }
     return 0;
 }
@@ -1121,7 +1128,8 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
 }
 
 // token steps 0 .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
-static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s) {
+// lp (nullable, row pitch ld_lp): column t = the log-probability of the token step t emitted
+static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, float* lp = nullptr, int ld_lp = 0) {
     const bool chain = text_chain_ok(h, rows, 1);
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
     // bits -- and measured nothing: 4.926 vs 4.912 ms per 20-token caption; tools/experiments/argmax_fold_rows.txt.)
@@ -1129,7 +1137,8 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
     for (int t = 0; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
         const bool next = chain && t + 1 < max_len && t + 1 < h->c.max_text_pos;
-        const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next);
+        const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next,
+                                    lp ? lp + t : nullptr, ld_lp);
         if (rc) return rc;
         have_rows = next;
     }
@@ -1140,14 +1149,27 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
 // clips are independent, every kernel is batch invariant, the captions were bitwise the same: 16 clips 323-325 / 580 / 600 us
 // per token step against 302 for one loop (profiles/r04_sync_call_split_token_loop.txt).  Chains of ~6 us launches on
 // different streams do not overlap each other the way one chain overlaps an image pass.  Removed.)
-static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
+struct LpAttach { float* p; int ld; };
+// the pending attachment of gitcap_attach_token_logprobs: taken (and with that consumed) by every greedy-family entry point
+static LpAttach take_lp(gitcap* h) {
+    const LpAttach a{h->lp_attach, h->lp_ld};
+    h->lp_attach = nullptr; h->lp_ld = 0;
+    return a;
+}
+static int lp_check(gitcap* h, const LpAttach& lp, int max_len) {
+    if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached token log-probability buffer has ld < max_len");
+    return 0;
+}
+
+static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
+                            LpAttach lp = LpAttach{nullptr, 0}) {
     const int ld = max_len + 1;
     gitcap::Slot& sl = cur(h);
     int rc;
     // CLS start tokens [B,1] (model.py:171)
     HIP_OK(h, launch_fill_i64(ids_out, ld, B, h->c.cls_token_id, s));
     HIP_OK(h, hipMemsetAsync(sl.sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
-    if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s))) return rc;
+    if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld))) return rc;
     if (steps_out) HIP_OK(h, launch_finish_steps(sl.sep_cnt, B, max_len, stop, steps_out, s));
     return 0;
 }
@@ -1162,14 +1184,16 @@ static int greedy_check(gitcap* h, int max_len, int stop, const int64_t* ids_out
 int gitcap_greedy(gitcap_t* h, const float* frames, int B, int F, int max_len, int stop, int64_t* ids_out,
                   int32_t* steps_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "greedy: null handle");
+    const LpAttach lp = take_lp(h);
     GUARD(h);
     POLL(h);
     int rc = greedy_check(h, max_len, stop, ids_out);
+    rc = rc ? rc : lp_check(h, lp, max_len);
     if (rc) return rc;
     select_slot(h, 0);
     HIP_OK(h, join_async(h, (hipStream_t)stream));
     if ((rc = encode_impl(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, (hipStream_t)stream))) return rc;
-    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream);
+    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream, lp);
 }
 
 int gitcap_encode_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, float* visual_out, void* stream) {
@@ -1184,38 +1208,44 @@ int gitcap_encode_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, 
 int gitcap_greedy_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
                       int64_t* ids_out, int32_t* steps_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "greedy_raw: null handle");
+    const LpAttach lp = take_lp(h);
     GUARD(h);
     POLL(h);
     int rc = greedy_check(h, max_len, stop, ids_out);
+    rc = rc ? rc : lp_check(h, lp, max_len);
     if (rc) return rc;
     select_slot(h, 0);
     HIP_OK(h, join_async(h, (hipStream_t)stream));
     if ((rc = encode_impl(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, nullptr, (hipStream_t)stream))) return rc;
-    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream);
+    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream, lp);
 }
 
 int gitcap_greedy_submit(gitcap_t* h, const float* frames, int B, int F, int max_len, int stop, int64_t* ids_out,
                          int32_t* steps_out, void* stream, int* ticket) {
     if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "greedy_submit: null argument");
+    const LpAttach lp = take_lp(h);          // captured into the submission: the buffer stays valid until the wait, like ids_out
     GUARD(h);
     POLL(h);
     int rc = greedy_check(h, max_len, stop, ids_out);
+    rc = rc ? rc : lp_check(h, lp, max_len);
     if (rc) return rc;
     return submit_common(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s);
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
     });
 }
 
 int gitcap_greedy_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
                              int64_t* ids_out, int32_t* steps_out, void* stream, int* ticket) {
     if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "greedy_raw_submit: null argument");
+    const LpAttach lp = take_lp(h);
     GUARD(h);
     POLL(h);
     int rc = greedy_check(h, max_len, stop, ids_out);
+    rc = rc ? rc : lp_check(h, lp, max_len);
     if (rc) return rc;
     if ((rc = check_raw(h, frames_hwc_bgr, B, F, H, W))) return rc;
     return submit_common(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, nullptr, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s);
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
     });
 }
 
@@ -1409,13 +1439,15 @@ static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
 
 int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, int64_t* ids_out, int32_t* steps_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "window_greedy: null handle");
+    const LpAttach lp = take_lp(h);
     GUARD(h);
     POLL(h);
     int rc = greedy_check(h, max_len, stop, ids_out);
+    rc = rc ? rc : lp_check(h, lp, max_len);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = window_prefix(h, visual_out, s))) return rc;
-    return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
+    return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
 }
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
@@ -1428,6 +1460,19 @@ int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float lengt
     hipStream_t s = (hipStream_t)stream;
     if ((rc = window_prefix(h, visual_out, s))) return rc;
     return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+}
+
+int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: null handle");
+    if (!logprobs_out) { h->lp_attach = nullptr; h->lp_ld = 0; return 0; }
+    if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: ld < 1 or a misaligned pointer");
+    GUARD(h);
+    if (!h->slots[0].amax_sum) {            // first attach: the third head partial beside amax_val, one buffer per slot
+        for (auto& sl : h->slots)
+            if (int rc = dev_alloc(h, &sl.amax_sum, (size_t)sl.Mt * (size_t)((h->V + 15) / 16))) { h->slots[0].amax_sum = nullptr; return rc; }
+    }
+    h->lp_attach = logprobs_out; h->lp_ld = ld;
+    return 0;
 }
 
 int gitcap_reorder_rows(gitcap_t* h, const int32_t* src_rows, int rows, int t_len, void* stream) {
@@ -1602,21 +1647,31 @@ int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, 
 static int dbg_rc(hipError_t e) { return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP); }
 
 // launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
-int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                          float* logits, float* amax_val, int32_t* amax_idx, void* stream) {
+static int dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                          float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
     if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || (amax_val == nullptr) != (amax_idx == nullptr) ||
-        (!logits && !amax_val))
+        (!logits && !amax_val) || (amax_sum && !amax_val))
         return GITCAP_ERR_ARG;
     SkinnyArgs a{};
     a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
     a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
-    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr;
+    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
     return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream));
 }
+int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                          float* logits, float* amax_val, int32_t* amax_idx, void* stream) {
+    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, nullptr, stream);
+}
+// the same launch with the third partial (amax_sum [M][ntiles], required)
+int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                              float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
+    if (!amax_sum) return GITCAP_ERR_ARG;
+    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum, stream);
+}
 
-int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                             int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                            void* stream) {
+                            const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
     if (!amax_val || !amax_idx || !out || ntiles <= 0 || rows <= 0 || row_stride <= 0 || row_off < 0 || ld_out <= 0 || step < 0)
         return GITCAP_ERR_ARG;
     NextEmbed ne{};
@@ -1625,26 +1680,57 @@ int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int 
         ne = NextEmbed{emb->word, emb->pos, emb->gamma, emb->beta, emb->eps, emb->D, emb->vocab, emb->position, emb->xf, (bf16_t*)emb->xb};
     }
     return dbg_rc(launch_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id,
-                                      (hipStream_t)stream, emb ? &ne : nullptr));
+                                      (hipStream_t)stream, emb ? &ne : nullptr, amax_sum, lp_out, ld_lp));
+}
+int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                            void* stream) {
+    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, nullptr, nullptr, 0, stream);
+}
+int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                               const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
+    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
+    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, amax_sum, lp_out, ld_lp, stream);
 }
 
 // the two words the kernel publishes go through a page-locked int32[2] this hook owns (made once, kept for the process)
-int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
-                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream) {
+// (and, with lp_out, through a device int[B * n] scratch this hook owns as well)
+static int dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, const float* amax_sum, float* lp_out,
+                            int ld_lp, void* stream) {
     static std::mutex mu;
     static int32_t* host = nullptr;
+    static int* lp_tok = nullptr;
+    static int64_t lp_cap = 0;
     if (!host_out) return GITCAP_ERR_ARG;
     std::lock_guard<std::mutex> lock(mu);
     if (!host && hipHostMalloc((void**)&host, 16, hipHostMallocMapped) != hipSuccess) { host = nullptr; return GITCAP_ERR_NOMEM; }
+    if (lp_out && B > 0 && n > 0 && (int64_t)B * n > lp_cap) {
+        if (lp_tok) { (void)hipDeviceSynchronize(); (void)hipFree(lp_tok); }
+        lp_cap = std::max<int64_t>((int64_t)B * n, 1024);
+        if (hipMalloc((void**)&lp_tok, (size_t)lp_cap * 4) != hipSuccess) { lp_tok = nullptr; lp_cap = 0; return GITCAP_ERR_NOMEM; }
+    }
     const hipStream_t s = (hipStream_t)stream;
     ((volatile int32_t*)host)[0] = -1;
     ((volatile int32_t*)host)[1] = -1;
-    const hipError_t e = launch_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host, s);
+    const hipError_t e = launch_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host, s, amax_sum,
+                                             lp_out ? lp_tok : nullptr, lp_out, ld_lp);
     if (e != hipSuccess) return dbg_rc(e);
     if (hipStreamSynchronize(s) != hipSuccess) return GITCAP_ERR_HIP;
     host_out[0] = ((volatile int32_t*)host)[0];
     host_out[1] = ((volatile int32_t*)host)[1];
     return 0;
+}
+int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream) {
+    return dbg_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host_out, nullptr, nullptr, 0, stream);
+}
+int gitcap_dbg_draft_accept_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                               uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, const float* amax_sum, float* lp_out,
+                               int ld_lp, void* stream) {
+    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
+    return dbg_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host_out, amax_sum, lp_out, ld_lp, stream);
 }
 
 static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) {

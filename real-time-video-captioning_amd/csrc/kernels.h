@@ -87,6 +87,10 @@ struct SkinnyArgs {
     // optional fragment-major copy of W (launch_pack_frags: [tile][k32][lane][8]); when set the kernels read it instead of W
     const void* Wpk;
     int ksplit;                            // splitk: number of K slabs (0: skinny_ksplit(K))
+    // SK_BIAS_F32 with amax_val set (nullable): third per-tile partial [M][ntiles], sum of exp(logit - amax_val) over the tile's
+    // valid columns (0 where amax_val is -inf) -- what launch_argmax_final / launch_draft_accept turn into the chosen token's
+    // log-probability.  nullptr: the launch is the one without it.
+    float* amax_sum;
 };
 extern std::atomic<bool> g_row_prologue;                                 // gitcap.hip: GITCAP_NO_ROW_PROLOGUE / gitcap_dbg_config(1, .)
 // vocabulary head: four 16-column tiles per workgroup share the activation rows through LDS (skinny.hip: skinny_head_kernel);
@@ -130,14 +134,19 @@ hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
 struct NextEmbed { const float *word, *pos, *gamma, *beta; float eps; int D, vocab, position; float* xf; bf16_t* xb; };
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride,
                                int row_off, int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s,
-                               const NextEmbed* emb = nullptr);
+                               const NextEmbed* emb = nullptr, const float* amax_sum = nullptr, float* lp_out = nullptr, int ld_lp = 0);
+// amax_sum + lp_out (both or neither; SkinnyArgs::amax_sum of the same head launch): lp_out[r*ld_lp] = log_softmax(logits)[token]
+// of row r, natural log, -inf for a row with no logit above -inf.  Fixed summation order: bitwise independent of `rows`.
 // Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
 // reduces them under launch_argmax_final's tie rule and compares with the draft tokens staged in ids [B][ld] (columns 1..n; -1 =
 // not a word).  a = the leading positions at which every row's token equals its draft token; ids columns 1..min(a + 1, n) and
 // sep_cnt[0 .. min(a + 1, n) - 1] become what the token loop would have written; host (page-locked int32[2]) = {a, all rows
 // emitted SEP in one of those steps}.  tok: int[B * n] scratch; ticket: one word, zero between launches.
 hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
-                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s);
+                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s,
+                               const float* amax_sum = nullptr, int* lp_tok = nullptr, float* lp_out = nullptr, int ld_lp = 0);
+// amax_sum + lp_out (both or neither; lp_tok: int[B * n] scratch, ld_lp >= n): lp_out[r*ld_lp + j] = the log-probability of the
+// token at position j (launch_argmax_final's value of that row) for the covered positions; columns behind them are not written.
 
 // ---- attention ---------------------------------------------------------------------------
 // Full (unmasked) self-attention over groups of S rows: qkv [G*S][3*W] bf16 (q | k | v, head h

@@ -348,21 +348,58 @@ __device__ __forceinline__ void argmax_partials_waves(const float* __restrict__ 
     if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
     __syncthreads();
 }
-__device__ __forceinline__ int argmax_partials_pick(const float* sv, const int* si, float best, int bi) {
+__device__ __forceinline__ int argmax_partials_pick(const float* sv, const int* si, float best, int bi, float* vmax = nullptr) {
     for (int w = 1; w < 4; ++w)
         if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
     if (bi == 0x7fffffff) bi = 0;
+    if (vmax) *vmax = best;
     return bi;
 }
+// Log-probability of the row's winner from the third partial of the vocabulary head (skinny.hip: sum[t] = sum of exp(logit -
+// val[t]) over tile t): log_softmax(logits)[winner] = -log(sum_t sum[t] * exp(val[t] - M)), M = the row's maximum (the winner's
+// logit), tiles without a logit above -inf skipped.  The order of the adds is fixed and does not depend on the rows beside this
+// one: thread tid takes tiles tid, tid + 256, .. ascending, the xor butterfly 32 .. 1 inside the wave, then waves 0 .. 3 in that
+// order.  Called by every thread (one barrier inside; ss = four words of LDS); thread 0's return value is the row's, -inf for a
+// row with no logit above -inf (M = -inf).  The partials of a row are 3 x 7.6 KB at the GIT vocabulary: L2 resident.
+__device__ __forceinline__ float lp_partials(const float* __restrict__ val, const float* __restrict__ sum, const size_t base,
+                                             const int ntiles, const float M, float* ss) {
+    const int tid = threadIdx.x;
+    float acc = 0.f;
+    if (M != -INFINITY) {                                                  // (uniform: M comes from LDS)
+        for (int i0 = tid; i0 < ntiles; i0 += 256 * 8) {
+            float v8[8], s8[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = min(i0 + 256 * u, ntiles - 1);
+                v8[u] = val[base + i];
+                s8[u] = sum[base + i];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)                                     // (+ 0.f leaves a sum of non-negative terms as it is)
+                acc += (i0 + 256 * u < ntiles && v8[u] != -INFINITY) ? s8[u] * __expf(v8[u] - M) : 0.f;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((tid & 63) == 0) ss[tid >> 6] = acc;
+    __syncthreads();
+    if (M == -INFINITY) return -INFINITY;
+    return -__logf(((ss[0] + ss[1]) + ss[2]) + ss[3]);
+}
 
-template <int NV>
+// LP: also lp_out[r * ld_lp] = the log-probability of the token (lp_partials); a form of its own, so that the launches without it
+// stay the code they were
+template <int NV, bool LP = false>
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
                                                            int ntiles, int row_stride, int row_off,
                                                            int64_t* __restrict__ out, int ld_out,
-                                                           int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb) {
+                                                           int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb,
+                                                           const float* __restrict__ psum = nullptr, float* __restrict__ lp_out = nullptr,
+                                                           int ld_lp = 0) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int chosen;
+    __shared__ float vmax, ss[4];
     const int r = blockIdx.x, tid = threadIdx.x;
     const size_t base = (size_t)(r * row_stride + row_off) * ntiles;
     // gamma / beta of the next step's input row do not depend on the token chosen below: requested now (wave 0 uses them)
@@ -375,10 +412,15 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
     int bi;
     argmax_partials_waves(val, idx, base, ntiles, sv, si, best, bi);
     if (tid == 0) {
-        bi = argmax_partials_pick(sv, si, best, bi);
+        bi = argmax_partials_pick(sv, si, best, bi, LP ? &vmax : nullptr);
         out[(size_t)r * ld_out] = bi;
         if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
         chosen = bi;
+    }
+    if (LP) {
+        __syncthreads();
+        const float lp = lp_partials(val, psum, base, ntiles, vmax, ss);
+        if (tid == 0) lp_out[(size_t)r * ld_lp] = lp;
     }
     if (NV > 0) {       // the next step's input row: embedding of the token just chosen + LayerNorm (one wave)
         __syncthreads();
@@ -403,17 +445,28 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
 //   ids[r][1 .. covered] = the model's tokens (columns 1..a are the accepted draft tokens, the same values);
 //   sep_cnt[t] = rows whose token at step t < covered is SEP, counted from the model's tokens as the token loop counts them;
 //   host[0] = a, host[1] = 1 when all rows emitted SEP in one of the covered steps (page-locked host words).
+// LP: every workgroup also computes its position's log-probability (lp_partials) and hands its bits over beside the token
+// (lp_tok: int[B * n]); the bookkeeping wave writes those of the covered positions to lp_out[r * ld_lp + j] and nothing behind them.
+template <bool LP>
 __global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restrict__ val, const int* __restrict__ idx, int ntiles, int B,
                                                            int n, int64_t* ids, int ld, int* tok, unsigned* ticket,
-                                                           int32_t* __restrict__ sep_cnt, int sep_id, int32_t* host) {
+                                                           int32_t* __restrict__ sep_cnt, int sep_id, int32_t* host,
+                                                           const float* __restrict__ psum, int* lp_tok, float* lp_out, int ld_lp) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int last_flag;
+    __shared__ float vmax, ss[4];
     const int m = blockIdx.x, tid = threadIdx.x;
     float best;
     int bi;
     argmax_partials_waves(val, idx, (size_t)m * ntiles, ntiles, sv, si, best, bi);
-    if (tid == 0) __hip_atomic_store(tok + m, argmax_partials_pick(sv, si, best, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0)
+        __hip_atomic_store(tok + m, argmax_partials_pick(sv, si, best, bi, LP ? &vmax : nullptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (LP) {
+        __syncthreads();
+        const float lp = lp_partials(val, psum, (size_t)m * ntiles, ntiles, vmax, ss);
+        if (tid == 0) __hip_atomic_store(lp_tok + m, __float_as_int(lp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
@@ -439,6 +492,8 @@ __global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restri
             const int t = __hip_atomic_load(tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             ids[(size_t)r * ld + j + 1] = t;
             seps += t == sep_id;
+            if (LP)
+                lp_out[(size_t)r * ld_lp + j] = __int_as_float(__hip_atomic_load(lp_tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         }
     }
     if (j < covered) sep_cnt[j] = seps;
@@ -750,12 +805,27 @@ hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int 
 }
 
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s, const NextEmbed* emb) {
+                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s, const NextEmbed* emb,
+                               const float* amax_sum, float* lp_out, int ld_lp) {
     const NextEmbed e = emb ? *emb : NextEmbed{};
     const int nv = emb ? (e.D + 255) / 256 : 0;
     if (emb && (nv < 1 || nv > 4 || (e.D & 3) || !e.word || !e.pos || !e.gamma || !e.beta || !e.xf || !e.xb)) return hipErrorInvalidValue;
-#define AF_LAUNCH(NV) hipLaunchKernelGGL(argmax_final_kernel<NV>, dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, row_off, \
-                                         out, ld_out, sep_cnt, step, sep_id, e)
+    if ((amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1)) return hipErrorInvalidValue;
+    if (lp_out) {
+#define AF_LAUNCH_LP(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, true>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, \
+                                            row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp)
+        switch (nv) {
+            case 0: AF_LAUNCH_LP(0); break;
+            case 1: AF_LAUNCH_LP(1); break;
+            case 2: AF_LAUNCH_LP(2); break;
+            case 3: AF_LAUNCH_LP(3); break;
+            default: AF_LAUNCH_LP(4); break;
+        }
+#undef AF_LAUNCH_LP
+        return hipGetLastError();
+    }
+#define AF_LAUNCH(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, false>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, row_off, \
+                                         out, ld_out, sep_cnt, step, sep_id, e, (const float*)nullptr, (float*)nullptr, 0)
     switch (nv) {
         case 0: AF_LAUNCH(0); break;
         case 1: AF_LAUNCH(1); break;
@@ -768,11 +838,17 @@ hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int n
 }
 
 hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
-                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s) {
+                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s, const float* amax_sum,
+                               int* lp_tok, float* lp_out, int ld_lp) {
     if (B <= 0 || n < 1 || n > 63 || ld < n + 1 || ntiles <= 0 || !amax_val || !amax_idx || !ids || !tok || !ticket || !sep_cnt || !host)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(draft_accept_kernel, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt,
-                       sep_id, host);
+    if ((amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && (!lp_tok || ld_lp < n))) return hipErrorInvalidValue;
+    if (lp_out)
+        hipLaunchKernelGGL(draft_accept_kernel<true>, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket,
+                           sep_cnt, sep_id, host, amax_sum, lp_tok, lp_out, ld_lp);
+    else
+        hipLaunchKernelGGL(draft_accept_kernel<false>, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket,
+                           sep_cnt, sep_id, host, (const float*)nullptr, (int*)nullptr, (float*)nullptr, 0);
     return hipGetLastError();
 }
 

@@ -71,6 +71,9 @@ __device__ __forceinline__ void load_wfrags(const void* W, const void* Wpk, cons
 }
 
 // fp32 logits of one 16 x 16 tile (lane: out[m][n .. n+3]) and the tile's arg-max partial per row (ascending n: first max wins)
+// LSE: also the tile's third partial (a.amax_sum) -- kernels of their own, picked by the launcher where the pointer is set, so that
+// the launches without it stay the code they were
+template <bool LSE>
 __device__ __forceinline__ void logits_epilogue(const SkinnyArgs& a, const float (&y)[4], const int m, const bool mvalid, const int n,
                                                 const int fq, const int tile, const int ntiles) {
     if (mvalid && a.out) {
@@ -95,10 +98,24 @@ __device__ __forceinline__ void logits_epilogue(const SkinnyArgs& a, const float
             a.amax_val[(size_t)m * ntiles + tile] = best;
             a.amax_idx[(size_t)m * ntiles + tile] = bi;
         }
+        // third partial (token log-probabilities attached): sum of exp(logit - tile max) over the tile's valid columns, the lane's
+        // own columns in ascending order, then the four column groups by the butterfly above; 0 for a tile with no logit above -inf
+        // (never -inf - -inf).  argmax_final / draft_accept (rowops.hip) merge the tiles in a fixed order.
+        if (LSE) {
+            float se = 0.f;
+            if (best != -INFINITY) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (n + r < a.N) se += __expf(y[r] - best);
+            }
+#pragma unroll
+            for (int off = 16; off < 64; off <<= 1) se += __shfl_xor(se, off);
+            if (fq == 0 && mvalid) a.amax_sum[(size_t)m * ntiles + tile] = se;
+        }
     }
 }
 
-template <int K32, int EPI, bool FP8, bool LNR>
+template <int K32, int EPI, bool FP8, bool LNR, bool LSE = false>
 __global__ __launch_bounds__(64) void skinny_full_kernel(SkinnyArgs a) {
     const int lane = threadIdx.x;
     const int frow = lane & 15, fq = lane >> 4;
@@ -193,7 +210,7 @@ __global__ __launch_bounds__(64) void skinny_full_kernel(SkinnyArgs a) {
                 }
             }
         } else {  // SK_BIAS_F32: logits (+ arg-max partial of this 16-column tile)
-            logits_epilogue(a, y, m, mvalid, n, fq, blockIdx.x, gridDim.x);
+            logits_epilogue<LSE>(a, y, m, mvalid, n, fq, blockIdx.x, gridDim.x);
         }
     }
 }
@@ -206,8 +223,8 @@ __global__ __launch_bounds__(64) void skinny_full_kernel(SkinnyArgs a) {
 // ds_read_b128 group fall into 16 different 16-byte slots), requested ahead of the weight fragments so that the LDS copy
 // waits for it alone (vmcnt counts in order) while the weights stay in flight; m-tile mt + 1 is in flight under m-tile mt
 // (two LDS images).  Every output element is the same MFMA chain over the same operands as in skinny_full: same bits.
-template <int K32, bool FP8>
-__global__ __launch_bounds__(256) void skinny_head_kernel(SkinnyArgs a, const int ntiles) {
+template <int K32, bool FP8, bool LSE>
+__device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int ntiles) {
     constexpr int PITCH = K32 * 64 + 16, CPR = K32 * 4, NC = (16 * CPR + 255) / 256;     // 16 x CPR 16-byte pieces over 256 threads
     __shared__ __attribute__((aligned(16))) char xs[2][16 * PITCH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -256,11 +273,17 @@ __global__ __launch_bounds__(256) void skinny_head_kernel(SkinnyArgs a, const in
         float y[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[r] = acc[r] + bias[r];
-        logits_epilogue(a, y, m < a.M ? m : a.M - 1, mvalid, n, fq, tile, ntiles);
+        logits_epilogue<LSE>(a, y, m < a.M ? m : a.M - 1, mvalid, n, fq, tile, ntiles);
         if (mt + 1 < mtiles) lstore((mt + 1) & 1);              // the image m-tile mt - 1 was read from: every wave is past the
         __syncthreads();                                         // barrier that closed that iteration
     }
 }
+
+template <int K32, bool FP8>
+__global__ __launch_bounds__(256) void skinny_head_kernel(SkinnyArgs a, const int ntiles) { skinny_head_body<K32, FP8, false>(a, ntiles); }
+// the same kernel with the third partial of the token log-probabilities (logits_epilogue<true>)
+template <int K32, bool FP8>
+__global__ __launch_bounds__(256) void skinny_head_lse_kernel(SkinnyArgs a, const int ntiles) { skinny_head_body<K32, FP8, true>(a, ntiles); }
 
 // ---- one/two-row prologue over many slabs: three waves share the reduce ---------------------------------------------------
 // The fused FFN launch (ffn_txt.hip) leaves dec_ffn / 64 = 48 slabs; the single wave of skinny_full<LNR> walks them in three
@@ -403,10 +426,13 @@ template <int K32, bool FP8>
 hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s) {
     const int grid = (a.N + 15) / 16;
     if (a.ln.kind) return hipErrorInvalidValue;          // row prologue: launch_full_rows
+    const bool lse = a.amax_sum != nullptr;              // the third partial of the token log-probabilities: the <.., true> kernels
+    if (lse && (epi != SK_BIAS_F32 || !a.amax_val || !a.amax_idx)) return hipErrorInvalidValue;
     if constexpr (K32 * 64 * 32 + 512 <= 64 * 1024) {          // two LDS images of 16 rows (K <= 768)
         // the vocabulary head (many tiles over few rows): four tiles per workgroup share the activation rows through LDS
         if (epi == SK_BIAS_F32 && g_head_share && grid >= 4 && a.ldx % 8 == 0 && ((uintptr_t)a.X & 15) == 0) {
-            hipLaunchKernelGGL((skinny_head_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
+            if (lse) hipLaunchKernelGGL((skinny_head_lse_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
+            else hipLaunchKernelGGL((skinny_head_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
             return hipGetLastError();
         }
     }
@@ -414,7 +440,10 @@ hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s) {
         case SK_BIAS_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_GELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_GELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_RELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_RELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
-        case SK_BIAS_F32: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
+        case SK_BIAS_F32:
+            if (lse) hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, true>), dim3(grid), dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, false>), dim3(grid), dim3(64), 0, s, a);
+            break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -191,17 +191,23 @@ struct gitcap_student : HandleCore {
     // ids / steps buffers, which are copied to the caller's after the replay
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct GreedyGraph { int B, max_len, stop; bool rows_pro, head_share; hipGraphExec_t exec; };
+    struct GreedyGraph { int B, max_len, stop; bool rows_pro, head_share, lp; hipGraphExec_t exec; };
     std::vector<GreedyGraph> graphs;
     // draft verification (gitcap_student_*_greedy_draft): the token steps t = 1 .. max_len - 1 of a (B, max_len, switches) as one
     // graph each (step[t - 1]; the stop rule is not in a step), captured together at the first draft call with that key; acc_tok /
     // acc_ticket = draft_accept_kernel's scratch, acc_host = its page-locked {accepted, stop rule fired}, read behind acc_ev
-    struct TailGraphs { int B, max_len; bool rows_pro, head_share; std::vector<hipGraphExec_t> step; };
+    struct TailGraphs { int B, max_len; bool rows_pro, head_share, lp; std::vector<hipGraphExec_t> step; };
     std::vector<TailGraphs> tails;
     int* acc_tok = nullptr;
     unsigned* acc_ticket = nullptr;
     int32_t* acc_host = nullptr;
     hipEvent_t acc_ev = nullptr;
+    // token log-probabilities (gitcap_student_attach_token_logprobs): lp_attach / lp_ld = the pending one-shot attachment; the first
+    // attach allocates amax_sum (the head's third partial, sized as amax_val), acc_lp (draft_accept_kernel's hand-over words) and
+    // g_lp, the handle's own [B][max_len] rows the captured loops write (copied to the caller's buffer behind the replay, like g_ids)
+    float *lp_attach = nullptr, *amax_sum = nullptr, *g_lp = nullptr;
+    int lp_ld = 0;
+    int* acc_lp = nullptr;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -272,7 +278,7 @@ int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx,
 
 // model.py:128-154 for rows x T query positions t0..t0+T-1 (K/V of earlier positions come from the cache)
 int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int t0, int T, float* logits_out,
-                 int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s) {
+                 int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s, float* lp_out = nullptr, int ld_lp = 0) {
     const gitcap_student_config& c = h->c;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student: decoder called before set_memory");
@@ -344,10 +350,12 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         ha.X = h->xb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows;
     }
     if (argmax_out) { ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx; }
+    if (lp_out && (!argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
+    if (lp_out) ha.amax_sum = h->amax_sum;
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     if (argmax_out)
         HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
-                                        sep_cnt, step, c.sep_token_id, s));
+                                        sep_cnt, step, c.sep_token_id, s, nullptr, lp_out ? h->amax_sum : nullptr, lp_out, ld_lp));
     return 0;
 }
 
@@ -514,8 +522,27 @@ int greedy_check(gitcap_student* h, const char* who, int max_len, int stop, cons
     return 0;
 }
 
+// the pending attachment of gitcap_student_attach_token_logprobs: taken (and with that consumed) by every greedy-family entry point
+struct LpAttach { float* p; int ld; };
+LpAttach take_lp(gitcap_student* h) {
+    const LpAttach a{h->lp_attach, h->lp_ld};
+    h->lp_attach = nullptr; h->lp_ld = 0;
+    return a;
+}
+int lp_check(gitcap_student* h, const char* who, const LpAttach& lp, int max_len) {
+    if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached token log-probability buffer has ld < max_len");
+    return 0;
+}
+// g_lp [B][max_len] -> the caller's rows (pitch lp.ld): columns behind max_len are not touched
+hipError_t lp_copy_out(gitcap_student* h, const LpAttach& lp, int B, int max_len, hipStream_t s) {
+    return hipMemcpy2DAsync(lp.p, (size_t)lp.ld * 4, h->g_lp, (size_t)max_len * 4, (size_t)max_len * 4, (size_t)B, hipMemcpyDeviceToDevice, s);
+}
+
 // the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
-int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
+// lp.p set: the loop with token log-probabilities (a graph of its own; column t of g_lp = step t's)
+int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
+                LpAttach lp = LpAttach{nullptr, 0}) {
+    const bool want_lp = lp.p != nullptr;
     int rc;
     const int ld = max_len + 1;
     // The token loop is launch-latency bound (26 kernels per token): it is captured once per (B, max_len, stop)
@@ -525,7 +552,8 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
         HIP_OK(h, launch_fill_i64(h->g_ids, ld, B, h->c.cls_token_id, q));                 // model.py:171
         HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
         for (int t = 0; t < max_len; ++t) {                                                  // model.py:173-182
-            int r = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q);
+            int r = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q,
+                                 want_lp ? h->g_lp + t : nullptr, max_len);
             if (r) return r;
         }
         HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
@@ -534,7 +562,7 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
     if (use_graph) {
         hipGraphExec_t exec = nullptr;
         for (auto& g : h->graphs)
-            if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share) exec = g.exec;
+            if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp) exec = g.exec;
         if (!exec) {
             hipGraph_t graph = nullptr;
             if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -546,7 +574,7 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
             e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             HIP_OK(h, e);
-            h->graphs.push_back({B, max_len, stop, g_row_prologue, g_head_share, exec});
+            h->graphs.push_back({B, max_len, stop, g_row_prologue, g_head_share, want_lp, exec});
         }
         HIP_OK(h, hipGraphLaunch(exec, s));
     } else if ((rc = enqueue_loop(s))) {
@@ -554,6 +582,7 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
     }
     HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (want_lp) HIP_OK(h, lp_copy_out(h, lp, B, max_len, s));
     return 0;
 }
 
@@ -564,11 +593,11 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
 // every leading draft token that equals it is a token the loop would have produced: accepted, together with the K/V rows the pass
 // wrote for its position.  The first position that differs holds the loop's own token (the corrected one).  The steps behind it
 // are the loop's own launches, text_forward(t, 1).
-int draft_tail_graphs(gitcap_student* h, int B, int max_len, std::vector<hipGraphExec_t>** out) {
+int draft_tail_graphs(gitcap_student* h, int B, int max_len, bool want_lp, std::vector<hipGraphExec_t>** out) {
     for (auto& t : h->tails)
-        if (t.B == B && t.max_len == max_len && t.rows_pro == g_row_prologue && t.head_share == g_head_share) { *out = &t.step; return 0; }
+        if (t.B == B && t.max_len == max_len && t.rows_pro == g_row_prologue && t.head_share == g_head_share && t.lp == want_lp) { *out = &t.step; return 0; }
     const int ld = max_len + 1;
-    gitcap_student::TailGraphs tg{B, max_len, g_row_prologue, g_head_share, {}};
+    gitcap_student::TailGraphs tg{B, max_len, g_row_prologue, g_head_share, want_lp, {}};
     if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     int rc = 0;
     for (int t = 1; t < max_len && !rc; ++t) {
@@ -576,7 +605,8 @@ int draft_tail_graphs(gitcap_student* h, int B, int max_len, std::vector<hipGrap
         hipGraphExec_t exec = nullptr;
         hipError_t e = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-            rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, h->cap_stream);
+            rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, h->cap_stream,
+                              want_lp ? h->g_lp + t : nullptr, max_len);
             e = hipStreamEndCapture(h->cap_stream, &graph);
         }
         if (!rc && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -603,9 +633,10 @@ int draft_check(gitcap_student* h, const char* who, const int64_t* draft_ids, in
 
 // verify -> accept -> tail against the memory K|V in h->memkv; same results as greedy_loop(B, max_len, stop)
 int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_draft, int n, int max_len, int stop, int64_t* ids_out,
-                      int32_t* steps_out, int32_t* accepted_out, hipStream_t s) {
+                      int32_t* steps_out, int32_t* accepted_out, hipStream_t s, LpAttach lp = LpAttach{nullptr, 0}) {
     int rc;
     const int ld = max_len + 1;
+    const bool want_lp = lp.p != nullptr;
     static const bool use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
     if (!h->acc_host) {
         HIP_OK(h, hipHostMalloc((void**)&h->acc_host, 16, hipHostMallocMapped));
@@ -613,7 +644,7 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     }
     // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
     std::vector<hipGraphExec_t>* steps = nullptr;
-    if (use_graph && (rc = draft_tail_graphs(h, B, max_len, &steps))) return rc;
+    if (use_graph && (rc = draft_tail_graphs(h, B, max_len, want_lp, &steps))) return rc;
     // 1. verify: one pass over positions 0 .. n-1 of the staged draft (K/V rows of those positions -> the cache), then the
     //    vocabulary head over all B * n rows, arg-max partials only
     hipLaunchKernelGGL(student_draft_stage_kernel, dim3((B * (n + 1) + 255) / 256), dim3(256), 0, s, draft, ld_draft, n, B, h->V,
@@ -625,11 +656,13 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     SkinnyArgs ha{};
     ha.X = h->xb; ha.ldx = h->D; ha.W = h->head_w; ha.bias = h->head_b; ha.M = B * n; ha.N = h->V; ha.K = h->D; ha.ldo = h->V;
     ha.T = 1; ha.row_stride = 1; ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx;
+    if (want_lp) ha.amax_sum = h->amax_sum;     // covered positions: their log-probabilities come from this pass (the same bits as the loop's)
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     // 2. accept
     *(volatile int32_t*)h->acc_host = -1;
     HIP_OK(h, launch_draft_accept(h->amax_val, h->amax_idx, ntiles, B, n, h->g_ids, ld, h->acc_tok, h->acc_ticket, h->sep_cnt,
-                                  h->c.sep_token_id, h->acc_host, s));
+                                  h->c.sep_token_id, h->acc_host, s, want_lp ? h->amax_sum : nullptr, want_lp ? h->acc_lp : nullptr,
+                                  want_lp ? h->g_lp : nullptr, max_len));
     HIP_OK(h, hipEventRecord(h->acc_ev, s));
     HIP_OK(h, hipEventSynchronize(h->acc_ev));
     const int a = ((volatile int32_t*)h->acc_host)[0];
@@ -640,11 +673,13 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     const bool tail = t0 < max_len && !(stop == GITCAP_STOP_ALL_SEP && fired);
     for (int t = t0; tail && t < max_len; ++t) {
         if (use_graph) HIP_OK(h, hipGraphLaunch((*steps)[t - 1], s));
-        else if ((rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, s))) return rc;
+        else if ((rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, s,
+                                    want_lp ? h->g_lp + t : nullptr, max_len))) return rc;
     }
     HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, s));
     HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (want_lp) HIP_OK(h, lp_copy_out(h, lp, B, max_len, s));
     if (accepted_out) *accepted_out = a;
     ++h->draft_calls; h->draft_offered += n; h->draft_accepted += a; h->draft_tail_steps += tail ? max_len - t0 : 0;
     return 0;
@@ -739,12 +774,14 @@ extern "C" {
 int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
                           int32_t* steps_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
+    const LpAttach lp = take_lp(h);
     if (int bad = greedy_check(h, "student_greedy", max_len, stop, ids_out)) return bad;
+    if (int bad = lp_check(h, "student_greedy", lp, max_len)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = set_memory(h, memory, B, s);           // reads the caller's buffer: outside the graph
     if (rc) return rc;
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
 }
 
 // StudentCandidateV1.beam_search (model.py:189-318) on the device with the exact KV cache: k beams per clip as rows
@@ -837,38 +874,62 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
 
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy: null handle");
+    const LpAttach lp = take_lp(h);
     if (int bad = greedy_check(h, "student_window_greedy", max_len, stop, ids_out)) return bad;
+    if (int bad = lp_check(h, "student_window_greedy", lp, max_len)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy: weights not finalized");
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = window_memory(h, "student_window_greedy", 1, s);
     if (rc) return rc;
-    return greedy_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
+    return greedy_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
 }
 
 int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
                                 int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy_draft: null handle");
+    const LpAttach lp = take_lp(h);
     if (int bad = greedy_check(h, "student_greedy_draft", max_len, stop, ids_out)) return bad;
+    if (int bad = lp_check(h, "student_greedy_draft", lp, max_len)) return bad;
     if (int bad = draft_check(h, "student_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = set_memory(h, memory, B, s);
     if (rc) return rc;
-    return greedy_draft_core(h, B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s);
+    return greedy_draft_core(h, B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s, lp);
 }
 
 int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
                                        int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy_draft: null handle");
+    const LpAttach lp = take_lp(h);
     if (int bad = greedy_check(h, "student_window_greedy_draft", max_len, stop, ids_out)) return bad;
+    if (int bad = lp_check(h, "student_window_greedy_draft", lp, max_len)) return bad;
     if (int bad = draft_check(h, "student_window_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy_draft: weights not finalized");
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = window_memory(h, "student_window_greedy_draft", 1, s);
     if (rc) return rc;
-    return greedy_draft_core(h, h->win_B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s);
+    return greedy_draft_core(h, h->win_B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s, lp);
+}
+
+int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: null handle");
+    if (!logprobs_out) { h->lp_attach = nullptr; h->lp_ld = 0; return 0; }
+    if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: ld < 1 or a misaligned pointer");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_token_logprobs: weights not finalized");
+    GUARD(h);
+    if (!h->g_lp) {                             // first attach: sized as amax_val (covers the verify pass's B * n rows)
+        const size_t Mt = (size_t)h->Mt, ntiles = ((size_t)h->V + 15) / 16;
+        int rc;
+        if ((rc = dev_alloc(h, &h->amax_sum, Mt * ntiles)) || (rc = dev_alloc(h, &h->acc_lp, Mt)) || (rc = dev_alloc(h, &h->g_lp, Mt))) {
+            h->g_lp = nullptr;
+            return rc;
+        }
+    }
+    h->lp_attach = logprobs_out; h->lp_ld = ld;
+    return 0;
 }
 
 int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {

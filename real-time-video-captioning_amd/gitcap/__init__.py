@@ -9,4 +9,7 @@ def __getattr__(name):
     if name == "GitCaptioner":
         from .model import GitCaptioner
         return GitCaptioner
+    if name == "caption_confidence":
+        from .confidence import caption_confidence
+        return caption_confidence
     raise AttributeError(name)

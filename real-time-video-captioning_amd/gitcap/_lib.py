@@ -86,11 +86,19 @@ SYMBOLS = {
                                         POINTER(CDbgNextEmbed), c_void_p]),
     "gitcap_dbg_draft_accept": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                         POINTER(c_int32), c_void_p]),
+    # the same three with the third partial / the token's log-probability (tests/test_logprob_gpu.py)
+    "gitcap_dbg_vocab_head_lse": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_argmax_final_lp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                           POINTER(CDbgNextEmbed), c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_draft_accept_lp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int, POINTER(c_int32), c_void_p, c_void_p, c_int, c_void_p]),
     "gitcap_dbg_beam_init": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_int, c_void_p]),
     "gitcap_dbg_beam_step": (c_int, [POINTER(CDbgBeamBuffers), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),
     "gitcap_dbg_beam_finish": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
+    "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),
@@ -110,6 +118,7 @@ SYMBOLS = {
     "gitcap_student_window_greedy_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                                    POINTER(c_int32), c_void_p]),
     "gitcap_student_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
+    "gitcap_student_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),

@@ -256,9 +256,11 @@ class CaptionStream:
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None):
+                 gate=None, logprobs=False):
         self._m = model
         self._gate = gate
+        self._want_lp = logprobs
+        self.last_logprobs = None        # logprobs=True: fp32 [B, steps] of the caption the last push returned (on the CPU when the frames were)
         self._sched = WindowSchedule(batch, window, hop)
         self._max_len, self._mode = max_len, mode
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
@@ -359,6 +361,10 @@ class CaptionStream:
             if self._beam is None:
                 ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
                 steps = torch.zeros((1,), dtype=torch.int32, device=m._dev)
+                lp = None
+                if self._want_lp:
+                    lp = torch.empty((B, self._max_len), dtype=torch.float32, device=m._dev)
+                    m._call("gitcap_attach_token_logprobs", ctypes.c_void_p(lp.data_ptr()), self._max_len)
                 m._call("gitcap_window_greedy", self._max_len, self._mode, vp, ctypes.c_void_p(ids.data_ptr()),
                         ctypes.c_void_p(steps.data_ptr()), m._stream())
             else:
@@ -372,6 +378,8 @@ class CaptionStream:
             return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]), "logits_dict": [], "visual_features": mv(vis)}
         if self._mode == STOP_ALL_SEP:
             ids = ids[:, :1 + int(steps.item())]
+        if lp is not None:
+            self.last_logprobs = mv(lp[:, :ids.shape[1] - 1])
         return mv(ids)
 
 
@@ -806,29 +814,34 @@ class GitCaptioner(nn.Module):
         return [l[None] for l in logits], [v[None] for v in vis], [h for h in hid]
 
     @torch.no_grad()
-    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None) -> torch.Tensor:
+    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
-        truncation the reference's `break` implies is applied afterwards."""
+        truncation the reference's `break` implies is applied afterwards.  return_logprobs=True: (ids, logprobs), logprobs fp32
+        [B, steps] on src's device, column t = log_softmax(step t's logits)[ids[:, t + 1]] (include/gitcap.h:
+        gitcap_attach_token_logprobs; the ids are the same either way)."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
         if src.device.type == "cpu":              # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs)
 
-    def _greedy_decode(self, src, max_len, mode):
+    def _greedy_decode(self, src, max_len, mode, want_lp=False):
         self._drain()
         fr, raw = self._check_frames(src)         # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
         B, F = fr.shape[:2]
-        outs, steps_all = [], []
+        outs, steps_all, lps = [], [], []
         with torch.cuda.device(self._dev):
             for b0 in range(0, B, self.max_batch):
                 chunk = self._to_device(fr[b0:b0 + self.max_batch])      # (a CPU tensor: staged chunk by chunk, stream ordered)
                 ids = torch.empty((chunk.shape[0], max_len + 1), dtype=torch.int64, device=self._dev)
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
+                if want_lp:                      # one-shot: consumed by the greedy call below
+                    lps.append(torch.empty((chunk.shape[0], max_len), dtype=torch.float32, device=self._dev))
+                    self._call("gitcap_attach_token_logprobs", ctypes.c_void_p(lps[-1].data_ptr()), max_len)
                 if raw:
                     self._call("gitcap_greedy_raw", ctypes.c_void_p(chunk.data_ptr()), chunk.shape[0], F, chunk.shape[2],
                                chunk.shape[3], max_len, mode, ctypes.c_void_p(ids.data_ptr()),
@@ -848,7 +861,11 @@ class GitCaptioner(nn.Module):
                 nz = torch.nonzero(all_sep)
                 n = int(nz[0].item()) + 1 if nz.numel() else max_len
             ids = ids[:, :1 + n]
-        return ids.to(src.device) if src.device != ids.device else ids
+        ids = ids.to(src.device) if src.device != ids.device else ids
+        if not want_lp:
+            return ids
+        lp = torch.cat(lps, 0)[:, :ids.shape[1] - 1]
+        return ids, (lp.to(src.device) if src.device != lp.device else lp)
 
     generate = greedy_decode      # the name BASELINE.json's north_star uses for this entry point
 
@@ -1085,14 +1102,18 @@ class GitCaptioner(nn.Module):
 
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
-                       visual_features: bool = False, gate=None) -> CaptionStream:
+                       visual_features: bool = False, gate=None, logprobs: bool = False) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
         default (ids as greedy_decode(max_len, stop)); with beam_size the dict of infer's device search (max_len = its
         max_steps; visual_features adds the window's features).  One live stream per model: opening another one, or .to() /
         .cuda(), invalidates this one.  ``gate``: a gitcap.framegate.FrameGate that decides on the device which pushed camera frames
-        are worth encoding (it is reset here); without one every pushed frame is."""
+        are worth encoding (it is reset here); without one every pushed frame is.  ``logprobs`` (greedy streams only): after a push
+        that returned a caption, ``stream.last_logprobs`` holds its per-token log-probabilities [B, steps] (greedy_decode's
+        return_logprobs; gitcap.caption_confidence turns them into one number per clip)."""
+        if logprobs and beam_size is not None:
+            raise ValueError("logprobs=True is for greedy streams (the beam-search dict carries its own sequence score)")
         window = int(window or max(1, self.cfg.num_frames))
         if batch > self.max_batch or window > self.max_frames or (self.cfg.num_frames > 0 and window > self.cfg.num_frames):
             raise ValueError(f"batch {batch} / window {window} exceed max_batch={self.max_batch} / max_frames={self.max_frames} "
@@ -1112,7 +1133,8 @@ class GitCaptioner(nn.Module):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate)
+        return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
+                             logprobs)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip

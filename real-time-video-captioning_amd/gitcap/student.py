@@ -44,9 +44,11 @@ class StudentCaptionStream:
     ``carry`` a greedy stream offers its previous caption as the draft of the next window call
     (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False):
         self._m = model
         self._gate = gate
+        self._want_lp = logprobs
+        self.last_logprobs = None        # logprobs=True: fp32 [B, steps] of the caption the last push returned (on the CPU when the frames were)
         self._carry, self._prev = bool(carry), None
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
         self._sched = WindowSchedule(batch, model.cfg.mem_tokens, hop)
@@ -117,15 +119,20 @@ class StudentCaptionStream:
                 ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
                 steps = torch.zeros(1, dtype=torch.int32, device=m._dev)
                 last = dict(draft_tokens=0, accepted=0, tail_steps=0)
+                lp = torch.empty((B, self._max_len), dtype=torch.float32, device=m._dev) if self._want_lp else None
                 if self._carry and self._prev is not None:
-                    last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps)
+                    last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
+                    m._attach_logprobs(lp)
                     m._call("gitcap_student_window_greedy", self._max_len, self._mode, ctypes.c_void_p(ids.data_ptr()),
                             ctypes.c_void_p(steps.data_ptr()), m._stream())
                 if self._mode == STOP_ALL_SEP:
                     ids = ids[:, :1 + int(steps.item())]
                 if self._carry:
                     self._prev = ids
+                if lp is not None:
+                    lp = lp[:, :ids.shape[1] - 1]
+                    self.last_logprobs = lp.cpu() if to_cpu else lp
                 for k, v in last.items():
                     self._stats[k] += v
                 self._stats["last"] = last
@@ -340,9 +347,16 @@ class StudentCaptioner(nn.Module):
         fmaps, memory = self.forward_image_enc(x)
         return list(fmaps) + [self.forward_decoder(y, memory)]
 
-    def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor) -> dict:
+    def _attach_logprobs(self, lp: Optional[torch.Tensor]):
+        """One-shot: the next greedy-family call writes its per-token log-probabilities to ``lp`` (fp32 [B, max_len], contiguous)."""
+        if lp is not None:
+            self._call("gitcap_student_attach_token_logprobs", ctypes.c_void_p(lp.data_ptr()), lp.shape[1])
+
+    def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor,
+                    lp: Optional[torch.Tensor] = None) -> dict:
         """One of the two draft entry points (``head`` = the arguments in front of the draft's); ``draft`` int64 [B, 1+n] on
-        either device, trimmed to max_len columns beyond CLS.  -> what the call offered, accepted and decoded behind it."""
+        either device, trimmed to max_len columns beyond CLS.  -> what the call offered, accepted and decoded behind it.
+        ``lp``: see _attach_logprobs."""
         B = ids.shape[0]
         if draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] < 2 or draft.dtype != torch.int64:
             raise ValueError(f"draft must be int64 [{B}, 1+n] with n >= 1, got {draft.dtype} {tuple(draft.shape)}")
@@ -350,6 +364,7 @@ class StudentCaptioner(nn.Module):
         n = d.shape[1] - 1
         acc = ctypes.c_int32(-1)
         before = self._draft_stats()
+        self._attach_logprobs(lp)
         self._call(name, *head, ctypes.c_void_p(d.data_ptr()), n + 1, n, max_len, mode, ctypes.c_void_p(ids.data_ptr()),
                    ctypes.c_void_p(steps.data_ptr()), ctypes.byref(acc), self._stream())
         self.last_accepted = int(acc.value)
@@ -363,14 +378,16 @@ class StudentCaptioner(nn.Module):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
-                      draft: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      draft: Optional[torch.Tensor] = None, return_logprobs: bool = False):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
         ``draft``: int64 [B, 1+n], a guess at the result (e.g. the previous caption of a live stream; column 0 is taken as CLS,
         any ids are allowed).  The result is the one without it, bit for bit: the draft is verified in one pass, the tokens the
         loop would have produced anyway are accepted (``last_accepted`` = their number) and only the rest is decoded step by
-        step (include/gitcap.h: gitcap_student_greedy_draft).  The call waits on the host for the verify pass."""
+        step (include/gitcap.h: gitcap_student_greedy_draft).  The call waits on the host for the verify pass.
+        ``return_logprobs``: -> (ids, logprobs), logprobs fp32 [B, steps] on ``src``'s device, column t =
+        log_softmax(step t's logits)[ids[:, t + 1]]; with a ``draft`` bit for bit the values without it."""
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
@@ -380,15 +397,21 @@ class StudentCaptioner(nn.Module):
         B = mem.shape[0]
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
+        lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
         with torch.cuda.device(self._dev):
             if draft is not None:
-                self._draft_call("gitcap_student_greedy_draft", (ctypes.c_void_p(mem.data_ptr()), B), draft, max_len, mode, ids, steps)
+                self._draft_call("gitcap_student_greedy_draft", (ctypes.c_void_p(mem.data_ptr()), B), draft, max_len, mode, ids, steps, lp)
             else:
+                self._attach_logprobs(lp)
                 self._call("gitcap_student_greedy", ctypes.c_void_p(mem.data_ptr()), B, max_len, mode,
                            ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
-        return ids.to(out_dev) if out_dev != ids.device else ids
+        ids = ids.to(out_dev) if out_dev != ids.device else ids
+        if lp is None:
+            return ids
+        lp = lp[:, :n]
+        return ids, (lp.to(out_dev) if out_dev != lp.device else lp)
 
     generate = greedy_decode
 
@@ -415,7 +438,8 @@ class StudentCaptioner(nn.Module):
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
-                       beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False) -> StudentCaptionStream:
+                       beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
+                       logprobs: bool = False) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -425,7 +449,11 @@ class StudentCaptioner(nn.Module):
         ``gate``: a FrameGate that decides on the device which pushed camera frames are worth encoding (it is reset here);
         without one every pushed frame is.
         ``carry``: a greedy stream passes its previous caption as the draft of the next window call (greedy_decode's ``draft``):
-        the same captions; ``stats()`` tells how much of the drafts was accepted.  Not with ``beams``."""
+        the same captions; ``stats()`` tells how much of the drafts was accepted.  Not with ``beams``.
+        ``logprobs`` (greedy streams only): after a push that returned a caption, ``stream.last_logprobs`` holds its per-token
+        log-probabilities [B, steps] (greedy_decode's return_logprobs); works with ``gate`` and ``carry``."""
+        if logprobs and beams is not None:
+            raise ValueError("logprobs=True is for greedy streams: it cannot be combined with beams")
         if carry and beams is not None:
             raise ValueError("carry=True verifies the previous greedy caption: it cannot be combined with beams")
         if not self._native():
@@ -446,7 +474,7 @@ class StudentCaptioner(nn.Module):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
