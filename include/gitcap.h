@@ -454,6 +454,77 @@ int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* bb, const float* cand_sc
 int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* bb, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
                            void* stream);
 
+/* The text-row kernels of the token loop, one launcher per hook on caller-owned device buffers (tests/test_text_rows_gpu.py; a
+ * plain fp64 statement of each: tests/text_rows_reference.py).  No allocation, no handle; GITCAP_ERR_ARG for arguments a launcher
+ * rejects.  Weights are [Npad16][K] (rows padded to a multiple of 16), bf16, or e4m3 codes with one power-of-two scale per row.
+ *   pack_frags:    dst = the fragment-major copy [tile = n / 16][k32 = k / 32][lane][8] of src [rows16][K], lane = n % 16 +
+ *                  16 * ((k % 32) / 8); elem_bytes 2 (bf16) or 1 (e4m3 codes); rows16 % 16 == 0, K % 32 == 0.
+ *   kv_quant_v:    the V slice of kv bf16 [rows][3 D] (columns 2 D ..) -> e4m3 codes v8 [H][pitch][64] and scales vs fp32 [H][pitch],
+ *                  head-major, pitch >= rows; per (row, head) the scale is the smallest 2^e, e >= -126, with amax <= 448 * 2^e (1 for
+ *                  an all-zero group), codes round to nearest even.  Rows >= `rows` of a head are not written.
+ *   skinny:        out[orow(m)][n] = epi(X[m] . W[n] * wscale[n] + bias[n]) as bf16, orow(m) = (m / T) * row_stride + row_off + m % T,
+ *                  n < N; epi 0 bias, 1 + erf-GELU, 2 + ReLU; K in 64, 128, 256, 576, 768, 1024 (e4m3: 128, 768).  Wpk (nullable):
+ *                  the pack_frags copy of W, read instead of it.  ln_kind != 0 (M <= 2; K 64, 128, 576, 768; bf16; epi 0 or 2): X
+ *                  is not read, the rows are 1: LayerNorm(sum_s ln_slabs[s][m] + ln_bias + ln_resid[m]) (slabs fp32 [nslab][M][K])
+ *                  or 2: LayerNorm(ln_word[id] + ln_pos[ln_t0 + j]), id = ln_ids[(m / ln_T) * ln_ld_ids + m % ln_T] clamped into
+ *                  [0, ln_vocab), j = m % ln_T; their bf16 rounding is the GEMM operand and ln_xf [M][K] receives the fp32 rows.
+ *   skinny_splitk: slabs[s][m][0..N) = X[m][s Ks .. (s + 1) Ks) . W[n][the same]^T * wscale[n] (fp32 [ksplit][M][ldo], rows < M only),
+ *                  Ks = K / ksplit in 32 x {1, 2, 6, 8, 12} (e4m3: 1, 2, 12); ksplit 0 = the launcher's default; N % 16 == 0.
+ *   ln_reduce:     xf / xb [M][D] = LayerNorm(sum_s slabs[s][m] + bias + resid[m]) as fp32 / bf16; nslab 1..64, D % 4 == 0, <= 1024.
+ *   ffn_txt:       slabs[s][m][0..D) = h[m][64 s .. 64 s + 63] . W2[:, the same]^T, h = bf16(erf-GELU(X W1^T + b1)); W1pk / W2pk the
+ *                  pack_frags copies of W1 [F][D] / W2 [D][F] (bf16, or e4m3 with w1scale [F] / w2scale [D]); D 128 or 768, F % 64 == 0.
+ *   txt_block:     the attention sub-layer of M = rows * T text rows (a plain-C mirror of TxtBlockArgs; csrc/kernels.h).  Query m =
+ *                  (r, j) at position t0 + j reads q from kv_txt [rows][Tmax][3 D] (q | k | v) and attends the S_img image keys of clip
+ *                  r / beams in kv_img [clips * S_img][3 D] and the text keys 0 .. t0 + j of row r, scale 1/8, H = D / 64 heads; with
+ *                  v8_img / vs_img (kv_quant_v's output, pitch v8_pitch >= clips * S_img) the image V is code * scale.  part [M][H][D]
+ *                  = bf16(ctx_h) . aow[:, 64 h .. 64 h + 63]^T per head (aow [D][D] bf16, aowpk its pack_frags copy or NULL; or e4m3
+ *                  codes with aoscale [D], aowpk ignored); xs / xsb [M][D] = LayerNorm(sum_h part + aob + xin) as fp32 / bf16.  cnt [M]
+ *                  are the arrival tickets: zero before the first launch, zero again after every launch.  nt_kv: non-temporal K/V
+ *                  loads (same bits).  D 128 or 768; t0 + T <= Tmax. */
+int gitcap_dbg_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, void* stream);
+int gitcap_dbg_kv_quant_v(const void* kv, void* v8, float* vs, int rows, int D, int H, int64_t pitch, void* stream);
+typedef struct gitcap_dbg_skinny_args {
+    const void* X;
+    int32_t ldx;
+    const void *W, *Wpk;
+    const float *wscale, *bias;
+    int32_t M, N, K;
+    void* out;
+    int32_t ldo, T, row_stride, row_off;
+    int32_t ln_kind;
+    const float* ln_slabs;
+    int32_t ln_nslab;
+    const float *ln_bias, *ln_resid;
+    const int64_t* ln_ids;
+    int32_t ln_ld_ids, ln_T, ln_t0, ln_vocab;
+    const float *ln_word, *ln_pos, *ln_g, *ln_b;
+    float ln_eps;
+    float* ln_xf;
+} gitcap_dbg_skinny_args;
+int gitcap_dbg_skinny(const gitcap_dbg_skinny_args* a, int epi, void* stream);
+int gitcap_dbg_skinny_splitk(const void* X, int ldx, const void* W, const void* Wpk, const float* wscale, int M, int N, int K, int ksplit,
+                             float* slabs, int ldo, void* stream);
+int gitcap_dbg_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid, const float* gamma, const float* beta,
+                         float eps, int M, int D, float* xf, void* xb, void* stream);
+int gitcap_dbg_ffn_txt(const void* X, int ldx, const void* W1pk, const void* W2pk, const float* w1scale, const float* w2scale,
+                       const float* b1, int M, int D, int F, float* slabs, void* stream);
+typedef struct gitcap_dbg_txt_block_args {
+    const void *kv_img, *kv_txt;
+    int32_t rows, beams, t0, T, Tmax, S_img, H, D;
+    const void *aow, *aowpk;
+    const float *aoscale, *aob, *g1, *b1, *xin;
+    float eps;
+    float* part;
+    uint32_t* cnt;
+    float* xs;
+    void* xsb;
+    const void* v8_img;
+    const float* vs_img;
+    int64_t v8_pitch;
+    int32_t nt_kv;
+} gitcap_dbg_txt_block_args;
+int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* a, void* stream);
+
 /* Residual stream of the ViT per block (tests/test_stress_layers_gpu.py: single-block checks on the device's own inputs).
  * While `buf` is non-NULL every SYNCHRONOUS image pass (gitcap_encode / _greedy / _beam_search and their _raw forms) copies
  * the fp32 residual stream x [rows][enc_width] (rows = B * F * tokens per frame, unpadded) to buf + e * rows * enc_width:

@@ -1761,6 +1761,99 @@ int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len,
     return dbg_rc(launch_beam_finish(bb, B, max_len, eos, decoded, logprobs, (hipStream_t)stream));
 }
 
+// ---- text-row kernels of the token loop (tests/test_text_rows_gpu.py): each hook is ONE launcher on caller-owned device buffers,
+// no allocation, no handle; what a launcher does not check itself and a wrong value of which would index outside a buffer is
+// checked here
+int gitcap_dbg_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, void* stream) {
+    if (!src || !dst || K <= 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_pack_frags(src, dst, rows16, K, elem_bytes, (hipStream_t)stream));
+}
+
+int gitcap_dbg_kv_quant_v(const void* kv, void* v8, float* vs, int rows, int D, int H, int64_t pitch, void* stream) {
+    if (!kv || !v8 || !vs || H <= 0 || ((uintptr_t)kv & 15) || ((uintptr_t)v8 & 7)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_kv_quant_v((const bf16_t*)kv, (unsigned char*)v8, vs, rows, D, H, pitch, (hipStream_t)stream));
+}
+
+int gitcap_dbg_skinny(const gitcap_dbg_skinny_args* g, int epi, void* stream) {
+    if (!g || !g->W || !g->out || g->M <= 0 || g->N <= 0 || !skinny_full_ok(g->K) || g->ldo < g->N || g->T <= 0 || g->row_stride < 0 ||
+        g->row_off < 0 || ((uintptr_t)g->W & 15) || ((uintptr_t)g->Wpk & 15) || ((uintptr_t)g->out & 7) || (g->ldo & 3))
+        return GITCAP_ERR_ARG;
+    if (epi != SK_BIAS_BF16 && epi != SK_BIAS_GELU_BF16 && epi != SK_BIAS_RELU_BF16) return GITCAP_ERR_ARG;   // the head: gitcap_dbg_vocab_head
+    if (g->wscale && g->K != 128 && g->K != 768) return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)g->X; a.ldx = g->ldx; a.W = g->W; a.Wpk = g->Wpk; a.wscale = g->wscale; a.bias = g->bias;
+    a.M = g->M; a.N = g->N; a.K = g->K; a.out = g->out; a.ldo = g->ldo; a.T = g->T; a.row_stride = g->row_stride; a.row_off = g->row_off;
+    if (g->ln_kind) {
+        if ((g->ln_kind != 1 && g->ln_kind != 2) || !skinny_row_prologue_ok(g->M, g->K, g->wscale != nullptr) || epi == SK_BIAS_GELU_BF16 ||
+            !g->ln_g || !g->ln_b || !g->ln_xf)
+            return GITCAP_ERR_ARG;
+        if (g->ln_kind == 1 && (!g->ln_slabs || g->ln_nslab <= 0 || !g->ln_bias || !g->ln_resid || g->ln_resid == g->ln_xf)) return GITCAP_ERR_ARG;
+        if (g->ln_kind == 2 && (!g->ln_ids || g->ln_T <= 0 || g->ln_ld_ids < g->ln_T || g->ln_t0 < 0 || g->ln_vocab <= 0 || !g->ln_word || !g->ln_pos))
+            return GITCAP_ERR_ARG;
+        a.ln.kind = g->ln_kind; a.ln.slabs = g->ln_slabs; a.ln.nslab = g->ln_nslab; a.ln.bias = g->ln_bias; a.ln.resid = g->ln_resid;
+        a.ln.ids = g->ln_ids; a.ln.ld_ids = g->ln_ld_ids; a.ln.T = g->ln_T; a.ln.t0 = g->ln_t0; a.ln.vocab = g->ln_vocab;
+        a.ln.word = g->ln_word; a.ln.pos = g->ln_pos; a.ln.g = g->ln_g; a.ln.b = g->ln_b; a.ln.eps = g->ln_eps; a.ln.xf = g->ln_xf;
+    } else if (!g->X || g->ldx < g->K || (g->ldx & 7) || ((uintptr_t)g->X & 15)) {
+        return GITCAP_ERR_ARG;
+    }
+    return dbg_rc(launch_skinny(a, epi, (hipStream_t)stream));
+}
+
+int gitcap_dbg_skinny_splitk(const void* X, int ldx, const void* W, const void* Wpk, const float* wscale, int M, int N, int K, int ksplit,
+                             float* slabs, int ldo, void* stream) {
+    if (!X || !W || !slabs || M <= 0 || N <= 0 || K <= 0 || ksplit < 0 || ldx < K || (ldx & 7) || ldo < N || (ldo & 3) ||
+        ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || ((uintptr_t)Wpk & 15) || ((uintptr_t)slabs & 15))
+        return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.Wpk = Wpk; a.wscale = wscale; a.M = M; a.N = N; a.K = K;
+    a.out = slabs; a.ldo = ldo; a.T = M; a.row_stride = M; a.ksplit = ksplit;
+    return dbg_rc(launch_skinny_splitk(a, (hipStream_t)stream));
+}
+
+int gitcap_dbg_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid, const float* gamma, const float* beta,
+                         float eps, int M, int D, float* xf, void* xb, void* stream) {
+    if (!slabs || !bias || !resid || !gamma || !beta || !xf || !xb || M <= 0 || D <= 0 || (D & 3) || nslab <= 0) return GITCAP_ERR_ARG;
+    if (((uintptr_t)slabs & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)resid & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15) ||
+        ((uintptr_t)xf & 15) || ((uintptr_t)xb & 7))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ln_reduce(slabs, nslab, bias, resid, gamma, beta, eps, M, D, xf, (bf16_t*)xb, (hipStream_t)stream));
+}
+
+int gitcap_dbg_ffn_txt(const void* X, int ldx, const void* W1pk, const void* W2pk, const float* w1scale, const float* w2scale,
+                       const float* b1, int M, int D, int F, float* slabs, void* stream) {
+    if (!X || !W1pk || !W2pk || !b1 || !slabs || M <= 0 || !ffn_txt_ok(D, F) || (w1scale != nullptr) != (w2scale != nullptr) || ldx < D ||
+        (ldx & 7) || ((uintptr_t)X & 15) || ((uintptr_t)W1pk & 15) || ((uintptr_t)W2pk & 15) || ((uintptr_t)slabs & 15))
+        return GITCAP_ERR_ARG;
+    FfnTxtArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W1pk = W1pk; a.W2pk = W2pk; a.w1scale = w1scale; a.w2scale = w2scale; a.b1 = b1;
+    a.M = M; a.D = D; a.F = F; a.slabs = slabs;
+    return dbg_rc(launch_ffn_txt(a, (hipStream_t)stream));
+}
+
+int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) {
+    if (!g || !g->kv_img || !g->kv_txt || !g->aow || !g->aob || !g->g1 || !g->b1 || !g->xin || !g->part || !g->cnt || !g->xs || !g->xsb)
+        return GITCAP_ERR_ARG;
+    if (g->rows <= 0 || g->beams <= 0 || g->T <= 0 || g->t0 < 0 || g->t0 + g->T > g->Tmax || g->S_img < 0 || !txt_block_ok(g->D) ||
+        g->H * 64 != g->D || (g->v8_img != nullptr) != (g->vs_img != nullptr) ||
+        (g->v8_img && g->v8_pitch < (int64_t)((g->rows - 1) / g->beams + 1) * g->S_img))
+        return GITCAP_ERR_ARG;
+    // the widest access txt_block_kernel makes on each buffer: 16-byte rows of q / k / v and of the output dense (8 bytes of e4m3 codes),
+    // 8 bytes of V codes; everything else -- scales, bias, gamma / beta, residual, part, tickets, xs -- one float or word at a time, xsb
+    // one bf16 at a time
+    if (((uintptr_t)g->kv_img & 15) || ((uintptr_t)g->kv_txt & 15) || ((uintptr_t)g->aow & 15) || ((uintptr_t)g->aowpk & 15) ||
+        ((uintptr_t)g->v8_img & 7) || ((uintptr_t)g->vs_img & 3) || ((uintptr_t)g->aoscale & 3) || ((uintptr_t)g->aob & 3) ||
+        ((uintptr_t)g->g1 & 3) || ((uintptr_t)g->b1 & 3) || ((uintptr_t)g->xin & 3) || ((uintptr_t)g->part & 3) || ((uintptr_t)g->cnt & 3) ||
+        ((uintptr_t)g->xs & 3) || ((uintptr_t)g->xsb & 1))
+        return GITCAP_ERR_ARG;
+    TxtBlockArgs a{};
+    a.kv_img = (const bf16_t*)g->kv_img; a.kv_txt = (const bf16_t*)g->kv_txt;
+    a.rows = g->rows; a.beams = g->beams; a.t0 = g->t0; a.T = g->T; a.Tmax = g->Tmax; a.S_img = g->S_img; a.H = g->H; a.D = g->D;
+    a.aow = g->aow; a.aowpk = g->aoscale ? nullptr : g->aowpk; a.aoscale = g->aoscale; a.aob = g->aob; a.g1 = g->g1; a.b1 = g->b1;
+    a.xin = g->xin; a.eps = g->eps; a.part = g->part; a.cnt = g->cnt; a.xs = g->xs; a.xsb = (bf16_t*)g->xsb;
+    a.v8_img = (const unsigned char*)g->v8_img; a.vs_img = g->vs_img; a.v8_pitch = g->v8_pitch; a.nt_kv = g->nt_kv ? 1 : 0;
+    return dbg_rc(launch_txt_block(a, (hipStream_t)stream));
+}
+
 // Threads a host-side copy may use: the affinity mask capped by the cgroup CPU quota (a 1-GPU box gives the job a share of the
 // host: a pool as wide as the machine only time-slices against itself), at most 8 (a copy is memory bound long before that).
 static int host_copy_threads() {

@@ -915,8 +915,9 @@ hipError_t launch_im2col(const float* frames, bf16_t* patches, int nf, int img, 
 // ---- V of the image prefix as OCP e4m3 codes + one power-of-two scale per (token, head) (opt-in kv_cache = v_e4m3) -------
 // kv: [rows][3D] bf16 (q | k | v of one decoder layer's image rows) -> v8 [H][pitch][64] codes, vs [H][pitch] scales, HEAD-MAJOR: the
 // V stream of one (row, head) unit of txt_block is one contiguous run of 64-byte records (two keys per cache line).  Eight lanes per
-// (row, head): 8 values each; scale = the smallest 2^e with amax <= 448 * 2^e (exact: amax / 2^(E-8) lies in [256, 512), compared
-// with 448 after an exact scaling), codes round to nearest even; code * scale is a bf16 value.
+// (row, head): 8 values each; scale = the smallest 2^e, e >= -126, with amax <= 448 * 2^e (exact: for amax >= 2^-118,
+// amax / 2^(E-8) lies in [256, 512) and is compared with 448 after an exact scaling; a smaller amax keeps the floor 2^-126 and small
+// codes; an all-zero group has scale 1), codes round to nearest even; code * scale is a bf16 value.
 namespace {
 __global__ __launch_bounds__(256) void kv_quant_v_kernel(const bf16_t* __restrict__ kv, unsigned char* __restrict__ v8, float* __restrict__ vs,
                                                          int64_t groups, int D, int H, int64_t pitch) {
@@ -936,8 +937,10 @@ __global__ __launch_bounds__(256) void kv_quant_v_kernel(const bf16_t* __restric
     amax = fmaxf(amax, __shfl_xor(amax, 4));
     float scale = 1.0f;
     if (amax > 0.f) {
-        const int E = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127;          // floor(log2 amax) (bf16 values: never denormal in fp32)
-        scale = __uint_as_float((unsigned)(E - 8 + 127) << 23);                    // amax / scale in [256, 512)
+        const int E = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127;          // floor(log2 amax); -127 for a denormal amax
+        // amax / scale in [256, 512); never below 2^-126: for amax < 2^-118 the exponent field E - 8 + 127 would be <= 0, i.e. a
+        // scale of 0, -inf or worse (and 0 * inf = NaN in txt_block) -- such a group keeps the smallest normal scale, its codes are small
+        scale = __uint_as_float((unsigned)((E - 8 < -126 ? -126 : E - 8) + 127) << 23);
         if (amax > 448.0f * scale) scale *= 2.0f;
     }
     const float inv = 1.0f / scale;                                                // a power of two: exact

@@ -25,6 +25,25 @@ class CDbgBeamBuffers(ctypes.Structure):
                 ("hyp_score", c_void_p), ("src_rows", c_void_p), ("done", c_void_p), ("hyp_len", c_void_p)]
 
 
+class CDbgSkinnyArgs(ctypes.Structure):
+    """struct gitcap_dbg_skinny_args (include/gitcap.h)."""
+    _fields_ = [("X", c_void_p), ("ldx", c_int32), ("W", c_void_p), ("Wpk", c_void_p), ("wscale", c_void_p), ("bias", c_void_p),
+                ("M", c_int32), ("N", c_int32), ("K", c_int32), ("out", c_void_p), ("ldo", c_int32), ("T", c_int32),
+                ("row_stride", c_int32), ("row_off", c_int32), ("ln_kind", c_int32), ("ln_slabs", c_void_p), ("ln_nslab", c_int32),
+                ("ln_bias", c_void_p), ("ln_resid", c_void_p), ("ln_ids", c_void_p), ("ln_ld_ids", c_int32), ("ln_T", c_int32),
+                ("ln_t0", c_int32), ("ln_vocab", c_int32), ("ln_word", c_void_p), ("ln_pos", c_void_p), ("ln_g", c_void_p),
+                ("ln_b", c_void_p), ("ln_eps", c_float), ("ln_xf", c_void_p)]
+
+
+class CDbgTxtBlockArgs(ctypes.Structure):
+    """struct gitcap_dbg_txt_block_args (include/gitcap.h)."""
+    _fields_ = [("kv_img", c_void_p), ("kv_txt", c_void_p), ("rows", c_int32), ("beams", c_int32), ("t0", c_int32), ("T", c_int32),
+                ("Tmax", c_int32), ("S_img", c_int32), ("H", c_int32), ("D", c_int32), ("aow", c_void_p), ("aowpk", c_void_p),
+                ("aoscale", c_void_p), ("aob", c_void_p), ("g1", c_void_p), ("b1", c_void_p), ("xin", c_void_p), ("eps", c_float),
+                ("part", c_void_p), ("cnt", c_void_p), ("xs", c_void_p), ("xsb", c_void_p), ("v8_img", c_void_p), ("vs_img", c_void_p),
+                ("v8_pitch", c_int64), ("nt_kv", c_int32)]
+
+
 # every symbol include/gitcap.h declares (tests/test_cabi.py checks the list against the header)
 SYMBOLS = {
     "gitcap_abi_version": (c_int, []),
@@ -97,6 +116,17 @@ SYMBOLS = {
     "gitcap_dbg_beam_step": (c_int, [POINTER(CDbgBeamBuffers), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),
     "gitcap_dbg_beam_finish": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # text-row kernel hooks (tests/test_text_rows_gpu.py)
+    "gitcap_dbg_pack_frags": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_kv_quant_v": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "gitcap_dbg_skinny": (c_int, [POINTER(CDbgSkinnyArgs), c_int, c_void_p]),
+    "gitcap_dbg_skinny_splitk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                         c_void_p]),
+    "gitcap_dbg_ln_reduce": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p]),
+    "gitcap_dbg_ffn_txt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                   c_void_p]),
+    "gitcap_dbg_txt_block": (c_int, [POINTER(CDbgTxtBlockArgs), c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     # student decoder (gitcap/student.py)

@@ -79,6 +79,14 @@ def test_ctypes_structs_mirror_the_header_field_order():
     assert [f for f, _ in CGitCapConfig._fields_] == _struct_fields("gitcap_config")
 
 
+def test_debug_hook_structs_mirror_the_header_field_order():
+    """The text-row hooks' argument structs (pointer fields: the names behind the stars)."""
+    txt = open(os.path.join(ROOT, "include", "gitcap.h")).read()
+    for name, cls in (("gitcap_dbg_skinny_args", _lib.CDbgSkinnyArgs), ("gitcap_dbg_txt_block_args", _lib.CDbgTxtBlockArgs)):
+        body = re.search(r"struct\s+%s\s*\{(.*?)\}\s*\w*\s*;" % name, txt, flags=re.S).group(1)
+        assert re.findall(r"(\w+)\s*(?=[,;])", body) == [f for f, _ in cls._fields_], name
+
+
 def test_student_abi_rejects_bad_configs_and_has_no_cpu_path():
     from gitcap.student_config import CStudentConfig, StudentConfig, student_tiny
     lib = _lib.load()
