@@ -197,8 +197,14 @@ class GitcapExchangeTimeout(GitcapError):
 ERR_EXCHANGE = -5
 
 
-def check(lib, handle, rc: int, what: str) -> None:
+def check(lib, handle, rc: int, what: str, last_error: str = "gitcap_last_error") -> None:
+    """The one place a status becomes an exception; `last_error`: the ``*_last_error`` symbol of the handle's family."""
     if rc != 0:
-        msg = lib.gitcap_last_error(handle)
+        msg = getattr(lib, last_error)(handle)
         cls = GitcapExchangeTimeout if rc == ERR_EXCHANGE else GitcapError
         raise cls(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
+
+
+def ptr(t) -> c_void_p:
+    """The address of tensor `t`'s data as the C ABI takes it; None -> NULL."""
+    return c_void_p(None if t is None else t.data_ptr())

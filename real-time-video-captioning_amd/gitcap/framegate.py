@@ -45,10 +45,10 @@ def frame_change(frames: torch.Tensor, ref: torch.Tensor, channel: int = 2, outp
     shapes = {"ssd": ((B,), torch.int64), "hist_frame": ((B, 256), torch.int32), "hist_ref": ((B, 256), torch.int32),
               "mse": ((B,), torch.float64), "chisq": ((B,), torch.float64)}
     out = {o: torch.empty(shapes[o][0], dtype=shapes[o][1], device=dev) for o in OUTPUTS if o in outputs}
-    ptr = [ctypes.c_void_p(out[o].data_ptr() if o in out else None) for o in OUTPUTS]
+    ptr = [_lib.ptr(out.get(o)) for o in OUTPUTS]
     with torch.cuda.device(dev):
-        rc = lib.gitcap_frame_change(ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(ref.data_ptr()), B, H, W, int(channel),
-                                     *ptr, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = lib.gitcap_frame_change(_lib.ptr(frames), _lib.ptr(ref), B, H, W, int(channel), *ptr,
+                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise _lib.GitcapError(f"gitcap_frame_change failed (status {rc}): {B} frames {H}x{W}, channel {channel}")
     return out

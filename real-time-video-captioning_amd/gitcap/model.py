@@ -24,15 +24,14 @@ from typing import Dict, Mapping, Optional
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib
 from .config import CGitCapConfig, GitCapConfig, git_base
-from .framegate import FrameGate, gated_frames
+from .framegate import FrameGate
 from . import weights as W
+from ._handle import _NativeModule
+from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
 from .window import WindowSchedule
-
-STOP_NEVER, STOP_ALL_SEP = 0, 1
 
 
 class _Submission:
@@ -100,7 +99,7 @@ class _StagingRing:
         """src (CPU tensor, any memory) -> dst (a view of the pinned buffer, same shape)."""
         if src.dtype == dst.dtype and src.is_contiguous():
             nbytes = src.numel() * src.element_size()
-            rc = self.lib.gitcap_host_copy(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), nbytes)
+            rc = self.lib.gitcap_host_copy(_lib.ptr(dst), _lib.ptr(src), nbytes)
             if rc != 0:
                 raise _lib.GitcapError(f"gitcap_host_copy failed (status {rc})")
         else:
@@ -249,7 +248,7 @@ class InferFuture(_Future):
         return self._done
 
 
-class CaptionStream:
+class CaptionStream(_WindowStream):
     """Live captioning over a sliding window of frames (GitCaptioner.caption_stream; include/gitcap.h: gitcap_window_*).  Every
     frame is encoded once, when it is pushed; a caption of the last `window` frames re-runs only the decoder's image prefix and the
     token loop.  Captions are bitwise those of greedy_decode (or of infer's device search) on the window's frames.  With a ``gate``
@@ -257,33 +256,17 @@ class CaptionStream:
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
                  gate=None, logprobs=False):
-        self._m = model
-        self._gate = gate
-        self._want_lp = logprobs
-        self.last_logprobs = None        # logprobs=True: fp32 [B, steps] of the caption the last push returned (on the CPU when the frames were)
-        self._sched = WindowSchedule(batch, window, hop)
-        self._max_len, self._mode = max_len, mode
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
-        self._kept = []                  # the last `window` frames per push order, [B, ...] each: what a recovery pushes again
-        self._kind = None                # (raw, device) of the frames since the reset
-        self._token = object()
-        model._window_owner = self._token
-        with torch.cuda.device(model._dev):
-            model._call("gitcap_window_reset", batch, window)
+        self._clear()
+        super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
 
-    def _check_live(self):
-        if self._m._window_owner is not self._token:
-            raise _lib.GitcapError("this CaptionStream was invalidated (another caption_stream() was opened, or the model was moved)")
-
-    def reset(self):
-        """Empty the window: the next caption needs `window` new frames."""
-        self._check_live()
+    def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
             self._m._call("gitcap_window_reset", self._sched.batch, self._sched.window)
-        self._sched.reset()
-        self._kept, self._kind = [], None
-        if self._gate is not None:
-            self._gate.reset()
+
+    def _clear(self):
+        self._kept = []                  # the last `window` frames per push order, [B, ...] each: what a recovery pushes again
+        self._kind = None                # (raw, device) of the frames since the reset
 
     def _shape(self, frames):
         """[B,H,W,3] uint8 / [B,3,S,S] fp32 (one frame per clip) or [B,n,...] -> (5-D view, raw)."""
@@ -297,27 +280,18 @@ class CaptionStream:
         B, n = fr.shape[:2]
         with torch.cuda.device(m._dev):
             if raw:
-                m._call("gitcap_window_push_raw", ctypes.c_void_p(fr.data_ptr()), B, n, fr.shape[2], fr.shape[3], m._stream())
+                m._call("gitcap_window_push_raw", _lib.ptr(fr), B, n, fr.shape[2], fr.shape[3], m._stream())
             else:
-                m._call("gitcap_window_push", ctypes.c_void_p(fr.data_ptr()), B, n, m._stream())
+                m._call("gitcap_window_push", _lib.ptr(fr), B, n, m._stream())
 
     def _repush(self):
         """After a failed statistics exchange the library emptied the ring: push the frames it held again (one push)."""
         self._push_lib(torch.stack(self._kept, 1), self._kind[0])
 
-    def push(self, frames: torch.Tensor):
-        """Append one frame per clip ([B,H,W,3] uint8 camera frames or [B,3,S,S] transformed frames) or n of them ([B,n,...]), on
-        the CPU or the device.  -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in
-        greedy_decode), or with beam_size the dict infer returns.  CPU frames in: the result is on the CPU and vouched for.  A
-        gated stream takes uint8 camera frames only; the window and `hop` count the frames the gate admits, and a push with none
-        admitted returns None."""
-        self._check_live()
-        if self._gate is None:
-            return self._push(frames, frames.device.type == "cpu")
-        admitted = gated_frames(self._gate, frames, self._sched, self._m._dev)
-        return None if admitted is None else self._push(admitted, frames.device.type == "cpu")
-
     def _push(self, frames: torch.Tensor, on_cpu: bool):
+        """frames: [B,H,W,3] uint8 camera frames or [B,3,S,S] transformed frames, or n of them ([B,n,...]).  -> None, or the caption
+        of the window when one is due: greedy ids [B, 1+steps] (truncated as in greedy_decode), or with beam_size the dict infer
+        returns.  CPU frames in: the result is on the CPU and vouched for."""
         m = self._m
         x, raw = self._shape(frames)
         B, n = x.shape[:2]
@@ -356,38 +330,31 @@ class CaptionStream:
         vis = None
         if self._vis:
             vis = torch.empty((B, self._sched.window * m.cfg.tokens_per_frame, m.cfg.enc_width), dtype=torch.float32, device=m._dev)
-        vp = ctypes.c_void_p(vis.data_ptr() if vis is not None else None)
         with torch.cuda.device(m._dev):
             if self._beam is None:
-                ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
-                steps = torch.zeros((1,), dtype=torch.int32, device=m._dev)
-                lp = None
-                if self._want_lp:
-                    lp = torch.empty((B, self._max_len), dtype=torch.float32, device=m._dev)
-                    m._call("gitcap_attach_token_logprobs", ctypes.c_void_p(lp.data_ptr()), self._max_len)
-                m._call("gitcap_window_greedy", self._max_len, self._mode, vp, ctypes.c_void_p(ids.data_ptr()),
-                        ctypes.c_void_p(steps.data_ptr()), m._stream())
+                ids, steps, lp = self._greedy_buffers(B)
+                if lp is not None:
+                    m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), self._max_len)
+                m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
                 decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 logprobs = torch.empty((B,), dtype=torch.float32, device=m._dev)
-                m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, vp,
-                        ctypes.c_void_p(decoded.data_ptr()), ctypes.c_void_p(logprobs.data_ptr()), m._stream())
+                m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
+                        _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
         m._last_memory = None
+        if self._beam is None:
+            return self._finish_greedy(ids, steps, lp, on_cpu)
         mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
-        if self._beam is not None:
-            return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]), "logits_dict": [], "visual_features": mv(vis)}
-        if self._mode == STOP_ALL_SEP:
-            ids = ids[:, :1 + int(steps.item())]
-        if lp is not None:
-            self.last_logprobs = mv(lp[:, :ids.shape[1] - 1])
-        return mv(ids)
+        return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]), "logits_dict": [], "visual_features": mv(vis)}
 
 
 def _rebuild(cfg_dict, weights, kwargs):
     return GitCaptioner(GitCapConfig(**cfg_dict), weights, **kwargs)
 
 
-class GitCaptioner(nn.Module):
+class GitCaptioner(_NativeModule):
+    _PREFIX, _FINALIZE = "gitcap", "gitcap_finalize_weights"
+
     def __init__(self, cfg: Optional[GitCapConfig] = None, weights: Optional[Mapping[str, np.ndarray]] = None, *,
                  device: str | torch.device = "cuda:0", max_batch: int = 16, max_frames: Optional[int] = None,
                  max_text_len: int = 32, max_beams: int = 1, tokenizer=None, stop: str = "all_sep",
@@ -438,28 +405,20 @@ class GitCaptioner(nn.Module):
         self._window_owner = None                       # token of the one live CaptionStream (the handle has one frame window)
         self._copy_stream = os.environ.get("GITCAP_COPY_STREAM", "caller")  # "caller" | "own" (A/B switch; see _StagingRing)
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
-        self._create()
+        self._open()
         if weights is not None:
             self.load_state_dict(weights)
 
     # ------------------------------------------------------------------ handle management
-    def _create(self):
-        if self._dev.type != "cuda":
-            raise _lib.GitcapError("gitcap runs on an AMD GPU only (no CPU path); got device %s" % self._dev)
-        if not torch.cuda.is_available():
-            raise _lib.GitcapError("no HIP device visible: gitcap has no CPU fallback")
+    def _cconfig(self):
         kw = self._kw
         self.max_batch = int(kw["max_batch"])
         self.max_frames = int(kw["max_frames"] or max(1, self.cfg.num_frames))
         self.max_text_len = int(kw["max_text_len"])
         self.max_beams = int(kw["max_beams"])
-        cc = CGitCapConfig.from_config(self.cfg, self.max_batch, self.max_frames, self.max_text_len, self.max_beams)
-        h = ctypes.c_void_p()
-        idx = self._dev.index if self._dev.index is not None else torch.cuda.current_device()
-        self._dev = torch.device("cuda", idx)
-        rc = self._lib.gitcap_create(ctypes.byref(cc), idx, ctypes.byref(h))
-        _lib.check(self._lib, None, rc, "gitcap_create")
-        self._handle = h
+        return CGitCapConfig.from_config(self.cfg, self.max_batch, self.max_frames, self.max_text_len, self.max_beams)
+
+    def _configure(self):
         if self.weight_dtype == "fp8_e4m3":     # GEMM weights live in HBM as e4m3 + per-row 2^k scale (half the bytes)
             self._call("gitcap_set_weight_storage", 1)
         if self.compute == "fp8_ffn":           # FC1 / FC2 of the image rows on fp8 MFMA (include/gitcap.h: gitcap_set_compute)
@@ -469,24 +428,13 @@ class GitCaptioner(nn.Module):
         if self.kv_cache == "v_e4m3":           # image-prefix V as e4m3 codes for the token loop (include/gitcap.h: gitcap_set_kv_cache)
             self._call("gitcap_set_kv_cache", 1)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.gitcap_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-
     def _call(self, name, *args):
         rc = getattr(self._lib, name)(self._handle, *args)
         if rc == _lib.ERR_EXCHANGE:
             # whichever call learns of a failed statistics exchange: every submission whose rows have not been handed out yet
             # (in flight, or already stream-waited by a synchronous call but not delivered) holds undefined ids
             self._poison_inflight()
-        _lib.check(self._lib, self._handle, rc, name)
+        self._check(self._handle, rc, name)
 
     def _staging(self):
         if self._ring is None:
@@ -560,33 +508,17 @@ class GitCaptioner(nn.Module):
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, *args, **kwargs):
         self._window_owner = None                       # a CaptionStream does not follow the model
-        dev = kwargs.get("device", args[0] if args else None)
-        if isinstance(dev, (str, torch.device)):
-            dev = torch.device(dev)
-            if dev.type != "cuda":
-                raise _lib.GitcapError("gitcap has no CPU path; .to(%s) refused" % dev)
-            idx = dev.index if dev.index is not None else torch.cuda.current_device()
-            if idx != self._dev.index:
-                self._lib.gitcap_destroy(self._handle)
-                self._dev = torch.device("cuda", idx)
-                self._create()
-                if self._weights is not None:
-                    self._upload(self._weights)
-        return self
+        return super().to(*args, **kwargs)
 
     def cuda(self, device=None):
         return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
-
-    def state_dict(self, *a, **k):
-        return {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts canonical names (gitcap/weights.py), a transformers GitForCausalLM state dict or the
         MS GenerativeImage2Text checkpoint layout the reference loads (model.py:736-738)."""
         keys = state_dict.keys()
         if "enc.patch_w" in keys:
-            w = {k: np.ascontiguousarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else v,
-                                         dtype=np.float32) for k, v in state_dict.items()}
+            w = {k: self._as_f32(v) for k, v in state_dict.items()}
             W.check_shapes(self.cfg, w)
         elif any(k.startswith("git.") for k in keys):
             w = W.from_hf_state_dict(self.cfg, state_dict)
@@ -601,12 +533,7 @@ class GitCaptioner(nn.Module):
         return self
 
     def _upload(self, w: Mapping[str, np.ndarray]):
-        with torch.cuda.device(self._dev):
-            for name in W.canonical_shapes(self.cfg):
-                arr = np.ascontiguousarray(w[name], dtype=np.float32)
-                shape = (ctypes.c_int64 * arr.ndim)(*arr.shape)
-                self._call("gitcap_load_tensor", name.encode(), arr.ctypes.data_as(ctypes.c_void_p), shape, arr.ndim)
-            self._call("gitcap_finalize_weights")
+        self._load_tensors((name, w[name]) for name in W.canonical_shapes(self.cfg))
 
     def __reduce__(self):
         kw = dict(self._kw)
@@ -681,10 +608,9 @@ class GitCaptioner(nn.Module):
         vis = torch.empty((B, F * self.cfg.tokens_per_frame, self.cfg.enc_width), dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
             if raw:
-                self._call("gitcap_encode_raw", ctypes.c_void_p(fr.data_ptr()), B, F, fr.shape[2], fr.shape[3],
-                           ctypes.c_void_p(vis.data_ptr()), self._stream())
+                self._call("gitcap_encode_raw", _lib.ptr(fr), B, F, fr.shape[2], fr.shape[3], _lib.ptr(vis), self._stream())
             else:
-                self._call("gitcap_encode", ctypes.c_void_p(fr.data_ptr()), B, F, ctypes.c_void_p(vis.data_ptr()), self._stream())
+                self._call("gitcap_encode", _lib.ptr(fr), B, F, _lib.ptr(vis), self._stream())
         self._remember_memory(vis)
         return [], vis
 
@@ -706,11 +632,10 @@ class GitCaptioner(nn.Module):
         with torch.cuda.device(self._dev):
             if not self._is_last_memory(memory):
                 mem = memory.to(device=self._dev, dtype=torch.float32).contiguous()
-                self._call("gitcap_set_visual", ctypes.c_void_p(mem.data_ptr()), mem.shape[0], mem.shape[1], self._stream())
+                self._call("gitcap_set_visual", _lib.ptr(mem), mem.shape[0], mem.shape[1], self._stream())
                 self._remember_memory(memory)
             logits = torch.empty((B, T, self.cfg.vocab_size), dtype=torch.float32, device=self._dev)
-            self._call("gitcap_text_forward", ctypes.c_void_p(ids.data_ptr()), T, B, 1, 0, T,
-                       ctypes.c_void_p(logits.data_ptr()), 1, None, 0, self._stream())
+            self._call("gitcap_text_forward", _lib.ptr(ids), T, B, 1, 0, T, _lib.ptr(logits), 1, None, 0, self._stream())
         return logits
 
     def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):
@@ -807,7 +732,7 @@ class GitCaptioner(nn.Module):
             B, S_img, T = vis.shape[0], vis.shape[1], logits.shape[1]
             hid = torch.empty((B, self.cfg.dec_layers + 1, S_img + T, self.cfg.dec_width), dtype=torch.float32, device=self._dev)
             with torch.cuda.device(self._dev):
-                self._call("gitcap_hidden_states_read", B, S_img, T, ctypes.c_void_p(hid.data_ptr()), self._stream())
+                self._call("gitcap_hidden_states_read", B, S_img, T, _lib.ptr(hid), self._stream())
         finally:
             self._call("gitcap_hidden_states_enable", 0)
             self._last_memory = None
@@ -841,14 +766,13 @@ class GitCaptioner(nn.Module):
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
                 if want_lp:                      # one-shot: consumed by the greedy call below
                     lps.append(torch.empty((chunk.shape[0], max_len), dtype=torch.float32, device=self._dev))
-                    self._call("gitcap_attach_token_logprobs", ctypes.c_void_p(lps[-1].data_ptr()), max_len)
+                    self._call("gitcap_attach_token_logprobs", _lib.ptr(lps[-1]), max_len)
                 if raw:
-                    self._call("gitcap_greedy_raw", ctypes.c_void_p(chunk.data_ptr()), chunk.shape[0], F, chunk.shape[2],
-                               chunk.shape[3], max_len, mode, ctypes.c_void_p(ids.data_ptr()),
-                               ctypes.c_void_p(steps.data_ptr()), self._stream())
+                    self._call("gitcap_greedy_raw", _lib.ptr(chunk), chunk.shape[0], F, chunk.shape[2], chunk.shape[3], max_len, mode,
+                               _lib.ptr(ids), _lib.ptr(steps), self._stream())
                 else:
-                    self._call("gitcap_greedy", ctypes.c_void_p(chunk.data_ptr()), chunk.shape[0], F, max_len, mode,
-                               ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), self._stream())
+                    self._call("gitcap_greedy", _lib.ptr(chunk), chunk.shape[0], F, max_len, mode, _lib.ptr(ids), _lib.ptr(steps),
+                               self._stream())
                 outs.append(ids)
                 steps_all.append(steps)
         self._last_memory = None
@@ -937,12 +861,11 @@ class GitCaptioner(nn.Module):
             ticket = ctypes.c_int(-1)
             stop = STOP_NEVER if len(group) > 1 else mode       # the stop rule is per caller batch: applied in result()
             if raw:
-                self._submit("gitcap_greedy_raw_submit", ctypes.c_void_p(frames.data_ptr()), B, F, frames.shape[2], frames.shape[3],
-                             max_len, stop, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), stream,
-                             ctypes.byref(ticket))
+                self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, F, frames.shape[2], frames.shape[3], max_len, stop,
+                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket))
             else:
-                self._submit("gitcap_greedy_submit", ctypes.c_void_p(frames.data_ptr()), B, F, max_len, stop,
-                             ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), stream, ctypes.byref(ticket))
+                self._submit("gitcap_greedy_submit", _lib.ptr(frames), B, F, max_len, stop, _lib.ptr(ids), _lib.ptr(steps), stream,
+                             ctypes.byref(ticket))
         self._last_memory = None
         shared = _Submission(ticket.value, frames, (ids, steps), len(group) > 1, users=len(group), parts=parts)
         if entry is not None:
@@ -963,8 +886,7 @@ class GitCaptioner(nn.Module):
         rows = ids.shape[0]
         logits = torch.empty((rows, self.cfg.vocab_size), dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
-            self._call("gitcap_text_forward", ctypes.c_void_p(ids.data_ptr()), 1, rows, beams, t, 1,
-                       ctypes.c_void_p(logits.data_ptr()), 0, None, 0, self._stream())
+            self._call("gitcap_text_forward", _lib.ptr(ids), 1, rows, beams, t, 1, _lib.ptr(logits), 0, None, 0, self._stream())
         return logits
 
     @torch.no_grad()
@@ -1035,13 +957,11 @@ class GitCaptioner(nn.Module):
         B, F = fr.shape[:2]
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
-        null = ctypes.c_void_p(None)
         with torch.cuda.device(self._dev):
             if sync and not save_logits and not want_visual and not raw:
                 self._drain()
-                self._call("gitcap_beam_search", ctypes.c_void_p(fr.data_ptr()), B, F, beam_size, max_steps,
-                           ctypes.c_float(length_penalty), per_node_beam_size, ctypes.c_void_p(decoded.data_ptr()),
-                           ctypes.c_void_p(logprobs.data_ptr()), self._stream())
+                self._call("gitcap_beam_search", _lib.ptr(fr), B, F, beam_size, max_steps, ctypes.c_float(length_penalty),
+                           per_node_beam_size, _lib.ptr(decoded), _lib.ptr(logprobs), self._stream())
                 self._last_memory = None
                 return decoded, logprobs, None, None
             steps = torch.empty((max_steps - 1, B * beam_size, self.cfg.vocab_size), dtype=torch.float32, device=self._dev) if save_logits else None
@@ -1049,14 +969,12 @@ class GitCaptioner(nn.Module):
             while len(self._inflight) >= 4:
                 self._wait_submission(self._inflight[0])
             ticket = ctypes.c_int(-1)
-            tail = (ctypes.c_void_p(vis.data_ptr()) if want_visual else null, beam_size, max_steps, ctypes.c_float(length_penalty),
-                    per_node_beam_size, ctypes.c_void_p(decoded.data_ptr()), ctypes.c_void_p(logprobs.data_ptr()),
-                    ctypes.c_void_p(steps.data_ptr()) if save_logits else null, stream if stream is not None else self._stream(),
-                    ctypes.byref(ticket))
+            tail = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(decoded),
+                    _lib.ptr(logprobs), _lib.ptr(steps), stream if stream is not None else self._stream(), ctypes.byref(ticket))
             if raw:
-                self._submit("gitcap_beam_search_raw_submit", ctypes.c_void_p(fr.data_ptr()), B, F, fr.shape[2], fr.shape[3], *tail)
+                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fr.shape[2], fr.shape[3], *tail)
             else:
-                self._submit("gitcap_beam_search_submit", ctypes.c_void_p(fr.data_ptr()), B, F, *tail)
+                self._submit("gitcap_beam_search_submit", _lib.ptr(fr), B, F, *tail)
             self._last_memory = None
             if sync:                           # (a re-run, or a synchronous call that wants logits / visual features / takes raw frames)
                 self._call("gitcap_beam_search_wait", ticket.value, self._stream())
@@ -1146,7 +1064,7 @@ class GitCaptioner(nn.Module):
         """Beam reorder of the text K/V cache (what model.py:623-634 sketches in comments)."""
         idx = src_rows.to(device=self._dev, dtype=torch.int32).contiguous()
         with torch.cuda.device(self._dev):
-            self._call("gitcap_reorder_rows", ctypes.c_void_p(idx.data_ptr()), idx.numel(), t_len, self._stream())
+            self._call("gitcap_reorder_rows", _lib.ptr(idx), idx.numel(), t_len, self._stream())
 
     PROF_CLASSES = ("gemm", "attn_full", "skinny", "attn_text", "rowops", "gemm_ln")
 

@@ -71,9 +71,8 @@ class GeneratorWithBeamSearch:
         out_s = torch.empty((B, K), dtype=torch.float32, device=logits.device)
         out_i = torch.empty((B, K), dtype=torch.int32, device=logits.device)
         with torch.cuda.device(logits.device):
-            rc = self._lib.gitcap_beam_topk(ctypes.c_void_p(logits.data_ptr()), logits.stride(0),
-                                            ctypes.c_void_p(beam_scores.data_ptr()), B, beams, V, K,
-                                            ctypes.c_void_p(out_s.data_ptr()), ctypes.c_void_p(out_i.data_ptr()),
+            rc = self._lib.gitcap_beam_topk(_lib.ptr(logits), logits.stride(0), _lib.ptr(beam_scores), B, beams, V, K,
+                                            _lib.ptr(out_s), _lib.ptr(out_i),
                                             ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
         if rc != 0:
             raise _lib.GitcapError(f"gitcap_beam_topk failed (status {rc})")

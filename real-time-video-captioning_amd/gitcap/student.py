@@ -22,20 +22,19 @@ from typing import Dict, Mapping, Optional
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib
-from .framegate import FrameGate, gated_frames
+from ._handle import _NativeModule
+from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
+from .framegate import FrameGate
 from .student_config import (CStudentConfig, StudentConfig, check_student_shapes, positional_table, student_shapes)
 from .tinyvit import TinyViTEncoder, tinyvit_config
 from .window import WindowSchedule
 
 ENC_PREFIX = "image_encoder.model."
 
-STOP_NEVER, STOP_ALL_SEP = 0, 1
 
-
-class StudentCaptionStream:
+class StudentCaptionStream(_WindowStream):
     """Live captioning on the student over a sliding window of ``mem_tokens`` frames (StudentCaptioner.caption_stream;
     include/gitcap.h: gitcap_student_window_*).  A frame is encoded once, when it is pushed, and its cross-attention K|V rows
     are computed then; a caption of the window only orders those rows and runs the token loop.  Captions are bitwise those of
@@ -45,32 +44,16 @@ class StudentCaptionStream:
     (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
 
     def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False):
-        self._m = model
-        self._gate = gate
-        self._want_lp = logprobs
-        self.last_logprobs = None        # logprobs=True: fp32 [B, steps] of the caption the last push returned (on the CPU when the frames were)
-        self._carry, self._prev = bool(carry), None
+        self._carry, self._prev, self._beams = bool(carry), None, beams
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
-        self._sched = WindowSchedule(batch, model.cfg.mem_tokens, hop)
-        self._max_len, self._mode, self._beams = max_len, mode, beams
-        self._token = object()
-        model._window_owner = self._token
-        with torch.cuda.device(model._dev):
-            model._call("gitcap_student_window_reset", batch)
+        super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop), max_len, mode, gate, logprobs)
 
-    def _check_live(self):
-        if self._m._window_owner is not self._token:
-            raise _lib.GitcapError("this StudentCaptionStream was invalidated (another caption_stream() was opened, or the model was moved)")
-
-    def reset(self):
-        """Empty the window: the next caption needs ``mem_tokens`` new frames."""
-        self._check_live()
+    def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
             self._m._call("gitcap_student_window_reset", self._sched.batch)
-        self._sched.reset()
+
+    def _clear(self):
         self._prev = None                                # the next caption is a plain call
-        if self._gate is not None:
-            self._gate.reset()
 
     def stats(self) -> dict:
         """Since the stream was opened: ``captions`` returned, ``draft_tokens`` offered to the verify pass (per clip; 0 for a
@@ -94,60 +77,47 @@ class StudentCaptionStream:
         self._sched.check(frames.shape[0], frames.shape[1])          # before any device work
         return m.image_encoder.memory(frames).contiguous()
 
-    def push(self, frames: torch.Tensor):
-        """Append one frame per clip or n of them (see ``_tokens``), on the CPU or the device; only these frames are encoded.
-        -> None, or the caption of the window when one is due: greedy ids [B, 1+steps] (truncated as in greedy_decode), or
-        with ``beams`` the best beam [B, max_len]; on the CPU when the frames were.  A gated stream takes uint8 camera frames
-        only, [B,H,W,3] or [B,n,H,W,3]; the window and `hop` count the frames the gate admits, and a push with none returns None."""
-        self._check_live()
-        if self._gate is None:
-            return self._push(frames, frames.device.type == "cpu")
-        admitted = gated_frames(self._gate, frames, self._sched, self._m._dev)
-        return None if admitted is None else self._push(admitted, frames.device.type == "cpu")
-
     def _push(self, frames: torch.Tensor, to_cpu: bool):
+        """frames: see ``_tokens``; only these frames are encoded.  -> None, or the caption of the window when one is due: greedy
+        ids [B, 1+steps] (truncated as in greedy_decode), or with ``beams`` the best beam [B, max_len]."""
         m = self._m
         mem = self._tokens(frames)
         B, n = mem.shape[:2]
         self._sched.check(B, n)
         with torch.cuda.device(m._dev):
-            m._call("gitcap_student_window_push", ctypes.c_void_p(mem.data_ptr()), B, n, m._stream())
+            m._call("gitcap_student_window_push", _lib.ptr(mem), B, n, m._stream())
         if not self._sched.push(B, n):
             return None
         with torch.cuda.device(m._dev):
             if self._beams is None:
-                ids = torch.empty((B, self._max_len + 1), dtype=torch.int64, device=m._dev)
-                steps = torch.zeros(1, dtype=torch.int32, device=m._dev)
+                ids, steps, lp = self._greedy_buffers(B)
                 last = dict(draft_tokens=0, accepted=0, tail_steps=0)
-                lp = torch.empty((B, self._max_len), dtype=torch.float32, device=m._dev) if self._want_lp else None
                 if self._carry and self._prev is not None:
                     last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
                     m._attach_logprobs(lp)
-                    m._call("gitcap_student_window_greedy", self._max_len, self._mode, ctypes.c_void_p(ids.data_ptr()),
-                            ctypes.c_void_p(steps.data_ptr()), m._stream())
-                if self._mode == STOP_ALL_SEP:
-                    ids = ids[:, :1 + int(steps.item())]
+                    m._call("gitcap_student_window_greedy", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps), m._stream())
+                out = self._finish_greedy(ids, steps, lp, to_cpu)
                 if self._carry:
-                    self._prev = ids
-                if lp is not None:
-                    lp = lp[:, :ids.shape[1] - 1]
-                    self.last_logprobs = lp.cpu() if to_cpu else lp
+                    self._prev = ids[:, :out.shape[1]]       # stays on the device, truncated as the caption is
                 for k, v in last.items():
                     self._stats[k] += v
                 self._stats["last"] = last
             else:
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
-                m._call("gitcap_student_window_beam_search", self._beams, self._max_len, ctypes.c_void_p(ids.data_ptr()), m._stream())
+                m._call("gitcap_student_window_beam_search", self._beams, self._max_len, _lib.ptr(ids), m._stream())
+                out = ids.cpu() if to_cpu else ids
         self._stats["captions"] += 1
-        return ids.cpu() if to_cpu else ids
+        return out
 
 
 def _rebuild_student(cfg_dict, weights, kwargs, encoder=None):
     return StudentCaptioner(cfg=StudentConfig(**cfg_dict), weights=weights, image_encoder=encoder, **kwargs)
 
 
-class StudentCaptioner(nn.Module):
+class StudentCaptioner(_NativeModule):
+    _PREFIX, _FINALIZE = "gitcap_student", "gitcap_student_finalize"
+
     def __init__(self, image_enc_name: Optional[str] = None, d_model: int = 576, n_head: int = 8, d_ffn: int = 1024,
                  dropout: float = 0.0, num_decoder_layers: int = 2, vocab_length: int = 30522, cls_token_id: int = 101,
                  sep_token_id: int = 102, *, cfg: Optional[StudentConfig] = None,
@@ -180,68 +150,30 @@ class StudentCaptioner(nn.Module):
         self.last_accepted: Optional[int] = None        # draft tokens the last greedy_decode(draft=...) accepted
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
-        self._create()
+        self._open()
         if weights is not None:
             self.load_state_dict(weights)
 
     # ------------------------------------------------------------------ handle management
-    def _create(self):
-        if self._dev.type != "cuda":
-            raise _lib.GitcapError("gitcap runs on an AMD GPU only (no CPU path); got device %s" % self._dev)
-        if not torch.cuda.is_available():
-            raise _lib.GitcapError("no HIP device visible: gitcap has no CPU fallback")
+    def _cconfig(self):
         self.max_batch, self.max_text_len = self._kw["max_batch"], self._kw["max_text_len"]
-        cc = CStudentConfig.from_config(self.cfg, self.max_batch, self.max_text_len)
-        h = ctypes.c_void_p()
-        idx = self._dev.index if self._dev.index is not None else torch.cuda.current_device()
-        self._dev = torch.device("cuda", idx)
-        rc = self._lib.gitcap_student_create(ctypes.byref(cc), idx, ctypes.byref(h))
-        self._check(None, rc, "gitcap_student_create")
-        self._handle = h
+        return CStudentConfig.from_config(self.cfg, self.max_batch, self.max_text_len)
 
-    def _check(self, handle, rc, what):
-        if rc != 0:
-            msg = self._lib.gitcap_student_last_error(handle)
-            raise _lib.GitcapError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
-
-    def _call(self, name, *args):
-        self._check(self._handle, getattr(self._lib, name)(self._handle, *args), name)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.gitcap_student_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+    def _moved(self):
+        self._window_owner = None                       # the window lived in the old handle
 
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, *args, **kwargs):
-        dev = kwargs.get("device", args[0] if args else None)
-        if isinstance(dev, (str, torch.device)):
-            dev = torch.device(dev)
-            if dev.type != "cuda":
-                raise _lib.GitcapError("gitcap has no CPU path; .to(%s) refused" % dev)
-            idx = dev.index if dev.index is not None else torch.cuda.current_device()
-            if idx != self._dev.index:
-                self._lib.gitcap_student_destroy(self._handle)
-                self._window_owner = None               # the window lived in the old handle
-                self._dev = torch.device("cuda", idx)
-                self._create()
-                if self._weights is not None:
-                    self._upload(self._weights)
-            if self.image_encoder is not None:
-                self.image_encoder.to(self._dev)
+        super().to(*args, **kwargs)
+        if self._device_arg(args, kwargs) is not None and self.image_encoder is not None:
+            self.image_encoder.to(self._dev)            # whether or not the decoder had to move
         return self
 
     def _native(self) -> bool:
         return isinstance(self.image_encoder, TinyViTEncoder)
 
     def state_dict(self, *a, **k):
-        sd = {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
+        sd = super().state_dict()
         if self._native():
             sd.update({ENC_PREFIX + n: v for n, v in self.image_encoder.state_dict().items()})
         return sd
@@ -265,20 +197,14 @@ class StudentCaptioner(nn.Module):
                     w[name] = positional_table(self.cfg.d_model, self.cfg.max_pos)
                     continue
                 raise KeyError(f"missing student weight {name}")
-            v = state_dict[name]
-            w[name] = np.ascontiguousarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+            w[name] = self._as_f32(state_dict[name])
         check_student_shapes(self.cfg, w)
         self._upload(w)
         self._weights = w
         return self
 
     def _upload(self, w):
-        with torch.cuda.device(self._dev):
-            for name in student_shapes(self.cfg):
-                arr = np.ascontiguousarray(w[name], dtype=np.float32)
-                shape = (ctypes.c_int64 * arr.ndim)(*arr.shape)
-                self._call("gitcap_student_load_tensor", name.encode(), arr.ctypes.data_as(ctypes.c_void_p), shape, arr.ndim)
-            self._call("gitcap_student_finalize")
+        self._load_tensors((name, w[name]) for name in student_shapes(self.cfg))
 
     def __reduce__(self):
         if self.image_encoder is not None and not self._native():
@@ -337,9 +263,8 @@ class StudentCaptioner(nn.Module):
             raise ValueError(f"T={T} outside 1..max_text_len+1={self.max_text_len + 1}")
         logits = torch.empty((B, T, self.cfg.vocab_length), dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
-            self._call("gitcap_student_set_memory", ctypes.c_void_p(mem.data_ptr()), B, self._stream())
-            self._call("gitcap_student_forward_decoder", ctypes.c_void_p(ids.data_ptr()), T, B, T,
-                       ctypes.c_void_p(logits.data_ptr()), self._stream())
+            self._call("gitcap_student_set_memory", _lib.ptr(mem), B, self._stream())
+            self._call("gitcap_student_forward_decoder", _lib.ptr(ids), T, B, T, _lib.ptr(logits), self._stream())
         return logits
 
     def forward(self, x: torch.Tensor, y: torch.Tensor):
@@ -350,7 +275,7 @@ class StudentCaptioner(nn.Module):
     def _attach_logprobs(self, lp: Optional[torch.Tensor]):
         """One-shot: the next greedy-family call writes its per-token log-probabilities to ``lp`` (fp32 [B, max_len], contiguous)."""
         if lp is not None:
-            self._call("gitcap_student_attach_token_logprobs", ctypes.c_void_p(lp.data_ptr()), lp.shape[1])
+            self._call("gitcap_student_attach_token_logprobs", _lib.ptr(lp), lp.shape[1])
 
     def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor,
                     lp: Optional[torch.Tensor] = None) -> dict:
@@ -365,8 +290,7 @@ class StudentCaptioner(nn.Module):
         acc = ctypes.c_int32(-1)
         before = self._draft_stats()
         self._attach_logprobs(lp)
-        self._call(name, *head, ctypes.c_void_p(d.data_ptr()), n + 1, n, max_len, mode, ctypes.c_void_p(ids.data_ptr()),
-                   ctypes.c_void_p(steps.data_ptr()), ctypes.byref(acc), self._stream())
+        self._call(name, *head, _lib.ptr(d), n + 1, n, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), ctypes.byref(acc), self._stream())
         self.last_accepted = int(acc.value)
         return dict(draft_tokens=n, accepted=self.last_accepted, tail_steps=self._draft_stats()[3] - before[3])
 
@@ -400,11 +324,10 @@ class StudentCaptioner(nn.Module):
         lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
         with torch.cuda.device(self._dev):
             if draft is not None:
-                self._draft_call("gitcap_student_greedy_draft", (ctypes.c_void_p(mem.data_ptr()), B), draft, max_len, mode, ids, steps, lp)
+                self._draft_call("gitcap_student_greedy_draft", (_lib.ptr(mem), B), draft, max_len, mode, ids, steps, lp)
             else:
                 self._attach_logprobs(lp)
-                self._call("gitcap_student_greedy", ctypes.c_void_p(mem.data_ptr()), B, max_len, mode,
-                           ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), self._stream())
+                self._call("gitcap_student_greedy", _lib.ptr(mem), B, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
         ids = ids.to(out_dev) if out_dev != ids.device else ids
@@ -433,8 +356,7 @@ class StudentCaptioner(nn.Module):
             raise ValueError("beam_search needs max_len >= 2 and 1 <= k <= 16")
         best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
         with torch.cuda.device(self._dev):
-            self._call("gitcap_student_beam_search", ctypes.c_void_p(mem.data_ptr()), B, k, max_len,
-                       ctypes.c_void_p(best.data_ptr()), self._stream())
+            self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, _lib.ptr(best), self._stream())
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,

@@ -16,9 +16,9 @@ from typing import Dict, Mapping, Optional
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib
+from ._handle import _NativeModule
 from .tinyvit_config import (CTinyViTConfig, TinyViTConfig, canonical_key, check_tinyvit_shapes, fold_convnorm,  # noqa: F401
                              folded_tensors, normalise_keys, tinyvit_config, tinyvit_shapes, tinyvit_synthetic_weights,
                              tinyvit_tiny)
@@ -31,7 +31,9 @@ def _rebuild_tinyvit(cfg_dict, weights, kwargs):
     return TinyViTEncoder(TinyViTConfig(**cfg_dict), weights=weights, **kwargs)
 
 
-class TinyViTEncoder(nn.Module):
+class TinyViTEncoder(_NativeModule):
+    _PREFIX, _FINALIZE = "gitcap_tinyvit", "gitcap_tinyvit_finalize"
+
     def __init__(self, cfg: TinyViTConfig, weights: Optional[Mapping[str, object]] = None,
                  device: str | torch.device = "cuda:0", max_frames: int = 96):
         super().__init__()
@@ -42,39 +44,13 @@ class TinyViTEncoder(nn.Module):
         self._handle = None
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._lib = _lib.load()
-        self._create()
+        self._open()
         if weights is not None:
             self.load_state_dict(weights)
 
     # ------------------------------------------------------------------ handle management
-    def _create(self):
-        if self._dev.type != "cuda":
-            raise _lib.GitcapError("gitcap runs on an AMD GPU only (no CPU path); got device %s" % self._dev)
-        if not torch.cuda.is_available():
-            raise _lib.GitcapError("no HIP device visible: gitcap has no CPU fallback")
-        idx = self._dev.index if self._dev.index is not None else torch.cuda.current_device()
-        self._dev = torch.device("cuda", idx)
-        cc = CTinyViTConfig.from_config(self.cfg, self.max_frames)
-        h = ctypes.c_void_p()
-        rc = self._lib.gitcap_tinyvit_create(ctypes.byref(cc), idx, ctypes.byref(h))
-        self._check(None, rc, "gitcap_tinyvit_create")
-        self._handle = h
-
-    def _check(self, handle, rc, what):
-        if rc != 0:
-            msg = self._lib.gitcap_tinyvit_last_error(handle)
-            raise _lib.GitcapError(f"{what} failed (status {rc}): {msg.decode() if msg else '?'}")
-
-    def _call(self, name, *args):
-        self._check(self._handle, getattr(self._lib, name)(self._handle, *args), name)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None):
-                self._lib.gitcap_tinyvit_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
+    def _cconfig(self):
+        return CTinyViTConfig.from_config(self.cfg, self.max_frames)
 
     @property
     def device(self) -> torch.device:
@@ -84,22 +60,6 @@ class TinyViTEncoder(nn.Module):
     def out_dim(self) -> int:
         return self.cfg.embed_dims[3]
 
-    def to(self, *args, **kwargs):
-        dev = kwargs.get("device", args[0] if args else None)
-        if isinstance(dev, (str, torch.device)):
-            dev = torch.device(dev)
-            if dev.type != "cuda":
-                raise _lib.GitcapError("gitcap has no CPU path; .to(%s) refused" % dev)
-            idx = dev.index if dev.index is not None else torch.cuda.current_device()
-            if idx != self._dev.index:
-                self._lib.gitcap_tinyvit_destroy(self._handle)
-                self._handle = None
-                self._dev = torch.device("cuda", idx)
-                self._create()
-                if self._weights is not None:
-                    self._upload(self._weights)
-        return self
-
     def cpu(self):
         raise _lib.GitcapError("gitcap has no CPU path; .cpu() refused")
 
@@ -108,21 +68,17 @@ class TinyViTEncoder(nn.Module):
     def loaded(self) -> bool:
         return self._weights is not None
 
-    def state_dict(self, *a, **k):
-        """Canonical keys (``stages_i`` form, no prefix), BatchNorms unfolded, as loaded."""
-        return {n: torch.from_numpy(v) for n, v in (self._weights or {}).items()}
-
     def load_state_dict(self, state_dict, strict: bool = True):
         """Takes the keys with the prefix ``image_encoder.model.``, ``model.`` or none, and ``stages_i`` or ``stages.i``;
         ``num_batches_tracked`` and ``attention_bias_idxs`` are ignored (the index table is rebuilt).  Every key of
-        ``tinyvit_shapes`` must be present."""
+        ``tinyvit_shapes`` must be present.  ``state_dict()`` returns them as loaded: canonical keys (``stages_i`` form, no
+        prefix), BatchNorms unfolded."""
         state = normalise_keys(state_dict)
         w = {}
         for name in tinyvit_shapes(self.cfg):
             if name not in state:
                 raise KeyError(f"missing TinyViT weight {name}")
-            v = state[name]
-            w[name] = np.ascontiguousarray(v.detach().cpu().float().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+            w[name] = self._as_f32(state[name])
         if strict:
             extra = sorted(set(state) - set(w))
             if extra:
@@ -133,12 +89,7 @@ class TinyViTEncoder(nn.Module):
         return self
 
     def _upload(self, w):
-        with torch.cuda.device(self._dev):
-            for name, arr in folded_tensors(self.cfg, w).items():
-                arr = np.ascontiguousarray(arr, dtype=np.float32)
-                shape = (ctypes.c_int64 * arr.ndim)(*arr.shape)
-                self._call("gitcap_tinyvit_load_tensor", name.encode(), arr.ctypes.data_as(ctypes.c_void_p), shape, arr.ndim)
-            self._call("gitcap_tinyvit_finalize")
+        self._load_tensors(folded_tensors(self.cfg, w).items())
 
     def __reduce__(self):
         return _rebuild_tinyvit, (asdict(self.cfg), self._weights, dict(device=str(self._dev), max_frames=self.max_frames))
@@ -178,13 +129,10 @@ class TinyViTEncoder(nn.Module):
             ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in fmaps])
             arr = ctypes.cast(ptrs, ctypes.c_void_p)
         with torch.cuda.device(self._dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
             if x.dtype == torch.uint8:       # the transform is fused with the first stem convolution's gather
-                self._call("gitcap_tinyvit_encode_raw", ctypes.c_void_p(x.data_ptr()), n, x.shape[1], x.shape[2],
-                           ctypes.c_void_p(mem.data_ptr()), arr, stream)
+                self._call("gitcap_tinyvit_encode_raw", _lib.ptr(x), n, x.shape[1], x.shape[2], _lib.ptr(mem), arr, self._stream())
             else:
-                self._call("gitcap_tinyvit_encode", ctypes.c_void_p(x.data_ptr()), n, ctypes.c_void_p(mem.data_ptr()),
-                           arr, stream)
+                self._call("gitcap_tinyvit_encode", _lib.ptr(x), n, _lib.ptr(mem), arr, self._stream())
         return fmaps, mem
 
     @torch.no_grad()
