@@ -155,15 +155,14 @@ struct gitcap : HandleCore {
     int lp_ld = 0;
 
     // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
-    // last win_F frames of win_B clips, clip-major [B][F][N][Dv].  win_head = the slot the next frame goes to (= the oldest frame
-    // once the window is full); win_count = frames pushed since the reset, capped at F.  A push orders itself behind the last
-    // window call's image prefix (ev_read: it rewrites the encoder workspace, hb included) and a window call behind the last
-    // push (ev_ring), whichever streams they were issued on.
+    // last win.slots frames of win_B clips, clip-major [B][F][N][Dv]; win (RingCursor) = where the next frame goes and how many
+    // have been pushed.  win_order (RingOrder): a push orders itself behind the last window call's image prefix (it rewrites the
+    // encoder workspace, hb included) and a window call behind the last push, whichever streams they were issued on.
     float* win_ring = nullptr;
     int64_t win_bytes = 0;
-    int win_B = 0, win_F = 0, win_head = 0, win_count = 0;
-    hipEvent_t win_ev_ring = nullptr, win_ev_read = nullptr;
-    bool win_ring_rec = false, win_read_rec = false;
+    int win_B = 0;
+    RingCursor win;
+    RingOrder win_order;
 
     // instrumentation (bench.py): HIP-event brackets per kernel class, on the launch stream
     bool prof_on = false;
@@ -220,7 +219,7 @@ int poll_exchange(gitcap* h) {
     h->poison_upto = poison_mark(h->next_ticket);   // every submission made so far may hold undefined rows: its wait says so, every time
     *(volatile unsigned*)h->ln_fail = 0;
     if (h->ln_cnt) (void)hipMemset(h->ln_cnt, 0, h->ln_cnt_words * sizeof(unsigned));
-    h->win_count = 0;       // the frame window's rows may be undefined too: it is emptied, the caller pushes its frames again
+    h->win.clear();         // the frame window's rows may be undefined too: it is emptied, the caller pushes its frames again
     return fail(h, GITCAP_ERR_EXCHANGE, "a GEMM + LayerNorm launch timed out waiting for its sibling tiles (CUs held by another "
                 "process or a CU-masked stream?): results since the last call are undefined -- re-run them; this handle now uses "
                 "separate LayerNorm launches");
@@ -601,25 +600,18 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     if (!logits_out && !argmax_out) return 0;
     // vocabulary head (+ arg-max partials per 16-column tile, reduced by argmax_final)
     const int V = c.vocab_size, ntiles = (V + 15) / 16;
-    SkinnyArgs ha{};
-    ha.W = h->head_w.p; ha.Wpk = h->head_w.pk; ha.wscale = h->head_w.scale; ha.bias = h->head_b; ha.N = V; ha.K = D; ha.ldo = V; ha.T = 1; ha.row_stride = 1; ha.row_off = 0;
-    int am_stride = 1, am_off = 0;
-    if (all_positions && logits_out) {
-        ha.X = sl.xsb; ha.ldx = D; ha.M = M; ha.out = logits_out;
-        am_stride = T; am_off = T - 1;
-    } else {
-        ha.X = sl.xsb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows; ha.out = logits_out;
-    }
-    if (argmax_out) { ha.amax_val = sl.amax_val; ha.amax_idx = sl.amax_idx; }
     if (lp_out && (!argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
-    if (lp_out) ha.amax_sum = sl.amax_sum;      // the head's third partial -> the chosen token's log-probability (argmax_final)
+    SkinnyArgs ha;      // amax_sum: the head's third partial -> the chosen token's log-probability (argmax_final)
+    const HeadRows hr = vocab_head_args(ha, HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, rows, T,
+                                        all_positions && logits_out, logits_out, argmax_out ? sl.amax_val : nullptr,
+                                        argmax_out ? sl.amax_idx : nullptr, lp_out ? sl.amax_sum : nullptr);
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
         HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     }
     if (argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
-        HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
+        HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, hr.am_stride, hr.am_off, argmax_out, ld_argmax,
                                       sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr, lp_out ? sl.amax_sum : nullptr,
                                       lp_out, ld_lp));
     }
@@ -645,6 +637,7 @@ int check_raw(gitcap* h, const uint8_t* frames, int B, int F, int H, int W) {
 
 struct FrameSrc { const float* f32; const uint8_t* u8; int H, W; };     // fp32 NCHW (CLIP-normalised) or raw uint8 HWC BGR
 static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream);
+static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t s);
 
 // Pipelined submission: the image pass on the encoder stream, `text_loop` on the slot's decode stream (see gitcap_greedy_submit).
 // A failure after the first enqueue must not leave the slot unordered (the next user of the slot waits on ev_dec only): from
@@ -830,8 +823,7 @@ void gitcap_destroy(gitcap_t* h) {
     for (auto& t : h->txt_streams)
         if (t) (void)hipStreamDestroy(t);
     if (h->s_enc) (void)hipStreamDestroy(h->s_enc);
-    if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
-    if (h->win_ev_read) (void)hipEventDestroy(h->win_ev_read);
+    h->win_order.destroy();
     if (h->win_ring) (void)hipFree(h->win_ring);
     free_allocs(*h);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
@@ -990,9 +982,7 @@ int gitcap_encode(gitcap_t* h, const float* frames, int B, int F, float* visual_
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode: null handle");
     GUARD(h);
     POLL(h);
-    select_slot(h, 0);
-    HIP_OK(h, join_async(h, (hipStream_t)stream));
-    return encode_impl(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
+    return encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
 }
 
 // The encoder half of the image pass: B x F frames (checked by the caller) through patch gather, the ViT blocks and ln_post.
@@ -1100,6 +1090,13 @@ static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
     return image_prefix(h, B, F * h->N, stream);
 }
 
+// a synchronous call's image pass: slot 0, the caller's stream, behind the submissions in flight
+static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t s) {
+    select_slot(h, 0);
+    HIP_OK(h, join_async(h, s));
+    return encode_impl(h, src, B, F, visual_out, s);
+}
+
 int gitcap_set_visual(gitcap_t* h, const float* visual, int B, int S_img, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "set_visual: null handle");
     GUARD(h);
@@ -1149,18 +1146,6 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
 // clips are independent, every kernel is batch invariant, the captions were bitwise the same: 16 clips 323-325 / 580 / 600 us
 // per token step against 302 for one loop (profiles/r04_sync_call_split_token_loop.txt).  Chains of ~6 us launches on
 // different streams do not overlap each other the way one chain overlaps an image pass.  Removed.)
-struct LpAttach { float* p; int ld; };
-// the pending attachment of gitcap_attach_token_logprobs: taken (and with that consumed) by every greedy-family entry point
-static LpAttach take_lp(gitcap* h) {
-    const LpAttach a{h->lp_attach, h->lp_ld};
-    h->lp_attach = nullptr; h->lp_ld = 0;
-    return a;
-}
-static int lp_check(gitcap* h, const LpAttach& lp, int max_len) {
-    if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached token log-probability buffer has ld < max_len");
-    return 0;
-}
-
 static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
                             LpAttach lp = LpAttach{nullptr, 0}) {
     const int ld = max_len + 1;
@@ -1174,79 +1159,71 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
     return 0;
 }
 
-static int greedy_check(gitcap* h, int max_len, int stop, const int64_t* ids_out) {
-    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
-    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "greedy: max_len exceeds max_text_len");
-    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
-    return 0;
-}
+}  // extern "C"
 
-int gitcap_greedy(gitcap_t* h, const float* frames, int B, int F, int max_len, int stop, int64_t* ids_out,
-                  int32_t* steps_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "greedy: null handle");
+// The head of every greedy-family entry point: the null check (its message names the entry point), the pending log-probability
+// attachment is taken (a call refused below has consumed it), device, exchange health, the argument checks; then body(lp).
+template <typename Body>
+static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_len, int stop, const int64_t* ids_out, Body body) {
+    if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
     const LpAttach lp = take_lp(h);
     GUARD(h);
     POLL(h);
-    int rc = greedy_check(h, max_len, stop, ids_out);
-    rc = rc ? rc : lp_check(h, lp, max_len);
-    if (rc) return rc;
-    select_slot(h, 0);
-    HIP_OK(h, join_async(h, (hipStream_t)stream));
-    if ((rc = encode_impl(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, (hipStream_t)stream))) return rc;
-    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream, lp);
+    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
+    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "greedy: max_len exceeds max_text_len");
+    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
+    const int rc = lp_check(h, "greedy", lp, max_len);
+    return rc ? rc : body(lp);
+}
+
+// synchronous: image pass and token loop on the caller's stream, slot 0 (a raw source is checked by the image pass alone)
+static int greedy_sync(gitcap* h, const char* null_msg, FrameSrc src, int B, int F, int max_len, int stop, int64_t* ids_out,
+                       int32_t* steps_out, hipStream_t s) {
+    return greedy_entry(h, true, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+        if (int rc = encode_sync(h, src, B, F, nullptr, s)) return rc;
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+    });
+}
+
+// submitted: lp's buffer stays valid until the wait, like ids_out; raw: camera frames, checked before the submission takes a slot
+static int greedy_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, int max_len, int stop, int64_t* ids_out,
+                         int32_t* steps_out, hipStream_t stream, int* ticket) {
+    return greedy_entry(h, ticket != nullptr, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+        if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
+        return submit_common(h, src, B, F, nullptr, stream, ticket, [&](hipStream_t s) {
+            return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+        });
+    });
+}
+
+extern "C" {
+
+int gitcap_greedy(gitcap_t* h, const float* frames, int B, int F, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
+    return greedy_sync(h, "greedy: null handle", FrameSrc{frames, nullptr, 0, 0}, B, F, max_len, stop, ids_out, steps_out, (hipStream_t)stream);
 }
 
 int gitcap_encode_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, float* visual_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode_raw: null handle");
     GUARD(h);
     POLL(h);
-    select_slot(h, 0);
-    HIP_OK(h, join_async(h, (hipStream_t)stream));
-    return encode_impl(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
+    return encode_sync(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
 }
 
 int gitcap_greedy_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
                       int64_t* ids_out, int32_t* steps_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "greedy_raw: null handle");
-    const LpAttach lp = take_lp(h);
-    GUARD(h);
-    POLL(h);
-    int rc = greedy_check(h, max_len, stop, ids_out);
-    rc = rc ? rc : lp_check(h, lp, max_len);
-    if (rc) return rc;
-    select_slot(h, 0);
-    HIP_OK(h, join_async(h, (hipStream_t)stream));
-    if ((rc = encode_impl(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, nullptr, (hipStream_t)stream))) return rc;
-    return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, (hipStream_t)stream, lp);
+    return greedy_sync(h, "greedy_raw: null handle", FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, max_len, stop, ids_out, steps_out, (hipStream_t)stream);
 }
 
 int gitcap_greedy_submit(gitcap_t* h, const float* frames, int B, int F, int max_len, int stop, int64_t* ids_out,
                          int32_t* steps_out, void* stream, int* ticket) {
-    if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "greedy_submit: null argument");
-    const LpAttach lp = take_lp(h);          // captured into the submission: the buffer stays valid until the wait, like ids_out
-    GUARD(h);
-    POLL(h);
-    int rc = greedy_check(h, max_len, stop, ids_out);
-    rc = rc ? rc : lp_check(h, lp, max_len);
-    if (rc) return rc;
-    return submit_common(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
-    });
+    return greedy_submit(h, "greedy_submit: null argument", FrameSrc{frames, nullptr, 0, 0}, false, B, F, max_len, stop, ids_out, steps_out,
+                         (hipStream_t)stream, ticket);
 }
 
 int gitcap_greedy_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
                              int64_t* ids_out, int32_t* steps_out, void* stream, int* ticket) {
-    if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "greedy_raw_submit: null argument");
-    const LpAttach lp = take_lp(h);
-    GUARD(h);
-    POLL(h);
-    int rc = greedy_check(h, max_len, stop, ids_out);
-    rc = rc ? rc : lp_check(h, lp, max_len);
-    if (rc) return rc;
-    if ((rc = check_raw(h, frames_hwc_bgr, B, F, H, W))) return rc;
-    return submit_common(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, nullptr, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
-    });
+    return greedy_submit(h, "greedy_raw_submit: null argument", FrameSrc{nullptr, frames_hwc_bgr, H, W}, true, B, F, max_len, stop, ids_out,
+                         steps_out, (hipStream_t)stream, ticket);
 }
 
 int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
@@ -1259,17 +1236,6 @@ int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
         return fail(h, GITCAP_ERR_EXCHANGE, "this submission was in flight when a GEMM + LayerNorm launch timed out waiting for its sibling "
                     "tiles: its results are undefined -- submit it again (the handle now uses separate LayerNorm launches)");
     HIP_OK(h, hipStreamWaitEvent((hipStream_t)stream, h->slots[ticket_slot(ticket, gitcap::NSLOT)].ev_dec, 0));
-    return 0;
-}
-
-static int beam_check(gitcap* h, int beams, int max_steps, int per_node_beam_size, const int64_t* decoded_out, const float* logprobs_out) {
-    if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
-    if (beams > h->c.max_beams || beams > 16 || beams * per_node_beam_size > 16)
-        return fail(h, GITCAP_ERR_ARG, "beam_search: beams exceed max_beams / 16 candidates");
-    if (max_steps < 2 || max_steps > h->Tmax) return fail(h, GITCAP_ERR_ARG, "beam_search: max_steps outside [2, max_text_len]");
-    // with fewer than 2 candidates per beam one EOS candidate leaves a sentence short of `beams` live beams, which the
-    // reference asserts against (model.py:606); the device bookkeeping has no way to report it, so refuse up front
-    if (per_node_beam_size < 2) return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size must be >= 2 (model.py:606)");
     return 0;
 }
 
@@ -1303,45 +1269,60 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
 
 int gitcap_beam_search_wait(gitcap_t* h, int ticket, void* stream) { return gitcap_greedy_wait(h, ticket, stream); }
 
-int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams, int max_steps, float length_penalty,
-                       int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "beam_search: null handle");
+}  // extern "C"
+
+// The head of every beam-search entry point (as greedy_entry, without an attachment); then `body()`.
+template <typename Body>
+static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, int max_steps, int per_node_beam_size,
+                      const int64_t* decoded_out, const float* logprobs_out, Body body) {
+    if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
     GUARD(h);
     POLL(h);
-    int rc = beam_check(h, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    select_slot(h, 0);
-    HIP_OK(h, join_async(h, s));
-    if ((rc = encode_impl(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s))) return rc;
-    return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+    if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
+    if (beams > h->c.max_beams || beams > 16 || beams * per_node_beam_size > 16)
+        return fail(h, GITCAP_ERR_ARG, "beam_search: beams exceed max_beams / 16 candidates");
+    if (max_steps < 2 || max_steps > h->Tmax) return fail(h, GITCAP_ERR_ARG, "beam_search: max_steps outside [2, max_text_len]");
+    // with fewer than 2 candidates per beam one EOS candidate leaves a sentence short of `beams` live beams, which the
+    // reference asserts against (model.py:606); the device bookkeeping has no way to report it, so refuse up front
+    if (per_node_beam_size < 2) return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size must be >= 2 (model.py:606)");
+    return body();
+}
+
+extern "C" {
+
+int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams, int max_steps, float length_penalty,
+                       int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
+    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s)) return rc;
+        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+    });
+}
+
+// raw: as greedy_submit
+static int beam_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, float* visual_out, int beams, int max_steps,
+                       float length_penalty, int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, float* step_logits_out,
+                       hipStream_t stream, int* ticket) {
+    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+        if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
+        return submit_common(h, src, B, F, visual_out, stream, ticket, [&](hipStream_t s) {
+            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
+        });
+    });
 }
 
 int gitcap_beam_search_submit(gitcap_t* h, const float* frames, int B, int F, float* visual_out, int beams, int max_steps,
                               float length_penalty, int per_node_beam_size, int64_t* decoded_out, float* logprobs_out,
                               float* step_logits_out, void* stream, int* ticket) {
-    if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "beam_search_submit: null argument");
-    GUARD(h);
-    POLL(h);
-    int rc = beam_check(h, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out);
-    if (rc) return rc;
-    return submit_common(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
-    });
+    return beam_submit(h, "beam_search_submit: null argument", FrameSrc{frames, nullptr, 0, 0}, false, B, F, visual_out, beams, max_steps,
+                       length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, (hipStream_t)stream, ticket);
 }
 
 int gitcap_beam_search_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, float* visual_out, int beams,
                                   int max_steps, float length_penalty, int per_node_beam_size, int64_t* decoded_out,
                                   float* logprobs_out, float* step_logits_out, void* stream, int* ticket) {
-    if (!h || !ticket) return fail(h, GITCAP_ERR_ARG, "beam_search_raw_submit: null argument");
-    GUARD(h);
-    POLL(h);
-    int rc = beam_check(h, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out);
-    if (rc) return rc;
-    if ((rc = check_raw(h, frames_hwc_bgr, B, F, H, W))) return rc;
-    return submit_common(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream, ticket, [&](hipStream_t s) {
-        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
-    });
+    return beam_submit(h, "beam_search_raw_submit: null argument", FrameSrc{nullptr, frames_hwc_bgr, H, W}, true, B, F, visual_out, beams,
+                       max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, (hipStream_t)stream, ticket);
 }
 
 // ---- frame window ------------------------------------------------------------------------------------------------------------
@@ -1361,43 +1342,39 @@ int gitcap_window_reset(gitcap_t* h, int B, int F) {
         HIP_OK(h, hipFree(h->win_ring));
         h->win_ring = nullptr; h->win_bytes = 0;
     }
-    h->win_B = h->win_F = h->win_head = h->win_count = 0;
+    h->win_B = 0;
+    h->win.reset(0);
     if (B == 0) return 0;
-    if (!h->win_ev_ring) {
-        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
-        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
-    }
+    HIP_OK(h, h->win_order.ensure());
     if (!h->win_ring) {
         hipError_t e = hipMalloc(&h->win_ring, (size_t)bytes);
         if (e != hipSuccess) { h->win_ring = nullptr; return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc frame window: ") + hipGetErrorString(e)); }
         h->win_bytes = bytes;
     }
-    h->win_B = B; h->win_F = F;
+    h->win_B = B;
+    h->win.reset(F);
     return 0;
 }
 
 // encode n new frames of each clip and append them to the ring: fp32 ln_post rows -> staging -> ring slots
 static int window_push(gitcap* h, FrameSrc src, int B, int n, hipStream_t s) {
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "window_push: no frame window (gitcap_window_reset first)");
-    if (B != h->win_B || n < 1 || n > h->win_F) return fail(h, GITCAP_ERR_ARG, "window_push: B differs from the reset's, or n outside [1, F]");
+    if (B != h->win_B || n < 1 || n > h->win.slots) return fail(h, GITCAP_ERR_ARG, "window_push: B differs from the reset's, or n outside [1, F]");
     int rc = src.u8 ? check_raw(h, src.u8, B, n, src.H, src.W) : check_frames(h, src.f32, B, n);
     if (rc) return rc;
     select_slot(h, 0);
     HIP_OK(h, join_async(h, s));
-    if (h->win_read_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
-    if (h->win_ring_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    HIP_OK(h, h->win_order.before_push(s));
     // staging: the q|k|v buffer of the image rows (bf16 [Mi][3 Dv], 1.5x the bytes of fp32 [Mi][Dv]) is dead once the last block's
     // attention has read it, and only the final FC2 + ln_post launch and the scatter run after that
     float* stage = (float*)h->qkv;
     if ((rc = encode_frames(h, src, B, n, stage, nullptr, false, s))) return rc;
     {
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, 8.0 * B * n * (double)h->N * h->Dv);
-        HIP_OK(h, launch_window_scatter(stage, h->win_ring, B, n, h->win_F, h->win_head, h->N, h->Dv, s));
+        HIP_OK(h, launch_window_scatter(stage, h->win_ring, B, n, h->win.slots, h->win.head, h->N, h->Dv, s));
     }
-    HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
-    h->win_ring_rec = true;
-    h->win_head = (h->win_head + n) % h->win_F;
-    h->win_count = std::min(h->win_count + n, h->win_F);
+    HIP_OK(h, h->win_order.after_push(s));
+    h->win.push(n);
     return 0;
 }
 
@@ -1417,49 +1394,40 @@ int gitcap_window_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, in
 
 // the current window -> decoder input (+ visual features) -> image prefix on slot 0
 static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
-    if (!h->win_ring || h->win_count < h->win_F) return fail(h, GITCAP_ERR_STATE, "window: fewer than F frames pushed since the reset");
+    if (!h->win_ring || !h->win.full()) return fail(h, GITCAP_ERR_STATE, "window: fewer than F frames pushed since the reset");
     if (((uintptr_t)visual_out & 15) != 0) return fail(h, GITCAP_ERR_ARG, "window: visual_out must be 16-byte aligned");
-    const int B = h->win_B, F = h->win_F, N = h->N, Dv = h->Dv;
+    const int B = h->win_B, F = h->win.slots, N = h->N, Dv = h->Dv;
     const float* temporal = h->c.num_frames > 0 ? h->temporal : nullptr;
     select_slot(h, 0);
     HIP_OK(h, join_async(h, s));
-    HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    HIP_OK(h, h->win_order.before_read(s));
     cur(h).have = false;
     {
         const double rows = (double)B * F * N;
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, rows * Dv * (4.0 + 2.0 + (visual_out ? 4.0 : 0.0)));
-        HIP_OK(h, launch_window_assemble(h->win_ring, temporal, h->hb, visual_out, B, F, h->win_head, N, Dv, s));
+        HIP_OK(h, launch_window_assemble(h->win_ring, temporal, h->hb, visual_out, B, F, h->win.head, N, Dv, s));
     }
     int rc = image_prefix(h, B, F * N, s);
     if (rc) return rc;
-    HIP_OK(h, hipEventRecord(h->win_ev_read, s));
-    h->win_read_rec = true;
+    HIP_OK(h, h->win_order.after_read(s));
     return 0;
 }
 
 int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "window_greedy: null handle");
-    const LpAttach lp = take_lp(h);
-    GUARD(h);
-    POLL(h);
-    int rc = greedy_check(h, max_len, stop, ids_out);
-    rc = rc ? rc : lp_check(h, lp, max_len);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = window_prefix(h, visual_out, s))) return rc;
-    return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
+    return greedy_entry(h, true, "window_greedy: null handle", max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc = window_prefix(h, visual_out, s)) return rc;
+        return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
+    });
 }
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "window_beam_search: null handle");
-    GUARD(h);
-    POLL(h);
-    int rc = beam_check(h, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = window_prefix(h, visual_out, s))) return rc;
-    return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc = window_prefix(h, visual_out, s)) return rc;
+        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+    });
 }
 
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {

@@ -1,6 +1,7 @@
 // CPU-only driver of the host logic under AddressSanitizer + UBSan (`make asan`): no HIP, no GPU.
 #include "host_logic.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -79,6 +80,29 @@ int main() {
         upto = poison_mark(9);
         CHECK(ticket_poisoned(8, upto) && !ticket_poisoned(9, upto));
     }
+    // window ring: a push of n entries from every head splits into the run up to the wrap and the remainder from slot 0, the
+    // head moves by n modulo the slots, the count saturates, and emptying the ring keeps its size
+    for (int F = 1; F <= 8; ++F)
+        for (int head = 0; head < F; ++head)
+            for (int n = 1; n <= F; ++n) {
+                RingCursor r;
+                r.reset(F);
+                CHECK(r.slots == F && r.head == 0 && r.count == 0 && !r.full());
+                for (int i = 0; i < head; ++i) r.push(1);
+                CHECK(r.head == head && r.count == head && r.full() == (head == F));
+                const int n1 = r.first_run(n), n2 = n - n1;
+                CHECK(n1 >= 1 && n2 >= 0 && n1 + n2 == n && head + n1 <= F && (n2 == 0 || head + n1 == F) && n2 <= head);
+                r.push(n);
+                CHECK(r.head == (head + n1) % F + n2 && r.head < F && r.count == std::min(head + n, F) && r.full() == (head + n >= F));
+                for (int i = 0; i < F; ++i) r.push(1);                    // F single pushes: the head is back where it was, the ring full
+                CHECK(r.head == (head + n) % F && r.count == F && r.full());
+                r.clear();
+                CHECK(r.slots == F && r.count == 0 && !r.full() && r.head == (head + n) % F);
+                r.reset(F);
+                for (int i = 0; i < F; ++i) r.push(1);
+                CHECK(r.head == 0 && r.full());
+            }
+    { RingCursor r; CHECK(!r.full()); }
     // residual + LayerNorm GEMM: every tile exactly once, a row block's tiles = consecutive workgroups of one XCD
     for (int ntn = 1; ntn <= 4; ++ntn)
         for (int nrb = 1; nrb <= 300; ++nrb) {

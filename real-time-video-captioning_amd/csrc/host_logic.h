@@ -1,6 +1,6 @@
 // Host-only logic of libgitcap, free of any HIP dependency so that it also compiles for the CPU under
 // -fsanitize=address,undefined (`make asan`, tests/test_host_asan.py): numeric encodings of the weight loader, the
-// canonical tensor table, the pipeline's ticket -> slot bookkeeping and the workgroup -> tile map of the residual +
+// canonical tensor table, the pipeline's ticket -> slot bookkeeping, the window rings' cursor and the workgroup -> tile map of the residual +
 // LayerNorm GEMM (shared with the kernel, which compiles the same function for the device).
 #pragma once
 #include <cmath>
@@ -155,6 +155,16 @@ inline bool ticket_waitable(int ticket, int next_ticket, int nslot) {
 inline int poison_mark(int next_ticket) { return next_ticket; }
 inline bool ticket_poisoned(int ticket, int poison_upto) { return ticket < poison_upto; }
 
+// Window ring (the teacher's frame window and the student's memory-token window): `slots` entries per clip, head = the slot the
+// next entry goes to (the oldest entry once the ring is full), count = entries pushed since the reset, capped at slots.
+struct RingCursor {
+    int slots = 0, head = 0, count = 0;
+    void reset(int n) { slots = n; head = count = 0; }
+    int first_run(int n) const { return n < slots - head ? n : slots - head; }      // of n <= slots new entries, those up to the wrap
+    void push(int n) { head = (head + n) % slots; count = count + n < slots ? count + n : slots; }
+    bool full() const { return slots > 0 && count >= slots; }
+    void clear() { count = 0; }     // the entries may be undefined (a failed push, a failed exchange): pushed again by the caller
+};
 
 // ---- residual + LayerNorm GEMM: workgroup -> tile ----------------------------------------------------------------
 // The N/256 tiles of a 256-row block wait for each other (statistics exchange, gemm_epilogue.h), so they must be

@@ -87,3 +87,41 @@ int upload_bf16_panel(H* h, DevTensor& t, const float* data, int64_t rows, int64
     t.bytes = (int64_t)hb.size() * 2;
     return 0;
 }
+
+// The pending attachment of *_attach_token_logprobs (handle fields lp_attach / lp_ld): taken, and with that consumed, by every
+// greedy-family entry point before its argument checks.  `who` leads the message ("greedy", "student_greedy", ...).
+struct LpAttach { float* p; int ld; };
+template <class H>
+LpAttach take_lp(H* h) {
+    const LpAttach a{h->lp_attach, h->lp_ld};
+    h->lp_attach = nullptr; h->lp_ld = 0;
+    return a;
+}
+template <class H>
+int lp_check(H* h, const char* who, const LpAttach& lp, int max_len) {
+    if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached token log-probability buffer has ld < max_len");
+    return 0;
+}
+
+// Ordering of a window ring's pushes and reads, whichever streams they are issued on: a push waits for the last read and the
+// last push (they share the staging rows) and records the ring event; a read waits for the ring event and records the read event.
+struct RingOrder {
+    hipEvent_t ev_ring = nullptr, ev_read = nullptr;
+    bool ring_rec = false, read_rec = false;
+    hipError_t ensure() {       // lazy create
+        const hipError_t e = ev_ring ? hipSuccess : hipEventCreateWithFlags(&ev_ring, hipEventDisableTiming);
+        return e != hipSuccess || ev_read ? e : hipEventCreateWithFlags(&ev_read, hipEventDisableTiming);
+    }
+    hipError_t before_push(hipStream_t s) {
+        const hipError_t e = read_rec ? hipStreamWaitEvent(s, ev_read, 0) : hipSuccess;
+        return e == hipSuccess && ring_rec ? hipStreamWaitEvent(s, ev_ring, 0) : e;
+    }
+    hipError_t after_push(hipStream_t s) { const hipError_t e = hipEventRecord(ev_ring, s); ring_rec |= e == hipSuccess; return e; }
+    hipError_t before_read(hipStream_t s) { return hipStreamWaitEvent(s, ev_ring, 0); }     // a full ring has been pushed to
+    hipError_t after_read(hipStream_t s) { const hipError_t e = hipEventRecord(ev_read, s); read_rec |= e == hipSuccess; return e; }
+    void destroy() {
+        if (ev_ring) (void)hipEventDestroy(ev_ring);
+        if (ev_read) (void)hipEventDestroy(ev_read);
+        ev_ring = ev_read = nullptr;
+    }
+};

@@ -101,7 +101,27 @@ extern std::atomic<bool> g_head_share;
 extern std::atomic<bool> g_rows3;
 bool skinny_row_prologue_ok(int M, int K, bool fp8);         // shapes the row-prologue form is instantiated for
 hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s);
-bool skinny_full_ok(int K);                                  // K depths launch_skinny is instantiated for
+// The vocabulary head's launch_skinny(SK_BIAS_F32) arguments over the bf16 rows xb [rows * T][D] (host only): every position
+// (all_positions) or the last position of every row.  The partial buffers are nullable.  Returns the row stride and offset at
+// which launch_argmax_final finds the last position of each row among the head's rows.
+struct HeadWeight { const void *W, *Wpk; const float *wscale, *bias; int V, D; };    // row-major, optional fragment-major copy / row scales
+struct HeadRows { int am_stride, am_off; };
+inline HeadRows vocab_head_args(SkinnyArgs& ha, const HeadWeight& hw, const bf16_t* xb, int rows, int T, bool all_positions,
+                                float* logits_out, float* amax_val, int* amax_idx, float* amax_sum) {
+    ha = SkinnyArgs{};
+    ha.W = hw.W; ha.Wpk = hw.Wpk; ha.wscale = hw.wscale; ha.bias = hw.bias; ha.N = hw.V; ha.K = hw.D; ha.ldo = hw.V;
+    ha.T = 1; ha.row_stride = 1; ha.row_off = 0; ha.out = logits_out;
+    ha.amax_val = amax_val; ha.amax_idx = amax_idx; ha.amax_sum = amax_sum;
+    HeadRows r{1, 0};
+    if (all_positions) {
+        ha.X = xb; ha.ldx = hw.D; ha.M = rows * T;
+        r.am_stride = T; r.am_off = T - 1;
+    } else {
+        ha.X = xb + (size_t)(T - 1) * hw.D; ha.ldx = T * hw.D; ha.M = rows;
+    }
+    return r;
+}
+bool skinny_full_ok(int K);                                 // K depths launch_skinny is instantiated for
 int skinny_ksplit(int K);                                    // number of K slabs launch_skinny_splitk writes
 hipError_t launch_skinny_splitk(const SkinnyArgs& a, hipStream_t s);
 // x = LayerNorm(sum_s slab[s][m][:] + bias + resid[m][:]) -> xf (fp32) and xb (bf16); one wave per row

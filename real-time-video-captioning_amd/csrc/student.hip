@@ -187,17 +187,15 @@ struct gitcap_student : HandleCore {
     int* amax_idx = nullptr;
     bf16_t *xb = nullptr, *qc = nullptr, *ctx = nullptr, *ffn = nullptr, *kvs = nullptr, *memb = nullptr, *memkv = nullptr;
     int32_t* sep_cnt = nullptr;
-    // greedy loop captured as a hipGraph (one per (B, max_len, stop, row-prologue switch)); it works on the handle's own
-    // ids / steps buffers, which are copied to the caller's after the replay
+    // the token loops work on the handle's own ids / steps buffers (copy_out: to the caller's); their captured graphs, one entry per
+    // key: stop = a stop rule -> execs[0] the whole greedy loop; TAIL_STEPS -> execs[t - 1] token step t of the draft path, t >= 1
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct GreedyGraph { int B, max_len, stop; bool rows_pro, head_share, lp; hipGraphExec_t exec; };
-    std::vector<GreedyGraph> graphs;
-    // draft verification (gitcap_student_*_greedy_draft): the token steps t = 1 .. max_len - 1 of a (B, max_len, switches) as one
-    // graph each (step[t - 1]; the stop rule is not in a step), captured together at the first draft call with that key; acc_tok /
-    // acc_ticket = draft_accept_kernel's scratch, acc_host = its page-locked {accepted, stop rule fired}, read behind acc_ev
-    struct TailGraphs { int B, max_len; bool rows_pro, head_share, lp; std::vector<hipGraphExec_t> step; };
-    std::vector<TailGraphs> tails;
+    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; std::vector<hipGraphExec_t> execs; };
+    static constexpr int TAIL_STEPS = -1;
+    std::vector<Graphs> graphs;
+    // draft verification (gitcap_student_*_greedy_draft): acc_tok / acc_ticket = draft_accept_kernel's scratch, acc_host = its
+    // page-locked {accepted, stop rule fired}, read behind acc_ev
     int* acc_tok = nullptr;
     unsigned* acc_ticket = nullptr;
     int32_t* acc_host = nullptr;
@@ -218,13 +216,13 @@ struct gitcap_student : HandleCore {
         bf16_t* kvs2 = nullptr; char* topk_scratch = nullptr;
     } bw;
     // memory-token window (gitcap_student_window_*), allocated by window_reset: ring = the cross-attention K|V rows of the last F
-    // tokens of win_B clips, bf16 [L][win_B][F slots][2D]; win_head = the slot the next token goes to (the oldest token once the
-    // ring is full); win_count = tokens per clip pushed since the reset, capped at F.  A push orders itself behind the last window
-    // call's gather (win_ev_read) and the last push (win_ev_ring: they share the staging rows); a window call behind the last push.
+    // tokens of win_B clips, bf16 [L][win_B][F slots][2D]; win (RingCursor) = where the next token goes and how many have been
+    // pushed per clip; win_order (RingOrder) = a push behind the last window call's gather and the last push, a window call behind
+    // the last push.
     bf16_t *win_ring = nullptr, *win_stage = nullptr;
-    int win_B = 0, win_head = 0, win_count = 0;
-    hipEvent_t win_ev_ring = nullptr, win_ev_read = nullptr;
-    bool win_ring_rec = false, win_read_rec = false;
+    int win_B = 0;
+    RingCursor win;
+    RingOrder win_order;
     // resolved weights
     const float *embed = nullptr, *pe = nullptr, *head_b = nullptr;
     const bf16_t* head_w = nullptr;
@@ -235,11 +233,9 @@ namespace {
 
 // the captured token loops and token steps: weight pointers are baked into their nodes
 void destroy_graphs(gitcap_student* h) {
-    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+    for (auto& g : h->graphs)
+        for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
     h->graphs.clear();
-    for (auto& t : h->tails)
-        for (hipGraphExec_t e : t.step) (void)hipGraphExecDestroy(e);
-    h->tails.clear();
 }
 
 bool student_is_gemm_weight(const std::string& n) {
@@ -266,6 +262,8 @@ void expected_shapes(const gitcap_student_config& c, std::vector<std::pair<std::
     add("linear.weight", {V, D});
     add("linear.bias", {V});
 }
+
+HeadWeight head_weight(const gitcap_student* h) { return HeadWeight{h->head_w, nullptr, nullptr, h->head_b, h->V, h->D}; }
 
 int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx, const bf16_t* W, const float* bias, int M,
             int N, int K, void* out, int ldo, int T = 1, int row_stride = 1, int row_off = 0) {
@@ -339,22 +337,13 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
     }
     if (!logits_out && !argmax_out) return 0;
     // vocabulary head: all positions when logits are requested, else the last position of every row
-    const int V = h->V, ntiles = (V + 15) / 16;
-    SkinnyArgs ha{};
-    ha.W = h->head_w; ha.bias = h->head_b; ha.N = V; ha.K = D; ha.ldo = V; ha.T = 1; ha.row_stride = 1; ha.row_off = 0;
-    int am_stride = 1, am_off = 0;
-    if (logits_out) {
-        ha.X = h->xb; ha.ldx = D; ha.M = M; ha.out = logits_out;
-        am_stride = T; am_off = T - 1;
-    } else {
-        ha.X = h->xb + (size_t)(T - 1) * D; ha.ldx = T * D; ha.M = rows;
-    }
-    if (argmax_out) { ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx; }
     if (lp_out && (!argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
-    if (lp_out) ha.amax_sum = h->amax_sum;
+    SkinnyArgs ha;
+    const HeadRows hr = vocab_head_args(ha, head_weight(h), h->xb, rows, T, logits_out != nullptr, logits_out, argmax_out ? h->amax_val : nullptr,
+                                        argmax_out ? h->amax_idx : nullptr, lp_out ? h->amax_sum : nullptr);
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     if (argmax_out)
-        HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, ntiles, rows, am_stride, am_off, argmax_out, ld_argmax,
+        HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, (h->V + 15) / 16, rows, hr.am_stride, hr.am_off, argmax_out, ld_argmax,
                                         sep_cnt, step, c.sep_token_id, s, nullptr, lp_out ? h->amax_sum : nullptr, lp_out, ld_lp));
     return 0;
 }
@@ -427,8 +416,7 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
-    if (h->win_ev_ring) (void)hipEventDestroy(h->win_ev_ring);
-    if (h->win_ev_read) (void)hipEventDestroy(h->win_ev_read);
+    h->win_order.destroy();
     delete h;
 }
 
@@ -514,76 +502,90 @@ int gitcap_student_forward_decoder(gitcap_student_t* h, const int64_t* ids, int 
 
 namespace {
 
-// argument checks shared by gitcap_student_greedy and gitcap_student_window_greedy
-int greedy_check(gitcap_student* h, const char* who, int max_len, int stop, const int64_t* ids_out) {
-    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
-    if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len");
-    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": unknown stop rule");
+// The token loops are launch-latency bound (26 kernels per token): they are captured and replayed.  GITCAP_STUDENT_GRAPH=0
+// launches them kernel by kernel (same kernels, same results).
+const bool g_use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
+
+// Token step t of the greedy loop (model.py:173-182) on the handle's id rows: position t in, the arg-max as token t + 1 (and, with
+// want_lp, its log-probability as column t of g_lp).  The full loop, the captured tail steps and the un-graphed tail are this call.
+int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q) {
+    const int ld = max_len + 1;
+    return text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q, want_lp ? h->g_lp + t : nullptr, max_len);
+}
+
+// What enqueue(cap_stream) launches -> one executable graph (replayed on the caller's stream).  A failed enqueue still ends the
+// capture and its own status is returned; whatever fails, the hipGraph_t is destroyed and *exec stays null.
+template <typename Enqueue>
+int capture(gitcap_student* h, const char* what, Enqueue enqueue, hipGraphExec_t* exec) {
+    *exec = nullptr;
+    if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    int rc = 0;
+    hipError_t e = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        rc = enqueue(h->cap_stream);
+        e = hipStreamEndCapture(h->cap_stream, &graph);
+    }
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!rc && e != hipSuccess) rc = fail(h, GITCAP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return rc;
+}
+
+// The executables of a key, captured by fill(execs) at the key's first use; a failed fill caches nothing.  Weight and workspace
+// pointers are baked into the nodes (destroy_graphs at every finalize).
+template <typename Fill>
+int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, Fill fill, const std::vector<hipGraphExec_t>** out) {
+    for (auto& g : h->graphs)
+        if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp) {
+            *out = &g.execs;
+            return 0;
+        }
+    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, {}};
+    if (int rc = fill(g.execs)) {
+        for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
+        return rc;
+    }
+    h->graphs.push_back(std::move(g));
+    *out = &h->graphs.back().execs;
     return 0;
 }
 
-// the pending attachment of gitcap_student_attach_token_logprobs: taken (and with that consumed) by every greedy-family entry point
-struct LpAttach { float* p; int ld; };
-LpAttach take_lp(gitcap_student* h) {
-    const LpAttach a{h->lp_attach, h->lp_ld};
-    h->lp_attach = nullptr; h->lp_ld = 0;
-    return a;
-}
-int lp_check(gitcap_student* h, const char* who, const LpAttach& lp, int max_len) {
-    if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached token log-probability buffer has ld < max_len");
+// the handle's ids [B][max_len + 1], steps and (lp.p set) log-probabilities [B][max_len] -> the caller's buffers; the columns of
+// lp.p behind max_len (row pitch lp.ld) are not touched
+int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* steps_out, const LpAttach& lp, hipStream_t s) {
+    HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * (max_len + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (lp.p)
+        HIP_OK(h, hipMemcpy2DAsync(lp.p, (size_t)lp.ld * 4, h->g_lp, (size_t)max_len * 4, (size_t)max_len * 4, (size_t)B, hipMemcpyDeviceToDevice, s));
     return 0;
-}
-// g_lp [B][max_len] -> the caller's rows (pitch lp.ld): columns behind max_len are not touched
-hipError_t lp_copy_out(gitcap_student* h, const LpAttach& lp, int B, int max_len, hipStream_t s) {
-    return hipMemcpy2DAsync(lp.p, (size_t)lp.ld * 4, h->g_lp, (size_t)max_len * 4, (size_t)max_len * 4, (size_t)B, hipMemcpyDeviceToDevice, s);
 }
 
 // the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
 // lp.p set: the loop with token log-probabilities (a graph of its own; column t of g_lp = step t's)
-int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
-                LpAttach lp = LpAttach{nullptr, 0}) {
+int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s, const LpAttach& lp) {
     const bool want_lp = lp.p != nullptr;
     int rc;
-    const int ld = max_len + 1;
-    // The token loop is launch-latency bound (26 kernels per token): it is captured once per (B, max_len, stop)
-    // and replayed.  GITCAP_STUDENT_GRAPH=0 launches it kernel by kernel (same kernels, same results).
-    static const bool use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
     auto enqueue_loop = [&](hipStream_t q) -> int {
-        HIP_OK(h, launch_fill_i64(h->g_ids, ld, B, h->c.cls_token_id, q));                 // model.py:171
+        HIP_OK(h, launch_fill_i64(h->g_ids, max_len + 1, B, h->c.cls_token_id, q));        // model.py:171
         HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
-        for (int t = 0; t < max_len; ++t) {                                                  // model.py:173-182
-            int r = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q,
-                                 want_lp ? h->g_lp + t : nullptr, max_len);
-            if (r) return r;
-        }
+        for (int t = 0; t < max_len; ++t)                                                    // model.py:173-182
+            if (int r = token_step(h, B, t, max_len, want_lp, q)) return r;
         HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
         return 0;
     };
-    if (use_graph) {
-        hipGraphExec_t exec = nullptr;
-        for (auto& g : h->graphs)
-            if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp) exec = g.exec;
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-            HIP_OK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_loop(h->cap_stream);
-            hipError_t e = hipStreamEndCapture(h->cap_stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            HIP_OK(h, e);
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_OK(h, e);
-            h->graphs.push_back({B, max_len, stop, g_row_prologue, g_head_share, want_lp, exec});
-        }
-        HIP_OK(h, hipGraphLaunch(exec, s));
+    if (g_use_graph) {
+        const std::vector<hipGraphExec_t>* loop = nullptr;
+        rc = captured_graphs(h, B, max_len, stop, want_lp, [&](std::vector<hipGraphExec_t>& execs) {
+            execs.push_back(nullptr);
+            return capture(h, "student greedy: capturing the token loop", enqueue_loop, &execs.back());
+        }, &loop);
+        if (rc) return rc;
+        HIP_OK(h, hipGraphLaunch((*loop)[0], s));
     } else if ((rc = enqueue_loop(s))) {
         return rc;
     }
-    HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (want_lp) HIP_OK(h, lp_copy_out(h, lp, B, max_len, s));
-    return 0;
+    return copy_out(h, B, max_len, ids_out, steps_out, lp, s);
 }
 
 // ---- greedy decoding that verifies a draft caption ------------------------------------------------------------------------
@@ -592,59 +594,31 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
 // CLS, d_1, .., d_j are the head's arg-max at position j of ONE pass over the draft (T = n, the launches of one token step), and
 // every leading draft token that equals it is a token the loop would have produced: accepted, together with the K/V rows the pass
 // wrote for its position.  The first position that differs holds the loop's own token (the corrected one).  The steps behind it
-// are the loop's own launches, text_forward(t, 1).
-int draft_tail_graphs(gitcap_student* h, int B, int max_len, bool want_lp, std::vector<hipGraphExec_t>** out) {
-    for (auto& t : h->tails)
-        if (t.B == B && t.max_len == max_len && t.rows_pro == g_row_prologue && t.head_share == g_head_share && t.lp == want_lp) { *out = &t.step; return 0; }
-    const int ld = max_len + 1;
-    gitcap_student::TailGraphs tg{B, max_len, g_row_prologue, g_head_share, want_lp, {}};
-    if (!h->cap_stream) HIP_OK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-    int rc = 0;
-    for (int t = 1; t < max_len && !rc; ++t) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, h->cap_stream,
-                              want_lp ? h->g_lp + t : nullptr, max_len);
-            e = hipStreamEndCapture(h->cap_stream, &graph);
-        }
-        if (!rc && e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (!rc && e != hipSuccess) rc = fail(h, GITCAP_ERR_HIP, std::string("student draft: capturing a token step: ") + hipGetErrorString(e));
-        if (!rc) tg.step.push_back(exec);
-    }
-    if (rc) {
-        for (hipGraphExec_t e : tg.step) (void)hipGraphExecDestroy(e);
-        return rc;
-    }
-    h->tails.push_back(std::move(tg));
-    *out = &h->tails.back().step;
-    return 0;
-}
-
-// argument checks of the two draft calls (behind greedy_check)
-int draft_check(gitcap_student* h, const char* who, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len) {
-    if (!draft_ids) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": null draft_ids");
-    if (n_draft < 1 || n_draft > max_len || ld_draft < n_draft + 1)
-        return fail(h, GITCAP_ERR_ARG, std::string(who) + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
-    return 0;
-}
+// are the loop's own launches, token_step(t).
 
 // verify -> accept -> tail against the memory K|V in h->memkv; same results as greedy_loop(B, max_len, stop)
 int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_draft, int n, int max_len, int stop, int64_t* ids_out,
-                      int32_t* steps_out, int32_t* accepted_out, hipStream_t s, LpAttach lp = LpAttach{nullptr, 0}) {
+                      int32_t* steps_out, int32_t* accepted_out, hipStream_t s, const LpAttach& lp) {
     int rc;
     const int ld = max_len + 1;
     const bool want_lp = lp.p != nullptr;
-    static const bool use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
     if (!h->acc_host) {
         HIP_OK(h, hipHostMalloc((void**)&h->acc_host, 16, hipHostMallocMapped));
         HIP_OK(h, hipEventCreateWithFlags(&h->acc_ev, hipEventDisableTiming));
     }
     // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
-    std::vector<hipGraphExec_t>* steps = nullptr;
-    if (use_graph && (rc = draft_tail_graphs(h, B, max_len, want_lp, &steps))) return rc;
+    const std::vector<hipGraphExec_t>* steps = nullptr;
+    if (g_use_graph) {
+        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, [&](std::vector<hipGraphExec_t>& execs) {
+            for (int t = 1; t < max_len; ++t) {
+                execs.push_back(nullptr);
+                if (int r = capture(h, "student draft: capturing a token step", [&](hipStream_t q) { return token_step(h, B, t, max_len, want_lp, q); },
+                                    &execs.back())) { execs.pop_back(); return r; }
+            }
+            return 0;
+        }, &steps);
+        if (rc) return rc;
+    }
     // 1. verify: one pass over positions 0 .. n-1 of the staged draft (K/V rows of those positions -> the cache), then the
     //    vocabulary head over all B * n rows, arg-max partials only
     hipLaunchKernelGGL(student_draft_stage_kernel, dim3((B * (n + 1) + 255) / 256), dim3(256), 0, s, draft, ld_draft, n, B, h->V,
@@ -653,10 +627,8 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
     if ((rc = text_forward(h, h->g_ids, ld, B, 0, n, nullptr, nullptr, 0, nullptr, 0, s))) return rc;
     const int ntiles = (h->V + 15) / 16;
-    SkinnyArgs ha{};
-    ha.X = h->xb; ha.ldx = h->D; ha.W = h->head_w; ha.bias = h->head_b; ha.M = B * n; ha.N = h->V; ha.K = h->D; ha.ldo = h->V;
-    ha.T = 1; ha.row_stride = 1; ha.amax_val = h->amax_val; ha.amax_idx = h->amax_idx;
-    if (want_lp) ha.amax_sum = h->amax_sum;     // covered positions: their log-probabilities come from this pass (the same bits as the loop's)
+    SkinnyArgs ha;      // want_lp: the covered positions' log-probabilities come from this pass (the same bits as the loop's)
+    vocab_head_args(ha, head_weight(h), h->xb, B, n, true, nullptr, h->amax_val, h->amax_idx, want_lp ? h->amax_sum : nullptr);
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     // 2. accept
     *(volatile int32_t*)h->acc_host = -1;
@@ -672,14 +644,11 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     const int t0 = a < n ? a + 1 : n;
     const bool tail = t0 < max_len && !(stop == GITCAP_STOP_ALL_SEP && fired);
     for (int t = t0; tail && t < max_len; ++t) {
-        if (use_graph) HIP_OK(h, hipGraphLaunch((*steps)[t - 1], s));
-        else if ((rc = text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, s,
-                                    want_lp ? h->g_lp + t : nullptr, max_len))) return rc;
+        if (g_use_graph) HIP_OK(h, hipGraphLaunch((*steps)[t - 1], s));
+        else if ((rc = token_step(h, B, t, max_len, want_lp, s))) return rc;
     }
     HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, s));
-    HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * ld * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (want_lp) HIP_OK(h, lp_copy_out(h, lp, B, max_len, s));
+    if ((rc = copy_out(h, B, max_len, ids_out, steps_out, lp, s))) return rc;
     if (accepted_out) *accepted_out = a;
     ++h->draft_calls; h->draft_offered += n; h->draft_accepted += a; h->draft_tail_steps += tail ? max_len - t0 : 0;
     return 0;
@@ -752,19 +721,43 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
 // GEMM whose output rows do not depend on each other: everything per frame is computed once, at the push, and a caption of the
 // window only orders the F rows (student_window_gather_kernel) in front of the token loop of the full call.
 int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s) {
-    if (!h->win_ring || h->win_count < h->F)
+    if (!h->win_ring || !h->win.full())
         return fail(h, GITCAP_ERR_STATE, std::string(who) + ": fewer than mem_tokens tokens pushed since the reset");
     const int rows = h->win_B * k, D = h->D;
-    HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
+    HIP_OK(h, h->win_order.before_read(s));
     h->have_memory = false;
-    hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * h->F, h->L), dim3(64), 0, s, h->win_ring, h->memkv, h->F, h->win_head, k,
+    hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * h->F, h->L), dim3(64), 0, s, h->win_ring, h->memkv, h->F, h->win.head, k,
                        2 * D / 8, (size_t)h->win_B * h->F * 2 * D, (size_t)h->R * h->F * 2 * D);
     HIP_OK(h, hipGetLastError());
-    HIP_OK(h, hipEventRecord(h->win_ev_read, s));
-    h->win_read_rec = true;
+    HIP_OK(h, h->win_order.after_read(s));
     h->cur_B = rows;
     h->have_memory = true;
     return 0;
+}
+
+// The four greedy entry points.  who = the entry point's name in every message; window: the memory K|V come from the ring (win_B
+// clips) instead of the caller's `memory` (set_memory reads the caller's buffer: outside the graphs); draft set: the loop verifies
+// it.  The pending log-probability attachment is taken before the checks: a refused call has consumed it.
+struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
+int greedy_entry(gitcap_student* h, const char* who, bool window, const float* memory, int B, const Draft* draft, int max_len, int stop,
+                 int64_t* ids_out, int32_t* steps_out, void* stream) {
+    const std::string w(who);
+    if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
+    const LpAttach lp = take_lp(h);
+    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
+    if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
+    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
+    if (int bad = lp_check(h, who, lp, max_len)) return bad;
+    if (draft && !draft->ids) return fail(h, GITCAP_ERR_ARG, w + ": null draft_ids");
+    if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
+        return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
+    if (window && !h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = window ? window_memory(h, who, 1, s) : set_memory(h, memory, B, s)) return rc;
+    if (window) B = h->win_B;
+    if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
 }
 
 }  // namespace
@@ -773,15 +766,7 @@ extern "C" {
 
 int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
                           int32_t* steps_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy: null handle");
-    const LpAttach lp = take_lp(h);
-    if (int bad = greedy_check(h, "student_greedy", max_len, stop, ids_out)) return bad;
-    if (int bad = lp_check(h, "student_greedy", lp, max_len)) return bad;
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = set_memory(h, memory, B, s);           // reads the caller's buffer: outside the graph
-    if (rc) return rc;
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+    return greedy_entry(h, "student_greedy", false, memory, B, nullptr, max_len, stop, ids_out, steps_out, stream);
 }
 
 // StudentCandidateV1.beam_search (model.py:189-318) on the device with the exact KV cache: k beams per clip as rows
@@ -815,12 +800,10 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B) {
         (void)hipFree(h->win_ring); (void)hipFree(h->win_stage);
         h->win_ring = h->win_stage = nullptr;
     }
-    h->win_B = h->win_head = h->win_count = 0;
+    h->win_B = 0;
+    h->win.reset(h->F);
     if (B == 0) return 0;
-    if (!h->win_ev_ring) {
-        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_ring, hipEventDisableTiming));
-        HIP_OK(h, hipEventCreateWithFlags(&h->win_ev_read, hipEventDisableTiming));
-    }
+    HIP_OK(h, h->win_order.ensure());
     if (!h->win_ring) {
         const size_t rows = (size_t)B * h->F;
         hipError_t e = hipMalloc((void**)&h->win_ring, (size_t)h->L * rows * 2 * h->D * sizeof(bf16_t));
@@ -845,9 +828,8 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
     if (B != h->win_B || n < 1 || n > h->F) return fail(h, GITCAP_ERR_ARG, "student_window_push: B differs from the reset's, or n outside [1, mem_tokens]");
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->win_read_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_read, 0));
-    if (h->win_ring_rec) HIP_OK(h, hipStreamWaitEvent(s, h->win_ev_ring, 0));
-    const int D = h->D, F = h->F, n1 = std::min(n, F - h->win_head), n2 = n - n1;
+    HIP_OK(h, h->win_order.before_push(s));
+    const int D = h->D, F = h->F, n1 = h->win.first_run(n), n2 = n - n1;
     const int64_t total = (int64_t)B * n * (D / 4);
     hipLaunchKernelGGL(student_window_stage_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1024)), dim3(256), 0, s, memory,
                        h->win_stage, B, n, n1, D / 4);
@@ -859,59 +841,31 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
         // of every clip and, wrapped, 0 .. n2 - 1
         bf16_t* ring = h->win_ring + (size_t)l * ring_layer;
         int rc = sk_full(h, s, SK_BIAS_BF16, h->win_stage, D, Ly.ca_in_w + (size_t)D * D, Ly.ca_in_b + D, B * n1, 2 * D, D, ring, 2 * D,
-                         n1, F, h->win_head);
+                         n1, F, h->win.head);
         if (!rc && n2)
             rc = sk_full(h, s, SK_BIAS_BF16, h->win_stage + (size_t)B * n1 * D, D, Ly.ca_in_w + (size_t)D * D, Ly.ca_in_b + D, B * n2, 2 * D, D,
                          ring, 2 * D, n2, F, 0);
-        if (rc) { h->win_count = 0; return rc; }      // some slots may be half written: the window is emptied
+        if (rc) { h->win.clear(); return rc; }        // some slots may be half written: the window is emptied
     }
-    HIP_OK(h, hipEventRecord(h->win_ev_ring, s));
-    h->win_ring_rec = true;
-    h->win_head = (h->win_head + n) % F;
-    h->win_count = std::min(h->win_count + n, F);
+    HIP_OK(h, h->win_order.after_push(s));
+    h->win.push(n);
     return 0;
 }
 
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy: null handle");
-    const LpAttach lp = take_lp(h);
-    if (int bad = greedy_check(h, "student_window_greedy", max_len, stop, ids_out)) return bad;
-    if (int bad = lp_check(h, "student_window_greedy", lp, max_len)) return bad;
-    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy: weights not finalized");
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = window_memory(h, "student_window_greedy", 1, s);
-    if (rc) return rc;
-    return greedy_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
+    return greedy_entry(h, "student_window_greedy", true, nullptr, 0, nullptr, max_len, stop, ids_out, steps_out, stream);
 }
 
 int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
                                 int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_greedy_draft: null handle");
-    const LpAttach lp = take_lp(h);
-    if (int bad = greedy_check(h, "student_greedy_draft", max_len, stop, ids_out)) return bad;
-    if (int bad = lp_check(h, "student_greedy_draft", lp, max_len)) return bad;
-    if (int bad = draft_check(h, "student_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = set_memory(h, memory, B, s);
-    if (rc) return rc;
-    return greedy_draft_core(h, B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s, lp);
+    const Draft d{draft_ids, ld_draft, n_draft, accepted_out};
+    return greedy_entry(h, "student_greedy_draft", false, memory, B, &d, max_len, stop, ids_out, steps_out, stream);
 }
 
 int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
                                        int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_greedy_draft: null handle");
-    const LpAttach lp = take_lp(h);
-    if (int bad = greedy_check(h, "student_window_greedy_draft", max_len, stop, ids_out)) return bad;
-    if (int bad = lp_check(h, "student_window_greedy_draft", lp, max_len)) return bad;
-    if (int bad = draft_check(h, "student_window_greedy_draft", draft_ids, ld_draft, n_draft, max_len)) return bad;
-    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_greedy_draft: weights not finalized");
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = window_memory(h, "student_window_greedy_draft", 1, s);
-    if (rc) return rc;
-    return greedy_draft_core(h, h->win_B, draft_ids, ld_draft, n_draft, max_len, stop, ids_out, steps_out, accepted_out, s, lp);
+    const Draft d{draft_ids, ld_draft, n_draft, accepted_out};
+    return greedy_entry(h, "student_window_greedy_draft", true, nullptr, 0, &d, max_len, stop, ids_out, steps_out, stream);
 }
 
 int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld) {
