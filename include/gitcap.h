@@ -202,7 +202,8 @@ int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int 
 
 /* Replaces: GenerativeImageTextModel.infer + GeneratorWithBeamSearchV2.search
  *                                                         src/models/model.py:426-462, :479-678
- * (num_keep_best = 1, do_sample = False: the way GenerativeImageTextTeacher.forward drives it, :768).
+ * (do_sample = False; num_keep_best = 1 and no repetition penalty, the way GenerativeImageTextTeacher.forward drives it, :768,
+ * unless gitcap_attach_search_options says otherwise for this call).
  * The whole search runs on the device with no host round trip: per step decoder forward, beam top-k
  * (log-softmax + beam scores, :557-565), hypothesis/beam bookkeeping (:573-621) and the KV reorder the
  * reference leaves commented out (:623-634).  decoded_out: device int64 [B][max_steps], CLS-prefixed best
@@ -307,6 +308,49 @@ int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float lengt
  * set-up step: it may synchronise; gitcap_workspace_bytes counts it from then on).  A handle that never attaches allocates
  * nothing and runs exactly the launches it ran before. */
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld);
+
+/* Options of the device-resident search: the reference's search operator keeps `num_keep_best` finished hypotheses per clip and
+ * applies a `repetition_penalty` (GeneratorWithBeamSearchV2.search, src/models/model.py:479-678; the penalty :522-531, the n-best
+ * output :653-678).  A ONE-SHOT attachment, like gitcap_attach_token_logprobs: it applies to the NEXT beam-family call or
+ * submission on the handle -- gitcap_beam_search, gitcap_beam_search_submit, gitcap_beam_search_raw_submit,
+ * gitcap_window_beam_search -- and is consumed by it, whether that call succeeds or fails; every other entry point (encode,
+ * text_forward, the greedy family, pushes, waits) leaves a pending attachment alone; opt == NULL detaches.  A pipelined submission
+ * captures the two pointers: the buffers stay valid until the wait, like decoded_out.
+ *   repetition_penalty  before the candidates of a step are ranked, every logit whose column occurs in the row's prefix (CLS
+ *                       included) becomes x < 0 ? x * rp : x / rp -- once however often the token occurs, -inf stays -inf, plain fp32
+ *                       IEEE multiply / divide -- and the log-softmax is taken over the penalised row.  step_logits_out stays raw
+ *                       (model.py:521 saves before :522).  1.0: no penalty, the ranking launches are those without options.
+ *   num_keep_best = n   BeamHypotheses with n slots: while fewer than n hypotheses are stored a finished one is stored; afterwards it
+ *                       replaces the stored minimum (the earliest stored among equal minima) only if its score is strictly greater;
+ *                       a clip is done once n are stored and the minimum >= best candidate sum / (max_steps - 1)^length_penalty.
+ *   nbest_out           device int64 [B][n][max_steps]: the stored hypotheses by descending score (equal scores in storage order),
+ *                       CLS first, EOS padded; a rank with no hypothesis is all-EOS.
+ *   nbest_logprobs_out  device fp32 [B][n]: their scores; -1e5 for a rank with no hypothesis (model.py:654).
+ * The call's own decoded_out / logprobs_out receive rank 0 of the n-best under the attached options.  With n > 1 the done rule
+ * waits for n hypotheses and compares against the WORST of them, so a clip searches on where n = 1 would have stopped: rank 0 need
+ * not equal the result of the same call without options.  With n = 1 both pointers may be NULL; if given they receive a copy.
+ * Errors: GITCAP_ERR_ARG for num_keep_best outside [1, 16], a penalty that is not finite and > 0, a missing pointer with n > 1, a
+ * pointer that is not aligned to its element; at the consuming call n > beams * per_node_beam_size gives GITCAP_ERR_ARG with
+ * nothing launched (the attachment is consumed all the same).
+ * Memory: the first attach with n > 1 allocates the n-best state, once per pipeline slot, sized for max_batch clips x 16
+ * hypotheses x (max_text_len + 1) ids (a set-up step: it may synchronise; gitcap_workspace_bytes counts it from then on).  A handle
+ * that never attaches allocates nothing and runs exactly the launches it ran before. */
+typedef struct gitcap_search_options {
+    int32_t num_keep_best;       /* 1..16; at the consuming call also <= beams * per_node_beam_size */
+    float   repetition_penalty;  /* finite, > 0; 1.0 = none */
+    int64_t* nbest_out;          /* device int64 [B][num_keep_best][max_steps]; required when num_keep_best > 1, else nullable */
+    float*   nbest_logprobs_out; /* device fp32 [B][num_keep_best]; same rule */
+} gitcap_search_options;
+int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt);
+
+/* gitcap_beam_topk under a repetition penalty: prefix_ids device int64 [B*beams][ld_ids], the first cur_len columns of row r are
+ * the tokens whose logits in row r are penalised (ids outside [0, V) are ignored; see gitcap_search_options for the rule).  Same
+ * limits, outputs and refusals as gitcap_beam_topk; also GITCAP_ERR_ARG for a penalty that is not finite and > 0 and, unless the
+ * penalty is 1.0 (then the call IS gitcap_beam_topk and prefix_ids is not read), for a null or misaligned prefix_ids, cur_len < 1
+ * or ld_ids < cur_len.  Stateless (no handle). */
+int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids,
+                               int cur_len, float repetition_penalty, int B, int beams, int V, int K,
+                               float* out_scores, int32_t* out_idx, void* stream);
 
 /* Host-side staging copy for host-fed callers (no reference counterpart): bytes from pageable memory (a DataLoader batch without
  * pin_memory, OpenCV frames) into a page-locked staging buffer, split over up to 8 threads -- as many as the process may really use
@@ -453,6 +497,22 @@ int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* bb, const float* cand_sc
                          int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
 int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* bb, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
                            void* stream);
+
+/* The same bookkeeping with n hypotheses per clip (gitcap_search_options: num_keep_best; 1 <= n <= 16): hyp_ids int64
+ * [B][n][max_len], hyp_score fp32 [B][n], hyp_len int32 [B][n]; the stored hypotheses of a clip sit in storage order in slots
+ * 0 .. count - 1, hyp_len = 0 marks an empty slot (gitcap_dbg_beam_init on the first nine fields zeroes hyp_len[0 .. B) only: zero
+ * all B * n before step 1).  beam_finish_nbest: decoded int64 [B][n][max_len], logprobs fp32 [B][n], by descending score.  With
+ * n = 1 the two hooks write what gitcap_dbg_beam_step / _finish write, bit for bit. */
+typedef struct gitcap_dbg_beam_buffers_nbest {
+    int64_t *ids0, *ids1, *words, *hyp_ids;
+    float *beam_scores, *hyp_score;
+    int32_t *src_rows, *done, *hyp_len;
+    int32_t n;
+} gitcap_dbg_beam_buffers_nbest;
+int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* bb, const float* cand_scores, const int32_t* cand_idx, int B,
+                               int beams, int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
+int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* bb, int B, int max_len, int eos, int64_t* decoded,
+                                 float* logprobs, void* stream);
 
 /* The text-row kernels of the token loop, one launcher per hook on caller-owned device buffers (tests/test_text_rows_gpu.py; a
  * plain fp64 statement of each: tests/text_rows_reference.py).  No allocation, no handle; GITCAP_ERR_ARG for arguments a launcher

@@ -66,6 +66,9 @@ struct DecLayer {
 
 }  // namespace
 
+// Options of one device-resident search (gitcap_attach_search_options): hypotheses kept per clip, repetition penalty, n-best outputs.
+struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; };
+
 struct gitcap : HandleCore {
     gitcap_config c;
     std::map<std::string, DevTensor> w;
@@ -136,6 +139,9 @@ struct gitcap : HandleCore {
         float* cand_scores = nullptr;       // [B][16]
         int* cand_idx = nullptr;
         char* topk_scratch = nullptr;       // beam_topk chunk statistics + per-chunk candidates (sized for max_batch x max_beams rows)
+        // n-best hypotheses of the search (num_keep_best > 1): [max_batch][16][Tmax + 1] ids, [max_batch][16] scores and lengths;
+        // allocated by the first gitcap_attach_search_options that asks for more than one
+        int64_t* nb_ids = nullptr; float* nb_score = nullptr; int32_t* nb_len = nullptr;
         int B = 0, S = 0;                   // clips and image rows per clip of the image prefix the slot holds (have: it holds one)
         bool have = false, used = false;
         int Mt = 0;             // text rows (rows x positions) the slot's row workspace holds
@@ -153,6 +159,8 @@ struct gitcap : HandleCore {
     // gitcap_attach_token_logprobs: the pending one-shot attachment (device fp32 [B][lp_ld]); taken by the next greedy-family call
     float* lp_attach = nullptr;
     int lp_ld = 0;
+    // gitcap_attach_search_options: the pending one-shot attachment; taken by the next beam-family call (n = 1, rp = 1: none)
+    SearchOpt so_attach{};
 
     // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
     // last win.slots frames of win_B clips, clip-major [B][F][N][Dv]; win (RingCursor) = where the next frame goes and how many
@@ -1241,12 +1249,19 @@ int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
 
 // The search loop over the image K/V of the selected slot (its beam state, text K/V and row workspace), on stream s.
 // step_logits_out (nullable): [max_steps - 1][B * beams][V], the raw logits of every step (what model.py:521 saves).
+// so: the call's search options.  rp != 1: the candidates are ranked on the logits penalised at the columns of every row's prefix
+// (the saved step logits stay raw, model.py:521 comes before :522); n > 1: the n-best bookkeeping over the slot's nb_* state,
+// decoded_out / logprobs_out receive rank 0.  The defaults issue exactly the launches of a search without options.
 static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_penalty, int per_node_beam_size,
-                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, hipStream_t s) {
+                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, const SearchOpt& so, hipStream_t s) {
     const int rows = B * beams, K = beams * per_node_beam_size, V = h->c.vocab_size, L = max_steps;
     gitcap::Slot& sl = cur(h);
     int rc;
-    HIP_OK(h, launch_beam_init(sl.beam, B, beams, L, h->c.cls_token_id, s));
+    const bool nbest = so.n > 1;
+    BeamBuffers bb = sl.beam;
+    if (nbest) { bb.hyp_ids = sl.nb_ids; bb.hyp_score = sl.nb_score; bb.hyp_len = sl.nb_len; }
+    HIP_OK(h, launch_beam_init(bb, B, beams, L, h->c.cls_token_id, s));
+    if (nbest) HIP_OK(h, hipMemsetAsync(sl.nb_len, 0, (size_t)B * so.n * sizeof(int32_t), s));
     // while cur_len < max_length (model.py:518): the token at position cur_len-1 is decoded, candidates for
     // position cur_len are ranked, bookkept and the text K/V rows follow their beams -- no host round trip
     for (int cur_len = 1, cur = 0; cur_len < L; ++cur_len, cur ^= 1) {
@@ -1259,11 +1274,25 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : sl.beam_logits;
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
-        HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, B, beams, V, K, sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
-        HIP_OK(h, launch_beam_step(sl.beam, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
-                                   length_penalty, cur, s));
+        if (so.rp != 1.0f)
+            HIP_OK(h, launch_beam_topk_penalized(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
+                                                 sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+        else
+            HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, B, beams, V, K, sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+        if (nbest)
+            HIP_OK(h, launch_beam_step_nbest(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
+                                             length_penalty, cur, s));
+        else
+            HIP_OK(h, launch_beam_step(sl.beam, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
+                                       length_penalty, cur, s));
+    }
+    if (nbest) {
+        HIP_OK(h, launch_beam_finish_nbest(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
+        return 0;
     }
     HIP_OK(h, launch_beam_finish(sl.beam, B, L, h->c.sep_token_id, decoded_out, logprobs_out, s));
+    if (so.nbest) HIP_OK(h, hipMemcpyAsync(so.nbest, decoded_out, (size_t)B * L * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (so.nbest_lp) HIP_OK(h, hipMemcpyAsync(so.nbest_lp, logprobs_out, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -1271,11 +1300,14 @@ int gitcap_beam_search_wait(gitcap_t* h, int ticket, void* stream) { return gitc
 
 }  // extern "C"
 
-// The head of every beam-search entry point (as greedy_entry, without an attachment); then `body()`.
+// The head of every beam-search entry point (as greedy_entry): the pending search options are taken (a call refused below has
+// consumed them); then `body(so)`.
 template <typename Body>
 static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, int max_steps, int per_node_beam_size,
                       const int64_t* decoded_out, const float* logprobs_out, Body body) {
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
+    const SearchOpt so = h->so_attach;
+    h->so_attach = SearchOpt{};
     GUARD(h);
     POLL(h);
     if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
@@ -1285,17 +1317,19 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
     // with fewer than 2 candidates per beam one EOS candidate leaves a sentence short of `beams` live beams, which the
     // reference asserts against (model.py:606); the device bookkeeping has no way to report it, so refuse up front
     if (per_node_beam_size < 2) return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size must be >= 2 (model.py:606)");
-    return body();
+    if (so.n > beams * per_node_beam_size)
+        return fail(h, GITCAP_ERR_ARG, "beam_search: the attached num_keep_best exceeds beams * per_node_beam_size");
+    return body(so);
 }
 
 extern "C" {
 
 int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams, int max_steps, float length_penalty,
                        int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s)) return rc;
-        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, s);
     });
 }
 
@@ -1303,10 +1337,10 @@ int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams
 static int beam_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, float* visual_out, int beams, int max_steps,
                        float length_penalty, int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, float* step_logits_out,
                        hipStream_t stream, int* ticket) {
-    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
         if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
         return submit_common(h, src, B, F, visual_out, stream, ticket, [&](hipStream_t s) {
-            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
+            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, so, s);
         });
     });
 }
@@ -1423,10 +1457,10 @@ int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, 
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = window_prefix(h, visual_out, s)) return rc;
-        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, s);
     });
 }
 
@@ -1440,6 +1474,31 @@ int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
             if (int rc = dev_alloc(h, &sl.amax_sum, (size_t)sl.Mt * (size_t)((h->V + 15) / 16))) { h->slots[0].amax_sum = nullptr; return rc; }
     }
     h->lp_attach = logprobs_out; h->lp_ld = ld;
+    return 0;
+}
+
+int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_search_options: null handle");
+    if (!opt) { h->so_attach = SearchOpt{}; return 0; }
+    if (opt->num_keep_best < 1 || opt->num_keep_best > 16)
+        return fail(h, GITCAP_ERR_ARG, "attach_search_options: num_keep_best outside [1, 16]");
+    if (!(opt->repetition_penalty > 0.f) || !std::isfinite(opt->repetition_penalty))
+        return fail(h, GITCAP_ERR_ARG, "attach_search_options: repetition_penalty must be finite and > 0");
+    if (opt->num_keep_best > 1 && (!opt->nbest_out || !opt->nbest_logprobs_out))
+        return fail(h, GITCAP_ERR_ARG, "attach_search_options: num_keep_best > 1 needs nbest_out and nbest_logprobs_out");
+    if (((uintptr_t)opt->nbest_out & 7) != 0 || ((uintptr_t)opt->nbest_logprobs_out & 3) != 0)
+        return fail(h, GITCAP_ERR_ARG, "attach_search_options: a misaligned output pointer");
+    GUARD(h);
+    if (opt->num_keep_best > 1 && !h->slots[0].nb_len) {     // first n-best attach: the hypothesis state of every pipeline slot
+        const size_t Bm = (size_t)h->c.max_batch, T = (size_t)h->Tmax + 1;
+        for (auto& sl : h->slots) {
+            int rc = dev_alloc(h, &sl.nb_ids, Bm * 16 * T);
+            rc = rc ? rc : dev_alloc(h, &sl.nb_score, Bm * 16);
+            rc = rc ? rc : dev_alloc(h, &sl.nb_len, Bm * 16);
+            if (rc) { h->slots[0].nb_len = nullptr; return rc; }
+        }
+    }
+    h->so_attach = SearchOpt{opt->num_keep_best, opt->repetition_penalty, opt->nbest_out, opt->nbest_logprobs_out};
     return 0;
 }
 
@@ -1503,6 +1562,21 @@ int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int 
     hipStream_t s = (hipStream_t)stream;
     if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
     const hipError_t e = launch_beam_topk(logits, ld, beam_scores, B, beams, V, K, out_scores, out_idx, scratch, s);
+    (void)hipFreeAsync(scratch, s);
+    return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
+}
+
+int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                               float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
+    if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || K <= 0) return GITCAP_ERR_ARG;
+    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty)) return GITCAP_ERR_ARG;
+    if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
+    if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
+    void* scratch = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
+    const hipError_t e = launch_beam_topk_penalized(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K,
+                                                    out_scores, out_idx, scratch, s);
     (void)hipFreeAsync(scratch, s);
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
@@ -1727,6 +1801,31 @@ int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len,
     BeamBuffers bb;
     if (!dbg_beam_buffers(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
     return dbg_rc(launch_beam_finish(bb, B, max_len, eos, decoded, logprobs, (hipStream_t)stream));
+}
+
+static bool dbg_beam_buffers_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamBuffers& bb) {
+    if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len ||
+        b->n < 1 || b->n > 16)
+        return false;
+    bb = BeamBuffers{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
+    return true;
+}
+
+int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                               int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || V <= 0 ||
+        cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_step_nbest(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
+                                         (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                                 void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_finish_nbest(bb, b->n, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
 }
 
 // ---- text-row kernels of the token loop (tests/test_text_rows_gpu.py): each hook is ONE launcher on caller-owned device buffers,

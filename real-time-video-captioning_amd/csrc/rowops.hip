@@ -2,6 +2,7 @@
 // (im2col of NCHW fp32 frames, coalesced 16-B reads along W), text embedding, token selection.
 #include "kernels.h"
 #include <algorithm>
+#include <cmath>
 #include "ln_canon.h"
 #include "rowln.h"
 
@@ -580,6 +581,94 @@ __global__ __launch_bounds__(256) void beam_topk_chunks_kernel(const float* __re
     }
 }
 
+// The chunk kernel under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
+// ids[row * ld_ids + 0 .. cur_len - 1] (CLS included) is rewritten x < 0 ? x * rp : x / rp before the chunk statistics and the
+// chunk's top K are taken, so the log-softmax is that of the penalised row.  A column is penalised once however often it occurs:
+// the prefix sets bits of a 2048-bit LDS map of the chunk, every thread then tests the bits of its 8 columns.  An id outside
+// [0, V) sets no bit.  -inf stays -inf; plain IEEE fp32 multiply / divide.  A kernel of its own: the one above stays the code it was.
+template <int KMAX>
+__global__ __launch_bounds__(256) void beam_topk_chunks_pen_kernel(const float* __restrict__ logits, int ld, int V, int K, int nch,
+                                                                   const int64_t* __restrict__ prefix_ids, int ld_ids, int cur_len,
+                                                                   float rp, float2* __restrict__ stats, float* __restrict__ cval,
+                                                                   int* __restrict__ cidx) {
+    __shared__ float red[4];
+    __shared__ int redi[4];
+    __shared__ unsigned seen[BT_CHUNK / 32];
+    const int row = blockIdx.x / nch, c = blockIdx.x - row * nch;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float* src = logits + (size_t)row * ld;
+    if (tid < BT_CHUNK / 32) seen[tid] = 0u;
+    __syncthreads();
+    for (int t = tid; t < cur_len; t += 256) {
+        const int64_t id = prefix_ids[(size_t)row * ld_ids + t];
+        if (id >= 0 && id < (int64_t)V) {
+            const int rel = (int)id - c * BT_CHUNK;
+            if (rel >= 0 && rel < BT_CHUNK) atomicOr(&seen[rel >> 5], 1u << (rel & 31));
+        }
+    }
+    __syncthreads();
+    float x[8];
+    float m = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int rel = q * 256 + tid;
+        const int i = c * BT_CHUNK + rel;
+        float v = i < V ? src[i] : -INFINITY;
+        if ((seen[rel >> 5] >> (rel & 31)) & 1u) v = v < 0.f ? v * rp : v / rp;
+        x[q] = v;
+        m = fmaxf(m, v);
+    }
+    m = wave_max(m);
+    if (lane == 0) red[wid] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) sum += x[q] == -INFINITY ? 0.f : expf(x[q] - m);
+    sum = wave_sum(sum);
+    if (lane == 0) red[wid] = sum;
+    __syncthreads();
+    if (tid == 0) stats[blockIdx.x] = float2{m, (red[0] + red[1]) + (red[2] + red[3])};
+    __syncthreads();
+    float tv[KMAX];
+    int ti[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) { tv[k] = -INFINITY; ti[k] = 0x7fffffff; }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        float v = x[q];
+        int id = c * BT_CHUNK + q * 256 + tid;
+        if (v > tv[KMAX - 1]) {
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (v > tv[k]) { const float fv = tv[k]; const int fi = ti[k]; tv[k] = v; ti[k] = id; v = fv; id = fi; }
+        }
+    }
+    for (int k = 0; k < K; ++k) {
+        float bv = tv[0];
+        int bi = ti[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(bv, o);
+            const int i2 = __shfl_xor(bi, o);
+            if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
+        }
+        if (lane == 0) { red[wid] = bv; redi[wid] = bi; }
+        __syncthreads();
+        bv = red[0]; bi = redi[0];
+        for (int w = 1; w < 4; ++w)
+            if (red[w] > bv || (red[w] == bv && redi[w] < bi)) { bv = red[w]; bi = redi[w]; }
+        if (tid == 0) { cval[(size_t)blockIdx.x * K + k] = bv; cidx[(size_t)blockIdx.x * K + k] = bi; }
+        if (ti[0] == bi && bi != 0x7fffffff) {
+#pragma unroll
+            for (int q = 0; q + 1 < KMAX; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
+            tv[KMAX - 1] = -INFINITY; ti[KMAX - 1] = 0x7fffffff;
+        }
+        __syncthreads();
+    }
+}
+
 template <int KMAX>
 __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float2* __restrict__ stats, const float* __restrict__ cval,
                                                              const int* __restrict__ cidx, const float* __restrict__ beam_scores,
@@ -736,6 +825,150 @@ __global__ void beam_init_kernel(BeamState st, int B, int beams, int max_len, in
     if (r < B) { st.done[r] = 0; st.hyp_len[r] = 0; st.hyp_score[r] = 0.f; }
 }
 
+// ---- the same bookkeeping with n finished hypotheses per clip (num_keep_best = n, 1 <= n <= 16) ---------------------------------
+// BeamHypotheses of the reference's search (model.py:503): hyp_ids [B][n][max_len], hyp_score [B][n], hyp_len [B][n] hold the
+// stored hypotheses of a clip in STORAGE ORDER in slots 0 .. cnt - 1 (hyp_len > 0: a hypothesis is at least CLS); slots behind
+// them have hyp_len 0.
+//   add:     fewer than n stored: append.  Otherwise the stored minimum (the earliest stored among equal minima) is deleted --
+//            the slots behind it move down one, as `del list[i]` does -- and the new one is appended, only if its score is
+//            strictly greater than that minimum.
+//   is_done: false while fewer than n are stored, else min stored score >= best candidate sum / (max_len - 1)^length_penalty.
+// One wave per clip.  Thread 0 walks the <= 16 sorted candidates as beam_step_kernel does and posts what to store (s_cmd); the
+// wave moves the ids (lane t owns column t of every slot, so the slots of a shift need no barrier between them).
+__global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n, const float* __restrict__ cand_scores,
+                                                             const int* __restrict__ cand_idx, int beams, int K, int V,
+                                                             int cur_len, int max_len, int eos, float length_penalty, int cur) {
+    __shared__ int s_src[16];
+    __shared__ long long s_word[16];
+    __shared__ float s_hs[16];
+    __shared__ int s_hl[16];
+    __shared__ int s_cnt, s_cmd, s_from;
+    __shared__ float s_score;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t* ids_old = st.ids[cur];
+    int64_t* ids_new = st.ids[cur ^ 1];
+    int64_t* hyp = st.hyp_ids + (size_t)b * n * max_len;
+    if (tid < n) { s_hs[tid] = st.hyp_score[b * n + tid]; s_hl[tid] = st.hyp_len[b * n + tid]; }
+    __syncthreads();
+    const float* cs = cand_scores + (size_t)b * K;
+    const int* ci = cand_idx + (size_t)b * K;
+    bool done = false;
+    int kept = 0;
+    if (tid == 0) {
+        int cnt = 0;
+        while (cnt < n && s_hl[cnt] > 0) ++cnt;
+        s_cnt = cnt;
+        done = st.done[b] != 0;
+        if (!done && cnt == n) {                                          // BeamHypotheses.is_done(best_sum_logprobs)
+            float worst = s_hs[0];
+            for (int i = 1; i < n; ++i) worst = fminf(worst, s_hs[i]);
+            done = worst >= cs[0] / powf((float)(max_len - 1), length_penalty);
+        }
+    }
+    for (int c = 0; c < K; ++c) {
+        if (tid == 0) {
+            int cmd = -2;                                                 // -2: nothing to store; -1: stop; n: append; e < n: delete slot e, append
+            if (done || kept >= beams) {
+                cmd = -1;
+            } else {
+                const int beam_id = ci[c] / V, word = ci[c] - beam_id * V;
+                if (word == eos || cur_len + 1 == max_len) {              // finished hypothesis: ids[:cur_len]
+                    const float score = cs[c] / powf((float)cur_len, length_penalty);
+                    const int cnt = s_cnt;
+                    if (cnt < n) {
+                        cmd = n;
+                    } else {
+                        int e = 0;
+                        for (int i = 1; i < n; ++i)
+                            if (s_hs[i] < s_hs[e]) e = i;                 // strict <: the earliest stored of equal minima
+                        if (score > s_hs[e]) cmd = e;
+                    }
+                    s_score = score;
+                    s_from = b * beams + beam_id;
+                } else {
+                    s_src[kept] = b * beams + beam_id;
+                    s_word[kept] = word;
+                    st.beam_scores[b * beams + kept] = cs[c];
+                    ++kept;
+                }
+            }
+            s_cmd = cmd;
+        }
+        __syncthreads();
+        const int cmd = s_cmd;
+        if (cmd == -1) break;
+        if (cmd >= 0) {
+            const int cnt = s_cnt;
+            const int dst = cmd < n ? cnt - 1 : cnt;
+            for (int i = cmd; i < cnt - 1; ++i) {                         // (append: cmd = n >= cnt, no trip)
+                const int len = s_hl[i + 1];
+                for (int t = tid; t < len; t += 64) hyp[(size_t)i * max_len + t] = hyp[(size_t)(i + 1) * max_len + t];
+            }
+            const int64_t* srow = ids_old + (size_t)s_from * max_len;
+            for (int t = tid; t < cur_len; t += 64) hyp[(size_t)dst * max_len + t] = srow[t];
+            __syncthreads();                                              // every lane has read s_hl / s_cnt / s_from
+            if (tid == 0) {
+                for (int i = cmd; i < cnt - 1; ++i) { s_hs[i] = s_hs[i + 1]; s_hl[i] = s_hl[i + 1]; }
+                s_hs[dst] = s_score;
+                s_hl[dst] = cur_len;
+                s_cnt = dst + 1;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (kept < beams) {                                               // done, or the last step: pad (0, eos, row 0)
+            for (int j = 0; j < beams; ++j) {
+                s_src[j] = 0; s_word[j] = eos;
+                st.beam_scores[b * beams + j] = 0.f;
+            }
+        }
+        st.done[b] = done ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < n) { st.hyp_score[b * n + tid] = s_hs[tid]; st.hyp_len[b * n + tid] = s_hl[tid]; }
+    for (int j = 0; j < beams; ++j) {
+        const int r = b * beams + j, src = s_src[j];
+        for (int t = tid; t < cur_len; t += 64) ids_new[(size_t)r * max_len + t] = ids_old[(size_t)src * max_len + t];
+        if (tid == 0) {
+            ids_new[(size_t)r * max_len + cur_len] = s_word[j];
+            st.words[r] = s_word[j];
+            st.src_rows[r] = src;
+        }
+    }
+}
+
+// decoded[b][k] = the stored hypothesis of rank k by descending score (equal scores in storage order) + EOS padding, logprobs[b][k]
+// = its score; a rank with no hypothesis is all-EOS with score -1e5 (model.py:653-678).  One workgroup per (clip, slot): it counts
+// the slots ranked before its own.  first_decoded / first_logprobs (nullable): rank 0 once more, [B][max_len] / [B].
+__global__ __launch_bounds__(64) void beam_finish_nbest_kernel(BeamState st, int n, int max_len, int eos, int64_t* __restrict__ decoded,
+                                                               float* __restrict__ logprobs, int64_t* __restrict__ first_decoded,
+                                                               float* __restrict__ first_logprobs) {
+    const int b = blockIdx.x, i = blockIdx.y;
+    const int len = st.hyp_len[b * n + i];
+    const float score = st.hyp_score[b * n + i];
+    int rank = i;                                                         // an empty slot: behind every stored one, in slot order
+    if (len > 0) {
+        rank = 0;
+        for (int j = 0; j < n; ++j) {
+            if (j == i || st.hyp_len[b * n + j] <= 0) continue;
+            const float sj = st.hyp_score[b * n + j];
+            rank += sj > score || (sj == score && j < i);
+        }
+    }
+    const int64_t* src = st.hyp_ids + ((size_t)b * n + i) * max_len;
+    for (int t = threadIdx.x; t < max_len; t += blockDim.x) {
+        const int64_t v = t < len ? src[t] : (int64_t)eos;
+        decoded[((size_t)b * n + rank) * max_len + t] = v;
+        if (rank == 0 && first_decoded) first_decoded[(size_t)b * max_len + t] = v;
+    }
+    if (threadIdx.x == 0) {
+        const float lp = len > 0 ? score : -1e5f;
+        logprobs[b * n + rank] = lp;
+        if (rank == 0 && first_logprobs) first_logprobs[b] = lp;
+    }
+}
+
 // steps_out = number of generated columns that are valid under the stop rule
 __global__ void finish_steps_kernel(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out) {
     int steps = max_len;
@@ -872,6 +1105,47 @@ hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_score
         hipLaunchKernelGGL(beam_topk_chunks_kernel<16>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx);
         hipLaunchKernelGGL(beam_topk_merge_kernel<16>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids,
+                                      int cur_len, float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx,
+                                      void* scratch, hipStream_t s) {
+    if (rp == 1.0f) return launch_beam_topk(logits, ld, beam_scores, B, beams, V, K, out_scores, out_idx, scratch, s);
+    const int nch = (V + BT_CHUNK - 1) / BT_CHUNK;
+    if (B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || K > beams * V || nch > 64 || !scratch) return hipErrorInvalidValue;
+    if (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp)) return hipErrorInvalidValue;
+    const size_t n = (size_t)B * beams * nch;
+    float2* stats = (float2*)scratch;
+    float* cval = (float*)(stats + n);
+    int* cidx = (int*)(cval + n * K);
+    if (K <= 8) {
+        hipLaunchKernelGGL(beam_topk_chunks_pen_kernel<8>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, prefix_ids, ld_ids,
+                           cur_len, rp, stats, cval, cidx);
+        hipLaunchKernelGGL(beam_topk_merge_kernel<8>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
+    } else {
+        hipLaunchKernelGGL(beam_topk_chunks_pen_kernel<16>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, prefix_ids, ld_ids,
+                           cur_len, rp, stats, cval, cidx);
+        hipLaunchKernelGGL(beam_topk_merge_kernel<16>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_step_nbest(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
+                                  int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s) {
+    if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
+    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
+    hipLaunchKernelGGL(beam_step_nbest_kernel, dim3(B), dim3(64), 0, s, st, n, cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
+                       length_penalty, cur);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_finish_nbest(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                                    int64_t* first_decoded, float* first_logprobs, hipStream_t s) {
+    if (n < 1 || n > 16) return hipErrorInvalidValue;
+    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
+    hipLaunchKernelGGL(beam_finish_nbest_kernel, dim3(B, n), dim3(64), 0, s, st, n, max_len, eos, decoded, logprobs, first_decoded,
+                       first_logprobs);
     return hipGetLastError();
 }
 

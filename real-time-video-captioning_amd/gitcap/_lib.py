@@ -25,6 +25,16 @@ class CDbgBeamBuffers(ctypes.Structure):
                 ("hyp_score", c_void_p), ("src_rows", c_void_p), ("done", c_void_p), ("hyp_len", c_void_p)]
 
 
+class CDbgBeamBuffersNbest(ctypes.Structure):
+    """struct gitcap_dbg_beam_buffers_nbest (include/gitcap.h): the same nine pointers with [B][n] hypothesis buffers, and n."""
+    _fields_ = CDbgBeamBuffers._fields_ + [("n", c_int32)]
+
+
+class CSearchOptions(ctypes.Structure):
+    """struct gitcap_search_options (include/gitcap.h)."""
+    _fields_ = [("num_keep_best", c_int32), ("repetition_penalty", c_float), ("nbest_out", c_void_p), ("nbest_logprobs_out", c_void_p)]
+
+
 class CDbgSkinnyArgs(ctypes.Structure):
     """struct gitcap_dbg_skinny_args (include/gitcap.h)."""
     _fields_ = [("X", c_void_p), ("ldx", c_int32), ("W", c_void_p), ("Wpk", c_void_p), ("wscale", c_void_p), ("bias", c_void_p),
@@ -129,6 +139,13 @@ SYMBOLS = {
     "gitcap_dbg_txt_block": (c_int, [POINTER(CDbgTxtBlockArgs), c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
+    # search options of the device-resident search: n-best hypotheses, repetition penalty (tests/test_search_options_gpu.py)
+    "gitcap_attach_search_options": (c_int, [c_void_p, POINTER(CSearchOptions)]),
+    "gitcap_beam_topk_penalized": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_beam_step_nbest": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_float, c_int, c_void_p]),
+    "gitcap_dbg_beam_finish_nbest": (c_int, [POINTER(CDbgBeamBuffersNbest), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),

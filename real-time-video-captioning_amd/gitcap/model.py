@@ -18,6 +18,7 @@ in the hand-written gfx950 kernels behind the C ABI (include/gitcap.h).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import weakref
 from typing import Dict, Mapping, Optional
@@ -156,6 +157,11 @@ class _StagingRing:
         return dview, e, st
 
 
+def _lp2d(logprobs):
+    """The search's scores as the reference returns them, [B, num_keep_best] (the one-hypothesis call writes [B])."""
+    return logprobs[:, None] if logprobs.dim() == 1 else logprobs
+
+
 class _Future:
     """Common part of the result handles: wait, vouch for the result where a host synchronisation makes that possible, and
     re-run the batch on the (by then degraded) handle if the submission was poisoned by a failed statistics exchange."""
@@ -235,7 +241,7 @@ class InferFuture(_Future):
             decoded, logprobs, steps, vis = sub.outs
             dev = self._out_device
             mv = lambda t: t if t is None or t.device == dev else t.to(dev)
-            return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]),
+            return {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)),
                     "logits_dict": [] if steps is None else steps, "visual_features": mv(vis)}
 
         def rerun():
@@ -255,8 +261,9 @@ class CaptionStream(_WindowStream):
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None, logprobs=False):
+                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0):
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
+        self._nbest, self._rp = int(num_keep_best), float(repetition_penalty)
         self._clear()
         super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
 
@@ -339,13 +346,17 @@ class CaptionStream(_WindowStream):
             else:
                 decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 logprobs = torch.empty((B,), dtype=torch.float32, device=m._dev)
+                attach, nbest, nbest_lp, _ = m._search_options(B, self._max_len, self._nbest, self._rp)
+                attach()                         # one-shot: consumed by the search below (a repeated caption attaches again)
                 m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
                         _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
+                if nbest is not None:
+                    decoded, logprobs = nbest, nbest_lp
         m._last_memory = None
         if self._beam is None:
             return self._finish_greedy(ids, steps, lp, on_cpu)
         mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
-        return {"predictions": mv(decoded), "logprobs": mv(logprobs[:, None]), "logits_dict": [], "visual_features": mv(vis)}
+        return {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)), "logits_dict": [], "visual_features": mv(vis)}
 
 
 def _rebuild(cfg_dict, weights, kwargs):
@@ -441,14 +452,19 @@ class GitCaptioner(_NativeModule):
             self._ring = _StagingRing(self._dev, self._lib, own_stream=self._copy_stream == "own")
         return self._ring
 
-    def _submit(self, name, *args):
+    def _submit(self, name, *args, before=None):
         """A gitcap_*_submit call.  If the library reports a failed statistics exchange at this entry (GITCAP_ERR_EXCHANGE, once)
         nothing was submitted: everything already in flight is undefined (marked; each future re-runs its batch when asked) and the
-        call is repeated on the handle, which has switched to the unfused launches."""
+        call is repeated on the handle, which has switched to the unfused launches.  ``before``: a one-shot attachment the call
+        consumes (it is made again before the repeat: the refused call consumed the first)."""
         try:
+            if before is not None:
+                before()
             self._call(name, *args)
         except _lib.GitcapExchangeTimeout:
             self._poison_inflight()
+            if before is not None:
+                before()
             self._call(name, *args)
 
     def poll_errors(self):
@@ -892,15 +908,18 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def infer(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
-              on_device: Optional[bool] = None) -> dict:
+              on_device: Optional[bool] = None, repetition_penalty: float = 1.0) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
-        reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded), logprobs [B,1],
+        reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
+        score for num_keep_best > 1, the squeeze of :676), logprobs [B, num_keep_best] (-1e5 where a clip finished fewer),
         logits_dict (when save_logits, cf. :521: per-step [B*beams, V] host arrays from the host operator, which stops once every
         clip is done (:640); ONE device tensor [max_steps - 1, B*beams, V] from the device search, which runs every step) and
         visual_features.
-        Default: the device-resident search (no host sync per step); on_device=False runs the host-side
-        operator of gitcap/search.py (needed for num_keep_best > 1 or save_logits)."""
+        Default: the device-resident search (no host sync per step), whenever num_keep_best <= beam_size * per_node_beam_size
+        <= 16 and per_node_beam_size >= 2; it keeps num_keep_best hypotheses and applies repetition_penalty (model.py:522-531) on
+        the device (include/gitcap.h: gitcap_attach_search_options).  on_device=False runs the host-side operator of
+        gitcap/search.py with the same two arguments (the default with save_logits)."""
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
@@ -913,17 +932,19 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"batch {B} > max_batch={self.max_batch}")
         fr = self._to_device(fr)
         if on_device is None:
-            on_device = (num_keep_best == 1 and not save_logits and beam_size * per_node_beam_size <= 16
+            on_device = (not save_logits and 1 <= num_keep_best <= beam_size * per_node_beam_size <= 16
                          and per_node_beam_size >= 2)
         if on_device:
-            self._check_device_search(beam_size, per_node_beam_size, num_keep_best)
+            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
             decoded, logprobs, steps, vis = self._infer_device(fr, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
                                                                per_node_beam_size=per_node_beam_size, sync=True,
-                                                               save_logits=save_logits, want_visual=False, raw=raw)
-            return {"predictions": decoded, "logprobs": logprobs[:, None], "logits_dict": [] if steps is None else steps,
+                                                               save_logits=save_logits, want_visual=False, raw=raw,
+                                                               num_keep_best=num_keep_best, repetition_penalty=repetition_penalty)
+            return {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
                     "visual_features": None}
         _, vis = self.forward_image_enc(fr)
-        searcher = GeneratorWithBeamSearch(self.sep_token_id, max_steps, beam_size, per_node_beam_size, length_penalty)
+        searcher = GeneratorWithBeamSearch(self.sep_token_id, max_steps, beam_size, per_node_beam_size, length_penalty,
+                                           repetition_penalty=repetition_penalty)
         start = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev)      # model.py:429-431
 
         def step(ids):                       # decoding_step bound at model.py:442-445, KV-cached
@@ -936,32 +957,58 @@ class GitCaptioner(_NativeModule):
                                                    save_logits=save_logits)
         return {"predictions": decoded, "logprobs": logprobs, "logits_dict": saved, "visual_features": vis}
 
-    def _check_device_search(self, beam_size, per_node_beam_size, num_keep_best):
+    def _check_device_search(self, beam_size, per_node_beam_size, num_keep_best=1, repetition_penalty=1.0):
         if per_node_beam_size < 2:
             raise ValueError("the device-resident search needs per_node_beam_size >= 2: with one candidate per beam "
                              "a single EOS leaves fewer than beam_size live beams (model.py:606 asserts against it); "
                              "the host operator (on_device=False) raises when that happens")
-        if num_keep_best != 1:
-            raise ValueError("the device-resident search keeps one hypothesis")
         if beam_size * per_node_beam_size > 16:
             raise ValueError("the device-resident search ranks at most 16 candidates per clip")
+        if not 1 <= num_keep_best <= beam_size * per_node_beam_size:
+            raise ValueError(f"num_keep_best {num_keep_best} outside [1, beam_size * per_node_beam_size = "
+                             f"{beam_size * per_node_beam_size}]: a step ranks no more candidates than that")
+        if not (math.isfinite(repetition_penalty) and repetition_penalty > 0):
+            raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
+
+    def _search_options(self, B, max_steps, num_keep_best, repetition_penalty):
+        """-> (attach, nbest, nbest_logprobs, rank0): ``attach()`` makes the one-shot gitcap_attach_search_options call that the NEXT
+        beam-family call consumes (every issue of that call, a repeat after a failed statistics exchange included, needs its own);
+        the n-best output buffers and, cut from the same two allocations, (decoded, logprobs) buffers for the call's own outputs;
+        None for num_keep_best == 1.  With the defaults attach() does nothing at all."""
+        if num_keep_best == 1 and repetition_penalty == 1.0:
+            return (lambda: None), None, None, None
+        nbest = nbest_lp = rank0 = None
+        if num_keep_best > 1:                    # [B, n, ...] with room for the call's own [B, ...] outputs behind it
+            n = num_keep_best
+            ids = torch.empty((B * (n + 1) * max_steps,), dtype=torch.int64, device=self._dev)
+            lps = torch.empty((B * (n + 1),), dtype=torch.float32, device=self._dev)
+            nbest, nbest_lp = ids[:B * n * max_steps].view(B, n, max_steps), lps[:B * n].view(B, n)
+            rank0 = (ids[B * n * max_steps:].view(B, max_steps), lps[B * n:])
+        opt = _lib.CSearchOptions(int(num_keep_best), float(repetition_penalty), nbest.data_ptr() if nbest is not None else None,
+                                  nbest_lp.data_ptr() if nbest_lp is not None else None)
+        return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
 
     def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None):
+                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0):
         """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
         stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
         the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
-        visual | None) [+ the ticket when submitted]."""
+        visual | None) [+ the ticket when submitted]; with num_keep_best > 1 decoded is [B, n, max_steps] and logprobs [B, n]."""
         if raw is None:
             raw = fr.dtype == torch.uint8
         B, F = fr.shape[:2]
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
+        attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty)
+        first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
+        if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
+            first, decoded, logprobs = rank0, nbest, nbest_lp
         with torch.cuda.device(self._dev):
             if sync and not save_logits and not want_visual and not raw:
                 self._drain()
+                attach()
                 self._call("gitcap_beam_search", _lib.ptr(fr), B, F, beam_size, max_steps, ctypes.c_float(length_penalty),
-                           per_node_beam_size, _lib.ptr(decoded), _lib.ptr(logprobs), self._stream())
+                           per_node_beam_size, _lib.ptr(first[0]), _lib.ptr(first[1]), self._stream())
                 self._last_memory = None
                 return decoded, logprobs, None, None
             steps = torch.empty((max_steps - 1, B * beam_size, self.cfg.vocab_size), dtype=torch.float32, device=self._dev) if save_logits else None
@@ -969,12 +1016,12 @@ class GitCaptioner(_NativeModule):
             while len(self._inflight) >= 4:
                 self._wait_submission(self._inflight[0])
             ticket = ctypes.c_int(-1)
-            tail = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(decoded),
-                    _lib.ptr(logprobs), _lib.ptr(steps), stream if stream is not None else self._stream(), ctypes.byref(ticket))
+            tail = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(first[0]),
+                    _lib.ptr(first[1]), _lib.ptr(steps), stream if stream is not None else self._stream(), ctypes.byref(ticket))
             if raw:
-                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fr.shape[2], fr.shape[3], *tail)
+                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fr.shape[2], fr.shape[3], *tail, before=attach)
             else:
-                self._submit("gitcap_beam_search_submit", _lib.ptr(fr), B, F, *tail)
+                self._submit("gitcap_beam_search_submit", _lib.ptr(fr), B, F, *tail, before=attach)
             self._last_memory = None
             if sync:                           # (a re-run, or a synchronous call that wants logits / visual features / takes raw frames)
                 self._call("gitcap_beam_search_wait", ticket.value, self._stream())
@@ -983,14 +1030,16 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def infer_async(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
-                    per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False) -> "InferFuture":
+                    per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False,
+                    num_keep_best: int = 1, repetition_penalty: float = 1.0) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
         tensor [max_steps - 1, B * beam_size, V] (the raw logits of every step, model.py:521), with ``visual_features`` the fp32
-        features [B, F*N, Dv] (model.py:460).  Results are bitwise those of the synchronous call.  `src` as in
+        features [B, F*N, Dv] (model.py:460); num_keep_best / repetition_penalty as in ``infer``.  Results are bitwise those of the
+        synchronous call.  `src` as in
         greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
-        self._check_device_search(beam_size, per_node_beam_size, 1)
+        self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
         if max_steps > self.max_text_len:
@@ -1000,7 +1049,8 @@ class GitCaptioner(_NativeModule):
         fr, raw = self._check_frames(src)
         if fr.shape[0] > self.max_batch:
             raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
-        kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size)
+        kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
+                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty)
         parts = entry = stream = None
         if fr.device.type == "cpu":
             while len(self._inflight) >= 4:      # (before the staging: the entry about to be reused belongs to the oldest)
@@ -1020,12 +1070,13 @@ class GitCaptioner(_NativeModule):
 
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
-                       visual_features: bool = False, gate=None, logprobs: bool = False) -> CaptionStream:
+                       visual_features: bool = False, gate=None, logprobs: bool = False, num_keep_best: int = 1,
+                       repetition_penalty: float = 1.0) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
         default (ids as greedy_decode(max_len, stop)); with beam_size the dict of infer's device search (max_len = its
-        max_steps; visual_features adds the window's features).  One live stream per model: opening another one, or .to() /
+        max_steps; visual_features adds the window's features; num_keep_best / repetition_penalty as in infer).  One live stream per model: opening another one, or .to() /
         .cuda(), invalidates this one.  ``gate``: a gitcap.framegate.FrameGate that decides on the device which pushed camera frames
         are worth encoding (it is reset here); without one every pushed frame is.  ``logprobs`` (greedy streams only): after a push
         that returned a caption, ``stream.last_logprobs`` holds its per-token log-probabilities [B, steps] (greedy_decode's
@@ -1042,9 +1093,11 @@ class GitCaptioner(_NativeModule):
         if beam_size is None:
             if visual_features:
                 raise ValueError("visual_features come with the beam-search dict (beam_size=...)")
+            if num_keep_best != 1 or repetition_penalty != 1.0:
+                raise ValueError("num_keep_best / repetition_penalty are options of the beam search (beam_size=...)")
         else:
             per_node_beam_size = 2 if per_node_beam_size is None else per_node_beam_size
-            self._check_device_search(beam_size, per_node_beam_size, 1)
+            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
             if beam_size > self.max_beams:
                 raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
         if gate is not None:
@@ -1052,7 +1105,7 @@ class GitCaptioner(_NativeModule):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
-                             logprobs)
+                             logprobs, num_keep_best, repetition_penalty)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip
