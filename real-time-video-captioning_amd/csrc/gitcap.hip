@@ -1250,18 +1250,16 @@ int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
 // The search loop over the image K/V of the selected slot (its beam state, text K/V and row workspace), on stream s.
 // step_logits_out (nullable): [max_steps - 1][B * beams][V], the raw logits of every step (what model.py:521 saves).
 // so: the call's search options.  rp != 1: the candidates are ranked on the logits penalised at the columns of every row's prefix
-// (the saved step logits stay raw, model.py:521 comes before :522); n > 1: the n-best bookkeeping over the slot's nb_* state,
-// decoded_out / logprobs_out receive rank 0.  The defaults issue exactly the launches of a search without options.
+// (the saved step logits stay raw, model.py:521 comes before :522); n > 1: the bookkeeping keeps n hypotheses in the slot's nb_* state.
+// decoded_out / logprobs_out receive rank 0, the attached outputs all n ranks.
 static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                      int64_t* decoded_out, float* logprobs_out, float* step_logits_out, const SearchOpt& so, hipStream_t s) {
     const int rows = B * beams, K = beams * per_node_beam_size, V = h->c.vocab_size, L = max_steps;
     gitcap::Slot& sl = cur(h);
     int rc;
-    const bool nbest = so.n > 1;
     BeamBuffers bb = sl.beam;
-    if (nbest) { bb.hyp_ids = sl.nb_ids; bb.hyp_score = sl.nb_score; bb.hyp_len = sl.nb_len; }
-    HIP_OK(h, launch_beam_init(bb, B, beams, L, h->c.cls_token_id, s));
-    if (nbest) HIP_OK(h, hipMemsetAsync(sl.nb_len, 0, (size_t)B * so.n * sizeof(int32_t), s));
+    if (so.n > 1) { bb.hyp_ids = sl.nb_ids; bb.hyp_score = sl.nb_score; bb.hyp_len = sl.nb_len; }
+    HIP_OK(h, launch_beam_init(bb, B, beams, so.n, L, h->c.cls_token_id, s));
     // while cur_len < max_length (model.py:518): the token at position cur_len-1 is decoded, candidates for
     // position cur_len are ranked, bookkept and the text K/V rows follow their beams -- no host round trip
     for (int cur_len = 1, cur = 0; cur_len < L; ++cur_len, cur ^= 1) {
@@ -1274,25 +1272,11 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : sl.beam_logits;
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
-        if (so.rp != 1.0f)
-            HIP_OK(h, launch_beam_topk_penalized(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
-                                                 sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
-        else
-            HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, B, beams, V, K, sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
-        if (nbest)
-            HIP_OK(h, launch_beam_step_nbest(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
-                                             length_penalty, cur, s));
-        else
-            HIP_OK(h, launch_beam_step(sl.beam, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id,
-                                       length_penalty, cur, s));
+        HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
+                                   sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+        HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s));
     }
-    if (nbest) {
-        HIP_OK(h, launch_beam_finish_nbest(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
-        return 0;
-    }
-    HIP_OK(h, launch_beam_finish(sl.beam, B, L, h->c.sep_token_id, decoded_out, logprobs_out, s));
-    if (so.nbest) HIP_OK(h, hipMemcpyAsync(so.nbest, decoded_out, (size_t)B * L * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (so.nbest_lp) HIP_OK(h, hipMemcpyAsync(so.nbest_lp, logprobs_out, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
     return 0;
 }
 
@@ -1554,31 +1538,29 @@ int gitcap_preprocess(const uint8_t* frames_hwc_bgr, int nf, int H, int W, float
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
 
-int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
-                     float* out_scores, int32_t* out_idx, void* stream) {
+// no handle here: the scratch of the two-stage top-k is a stream-ordered allocation
+static int beam_topk_hook(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
+                          int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
     if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || K <= 0) return GITCAP_ERR_ARG;
-    // no handle here: the scratch of the two-stage top-k is a stream-ordered allocation
     void* scratch = nullptr;
     hipStream_t s = (hipStream_t)stream;
     if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
-    const hipError_t e = launch_beam_topk(logits, ld, beam_scores, B, beams, V, K, out_scores, out_idx, scratch, s);
+    const hipError_t e = launch_beam_topk(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, out_scores, out_idx, scratch, s);
     (void)hipFreeAsync(scratch, s);
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
 
+int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
+                     float* out_scores, int32_t* out_idx, void* stream) {
+    return beam_topk_hook(logits, ld, beam_scores, nullptr, 0, 0, 1.0f, B, beams, V, K, out_scores, out_idx, stream);
+}
+
 int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
                                float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
-    if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || K <= 0) return GITCAP_ERR_ARG;
     if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty)) return GITCAP_ERR_ARG;
     if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
     if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
-    void* scratch = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
-    const hipError_t e = launch_beam_topk_penalized(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K,
-                                                    out_scores, out_idx, scratch, s);
-    (void)hipFreeAsync(scratch, s);
-    return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
+    return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream);
 }
 
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
@@ -1782,10 +1764,17 @@ static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) 
     return true;
 }
 
+// (gitcap_dbg_beam_buffers_nbest is gitcap_dbg_beam_buffers with the slot count n behind it)
+static bool dbg_beam_buffers_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamBuffers& bb) {
+    if (!b || b->n < 1 || b->n > 16) return false;
+    const gitcap_dbg_beam_buffers first{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
+    return dbg_beam_buffers(&first, bb);
+}
+
 int gitcap_dbg_beam_init(const gitcap_dbg_beam_buffers* b, int B, int beams, int max_len, int cls, void* stream) {
     BeamBuffers bb;
     if (!dbg_beam_buffers(b, bb) || B <= 0 || beams <= 0 || beams > 16 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_init(bb, B, beams, max_len, cls, (hipStream_t)stream));
+    return dbg_rc(launch_beam_init(bb, B, beams, 1, max_len, cls, (hipStream_t)stream));
 }
 
 int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams, int K,
@@ -1794,38 +1783,30 @@ int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* b, const float* cand_sco
     if (!dbg_beam_buffers(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || K <= 0 || V <= 0 || cur_len < 1 ||
         cur_len >= max_len || (cur != 0 && cur != 1))
         return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_step(bb, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, (hipStream_t)stream));
+    return dbg_rc(launch_beam_step(bb, 1, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, (hipStream_t)stream));
 }
 
 int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs, void* stream) {
     BeamBuffers bb;
     if (!dbg_beam_buffers(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_finish(bb, B, max_len, eos, decoded, logprobs, (hipStream_t)stream));
-}
-
-static bool dbg_beam_buffers_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamBuffers& bb) {
-    if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len ||
-        b->n < 1 || b->n > 16)
-        return false;
-    bb = BeamBuffers{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
-    return true;
+    return dbg_rc(launch_beam_finish(bb, 1, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
 }
 
 int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
                                int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
     BeamBuffers bb;
-    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || V <= 0 ||
-        cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
+    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
+        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
         return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_step_nbest(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
-                                         (hipStream_t)stream));
+    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
+                                   (hipStream_t)stream));
 }
 
 int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
                                  void* stream) {
     BeamBuffers bb;
     if (!dbg_beam_buffers_nbest(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_finish_nbest(bb, b->n, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
+    return dbg_rc(launch_beam_finish(bb, b->n, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
 }
 
 // ---- text-row kernels of the token loop (tests/test_text_rows_gpu.py): each hook is ONE launcher on caller-owned device buffers,

@@ -268,14 +268,11 @@ hipError_t launch_gather_txt_rows(const bf16_t* src, bf16_t* dst, const int32_t*
 // j*V + v.  Logits of -inf are no candidates; where a clip has fewer than K candidates the remaining slots hold the sentinel
 // (score -inf, index 0x7fffffff) -- launch_beam_step divides the index by V and must never be handed one.
 size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scratch launch_beam_topk needs (V <= 131072)
-hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
-                            float* out_scores, int* out_idx, void* scratch, hipStream_t s);
-// The same ranking under a repetition penalty rp (model.py:522-531): every logit whose column occurs in the row's prefix
+// rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
 // prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
-// often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f IS launch_beam_topk (the prefix is not read).
-hipError_t launch_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids,
-                                      int cur_len, float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx,
-                                      void* scratch, hipStream_t s);
+// often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
+hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s);
 // uint8 HWC BGR frames [nf][H][W][3] -> CLIP-normalised fp32 NCHW [nf][3][crop][crop] (bicubic resize + centre crop)
 hipError_t launch_preprocess(const unsigned char* in, float* out, int nf, int H, int W, int crop, hipStream_t s);
 // the same transform fused with the patch gather: -> bf16 patch rows [nf*G*G][Kp] (layout of launch_im2col)
@@ -289,14 +286,11 @@ struct BeamBuffers {
     float *beam_scores, *hyp_score;
     int32_t *src_rows, *done, *hyp_len;
 };
-hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int max_len, int cls, hipStream_t s);
-hipError_t launch_beam_step(const BeamBuffers& bb, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s);
-hipError_t launch_beam_finish(const BeamBuffers& bb, int B, int max_len, int eos, int64_t* decoded, float* logprobs, hipStream_t s);
 // n finished hypotheses per clip (1 <= n <= 16): hyp_ids [B][n][max_len], hyp_score / hyp_len [B][n], stored in storage order in
-// slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes the first B entries only: zero hyp_len [B][n] before step 1).
-// finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_* (nullable): rank 0 again as [B][max_len] / [B].
-hipError_t launch_beam_step_nbest(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                                  int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s);
-hipError_t launch_beam_finish_nbest(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
-                                    int64_t* first_decoded, float* first_logprobs, hipStream_t s);
+// slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes all B * n).  step: n = 1 runs beam_step_kernel, n > 1 the n-slot kernel.
+// finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_*: rank 0 again as [B][max_len] / [B]; all nullable.
+hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s);
+hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
+                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s);
+hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                              int64_t* first_decoded, float* first_logprobs, hipStream_t s);

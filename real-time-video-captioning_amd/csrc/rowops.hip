@@ -511,24 +511,54 @@ __global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restri
 //           (inside a row the order by logit IS the order by score);
 //   merge:  one wave per clip: log-sum-exp of every row from the chunk statistics (fixed order), score of every candidate,
 //           top K of the beams x chunks x K candidates.  The global top K is a subset of the per-chunk top K's: exact.
+// Both keep a descending list tv / ti of KMAX (value, id) per thread and take K rounds of arg-max over the list heads, the owner
+// of a round's winner popping it.  The insert, the arg-max round and the pop are written out in both kernels: as shared inline
+// functions they compile to a different schedule of both (docs/LAB_NOTEBOOK.md, round 15).
 constexpr int BT_CHUNK = 2048;
 
-template <int KMAX>
+// PEN: the chunk kernel under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
+// ids[row * ld_ids + 0 .. cur_len - 1] (CLS included) is rewritten x < 0 ? x * rp : x / rp before the chunk statistics and the
+// chunk's top K are taken, so the log-softmax is that of the penalised row.  A column is penalised once however often it occurs:
+// the prefix sets bits of a 2048-bit LDS map of the chunk, every thread then tests the bits of its 8 columns.  An id outside
+// [0, V) sets no bit.  -inf stays -inf; plain IEEE fp32 multiply / divide.  The penalty's arguments come last and are empty
+// without it: the plain instantiation has the bit map, its two barriers and the rewrite compiled out.
+template <bool PEN> struct BeamPenalty {};
+template <> struct BeamPenalty<true> { const int64_t* prefix_ids; int ld_ids, cur_len; float rp; };
+
+template <int KMAX, bool PEN>
 __global__ __launch_bounds__(256) void beam_topk_chunks_kernel(const float* __restrict__ logits, int ld, int V, int K, int nch,
                                                                float2* __restrict__ stats, float* __restrict__ cval,
-                                                               int* __restrict__ cidx) {
+                                                               int* __restrict__ cidx, BeamPenalty<PEN> pen) {
     __shared__ float red[4];
     __shared__ int redi[4];
+    __shared__ unsigned seen[PEN ? BT_CHUNK / 32 : 1];
     const int row = blockIdx.x / nch, c = blockIdx.x - row * nch;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* src = logits + (size_t)row * ld;
+    if constexpr (PEN) {
+        if (tid < BT_CHUNK / 32) seen[tid] = 0u;
+        __syncthreads();
+        for (int t = tid; t < pen.cur_len; t += 256) {
+            const int64_t id = pen.prefix_ids[(size_t)row * pen.ld_ids + t];
+            if (id >= 0 && id < (int64_t)V) {
+                const int rel = (int)id - c * BT_CHUNK;
+                if (rel >= 0 && rel < BT_CHUNK) atomicOr(&seen[rel >> 5], 1u << (rel & 31));
+            }
+        }
+        __syncthreads();
+    }
     float x[8];
     float m = -INFINITY;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        const int i = c * BT_CHUNK + q * 256 + tid;
-        x[q] = i < V ? src[i] : -INFINITY;
-        m = fmaxf(m, x[q]);
+        const int rel = q * 256 + tid;
+        const int i = c * BT_CHUNK + rel;
+        float v = i < V ? src[i] : -INFINITY;
+        if constexpr (PEN) {
+            if ((seen[rel >> 5] >> (rel & 31)) & 1u) v = v < 0.f ? v * pen.rp : v / pen.rp;
+        }
+        x[q] = v;
+        m = fmaxf(m, v);
     }
     m = wave_max(m);
     if (lane == 0) red[wid] = m;
@@ -573,94 +603,6 @@ __global__ __launch_bounds__(256) void beam_topk_chunks_kernel(const float* __re
             if (red[w] > bv || (red[w] == bv && redi[w] < bi)) { bv = red[w]; bi = redi[w]; }
         if (tid == 0) { cval[(size_t)blockIdx.x * K + k] = bv; cidx[(size_t)blockIdx.x * K + k] = bi; }
         if (ti[0] == bi && bi != 0x7fffffff) {                           // the owner pops its head
-#pragma unroll
-            for (int q = 0; q + 1 < KMAX; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
-            tv[KMAX - 1] = -INFINITY; ti[KMAX - 1] = 0x7fffffff;
-        }
-        __syncthreads();
-    }
-}
-
-// The chunk kernel under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
-// ids[row * ld_ids + 0 .. cur_len - 1] (CLS included) is rewritten x < 0 ? x * rp : x / rp before the chunk statistics and the
-// chunk's top K are taken, so the log-softmax is that of the penalised row.  A column is penalised once however often it occurs:
-// the prefix sets bits of a 2048-bit LDS map of the chunk, every thread then tests the bits of its 8 columns.  An id outside
-// [0, V) sets no bit.  -inf stays -inf; plain IEEE fp32 multiply / divide.  A kernel of its own: the one above stays the code it was.
-template <int KMAX>
-__global__ __launch_bounds__(256) void beam_topk_chunks_pen_kernel(const float* __restrict__ logits, int ld, int V, int K, int nch,
-                                                                   const int64_t* __restrict__ prefix_ids, int ld_ids, int cur_len,
-                                                                   float rp, float2* __restrict__ stats, float* __restrict__ cval,
-                                                                   int* __restrict__ cidx) {
-    __shared__ float red[4];
-    __shared__ int redi[4];
-    __shared__ unsigned seen[BT_CHUNK / 32];
-    const int row = blockIdx.x / nch, c = blockIdx.x - row * nch;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const float* src = logits + (size_t)row * ld;
-    if (tid < BT_CHUNK / 32) seen[tid] = 0u;
-    __syncthreads();
-    for (int t = tid; t < cur_len; t += 256) {
-        const int64_t id = prefix_ids[(size_t)row * ld_ids + t];
-        if (id >= 0 && id < (int64_t)V) {
-            const int rel = (int)id - c * BT_CHUNK;
-            if (rel >= 0 && rel < BT_CHUNK) atomicOr(&seen[rel >> 5], 1u << (rel & 31));
-        }
-    }
-    __syncthreads();
-    float x[8];
-    float m = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int rel = q * 256 + tid;
-        const int i = c * BT_CHUNK + rel;
-        float v = i < V ? src[i] : -INFINITY;
-        if ((seen[rel >> 5] >> (rel & 31)) & 1u) v = v < 0.f ? v * rp : v / rp;
-        x[q] = v;
-        m = fmaxf(m, v);
-    }
-    m = wave_max(m);
-    if (lane == 0) red[wid] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) sum += x[q] == -INFINITY ? 0.f : expf(x[q] - m);
-    sum = wave_sum(sum);
-    if (lane == 0) red[wid] = sum;
-    __syncthreads();
-    if (tid == 0) stats[blockIdx.x] = float2{m, (red[0] + red[1]) + (red[2] + red[3])};
-    __syncthreads();
-    float tv[KMAX];
-    int ti[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) { tv[k] = -INFINITY; ti[k] = 0x7fffffff; }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        float v = x[q];
-        int id = c * BT_CHUNK + q * 256 + tid;
-        if (v > tv[KMAX - 1]) {
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k)
-                if (v > tv[k]) { const float fv = tv[k]; const int fi = ti[k]; tv[k] = v; ti[k] = id; v = fv; id = fi; }
-        }
-    }
-    for (int k = 0; k < K; ++k) {
-        float bv = tv[0];
-        int bi = ti[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float v2 = __shfl_xor(bv, o);
-            const int i2 = __shfl_xor(bi, o);
-            if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
-        }
-        if (lane == 0) { red[wid] = bv; redi[wid] = bi; }
-        __syncthreads();
-        bv = red[0]; bi = redi[0];
-        for (int w = 1; w < 4; ++w)
-            if (red[w] > bv || (red[w] == bv && redi[w] < bi)) { bv = red[w]; bi = redi[w]; }
-        if (tid == 0) { cval[(size_t)blockIdx.x * K + k] = bv; cidx[(size_t)blockIdx.x * K + k] = bi; }
-        if (ti[0] == bi && bi != 0x7fffffff) {
 #pragma unroll
             for (int q = 0; q + 1 < KMAX; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
             tv[KMAX - 1] = -INFINITY; ti[KMAX - 1] = 0x7fffffff;
@@ -729,7 +671,7 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float2* __res
             if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
         }
         if (lane == 0) { out_scores[b * K + k] = bv; out_idx[b * K + k] = bi; }
-        if (ti[0] == bi && bi != 0x7fffffff) {
+        if (ti[0] == bi && bi != 0x7fffffff) {                           // the owner pops its head
 #pragma unroll
             for (int q = 0; q + 1 < KMAX; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
             tv[KMAX - 1] = -INFINITY; ti[KMAX - 1] = 0x7fffffff;
@@ -741,16 +683,19 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float2* __res
 // One block per batch element; thread 0 walks the <= 16 sorted candidates exactly like the reference's
 // Python loop (finished hypotheses kept n_best = 1: score = sum_logprob / len^length_penalty, :503, :592-594;
 // is_done test :576), then the block copies the surviving prefixes into the next id buffer (:620-621).
+
 struct BeamState {
     int64_t* ids[2];          // [B*beams][max_len] prefixes, double buffered
     float* beam_scores;       // [B*beams]
     int64_t* words;           // [B*beams] token chosen for the next position (input of the next decoder step)
     int32_t* src_rows;        // [B*beams] row each new beam continues (for the KV reorder)
     int32_t* done;            // [B]
-    int32_t* hyp_len;         // [B] 0 = no finished hypothesis yet
-    float* hyp_score;         // [B]
-    int64_t* hyp_ids;         // [B][max_len]
+    int32_t* hyp_len;         // [B][n] 0 = an empty slot
+    float* hyp_score;         // [B][n]
+    int64_t* hyp_ids;         // [B][n][max_len]
 };
+
+// n = 1: one finished hypothesis per clip in hyp_ids [B][max_len], hyp_score [B], hyp_len [B] (0 = none yet).
 __global__ __launch_bounds__(64) void beam_step_kernel(BeamState st, const float* __restrict__ cand_scores,
                                                        const int* __restrict__ cand_idx, int beams, int K, int V,
                                                        int cur_len, int max_len, int eos, float length_penalty, int cur) {
@@ -805,25 +750,6 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamState st, const float
     }
 }
 
-// decoded[b] = best hypothesis + EOS padding (model.py:653-678, num_keep_best = 1)
-__global__ void beam_finish_kernel(BeamState st, int max_len, int eos, int64_t* __restrict__ decoded, float* __restrict__ logprobs) {
-    const int b = blockIdx.x;
-    const int n = st.hyp_len[b];
-    for (int t = threadIdx.x; t < max_len; t += blockDim.x)
-        decoded[(size_t)b * max_len + t] = t < n ? st.hyp_ids[(size_t)b * max_len + t] : eos;
-    if (threadIdx.x == 0) logprobs[b] = n > 0 ? st.hyp_score[b] : -1e5f;
-}
-
-__global__ void beam_init_kernel(BeamState st, int B, int beams, int max_len, int cls) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < B * beams) {
-        st.ids[0][(size_t)r * max_len] = cls;
-        st.words[r] = cls;
-        st.beam_scores[r] = (r % beams == 0) ? 0.f : -1e9f;                 // model.py:508-509
-        st.src_rows[r] = r;
-    }
-    if (r < B) { st.done[r] = 0; st.hyp_len[r] = 0; st.hyp_score[r] = 0.f; }
-}
 
 // ---- the same bookkeeping with n finished hypotheses per clip (num_keep_best = n, 1 <= n <= 16) ---------------------------------
 // BeamHypotheses of the reference's search (model.py:503): hyp_ids [B][n][max_len], hyp_score [B][n], hyp_len [B][n] hold the
@@ -834,7 +760,9 @@ __global__ void beam_init_kernel(BeamState st, int B, int beams, int max_len, in
 //            strictly greater than that minimum.
 //   is_done: false while fewer than n are stored, else min stored score >= best candidate sum / (max_len - 1)^length_penalty.
 // One wave per clip.  Thread 0 walks the <= 16 sorted candidates as beam_step_kernel does and posts what to store (s_cmd); the
-// wave moves the ids (lane t owns column t of every slot, so the slots of a shift need no barrier between them).
+// wave moves the ids (lane t owns column t of every slot, so the slots of a shift need no barrier between them).  n = 1 never
+// gets here: launch_beam_step sends it to beam_step_kernel, which the n-slot kernel does not match for speed (5.7 against 6.0 us
+// per call at the configs[4] shape); the two are the parent's code to the instruction.
 __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n, const float* __restrict__ cand_scores,
                                                              const int* __restrict__ cand_idx, int beams, int K, int V,
                                                              int cur_len, int max_len, int eos, float length_penalty, int cur) {
@@ -940,10 +868,10 @@ __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n
 
 // decoded[b][k] = the stored hypothesis of rank k by descending score (equal scores in storage order) + EOS padding, logprobs[b][k]
 // = its score; a rank with no hypothesis is all-EOS with score -1e5 (model.py:653-678).  One workgroup per (clip, slot): it counts
-// the slots ranked before its own.  first_decoded / first_logprobs (nullable): rank 0 once more, [B][max_len] / [B].
-__global__ __launch_bounds__(64) void beam_finish_nbest_kernel(BeamState st, int n, int max_len, int eos, int64_t* __restrict__ decoded,
-                                                               float* __restrict__ logprobs, int64_t* __restrict__ first_decoded,
-                                                               float* __restrict__ first_logprobs) {
+// the slots ranked before its own.  first_decoded / first_logprobs: rank 0 once more, [B][max_len] / [B].  Every output is nullable.
+__global__ __launch_bounds__(64) void beam_finish_kernel(BeamState st, int n, int max_len, int eos, int64_t* __restrict__ decoded,
+                                                         float* __restrict__ logprobs, int64_t* __restrict__ first_decoded,
+                                                         float* __restrict__ first_logprobs) {
     const int b = blockIdx.x, i = blockIdx.y;
     const int len = st.hyp_len[b * n + i];
     const float score = st.hyp_score[b * n + i];
@@ -959,14 +887,26 @@ __global__ __launch_bounds__(64) void beam_finish_nbest_kernel(BeamState st, int
     const int64_t* src = st.hyp_ids + ((size_t)b * n + i) * max_len;
     for (int t = threadIdx.x; t < max_len; t += blockDim.x) {
         const int64_t v = t < len ? src[t] : (int64_t)eos;
-        decoded[((size_t)b * n + rank) * max_len + t] = v;
+        if (decoded) decoded[((size_t)b * n + rank) * max_len + t] = v;
         if (rank == 0 && first_decoded) first_decoded[(size_t)b * max_len + t] = v;
     }
     if (threadIdx.x == 0) {
         const float lp = len > 0 ? score : -1e5f;
-        logprobs[b * n + rank] = lp;
+        if (logprobs) logprobs[b * n + rank] = lp;
         if (rank == 0 && first_logprobs) first_logprobs[b] = lp;
     }
+}
+
+__global__ void beam_init_kernel(BeamState st, int B, int beams, int n, int max_len, int cls) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < B * beams) {
+        st.ids[0][(size_t)r * max_len] = cls;
+        st.words[r] = cls;
+        st.beam_scores[r] = (r % beams == 0) ? 0.f : -1e9f;                 // model.py:508-509
+        st.src_rows[r] = r;
+    }
+    if (r < B) st.done[r] = 0;
+    if (r < B * n) { st.hyp_len[r] = 0; st.hyp_score[r] = 0.f; }
 }
 
 // steps_out = number of generated columns that are valid under the stop rule
@@ -1090,83 +1030,60 @@ size_t beam_topk_scratch_bytes(int B, int beams, int V, int K) {
     return n * 8 + n * K * 8;                          // chunk (max, sum) + K (value, index) candidates per chunk
 }
 
-hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
-                            float* out_scores, int* out_idx, void* scratch, hipStream_t s) {
-    const int nch = (V + BT_CHUNK - 1) / BT_CHUNK;
-    if (B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || K > beams * V || nch > 64 || !scratch) return hipErrorInvalidValue;
+template <int KMAX>
+static void beam_topk_launch(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
+                             int B, int beams, int V, int K, int nch, float* out_scores, int* out_idx, void* scratch, hipStream_t s) {
     const size_t n = (size_t)B * beams * nch;
     float2* stats = (float2*)scratch;
     float* cval = (float*)(stats + n);
     int* cidx = (int*)(cval + n * K);
-    if (K <= 8) {
-        hipLaunchKernelGGL(beam_topk_chunks_kernel<8>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx);
-        hipLaunchKernelGGL(beam_topk_merge_kernel<8>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
-    } else {
-        hipLaunchKernelGGL(beam_topk_chunks_kernel<16>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx);
-        hipLaunchKernelGGL(beam_topk_merge_kernel<16>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
-    }
-    return hipGetLastError();
+    if (rp != 1.0f)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
+                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp});
+    else
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
+                           BeamPenalty<false>{});
+    hipLaunchKernelGGL(beam_topk_merge_kernel<KMAX>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
 }
 
-hipError_t launch_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids,
-                                      int cur_len, float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx,
-                                      void* scratch, hipStream_t s) {
-    if (rp == 1.0f) return launch_beam_topk(logits, ld, beam_scores, B, beams, V, K, out_scores, out_idx, scratch, s);
+hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s) {
     const int nch = (V + BT_CHUNK - 1) / BT_CHUNK;
     if (B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || K > beams * V || nch > 64 || !scratch) return hipErrorInvalidValue;
-    if (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp)) return hipErrorInvalidValue;
-    const size_t n = (size_t)B * beams * nch;
-    float2* stats = (float2*)scratch;
-    float* cval = (float*)(stats + n);
-    int* cidx = (int*)(cval + n * K);
-    if (K <= 8) {
-        hipLaunchKernelGGL(beam_topk_chunks_pen_kernel<8>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, prefix_ids, ld_ids,
-                           cur_len, rp, stats, cval, cidx);
-        hipLaunchKernelGGL(beam_topk_merge_kernel<8>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
-    } else {
-        hipLaunchKernelGGL(beam_topk_chunks_pen_kernel<16>, dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, prefix_ids, ld_ids,
-                           cur_len, rp, stats, cval, cidx);
-        hipLaunchKernelGGL(beam_topk_merge_kernel<16>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
-    }
+    // rp == 1: the plain kernel, the prefix is neither checked nor read
+    if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
+    if (K <= 8) beam_topk_launch<8>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s);
+    else beam_topk_launch<16>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s);
     return hipGetLastError();
 }
 
-hipError_t launch_beam_step_nbest(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                                  int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s) {
-    if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
-    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
-    hipLaunchKernelGGL(beam_step_nbest_kernel, dim3(B), dim3(64), 0, s, st, n, cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
-                       length_penalty, cur);
-    return hipGetLastError();
+static BeamState beam_state(const BeamBuffers& bb) {
+    return BeamState{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
 }
 
-hipError_t launch_beam_finish_nbest(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
-                                    int64_t* first_decoded, float* first_logprobs, hipStream_t s) {
+hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s) {
     if (n < 1 || n > 16) return hipErrorInvalidValue;
-    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
-    hipLaunchKernelGGL(beam_finish_nbest_kernel, dim3(B, n), dim3(64), 0, s, st, n, max_len, eos, decoded, logprobs, first_decoded,
-                       first_logprobs);
+    hipLaunchKernelGGL(beam_init_kernel, dim3((B * std::max(beams, n) + 63) / 64), dim3(64), 0, s, beam_state(bb), B, beams, n, max_len, cls);
     return hipGetLastError();
 }
 
-hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int max_len, int cls, hipStream_t s) {
-    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
-    hipLaunchKernelGGL(beam_init_kernel, dim3((B * beams + 63) / 64), dim3(64), 0, s, st, B, beams, max_len, cls);
-    return hipGetLastError();
-}
-
-hipError_t launch_beam_step(const BeamBuffers& bb, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
+hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
                             int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s) {
-    if (beams > 16 || K > 16) return hipErrorInvalidValue;
-    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
-    hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, s, st, cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
-                       length_penalty, cur);
+    if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
+    if (n == 1)
+        hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
+                           length_penalty, cur);
+    else
+        hipLaunchKernelGGL(beam_step_nbest_kernel, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len, max_len,
+                           eos, length_penalty, cur);
     return hipGetLastError();
 }
 
-hipError_t launch_beam_finish(const BeamBuffers& bb, int B, int max_len, int eos, int64_t* decoded, float* logprobs, hipStream_t s) {
-    BeamState st{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
-    hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, st, max_len, eos, decoded, logprobs);
+hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                              int64_t* first_decoded, float* first_logprobs, hipStream_t s) {
+    if (n < 1 || n > 16) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(beam_finish_kernel, dim3(B, n), dim3(64), 0, s, beam_state(bb), n, max_len, eos, decoded, logprobs, first_decoded,
+                       first_logprobs);
     return hipGetLastError();
 }
 

@@ -703,7 +703,7 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
         }
         rc = text_forward(h, cur, ld, rows, t, 1, w.logits, nullptr, 0, nullptr, 0, s);
         if (rc) break;
-        hipError_t e = launch_beam_topk(w.logits, V, w.scores, B, k, V, k, w.cand_scores, w.cand_idx, w.topk_scratch, s);
+        hipError_t e = launch_beam_topk(w.logits, V, w.scores, nullptr, 0, 0, 1.0f, B, k, V, k, w.cand_scores, w.cand_idx, w.topk_scratch, s);
         if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
         hipLaunchKernelGGL(student_beam_step_kernel, dim3(B), dim3(64), 0, s, w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, k, V, t, ld);
         if (hipGetLastError() != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }

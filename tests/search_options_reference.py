@@ -135,6 +135,14 @@ def topk_cases():
     cols = [0, 2047, 2048, 30521, 28672, 28671, 15000, 101, 102, 20000, 9999]
     x = _spiked(rng, rows_b, Vb, [(b * beams_b + k % beams_b, c) for b in range(2) for k, c in enumerate(cols)], step=0.21)
     case("vocab30522", x, [[101, 30521, 2048, 28672, 102, 15000 + r] for r in range(rows_b)], 6, 1.5, beams_b, Kb)
+    # 10. K = 12: the 16-deep lists.  Three chunks, the last one 4 columns wide; penalised spikes at 2047, 2048 and V - 1; id 2053 is
+    # column 5 of chunk 1 while the spike at column 5 lies in chunk 0 (a chunk-relative reading would penalise it); columns
+    # 7 + r, 263 + r, 519 + r belong to one thread of the chunk kernel, so its list holds three of the winners
+    beams_k, Kk = 4, 12
+    rows_k = 2 * beams_k
+    x = _spiked(rng, rows_k, V, [(r, c) for c in (2047, 2048, V - 1, 5) for r in range(rows_k)] +
+                [(r, c + r) for c in (7, 263, 519, 3000) for r in range(rows_k)], step=0.043)
+    case("k12", x, [[2047, 2048, V - 1, 2053, 5]] * rows_k, 4, 1.5, beams_k, Kk)                # column 5 lies behind cur_len
     return cases
 
 

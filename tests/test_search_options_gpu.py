@@ -4,9 +4,12 @@
      indices exactly, scores within 1e-4 on inputs whose distinct candidate scores are more than 1e-3 apart -- the bar and the input
      condition of test_selection_gpu.py::test_beam_topk_vs_restatement; the fp32 penalty adds one rounding of a logit (~1e-6);
   b. gitcap_dbg_beam_step_nbest / _finish_nbest (with the penalised ranking) driven as a whole toy search against
-     oracle.search_oracle.beam_search(num_keep_best=, repetition_penalty=).
+     oracle.search_oracle.beam_search(num_keep_best=, repetition_penalty=);
+  c. both, and the one-hypothesis hooks gitcap_dbg_beam_step / _finish, against tests/golden/device_search_options.npz: the bits the
+     same hooks produced before the kernels behind them were unified (tools/gen_device_regression.py rewrites it).
 """
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -135,7 +138,7 @@ def _device_search(lib, table, beams, lp, n, rp, seen=None, old_hooks=False):
     d_table = table.cuda()
     clip = torch.arange(rows, device="cuda") // beams
     assert lib.gitcap_dbg_beam_init(ctypes.byref(bb1), B, beams, L, S.TOY_CLS, _stream()) == 0
-    t["hyp_len"].zero_()                                    # beam_init knows one slot per clip: all B * n are zeroed here
+    t["hyp_len"].zero_()                                    # the init hook passes n = 1 (one slot per clip): all B * n are zeroed here
     ids = [t["ids0"], t["ids1"]]
     cs = torch.empty(B, K, device="cuda")
     ci = torch.empty(B, K, device="cuda", dtype=torch.int32)
@@ -255,3 +258,45 @@ def test_nbest_finish_orders_equal_scores_by_storage_and_pads_empty_ranks(lib):
     torch.cuda.synchronize()
     assert dec[0].tolist() == [[0, 5, 6, 22, 22, 22], [0, 4, 22, 22, 22, 22], [0, 22, 22, 22, 22, 22], [22] * 6]
     assert lp[0].tolist() == [-0.5, -1.5, -1.5, -1e5]
+
+
+# ---- c. the recorded bits --------------------------------------------------------------------------------------------------------
+
+def _bits(t):
+    return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
+
+
+def _record(lib, toy_table):
+    rec = {}
+    for name in sorted(CASES):
+        for tag, plain in (("pen", False), ("plain", True)):
+            gs, gi = _run_pen(lib, CASES[name], plain=plain)
+            rec["topk_%s_%s_idx" % (tag, name)] = gi.cpu().numpy()
+            rec["topk_%s_%s_scores" % (tag, name)] = _bits(gs)
+    runs = [("n%d_b%d_lp%s_rp%s" % c, c, False) for c in S.toy_configs()]
+    runs += [("old_b%d_lp%s" % (c[1], c[2]), c, True) for c in S.toy_configs() if c[0] == 1 and c[3] == 1.0]
+    for key, (n, beams, lp, rp), old in runs:
+        decoded, logprobs, snaps = _device_search(lib, toy_table, beams, lp, n, rp, old_hooks=old)
+        last = snaps[-1]
+        rec["toy_%s_decoded" % key] = decoded.cpu().numpy()
+        rec["toy_%s_logprobs" % key] = _bits(logprobs)
+        rec["toy_%s_hyp_len" % key] = last["hyp_len"].cpu().numpy()
+        rec["toy_%s_done" % key] = last["done"].cpu().numpy()
+        rec["toy_%s_beam_scores" % key] = _bits(last["beam_scores"])
+    return rec
+
+
+def test_hooks_reproduce_the_recorded_parent_bits(lib, toy_table):
+    """Every top-k case (penalised and plain) and every toy search (n-best hooks; the one-hypothesis hooks where n = 1, rp = 1):
+    indices, ids and the bit patterns of every float equal the fixture.  GITCAP_WRITE_REGRESSION=dir writes it instead."""
+    rec = _record(lib, toy_table)
+    name = "device_search_options.npz"
+    wdir = os.environ.get("GITCAP_WRITE_REGRESSION")
+    if wdir:
+        os.makedirs(wdir, exist_ok=True)
+        np.savez_compressed(os.path.join(wdir, name), **rec)
+        return
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name))
+    assert sorted(g.files) == sorted(rec)
+    for k in sorted(rec):
+        assert g[k].dtype == rec[k].dtype and np.array_equal(g[k], rec[k]), k
