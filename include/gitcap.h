@@ -585,6 +585,49 @@ typedef struct gitcap_dbg_txt_block_args {
 } gitcap_dbg_txt_block_args;
 int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* a, void* stream);
 
+/* The TinyViT encoder's kernels (csrc/tinyvit.hip) and the student decoder's attention (csrc/student.hip), one kernel per hook on
+ * caller-owned device buffers (tests/test_encoder_kernels_gpu.py; a plain fp64 statement of each: tests/encoder_kernels_reference.py).
+ * No handle, no weight upload; GITCAP_ERR_ARG for arguments the launcher refuses, before any launch.  Activations are bf16.
+ *   tv_gemm:    out[m][n] = epi(A[m] . W[n] + bias[n]), A [M][lda], W [N][K], bias fp32 [N], res [M][ldr], out [M][ldo]; epi 0, 1 (erf-GELU),
+ *               2 (+ res), 2 | 4 (+ res, then erf-GELU); res may be out.  N % 4 == 0, K % 32 == 0, lda % 8 == 0, ldo % 4 == 0, ldr % 4 == 0.
+ *   tv_im2col:  the 3x3 stride-2 pad-1 patches of the stem convolutions: out [n * H/2 * W/2][Kp], column ci * 9 + ky * 3 + kx, zero for
+ *               columns >= 9 Cin; in: fp32 NCHW [n][Cin][H][W] (f32_nchw != 0) or bf16 NHWC [n][H][W][Cin].  H, W even, Kp >= 9 Cin.
+ *   tv_dwconv:  depthwise 3x3, pad 1, stride 1 or 2, + bias (+ erf-GELU): x [n][H][W][C] -> out [n][H/stride][W/stride][C]; w9 is the
+ *               device layout fp32 [9][C] (tap ky * 3 + kx major).  C % 8 == 0; stride 2 needs even H and W.
+ *   tv_ln:      LayerNorm of the rows of x [M][C] -> out [M][C]; g, b fp32 [C].  C % 8 == 0, C <= 2048.
+ *   tv_attn:    windowed attention of qkv [n * H * W][3 * 32 * heads] (head h's q | k | v at columns 96 h + {0, 32, 64}) -> ctx
+ *               [n * H * W][32 * heads], windows of ws x ws pixels, scale 32^-1/2.  attention_biases: the COMPACT checkpoint table, device
+ *               fp32 [heads][ws * ws]; the hook expands it to the dense [heads][ws^2][ws^2] table with the function
+ *               gitcap_tinyvit_finalize uses, launches, synchronises `stream` and frees the table.  1 <= ws <= 14, H % ws == W % ws == 0.
+ *   tv_pool:    mem fp32 [n][C] = the mean over the HW rows of x [n][HW][C].
+ *   tv_to_nchw: out fp32 [n][C][HW] = x [n][HW][C].
+ *   attn_small: a plain-C mirror of SmallAttnArgs (csrc/kernels.h), passed to launch_attn_small: query m = (r, j), r = m / T, reads q at
+ *               row r * q_row_stride + q_row_off + j (ldq columns per row), head h at columns h * hd; key / value i of row r at row
+ *               r * keys_stride + i of k / v (ldkv); nkeys > 0: keys 0 .. nkeys - 1, nkeys == 0: causal, keys 0 .. t0 + j; ids (nullable):
+ *               key i of row r is masked when ids[r * ld_ids + i] == pad_id (every key masked: NaN); ctx [M][ldc].  At most 64 keys,
+ *               hd % 8 == 0, hd <= 128, ldkv % 8 == 0. */
+int gitcap_dbg_tv_gemm(const void* A, int lda, const void* W, const float* bias, const void* res, int ldr, void* out, int ldo, int M,
+                       int N, int K, int epi, void* stream);
+int gitcap_dbg_tv_im2col(const void* in, int f32_nchw, void* out, int n, int H, int W, int Cin, int Kp, void* stream);
+int gitcap_dbg_tv_dwconv(const void* x, const float* w9, const float* bias, void* out, int n, int H, int W, int C, int stride, int gelu,
+                         void* stream);
+int gitcap_dbg_tv_ln(const void* x, const float* g, const float* b, void* out, int M, int C, float eps, void* stream);
+int gitcap_dbg_tv_attn(const void* qkv, const float* attention_biases, void* ctx, int n, int H, int W, int heads, int ws, void* stream);
+int gitcap_dbg_tv_pool(const void* x, float* mem, int n, int HW, int C, void* stream);
+int gitcap_dbg_tv_to_nchw(const void* x, float* out, int n, int HW, int C, void* stream);
+typedef struct gitcap_dbg_attn_small_args {
+    const void* q;
+    int32_t ldq, T, q_row_stride, q_row_off;
+    const void *k, *v;
+    int32_t ldkv, keys_stride, nkeys, t0;
+    const int64_t* ids;
+    int32_t ld_ids, pad_id;
+    void* ctx;
+    int32_t ldc;
+    int32_t M, H, hd;
+} gitcap_dbg_attn_small_args;
+int gitcap_dbg_attn_small(const gitcap_dbg_attn_small_args* a, void* stream);
+
 /* Residual stream of the ViT per block (tests/test_stress_layers_gpu.py: single-block checks on the device's own inputs).
  * While `buf` is non-NULL every SYNCHRONOUS image pass (gitcap_encode / _greedy / _beam_search and their _raw forms) copies
  * the fp32 residual stream x [rows][enc_width] (rows = B * F * tokens per frame, unpadded) to buf + e * rows * enc_width:

@@ -1668,8 +1668,6 @@ int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, 
 }
 
 // ---- token selection (tests/test_selection_gpu.py): each hook is ONE launcher on caller-owned device buffers --------------
-static int dbg_rc(hipError_t e) { return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP); }
-
 // launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
 static int dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
                           float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {

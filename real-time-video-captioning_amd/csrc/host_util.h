@@ -39,6 +39,9 @@ int fail(const H* h, int code, const std::string& msg) {
             return fail(h, GITCAP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
+// status of a gitcap_dbg_* hook from its launcher's: a launcher refuses arguments with hipErrorInvalidValue
+inline int dbg_rc(hipError_t e) { return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP); }
+
 // Makes a handle's device current for the duration of an entry point and restores the caller's.
 struct DeviceGuard {
     int prev = -1; bool ok = true;

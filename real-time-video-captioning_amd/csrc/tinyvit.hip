@@ -359,6 +359,26 @@ std::string tinyvit_check(const gitcap_tinyvit_config& c, int C[4], int map[4]) 
     return "";
 }
 
+// dense [heads][N][N] bias table of a ws x ws window (N = ws * ws) from the checkpoint's compact [heads][N] one: entry (p, q) is
+// attention_biases[h][idx(p, q)], idx = the order in which (|dy|, |dx|) first appears over points x points in row-major order
+std::vector<float> tv_dense_bias_table(const float* ab, int heads, int ws) {
+    const int N = ws * ws;
+    std::vector<int> idx((size_t)N * N);
+    std::map<std::pair<int, int>, int> first;
+    for (int p = 0; p < N; ++p)
+        for (int q = 0; q < N; ++q) {
+            const std::pair<int, int> off(std::abs(p / ws - q / ws), std::abs(p % ws - q % ws));
+            auto f = first.find(off);
+            const int id = f == first.end() ? (int)first.size() : f->second;
+            if (f == first.end()) first[off] = id;
+            idx[(size_t)p * N + q] = id;
+        }
+    std::vector<float> dense((size_t)heads * N * N);
+    for (int hh = 0; hh < heads; ++hh)
+        for (int e = 0; e < N * N; ++e) dense[(size_t)hh * N * N + e] = ab[(size_t)hh * N + idx[e]];
+    return dense;
+}
+
 }  // namespace
 
 extern "C" {
@@ -496,24 +516,10 @@ int gitcap_tinyvit_finalize(gitcap_tinyvit_t* h) {
             b.ln2g = (const float*)P(bp + "mlp.norm.weight"); b.ln2b = (const float*)P(bp + "mlp.norm.bias");
             b.fc1w = (const bf16_t*)P(bp + "mlp.fc1.weight"); b.fc1b = (const float*)P(bp + "mlp.fc1.bias");
             b.fc2w = (const bf16_t*)P(bp + "mlp.fc2.weight"); b.fc2b = (const float*)P(bp + "mlp.fc2.bias");
-            // dense bias table: entry (i, j) of a w x w window is attention_biases[h][idx(i, j)], idx = the order in which
-            // (|dy|, |dx|) first appears over points x points in row-major order
-            const int ws = c.window_sizes[i], N = ws * ws, heads = c.num_heads[i];
-            std::vector<int> idx((size_t)N * N);
-            std::map<std::pair<int, int>, int> first;
-            for (int p = 0; p < N; ++p)
-                for (int q = 0; q < N; ++q) {
-                    const std::pair<int, int> off(std::abs(p / ws - q / ws), std::abs(p % ws - q % ws));
-                    auto f = first.find(off);
-                    const int id = f == first.end() ? (int)first.size() : f->second;
-                    if (f == first.end()) first[off] = id;
-                    idx[(size_t)p * N + q] = id;
-                }
-            std::vector<float> ab((size_t)heads * N);
+            const int ws = c.window_sizes[i], heads = c.num_heads[i];
+            std::vector<float> ab((size_t)heads * ws * ws);
             HIP_OK(h, hipMemcpy(ab.data(), P(bp + "attn.attention_biases"), ab.size() * 4, hipMemcpyDeviceToHost));
-            std::vector<float> dense((size_t)heads * N * N);
-            for (int hh = 0; hh < heads; ++hh)
-                for (int e = 0; e < N * N; ++e) dense[(size_t)hh * N * N + e] = ab[(size_t)hh * N + idx[e]];
+            const std::vector<float> dense = tv_dense_bias_table(ab.data(), heads, ws);
             float* dt = nullptr;
             HIP_OK(h, hipMalloc(&dt, dense.size() * 4));
             h->tables.push_back(dt);
@@ -659,6 +665,103 @@ int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr
     if (n > h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: n exceeds max_frames");
     if ((int64_t)n * H * W * 3 > ((int64_t)1 << 40)) return fail(h, GITCAP_ERR_ARG, "tinyvit_encode_raw: sizes overflow");
     return tinyvit_encode(h, nullptr, frames_hwc_bgr, H, W, n, memory, fmaps, stream);
+}
+
+// ---- kernel-level test hooks (tests/test_encoder_kernels_gpu.py): each launches ONE kernel of this file (attn_small: of
+// student.hip) on caller-owned device buffers, no handle; what a wrong value of would index outside a buffer or misalign a vector
+// access is refused here, before any launch
+static bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
+
+int gitcap_dbg_tv_gemm(const void* A, int lda, const void* W, const float* bias, const void* res, int ldr, void* out, int ldo, int M,
+                       int N, int K, int epi, void* stream) {
+    if (!A || !W || !bias || !out || M <= 0 || N <= 0 || (N & 3) || K <= 0 || (K & 31) || lda < K || (lda & 7) || ldo < N || (ldo & 3) ||
+        (ldr & 3))
+        return GITCAP_ERR_ARG;
+    if (epi != 0 && epi != TV_GELU && epi != TV_RES && epi != (TV_RES | TV_RES_GELU)) return GITCAP_ERR_ARG;
+    if ((epi & TV_RES) && (!res || ldr < N || misaligned(res, 8))) return GITCAP_ERR_ARG;
+    if (misaligned(A, 16) || misaligned(W, 16) || misaligned(bias, 16) || misaligned(out, 8)) return GITCAP_ERR_ARG;
+    const TvGemmArgs a{(const bf16_t*)A, lda, (const bf16_t*)W, bias, (const bf16_t*)res, ldr, (bf16_t*)out, ldo, M, N, K};
+    return dbg_rc(tv_gemm(a, epi, (hipStream_t)stream));
+}
+
+int gitcap_dbg_tv_im2col(const void* in, int f32_nchw, void* out, int n, int H, int W, int Cin, int Kp, void* stream) {
+    if (!in || !out || n <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cin <= 0 || Kp < 9 * Cin || misaligned(in, f32_nchw ? 4 : 2) ||
+        misaligned(out, 2))
+        return GITCAP_ERR_ARG;
+    const int Ho = H / 2, Wo = W / 2;
+    const dim3 grid(grid_for((int64_t)n * Ho * Wo * Kp));
+    if (f32_nchw) hipLaunchKernelGGL(tv_im2col_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, n, H, W, Cin, Ho, Wo, Kp);
+    else hipLaunchKernelGGL(tv_im2col_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, n, H, W, Cin, Ho, Wo, Kp);
+    return dbg_rc(hipGetLastError());
+}
+
+int gitcap_dbg_tv_dwconv(const void* x, const float* w9, const float* bias, void* out, int n, int H, int W, int C, int stride, int gelu,
+                         void* stream) {
+    if (!x || !w9 || !bias || !out || n <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (stride != 1 && stride != 2) ||
+        (stride == 2 && ((H & 1) || (W & 1))) || misaligned(x, 16) || misaligned(w9, 16) || misaligned(bias, 4) || misaligned(out, 16))
+        return GITCAP_ERR_ARG;
+    const int Ho = H / stride, Wo = W / stride;
+    const dim3 grid(grid_for((int64_t)n * Ho * Wo * (C / 8)));
+    if (gelu) hipLaunchKernelGGL(tv_dwconv_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, w9, bias, (bf16_t*)out, n, H, W, C, stride, Ho, Wo);
+    else hipLaunchKernelGGL(tv_dwconv_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, w9, bias, (bf16_t*)out, n, H, W, C, stride, Ho, Wo);
+    return dbg_rc(hipGetLastError());
+}
+
+int gitcap_dbg_tv_ln(const void* x, const float* g, const float* b, void* out, int M, int C, float eps, void* stream) {
+    if (!x || !g || !b || !out || M <= 0 || C <= 0 || (C & 7) || C > 2048 || misaligned(x, 16) || misaligned(g, 4) || misaligned(b, 4) ||
+        misaligned(out, 16))
+        return GITCAP_ERR_ARG;
+    hipLaunchKernelGGL(tv_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, g, b, (bf16_t*)out, M, C, eps);
+    return dbg_rc(hipGetLastError());
+}
+
+// attention_biases: the compact checkpoint table, device fp32 [heads][ws * ws]; the dense table the kernel reads is built as
+// gitcap_tinyvit_finalize builds it and lives until the launch has finished (the call synchronises `stream`)
+int gitcap_dbg_tv_attn(const void* qkv, const float* attention_biases, void* ctx, int n, int H, int W, int heads, int ws, void* stream) {
+    if (!qkv || !attention_biases || !ctx || n <= 0 || heads <= 0 || ws < 1 || ws > 14 || H <= 0 || W <= 0 || H % ws || W % ws ||
+        misaligned(qkv, 16) || misaligned(attention_biases, 4) || misaligned(ctx, 16))
+        return GITCAP_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int N = ws * ws;
+    std::vector<float> ab((size_t)heads * N);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(ab.data(), attention_biases, ab.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return GITCAP_ERR_HIP;
+    const std::vector<float> dense = tv_dense_bias_table(ab.data(), heads, ws);
+    float* dt = nullptr;
+    if (hipMalloc(&dt, dense.size() * 4) != hipSuccess) return GITCAP_ERR_NOMEM;
+    hipError_t e = hipMemcpy(dt, dense.data(), dense.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(tv_attn_kernel, dim3(n * (H / ws) * (W / ws), heads), dim3((N + 63) / 64 * 64), 0, s, (const bf16_t*)qkv, dt,
+                           (bf16_t*)ctx, H, W, heads * 32, ws, 0.17677669529663687f);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    (void)hipFree(dt);
+    return dbg_rc(e != hipSuccess ? e : es);
+}
+
+int gitcap_dbg_tv_pool(const void* x, float* mem, int n, int HW, int C, void* stream) {
+    if (!x || !mem || n <= 0 || HW <= 0 || C <= 0 || misaligned(x, 2) || misaligned(mem, 4)) return GITCAP_ERR_ARG;
+    hipLaunchKernelGGL(tv_pool_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, mem, HW, C);
+    return dbg_rc(hipGetLastError());
+}
+
+int gitcap_dbg_tv_to_nchw(const void* x, float* out, int n, int HW, int C, void* stream) {
+    if (!x || !out || n <= 0 || HW <= 0 || C <= 0 || misaligned(x, 2) || misaligned(out, 4)) return GITCAP_ERR_ARG;
+    hipLaunchKernelGGL(tv_to_nchw_kernel, dim3(grid_for((int64_t)n * HW * C)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, out, n, HW, C);
+    return dbg_rc(hipGetLastError());
+}
+
+// the student decoder's attention (student.hip: attn_small_kernel) through its launcher; the struct mirrors SmallAttnArgs
+int gitcap_dbg_attn_small(const gitcap_dbg_attn_small_args* g, void* stream) {
+    if (!g || !g->q || !g->k || !g->v || !g->ctx || g->T <= 0 || g->M <= 0 || g->M % g->T || g->H <= 0 || g->hd <= 0 || g->nkeys < 0 ||
+        g->t0 < 0 || g->q_row_stride < 0 || g->q_row_off < 0 || g->keys_stride < 0 || g->ldq < g->H * g->hd || g->ldkv < g->H * g->hd ||
+        (g->ldkv & 7) || g->ldc < g->H * g->hd || (g->ids && g->ld_ids < (g->nkeys > 0 ? g->nkeys : g->t0 + g->T)) || misaligned(g->q, 2) ||
+        misaligned(g->k, 16) || misaligned(g->v, 2) || misaligned(g->ids, 8) || misaligned(g->ctx, 2))
+        return GITCAP_ERR_ARG;
+    const SmallAttnArgs a{(const bf16_t*)g->q, g->ldq, g->T, g->q_row_stride, g->q_row_off, (const bf16_t*)g->k, (const bf16_t*)g->v,
+                          g->ldkv, g->keys_stride, g->nkeys, g->t0, g->ids, g->ld_ids, g->pad_id, (bf16_t*)g->ctx, g->ldc, g->M, g->H, g->hd};
+    return dbg_rc(launch_attn_small(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -54,6 +54,14 @@ class CDbgTxtBlockArgs(ctypes.Structure):
                 ("v8_pitch", c_int64), ("nt_kv", c_int32)]
 
 
+class CDbgAttnSmallArgs(ctypes.Structure):
+    """struct gitcap_dbg_attn_small_args (include/gitcap.h): SmallAttnArgs of csrc/kernels.h, field for field."""
+    _fields_ = [("q", c_void_p), ("ldq", c_int32), ("T", c_int32), ("q_row_stride", c_int32), ("q_row_off", c_int32), ("k", c_void_p),
+                ("v", c_void_p), ("ldkv", c_int32), ("keys_stride", c_int32), ("nkeys", c_int32), ("t0", c_int32), ("ids", c_void_p),
+                ("ld_ids", c_int32), ("pad_id", c_int32), ("ctx", c_void_p), ("ldc", c_int32), ("M", c_int32), ("H", c_int32),
+                ("hd", c_int32)]
+
+
 # every symbol include/gitcap.h declares (tests/test_cabi.py checks the list against the header)
 SYMBOLS = {
     "gitcap_abi_version": (c_int, []),
@@ -137,6 +145,16 @@ SYMBOLS = {
     "gitcap_dbg_ffn_txt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                    c_void_p]),
     "gitcap_dbg_txt_block": (c_int, [POINTER(CDbgTxtBlockArgs), c_void_p]),
+    # encoder kernel hooks (tests/test_encoder_kernels_gpu.py)
+    "gitcap_dbg_tv_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p]),
+    "gitcap_dbg_tv_im2col": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_tv_dwconv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_tv_ln": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "gitcap_dbg_tv_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_tv_pool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_tv_to_nchw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_attn_small": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     # search options of the device-resident search: n-best hypotheses, repetition penalty (tests/test_search_options_gpu.py)

@@ -80,9 +80,10 @@ def test_ctypes_structs_mirror_the_header_field_order():
 
 
 def test_debug_hook_structs_mirror_the_header_field_order():
-    """The text-row hooks' argument structs (pointer fields: the names behind the stars)."""
+    """The text-row and attn_small hooks' argument structs (pointer fields: the names behind the stars)."""
     txt = open(os.path.join(ROOT, "include", "gitcap.h")).read()
-    for name, cls in (("gitcap_dbg_skinny_args", _lib.CDbgSkinnyArgs), ("gitcap_dbg_txt_block_args", _lib.CDbgTxtBlockArgs)):
+    for name, cls in (("gitcap_dbg_skinny_args", _lib.CDbgSkinnyArgs), ("gitcap_dbg_txt_block_args", _lib.CDbgTxtBlockArgs),
+                      ("gitcap_dbg_attn_small_args", _lib.CDbgAttnSmallArgs)):
         body = re.search(r"struct\s+%s\s*\{(.*?)\}\s*\w*\s*;" % name, txt, flags=re.S).group(1)
         assert re.findall(r"(\w+)\s*(?=[,;])", body) == [f for f, _ in cls._fields_], name
 
