@@ -352,6 +352,55 @@ int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_sc
                                int cur_len, float repetition_penalty, int B, int beams, int V, int K,
                                float* out_scores, int32_t* out_idx, void* stream);
 
+/* Sampling on the device: the do_sample branch of the reference's search operator (model.py:532-554: temperature,
+ * top_k_top_p_filtering with min_tokens_to_keep = 2, per_node_beam_size draws per beam row) in place of the K best candidates.  A
+ * ONE-SHOT attachment with the life cycle of gitcap_attach_search_options: consumed by the NEXT beam-family call whether it succeeds
+ * or is refused; it combines with a pending gitcap_attach_search_options (n-best, penalty; either may come first); opt == NULL detaches.
+ * The draw is a contract of this library (torch.multinomial's stream cannot be reproduced):
+ *   random numbers  Philox4x32-10, key = (seed low word, seed high word), counter = (v / 4, row, cur_len, 0) for column v of row
+ *                   row = b * beams + j at step cur_len; output lane v % 4 is column v's; u = ((x >> 8) + 0.5) * 2^-24, strictly inside
+ *                   (0, 1).  No state, no host round trip: a caption depends on (seed, the clip's position in the batch, logits) only,
+ *                   not on the entry point or the pipeline slot.  A clip's draws DO depend on its position in the batch.
+ *   the row         raw logits, penalised at the prefix columns (gitcap_search_options), divided by temperature when it is not 1,
+ *                   filtered, log-softmax of the filtered row.
+ *   the filter      top_k > 0: k' = min(max(top_k, 2), V), every column below the k'-th largest value is dropped, ties with it stay.
+ *                   top_p < 1, on the softmax of the top-k-filtered row: column v stays iff fewer than 3 columns are strictly greater
+ *                   or the probability mass of the strictly greater columns is <= top_p (ranks 0, 1, 2 of the reference's sort stay
+ *                   unconditionally).  Columns of equal value share one fate: the reference's choice among equal values is the order
+ *                   its sort happens to leave them in, which is no contract.  -inf columns are never kept.
+ *   the draw        the per_node_beam_size largest of key_v = z_v - log(-log u_v) over the kept columns (z: the filtered row), in
+ *                   descending key order, ties to the smaller column: sampling without replacement, the distribution of
+ *                   torch.multinomial(softmax(z), replacement=False).  score = log_softmax(z)[word] + beam_score[row].
+ *   candidates      clip b has K = beams * per_node_beam_size, UNSORTED: candidate p is draw p % per_node_beam_size of row
+ *                   b * beams + p / per_node_beam_size with flat index (p % beams) * V + word (model.py:549-552 tiles the beam offsets
+ *                   over the row; kept as written).  The bookkeeping takes the maximum of the K scores for the done test, walks the
+ *                   candidates as given and pads only the missing beams of a clip left with fewer than `beams` live ones.
+ * The same inputs give the same bits run to run (every sum has a fixed order).  step_logits_out stays the raw logits.
+ * Errors: GITCAP_ERR_ARG for a temperature that is not finite and > 0, top_k < 0, top_p outside (0, 1]; at the consuming call for a
+ * per_node_beam_size greater than the columns the filter is sure to keep -- per_node_beam_size > 2 with top_p < 1, or
+ * 0 < max(top_k, 2) < per_node_beam_size -- or on a handle whose vocabulary is wider than 32768 columns (the kernel holds a row in
+ * LDS), with nothing launched (the attachment is consumed all the same).
+ * Preconditions: a row offers at least per_node_beam_size finite logits (a row that runs out of kept columns yields sentinel
+ * candidates, which the bookkeeping passes over: the clip then continues with fewer live beams, padded as above).
+ * Memory: none.  A handle that never attaches runs exactly the launches it ran before. */
+typedef struct gitcap_sampling_options {
+    float    temperature;   /* finite, > 0 */
+    int32_t  top_k;         /* >= 0; 0 = off */
+    float    top_p;         /* (0, 1]; 1 = off */
+    uint64_t seed;
+} gitcap_sampling_options;
+int gitcap_attach_sampling(gitcap_t* h, const gitcap_sampling_options* opt);
+
+/* The stateless row call behind it, beside gitcap_beam_topk / gitcap_beam_topk_penalized: logits device fp32 [B*beams][ld], prefix_ids
+ * as gitcap_beam_topk_penalized (read only when repetition_penalty != 1), out_scores fp32 / out_idx int32 [B][beams * per_node] in
+ * the candidate layout above; kept_out (nullable) int32 [B*beams]: the columns the filter kept; logz_out (nullable) fp32 [B*beams]:
+ * the log-sum-exp of the filtered row.  A row with fewer than per_node kept columns fills the rest with (-inf, 0x7fffffff).
+ * GITCAP_ERR_ARG as gitcap_beam_topk (beams > 16, beams * per_node > 16, per_node > V, ld < V), for V > 32768 (the row is held in
+ * the CU's LDS) and for the values gitcap_attach_sampling refuses. */
+int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int32_t top_k, float top_p,
+                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream);
+
 /* Host-side staging copy for host-fed callers (no reference counterpart): bytes from pageable memory (a DataLoader batch without
  * pin_memory, OpenCV frames) into a page-locked staging buffer, split over up to 8 threads -- as many as the process may really use
  * (affinity mask, cgroup CPU quota; GITCAP_HOST_COPY_THREADS overrides).  Plain memcpy semantics, blocking, no device work.
@@ -513,6 +562,9 @@ int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* bb, const fl
                                int beams, int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
 int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* bb, int B, int max_len, int eos, int64_t* decoded,
                                  float* logprobs, void* stream);
+/* gitcap_dbg_beam_step_nbest for UNSORTED candidates (gitcap_attach_sampling: candidates), any n in [1, 16]. */
+int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* bb, const float* cand_scores, const int32_t* cand_idx, int B,
+                                 int beams, int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
 
 /* The text-row kernels of the token loop, one launcher per hook on caller-owned device buffers (tests/test_text_rows_gpu.py; a
  * plain fp64 statement of each: tests/text_rows_reference.py).  No allocation, no handle; GITCAP_ERR_ARG for arguments a launcher

@@ -67,7 +67,9 @@ struct DecLayer {
 }  // namespace
 
 // Options of one device-resident search (gitcap_attach_search_options): hypotheses kept per clip, repetition penalty, n-best outputs.
-struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; };
+// smp: the sampling branch (gitcap_attach_sampling), pending beside the options above and consumed with them.
+struct SampleOpt { bool on = false; float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; uint64_t seed = 0; };
+struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; SampleOpt smp{}; };
 
 struct gitcap : HandleCore {
     gitcap_config c;
@@ -1272,9 +1274,15 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : sl.beam_logits;
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
-        HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
-                                   sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
-        HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s));
+        if (so.smp.on)                                                       // model.py:532-554: K draws instead of the K best
+            HIP_OK(h, launch_sample_rows(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V,
+                                         per_node_beam_size, so.smp.temperature, so.smp.top_k, so.smp.top_p, so.smp.seed, sl.cand_scores,
+                                         sl.cand_idx, nullptr, nullptr, s));
+        else
+            HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
+                                       sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+        HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s,
+                                   so.smp.on));
     }
     HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
     return 0;
@@ -1303,6 +1311,11 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
     if (per_node_beam_size < 2) return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size must be >= 2 (model.py:606)");
     if (so.n > beams * per_node_beam_size)
         return fail(h, GITCAP_ERR_ARG, "beam_search: the attached num_keep_best exceeds beams * per_node_beam_size");
+    // a row must be left with per_node_beam_size columns to draw: the filter guarantees max(top_k, 2) under top_k and 2 under top_p
+    if (so.smp.on && ((so.smp.top_p < 1.0f && per_node_beam_size > 2) ||
+                      (so.smp.top_k > 0 && std::max(so.smp.top_k, 2) < per_node_beam_size) || per_node_beam_size > h->c.vocab_size))
+        return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep");
+    if (so.smp.on && h->c.vocab_size > 32768) return fail(h, GITCAP_ERR_ARG, "beam_search: sampling takes a vocabulary of at most 32768 columns");
     return body(so);
 }
 
@@ -1463,7 +1476,8 @@ int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
 
 int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_search_options: null handle");
-    if (!opt) { h->so_attach = SearchOpt{}; return 0; }
+    const SampleOpt smp = h->so_attach.smp;                  // a pending gitcap_attach_sampling stays pending
+    if (!opt) { h->so_attach = SearchOpt{}; h->so_attach.smp = smp; return 0; }
     if (opt->num_keep_best < 1 || opt->num_keep_best > 16)
         return fail(h, GITCAP_ERR_ARG, "attach_search_options: num_keep_best outside [1, 16]");
     if (!(opt->repetition_penalty > 0.f) || !std::isfinite(opt->repetition_penalty))
@@ -1482,7 +1496,18 @@ int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) 
             if (rc) { h->slots[0].nb_len = nullptr; return rc; }
         }
     }
-    h->so_attach = SearchOpt{opt->num_keep_best, opt->repetition_penalty, opt->nbest_out, opt->nbest_logprobs_out};
+    h->so_attach = SearchOpt{opt->num_keep_best, opt->repetition_penalty, opt->nbest_out, opt->nbest_logprobs_out, smp};
+    return 0;
+}
+
+int gitcap_attach_sampling(gitcap_t* h, const gitcap_sampling_options* opt) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_sampling: null handle");
+    if (!opt) { h->so_attach.smp = SampleOpt{}; return 0; }
+    if (!(opt->temperature > 0.f) || !std::isfinite(opt->temperature))
+        return fail(h, GITCAP_ERR_ARG, "attach_sampling: temperature must be finite and > 0");
+    if (opt->top_k < 0) return fail(h, GITCAP_ERR_ARG, "attach_sampling: top_k must be >= 0");
+    if (!(opt->top_p > 0.f) || !(opt->top_p <= 1.0f)) return fail(h, GITCAP_ERR_ARG, "attach_sampling: top_p outside (0, 1]");
+    h->so_attach.smp = SampleOpt{true, opt->temperature, opt->top_k, opt->top_p, opt->seed};
     return 0;
 }
 
@@ -1561,6 +1586,16 @@ int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_sc
     if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
     if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
     return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream);
+}
+
+int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream) {
+    if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || per_node <= 0) return GITCAP_ERR_ARG;
+    if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)kept_out & 3) != 0 || ((uintptr_t)logz_out & 3) != 0) return GITCAP_ERR_ARG;
+    const hipError_t e = launch_sample_rows(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node,
+                                            temperature, top_k, top_p, seed, out_scores, out_idx, kept_out, logz_out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
 
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
@@ -1798,6 +1833,16 @@ int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, const flo
         return GITCAP_ERR_ARG;
     return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
                                    (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                                 int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
+        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
+                                   (hipStream_t)stream, true));
 }
 
 int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,

@@ -290,7 +290,16 @@ struct BeamBuffers {
 // slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes all B * n).  step: n = 1 runs beam_step_kernel, n > 1 the n-slot kernel.
 // finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_*: rank 0 again as [B][max_len] / [B]; all nullable.
 hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s);
+// sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates are
+// walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
 hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s);
+                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled = false);
+// the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
+// (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
+// candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (rowops.hip).
+// kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
+hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                              float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
+                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s);
 hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
                               int64_t* first_decoded, float* first_logprobs, hipStream_t s);

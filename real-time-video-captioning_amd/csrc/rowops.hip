@@ -679,6 +679,206 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float2* __res
     }
 }
 
+// ---- sampled candidates: the do_sample branch of the search (model.py:532-554) ----------------------------------------------------
+// One 1024-thread workgroup per row, the row in LDS (V fp32 of dynamic LDS, V <= 32768: 128 of the CU's 160 KB); thread t owns columns
+// t, t + 1024, ... and is the only one to touch them, so the row needs no barrier of its own and the accesses are conflict free.
+// Rows are few -- 64 at the configs[4] shape -- but every decision below needs a statistic of the WHOLE row, and the bisections need
+// ~64 of them in sequence: chunk workgroups (beam_topk's shape) would pay a grid-wide hand-off per statistic, one workgroup pays a
+// barrier.  Registers cannot hold the row (32 columns per thread beside the filter's temporaries do not fit the 128 VGPRs of a
+// 16-wave workgroup); LDS does, and the loops over it stay rolled.
+//   row:    raw logit, penalised when its column occurs in the row's prefix (the rule of beam_topk_chunks_kernel<.., true>: once per
+//           column, ids outside [0, V) match nothing), divided by the temperature when it is not 1, -0 made +0.
+//   top_k:  k' = min(max(top_k, 2), V); T = the k'-th largest value, found by bisection on the order-preserving integer image of
+//           fp32 (32 counting passes, integer sums); columns below T become -inf, ties with T stay.
+//   top_p:  on the softmax of that row: column v stays iff fewer than 3 columns are strictly greater or the mass of the strictly
+//           greater columns is <= top_p.  Both conditions are monotone in the value, so the kept set is {x >= t*}; t* by bisection,
+//           each pass one count and one mass sum.  Columns of equal value share one fate (the oracle's choice among equal values is
+//           the order its sort leaves them in, which is no contract).  -inf is never kept.
+//   draw:   u_v from Philox4x32-10, key (seed_lo, seed_hi), counter (v / 4, row, cur_len, 0), lane v % 4: u = ((x >> 8) + 0.5) 2^-24.
+//           With n = x >> 8: n < 2^23 makes u exact in fp32 and E = -logf(u); otherwise 1 - u = ((2^24 - 1 - n) + 0.5) 2^-24 is exact
+//           and E = -log1pf(-(1 - u)) (u itself would round to 1 at the top of the range).  key_v = z_v - logf(E_v) over the kept
+//           columns, written over the row; the pn largest keys, descending, ties to the smaller column, are the draws: sampling
+//           without replacement.  The logit of a drawn column is computed again from the raw row (the same operations: the same bits).
+//   score:  (z_w - logZ) + beam_score[row], logZ = M + logf(sum of expf(z - M) over the kept columns).
+// Every sum is a per-thread sum in column order, a wave butterfly and 16 partials added in wave order: the same bits every run.
+// Candidate p = j * pn + d of clip b is draw d of row b * beams + j, flat index (p % beams) * V + word (model.py:549-552 tiles the
+// beam offsets over the row; kept as the host operator has it).  A row with fewer than pn kept columns fills the rest with the
+// sentinel (-inf, 0x7fffffff), which beam_step_nbest_kernel<true> passes over.
+constexpr int SR_THREADS = 1024, SR_WAVES = SR_THREADS / 64, SR_MAX_V = 32768;
+
+__device__ __forceinline__ unsigned f32_ord(float x) {
+    const unsigned b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned philox4x32_10_lane(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, int lane) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c2 : c3;
+}
+
+// column i of the row as the filter sees it: penalty, temperature, -0 -> +0 (one integer image per value)
+__device__ __forceinline__ float sr_logit(const float* __restrict__ src, int i, const int64_t* __restrict__ pre, int cur_len, float rp,
+                                          float temperature) {
+    float v = src[i];
+    if (rp != 1.0f) {
+        bool hit = false;
+        for (int t = 0; t < cur_len; ++t) hit |= pre[t] == (int64_t)i;
+        if (hit) v = v < 0.f ? v * rp : v / rp;
+    }
+    if (temperature != 1.0f) v = v / temperature;
+    if (v == 0.f) v = 0.f;
+    return v;
+}
+
+struct SrRed { float f[2][SR_WAVES]; int i[2][SR_WAVES]; };
+
+// block sums of (f, i) in a fixed order; one barrier per call (the two halves of SrRed alternate)
+__device__ __forceinline__ void sr_block_sum(SrRed& r, int& phase, float& f, int& i) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    f = wave_sum(f);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) i += __shfl_xor(i, o);
+    if (lane == 0) { r.f[phase][wid] = f; r.i[phase][wid] = i; }
+    __syncthreads();
+    float fs = 0.f;
+    int is = 0;
+#pragma unroll
+    for (int w = 0; w < SR_WAVES; ++w) { fs += r.f[phase][w]; is += r.i[phase][w]; }
+    f = fs; i = is;
+    phase ^= 1;
+}
+
+__global__ __launch_bounds__(SR_THREADS) void sample_rows_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                 const float* __restrict__ beam_scores,
+                                                                 const int64_t* __restrict__ prefix_ids, int ld_ids, int cur_len, float rp,
+                                                                 int beams, int pn, float temperature, int top_k, float top_p,
+                                                                 unsigned seed_lo, unsigned seed_hi, float* __restrict__ out_scores,
+                                                                 int* __restrict__ out_idx, int* __restrict__ kept_out,
+                                                                 float* __restrict__ logz_out) {
+    extern __shared__ float sr_row[];                                    // [V]: the row, later its keys
+    __shared__ SrRed red;
+    __shared__ float s_bk[2][SR_WAVES];
+    __shared__ int s_bi[2][SR_WAVES];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const float* src = logits + (size_t)row * ld;
+    const int64_t* pre = rp != 1.0f ? prefix_ids + (size_t)row * ld_ids : nullptr;
+    int phase = 0;
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += SR_THREADS) {
+        const float v = sr_logit(src, i, pre, cur_len, rp, temperature);
+        sr_row[i] = v;
+        m = fmaxf(m, v);
+    }
+    m = wave_max(m);
+    if (lane == 0) red.f[phase][wid] = m;
+    __syncthreads();
+    m = red.f[phase][0];
+#pragma unroll
+    for (int w = 1; w < SR_WAVES; ++w) m = fmaxf(m, red.f[phase][w]);
+    phase ^= 1;
+
+    if (top_k > 0) {
+        const int kk = min(max(top_k, 2), V);
+        unsigned T = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = T | (1u << bit);
+            int c = 0;
+            float unused = 0.f;
+            for (int i = tid; i < V; i += SR_THREADS) c += f32_ord(sr_row[i]) >= cand;
+            sr_block_sum(red, phase, unused, c);
+            if (c >= kk) T = cand;
+        }
+        for (int i = tid; i < V; i += SR_THREADS)
+            if (f32_ord(sr_row[i]) < T) sr_row[i] = -INFINITY;
+    }
+
+    unsigned tstar = 0u;
+    if (top_p < 1.0f) {
+        float Z = 0.f;
+        int unused = 0;
+        for (int i = tid; i < V; i += SR_THREADS) { const float x = sr_row[i]; Z += x == -INFINITY ? 0.f : expf(x - m); }
+        sr_block_sum(red, phase, Z, unused);
+        const float lim = top_p * Z;
+        unsigned L = 0u;
+        bool all = false;
+        for (int it = -1; it < 32; ++it) {                               // f(t) = fewer than 3 above t, or their mass <= top_p Z
+            const unsigned cand = it < 0 ? 0u : (L | (1u << (31 - it)));
+            int c = 0;
+            float mass = 0.f;
+            for (int i = tid; i < V; i += SR_THREADS) {
+                const float x = sr_row[i];
+                const bool above = f32_ord(x) > cand;
+                c += above;
+                mass += above && x != -INFINITY ? expf(x - m) : 0.f;
+            }
+            sr_block_sum(red, phase, mass, c);
+            const bool ok = c < 3 || mass <= lim;
+            if (it < 0) { if (ok) { all = true; break; } }
+            else if (!ok) L = cand;
+        }
+        tstar = all ? 0u : L + 1u;                                       // the smallest t with f(t): L is the largest without
+    }
+
+    float S = 0.f;
+    int kept = 0;
+    for (int i = tid; i < V; i += SR_THREADS) {
+        const float x = sr_row[i];
+        const bool keep = x != -INFINITY && f32_ord(x) >= tstar;
+        kept += keep;
+        S += keep ? expf(x - m) : 0.f;
+        float k = -INFINITY;
+        if (keep) {
+            const unsigned n = philox4x32_10_lane((unsigned)i >> 2, (unsigned)row, (unsigned)cur_len, 0u, seed_lo, seed_hi, i & 3) >> 8;
+            const float E = n < (1u << 23) ? -logf(((float)n + 0.5f) * 0x1p-24f)
+                                           : -log1pf(-(((float)((1u << 24) - 1u - n) + 0.5f) * 0x1p-24f));
+            k = x - logf(E);
+        }
+        sr_row[i] = k;                                                   // the row becomes its keys
+    }
+    sr_block_sum(red, phase, S, kept);
+    const float logZ = m + logf(S);
+    if (tid == 0) {
+        if (kept_out) kept_out[row] = kept;
+        if (logz_out) logz_out[row] = logZ;
+    }
+
+    const int b = row / beams, j = row - b * beams, K = beams * pn;
+    for (int d = 0; d < pn; ++d) {
+        float bk = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = tid; i < V; i += SR_THREADS) {                      // ascending columns: strict > keeps the smaller
+            const float k = sr_row[i];
+            if (k > bk) { bk = k; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float k2 = __shfl_xor(bk, o);
+            const int i2 = __shfl_xor(bi, o);
+            if (k2 > bk || (k2 == bk && i2 < bi)) { bk = k2; bi = i2; }
+        }
+        const int ph = d & 1;
+        if (lane == 0) { s_bk[ph][wid] = bk; s_bi[ph][wid] = bi; }
+        __syncthreads();
+        bk = s_bk[ph][0]; bi = s_bi[ph][0];
+#pragma unroll
+        for (int w = 1; w < SR_WAVES; ++w)
+            if (s_bk[ph][w] > bk || (s_bk[ph][w] == bk && s_bi[ph][w] < bi)) { bk = s_bk[ph][w]; bi = s_bi[ph][w]; }
+        const bool none = bi == 0x7fffffff;
+        if (tid == 0) {
+            const int p = j * pn + d;
+            out_scores[(size_t)b * K + p] = none ? -INFINITY : (sr_logit(src, bi, pre, cur_len, rp, temperature) - logZ) + beam_scores[row];
+            out_idx[(size_t)b * K + p] = none ? 0x7fffffff : (p % beams) * V + bi;
+        }
+        if (!none && (bi & (SR_THREADS - 1)) == tid) sr_row[bi] = -INFINITY;    // the owner retires the drawn column
+    }
+}
+
 // ---- device-side beam bookkeeping: one step of GeneratorWithBeamSearchV2.search (model.py:573-621) -----
 // One block per batch element; thread 0 walks the <= 16 sorted candidates exactly like the reference's
 // Python loop (finished hypotheses kept n_best = 1: score = sum_logprob / len^length_penalty, :503, :592-594;
@@ -762,7 +962,10 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamState st, const float
 // One wave per clip.  Thread 0 walks the <= 16 sorted candidates as beam_step_kernel does and posts what to store (s_cmd); the
 // wave moves the ids (lane t owns column t of every slot, so the slots of a shift need no barrier between them).  n = 1 never
 // gets here: launch_beam_step sends it to beam_step_kernel, which the n-slot kernel does not match for speed (5.7 against 6.0 us
-// per call at the configs[4] shape); the two are the parent's code to the instruction.
+// per call at the configs[4] shape).  SAMPLED: the candidates are draws in no order (sample_rows_kernel): the done test takes the
+// maximum of the K scores, sentinel candidates are passed over, and a clip left with 0 < kept < beams live beams pads only the
+// missing ones.  <false> has the registers, scratch and occupancy of the kernel before it was a template (profiles/).
+template <bool SAMPLED>
 __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n, const float* __restrict__ cand_scores,
                                                              const int* __restrict__ cand_idx, int beams, int K, int V,
                                                              int cur_len, int max_len, int eos, float length_penalty, int cur) {
@@ -790,7 +993,10 @@ __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n
         if (!done && cnt == n) {                                          // BeamHypotheses.is_done(best_sum_logprobs)
             float worst = s_hs[0];
             for (int i = 1; i < n; ++i) worst = fminf(worst, s_hs[i]);
-            done = worst >= cs[0] / powf((float)(max_len - 1), length_penalty);
+            float best = cs[0];
+            if constexpr (SAMPLED)
+                for (int c = 1; c < K; ++c) best = fmaxf(best, cs[c]);    // (a sentinel's -inf never wins)
+            done = worst >= best / powf((float)(max_len - 1), length_penalty);
         }
     }
     for (int c = 0; c < K; ++c) {
@@ -798,6 +1004,7 @@ __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n
             int cmd = -2;                                                 // -2: nothing to store; -1: stop; n: append; e < n: delete slot e, append
             if (done || kept >= beams) {
                 cmd = -1;
+            } else if (SAMPLED && ci[c] == 0x7fffffff) {                  // a row that ran out of columns: no candidate
             } else {
                 const int beam_id = ci[c] / V, word = ci[c] - beam_id * V;
                 if (word == eos || cur_len + 1 == max_len) {              // finished hypothesis: ids[:cur_len]
@@ -846,7 +1053,7 @@ __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n
     }
     if (tid == 0) {
         if (kept < beams) {                                               // done, or the last step: pad (0, eos, row 0)
-            for (int j = 0; j < beams; ++j) {
+            for (int j = SAMPLED ? kept : 0; j < beams; ++j) {            // (SAMPLED: EOS was drawn often -- only the missing beams)
                 s_src[j] = 0; s_word[j] = eos;
                 st.beam_scores[b * beams + j] = 0.f;
             }
@@ -1057,6 +1264,19 @@ hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_score
     return hipGetLastError();
 }
 
+hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                              float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
+                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s) {
+    if (B <= 0 || beams <= 0 || beams > 16 || pn <= 0 || beams * pn > 16 || pn > V || V > SR_MAX_V || ld < V || cur_len < 0) return hipErrorInvalidValue;
+    if (!(temperature > 0.f) || !std::isfinite(temperature) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f)) return hipErrorInvalidValue;
+    if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
+    if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel>(SR_MAX_V * 4); e != hipSuccess) return e;
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids, ld_ids,
+                       cur_len, rp, beams, pn, temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), out_scores, out_idx,
+                       kept_out, logz_out);
+    return hipGetLastError();
+}
+
 static BeamState beam_state(const BeamBuffers& bb) {
     return BeamState{{bb.ids0, bb.ids1}, bb.beam_scores, bb.words, bb.src_rows, bb.done, bb.hyp_len, bb.hyp_score, bb.hyp_ids};
 }
@@ -1068,14 +1288,17 @@ hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int 
 }
 
 hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s) {
+                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled) {
     if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
-    if (n == 1)
+    if (sampled)
+        hipLaunchKernelGGL(beam_step_nbest_kernel<true>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
+                           max_len, eos, length_penalty, cur);
+    else if (n == 1)
         hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
                            length_penalty, cur);
     else
-        hipLaunchKernelGGL(beam_step_nbest_kernel, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len, max_len,
-                           eos, length_penalty, cur);
+        hipLaunchKernelGGL(beam_step_nbest_kernel<false>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
+                           max_len, eos, length_penalty, cur);
     return hipGetLastError();
 }
 

@@ -35,6 +35,11 @@ class CSearchOptions(ctypes.Structure):
     _fields_ = [("num_keep_best", c_int32), ("repetition_penalty", c_float), ("nbest_out", c_void_p), ("nbest_logprobs_out", c_void_p)]
 
 
+class CSamplingOptions(ctypes.Structure):
+    """struct gitcap_sampling_options (include/gitcap.h)."""
+    _fields_ = [("temperature", c_float), ("top_k", c_int32), ("top_p", c_float), ("seed", ctypes.c_uint64)]
+
+
 class CDbgSkinnyArgs(ctypes.Structure):
     """struct gitcap_dbg_skinny_args (include/gitcap.h)."""
     _fields_ = [("X", c_void_p), ("ldx", c_int32), ("W", c_void_p), ("Wpk", c_void_p), ("wscale", c_void_p), ("bias", c_void_p),
@@ -164,6 +169,12 @@ SYMBOLS = {
     "gitcap_dbg_beam_step_nbest": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                            c_int, c_float, c_int, c_void_p]),
     "gitcap_dbg_beam_finish_nbest": (c_int, [POINTER(CDbgBeamBuffersNbest), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # sampling on the device (tests/test_sampling_gpu.py)
+    "gitcap_attach_sampling": (c_int, [c_void_p, POINTER(CSamplingOptions)]),
+    "gitcap_sample_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_float, c_int32,
+                                   c_float, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_beam_step_sampled": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                             c_int, c_float, c_int, c_void_p]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),

@@ -241,8 +241,11 @@ class InferFuture(_Future):
             decoded, logprobs, steps, vis = sub.outs
             dev = self._out_device
             mv = lambda t: t if t is None or t.device == dev else t.to(dev)
-            return {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)),
-                    "logits_dict": [] if steps is None else steps, "visual_features": mv(vis)}
+            out = {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)),
+                   "logits_dict": [] if steps is None else steps, "visual_features": mv(vis)}
+            if self._kw.get("sampling") is not None:
+                out["seed"] = self._kw["sampling"][3]
+            return out
 
         def rerun():
             r = m._infer_device(m._to_device(sub.rows(0, sub.outs[0].shape[0])), sync=True, save_logits=self._save,
@@ -261,9 +264,11 @@ class CaptionStream(_WindowStream):
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0):
+                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None):
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
         self._nbest, self._rp = int(num_keep_best), float(repetition_penalty)
+        self._sampling = sampling        # (temperature, top_k, top_p, seed | None) of a do_sample stream
+        self.last_seed = None            # do_sample: the seed of the caption the last push returned
         self._clear()
         super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
 
@@ -346,12 +351,15 @@ class CaptionStream(_WindowStream):
             else:
                 decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 logprobs = torch.empty((B,), dtype=torch.float32, device=m._dev)
-                attach, nbest, nbest_lp, _ = m._search_options(B, self._max_len, self._nbest, self._rp)
+                sampling = m._seeded(self._sampling)
+                attach, nbest, nbest_lp, _ = m._search_options(B, self._max_len, self._nbest, self._rp, sampling)
                 attach()                         # one-shot: consumed by the search below (a repeated caption attaches again)
                 m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
                         _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
                 if nbest is not None:
                     decoded, logprobs = nbest, nbest_lp
+                if sampling is not None:
+                    self.last_seed = sampling[3]
         m._last_memory = None
         if self._beam is None:
             return self._finish_greedy(ids, steps, lp, on_cpu)
@@ -908,7 +916,8 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def infer(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
-              on_device: Optional[bool] = None, repetition_penalty: float = 1.0) -> dict:
+              on_device: Optional[bool] = None, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
+              top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
         reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
@@ -919,7 +928,14 @@ class GitCaptioner(_NativeModule):
         Default: the device-resident search (no host sync per step), whenever num_keep_best <= beam_size * per_node_beam_size
         <= 16 and per_node_beam_size >= 2; it keeps num_keep_best hypotheses and applies repetition_penalty (model.py:522-531) on
         the device (include/gitcap.h: gitcap_attach_search_options).  on_device=False runs the host-side operator of
-        gitcap/search.py with the same two arguments (the default with save_logits)."""
+        gitcap/search.py with the same two arguments (the default with save_logits).
+        do_sample: the operator's sampling branch (model.py:532-554): temperature, top_k / top_p filter (at least 2 columns stay),
+        per_node_beam_size draws per beam row instead of the best candidates.  On the device the draws come from a counter-based
+        Philox stream keyed by `seed` (include/gitcap.h: gitcap_attach_sampling): the same seed, frames and batch position give the
+        same caption from infer, infer_async and caption_stream; a clip's draws depend on its position in the batch.  seed=None
+        takes one int64 from torch's global CPU generator (torch.manual_seed makes a run repeatable); the seed used is returned as
+        ``seed``.  on_device=False draws with torch.multinomial from torch.Generator().manual_seed(seed): the two paths draw from
+        different streams and agree in distribution only."""
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
@@ -934,17 +950,22 @@ class GitCaptioner(_NativeModule):
         if on_device is None:
             on_device = (not save_logits and 1 <= num_keep_best <= beam_size * per_node_beam_size <= 16
                          and per_node_beam_size >= 2)
+        sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
         if on_device:
-            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
+            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
             decoded, logprobs, steps, vis = self._infer_device(fr, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
                                                                per_node_beam_size=per_node_beam_size, sync=True,
                                                                save_logits=save_logits, want_visual=False, raw=raw,
-                                                               num_keep_best=num_keep_best, repetition_penalty=repetition_penalty)
-            return {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
-                    "visual_features": None}
+                                                               num_keep_best=num_keep_best, repetition_penalty=repetition_penalty,
+                                                               sampling=sampling)
+            out = {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
+                   "visual_features": None}
+            if sampling is not None:
+                out["seed"] = sampling[3]
+            return out
         _, vis = self.forward_image_enc(fr)
         searcher = GeneratorWithBeamSearch(self.sep_token_id, max_steps, beam_size, per_node_beam_size, length_penalty,
-                                           repetition_penalty=repetition_penalty)
+                                           repetition_penalty=repetition_penalty, temperature=temperature)
         start = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev)      # model.py:429-431
 
         def step(ids):                       # decoding_step bound at model.py:442-445, KV-cached
@@ -953,11 +974,30 @@ class GitCaptioner(_NativeModule):
         def reorder(beam_idx, cur_len):      # what model.py:623-634 leaves commented out
             self.reorder_rows(beam_idx, cur_len)
 
-        decoded, logprobs, saved = searcher.search(start, step, num_keep_best=num_keep_best, reorder=reorder,
-                                                   save_logits=save_logits)
-        return {"predictions": decoded, "logprobs": logprobs, "logits_dict": saved, "visual_features": vis}
+        if sampling is None:
+            decoded, logprobs, saved = searcher.search(start, step, num_keep_best=num_keep_best, reorder=reorder,
+                                                       save_logits=save_logits)
+            return {"predictions": decoded, "logprobs": logprobs, "logits_dict": saved, "visual_features": vis}
+        decoded, logprobs, saved = searcher.search(start, step, num_keep_best=num_keep_best, reorder=reorder, save_logits=save_logits,
+                                                   do_sample=True, top_k=top_k, top_p=top_p,
+                                                   generator=torch.Generator().manual_seed(sampling[3]))
+        return {"predictions": decoded, "logprobs": logprobs, "logits_dict": saved, "visual_features": vis, "seed": sampling[3]}
 
-    def _check_device_search(self, beam_size, per_node_beam_size, num_keep_best=1, repetition_penalty=1.0):
+    @staticmethod
+    def _sampling(do_sample, temperature, top_k, top_p, seed):
+        """The sampling arguments of the public calls -> None (no sampling) or (temperature, top_k, top_p, seed | None)."""
+        if not do_sample:
+            return None
+        return (float(temperature), int(top_k or 0), 1.0 if top_p is None else float(top_p), None if seed is None else int(seed))
+
+    @staticmethod
+    def _seeded(sampling):
+        """A _sampling tuple with its seed filled in: None takes one int64 from torch's global CPU generator."""
+        if sampling is None or sampling[3] is not None:
+            return sampling
+        return sampling[:3] + (int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()),)
+
+    def _check_device_search(self, beam_size, per_node_beam_size, num_keep_best=1, repetition_penalty=1.0, sampling=None):
         if per_node_beam_size < 2:
             raise ValueError("the device-resident search needs per_node_beam_size >= 2: with one candidate per beam "
                              "a single EOS leaves fewer than beam_size live beams (model.py:606 asserts against it); "
@@ -969,12 +1009,33 @@ class GitCaptioner(_NativeModule):
                              f"{beam_size * per_node_beam_size}]: a step ranks no more candidates than that")
         if not (math.isfinite(repetition_penalty) and repetition_penalty > 0):
             raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
+        if sampling is not None:
+            t, k, p = sampling[:3]
+            if not (math.isfinite(t) and t > 0):
+                raise ValueError("attach_sampling: temperature must be finite and > 0")
+            if k < 0:
+                raise ValueError("attach_sampling: top_k must be >= 0")
+            if not 0 < p <= 1:
+                raise ValueError("attach_sampling: top_p outside (0, 1]")
+            if self.cfg.vocab_size > 32768:
+                raise ValueError("beam_search: sampling takes a vocabulary of at most 32768 columns")
+            if (p < 1 and per_node_beam_size > 2) or (k > 0 and max(k, 2) < per_node_beam_size):
+                raise ValueError("beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep")
 
-    def _search_options(self, B, max_steps, num_keep_best, repetition_penalty):
+    def _search_options(self, B, max_steps, num_keep_best, repetition_penalty, sampling=None):
         """-> (attach, nbest, nbest_logprobs, rank0): ``attach()`` makes the one-shot gitcap_attach_search_options call that the NEXT
         beam-family call consumes (every issue of that call, a repeat after a failed statistics exchange included, needs its own);
         the n-best output buffers and, cut from the same two allocations, (decoded, logprobs) buffers for the call's own outputs;
-        None for num_keep_best == 1.  With the defaults attach() does nothing at all."""
+        None for num_keep_best == 1.  With the defaults attach() does nothing at all.  ``sampling`` (temperature, top_k, top_p, seed):
+        attach() also makes the one-shot gitcap_attach_sampling call."""
+        if sampling is not None:
+            smp = _lib.CSamplingOptions(sampling[0], sampling[1], sampling[2], sampling[3] & (2 ** 64 - 1))
+            inner = self._search_options(B, max_steps, num_keep_best, repetition_penalty)
+
+            def attach():
+                inner[0]()
+                self._call("gitcap_attach_sampling", ctypes.byref(smp))
+            return (attach,) + inner[1:]
         if num_keep_best == 1 and repetition_penalty == 1.0:
             return (lambda: None), None, None, None
         nbest = nbest_lp = rank0 = None
@@ -989,7 +1050,7 @@ class GitCaptioner(_NativeModule):
         return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
 
     def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0):
+                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None):
         """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
         stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
         the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
@@ -999,7 +1060,7 @@ class GitCaptioner(_NativeModule):
         B, F = fr.shape[:2]
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
-        attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty)
+        attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty, sampling)
         first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
         if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
             first, decoded, logprobs = rank0, nbest, nbest_lp
@@ -1031,15 +1092,17 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def infer_async(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
                     per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False,
-                    num_keep_best: int = 1, repetition_penalty: float = 1.0) -> "InferFuture":
+                    num_keep_best: int = 1, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
+                    top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
         tensor [max_steps - 1, B * beam_size, V] (the raw logits of every step, model.py:521), with ``visual_features`` the fp32
         features [B, F*N, Dv] (model.py:460); num_keep_best / repetition_penalty as in ``infer``.  Results are bitwise those of the
-        synchronous call.  `src` as in
-        greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
-        self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
+        synchronous call, with do_sample too (its arguments as in ``infer``; the seed is fixed at submission and returned as
+        ``seed``).  `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
+        sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
+        self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
         if max_steps > self.max_text_len:
@@ -1050,7 +1113,7 @@ class GitCaptioner(_NativeModule):
         if fr.shape[0] > self.max_batch:
             raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
         kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
-                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty)
+                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling)
         parts = entry = stream = None
         if fr.device.type == "cpu":
             while len(self._inflight) >= 4:      # (before the staging: the entry about to be reused belongs to the oldest)
@@ -1071,7 +1134,8 @@ class GitCaptioner(_NativeModule):
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
                        visual_features: bool = False, gate=None, logprobs: bool = False, num_keep_best: int = 1,
-                       repetition_penalty: float = 1.0) -> CaptionStream:
+                       repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
+                       top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1080,7 +1144,9 @@ class GitCaptioner(_NativeModule):
         .cuda(), invalidates this one.  ``gate``: a gitcap.framegate.FrameGate that decides on the device which pushed camera frames
         are worth encoding (it is reset here); without one every pushed frame is.  ``logprobs`` (greedy streams only): after a push
         that returned a caption, ``stream.last_logprobs`` holds its per-token log-probabilities [B, steps] (greedy_decode's
-        return_logprobs; gitcap.caption_confidence turns them into one number per clip)."""
+        return_logprobs; gitcap.caption_confidence turns them into one number per clip).  do_sample / top_k / top_p / temperature /
+        seed (beam streams only) as in infer: every caption samples with `seed` (seed=None: a fresh one per caption from torch's
+        global CPU generator); ``stream.last_seed`` is the seed of the caption the last push returned."""
         if logprobs and beam_size is not None:
             raise ValueError("logprobs=True is for greedy streams (the beam-search dict carries its own sequence score)")
         window = int(window or max(1, self.cfg.num_frames))
@@ -1090,14 +1156,17 @@ class GitCaptioner(_NativeModule):
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        sampling = self._sampling(do_sample, temperature, top_k, top_p, seed)
         if beam_size is None:
             if visual_features:
                 raise ValueError("visual_features come with the beam-search dict (beam_size=...)")
             if num_keep_best != 1 or repetition_penalty != 1.0:
                 raise ValueError("num_keep_best / repetition_penalty are options of the beam search (beam_size=...)")
+            if do_sample:
+                raise ValueError("do_sample is an option of the beam search (beam_size=...)")
         else:
             per_node_beam_size = 2 if per_node_beam_size is None else per_node_beam_size
-            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty)
+            self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
             if beam_size > self.max_beams:
                 raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
         if gate is not None:
@@ -1105,7 +1174,8 @@ class GitCaptioner(_NativeModule):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
-                             logprobs, num_keep_best, repetition_penalty)
+                             logprobs, num_keep_best, repetition_penalty,
+                             sampling)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip
