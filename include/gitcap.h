@@ -309,6 +309,39 @@ int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float lengt
  * nothing and runs exactly the launches it ran before. */
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld);
 
+/* Score GIVEN captions: the log-probability of every token of captions somebody else supplied (a ground truth, an n-best entry, a
+ * sampled or carried caption), teacher-forced in one pass, without a logits tensor.
+ *   ids   device int64 [rows][ld_ids], CLS first, T >= 2 columns used, ld_ids >= T; rows = B * beams, row r belongs to clip
+ *         r / beams (the rows of a clip share its image K/V, as in gitcap_text_forward);
+ *   lp[r][j] = log_softmax(logits[r][j][:])[ids[r][j + 1]],  j = 0 .. T - 2  (natural log).
+ * Ignored positions: (r, j) is ignored when its target ids[r][j + 1] lies outside [0, vocab_size), when it equals ignore_id (-1:
+ * none), or when lengths (nullable, device int32 [rows]: valid tokens of the row, CLS included) is given and j + 1 >= lengths[r].
+ * An ignored position gets lp = 0 and is not counted.  The kernels decide this themselves: the ids live on the device.
+ * -inf: a target whose logit is -inf (a masked bias column) gives lp = -inf, a row of logits that are all -inf gives -inf; for
+ * logits that are finite or -inf NaN never appears.
+ * Outputs (device, each nullable):
+ *   token_lp  fp32 [rows][ld_lp], ld_lp >= T - 1; columns >= T - 1 are not written;
+ *   row_sum   fp32 [rows]: the counted positions' lp added in ascending position order by one thread (one fixed order);
+ *   row_cnt   int32 [rows]: the number of counted positions;
+ *   top1_ids  int64 / top1_lp fp32 [rows][T - 1]: the model's own arg-max at each position (ignored ones included) and its
+ *             log-probability, under the tie rule and bit for bit the values of the greedy loop's arg-max launch
+ *             (gitcap_dbg_argmax_final_lp on the same partials).
+ * How: the vocabulary head runs in a form of its own that stores no logits and leaves, beside the three per-tile partials of the
+ * token log-probabilities, the one logit of each row's given next token; one workgroup per (row, position) merges the partials in
+ * the fixed order of the greedy loop and forms (y_t - M) - log(total); a second small launch adds the rows.  Every element comes
+ * from the same MFMA chain and the same merge order whatever else is in the call: a row's values are bit for bit independent of
+ * the other rows, of `beams` and of the form of the head kernel.
+ * Preconditions and argument checks are gitcap_text_forward's with t0 = 0 (after gitcap_encode / gitcap_set_visual; rows ==
+ * encoded clips * beams; rows <= max_batch * max_beams; T <= max_text_len), plus GITCAP_ERR_ARG for T < 2, ld_ids < T or
+ * ld_lp < T - 1; a refused call launches nothing.  Synchronous path, slot 0: it overwrites the text K/V of positions 0..T-1.
+ * Memory: the first call allocates the third partial (as gitcap_attach_token_logprobs does) and 8 bytes per text row of the slot;
+ * gitcap_workspace_bytes counts them from then on.  A handle that never scores runs exactly the launches it ran before. */
+int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beams, int T, const int32_t* lengths, int64_t ignore_id,
+                 float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream);
+/* debug read: the first n target logits the last gitcap_score captured (head row m = r * T + j; rows without a target in range
+ * keep whatever they held) -> out (device fp32 [n]) */
+int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream);
+
 /* Options of the device-resident search: the reference's search operator keeps `num_keep_best` finished hypotheses per clip and
  * applies a `repetition_penalty` (GeneratorWithBeamSearchV2.search, src/models/model.py:479-678; the penalty :522-531, the n-best
  * output :653-678).  A ONE-SHOT attachment, like gitcap_attach_token_logprobs: it applies to the NEXT beam-family call or
@@ -491,6 +524,19 @@ int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* ws
  * amax_val / amax_idx are bit for bit those of gitcap_dbg_vocab_head. */
 int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
                               float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream);
+/* vocab_head_score: the _lse launch in the form gitcap_score uses: targets int64 [M] (one column per row), tgt_logit fp32 [M]: the
+ * lane that holds logits[m][targets[m]] also stores it to tgt_logit[m], bit for bit the value gitcap_dbg_vocab_head writes; a
+ * target outside [0, N) leaves tgt_logit[m] untouched.  The three partials are bit for bit those of gitcap_dbg_vocab_head_lse.
+ * logits stays nullable (gitcap_score passes NULL).  (ignore_id and lengths are gitcap_dbg_score_final's business.) */
+int gitcap_dbg_vocab_head_score(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const int64_t* targets, float* tgt_logit,
+                                void* stream);
+/* score_final: the merge of gitcap_score on caller-owned buffers.  Partials [rows * T][ntiles] and tgt_logit [rows * T] are indexed
+ * by head row m = r * T + j (the rows j = T - 1 are not read); ids int64 [rows][ld_ids]; V = the vocabulary the ignore rule uses.
+ * Outputs as gitcap_score's; token_lp is required here. */
+int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                           const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                           float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream);
 /* argmax_final: out[r * ld_out] = amax_idx of the best of the ntiles partials of row r * row_stride + row_off, r < rows (a row
  * whose winner carries the empty-tile index 0x7fffffff, i.e. no logit above -inf: 0); sep_cnt (nullable): sep_cnt[step] += rows whose token is sep_id.  emb (nullable, all of
  * its fields or none): the launch goes on to write row r of xf fp32 / xb bf16 [rows][D] = LayerNorm(word[token] + pos[position])
@@ -806,6 +852,12 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4);
  * launched, attachment consumed).  The first attach allocates the third partial (sized as the arg-max partials, which covers
  * the verify pass's B * n_draft rows) and the handle's own [rows][max_len] staging the captured loops write. */
 int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld);
+/* gitcap_score over the student decoder's teacher-forced pass (the rows of gitcap_student_forward_decoder, after
+ * gitcap_student_set_memory with `rows` rows): same semantics, outputs and ignore rules; no `beams` (candidates of one clip are
+ * rows whose memory the caller repeated).  Checks: gitcap_student_forward_decoder's, plus T < 2, ld_ids < T, ld_lp < T - 1. */
+int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
+                         float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream);
+int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with

@@ -133,6 +133,7 @@ struct gitcap : HandleCore {
         // text-row workspace of the slot (token loops of different slots may run concurrently)
         float *xs = nullptr, *xs2 = nullptr, *slabs = nullptr, *part = nullptr, *amax_val = nullptr; int* amax_idx = nullptr;
         float* amax_sum = nullptr;          // third head partial, [Mt][ntiles] like amax_val: allocated by the first gitcap_attach_token_logprobs
+        float* score_buf = nullptr;         // gitcap_score (slot 0 only, first use): [2][Mt] target logits, lp rows the caller did not ask for
         unsigned* row_cnt = nullptr;
         bf16_t *xsb = nullptr, *fs = nullptr, *kv_txt = nullptr, *kv_txt2 = nullptr;
         // device-resident beam-search state of the slot (gitcap_beam_search / _submit)
@@ -515,7 +516,7 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 
 int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams, int t0, int T, float* logits_out,
                  int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
-                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0) {
+                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0, const ScoreReq* score = nullptr) {
     const gitcap_config& c = h->c;
     gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -607,9 +608,16 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
         if ((rc = ln_reduce(h, s, sl.slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, sl.xsb))) return rc;
         HIP_OK(h, keep_txt(c.dec_layers));
     }
-    if (!logits_out && !argmax_out) return 0;
+    if (!logits_out && !argmax_out && !score) return 0;
     // vocabulary head (+ arg-max partials per 16-column tile, reduced by argmax_final)
     const int V = c.vocab_size, ntiles = (V + 15) / 16;
+    if (score) {        // gitcap_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
+        if (!sl.amax_sum || !sl.score_buf) return fail(h, GITCAP_ERR_STATE, "text_forward: scoring without its buffers");
+        ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * M * V * D, (h->head_w.scale ? 1.0 : 2.0) * V * D);
+        HIP_OK(h, launch_score(HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, ids, ld_ids, rows, T,
+                               sl.amax_val, sl.amax_idx, sl.amax_sum, sl.score_buf, *score, s));
+        return 0;
+    }
     if (lp_out && (!argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
     SkinnyArgs ha;      // amax_sum: the head's third partial -> the chosen token's log-probability (argmax_final)
     const HeadRows hr = vocab_head_args(ha, HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, rows, T,
@@ -1461,16 +1469,48 @@ int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float lengt
     });
 }
 
+// first use by gitcap_attach_token_logprobs or gitcap_score: the third head partial beside amax_val, one buffer per slot
+static int ensure_amax_sum(gitcap* h) {
+    if (h->slots[0].amax_sum) return 0;
+    for (auto& sl : h->slots)
+        if (int rc = dev_alloc(h, &sl.amax_sum, (size_t)sl.Mt * (size_t)((h->V + 15) / 16))) { h->slots[0].amax_sum = nullptr; return rc; }
+    return 0;
+}
+
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: null handle");
     if (!logprobs_out) { h->lp_attach = nullptr; h->lp_ld = 0; return 0; }
     if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: ld < 1 or a misaligned pointer");
     GUARD(h);
-    if (!h->slots[0].amax_sum) {            // first attach: the third head partial beside amax_val, one buffer per slot
-        for (auto& sl : h->slots)
-            if (int rc = dev_alloc(h, &sl.amax_sum, (size_t)sl.Mt * (size_t)((h->V + 15) / 16))) { h->slots[0].amax_sum = nullptr; return rc; }
-    }
+    if (int rc = ensure_amax_sum(h)) return rc;
     h->lp_attach = logprobs_out; h->lp_ld = ld;
+    return 0;
+}
+
+int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beams, int T, const int32_t* lengths, int64_t ignore_id,
+                 float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "score: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "score: weights not finalized");
+    if (!h->slots[0].have) return fail(h, GITCAP_ERR_STATE, "score before encode/set_visual");
+    if (T < 2 || ld_ids < T) return fail(h, GITCAP_ERR_ARG, "score: T < 2 (CLS and at least one token) or ld_ids < T");
+    if (token_lp && ld_lp < T - 1) return fail(h, GITCAP_ERR_ARG, "score: ld_lp < T - 1");
+    GUARD(h);
+    POLL(h);
+    select_slot(h, 0);
+    gitcap::Slot& sl = cur(h);
+    int rc;
+    if ((rc = ensure_amax_sum(h))) return rc;
+    if (!sl.score_buf && (rc = dev_alloc(h, &sl.score_buf, 2 * (size_t)sl.Mt))) return rc;
+    HIP_OK(h, join_async(h, (hipStream_t)stream));
+    const ScoreReq q{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    return text_forward(h, ids, ld_ids, rows, beams, 0, T, nullptr, 1, nullptr, 0, nullptr, 0, (hipStream_t)stream, false, false, nullptr, 0, &q);
+}
+
+int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream) {
+    if (!h || !out || n <= 0) return fail(h, GITCAP_ERR_ARG, "dbg_score_target_logits: null argument");
+    if (!h->slots[0].score_buf || n > h->slots[0].Mt) return fail(h, GITCAP_ERR_STATE, "dbg_score_target_logits: no gitcap_score call yet, or n beyond the workspace");
+    GUARD(h);
+    HIP_OK(h, hipMemcpyAsync(out, h->slots[0].score_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -1724,6 +1764,29 @@ int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float
                               float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
     if (!amax_sum) return GITCAP_ERR_ARG;
     return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum, stream);
+}
+
+// the scoring head: the _lse launch + the logit of each row's target column (targets int64 [M], tgt_logit fp32 [M])
+int gitcap_dbg_vocab_head_score(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const int64_t* targets, float* tgt_logit,
+                                void* stream) {
+    if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || !amax_val || !amax_idx || !amax_sum || !targets || !tgt_logit)
+        return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
+    a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
+    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
+    const HeadTargets tg{targets, M, M, 0, tgt_logit};
+    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream, &tg));
+}
+// launch_score_final on caller-owned buffers: partials [rows * T][ntiles], tgt_logit [rows * T], ids [rows][ld_ids]
+int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                           const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                           float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
+    if (!token_lp) return GITCAP_ERR_ARG;
+    const ScoreOut o{token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    return dbg_rc(launch_score_final(amax_val, amax_idx, amax_sum, ntiles, tgt_logit, ids, ld_ids, rows, T, lengths, ignore_id, V, o,
+                                     (hipStream_t)stream));
 }
 
 static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,

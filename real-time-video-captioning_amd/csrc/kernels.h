@@ -100,7 +100,12 @@ extern std::atomic<bool> g_head_share;
 // GITCAP_NO_ROWS3 / gitcap_dbg_config(11, 0): the single-wave form.  Same bits either way.
 extern std::atomic<bool> g_rows3;
 bool skinny_row_prologue_ok(int M, int K, bool fp8);         // shapes the row-prologue form is instantiated for
-hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s);
+// Target capture of the scoring head (gitcap_score; kernels of their own, skinny.hip "LSE plus target"): head row m is position
+// j = m % T of id row m / T and its target is ids[(m / T) * ld + j + shift] -- none when j + shift >= T.  The lane that holds that
+// column of row m also stores the fp32 logit to logit[m]; a target outside [0, N) stores nothing.
+struct HeadTargets { const int64_t* ids; int T, ld, shift; float* logit; };
+// tg (nullable): SK_BIAS_F32 with all three partial buffers set; a.out stays nullable
+hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg = nullptr);
 // The vocabulary head's launch_skinny(SK_BIAS_F32) arguments over the bf16 rows xb [rows * T][D] (host only): every position
 // (all_positions) or the last position of every row.  The partial buffers are nullable.  Returns the row stride and offset at
 // which launch_argmax_final finds the last position of each row among the head's rows.
@@ -120,6 +125,30 @@ inline HeadRows vocab_head_args(SkinnyArgs& ha, const HeadWeight& hw, const bf16
         ha.X = xb + (size_t)(T - 1) * hw.D; ha.ldx = T * hw.D; ha.M = rows;
     }
     return r;
+}
+// Teacher-forced scoring of given captions ids [rows][ld_ids] (CLS first) from the head's partials of all rows x T positions
+// (row m = r * T + j) and the target logits the scoring head captured (HeadTargets with shift 1).  Position (r, j), j < T - 1,
+// is counted unless its target y = ids[r][j + 1] lies outside [0, V), equals ignore_id, or lengths (nullable, device) has
+// j + 1 >= lengths[r].  One workgroup per (r, j): top1_ids / top1_lp [rows][T - 1] (nullable) = launch_argmax_final's token and
+// log-probability of row m, bit for bit; lp[r * ld_lp + j] = (logit[m] - max) - log(total) of a counted position (-inf for a
+// -inf target logit, never NaN), 0 of an ignored one.  row_sum / row_cnt (nullable; a second launch, one thread per row) = the
+// sum of the counted positions' lp in ascending position order and their number.  lp is required (the caller's or a scratch).
+struct ScoreOut { float* lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; };
+hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                              const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                              const ScoreOut& o, hipStream_t s);
+// The scoring head over the bf16 rows xb [rows * T][D] + launch_score_final (host only; what gitcap_score / gitcap_student_score
+// run behind their decoder stacks).  scratch: fp32 [2][rows * T] = the target logits, then the lp rows where the caller wants none.
+struct ScoreReq { const int32_t* lengths; int64_t ignore_id; float* token_lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; };
+inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int64_t* ids, int ld_ids, int rows, int T, float* amax_val,
+                               int* amax_idx, float* amax_sum, float* scratch, const ScoreReq& q, hipStream_t s) {
+    SkinnyArgs ha;
+    vocab_head_args(ha, hw, xb, rows, T, true, nullptr, amax_val, amax_idx, amax_sum);
+    const HeadTargets tg{ids, T, ld_ids, 1, scratch};
+    hipError_t e = launch_skinny(ha, SK_BIAS_F32, s, &tg);
+    if (e != hipSuccess) return e;
+    const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
+    return launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
 }
 bool skinny_full_ok(int K);                                 // K depths launch_skinny is instantiated for
 int skinny_ksplit(int K);                                    // number of K slabs launch_skinny_splitk writes

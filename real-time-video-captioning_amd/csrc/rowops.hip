@@ -502,6 +502,59 @@ __global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restri
     if (j == 0) { host[0] = a; host[1] = fired ? 1 : 0; }
 }
 
+// ---- scoring of given captions (gitcap_score; kernels.h: launch_score_final) ---------------------------------------------------
+// the one statement of which positions count: target y = ids[r][j + 1] inside the vocabulary, not ignore_id, in front of lengths[r]
+__device__ __forceinline__ bool score_counted(const int64_t* __restrict__ ids, int ld_ids, const int32_t* __restrict__ lengths,
+                                              int64_t ignore_id, int V, int r, int j) {
+    const int64_t y = ids[(size_t)r * ld_ids + j + 1];
+    return y >= 0 && y < V && y != ignore_id && (!lengths || j + 1 < lengths[r]);
+}
+// One workgroup per (row r, position j < T - 1) over the partials of head row m = r * T + j: the row's winner and its
+// log-probability exactly as argmax_final_kernel<.., true> forms them (argmax_partials_waves / _pick, lp_partials: same tie rule,
+// same summation order, same bits), and the given token's: (its logit - M) + the winner's log-probability, i.e.
+// (y_t - M) - log(total).  A -inf target logit gives -inf outright (an all -inf row has M = -inf: never -inf - -inf).  The
+// target logit of an ignored position was never written and is not used.
+__global__ __launch_bounds__(256) void score_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
+                                                          const float* __restrict__ psum, int ntiles, const float* __restrict__ tgt_logit,
+                                                          const int64_t* __restrict__ ids, int ld_ids, int T,
+                                                          const int32_t* __restrict__ lengths, int64_t ignore_id, int V,
+                                                          float* __restrict__ lp_out, int ld_lp, int64_t* __restrict__ top1_ids,
+                                                          float* __restrict__ top1_lp) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ float vmax, ss[4];
+    const int r = blockIdx.x / (T - 1), j = blockIdx.x - r * (T - 1), tid = threadIdx.x;
+    const size_t m = (size_t)r * T + j, base = m * ntiles;
+    float best;
+    int bi;
+    argmax_partials_waves(val, idx, base, ntiles, sv, si, best, bi);
+    if (tid == 0) bi = argmax_partials_pick(sv, si, best, bi, &vmax);
+    __syncthreads();
+    const float lp1 = lp_partials(val, psum, base, ntiles, vmax, ss);
+    if (tid != 0) return;
+    if (top1_ids) top1_ids[blockIdx.x] = bi;
+    if (top1_lp) top1_lp[blockIdx.x] = lp1;
+    float lp = 0.f;
+    if (score_counted(ids, ld_ids, lengths, ignore_id, V, r, j)) {
+        const float yt = tgt_logit[m];
+        lp = yt == -INFINITY ? -INFINITY : (yt - vmax) + lp1;
+    }
+    lp_out[(size_t)r * ld_lp + j] = lp;
+}
+// row_sum[r] = the counted positions' lp, added in ascending position order by one thread; row_cnt[r] = their number
+__global__ __launch_bounds__(64) void score_rows_kernel(const float* __restrict__ lp, int ld_lp, const int64_t* __restrict__ ids, int ld_ids,
+                                                        int rows, int T, const int32_t* __restrict__ lengths, int64_t ignore_id, int V,
+                                                        float* __restrict__ row_sum, int32_t* __restrict__ row_cnt) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    float sum = 0.f;
+    int cnt = 0;
+    for (int j = 0; j + 1 < T; ++j)
+        if (score_counted(ids, ld_ids, lengths, ignore_id, V, r, j)) { sum += lp[(size_t)r * ld_lp + j]; ++cnt; }
+    if (row_sum) row_sum[r] = sum;
+    if (row_cnt) row_cnt[r] = cnt;
+}
+
 // ---- beam candidates: top-K of (log_softmax(logits[b*beams+j]) + beam_score[b*beams+j]) over j, v ----
 // Replaces log_softmax (:557) + add (:561) + view + topk (:563-565) of the reference search loop
 // (src/models/model.py); flat index = j*V + v, sorted descending, ties by smaller flat index.
@@ -1214,6 +1267,20 @@ hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int n
         default: AF_LAUNCH(4); break;
     }
 #undef AF_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                              const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                              const ScoreOut& o, hipStream_t s) {
+    if (!amax_val || !amax_idx || !amax_sum || !tgt_logit || !ids || !o.lp || ntiles <= 0 || rows <= 0 || T < 2 || ld_ids < T || V <= 0 ||
+        o.ld_lp < T - 1 || (int64_t)rows * (T - 1) > 0x7fffffff)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(score_final_kernel, dim3(rows * (T - 1)), dim3(256), 0, s, amax_val, amax_idx, amax_sum, ntiles, tgt_logit, ids, ld_ids, T,
+                       lengths, ignore_id, V, o.lp, o.ld_lp, o.top1_ids, o.top1_lp);
+    if (o.row_sum || o.row_cnt)
+        hipLaunchKernelGGL(score_rows_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, (const float*)o.lp, o.ld_lp, ids, ld_ids, rows, T, lengths,
+                           ignore_id, V, o.row_sum, o.row_cnt);
     return hipGetLastError();
 }
 

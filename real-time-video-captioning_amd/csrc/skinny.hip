@@ -70,12 +70,28 @@ __device__ __forceinline__ void load_wfrags(const void* W, const void* Wpk, cons
     }
 }
 
+// the given next token of head row m (kernels.h: HeadTargets), -1 where the row has none
+__device__ __forceinline__ int64_t head_target(const HeadTargets& t, const int m) {
+    const int r = m / t.T, j = m - r * t.T + t.shift;
+    return j < t.T ? t.ids[(size_t)r * t.ld + j] : -1;
+}
+
 // fp32 logits of one 16 x 16 tile (lane: out[m][n .. n+3]) and the tile's arg-max partial per row (ascending n: first max wins)
 // LSE: also the tile's third partial (a.amax_sum) -- kernels of their own, picked by the launcher where the pointer is set, so that
 // the launches without it stay the code they were
-template <bool LSE>
+// TGT (the scoring head, with LSE): the lane that holds column tcol of row m -- the row's given next token -- also stores that logit
+// to tlogit[m]; a column outside [0, N) is in no lane.  Padded rows and idle waves (!mvalid) store nothing.
+template <bool LSE, bool TGT = false>
 __device__ __forceinline__ void logits_epilogue(const SkinnyArgs& a, const float (&y)[4], const int m, const bool mvalid, const int n,
-                                                const int fq, const int tile, const int ntiles) {
+                                                const int fq, const int tile, const int ntiles, const int64_t tcol = -1,
+                                                float* tlogit = nullptr) {
+    if (TGT) {
+        if (mvalid && tcol >= n && tcol < n + 4 && tcol < a.N) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)                         // (one store each: an indexed pick of y[] would move it out of registers)
+                if (tcol == n + r) tlogit[m] = y[r];
+        }
+    }
     if (mvalid && a.out) {
         float* op = (float*)a.out + (size_t)m * a.ldo + n;
 #pragma unroll
@@ -215,6 +231,50 @@ __global__ __launch_bounds__(64) void skinny_full_kernel(SkinnyArgs a) {
     }
 }
 
+// The single-wave vocabulary head of the scoring pass (gitcap_score behind gitcap_dbg_config(10, 0), or fewer than four tiles): the
+// SK_BIAS_F32 path of skinny_full_kernel with the three partials and the target logit (logits_epilogue<true, true>) -- a kernel of
+// its own, so that skinny_full_kernel stays the code it was.  Same operands, same MFMA chain, same bits.  The target of the lane's
+// row is requested ahead of the activation fragments of its m-tile (vmcnt counts in order: the epilogue that needs it leaves the
+// next m-tile's fragments in flight).
+template <int K32, bool FP8>
+__global__ __launch_bounds__(64) void skinny_full_score_kernel(SkinnyArgs a, HeadTargets tg) {
+    const int lane = threadIdx.x;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    bf16x8 wf[K32];
+    load_wfrags<K32, FP8>(a.W, a.Wpk, a.wscale, (size_t)(n0 + frow), a.K, fq * 8, wf);
+    const int n = n0 + fq * 4;
+    float bias[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bias[r] = (a.bias && n + r < a.N) ? a.bias[n + r] : 0.f;
+    const int mtiles = (a.M + 15) >> 4;
+    bf16x8 xnext[K32];
+    int64_t tnext;
+    auto load_x = [&](int mt) {
+        const int m = min(mt * 16 + frow, a.M - 1);
+        tnext = head_target(tg, m);
+        const bf16_t* xp = a.X + (size_t)m * a.ldx + fq * 8;
+#pragma unroll
+        for (int k = 0; k < K32; ++k) xnext[k] = *(const bf16x8*)(xp + k * 32);
+    };
+    load_x(0);
+    for (int mt = 0; mt < mtiles; ++mt) {
+        const int m = mt * 16 + frow;
+        bf16x8 xcur[K32];
+#pragma unroll
+        for (int k = 0; k < K32; ++k) xcur[k] = xnext[k];
+        const int64_t tcol = tnext;
+        if (mt + 1 < mtiles) load_x(mt + 1);
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < K32; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k], xcur[k], acc, 0, 0, 0);
+        float y[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) y[r] = acc[r] + bias[r];
+        logits_epilogue<true, true>(a, y, min(m, a.M - 1), m < a.M, n, fq, blockIdx.x, gridDim.x, tcol, tg.logit);
+    }
+}
+
 // ---- vocabulary head with shared activation rows ------------------------------------------------------------------------
 // skinny_full with SK_BIAS_F32 runs one single-wave workgroup per 16-column tile and every one of them fetches the same
 // 16 x K activation tile -- at K = 768 as many bytes as the weight tile it owns, 1908 times over for the 30522-word
@@ -223,8 +283,8 @@ __global__ __launch_bounds__(64) void skinny_full_kernel(SkinnyArgs a) {
 // ds_read_b128 group fall into 16 different 16-byte slots), requested ahead of the weight fragments so that the LDS copy
 // waits for it alone (vmcnt counts in order) while the weights stay in flight; m-tile mt + 1 is in flight under m-tile mt
 // (two LDS images).  Every output element is the same MFMA chain over the same operands as in skinny_full: same bits.
-template <int K32, bool FP8, bool LSE>
-__device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int ntiles) {
+template <int K32, bool FP8, bool LSE, bool TGT = false>
+__device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int ntiles, const HeadTargets tg = HeadTargets{}) {
     constexpr int PITCH = K32 * 64 + 16, CPR = K32 * 4, NC = (16 * CPR + 255) / 256;     // 16 x CPR 16-byte pieces over 256 threads
     __shared__ __attribute__((aligned(16))) char xs[2][16 * PITCH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -253,6 +313,10 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
             if (c < 16 * CPR) *(u32x4*)(&xs[buf][row * PITCH + col * 16]) = st[i];
         }
     };
+    // TGT: the target of the lane's row of m-tile mt, requested ahead of the activation rows of that m-tile: the LDS copy's wait
+    // covers it and leaves the same requests in flight as before
+    int64_t tnext = -1;
+    if (TGT) tnext = head_target(tg, min(frow, a.M - 1));
     gload(0);
     bf16x8 wf[K32];
     load_wfrags<K32, FP8>(a.W, a.Wpk, a.wscale, (size_t)(n0 + frow), a.K, fq * 8, wf);
@@ -263,7 +327,11 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
     lstore(0);
     __syncthreads();
     for (int mt = 0; mt < mtiles; ++mt) {
-        if (mt + 1 < mtiles) gload(mt + 1);
+        const int64_t tcol = tnext;
+        if (mt + 1 < mtiles) {
+            if (TGT) tnext = head_target(tg, min((mt + 1) * 16 + frow, a.M - 1));
+            gload(mt + 1);
+        }
         const char* xb = &xs[mt & 1][frow * PITCH + fq * 16];
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -273,7 +341,7 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
         float y[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[r] = acc[r] + bias[r];
-        logits_epilogue<LSE>(a, y, m < a.M ? m : a.M - 1, mvalid, n, fq, tile, ntiles);
+        logits_epilogue<LSE, TGT>(a, y, m < a.M ? m : a.M - 1, mvalid, n, fq, tile, ntiles, tcol, tg.logit);
         if (mt + 1 < mtiles) lstore((mt + 1) & 1);              // the image m-tile mt - 1 was read from: every wave is past the
         __syncthreads();                                         // barrier that closed that iteration
     }
@@ -284,6 +352,11 @@ __global__ __launch_bounds__(256) void skinny_head_kernel(SkinnyArgs a, const in
 // the same kernel with the third partial of the token log-probabilities (logits_epilogue<true>)
 template <int K32, bool FP8>
 __global__ __launch_bounds__(256) void skinny_head_lse_kernel(SkinnyArgs a, const int ntiles) { skinny_head_body<K32, FP8, true>(a, ntiles); }
+// the scoring pass: the three partials + the logit of each row's given next token (logits_epilogue<true, true>)
+template <int K32, bool FP8>
+__global__ __launch_bounds__(256) void skinny_head_score_kernel(SkinnyArgs a, const int ntiles, HeadTargets tg) {
+    skinny_head_body<K32, FP8, true, true>(a, ntiles, tg);
+}
 
 // ---- one/two-row prologue over many slabs: three waves share the reduce ---------------------------------------------------
 // The fused FFN launch (ffn_txt.hip) leaves dec_ffn / 64 = 48 slabs; the single wave of skinny_full<LNR> walks them in three
@@ -423,15 +496,18 @@ __global__ __launch_bounds__(64) void skinny_splitk_kernel(SkinnyArgs a) {
 }
 
 template <int K32, bool FP8>
-hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s) {
+hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg) {
     const int grid = (a.N + 15) / 16;
     if (a.ln.kind) return hipErrorInvalidValue;          // row prologue: launch_full_rows
     const bool lse = a.amax_sum != nullptr;              // the third partial of the token log-probabilities: the <.., true> kernels
     if (lse && (epi != SK_BIAS_F32 || !a.amax_val || !a.amax_idx)) return hipErrorInvalidValue;
+    // target capture (the scoring pass): kernels of their own, in the two forms of the head
+    if (tg && (!lse || !tg->ids || !tg->logit || tg->T <= 0 || tg->ld < tg->T || tg->shift < 0 || a.M % tg->T)) return hipErrorInvalidValue;
     if constexpr (K32 * 64 * 32 + 512 <= 64 * 1024) {          // two LDS images of 16 rows (K <= 768)
         // the vocabulary head (many tiles over few rows): four tiles per workgroup share the activation rows through LDS
         if (epi == SK_BIAS_F32 && g_head_share && grid >= 4 && a.ldx % 8 == 0 && ((uintptr_t)a.X & 15) == 0) {
-            if (lse) hipLaunchKernelGGL((skinny_head_lse_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
+            if (tg) hipLaunchKernelGGL((skinny_head_score_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid, *tg);
+            else if (lse) hipLaunchKernelGGL((skinny_head_lse_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
             else hipLaunchKernelGGL((skinny_head_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
             return hipGetLastError();
         }
@@ -441,7 +517,8 @@ hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s) {
         case SK_BIAS_GELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_GELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_RELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_RELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_F32:
-            if (lse) hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, true>), dim3(grid), dim3(64), 0, s, a);
+            if (tg) hipLaunchKernelGGL((skinny_full_score_kernel<K32, FP8>), dim3(grid), dim3(64), 0, s, a, *tg);
+            else if (lse) hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, true>), dim3(grid), dim3(64), 0, s, a);
             else hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, false>), dim3(grid), dim3(64), 0, s, a);
             break;
         default: return hipErrorInvalidValue;
@@ -481,25 +558,26 @@ bool skinny_full_ok(int K) {
 
 bool skinny_row_prologue_ok(int M, int K, bool fp8) { return M >= 1 && M <= 2 && (K == 64 || K == 128 || K == 576 || K == 768) && !fp8; }
 
-hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s) {
+hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg) {
     if (a.K % 32 || a.M <= 0 || a.T <= 0) return hipErrorInvalidValue;
+    if (tg && (a.ln.kind || epi != SK_BIAS_F32)) return hipErrorInvalidValue;
     if (a.ln.kind)
         return a.K == 64 ? launch_full_rows<2>(a, epi, s) : a.K == 128 ? launch_full_rows<4>(a, epi, s)
              : a.K == 576 ? launch_full_rows<18>(a, epi, s) : launch_full_rows<24>(a, epi, s);
     if (a.wscale) {                                     // e4m3 weights (GIT decoder widths only)
         switch (a.K / 32) {
-            case 4: return launch_full<4, true>(a, epi, s);
-            case 24: return launch_full<24, true>(a, epi, s);
+            case 4: return launch_full<4, true>(a, epi, s, tg);
+            case 24: return launch_full<24, true>(a, epi, s, tg);
         }
         return hipErrorInvalidValue;
     }
     switch (a.K / 32) {
-        case 2: return launch_full<2, false>(a, epi, s);      // K = 64  (tiny student test config)
-        case 4: return launch_full<4, false>(a, epi, s);      // K = 128 (tiny test config)
-        case 8: return launch_full<8, false>(a, epi, s);      // K = 256
-        case 18: return launch_full<18, false>(a, epi, s);    // K = 576 (student decoder)
-        case 24: return launch_full<24, false>(a, epi, s);    // K = 768
-        case 32: return launch_full<32, false>(a, epi, s);    // K = 1024
+        case 2: return launch_full<2, false>(a, epi, s, tg);      // K = 64  (tiny student test config)
+        case 4: return launch_full<4, false>(a, epi, s, tg);      // K = 128 (tiny test config)
+        case 8: return launch_full<8, false>(a, epi, s, tg);      // K = 256
+        case 18: return launch_full<18, false>(a, epi, s, tg);    // K = 576 (student decoder)
+        case 24: return launch_full<24, false>(a, epi, s, tg);    // K = 768
+        case 32: return launch_full<32, false>(a, epi, s, tg);    // K = 1024
     }
     return hipErrorInvalidValue;
 }

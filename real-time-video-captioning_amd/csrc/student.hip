@@ -206,6 +206,7 @@ struct gitcap_student : HandleCore {
     float *lp_attach = nullptr, *amax_sum = nullptr, *g_lp = nullptr;
     int lp_ld = 0;
     int* acc_lp = nullptr;
+    float* score_buf = nullptr;         // gitcap_student_score (first use): [2][Mt] target logits, lp rows the caller did not ask for
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -276,7 +277,8 @@ int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx,
 
 // model.py:128-154 for rows x T query positions t0..t0+T-1 (K/V of earlier positions come from the cache)
 int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int t0, int T, float* logits_out,
-                 int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s, float* lp_out = nullptr, int ld_lp = 0) {
+                 int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s, float* lp_out = nullptr, int ld_lp = 0,
+                 const ScoreReq* score = nullptr) {
     const gitcap_student_config& c = h->c;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student: decoder called before set_memory");
@@ -335,7 +337,12 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         if ((rc = proj(SK_BIAS_RELU_BF16, Ly.l1w, Ly.l1b, h->FF, h->ffn, h->FF, 1, 1, 0))) return rc;
         if ((rc = dense_ln(h->ffn, h->FF, Ly.l2w, Ly.l2b, Ly.n3w, Ly.n3b, l + 1 < h->L))) return rc;
     }
-    if (!logits_out && !argmax_out) return 0;
+    if (!logits_out && !argmax_out && !score) return 0;
+    if (score) {        // gitcap_student_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
+        if (!h->amax_sum || !h->score_buf) return fail(h, GITCAP_ERR_STATE, "student: scoring without its buffers");
+        HIP_OK(h, launch_score(head_weight(h), h->xb, ids, ld_ids, rows, T, h->amax_val, h->amax_idx, h->amax_sum, h->score_buf, *score, s));
+        return 0;
+    }
     // vocabulary head: all positions when logits are requested, else the last position of every row
     if (lp_out && (!argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
     SkinnyArgs ha;
@@ -877,12 +884,35 @@ int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_ou
     if (!h->g_lp) {                             // first attach: sized as amax_val (covers the verify pass's B * n rows)
         const size_t Mt = (size_t)h->Mt, ntiles = ((size_t)h->V + 15) / 16;
         int rc;
-        if ((rc = dev_alloc(h, &h->amax_sum, Mt * ntiles)) || (rc = dev_alloc(h, &h->acc_lp, Mt)) || (rc = dev_alloc(h, &h->g_lp, Mt))) {
+        if ((rc = h->amax_sum ? 0 : dev_alloc(h, &h->amax_sum, Mt * ntiles)) || (rc = dev_alloc(h, &h->acc_lp, Mt)) || (rc = dev_alloc(h, &h->g_lp, Mt))) {
             h->g_lp = nullptr;
             return rc;
         }
     }
     h->lp_attach = logprobs_out; h->lp_ld = ld;
+    return 0;
+}
+
+int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
+                         float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_score: weights not finalized");
+    if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student_score before set_memory");
+    if (T < 2 || ld_ids < T) return fail(h, GITCAP_ERR_ARG, "student_score: T < 2 (CLS and at least one token) or ld_ids < T");
+    if (token_lp && ld_lp < T - 1) return fail(h, GITCAP_ERR_ARG, "student_score: ld_lp < T - 1");
+    GUARD(h);
+    int rc;
+    if (!h->amax_sum && (rc = dev_alloc(h, &h->amax_sum, (size_t)h->Mt * (((size_t)h->V + 15) / 16)))) return rc;
+    if (!h->score_buf && (rc = dev_alloc(h, &h->score_buf, 2 * (size_t)h->Mt))) return rc;
+    const ScoreReq q{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    return text_forward(h, ids, ld_ids, rows, 0, T, nullptr, nullptr, 0, nullptr, 0, (hipStream_t)stream, nullptr, 0, &q);
+}
+
+int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream) {
+    if (!h || !out || n <= 0) return fail(h, GITCAP_ERR_ARG, "student_dbg_score_target_logits: null argument");
+    if (!h->score_buf || n > h->Mt) return fail(h, GITCAP_ERR_STATE, "student_dbg_score_target_logits: no gitcap_student_score call yet, or n beyond the workspace");
+    GUARD(h);
+    HIP_OK(h, hipMemcpyAsync(out, h->score_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

@@ -135,6 +135,11 @@ SYMBOLS = {
                                            POINTER(CDbgNextEmbed), c_void_p, c_void_p, c_int, c_void_p]),
     "gitcap_dbg_draft_accept_lp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                            c_int, POINTER(c_int32), c_void_p, c_void_p, c_int, c_void_p]),
+    # scoring of given captions (tests/test_score_gpu.py): the head with target capture, the merge
+    "gitcap_dbg_vocab_head_score": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_score_final": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64,
+                                       c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_beam_init": (c_int, [POINTER(CDbgBeamBuffers), c_int, c_int, c_int, c_int, c_void_p]),
     "gitcap_dbg_beam_step": (c_int, [POINTER(CDbgBeamBuffers), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),
@@ -162,6 +167,9 @@ SYMBOLS = {
     "gitcap_dbg_attn_small": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
+    "gitcap_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # search options of the device-resident search: n-best hypotheses, repetition penalty (tests/test_search_options_gpu.py)
     "gitcap_attach_search_options": (c_int, [c_void_p, POINTER(CSearchOptions)]),
     "gitcap_beam_topk_penalized": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
@@ -195,6 +203,9 @@ SYMBOLS = {
                                                    POINTER(c_int32), c_void_p]),
     "gitcap_student_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_student_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
+    "gitcap_student_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
+    "gitcap_student_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),

@@ -662,6 +662,64 @@ class GitCaptioner(_NativeModule):
             self._call("gitcap_text_forward", _lib.ptr(ids), T, B, 1, 0, T, _lib.ptr(logits), 1, None, 0, self._stream())
         return logits
 
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
+              ignore_id: Optional[int] = None, return_top1: bool = False) -> dict:
+        """Log-probabilities of GIVEN captions, teacher-forced in one pass without a logits tensor (include/gitcap.h:
+        gitcap_score).  ``x``: frames [B,F,3,S,S] or ``memory`` from forward_image_enc (treated as forward_decoder treats it);
+        ``y``: CLS-first ids [B, T] or [B, n, T] -- n candidates per clip, run as n rows that share the clip's image K/V.
+        A position is ignored (log-probability 0, not counted) when its target is outside the vocabulary, equals ``ignore_id``,
+        or lies behind the row's length: through its first SEP (``until_sep``) and / or the caller's ``lengths`` ([B] or [B, n],
+        valid tokens, CLS included).  -> dict: ``token_logprobs`` fp32 [B, (n,) T-1] (column j belongs to y[..., j + 1]),
+        ``sum`` fp32 and ``count`` int32 [B, (n)]; with ``return_top1`` also ``top1_ids`` / ``top1_logprobs`` [B, (n,) T-1], the
+        model's own arg-max at each position.  More clips than max_batch go through in chunks.  On ``x``'s device."""
+        from . import scoring
+        self._drain()
+        ids, had_n = scoring.candidates(y, self._dev)
+        B, n, T = ids.shape
+        if x.shape[0] != B:
+            raise ValueError("x and y disagree on the number of clips")
+        if T > self.max_text_len:
+            raise ValueError(f"T={T} > max_text_len={self.max_text_len} the handle was created for")
+        Bc = min(B, self.max_batch)
+        if Bc * n > self.max_batch * self.max_beams:
+            raise ValueError(f"{Bc} clips x {n} candidates = {Bc * n} rows > max_batch * max_beams = {self.max_batch * self.max_beams} "
+                             "the handle was created for")
+        ln = scoring.row_lengths(ids, self.sep_token_id, until_sep, lengths)
+        frames = x.dim() == 5
+        chunks = []
+        with torch.cuda.device(self._dev):
+            for b0 in range(0, B, Bc):
+                b1 = min(B, b0 + Bc)
+                if frames:
+                    self.forward_image_enc(x[b0:b1])
+                elif not (b0 == 0 and b1 == B and self._is_last_memory(x)):
+                    mem = x[b0:b1].to(device=self._dev, dtype=torch.float32).contiguous()
+                    self._call("gitcap_set_visual", _lib.ptr(mem), mem.shape[0], mem.shape[1], self._stream())
+                    self._last_memory = None
+                    if b0 == 0 and b1 == B:
+                        self._remember_memory(x)
+                rows = (b1 - b0) * n
+                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1)
+                cid = ids[b0:b1].reshape(rows, T)
+                cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
+                self._call("gitcap_score", _lib.ptr(cid), T, rows, n, T, _lib.ptr(cl), -1 if ignore_id is None else int(ignore_id),
+                           *buf.args(T), self._stream())
+                chunks.append(buf)
+        if B > Bc:
+            self._last_memory = None
+        return scoring.result(chunks, B, n, had_n, return_top1, x.device)
+
+    @torch.no_grad()
+    def rerank(self, x: torch.Tensor, candidates: torch.Tensor, length_penalty: float = 0.6) -> dict:
+        """Order n candidate captions per clip ([B, n, T], e.g. infer(num_keep_best=n), sampled captions, the student's beams)
+        by this model's sum / count ** length_penalty, the BeamHypotheses score of the reference's search.  -> score()'s dict
+        plus ``scores`` fp32 [B, n] and ``order`` int64 [B, n], best first."""
+        from . import scoring
+        if candidates.dim() != 3:
+            raise ValueError(f"expected candidates [B, n, T], got {tuple(candidates.shape)}")
+        return scoring.rerank_scores(self.score(x, candidates), length_penalty)
+
     def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):
         """``forward(x, y)``: teacher-forced logits [B,T,V] (student signature, model.py:99-106).
         ``forward(x)``: the teacher's form (``GenerativeImageTextTeacher.forward``, model.py:762-793)."""

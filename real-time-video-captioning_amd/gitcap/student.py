@@ -267,6 +267,38 @@ class StudentCaptioner(_NativeModule):
             self._call("gitcap_student_forward_decoder", _lib.ptr(ids), T, B, T, _lib.ptr(logits), self._stream())
         return logits
 
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
+              ignore_id: Optional[int] = None, return_top1: bool = False) -> dict:
+        """GitCaptioner.score over the student decoder (include/gitcap.h: gitcap_student_score): ``x`` frames or memory [B,F,D],
+        ``y`` CLS-first ids [B, T] or [B, n, T] (n candidates per clip: rows whose memory is repeated).  Same ignore rules and
+        the same dict; clips go through in chunks of max_batch // n."""
+        from . import scoring
+        ids, had_n = scoring.candidates(y, self._dev)
+        B, n, T = ids.shape
+        if x.shape[0] != B:
+            raise ValueError("x and y disagree on the number of clips")
+        if T > self.max_text_len + 1:
+            raise ValueError(f"T={T} > max_text_len+1={self.max_text_len + 1}")
+        if n > self.max_batch:
+            raise ValueError(f"{n} candidates per clip > max_batch={self.max_batch} rows the handle was created for")
+        ln = scoring.row_lengths(ids, self.cfg.sep_token_id, until_sep, lengths)
+        Bc = min(B, self.max_batch // n)
+        chunks = []
+        with torch.cuda.device(self._dev):
+            for b0 in range(0, B, Bc):
+                b1 = min(B, b0 + Bc)
+                mem = self._memory(self._src_memory(x[b0:b1])).repeat_interleave(n, dim=0) if n > 1 else self._memory(self._src_memory(x[b0:b1]))
+                rows = (b1 - b0) * n
+                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1)
+                cid = ids[b0:b1].reshape(rows, T)
+                cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
+                self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
+                self._call("gitcap_student_score", _lib.ptr(cid), T, rows, T, _lib.ptr(cl), -1 if ignore_id is None else int(ignore_id),
+                           *buf.args(T), self._stream())
+                chunks.append(buf)
+        return scoring.result(chunks, B, n, had_n, return_top1, x.device)
+
     def forward(self, x: torch.Tensor, y: torch.Tensor):
         """model.py:99-106: feature maps + [logits]."""
         fmaps, memory = self.forward_image_enc(x)
