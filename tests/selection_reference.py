@@ -76,6 +76,55 @@ def draft_accept(tok, ids, sep_id):
             "host": (a, 1 if any(c == B for c in sep_cnt) else 0)}
 
 
+# ---- inputs of the draft_accept tests (tests/test_selection_gpu.py, tests/test_logprob_gpu.py) ----
+
+DRAFT_NT, DRAFT_SEP, DRAFT_POISON = 5, 9, -777
+
+
+def draft_scenario(B, n, a_rows, sep_at, rng):
+    """Model tokens tok [B][n] with SEP at the (row, step) pairs of sep_at, and ids [B][ld] whose draft agrees with row r at
+    exactly its first a_rows[r] positions (the first disagreement of row 0 is a staged -1); ld = n + 4."""
+    vocab, ld = 16 * DRAFT_NT, n + 4
+    tok = rng.integers(10, vocab, (B, n))
+    for r, t in sep_at:
+        tok[r, t] = DRAFT_SEP
+    ids = np.full((B, ld), DRAFT_POISON, np.int64)
+    ids[:, 0] = 1
+    for r in range(B):
+        for j in range(n):
+            if j < a_rows[r] or (j > a_rows[r] and rng.random() < 0.5):
+                ids[r, j + 1] = tok[r, j]
+            elif j == a_rows[r] and r == 0:
+                ids[r, j + 1] = -1
+            else:
+                ids[r, j + 1] = 10 + (tok[r, j] - 10 + 1 + rng.integers(0, vocab - 12)) % (vocab - 10)
+                assert ids[r, j + 1] != tok[r, j]
+    # partials that reduce to tok: the winner's tile holds 2.0 and the token; every second row has an equal value with a
+    # larger index in another tile (the tie rule picks the token)
+    val = rng.random((B * n, DRAFT_NT)).astype(np.float32)
+    idx = np.arange(DRAFT_NT, dtype=np.int64)[None, :] * 16 + rng.integers(0, 16, (B * n, DRAFT_NT))
+    for m in range(B * n):
+        t = int(tok[m // n, m % n])
+        val[m, t // 16], idx[m, t // 16] = 2.0, t
+        if m % 2:
+            o = (t // 16 + 1 + m % (DRAFT_NT - 1)) % DRAFT_NT
+            val[m, o], idx[m, o] = 2.0, t + 1 + m % 3
+    return tok, ids, val, idx
+
+
+def draft_scenarios(B, n):
+    mid = n // 2
+    out = [([n] * B, [(r, n - 1) for r in range(B)]),                           # a = n; all rows SEP in the last step: fired
+           ([0] + [n] * (B - 1), [(r, 0) for r in range(B)])]                   # a = 0; SEP at once in the model's own tokens
+    if n >= 2:
+        stair = [min(n, mid + r % 3) for r in range(B)]                         # rows disagree at different positions
+        sep = [(r, mid + 1) for r in range(B)] if mid + 1 < n else []           # all rows, but beyond `covered`: not fired
+        sep += [(r, r % (mid + 1)) for r in range(B)] if B > 1 else []          # inside `covered`, in different steps
+        out.append((stair, sep))
+        out.append(([n] * (B - 1) + [mid], []))                                 # the minimum sits in the last row
+    return out
+
+
 def beam_candidates(logits, beam_scores, beams, K):
     """logits [B*beams][V], beam_scores [B*beams] -> (scores fp64 [B][K], idx int64 [B][K], gap [B]).
     Candidate (j, v) of clip b scores log_softmax(logits[b*beams + j])[v] + beam_scores[b*beams + j] in fp64 (the softmax over

@@ -18,38 +18,12 @@ import pytest
 import torch
 
 import encoder_kernels_reference as E
+from gpu_support import bf16_bits, close_to_fp64, f64, lib, ptr, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
 POISON16 = 0xABAB - 0x10000              # 0xABAB as int16
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _t(a, dtype=torch.bfloat16):
-    return None if a is None else torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
-
-
-def _np(t):
-    return t.detach().float().cpu().numpy().astype(np.float64)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
 def _nan(count, dtype=torch.bfloat16):
@@ -58,17 +32,7 @@ def _nan(count, dtype=torch.bfloat16):
 
 def _strided(a, ld, rows=None):
     """a [M][N] -> device bf16 [rows][ld], NaN in the pad columns and rows"""
-    return _t(E.tv_gemm_buffer(np.asarray(a), rows or a.shape[0], ld))
-
-
-def _close(dev, ref, bound, what, flips=True):
-    dev, ref = np.asarray(dev, np.float64), np.asarray(ref, np.float64)
-    assert not np.isnan(dev).any(), what
-    ratio = float((np.abs(dev - ref) / bound).max())
-    share = E.flip_share(dev, ref) if flips else 0.0
-    print(f"{what}: max |device - fp64| / bound = {ratio:.3f}" + (f", share off the correctly rounded value {share:.4f}" if flips else ""))
-    assert ratio <= 1.0, what
-    assert share <= 0.02, what
+    return to_dev(E.tv_gemm_buffer(np.asarray(a), rows or a.shape[0], ld), torch.bfloat16)
 
 
 # ---- tv_gemm ----------------------------------------------------------------------------------------------------------------------
@@ -82,7 +46,7 @@ def _gemm_case(M, N, K, epi):
 def _gemm(lib, a, M, N, K, epi, lda, ldo, ldr, inplace=False):
     """-> the whole output buffer [M + 2][ldo] (bf16); its tail is checked here.  inplace: res == out (ldr = ldo), the buffer starts as
     the residual with NaN in its pad columns and rows."""
-    A, W, bias = _strided(a["A"], lda), _t(a["W"]), _t(a["bias"], torch.float32)
+    A, W, bias = _strided(a["A"], lda), to_dev(a["W"], torch.bfloat16), to_dev(a["bias"], torch.float32)
     rows = M + 2
     out = _nan(rows * ldo + 32)
     res = None
@@ -92,7 +56,7 @@ def _gemm(lib, a, M, N, K, epi, lda, ldo, ldr, inplace=False):
         res = out
     elif epi & E.TV_RES:
         res = _strided(a["res"], ldr, M + 1)
-    rc = lib.gitcap_dbg_tv_gemm(_p(A), lda, _p(W), _p(bias), _p(res), ldr, _p(out), ldo, M, N, K, epi, _stream())
+    rc = lib.gitcap_dbg_tv_gemm(ptr(A), lda, ptr(W), ptr(bias), ptr(res), ldr, ptr(out), ldo, M, N, K, epi, stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out[rows * ldo:]).all())
@@ -113,18 +77,18 @@ def test_tv_gemm_against_fp64(lib, M, N, K, epi, wide):
     a, (ref, bound) = _gemm_case(M, N, K, epi)
     lda, ldo, ldr = E.gemm_strides(N, K, wide)
     got = _gemm_written(_gemm(lib, a, M, N, K, epi, lda, ldo, ldr), M, N)
-    _close(_np(got), ref, bound, f"tv_gemm M={M} N={N} K={K} epi={epi} lda={lda} ldo={ldo} ldr={ldr}")
+    close_to_fp64(f64(got), ref, bound, f"tv_gemm M={M} N={N} K={K} epi={epi} lda={lda} ldo={ldo} ldr={ldr}")
 
 
 @pytest.mark.parametrize("M,N,K,epi", [c for c in E.GEMM_CASES if c[3] & E.TV_RES])
 def test_tv_gemm_in_place_residual_gives_the_same_bits(lib, M, N, K, epi):
     """res == out, as the encoder calls it; in both layouts, against the out-of-place launch."""
     a, _ = _gemm_case(M, N, K, epi)
-    want = _bits(_gemm_written(_gemm(lib, a, M, N, K, epi, K, N, N), M, N))
+    want = bf16_bits(_gemm_written(_gemm(lib, a, M, N, K, epi, K, N, N), M, N))
     for wide in (False, True):
         lda, ldo, _ = E.gemm_strides(N, K, wide)
         got = _gemm_written(_gemm(lib, a, M, N, K, epi, lda, ldo, ldo, inplace=True), M, N)
-        assert np.array_equal(_bits(got), want), wide
+        assert np.array_equal(bf16_bits(got), want), wide
 
 
 def test_tv_gemm_hook_rejects_bad_arguments(lib):
@@ -133,7 +97,7 @@ def test_tv_gemm_hook_rejects_bad_arguments(lib):
     out = _nan(64 * 64)
 
     def rc(M=4, N=8, K=32, lda=32, ldo=8, ldr=8, epi=0, res=None, A=x, o=out):
-        return lib.gitcap_dbg_tv_gemm(_p(A), lda, _p(x), _p(b), _p(res), ldr, _p(o), ldo, M, N, K, epi, _stream())
+        return lib.gitcap_dbg_tv_gemm(ptr(A), lda, ptr(x), ptr(b), ptr(res), ldr, ptr(o), ldo, M, N, K, epi, stream())
 
     assert rc(N=6) != 0 and rc(K=48, lda=48) != 0 and rc(lda=36) != 0 and rc(ldo=10) != 0 and rc(ldr=10, epi=E.TV_RES, res=x) != 0
     assert rc(epi=3) != 0 and rc(epi=E.TV_RES_GELU) != 0 and rc(epi=E.TV_GELU | E.TV_RES, res=x) != 0 and rc(epi=8) != 0
@@ -152,22 +116,22 @@ def test_tv_gemm_hook_rejects_bad_arguments(lib):
 @pytest.mark.parametrize("n,H,W,Cin,Kp", E.IM2COL_CASES)
 def test_tv_im2col_is_exact(lib, n, H, W, Cin, Kp, f32_nchw):
     x = E.im2col_inputs(n, H, W, Cin, f32_nchw, seed=n + H + W + Cin)
-    dx = _t(x, torch.float32 if f32_nchw else torch.bfloat16)
+    dx = to_dev(x, torch.float32 if f32_nchw else torch.bfloat16)
     count = n * (H // 2) * (W // 2) * Kp
     out = torch.full((count + 64,), POISON16, device="cuda", dtype=torch.int16)
-    rc = lib.gitcap_dbg_tv_im2col(_p(dx), int(f32_nchw), _p(out), n, H, W, Cin, Kp, _stream())
+    rc = lib.gitcap_dbg_tv_im2col(ptr(dx), int(f32_nchw), ptr(out), n, H, W, Cin, Kp, stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool((out[count:] == POISON16).all())
     want = E.tv_im2col(x, f32_nchw, Kp)
-    assert np.array_equal(out[:count].cpu().numpy().view(np.uint16).reshape(want.shape), _bits(_t(want)).reshape(want.shape))
+    assert np.array_equal(out[:count].cpu().numpy().view(np.uint16).reshape(want.shape), bf16_bits(to_dev(want, torch.bfloat16)).reshape(want.shape))
     assert not out[:count].view(-1, Kp)[:, 9 * Cin:].any()                                  # the pad columns are +0, bit for bit
 
 
 def test_tv_im2col_hook_rejects_bad_arguments(lib):
     x = torch.zeros(4096, device="cuda")
     out = torch.full((4096,), POISON16, device="cuda", dtype=torch.int16)
-    rc = lambda n=1, H=4, W=4, Cin=3, Kp=32, i=x, o=out: lib.gitcap_dbg_tv_im2col(_p(i), 1, _p(o), n, H, W, Cin, Kp, _stream())
+    rc = lambda n=1, H=4, W=4, Cin=3, Kp=32, i=x, o=out: lib.gitcap_dbg_tv_im2col(ptr(i), 1, ptr(o), n, H, W, Cin, Kp, stream())
     assert rc(H=3) != 0 and rc(W=5) != 0 and rc(Kp=26) != 0 and rc(Cin=4) != 0 and rc(n=0) != 0 and rc(i=None) != 0 and rc(o=None) != 0
     torch.cuda.synchronize()
     assert bool((out == POISON16).all())
@@ -179,12 +143,12 @@ def test_tv_im2col_hook_rejects_bad_arguments(lib):
 @pytest.mark.parametrize("n,HW,C", E.NCHW_CASES)
 def test_tv_to_nchw_is_exact(lib, n, HW, C):
     x = E.pool_inputs(n, HW, C, seed=400 + n + HW + C)
-    out, dx = _nan(n * HW * C + 16, torch.float32), _t(x)
-    rc = lib.gitcap_dbg_tv_to_nchw(_p(dx), _p(out), n, HW, C, _stream())
+    out, dx = _nan(n * HW * C + 16, torch.float32), to_dev(x, torch.bfloat16)
+    rc = lib.gitcap_dbg_tv_to_nchw(ptr(dx), ptr(out), n, HW, C, stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out[n * HW * C:]).all())
-    assert np.array_equal(_np(out[:n * HW * C]).reshape(n, C, HW), E.tv_to_nchw(x))
+    assert np.array_equal(f64(out[:n * HW * C]).reshape(n, C, HW), E.tv_to_nchw(x))
 
 
 # ---- tv_dwconv ------------------------------------------------------------------------------------------------------------------------
@@ -194,20 +158,20 @@ def test_tv_dwconv_against_fp64(lib, n, H, W, C, stride, g):
     a = E.dwconv_inputs(n, H, W, C, seed=200 + n + H + W + C)
     count = n * (H // stride) * (W // stride) * C
     out = _nan(count + 64)
-    x, w9, bias = _t(a["x"]), _t(a["w9"], torch.float32), _t(a["bias"], torch.float32)
-    rc = lib.gitcap_dbg_tv_dwconv(_p(x), _p(w9), _p(bias), _p(out), n, H, W, C, stride, int(g), _stream())
+    x, w9, bias = to_dev(a["x"], torch.bfloat16), to_dev(a["w9"], torch.float32), to_dev(a["bias"], torch.float32)
+    rc = lib.gitcap_dbg_tv_dwconv(ptr(x), ptr(w9), ptr(bias), ptr(out), n, H, W, C, stride, int(g), stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out[count:]).all())
     ref, bound = E.tv_dwconv(a["x"], a["w9"], a["bias"], stride, g)
-    _close(_np(out[:count]).reshape(ref.shape), ref, bound, f"tv_dwconv n={n} H={H} W={W} C={C} stride={stride} gelu={g}")
+    close_to_fp64(f64(out[:count]).reshape(ref.shape), ref, bound, f"tv_dwconv n={n} H={H} W={W} C={C} stride={stride} gelu={g}")
 
 
 def test_tv_dwconv_hook_rejects_bad_arguments(lib):
     x = torch.zeros(4096, device="cuda", dtype=torch.bfloat16)
     w = torch.zeros(4096, device="cuda")
     out = _nan(4096)
-    rc = lambda n=1, H=4, W=4, C=8, stride=1, i=x, o=out: lib.gitcap_dbg_tv_dwconv(_p(i), _p(w), _p(w), _p(o), n, H, W, C, stride, 0, _stream())
+    rc = lambda n=1, H=4, W=4, C=8, stride=1, i=x, o=out: lib.gitcap_dbg_tv_dwconv(ptr(i), ptr(w), ptr(w), ptr(o), n, H, W, C, stride, 0, stream())
     assert rc(C=12) != 0 and rc(C=4) != 0 and rc(stride=0) != 0 and rc(stride=3) != 0 and rc(stride=2, H=3) != 0 and rc(stride=2, W=5) != 0
     assert rc(n=0) != 0 and rc(i=None) != 0 and rc(o=None) != 0
     torch.cuda.synchronize()
@@ -224,20 +188,20 @@ def test_tv_ln_against_fp64(lib, M, C):
     """The last row of a case with more than one has a mean of 257 and a spread of 1."""
     q = E.ln_inputs(M, C, seed=300 + M + C)
     out = _nan(M * C + 64)
-    x, g, b = _t(q["x"]), _t(q["g"], torch.float32), _t(q["b"], torch.float32)
-    rc = lib.gitcap_dbg_tv_ln(_p(x), _p(g), _p(b), _p(out), M, C, q["eps"], _stream())
+    x, g, b = to_dev(q["x"], torch.bfloat16), to_dev(q["g"], torch.float32), to_dev(q["b"], torch.float32)
+    rc = lib.gitcap_dbg_tv_ln(ptr(x), ptr(g), ptr(b), ptr(out), M, C, q["eps"], stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out[M * C:]).all())
     ref, bound = E.tv_ln(**q)
-    _close(_np(out[:M * C]).reshape(M, C), ref, bound, f"tv_ln M={M} C={C}")
+    close_to_fp64(f64(out[:M * C]).reshape(M, C), ref, bound, f"tv_ln M={M} C={C}")
 
 
 def test_tv_ln_hook_rejects_bad_arguments(lib):
     x = torch.zeros(8192, device="cuda", dtype=torch.bfloat16)
     g = torch.ones(4096, device="cuda")
     out = _nan(8192)
-    rc = lambda M=2, C=32, i=x, o=out: lib.gitcap_dbg_tv_ln(_p(i), _p(g), _p(g), _p(o), M, C, 1e-5, _stream())
+    rc = lambda M=2, C=32, i=x, o=out: lib.gitcap_dbg_tv_ln(ptr(i), ptr(g), ptr(g), ptr(o), M, C, 1e-5, stream())
     assert rc(C=12) != 0 and rc(C=2056) != 0 and rc(C=4096, M=1) != 0 and rc(M=0) != 0 and rc(C=0) != 0 and rc(i=None) != 0 and rc(o=None) != 0
     torch.cuda.synchronize()
     assert bool(torch.isnan(out).all())
@@ -251,24 +215,24 @@ def test_tv_ln_hook_rejects_bad_arguments(lib):
 @pytest.mark.parametrize("n,HW,C", E.POOL_CASES)
 def test_tv_pool_against_fp64(lib, n, HW, C):
     x = E.pool_inputs(n, HW, C, seed=400 + n + HW + C)
-    mem, dx = _nan(n * C + 16, torch.float32), _t(x)
-    rc = lib.gitcap_dbg_tv_pool(_p(dx), _p(mem), n, HW, C, _stream())
+    mem, dx = _nan(n * C + 16, torch.float32), to_dev(x, torch.bfloat16)
+    rc = lib.gitcap_dbg_tv_pool(ptr(dx), ptr(mem), n, HW, C, stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(mem[n * C:]).all())
     ref, bound = E.tv_pool(x)
-    _close(mem[:n * C].cpu().numpy().astype(np.float64).reshape(n, C), ref, bound + 1e-300, f"tv_pool n={n} HW={HW} C={C}", flips=False)
+    close_to_fp64(mem[:n * C].cpu().numpy().astype(np.float64).reshape(n, C), ref, bound + 1e-300, f"tv_pool n={n} HW={HW} C={C}", flips=False)
 
 
 def test_tv_pool_and_to_nchw_hooks_reject_bad_arguments(lib):
     x = torch.zeros(4096, device="cuda", dtype=torch.bfloat16)
     out = _nan(4096, torch.float32)
     for fn in (lib.gitcap_dbg_tv_pool, lib.gitcap_dbg_tv_to_nchw):
-        rc = lambda n=1, HW=4, C=32, i=x, o=out: fn(_p(i), _p(o), n, HW, C, _stream())
+        rc = lambda n=1, HW=4, C=32, i=x, o=out: fn(ptr(i), ptr(o), n, HW, C, stream())
         assert rc(n=0) != 0 and rc(HW=0) != 0 and rc(C=0) != 0 and rc(i=None) != 0 and rc(o=None) != 0
         torch.cuda.synchronize()
         assert bool(torch.isnan(out).all())
-    assert lib.gitcap_dbg_tv_pool(_p(x), _p(out), 1, 4, 32, _stream()) == 0
+    assert lib.gitcap_dbg_tv_pool(ptr(x), ptr(out), 1, 4, 32, stream()) == 0
     torch.cuda.synchronize()
     assert bool((out[:32] == 0).all()) and bool(torch.isnan(out[32:]).all())
 
@@ -282,20 +246,20 @@ def test_tv_attn_against_fp64(lib, i):
     a = E.tv_attn_inputs(*case, seed=500 + i)
     count = n * H * W * heads * 32
     ctx = _nan(count + 64)
-    qkv, ab = _t(a["qkv"]), _t(a["ab"], torch.float32)
-    rc = lib.gitcap_dbg_tv_attn(_p(qkv), _p(ab), _p(ctx), n, H, W, heads, ws, _stream())
+    qkv, ab = to_dev(a["qkv"], torch.bfloat16), to_dev(a["ab"], torch.float32)
+    rc = lib.gitcap_dbg_tv_attn(ptr(qkv), ptr(ab), ptr(ctx), n, H, W, heads, ws, stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(ctx[count:]).all())
     ref = E.tv_attn(a["qkv"], a["ab"], n, H, W, heads, ws)
-    _close(_np(ctx[:count]).reshape(ref.shape), ref, E.attn_bound(ref, E.DELTA_TV_ATTN_MEASURED), f"tv_attn {case}")
+    close_to_fp64(f64(ctx[:count]).reshape(ref.shape), ref, E.attn_bound(ref, E.DELTA_TV_ATTN_MEASURED), f"tv_attn {case}")
 
 
 def test_tv_attn_hook_rejects_bad_arguments(lib):
     x = torch.zeros(16 * 96, device="cuda", dtype=torch.bfloat16)
     ab = torch.zeros(256, device="cuda")
     ctx = _nan(16 * 32 + 64)
-    rc = lambda n=1, H=4, W=4, heads=1, ws=2, i=x, t=ab, o=ctx: lib.gitcap_dbg_tv_attn(_p(i), _p(t), _p(o), n, H, W, heads, ws, _stream())
+    rc = lambda n=1, H=4, W=4, heads=1, ws=2, i=x, t=ab, o=ctx: lib.gitcap_dbg_tv_attn(ptr(i), ptr(t), ptr(o), n, H, W, heads, ws, stream())
     assert rc(ws=0) != 0 and rc(ws=15, H=15, W=15) != 0 and rc(ws=3) != 0 and rc(H=3, ws=3) != 0 and rc(W=6, ws=4) != 0
     assert rc(n=0) != 0 and rc(heads=0) != 0 and rc(i=None) != 0 and rc(t=None) != 0 and rc(o=None) != 0
     torch.cuda.synchronize()
@@ -319,17 +283,17 @@ def _attn_small(lib, a, **override):
     kv = np.full((rows, kstride, ldkv), np.nan)
     kv[:, :keys, :D] = a["k"].reshape(rows, keys, D)
     kv[:, :keys, D:2 * D] = a["v"].reshape(rows, keys, D)
-    kv = _t(kv)
-    ids = _t(a["ids"], torch.int64)
+    kv = to_dev(kv, torch.bfloat16)
+    ids = to_dev(a["ids"], torch.int64)
     ctx = _nan((M + 1) * ldc + 32)
     g = CDbgAttnSmallArgs()
-    g.q, g.ldq, g.T, g.q_row_stride, g.q_row_off = _p(q).value, ldq, T, a["q_rows"], a["q_row_off"]
-    g.k, g.v, g.ldkv, g.keys_stride, g.nkeys, g.t0 = _p(kv).value, _p(kv).value + 2 * D, ldkv, kstride, a["nkeys"], a["t0"]
-    g.ids, g.ld_ids, g.pad_id = (_p(ids).value if ids is not None else None), keys + 2, a["pad_id"]
-    g.ctx, g.ldc, g.M, g.H, g.hd = _p(ctx).value, ldc, M, H, hd
+    g.q, g.ldq, g.T, g.q_row_stride, g.q_row_off = ptr(q).value, ldq, T, a["q_rows"], a["q_row_off"]
+    g.k, g.v, g.ldkv, g.keys_stride, g.nkeys, g.t0 = ptr(kv).value, ptr(kv).value + 2 * D, ldkv, kstride, a["nkeys"], a["t0"]
+    g.ids, g.ld_ids, g.pad_id = (ptr(ids).value if ids is not None else None), keys + 2, a["pad_id"]
+    g.ctx, g.ldc, g.M, g.H, g.hd = ptr(ctx).value, ldc, M, H, hd
     for k, v in override.items():
         setattr(g, k, v)
-    rc = lib.gitcap_dbg_attn_small(ctypes.byref(g), _stream())
+    rc = lib.gitcap_dbg_attn_small(ctypes.byref(g), stream())
     torch.cuda.synchronize()
     if rc != 0:
         assert bool(torch.isnan(ctx).all())
@@ -337,7 +301,7 @@ def _attn_small(lib, a, **override):
     assert bool(torch.isnan(ctx[M * ldc:]).all())
     buf = ctx[:M * ldc].view(M, ldc)
     assert bool(torch.isnan(buf[:, D:]).all())
-    return 0, _np(buf[:, :D]).reshape(M, H, hd)
+    return 0, f64(buf[:, :D]).reshape(M, H, hd)
 
 
 @pytest.mark.parametrize("with_ids", [False, True])
@@ -354,7 +318,7 @@ def test_attn_small_against_fp64(lib, i, with_ids):
     if i == 0 and with_ids:
         assert not ok.any()
     else:
-        _close(got[ok], ref[ok], E.attn_bound(ref, E.DELTA_ATTN_SMALL_MEASURED)[ok], f"attn_small {case} ids={with_ids}")
+        close_to_fp64(got[ok], ref[ok], E.attn_bound(ref, E.DELTA_ATTN_SMALL_MEASURED)[ok], f"attn_small {case} ids={with_ids}")
 
 
 def test_attn_small_hook_rejects_bad_arguments(lib):
@@ -364,5 +328,5 @@ def test_attn_small_hook_rejects_bad_arguments(lib):
                 dict(v=None), dict(ctx=None)):
         rc, _ = _attn_small(lib, a, **bad)
         assert rc != 0, bad
-    assert lib.gitcap_dbg_attn_small(None, _stream()) != 0
+    assert lib.gitcap_dbg_attn_small(None, stream()) != 0
     assert _attn_small(lib, a)[0] == 0

@@ -17,6 +17,7 @@ import torch
 from gitcap.config import git_tiny
 from gitcap.student_config import student_synthetic_weights, student_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import camera, stream
 from oracle.git_oracle import make_frames
 from oracle.student_oracle import make_memory
 
@@ -27,11 +28,8 @@ POISON = -4321.0
 
 
 def _p(t, off=0):
+    """gpu_support.ptr with a byte offset: the misaligned buffers the entry points must refuse"""
     return ctypes.c_void_p(t.data_ptr() + off) if t is not None else None
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- teacher ---------------------------------------------------------------------------------------------------------------------
@@ -48,7 +46,7 @@ class _Teacher:
                               max_beams=2, stop="never")
         self.lib, self.h = self.m._lib, self.m._handle
         self.f32 = make_frames(2, 2, cfg.image_size, 1234).cuda()
-        self.u8 = torch.randint(0, 256, (2, 2, 80, 96, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(5)).cuda()
+        self.u8 = camera((2, 2, 80, 96, 3), 5).cuda()
         self.ids = torch.full((2, L + 1), -1, dtype=torch.int64, device="cuda")
         self.steps = torch.zeros(1, dtype=torch.int32, device="cuda")
         self.dec = torch.zeros((2, 16), dtype=torch.int64, device="cuda")
@@ -69,10 +67,10 @@ class _Teacher:
         src = (_p(self.u8) if raw else _p(self.f32)) if src == "own" else src
         tk = ctypes.c_int(-1)
         args = [self.h if h else None, src, B, F] + ([H, W] if raw else []) + [max_len, stop, _p(self.ids) if ids == "own" else ids,
-                                                                              _p(self.steps), _st()]
+                                                                              _p(self.steps), stream()]
         rc = getattr(self.lib, name)(*args, *([ctypes.byref(tk) if ticket else None] if sub else []))
         if sub and rc == 0:
-            assert self.lib.gitcap_greedy_wait(self.h, tk.value, _st()) == 0
+            assert self.lib.gitcap_greedy_wait(self.h, tk.value, stream()) == 0
         return rc
 
     def beam(self, name, h=True, src="own", B=2, F=2, H=80, W=96, beams=2, steps=L, pnb=2, dec="own", blp="own", ticket=True):
@@ -81,16 +79,16 @@ class _Teacher:
         tk = ctypes.c_int(-1)
         args = [self.h if h else None, src, B, F] + ([H, W] if raw else []) + ([None] if sub else [])
         args += [beams, steps, 1.0, pnb, _p(self.dec) if dec == "own" else dec, _p(self.blp) if blp == "own" else blp]
-        args += ([None] if sub else []) + [_st()] + ([ctypes.byref(tk) if ticket else None] if sub else [])
+        args += ([None] if sub else []) + [stream()] + ([ctypes.byref(tk) if ticket else None] if sub else [])
         return getattr(self.lib, name)(*args)
 
     def window_greedy(self, h=True, max_len=L, stop=0, vis=None, ids="own"):
         return self.lib.gitcap_window_greedy(self.h if h else None, max_len, stop, vis, _p(self.ids) if ids == "own" else ids,
-                                             _p(self.steps), _st())
+                                             _p(self.steps), stream())
 
     def window_beam(self, h=True, beams=2, steps=L, pnb=2, vis=None, dec="own"):
         return self.lib.gitcap_window_beam_search(self.h if h else None, beams, steps, 1.0, pnb, vis,
-                                                  _p(self.dec) if dec == "own" else dec, _p(self.blp), _st())
+                                                  _p(self.dec) if dec == "own" else dec, _p(self.blp), stream())
 
 
 def _teacher_observed():
@@ -167,10 +165,10 @@ def _teacher_observed():
     t.rec("gitcap_window_greedy: empty window", t.window_greedy())
     t.rec("gitcap_window_beam_search: empty window", t.window_beam())
     one = t.f32[:, :1].contiguous()
-    assert t.lib.gitcap_window_push(t.h, _p(one), 2, 1, _st()) == 0
+    assert t.lib.gitcap_window_push(t.h, _p(one), 2, 1, stream()) == 0
     t.rec("gitcap_window_greedy: 1 of 2 frames", t.window_greedy())
     t.rec("gitcap_window_beam_search: 1 of 2 frames", t.window_beam())
-    assert t.lib.gitcap_window_push(t.h, _p(one), 2, 1, _st()) == 0
+    assert t.lib.gitcap_window_push(t.h, _p(one), 2, 1, stream()) == 0
     t.rec("gitcap_window_greedy: misaligned visual_out", t.window_greedy(vis=_p(t.vis, 4)))
     t.rec("gitcap_window_beam_search: misaligned visual_out", t.window_beam(vis=_p(t.vis, 4)))
     t.lp.fill_(POISON)
@@ -228,7 +226,7 @@ class _Student:
         args += [max_len, stop, _p(self.ids) if ids == "own" else ids, _p(self.steps)]
         if "draft" in name:
             args += [None]
-        return getattr(self.lib, name)(*args, _st())
+        return getattr(self.lib, name)(*args, stream())
 
 
 def _student_observed():
@@ -266,12 +264,12 @@ def _student_observed():
     for name in STUDENT[1::2]:
         t.rec(f"{name}: empty window", t.call(name))
     part = t.mem[:, :F - 1].contiguous()
-    assert t.lib.gitcap_student_window_push(t.h, _p(part), 2, F - 1, _st()) == 0
+    assert t.lib.gitcap_student_window_push(t.h, _p(part), 2, F - 1, stream()) == 0
     for name in STUDENT[1::2]:
         t.rec(f"{name}: F - 1 tokens", t.call(name))
         t.rec(f"{name}: F - 1 tokens, stop 7", t.call(name, stop=7))
     t.rec("gitcap_student_window_greedy_draft: F - 1 tokens, n_draft 0", t.call(STUDENT[3], n=0))
-    assert t.lib.gitcap_student_window_push(t.h, _p(t.mem[:, F - 1:].contiguous()), 2, 1, _st()) == 0
+    assert t.lib.gitcap_student_window_push(t.h, _p(t.mem[:, F - 1:].contiguous()), 2, 1, stream()) == 0
     for name in STUDENT:
         if "window" in name:
             checks(name, "full window")

@@ -4,8 +4,6 @@ gated caption streams of StudentCaptioner and GitCaptioner against ungated strea
 ssd and the histograms are integers: exact equality.  mse and chisq: relative 1e-12 -- a bound, not a fit: at most 256 fp64
 additions and one division per term, a few hundred units of 2^-53 ~ 1e-16, with two orders of room; and 0 must be exactly 0.
 Captions are compared with torch.equal."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -15,6 +13,7 @@ from gitcap.config import git_tiny
 from gitcap.student_config import student_base, student_synthetic_weights, student_tiny
 from gitcap.tinyvit_config import tinyvit_config, tinyvit_synthetic_weights, tinyvit_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import ptr, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +21,7 @@ ERR_ARG = -1
 REL = 1e-12
 
 
-def _p(t):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
-
-
-def _close(got, want):
+def _near(got, want):
     return abs(got - want) <= REL * abs(want)          # want == 0: got must be exactly 0
 
 
@@ -42,7 +37,7 @@ def _check(frames, ref, channel, what):
     for key in ("mse", "chisq"):
         g = got[key].tolist()
         print(f"{what} {key}: device {g} restatement {want[key]}")
-        assert all(_close(a, b) for a, b in zip(g, want[key])), (what, key, g, want[key])
+        assert all(_near(a, b) for a, b in zip(g, want[key])), (what, key, g, want[key])
 
 
 @pytest.mark.parametrize("B", [1, 2, 7])
@@ -93,7 +88,7 @@ def test_frame_change_at_any_alignment():
         assert got["ssd"].tolist() == want["ssd"], (off_f, off_r)
         assert np.array_equal(got["hist_frame"].cpu().numpy(), want["hist_frame"]), (off_f, off_r)
         assert np.array_equal(got["hist_ref"].cpu().numpy(), want["hist_ref"]), (off_f, off_r)
-        assert all(_close(x, y) for x, y in zip(got["chisq"].tolist(), want["chisq"])), (off_f, off_r)
+        assert all(_near(x, y) for x, y in zip(got["chisq"].tolist(), want["chisq"])), (off_f, off_r)
         ran += 1
     assert ran == 8
 
@@ -108,12 +103,12 @@ def test_frame_change_null_outputs_and_bad_arguments():
     f, r = torch.from_numpy(f_np).cuda(), torch.from_numpy(r_np).cuda()
     want = R.frame_change(f_np, r_np, 2)
     full = frame_change(f, r, 2)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
     # every output alone (the other four null), through the binding; all null: accepted, nothing to do
     for key in OUTPUTS:
         one = frame_change(f, r, 2, outputs=(key,))
         assert list(one) == [key] and torch.equal(one[key], full[key]), key
-    assert full["ssd"].tolist() == want["ssd"] and all(_close(a, b) for a, b in zip(full["chisq"].tolist(), want["chisq"]))
+    assert full["ssd"].tolist() == want["ssd"] and all(_near(a, b) for a, b in zip(full["chisq"].tolist(), want["chisq"]))
     assert frame_change(f, r, 2, outputs=()) == {}
     # a side stream: ordered on that stream, same numbers
     side = torch.cuda.Stream()
@@ -124,13 +119,13 @@ def test_frame_change_null_outputs_and_bad_arguments():
     assert all(torch.equal(on_side[k], full[k]) for k in OUTPUTS)
     # bad arguments: refused, nothing is launched and the guard word behind the output stays
     out = torch.full((B + 1,), -7, dtype=torch.int64, device="cuda")
-    call = lambda fp, rp, b, h, w, ch: lib.gitcap_frame_change(fp, rp, b, h, w, ch, _p(out), None, None, None, None, st)
-    for args in ((None, _p(r), B, H, W, 2), (_p(f), None, B, H, W, 2), (_p(f), _p(r), 0, H, W, 2), (_p(f), _p(r), -1, H, W, 2),
-                 (_p(f), _p(r), B, 0, W, 2), (_p(f), _p(r), B, H, 0, 2), (_p(f), _p(r), B, H, W, 3), (_p(f), _p(r), B, H, W, -1)):
+    call = lambda fp, rp, b, h, w, ch: lib.gitcap_frame_change(fp, rp, b, h, w, ch, ptr(out), None, None, None, None, st)
+    for args in ((None, ptr(r), B, H, W, 2), (ptr(f), None, B, H, W, 2), (ptr(f), ptr(r), 0, H, W, 2), (ptr(f), ptr(r), -1, H, W, 2),
+                 (ptr(f), ptr(r), B, 0, W, 2), (ptr(f), ptr(r), B, H, 0, 2), (ptr(f), ptr(r), B, H, W, 3), (ptr(f), ptr(r), B, H, W, -1)):
         assert call(*args) == ERR_ARG, args
     torch.cuda.synchronize()
     assert out.tolist() == [-7] * (B + 1)
-    assert call(_p(f), _p(r), B, H, W, 2) == 0
+    assert call(ptr(f), ptr(r), B, H, W, 2) == 0
     torch.cuda.synchronize()
     assert out.tolist() == want["ssd"] + [-7]
     with pytest.raises(ValueError):
@@ -266,7 +261,7 @@ def test_gated_stream_captions_what_the_restatement_admits(name, B, metric):
         if last:                                         # the distances of the last looked-at frame, from the device
             dev = gate.stats["last_distance"]
             print(f"{name} B={B} {metric} frame {idx[-1]}: device {dev} restatement {last[-1]}")
-            assert all(_close(a, b) for a, b in zip(dev, last[-1])), (idx, dev, last[-1])
+            assert all(_near(a, b) for a, b in zip(dev, last[-1])), (idx, dev, last[-1])
     assert seen == admitted, (seen, admitted)
     assert gate.stats["pushed"] == feed.shape[1] and gate.stats["admitted"] == len(admitted)
     assert gate.stats["looked_at"] == len(looked) + 1

@@ -10,20 +10,9 @@ import torch
 from gitcap.config import git_base, git_tiny
 from gitcap.weights import synthetic_weights
 from oracle.git_oracle import make_frames
+from gpu_support import camera, captioner_cls, ptr, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
-
-
-def _camera(b, f, h, w, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, 256, (b, f, h, w, 3), dtype=torch.uint8, generator=g)
 
 
 @pytest.mark.parametrize("size", ["tiny", "base"])
@@ -35,7 +24,7 @@ def test_host_fed_greedy_bitwise(captioner_cls, size):
     S = cfg.image_size
     m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=4, max_frames=2, max_text_len=10, stop="never")
     f32 = [make_frames(b, 2, S, 900 + i) for i, b in enumerate((4, 3, 1))]
-    cams = [_camera(4, 2, S, S, 1), _camera(2, 2, 240, 320, 2), _camera(3, 2, 300, 224, 3)]
+    cams = [camera((4, 2, S, S, 3), 1), camera((2, 2, 240, 320, 3), 2), camera((3, 2, 300, 224, 3), 3)]
     cases = []
     for x in f32:
         cases += [("f32 pageable", x), ("f32 pinned", x.clone().pin_memory()), ("f32 device", x.cuda())]
@@ -88,7 +77,7 @@ def test_host_fed_beam_search_and_teacher_forward(captioner_cls):
     S = cfg.image_size
     m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=4, max_frames=2, max_text_len=12, max_beams=4, stop="never")
     x = make_frames(4, 2, S, 31)
-    cam = _camera(3, 2, 260, 300, 5)
+    cam = camera((3, 2, 260, 300, 3), 5)
     from gitcap.preprocess import preprocess_frames
     cam_pre = preprocess_frames(cam, S)
     kw = dict(beam_size=4, max_steps=10)
@@ -123,7 +112,7 @@ def test_host_fed_bench_shape_bitwise(captioner_cls):
     flight, more batches than ring entries): ids bitwise the synchronous raw call's."""
     cfg = git_base(6)
     m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=16, max_frames=6, max_text_len=20, stop="never")
-    ins = [_camera(16, 6, 224, 224, 40 + i).pin_memory() for i in range(3)]
+    ins = [camera((16, 6, 224, 224, 3), 40 + i).pin_memory() for i in range(3)]
     want = [m.greedy_decode(x.cuda(), max_len=20).cpu().clone() for x in ins]
     pend, bad = [], []
     for i in range(10):
@@ -172,13 +161,13 @@ def test_refused_submissions_leave_the_pipeline_usable(captioner_cls):
     cfg = git_tiny(2)
     m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=10, stop="never")
     x = make_frames(2, 2, cfg.image_size, 11).cuda()
-    cam = _camera(2, 2, 80, 96, 4).cuda()
+    cam = camera((2, 2, 80, 96, 3), 4).cuda()
     want_x, want_c = m.greedy_decode(x, max_len=9).clone(), m.greedy_decode(cam, max_len=9).clone()
     ids = torch.empty((4, 10), dtype=torch.int64, device="cuda")
     steps = torch.zeros((1,), dtype=torch.int32, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
     tk = ctypes.c_int(-7)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    p = ptr
     futs = [m.greedy_decode_async(x, max_len=9), m.greedy_decode_async(cam, max_len=9)]
     assert lib.gitcap_greedy_raw_submit(m._handle, p(cam), 2, 2, 0, 96, 9, 0, p(ids), p(steps), st, ctypes.byref(tk)) == -1      # H = 0
     assert b"raw frames" in lib.gitcap_last_error(m._handle) and tk.value == -7

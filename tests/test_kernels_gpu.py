@@ -7,22 +7,9 @@ import ctypes
 import pytest
 import torch
 
+from gpu_support import lib, ptr, stream  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @pytest.mark.parametrize("tile", [64, 128, 256])
@@ -37,7 +24,7 @@ def test_gemm_vs_fp32_reference(lib, tile, M, N, K, epi):
     bias = torch.linspace(-1, 1, N, device="cuda")
     resid = torch.randn(M, N, device="cuda", generator=g) if epi == 3 else None
     out = torch.empty(M, N, device="cuda", dtype=torch.float32 if epi in (3, 4) else torch.bfloat16)
-    rc = lib.gitcap_dbg_gemm(_p(A), _p(W), _p(bias), _p(resid), _p(out), M, N, K, epi, tile, _stream())
+    rc = lib.gitcap_dbg_gemm(ptr(A), ptr(W), ptr(bias), ptr(resid), ptr(out), M, N, K, epi, tile, stream())
     assert rc == 0
     ref = A.float() @ W.float().t() + bias
     if epi == 1:
@@ -59,7 +46,7 @@ def test_gemm_identity_weight_asymmetric_input(lib):
     W = torch.eye(N, K, device="cuda").bfloat16()
     for tile in (64, 128, 256):
         out = torch.empty(M, N, device="cuda", dtype=torch.float32)
-        assert lib.gitcap_dbg_gemm(_p(A), _p(W), None, None, _p(out), M, N, K, 4, tile, _stream()) == 0
+        assert lib.gitcap_dbg_gemm(ptr(A), ptr(W), None, None, ptr(out), M, N, K, 4, tile, stream()) == 0
         assert torch.equal(out, A.float())
 
 
@@ -77,7 +64,7 @@ def test_gemm_tile_variants_are_bitwise_equal(lib):
         outs = []
         for tile in (256, 128, 64):
             out = torch.empty(M, N, device="cuda", dtype=dt)
-            assert lib.gitcap_dbg_gemm(_p(A), _p(W), _p(bias), _p(resid), _p(out), M, N, K, epi, tile, _stream()) == 0
+            assert lib.gitcap_dbg_gemm(ptr(A), ptr(W), ptr(bias), ptr(resid), ptr(out), M, N, K, epi, tile, stream()) == 0
             outs.append(out)
         for o in outs[1:]:
             assert torch.equal(outs[0], o)
@@ -104,8 +91,8 @@ def test_gemm_layernorm_epilogue_equals_gemm_then_layernorm(lib, M, N, K, post, 
         of = torch.full((M, N), float("nan"), device="cuda")
         ob = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
         for _ in range(2):          # twice: the exchange barrier must be reusable
-            assert lib.gitcap_dbg_gemm_ln(_p(A), _p(W), _p(bias), _p(resid), _p(gamma), _p(beta), ctypes.c_float(1e-5), _p(of), _p(ob),
-                                          M, N, K, post, fused, tile, _stream()) == 0
+            assert lib.gitcap_dbg_gemm_ln(ptr(A), ptr(W), ptr(bias), ptr(resid), ptr(gamma), ptr(beta), ctypes.c_float(1e-5), ptr(of), ptr(ob),
+                                          M, N, K, post, fused, tile, stream()) == 0
         torch.cuda.synchronize()
         outs.append((of, ob))
     for of, ob in outs[1:]:
@@ -123,7 +110,7 @@ def test_attn_full_vs_reference(lib, G, S, H):
     g = torch.Generator(device="cuda").manual_seed(S)
     qkv = (torch.randn(G * S, 3 * W, device="cuda", generator=g) * 1.5).bfloat16()
     ctx = torch.zeros(G * S, W, device="cuda", dtype=torch.bfloat16)
-    assert lib.gitcap_dbg_attn_full(_p(qkv), _p(ctx), G, S, H, _stream()) == 0
+    assert lib.gitcap_dbg_attn_full(ptr(qkv), ptr(ctx), G, S, H, stream()) == 0
     q, k, v = (t.float().view(G, S, H, 64).transpose(1, 2) for t in qkv.split(W, dim=1))
     s = q @ k.transpose(-1, -2) * 0.125
     p = torch.exp(s - s.max(-1, keepdim=True).values)
@@ -143,7 +130,7 @@ def test_attn_full_forced_rescale(lib):
     qkv[:, 128:192] = torch.arange(S, device="cuda", dtype=torch.float32)[:, None] / S
     qkv = qkv.bfloat16()
     ctx = torch.zeros(S, 64, device="cuda", dtype=torch.bfloat16)
-    assert lib.gitcap_dbg_attn_full(_p(qkv), _p(ctx), G, S, H, _stream()) == 0
+    assert lib.gitcap_dbg_attn_full(ptr(qkv), ptr(ctx), G, S, H, stream()) == 0
     q, k, v = (t.float() for t in qkv.split(64, dim=1))
     ref = torch.softmax(q @ k.t() * 0.125, -1) @ v
     assert (ctx.float() - ref).abs().max().item() < 1e-2
@@ -155,7 +142,7 @@ def test_layernorm_vs_reference(lib, rows, D):
     gamma, beta = torch.randn(D, device="cuda"), torch.randn(D, device="cuda")
     of = torch.empty_like(x)
     ob = torch.empty(rows, D, device="cuda", dtype=torch.bfloat16)
-    assert lib.gitcap_dbg_layernorm(_p(x), _p(gamma), _p(beta), ctypes.c_float(1e-5), rows, D, _p(of), _p(ob), _stream()) == 0
+    assert lib.gitcap_dbg_layernorm(ptr(x), ptr(gamma), ptr(beta), ctypes.c_float(1e-5), rows, D, ptr(of), ptr(ob), stream()) == 0
     ref = torch.nn.functional.layer_norm(x, (D,), gamma, beta, 1e-5)
     assert torch.allclose(of, ref, rtol=1e-5, atol=1e-5)
     assert torch.equal(ob, of.bfloat16())
@@ -175,12 +162,12 @@ def test_gemm_fp8_vs_fp32_reference(lib, M, N, K):
     bias = torch.linspace(-1, 1, N, device="cuda")
     ref = (A8.float() * ascale) @ (W8.float() * wscale[:, None]).t() + bias
     out = torch.empty(M, N, device="cuda", dtype=torch.float32)
-    rc = lib.gitcap_dbg_gemm_f8(_p(A8), _p(W8), _p(wscale), ascale, _p(bias), _p(out), M, N, K, 4, 0.0, _stream())
+    rc = lib.gitcap_dbg_gemm_f8(ptr(A8), ptr(W8), ptr(wscale), ascale, ptr(bias), ptr(out), M, N, K, 4, 0.0, stream())
     assert rc == 0
     assert torch.allclose(out, ref, rtol=1e-3, atol=1e-3), float((out - ref).abs().max())
     for epi, act in ((8, lambda x: x * torch.sigmoid(1.702 * x)), (9, torch.nn.functional.gelu)):
         o8 = torch.empty(M, N, device="cuda", dtype=torch.uint8)
-        assert lib.gitcap_dbg_gemm_f8(_p(A8), _p(W8), _p(wscale), ascale, _p(bias), _p(o8), M, N, K, epi, 16.0, _stream()) == 0
+        assert lib.gitcap_dbg_gemm_f8(ptr(A8), ptr(W8), ptr(wscale), ascale, ptr(bias), ptr(o8), M, N, K, epi, 16.0, stream()) == 0
         got = o8.view(torch.float8_e4m3fn).float() / 16.0
         want = (act(ref) * 16.0).clamp(-448, 448).to(torch.float8_e4m3fn).float() / 16.0
         # a value on an e4m3 rounding boundary may fall either way (the GELU differs in the last bits): one e4m3 step

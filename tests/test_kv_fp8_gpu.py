@@ -16,26 +16,15 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stress_layers import device_stages, ulps_of_rowmax                                   # noqa: E402
-from test_stress_layers_gpu import TOL_DEC_MAX_ULP, TOL_RMS_ULP                            # noqa: E402
+from stress_layers import TOL_DEC_MAX_ULP, TOL_RMS_ULP, device_stages, ulps_of_rowmax       # noqa: E402
 
 from gitcap.config import git_base                                                         # noqa: E402
 from gitcap.weights import stress_weights, synthetic_weights                               # noqa: E402
 from oracle.git_oracle import GitOracle, make_frames                                       # noqa: E402
+from gpu_support import captioner_cls, rms                                                 # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 LOGIT_TOL_EMUL = 0.08                    # tests/test_parity_gpu.py
-
-
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
-
-
-def _rms(t):
-    return float(t.double().pow(2).mean().sqrt())
 
 
 @pytest.mark.parametrize("family", ["plain", "stress"])
@@ -57,7 +46,7 @@ def test_v_e4m3_text_rows_track_their_oracle_per_layer(captioner_cls, family):
         for l in range(cfg.dec_layers):
             got = hid[:, l + 1, S_img:]
             a, b = own.dec_layer_text(l, hid[:, l], S_img), bf.dec_layer_text(l, hid[:, l], S_img)
-            rows.append((l, ulps_of_rowmax(got, a), _rms(got - a), _rms(got - b)))
+            rows.append((l, ulps_of_rowmax(got, a), rms(got - a), rms(got - b)))
         # the image rows are untouched by the mode: same single-stage tolerance against the plain emulating oracle
         for l in range(cfg.dec_layers):
             e = ulps_of_rowmax(hid[:, l + 1, :S_img], bf.dec_layer_img(l, hid[:, l, :S_img]))

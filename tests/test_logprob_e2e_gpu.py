@@ -12,8 +12,8 @@ import torch
 
 from gitcap.config import git_tiny
 from gitcap.student_config import student_synthetic_weights, student_tiny
-from gitcap.tinyvit_config import tinyvit_synthetic_weights, tinyvit_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import camera, captioner_cls, make_student_native, ptr, stream  # noqa: F401
 from oracle.git_oracle import make_frames
 from oracle.student_oracle import make_memory
 
@@ -26,22 +26,12 @@ MAX_LEN = 8
 POISON = -4321.0
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 # ---- teacher --------------------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
-def teacher():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+def teacher(captioner_cls):
     cfg = git_tiny(2)
-    m = GitCaptioner(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=MAX_LEN, stop="never")
+    m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=MAX_LEN, stop="never")
     fr = make_frames(2, 2, cfg.image_size, 1234).cuda()
     plain = m.greedy_decode(fr, max_len=MAX_LEN).clone()
     ids, lp = m.greedy_decode(fr, max_len=MAX_LEN, return_logprobs=True)
@@ -56,8 +46,8 @@ def _c_greedy(m, name, frames, B, extra=(), lp_ld=MAX_LEN + 2, attach=True):
     lp = torch.full((B, MAX_LEN + 2), POISON, device="cuda")
     assert lp_ld <= MAX_LEN + 2
     if attach:
-        assert m._lib.gitcap_attach_token_logprobs(m._handle, _p(lp), lp_ld) == 0
-    rc = getattr(m._lib, name)(m._handle, _p(frames), B, 2, *extra, MAX_LEN, STOP_NEVER, _p(ids), _p(steps), _st())
+        assert m._lib.gitcap_attach_token_logprobs(m._handle, ptr(lp), lp_ld) == 0
+    rc = getattr(m._lib, name)(m._handle, ptr(frames), B, 2, *extra, MAX_LEN, STOP_NEVER, ptr(ids), ptr(steps), stream())
     torch.cuda.synchronize()
     return rc, ids, lp
 
@@ -86,8 +76,7 @@ def test_teacher_logprobs_vs_teacher_forced_logits(teacher, B):
 def test_teacher_logprobs_are_the_same_through_every_entry_point(teacher):
     m, cfg, fr, plain, ids2, lp2 = teacher
     from gitcap.preprocess import preprocess_frames
-    g = torch.Generator().manual_seed(5)
-    cam = torch.randint(0, 256, (2, 2, 80, 96, 3), dtype=torch.uint8, generator=g).cuda()
+    cam = camera((2, 2, 80, 96, 3), 5).cuda()
     pre = preprocess_frames(cam, cfg.image_size).contiguous()
     # gitcap_greedy on the transformed frames == gitcap_greedy_raw on the camera frames
     rc, ids_a, lp_a = _c_greedy(m, "gitcap_greedy", pre, 2)
@@ -103,11 +92,11 @@ def test_teacher_logprobs_are_the_same_through_every_entry_point(teacher):
         steps = torch.zeros(1, dtype=torch.int32, device="cuda")
         lp = torch.full((2, MAX_LEN + 3), POISON, device="cuda")
         tk = ctypes.c_int(-1)
-        assert m._lib.gitcap_attach_token_logprobs(m._handle, _p(lp), MAX_LEN + 3) == 0
-        assert m._lib.gitcap_greedy_submit(m._handle, _p(x), 2, 2, MAX_LEN, STOP_NEVER, _p(ids), _p(steps), _st(), ctypes.byref(tk)) == 0
+        assert m._lib.gitcap_attach_token_logprobs(m._handle, ptr(lp), MAX_LEN + 3) == 0
+        assert m._lib.gitcap_greedy_submit(m._handle, ptr(x), 2, 2, MAX_LEN, STOP_NEVER, ptr(ids), ptr(steps), stream(), ctypes.byref(tk)) == 0
         bufs.append((tk.value, ids, lp, steps))
     for tk, _, _, _ in bufs:
-        assert m._lib.gitcap_greedy_wait(m._handle, tk, _st()) == 0
+        assert m._lib.gitcap_greedy_wait(m._handle, tk, stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(bufs[0][1], ids2) and torch.equal(bufs[0][2][:, :MAX_LEN], lp2)
     assert torch.equal(bufs[1][1], ids_a) and torch.equal(bufs[1][2][:, :MAX_LEN], lp_a[:, :MAX_LEN])
@@ -132,13 +121,13 @@ def test_teacher_attachment_is_one_shot_and_checked(teacher):
     assert rc == 0 and torch.equal(ids, ids2) and bool((lp == POISON).all())
     # a pending attachment survives gitcap_encode, and is consumed by the greedy call behind it
     lp = torch.full((2, MAX_LEN), POISON, device="cuda")
-    assert lib.gitcap_attach_token_logprobs(h, _p(lp), MAX_LEN) == 0
-    assert lib.gitcap_encode(h, _p(fr), 2, 2, None, _st()) == 0
+    assert lib.gitcap_attach_token_logprobs(h, ptr(lp), MAX_LEN) == 0
+    assert lib.gitcap_encode(h, ptr(fr), 2, 2, None, stream()) == 0
     rc, ids, _ = _c_greedy(m, "gitcap_greedy", fr, 2, attach=False)
     assert rc == 0 and torch.equal(lp, lp2)
     # NULL detaches
     lp.fill_(POISON)
-    assert lib.gitcap_attach_token_logprobs(h, _p(lp), MAX_LEN) == 0 and lib.gitcap_attach_token_logprobs(h, None, 0) == 0
+    assert lib.gitcap_attach_token_logprobs(h, ptr(lp), MAX_LEN) == 0 and lib.gitcap_attach_token_logprobs(h, None, 0) == 0
     rc, ids, _ = _c_greedy(m, "gitcap_greedy", fr, 2, attach=False)
     assert rc == 0 and bool((lp == POISON).all())
     # ld < max_len: the ARG error at the consuming call, nothing written, and the attachment is consumed all the same
@@ -148,7 +137,7 @@ def test_teacher_attachment_is_one_shot_and_checked(teacher):
     rc, ids, _ = _c_greedy(m, "gitcap_greedy", fr, 2, attach=False)
     assert rc == 0 and torch.equal(ids, ids2) and bool((lp == POISON).all())
     # bad attachments
-    assert lib.gitcap_attach_token_logprobs(h, _p(lp), 0) == ERR_ARG
+    assert lib.gitcap_attach_token_logprobs(h, ptr(lp), 0) == ERR_ARG
     assert lib.gitcap_attach_token_logprobs(h, ctypes.c_void_p(lp.data_ptr() + 2), MAX_LEN) == ERR_ARG
     rc, ids, _ = _c_greedy(m, "gitcap_greedy", fr, 2, attach=False)             # neither left anything pending
     assert rc == 0 and bool((lp == POISON).all())
@@ -223,16 +212,16 @@ def test_student_attachment_is_checked(student):
     lp = torch.full((3, S_LEN), POISON, device="cuda")
     ids = torch.full((3, S_LEN + 1), -1, dtype=torch.int64, device="cuda")
     steps = torch.zeros(1, dtype=torch.int32, device="cuda")
-    assert lib.gitcap_student_attach_token_logprobs(h, _p(lp), 0) == ERR_ARG
-    assert lib.gitcap_student_attach_token_logprobs(h, _p(lp), S_LEN - 1) == 0
-    assert lib.gitcap_student_greedy(h, _p(mem), 3, S_LEN, STOP_NEVER, _p(ids), _p(steps), _st()) == ERR_ARG
-    assert lib.gitcap_student_greedy(h, _p(mem), 3, S_LEN, STOP_NEVER, _p(ids), _p(steps), _st()) == 0      # consumed by the failure
+    assert lib.gitcap_student_attach_token_logprobs(h, ptr(lp), 0) == ERR_ARG
+    assert lib.gitcap_student_attach_token_logprobs(h, ptr(lp), S_LEN - 1) == 0
+    assert lib.gitcap_student_greedy(h, ptr(mem), 3, S_LEN, STOP_NEVER, ptr(ids), ptr(steps), stream()) == ERR_ARG
+    assert lib.gitcap_student_greedy(h, ptr(mem), 3, S_LEN, STOP_NEVER, ptr(ids), ptr(steps), stream()) == 0      # consumed by the failure
     torch.cuda.synchronize()
     assert bool((lp == POISON).all()) and torch.equal(ids, plain)
     # ld > max_len: the columns behind max_len stay as they were
     wide = torch.full((3, S_LEN + 4), POISON, device="cuda")
-    assert lib.gitcap_student_attach_token_logprobs(h, _p(wide), S_LEN + 4) == 0
-    assert lib.gitcap_student_greedy(h, _p(mem), 3, S_LEN, STOP_NEVER, _p(ids), _p(steps), _st()) == 0
+    assert lib.gitcap_student_attach_token_logprobs(h, ptr(wide), S_LEN + 4) == 0
+    assert lib.gitcap_student_greedy(h, ptr(mem), 3, S_LEN, STOP_NEVER, ptr(ids), ptr(steps), stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(wide[:, :S_LEN], lp3) and bool((wide[:, S_LEN:] == POISON).all())
 
@@ -240,17 +229,10 @@ def test_student_attachment_is_checked(student):
 def test_student_stream_logprobs_with_carry():
     from gitcap import caption_confidence
     from gitcap.student import StudentCaptioner
-    from gitcap.tinyvit import TinyViTEncoder
 
-    def native():
-        tcfg, scfg = tinyvit_tiny(), student_tiny()
-        w = dict(student_synthetic_weights(scfg, 0))
-        w.update({"image_encoder.model." + k: v for k, v in tinyvit_synthetic_weights(tcfg, 0).items()})
-        enc = TinyViTEncoder(tcfg, device="cuda:0", max_frames=2 * scfg.mem_tokens)
-        return StudentCaptioner(cfg=scfg, weights=w, image_encoder=enc, device="cuda:0", max_batch=2, max_text_len=16)
-    ma, mb = native(), native()
+    ma, mb = (make_student_native("tiny", max_batch=2, max_text_len=16) for _ in range(2))
     F, max_len, n = ma.cfg.mem_tokens, 8, ma.cfg.mem_tokens + 4
-    cam = torch.randint(0, 256, (1, n, 64, 80, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(3))
+    cam = camera((1, n, 64, 80, 3), 3)
     cam[:, F:F + 3] = cam[:, F:F + 1]                   # a repeated frame: the carried draft is accepted for a while
     cam = cam.cuda()
     with pytest.raises(ValueError):

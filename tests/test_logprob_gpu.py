@@ -20,7 +20,8 @@ import torch
 
 import logprob_reference as L
 import selection_reference as R
-from test_selection_gpu import DRAFT_NT, DRAFT_SEP, _draft_scenario, _draft_scenarios
+from selection_reference import DRAFT_NT, DRAFT_SEP, draft_scenario, draft_scenarios
+from gpu_support import lib, ptr, run_vocab_head, softmax_head_inputs, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,74 +29,12 @@ TOL = 2e-5
 NINF = float("-inf")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
-
-
 # ---- a. / b. the head's third partial ---------------------------------------------------------------------------------------
-
-def _head_inputs(M, N, K, fp8, seed, ninf=False):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Np = (N + 15) // 16 * 16
-    X = torch.randn(M, K, device="cuda", generator=g).bfloat16()
-    Wf = torch.randn(Np, K, device="cuda", generator=g) * (3.0 / K ** 0.5)        # logits of a few units: a softmax with a shape
-    bias = torch.randn(N, device="cuda", generator=g)
-    for n in range(N, Np):                          # padding rows: a missing n < N guard would put e^large into the last tile's sum
-        Wf[n] = 4.0 * X[n % M].float()
-    if ninf:
-        if N >= 32:
-            bias[16:32] = NINF                      # a whole tile: the 0-sum rule
-        bias[torch.arange(1, N, 7, device="cuda")] = NINF
-    if fp8:
-        wscale = torch.exp2(torch.ceil(torch.log2(Wf.abs().amax(dim=1) / 448.0)))
-        W = (Wf / wscale[:, None]).to(torch.float8_e4m3fn)
-    else:
-        wscale, W = None, Wf.bfloat16()
-    return X, W, wscale, bias
-
-
-def _run_lse(lib, X, W, wscale, bias, M, N, K, share=1, lse=True):
-    """-> logits [M][N], val, idx, sum [M][nt] (sum None for the hook without it); poison behind every buffer is checked."""
-    nt = (N + 15) // 16
-    logits = torch.full((M * N + 16,), float("nan"), device="cuda")
-    val = torch.full((M * nt + 16,), float("nan"), device="cuda")
-    idx = torch.full((M * nt + 16,), -5, device="cuda", dtype=torch.int32)
-    ssum = torch.full((M * nt + 16,), float("nan"), device="cuda")
-    old = lib.gitcap_dbg_config(10, share)
-    try:
-        if lse:
-            rc = lib.gitcap_dbg_vocab_head_lse(_p(X), K, _p(W), _p(wscale), _p(bias), M, N, K, _p(logits), _p(val), _p(idx), _p(ssum),
-                                               _stream())
-        else:
-            rc = lib.gitcap_dbg_vocab_head(_p(X), K, _p(W), _p(wscale), _p(bias), M, N, K, _p(logits), _p(val), _p(idx), _stream())
-        torch.cuda.synchronize()
-    finally:
-        lib.gitcap_dbg_config(10, old)
-    assert rc == 0
-    assert bool(torch.isnan(logits[M * N:]).all()) and bool(torch.isnan(val[M * nt:]).all()) and bool((idx[M * nt:] == -5).all())
-    assert bool(torch.isnan(ssum[M * nt if lse else 0:]).all())
-    return logits[:M * N].view(M, N), val[:M * nt].view(M, nt), idx[:M * nt].view(M, nt), ssum[:M * nt].view(M, nt) if lse else None
-
 
 def _argmax_final_lp(lib, val, idx, ssum, rows, nt):
     out = torch.full((rows,), -9, device="cuda", dtype=torch.int64)
     lp = torch.full((rows,), float("nan"), device="cuda")
-    rc = lib.gitcap_dbg_argmax_final_lp(_p(val), _p(idx), nt, rows, 1, 0, _p(out), 1, None, 0, -1, None, _p(ssum), _p(lp), 1, _stream())
+    rc = lib.gitcap_dbg_argmax_final_lp(ptr(val), ptr(idx), nt, rows, 1, 0, ptr(out), 1, None, 0, -1, None, ptr(ssum), ptr(lp), 1, stream())
     torch.cuda.synchronize()
     assert rc == 0
     return out.cpu().numpy(), lp.cpu().numpy().astype(np.float64)
@@ -103,9 +42,9 @@ def _argmax_final_lp(lib, val, idx, ssum, rows, nt):
 
 def _head_case(lib, M, N, K, fp8=False, ninf=False):
     nt = (N + 15) // 16
-    X, W, wscale, bias = _head_inputs(M, N, K, fp8, seed=7000 + 100 * M + N + K, ninf=ninf)
-    logits, val, idx, ssum = _run_lse(lib, X, W, wscale, bias, M, N, K)
-    lg0, val0, idx0, _ = _run_lse(lib, X, W, wscale, bias, M, N, K, lse=False)
+    X, W, wscale, bias = softmax_head_inputs(M, N, K, fp8, seed=7000 + 100 * M + N + K, ninf=ninf)
+    logits, val, idx, ssum = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, hook="lse")[:4]
+    lg0, val0, idx0, _ = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K)[:4]
     assert torch.equal(logits, lg0) and torch.equal(val, val0) and torch.equal(idx, idx0)        # y, best, bi untouched
     lg = logits.cpu().numpy()
     assert not np.isnan(lg).any()
@@ -154,14 +93,14 @@ def test_head_sum_partials_masked_columns(lib, M, N, K):
 def test_head_sum_partials_bitwise_invariants(lib, N, K):
     """The third partial does not depend on the form of the head kernel (gitcap_dbg_config(10, .)) nor on the rows beside it."""
     M = 33
-    X, W, wscale, bias = _head_inputs(M, N, K, False, seed=N + K)
-    a = _run_lse(lib, X, W, wscale, bias, M, N, K, share=1)
-    b = _run_lse(lib, X, W, wscale, bias, M, N, K, share=0)
+    X, W, wscale, bias = softmax_head_inputs(M, N, K, False, seed=N + K)
+    a = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, share=1, hook="lse")[:4]
+    b = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, share=0, hook="lse")[:4]
     for u, v in zip(a, b):
         assert torch.equal(u, v)
     for m in (0, 15, 16, 32):
         for share in (1, 0):
-            one = _run_lse(lib, X[m:m + 1].contiguous(), W, wscale, bias, 1, N, K, share=share)
+            one = run_vocab_head(lib, X[m:m + 1].contiguous(), K, W, wscale, bias, 1, N, K, share=share, hook="lse")[:4]
             for u, v in zip(a, one):
                 assert torch.equal(u[m:m + 1], v), (m, share)
 
@@ -171,11 +110,11 @@ def test_lse_hooks_reject_bad_arguments(lib):
     f = torch.zeros(64, device="cuda")
     i = torch.zeros(64, device="cuda", dtype=torch.int32)
     o = torch.zeros(4, device="cuda", dtype=torch.int64)
-    assert lib.gitcap_dbg_vocab_head_lse(_p(x), 64, _p(x), None, None, 1, 16, 64, _p(f), _p(f), _p(i), None, None) == -1    # no sum buffer
-    assert lib.gitcap_dbg_vocab_head_lse(_p(x), 64, _p(x), None, None, 1, 16, 64, _p(f), None, None, _p(f), None) == -1     # sum without the pair
-    assert lib.gitcap_dbg_argmax_final_lp(_p(f), _p(i), 1, 1, 1, 0, _p(o), 1, None, 0, -1, None, None, _p(f), 1, None) == -1
-    assert lib.gitcap_dbg_argmax_final_lp(_p(f), _p(i), 1, 1, 1, 0, _p(o), 1, None, 0, -1, None, _p(f), None, 1, None) == -1
-    assert lib.gitcap_dbg_argmax_final_lp(_p(f), _p(i), 1, 1, 1, 0, _p(o), 1, None, 0, -1, None, _p(f), _p(f), 0, None) == -1
+    assert lib.gitcap_dbg_vocab_head_lse(ptr(x), 64, ptr(x), None, None, 1, 16, 64, ptr(f), ptr(f), ptr(i), None, None) == -1    # no sum buffer
+    assert lib.gitcap_dbg_vocab_head_lse(ptr(x), 64, ptr(x), None, None, 1, 16, 64, ptr(f), None, None, ptr(f), None) == -1     # sum without the pair
+    assert lib.gitcap_dbg_argmax_final_lp(ptr(f), ptr(i), 1, 1, 1, 0, ptr(o), 1, None, 0, -1, None, None, ptr(f), 1, None) == -1
+    assert lib.gitcap_dbg_argmax_final_lp(ptr(f), ptr(i), 1, 1, 1, 0, ptr(o), 1, None, 0, -1, None, ptr(f), None, 1, None) == -1
+    assert lib.gitcap_dbg_argmax_final_lp(ptr(f), ptr(i), 1, 1, 1, 0, ptr(o), 1, None, 0, -1, None, ptr(f), ptr(f), 0, None) == -1
 
 
 # ---- c. the final merge -----------------------------------------------------------------------------------------------------
@@ -216,14 +155,14 @@ def _merge_case(lib, nt, D=0):
     want = [L.merge(v, i, s) for v, i, s in rows]
     assert [t for t, _ in want] == [R.argmax_partials(v, i) for v, i, _ in rows]
     assert want[2][0] == 16 * (nt - 1) + 5 and want[-1] == (0, NINF)
-    d_val, d_idx, d_sum = _dev(val, torch.float32), _dev(idx, torch.int32), _dev(ssum, torch.float32)
+    d_val, d_idx, d_sum = to_dev(val, torch.float32), to_dev(idx, torch.int32), to_dev(ssum, torch.float32)
     emb = None
     from gitcap._lib import CDbgNextEmbed
 
     def launch(with_lp):
         out = torch.full((n, ld_out), -7, device="cuda", dtype=torch.int64)
         lp = torch.full((n, ld_lp), float("nan"), device="cuda")
-        sep_cnt = _dev([100, 200, 300, 400], torch.int32)
+        sep_cnt = to_dev([100, 200, 300, 400], torch.int32)
         xf = xb = e = None
         if D:
             g = torch.Generator(device="cuda").manual_seed(D)
@@ -237,10 +176,10 @@ def _merge_case(lib, nt, D=0):
                               xf.data_ptr(), xb.data_ptr())
         ep = ctypes.byref(e) if e else None
         if with_lp:
-            rc = lib.gitcap_dbg_argmax_final_lp(_p(d_val), _p(d_idx), nt, n, stride, off, _p(out), ld_out, _p(sep_cnt), step, SEP, ep,
-                                                _p(d_sum), _p(lp), ld_lp, _stream())
+            rc = lib.gitcap_dbg_argmax_final_lp(ptr(d_val), ptr(d_idx), nt, n, stride, off, ptr(out), ld_out, ptr(sep_cnt), step, SEP, ep,
+                                                ptr(d_sum), ptr(lp), ld_lp, stream())
         else:
-            rc = lib.gitcap_dbg_argmax_final(_p(d_val), _p(d_idx), nt, n, stride, off, _p(out), ld_out, _p(sep_cnt), step, SEP, ep, _stream())
+            rc = lib.gitcap_dbg_argmax_final(ptr(d_val), ptr(d_idx), nt, n, stride, off, ptr(out), ld_out, ptr(sep_cnt), step, SEP, ep, stream())
         torch.cuda.synchronize()
         assert rc == 0
         return out, lp, sep_cnt, xf, xb
@@ -279,9 +218,9 @@ def test_argmax_final_lp_is_independent_of_the_rows_beside_it(lib):
     nt = 1908
     rows = _merge_rows(nt, np.random.default_rng(5))
     n = len(rows)
-    val = _dev(np.stack([v for v, _, _ in rows]), torch.float32)
-    idx = _dev(np.stack([i for _, i, _ in rows]), torch.int32)
-    ssum = _dev(np.stack([s for _, _, s in rows]), torch.float32)
+    val = to_dev(np.stack([v for v, _, _ in rows]), torch.float32)
+    idx = to_dev(np.stack([i for _, i, _ in rows]), torch.int32)
+    ssum = to_dev(np.stack([s for _, _, s in rows]), torch.float32)
     tok, lp = _argmax_final_lp(lib, val, idx, ssum, n, nt)
     for r in range(n):
         t1, l1 = _argmax_final_lp(lib, val[r:r + 1].contiguous(), idx[r:r + 1].contiguous(), ssum[r:r + 1].contiguous(), 1, nt)
@@ -300,24 +239,24 @@ def test_draft_accept_lp_vs_restatement(lib, B, n):
     tok_scratch = torch.full((B * n,), -3, device="cuda", dtype=torch.int32)
     ticket = torch.zeros(1, device="cuda", dtype=torch.int32)
     ld_lp = n + 3
-    for a_rows, sep_at in _draft_scenarios(B, n):          # every launch on the same ticket word
-        tok, ids, val, idx = _draft_scenario(B, n, a_rows, sep_at, rng)
+    for a_rows, sep_at in draft_scenarios(B, n):          # every launch on the same ticket word
+        tok, ids, val, idx = draft_scenario(B, n, a_rows, sep_at, rng)
         ssum = (1.0 + 15.0 * rng.random(val.shape)).astype(np.float32)
         want = R.draft_accept(tok, ids, DRAFT_SEP)
         ld = ids.shape[1]
-        d_val, d_idx, d_sum = _dev(val, torch.float32), _dev(idx, torch.int32), _dev(ssum, torch.float32)
+        d_val, d_idx, d_sum = to_dev(val, torch.float32), to_dev(idx, torch.int32), to_dev(ssum, torch.float32)
         res = []
         for with_lp in (True, False):
-            d_ids = _dev(ids, torch.int64)
+            d_ids = to_dev(ids, torch.int64)
             sep_cnt = torch.full((n + 2,), 77, device="cuda", dtype=torch.int32)
             lp = torch.full((B, ld_lp), LP_POISON, device="cuda")
             host = (ctypes.c_int32 * 2)(-5, -5)
             if with_lp:
-                rc = lib.gitcap_dbg_draft_accept_lp(_p(d_val), _p(d_idx), DRAFT_NT, B, n, _p(d_ids), ld, _p(tok_scratch), _p(ticket),
-                                                    _p(sep_cnt), DRAFT_SEP, host, _p(d_sum), _p(lp), ld_lp, _stream())
+                rc = lib.gitcap_dbg_draft_accept_lp(ptr(d_val), ptr(d_idx), DRAFT_NT, B, n, ptr(d_ids), ld, ptr(tok_scratch), ptr(ticket),
+                                                    ptr(sep_cnt), DRAFT_SEP, host, ptr(d_sum), ptr(lp), ld_lp, stream())
             else:
-                rc = lib.gitcap_dbg_draft_accept(_p(d_val), _p(d_idx), DRAFT_NT, B, n, _p(d_ids), ld, _p(tok_scratch), _p(ticket),
-                                                 _p(sep_cnt), DRAFT_SEP, host, _stream())
+                rc = lib.gitcap_dbg_draft_accept(ptr(d_val), ptr(d_idx), DRAFT_NT, B, n, ptr(d_ids), ld, ptr(tok_scratch), ptr(ticket),
+                                                 ptr(sep_cnt), DRAFT_SEP, host, stream())
             torch.cuda.synchronize()
             assert rc == 0 and int(ticket.item()) == 0
             res.append((d_ids.cpu(), sep_cnt.cpu(), (host[0], host[1]), lp.cpu().numpy().astype(np.float64)))

@@ -21,19 +21,13 @@ import torch
 from gitcap.config import git_base, git_tiny
 from gitcap.weights import quantize_weights_fp8, synthetic_weights
 from oracle.git_oracle import GitOracle, make_frames
+from gpu_support import captioner_cls, ptr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL_EMUL = 0.08      # |dev - bf16-emulating oracle| on logits with std ~4  (2 % of the spread)
 LOGIT_TOL_FP32 = 0.20      # |dev - fp32 oracle|
 NEAR_TIE = 0.16            # = 2 x LOGIT_TOL_EMUL: a device token may differ from the oracle's argmax only inside this margin
-
-
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
 
 
 def _tokens_match_margin_gated(dev_ids, oracle: GitOracle, frames):
@@ -345,17 +339,16 @@ def test_errors_are_loud(captioner_cls):
     with pytest.raises(GitcapError):                          # weights never loaded
         bare.greedy_decode(make_frames(1, 2, cfg.image_size, 0), max_len=2)
     # round-2 entry points: call order and arguments are checked, nothing fails silently
-    import ctypes
     with pytest.raises(GitcapError, match="before the first"):          # storage must be chosen before any tensor is loaded
         m._call("gitcap_set_weight_storage", 1)
     buf = torch.empty(64, device="cuda")
     with pytest.raises(GitcapError, match="enable"):                    # hidden states were never requested
-        m._call("gitcap_hidden_states_read", 1, 2 * cfg.tokens_per_frame, 3, ctypes.c_void_p(buf.data_ptr()), m._stream())
+        m._call("gitcap_hidden_states_read", 1, 2 * cfg.tokens_per_frame, 3, ptr(buf), m._stream())
     with pytest.raises(ValueError):                                     # the device search refuses a beam underflow set-up
         captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=1, max_text_len=6, max_beams=2).infer(
             make_frames(1, 2, cfg.image_size, 0), beam_size=2, max_steps=4, per_node_beam_size=1, on_device=True)
     with pytest.raises(GitcapError):                                    # raw frames smaller than... zero-sized
-        m._call("gitcap_greedy_raw", ctypes.c_void_p(buf.data_ptr()), 1, 2, 0, 0, 2, 0, ctypes.c_void_p(buf.data_ptr()), None, m._stream())
+        m._call("gitcap_greedy_raw", ptr(buf), 1, 2, 0, 0, 2, 0, ptr(buf), None, m._stream())
     assert m.weight_bytes() > 0 and m.workspace_bytes() > m.weight_bytes()
 
 
@@ -425,7 +418,6 @@ def test_sync_calls_interleaved_with_submissions_in_flight(captioner_cls):
     """A synchronous call while gitcap_greedy_submit work is still running on the library's streams shares the image-row
     workspace with it: the C ABI orders the caller's stream behind every submission in flight (no device sync, no
     .result() first), and a future dropped without .result() keeps its buffers alive in the model's table."""
-    import ctypes
     cfg = git_base(2)
     m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=4, max_frames=2, max_text_len=8)
     batches = [make_frames(4, 2, cfg.image_size, 300 + i).cuda() for i in range(4)]
@@ -437,8 +429,8 @@ def test_sync_calls_interleaved_with_submissions_in_flight(captioner_cls):
         ids = torch.empty((4, 9), dtype=torch.int64, device="cuda")
         steps = torch.zeros((1,), dtype=torch.int32, device="cuda")
         with torch.cuda.device(m._dev):
-            m._call("gitcap_greedy", ctypes.c_void_p(batches[3].data_ptr()), 4, 2, 8, 0,
-                    ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(steps.data_ptr()), m._stream())
+            m._call("gitcap_greedy", ptr(batches[3]), 4, 2, 8, 0,
+                    ptr(ids), ptr(steps), m._stream())
         assert torch.equal(ids, want[3])
         # (b) the Python surface: a synchronous greedy_decode with futures outstanding, one of them never resolved
         del futs[1]
@@ -702,7 +694,6 @@ def _beam_search_matches_margin_gated(dev_out, host_out, oracle_step, oracle_sea
                            "oracle_logprob": round(float(want[1][b]), 4)})
     print("beam search vs oracle, first divergence per clip:", report)
     return report, dev_trace
-
 
 
 def _check_device_regression(golden_dir, name, out, dev_trace, report):

@@ -12,15 +12,9 @@ import torch
 from gitcap.config import git_base, git_large, git_tiny
 from gitcap.weights import quantize_weights_fp8, synthetic_weights
 from oracle.git_oracle import make_frames
+from gpu_support import captioner_cls  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
 
 
 @pytest.mark.parametrize("size", ["tiny", "base"])

@@ -16,6 +16,7 @@ import torch
 import sampling_reference as S
 from gitcap.config import git_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import captioner_cls, ptr, stream  # noqa: F401
 from oracle.git_oracle import make_frames
 
 pytestmark = pytest.mark.gpu
@@ -28,20 +29,10 @@ FRAME_SEEDS = (1247, 1248, 1249, 1250)
 FILTERS = (dict(), dict(top_k=5, temperature=0.7), dict(top_p=0.9, temperature=2.0, repetition_penalty=1.3))
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 @pytest.fixture(scope="module")
-def model():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+def model(captioner_cls):
     cfg = git_tiny(2)
-    m = GitCaptioner(cfg, synthetic_weights(cfg, 0), max_batch=B, max_frames=F, max_text_len=L, max_beams=4, stop="never")
+    m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=B, max_frames=F, max_text_len=L, max_beams=4, stop="never")
     fr = make_frames(B, F, cfg.image_size, 1247).cuda()
     r = m.infer(fr, on_device=True, **KW)                  # before any attachment
     return m, cfg, fr, (r["predictions"].clone(), r["logprobs"].clone()), None
@@ -216,7 +207,7 @@ def test_refusals_consume_the_attachment(model):
     def search(pnb=PNB, beams=BEAMS):
         dec = torch.full((B, L), -777, dtype=torch.int64, device="cuda")
         lp = torch.full((B,), float("nan"), device="cuda")
-        rc = lib.gitcap_beam_search(h, _p(fr), B, F, beams, L, ctypes.c_float(LP), pnb, _p(dec), _p(lp), _st())
+        rc = lib.gitcap_beam_search(h, ptr(fr), B, F, beams, L, ctypes.c_float(LP), pnb, ptr(dec), ptr(lp), stream())
         torch.cuda.synchronize()
         return rc, dec, lp
 

@@ -13,29 +13,11 @@ import pytest
 import torch
 
 import sampling_reference as S
+from gpu_support import beam_state, lib, ptr, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CASES = S.row_cases()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
 
 
 def _run(lib, x, bs, prefix, cur_len, rp, B, beams, pn, T, top_k, top_p, seed, pad=0, stats=True):
@@ -43,15 +25,15 @@ def _run(lib, x, bs, prefix, cur_len, rp, B, beams, pn, T, top_k, top_p, seed, p
     ld, K = V + pad, beams * pn
     buf = np.full((rows, ld), 1e30, np.float32)                    # row padding the kernel must not read
     buf[:, :V] = x
-    d_x, d_bs = _dev(buf, torch.float32), _dev(bs, torch.float32)
-    d_pre = _dev(prefix, torch.int64) if prefix is not None else None
+    d_x, d_bs = to_dev(buf, torch.float32), to_dev(bs, torch.float32)
+    d_pre = to_dev(prefix, torch.int64) if prefix is not None else None
     out_s = torch.full((B * K + 4,), float("nan"), device="cuda")
     out_i = torch.full((B * K + 4,), -5, device="cuda", dtype=torch.int32)
     kept = torch.full((rows + 2,), -5, device="cuda", dtype=torch.int32) if stats else None
     logz = torch.full((rows + 2,), float("nan"), device="cuda") if stats else None
-    rc = lib.gitcap_sample_rows(_p(d_x), ld, _p(d_bs), _p(d_pre), 0 if prefix is None else prefix.shape[1], cur_len, ctypes.c_float(rp),
-                                B, beams, V, pn, ctypes.c_float(T), top_k, ctypes.c_float(top_p), ctypes.c_uint64(seed), _p(out_s),
-                                _p(out_i), _p(kept), _p(logz), _stream())
+    rc = lib.gitcap_sample_rows(ptr(d_x), ld, ptr(d_bs), ptr(d_pre), 0 if prefix is None else prefix.shape[1], cur_len, ctypes.c_float(rp),
+                                B, beams, V, pn, ctypes.c_float(T), top_k, ctypes.c_float(top_p), ctypes.c_uint64(seed), ptr(out_s),
+                                ptr(out_i), ptr(kept), ptr(logz), stream())
     torch.cuda.synchronize()
     return rc, out_s, out_i, kept, logz
 
@@ -137,20 +119,6 @@ def test_sample_rows_refuses_bad_arguments(lib):
 
 # ---- c. the bookkeeping for unsorted candidates ---------------------------------------------------------------------------------
 
-def _state(B, beams, n, L):
-    from gitcap._lib import CDbgBeamBuffers, CDbgBeamBuffersNbest
-    rows = B * beams
-    i64 = dict(device="cuda", dtype=torch.int64)
-    i32 = dict(device="cuda", dtype=torch.int32)
-    t = dict(ids0=torch.full((rows, L), -777, **i64), ids1=torch.full((rows, L), -777, **i64), words=torch.full((rows,), -777, **i64),
-             hyp_ids=torch.full((B, n, L), -777, **i64), beam_scores=torch.full((rows,), float("nan"), device="cuda"),
-             hyp_score=torch.full((B, n), float("nan"), device="cuda"), src_rows=torch.full((rows,), -777, **i32),
-             done=torch.full((B,), -777, **i32), hyp_len=torch.full((B, n), -777, **i32))
-    order = ("ids0", "ids1", "words", "hyp_ids", "beam_scores", "hyp_score", "src_rows", "done", "hyp_len")
-    ptrs = [t[k].data_ptr() for k in order]
-    return t, CDbgBeamBuffers(*ptrs), CDbgBeamBuffersNbest(*ptrs, n)
-
-
 def _forced(beams, mode):
     """EOS drawn by one row, by all rows but one, and by every live row of a clip (tests/test_sampling.py: _forced)."""
     E = S.TOY_EOS
@@ -173,17 +141,17 @@ def test_sampled_bookkeeping_vs_restatement(lib, n, beams, mode, lp):
     K = beams * pn
     table, forced = S.toy_table(), _forced(beams, mode)
     book = S.Book(B, beams, n, L, S.TOY_CLS, S.TOY_EOS, lp)
-    t, bb1, bbn = _state(B, beams, n, L)
-    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb1), B, beams, L, S.TOY_CLS, _stream()) == 0
+    t, bb1, bbn = beam_state(B, beams, n, L)
+    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb1), B, beams, L, S.TOY_CLS, stream()) == 0
     t["hyp_len"].zero_()
     ids, cur, max_not_first = [t["ids0"], t["ids1"]], 0, 0
     for cur_len in range(1, L):
         ci, cs = S.toy_candidates(table, book, beams, pn, 1.0, 1.0, 0, 1.0, 31337, cur_len, forced)
         cs32 = cs.astype(np.float32)
         max_not_first += int((cs32.argmax(axis=1) != 0).sum())
-        d_cs, d_ci = _dev(cs32, torch.float32), _dev(ci, torch.int32)
-        assert lib.gitcap_dbg_beam_step_sampled(ctypes.byref(bbn), _p(d_cs), _p(d_ci), B, beams, K, V, cur_len, L, S.TOY_EOS,
-                                                ctypes.c_float(lp), cur, _stream()) == 0
+        d_cs, d_ci = to_dev(cs32, torch.float32), to_dev(ci, torch.int32)
+        assert lib.gitcap_dbg_beam_step_sampled(ctypes.byref(bbn), ptr(d_cs), ptr(d_ci), B, beams, K, V, cur_len, L, S.TOY_EOS,
+                                                ctypes.c_float(lp), cur, stream()) == 0
         torch.cuda.synchronize()
         book.step(cs32, ci, V, cur_len)
         cur ^= 1
@@ -201,7 +169,7 @@ def test_sampled_bookkeeping_vs_restatement(lib, n, beams, mode, lp):
     assert max_not_first >= 1
     dec = torch.full((B, n, L), -777, device="cuda", dtype=torch.int64)
     lps = torch.full((B, n), float("nan"), device="cuda")
-    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, S.TOY_EOS, _p(dec), _p(lps), _stream()) == 0
+    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, S.TOY_EOS, ptr(dec), ptr(lps), stream()) == 0
     torch.cuda.synchronize()
     rdec, rlps = book.finish()
     assert np.array_equal(dec.cpu().numpy(), rdec)
@@ -211,12 +179,12 @@ def test_sampled_bookkeeping_vs_restatement(lib, n, beams, mode, lp):
 def test_sampled_step_refuses_bad_arguments(lib):
     from gitcap._lib import CDbgBeamBuffersNbest
     B, beams, L, K, V = 2, 2, 5, 4, 23
-    t, _, bbn = _state(B, beams, 3, L)
+    t, _, bbn = beam_state(B, beams, 3, L)
     before = {k: v.clone() for k, v in t.items()}
     cs = torch.zeros(B, K, device="cuda")
     ci = torch.zeros(B, K, device="cuda", dtype=torch.int32)
     step = lambda bb, cur_len=1, cur=0, beams=beams, K=K: lib.gitcap_dbg_beam_step_sampled(
-        ctypes.byref(bb), _p(cs), _p(ci), B, beams, K, V, cur_len, L, 22, ctypes.c_float(0.6), cur, _stream())
+        ctypes.byref(bb), ptr(cs), ptr(ci), B, beams, K, V, cur_len, L, 22, ctypes.c_float(0.6), cur, stream())
     for bad_n in (0, 17):
         bad = CDbgBeamBuffersNbest(*[getattr(bbn, f) for f, _ in CDbgBeamBuffersNbest._fields_[:-1]], bad_n)
         assert step(bad) == -1

@@ -6,8 +6,6 @@ Reference: log_softmax in fp64 of the SAME handle's teacher-forced fp32 logits (
 under the bound derived in tests/test_score_gpu.py (score_reference.bound_lp / bound_sum).  The captured target logit is bit for
 bit logits[r, j, y[r, j + 1]]; candidates [B, n, T] are bit for bit n separate [B, T] calls; the score of a greedy caption is bit
 for bit the log-probabilities the greedy loop reported (cached == teacher-forced)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -16,6 +14,7 @@ import score_reference as S
 from gitcap.config import git_tiny
 from gitcap.student_config import student_synthetic_weights, student_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import captioner_cls, ptr, stream  # noqa: F401
 from oracle.git_oracle import make_frames
 from oracle.student_oracle import make_memory
 
@@ -23,14 +22,6 @@ pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE = -1, -2
 MAX_LEN = 8
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check_against_logits(d, logits, y, lengths, ignore_id, V, what):
@@ -62,11 +53,9 @@ def _check_against_logits(d, logits, y, lengths, ignore_id, V, what):
 # ---- teacher --------------------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
-def teacher():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+def teacher(captioner_cls):
     cfg = git_tiny(2)
-    m = GitCaptioner(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=MAX_LEN, max_beams=3, stop="never")
+    m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=MAX_LEN, max_beams=3, stop="never")
     fr = make_frames(2, 2, cfg.image_size, 1234).cuda()
     ids, lp = m.greedy_decode(fr, max_len=MAX_LEN - 1, return_logprobs=True)         # [2, 8] ids: CLS + 7 tokens
     return m, cfg, fr, ids.clone(), lp.clone()
@@ -95,7 +84,7 @@ def test_teacher_score_vs_forward_decoder(teacher):
     _check_against_logits(d, logits, y, None, -1, cfg.vocab_size, "teacher, all positions")
     # the captured target logits: bit for bit the logits tensor's elements
     tl = torch.zeros(B * T, device="cuda")
-    assert m._lib.gitcap_dbg_score_target_logits(m._handle, _p(tl), B * T, _st()) == 0
+    assert m._lib.gitcap_dbg_score_target_logits(m._handle, ptr(tl), B * T, stream()) == 0
     torch.cuda.synchronize()
     tl = tl.view(B, T)
     for r in range(B):
@@ -167,16 +156,16 @@ def test_teacher_score_error_paths(teacher):
     fresh = GitCaptioner(cfg, synthetic_weights(cfg, 0), max_batch=2, max_frames=2, max_text_len=MAX_LEN, stop="never")
     y = ids.contiguous()
     lp = torch.full((2, 7), -5.0, device="cuda")
-    rc = fresh._lib.gitcap_score(fresh._handle, _p(y), 8, 2, 1, 8, None, -1, _p(lp), 7, None, None, None, None, _st())
+    rc = fresh._lib.gitcap_score(fresh._handle, ptr(y), 8, 2, 1, 8, None, -1, ptr(lp), 7, None, None, None, None, stream())
     assert rc == ERR_STATE                                                          # before encode / set_visual
     m.forward_image_enc(fr)
     long_y = torch.zeros((2, MAX_LEN + 1), dtype=torch.int64, device="cuda")
-    assert m._lib.gitcap_score(m._handle, _p(long_y), MAX_LEN + 1, 2, 1, MAX_LEN + 1, None, -1, _p(lp), 8, None, None, None, None, _st()) == ERR_ARG
-    assert m._lib.gitcap_score(m._handle, _p(y), 8, 2, 1, 1, None, -1, _p(lp), 7, None, None, None, None, _st()) == ERR_ARG       # T < 2
-    assert m._lib.gitcap_score(m._handle, _p(y), 8, 2, 1, 8, None, -1, _p(lp), 6, None, None, None, None, _st()) == ERR_ARG       # ld_lp < T - 1
-    assert m._lib.gitcap_score(m._handle, _p(y), 8, 3, 1, 8, None, -1, _p(lp), 7, None, None, None, None, _st()) == ERR_ARG       # rows != clips * beams
+    assert m._lib.gitcap_score(m._handle, ptr(long_y), MAX_LEN + 1, 2, 1, MAX_LEN + 1, None, -1, ptr(lp), 8, None, None, None, None, stream()) == ERR_ARG
+    assert m._lib.gitcap_score(m._handle, ptr(y), 8, 2, 1, 1, None, -1, ptr(lp), 7, None, None, None, None, stream()) == ERR_ARG       # T < 2
+    assert m._lib.gitcap_score(m._handle, ptr(y), 8, 2, 1, 8, None, -1, ptr(lp), 6, None, None, None, None, stream()) == ERR_ARG       # ld_lp < T - 1
+    assert m._lib.gitcap_score(m._handle, ptr(y), 8, 3, 1, 8, None, -1, ptr(lp), 7, None, None, None, None, stream()) == ERR_ARG       # rows != clips * beams
     big = torch.zeros((8, 8), dtype=torch.int64, device="cuda")
-    assert m._lib.gitcap_score(m._handle, _p(big), 8, 8, 4, 8, None, -1, None, 0, None, None, None, None, _st()) == ERR_ARG      # rows > max_batch * max_beams
+    assert m._lib.gitcap_score(m._handle, ptr(big), 8, 8, 4, 8, None, -1, None, 0, None, None, None, None, stream()) == ERR_ARG      # rows > max_batch * max_beams
     torch.cuda.synchronize()
     assert bool((lp == -5.0).all())
     with pytest.raises(ValueError, match="max_text_len"):
@@ -185,7 +174,7 @@ def test_teacher_score_error_paths(teacher):
         m.score(fr, torch.zeros((2, 4, 8), dtype=torch.int64))
     with pytest.raises(ValueError):
         m.score(fr, ids[:, :1])
-    assert m._lib.gitcap_score(None, _p(y), 8, 2, 1, 8, None, -1, _p(lp), 7, None, None, None, None, None) == ERR_ARG
+    assert m._lib.gitcap_score(None, ptr(y), 8, 2, 1, 8, None, -1, ptr(lp), 7, None, None, None, None, None) == ERR_ARG
 
 
 def test_teacher_score_reports_its_memory(teacher):
@@ -231,7 +220,7 @@ def test_student_score_vs_forward_decoder(student):
     d = m.score(mem, y, until_sep=False, return_top1=True)
     _check_against_logits(d, logits, y, None, -1, cfg.vocab_length, "student, all positions")
     tl = torch.zeros(B * T, device="cuda")
-    assert m._lib.gitcap_student_dbg_score_target_logits(m._handle, _p(tl), B * T, _st()) == 0
+    assert m._lib.gitcap_student_dbg_score_target_logits(m._handle, ptr(tl), B * T, stream()) == 0
     torch.cuda.synchronize()
     tl = tl.view(B, T)
     for r in range(B):

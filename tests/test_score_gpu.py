@@ -11,28 +11,19 @@ fp32 add; y_t - M <= 0 and lp_winner <= 0 (up to its own error), so both magnitu
 2^-24 |lp|: 2e-5 + 2^-23 |lp_ref|, absolute (score_reference.bound_lp) -- the estimate of the feature's description, confirmed.
 row_sum adds T - 1 such terms with one accumulator: the terms' bounds plus (T - 1) * 2^-24 * sum |lp| (score_reference.bound_sum).
 row_cnt, top1_ids and the -inf pattern are exact; top1_lp is bit for bit gitcap_dbg_argmax_final_lp's."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import logprob_reference as L
 import score_reference as S
-from test_logprob_gpu import _dev, _head_inputs, _p, _run_lse, _stream
+from gpu_support import TGT_FILL, lib, ptr, run_vocab_head, softmax_head_inputs, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NINF = float("-inf")
-SENT = -777.25                  # pre-fill of tgt_logit
+SENT = TGT_FILL                 # pre-fill of tgt_logit
 IGN = 7                         # the ignore_id the head must NOT know about (score_final's business)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
 
 
 def _targets(M, N, logits):
@@ -45,33 +36,10 @@ def _targets(M, N, logits):
     return np.array([int(am[m]) if pool[m % len(pool)] is None else pool[m % len(pool)] for m in range(M)], dtype=np.int64)
 
 
-def _run_score(lib, X, W, wscale, bias, M, N, K, targets, share=1, with_logits=False):
-    nt = (N + 15) // 16
-    val = torch.full((M * nt + 16,), float("nan"), device="cuda")
-    idx = torch.full((M * nt + 16,), -5, device="cuda", dtype=torch.int32)
-    ssum = torch.full((M * nt + 16,), float("nan"), device="cuda")
-    tl = torch.full((M + 16,), SENT, device="cuda")
-    logits = torch.full((M * N + 16,), float("nan"), device="cuda") if with_logits else None
-    tg = _dev(targets, torch.int64)
-    old = lib.gitcap_dbg_config(10, share)
-    try:
-        rc = lib.gitcap_dbg_vocab_head_score(_p(X), K, _p(W), _p(wscale), _p(bias), M, N, K, _p(logits), _p(val), _p(idx), _p(ssum),
-                                             _p(tg), _p(tl), _stream())
-        torch.cuda.synchronize()
-    finally:
-        lib.gitcap_dbg_config(10, old)
-    assert rc == 0
-    assert bool(torch.isnan(val[M * nt:]).all()) and bool((idx[M * nt:] == -5).all()) and bool(torch.isnan(ssum[M * nt:]).all())
-    assert bool((tl[M:] == SENT).all())
-    if with_logits:
-        assert bool(torch.isnan(logits[M * N:]).all())
-    return val[:M * nt].view(M, nt), idx[:M * nt].view(M, nt), ssum[:M * nt].view(M, nt), tl[:M], (logits[:M * N].view(M, N) if with_logits else None)
-
-
 def _head_score_case(lib, M, N, K, fp8):
-    X, W, wscale, bias = _head_inputs(M, N, K, fp8, seed=9000 + 100 * M + N + K)
+    X, W, wscale, bias = softmax_head_inputs(M, N, K, fp8, seed=9000 + 100 * M + N + K)
     bias[3 if N > 3 else 1] = NINF
-    lg, val0, idx0, sum0 = _run_lse(lib, X, W, wscale, bias, M, N, K)              # the logits and partials of the existing hooks
+    lg, val0, idx0, sum0 = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, hook="lse")[:4]              # the logits and partials of the existing hooks
     targets = _targets(M, N, lg)
     inr = (targets >= 0) & (targets < N)
     want = torch.full((M,), SENT, device="cuda")
@@ -79,18 +47,19 @@ def _head_score_case(lib, M, N, K, fp8):
     want[rows] = lg[rows, torch.as_tensor(targets[inr], device="cuda")]
     res = {}
     for share in (1, 0):
-        val, idx, ssum, tl, _ = _run_score(lib, X, W, wscale, bias, M, N, K, targets, share=share)
+        _, val, idx, ssum, tl = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, share=share, hook="score", targets=targets, want_logits=False)
         assert torch.equal(val, val0) and torch.equal(idx, idx0) and torch.equal(ssum, sum0), share
         assert torch.equal(tl.view(torch.int32), want.view(torch.int32)), (share, tl, want)      # bit for bit; untouched where out of range
         res[share] = tl
     assert bool(torch.isinf(want).any()) or M < 7                                    # the -inf column is among the targets
     # with a logits buffer the launch writes the same logits as the hook without targets
-    _, _, _, tl2, lg2 = _run_score(lib, X, W, wscale, bias, M, N, K, targets, with_logits=True)
+    lg2, _, _, _, tl2 = run_vocab_head(lib, X, K, W, wscale, bias, M, N, K, hook="score", targets=targets)
     assert torch.equal(lg2, lg) and torch.equal(tl2.view(torch.int32), want.view(torch.int32))
     # the rows beside a row do not matter: every row launched alone, in both forms
     for m in sorted({0, M - 1, min(M - 1, 15), min(M - 1, 16)}):
         for share in (1, 0):
-            v1, i1, s1, t1, _ = _run_score(lib, X[m:m + 1].contiguous(), W, wscale, bias, 1, N, K, targets[m:m + 1], share=share)
+            _, v1, i1, s1, t1 = run_vocab_head(lib, X[m:m + 1].contiguous(), K, W, wscale, bias, 1, N, K, share=share, hook="score", targets=targets[m:m + 1],
+                                               want_logits=False)
             assert torch.equal(v1, val0[m:m + 1]) and torch.equal(s1, sum0[m:m + 1]) and torch.equal(t1.view(torch.int32), want[m:m + 1].view(torch.int32))
 
 
@@ -107,12 +76,12 @@ def test_head_score_hook_rejects_bad_arguments(lib):
     f = torch.zeros(64, device="cuda")
     i = torch.zeros(64, device="cuda", dtype=torch.int32)
     t = torch.zeros(4, device="cuda", dtype=torch.int64)
-    assert lib.gitcap_dbg_vocab_head_score(_p(x), 64, _p(x), None, None, 1, 16, 64, None, _p(f), _p(i), _p(f), None, _p(f), None) == -1
-    assert lib.gitcap_dbg_vocab_head_score(_p(x), 64, _p(x), None, None, 1, 16, 64, None, _p(f), _p(i), _p(f), _p(t), None, None) == -1
-    assert lib.gitcap_dbg_vocab_head_score(_p(x), 64, _p(x), None, None, 1, 16, 64, None, _p(f), _p(i), None, _p(t), _p(f), None) == -1
-    assert lib.gitcap_dbg_score_final(_p(f), _p(i), _p(f), 1, _p(f), _p(t), 2, 1, 2, None, -1, 16, None, 1, None, None, None, None, None) == -1
-    assert lib.gitcap_dbg_score_final(_p(f), _p(i), _p(f), 1, _p(f), _p(t), 2, 1, 1, None, -1, 16, _p(f), 1, None, None, None, None, None) == -1   # T < 2
-    assert lib.gitcap_dbg_score_final(_p(f), _p(i), _p(f), 1, _p(f), _p(t), 1, 1, 2, None, -1, 16, _p(f), 1, None, None, None, None, None) == -1   # ld_ids < T
+    assert lib.gitcap_dbg_vocab_head_score(ptr(x), 64, ptr(x), None, None, 1, 16, 64, None, ptr(f), ptr(i), ptr(f), None, ptr(f), None) == -1
+    assert lib.gitcap_dbg_vocab_head_score(ptr(x), 64, ptr(x), None, None, 1, 16, 64, None, ptr(f), ptr(i), ptr(f), ptr(t), None, None) == -1
+    assert lib.gitcap_dbg_vocab_head_score(ptr(x), 64, ptr(x), None, None, 1, 16, 64, None, ptr(f), ptr(i), None, ptr(t), ptr(f), None) == -1
+    assert lib.gitcap_dbg_score_final(ptr(f), ptr(i), ptr(f), 1, ptr(f), ptr(t), 2, 1, 2, None, -1, 16, None, 1, None, None, None, None, None) == -1
+    assert lib.gitcap_dbg_score_final(ptr(f), ptr(i), ptr(f), 1, ptr(f), ptr(t), 2, 1, 1, None, -1, 16, ptr(f), 1, None, None, None, None, None) == -1   # T < 2
+    assert lib.gitcap_dbg_score_final(ptr(f), ptr(i), ptr(f), 1, ptr(f), ptr(t), 1, 1, 2, None, -1, 16, ptr(f), 1, None, None, None, None, None) == -1   # ld_ids < T
 
 
 # ---- b. score_final on hand-made partials -----------------------------------------------------------------------------------
@@ -169,22 +138,22 @@ def _final_case(lib, nt, T, use_lengths):
     R = y.shape[0]
     ld_ids, ld_lp = T + 2, T + 1
     yp = np.full((R, ld_ids), 3, np.int64); yp[:, :T] = y
-    d_val, d_idx, d_sum, d_tgt, d_y = _dev(val, torch.float32), _dev(idx, torch.int32), _dev(ssum, torch.float32), _dev(tgt, torch.float32), _dev(yp, torch.int64)
-    d_len = _dev(lengths, torch.int32) if use_lengths else None
+    d_val, d_idx, d_sum, d_tgt, d_y = to_dev(val, torch.float32), to_dev(idx, torch.int32), to_dev(ssum, torch.float32), to_dev(tgt, torch.float32), to_dev(yp, torch.int64)
+    d_len = to_dev(lengths, torch.int32) if use_lengths else None
     lp = torch.full((R, ld_lp), float("nan"), device="cuda")
     rsum = torch.full((R + 1,), float("nan"), device="cuda")
     rcnt = torch.full((R + 1,), -9, device="cuda", dtype=torch.int32)
     t1 = torch.full((R * (T - 1) + 1,), -9, device="cuda", dtype=torch.int64)
     t1lp = torch.full((R * (T - 1) + 1,), float("nan"), device="cuda")
-    rc = lib.gitcap_dbg_score_final(_p(d_val), _p(d_idx), _p(d_sum), nt, _p(d_tgt), _p(d_y), ld_ids, R, T, _p(d_len), IGN, V,
-                                    _p(lp), ld_lp, _p(rsum), _p(rcnt), _p(t1), _p(t1lp), _stream())
+    rc = lib.gitcap_dbg_score_final(ptr(d_val), ptr(d_idx), ptr(d_sum), nt, ptr(d_tgt), ptr(d_y), ld_ids, R, T, ptr(d_len), IGN, V,
+                                    ptr(lp), ld_lp, ptr(rsum), ptr(rcnt), ptr(t1), ptr(t1lp), stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(lp[:, T - 1:]).all()) and bool(torch.isnan(rsum[R:]).all()) and int(rcnt[R]) == -9 and int(t1[-1]) == -9
     # top-1: bit for bit the greedy loop's arg-max launch on the same partials
     out = torch.full((R * T,), -9, device="cuda", dtype=torch.int64)
     alp = torch.full((R * T,), float("nan"), device="cuda")
-    assert lib.gitcap_dbg_argmax_final_lp(_p(d_val), _p(d_idx), nt, R * T, 1, 0, _p(out), 1, None, 0, -1, None, _p(d_sum), _p(alp), 1, _stream()) == 0
+    assert lib.gitcap_dbg_argmax_final_lp(ptr(d_val), ptr(d_idx), nt, R * T, 1, 0, ptr(out), 1, None, 0, -1, None, ptr(d_sum), ptr(alp), 1, stream()) == 0
     torch.cuda.synchronize()
     keep = torch.as_tensor([r * T + j for r in range(R) for j in range(T - 1)], device="cuda")
     assert torch.equal(t1[:-1], out[keep]) and torch.equal(t1lp[:-1].view(torch.int32), alp[keep].view(torch.int32))
@@ -210,8 +179,8 @@ def _final_case(lib, nt, T, use_lengths):
         assert gs[0] == 0.0                                                        # lengths 1: nothing counted
     # nullable outputs: token_lp alone gives the same values
     lp2 = torch.full((R, ld_lp), float("nan"), device="cuda")
-    assert lib.gitcap_dbg_score_final(_p(d_val), _p(d_idx), _p(d_sum), nt, _p(d_tgt), _p(d_y), ld_ids, R, T, _p(d_len), IGN, V,
-                                      _p(lp2), ld_lp, None, None, None, None, _stream()) == 0
+    assert lib.gitcap_dbg_score_final(ptr(d_val), ptr(d_idx), ptr(d_sum), nt, ptr(d_tgt), ptr(d_y), ld_ids, R, T, ptr(d_len), IGN, V,
+                                      ptr(lp2), ld_lp, None, None, None, None, stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(lp2[:, :T - 1].view(torch.int32), lp[:, :T - 1].view(torch.int32))
 
@@ -236,10 +205,10 @@ def test_score_final_is_independent_of_the_rows_beside_it(lib):
 
     def run(r0, r1):
         n = r1 - r0
-        a = [_dev(x[r0 * T:r1 * T], t) for x, t in ((val, torch.float32), (idx, torch.int32), (ssum, torch.float32), (tgt, torch.float32))]
+        a = [to_dev(x[r0 * T:r1 * T], t) for x, t in ((val, torch.float32), (idx, torch.int32), (ssum, torch.float32), (tgt, torch.float32))]
         lp = torch.zeros((n, T - 1), device="cuda"); rs = torch.zeros((n,), device="cuda")
-        assert lib.gitcap_dbg_score_final(_p(a[0]), _p(a[1]), _p(a[2]), nt, _p(a[3]), _p(_dev(y[r0:r1], torch.int64)), T, n, T, None, -1, V,
-                                          _p(lp), T - 1, _p(rs), None, None, None, _stream()) == 0
+        assert lib.gitcap_dbg_score_final(ptr(a[0]), ptr(a[1]), ptr(a[2]), nt, ptr(a[3]), ptr(to_dev(y[r0:r1], torch.int64)), T, n, T, None, -1, V,
+                                          ptr(lp), T - 1, ptr(rs), None, None, None, stream()) == 0
         torch.cuda.synchronize()
         return lp.view(torch.int32), rs.view(torch.int32)
     lp, rs = run(0, R)

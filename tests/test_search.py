@@ -71,17 +71,15 @@ def test_oracle_beam_output_format_and_greedy_limit():
 
 @pytest.mark.gpu
 def test_beam_topk_kernel_vs_torch():
-    import ctypes
     from gitcap import _lib
+    from gpu_support import ptr, stream
     lib = _lib.load()
     for B, beams, V, K in [(3, 4, 30522, 8), (2, 1, 197, 2), (1, 8, 1000, 16), (5, 3, 64, 6)]:
         g = torch.Generator(device="cuda").manual_seed(V)
         logits = torch.randn(B * beams, V, device="cuda", generator=g) * 3
         bs = torch.randn(B * beams, device="cuda", generator=g)
         out_s = torch.empty(B, K, device="cuda"); out_i = torch.empty(B, K, device="cuda", dtype=torch.int32)
-        rc = lib.gitcap_beam_topk(ctypes.c_void_p(logits.data_ptr()), V, ctypes.c_void_p(bs.data_ptr()), B, beams, V, K,
-                                  ctypes.c_void_p(out_s.data_ptr()), ctypes.c_void_p(out_i.data_ptr()),
-                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = lib.gitcap_beam_topk(ptr(logits), V, ptr(bs), B, beams, V, K, ptr(out_s), ptr(out_i), stream())
         assert rc == 0
         ref = (torch.log_softmax(logits, -1) + bs[:, None]).view(B, beams * V)
         rs, ri = ref.topk(K, dim=1)

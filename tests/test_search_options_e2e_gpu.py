@@ -14,6 +14,7 @@ import torch
 import search_options_reference as S
 from gitcap.config import git_tiny
 from gitcap.weights import synthetic_weights
+from gpu_support import camera, captioner_cls, ptr, stream  # noqa: F401
 from oracle.git_oracle import make_frames
 
 pytestmark = pytest.mark.gpu
@@ -25,20 +26,10 @@ KW = dict(beam_size=BEAMS, max_steps=L, length_penalty=LP, per_node_beam_size=PN
 OPT = dict(num_keep_best=N, repetition_penalty=RP)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 @pytest.fixture(scope="module")
-def model():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+def model(captioner_cls):
     cfg = git_tiny(2)
-    m = GitCaptioner(cfg, synthetic_weights(cfg, 0), max_batch=B, max_frames=F, max_text_len=L, max_beams=BEAMS, stop="never")
+    m = captioner_cls(cfg, synthetic_weights(cfg, 0), max_batch=B, max_frames=F, max_text_len=L, max_beams=BEAMS, stop="never")
     fr = make_frames(B, F, cfg.image_size, SEED).cuda()
     ws0 = m.workspace_bytes()
     r = m.infer(fr, on_device=True, **KW)                  # before any attachment
@@ -60,7 +51,7 @@ def _c_search(m, fr, opt=None, beams=BEAMS, nb=B, fill=-777):
         n, rp = opt
         o = CSearchOptions(n, rp, nbest.data_ptr(), nlp.data_ptr())
         rc_attach = m._lib.gitcap_attach_search_options(m._handle, ctypes.byref(o))
-    rc = m._lib.gitcap_beam_search(m._handle, _p(fr), nb, F, beams, L, ctypes.c_float(LP), PNB, _p(dec), _p(lp), _st())
+    rc = m._lib.gitcap_beam_search(m._handle, ptr(fr), nb, F, beams, L, ctypes.c_float(LP), PNB, ptr(dec), ptr(lp), stream())
     torch.cuda.synchronize()
     return rc_attach, rc, dec, lp, nbest, nlp
 
@@ -104,8 +95,7 @@ def test_every_entry_point_gives_the_same_bits(model):
     w = s.push(fr)
     assert torch.equal(w["predictions"], dev[0]) and torch.equal(w["logprobs"], dev[1])
     # raw camera frames: the raw submission == the transform followed by the plain call
-    g = torch.Generator().manual_seed(5)
-    cam = torch.randint(0, 256, (B, F, 80, 96, 3), dtype=torch.uint8, generator=g).cuda()
+    cam = camera((B, F, 80, 96, 3), 5).cuda()
     pre = preprocess_frames(cam, cfg.image_size).contiguous()
     a, b = m.infer(cam, on_device=True, **KW, **OPT), m.infer(pre, on_device=True, **KW, **OPT)
     c = m.infer_async(cam, **KW, **OPT).result()
@@ -158,9 +148,9 @@ def test_attachment_is_one_shot_and_checked(model):
     nlp = torch.full((B, N), float("nan"), device="cuda")
     o = CSearchOptions(N, RP, nbest.data_ptr(), nlp.data_ptr())
     assert lib.gitcap_attach_search_options(h, ctypes.byref(o)) == 0
-    assert lib.gitcap_encode(h, _p(fr), B, F, None, _st()) == 0
+    assert lib.gitcap_encode(h, ptr(fr), B, F, None, stream()) == 0
     ids = torch.empty((B, L + 1), dtype=torch.int64, device="cuda")
-    assert lib.gitcap_greedy(h, _p(fr), B, F, L, 0, _p(ids), None, _st()) == 0
+    assert lib.gitcap_greedy(h, ptr(fr), B, F, L, 0, ptr(ids), None, stream()) == 0
     torch.cuda.synchronize()
     assert bool((nbest == -777).all())
     _, rc, dec, lp, _, _ = _c_search(m, fr)

@@ -17,29 +17,11 @@ import torch
 
 import search_options_reference as S
 import selection_reference as R
+from gpu_support import beam_state, lib, ptr, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CASES = S.topk_cases()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
 
 
 def _run_pen(lib, c, rp=None, pad=3, plain=False):
@@ -49,14 +31,14 @@ def _run_pen(lib, c, rp=None, pad=3, plain=False):
     ld = V + pad
     buf = np.full((rows, ld), 1e30, np.float32)                    # row padding the kernel must not read
     buf[:, :V] = x
-    d_x, d_bs, d_pre = _dev(buf, torch.float32), _dev(c["bs"], torch.float32), _dev(c["prefix"], torch.int64)
+    d_x, d_bs, d_pre = to_dev(buf, torch.float32), to_dev(c["bs"], torch.float32), to_dev(c["prefix"], torch.int64)
     out_s = torch.full((B * K + 4,), float("nan"), device="cuda")
     out_i = torch.full((B * K + 4,), -5, device="cuda", dtype=torch.int32)
     if plain:
-        rc = lib.gitcap_beam_topk(_p(d_x), ld, _p(d_bs), B, beams, V, K, _p(out_s), _p(out_i), _stream())
+        rc = lib.gitcap_beam_topk(ptr(d_x), ld, ptr(d_bs), B, beams, V, K, ptr(out_s), ptr(out_i), stream())
     else:
-        rc = lib.gitcap_beam_topk_penalized(_p(d_x), ld, _p(d_bs), _p(d_pre), c["prefix"].shape[1], c["cur_len"],
-                                            ctypes.c_float(c["rp"] if rp is None else rp), B, beams, V, K, _p(out_s), _p(out_i), _stream())
+        rc = lib.gitcap_beam_topk_penalized(ptr(d_x), ld, ptr(d_bs), ptr(d_pre), c["prefix"].shape[1], c["cur_len"],
+                                            ctypes.c_float(c["rp"] if rp is None else rp), B, beams, V, K, ptr(out_s), ptr(out_i), stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out_s[B * K:]).all()) and bool((out_i[B * K:] == -5).all())
@@ -94,8 +76,8 @@ def test_beam_topk_penalized_refuses_bad_arguments(lib):
     out_i = torch.full((8,), -5, device="cuda", dtype=torch.int32)
 
     def call(x=x, ld=V, bs=bs, pre=pre, ld_ids=4, cur_len=3, rp=1.5, B=1, beams=beams, V=V, K=K, out_s=out_s, out_i=out_i, pre_ptr=None):
-        return lib.gitcap_beam_topk_penalized(_p(x), ld, _p(bs), pre_ptr if pre_ptr is not None else _p(pre), ld_ids, cur_len,
-                                              ctypes.c_float(rp), B, beams, V, K, _p(out_s), _p(out_i), _stream())
+        return lib.gitcap_beam_topk_penalized(ptr(x), ld, ptr(bs), pre_ptr if pre_ptr is not None else ptr(pre), ld_ids, cur_len,
+                                              ctypes.c_float(rp), B, beams, V, K, ptr(out_s), ptr(out_i), stream())
     assert call(x=None) == -1 and call(bs=None) == -1 and call(out_s=None) == -1 and call(out_i=None) == -1
     assert call(pre=None) == -1                                                   # a penalty needs the prefix
     assert call(pre_ptr=ctypes.c_void_p(pre.data_ptr() + 4)) == -1                # int64 ids: 8-byte aligned
@@ -115,29 +97,15 @@ def test_beam_topk_penalized_refuses_bad_arguments(lib):
 
 # ---- b. the n-best bookkeeping: whole toy searches --------------------------------------------------------------------------
 
-def _state(B, beams, n, L):
-    from gitcap._lib import CDbgBeamBuffers, CDbgBeamBuffersNbest
-    rows = B * beams
-    i64 = dict(device="cuda", dtype=torch.int64)
-    i32 = dict(device="cuda", dtype=torch.int32)
-    t = dict(ids0=torch.full((rows, L), -777, **i64), ids1=torch.full((rows, L), -777, **i64), words=torch.full((rows,), -777, **i64),
-             hyp_ids=torch.full((B, n, L), -777, **i64), beam_scores=torch.full((rows,), float("nan"), device="cuda"),
-             hyp_score=torch.full((B, n), float("nan"), device="cuda"), src_rows=torch.full((rows,), -777, **i32),
-             done=torch.full((B,), -777, **i32), hyp_len=torch.full((B, n), -777, **i32))
-    order = ("ids0", "ids1", "words", "hyp_ids", "beam_scores", "hyp_score", "src_rows", "done", "hyp_len")
-    ptrs = [t[k].data_ptr() for k in order]
-    return t, CDbgBeamBuffers(*ptrs), CDbgBeamBuffersNbest(*ptrs, n)
-
-
 def _device_search(lib, table, beams, lp, n, rp, seen=None, old_hooks=False):
     """The toy search on the device: penalised ranking + n-best step per position, then the finish.  old_hooks: the one-hypothesis
     hooks gitcap_dbg_beam_step / _finish (n = 1, rp = 1 only).  -> (decoded [B][n][L], logprobs [B][n], per-step snapshots)"""
     B, V, L, K = S.TOY_B, S.TOY_V, S.TOY_MAXLEN, 2 * beams
     rows = B * beams
-    t, bb1, bbn = _state(B, beams, n, L)
+    t, bb1, bbn = beam_state(B, beams, n, L)
     d_table = table.cuda()
     clip = torch.arange(rows, device="cuda") // beams
-    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb1), B, beams, L, S.TOY_CLS, _stream()) == 0
+    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb1), B, beams, L, S.TOY_CLS, stream()) == 0
     t["hyp_len"].zero_()                                    # the init hook passes n = 1 (one slot per clip): all B * n are zeroed here
     ids = [t["ids0"], t["ids1"]]
     cs = torch.empty(B, K, device="cuda")
@@ -147,16 +115,16 @@ def _device_search(lib, table, beams, lp, n, rp, seen=None, old_hooks=False):
         if seen is not None and cur_len - 1 < len(seen):   # the oracle's step function saw exactly these prefixes
             assert torch.equal(ids[cur][:, :cur_len].cpu(), seen[cur_len - 1]), cur_len
         logits = d_table[clip, (cur_len - 1) % 8, t["words"] % V].contiguous()
-        assert lib.gitcap_beam_topk_penalized(_p(logits), V, _p(t["beam_scores"]), _p(ids[cur]), L, cur_len, ctypes.c_float(rp), B, beams, V,
-                                              K, _p(cs), _p(ci), _stream()) == 0
+        assert lib.gitcap_beam_topk_penalized(ptr(logits), V, ptr(t["beam_scores"]), ptr(ids[cur]), L, cur_len, ctypes.c_float(rp), B, beams, V,
+                                              K, ptr(cs), ptr(ci), stream()) == 0
         torch.cuda.synchronize()
         assert bool(((ci >= 0) & (ci < beams * V)).all())
         if old_hooks:
-            rc = lib.gitcap_dbg_beam_step(ctypes.byref(bb1), _p(cs), _p(ci), B, beams, K, V, cur_len, L, S.TOY_EOS, ctypes.c_float(lp), cur,
-                                          _stream())
+            rc = lib.gitcap_dbg_beam_step(ctypes.byref(bb1), ptr(cs), ptr(ci), B, beams, K, V, cur_len, L, S.TOY_EOS, ctypes.c_float(lp), cur,
+                                          stream())
         else:
-            rc = lib.gitcap_dbg_beam_step_nbest(ctypes.byref(bbn), _p(cs), _p(ci), B, beams, K, V, cur_len, L, S.TOY_EOS,
-                                                ctypes.c_float(lp), cur, _stream())
+            rc = lib.gitcap_dbg_beam_step_nbest(ctypes.byref(bbn), ptr(cs), ptr(ci), B, beams, K, V, cur_len, L, S.TOY_EOS,
+                                                ctypes.c_float(lp), cur, stream())
         assert rc == 0
         torch.cuda.synchronize()
         cnt = (t["hyp_len"] > 0).sum(dim=1)
@@ -167,9 +135,9 @@ def _device_search(lib, table, beams, lp, n, rp, seen=None, old_hooks=False):
     decoded = torch.full((B, n, L), -777, device="cuda", dtype=torch.int64)
     logprobs = torch.full((B, n), float("nan"), device="cuda")
     if old_hooks:
-        rc = lib.gitcap_dbg_beam_finish(ctypes.byref(bb1), B, L, S.TOY_EOS, _p(decoded), _p(logprobs), _stream())
+        rc = lib.gitcap_dbg_beam_finish(ctypes.byref(bb1), B, L, S.TOY_EOS, ptr(decoded), ptr(logprobs), stream())
     else:
-        rc = lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, S.TOY_EOS, _p(decoded), _p(logprobs), _stream())
+        rc = lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, S.TOY_EOS, ptr(decoded), ptr(logprobs), stream())
     assert rc == 0
     torch.cuda.synchronize()
     return decoded, logprobs, snaps
@@ -219,21 +187,21 @@ def test_nbest_hooks_with_one_slot_are_the_old_hooks_bit_for_bit(lib, toy_table,
 def test_nbest_hooks_refuse_bad_arguments(lib):
     from gitcap._lib import CDbgBeamBuffersNbest
     B, beams, L, K, V = 2, 2, 5, 4, 23
-    t, _, bbn = _state(B, beams, 3, L)
+    t, _, bbn = beam_state(B, beams, 3, L)
     before = {k: v.clone() for k, v in t.items()}
     cs = torch.zeros(B, K, device="cuda")
     ci = torch.zeros(B, K, device="cuda", dtype=torch.int32)
     dec = torch.full((B, 3, L), -777, device="cuda", dtype=torch.int64)
     lp = torch.full((B, 3), float("nan"), device="cuda")
     step = lambda bb, cur_len=1, cur=0, beams=beams, K=K: lib.gitcap_dbg_beam_step_nbest(
-        ctypes.byref(bb), _p(cs), _p(ci), B, beams, K, V, cur_len, L, 22, ctypes.c_float(0.6), cur, _stream())
+        ctypes.byref(bb), ptr(cs), ptr(ci), B, beams, K, V, cur_len, L, 22, ctypes.c_float(0.6), cur, stream())
     for bad_n in (0, 17):
         bad = CDbgBeamBuffersNbest(*[getattr(bbn, f) for f, _ in CDbgBeamBuffersNbest._fields_[:-1]], bad_n)
         assert step(bad) == -1
-        assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bad), B, L, 22, _p(dec), _p(lp), _stream()) == -1
+        assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bad), B, L, 22, ptr(dec), ptr(lp), stream()) == -1
     assert step(bbn, cur_len=0) == -1 and step(bbn, cur_len=L) == -1 and step(bbn, cur=2) == -1
     assert step(bbn, beams=17) == -1 and step(bbn, K=17) == -1
-    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, 22, None, _p(lp), _stream()) == -1
+    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, 22, None, ptr(lp), stream()) == -1
     torch.cuda.synchronize()
     for k in t:
         a, b = t[k], before[k]
@@ -246,7 +214,7 @@ def test_nbest_hooks_refuse_bad_arguments(lib):
 def test_nbest_finish_orders_equal_scores_by_storage_and_pads_empty_ranks(lib):
     """Hand-made state: three stored hypotheses of four slots, two of them with the same score."""
     B, beams, n, L = 1, 1, 4, 6
-    t, _, bbn = _state(B, beams, n, L)
+    t, _, bbn = beam_state(B, beams, n, L)
     t["hyp_len"].copy_(torch.tensor([[2, 3, 1, 0]], dtype=torch.int32))
     t["hyp_score"].copy_(torch.tensor([[-1.5, -0.5, -1.5, 7.0]]))           # slot 3 is empty: its score is no score
     t["hyp_ids"][0, 0, :2] = torch.tensor([0, 4], device="cuda")
@@ -254,7 +222,7 @@ def test_nbest_finish_orders_equal_scores_by_storage_and_pads_empty_ranks(lib):
     t["hyp_ids"][0, 2, :1] = torch.tensor([0], device="cuda")
     dec = torch.full((B, n, L), -777, device="cuda", dtype=torch.int64)
     lp = torch.full((B, n), float("nan"), device="cuda")
-    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, 22, _p(dec), _p(lp), _stream()) == 0
+    assert lib.gitcap_dbg_beam_finish_nbest(ctypes.byref(bbn), B, L, 22, ptr(dec), ptr(lp), stream()) == 0
     torch.cuda.synchronize()
     assert dec[0].tolist() == [[0, 5, 6, 22, 22, 22], [0, 4, 22, 22, 22, 22], [0, 22, 22, 22, 22, 22], [22] * 6]
     assert lp[0].tolist() == [-0.5, -1.5, -1.5, -1e5]

@@ -16,31 +16,14 @@ import pytest
 import torch
 
 import selection_reference as R
+from selection_reference import DRAFT_NT, DRAFT_SEP, draft_scenario, draft_scenarios
 from oracle import search_oracle
+from gpu_support import e4m3_rows, lib, ptr, run_vocab_head, stream, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NINF = float("-inf")
 SENT = R.SENTINEL
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from gitcap import _lib
-    assert torch.cuda.is_available()
-    return _lib.load()
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype)
 
 
 # ---- a. vocabulary head -------------------------------------------------------------------------------------------------
@@ -72,9 +55,7 @@ def _head_inputs(M, N, K, variant, fp8, seed):
     for i, n in enumerate(range(N, Np)):            # padding rows: a missing n < N guard would make them the arg-max
         Wf[n] = 4.0 * X[i % M, :K].float()
     if fp8:
-        wscale = torch.exp2(torch.ceil(torch.log2(Wf.abs().amax(dim=1) / 448.0)))
-        W = (Wf / wscale[:, None]).to(torch.float8_e4m3fn)
-        Weff = W.float() * wscale[:, None]
+        W, wscale, Weff = e4m3_rows(Wf)
     else:
         wscale = None
         W = Wf.bfloat16()
@@ -82,25 +63,9 @@ def _head_inputs(M, N, K, variant, fp8, seed):
     return X, ldx, W, wscale, bias, Weff, ties
 
 
-def _run_head(lib, X, ldx, W, wscale, bias, M, N, K, share):
-    nt = (N + 15) // 16
-    logits = torch.full((M * N + 16,), float("nan"), device="cuda")
-    val = torch.full((M * nt + 16,), float("nan"), device="cuda")
-    idx = torch.full((M * nt + 16,), -5, device="cuda", dtype=torch.int32)
-    old = lib.gitcap_dbg_config(10, share)
-    try:
-        rc = lib.gitcap_dbg_vocab_head(_p(X), ldx, _p(W), _p(wscale), _p(bias), M, N, K, _p(logits), _p(val), _p(idx), _stream())
-        torch.cuda.synchronize()
-    finally:
-        lib.gitcap_dbg_config(10, old)
-    assert rc == 0
-    assert bool(torch.isnan(logits[M * N:]).all()) and bool(torch.isnan(val[M * nt:]).all()) and bool((idx[M * nt:] == -5).all())
-    return logits[:M * N].view(M, N), val[:M * nt].view(M, nt), idx[:M * nt].view(M, nt)
-
-
 def _argmax_final(lib, val, idx, rows, nt):
     out = torch.full((rows,), -9, device="cuda", dtype=torch.int64)
-    assert lib.gitcap_dbg_argmax_final(_p(val), _p(idx), nt, rows, 1, 0, _p(out), 1, None, 0, -1, None, _stream()) == 0
+    assert lib.gitcap_dbg_argmax_final(ptr(val), ptr(idx), nt, rows, 1, 0, ptr(out), 1, None, 0, -1, None, stream()) == 0
     return out.cpu().tolist()
 
 
@@ -108,7 +73,7 @@ def _head_check(lib, X, ldx, W, wscale, bias, Weff, M, N, K):
     """Both forms of the kernel: equal bits; partials == first arg-max of the logits the kernel wrote; logits ~ fp64 product;
     the token argmax_final makes of the partials == the first arg-max of the row.  Returns the logits (numpy)."""
     nt = (N + 15) // 16
-    outs = [_run_head(lib, X, ldx, W, wscale, bias, M, N, K, share) for share in (1, 0)]
+    outs = [run_vocab_head(lib, X, ldx, W, wscale, bias, M, N, K, share=share)[:3] for share in (1, 0)]
     for a, b in zip(outs[0], outs[1]):
         assert torch.equal(a, b)
     logits, val, idx = outs[0]
@@ -164,11 +129,11 @@ def test_vocab_head_rejects_bad_arguments(lib):
     x = torch.zeros(16, 64, device="cuda", dtype=torch.bfloat16)
     f = torch.zeros(64, device="cuda")
     i = torch.zeros(64, device="cuda", dtype=torch.int32)
-    assert lib.gitcap_dbg_vocab_head(None, 64, _p(x), None, None, 1, 16, 64, _p(f), _p(f), _p(i), None) == -1
-    assert lib.gitcap_dbg_vocab_head(_p(x), 64, _p(x), None, None, 1, 16, 96, _p(f), _p(f), _p(i), None) == -1      # K not built
-    assert lib.gitcap_dbg_vocab_head(_p(x), 60, _p(x), None, None, 1, 16, 64, _p(f), _p(f), _p(i), None) == -1      # ldx < K
-    assert lib.gitcap_dbg_vocab_head(_p(x), 64, _p(x), None, None, 1, 16, 64, _p(f), _p(f), None, None) == -1       # half a pair
-    assert lib.gitcap_dbg_vocab_head(_p(x), 64, _p(x), _p(f), None, 1, 16, 64, _p(f), _p(f), _p(i), None) == -1     # e4m3 at K = 64
+    assert lib.gitcap_dbg_vocab_head(None, 64, ptr(x), None, None, 1, 16, 64, ptr(f), ptr(f), ptr(i), None) == -1
+    assert lib.gitcap_dbg_vocab_head(ptr(x), 64, ptr(x), None, None, 1, 16, 96, ptr(f), ptr(f), ptr(i), None) == -1      # K not built
+    assert lib.gitcap_dbg_vocab_head(ptr(x), 60, ptr(x), None, None, 1, 16, 64, ptr(f), ptr(f), ptr(i), None) == -1      # ldx < K
+    assert lib.gitcap_dbg_vocab_head(ptr(x), 64, ptr(x), None, None, 1, 16, 64, ptr(f), ptr(f), None, None) == -1       # half a pair
+    assert lib.gitcap_dbg_vocab_head(ptr(x), 64, ptr(x), ptr(f), None, 1, 16, 64, ptr(f), ptr(f), ptr(i), None) == -1     # e4m3 at K = 64
 
 
 # ---- b. argmax_final ----------------------------------------------------------------------------------------------------
@@ -212,9 +177,9 @@ def _argmax_final_case(lib, nt, D=0):
         val[r * stride + off], idx[r * stride + off] = v, i
     want = [R.argmax_partials(v, i) for v, i in rows]
     assert want[1] == 5 and want[2] == 16 * (nt - 1) + 5 and want[-1] == 0 and want[-2] == 5 and want[-3] == 5
-    d_val, d_idx = _dev(val, torch.float32), _dev(idx, torch.int32)
+    d_val, d_idx = to_dev(val, torch.float32), to_dev(idx, torch.int32)
     out = torch.full((n, ld_out), -7, device="cuda", dtype=torch.int64)
-    sep_cnt = _dev([100, 200, 300, 400], torch.int32)
+    sep_cnt = to_dev([100, 200, 300, 400], torch.int32)
     emb = None
     if D:
         g = torch.Generator(device="cuda").manual_seed(D)
@@ -227,8 +192,8 @@ def _argmax_final_case(lib, nt, D=0):
         from gitcap._lib import CDbgNextEmbed
         emb = CDbgNextEmbed(word.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-5, D, vocab, position,
                             xf.data_ptr(), xb.data_ptr())
-    rc = lib.gitcap_dbg_argmax_final(_p(d_val), _p(d_idx), nt, n, stride, off, _p(out), ld_out, _p(sep_cnt), step, SEP,
-                                     ctypes.byref(emb) if emb else None, _stream())
+    rc = lib.gitcap_dbg_argmax_final(ptr(d_val), ptr(d_idx), nt, n, stride, off, ptr(out), ld_out, ptr(sep_cnt), step, SEP,
+                                     ctypes.byref(emb) if emb else None, stream())
     torch.cuda.synchronize()
     assert rc == 0
     got = out.cpu().numpy()
@@ -260,53 +225,6 @@ def test_argmax_final_next_embed(lib, nt, D):
 
 # ---- c. draft_accept ----------------------------------------------------------------------------------------------------
 
-DRAFT_NT, DRAFT_SEP, DRAFT_POISON = 5, 9, -777
-
-
-def _draft_scenario(B, n, a_rows, sep_at, rng):
-    """Model tokens tok [B][n] with SEP at the (row, step) pairs of sep_at, and ids [B][ld] whose draft agrees with row r at
-    exactly its first a_rows[r] positions (the first disagreement of row 0 is a staged -1); ld = n + 4."""
-    vocab, ld = 16 * DRAFT_NT, n + 4
-    tok = rng.integers(10, vocab, (B, n))
-    for r, t in sep_at:
-        tok[r, t] = DRAFT_SEP
-    ids = np.full((B, ld), DRAFT_POISON, np.int64)
-    ids[:, 0] = 1
-    for r in range(B):
-        for j in range(n):
-            if j < a_rows[r] or (j > a_rows[r] and rng.random() < 0.5):
-                ids[r, j + 1] = tok[r, j]
-            elif j == a_rows[r] and r == 0:
-                ids[r, j + 1] = -1
-            else:
-                ids[r, j + 1] = 10 + (tok[r, j] - 10 + 1 + rng.integers(0, vocab - 12)) % (vocab - 10)
-                assert ids[r, j + 1] != tok[r, j]
-    # partials that reduce to tok: the winner's tile holds 2.0 and the token; every second row has an equal value with a
-    # larger index in another tile (the tie rule picks the token)
-    val = rng.random((B * n, DRAFT_NT)).astype(np.float32)
-    idx = np.arange(DRAFT_NT, dtype=np.int64)[None, :] * 16 + rng.integers(0, 16, (B * n, DRAFT_NT))
-    for m in range(B * n):
-        t = int(tok[m // n, m % n])
-        val[m, t // 16], idx[m, t // 16] = 2.0, t
-        if m % 2:
-            o = (t // 16 + 1 + m % (DRAFT_NT - 1)) % DRAFT_NT
-            val[m, o], idx[m, o] = 2.0, t + 1 + m % 3
-    return tok, ids, val, idx
-
-
-def _draft_scenarios(B, n):
-    mid = n // 2
-    out = [([n] * B, [(r, n - 1) for r in range(B)]),                           # a = n; all rows SEP in the last step: fired
-           ([0] + [n] * (B - 1), [(r, 0) for r in range(B)])]                   # a = 0; SEP at once in the model's own tokens
-    if n >= 2:
-        stair = [min(n, mid + r % 3) for r in range(B)]                         # rows disagree at different positions
-        sep = [(r, mid + 1) for r in range(B)] if mid + 1 < n else []           # all rows, but beyond `covered`: not fired
-        sep += [(r, r % (mid + 1)) for r in range(B)] if B > 1 else []          # inside `covered`, in different steps
-        out.append((stair, sep))
-        out.append(([n] * (B - 1) + [mid], []))                                 # the minimum sits in the last row
-    return out
-
-
 @pytest.mark.parametrize("n", [1, 2, 63])
 @pytest.mark.parametrize("B", [1, 2, 5])
 def test_draft_accept_vs_restatement(lib, B, n):
@@ -314,19 +232,19 @@ def test_draft_accept_vs_restatement(lib, B, n):
     tok_scratch = torch.full((B * n,), -3, device="cuda", dtype=torch.int32)
     ticket = torch.zeros(1, device="cuda", dtype=torch.int32)
     seen_a = set()
-    for a_rows, sep_at in _draft_scenarios(B, n):          # every launch on the same ticket word
-        tok, ids, val, idx = _draft_scenario(B, n, a_rows, sep_at, rng)
+    for a_rows, sep_at in draft_scenarios(B, n):          # every launch on the same ticket word
+        tok, ids, val, idx = draft_scenario(B, n, a_rows, sep_at, rng)
         assert [R.argmax_partials(v, i) for v, i in zip(val, idx)] == tok.reshape(-1).tolist()
         want = R.draft_accept(tok, ids, DRAFT_SEP)
         assert want["a_r"] == a_rows                       # the inputs are what they were designed to be
         seen_a.add(want["a"])
         ld = ids.shape[1]
-        d_ids = _dev(ids, torch.int64)
+        d_ids = to_dev(ids, torch.int64)
         sep_cnt = torch.full((n + 2,), 77, device="cuda", dtype=torch.int32)
         host = (ctypes.c_int32 * 2)(-5, -5)
-        d_val, d_idx = _dev(val, torch.float32), _dev(idx, torch.int32)
-        rc = lib.gitcap_dbg_draft_accept(_p(d_val), _p(d_idx), DRAFT_NT, B, n, _p(d_ids), ld, _p(tok_scratch), _p(ticket),
-                                         _p(sep_cnt), DRAFT_SEP, host, _stream())
+        d_val, d_idx = to_dev(val, torch.float32), to_dev(idx, torch.int32)
+        rc = lib.gitcap_dbg_draft_accept(ptr(d_val), ptr(d_idx), DRAFT_NT, B, n, ptr(d_ids), ld, ptr(tok_scratch), ptr(ticket),
+                                         ptr(sep_cnt), DRAFT_SEP, host, stream())
         torch.cuda.synchronize()
         assert rc == 0
         assert (host[0], host[1]) == want["host"]
@@ -343,17 +261,17 @@ def test_draft_accept_fired_flag_cases(lib):
     for a_rows, sep_at, fired in [([4, 4], [(0, 1), (1, 1)], 1), ([4, 4], [(0, 1), (1, 2)], 0), ([1, 4], [(0, 2), (1, 2)], 0),
                                   ([1, 4], [(0, 1), (1, 1)], 1), ([1, 4], [(0, 0)], 0)]:
         rng = np.random.default_rng(7)
-        tok, ids, val, idx = _draft_scenario(B, n, a_rows, sep_at, rng)
+        tok, ids, val, idx = draft_scenario(B, n, a_rows, sep_at, rng)
         want = R.draft_accept(tok, ids, DRAFT_SEP)
         assert want["host"] == (min(a_rows), fired)
-        d_ids = _dev(ids, torch.int64)
+        d_ids = to_dev(ids, torch.int64)
         sep_cnt = torch.full((n + 2,), 77, device="cuda", dtype=torch.int32)
         scratch = torch.zeros(B * n, device="cuda", dtype=torch.int32)
         ticket = torch.zeros(1, device="cuda", dtype=torch.int32)
         host = (ctypes.c_int32 * 2)(-5, -5)
-        d_val, d_idx = _dev(val, torch.float32), _dev(idx, torch.int32)
-        assert lib.gitcap_dbg_draft_accept(_p(d_val), _p(d_idx), DRAFT_NT, B, n, _p(d_ids), ids.shape[1], _p(scratch), _p(ticket),
-                                           _p(sep_cnt), DRAFT_SEP, host, _stream()) == 0
+        d_val, d_idx = to_dev(val, torch.float32), to_dev(idx, torch.int32)
+        assert lib.gitcap_dbg_draft_accept(ptr(d_val), ptr(d_idx), DRAFT_NT, B, n, ptr(d_ids), ids.shape[1], ptr(scratch), ptr(ticket),
+                                           ptr(sep_cnt), DRAFT_SEP, host, stream()) == 0
         assert (host[0], host[1]) == want["host"] and np.array_equal(d_ids.cpu().numpy(), want["ids"])
         assert sep_cnt.cpu().tolist() == want["sep_cnt"] + [77] * (n + 2 - want["covered"])
 
@@ -458,10 +376,10 @@ def _run_topk(lib, x, bs, beams, K, pad=3):
     ld = V + pad
     buf = np.full((rows, ld), 1e30, np.float32)                    # row padding the kernel must not read
     buf[:, :V] = x
-    d_x, d_bs = _dev(buf, torch.float32), _dev(bs, torch.float32)
+    d_x, d_bs = to_dev(buf, torch.float32), to_dev(bs, torch.float32)
     out_s = torch.full((B * K + 4,), float("nan"), device="cuda")
     out_i = torch.full((B * K + 4,), -5, device="cuda", dtype=torch.int32)
-    rc = lib.gitcap_beam_topk(_p(d_x), ld, _p(d_bs), B, beams, V, K, _p(out_s), _p(out_i), _stream())
+    rc = lib.gitcap_beam_topk(ptr(d_x), ld, ptr(d_bs), B, beams, V, K, ptr(out_s), ptr(out_i), stream())
     torch.cuda.synchronize()
     assert rc == 0
     assert bool(torch.isnan(out_s[B * K:]).all()) and bool((out_i[B * K:] == -5).all())
@@ -499,7 +417,7 @@ def test_beam_topk_refuses_more_than_64_chunks(lib):
     bs = torch.zeros(1, device="cuda")
     out_s = torch.full((8,), float("nan"), device="cuda")
     out_i = torch.full((8,), -5, device="cuda", dtype=torch.int32)
-    assert lib.gitcap_beam_topk(_p(x), V, _p(bs), 1, 1, V, 8, _p(out_s), _p(out_i), _stream()) == -1
+    assert lib.gitcap_beam_topk(ptr(x), V, ptr(bs), 1, 1, V, 8, ptr(out_s), ptr(out_i), stream()) == -1
     torch.cuda.synchronize()
     assert bool(torch.isnan(out_s).all()) and bool((out_i == -5).all())          # nothing was launched
 
@@ -561,7 +479,7 @@ def test_beam_bookkeeping_whole_search_vs_oracle(lib, monkeypatch, beams, lp):
     src_rows, done, hyp_len = torch.full((rows,), -777, **i32), torch.full((B,), -777, **i32), torch.full((B,), -777, **i32)
     bb = CDbgBeamBuffers(ids[0].data_ptr(), ids[1].data_ptr(), words.data_ptr(), hyp_ids.data_ptr(), scores.data_ptr(),
                          hyp_score.data_ptr(), src_rows.data_ptr(), done.data_ptr(), hyp_len.data_ptr())
-    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb), B, beams, L, BEAM_CLS, _stream()) == 0
+    assert lib.gitcap_dbg_beam_init(ctypes.byref(bb), B, beams, L, BEAM_CLS, stream()) == 0
     torch.cuda.synchronize()
     assert ids[0][:, 0].tolist() == [BEAM_CLS] * rows and words.tolist() == [BEAM_CLS] * rows
     assert bool((ids[0][:, 1:] == -777).all()) and bool((ids[1] == -777).all())
@@ -574,12 +492,12 @@ def test_beam_bookkeeping_whole_search_vs_oracle(lib, monkeypatch, beams, lp):
     for cur_len in range(1, L):
         assert torch.equal(ids[cur][:, :cur_len].cpu(), seen[cur_len - 1]) if cur_len - 1 < len(seen) else True
         logits = d_table[clip, (cur_len - 1) % 8, words % V].contiguous()
-        assert lib.gitcap_beam_topk(_p(logits), V, _p(scores), B, beams, V, K, _p(cs), _p(ci), _stream()) == 0
+        assert lib.gitcap_beam_topk(ptr(logits), V, ptr(scores), B, beams, V, K, ptr(cs), ptr(ci), stream()) == 0
         torch.cuda.synchronize()
         assert bool(((ci >= 0) & (ci < beams * V)).all())               # never hand beam_step the sentinel
         old = ids[cur].clone()
-        assert lib.gitcap_dbg_beam_step(ctypes.byref(bb), _p(cs), _p(ci), B, beams, K, V, cur_len, L, BEAM_EOS,
-                                        ctypes.c_float(lp), cur, _stream()) == 0
+        assert lib.gitcap_dbg_beam_step(ctypes.byref(bb), ptr(cs), ptr(ci), B, beams, K, V, cur_len, L, BEAM_EOS,
+                                        ctypes.c_float(lp), cur, stream()) == 0
         torch.cuda.synchronize()
         new, src = ids[cur ^ 1], src_rows.long()
         assert bool(((src >= 0) & (src < rows)).all())
@@ -599,7 +517,7 @@ def test_beam_bookkeeping_whole_search_vs_oracle(lib, monkeypatch, beams, lp):
         cur ^= 1
     decoded = torch.full((B, L), -777, **i64)
     logprobs = torch.full((B,), float("nan"), device="cuda")
-    assert lib.gitcap_dbg_beam_finish(ctypes.byref(bb), B, L, BEAM_EOS, _p(decoded), _p(logprobs), _stream()) == 0
+    assert lib.gitcap_dbg_beam_finish(ctypes.byref(bb), B, L, BEAM_EOS, ptr(decoded), ptr(logprobs), stream()) == 0
     torch.cuda.synchronize()
     assert torch.equal(decoded.cpu(), dec)
     assert torch.allclose(logprobs.cpu(), lps.view(-1), rtol=0, atol=1e-4)

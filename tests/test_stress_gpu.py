@@ -28,29 +28,19 @@ import numpy as np
 import pytest
 import torch
 
-from gitcap.config import GitCapConfig, git_base, git_tiny
+from gitcap.config import git_base, git_tiny
 from gitcap.weights import quantize_weights_fp8, stress_weights, synthetic_weights
 from oracle.git_oracle import GitOracle, make_frames
+from gpu_support import captioner_cls, mid768, rms  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL_EMUL, LOGIT_TOL_FP32, NEAR_TIE = 0.08, 0.20, 0.16      # tests/test_parity_gpu.py
 
 
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
-
-
 def _tols(l_e, l_f):
     d = float((l_e - l_f).abs().max())
     return max(LOGIT_TOL_EMUL, 1.5 * d), max(LOGIT_TOL_FP32, 2.0 * d), d
-
-
-def _rms(x):
-    return float(x.double().pow(2).mean().sqrt())
 
 
 # measured (GPUTEST r05 / r06 logs: max, rms of device - emulating oracle) -> allowed (about 1.4 x)
@@ -67,7 +57,7 @@ def _check_logits(tag, lg, l_e, l_f):
     roundings of an ill-conditioned row move only the max."""
     tol_e, tol_f, d = _tols(l_e, l_f)
     de, df = float((lg - l_e).abs().max()), float((lg - l_f).abs().max())
-    re, rf, r0 = _rms(lg - l_e), _rms(lg - l_f), _rms(l_e - l_f)
+    re, rf, r0 = rms(lg - l_e), rms(lg - l_f), rms(l_e - l_f)
     print(f"{tag}: max |emul - fp32| {d:.3f}, device vs emul {de:.3f} (tol {tol_e:.3f}), vs fp32 {df:.3f} (tol {tol_f:.3f}); "
           f"rms emul - fp32 {r0:.4f}, device - emul {re:.4f}, device - fp32 {rf:.4f}; logit std {float(l_f.std()):.2f}")
     assert de < tol_e and df < tol_f
@@ -100,7 +90,7 @@ def test_tiny_stress_stages_vs_oracle_and_hf(captioner_cls, golden_dir):
     assert float(vis.abs().max()) > 8.0                                        # the outliers reach the device
     assert (vis - v_e).abs().max() < max(2e-2, 1.5 * dv), (float((vis - v_e).abs().max()), dv)
     assert (vis - v_f).abs().max() < 2.0 * dv + 1e-2
-    assert _rms(vis - v_e) < 1.5 * _rms(v_e - v_f) + 1e-3
+    assert rms(vis - v_e) < 1.5 * rms(v_e - v_f) + 1e-3
     assert np.abs(vis.numpy() - g["visual"]).max() < 2.0 * dv + 1e-2          # HF fp32 fixture
     ids = torch.from_numpy(g["prefix_ids"])
     lg = m(fr, ids).cpu()
@@ -155,7 +145,7 @@ def test_base_stress_vs_hf_golden(captioner_cls, golden_dir):
     _, vis = m.forward_image_enc(fr)
     assert float(vis.abs().max()) > 10.0
     assert (vis.cpu() - v_e).abs().max() < max(2e-2, 1.5 * dv), (float((vis.cpu() - v_e).abs().max()), dv)
-    assert _rms(vis.cpu() - v_e) < 1.5 * _rms(v_e - v_f) + 1e-3
+    assert rms(vis.cpu() - v_e) < 1.5 * rms(v_e - v_f) + 1e-3
     assert np.abs(vis.cpu()[:, ::97, :32].numpy() - g["visual_slice"]).max() < 2.0 * dv + 1e-2
     lg = m.forward_decoder(gold[:, :-1], vis).cpu()
     tol_e, tol_f = _check_logits("base stress", lg, l_e, l_f)
@@ -283,18 +273,13 @@ def test_student_decoder_at_caller_lengths(L):
     assert torch.equal(m.beam_search(mem, max_len=L + 1, k=3), m.beam_search_host(mem, max_len=L + 1, k=3))
 
 
-def _mid768():
-    return GitCapConfig(image_size=64, patch_size=16, enc_width=768, enc_layers=2, enc_heads=12, enc_ffn=3072, dec_width=768,
-                        dec_layers=2, dec_heads=12, dec_ffn=3072, vocab_size=997, max_text_pos=64, num_frames=3)
-
-
 def test_fp8_ffn_saturation_is_counted_and_scale_is_settable(captioner_cls):
     """compute="fp8_ffn" quantises the FFN activations of the image rows with ONE static scale (default 1/16: codes cover
     +-28).  On weights with outlier channels and saturating GELU inputs that clamps -- and the clamps are counted on the
     device (gitcap_fp8_saturations), as many as the oracle emulating the mode counts.  With the scale raised until
     nothing clamps (gitcap_set_fp8_scale) the mode is back within a few percent of the logit spread.  Plain weights never clamp at
     the default scale."""
-    cfg = _mid768()
+    cfg = mid768()
     fr = make_frames(3, 3, cfg.image_size, 19)
     ids = torch.tensor([[101, 5, 9, 7], [101, 77, 3, 2], [101, 500, 41, 8]])
     # plain weights: nothing clamps at the default scale
@@ -341,7 +326,7 @@ def test_fp8_ffn_saturation_is_counted_and_scale_is_settable(captioner_cls):
         with torch.no_grad():
             olc = oc.decoder_text(oc.image_kv(oc.forward_image_enc(fr)[1]), ids)
         row = dict(scale=scale, dev_sat=n, orc_sat=oc.f8_sat, d_own=float((l - olc).abs().max()), d_bf16=float((l - olb).abs().max()),
-                   rms_own=_rms(l - olc), rms_bf16=_rms(l - olb), orc_d_bf16=float((olc - olb).abs().max()))
+                   rms_own=rms(l - olc), rms_bf16=rms(l - olb), orc_d_bf16=float((olc - olb).abs().max()))
         table.append(row)
         print("fp8_ffn on stress weights:", {k: (round(x, 4) if isinstance(x, float) else x) for k, x in row.items()})
         assert abs(n - oc.f8_sat) <= max(8, 0.02 * oc.f8_sat), row

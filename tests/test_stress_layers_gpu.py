@@ -17,31 +17,15 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stress_layers import device_stages, format_table, stage_table, ulps_of_rowmax      # noqa: E402
+from stress_layers import (TOL_DEC_MAX_ULP, TOL_ENC_MAX_ULP, TOL_GEMM_STAGE_ULP, TOL_RMS_ULP, device_stages, format_table, stage_table,   # noqa: E402
+                           ulps_of_rowmax)
 
-from gitcap.config import GitCapConfig, git_base, git_large                               # noqa: E402
+from gitcap.config import git_base, git_large                                             # noqa: E402
 from gitcap.weights import quantize_weights_fp8, stress_weights, synthetic_weights        # noqa: E402
 from oracle.git_oracle import GitOracle, make_frames                                      # noqa: E402
+from gpu_support import captioner_cls, mid768, ptr, rms, stream                           # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
-
-# Fixed tolerances, in bf16 ulps of the row maximum, for ONE stage on shared inputs.  A stage's output differs between the device
-# and the emulating oracle only where a GEMM operand sits within fp32 summation noise of a bf16 rounding boundary and falls the other
-# way (one operand ulp, times a weight), and by the fp32 summation order itself.  Measured (profiles/r06_stress_divergence.md; plain
-# and stress weights, GIT-base and the configs[4] shape): single-GEMM stages 0.0001; encoder blocks max 0.14 - 0.58, rms 0.008 - 0.048;
-# decoder layers max 0.30 - 0.34 (plain) and 0.63 - 2.13 (stress: inside a layer a flipped q / k operand still moves a
-# winner-take-all softmax row), rms 0.017 - 0.050 -- while END TO END the same runs reach 2.3 - 33 ulp.  The numbers below are those
-# measurements with about 2 x headroom; none is computed from the data under test.
-TOL_GEMM_STAGE_ULP = 0.01                   # patch embed + ln_pre, projection, text embedding, vocabulary head: one GEMM / gather + LayerNorm
-TOL_ENC_MAX_ULP, TOL_DEC_MAX_ULP = 1.25, 4.0
-TOL_RMS_ULP = 0.1
-
-
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
 
 
 def _check(title, rows):
@@ -88,11 +72,6 @@ def test_config4_shape_every_stage_on_device_inputs(captioner_cls):
     _check("GIT-large (configs[4] shape), stress weights, 1 clip x 10 frames, T = 6", rows)
 
 
-def _mid768(dec_layers=2):
-    return GitCapConfig(image_size=64, patch_size=16, enc_width=768, enc_layers=2, enc_heads=12, enc_ffn=3072, dec_width=768,
-                        dec_layers=dec_layers, dec_heads=12, dec_ffn=3072, vocab_size=997, max_text_pos=64, num_frames=3)
-
-
 @pytest.mark.parametrize("scale", [1.0 / 16.0, 0.5])
 def test_fp8_ffn_tracks_its_own_oracle_per_layer(captioner_cls, scale):
     """compute="fp8_ffn" at the single-layer level: FC1 -> GELU -> FC2 on e4m3 operands inside one block, device vs
@@ -100,7 +79,7 @@ def test_fp8_ffn_tracks_its_own_oracle_per_layer(captioner_cls, scale):
     at most HALF as far (rms) from it as from the bf16-compute oracle on the same input (= what the mode costs in that block) --
     the assertion tests/test_stress_gpu.py had to give up end to end.  At the default scale the stress weights clamp (counted);
     the oracle clamps the same codes, so the rule holds there too."""
-    cfg = _mid768()
+    cfg = mid768()
     ws = quantize_weights_fp8(stress_weights(cfg, 0))
     fr = make_frames(3, 3, cfg.image_size, 19)
     ids = torch.tensor([[101, 5, 9, 7], [101, 77, 3, 2], [101, 500, 41, 8]])
@@ -109,7 +88,6 @@ def test_fp8_ffn_tracks_its_own_oracle_per_layer(captioner_cls, scale):
     own = GitOracle(cfg, ws, emulate_bf16=True, emulate_fp8_act="ffn", fp8_scale=scale)
     bf = GitOracle(cfg, ws, emulate_bf16=True)
     S_img = 3 * cfg.tokens_per_frame
-    rms = lambda t: float(t.double().pow(2).mean().sqrt())
     rows = []
     with torch.no_grad():
         enc, hid = dev["enc"], dev["hidden"]
@@ -132,14 +110,6 @@ def test_fp8_ffn_tracks_its_own_oracle_per_layer(captioner_cls, scale):
 
 
 # ------------------------------------------------------------------------------------------------ kernels, stress-shaped operands
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 @pytest.mark.parametrize("M,N,K,post", [(1024, 768, 768, 0), (1024, 768, 3072, 0), (1024, 768, 3072, 1), (512, 1024, 1024, 1)])
 def test_gemm_ln_outlier_operands(M, N, K, post):
     """gemm_ln (fused and unfused) on stress-shaped operands: four outlier columns x 20-60 in A (the FC2 operand behind saturating
@@ -165,8 +135,8 @@ def test_gemm_ln_outlier_operands(M, N, K, post):
     for fused, tile in ((1, 256), (0, 256), (0, 128)):
         of = torch.full((M, N), float("nan"), device="cuda")
         ob = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
-        assert lib.gitcap_dbg_gemm_ln(_p(A), _p(W), _p(bias), _p(resid), _p(gamma), _p(beta), ctypes.c_float(1e-5), _p(of), _p(ob),
-                                      M, N, K, post, fused, tile, _stream()) == 0
+        assert lib.gitcap_dbg_gemm_ln(ptr(A), ptr(W), ptr(bias), ptr(resid), ptr(gamma), ptr(beta), ctypes.c_float(1e-5), ptr(of), ptr(ob),
+                                      M, N, K, post, fused, tile, stream()) == 0
         torch.cuda.synchronize()
         outs.append((of, ob))
     for of, ob in outs[1:]:
@@ -204,7 +174,7 @@ def test_attn_full_peaked_scores(G, S, H):
     qkv[:, 2 * W + 7] *= 40.0                                                  # outlier value column
     qkv = qkv.bfloat16()
     ctx = torch.zeros(G * S, W, device="cuda", dtype=torch.bfloat16)
-    assert lib.gitcap_dbg_attn_full(_p(qkv), _p(ctx), G, S, H, _stream()) == 0
+    assert lib.gitcap_dbg_attn_full(ptr(qkv), ptr(ctx), G, S, H, stream()) == 0
     q, k, v = (t.double().view(G, S, H, 64).transpose(1, 2) for t in qkv.split(W, dim=1))
     s = q @ k.transpose(-1, -2) * 0.125
     p = torch.exp(s - s.max(-1, keepdim=True).values)
@@ -226,7 +196,7 @@ def test_text_rows_one_layer_peaked_head(captioner_cls):
     """txt_block / ffn_txt / ln_reduce through gitcap_text_forward on a ONE-layer decoder whose head 0 is peaked harder than the
     stress default (q, k x 4: scores x 16 -- winner-take-all rows): the text rows of that layer against the emulating oracle on the
     device's own layer input, at T = 1 ... 20 and with 1, 2 and 5 rows (row-prologue and row-kernel forms)."""
-    cfg = _mid768(dec_layers=1)
+    cfg = mid768(dec_layers=1)
     w = stress_weights(cfg, 0, qk_gain=4.0)
     emul = GitOracle(cfg, w, emulate_bf16=True)
     S_img = 3 * cfg.tokens_per_frame

@@ -11,8 +11,8 @@ import sys
 import pytest
 import torch
 
-from gitcap.student_config import student_base, student_synthetic_weights, student_tiny
-from gitcap.tinyvit_config import tinyvit_synthetic_weights, tinyvit_tiny
+from gitcap.student_config import student_synthetic_weights, student_tiny
+from gpu_support import make_student, make_student_native, ptr, student_cfg
 from oracle.student_oracle import StudentOracle, make_memory
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,37 +21,13 @@ STOP_NEVER, STOP_ALL_SEP = 0, 1
 MAX_B, MAX_T = 5, 25
 
 
-def _scfg(name):
-    return student_tiny() if name == "tiny" else student_base()
-
-
-def _student(name, seed=0, **kw):
-    from gitcap.student import StudentCaptioner
-    cfg = _scfg(name)
-    return StudentCaptioner(cfg=cfg, weights=student_synthetic_weights(cfg, seed), device="cuda:0", **kw)
-
-
-def _student_native(name, **kw):
-    from gitcap.student import StudentCaptioner
-    from gitcap.tinyvit import TinyViTEncoder
-    tcfg, scfg = tinyvit_tiny(), _scfg(name)
-    weights = dict(student_synthetic_weights(scfg, 0))
-    weights.update({"image_encoder.model." + k: v for k, v in tinyvit_synthetic_weights(tcfg, 0).items()})
-    enc = TinyViTEncoder(tcfg, device="cuda:0", max_frames=kw.get("max_batch", 4) * scfg.mem_tokens)
-    return StudentCaptioner(cfg=scfg, weights=weights, image_encoder=enc, device="cuda:0", **kw)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 _MODELS, _REFS = {}, {}
 
 
 def _model(name):
     """One model per size for the whole module (max_batch 5, max_text_len 25)."""
     if name not in _MODELS:
-        _MODELS[name] = _student(name, max_batch=MAX_B, max_text_len=MAX_T)
+        _MODELS[name] = make_student(name, max_batch=MAX_B, max_text_len=MAX_T)
     return _MODELS[name]
 
 
@@ -59,7 +35,7 @@ def _ref(name, B, max_len):
     """(memory on the device, plain greedy ids under stop='never', the same for another memory): computed once per case."""
     key = (name, B, max_len)
     if key not in _REFS:
-        m, cfg = _model(name), _scfg(name)
+        m, cfg = _model(name), student_cfg(name)
         mem = make_memory(B, cfg.mem_tokens, cfg.d_model, 40 + B).cuda()
         other = make_memory(B, cfg.mem_tokens, cfg.d_model, 90 + B).cuda()
         _REFS[key] = (mem, m.greedy_decode(mem, max_len=max_len, stop="never").clone(),
@@ -112,7 +88,7 @@ CASES = [(name, B, L) for name in ("tiny", "base") for B in (1, 2, 3, 5) for L i
 @pytest.mark.parametrize("name,B,max_len", CASES)
 def test_gpu_draft_never_changes_the_result(name, B, max_len, stop):
     """B = 1, 2: the token steps take the one/two-row prologue of skinny.hip and the verify pass (n_draft >= 3) does not."""
-    m, cfg = _model(name), _scfg(name)
+    m, cfg = _model(name), student_cfg(name)
     mem, ref, other_ids = _ref(name, B, max_len)
     want = m.greedy_decode(mem, max_len=max_len, stop=stop).clone()
     if stop == "never":
@@ -128,7 +104,7 @@ def test_gpu_draft_never_changes_the_result(name, B, max_len, stop):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,B,max_len", CASES)
 def test_gpu_draft_accepts_the_common_prefix(name, B, max_len):
-    m, cfg = _model(name), _scfg(name)
+    m, cfg = _model(name), student_cfg(name)
     mem, ref, other_ids = _ref(name, B, max_len)
     seen = {}
     for label, d in _drafts(cfg, ref, other_ids, max_len):
@@ -198,7 +174,7 @@ class _Abi:
 
     def greedy(self, mem, max_len, stop):
         ids, steps = self._out(mem.shape[0], max_len)
-        rc = self.lib.gitcap_student_greedy(self.h, _p(mem), mem.shape[0], max_len, stop, _p(ids), _p(steps), self.m._stream())
+        rc = self.lib.gitcap_student_greedy(self.h, ptr(mem), mem.shape[0], max_len, stop, ptr(ids), ptr(steps), self.m._stream())
         assert rc == 0, self.err()
         return ids, steps
 
@@ -206,21 +182,21 @@ class _Abi:
         B = mem.shape[0] if B is None else B
         ids, steps = self._out(max(B, 1), max_len)
         acc = ctypes.c_int32(-7)
-        rc = self.lib.gitcap_student_greedy_draft(self.h, _p(mem), B, _p(d), d.shape[1] if ld is None else ld,
-                                                  d.shape[1] - 1 if n is None else n, max_len, stop, _p(ids), _p(steps),
+        rc = self.lib.gitcap_student_greedy_draft(self.h, ptr(mem), B, ptr(d), d.shape[1] if ld is None else ld,
+                                                  d.shape[1] - 1 if n is None else n, max_len, stop, ptr(ids), ptr(steps),
                                                   ctypes.byref(acc), self.m._stream())
         return rc, ids, steps, acc.value
 
     def window_greedy(self, B, max_len, stop):
         ids, steps = self._out(B, max_len)
-        rc = self.lib.gitcap_student_window_greedy(self.h, max_len, stop, _p(ids), _p(steps), self.m._stream())
+        rc = self.lib.gitcap_student_window_greedy(self.h, max_len, stop, ptr(ids), ptr(steps), self.m._stream())
         return rc, ids, steps
 
     def window_draft(self, B, d, max_len, stop, ld=None, n=None):
         ids, steps = self._out(B, max_len)
         acc = ctypes.c_int32(-7)
-        rc = self.lib.gitcap_student_window_greedy_draft(self.h, _p(d), d.shape[1] if ld is None else ld,
-                                                         d.shape[1] - 1 if n is None else n, max_len, stop, _p(ids), _p(steps),
+        rc = self.lib.gitcap_student_window_greedy_draft(self.h, ptr(d), d.shape[1] if ld is None else ld,
+                                                         d.shape[1] - 1 if n is None else n, max_len, stop, ptr(ids), ptr(steps),
                                                          ctypes.byref(acc), self.m._stream())
         return rc, ids, steps, acc.value
 
@@ -228,8 +204,8 @@ class _Abi:
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["tiny", "base"])
 def test_gpu_draft_c_abi_equals_the_plain_calls(name):
-    cfg, B, max_len = _scfg(name), 2, 10
-    m = _student(name, max_batch=4, max_text_len=12)
+    cfg, B, max_len = student_cfg(name), 2, 10
+    m = make_student(name, max_batch=4, max_text_len=12)
     a = _Abi(m)
     F = cfg.mem_tokens
     toks = make_memory(B, F + 2, cfg.d_model, 23).cuda()
@@ -247,8 +223,8 @@ def test_gpu_draft_c_abi_equals_the_plain_calls(name):
     wide = torch.full((B, max_len + 4), 5, dtype=torch.int64, device="cuda:0")
     wide[:, :max_len + 1] = ids0
     ids3, steps3 = a._out(B, max_len)
-    assert a.lib.gitcap_student_greedy_draft(a.h, _p(mem), B, _p(wide), max_len + 4, max_len, max_len, STOP_ALL_SEP, _p(ids3),
-                                             _p(steps3), None, m._stream()) == 0, a.err()
+    assert a.lib.gitcap_student_greedy_draft(a.h, ptr(mem), B, ptr(wide), max_len + 4, max_len, max_len, STOP_ALL_SEP, ptr(ids3),
+                                             ptr(steps3), None, m._stream()) == 0, a.err()
     want_ids, want_steps = a.greedy(mem, max_len, STOP_ALL_SEP)
     n = int(want_steps.item())
     assert torch.equal(steps3, want_steps) and torch.equal(ids3[:, :1 + n], want_ids[:, :1 + n])
@@ -259,7 +235,7 @@ def test_gpu_draft_c_abi_equals_the_plain_calls(name):
 
     def decoder_only():
         logits = torch.empty((B, T, cfg.vocab_length), dtype=torch.float32, device="cuda:0")
-        assert a.lib.gitcap_student_forward_decoder(a.h, _p(y), T, B, T, _p(logits), m._stream()) == 0, a.err()
+        assert a.lib.gitcap_student_forward_decoder(a.h, ptr(y), T, B, T, ptr(logits), m._stream()) == 0, a.err()
         return logits
 
     a.greedy(mem, max_len, STOP_NEVER)
@@ -272,7 +248,7 @@ def test_gpu_draft_c_abi_equals_the_plain_calls(name):
     assert rc == ERR_STATE and a.err()                                          # before mem_tokens pushes
     for lo, hi in ((0, F), (F, F + 1), (F + 1, F + 2)):
         chunk = toks[:, lo:hi].contiguous()
-        assert a.lib.gitcap_student_window_push(a.h, _p(chunk), B, hi - lo, m._stream()) == 0, a.err()
+        assert a.lib.gitcap_student_window_push(a.h, ptr(chunk), B, hi - lo, m._stream()) == 0, a.err()
         for stop in (STOP_NEVER, STOP_ALL_SEP):
             rc, want_ids, want_steps = a.window_greedy(B, max_len, stop)
             assert rc == 0, a.err()
@@ -293,7 +269,7 @@ def test_gpu_draft_c_abi_equals_the_plain_calls(name):
 @pytest.mark.gpu
 def test_gpu_draft_c_abi_errors():
     cfg, max_len = student_tiny(), 6
-    m = _student("tiny", max_batch=2, max_text_len=8)
+    m = make_student("tiny", max_batch=2, max_text_len=8)
     a = _Abi(m)
     F = cfg.mem_tokens
     mem = make_memory(2, F, cfg.d_model, 5).cuda()
@@ -306,11 +282,11 @@ def test_gpu_draft_c_abi_errors():
         assert a.err()
 
     lib, h = a.lib, a.h
-    assert lib.gitcap_student_greedy_draft(None, _p(mem), 2, _p(d), 7, 6, max_len, 0, _p(ids), _p(steps), None, s) == ERR_ARG
+    assert lib.gitcap_student_greedy_draft(None, ptr(mem), 2, ptr(d), 7, 6, max_len, 0, ptr(ids), ptr(steps), None, s) == ERR_ARG
     assert lib.gitcap_student_last_error(None)                                            # a null handle: the message of the type
-    refused(lib.gitcap_student_greedy_draft(h, _p(mem), 2, None, 7, 6, max_len, 0, _p(ids), _p(steps), None, s), ERR_ARG)
-    refused(lib.gitcap_student_greedy_draft(h, _p(mem), 2, _p(d), 7, 6, max_len, 0, None, _p(steps), None, s), ERR_ARG)
-    refused(lib.gitcap_student_greedy_draft(h, None, 2, _p(d), 7, 6, max_len, 0, _p(ids), _p(steps), None, s), ERR_ARG)
+    refused(lib.gitcap_student_greedy_draft(h, ptr(mem), 2, None, 7, 6, max_len, 0, ptr(ids), ptr(steps), None, s), ERR_ARG)
+    refused(lib.gitcap_student_greedy_draft(h, ptr(mem), 2, ptr(d), 7, 6, max_len, 0, None, ptr(steps), None, s), ERR_ARG)
+    refused(lib.gitcap_student_greedy_draft(h, None, 2, ptr(d), 7, 6, max_len, 0, ptr(ids), ptr(steps), None, s), ERR_ARG)
     refused(a.greedy_draft(mem, d, max_len, STOP_NEVER, n=0)[0], ERR_ARG)
     refused(a.greedy_draft(mem, d, max_len, STOP_NEVER, n=max_len + 1, ld=max_len + 2)[0], ERR_ARG)
     refused(a.greedy_draft(mem, d, max_len, STOP_NEVER, n=6, ld=6)[0], ERR_ARG)           # ld_draft < n_draft + 1
@@ -325,16 +301,16 @@ def test_gpu_draft_c_abi_errors():
     assert lib.gitcap_student_window_reset(h, 2) == 0
     refused(a.window_draft(2, d, max_len, STOP_NEVER)[0], ERR_STATE)                      # empty window
     part = mem[:, :F - 1].contiguous()
-    assert lib.gitcap_student_window_push(h, _p(part), 2, F - 1, s) == 0
+    assert lib.gitcap_student_window_push(h, ptr(part), 2, F - 1, s) == 0
     refused(a.window_draft(2, d, max_len, STOP_NEVER)[0], ERR_STATE)                      # F - 1 tokens
-    refused(lib.gitcap_student_window_push(h, _p(part), 1, 1, s), ERR_ARG)                # B different from the reset's
+    refused(lib.gitcap_student_window_push(h, ptr(part), 1, 1, s), ERR_ARG)                # B different from the reset's
     last = mem[:, F - 1:].contiguous()
-    assert lib.gitcap_student_window_push(h, _p(last), 2, 1, s) == 0
+    assert lib.gitcap_student_window_push(h, ptr(last), 2, 1, s) == 0
     rc, got, _, acc = a.window_draft(2, d, max_len, STOP_NEVER)
     assert rc == 0 and torch.equal(got, a.greedy(mem, max_len, STOP_NEVER)[0]) and 0 <= acc <= max_len
-    assert lib.gitcap_student_window_greedy_draft(None, _p(d), 7, 6, max_len, 0, _p(ids), _p(steps), None, s) == ERR_ARG
-    refused(lib.gitcap_student_window_greedy_draft(h, None, 7, 6, max_len, 0, _p(ids), _p(steps), None, s), ERR_ARG)
-    refused(lib.gitcap_student_window_greedy_draft(h, _p(d), 7, 6, max_len, 0, None, _p(steps), None, s), ERR_ARG)
+    assert lib.gitcap_student_window_greedy_draft(None, ptr(d), 7, 6, max_len, 0, ptr(ids), ptr(steps), None, s) == ERR_ARG
+    refused(lib.gitcap_student_window_greedy_draft(h, None, 7, 6, max_len, 0, ptr(ids), ptr(steps), None, s), ERR_ARG)
+    refused(lib.gitcap_student_window_greedy_draft(h, ptr(d), 7, 6, max_len, 0, None, ptr(steps), None, s), ERR_ARG)
     refused(a.window_draft(2, d, max_len, STOP_NEVER, n=0)[0], ERR_ARG)
     refused(a.window_draft(2, d, max_len, STOP_NEVER, n=7, ld=8)[0], ERR_ARG)
     refused(a.window_draft(2, d, max_len, STOP_NEVER, n=6, ld=6)[0], ERR_ARG)
@@ -390,8 +366,8 @@ def test_gpu_draft_without_graphs_in_a_fresh_process():
 @pytest.mark.parametrize("batch", [1, 2])
 def test_gpu_caption_stream_carries_its_caption(batch):
     max_len = 12
-    ma = _student_native("tiny", max_batch=4, max_text_len=16)
-    mb = _student_native("tiny", max_batch=4, max_text_len=16)
+    ma = make_student_native("tiny", tinyvit="tiny", max_batch=4, max_text_len=16)
+    mb = make_student_native("tiny", tinyvit="tiny", max_batch=4, max_text_len=16)
     F = ma.cfg.mem_tokens
     cam = torch.randint(0, 256, (batch, 14, 64, 80, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(31 + batch))
     cam[:, 6:12] = cam[:, 6:7]                                                  # frames 6..11: one repeated frame
@@ -441,7 +417,7 @@ def test_gpu_draft_speed_switches_change_nothing(name):
     captured again per switch setting."""
     from gitcap import _lib
     lib = _lib.load()
-    m, cfg = _model(name), _scfg(name)
+    m, cfg = _model(name), student_cfg(name)
     mem, ref, other_ids = _ref(name, 1, 25)
     drafts = _drafts(cfg, ref, other_ids, 25)
     for key in (1, 10):

@@ -4,56 +4,16 @@ window (gitcap_student_window_*) and StudentCaptioner.caption_stream.
 Every comparison is torch.equal: each new path is defined as bitwise equal to a composition of existing entry points
 (gitcap_preprocess + gitcap_tinyvit_encode; gitcap_student_greedy / _beam_search on the window's tokens), and those are held to
 the oracle by test_preprocess.py, test_tinyvit_gpu.py and test_student.py."""
-import ctypes
-
 import pytest
 import torch
 
 from gitcap.student_config import student_base, student_synthetic_weights, student_tiny
-from gitcap.tinyvit_config import tinyvit_config, tinyvit_synthetic_weights, tinyvit_tiny
+from gpu_support import camera, make_encoder, make_student, make_student_native, ptr, student_cfg
 from oracle.student_oracle import make_memory
 
 ERR_ARG, ERR_STATE = -1, -2
 STOP_NEVER, STOP_ALL_SEP = 0, 1
 GROUPS = [1, 1, 2, 1, 3, 1, 6, 1, 1, 2, 1, 4]          # 24 tokens through a ring of 6: it wraps four times
-
-
-def _tcfg(name):
-    return tinyvit_tiny() if name == "tiny" else tinyvit_config("tiny_vit_21m_224")
-
-
-def _scfg(name):
-    return student_tiny() if name == "tiny" else student_base()
-
-
-def _encoder(name, max_frames=8):
-    from gitcap.tinyvit import TinyViTEncoder
-    cfg = _tcfg(name)
-    return TinyViTEncoder(cfg, tinyvit_synthetic_weights(cfg, 0), device="cuda:0", max_frames=max_frames)
-
-
-def _student(name, seed=0, **kw):
-    from gitcap.student import StudentCaptioner
-    cfg = _scfg(name)
-    return StudentCaptioner(cfg=cfg, weights=student_synthetic_weights(cfg, seed), device="cuda:0", **kw)
-
-
-def _student_native(name, **kw):
-    from gitcap.student import StudentCaptioner
-    from gitcap.tinyvit import TinyViTEncoder
-    tcfg, scfg = _tcfg(name), _scfg(name)
-    weights = dict(student_synthetic_weights(scfg, 0))
-    weights.update({"image_encoder.model." + k: v for k, v in tinyvit_synthetic_weights(tcfg, 0).items()})
-    enc = TinyViTEncoder(tcfg, device="cuda:0", max_frames=kw.get("max_batch", 4) * scfg.mem_tokens)
-    return StudentCaptioner(cfg=scfg, weights=weights, image_encoder=enc, device="cuda:0", **kw)
-
-
-def _camera(shape, seed):
-    return torch.randint(0, 256, shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 # ---------------------------------------------------------------------------------------------------- encode_raw
@@ -63,8 +23,8 @@ def _p(t):
 @pytest.mark.parametrize("name", ["tiny", "21m"])
 def test_gpu_encode_raw_equals_preprocess_then_encode(name, n, H, W):
     from gitcap.preprocess import preprocess_frames
-    enc = _encoder(name)
-    frames = _camera((n, H, W, 3), 1000 * H + W + n)
+    enc = make_encoder(name)
+    frames = camera((n, H, W, 3), 1000 * H + W + n)
     x = preprocess_frames(frames, crop=enc.cfg.img_size)
     want_maps, want_mem = enc(x), enc.memory(x[None])
     got_maps, got_mem = enc(frames), enc.memory(frames)               # CPU uint8 [n,H,W,3]: one clip
@@ -78,15 +38,15 @@ def test_gpu_encode_raw_equals_preprocess_then_encode(name, n, H, W):
 
 @pytest.mark.gpu
 def test_gpu_encode_raw_refuses_bad_arguments():
-    enc = _encoder("tiny", max_frames=2)
+    enc = make_encoder("tiny", max_frames=2)
     lib, h = enc._lib, enc._handle
-    frames = _camera((3, 80, 96, 3), 5).cuda()
+    frames = camera((3, 80, 96, 3), 5).cuda()
     mem = torch.empty((3, enc.out_dim), dtype=torch.float32, device="cuda:0")
     call = lambda fr, n, H, W, m: lib.gitcap_tinyvit_encode_raw(h, fr, n, H, W, m, None, None)
-    assert call(_p(frames), 2, 80, 96, _p(mem)) == 0
-    for args in ((None, 2, 80, 96, _p(mem)), (_p(frames), 2, 80, 96, None), (_p(frames), 0, 80, 96, _p(mem)),
-                 (_p(frames), 3, 80, 96, _p(mem)),                     # n > max_frames
-                 (_p(frames), 2, 0, 96, _p(mem)), (_p(frames), 2, 80, 0, _p(mem))):   # no resized frame reaches the crop
+    assert call(ptr(frames), 2, 80, 96, ptr(mem)) == 0
+    for args in ((None, 2, 80, 96, ptr(mem)), (ptr(frames), 2, 80, 96, None), (ptr(frames), 0, 80, 96, ptr(mem)),
+                 (ptr(frames), 3, 80, 96, ptr(mem)),                     # n > max_frames
+                 (ptr(frames), 2, 0, 96, ptr(mem)), (ptr(frames), 2, 80, 0, ptr(mem))):   # no resized frame reaches the crop
         assert call(*args) == ERR_ARG, args
         assert lib.gitcap_tinyvit_last_error(h)
     torch.cuda.synchronize()
@@ -109,13 +69,13 @@ class _Win:
 
     def push(self, mem, B=None, n=None):
         mem = mem.contiguous()
-        return self.lib.gitcap_student_window_push(self.h, _p(mem), mem.shape[0] if B is None else B,
+        return self.lib.gitcap_student_window_push(self.h, ptr(mem), mem.shape[0] if B is None else B,
                                                    mem.shape[1] if n is None else n, self.stream())
 
     def greedy(self, B, max_len, stop):
         ids = torch.full((B, max_len + 1), -1, dtype=torch.int64, device="cuda:0")
         steps = torch.full((1,), -1, dtype=torch.int32, device="cuda:0")
-        rc = self.lib.gitcap_student_window_greedy(self.h, max_len, stop, _p(ids), _p(steps), self.stream())
+        rc = self.lib.gitcap_student_window_greedy(self.h, max_len, stop, ptr(ids), ptr(steps), self.stream())
         return rc, ids, steps
 
     def full_greedy(self, mem, max_len, stop):
@@ -123,13 +83,13 @@ class _Win:
         B = mem.shape[0]
         ids = torch.full((B, max_len + 1), -1, dtype=torch.int64, device="cuda:0")
         steps = torch.full((1,), -1, dtype=torch.int32, device="cuda:0")
-        rc = self.lib.gitcap_student_greedy(self.h, _p(mem), B, max_len, stop, _p(ids), _p(steps), self.stream())
+        rc = self.lib.gitcap_student_greedy(self.h, ptr(mem), B, max_len, stop, ptr(ids), ptr(steps), self.stream())
         assert rc == 0, self.err()
         return ids, steps
 
     def beam(self, B, k, max_len):
         ids = torch.full((B, max_len), -1, dtype=torch.int64, device="cuda:0")
-        return self.lib.gitcap_student_window_beam_search(self.h, k, max_len, _p(ids), self.stream()), ids
+        return self.lib.gitcap_student_window_beam_search(self.h, k, max_len, ptr(ids), self.stream()), ids
 
     def err(self):
         return self.lib.gitcap_student_last_error(self.h)
@@ -148,7 +108,7 @@ def _sep_friendly(cfg, seed):
 @pytest.mark.parametrize("name", ["tiny", "base"])
 def test_gpu_sliding_window_equals_full_call(name, B):
     from gitcap.student import StudentCaptioner
-    cfg = _scfg(name)
+    cfg = student_cfg(name)
     F, max_len = cfg.mem_tokens, 12
     m = StudentCaptioner(cfg=cfg, weights=_sep_friendly(cfg, 0), device="cuda:0", max_batch=6, max_text_len=16)
     w = _Win(m)
@@ -192,7 +152,7 @@ def test_gpu_sliding_window_equals_full_call(name, B):
 @pytest.mark.gpu
 def test_gpu_window_isolation():
     cfg = student_base()
-    m = _student("base", max_batch=4, max_text_len=12)
+    m = make_student("base", max_batch=4, max_text_len=12)
     w = _Win(m)
     F, B, T = cfg.mem_tokens, 2, 7
     mem0 = make_memory(B, F, cfg.d_model, 3).cuda()
@@ -203,7 +163,7 @@ def test_gpu_window_isolation():
 
     def decoder_only():
         logits = torch.empty((B, T, cfg.vocab_length), dtype=torch.float32, device="cuda:0")
-        assert m._lib.gitcap_student_forward_decoder(m._handle, _p(y), T, B, T, _p(logits), m._stream()) == 0, w.err()
+        assert m._lib.gitcap_student_forward_decoder(m._handle, ptr(y), T, B, T, ptr(logits), m._stream()) == 0, w.err()
         return logits
 
     assert w.reset(B) == 0
@@ -221,7 +181,7 @@ def test_gpu_window_isolation():
     assert rc == 0, w.err()
     y2 = y.repeat_interleave(2, dim=0).contiguous()
     logits = torch.empty((2 * B, T, cfg.vocab_length), dtype=torch.float32, device="cuda:0")
-    assert m._lib.gitcap_student_forward_decoder(m._handle, _p(y2), T, 2 * B, T, _p(logits), m._stream()) == 0, w.err()
+    assert m._lib.gitcap_student_forward_decoder(m._handle, ptr(y2), T, 2 * B, T, ptr(logits), m._stream()) == 0, w.err()
     assert torch.equal(logits, m.forward_decoder(y2, window.repeat_interleave(2, dim=0)))
     # pushes on a side stream, window calls on the current one: the two events order them
     side = torch.cuda.Stream()
@@ -243,7 +203,7 @@ def test_gpu_window_errors():
     from gitcap.student import StudentCaptioner
     cfg = student_tiny()
     F = cfg.mem_tokens
-    m = _student("tiny", max_batch=4, max_text_len=8)
+    m = make_student("tiny", max_batch=4, max_text_len=8)
     w = _Win(m)
     toks = make_memory(2, F + 1, cfg.d_model, 1).cuda()
     def refused(rc, code):
@@ -293,9 +253,9 @@ def test_gpu_window_errors():
 def test_gpu_caption_stream_end_to_end(name):
     from gitcap._lib import GitcapError
     from gitcap.preprocess import preprocess_frames
-    m = _student_native(name, max_batch=4, max_text_len=25)
+    m = make_student_native(name, max_batch=4, max_text_len=25)
     F, S = m.cfg.mem_tokens, m.image_encoder.cfg.img_size
-    cam = _camera((1, 14, 480, 640, 3), 77)                                   # one clip, 14 CPU camera frames
+    cam = camera((1, 14, 480, 640, 3), 77)                                   # one clip, 14 CPU camera frames
     x = preprocess_frames(cam, crop=S)                                        # [1,14,3,S,S] on the device
     # raw frames straight into the decode calls == the transformed frames
     assert torch.equal(m.greedy_decode(cam[:, :F], max_len=25, stop="never"),
@@ -336,7 +296,7 @@ def test_gpu_caption_stream_end_to_end(name):
     with pytest.raises(ValueError):
         m.caption_stream(batch=3, beams=2)                                    # 6 rows > max_batch
     # two clips in lockstep
-    cam2 = _camera((2, F + 1, 120, 160, 3), 78)
+    cam2 = camera((2, F + 1, 120, 160, 3), 78)
     x2 = preprocess_frames(cam2, crop=S)
     s2 = m.caption_stream(batch=2, hop=1, max_len=12, stop="never")
     outs = [s2.push(cam2[:, i]) for i in range(F + 1)]
@@ -348,8 +308,8 @@ def test_gpu_caption_stream_end_to_end(name):
 @pytest.mark.gpu
 def test_gpu_caption_stream_needs_the_native_encoder():
     from gitcap._lib import GitcapError
-    m = _student("tiny", max_batch=2, max_text_len=8)
+    m = make_student("tiny", max_batch=2, max_text_len=8)
     with pytest.raises(GitcapError, match="native"):
         m.caption_stream()
     with pytest.raises(GitcapError):
-        m.greedy_decode(_camera((1, 6, 48, 64, 3), 1), max_len=4)             # raw frames without an encoder
+        m.greedy_decode(camera((1, 6, 48, 64, 3), 1), max_len=4)             # raw frames without an encoder

@@ -10,6 +10,7 @@ import torch
 from gitcap.config import git_base, git_tiny
 from gitcap.weights import quantize_weights_fp8, synthetic_weights
 from oracle.git_oracle import make_frames
+from gpu_support import captioner_cls, ptr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -18,41 +19,30 @@ STOP_NEVER, STOP_ALL_SEP = 0, 1
 PUSHES = [1, 1, 2, 1, 3, 1, 6, 1, 1, 2, 1, 4]           # 24 frames: the 6-slot ring wraps four times
 
 
-@pytest.fixture(scope="module")
-def captioner_cls():
-    from gitcap.model import GitCaptioner
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return GitCaptioner
-
-
-def P(t):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
-
-
 def _greedy(m, fr, max_len, mode=STOP_ALL_SEP):
     B, F = fr.shape[:2]
     ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=m._dev)
     steps = torch.zeros((1,), dtype=torch.int32, device=m._dev)
-    m._call("gitcap_greedy", P(fr), B, F, max_len, mode, P(ids), P(steps), m._stream())
+    m._call("gitcap_greedy", ptr(fr), B, F, max_len, mode, ptr(ids), ptr(steps), m._stream())
     return ids, steps
 
 
 def _encode(m, fr):
     B, F = fr.shape[:2]
     vis = torch.empty((B, F * m.cfg.tokens_per_frame, m.cfg.enc_width), dtype=torch.float32, device=m._dev)
-    m._call("gitcap_encode", P(fr), B, F, P(vis), m._stream())
+    m._call("gitcap_encode", ptr(fr), B, F, ptr(vis), m._stream())
     return vis
 
 
 def _push(m, fr):
-    m._call("gitcap_window_push", P(fr), fr.shape[0], fr.shape[1], m._stream())
+    m._call("gitcap_window_push", ptr(fr), fr.shape[0], fr.shape[1], m._stream())
 
 
 def _wgreedy(m, B, F, max_len, mode=STOP_ALL_SEP, want_vis=True):
     ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=m._dev)
     steps = torch.zeros((1,), dtype=torch.int32, device=m._dev)
     vis = torch.empty((B, F * m.cfg.tokens_per_frame, m.cfg.enc_width), dtype=torch.float32, device=m._dev) if want_vis else None
-    m._call("gitcap_window_greedy", max_len, mode, P(vis), P(ids), P(steps), m._stream())
+    m._call("gitcap_window_greedy", max_len, mode, ptr(vis), ptr(ids), ptr(steps), m._stream())
     return ids, steps, vis
 
 
@@ -98,18 +88,18 @@ def test_raw_frames(captioner_cls):
     raw = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (B, T, H, W, 3), dtype=np.uint8)).cuda()
     S = cfg.image_size
     pre = torch.empty((B * T, 3, S, S), dtype=torch.float32, device="cuda")
-    assert m._lib.gitcap_preprocess(P(raw), B * T, H, W, P(pre), S, m._stream()) == 0
+    assert m._lib.gitcap_preprocess(ptr(raw), B * T, H, W, ptr(pre), S, m._stream()) == 0
     pre = pre.view(B, T, 3, S, S)
     got_raw, got_pre = [], []
     m._call("gitcap_window_reset", B, 6)
     for at in range(T):
-        m._call("gitcap_window_push_raw", P(raw[:, at:at + 1].contiguous()), B, 1, H, W, m._stream())
+        m._call("gitcap_window_push_raw", ptr(raw[:, at:at + 1].contiguous()), B, 1, H, W, m._stream())
         if at + 1 >= 6:
             got_raw.append(_wgreedy(m, B, 6, 8))
             win = raw[:, at + 1 - 6:at + 1].contiguous()
             ids = torch.empty((B, 9), dtype=torch.int64, device="cuda")
             steps = torch.zeros((1,), dtype=torch.int32, device="cuda")
-            m._call("gitcap_greedy_raw", P(win), B, 6, H, W, 8, STOP_ALL_SEP, P(ids), P(steps), m._stream())
+            m._call("gitcap_greedy_raw", ptr(win), B, 6, H, W, 8, STOP_ALL_SEP, ptr(ids), ptr(steps), m._stream())
             assert torch.equal(got_raw[-1][0], ids) and torch.equal(got_raw[-1][1], steps), at
     m._call("gitcap_window_reset", B, 6)
     for at in range(0, T, 2):
@@ -133,10 +123,10 @@ def test_beam_search(captioner_cls):
         dec = torch.empty((2, 10), dtype=torch.int64, device="cuda")
         lp = torch.empty((2,), dtype=torch.float32, device="cuda")
         vis = torch.empty((2, 6 * cfg.tokens_per_frame, cfg.enc_width), dtype=torch.float32, device="cuda")
-        m._call("gitcap_window_beam_search", 4, 10, ctypes.c_float(0.6), 2, P(vis), P(dec), P(lp), m._stream())
+        m._call("gitcap_window_beam_search", 4, 10, ctypes.c_float(0.6), 2, ptr(vis), ptr(dec), ptr(lp), m._stream())
         win = pool[:, at + 1 - 6:at + 1].contiguous()
         dec2, lp2 = torch.empty_like(dec), torch.empty_like(lp)
-        m._call("gitcap_beam_search", P(win), 2, 6, 4, 10, ctypes.c_float(0.6), 2, P(dec2), P(lp2), m._stream())
+        m._call("gitcap_beam_search", ptr(win), 2, 6, 4, 10, ctypes.c_float(0.6), 2, ptr(dec2), ptr(lp2), m._stream())
         assert torch.equal(dec, dec2) and torch.equal(lp, lp2), at
         assert torch.equal(vis, _encode(m, win)), at
 
@@ -168,7 +158,7 @@ def test_isolation(captioner_cls):
     f = m.greedy_decode_async(other, max_len=8)                    # pipelined submission between pushes
     _push(m, pool[:, 6:7].contiguous())
     f.result()
-    m._call("gitcap_set_visual", P(_encode(m, other)), 2, 6 * cfg.tokens_per_frame, m._stream())
+    m._call("gitcap_set_visual", ptr(_encode(m, other)), 2, 6 * cfg.tokens_per_frame, m._stream())
     ids, steps, _ = _wgreedy(m, 2, 6, 8)
     assert torch.equal(ids, want[1][0]) and torch.equal(steps, want[1][1])
     # a push leaves the current image (slot 0's K/V, text cache) alone: text_forward continues against it
@@ -181,7 +171,7 @@ def test_isolation(captioner_cls):
             m._call("gitcap_window_reset", 2, 6)
             _push(m, pool[:, 1:7].contiguous())
         lg = torch.empty((2, 3, cfg.vocab_size), dtype=torch.float32, device="cuda")
-        m._call("gitcap_text_forward", P(tok), 3, 2, 1, 0, 3, P(lg), 1, None, 0, m._stream())
+        m._call("gitcap_text_forward", ptr(tok), 3, 2, 1, 0, 3, ptr(lg), 1, None, 0, m._stream())
         return lg
     assert torch.equal(logits_after(False), logits_after(True))
     # push on one stream, caption on another: the library orders them by an event
@@ -206,30 +196,30 @@ def test_errors_and_workspace(captioner_cls):
     fr = make_frames(2, 6, cfg.image_size, 71).cuda()
     ids = torch.empty((2, 9), dtype=torch.int64, device="cuda")
     st = m._stream()
-    assert lib.gitcap_window_push(h, P(fr), 2, 1, st) == ERR_STATE                     # no window yet
-    assert lib.gitcap_window_greedy(h, 8, 0, None, P(ids), None, st) == ERR_STATE
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 1, st) == ERR_STATE                     # no window yet
+    assert lib.gitcap_window_greedy(h, 8, 0, None, ptr(ids), None, st) == ERR_STATE
     w0 = m.workspace_bytes()
     assert lib.gitcap_window_reset(h, 3, 6) == ERR_ARG                                  # > max_batch
     assert lib.gitcap_window_reset(h, 2, 7) == ERR_ARG                                  # > max_frames / num_frames
     assert lib.gitcap_window_reset(h, 2, 6) == 0
     assert m.workspace_bytes() >= w0 + 2 * 6 * cfg.tokens_per_frame * cfg.enc_width * 4
-    assert lib.gitcap_window_push(h, P(fr), 1, 1, st) == ERR_ARG                        # B differs from the reset's
-    assert lib.gitcap_window_push(h, P(fr), 2, 0, st) == ERR_ARG
-    assert lib.gitcap_window_push(h, P(fr), 2, 7, st) == ERR_ARG
+    assert lib.gitcap_window_push(h, ptr(fr), 1, 1, st) == ERR_ARG                        # B differs from the reset's
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 0, st) == ERR_ARG
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 7, st) == ERR_ARG
     assert lib.gitcap_window_push(h, None, 2, 1, st) == ERR_ARG
     assert lib.gitcap_window_push(h, ctypes.c_void_p(fr.data_ptr() + 4), 2, 1, st) == ERR_ARG
     assert lib.gitcap_window_push_raw(h, None, 2, 1, 480, 640, st) == ERR_ARG
-    assert lib.gitcap_window_push(h, P(fr), 2, 5, st) == 0
-    assert lib.gitcap_window_greedy(h, 8, 0, None, P(ids), None, st) == ERR_STATE     # 5 < F frames
-    assert lib.gitcap_window_push(h, P(fr), 2, 1, st) == 0
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 5, st) == 0
+    assert lib.gitcap_window_greedy(h, 8, 0, None, ptr(ids), None, st) == ERR_STATE     # 5 < F frames
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 1, st) == 0
     vis = torch.empty((2, 6 * cfg.tokens_per_frame + 1, cfg.enc_width), dtype=torch.float32, device="cuda")
-    assert lib.gitcap_window_greedy(h, 8, 0, ctypes.c_void_p(vis.data_ptr() + 4), P(ids), None, st) == ERR_ARG
-    assert lib.gitcap_window_greedy(h, 8, 0, None, P(ids), None, st) == 0
+    assert lib.gitcap_window_greedy(h, 8, 0, ctypes.c_void_p(vis.data_ptr() + 4), ptr(ids), None, st) == ERR_ARG
+    assert lib.gitcap_window_greedy(h, 8, 0, None, ptr(ids), None, st) == 0
     assert lib.gitcap_window_reset(h, 2, 6) == 0                                        # empties it
-    assert lib.gitcap_window_greedy(h, 8, 0, None, P(ids), None, st) == ERR_STATE
+    assert lib.gitcap_window_greedy(h, 8, 0, None, ptr(ids), None, st) == ERR_STATE
     assert lib.gitcap_window_reset(h, 0, 0) == 0
     assert m.workspace_bytes() == w0
-    assert lib.gitcap_window_push(h, P(fr), 2, 1, st) == ERR_STATE                     # released
+    assert lib.gitcap_window_push(h, ptr(fr), 2, 1, st) == ERR_STATE                     # released
     torch.cuda.synchronize()
 
 
@@ -296,8 +286,8 @@ def test_exchange_failure_empties_the_window(captioner_cls):
         m._call("gitcap_window_reset", 10, 6)
         _push(m, frd[:, :6].contiguous())
         torch.cuda.synchronize()
-        assert lib.gitcap_window_greedy(m._handle, 8, 0, None, P(ids), None, m._stream()) == ERR_EXCHANGE
-        assert lib.gitcap_window_greedy(m._handle, 8, 0, None, P(ids), None, m._stream()) == ERR_STATE   # emptied
+        assert lib.gitcap_window_greedy(m._handle, 8, 0, None, ptr(ids), None, m._stream()) == ERR_EXCHANGE
+        assert lib.gitcap_window_greedy(m._handle, 8, 0, None, ptr(ids), None, m._stream()) == ERR_STATE   # emptied
         _push(m, frd[:, :6].contiguous())                       # (the handle now runs the unfused launches)
         got, _, _ = _wgreedy(m, 10, 6, 8, mode=STOP_NEVER, want_vis=False)
         assert torch.equal(got.cpu(), want[0])
