@@ -342,6 +342,38 @@ int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beam
  * keep whatever they held) -> out (device fp32 [n]) */
 int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream);
 
+/* Prompted decoding: per-clip text prefixes for the greedy and the beam family -- the `prefix` branch of the reference's
+ * GenerativeImageTextModel.infer (src/models/model.py:432-437, :453-455: the search starts from the given tokens instead of a lone
+ * CLS; how a GIT model is asked a question, told how a caption begins, or made to continue one).  The reference takes one prefix
+ * (`assert len(batch['prefix']) == 1`); here every clip has its own, of its own length.
+ * A ONE-SHOT attachment with the life cycle of gitcap_attach_token_logprobs / gitcap_attach_search_options / gitcap_attach_sampling
+ * and combinable with all three: it applies to the NEXT call or submission of the greedy family (gitcap_greedy, gitcap_greedy_raw,
+ * their _submit forms, gitcap_window_greedy) or of the beam family (gitcap_beam_search, its _submit / _raw_submit forms,
+ * gitcap_window_beam_search), whichever comes first, and is consumed by it whether that call succeeds or is refused; every other
+ * entry point leaves it pending; prompt_ids == NULL and lengths == NULL detach.  A pipelined submission captures the two pointers:
+ * the buffers stay valid and unchanged until the wait.  The student model takes no prompt.
+ *   prompt_ids  device int64 [B][ld], CLS at column 0 (the beam family starts every row from the handle's CLS whatever column 0 says).
+ *   lengths     device int32 [B]: valid tokens per clip, CLS included, 1 <= lengths[b] <= ld; 1 = no prompt for that clip.
+ *   min_len, max_len  the host's minimum and maximum of lengths (launches are planned without a round trip).  The kernels clamp
+ *               lengths[b] to [1, max_len], so a mismatch reads nothing outside the clip's row.
+ * Ids outside the vocabulary are the caller's error: they are written to the output as given, and the text embedding clamps them
+ * into its table (< 0 -> row 0, >= vocab_size -> the last row), as it does for every id gitcap_text_forward is handed.
+ * Greedy: ids_out[b][0 .. lengths[b] - 1] is the prompt, the columns behind it are the model's; a step that writes a position
+ * inside a row's prompt takes the prompt's token instead of the arg-max, for the output and for the next step's input alike.  A
+ * forced token is not counted by the stop rule (GITCAP_STOP_ALL_SEP looks at what the model emitted), and an attached
+ * log-probability buffer gets 0.0f at a forced position, as gitcap_score gives an ignored one (gitcap_score supplies the values of
+ * given tokens).  Positions 0 .. min_len - 1 run as ONE multi-position pass where the slot's row workspace holds B * min_len rows
+ * (always on the synchronous path): a P-token prompt shared by all rows costs one pass, not P token steps.  Because a cached token
+ * step is bit for bit the teacher-forced position, the ids do not depend on that plan, on the batch, or on the other rows' lengths.
+ * Beam: as the reference, the prompt is the start of input_ids, the beam scores start at [0, -1e9, ..] and prompt tokens add
+ * nothing to a score; max_steps counts the prompt and so does the length penalty's cur_len (:592-594); the repetition penalty sees
+ * the prompt's tokens.  A clip at cur_len < lengths[b] is forced: it is not ranked, every beam appends prompt_ids[b][cur_len],
+ * src_rows is the identity, and beam_scores, done and the hypothesis slots are untouched.  decoded_out / the n-best include the prompt.
+ * Errors: GITCAP_ERR_ARG for one null pointer, a misaligned pointer, or min_len < 1, max_len < min_len, ld < max_len; at the
+ * consuming call max_len > the call's max_len (greedy) or > max_steps - 1 (beam) gives GITCAP_ERR_ARG with nothing launched (the
+ * attachment is consumed all the same).  A handle that never attaches runs exactly the launches it ran before. */
+int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len);
+
 /* Options of the device-resident search: the reference's search operator keeps `num_keep_best` finished hypotheses per clip and
  * applies a `repetition_penalty` (GeneratorWithBeamSearchV2.search, src/models/model.py:479-678; the penalty :522-531, the n-best
  * output :653-678).  A ONE-SHOT attachment, like gitcap_attach_token_logprobs: it applies to the NEXT beam-family call or
@@ -498,7 +530,8 @@ int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const fl
  * FC1 -> GELU -> FC2 as one launch over hidden slices on/off; 8: fragment-major copies of the text-path weights at the next
  * gitcap_finalize_weights on/off; 9: 8-wave workgroups for text-attention launches of more (row, head) units than CUs on/off;
  * 10: the vocabulary head's four-tile workgroups that share the activation rows through LDS on/off; 11: three-wave workgroups
- * that share the slab reduce of the one/two-row prologue on/off.  Returns the previous value (< 0: bad key).  The switches are process-wide atomics: a call on another thread sees either value,
+ * that share the slab reduce of the one/two-row prologue on/off; 20: a prompted greedy loop (gitcap_attach_prompt) runs the
+ * positions every row's prompt covers as one multi-position pass on/off (off: as forced token steps).  Returns the previous value (< 0: bad key).  The switches are process-wide atomics: a call on another thread sees either value,
  * and either value gives the same bits. */
 int gitcap_dbg_config(int key, int value);
 /* attn_full: qkv [G*S][3*H*64] bf16 -> ctx [G*S][H*64] bf16 */
@@ -559,6 +592,14 @@ int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int 
 int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                                int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
                                const float* amax_sum, float* lp_out, int ld_lp, void* stream);
+/* argmax_final_forced: the launch of a prompted greedy step that writes position p = step + 1 (gitcap_attach_prompt): prompt_ids
+ * int64 [rows][ld_prompt], lengths int32 [rows] (clamped to [1, max_len]; max_len <= ld_prompt).  A row with p < lengths[r] gets
+ * out = prompt_ids[r][p] -- also the token of its emb row --, adds nothing to sep_cnt and gets lp_out 0.0f; every other row is
+ * gitcap_dbg_argmax_final(_lp)'s, bit for bit.  amax_sum / lp_out: both or neither.  p >= max_len runs the launch without a prompt. */
+int gitcap_dbg_argmax_final_forced(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                   int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                                   const float* amax_sum, float* lp_out, int ld_lp, const int64_t* prompt_ids, int ld_prompt,
+                                   const int32_t* lengths, int max_len, void* stream);
 /* draft_accept (the accept step of gitcap_student_greedy_draft): partials [B * n][ntiles] (row r * n + j = position j of caption
  * r, n <= 63), ids int64 [B][ld] with the draft staged in columns 1..n (-1 = no word), ld >= n + 1.  a = the leading positions
  * at which every row's token equals its draft token; covered = min(a + 1, n); ids columns 1..covered and sep_cnt[0..covered - 1]
@@ -611,6 +652,14 @@ int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* bb, int B,
 /* gitcap_dbg_beam_step_nbest for UNSORTED candidates (gitcap_attach_sampling: candidates), any n in [1, 16]. */
 int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* bb, const float* cand_scores, const int32_t* cand_idx, int B,
                                  int beams, int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream);
+/* The bookkeeping step of a prompted search (gitcap_attach_prompt): prompt_ids int64 [B][ld_prompt], lengths int32 [B] (clamped to
+ * [1, prompt_max_len]; prompt_max_len <= ld_prompt, < max_len).  A clip with cur_len < lengths[b] is forced: ids[cur ^ 1] of each of
+ * its beams = its own prefix + prompt_ids[b][cur_len], words = that token, src_rows = the identity; beam_scores, done, hyp_* and the
+ * candidates of the clip are neither written nor read.  Every other clip is the plain step's, bit for bit: sampled = 0 and n = 1
+ * gitcap_dbg_beam_step's kernel, n > 1 gitcap_dbg_beam_step_nbest's, sampled != 0 gitcap_dbg_beam_step_sampled's. */
+int gitcap_dbg_beam_step_forced(const gitcap_dbg_beam_buffers_nbest* bb, const float* cand_scores, const int32_t* cand_idx, int B,
+                                int beams, int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, int sampled,
+                                const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int prompt_max_len, void* stream);
 
 /* The text-row kernels of the token loop, one launcher per hook on caller-owned device buffers (tests/test_text_rows_gpu.py; a
  * plain fp64 statement of each: tests/text_rows_reference.py).  No allocation, no handle; GITCAP_ERR_ARG for arguments a launcher

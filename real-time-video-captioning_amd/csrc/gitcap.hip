@@ -164,6 +164,8 @@ struct gitcap : HandleCore {
     int lp_ld = 0;
     // gitcap_attach_search_options: the pending one-shot attachment; taken by the next beam-family call (n = 1, rp = 1: none)
     SearchOpt so_attach{};
+    // gitcap_attach_prompt: the pending one-shot attachment (ids == nullptr: none); taken by the next greedy- or beam-family call
+    PromptArgs pr_attach{};
 
     // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
     // last win.slots frames of win_B clips, clip-major [B][F][N][Dv]; win (RingCursor) = where the next frame goes and how many
@@ -508,6 +510,9 @@ std::atomic<bool> g_chain_steps{!env_flag("GITCAP_NO_STEP_CHAIN")};       // git
 // the kernels read the row-major originals; same bits, slower; the FFN then runs as two launches)
 std::atomic<bool> g_wpack{!env_flag("GITCAP_NO_WPACK")};
 std::atomic<bool> g_ffn_fuse{!env_flag("GITCAP_NO_FFN_FUSE")};            // gitcap_dbg_config(7, .): ffn_txt.hip vs FC1 + split-K FC2 launches
+// a prompted greedy loop runs the positions every row's prompt covers as ONE multi-position pass (gitcap_dbg_config(20, 0): as
+// forced token steps, the plan of a ragged batch whose shortest prompt is the lone CLS; same ids either way)
+std::atomic<bool> g_prompt_prefill{true};
 
 bool text_chain_ok(gitcap* h, int rows, int T) {
     return g_chain_steps && T == 1 && !(h->want_hidden && h->cur_slot == 0 && !h->pipelined) &&
@@ -516,7 +521,8 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 
 int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams, int t0, int T, float* logits_out,
                  int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
-                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0, const ScoreReq* score = nullptr) {
+                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0, const ScoreReq* score = nullptr,
+                 const PromptArgs* prompt = nullptr) {
     const gitcap_config& c = h->c;
     gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -629,9 +635,10 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
     }
     if (argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
+        // prompt (greedy loop): the token goes to position t0 + T, where a row's prompt may still stand
         HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, hr.am_stride, hr.am_off, argmax_out, ld_argmax,
                                       sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr, lp_out ? sl.amax_sum : nullptr,
-                                      lp_out, ld_lp));
+                                      lp_out, ld_lp, prompt, t0 + T));
     }
     return 0;
 }
@@ -1142,18 +1149,20 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
                         (hipStream_t)stream);
 }
 
-// token steps 0 .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
+// token steps t_first .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
 // lp (nullable, row pitch ld_lp): column t = the log-probability of the token step t emitted
-static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, float* lp = nullptr, int ld_lp = 0) {
+// prompt (nullable): steps that write a position inside a row's prompt take the prompt's token there (launch_argmax_final)
+static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, float* lp = nullptr, int ld_lp = 0,
+                       const PromptArgs* prompt = nullptr, int t_first = 0) {
     const bool chain = text_chain_ok(h, rows, 1);
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
     // bits -- and measured nothing: 4.926 vs 4.912 ms per 20-token caption; tools/experiments/argmax_fold_rows.txt.)
     bool have_rows = false;                                  // the previous step's arg-max launch embedded this step's input rows
-    for (int t = 0; t < max_len; ++t) {
+    for (int t = t_first; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
         const bool next = chain && t + 1 < max_len && t + 1 < h->c.max_text_pos;
         const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next,
-                                    lp ? lp + t : nullptr, ld_lp);
+                                    lp ? lp + t : nullptr, ld_lp, nullptr, prompt);
         if (rc) return rc;
         have_rows = next;
     }
@@ -1165,51 +1174,78 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
 // per token step against 302 for one loop (profiles/r04_sync_call_split_token_loop.txt).  Chains of ~6 us launches on
 // different streams do not overlap each other the way one chain overlaps an image pass.  Removed.)
 static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
-                            LpAttach lp = LpAttach{nullptr, 0}) {
+                            LpAttach lp = LpAttach{nullptr, 0}, PromptArgs pr = PromptArgs{}) {
     const int ld = max_len + 1;
     gitcap::Slot& sl = cur(h);
     int rc;
-    // CLS start tokens [B,1] (model.py:171)
-    HIP_OK(h, launch_fill_i64(ids_out, ld, B, h->c.cls_token_id, s));
     HIP_OK(h, hipMemsetAsync(sl.sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
-    if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld))) return rc;
+    if (!pr.ids) {
+        // CLS start tokens [B,1] (model.py:171)
+        HIP_OK(h, launch_fill_i64(ids_out, ld, B, h->c.cls_token_id, s));
+        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld))) return rc;
+    } else {
+        // the prompts [B, lengths[b]] in place of the lone CLS (model.py:432-437)
+        HIP_OK(h, launch_fill_prompt(ids_out, ld, B, pr, s));
+        // positions 0 .. min_len-1 are prompt in every row: one multi-position pass (its arg-max is step min_len-1's), where the
+        // slot's row workspace holds B x min_len rows; the token loop goes on behind it.  Steps that write a position below the
+        // longest prompt run the forced arg-max.
+        const int P = (g_prompt_prefill && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
+        int t_first = 0;
+        if (P > 1) {
+            if (lp.p) HIP_OK(h, hipMemset2DAsync(lp.p, (size_t)lp.ld * 4, 0, (size_t)(P - 1) * 4, B, s));    // forced positions: 0.0f
+            if ((rc = text_forward(h, ids_out, ld, B, 1, 0, P, nullptr, 0, ids_out + P, ld, sl.sep_cnt, P - 1, s, false, false,
+                                   lp.p ? lp.p + (P - 1) : nullptr, lp.ld, nullptr, &pr))) return rc;
+            t_first = P;
+        }
+        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld, &pr, t_first))) return rc;
+    }
     if (steps_out) HIP_OK(h, launch_finish_steps(sl.sep_cnt, B, max_len, stop, steps_out, s));
     return 0;
 }
 
 }  // extern "C"
 
+// gitcap_attach_prompt's pending attachment: taken, and with that consumed, by every greedy- and beam-family entry point
+static PromptArgs take_prompt(gitcap* h) {
+    const PromptArgs pr = h->pr_attach;
+    h->pr_attach = PromptArgs{};
+    return pr;
+}
+
 // The head of every greedy-family entry point: the null check (its message names the entry point), the pending log-probability
-// attachment is taken (a call refused below has consumed it), device, exchange health, the argument checks; then body(lp).
+// and prompt attachments are taken (a call refused below has consumed them), device, exchange health, the argument checks; then
+// body(lp, pr).
 template <typename Body>
 static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_len, int stop, const int64_t* ids_out, Body body) {
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
     const LpAttach lp = take_lp(h);
+    const PromptArgs pr = take_prompt(h);
     GUARD(h);
     POLL(h);
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
     if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "greedy: max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
+    if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
     const int rc = lp_check(h, "greedy", lp, max_len);
-    return rc ? rc : body(lp);
+    return rc ? rc : body(lp, pr);
 }
 
 // synchronous: image pass and token loop on the caller's stream, slot 0 (a raw source is checked by the image pass alone)
 static int greedy_sync(gitcap* h, const char* null_msg, FrameSrc src, int B, int F, int max_len, int stop, int64_t* ids_out,
                        int32_t* steps_out, hipStream_t s) {
-    return greedy_entry(h, true, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+    return greedy_entry(h, true, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
         if (int rc = encode_sync(h, src, B, F, nullptr, s)) return rc;
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, pr);
     });
 }
 
 // submitted: lp's buffer stays valid until the wait, like ids_out; raw: camera frames, checked before the submission takes a slot
 static int greedy_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, int max_len, int stop, int64_t* ids_out,
                          int32_t* steps_out, hipStream_t stream, int* ticket) {
-    return greedy_entry(h, ticket != nullptr, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+    return greedy_entry(h, ticket != nullptr, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
         if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
         return submit_common(h, src, B, F, nullptr, stream, ticket, [&](hipStream_t s) {
-            return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+            return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, pr);
         });
     });
 }
@@ -1263,7 +1299,10 @@ int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
 // (the saved step logits stay raw, model.py:521 comes before :522); n > 1: the bookkeeping keeps n hypotheses in the slot's nb_* state.
 // decoded_out / logprobs_out receive rank 0, the attached outputs all n ranks.
 static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_penalty, int per_node_beam_size,
-                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, const SearchOpt& so, hipStream_t s) {
+                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, const SearchOpt& so, const PromptArgs& pr,
+                     hipStream_t s) {
+    const PromptArgs* prompt = pr.ids ? &pr : nullptr;
+    const int forced_all = prompt ? pr.min_len : 1;          // steps cur_len < forced_all rank nothing: every clip is inside its prompt
     const int rows = B * beams, K = beams * per_node_beam_size, V = h->c.vocab_size, L = max_steps;
     gitcap::Slot& sl = cur(h);
     int rc;
@@ -1274,15 +1313,19 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
     // position cur_len are ranked, bookkept and the text K/V rows follow their beams -- no host round trip
     for (int cur_len = 1, cur = 0; cur_len < L; ++cur_len, cur ^= 1) {
         const int t = cur_len - 1;
-        if (t > 0) {                                                         // rows continue beam src_rows[r]: all layers, one launch
+        const bool ranked = cur_len >= forced_all;
+        if (t >= forced_all) {                                               // rows continue beam src_rows[r]: all layers, one launch
+                                                                             // (t > 0; behind an all-forced step src_rows is the identity)
             HIP_OK(h, launch_gather_txt_rows(sl.kv_txt, sl.kv_txt2, sl.beam.src_rows, rows, t, h->Tmax, 3 * h->D, h->c.dec_layers,
                                              (size_t)h->R * h->Tmax * 3 * h->D, s));
             std::swap(sl.kv_txt, sl.kv_txt2);
         }
-        float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : sl.beam_logits;
+        // (an all-forced step needs the K/V append only: no vocabulary head unless the caller keeps the step logits)
+        float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : (ranked ? sl.beam_logits : nullptr);
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
-        if (so.smp.on)                                                       // model.py:532-554: K draws instead of the K best
+        if (!ranked) {
+        } else if (so.smp.on)                                                       // model.py:532-554: K draws instead of the K best
             HIP_OK(h, launch_sample_rows(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V,
                                          per_node_beam_size, so.smp.temperature, so.smp.top_k, so.smp.top_p, so.smp.seed, sl.cand_scores,
                                          sl.cand_idx, nullptr, nullptr, s));
@@ -1290,7 +1333,7 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
             HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
                                        sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
         HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s,
-                                   so.smp.on));
+                                   so.smp.on, prompt));
     }
     HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
     return 0;
@@ -1301,19 +1344,21 @@ int gitcap_beam_search_wait(gitcap_t* h, int ticket, void* stream) { return gitc
 }  // extern "C"
 
 // The head of every beam-search entry point (as greedy_entry): the pending search options are taken (a call refused below has
-// consumed them); then `body(so)`.
+// consumed them), and so is the pending prompt; then `body(so, pr)`.
 template <typename Body>
 static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, int max_steps, int per_node_beam_size,
                       const int64_t* decoded_out, const float* logprobs_out, Body body) {
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
     const SearchOpt so = h->so_attach;
     h->so_attach = SearchOpt{};
+    const PromptArgs pr = take_prompt(h);
     GUARD(h);
     POLL(h);
     if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
     if (beams > h->c.max_beams || beams > 16 || beams * per_node_beam_size > 16)
         return fail(h, GITCAP_ERR_ARG, "beam_search: beams exceed max_beams / 16 candidates");
     if (max_steps < 2 || max_steps > h->Tmax) return fail(h, GITCAP_ERR_ARG, "beam_search: max_steps outside [2, max_text_len]");
+    if (pr.ids && pr.max_len > max_steps - 1) return fail(h, GITCAP_ERR_ARG, "beam_search: the attached prompt is longer than max_steps - 1");
     // with fewer than 2 candidates per beam one EOS candidate leaves a sentence short of `beams` live beams, which the
     // reference asserts against (model.py:606); the device bookkeeping has no way to report it, so refuse up front
     if (per_node_beam_size < 2) return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size must be >= 2 (model.py:606)");
@@ -1324,17 +1369,17 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
                       (so.smp.top_k > 0 && std::max(so.smp.top_k, 2) < per_node_beam_size) || per_node_beam_size > h->c.vocab_size))
         return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep");
     if (so.smp.on && h->c.vocab_size > 32768) return fail(h, GITCAP_ERR_ARG, "beam_search: sampling takes a vocabulary of at most 32768 columns");
-    return body(so);
+    return body(so, pr);
 }
 
 extern "C" {
 
 int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams, int max_steps, float length_penalty,
                        int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
+    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s)) return rc;
-        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, s);
+        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, pr, s);
     });
 }
 
@@ -1342,10 +1387,10 @@ int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams
 static int beam_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, float* visual_out, int beams, int max_steps,
                        float length_penalty, int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, float* step_logits_out,
                        hipStream_t stream, int* ticket) {
-    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
+    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
         if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
         return submit_common(h, src, B, F, visual_out, stream, ticket, [&](hipStream_t s) {
-            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, so, s);
+            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, so, pr, s);
         });
     });
 }
@@ -1453,19 +1498,19 @@ static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
 }
 
 int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    return greedy_entry(h, true, "window_greedy: null handle", max_len, stop, ids_out, [&](const LpAttach& lp) -> int {
+    return greedy_entry(h, true, "window_greedy: null handle", max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = window_prefix(h, visual_out, s)) return rc;
-        return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp);
+        return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp, pr);
     });
 }
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so) -> int {
+    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = window_prefix(h, visual_out, s)) return rc;
-        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, s);
+        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, pr, s);
     });
 }
 
@@ -1511,6 +1556,17 @@ int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream)
     if (!h->slots[0].score_buf || n > h->slots[0].Mt) return fail(h, GITCAP_ERR_STATE, "dbg_score_target_logits: no gitcap_score call yet, or n beyond the workspace");
     GUARD(h);
     HIP_OK(h, hipMemcpyAsync(out, h->slots[0].score_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_prompt: null handle");
+    h->pr_attach = PromptArgs{};
+    if (!prompt_ids && !lengths) return 0;                   // detach
+    if (!prompt_ids || !lengths) return fail(h, GITCAP_ERR_ARG, "attach_prompt: prompt_ids and lengths are both required");
+    if (((uintptr_t)prompt_ids & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_prompt: a misaligned pointer");
+    if (min_len < 1 || max_len < min_len || ld < max_len) return fail(h, GITCAP_ERR_ARG, "attach_prompt: need 1 <= min_len <= max_len <= ld");
+    h->pr_attach = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
     return 0;
 }
 
@@ -1710,7 +1766,7 @@ int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const fl
 // 7: text rows' FC1 -> GELU -> FC2 as one launch over hidden slices (ffn_txt.hip) on/off,
 // 8: gitcap_finalize_weights makes fragment-major copies of the text-path weights on/off (takes effect at the next finalize),
 // 9: text attention launches of more units than CUs use 8-wave workgroups (two units per CU) on/off,
-// 10 / 11: see include/gitcap.h.
+// 10 / 11 / 20: see include/gitcap.h.
 // Returns the old value.
 int gitcap_dbg_config(int key, int value) {
     int old = -1;
@@ -1727,6 +1783,7 @@ int gitcap_dbg_config(int key, int value) {
         case 9: old = g_txt8.exchange(value != 0); break;
         case 10: old = g_head_share.exchange(value != 0); break;
         case 11: old = g_rows3.exchange(value != 0); break;
+        case 20: old = g_prompt_prefill.exchange(value != 0); break;     // (12 .. 19 stay unknown keys)
         default: return GITCAP_ERR_ARG;
     }
     return old;
@@ -1791,7 +1848,7 @@ int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const
 
 static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                             int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                            const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
+                            const float* amax_sum, float* lp_out, int ld_lp, void* stream, const PromptArgs* prompt = nullptr) {
     if (!amax_val || !amax_idx || !out || ntiles <= 0 || rows <= 0 || row_stride <= 0 || row_off < 0 || ld_out <= 0 || step < 0)
         return GITCAP_ERR_ARG;
     NextEmbed ne{};
@@ -1800,7 +1857,7 @@ static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int 
         ne = NextEmbed{emb->word, emb->pos, emb->gamma, emb->beta, emb->eps, emb->D, emb->vocab, emb->position, emb->xf, (bf16_t*)emb->xb};
     }
     return dbg_rc(launch_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id,
-                                      (hipStream_t)stream, emb ? &ne : nullptr, amax_sum, lp_out, ld_lp));
+                                      (hipStream_t)stream, emb ? &ne : nullptr, amax_sum, lp_out, ld_lp, prompt, step + 1));
 }
 int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                             int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
@@ -1812,6 +1869,18 @@ int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, i
                                const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
     if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
     return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, amax_sum, lp_out, ld_lp, stream);
+}
+
+// the forced form (gitcap_attach_prompt): the launch writes position step + 1; amax_sum / lp_out both or neither
+int gitcap_dbg_argmax_final_forced(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                   int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                                   const float* amax_sum, float* lp_out, int ld_lp, const int64_t* prompt_ids, int ld_prompt,
+                                   const int32_t* lengths, int max_len, void* stream) {
+    if (!prompt_ids || !lengths || max_len < 1 || ld_prompt < max_len || (amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1))
+        return GITCAP_ERR_ARG;
+    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, max_len};
+    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, amax_sum, lp_out, ld_lp,
+                            stream, &pr);
 }
 
 // the two words the kernel publishes go through a page-locked int32[2] this hook owns (made once, kept for the process)
@@ -1906,6 +1975,21 @@ int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* b, const f
         return GITCAP_ERR_ARG;
     return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
                                    (hipStream_t)stream, true));
+}
+
+// the forced forms (gitcap_attach_prompt): sampled = 0 and n = 1 runs beam_step_kernel, n > 1 the n-slot kernel, sampled != 0 its form
+// for draws; prompt_ids [B][ld_prompt], lengths [B], prompt_max_len < max_len
+int gitcap_dbg_beam_step_forced(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                                int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, int sampled,
+                                const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int prompt_max_len, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
+        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1) || !prompt_ids || !lengths ||
+        prompt_max_len < 1 || prompt_max_len >= max_len || ld_prompt < prompt_max_len)
+        return GITCAP_ERR_ARG;
+    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, prompt_max_len};
+    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
+                                   (hipStream_t)stream, sampled != 0, &pr));
 }
 
 int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,

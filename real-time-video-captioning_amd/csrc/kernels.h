@@ -181,9 +181,16 @@ hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
 // emb->position -- word + position embedding -> LayerNorm -> xf / xb row r (rowln.h: the code of launch_embed_text) -- so
 // the next token step starts at its q|k|v projection.
 struct NextEmbed { const float *word, *pos, *gamma, *beta; float eps; int D, vocab, position; float* xf; bf16_t* xb; };
+// A batch of prompts (gitcap_attach_prompt): ids device int64 [rows][ld], lengths device int32 [rows] = valid tokens per row (the
+// kernels clamp them to [1, max_len]; max_len <= ld, so a wrong length reads no other row), min_len / max_len = the host's bounds.
+struct PromptArgs { const int64_t* ids; int ld; const int32_t* lengths; int min_len, max_len; };
+// prompt (nullable) + prompt_pos = the position the launch writes: a row with prompt_pos < lengths[r] takes ids[r][prompt_pos]
+// instead of its arg-max (out, the embedded next row), leaves sep_cnt alone and gets lp 0.0f; with prompt_pos >= max_len the launch
+// is the one without a prompt.
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride,
                                int row_off, int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s,
-                               const NextEmbed* emb = nullptr, const float* amax_sum = nullptr, float* lp_out = nullptr, int ld_lp = 0);
+                               const NextEmbed* emb = nullptr, const float* amax_sum = nullptr, float* lp_out = nullptr, int ld_lp = 0,
+                               const PromptArgs* prompt = nullptr, int prompt_pos = 0);
 // amax_sum + lp_out (both or neither; SkinnyArgs::amax_sum of the same head launch): lp_out[r*ld_lp] = log_softmax(logits)[token]
 // of row r, natural log, -inf for a row with no logit above -inf.  Fixed summation order: bitwise independent of `rows`.
 // Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
@@ -291,6 +298,8 @@ hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, in
                              float eps, int D, int vocab, float* x_f32, bf16_t* x_bf16, hipStream_t s);
 hipError_t launch_finish_steps(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out, hipStream_t s);
 hipError_t launch_fill_i64(int64_t* p, int ld, int rows, int64_t v, hipStream_t s);
+// p[r][0 .. lengths[r] - 1] = prompt.ids[r][the same], r < rows (ld >= prompt.max_len): the start of a prompted greedy loop
+hipError_t launch_fill_prompt(int64_t* p, int ld, int rows, const PromptArgs& prompt, hipStream_t s);
 hipError_t launch_gather_txt_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_rows, int rows,
                                   int t_len, int Tmax, int width, int layers, size_t layer_stride, hipStream_t s);
 // top-K over (beam, vocab) of log_softmax(logits) + beam_scores per batch element: sorted descending, ties by smaller flat index
@@ -322,7 +331,11 @@ hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int 
 // sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates are
 // walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
 hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled = false);
+                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled = false,
+                            const PromptArgs* prompt = nullptr);
+// prompt (nullable; rows = clips): a clip with cur_len < lengths[b] is forced -- every beam keeps its prefix and appends
+// ids[b][cur_len], src_rows is the identity, beam_scores / done / the hypothesis slots are untouched, the candidates are not read;
+// with cur_len >= max_len (the prompt's) the launch is the one without a prompt.
 // the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
 // (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
 // candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (rowops.hip).

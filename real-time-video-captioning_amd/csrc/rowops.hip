@@ -388,20 +388,32 @@ __device__ __forceinline__ float lp_partials(const float* __restrict__ val, cons
     return -__logf(((ss[0] + ss[1]) + ss[2]) + ss[3]);
 }
 
+// The prompt of a forced selection (gitcap_attach_prompt): ids int64 [rows][ld], lengths int32 [rows] (valid tokens, CLS included,
+// clamped to [1, max_len] here: max_len <= ld is the host's check, so no read leaves a row), pos = the position the launch writes.
+// <false> is empty: the launches without a prompt carry nothing.
+template <bool FORCED> struct PromptSel {};
+template <> struct PromptSel<true> { const int64_t* ids; const int32_t* lengths; int ld, max_len, pos; };
+__device__ __forceinline__ int prompt_len(const int32_t* __restrict__ lengths, const int r, const int max_len) {
+    return min(max(lengths[r], 1), max_len);
+}
+
 // LP: also lp_out[r * ld_lp] = the log-probability of the token (lp_partials); a form of its own, so that the launches without it
-// stay the code they were
-template <int NV, bool LP = false>
+// stay the code they were.  FORCED (again a form of its own): a row whose prompt covers the position written (pr.pos <
+// lengths[r]) takes the prompt's token there instead of the arg-max -- into out, and into the next step's embedded row -- does not
+// count it in sep_cnt (the stop rule looks at what the model emitted) and writes 0.0f for its log-probability.
+template <int NV, bool LP = false, bool FORCED = false>
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
                                                            int ntiles, int row_stride, int row_off,
                                                            int64_t* __restrict__ out, int ld_out,
                                                            int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb,
                                                            const float* __restrict__ psum = nullptr, float* __restrict__ lp_out = nullptr,
-                                                           int ld_lp = 0) {
+                                                           int ld_lp = 0, PromptSel<FORCED> pr = PromptSel<FORCED>{}) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int chosen;
     __shared__ float vmax, ss[4];
     const int r = blockIdx.x, tid = threadIdx.x;
+    bool forced = false;                                                   // (thread 0's is the row's)
     const size_t base = (size_t)(r * row_stride + row_off) * ntiles;
     // gamma / beta of the next step's input row do not depend on the token chosen below: requested now (wave 0 uses them)
     f32x4 gv[NV > 0 ? NV : 1], bv[NV > 0 ? NV : 1];
@@ -414,14 +426,24 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
     argmax_partials_waves(val, idx, base, ntiles, sv, si, best, bi);
     if (tid == 0) {
         bi = argmax_partials_pick(sv, si, best, bi, LP ? &vmax : nullptr);
-        out[(size_t)r * ld_out] = bi;
-        if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
-        chosen = bi;
+        if constexpr (FORCED) {
+            forced = pr.pos < prompt_len(pr.lengths, r, pr.max_len);
+            if (forced) {
+                const int64_t tok = pr.ids[(size_t)r * pr.ld + pr.pos];
+                out[(size_t)r * ld_out] = tok;
+                chosen = tok < 0 ? -1 : (tok > 0x7fffffff ? 0x7fffffff : (int)tok);   // (the embedding clamps into its table)
+            }
+        }
+        if (!forced) {
+            out[(size_t)r * ld_out] = bi;
+            if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
+            chosen = bi;
+        }
     }
     if (LP) {
         __syncthreads();
         const float lp = lp_partials(val, psum, base, ntiles, vmax, ss);
-        if (tid == 0) lp_out[(size_t)r * ld_lp] = lp;
+        if (tid == 0) lp_out[(size_t)r * ld_lp] = forced ? 0.0f : lp;
     }
     if (NV > 0) {       // the next step's input row: embedding of the token just chosen + LayerNorm (one wave)
         __syncthreads();
@@ -948,13 +970,39 @@ struct BeamState {
     int64_t* hyp_ids;         // [B][n][max_len]
 };
 
+// A forced step of a prompted search (gitcap_attach_prompt): clip b at cur_len < lengths[b] is not ranked.  Every beam of the clip
+// keeps its prefix and appends the prompt's token, src_rows is the identity; beam_scores, done and the hypothesis slots are not
+// touched (no is_done test, no hypothesis added), the candidates are not read.  The whole wave; true = the clip was forced.
+__device__ __forceinline__ bool beam_step_forced(const BeamState& st, const PromptSel<true>& pr, const int b, const int beams,
+                                                 const int cur_len, const int max_len, const int cur) {
+    if (cur_len >= prompt_len(pr.lengths, b, pr.max_len)) return false;
+    const int64_t* ids_old = st.ids[cur];
+    int64_t* ids_new = st.ids[cur ^ 1];
+    const int64_t tok = pr.ids[(size_t)b * pr.ld + cur_len];
+    for (int j = 0; j < beams; ++j) {
+        const int r = b * beams + j;
+        for (int t = threadIdx.x; t < cur_len; t += 64) ids_new[(size_t)r * max_len + t] = ids_old[(size_t)r * max_len + t];
+        if (threadIdx.x == 0) {
+            ids_new[(size_t)r * max_len + cur_len] = tok;
+            st.words[r] = tok;
+            st.src_rows[r] = r;
+        }
+    }
+    return true;
+}
+
 // n = 1: one finished hypothesis per clip in hyp_ids [B][max_len], hyp_score [B], hyp_len [B] (0 = none yet).
+// FORCED: clips still inside their prompt take beam_step_forced; <false> is the kernel as it was before it became a template.
+template <bool FORCED>
 __global__ __launch_bounds__(64) void beam_step_kernel(BeamState st, const float* __restrict__ cand_scores,
                                                        const int* __restrict__ cand_idx, int beams, int K, int V,
-                                                       int cur_len, int max_len, int eos, float length_penalty, int cur) {
+                                                       int cur_len, int max_len, int eos, float length_penalty, int cur,
+                                                       PromptSel<FORCED> pr) {
     __shared__ int s_src[16];
     __shared__ long long s_word[16];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (FORCED)
+        if (beam_step_forced(st, pr, b, beams, cur_len, max_len, cur)) return;
     const int64_t* ids_old = st.ids[cur];
     int64_t* ids_new = st.ids[cur ^ 1];
     if (tid == 0) {
@@ -1018,10 +1066,12 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamState st, const float
 // per call at the configs[4] shape).  SAMPLED: the candidates are draws in no order (sample_rows_kernel): the done test takes the
 // maximum of the K scores, sentinel candidates are passed over, and a clip left with 0 < kept < beams live beams pads only the
 // missing ones.  <false> has the registers, scratch and occupancy of the kernel before it was a template (profiles/).
-template <bool SAMPLED>
+// FORCED: as beam_step_kernel's.
+template <bool SAMPLED, bool FORCED = false>
 __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n, const float* __restrict__ cand_scores,
                                                              const int* __restrict__ cand_idx, int beams, int K, int V,
-                                                             int cur_len, int max_len, int eos, float length_penalty, int cur) {
+                                                             int cur_len, int max_len, int eos, float length_penalty, int cur,
+                                                             PromptSel<FORCED> pr) {
     __shared__ int s_src[16];
     __shared__ long long s_word[16];
     __shared__ float s_hs[16];
@@ -1029,6 +1079,8 @@ __global__ __launch_bounds__(64) void beam_step_nbest_kernel(BeamState st, int n
     __shared__ int s_cnt, s_cmd, s_from;
     __shared__ float s_score;
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (FORCED)
+        if (beam_step_forced(st, pr, b, beams, cur_len, max_len, cur)) return;
     const int64_t* ids_old = st.ids[cur];
     int64_t* ids_new = st.ids[cur ^ 1];
     int64_t* hyp = st.hyp_ids + (size_t)b * n * max_len;
@@ -1184,6 +1236,14 @@ __global__ void fill_i64_kernel(int64_t* p, int ld, int rows, int64_t v) {
     if (r < rows) p[(size_t)r * ld] = v;
 }
 
+// the start of a prompted greedy loop: p[r][0 .. lengths[r] - 1] = prompt[r][the same] (lengths clamped to [1, max_len])
+__global__ void fill_prompt_kernel(int64_t* p, int ld, int rows, const int64_t* __restrict__ prompt, int ld_prompt,
+                                   const int32_t* __restrict__ lengths, int max_len) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = i / max_len, j = i - r * max_len;
+    if (r < rows && j < prompt_len(lengths, r, max_len)) p[(size_t)r * ld + j] = prompt[(size_t)r * ld_prompt + j];
+}
+
 // dst[l][r][t][:] = src[l][src_rows[r]][t][:] for t < t_len, every layer l = blockIdx.y in one launch
 // (text K/V rows, `width` bf16 per position, `layer_stride` elements between layers)
 __global__ void gather_txt_rows_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst,
@@ -1239,14 +1299,34 @@ hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int 
 
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride, int row_off,
                                int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s, const NextEmbed* emb,
-                               const float* amax_sum, float* lp_out, int ld_lp) {
+                               const float* amax_sum, float* lp_out, int ld_lp, const PromptArgs* prompt, int prompt_pos) {
     const NextEmbed e = emb ? *emb : NextEmbed{};
     const int nv = emb ? (e.D + 255) / 256 : 0;
     if (emb && (nv < 1 || nv > 4 || (e.D & 3) || !e.word || !e.pos || !e.gamma || !e.beta || !e.xf || !e.xb)) return hipErrorInvalidValue;
     if ((amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1)) return hipErrorInvalidValue;
+    if (prompt) {
+        if (!prompt->ids || !prompt->lengths || prompt->max_len < 1 || prompt->ld < prompt->max_len || prompt_pos < 0) return hipErrorInvalidValue;
+        if (prompt_pos < prompt->max_len) {           // (behind the longest prompt the plain forms below choose the same tokens)
+            const PromptSel<true> pr{prompt->ids, prompt->lengths, prompt->ld, prompt->max_len, prompt_pos};
+#define AF_LAUNCH_F(NV, LP) hipLaunchKernelGGL((argmax_final_kernel<NV, LP, true>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, \
+                                               row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp, pr)
+#define AF_SWITCH_F(LP)                                                                                                            \
+    switch (nv) {                                                                                                                  \
+        case 0: AF_LAUNCH_F(0, LP); break;                                                                                         \
+        case 1: AF_LAUNCH_F(1, LP); break;                                                                                         \
+        case 2: AF_LAUNCH_F(2, LP); break;                                                                                         \
+        case 3: AF_LAUNCH_F(3, LP); break;                                                                                         \
+        default: AF_LAUNCH_F(4, LP); break;                                                                                        \
+    }
+            if (lp_out) { AF_SWITCH_F(true) } else { AF_SWITCH_F(false) }
+#undef AF_SWITCH_F
+#undef AF_LAUNCH_F
+            return hipGetLastError();
+        }
+    }
     if (lp_out) {
 #define AF_LAUNCH_LP(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, true>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, \
-                                            row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp)
+                                            row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp, PromptSel<false>{})
         switch (nv) {
             case 0: AF_LAUNCH_LP(0); break;
             case 1: AF_LAUNCH_LP(1); break;
@@ -1258,7 +1338,7 @@ hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int n
         return hipGetLastError();
     }
 #define AF_LAUNCH(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, false>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, row_off, \
-                                         out, ld_out, sep_cnt, step, sep_id, e, (const float*)nullptr, (float*)nullptr, 0)
+                                         out, ld_out, sep_cnt, step, sep_id, e, (const float*)nullptr, (float*)nullptr, 0, PromptSel<false>{})
     switch (nv) {
         case 0: AF_LAUNCH(0); break;
         case 1: AF_LAUNCH(1); break;
@@ -1355,17 +1435,33 @@ hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int 
 }
 
 hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled) {
+                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled,
+                            const PromptArgs* prompt) {
     if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
+    if (prompt && (!prompt->ids || !prompt->lengths || prompt->max_len < 1 || prompt->ld < prompt->max_len || prompt->max_len >= max_len))
+        return hipErrorInvalidValue;
+    if (prompt && cur_len < prompt->max_len) {        // (behind the longest prompt no clip is forced: the plain forms below)
+        const PromptSel<true> pr{prompt->ids, prompt->lengths, prompt->ld, prompt->max_len, cur_len};
+        if (sampled)
+            hipLaunchKernelGGL((beam_step_nbest_kernel<true, true>), dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V,
+                               cur_len, max_len, eos, length_penalty, cur, pr);
+        else if (n == 1)
+            hipLaunchKernelGGL(beam_step_kernel<true>, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len,
+                               max_len, eos, length_penalty, cur, pr);
+        else
+            hipLaunchKernelGGL((beam_step_nbest_kernel<false, true>), dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V,
+                               cur_len, max_len, eos, length_penalty, cur, pr);
+        return hipGetLastError();
+    }
     if (sampled)
         hipLaunchKernelGGL(beam_step_nbest_kernel<true>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
-                           max_len, eos, length_penalty, cur);
+                           max_len, eos, length_penalty, cur, PromptSel<false>{});
     else if (n == 1)
-        hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
-                           length_penalty, cur);
+        hipLaunchKernelGGL(beam_step_kernel<false>, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
+                           length_penalty, cur, PromptSel<false>{});
     else
         hipLaunchKernelGGL(beam_step_nbest_kernel<false>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
-                           max_len, eos, length_penalty, cur);
+                           max_len, eos, length_penalty, cur, PromptSel<false>{});
     return hipGetLastError();
 }
 
@@ -1507,6 +1603,14 @@ hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, in
 
 hipError_t launch_finish_steps(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out, hipStream_t s) {
     hipLaunchKernelGGL(finish_steps_kernel, dim3(1), dim3(1), 0, s, sep_cnt, rows, max_len, stop, steps_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_prompt(int64_t* p, int ld, int rows, const PromptArgs& prompt, hipStream_t s) {
+    if (!p || !prompt.ids || !prompt.lengths || rows < 1 || prompt.max_len < 1 || prompt.ld < prompt.max_len || ld < prompt.max_len)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fill_prompt_kernel, dim3((rows * prompt.max_len + 63) / 64), dim3(64), 0, s, p, ld, rows, prompt.ids, prompt.ld,
+                       prompt.lengths, prompt.max_len);
     return hipGetLastError();
 }
 

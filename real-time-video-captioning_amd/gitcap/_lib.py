@@ -183,6 +183,13 @@ SYMBOLS = {
                                    c_float, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_beam_step_sampled": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                              c_int, c_float, c_int, c_void_p]),
+    # prompted decoding: per-clip text prefixes (tests/test_prompt_gpu.py)
+    "gitcap_attach_prompt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "gitcap_dbg_argmax_final_forced": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                               POINTER(CDbgNextEmbed), c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                               c_void_p]),
+    "gitcap_dbg_beam_step_forced": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_float, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),

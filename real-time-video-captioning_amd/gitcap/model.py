@@ -157,6 +157,22 @@ class _StagingRing:
         return dview, e, st
 
 
+class _Prompt:
+    """A batch of per-clip text prefixes on the device (include/gitcap.h: gitcap_attach_prompt): ids int64 [B, P] with CLS at
+    column 0, lengths int32 [B] (valid tokens per clip, CLS included), and the host's copy of the lengths."""
+
+    def __init__(self, ids, lengths, host_lengths):
+        self.ids, self.lengths, self.host_lengths = ids, lengths, host_lengths
+        self.min_len, self.max_len = min(host_lengths), max(host_lengths)
+
+    def rows(self, r0, r1):
+        return _Prompt(self.ids[r0:r1].contiguous(), self.lengths[r0:r1].contiguous(), self.host_lengths[r0:r1])
+
+    def attach(self, model):
+        """The one-shot attachment the NEXT greedy- or beam-family call consumes (a repeated call attaches again)."""
+        model._call("gitcap_attach_prompt", _lib.ptr(self.ids), self.ids.shape[1], _lib.ptr(self.lengths), self.min_len, self.max_len)
+
+
 def _lp2d(logprobs):
     """The search's scores as the reference returns them, [B, num_keep_best] (the one-hypothesis call writes [B])."""
     return logprobs[:, None] if logprobs.dim() == 1 else logprobs
@@ -191,6 +207,7 @@ class CaptionFuture(_Future):
         self._m, self._frames, self._mode, self._max_len, self._out_device = model, frames, mode, max_len, out_device
         self._sub, self._r0, self._r1 = None, 0, 0
         self._done = None
+        self._prompt = None                      # greedy_decode_async(prompt=...): held until the result (the device reads it)
 
     def _attach(self, sub, r0, r1):
         self._sub, self._r0, self._r1 = sub, r0, r1
@@ -217,7 +234,7 @@ class CaptionFuture(_Future):
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         def rerun():
-            ids = m._greedy_decode(sub.rows(self._r0, self._r1), self._max_len, self._mode)
+            ids = m._greedy_decode(sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._prompt)
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         synced = self._mode == STOP_ALL_SEP or self._out_device.type == "cpu"
@@ -245,6 +262,8 @@ class InferFuture(_Future):
                    "logits_dict": [] if steps is None else steps, "visual_features": mv(vis)}
             if self._kw.get("sampling") is not None:
                 out["seed"] = self._kw["sampling"][3]
+            if self._kw.get("prompt") is not None:
+                out["prompt_lengths"] = mv(self._kw["prompt"].lengths)
             return out
 
         def rerun():
@@ -264,10 +283,11 @@ class CaptionStream(_WindowStream):
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None):
+                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None):
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
         self._nbest, self._rp = int(num_keep_best), float(repetition_penalty)
         self._sampling = sampling        # (temperature, top_k, top_p, seed | None) of a do_sample stream
+        self._prompt = prompt            # _Prompt | None: the stream's per-clip prompt, attached again for every caption
         self.last_seed = None            # do_sample: the seed of the caption the last push returned
         self._clear()
         super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
@@ -347,6 +367,8 @@ class CaptionStream(_WindowStream):
                 ids, steps, lp = self._greedy_buffers(B)
                 if lp is not None:
                     m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), self._max_len)
+                if self._prompt is not None:
+                    self._prompt.attach(m)
                 m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
                 decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
@@ -354,6 +376,8 @@ class CaptionStream(_WindowStream):
                 sampling = m._seeded(self._sampling)
                 attach, nbest, nbest_lp, _ = m._search_options(B, self._max_len, self._nbest, self._rp, sampling)
                 attach()                         # one-shot: consumed by the search below (a repeated caption attaches again)
+                if self._prompt is not None:
+                    self._prompt.attach(m)
                 m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
                         _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
                 if nbest is not None:
@@ -364,7 +388,10 @@ class CaptionStream(_WindowStream):
         if self._beam is None:
             return self._finish_greedy(ids, steps, lp, on_cpu)
         mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
-        return {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)), "logits_dict": [], "visual_features": mv(vis)}
+        out = {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)), "logits_dict": [], "visual_features": mv(vis)}
+        if self._prompt is not None:
+            out["prompt_lengths"] = mv(self._prompt.lengths)
+        return out
 
 
 def _rebuild(cfg_dict, weights, kwargs):
@@ -614,6 +641,38 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"expected uint8 frames [B,F,H,W,3], got {x.dtype}")
         return self._to_device(x)
 
+    def _prompt(self, prompt, prompt_lengths, B, limit, what):
+        """The ``prompt=`` argument of the decoding calls -> _Prompt or None.  prompt: int64 [B, P] (every row P tokens, or
+        ``prompt_lengths`` [B] valid tokens per row) or a list of B 1-D tensors (ragged).  CLS is prepended to a row that does not
+        start with it (the lengths then count it).  A set-up step: the lengths are read on the host."""
+        if prompt is None:
+            if prompt_lengths is not None:
+                raise ValueError("prompt_lengths without prompt")
+            return None
+        if isinstance(prompt, torch.Tensor):
+            if prompt.dim() != 2:
+                raise ValueError(f"prompt must be [B, P] or a list of B 1-D tensors, got {tuple(prompt.shape)}")
+            lens = [prompt.shape[1]] * prompt.shape[0] if prompt_lengths is None else [int(v) for v in torch.as_tensor(prompt_lengths).tolist()]
+            if len(lens) != prompt.shape[0] or any(not 0 <= n <= prompt.shape[1] for n in lens):
+                raise ValueError("prompt_lengths must hold one length in [0, P] per row of prompt")
+            host = prompt.detach().to("cpu", torch.int64)
+            rows = [host[b, :n] for b, n in enumerate(lens)]
+        else:
+            if prompt_lengths is not None:
+                raise ValueError("prompt_lengths goes with a [B, P] tensor; a list of rows carries its own lengths")
+            rows = [torch.as_tensor(r).detach().to("cpu", torch.int64).reshape(-1) for r in prompt]
+        if len(rows) != B:
+            raise ValueError(f"prompt has {len(rows)} rows for a batch of {B} clips")
+        cls = self.cls_token_id
+        rows = [r if r.numel() and int(r[0]) == cls else torch.cat([torch.tensor([cls], dtype=torch.int64), r]) for r in rows]
+        lens = [int(r.numel()) for r in rows]
+        if max(lens) > limit:
+            raise ValueError(f"a prompt of {max(lens)} tokens (CLS included) exceeds {what} = {limit}")
+        ids = torch.full((B, max(lens)), cls, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            ids[b, :lens[b]] = r
+        return _Prompt(ids.to(self._dev), torch.tensor(lens, dtype=torch.int32).to(self._dev), lens)
+
     def _ids(self, y: torch.Tensor) -> torch.Tensor:
         return y.to(device=self._dev, dtype=torch.int64).contiguous()
 
@@ -821,22 +880,29 @@ class GitCaptioner(_NativeModule):
         return [l[None] for l in logits], [v[None] for v in vis], [h for h in hid]
 
     @torch.no_grad()
-    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False):
+    def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
+                      prompt=None, prompt_lengths=None):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
         truncation the reference's `break` implies is applied afterwards.  return_logprobs=True: (ids, logprobs), logprobs fp32
         [B, steps] on src's device, column t = log_softmax(step t's logits)[ids[:, t + 1]] (include/gitcap.h:
-        gitcap_attach_token_logprobs; the ids are the same either way)."""
+        gitcap_attach_token_logprobs; the ids are the same either way).
+        prompt: per-clip text prefixes the captions start from (the `prefix` branch of model.py:432-437; include/gitcap.h:
+        gitcap_attach_prompt): int64 [B, P], optionally with prompt_lengths [B], or a list of B 1-D tensors of different lengths;
+        CLS is prepended where a row does not start with it.  The ids returned INCLUDE each row's prompt (columns
+        0 .. its length - 1; the reference strips its single prefix, :455, which a ragged batch cannot do); prompt tokens do not
+        count for stop='all_sep', and their logprobs columns are 0."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
+        pr = self._prompt(prompt, prompt_lengths, src.shape[0], max_len, "max_len")
         if src.device.type == "cpu":              # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, pr)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False):
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None):
         self._drain()
         fr, raw = self._check_frames(src)         # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
         B, F = fr.shape[:2]
@@ -849,6 +915,9 @@ class GitCaptioner(_NativeModule):
                 if want_lp:                      # one-shot: consumed by the greedy call below
                     lps.append(torch.empty((chunk.shape[0], max_len), dtype=torch.float32, device=self._dev))
                     self._call("gitcap_attach_token_logprobs", _lib.ptr(lps[-1]), max_len)
+                if pr is not None:               # one-shot as well
+                    part = pr if B <= self.max_batch else pr.rows(b0, b0 + chunk.shape[0])
+                    part.attach(self)
                 if raw:
                     self._call("gitcap_greedy_raw", _lib.ptr(chunk), chunk.shape[0], F, chunk.shape[2], chunk.shape[3], max_len, mode,
                                _lib.ptr(ids), _lib.ptr(steps), self._stream())
@@ -877,7 +946,7 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode_async(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
-                            coalesce: int = 1) -> "CaptionFuture":
+                            coalesce: int = 1, prompt=None, prompt_lengths=None) -> "CaptionFuture":
         """Pipelined greedy_decode for a stream of batches: returns immediately with a future; up to
         FOUR submissions may be in flight, so one batch's image pass (MFMA bound) overlaps the token
         loops (latency bound) of the batches before it on the handle's internal HIP streams.  Call
@@ -892,7 +961,8 @@ class GitCaptioner(_NativeModule):
         ``coalesce=k`` (dynamic batching): k consecutive calls with the same shape are concatenated and
         run as ONE pass of k*B clips (the per-clip results are bitwise the same: the kernels are batch
         invariant); a ``result()`` on a batch that is still waiting for partners flushes it.  Needs
-        max_batch >= k*B."""
+        max_batch >= k*B.  ``prompt`` / ``prompt_lengths`` as in greedy_decode; a prompted batch is submitted on its own (it does
+        not coalesce)."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
@@ -904,8 +974,12 @@ class GitCaptioner(_NativeModule):
         host = fr.device.type == "cpu"
         if not host:
             fr = self._to_device(fr)
+        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
         fut = CaptionFuture(self, fr, mode, max_len, src.device)
-        key = (tuple(fr.shape), max_len, mode, raw, host)
+        fut._prompt = pr
+        key = (tuple(fr.shape), max_len, mode, raw, host, None if pr is None else id(pr))
+        if pr is not None:
+            coalesce = 1
         if self._pending and self._pending_key != key:
             self._flush_pending()
         self._pending.append(fut)
@@ -942,12 +1016,14 @@ class GitCaptioner(_NativeModule):
             steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
             ticket = ctypes.c_int(-1)
             stop = STOP_NEVER if len(group) > 1 else mode       # the stop rule is per caller batch: applied in result()
+            pr = group[0]._prompt                # (a prompted batch is a group of one)
+            before = None if pr is None else (lambda: pr.attach(self))
             if raw:
                 self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, F, frames.shape[2], frames.shape[3], max_len, stop,
-                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket))
+                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket), before=before)
             else:
                 self._submit("gitcap_greedy_submit", _lib.ptr(frames), B, F, max_len, stop, _lib.ptr(ids), _lib.ptr(steps), stream,
-                             ctypes.byref(ticket))
+                             ctypes.byref(ticket), before=before)
         self._last_memory = None
         shared = _Submission(ticket.value, frames, (ids, steps), len(group) > 1, users=len(group), parts=parts)
         if entry is not None:
@@ -975,7 +1051,8 @@ class GitCaptioner(_NativeModule):
     def infer(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
               on_device: Optional[bool] = None, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
-              top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> dict:
+              top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
+              prompt_lengths=None) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
         reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
@@ -993,7 +1070,14 @@ class GitCaptioner(_NativeModule):
         same caption from infer, infer_async and caption_stream; a clip's draws depend on its position in the batch.  seed=None
         takes one int64 from torch's global CPU generator (torch.manual_seed makes a run repeatable); the seed used is returned as
         ``seed``.  on_device=False draws with torch.multinomial from torch.Generator().manual_seed(seed): the two paths draw from
-        different streams and agree in distribution only."""
+        different streams and agree in distribution only.
+        prompt / prompt_lengths (as in greedy_decode): the `prefix` of model.py:432-437, one per clip and of any length below
+        max_steps.  The search of a clip starts from its prompt; max_steps and the length penalty count the prompt's tokens, its
+        tokens add nothing to a score, the repetition penalty sees them.  ``predictions`` INCLUDE each clip's prompt and the dict
+        gains ``prompt_lengths`` [B] (CLS included), so a caller can strip what the reference strips at :455 -- the one deliberate
+        difference: the reference returns predictions with its single prefix removed, which a ragged batch cannot do.
+        on_device=False takes the reference's own route: the host operator clip by clip with start_predictions = the clip's prompt
+        (the batch-of-one form of :436-437)."""
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
@@ -1009,21 +1093,26 @@ class GitCaptioner(_NativeModule):
             on_device = (not save_logits and 1 <= num_keep_best <= beam_size * per_node_beam_size <= 16
                          and per_node_beam_size >= 2)
         sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
+        pr = self._prompt(prompt, prompt_lengths, B, max_steps - 1, "max_steps - 1")
         if on_device:
             self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
             decoded, logprobs, steps, vis = self._infer_device(fr, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
                                                                per_node_beam_size=per_node_beam_size, sync=True,
                                                                save_logits=save_logits, want_visual=False, raw=raw,
                                                                num_keep_best=num_keep_best, repetition_penalty=repetition_penalty,
-                                                               sampling=sampling)
+                                                               sampling=sampling, prompt=pr)
             out = {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
                    "visual_features": None}
             if sampling is not None:
                 out["seed"] = sampling[3]
+            if pr is not None:
+                out["prompt_lengths"] = pr.lengths
             return out
-        _, vis = self.forward_image_enc(fr)
         searcher = GeneratorWithBeamSearch(self.sep_token_id, max_steps, beam_size, per_node_beam_size, length_penalty,
                                            repetition_penalty=repetition_penalty, temperature=temperature)
+        if pr is not None:
+            return self._infer_host_prompted(fr, pr, searcher, beam_size, num_keep_best, save_logits, sampling, top_k, top_p)
+        _, vis = self.forward_image_enc(fr)
         start = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev)      # model.py:429-431
 
         def step(ids):                       # decoding_step bound at model.py:442-445, KV-cached
@@ -1040,6 +1129,36 @@ class GitCaptioner(_NativeModule):
                                                    do_sample=True, top_k=top_k, top_p=top_p,
                                                    generator=torch.Generator().manual_seed(sampling[3]))
         return {"predictions": decoded, "logprobs": logprobs, "logits_dict": saved, "visual_features": vis, "seed": sampling[3]}
+
+    def _infer_host_prompted(self, fr, pr, searcher, beam_size, num_keep_best, save_logits, sampling, top_k, top_p):
+        """infer(on_device=False, prompt=...): the host operator clip by clip from start_predictions = the clip's prompt.  The first
+        step of a clip runs the whole prompt through the decoder (every beam row holds it); the steps behind it are KV-cached."""
+        preds, lps, saved_all, vis_all = [], [], [], []
+        for b in range(fr.shape[0]):
+            _, vis = self.forward_image_enc(fr[b:b + 1])
+            n = pr.host_lengths[b]
+            start = pr.ids[b:b + 1, :n]
+
+            def step(ids, n=n):
+                if ids.shape[1] > n:
+                    return self.step_logits(ids[:, -1], ids.shape[1] - 1, beams=beam_size)
+                ids = self._ids(ids)
+                logits = torch.empty((ids.shape[0], self.cfg.vocab_size), dtype=torch.float32, device=self._dev)
+                with torch.cuda.device(self._dev):
+                    self._call("gitcap_text_forward", _lib.ptr(ids), ids.shape[1], ids.shape[0], beam_size, 0, ids.shape[1], _lib.ptr(logits),
+                               0, None, 0, self._stream())
+                return logits
+
+            kw = {} if sampling is None else dict(do_sample=True, top_k=top_k, top_p=top_p,
+                                                  generator=torch.Generator().manual_seed(sampling[3]))
+            decoded, logprobs, saved = searcher.search(start, step, num_keep_best=num_keep_best, reorder=self.reorder_rows,
+                                                       save_logits=save_logits, **kw)
+            preds.append(decoded); lps.append(logprobs); saved_all.append(saved); vis_all.append(vis)
+        out = {"predictions": torch.cat(preds, 0), "logprobs": torch.cat(lps, 0), "logits_dict": saved_all,
+               "visual_features": torch.cat(vis_all, 0), "prompt_lengths": pr.lengths}
+        if sampling is not None:
+            out["seed"] = sampling[3]
+        return out
 
     @staticmethod
     def _sampling(do_sample, temperature, top_k, top_p, seed):
@@ -1108,7 +1227,7 @@ class GitCaptioner(_NativeModule):
         return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
 
     def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None):
+                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None):
         """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
         stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
         the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
@@ -1119,6 +1238,12 @@ class GitCaptioner(_NativeModule):
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
         attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty, sampling)
+        if prompt is not None:                   # one-shot beside the options: every issue of the call attaches both
+            attach_options = attach
+
+            def attach():
+                attach_options()
+                prompt.attach(self)
         first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
         if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
             first, decoded, logprobs = rank0, nbest, nbest_lp
@@ -1151,14 +1276,15 @@ class GitCaptioner(_NativeModule):
     def infer_async(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
                     per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False,
                     num_keep_best: int = 1, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
-                    top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> "InferFuture":
+                    top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
+                    prompt_lengths=None) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
         tensor [max_steps - 1, B * beam_size, V] (the raw logits of every step, model.py:521), with ``visual_features`` the fp32
         features [B, F*N, Dv] (model.py:460); num_keep_best / repetition_penalty as in ``infer``.  Results are bitwise those of the
         synchronous call, with do_sample too (its arguments as in ``infer``; the seed is fixed at submission and returned as
-        ``seed``).  `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
+        ``seed``) and with prompt / prompt_lengths (as in ``infer``; the dict gains ``prompt_lengths``).  `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
         sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
         self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
         if beam_size > self.max_beams:
@@ -1171,7 +1297,8 @@ class GitCaptioner(_NativeModule):
         if fr.shape[0] > self.max_batch:
             raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
         kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
-                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling)
+                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling,
+                  prompt=self._prompt(prompt, prompt_lengths, fr.shape[0], max_steps - 1, "max_steps - 1"))
         parts = entry = stream = None
         if fr.device.type == "cpu":
             while len(self._inflight) >= 4:      # (before the staging: the entry about to be reused belongs to the oldest)
@@ -1193,7 +1320,8 @@ class GitCaptioner(_NativeModule):
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
                        visual_features: bool = False, gate=None, logprobs: bool = False, num_keep_best: int = 1,
                        repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
-                       top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None) -> CaptionStream:
+                       top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
+                       prompt_lengths=None) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1204,7 +1332,8 @@ class GitCaptioner(_NativeModule):
         that returned a caption, ``stream.last_logprobs`` holds its per-token log-probabilities [B, steps] (greedy_decode's
         return_logprobs; gitcap.caption_confidence turns them into one number per clip).  do_sample / top_k / top_p / temperature /
         seed (beam streams only) as in infer: every caption samples with `seed` (seed=None: a fresh one per caption from torch's
-        global CPU generator); ``stream.last_seed`` is the seed of the caption the last push returned."""
+        global CPU generator); ``stream.last_seed`` is the seed of the caption the last push returned.  prompt / prompt_lengths (as
+        in greedy_decode / infer): the stream's prompt, one row per clip, attached again for every caption."""
         if logprobs and beam_size is not None:
             raise ValueError("logprobs=True is for greedy streams (the beam-search dict carries its own sequence score)")
         window = int(window or max(1, self.cfg.num_frames))
@@ -1231,9 +1360,11 @@ class GitCaptioner(_NativeModule):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
+        pr = self._prompt(prompt, prompt_lengths, batch, max_len if beam_size is None else max_len - 1,
+                          "max_len" if beam_size is None else "max_len - 1")
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
                              logprobs, num_keep_best, repetition_penalty,
-                             sampling)
+                             sampling, pr)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip
