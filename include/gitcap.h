@@ -908,6 +908,49 @@ int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, in
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream);
 int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream);
 
+/* Teacher-student divergence of given captions, forward only: KL(teacher || student) of every position's next-token distribution
+ * at a temperature -- LOSS 2 of DistillationTrainer.training_step (src/models/model.py:919-935: KLDivLoss('batchmean') of
+ * log_softmax(student / t) against softmax(teacher / t)) -- without either model's [rows * T][V] logits: both vocabulary heads run
+ * over the same 16-column tiles in one launch that keeps seven per-tile statistics, and one merge launch follows (csrc/skinny.hip:
+ * skinny_head_dual_kernel, csrc/rowops.hip: distill_final_kernel).
+ * Preconditions: gitcap_score's on the teacher (after gitcap_encode / gitcap_set_visual; rows = encoded clips * beams) and
+ * gitcap_student_score's on the student (after gitcap_student_set_memory with `rows` rows, a clip's rows repeating its memory);
+ * both handles on one device, equal vocab_size, widths (768 | 1024, 576) or (128, 64), temperature > 0 and finite, T >= 1,
+ * ld_ids >= T, out and out->kl non-null, ld_kl >= T, ld_lp >= T - 1 where a log-probability output is set.  Every refusal is
+ * GITCAP_ERR_ARG / GITCAP_ERR_STATE with the message on the TEACHER's last_error, and launches nothing.
+ * Both passes run on `stream` (teacher, then student), synchronous path, slot 0; the text K/V of positions 0 .. T - 1 of both
+ * handles are overwritten, as gitcap_score does.  Outputs (device; all but kl nullable), with t = teacher logit / temperature:
+ *   kl            fp32 [rows][ld_kl], positions 0 .. T - 1: sum_v softmax(t)_v (log_softmax(t)_v - log_softmax(s)_v) in nats (NOT times
+ *                 temperature^2); +inf where the teacher gives mass to a word whose student logit is -inf; 0 at a position
+ *                 j >= lengths[r] (lengths nullable, device int32 [rows]) and for a row whose teacher logits are all -inf
+ *   teacher_top1 / student_top1  int64 [rows][T]: each model's arg-max under the token loops' tie rule; agree uint8 [rows][T]
+ *   teacher_lp / student_lp      fp32 [rows][ld_lp], positions 0 .. T - 2: log-probability (at the temperature) of the given next
+ *                 token ids[r][j + 1] under gitcap_score's ignore rules (0 where ignored); temperature 1: gitcap_score's bits
+ *   row_kl_sum fp32 [rows] / row_cnt int32 [rows]: the counted positions' kl added in ascending order, and their number
+ * A row's values are bit for bit independent of the rows beside it.  The first call allocates the partial buffers on the teacher
+ * handle; gitcap_workspace_bytes counts them from then on.  Handles that never call it run the launches they ran before. */
+typedef struct gitcap_distill_out {
+    float* kl; int ld_kl;
+    int64_t* teacher_top1; int64_t* student_top1; uint8_t* agree;
+    float* teacher_lp; float* student_lp; int ld_lp;
+    float* row_kl_sum; int32_t* row_cnt;
+} gitcap_distill_out;
+int gitcap_distill(gitcap_t* teacher, gitcap_student_t* student, const int64_t* ids, int ld_ids, int rows, int beams, int T,
+                   const int32_t* lengths, int64_t ignore_id, float temperature, const gitcap_distill_out* out, void* stream);
+/* debug: the dual head on caller-owned buffers.  Xt [M][ldxt] / Xs [M][ldxs] bf16 rows, Wt [Npad16][Kt] (bf16, or e4m3 codes with
+ * wscale [Npad16]) / Ws [Npad16][Ks] bf16, biases [N] (nullable); seven partials [M][ntiles]; targets int64 [M] (nullable; one
+ * column per row) -> t_logit / s_logit fp32 [M] (untouched for a target outside [0, N)). */
+int gitcap_dbg_vocab_head_dual(const void* Xt, int ldxt, const void* Wt, const float* wscale, const float* bias_t, int Kt, const void* Xs,
+                               int ldxs, const void* Ws, const float* bias_s, int Ks, int M, int N, float inv_temperature, float* t_max,
+                               int32_t* t_idx, float* t_sum, float* s_max, int32_t* s_idx, float* s_sum, float* cross,
+                               const int64_t* targets, float* t_logit, float* s_logit, void* stream);
+/* debug: the merge of gitcap_distill on caller-owned buffers: partials [rows * T][ntiles], t_logit / s_logit [rows * T] (required
+ * with the matching log-probability output), ids [rows][ld_ids]; out as gitcap_distill's, out->kl required. */
+int gitcap_dbg_distill_final(const float* t_max, const int32_t* t_idx, const float* t_sum, const float* s_max, const int32_t* s_idx,
+                             const float* s_sum, const float* cross, int ntiles, const float* t_logit, const float* s_logit,
+                             const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                             const gitcap_distill_out* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Student image encoder (SURVEY.md par. 8 row f.2): timm's TinyVit as StudentCandidateV1 loads it with
  * features_only=True (src/models/model.py:35-47, :108-126) -- conv stem, MBConv stage 0, three stages of

@@ -3,6 +3,7 @@
 #include "../../include/gitcap.h"
 #include "kernels.h"
 #include "host_util.h"
+#include "student_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -166,6 +167,11 @@ struct gitcap : HandleCore {
     SearchOpt so_attach{};
     // gitcap_attach_prompt: the pending one-shot attachment (ids == nullptr: none); taken by the next greedy- or beam-family call
     PromptArgs pr_attach{};
+
+    // gitcap_distill (first use): the dual head's seven partials [slot 0's Mt][ntiles], both models' target logits
+    // ([2][Mt])
+    struct Distill { float *t_max = nullptr, *t_sum = nullptr, *s_max = nullptr, *s_sum = nullptr, *cross = nullptr, *rows = nullptr;
+                     int *t_idx = nullptr, *s_idx = nullptr; } dist;
 
     // Frame window (gitcap_window_reset / _push / _greedy / _beam_search): the fp32 ln_post rows (no temporal embedding) of the
     // last win.slots frames of win_B clips, clip-major [B][F][N][Dv]; win (RingCursor) = where the next frame goes and how many
@@ -1559,6 +1565,70 @@ int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream)
     return 0;
 }
 
+// first gitcap_distill: the partial buffers (nothing is kept of a failed attempt but what the handle frees anyway)
+static int ensure_distill(gitcap* h) {
+    gitcap::Distill& d = h->dist;
+    if (d.rows) return 0;
+    const size_t n = (size_t)h->slots[0].Mt * (size_t)((h->V + 15) / 16);
+    int rc;
+    if ((rc = dev_alloc(h, &d.t_max, n)) || (rc = dev_alloc(h, &d.t_idx, n)) || (rc = dev_alloc(h, &d.t_sum, n)) || (rc = dev_alloc(h, &d.s_max, n)) ||
+        (rc = dev_alloc(h, &d.s_idx, n)) || (rc = dev_alloc(h, &d.s_sum, n)) || (rc = dev_alloc(h, &d.cross, n)))
+        return rc;
+    return dev_alloc(h, &d.rows, 2 * (size_t)h->slots[0].Mt);
+}
+
+int gitcap_distill(gitcap_t* h, gitcap_student_t* st, const int64_t* ids, int ld_ids, int rows, int beams, int T, const int32_t* lengths,
+                   int64_t ignore_id, float temperature, const gitcap_distill_out* out, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "distill: null teacher handle");
+    if (!st) return fail(h, GITCAP_ERR_ARG, "distill: null student handle");
+    if (!ids || !out || !out->kl) return fail(h, GITCAP_ERR_ARG, "distill: null ids, out or out->kl");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "distill: teacher weights not finalized");
+    if (!h->slots[0].have) return fail(h, GITCAP_ERR_STATE, "distill before encode/set_visual");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(h, GITCAP_ERR_ARG, "distill: temperature must be positive and finite");
+    if (T < 1 || ld_ids < T || out->ld_kl < T) return fail(h, GITCAP_ERR_ARG, "distill: T < 1, ld_ids < T or ld_kl < T");
+    if ((out->teacher_lp || out->student_lp) && out->ld_lp < T - 1) return fail(h, GITCAP_ERR_ARG, "distill: ld_lp < T - 1");
+    if (rows <= 0 || beams <= 0 || rows != h->slots[0].B * beams || rows > h->R) return fail(h, GITCAP_ERR_ARG, "distill: rows != encoded clips * beams, or beyond max_batch*max_beams");
+    if (T > h->Tmax || T > h->c.max_text_pos || (int64_t)rows * T > h->slots[0].Mt) return fail(h, GITCAP_ERR_ARG, "distill: T exceeds max_text_len / max_text_pos");
+    if (student_device(st) != h->device) return fail(h, GITCAP_ERR_ARG, "distill: the two handles live on different devices");
+    std::string why;
+    if (int rc = student_rows_check(st, rows, T, why)) return fail(h, rc, "distill: " + why);
+    const HeadWeight sw = student_head_weight(st);
+    if (sw.V != h->V) return fail(h, GITCAP_ERR_ARG, "distill: the two models' vocab_size differ");
+    if (!head_dual_ok(h->D, sw.D)) return fail(h, GITCAP_ERR_ARG, "distill: no dual head for these two widths");
+    const float inv_temp = 1.0f / temperature;
+    if (!(inv_temp > 0.f) || !std::isfinite(inv_temp)) return fail(h, GITCAP_ERR_ARG, "distill: 1 / temperature is not a positive finite fp32");
+    GUARD(h);
+    POLL(h);
+    select_slot(h, 0);
+    gitcap::Slot& sl = cur(h);
+    int rc;
+    if ((rc = ensure_distill(h))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(h, join_async(h, s));
+    // both stacks up to their final LayerNorm rows (the "rows only, no head" request of the existing passes), then the two launches
+    if ((rc = text_forward(h, ids, ld_ids, rows, beams, 0, T, nullptr, 1, nullptr, 0, nullptr, 0, s))) return rc;
+    StudentRows sr{};
+    if ((rc = student_forward_rows(st, ids, ld_ids, rows, T, s, &sr, why))) return fail(h, rc, "distill: " + why);
+    const gitcap::Distill& d = h->dist;
+    const int M = rows * T, V = h->V;
+    const bool want_lp = out->teacher_lp || out->student_lp;
+    DualHeadArgs da{};
+    da.Xt = sl.xsb; da.ldxt = h->D; da.Xs = sr.xb; da.ldxs = sr.head.D;
+    da.wt = HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, h->D}; da.ws = sr.head;
+    da.M = M; da.inv_temp = inv_temp;
+    da.t_max = d.t_max; da.t_idx = d.t_idx; da.t_sum = d.t_sum; da.s_max = d.s_max; da.s_idx = d.s_idx; da.s_sum = d.s_sum; da.cross = d.cross;
+    if (want_lp) { da.tg = HeadTargets{ids, T, ld_ids, 1, d.rows}; da.s_logit = d.rows + sl.Mt; }
+    {
+        ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * M * V * (h->D + sr.head.D), (h->head_w.scale ? 1.0 : 2.0) * V * h->D + 2.0 * V * sr.head.D);
+        HIP_OK(h, launch_head_dual(da, s));
+    }
+    const DistillOut o{out->kl, out->ld_kl, out->teacher_top1, out->student_top1, out->agree, out->teacher_lp, out->student_lp, out->ld_lp,
+                       out->row_kl_sum, out->row_cnt};
+    HIP_OK(h, launch_distill_final(DistillPartials{d.t_max, d.t_idx, d.t_sum, d.s_max, d.s_idx, d.s_sum, d.cross}, (V + 15) / 16, d.rows,
+                                   d.rows + sl.Mt, ids, ld_ids, rows, T, lengths, ignore_id, V, o, s));
+    return 0;
+}
+
 int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_prompt: null handle");
     h->pr_attach = PromptArgs{};
@@ -1844,6 +1914,30 @@ int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const
     const ScoreOut o{token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
     return dbg_rc(launch_score_final(amax_val, amax_idx, amax_sum, ntiles, tgt_logit, ids, ld_ids, rows, T, lengths, ignore_id, V, o,
                                      (hipStream_t)stream));
+}
+
+// launch_head_dual on caller-owned buffers, row-major weights; targets: one column per row (HeadTargets with T = ld = M, shift 0)
+int gitcap_dbg_vocab_head_dual(const void* Xt, int ldxt, const void* Wt, const float* wscale, const float* bias_t, int Kt, const void* Xs,
+                               int ldxs, const void* Ws, const float* bias_s, int Ks, int M, int N, float inv_temperature, float* t_max,
+                               int32_t* t_idx, float* t_sum, float* s_max, int32_t* s_idx, float* s_sum, float* cross,
+                               const int64_t* targets, float* t_logit, float* s_logit, void* stream) {
+    DualHeadArgs a{};
+    a.Xt = (const bf16_t*)Xt; a.ldxt = ldxt; a.Xs = (const bf16_t*)Xs; a.ldxs = ldxs;
+    a.wt = HeadWeight{Wt, nullptr, wscale, bias_t, N, Kt}; a.ws = HeadWeight{Ws, nullptr, nullptr, bias_s, N, Ks};
+    a.M = M; a.inv_temp = inv_temperature;
+    a.t_max = t_max; a.t_idx = t_idx; a.t_sum = t_sum; a.s_max = s_max; a.s_idx = s_idx; a.s_sum = s_sum; a.cross = cross;
+    if (targets) { a.tg = HeadTargets{targets, M, M, 0, t_logit}; a.s_logit = s_logit; }
+    return dbg_rc(launch_head_dual(a, (hipStream_t)stream));
+}
+int gitcap_dbg_distill_final(const float* t_max, const int32_t* t_idx, const float* t_sum, const float* s_max, const int32_t* s_idx,
+                             const float* s_sum, const float* cross, int ntiles, const float* t_logit, const float* s_logit,
+                             const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                             const gitcap_distill_out* out, void* stream) {
+    if (!out) return GITCAP_ERR_ARG;
+    const DistillOut o{out->kl, out->ld_kl, out->teacher_top1, out->student_top1, out->agree, out->teacher_lp, out->student_lp, out->ld_lp,
+                       out->row_kl_sum, out->row_cnt};
+    return dbg_rc(launch_distill_final(DistillPartials{t_max, t_idx, t_sum, s_max, s_idx, s_sum, cross}, ntiles, t_logit, s_logit, ids, ld_ids,
+                                       rows, T, lengths, ignore_id, V, o, (hipStream_t)stream));
 }
 
 static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,

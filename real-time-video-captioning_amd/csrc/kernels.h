@@ -150,6 +150,38 @@ inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int
     const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
     return launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
 }
+// ---- teacher-student divergence (gitcap_distill): both vocabulary heads over the same tiles, then one merge -------------------
+// launch_head_dual (skinny.hip: skinny_head_dual_kernel): the teacher's rows Xt [M][ldxt] against wt (bf16, or e4m3 codes with
+// wscale) and the student's rows Xs [M][ldxs] against ws (bf16), (wt.D, ws.D) one of (768, 576), (1024, 576), (128, 64), equal V.
+// With t = (acc + bias) * inv_temp and s likewise it leaves seven partials [M][ntiles]: each model's arg-max / sum-of-exp partials
+// as the single heads leave them (inv_temp == 1: bit for bit) and cross = sum exp(t - t_max) ((t - t_max) - (s - s_max)) over the
+// tile's columns with t > -inf (+inf where such a column has s = -inf, 0 where t_max = -inf).  tg.ids (nullable): the logits t / s
+// of each head row's target column go to tg.logit / s_logit (HeadTargets; untouched for a target outside [0, V)).
+struct DualHeadArgs {
+    const bf16_t *Xt, *Xs; int ldxt, ldxs;
+    HeadWeight wt, ws;
+    int M; float inv_temp;
+    float *t_max; int* t_idx; float *t_sum, *s_max; int* s_idx; float *s_sum, *cross;
+    HeadTargets tg; float* s_logit;
+};
+bool head_dual_ok(int Kt, int Ks);
+hipError_t launch_head_dual(const DualHeadArgs& a, hipStream_t s);
+// launch_distill_final (rowops.hip): one workgroup per (row r, position j < T) merges the partials of head row m = r * T + j in
+// launch_score_final's fixed order: each model's winner and log-sum-exp exactly as score_final_kernel forms them, C = sum over the
+// tiles of e^(t_max - Mt) (cross + t_sum ((t_max - Mt) - (s_max - Ms))), kl = C / Zt - log Zt + log Zs (a value in [-DISTILL_CLAMP,
+// 0) becomes 0, DISTILL_CLAMP = the two logs' share of the rounding bound: tests/distill_reference.py; +inf where the teacher puts mass on a column the
+// student excludes; 0 for a row the teacher gives no column at all).  A position j >= lengths[r] (nullable) gets kl 0 and is not
+// counted.  top1 / agree [rows][T] cover every position; t_lp / s_lp [rows][ld_lp] = the given next token's log-probability at
+// positions 0 .. T - 2 under launch_score_final's rules (0 where ignored), need t_logit / s_logit.  All outputs but kl nullable.
+// row_kl_sum / row_cnt (a second launch, one thread per row): the counted positions' kl in ascending order, and their number.
+constexpr float DISTILL_CLAMP = 4e-5f;                     // 2 x the 2e-5 nats of a merged log-sum-exp
+struct DistillOut {
+    float* kl; int ld_kl; int64_t *t_top1, *s_top1; uint8_t* agree; float *t_lp, *s_lp; int ld_lp; float* row_kl_sum; int32_t* row_cnt;
+};
+struct DistillPartials { const float* t_max; const int* t_idx; const float *t_sum, *s_max; const int* s_idx; const float *s_sum, *cross; };
+hipError_t launch_distill_final(const DistillPartials& p, int ntiles, const float* t_logit, const float* s_logit, const int64_t* ids,
+                                int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V, const DistillOut& o,
+                                hipStream_t s);
 bool skinny_full_ok(int K);                                 // K depths launch_skinny is instantiated for
 int skinny_ksplit(int K);                                    // number of K slabs launch_skinny_splitk writes
 hipError_t launch_skinny_splitk(const SkinnyArgs& a, hipStream_t s);

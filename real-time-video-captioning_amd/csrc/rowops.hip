@@ -362,8 +362,9 @@ __device__ __forceinline__ int argmax_partials_pick(const float* sv, const int* 
 // one: thread tid takes tiles tid, tid + 256, .. ascending, the xor butterfly 32 .. 1 inside the wave, then waves 0 .. 3 in that
 // order.  Called by every thread (one barrier inside; ss = four words of LDS); thread 0's return value is the row's, -inf for a
 // row with no logit above -inf (M = -inf).  The partials of a row are 3 x 7.6 KB at the GIT vocabulary: L2 resident.
+// total (nullable; launch_distill_final): thread 0's also gets the merged sum itself, 0 for such a row.
 __device__ __forceinline__ float lp_partials(const float* __restrict__ val, const float* __restrict__ sum, const size_t base,
-                                             const int ntiles, const float M, float* ss) {
+                                             const int ntiles, const float M, float* ss, float* total = nullptr) {
     const int tid = threadIdx.x;
     float acc = 0.f;
     if (M != -INFINITY) {                                                  // (uniform: M comes from LDS)
@@ -384,8 +385,13 @@ __device__ __forceinline__ float lp_partials(const float* __restrict__ val, cons
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((tid & 63) == 0) ss[tid >> 6] = acc;
     __syncthreads();
-    if (M == -INFINITY) return -INFINITY;
-    return -__logf(((ss[0] + ss[1]) + ss[2]) + ss[3]);
+    if (M == -INFINITY) {
+        if (total) *total = 0.f;
+        return -INFINITY;
+    }
+    const float z = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+    if (total) *total = z;
+    return -__logf(z);
 }
 
 // The prompt of a forced selection (gitcap_attach_prompt): ids int64 [rows][ld], lengths int32 [rows] (valid tokens, CLS included,
@@ -575,6 +581,88 @@ __global__ __launch_bounds__(64) void score_rows_kernel(const float* __restrict_
         if (score_counted(ids, ld_ids, lengths, ignore_id, V, r, j)) { sum += lp[(size_t)r * ld_lp + j]; ++cnt; }
     if (row_sum) row_sum[r] = sum;
     if (row_cnt) row_cnt[r] = cnt;
+}
+
+// ---- teacher-student divergence (gitcap_distill; kernels.h: launch_distill_final) -------------------------------------------------
+// One workgroup per (row r, position j < T) over the seven partials of head row m = r * T + j (skinny.hip: skinny_head_dual_kernel).
+// Each model's winner, maximum M, merged sum Z and -log Z exactly as score_final_kernel forms them (argmax_partials_waves / _pick,
+// lp_partials: same tie rule, same summation order, same bits).  The cross term re-centred with the tile maxima,
+//     C = sum_tiles e^(t_max - Mt) (cross + t_sum ((t_max - Mt) - (s_max - Ms))),
+// over the tiles with t_max > -inf in lp_partials' order (thread tid takes tiles tid, tid + 256, .. ascending, the xor butterfly,
+// waves 0 .. 3); a tile whose cross is +inf (the teacher puts mass where the student has -inf) adds +inf outright: its s_max may be
+// -inf, and neither 0 * inf nor -inf - -inf is ever formed.  kl = (C / Zt + -log Zt) - -log Zs; a negative value no further from 0
+// than DISTILL_CLAMP (the two logs' share of the rounding bound, tests/distill_reference.py) becomes 0, anything else is left to show.
+// A row the teacher gives no column at all (Mt = -inf) has kl 0.
+__global__ __launch_bounds__(256) void distill_final_kernel(DistillPartials p, int ntiles, const float* __restrict__ t_logit,
+                                                            const float* __restrict__ s_logit, const int64_t* __restrict__ ids, int ld_ids,
+                                                            int T, const int32_t* __restrict__ lengths, int64_t ignore_id, int V, DistillOut o) {
+    __shared__ float svt[4], svs[4], sst[4], sss[4], sc[4];
+    __shared__ int sit[4], sis[4];
+    __shared__ float vmax_t, vmax_s;
+    const int r = blockIdx.x / T, j = blockIdx.x - r * T, tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * ntiles;
+    float best, zt = 0.f, zs = 0.f;
+    int bt, bs;
+    argmax_partials_waves(p.t_max, p.t_idx, base, ntiles, svt, sit, best, bt);
+    if (tid == 0) bt = argmax_partials_pick(svt, sit, best, bt, &vmax_t);
+    argmax_partials_waves(p.s_max, p.s_idx, base, ntiles, svs, sis, best, bs);      // (its barrier publishes vmax_t)
+    if (tid == 0) bs = argmax_partials_pick(svs, sis, best, bs, &vmax_s);
+    const float lpt = lp_partials(p.t_max, p.t_sum, base, ntiles, vmax_t, sst, &zt);
+    __syncthreads();                                                                // vmax_s
+    const float lps = lp_partials(p.s_max, p.s_sum, base, ntiles, vmax_s, sss, &zs);
+    const float Mt = vmax_t, Ms = vmax_s;
+    float c = 0.f;
+    if (Mt != -INFINITY) {
+        for (int i0 = tid; i0 < ntiles; i0 += 256 * 8) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + 256 * u;
+                if (i < ntiles) {
+                    const float tm = p.t_max[base + i];
+                    if (tm != -INFINITY) {
+                        const float cr = p.cross[base + i];
+                        c += cr == INFINITY ? INFINITY : __expf(tm - Mt) * (cr + p.t_sum[base + i] * ((tm - Mt) - (p.s_max[base + i] - Ms)));
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((tid & 63) == 0) sc[tid >> 6] = c;
+    __syncthreads();
+    if (tid != 0) return;
+    const bool live = !lengths || j < lengths[r];
+    float kl = 0.f;
+    if (live && Mt != -INFINITY) {
+        const float C = ((sc[0] + sc[1]) + sc[2]) + sc[3];
+        kl = (C / zt + lpt) - lps;
+        if (kl < 0.f && kl >= -DISTILL_CLAMP) kl = 0.f;
+    }
+    o.kl[(size_t)r * o.ld_kl + j] = kl;
+    if (o.t_top1) o.t_top1[blockIdx.x] = bt;
+    if (o.s_top1) o.s_top1[blockIdx.x] = bs;
+    if (o.agree) o.agree[blockIdx.x] = bt == bs ? 1 : 0;
+    if (j + 1 < T && (o.t_lp || o.s_lp)) {
+        const bool cnt = score_counted(ids, ld_ids, lengths, ignore_id, V, r, j);
+        float a = 0.f, b = 0.f;
+        if (cnt && o.t_lp) { const float y = t_logit[blockIdx.x]; a = y == -INFINITY ? -INFINITY : (y - Mt) + lpt; }
+        if (cnt && o.s_lp) { const float y = s_logit[blockIdx.x]; b = y == -INFINITY ? -INFINITY : (y - Ms) + lps; }
+        if (o.t_lp) o.t_lp[(size_t)r * o.ld_lp + j] = a;
+        if (o.s_lp) o.s_lp[(size_t)r * o.ld_lp + j] = b;
+    }
+}
+// row_kl_sum[r] = the counted positions' kl, added in ascending position order by one thread; row_cnt[r] = their number
+__global__ __launch_bounds__(64) void distill_rows_kernel(const float* __restrict__ kl, int ld_kl, int rows, int T,
+                                                          const int32_t* __restrict__ lengths, float* __restrict__ row_sum,
+                                                          int32_t* __restrict__ row_cnt) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= rows) return;
+    const int n = lengths ? min(max(lengths[r], 0), T) : T;
+    float sum = 0.f;
+    for (int j = 0; j < n; ++j) sum += kl[(size_t)r * ld_kl + j];
+    if (row_sum) row_sum[r] = sum;
+    if (row_cnt) row_cnt[r] = n;
 }
 
 // ---- beam candidates: top-K of (log_softmax(logits[b*beams+j]) + beam_score[b*beams+j]) over j, v ----
@@ -1361,6 +1449,21 @@ hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const 
     if (o.row_sum || o.row_cnt)
         hipLaunchKernelGGL(score_rows_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, (const float*)o.lp, o.ld_lp, ids, ld_ids, rows, T, lengths,
                            ignore_id, V, o.row_sum, o.row_cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_distill_final(const DistillPartials& p, int ntiles, const float* t_logit, const float* s_logit, const int64_t* ids,
+                                int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V, const DistillOut& o,
+                                hipStream_t s) {
+    if (!p.t_max || !p.t_idx || !p.t_sum || !p.s_max || !p.s_idx || !p.s_sum || !p.cross || !o.kl || ntiles <= 0 || rows <= 0 || T < 1 ||
+        V <= 0 || o.ld_kl < T || (int64_t)rows * T > 0x7fffffff)
+        return hipErrorInvalidValue;
+    if ((o.t_lp || o.s_lp) && (!ids || ld_ids < T || o.ld_lp < T - 1 || (o.t_lp && !t_logit) || (o.s_lp && !s_logit))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(distill_final_kernel, dim3(rows * T), dim3(256), 0, s, p, ntiles, t_logit, s_logit, ids, ld_ids, T, lengths, ignore_id,
+                       V, o);
+    if (o.row_kl_sum || o.row_cnt)
+        hipLaunchKernelGGL(distill_rows_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, (const float*)o.kl, o.ld_kl, rows, T, lengths,
+                           o.row_kl_sum, o.row_cnt);
     return hipGetLastError();
 }
 

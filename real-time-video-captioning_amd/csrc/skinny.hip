@@ -358,6 +358,165 @@ __global__ __launch_bounds__(256) void skinny_head_score_kernel(SkinnyArgs a, co
     skinny_head_body<K32, FP8, true, true>(a, ntiles, tg);
 }
 
+// ---- two vocabulary heads over the same tile: teacher-student divergence (gitcap_distill) -----------------------------------
+// KL(teacher || student) of a row needs sum_v p_t(v) (t_v - s_v): both models' logits of the same column at the same time.  The
+// workgroup of skinny_head_body -- four waves = four neighbouring 16-column tiles -- here keeps the fragments of BOTH head weights
+// of its tile (KT + KS bf16x8 registers per lane: 42 at 768 + 576, 50 at 1024 + 576), stages both activation m-tiles through LDS
+// (pitch rule as above, two images) and runs two MFMA chains per m-tile, teacher then student, each over the operands and in the
+// order of the single-head kernels: t and s are bit for bit the logits those kernels produce.  No logit is stored.  Per (row, tile)
+// it leaves, with t = (acc + bias) * inv_temp and s likewise, over the columns < N:
+//     t_max / t_idx / t_sum, s_max / s_idx / s_sum   logits_epilogue<true>'s three partials of each model (same code order: the
+//                                                    lane's columns ascending, then the 16 / 32 xor butterfly; inv_temp == 1: same bits)
+//     cross = sum exp(t - t_max) ((t - t_max) - (s - s_max))   over the columns with t > -inf; the exp is the very value summed
+//                                                    into t_sum.  +inf outright where such a column has s = -inf (never 0 * inf,
+//                                                    never -inf - -inf); 0 for a tile whose t_max is -inf.
+// launch_distill_final (rowops.hip) re-centres with the tile maxima and merges in a fixed order.
+// LDS: 2 x 16 x ((KT + KS) * 64 + 32) bytes = 87 040 at 768 + 576, 103 424 at 1024 + 576, 13 312 at 128 + 64: one workgroup per CU
+// at the model sizes (160 KiB per CU), i.e. one wave per SIMD with the whole 512-register file to itself -- the fragments of both
+// weights (168 / 200 registers) stay resident across the m-tiles without scratch.  The launch streams both weights once (82 MB
+// at the GIT vocabulary) and is bound by that stream like the single heads.
+template <int K32> struct XTile {
+    static constexpr int PITCH = K32 * 64 + 16, CPR = K32 * 4, NC = (16 * CPR + 255) / 256, BYTES = 16 * PITCH;
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    u32x4 st[NC];
+    __device__ __forceinline__ void gload(const bf16_t* X, const int ldx, const int M, const int mt) {
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c0 = (int)threadIdx.x + 256 * i, c = c0 < 16 * CPR ? c0 : 0;
+            const int row = c / CPR, col = c - row * CPR;
+            int m = mt * 16 + row;
+            m = m < M ? m : M - 1;                               // clamp: padded rows are discarded
+            st[i] = *(const u32x4*)(X + (size_t)m * ldx + col * 8);
+        }
+    }
+    __device__ __forceinline__ void lstore(char* img) const {
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c = (int)threadIdx.x + 256 * i, row = c / CPR, col = c - row * CPR;
+            if (c < 16 * CPR) *(u32x4*)(&img[row * PITCH + col * 16]) = st[i];
+        }
+    }
+};
+
+// logits_epilogue<true>'s three partials of one model's 16 x 16 tile, in its order; e[r] = the exp terms summed into se (0 for
+// a column that is not counted)
+__device__ __forceinline__ void dual_tile_stats(const float (&y)[4], const int n, const int N, float& best, int& bi, float& se, float (&e)[4]) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (n + r < N && (y[r] > best)) { best = y[r]; bi = n + r; }
+#pragma unroll
+    for (int off = 16; off < 64; off <<= 1) {
+        const float v2 = __shfl_xor(best, off);
+        const int i2 = __shfl_xor(bi, off);
+        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+    }
+    se = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) e[r] = 0.f;
+    if (best != -INFINITY) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (n + r < N) { e[r] = __expf(y[r] - best); se += e[r]; }
+    }
+#pragma unroll
+    for (int off = 16; off < 64; off <<= 1) se += __shfl_xor(se, off);
+}
+
+template <int KT, int KS, bool FP8>
+__global__ __launch_bounds__(256) void skinny_head_dual_kernel(const DualHeadArgs a, const int ntiles) {
+    typedef XTile<KT> TT;
+    typedef XTile<KS> TS;
+    constexpr int IMG = TT::BYTES + TS::BYTES;
+    __shared__ __attribute__((aligned(16))) char xs[2][IMG];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int tile_raw = blockIdx.x * 4 + wave;
+    const bool active = tile_raw < ntiles;                       // (a wave past the last tile repeats it and stores nothing)
+    const int tile = active ? tile_raw : ntiles - 1;
+    const int n0 = tile * 16, N = a.wt.V;
+    const int mtiles = (a.M + 15) >> 4;
+    const bool tgt = a.tg.ids != nullptr;
+    TT xt;
+    TS xst;
+    int64_t tnext = -1;
+    if (tgt) tnext = head_target(a.tg, min(frow, a.M - 1));
+    xt.gload(a.Xt, a.ldxt, a.M, 0);
+    xst.gload(a.Xs, a.ldxs, a.M, 0);
+    bf16x8 wt[KT], ws[KS];
+    load_wfrags<KT, FP8>(a.wt.W, a.wt.Wpk, a.wt.wscale, (size_t)(n0 + frow), KT * 32, fq * 8, wt);
+    load_wfrags<KS, false>(a.ws.W, a.ws.Wpk, nullptr, (size_t)(n0 + frow), KS * 32, fq * 8, ws);
+    const int n = n0 + fq * 4;
+    float bt[4], bs[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        bt[r] = (a.wt.bias && n + r < N) ? a.wt.bias[n + r] : 0.f;
+        bs[r] = (a.ws.bias && n + r < N) ? a.ws.bias[n + r] : 0.f;
+    }
+    xt.lstore(&xs[0][0]);
+    xst.lstore(&xs[0][TT::BYTES]);
+    __syncthreads();
+    for (int mt = 0; mt < mtiles; ++mt) {
+        const int64_t tcol = tnext;
+        if (mt + 1 < mtiles) {
+            if (tgt) tnext = head_target(a.tg, min((mt + 1) * 16 + frow, a.M - 1));
+            xt.gload(a.Xt, a.ldxt, a.M, mt + 1);
+            xst.gload(a.Xs, a.ldxs, a.M, mt + 1);
+        }
+        const char* xbt = &xs[mt & 1][frow * TT::PITCH + fq * 16];
+        const char* xbs = &xs[mt & 1][TT::BYTES + frow * TS::PITCH + fq * 16];
+        f32x4 acct = f32x4{0.f, 0.f, 0.f, 0.f}, accs = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acct = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wt[k], *(const bf16x8*)(xbt + k * 64), acct, 0, 0, 0);
+#pragma unroll
+        for (int k = 0; k < KS; ++k) accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ws[k], *(const bf16x8*)(xbs + k * 64), accs, 0, 0, 0);
+        const int mraw = mt * 16 + frow, m = mraw < a.M ? mraw : a.M - 1;
+        const bool mvalid = mraw < a.M && active;
+        float t[4], sv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            t[r] = (acct[r] + bt[r]) * a.inv_temp;
+            sv[r] = (accs[r] + bs[r]) * a.inv_temp;
+        }
+        if (mvalid && tcol >= n && tcol < n + 4 && tcol < N) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)                         // (one store each, as logits_epilogue<.., true>)
+                if (tcol == n + r) { a.tg.logit[m] = t[r]; a.s_logit[m] = sv[r]; }
+        }
+        float tb, sb, tse, sse, te[4], se4[4];
+        int ti, si;
+        dual_tile_stats(t, n, N, tb, ti, tse, te);
+        dual_tile_stats(sv, n, N, sb, si, sse, se4);
+        float cr = 0.f;
+        if (tb != -INFINITY) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (n + r < N && t[r] != -INFINITY) cr += sv[r] == -INFINITY ? INFINITY : te[r] * ((t[r] - tb) - (sv[r] - sb));
+        }
+#pragma unroll
+        for (int off = 16; off < 64; off <<= 1) cr += __shfl_xor(cr, off);
+        if (fq == 0 && mvalid) {
+            const size_t o = (size_t)m * ntiles + tile;
+            a.t_max[o] = tb; a.t_idx[o] = ti; a.t_sum[o] = tse;
+            a.s_max[o] = sb; a.s_idx[o] = si; a.s_sum[o] = sse;
+            a.cross[o] = cr;
+        }
+        if (mt + 1 < mtiles) {                                   // the image m-tile mt - 1 was read from (skinny_head_body)
+            xt.lstore(&xs[(mt + 1) & 1][0]);
+            xst.lstore(&xs[(mt + 1) & 1][TT::BYTES]);
+        }
+        __syncthreads();
+    }
+}
+
+template <int KT, int KS>
+hipError_t launch_dual(const DualHeadArgs& a, const int ntiles, hipStream_t s) {
+    if (a.wt.wscale) hipLaunchKernelGGL((skinny_head_dual_kernel<KT, KS, true>), dim3((ntiles + 3) / 4), dim3(256), 0, s, a, ntiles);
+    else hipLaunchKernelGGL((skinny_head_dual_kernel<KT, KS, false>), dim3((ntiles + 3) / 4), dim3(256), 0, s, a, ntiles);
+    return hipGetLastError();
+}
+
 // ---- one/two-row prologue over many slabs: three waves share the reduce ---------------------------------------------------
 // The fused FFN launch (ffn_txt.hip) leaves dec_ffn / 64 = 48 slabs; the single wave of skinny_full<LNR> walks them in three
 // dependent round trips (two 8-slab groups each) before it can normalise its row -- in every one of the 144 workgroups, 150
@@ -614,4 +773,21 @@ hipError_t launch_skinny_splitk(const SkinnyArgs& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+bool head_dual_ok(int Kt, int Ks) { return (Kt == 128 && Ks == 64) || ((Kt == 768 || Kt == 1024) && Ks == 576); }
+
+hipError_t launch_head_dual(const DualHeadArgs& a, hipStream_t s) {
+    const int N = a.wt.V;
+    if (!a.Xt || !a.Xs || !a.wt.W || !a.ws.W || a.ws.wscale || a.M <= 0 || N <= 0 || a.ws.V != N || !head_dual_ok(a.wt.D, a.ws.D) ||
+        a.ldxt < a.wt.D || a.ldxs < a.ws.D || a.ldxt % 8 || a.ldxs % 8 || ((uintptr_t)a.Xt & 15) || ((uintptr_t)a.Xs & 15) ||
+        !(a.inv_temp > 0.f) || a.inv_temp == INFINITY || !a.t_max || !a.t_idx || !a.t_sum || !a.s_max || !a.s_idx || !a.s_sum || !a.cross)
+        return hipErrorInvalidValue;
+    if (a.tg.ids && (!a.tg.logit || !a.s_logit || a.tg.T <= 0 || a.tg.ld < a.tg.T || a.tg.shift < 0 || a.M % a.tg.T)) return hipErrorInvalidValue;
+    const int ntiles = (N + 15) / 16;
+    switch (a.wt.D) {
+        case 128: return launch_dual<4, 2>(a, ntiles, s);
+        case 768: return launch_dual<24, 18>(a, ntiles, s);
+        default: return launch_dual<32, 18>(a, ntiles, s);
+    }
 }

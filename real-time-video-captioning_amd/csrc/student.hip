@@ -12,6 +12,7 @@
 #include "../../include/gitcap.h"
 #include "kernels.h"
 #include "host_util.h"
+#include "student_internal.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -374,6 +375,26 @@ int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s) {
 }
 
 }  // namespace
+
+// ---- student_internal.h: what gitcap_distill (gitcap.hip) needs of this handle ----------------------------------------------------
+int student_device(const gitcap_student* h) { return h->device; }
+HeadWeight student_head_weight(const gitcap_student* h) { return head_weight(h); }
+int student_rows_check(const gitcap_student* h, int rows, int T, std::string& why) {
+    auto no = [&](int code, const char* m) { why = m; return code; };
+    if (!h->finalized) return no(GITCAP_ERR_STATE, "student: weights not finalized");
+    if (!h->have_memory) return no(GITCAP_ERR_STATE, "student: decoder called before set_memory");
+    if (rows <= 0 || T <= 0) return no(GITCAP_ERR_ARG, "student: bad arguments");
+    if (rows != h->cur_B) return no(GITCAP_ERR_ARG, "student: rows != rows of the current memory");
+    if (T > h->Tmax) return no(GITCAP_ERR_ARG, "student: T exceeds max_text_len+1");
+    if (T > h->c.max_pos) return no(GITCAP_ERR_ARG, "student: position exceeds the positional table");
+    return 0;
+}
+int student_forward_rows(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int T, hipStream_t s, StudentRows* out, std::string& why) {
+    const int rc = text_forward(h, ids, ld_ids, rows, 0, T, nullptr, nullptr, 0, nullptr, 0, s);
+    if (rc) { why = h->err; return rc; }
+    *out = StudentRows{h->xb, head_weight(h)};
+    return 0;
+}
 
 extern "C" {
 

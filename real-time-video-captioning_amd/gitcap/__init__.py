@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "caption_confidence":
         from .confidence import caption_confidence
         return caption_confidence
+    if name == "distill_report":
+        from .distill import distill_report
+        return distill_report
     raise AttributeError(name)

@@ -40,6 +40,12 @@ class CSamplingOptions(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int32), ("top_p", c_float), ("seed", ctypes.c_uint64)]
 
 
+class CDistillOut(ctypes.Structure):
+    """struct gitcap_distill_out (include/gitcap.h)."""
+    _fields_ = [("kl", c_void_p), ("ld_kl", c_int32), ("teacher_top1", c_void_p), ("student_top1", c_void_p), ("agree", c_void_p),
+                ("teacher_lp", c_void_p), ("student_lp", c_void_p), ("ld_lp", c_int32), ("row_kl_sum", c_void_p), ("row_cnt", c_void_p)]
+
+
 class CDbgSkinnyArgs(ctypes.Structure):
     """struct gitcap_dbg_skinny_args (include/gitcap.h)."""
     _fields_ = [("X", c_void_p), ("ldx", c_int32), ("W", c_void_p), ("Wpk", c_void_p), ("wscale", c_void_p), ("bias", c_void_p),
@@ -170,6 +176,14 @@ SYMBOLS = {
     "gitcap_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    # teacher-student divergence (gitcap/distill.py; tests/test_distill_gpu.py): the call, the dual head, the merge
+    "gitcap_distill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_float, POINTER(CDistillOut),
+                               c_void_p]),
+    "gitcap_dbg_vocab_head_dual": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                           c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_distill_final": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, POINTER(CDistillOut), c_void_p]),
     # search options of the device-resident search: n-best hypotheses, repetition penalty (tests/test_search_options_gpu.py)
     "gitcap_attach_search_options": (c_int, [c_void_p, POINTER(CSearchOptions)]),
     "gitcap_beam_topk_penalized": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
