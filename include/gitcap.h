@@ -374,6 +374,65 @@ int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream)
  * attachment is consumed all the same).  A handle that never attaches runs exactly the launches it ran before. */
 int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len);
 
+/* Constrained decoding: hard limits on what a step may emit.  Before a step ranks, arg-maxes or samples row r, every banned column
+ * of that row is -inf, and everything downstream sees the banned row: the head's tile partials, the chunk statistics, the
+ * log-softmax, the top-k / top-p filter, the token log-probabilities.  The edit sits where the reference edits its logits
+ * (src/models/model.py:522-531, ahead of the log_softmax at :557), so the probabilities renormalise over the allowed columns -- a
+ * deliberate difference from HF's beam search, which masks after normalising.  With prefix = the row's ids so far (CLS and any prompt
+ * included) and cur_len its length, the banned set of a row is the union of
+ *   no_repeat_ngram_size = n >= 1 (HF NoRepeatNGramLogitsProcessor): prefix[i + n - 1] for every i in 0 .. cur_len - n with
+ *       prefix[i .. i + n - 2] == prefix[cur_len - n + 1 .. cur_len - 1]; nothing while cur_len + 1 < n; n = 1: every token of the
+ *       prefix.  Ids are compared as values; an id outside [0, vocab_size) bans nothing.
+ *   min_length = m (HF MinLengthLogitsProcessor): the model's SEP while cur_len < m; m counts CLS and the prompt.
+ *   suppress (HF SuppressTokensLogitsProcessor): up to 256 ids banned at every step; duplicates allowed, ids outside the
+ *       vocabulary ignored.
+ * A position forced by a prompt (gitcap_attach_prompt) takes the prompt's token whatever is banned; under a repetition penalty -inf
+ * stays -inf.  gitcap_score, gitcap_distill, gitcap_text_forward and the student model are not constrained.
+ * A ONE-SHOT attachment with the life cycle of gitcap_attach_prompt: the next call of the greedy family (gitcap_greedy,
+ * gitcap_greedy_raw, their _submit forms, gitcap_window_greedy) or of the beam family (gitcap_beam_search, its _submit / _raw_submit
+ * forms, gitcap_window_beam_search, sampled or not) consumes it, whichever comes first, whether that call succeeds or is refused;
+ * every other entry point leaves it pending; NULL detaches.  It combines with the log-probability, search-option, sampling and
+ * prompt attachments.  A pipelined submission captures `suppress`: the buffer stays valid and unchanged until the wait.
+ * Each step of a constrained call makes one more small launch (the rows' ban mask, uint16 [rows][ld_mask], bit c & 15 of word
+ * c >> 4 = column c, built from the buffer that holds each row's current prefix; in the beam family the rows are the B * beams
+ * beam rows) and runs the BAN form of the vocabulary head (greedy) or of the candidate ranking / sampling kernel (beam).  The mask
+ * buffers -- one per pipeline slot, max_batch * max_beams rows -- are allocated by the first attach (a set-up step that may
+ * synchronise; gitcap_workspace_bytes counts them from then on); a handle that never attaches allocates nothing and runs exactly
+ * the launches it ran before.  A prompted greedy call with constraints attached runs its prompt as forced token steps: the one-pass
+ * plan of gitcap_attach_prompt is not combined with constraints (same ids either way).
+ * Errors, all GITCAP_ERR_ARG: a negative field; n_suppress > 256; n_suppress > 0 with a null or misaligned pointer; a vocabulary
+ * above 131072 columns; at the consuming call n_suppress + max_len >= vocab_size (greedy) or n_suppress + max_steps + beams *
+ * per_node_beam_size > vocab_size (beam): a row could otherwise lose every column, or a clip be left with fewer candidates than
+ * the bookkeeping ranks.  Nothing is launched then and the attachment is consumed all the same. */
+typedef struct gitcap_constraints {
+    int32_t no_repeat_ngram_size;   /* 0 = off, else 1..max_text_len */
+    int32_t min_length;             /* 0 = off; counts CLS and the prompt */
+    const int32_t* suppress;        /* device int32 [n_suppress], nullable when n_suppress == 0 */
+    int32_t n_suppress;             /* 0..256 */
+} gitcap_constraints;
+int gitcap_attach_constraints(gitcap_t* h, const gitcap_constraints* c);   /* NULL detaches */
+
+/* The kernels behind it, one launcher each on caller-owned device buffers (tests/test_constraints_gpu.py).
+ * gitcap_dbg_ban_mask: one workgroup per row writes every word of mask_out [rows][ld_mask] (ld_mask even, >= ceil(V / 16); the
+ * result does not depend on what the buffer held) from prefix_ids int64 [rows][ld_ids] (columns 0 .. cur_len - 1) and the device
+ * list suppress int32 [n_suppress]; V <= 131072.
+ * gitcap_dbg_vocab_head_banned: gitcap_dbg_vocab_head_lse under mask uint16 [M][ld_mask]; amax_sum NULL selects the plain form.
+ * gitcap_beam_topk_constrained / gitcap_sample_rows_constrained: gitcap_beam_topk_penalized / gitcap_sample_rows under mask
+ * [B * beams][ld_mask]; repetition_penalty = 1 selects the unpenalised BAN form.  Each equals its unconstrained call on logits
+ * that hold -inf at the banned columns, bit for bit. */
+int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                        const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream);
+int gitcap_dbg_vocab_head_banned(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                 float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const uint16_t* mask, int ld_mask,
+                                 void* stream);
+int gitcap_beam_topk_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                 float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx,
+                                 const uint16_t* mask, int ld_mask, void* stream);
+int gitcap_sample_rows_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                   float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                                   uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out,
+                                   const uint16_t* mask, int ld_mask, void* stream);
+
 /* Options of the device-resident search: the reference's search operator keeps `num_keep_best` finished hypotheses per clip and
  * applies a `repetition_penalty` (GeneratorWithBeamSearchV2.search, src/models/model.py:479-678; the penalty :522-531, the n-best
  * output :653-678).  A ONE-SHOT attachment, like gitcap_attach_token_logprobs: it applies to the NEXT beam-family call or

@@ -70,6 +70,8 @@ struct DecLayer {
 // Options of one device-resident search (gitcap_attach_search_options): hypotheses kept per clip, repetition penalty, n-best outputs.
 // smp: the sampling branch (gitcap_attach_sampling), pending beside the options above and consumed with them.
 struct SampleOpt { bool on = false; float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; uint64_t seed = 0; };
+// gitcap_attach_constraints: what a step may not emit (include/gitcap.h); on = false: none
+struct ConsOpt { bool on = false; int ngram = 0, min_length = 0; const int32_t* suppress = nullptr; int n_suppress = 0; };
 struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; SampleOpt smp{}; };
 
 struct gitcap : HandleCore {
@@ -142,6 +144,7 @@ struct gitcap : HandleCore {
         float* beam_logits = nullptr;       // [R][V]
         float* cand_scores = nullptr;       // [B][16]
         int* cand_idx = nullptr;
+        uint16_t* ban_mask = nullptr;       // constrained decoding: [R][ban_ld] ban mask of the step's rows; allocated by the first gitcap_attach_constraints
         char* topk_scratch = nullptr;       // beam_topk chunk statistics + per-chunk candidates (sized for max_batch x max_beams rows)
         // n-best hypotheses of the search (num_keep_best > 1): [max_batch][16][Tmax + 1] ids, [max_batch][16] scores and lengths;
         // allocated by the first gitcap_attach_search_options that asks for more than one
@@ -167,6 +170,10 @@ struct gitcap : HandleCore {
     SearchOpt so_attach{};
     // gitcap_attach_prompt: the pending one-shot attachment (ids == nullptr: none); taken by the next greedy- or beam-family call
     PromptArgs pr_attach{};
+    // gitcap_attach_constraints: the pending one-shot attachment (on = false: none); taken by the next greedy- or beam-family call.
+    // cons_cur: the constraints of the call whose launches are being issued (as cur_slot / pipelined); ban_ld: words per mask row
+    ConsOpt cons_attach{}, cons_cur{};
+    int ban_ld = 0;
 
     // gitcap_distill (first use): the dual head's seven partials [slot 0's Mt][ntiles], both models' target logits
     // ([2][Mt])
@@ -528,7 +535,7 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams, int t0, int T, float* logits_out,
                  int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
                  bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0, const ScoreReq* score = nullptr,
-                 const PromptArgs* prompt = nullptr) {
+                 const PromptArgs* prompt = nullptr, const HeadBan* ban = nullptr) {
     const gitcap_config& c = h->c;
     gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -637,7 +644,7 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
                                         argmax_out ? sl.amax_idx : nullptr, lp_out ? sl.amax_sum : nullptr);
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
-        HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
+        HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s, nullptr, ban));     // ban (constrained greedy step): the BAN form of the head
     }
     if (argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
@@ -1164,11 +1171,18 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
     // bits -- and measured nothing: 4.926 vs 4.912 ms per 20-token caption; tools/experiments/argmax_fold_rows.txt.)
     bool have_rows = false;                                  // the previous step's arg-max launch embedded this step's input rows
+    // constraints attached: one small launch per step builds the rows' ban mask from the ids so far (prefix 0 .. t, CLS and prompt
+    // included), and the head runs in its BAN form; a position a prompt forces takes the prompt's token whatever is banned
+    const ConsOpt& co = h->cons_cur;
+    const HeadBan bn{cur(h).ban_mask, h->ban_ld};
     for (int t = t_first; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
         const bool next = chain && t + 1 < max_len && t + 1 < h->c.max_text_pos;
+        if (co.on)
+            HIP_OK(h, launch_ban_mask(ids_out, ld, rows, t + 1, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress,
+                                      h->c.vocab_size, cur(h).ban_mask, bn.ld, s));
         const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next,
-                                    lp ? lp + t : nullptr, ld_lp, nullptr, prompt);
+                                    lp ? lp + t : nullptr, ld_lp, nullptr, prompt, co.on ? &bn : nullptr);
         if (rc) return rc;
         have_rows = next;
     }
@@ -1195,7 +1209,8 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
         // positions 0 .. min_len-1 are prompt in every row: one multi-position pass (its arg-max is step min_len-1's), where the
         // slot's row workspace holds B x min_len rows; the token loop goes on behind it.  Steps that write a position below the
         // longest prompt run the forced arg-max.
-        const int P = (g_prompt_prefill && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
+        // (with constraints attached the prompt runs as forced steps: the one-pass plan is not combined with the ban mask)
+        const int P = (g_prompt_prefill && !h->cons_cur.on && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
         int t_first = 0;
         if (P > 1) {
             if (lp.p) HIP_OK(h, hipMemset2DAsync(lp.p, (size_t)lp.ld * 4, 0, (size_t)(P - 1) * 4, B, s));    // forced positions: 0.0f
@@ -1218,6 +1233,23 @@ static PromptArgs take_prompt(gitcap* h) {
     return pr;
 }
 
+// gitcap_attach_constraints' pending attachment: taken like the prompt's.  cons_enter makes it the constraints of the call being
+// issued, or refuses a call whose rows could lose every column: each step bans at most n_suppress listed ids, one id per prefix
+// position and SEP.
+static ConsOpt take_cons(gitcap* h) {
+    const ConsOpt c = h->cons_attach;
+    h->cons_attach = ConsOpt{};
+    h->cons_cur = ConsOpt{};
+    return c;
+}
+static int cons_enter(gitcap* h, const ConsOpt& co, int max_len, int need, const char* who) {
+    if (!co.on) return 0;
+    if ((int64_t)co.n_suppress + max_len + need > h->c.vocab_size)
+        return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)");
+    h->cons_cur = co;
+    return 0;
+}
+
 // The head of every greedy-family entry point: the null check (its message names the entry point), the pending log-probability
 // and prompt attachments are taken (a call refused below has consumed them), device, exchange health, the argument checks; then
 // body(lp, pr).
@@ -1226,14 +1258,18 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_l
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
     const LpAttach lp = take_lp(h);
     const PromptArgs pr = take_prompt(h);
+    const ConsOpt co = take_cons(h);
     GUARD(h);
     POLL(h);
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
     if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "greedy: max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
     if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
-    const int rc = lp_check(h, "greedy", lp, max_len);
-    return rc ? rc : body(lp, pr);
+    int rc = lp_check(h, "greedy", lp, max_len);
+    if (!rc) rc = cons_enter(h, co, max_len, 1, "greedy");
+    if (!rc) rc = body(lp, pr);
+    h->cons_cur = ConsOpt{};
+    return rc;
 }
 
 // synchronous: image pass and token loop on the caller's stream, slot 0 (a raw source is checked by the image pass alone)
@@ -1330,14 +1366,21 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : (ranked ? sl.beam_logits : nullptr);
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
+        // constraints attached: the mask of the B * beams rows, each from the buffer that holds its current prefix
+        const ConsOpt& co = h->cons_cur;
+        const HeadBan bn{sl.ban_mask, h->ban_ld};
+        const HeadBan* ban = co.on ? &bn : nullptr;
+        if (ranked && ban)
+            HIP_OK(h, launch_ban_mask(cur ? sl.beam.ids1 : sl.beam.ids0, L, rows, cur_len, co.ngram, co.min_length, h->c.sep_token_id, co.suppress,
+                                      co.n_suppress, V, sl.ban_mask, bn.ld, s));
         if (!ranked) {
         } else if (so.smp.on)                                                       // model.py:532-554: K draws instead of the K best
             HIP_OK(h, launch_sample_rows(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V,
                                          per_node_beam_size, so.smp.temperature, so.smp.top_k, so.smp.top_p, so.smp.seed, sl.cand_scores,
-                                         sl.cand_idx, nullptr, nullptr, s));
+                                         sl.cand_idx, nullptr, nullptr, s, ban));
         else
             HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
-                                       sl.cand_scores, sl.cand_idx, sl.topk_scratch, s));
+                                       sl.cand_scores, sl.cand_idx, sl.topk_scratch, s, ban));
         HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s,
                                    so.smp.on, prompt));
     }
@@ -1358,6 +1401,7 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
     const SearchOpt so = h->so_attach;
     h->so_attach = SearchOpt{};
     const PromptArgs pr = take_prompt(h);
+    const ConsOpt co = take_cons(h);
     GUARD(h);
     POLL(h);
     if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
@@ -1375,7 +1419,11 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
                       (so.smp.top_k > 0 && std::max(so.smp.top_k, 2) < per_node_beam_size) || per_node_beam_size > h->c.vocab_size))
         return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep");
     if (so.smp.on && h->c.vocab_size > 32768) return fail(h, GITCAP_ERR_ARG, "beam_search: sampling takes a vocabulary of at most 32768 columns");
-    return body(so, pr);
+    // (a beam row must keep at least beams * per_node_beam_size allowed columns: launch_beam_step is never handed a sentinel)
+    int rc = cons_enter(h, co, max_steps, beams * per_node_beam_size, "beam_search");
+    if (!rc) rc = body(so, pr);
+    h->cons_cur = ConsOpt{};
+    return rc;
 }
 
 extern "C" {
@@ -1640,6 +1688,25 @@ int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const i
     return 0;
 }
 
+int gitcap_attach_constraints(gitcap_t* h, const gitcap_constraints* c) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_constraints: null handle");
+    h->cons_attach = ConsOpt{};
+    if (!c) return 0;                                        // detach
+    if (c->no_repeat_ngram_size < 0 || c->min_length < 0 || c->n_suppress < 0) return fail(h, GITCAP_ERR_ARG, "attach_constraints: a negative field");
+    if (c->n_suppress > 256) return fail(h, GITCAP_ERR_ARG, "attach_constraints: n_suppress > 256");
+    if (c->n_suppress > 0 && (!c->suppress || ((uintptr_t)c->suppress & 3) != 0))
+        return fail(h, GITCAP_ERR_ARG, "attach_constraints: n_suppress > 0 with a null or misaligned suppress pointer");
+    if (h->c.vocab_size > 131072) return fail(h, GITCAP_ERR_ARG, "attach_constraints: the ban mask takes a vocabulary of at most 131072 columns");
+    GUARD(h);
+    if (!h->slots[0].ban_mask) {                             // first attach: one mask per pipeline slot, rows x ld (ld even, >= ceil(V / 16))
+        h->ban_ld = (((h->V + 15) / 16) + 1) & ~1;
+        for (auto& sl : h->slots)
+            if (int rc = dev_alloc(h, &sl.ban_mask, (size_t)h->R * (size_t)h->ban_ld)) { h->slots[0].ban_mask = nullptr; return rc; }
+    }
+    h->cons_attach = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
+    return 0;
+}
+
 int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_search_options: null handle");
     const SampleOpt smp = h->so_attach.smp;                  // a pending gitcap_attach_sampling stays pending
@@ -1731,12 +1798,12 @@ int gitcap_preprocess(const uint8_t* frames_hwc_bgr, int nf, int H, int W, float
 
 // no handle here: the scratch of the two-stage top-k is a stream-ordered allocation
 static int beam_topk_hook(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
-                          int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
+                          int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream, const HeadBan* bn = nullptr) {
     if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || K <= 0) return GITCAP_ERR_ARG;
     void* scratch = nullptr;
     hipStream_t s = (hipStream_t)stream;
     if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
-    const hipError_t e = launch_beam_topk(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, out_scores, out_idx, scratch, s);
+    const hipError_t e = launch_beam_topk(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, out_scores, out_idx, scratch, s, bn);
     (void)hipFreeAsync(scratch, s);
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
@@ -1754,14 +1821,54 @@ int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_sc
     return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream);
 }
 
-int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
-                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream) {
+static int sample_rows_hook(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                            float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                            uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream,
+                            const HeadBan* bn) {
     if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || per_node <= 0) return GITCAP_ERR_ARG;
     if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)kept_out & 3) != 0 || ((uintptr_t)logz_out & 3) != 0) return GITCAP_ERR_ARG;
     const hipError_t e = launch_sample_rows(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node,
-                                            temperature, top_k, top_p, seed, out_scores, out_idx, kept_out, logz_out, (hipStream_t)stream);
+                                            temperature, top_k, top_p, seed, out_scores, out_idx, kept_out, logz_out, (hipStream_t)stream, bn);
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
+}
+
+int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream) {
+    return sample_rows_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node, temperature, top_k,
+                            top_p, seed, out_scores, out_idx, kept_out, logz_out, stream, nullptr);
+}
+
+// ---- constrained decoding (tests/test_constraints_gpu.py): each hook is ONE launcher on caller-owned device buffers ----------------
+static bool ban_mask_ok(const uint16_t* mask, int ld_mask, int V) {
+    return mask && ((uintptr_t)mask & 3) == 0 && V > 0 && ld_mask >= (V + 15) / 16 && (ld_mask & 1) == 0;
+}
+
+int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                        const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream) {
+    if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)suppress & 3) != 0) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ban_mask(prefix_ids, ld_ids, rows, cur_len, n, min_length, sep_id, suppress, n_suppress, V, mask_out, ld_mask,
+                                  (hipStream_t)stream));
+}
+
+int gitcap_beam_topk_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                 float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx,
+                                 const uint16_t* mask, int ld_mask, void* stream) {
+    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty) || !ban_mask_ok(mask, ld_mask, V)) return GITCAP_ERR_ARG;
+    if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
+    if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
+    const HeadBan bn{mask, ld_mask};
+    return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream, &bn);
+}
+
+int gitcap_sample_rows_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                   float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                                   uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out,
+                                   const uint16_t* mask, int ld_mask, void* stream) {
+    if (!ban_mask_ok(mask, ld_mask, V)) return GITCAP_ERR_ARG;
+    const HeadBan bn{mask, ld_mask};
+    return sample_rows_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node, temperature, top_k,
+                            top_p, seed, out_scores, out_idx, kept_out, logz_out, stream, &bn);
 }
 
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
@@ -1872,7 +1979,7 @@ int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, 
 // ---- token selection (tests/test_selection_gpu.py): each hook is ONE launcher on caller-owned device buffers --------------
 // launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
 static int dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                          float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
+                          float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream, const HeadBan* bn = nullptr) {
     if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || (amax_val == nullptr) != (amax_idx == nullptr) ||
         (!logits && !amax_val) || (amax_sum && !amax_val))
         return GITCAP_ERR_ARG;
@@ -1880,7 +1987,15 @@ static int dbg_vocab_head(const void* X, int ldx, const void* W, const float* ws
     a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
     a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
     a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
-    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream));
+    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream, nullptr, bn));
+}
+// the BAN forms of the same launch (mask uint16 [M][ld_mask], kernels.h: HeadBan); amax_sum NULL: the plain form, else the LSE form
+int gitcap_dbg_vocab_head_banned(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                 float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const uint16_t* mask, int ld_mask,
+                                 void* stream) {
+    if (!ban_mask_ok(mask, ld_mask, N)) return GITCAP_ERR_ARG;
+    const HeadBan bn{mask, ld_mask};
+    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum, stream, &bn);
 }
 int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
                           float* logits, float* amax_val, int32_t* amax_idx, void* stream) {

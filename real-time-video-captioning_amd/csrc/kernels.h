@@ -104,8 +104,24 @@ bool skinny_row_prologue_ok(int M, int K, bool fp8);         // shapes the row-p
 // j = m % T of id row m / T and its target is ids[(m / T) * ld + j + shift] -- none when j + shift >= T.  The lane that holds that
 // column of row m also stores the fp32 logit to logit[m]; a target outside [0, N) stores nothing.
 struct HeadTargets { const int64_t* ids; int T, ld, shift; float* logit; };
+// Ban mask of the constrained vocabulary head (gitcap_attach_constraints; kernels of their own, skinny.hip "BAN"): uint16
+// [rows][ld], bit c & 15 of word c >> 4 of row m set = column c of head row m is banned; one word = one 16-column tile.
+// ld >= ceil(N / 16) and even (rows 4-byte aligned).  A banned column's logit is -inf before a.out, the arg-max partial and
+// the sum partial are formed.  Built by launch_ban_mask (rowops.hip).
+struct HeadBan { const uint16_t* mask; int ld; };
 // tg (nullable): SK_BIAS_F32 with all three partial buffers set; a.out stays nullable
-hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg = nullptr);
+// bn (nullable; not with tg or a row prologue): SK_BIAS_F32, the BAN form of the head (plain, or with amax_sum the LSE form)
+hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg = nullptr, const HeadBan* bn = nullptr);
+// One workgroup per row builds the row's ban mask from scratch (every word of the row is written: the buffer is reused every
+// step): the union of
+//   n-gram (n >= 1; HF NoRepeatNGramLogitsProcessor): prefix[i + n - 1] for every i in 0 .. cur_len - n whose n - 1 tokens
+//           prefix[i .. i + n - 2] equal the last n - 1 tokens of the prefix (n = 1: every token of the prefix);
+//   length: sep_id while cur_len < min_length (HF MinLengthLogitsProcessor);
+//   suppress: the n_suppress ids of the device list (int32, duplicates allowed).
+// prefix = ids[row * ld_ids + 0 .. cur_len - 1], compared as values; an id outside [0, V) bans nothing.  Bits of the last word
+// beyond V and the words behind ceil(V / 16) are 0.  V <= 131072 (the row's bitmap is built in LDS), n_suppress <= 256.
+hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                           const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s);
 // The vocabulary head's launch_skinny(SK_BIAS_F32) arguments over the bf16 rows xb [rows * T][D] (host only): every position
 // (all_positions) or the last position of every row.  The partial buffers are nullable.  Returns the row stride and offset at
 // which launch_argmax_final finds the last position of each row among the head's rows.
@@ -341,8 +357,11 @@ size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scra
 // rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
 // prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
 // often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
+// bn (nullable): row b * beams + j of the mask bans columns of that beam row before the penalty, the chunk statistics and the
+// chunk's top K (the BAN forms of the chunk kernel, combinable with the penalty): the log-softmax is that of the banned row.
 hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s);
+                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
+                            const HeadBan* bn = nullptr);
 // uint8 HWC BGR frames [nf][H][W][3] -> CLIP-normalised fp32 NCHW [nf][3][crop][crop] (bicubic resize + centre crop)
 hipError_t launch_preprocess(const unsigned char* in, float* out, int nf, int H, int W, int crop, hipStream_t s);
 // the same transform fused with the patch gather: -> bf16 patch rows [nf*G*G][Kp] (layout of launch_im2col)
@@ -374,6 +393,7 @@ hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scor
 // kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
 hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
                               float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
-                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s);
+                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s, const HeadBan* bn = nullptr);
+// (bn, nullable: banned columns are -inf before the penalty, the temperature and the filter -- the BAN form of the kernel)
 hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
                               int64_t* first_decoded, float* first_logprobs, hipStream_t s);

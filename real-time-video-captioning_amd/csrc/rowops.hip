@@ -688,10 +688,17 @@ constexpr int BT_CHUNK = 2048;
 template <bool PEN> struct BeamPenalty {};
 template <> struct BeamPenalty<true> { const int64_t* prefix_ids; int ld_ids, cur_len; float rp; };
 
-template <int KMAX, bool PEN>
+// BAN (constrained decoding; kernels.h: HeadBan): every thread tests the mask bits of its 8 columns -- row `row` of the mask, one
+// uint16 word per 16 columns -- and a banned column is -inf before the penalty (under which -inf stays -inf: the order of the two
+// is immaterial), the chunk statistics and the chunk's top K.  Combinable with PEN; its arguments are empty without it, like the
+// penalty's: the plain instantiations have the test compiled out.
+template <bool BAN> struct BeamBan {};
+template <> struct BeamBan<true> { const uint16_t* mask; int ld; };
+
+template <int KMAX, bool PEN, bool BAN = false>
 __global__ __launch_bounds__(256) void beam_topk_chunks_kernel(const float* __restrict__ logits, int ld, int V, int K, int nch,
                                                                float2* __restrict__ stats, float* __restrict__ cval,
-                                                               int* __restrict__ cidx, BeamPenalty<PEN> pen) {
+                                                               int* __restrict__ cidx, BeamPenalty<PEN> pen, BeamBan<BAN> ban = BeamBan<BAN>{}) {
     __shared__ float red[4];
     __shared__ int redi[4];
     __shared__ unsigned seen[PEN ? BT_CHUNK / 32 : 1];
@@ -717,6 +724,9 @@ __global__ __launch_bounds__(256) void beam_topk_chunks_kernel(const float* __re
         const int rel = q * 256 + tid;
         const int i = c * BT_CHUNK + rel;
         float v = i < V ? src[i] : -INFINITY;
+        if constexpr (BAN) {
+            if (i < V && ((ban.mask[(size_t)row * ban.ld + (i >> 4)] >> (i & 15)) & 1u)) v = -INFINITY;
+        }
         if constexpr (PEN) {
             if ((seen[rel >> 5] >> (rel & 31)) & 1u) v = v < 0.f ? v * pen.rp : v / pen.rp;
         }
@@ -886,9 +896,11 @@ __device__ __forceinline__ unsigned philox4x32_10_lane(unsigned c0, unsigned c1,
 }
 
 // column i of the row as the filter sees it: penalty, temperature, -0 -> +0 (one integer image per value)
+// banrow (BAN form; nullable): the row of the ban mask (kernels.h: HeadBan) -- a banned column is -inf before everything else
 __device__ __forceinline__ float sr_logit(const float* __restrict__ src, int i, const int64_t* __restrict__ pre, int cur_len, float rp,
-                                          float temperature) {
+                                          float temperature, const uint16_t* __restrict__ banrow = nullptr) {
     float v = src[i];
+    if (banrow && ((banrow[i >> 4] >> (i & 15)) & 1u)) v = -INFINITY;
     if (rp != 1.0f) {
         bool hit = false;
         for (int t = 0; t < cur_len; ++t) hit |= pre[t] == (int64_t)i;
@@ -917,13 +929,14 @@ __device__ __forceinline__ void sr_block_sum(SrRed& r, int& phase, float& f, int
     phase ^= 1;
 }
 
+template <bool BAN>
 __global__ __launch_bounds__(SR_THREADS) void sample_rows_kernel(const float* __restrict__ logits, int ld, int V,
                                                                  const float* __restrict__ beam_scores,
                                                                  const int64_t* __restrict__ prefix_ids, int ld_ids, int cur_len, float rp,
                                                                  int beams, int pn, float temperature, int top_k, float top_p,
                                                                  unsigned seed_lo, unsigned seed_hi, float* __restrict__ out_scores,
                                                                  int* __restrict__ out_idx, int* __restrict__ kept_out,
-                                                                 float* __restrict__ logz_out) {
+                                                                 float* __restrict__ logz_out, BeamBan<BAN> ban) {
     extern __shared__ float sr_row[];                                    // [V]: the row, later its keys
     __shared__ SrRed red;
     __shared__ float s_bk[2][SR_WAVES];
@@ -931,10 +944,12 @@ __global__ __launch_bounds__(SR_THREADS) void sample_rows_kernel(const float* __
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* src = logits + (size_t)row * ld;
     const int64_t* pre = rp != 1.0f ? prefix_ids + (size_t)row * ld_ids : nullptr;
+    const uint16_t* banrow = nullptr;                                    // BAN: the bits are tested before temperature and filter
+    if constexpr (BAN) banrow = ban.mask + (size_t)row * ban.ld;
     int phase = 0;
     float m = -INFINITY;
     for (int i = tid; i < V; i += SR_THREADS) {
-        const float v = sr_logit(src, i, pre, cur_len, rp, temperature);
+        const float v = sr_logit(src, i, pre, cur_len, rp, temperature, banrow);
         sr_row[i] = v;
         m = fmaxf(m, v);
     }
@@ -1035,11 +1050,48 @@ __global__ __launch_bounds__(SR_THREADS) void sample_rows_kernel(const float* __
         const bool none = bi == 0x7fffffff;
         if (tid == 0) {
             const int p = j * pn + d;
-            out_scores[(size_t)b * K + p] = none ? -INFINITY : (sr_logit(src, bi, pre, cur_len, rp, temperature) - logZ) + beam_scores[row];
+            out_scores[(size_t)b * K + p] = none ? -INFINITY : (sr_logit(src, bi, pre, cur_len, rp, temperature, banrow) - logZ) + beam_scores[row];
             out_idx[(size_t)b * K + p] = none ? 0x7fffffff : (p % beams) * V + bi;
         }
         if (!none && (bi & (SR_THREADS - 1)) == tid) sr_row[bi] = -INFINITY;    // the owner retires the drawn column
     }
+}
+
+// ---- ban mask of constrained decoding (gitcap_attach_constraints; kernels.h: launch_ban_mask) -------------------------------------
+// One workgroup per row.  The row's bitmap is built in LDS (32-bit words, V <= 131072: 16 KB) -- cleared, a barrier, the three rules
+// set their bits with LDS atomics, a barrier -- and then EVERY 32-bit word of the row's ld_mask / 2 is stored, the ones behind
+// ceil(V / 16) as 0: the result does not depend on what the buffer held (it is reused every step) and needs no global atomic.
+// A uint16 word c >> 4, bit c & 15 of the mask is bit c & 31 of 32-bit word c >> 5 (little endian): the same bytes.
+//   n-gram (n >= 1; HF NoRepeatNGramLogitsProcessor): thread i <= cur_len - n compares prefix[i .. i + n - 2] with the last n - 1
+//           tokens prefix[cur_len - n + 1 .. cur_len - 1] as int64 values and bans prefix[i + n - 1]; nothing while cur_len < n;
+//   length: sep_id while cur_len < min_length (HF MinLengthLogitsProcessor);   suppress: the listed ids.
+// An id outside [0, V) sets no bit, so the bits of the last word beyond V stay 0.
+constexpr int BM_MAX_V = 131072;
+
+__global__ __launch_bounds__(256) void ban_mask_kernel(const int64_t* __restrict__ ids, int ld_ids, int cur_len, int n, int min_length,
+                                                       int sep_id, const int32_t* __restrict__ suppress, int n_suppress, int V,
+                                                       unsigned* __restrict__ mask32, int ld32) {
+    __shared__ unsigned bits[BM_MAX_V / 32];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int nw = (V + 31) >> 5;
+    for (int w = tid; w < nw; w += 256) bits[w] = 0u;
+    __syncthreads();
+    const int64_t* pre = ids + (size_t)row * ld_ids;
+    auto ban = [&](int64_t id) {
+        if (id >= 0 && id < (int64_t)V) atomicOr(&bits[(int)id >> 5], 1u << ((int)id & 31));
+    };
+    if (n >= 1) {
+        for (int i = tid; i <= cur_len - n; i += 256) {
+            bool eq = true;
+            for (int j = 0; j + 1 < n; ++j) eq &= pre[i + j] == pre[cur_len - n + 1 + j];
+            if (eq) ban(pre[i + n - 1]);
+        }
+    }
+    if (tid == 0 && cur_len < min_length) ban((int64_t)sep_id);
+    for (int k = tid; k < n_suppress; k += 256) ban((int64_t)suppress[k]);
+    __syncthreads();
+    unsigned* out = mask32 + (size_t)row * ld32;
+    for (int w = tid; w < ld32; w += 256) out[w] = w < nw ? bits[w] : 0u;
 }
 
 // ---- device-side beam bookkeeping: one step of GeneratorWithBeamSearchV2.search (model.py:573-621) -----
@@ -1489,41 +1541,68 @@ size_t beam_topk_scratch_bytes(int B, int beams, int V, int K) {
 
 template <int KMAX>
 static void beam_topk_launch(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
-                             int B, int beams, int V, int K, int nch, float* out_scores, int* out_idx, void* scratch, hipStream_t s) {
+                             int B, int beams, int V, int K, int nch, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
+                             const HeadBan* bn) {
     const size_t n = (size_t)B * beams * nch;
     float2* stats = (float2*)scratch;
     float* cval = (float*)(stats + n);
     int* cidx = (int*)(cval + n * K);
-    if (rp != 1.0f)
+    if (bn && rp != 1.0f)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
+                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp}, BeamBan<true>{bn->mask, bn->ld});
+    else if (bn)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
+                           BeamPenalty<false>{}, BeamBan<true>{bn->mask, bn->ld});
+    else if (rp != 1.0f)
         hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
-                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp});
+                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp}, BeamBan<false>{});
     else
         hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
-                           BeamPenalty<false>{});
+                           BeamPenalty<false>{}, BeamBan<false>{});
     hipLaunchKernelGGL(beam_topk_merge_kernel<KMAX>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
 }
 
 hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s) {
+                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
+                            const HeadBan* bn) {
     const int nch = (V + BT_CHUNK - 1) / BT_CHUNK;
     if (B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || K > beams * V || nch > 64 || !scratch) return hipErrorInvalidValue;
     // rp == 1: the plain kernel, the prefix is neither checked nor read
     if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
-    if (K <= 8) beam_topk_launch<8>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s);
-    else beam_topk_launch<16>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s);
+    if (bn && (!bn->mask || bn->ld < (V + 15) / 16)) return hipErrorInvalidValue;
+    if (K <= 8) beam_topk_launch<8>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s, bn);
+    else beam_topk_launch<16>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s, bn);
     return hipGetLastError();
 }
 
 hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
                               float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
-                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s) {
+                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s, const HeadBan* bn) {
     if (B <= 0 || beams <= 0 || beams > 16 || pn <= 0 || beams * pn > 16 || pn > V || V > SR_MAX_V || ld < V || cur_len < 0) return hipErrorInvalidValue;
     if (!(temperature > 0.f) || !std::isfinite(temperature) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f)) return hipErrorInvalidValue;
     if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
-    if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel>(SR_MAX_V * 4); e != hipSuccess) return e;
-    hipLaunchKernelGGL(sample_rows_kernel, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids, ld_ids,
+    if (bn) {
+        if (!bn->mask || bn->ld < (V + 15) / 16) return hipErrorInvalidValue;
+        if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel<true>>(SR_MAX_V * 4); e != hipSuccess) return e;
+        hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids,
+                           ld_ids, cur_len, rp, beams, pn, temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), out_scores,
+                           out_idx, kept_out, logz_out, BeamBan<true>{bn->mask, bn->ld});
+        return hipGetLastError();
+    }
+    if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel<false>>(SR_MAX_V * 4); e != hipSuccess) return e;
+    hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids, ld_ids,
                        cur_len, rp, beams, pn, temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), out_scores, out_idx,
-                       kept_out, logz_out);
+                       kept_out, logz_out, BeamBan<false>{});
+    return hipGetLastError();
+}
+
+hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                           const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s) {
+    if (!ids || !mask || rows <= 0 || cur_len < 0 || ld_ids < cur_len || n < 0 || min_length < 0 || n_suppress < 0 || n_suppress > 256 ||
+        (n_suppress > 0 && !suppress) || V <= 0 || V > BM_MAX_V || ld_mask < (V + 15) / 16 || (ld_mask & 1) || ((uintptr_t)mask & 3))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ban_mask_kernel, dim3(rows), dim3(256), 0, s, ids, ld_ids, cur_len, n, min_length, sep_id, suppress, n_suppress, V,
+                       (unsigned*)mask, ld_mask / 2);
     return hipGetLastError();
 }
 

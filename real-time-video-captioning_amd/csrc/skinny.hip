@@ -275,6 +275,49 @@ __global__ __launch_bounds__(64) void skinny_full_score_kernel(SkinnyArgs a, Hea
     }
 }
 
+// The single-wave vocabulary head under a ban mask (gitcap_dbg_config(10, 0), fewer than four tiles, K = 1024): the SK_BIAS_F32 path
+// of skinny_full_kernel with the banned columns of the lane's row written -inf ahead of the epilogue (skinny_head_body's BAN
+// form: same rule, same bits) -- a kernel of its own, as skinny_full_score_kernel.  The row's mask word of this tile is requested
+// ahead of the activation fragments of its m-tile.
+template <int K32, bool FP8, bool LSE>
+__global__ __launch_bounds__(64) void skinny_full_ban_kernel(SkinnyArgs a, HeadBan bn) {
+    const int lane = threadIdx.x;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    bf16x8 wf[K32];
+    load_wfrags<K32, FP8>(a.W, a.Wpk, a.wscale, (size_t)(n0 + frow), a.K, fq * 8, wf);
+    const int n = n0 + fq * 4;
+    float bias[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bias[r] = (a.bias && n + r < a.N) ? a.bias[n + r] : 0.f;
+    const int mtiles = (a.M + 15) >> 4;
+    bf16x8 xnext[K32];
+    unsigned bnext;
+    auto load_x = [&](int mt) {
+        const int m = min(mt * 16 + frow, a.M - 1);
+        bnext = bn.mask[(size_t)m * bn.ld + blockIdx.x];
+        const bf16_t* xp = a.X + (size_t)m * a.ldx + fq * 8;
+#pragma unroll
+        for (int k = 0; k < K32; ++k) xnext[k] = *(const bf16x8*)(xp + k * 32);
+    };
+    load_x(0);
+    for (int mt = 0; mt < mtiles; ++mt) {
+        const int m = mt * 16 + frow;
+        bf16x8 xcur[K32];
+#pragma unroll
+        for (int k = 0; k < K32; ++k) xcur[k] = xnext[k];
+        const unsigned bcur = bnext;
+        if (mt + 1 < mtiles) load_x(mt + 1);
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < K32; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k], xcur[k], acc, 0, 0, 0);
+        float y[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) y[r] = ((bcur >> (fq * 4 + r)) & 1u) ? -INFINITY : acc[r] + bias[r];
+        logits_epilogue<LSE>(a, y, min(m, a.M - 1), m < a.M, n, fq, blockIdx.x, gridDim.x);
+    }
+}
+
 // ---- vocabulary head with shared activation rows ------------------------------------------------------------------------
 // skinny_full with SK_BIAS_F32 runs one single-wave workgroup per 16-column tile and every one of them fetches the same
 // 16 x K activation tile -- at K = 768 as many bytes as the weight tile it owns, 1908 times over for the 30522-word
@@ -283,8 +326,16 @@ __global__ __launch_bounds__(64) void skinny_full_score_kernel(SkinnyArgs a, Hea
 // ds_read_b128 group fall into 16 different 16-byte slots), requested ahead of the weight fragments so that the LDS copy
 // waits for it alone (vmcnt counts in order) while the weights stay in flight; m-tile mt + 1 is in flight under m-tile mt
 // (two LDS images).  Every output element is the same MFMA chain over the same operands as in skinny_full: same bits.
-template <int K32, bool FP8, bool LSE, bool TGT = false>
-__device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int ntiles, const HeadTargets tg = HeadTargets{}) {
+// BAN (constrained decoding; kernels.h: HeadBan): the lane that holds columns n .. n + 3 of row m reads the row's mask word of its
+// tile -- one uint16 = the tile's 16 columns, its bits fq * 4 .. fq * 4 + 3 -- and writes -inf into the banned y[r] before the
+// epilogue forms a.out, the arg-max partial and the sum partial: a banned maximum leaves the runner-up, a wholly banned tile the
+// empty partial (-inf, 0x7fffffff, sum 0).  The edit sits where the reference edits its logits (model.py:522-531, ahead of the
+// log_softmax at :557), so the probabilities renormalise over the allowed columns -- unlike HF's beam search, which masks after
+// normalising.  The word is requested like TGT's target, ahead of the activation rows of its m-tile: the LDS copy's counted wait
+// covers it.  Kernels of their own, picked by the launcher where a mask is attached.
+template <int K32, bool FP8, bool LSE, bool TGT = false, bool BAN = false>
+__device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int ntiles, const HeadTargets tg = HeadTargets{},
+                                                 const HeadBan bn = HeadBan{}) {
     constexpr int PITCH = K32 * 64 + 16, CPR = K32 * 4, NC = (16 * CPR + 255) / 256;     // 16 x CPR 16-byte pieces over 256 threads
     __shared__ __attribute__((aligned(16))) char xs[2][16 * PITCH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -317,6 +368,8 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
     // covers it and leaves the same requests in flight as before
     int64_t tnext = -1;
     if (TGT) tnext = head_target(tg, min(frow, a.M - 1));
+    unsigned bnext = 0u;
+    if (BAN) bnext = bn.mask[(size_t)min(frow, a.M - 1) * bn.ld + tile];
     gload(0);
     bf16x8 wf[K32];
     load_wfrags<K32, FP8>(a.W, a.Wpk, a.wscale, (size_t)(n0 + frow), a.K, fq * 8, wf);
@@ -328,8 +381,10 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
     __syncthreads();
     for (int mt = 0; mt < mtiles; ++mt) {
         const int64_t tcol = tnext;
+        const unsigned bcur = bnext;
         if (mt + 1 < mtiles) {
             if (TGT) tnext = head_target(tg, min((mt + 1) * 16 + frow, a.M - 1));
+            if (BAN) bnext = bn.mask[(size_t)min((mt + 1) * 16 + frow, a.M - 1) * bn.ld + tile];
             gload(mt + 1);
         }
         const char* xb = &xs[mt & 1][frow * PITCH + fq * 16];
@@ -341,6 +396,11 @@ __device__ __forceinline__ void skinny_head_body(const SkinnyArgs a, const int n
         float y[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[r] = acc[r] + bias[r];
+        if (BAN) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((bcur >> (fq * 4 + r)) & 1u) y[r] = -INFINITY;
+        }
         logits_epilogue<LSE, TGT>(a, y, m < a.M ? m : a.M - 1, mvalid, n, fq, tile, ntiles, tcol, tg.logit);
         if (mt + 1 < mtiles) lstore((mt + 1) & 1);              // the image m-tile mt - 1 was read from: every wave is past the
         __syncthreads();                                         // barrier that closed that iteration
@@ -356,6 +416,11 @@ __global__ __launch_bounds__(256) void skinny_head_lse_kernel(SkinnyArgs a, cons
 template <int K32, bool FP8>
 __global__ __launch_bounds__(256) void skinny_head_score_kernel(SkinnyArgs a, const int ntiles, HeadTargets tg) {
     skinny_head_body<K32, FP8, true, true>(a, ntiles, tg);
+}
+// constrained decoding: the plain and the LSE head with the ban mask applied (skinny_head_body<.., BAN = true>)
+template <int K32, bool FP8, bool LSE>
+__global__ __launch_bounds__(256) void skinny_head_ban_kernel(SkinnyArgs a, const int ntiles, HeadBan bn) {
+    skinny_head_body<K32, FP8, LSE, false, true>(a, ntiles, HeadTargets{}, bn);
 }
 
 // ---- two vocabulary heads over the same tile: teacher-student divergence (gitcap_distill) -----------------------------------
@@ -655,17 +720,22 @@ __global__ __launch_bounds__(64) void skinny_splitk_kernel(SkinnyArgs a) {
 }
 
 template <int K32, bool FP8>
-hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg) {
+hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg, const HeadBan* bn) {
     const int grid = (a.N + 15) / 16;
     if (a.ln.kind) return hipErrorInvalidValue;          // row prologue: launch_full_rows
     const bool lse = a.amax_sum != nullptr;              // the third partial of the token log-probabilities: the <.., true> kernels
     if (lse && (epi != SK_BIAS_F32 || !a.amax_val || !a.amax_idx)) return hipErrorInvalidValue;
     // target capture (the scoring pass): kernels of their own, in the two forms of the head
     if (tg && (!lse || !tg->ids || !tg->logit || tg->T <= 0 || tg->ld < tg->T || tg->shift < 0 || a.M % tg->T)) return hipErrorInvalidValue;
+    // ban mask (constrained decoding): kernels of their own, in the two forms of the head, plain or with the third partial
+    if (bn && (tg || epi != SK_BIAS_F32 || !bn->mask || bn->ld < grid || (bn->ld & 1) || ((uintptr_t)bn->mask & 3) || (!a.out && !a.amax_val)))
+        return hipErrorInvalidValue;
     if constexpr (K32 * 64 * 32 + 512 <= 64 * 1024) {          // two LDS images of 16 rows (K <= 768)
         // the vocabulary head (many tiles over few rows): four tiles per workgroup share the activation rows through LDS
         if (epi == SK_BIAS_F32 && g_head_share && grid >= 4 && a.ldx % 8 == 0 && ((uintptr_t)a.X & 15) == 0) {
-            if (tg) hipLaunchKernelGGL((skinny_head_score_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid, *tg);
+            if (bn && lse) hipLaunchKernelGGL((skinny_head_ban_kernel<K32, FP8, true>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid, *bn);
+            else if (bn) hipLaunchKernelGGL((skinny_head_ban_kernel<K32, FP8, false>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid, *bn);
+            else if (tg) hipLaunchKernelGGL((skinny_head_score_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid, *tg);
             else if (lse) hipLaunchKernelGGL((skinny_head_lse_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
             else hipLaunchKernelGGL((skinny_head_kernel<K32, FP8>), dim3((grid + 3) / 4), dim3(256), 0, s, a, grid);
             return hipGetLastError();
@@ -676,7 +746,9 @@ hipError_t launch_full(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTa
         case SK_BIAS_GELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_GELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_RELU_BF16: hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_RELU_BF16, FP8, false>), dim3(grid), dim3(64), 0, s, a); break;
         case SK_BIAS_F32:
-            if (tg) hipLaunchKernelGGL((skinny_full_score_kernel<K32, FP8>), dim3(grid), dim3(64), 0, s, a, *tg);
+            if (bn && lse) hipLaunchKernelGGL((skinny_full_ban_kernel<K32, FP8, true>), dim3(grid), dim3(64), 0, s, a, *bn);
+            else if (bn) hipLaunchKernelGGL((skinny_full_ban_kernel<K32, FP8, false>), dim3(grid), dim3(64), 0, s, a, *bn);
+            else if (tg) hipLaunchKernelGGL((skinny_full_score_kernel<K32, FP8>), dim3(grid), dim3(64), 0, s, a, *tg);
             else if (lse) hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, true>), dim3(grid), dim3(64), 0, s, a);
             else hipLaunchKernelGGL((skinny_full_kernel<K32, SK_BIAS_F32, FP8, false, false>), dim3(grid), dim3(64), 0, s, a);
             break;
@@ -717,26 +789,26 @@ bool skinny_full_ok(int K) {
 
 bool skinny_row_prologue_ok(int M, int K, bool fp8) { return M >= 1 && M <= 2 && (K == 64 || K == 128 || K == 576 || K == 768) && !fp8; }
 
-hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg) {
+hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg, const HeadBan* bn) {
     if (a.K % 32 || a.M <= 0 || a.T <= 0) return hipErrorInvalidValue;
-    if (tg && (a.ln.kind || epi != SK_BIAS_F32)) return hipErrorInvalidValue;
+    if ((tg || bn) && (a.ln.kind || epi != SK_BIAS_F32)) return hipErrorInvalidValue;
     if (a.ln.kind)
         return a.K == 64 ? launch_full_rows<2>(a, epi, s) : a.K == 128 ? launch_full_rows<4>(a, epi, s)
              : a.K == 576 ? launch_full_rows<18>(a, epi, s) : launch_full_rows<24>(a, epi, s);
     if (a.wscale) {                                     // e4m3 weights (GIT decoder widths only)
         switch (a.K / 32) {
-            case 4: return launch_full<4, true>(a, epi, s, tg);
-            case 24: return launch_full<24, true>(a, epi, s, tg);
+            case 4: return launch_full<4, true>(a, epi, s, tg, bn);
+            case 24: return launch_full<24, true>(a, epi, s, tg, bn);
         }
         return hipErrorInvalidValue;
     }
     switch (a.K / 32) {
-        case 2: return launch_full<2, false>(a, epi, s, tg);      // K = 64  (tiny student test config)
-        case 4: return launch_full<4, false>(a, epi, s, tg);      // K = 128 (tiny test config)
-        case 8: return launch_full<8, false>(a, epi, s, tg);      // K = 256
-        case 18: return launch_full<18, false>(a, epi, s, tg);    // K = 576 (student decoder)
-        case 24: return launch_full<24, false>(a, epi, s, tg);    // K = 768
-        case 32: return launch_full<32, false>(a, epi, s, tg);    // K = 1024
+        case 2: return launch_full<2, false>(a, epi, s, tg, bn);      // K = 64  (tiny student test config)
+        case 4: return launch_full<4, false>(a, epi, s, tg, bn);      // K = 128 (tiny test config)
+        case 8: return launch_full<8, false>(a, epi, s, tg, bn);      // K = 256
+        case 18: return launch_full<18, false>(a, epi, s, tg, bn);    // K = 576 (student decoder)
+        case 24: return launch_full<24, false>(a, epi, s, tg, bn);    // K = 768
+        case 32: return launch_full<32, false>(a, epi, s, tg, bn);    // K = 1024
     }
     return hipErrorInvalidValue;
 }

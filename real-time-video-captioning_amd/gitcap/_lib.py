@@ -40,6 +40,11 @@ class CSamplingOptions(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int32), ("top_p", c_float), ("seed", ctypes.c_uint64)]
 
 
+class CConstraints(ctypes.Structure):
+    """struct gitcap_constraints (include/gitcap.h)."""
+    _fields_ = [("no_repeat_ngram_size", c_int32), ("min_length", c_int32), ("suppress", c_void_p), ("n_suppress", c_int32)]
+
+
 class CDistillOut(ctypes.Structure):
     """struct gitcap_distill_out (include/gitcap.h)."""
     _fields_ = [("kl", c_void_p), ("ld_kl", c_int32), ("teacher_top1", c_void_p), ("student_top1", c_void_p), ("agree", c_void_p),
@@ -204,6 +209,16 @@ SYMBOLS = {
                                                c_void_p]),
     "gitcap_dbg_beam_step_forced": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_float, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    # constrained decoding: n-gram, length and token bans (tests/test_constraints_gpu.py)
+    "gitcap_attach_constraints": (c_int, [c_void_p, POINTER(CConstraints)]),
+    "gitcap_dbg_ban_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_vocab_head_banned": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_beam_topk_constrained": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_sample_rows_constrained": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_float,
+                                               c_int32, c_float, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                               c_void_p]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),

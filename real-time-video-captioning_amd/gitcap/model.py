@@ -173,6 +173,21 @@ class _Prompt:
         model._call("gitcap_attach_prompt", _lib.ptr(self.ids), self.ids.shape[1], _lib.ptr(self.lengths), self.min_len, self.max_len)
 
 
+class _Constraints:
+    """Hard constraints of a decoding call on the device (include/gitcap.h: gitcap_attach_constraints): the n-gram size, the
+    minimum length and the suppress list as a device int32 tensor (held until the result: a submission reads it)."""
+
+    def __init__(self, model, n, min_length, suppress):
+        self.n, self.min_length, self.suppress = n, min_length, tuple(suppress)
+        self.key = (n, min_length, self.suppress)
+        self._ids = torch.tensor(suppress, dtype=torch.int32, device=model._dev) if suppress else None
+        self._c = _lib.CConstraints(n, min_length, None if self._ids is None else self._ids.data_ptr(), len(suppress))
+
+    def attach(self, model):
+        """The one-shot attachment the NEXT greedy- or beam-family call consumes (a repeated call attaches again)."""
+        model._call("gitcap_attach_constraints", ctypes.byref(self._c))
+
+
 def _lp2d(logprobs):
     """The search's scores as the reference returns them, [B, num_keep_best] (the one-hypothesis call writes [B])."""
     return logprobs[:, None] if logprobs.dim() == 1 else logprobs
@@ -208,6 +223,7 @@ class CaptionFuture(_Future):
         self._sub, self._r0, self._r1 = None, 0, 0
         self._done = None
         self._prompt = None                      # greedy_decode_async(prompt=...): held until the result (the device reads it)
+        self._cons = None                        # _Constraints | None, held likewise
 
     def _attach(self, sub, r0, r1):
         self._sub, self._r0, self._r1 = sub, r0, r1
@@ -234,7 +250,7 @@ class CaptionFuture(_Future):
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         def rerun():
-            ids = m._greedy_decode(sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._prompt)
+            ids = m._greedy_decode(sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._prompt, self._cons)
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         synced = self._mode == STOP_ALL_SEP or self._out_device.type == "cpu"
@@ -283,7 +299,8 @@ class CaptionStream(_WindowStream):
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None):
+                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None):
+        self._cons = constraints         # _Constraints | None: attached again for every caption
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
         self._nbest, self._rp = int(num_keep_best), float(repetition_penalty)
         self._sampling = sampling        # (temperature, top_k, top_p, seed | None) of a do_sample stream
@@ -369,6 +386,8 @@ class CaptionStream(_WindowStream):
                     m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), self._max_len)
                 if self._prompt is not None:
                     self._prompt.attach(m)
+                if self._cons is not None:
+                    self._cons.attach(m)
                 m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
                 decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
@@ -378,6 +397,8 @@ class CaptionStream(_WindowStream):
                 attach()                         # one-shot: consumed by the search below (a repeated caption attaches again)
                 if self._prompt is not None:
                     self._prompt.attach(m)
+                if self._cons is not None:
+                    self._cons.attach(m)
                 m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
                         _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
                 if nbest is not None:
@@ -641,6 +662,17 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"expected uint8 frames [B,F,H,W,3], got {x.dtype}")
         return self._to_device(x)
 
+    def _constraints(self, no_repeat_ngram_size, min_length, suppress_tokens, max_len, need=1):
+        """The constraint arguments of the decoding calls -> _Constraints or None (the defaults: nothing is attached).  ValueError
+        for what the library would refuse (include/gitcap.h: gitcap_attach_constraints), before anything is launched."""
+        from .search import check_constraints
+        n, m, sup = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
+        if not (n or m or sup):
+            return None
+        if len(sup) + max_len + need > self.cfg.vocab_size:
+            raise ValueError(f"{len(sup)} suppressed ids over {max_len} steps could ban every column of a row (vocab_size {self.cfg.vocab_size})")
+        return _Constraints(self, n, m, sup)
+
     def _prompt(self, prompt, prompt_lengths, B, limit, what):
         """The ``prompt=`` argument of the decoding calls -> _Prompt or None.  prompt: int64 [B, P] (every row P tokens, or
         ``prompt_lengths`` [B] valid tokens per row) or a list of B 1-D tensors (ragged).  CLS is prepended to a row that does not
@@ -881,7 +913,7 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
-                      prompt=None, prompt_lengths=None):
+                      prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
@@ -892,17 +924,24 @@ class GitCaptioner(_NativeModule):
         gitcap_attach_prompt): int64 [B, P], optionally with prompt_lengths [B], or a list of B 1-D tensors of different lengths;
         CLS is prepended where a row does not start with it.  The ids returned INCLUDE each row's prompt (columns
         0 .. its length - 1; the reference strips its single prefix, :455, which a ragged batch cannot do); prompt tokens do not
-        count for stop='all_sep', and their logprobs columns are 0."""
+        count for stop='all_sep', and their logprobs columns are 0.
+        no_repeat_ngram_size / min_length / suppress_tokens: hard constraints on what a step may emit (include/gitcap.h:
+        gitcap_attach_constraints; HF's NoRepeatNGram / MinLength / SuppressTokens processors): no n-gram of the row so far (CLS
+        and prompt included) may recur, SEP is banned while the row holds fewer than min_length tokens, the listed ids (a sequence
+        or an int tensor, at most 256) are never emitted.  A banned column is -inf inside the vocabulary head, so the logprobs
+        are those of the row renormalised over the allowed columns; a token a prompt forces is emitted even when banned.  With
+        the defaults nothing is attached."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
         pr = self._prompt(prompt, prompt_lengths, src.shape[0], max_len, "max_len")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
         if src.device.type == "cpu":              # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs, pr)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr, co))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, pr, co)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None):
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None, co=None):
         self._drain()
         fr, raw = self._check_frames(src)         # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
         B, F = fr.shape[:2]
@@ -918,6 +957,8 @@ class GitCaptioner(_NativeModule):
                 if pr is not None:               # one-shot as well
                     part = pr if B <= self.max_batch else pr.rows(b0, b0 + chunk.shape[0])
                     part.attach(self)
+                if co is not None:               # one-shot as well
+                    co.attach(self)
                 if raw:
                     self._call("gitcap_greedy_raw", _lib.ptr(chunk), chunk.shape[0], F, chunk.shape[2], chunk.shape[3], max_len, mode,
                                _lib.ptr(ids), _lib.ptr(steps), self._stream())
@@ -946,7 +987,8 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode_async(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
-                            coalesce: int = 1, prompt=None, prompt_lengths=None) -> "CaptionFuture":
+                            coalesce: int = 1, prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                            suppress_tokens=None) -> "CaptionFuture":
         """Pipelined greedy_decode for a stream of batches: returns immediately with a future; up to
         FOUR submissions may be in flight, so one batch's image pass (MFMA bound) overlaps the token
         loops (latency bound) of the batches before it on the handle's internal HIP streams.  Call
@@ -962,7 +1004,8 @@ class GitCaptioner(_NativeModule):
         run as ONE pass of k*B clips (the per-clip results are bitwise the same: the kernels are batch
         invariant); a ``result()`` on a batch that is still waiting for partners flushes it.  Needs
         max_batch >= k*B.  ``prompt`` / ``prompt_lengths`` as in greedy_decode; a prompted batch is submitted on its own (it does
-        not coalesce)."""
+        not coalesce).  no_repeat_ngram_size / min_length / suppress_tokens as in greedy_decode; a constrained batch coalesces
+        only with batches that carry equal constraints."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
@@ -977,7 +1020,8 @@ class GitCaptioner(_NativeModule):
         pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
         fut = CaptionFuture(self, fr, mode, max_len, src.device)
         fut._prompt = pr
-        key = (tuple(fr.shape), max_len, mode, raw, host, None if pr is None else id(pr))
+        fut._cons = co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+        key = (tuple(fr.shape), max_len, mode, raw, host, None if pr is None else id(pr), None if co is None else co.key)
         if pr is not None:
             coalesce = 1
         if self._pending and self._pending_key != key:
@@ -1017,7 +1061,14 @@ class GitCaptioner(_NativeModule):
             ticket = ctypes.c_int(-1)
             stop = STOP_NEVER if len(group) > 1 else mode       # the stop rule is per caller batch: applied in result()
             pr = group[0]._prompt                # (a prompted batch is a group of one)
-            before = None if pr is None else (lambda: pr.attach(self))
+            co = group[0]._cons                  # (every batch of a group carries equal constraints: the key holds them)
+            before = None
+            if pr is not None or co is not None:
+                def before():
+                    if pr is not None:
+                        pr.attach(self)
+                    if co is not None:
+                        co.attach(self)
             if raw:
                 self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, F, frames.shape[2], frames.shape[3], max_len, stop,
                              _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket), before=before)
@@ -1052,7 +1103,7 @@ class GitCaptioner(_NativeModule):
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
               on_device: Optional[bool] = None, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
               top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-              prompt_lengths=None) -> dict:
+              prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
         reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
@@ -1077,7 +1128,11 @@ class GitCaptioner(_NativeModule):
         gains ``prompt_lengths`` [B] (CLS included), so a caller can strip what the reference strips at :455 -- the one deliberate
         difference: the reference returns predictions with its single prefix removed, which a ragged batch cannot do.
         on_device=False takes the reference's own route: the host operator clip by clip with start_predictions = the clip's prompt
-        (the batch-of-one form of :436-437)."""
+        (the batch-of-one form of :436-437).
+        no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): every beam row's banned columns are -inf before
+        the step ranks or samples, ahead of the log-softmax (where the reference edits its logits, :522-531), so the scores
+        renormalise over the allowed columns -- unlike HF's beam search, which masks after normalising.  min_length counts CLS and
+        the prompt.  on_device=False applies the same rules in the host operator, on the raw logits next to its penalty."""
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
@@ -1094,13 +1149,14 @@ class GitCaptioner(_NativeModule):
                          and per_node_beam_size >= 2)
         sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
         pr = self._prompt(prompt, prompt_lengths, B, max_steps - 1, "max_steps - 1")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps, beam_size * per_node_beam_size)
         if on_device:
             self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
             decoded, logprobs, steps, vis = self._infer_device(fr, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
                                                                per_node_beam_size=per_node_beam_size, sync=True,
                                                                save_logits=save_logits, want_visual=False, raw=raw,
                                                                num_keep_best=num_keep_best, repetition_penalty=repetition_penalty,
-                                                               sampling=sampling, prompt=pr)
+                                                               sampling=sampling, prompt=pr, constraints=co)
             out = {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
                    "visual_features": None}
             if sampling is not None:
@@ -1109,7 +1165,9 @@ class GitCaptioner(_NativeModule):
                 out["prompt_lengths"] = pr.lengths
             return out
         searcher = GeneratorWithBeamSearch(self.sep_token_id, max_steps, beam_size, per_node_beam_size, length_penalty,
-                                           repetition_penalty=repetition_penalty, temperature=temperature)
+                                           repetition_penalty=repetition_penalty, temperature=temperature,
+                                           no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length,
+                                           suppress_tokens=suppress_tokens)
         if pr is not None:
             return self._infer_host_prompted(fr, pr, searcher, beam_size, num_keep_best, save_logits, sampling, top_k, top_p)
         _, vis = self.forward_image_enc(fr)
@@ -1227,7 +1285,7 @@ class GitCaptioner(_NativeModule):
         return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
 
     def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None):
+                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None):
         """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
         stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
         the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
@@ -1238,12 +1296,15 @@ class GitCaptioner(_NativeModule):
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
         attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty, sampling)
-        if prompt is not None:                   # one-shot beside the options: every issue of the call attaches both
+        if prompt is not None or constraints is not None:    # one-shot beside the options: every issue of the call attaches all
             attach_options = attach
 
             def attach():
                 attach_options()
-                prompt.attach(self)
+                if prompt is not None:
+                    prompt.attach(self)
+                if constraints is not None:
+                    constraints.attach(self)
         first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
         if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
             first, decoded, logprobs = rank0, nbest, nbest_lp
@@ -1277,14 +1338,15 @@ class GitCaptioner(_NativeModule):
                     per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False,
                     num_keep_best: int = 1, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                     top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-                    prompt_lengths=None) -> "InferFuture":
+                    prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
         tensor [max_steps - 1, B * beam_size, V] (the raw logits of every step, model.py:521), with ``visual_features`` the fp32
         features [B, F*N, Dv] (model.py:460); num_keep_best / repetition_penalty as in ``infer``.  Results are bitwise those of the
         synchronous call, with do_sample too (its arguments as in ``infer``; the seed is fixed at submission and returned as
-        ``seed``) and with prompt / prompt_lengths (as in ``infer``; the dict gains ``prompt_lengths``).  `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
+        ``seed``) and with prompt / prompt_lengths (as in ``infer``; the dict gains ``prompt_lengths``) and with no_repeat_ngram_size / min_length / suppress_tokens (as in ``infer``).
+        `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
         sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
         self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
         if beam_size > self.max_beams:
@@ -1298,7 +1360,9 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
         kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
                   num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling,
-                  prompt=self._prompt(prompt, prompt_lengths, fr.shape[0], max_steps - 1, "max_steps - 1"))
+                  prompt=self._prompt(prompt, prompt_lengths, fr.shape[0], max_steps - 1, "max_steps - 1"),
+                  constraints=self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps,
+                                                beam_size * per_node_beam_size))
         parts = entry = stream = None
         if fr.device.type == "cpu":
             while len(self._inflight) >= 4:      # (before the staging: the entry about to be reused belongs to the oldest)
@@ -1321,7 +1385,7 @@ class GitCaptioner(_NativeModule):
                        visual_features: bool = False, gate=None, logprobs: bool = False, num_keep_best: int = 1,
                        repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                        top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-                       prompt_lengths=None) -> CaptionStream:
+                       prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1333,7 +1397,8 @@ class GitCaptioner(_NativeModule):
         return_logprobs; gitcap.caption_confidence turns them into one number per clip).  do_sample / top_k / top_p / temperature /
         seed (beam streams only) as in infer: every caption samples with `seed` (seed=None: a fresh one per caption from torch's
         global CPU generator); ``stream.last_seed`` is the seed of the caption the last push returned.  prompt / prompt_lengths (as
-        in greedy_decode / infer): the stream's prompt, one row per clip, attached again for every caption."""
+        in greedy_decode / infer): the stream's prompt, one row per clip, attached again for every caption.  no_repeat_ngram_size /
+        min_length / suppress_tokens (as in greedy_decode / infer): the stream's constraints, attached again for every caption."""
         if logprobs and beam_size is not None:
             raise ValueError("logprobs=True is for greedy streams (the beam-search dict carries its own sequence score)")
         window = int(window or max(1, self.cfg.num_frames))
@@ -1362,9 +1427,11 @@ class GitCaptioner(_NativeModule):
             gate.reset()
         pr = self._prompt(prompt, prompt_lengths, batch, max_len if beam_size is None else max_len - 1,
                           "max_len" if beam_size is None else "max_len - 1")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len,
+                               1 if beam_size is None else beam_size * per_node_beam_size)
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
                              logprobs, num_keep_best, repetition_penalty,
-                             sampling, pr)
+                             sampling, pr, co)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip

@@ -52,11 +52,48 @@ class _Hyps:
         return self.worst >= best_sum_logprobs / self.max_length ** self.length_penalty
 
 
+def check_constraints(no_repeat_ngram_size, min_length, suppress_tokens):
+    """The constraint arguments of the public calls -> (n, min_length, suppress list); ValueError for what
+    gitcap_attach_constraints refuses (include/gitcap.h)."""
+    n, m = int(no_repeat_ngram_size), int(min_length)
+    if suppress_tokens is None:
+        sup = []
+    elif isinstance(suppress_tokens, torch.Tensor):
+        if suppress_tokens.dtype.is_floating_point or suppress_tokens.dtype == torch.bool:
+            raise ValueError("suppress_tokens must be a sequence of ints or an int tensor")
+        sup = [int(v) for v in suppress_tokens.detach().reshape(-1).tolist()]
+    else:
+        sup = [int(v) for v in suppress_tokens]
+    if n < 0 or m < 0:
+        raise ValueError(f"no_repeat_ngram_size / min_length must be >= 0, got {n} / {m}")
+    if len(sup) > 256:
+        raise ValueError(f"suppress_tokens holds {len(sup)} ids; at most 256")
+    return n, m, sup
+
+
+def banned_tokens(prefix: List[int], n: int, min_length: int, sep_id: int, suppress, V: int) -> List[int]:
+    """The columns a step may not emit after `prefix` (CLS and prompt included): the three rules of gitcap_attach_constraints
+    (include/gitcap.h), i.e. HF's NoRepeatNGram / MinLength / SuppressTokens processors.  Ids outside [0, V) ban nothing."""
+    L, out = len(prefix), set()
+    if n >= 1:
+        tail = prefix[L - n + 1:] if n > 1 else []
+        for i in range(0, L - n + 1):
+            if prefix[i:i + n - 1] == tail:
+                out.add(prefix[i + n - 1])
+    if L < min_length:
+        out.add(sep_id)
+    out.update(suppress)
+    return sorted(c for c in out if 0 <= c < V)
+
+
 class GeneratorWithBeamSearch:
     def __init__(self, eos_index: int, max_steps: int, beam_size: int, per_node_beam_size: int = 2,
-                 length_penalty: float = 1.0, repetition_penalty: float = 1.0, temperature: float = 1.0):
+                 length_penalty: float = 1.0, repetition_penalty: float = 1.0, temperature: float = 1.0,
+                 no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None):
         if beam_size * per_node_beam_size > 16:
             raise ValueError("beam_size * per_node_beam_size must be <= 16")
+        # hard constraints (include/gitcap.h: gitcap_attach_constraints), applied to the raw logits next to the penalty
+        self.ngram, self.min_length, self.suppress = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
         self._eos_index, self.max_steps, self.beam_size = eos_index, max_steps, beam_size
         self.per_node_beam_size, self.length_penalty = per_node_beam_size, length_penalty
         self.repetition_penalty, self.temperature = float(repetition_penalty), float(temperature)
@@ -136,6 +173,12 @@ class GeneratorWithBeamSearch:
             V = logits.shape[-1]
             if save_logits:
                 saved.append(logits.detach().float().cpu().numpy())               # model.py:521
+            if self.ngram or self.min_length or self.suppress:                      # banned columns are -inf before anything ranks
+                logits = logits.float().clone()
+                for r, prefix in enumerate(ids_host.tolist()):
+                    cols = banned_tokens(prefix, self.ngram, self.min_length, eos, self.suppress, V)
+                    if cols:
+                        logits[r, cols] = float("-inf")
             if self.repetition_penalty != 1.0:                                      # model.py:522-531
                 logits = logits.float().clone()
                 prev = torch.gather(logits, 1, ids)
