@@ -374,6 +374,27 @@ int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream)
  * attachment is consumed all the same).  A handle that never attaches runs exactly the launches it ran before. */
 int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len);
 
+/* Per-clip frame counts: a batch whose clips differ in length, packed -- no padding, no masking.
+ *   counts   HOST int32 [B] (copied by the call): clip b has counts[b] frames, 1 <= counts[b] <= min(max_frames, num_frames when
+ *            the model has temporal embeddings, 255); B <= min(max_batch, 256).
+ * A ONE-SHOT attachment with the life cycle of gitcap_attach_prompt: the next call of gitcap_encode, gitcap_encode_raw, the greedy
+ * family or the beam family (their _submit / _raw_submit forms included) consumes it, whether that call succeeds or is refused;
+ * NULL detaches.  In the consuming call `frames` holds the sum(counts) frames clip-major (clip b's frames adjacent), B is the
+ * attachment's B and F the largest count; visual_out receives the packed rows [sum(counts) * N][enc_width].  It combines with the
+ * log-probability, prompt, constraint, search-option and sampling attachments.
+ * Layout: clip b's image rows -- encoder output, decoder input, the per-layer image K/V and the opt-in e4m3 V codes and scales --
+ * start at off[b] = N * sum_{i<b} counts[i] and number len[b] = N * counts[b]; off / len live in the pipeline slot as device
+ * int32 arrays.  Every GEMM sees the N * sum(counts) valid rows; the decoder's image-prefix attention and the text rows' attention
+ * run their variable-length forms; the temporal embedding is added by a row kernel from a per-frame position table (the fp32 add
+ * of the fused epilogue).  A clip inside a ragged batch is bit for bit the clip captioned alone.  Later calls that read the
+ * slot's image prefix (gitcap_text_forward, gitcap_score, gitcap_distill, gitcap_reorder_rows, the token loops) follow the slot's
+ * tables.  Equal counts take the dense path, launch for launch.
+ * Errors, all GITCAP_ERR_ARG with a last_error text: a count of 0 or above the limit, B outside its range, a sum beyond
+ * max_batch * max_frames (at the attach); B or F that disagree with the counts (at the consuming call); gitcap_set_visual and the
+ * window family (gitcap_window_reset / _push / _push_raw / _greedy / _beam_search) with counts attached (the attachment is
+ * consumed); gitcap_hidden_states_read while slot 0 holds a ragged prefix. */
+int gitcap_attach_frame_counts(gitcap_t* h, const int32_t* counts, int B);
+
 /* Constrained decoding: hard limits on what a step may emit.  Before a step ranks, arg-maxes or samples row r, every banned column
  * of that row is -inf, and everything downstream sees the banned row: the head's tile partials, the chunk statistics, the
  * log-softmax, the top-k / top-p filter, the token log-probabilities.  The edit sits where the reference edits its logits
@@ -595,6 +616,10 @@ int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const fl
 int gitcap_dbg_config(int key, int value);
 /* attn_full: qkv [G*S][3*H*64] bf16 -> ctx [G*S][H*64] bf16 */
 int gitcap_dbg_attn_full(const void* qkv, void* ctx, int G, int S, int H, void* stream);
+/* attn_full, variable-length form (a ragged batch's image prefix): group g = rows off[g] .. off[g] + len[g] - 1 of the packed qkv /
+ * ctx; off, len device int32 [G], len[g] >= 1 (the hook drains the stream and reads them to size the grid).  Each group's rows are
+ * bit for bit gitcap_dbg_attn_full(G = 1, S = len[g]) on the group alone; no other row of ctx is written. */
+int gitcap_dbg_attn_full_varlen(const void* qkv, void* ctx, int G, const int32_t* off, const int32_t* len, int H, void* stream);
 /* layernorm: x fp32 [rows][D] -> out_f32 / out_bf16 (either may be NULL) */
 int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, float eps, int rows, int D,
                          float* out_f32, void* out_bf16, void* stream);
@@ -790,6 +815,10 @@ typedef struct gitcap_dbg_txt_block_args {
     int32_t nt_kv;
 } gitcap_dbg_txt_block_args;
 int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* a, void* stream);
+/* txt_block, variable-length form: clip c = row / beams has its image keys at rows off[c] .. off[c] + len[c] - 1 of the packed
+ * kv_img (and of v8_img / vs_img); off, len device int32 [ceil(rows / beams)]; S_img is not read.  A row's outputs are bit for bit
+ * gitcap_dbg_txt_block's with S_img = len[c] on that clip's keys. */
+int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* a, const int32_t* off, const int32_t* len, void* stream);
 
 /* The TinyViT encoder's kernels (csrc/tinyvit.hip) and the student decoder's attention (csrc/student.hip), one kernel per hook on
  * caller-owned device buffers (tests/test_encoder_kernels_gpu.py; a plain fp64 statement of each: tests/encoder_kernels_reference.py).

@@ -33,9 +33,13 @@ __device__ unsigned long long* g_attn_stamps;
 #define ATTN_STAMP(i) do {} while (0)
 #endif
 
-template <int NST>
+// VL (variable-length form, launch_attn_full_varlen): group g is the rows off[g] .. off[g] + len[g] - 1 of the packed qkv / ctx
+// and runs with S = len[g] -- its own tile count and last-tile form, so its bits are those of the plain kernel on that group
+// alone; S_arg sized the grid (nqb q-blocks per (group, head), the longest group's).
+template <int NST, bool VL = false>
 __global__ __launch_bounds__(256) void attn_full_kernel(const bf16_t* __restrict__ qkv,
-                                                        bf16_t* __restrict__ ctx, int S, int H, int G, int nqb) {
+                                                        bf16_t* __restrict__ ctx, int S_arg, int H, int G, int nqb,
+                                                        const int* __restrict__ off = nullptr, const int* __restrict__ len = nullptr) {
     __shared__ __attribute__((aligned(16))) char lds[NST * 16384];   // per stage: K 8 KiB | V 8 KiB
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -57,7 +61,15 @@ __global__ __launch_bounds__(256) void attn_full_kernel(const bf16_t* __restrict
     }
     const int head = pair % H, grp = pair / H;
     const int W = H * 64, ld = 3 * W;
-    const size_t row0 = (size_t)grp * S;
+    int S = S_arg;
+    size_t row0;
+    if constexpr (VL) {
+        S = len[grp];                                // workgroup-uniform (scalar loads)
+        row0 = (size_t)off[grp];
+        if (qb * 128 >= S) return;                   // a shorter group's spare q-blocks: the whole workgroup, before any DMA or barrier
+    } else {
+        row0 = (size_t)grp * S;
+    }
     const bf16_t* qbase = qkv + row0 * ld + head * 64;
     const bf16_t* kbase = qbase + W;
     const bf16_t* vbase = qbase + 2 * W;
@@ -262,6 +274,13 @@ __global__ __launch_bounds__(256) void attn_full_kernel(const bf16_t* __restrict
 }
 
 }  // namespace
+
+hipError_t launch_attn_full_varlen(const bf16_t* qkv, bf16_t* ctx, int G, const int* off, const int* len, int S_max, int H, hipStream_t s) {
+    if (G <= 0 || S_max <= 0 || H <= 0 || !off || !len) return hipErrorInvalidValue;
+    const int nqb = (S_max + 127) / 128;
+    hipLaunchKernelGGL((attn_full_kernel<2, true>), dim3(nqb * H * G), dim3(256), 0, s, qkv, ctx, S_max, H, G, nqb, off, len);
+    return hipGetLastError();
+}
 
 hipError_t launch_attn_full(const bf16_t* qkv, bf16_t* ctx, int G, int S, int H, hipStream_t s) {
     if (G <= 0 || S <= 0 || H <= 0) return hipErrorInvalidValue;

@@ -150,6 +150,12 @@ struct gitcap : HandleCore {
         // allocated by the first gitcap_attach_search_options that asks for more than one
         int64_t* nb_ids = nullptr; float* nb_score = nullptr; int32_t* nb_len = nullptr;
         int B = 0, S = 0;                   // clips and image rows per clip of the image prefix the slot holds (have: it holds one)
+        // ragged (gitcap_attach_frame_counts): clip b's image rows are off[b] .. off[b] + len[b] - 1 of the packed rows (device
+        // int32 [max_batch]), S is the largest len[b]; fpos [max_batch * max_frames] = each packed frame's index inside its clip.
+        // S_tot = the image rows the slot holds, B * S of a dense prefix.
+        int32_t *off = nullptr, *len = nullptr, *fpos = nullptr;
+        int S_tot = 0;
+        bool ragged = false;
         bool have = false, used = false;
         int Mt = 0;             // text rows (rows x positions) the slot's row workspace holds
         hipEvent_t ev_in = nullptr, ev_enc = nullptr, ev_dec = nullptr;
@@ -174,6 +180,9 @@ struct gitcap : HandleCore {
     // cons_cur: the constraints of the call whose launches are being issued (as cur_slot / pipelined); ban_ld: words per mask row
     ConsOpt cons_attach{}, cons_cur{};
     int ban_ld = 0;
+    // gitcap_attach_frame_counts: the pending one-shot attachment (B == 0: none); taken by the next call that runs an image pass.
+    // fc_cur: the counts of the call whose image pass is being issued (as cons_cur)
+    RaggedCounts fc_attach{}, fc_cur{};
 
     // gitcap_distill (first use): the dual head's seven partials [slot 0's Mt][ntiles], both models' target logits
     // ([2][Mt])
@@ -456,10 +465,18 @@ int ln_reduce(gitcap* h, hipStream_t s, const float* slabs, int nslab, const flo
 }
 
 // projected image tokens -> decoder layers over image rows only; fills kv_img (text independent)
-int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
+// ragged_rows > 0 (a ragged batch, h->fc_cur its counts): the packed rows of B clips whose tables the slot's off / len hold, S the
+// longest clip's -- every GEMM and row kernel sees the ragged_rows valid rows, the attention runs its variable-length form
+int image_prefix(gitcap* h, int B, int S, hipStream_t s, int ragged_rows = 0) {
     const gitcap_config& c = h->c;
     gitcap::Slot& sl = cur(h);
-    const int D = h->D, Dv = h->Dv, rows = B * S, Mp = pad_to(rows, 256);
+    const bool ragged = ragged_rows > 0;
+    const int D = h->D, Dv = h->Dv, rows = ragged ? ragged_rows : B * S, Mp = pad_to(rows, 256);
+    double attn_pairs = (double)B * S * S;                   // (query, key) pairs per head
+    if (ragged) {
+        attn_pairs = 0.0;
+        for (int b = 0; b < h->fc_cur.B; ++b) attn_pairs += (double)h->fc_cur.n[b] * h->N * h->fc_cur.n[b] * h->N;
+    }
     int rc;
     h->n_staged = 0;
     // 'linearLn' projection: Linear(Dv -> D) + LayerNorm
@@ -491,8 +508,9 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
             if ((rc = gemm(h, s, EPI_BIAS_BF16, h->hb, D, L.qkvw, L.qkvb, rows, Mp, 3 * D, D, kv, 3 * D))) return rc;
             if ((rc = quant_v(l, kv))) return rc;
             {
-                ProfScope ps(h, GITCAP_PROF_ATTN_FULL, s, 4.0 * B * c.dec_heads * (double)S * S * 64, 0.0);
-                HIP_OK(h, launch_attn_full(kv, h->ctx, B, S, c.dec_heads, s));
+                ProfScope ps(h, GITCAP_PROF_ATTN_FULL, s, 4.0 * c.dec_heads * attn_pairs * 64, 0.0);
+                if (ragged) HIP_OK(h, launch_attn_full_varlen(kv, h->ctx, B, sl.off, sl.len, S, c.dec_heads, s));
+                else HIP_OK(h, launch_attn_full(kv, h->ctx, B, S, c.dec_heads, s));
             }
             LnOpts ao; ao.ln8 = f8 ? h->hb8 : nullptr;
             if ((rc = gemm_ln(h, s, true, h->ctx, D, L.aow, L.aob, Mp, D, D, h->x, h->x, L.ln1w, L.ln1b, c.dec_ln_eps, rows,
@@ -510,7 +528,7 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s) {
             if ((rc = quant_v(l, kv))) return rc;
         }
     }
-    sl.B = B; sl.S = S; sl.have = true;
+    sl.B = B; sl.S = S; sl.S_tot = rows; sl.ragged = ragged; sl.have = true;
     return 0;
 }
 
@@ -606,10 +624,12 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
             // K/V of all layers that one token step streams: beyond what the 256 MiB Infinity Cache can keep next to the
             // 132 MB of decoder weights, the rows are loaded non-temporally (16 clips x 6 frames: 349 MB per step; measured
             // +0.6 % pipelined, -1 % serial step; one clip stays cached across steps and is 4 % faster with the default policy)
-            ta.nt_kv = (double)sl.B * c.dec_layers * 2.0 * sl.S * D * 2.0 > 128e6 ? 1 : 0;
+            // (S_tot = the image rows of all clips, B * S of a dense prefix; every beam of a clip streams its clip's rows)
+            ta.nt_kv = (double)sl.S_tot * c.dec_layers * 2.0 * D * 2.0 > 128e6 ? 1 : 0;
+            if (sl.ragged) { ta.off = sl.off; ta.len = sl.len; }
             double kvb = 0;
-            for (int j = 0; j < T; ++j) kvb += (double)rows * (sl.S + t0 + j + 1) * 2 * D * 2;
-            if (h->kv_v8) kvb -= (double)rows * T * sl.S * (D - 4.0 * H);          // image V: 1 byte per element + 4 per (key, head)
+            for (int j = 0; j < T; ++j) kvb += ((double)beams * sl.S_tot + (double)rows * (t0 + j + 1)) * 2 * D * 2;
+            if (h->kv_v8) kvb -= (double)beams * T * sl.S_tot * (D - 4.0 * H);     // image V: 1 byte per element + 4 per (key, head)
             ProfScope ps(h, GITCAP_PROF_ATTN_TEXT, s, 0.0, kvb + (L.aow.scale ? 1.0 : 2.0) * D * D);     // K/V read once + the output dense
             HIP_OK(h, launch_txt_block(ta, s));
         }
@@ -676,6 +696,20 @@ int check_raw(gitcap* h, const uint8_t* frames, int B, int F, int H, int W) {
 struct FrameSrc { const float* f32; const uint8_t* u8; int H, W; };     // fp32 NCHW (CLIP-normalised) or raw uint8 HWC BGR
 static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream);
 static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t s);
+
+// gitcap_attach_frame_counts' pending attachment: taken, and with that consumed, by every entry point that runs an image pass
+// (take_fc; the entry point makes it fc_cur, the counts of the call being issued, around its body -- as cons_cur) and refused by
+// those that cannot take it (fc_refuse)
+static RaggedCounts take_fc(gitcap* h) {
+    const RaggedCounts fc = h->fc_attach;
+    h->fc_attach.B = 0; h->fc_cur.B = 0;
+    return fc;
+}
+static int fc_refuse(gitcap* h, const char* who) {
+    const bool pending = h->fc_attach.B != 0 || h->fc_cur.B != 0;
+    h->fc_attach.B = 0; h->fc_cur.B = 0;
+    return pending ? fail(h, GITCAP_ERR_ARG, std::string(who) + ": per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take") : 0;
+}
 
 // Pipelined submission: the image pass on the encoder stream, `text_loop` on the slot's decode stream (see gitcap_greedy_submit).
 // A failure after the first enqueue must not leave the slot unordered (the next user of the slot waits on ev_dec only): from
@@ -786,6 +820,9 @@ int gitcap_create(const gitcap_config* cfg, int device, gitcap_t** out) {
         gitcap::Slot& sl = h->slots[i];
         rc = rc ? rc : dev_alloc(h, &sl.kv_img, (size_t)c.dec_layers * Mi * 3 * h->D);
         rc = rc ? rc : dev_alloc(h, &sl.sep_cnt, (size_t)h->Tmax + 1);
+        rc = rc ? rc : dev_alloc(h, &sl.off, (size_t)c.max_batch);
+        rc = rc ? rc : dev_alloc(h, &sl.len, (size_t)c.max_batch);
+        rc = rc ? rc : dev_alloc(h, &sl.fpos, (size_t)c.max_batch * c.max_frames);
         // Text-row workspace (48 fp32 FC2 slabs + 12 per-head partials = 184 KB per row, the arg-max partials, ...): slot 0 also
         // serves the synchronous entry points, whose teacher-forced passes run rows x positions text rows at once; slots 1-3 only
         // ever run token loops of pipelined submissions -- one position per row and step -- and are sized for that.
@@ -1018,9 +1055,13 @@ int gitcap_finalize_weights(gitcap_t* h) {
 
 int gitcap_encode(gitcap_t* h, const float* frames, int B, int F, float* visual_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode: null handle");
+    const RaggedCounts fc = take_fc(h);
     GUARD(h);
     POLL(h);
-    return encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
+    h->fc_cur = fc;
+    const int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
+    h->fc_cur.B = 0;
+    return rc;
 }
 
 // The encoder half of the image pass: B x F frames (checked by the caller) through patch gather, the ViT blocks and ln_post.
@@ -1124,6 +1165,30 @@ static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
     int rc = src.u8 ? check_frames(h, src.u8, B, F, true) : check_frames(h, src.f32, B, F);
     if (rc) return rc;
     cur(h).have = false;
+    if (const RaggedCounts& fc = h->fc_cur; fc.B != 0) {
+        // packed clips: `frames` holds sum(counts) frames, F is the largest count
+        if (fc.B != B) return fail(h, GITCAP_ERR_ARG, "encode: B differs from the attached frame counts'");
+        int total = 0, mx = 0, mn = 256;
+        for (int b = 0; b < B; ++b) { total += fc.n[b]; mx = std::max(mx, (int)fc.n[b]); mn = std::min(mn, (int)fc.n[b]); }
+        if (mx != F) return fail(h, GITCAP_ERR_ARG, "encode: F is not the largest of the attached frame counts");
+        if (total > h->c.max_batch * h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "encode: the attached frame counts sum beyond max_batch * max_frames");
+        if (mn != mx) {
+            gitcap::Slot& sl = cur(h);
+            const int N = h->N;
+            HIP_OK(h, launch_ragged_tables(fc, N, sl.off, sl.len, sl.fpos, stream));
+            if (h->c.num_frames > 0) {
+                // every frame is encoded on its own without the fused temporal add; the fp32 ln_post rows are staged in the q|k|v
+                // buffer (dead behind the last block's attention, as in window_push) and the row kernel adds temporal[pos[frame]]
+                float* stage = (float*)h->qkv;
+                if ((rc = encode_frames(h, src, total, 1, stage, nullptr, true, stream))) return rc;
+                const double rows = (double)total * N;
+                ProfScope ps(h, GITCAP_PROF_ROWOPS, stream, 0.0, rows * h->Dv * (4.0 + 2.0 + (visual_out ? 4.0 : 0.0)));
+                HIP_OK(h, launch_ragged_temporal(stage, h->temporal, sl.fpos, h->hb, visual_out, total, N, h->Dv, stream));
+            } else if ((rc = encode_frames(h, src, total, 1, visual_out, nullptr, true, stream))) return rc;
+            return image_prefix(h, B, F * N, stream, total * N);
+        }
+        // equal counts: the dense path, launch for launch
+    }
     if ((rc = encode_frames(h, src, B, F, visual_out, h->c.num_frames > 0 ? h->temporal : nullptr, true, stream))) return rc;
     return image_prefix(h, B, F * h->N, stream);
 }
@@ -1137,6 +1202,7 @@ static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
 
 int gitcap_set_visual(gitcap_t* h, const float* visual, int B, int S_img, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "set_visual: null handle");
+    if (int rc = fc_refuse(h, "set_visual")) return rc;
     GUARD(h);
     POLL(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -1259,6 +1325,7 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_l
     const LpAttach lp = take_lp(h);
     const PromptArgs pr = take_prompt(h);
     const ConsOpt co = take_cons(h);
+    const RaggedCounts fc = take_fc(h);
     GUARD(h);
     POLL(h);
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
@@ -1267,8 +1334,10 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_l
     if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
     int rc = lp_check(h, "greedy", lp, max_len);
     if (!rc) rc = cons_enter(h, co, max_len, 1, "greedy");
+    h->fc_cur = fc;
     if (!rc) rc = body(lp, pr);
     h->cons_cur = ConsOpt{};
+    h->fc_cur.B = 0;
     return rc;
 }
 
@@ -1300,9 +1369,13 @@ int gitcap_greedy(gitcap_t* h, const float* frames, int B, int F, int max_len, i
 
 int gitcap_encode_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, float* visual_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode_raw: null handle");
+    const RaggedCounts fc = take_fc(h);
     GUARD(h);
     POLL(h);
-    return encode_sync(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
+    h->fc_cur = fc;
+    const int rc = encode_sync(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
+    h->fc_cur.B = 0;
+    return rc;
 }
 
 int gitcap_greedy_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
@@ -1402,6 +1475,7 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
     h->so_attach = SearchOpt{};
     const PromptArgs pr = take_prompt(h);
     const ConsOpt co = take_cons(h);
+    const RaggedCounts fc = take_fc(h);
     GUARD(h);
     POLL(h);
     if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
@@ -1421,8 +1495,10 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
     if (so.smp.on && h->c.vocab_size > 32768) return fail(h, GITCAP_ERR_ARG, "beam_search: sampling takes a vocabulary of at most 32768 columns");
     // (a beam row must keep at least beams * per_node_beam_size allowed columns: launch_beam_step is never handed a sentinel)
     int rc = cons_enter(h, co, max_steps, beams * per_node_beam_size, "beam_search");
+    h->fc_cur = fc;
     if (!rc) rc = body(so, pr);
     h->cons_cur = ConsOpt{};
+    h->fc_cur.B = 0;
     return rc;
 }
 
@@ -1471,6 +1547,7 @@ int gitcap_beam_search_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, in
 
 int gitcap_window_reset(gitcap_t* h, int B, int F) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "window_reset: null handle");
+    if (int rc = fc_refuse(h, "window_reset")) return rc;
     GUARD(h);
     if (B < 0 || (B > 0 && (B > h->c.max_batch || F < 1 || F > h->c.max_frames || (h->c.num_frames > 0 && F > h->c.num_frames))))
         return fail(h, GITCAP_ERR_ARG, "window_reset: B / F outside the sizes the handle was created for");
@@ -1496,6 +1573,7 @@ int gitcap_window_reset(gitcap_t* h, int B, int F) {
 
 // encode n new frames of each clip and append them to the ring: fp32 ln_post rows -> staging -> ring slots
 static int window_push(gitcap* h, FrameSrc src, int B, int n, hipStream_t s) {
+    if (int rc = fc_refuse(h, "window_push")) return rc;
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "window_push: no frame window (gitcap_window_reset first)");
     if (B != h->win_B || n < 1 || n > h->win.slots) return fail(h, GITCAP_ERR_ARG, "window_push: B differs from the reset's, or n outside [1, F]");
     int rc = src.u8 ? check_raw(h, src.u8, B, n, src.H, src.W) : check_frames(h, src.f32, B, n);
@@ -1532,6 +1610,7 @@ int gitcap_window_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, in
 
 // the current window -> decoder input (+ visual features) -> image prefix on slot 0
 static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
+    if (int rc = fc_refuse(h, "window")) return rc;
     if (!h->win_ring || !h->win.full()) return fail(h, GITCAP_ERR_STATE, "window: fewer than F frames pushed since the reset");
     if (((uintptr_t)visual_out & 15) != 0) return fail(h, GITCAP_ERR_ARG, "window: visual_out must be 16-byte aligned");
     const int B = h->win_B, F = h->win.slots, N = h->N, Dv = h->Dv;
@@ -1685,6 +1764,25 @@ int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const i
     if (((uintptr_t)prompt_ids & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_prompt: a misaligned pointer");
     if (min_len < 1 || max_len < min_len || ld < max_len) return fail(h, GITCAP_ERR_ARG, "attach_prompt: need 1 <= min_len <= max_len <= ld");
     h->pr_attach = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
+    return 0;
+}
+
+int gitcap_attach_frame_counts(gitcap_t* h, const int32_t* counts, int B) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: null handle");
+    h->fc_attach.B = 0;
+    if (!counts) return 0;                                   // detach
+    if (B < 1 || B > h->c.max_batch || B > 256) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: B outside [1, min(max_batch, 256)]");
+    const int limit = std::min(255, h->c.num_frames > 0 ? std::min(h->c.max_frames, h->c.num_frames) : h->c.max_frames);
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 1 || counts[b] > limit)
+            return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: clip " + std::to_string(b) + " has " + std::to_string(counts[b]) +
+                        " frames, outside [1, " + std::to_string(limit) + "]");
+        total += counts[b];
+    }
+    if (total > (int64_t)h->c.max_batch * h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: the counts sum beyond max_batch * max_frames");
+    for (int b = 0; b < B; ++b) h->fc_attach.n[b] = (unsigned char)counts[b];
+    h->fc_attach.B = B;
     return 0;
 }
 
@@ -2277,12 +2375,46 @@ int gitcap_dbg_ffn_txt(const void* X, int ldx, const void* W1pk, const void* W2p
     return dbg_rc(launch_ffn_txt(a, (hipStream_t)stream));
 }
 
-int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) {
+// the tables of a variable-length hook (device int32 [n]) on the host: the stream is drained first (the caller may have
+// filled them on it)
+static bool dbg_read_tables(const int32_t* off, const int32_t* len, int n, hipStream_t s, std::vector<int32_t>& ho, std::vector<int32_t>& hl) {
+    if (!off || !len || n <= 0 || ((uintptr_t)off & 3) || ((uintptr_t)len & 3)) return false;
+    ho.resize(n); hl.resize(n);
+    return hipStreamSynchronize(s) == hipSuccess && hipMemcpy(ho.data(), off, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(hl.data(), len, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+int gitcap_dbg_attn_full_varlen(const void* qkv, void* ctx, int G, const int32_t* off, const int32_t* len, int H, void* stream) {
+    if (!qkv || !ctx || G <= 0 || H <= 0) return GITCAP_ERR_ARG;
+    std::vector<int32_t> ho, hl;
+    if (!dbg_read_tables(off, len, G, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
+    int mx = 0;
+    for (int g = 0; g < G; ++g) {
+        if (ho[g] < 0 || hl[g] < 1) return GITCAP_ERR_ARG;
+        mx = std::max(mx, hl[g]);
+    }
+    return launch_attn_full_varlen((const bf16_t*)qkv, (bf16_t*)ctx, G, off, len, mx, H, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream);
+int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) { return dbg_txt_block(g, nullptr, nullptr, stream); }
+// variable-length form: off / len device int32 [clips], clips = ceil(rows / beams); S_img is not read
+int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
+    if (!g || g->rows <= 0 || g->beams <= 0) return GITCAP_ERR_ARG;
+    std::vector<int32_t> ho, hl;
+    const int clips = (g->rows - 1) / g->beams + 1;
+    if (!dbg_read_tables(off, len, clips, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
+    for (int c = 0; c < clips; ++c)
+        if (ho[c] < 0 || hl[c] < 0 || (g->v8_img && (int64_t)ho[c] + hl[c] > g->v8_pitch)) return GITCAP_ERR_ARG;
+    return dbg_txt_block(g, off, len, stream);
+}
+
+static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
     if (!g || !g->kv_img || !g->kv_txt || !g->aow || !g->aob || !g->g1 || !g->b1 || !g->xin || !g->part || !g->cnt || !g->xs || !g->xsb)
         return GITCAP_ERR_ARG;
     if (g->rows <= 0 || g->beams <= 0 || g->T <= 0 || g->t0 < 0 || g->t0 + g->T > g->Tmax || g->S_img < 0 || !txt_block_ok(g->D) ||
         g->H * 64 != g->D || (g->v8_img != nullptr) != (g->vs_img != nullptr) ||
-        (g->v8_img && g->v8_pitch < (int64_t)((g->rows - 1) / g->beams + 1) * g->S_img))
+        (g->v8_img && !off && g->v8_pitch < (int64_t)((g->rows - 1) / g->beams + 1) * g->S_img))
         return GITCAP_ERR_ARG;
     // the widest access txt_block_kernel makes on each buffer: 16-byte rows of q / k / v and of the output dense (8 bytes of e4m3 codes),
     // 8 bytes of V codes; everything else -- scales, bias, gamma / beta, residual, part, tickets, xs -- one float or word at a time, xsb
@@ -2298,6 +2430,7 @@ int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) {
     a.aow = g->aow; a.aowpk = g->aoscale ? nullptr : g->aowpk; a.aoscale = g->aoscale; a.aob = g->aob; a.g1 = g->g1; a.b1 = g->b1;
     a.xin = g->xin; a.eps = g->eps; a.part = g->part; a.cnt = g->cnt; a.xs = g->xs; a.xsb = (bf16_t*)g->xsb;
     a.v8_img = (const unsigned char*)g->v8_img; a.vs_img = g->vs_img; a.v8_pitch = g->v8_pitch; a.nt_kv = g->nt_kv ? 1 : 0;
+    a.off = off; a.len = len;
     return dbg_rc(launch_txt_block(a, (hipStream_t)stream));
 }
 
@@ -2379,6 +2512,7 @@ int gitcap_hidden_states_read(gitcap_t* h, int B, int S_img, int T, float* out, 
     select_slot(h, 0);
     const gitcap::Slot& sl = cur(h);
     if (!h->want_hidden || !sl.have) return fail(h, GITCAP_ERR_STATE, "hidden_states_read: enable, encode and run a prefix (t0 = 0) first");
+    if (sl.ragged) return fail(h, GITCAP_ERR_ARG, "hidden_states_read: the image prefix is a ragged batch (gitcap_attach_frame_counts), whose rows have no [B][S_img] layout");
     if (B != sl.B || S_img != sl.S || T != h->hid_T || T <= 0)
         return fail(h, GITCAP_ERR_ARG, "hidden_states_read: B / S_img / T differ from the last encode + text_forward");
     HIP_OK(h, launch_gather_hidden(h->hid_img, h->hid_txt, out, h->c.dec_layers + 1, B, S_img, T, h->D, (size_t)h->Mi * h->D,

@@ -257,6 +257,10 @@ hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int n
 // at columns h*64), ctx [G*S][W] bf16.  Used for the ViT frames (S = N) and for the image
 // prefix of the decoder (S = F*N).
 hipError_t launch_attn_full(const bf16_t* qkv, bf16_t* ctx, int G, int S, int H, hipStream_t s);
+// Variable-length form (a ragged batch's decoder image prefix): group g = rows off[g] .. off[g] + len[g] - 1 of the packed
+// qkv / ctx (device int32 [G], 1 <= len[g] <= S_max; S_max sizes the grid).  Each group's ctx rows are bit for bit those of
+// launch_attn_full(G = 1, S = len[g]) on the group alone; no row outside the groups is written.
+hipError_t launch_attn_full_varlen(const bf16_t* qkv, bf16_t* ctx, int G, const int32_t* off, const int32_t* len, int S_max, int H, hipStream_t s);
 
 // Attention sub-layer for text rows (txtblock.hip): query (r, t0+j) attends the image keys of clip r/beams and the text
 // keys 0..t0+j of row r -> this head's share of the output dense -> the last head of a row to arrive adds bias +
@@ -279,6 +283,9 @@ struct TxtBlockArgs {
     const unsigned char* v8_img; const float* vs_img; int64_t v8_pitch;
     int Mh;                                     // set by the launcher
     int nt_kv;                                  // 1: the K/V rows are streamed with non-temporal loads (they do not fit the caches anyway)
+    // variable-length form (both or neither; device int32 [clips]): clip c's image keys are the rows off[c] .. off[c] + len[c] - 1
+    // of the packed kv_img / v8_img / vs_img, S_img is not read.  nullptr: every clip has S_img rows at c * S_img.
+    const int32_t *off, *len;
 };
 bool txt_block_ok(int D);
 extern std::atomic<bool> g_txt8;                                          // txtblock.hip: 8-wave workgroups where units > CUs (speed switch 9)
@@ -333,6 +340,15 @@ hipError_t launch_window_scatter(const float* src, float* ring, int B, int n, in
 // [B*F*N][D] (the decoder input) and vis fp32 (nullable); the same bits as the ln_post epilogue that adds the embedding itself
 hipError_t launch_window_assemble(const float* ring, const float* temporal, bf16_t* out, float* vis, int B, int F, int head, int N, int D,
                                   hipStream_t s);
+// Ragged batches (gitcap_attach_frame_counts): clips of 1..255 frames each, packed clip-major.  RaggedCounts travels by value
+// (a stream-ordered launch captures it), launch_ragged_tables writes off[b] = N * sum_{i<b} n[i], len[b] = N * n[b] (int32 [B])
+// and pos[frame] = the frame's index inside its clip (int32 [sum n]).
+struct RaggedCounts { int B; unsigned char n[256]; };
+hipError_t launch_ragged_tables(const RaggedCounts& rc, int N, int32_t* off, int32_t* len, int32_t* pos, hipStream_t s);
+// row r (frame r / N) of the decoder input = bf16(ln[r] + temporal[pos[r / N]]), optionally also the fp32 sum (visual features):
+// window_assemble's add and rounding, i.e. the fused ln_post epilogue's, with the frame's position read from a table
+hipError_t launch_ragged_temporal(const float* ln, const float* temporal, const int32_t* pos, bf16_t* out, float* vis, int frames, int N,
+                                  int D, hipStream_t s);
 // f32 -> bf16 copy
 hipError_t launch_cast_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t s);
 // e4m3 weight rows [rows][K] (+ per-row power-of-two scale) -> bf16 [rows][K] (exact); K % 16 == 0

@@ -211,6 +211,42 @@ __global__ __launch_bounds__(256) void window_assemble_kernel(const float* __res
     }
 }
 
+// ---- ragged batches (gitcap_attach_frame_counts) ------------------------------------------------
+// The tables of a packed batch from its per-clip frame counts (by value: at most 256 clips).  One thread: a few hundred adds.
+__global__ __launch_bounds__(64) void ragged_tables_kernel(RaggedCounts rc, int N, int32_t* __restrict__ off, int32_t* __restrict__ len,
+                                                           int32_t* __restrict__ pos) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int frame = 0;
+    for (int b = 0; b < rc.B; ++b) {
+        const int n = rc.n[b];
+        off[b] = frame * N;
+        len[b] = n * N;
+        for (int f = 0; f < n; ++f) pos[frame + f] = f;
+        frame += n;
+    }
+}
+
+// window_assemble_kernel with the frame's position read from pos[] and the rows read in place: one wave per row, lane = 4
+// consecutive columns; a lone fp32 add (no contraction) and pack_bf2, so the bits are the fused ln_post epilogue's.
+__global__ __launch_bounds__(256) void ragged_temporal_kernel(const float* __restrict__ ln, const float* __restrict__ temporal,
+                                                              const int32_t* __restrict__ pos, bf16_t* __restrict__ out,
+                                                              float* __restrict__ vis, int rows, int N, int D) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* src = ln + (size_t)row * D;
+    const float* t = temporal + (size_t)pos[row / N] * D;
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 y = *(const f32x4*)(src + c);
+        y += *(const f32x4*)(t + c);
+        if (vis) *(f32x4*)(vis + (size_t)row * D + c) = y;
+        uint2 o;
+        o.x = pack_bf2(y[0], y[1]);
+        o.y = pack_bf2(y[2], y[3]);
+        *(uint2*)(out + (size_t)row * D + c) = o;
+    }
+}
+
 // e4m3 weight panel -> bf16 staging panel for the big-tile GEMMs (16 values per thread: 16-B read, 32-B write)
 __global__ __launch_bounds__(256) void dequant_fp8_kernel(const unsigned char* __restrict__ w8, const float* __restrict__ scale,
                                                           bf16_t* __restrict__ out, int K, int64_t n16) {
@@ -1750,6 +1786,20 @@ hipError_t launch_window_assemble(const float* ring, const float* temporal, bf16
     const int rows = B * F * N;
     hipLaunchKernelGGL(window_assemble_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ring, temporal, out, vis, rows, F,
                        head, N, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_tables(const RaggedCounts& rc, int N, int32_t* off, int32_t* len, int32_t* pos, hipStream_t s) {
+    if (rc.B <= 0 || rc.B > 256 || N <= 0 || !off || !len || !pos) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ragged_tables_kernel, dim3(1), dim3(64), 0, s, rc, N, off, len, pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_temporal(const float* ln, const float* temporal, const int32_t* pos, bf16_t* out, float* vis, int frames, int N,
+                                  int D, hipStream_t s) {
+    if (frames <= 0 || N <= 0 || D % 4 || D > 1024 || !ln || !temporal || !pos || !out) return hipErrorInvalidValue;
+    const int rows = frames * N;
+    hipLaunchKernelGGL(ragged_temporal_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ln, temporal, pos, out, vis, rows, N, D);
     return hipGetLastError();
 }
 

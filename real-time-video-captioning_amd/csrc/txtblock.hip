@@ -116,7 +116,10 @@ __device__ __forceinline__ void block_layernorm(float (&v)[NC], const bool (&act
 // groups handled by the virtual wave that is next in the dealing, tw = ceil(S_img / 32) mod 16, after its image groups and into the
 // same softmax state.  The summation order is a function of (S_img, t) only: batch invariant, cached == teacher-forced bitwise.
 // p * (code * scale) is computed as (p * scale) * code: the same real product, rounded once by the same FMA.
-template <int K32, bool FP8, int NW, bool NT_KV, bool V8 = false>
+// VL (variable-length form, a.off / a.len set): the image keys of clip c are the rows a.off[c] .. a.off[c] + a.len[c] - 1 of the
+// packed kv_img (and of the packed e4m3 codes and scales) and their count a.len[c] stands wherever a.S_img stands in the plain
+// form -- the key count, the image / text split, the dealing of the key groups: the bits of the plain kernel at S_img = len[c].
+template <int K32, bool FP8, int NW, bool NT_KV, bool V8 = false, bool VL = false>
 __global__ __launch_bounds__(NW * 64, 4) void txt_block_kernel(TxtBlockArgs a) {
     constexpr int D = K32 * 32;
     constexpr int NC = 16 / NW;                                 // columns (virtual waves) per thread in the row reducer
@@ -153,12 +156,14 @@ __global__ __launch_bounds__(NW * 64, 4) void txt_block_kernel(TxtBlockArgs a) {
     const int frow = lane & 15, fq = lane >> 4;
     TXT_STAMP(0);
 
-    const int Lk = a.S_img + tq + 1;
+    const int S_img = VL ? a.len[clip] : a.S_img;                      // workgroup-uniform
+    const size_t img_row0 = VL ? (size_t)a.off[clip] : (size_t)clip * a.S_img;
+    const int Lk = S_img + tq + 1;
     const int sub = lane & 7, kk = lane >> 3;
     // (Round 4 timed a head-major image K/V cache -- one contiguous 256-B record per key and head, a contiguous stream per
     // unit -- by addressing this buffer that way: 301 vs 307 us per token step at 16 clips, 209 vs 211 at one
     // (profiles/r04_text_attention_head_major_kv_timing.txt).  Not worth a second GEMM epilogue and attention read path.)
-    const bf16_t* img = a.kv_img + (size_t)clip * a.S_img * ld + D + head * 64 + sub * 8;
+    const bf16_t* img = a.kv_img + img_row0 * ld + D + head * 64 + sub * 8;
     const bf16_t* txt = a.kv_txt + (size_t)r * a.Tmax * ld + D + head * 64 + sub * 8;
     TXT_STAMP(2);
     // ---- 1: attention of (row, position tq, head) ------------------------------------------------------------------
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(NW * 64, 4) void txt_block_kernel(TxtBlockArgs a) {
             int key = g0 + u * 8 + kk;
             valid[u] = key < Lk;
             key = valid[u] ? key : 0;
-            const bf16_t* kp = key < a.S_img ? img + (size_t)key * ld : txt + (size_t)(key - a.S_img) * ld;
+            const bf16_t* kp = key < S_img ? img + (size_t)key * ld : txt + (size_t)(key - S_img) * ld;
             // NT_KV: read once per launch and too large to stay cached: do not displace what the GEMMs re-read.  (A template flag: a
             // run-time branch around a load makes the compiler merge "loaded" with "not loaded" registers behind it and wait there.)
             kf[u] = NT_KV ? __builtin_nontemporal_load((const bf16x8*)kp) : *(const bf16x8*)kp;
@@ -239,12 +244,12 @@ __global__ __launch_bounds__(NW * 64, 4) void txt_block_kernel(TxtBlockArgs a) {
         }
     };
     if constexpr (V8) {
-        const int S = a.S_img;
+        const int S = S_img;
         // head-major codes: this unit's V stream is one contiguous run of 64-byte records (8 keys = 512 B per wave instruction), its
         // scales one contiguous run of floats: the 32 scales of a key group are ONE load (lane i: key g0 + (i & 31)), handed to the
         // lanes of each key by ds_bpermute
-        const unsigned char* v8p = a.v8_img + ((size_t)head * a.v8_pitch + (size_t)clip * S) * 64 + sub * 8;
-        const float* vsp = a.vs_img + (size_t)head * a.v8_pitch + (size_t)clip * S;
+        const unsigned char* v8p = a.v8_img + ((size_t)head * a.v8_pitch + img_row0) * 64 + sub * 8;
+        const float* vsp = a.vs_img + (size_t)head * a.v8_pitch + img_row0;
         typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
         struct G8 { bf16x8 k[4]; u32x2 v[4]; float sc; bool ok[4]; };
         auto load8 = [&](int g0, G8& x) {                                  // image keys g0 .. g0 + 31 (past the last: key 0, masked)
@@ -544,18 +549,20 @@ hipError_t launch_txt_block(const TxtBlockArgs& a_in, hipStream_t s) {
     static const int nt = getenv("GITCAP_TXT_NT") ? atoi(getenv("GITCAP_TXT_NT")) : -1;    // A/B switch: 0 never, 1 always
     if (nt >= 0) a.nt_kv = nt;
     const int M = a.rows * a.T;
-    if (M <= 0 || a.H * 64 != a.D || a.beams <= 0 || !a.xin || (a.v8_img != nullptr) != (a.vs_img != nullptr)) return hipErrorInvalidValue;
+    if (M <= 0 || a.H * 64 != a.D || a.beams <= 0 || !a.xin || (a.v8_img != nullptr) != (a.vs_img != nullptr) ||
+        (a.off != nullptr) != (a.len != nullptr)) return hipErrorInvalidValue;
     // first "half" of the rows for heads 8..11 (H == 12 mapping): whole clips (all beams of a clip stay together)
     const int unit = a.T == 1 ? a.beams : 1;
     a.Mh = ((M / unit + 1) / 2) * unit;
     const int grid = a.H == 12 ? 8 * (M + (a.Mh > M - a.Mh ? a.Mh : M - a.Mh)) : M * a.H;
     const bool w8 = g_txt8 && M * a.H > device_cus();
     const int key = a.D * 2 + (a.aoscale ? 1 : 0);
-#define TXT_LAUNCH_V(K32, F8, V8) do { \
-        if (w8) { if (a.nt_kv) hipLaunchKernelGGL((txt_block_kernel<K32, F8, 8, true, V8>), dim3(grid), dim3(512), 0, s, a); \
-                  else hipLaunchKernelGGL((txt_block_kernel<K32, F8, 8, false, V8>), dim3(grid), dim3(512), 0, s, a); } \
-        else { if (a.nt_kv) hipLaunchKernelGGL((txt_block_kernel<K32, F8, 16, true, V8>), dim3(grid), dim3(1024), 0, s, a); \
-               else hipLaunchKernelGGL((txt_block_kernel<K32, F8, 16, false, V8>), dim3(grid), dim3(1024), 0, s, a); } } while (0)
+#define TXT_LAUNCH_L(K32, F8, V8, VL) do { \
+        if (w8) { if (a.nt_kv) hipLaunchKernelGGL((txt_block_kernel<K32, F8, 8, true, V8, VL>), dim3(grid), dim3(512), 0, s, a); \
+                  else hipLaunchKernelGGL((txt_block_kernel<K32, F8, 8, false, V8, VL>), dim3(grid), dim3(512), 0, s, a); } \
+        else { if (a.nt_kv) hipLaunchKernelGGL((txt_block_kernel<K32, F8, 16, true, V8, VL>), dim3(grid), dim3(1024), 0, s, a); \
+               else hipLaunchKernelGGL((txt_block_kernel<K32, F8, 16, false, V8, VL>), dim3(grid), dim3(1024), 0, s, a); } } while (0)
+#define TXT_LAUNCH_V(K32, F8, V8) do { if (a.off) TXT_LAUNCH_L(K32, F8, V8, true); else TXT_LAUNCH_L(K32, F8, V8, false); } while (0)
 #define TXT_LAUNCH(K32, F8) do { if (a.v8_img) TXT_LAUNCH_V(K32, F8, true); else TXT_LAUNCH_V(K32, F8, false); } while (0)
     switch (key) {
         case 256: TXT_LAUNCH(4, false); break;
@@ -566,5 +573,6 @@ hipError_t launch_txt_block(const TxtBlockArgs& a_in, hipStream_t s) {
     }
 #undef TXT_LAUNCH
 #undef TXT_LAUNCH_V
+#undef TXT_LAUNCH_L
     return hipGetLastError();
 }

@@ -219,6 +219,10 @@ SYMBOLS = {
     "gitcap_sample_rows_constrained": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_float,
                                                c_int32, c_float, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                                c_void_p]),
+    # per-clip frame counts: ragged batches (tests/test_ragged_kernels_gpu.py, tests/test_ragged_e2e_gpu.py)
+    "gitcap_attach_frame_counts": (c_int, [c_void_p, POINTER(c_int32), c_int]),
+    "gitcap_dbg_attn_full_varlen": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_txt_block_varlen": (c_int, [POINTER(CDbgTxtBlockArgs), c_void_p, c_void_p, c_void_p]),
     # student decoder (gitcap/student.py)
     "gitcap_student_create": (c_int, [POINTER(CStudentConfig), c_int, POINTER(c_void_p)]),
     "gitcap_student_destroy": (None, [c_void_p]),

@@ -26,7 +26,7 @@ from typing import Dict, Mapping, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from .config import CGitCapConfig, GitCapConfig, git_base
 from .framegate import FrameGate
 from . import weights as W
@@ -224,6 +224,7 @@ class CaptionFuture(_Future):
         self._done = None
         self._prompt = None                      # greedy_decode_async(prompt=...): held until the result (the device reads it)
         self._cons = None                        # _Constraints | None, held likewise
+        self._rg = None                          # greedy_decode_async(frame_counts=...): the (clips, counts, raw) a re-run decodes again
 
     def _attach(self, sub, r0, r1):
         self._sub, self._r0, self._r1 = sub, r0, r1
@@ -250,7 +251,8 @@ class CaptionFuture(_Future):
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         def rerun():
-            ids = m._greedy_decode(sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._prompt, self._cons)
+            ids = m._greedy_decode(None if self._rg is not None else sub.rows(self._r0, self._r1), self._max_len, self._mode, False,
+                                   self._prompt, self._cons, self._rg)
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         synced = self._mode == STOP_ALL_SEP or self._out_device.type == "cpu"
@@ -280,10 +282,18 @@ class InferFuture(_Future):
                 out["seed"] = self._kw["sampling"][3]
             if self._kw.get("prompt") is not None:
                 out["prompt_lengths"] = mv(self._kw["prompt"].lengths)
+            counts = self._kw.get("counts")
+            if counts is not None and vis is not None:       # a ragged batch: packed rows -> the padded pair of the reference
+                pv, valid = ragged.unpack_rows(vis, counts, m.cfg.tokens_per_frame)
+                out["visual_features"], out["visual_features_valid"] = mv(pv), mv(valid)
             return out
 
         def rerun():
-            r = m._infer_device(m._to_device(sub.rows(0, sub.outs[0].shape[0])), sync=True, save_logits=self._save,
+            if self._kw.get("counts") is not None:           # the packed frames: on the device already, or the callers' host clips again
+                fr = sub.frames if sub.parts is None else m._pack_to_device(sub.parts, sub.parts[0].dtype == torch.uint8)
+            else:
+                fr = m._to_device(sub.rows(0, sub.outs[0].shape[0]))
+            r = m._infer_device(fr, sync=True, save_logits=self._save,
                                 want_visual=sub.outs[3] is not None, **self._kw)
             sub.outs = r
             return extract()
@@ -708,13 +718,69 @@ class GitCaptioner(_NativeModule):
     def _ids(self, y: torch.Tensor) -> torch.Tensor:
         return y.to(device=self._dev, dtype=torch.int64).contiguous()
 
+    # ------------------------------------------------------------------ ragged batches (frame_counts=; gitcap/ragged.py)
+    def _frame_limit(self) -> int:
+        nf = self.cfg.num_frames
+        return min(self.max_frames, nf) if nf > 0 else self.max_frames
+
+    def _ragged_input(self, src, frame_counts):
+        """``src`` + ``frame_counts`` of a decoding call -> (dense tensor [B, F, ...], None) when every clip has the same number
+        of frames (the existing path: nothing is attached) or (None, (clips, counts, raw)) for a ragged batch."""
+        parts, counts, raw = ragged.clips(src, frame_counts, self.cfg.image_size, self._frame_limit())
+        if ragged.is_dense(counts):
+            return ragged.dense(parts), None
+        return None, (parts, counts, raw)
+
+    def _pack_to_device(self, parts, raw) -> torch.Tensor:
+        """The clips of a ragged (chunk of a) batch -> packed device frames [sum(counts), ...] for a SYNCHRONOUS call: one
+        packing copy, for host clips into the pinned staging entry of the synchronous calls (as _to_device)."""
+        dtype = torch.uint8 if raw else torch.float32
+        if parts[0].device.type == "cpu":
+            with torch.cuda.device(self._dev):
+                dv, _, _ = self._staging().stage(self, list(parts), dtype, stream=torch.cuda.current_stream(self._dev))
+            return dv
+        x = ragged.pack(parts).to(device=self._dev, dtype=dtype).contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        return x
+
+    def _attach_counts(self, counts):
+        """The one-shot attachment the NEXT call with an image pass consumes (gitcap_attach_frame_counts; the counts are copied)."""
+        self._call("gitcap_attach_frame_counts", (ctypes.c_int32 * len(counts))(*counts), len(counts))
+
+    def _encode_ragged(self, parts, counts, raw) -> torch.Tensor:
+        """The image pass of one ragged batch of at most max_batch clips -> the packed fp32 visual rows [sum(counts) * N, Dv];
+        leaves the decoder's image K/V (and the slot's row tables) in the handle."""
+        if len(counts) > self.max_batch:
+            raise ValueError(f"batch {len(counts)} > max_batch={self.max_batch}")
+        fr = self._pack_to_device(parts, raw)
+        vis = torch.empty((fr.shape[0] * self.cfg.tokens_per_frame, self.cfg.enc_width), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            self._attach_counts(counts)
+            if raw:
+                self._call("gitcap_encode_raw", _lib.ptr(fr), len(counts), max(counts), fr.shape[1], fr.shape[2], _lib.ptr(vis), self._stream())
+            else:
+                self._call("gitcap_encode", _lib.ptr(fr), len(counts), max(counts), _lib.ptr(vis), self._stream())
+        self._last_memory = None
+        return vis
+
     # ------------------------------------------------------------------ reference API
     @torch.no_grad()
-    def forward_image_enc(self, x: torch.Tensor):
+    def forward_image_enc(self, x: torch.Tensor, frame_counts=None):
         """-> ([], memory) with memory = visual features [B, F*N, Dv] (ln_post + temporal embedding,
         frames concatenated along tokens, model.py:378-382).  Also leaves the decoder's image K/V
-        in the handle."""
+        in the handle.
+        frame_counts (or ``x`` as a list of B clips [F_b, ...]): clips that differ in length -> (visual [B, Fmax*N, Dv], zero
+        beyond a clip's rows, valid bool [B, Fmax*N]): the reference's visual_features / visual_features_valid pair
+        (model.py:426, :443).  The handle then holds the batch packed; score / forward_decoder-style calls follow it."""
         self._drain()
+        if frame_counts is not None or not isinstance(x, torch.Tensor):
+            x, rg = self._ragged_input(x, frame_counts)
+            if rg is not None:
+                parts, counts, raw = rg
+                return ragged.unpack_rows(self._encode_ragged(parts, counts, raw), counts, self.cfg.tokens_per_frame)
+            vis = self.forward_image_enc(x)[1]
+            return vis, torch.ones(vis.shape[:2], dtype=torch.bool, device=vis.device)
         raw = x.dtype == torch.uint8
         fr = self._raw_frames(x) if raw else self._frames(x)
         B, F = fr.shape[:2]
@@ -755,7 +821,7 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
-              ignore_id: Optional[int] = None, return_top1: bool = False) -> dict:
+              ignore_id: Optional[int] = None, return_top1: bool = False, frame_counts=None) -> dict:
         """Log-probabilities of GIVEN captions, teacher-forced in one pass without a logits tensor (include/gitcap.h:
         gitcap_score).  ``x``: frames [B,F,3,S,S] or ``memory`` from forward_image_enc (treated as forward_decoder treats it);
         ``y``: CLS-first ids [B, T] or [B, n, T] -- n candidates per clip, run as n rows that share the clip's image K/V.
@@ -763,12 +829,17 @@ class GitCaptioner(_NativeModule):
         or lies behind the row's length: through its first SEP (``until_sep``) and / or the caller's ``lengths`` ([B] or [B, n],
         valid tokens, CLS included).  -> dict: ``token_logprobs`` fp32 [B, (n,) T-1] (column j belongs to y[..., j + 1]),
         ``sum`` fp32 and ``count`` int32 [B, (n)]; with ``return_top1`` also ``top1_ids`` / ``top1_logprobs`` [B, (n,) T-1], the
-        model's own arg-max at each position.  More clips than max_batch go through in chunks.  On ``x``'s device."""
+        model's own arg-max at each position.  More clips than max_batch go through in chunks.  On ``x``'s device.
+        frame_counts (or ``x`` as a list of clips; as in greedy_decode): frames of clips that differ in length; every clip's values
+        are bit for bit those of the clip scored alone."""
         from . import scoring
         self._drain()
         ids, had_n = scoring.candidates(y, self._dev)
         B, n, T = ids.shape
-        if x.shape[0] != B:
+        rg = None
+        if frame_counts is not None or not isinstance(x, torch.Tensor):
+            x, rg = self._ragged_input(x, frame_counts)
+        if (x.shape[0] if rg is None else len(rg[1])) != B:
             raise ValueError("x and y disagree on the number of clips")
         if T > self.max_text_len:
             raise ValueError(f"T={T} > max_text_len={self.max_text_len} the handle was created for")
@@ -777,12 +848,15 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"{Bc} clips x {n} candidates = {Bc * n} rows > max_batch * max_beams = {self.max_batch * self.max_beams} "
                              "the handle was created for")
         ln = scoring.row_lengths(ids, self.sep_token_id, until_sep, lengths)
-        frames = x.dim() == 5
+        frames = rg is None and x.dim() == 5
+        out_dev = x.device if rg is None else rg[0][0].device
         chunks = []
         with torch.cuda.device(self._dev):
             for b0 in range(0, B, Bc):
                 b1 = min(B, b0 + Bc)
-                if frames:
+                if rg is not None:
+                    self._encode_ragged(rg[0][b0:b1], rg[1][b0:b1], rg[2])
+                elif frames:
                     self.forward_image_enc(x[b0:b1])
                 elif not (b0 == 0 and b1 == B and self._is_last_memory(x)):
                     mem = x[b0:b1].to(device=self._dev, dtype=torch.float32).contiguous()
@@ -799,28 +873,43 @@ class GitCaptioner(_NativeModule):
                 chunks.append(buf)
         if B > Bc:
             self._last_memory = None
-        return scoring.result(chunks, B, n, had_n, return_top1, x.device)
+        return scoring.result(chunks, B, n, had_n, return_top1, out_dev)
 
     @torch.no_grad()
-    def rerank(self, x: torch.Tensor, candidates: torch.Tensor, length_penalty: float = 0.6) -> dict:
+    def rerank(self, x: torch.Tensor, candidates: torch.Tensor, length_penalty: float = 0.6, frame_counts=None) -> dict:
         """Order n candidate captions per clip ([B, n, T], e.g. infer(num_keep_best=n), sampled captions, the student's beams)
         by this model's sum / count ** length_penalty, the BeamHypotheses score of the reference's search.  -> score()'s dict
         plus ``scores`` fp32 [B, n] and ``order`` int64 [B, n], best first."""
         from . import scoring
         if candidates.dim() != 3:
             raise ValueError(f"expected candidates [B, n, T], got {tuple(candidates.shape)}")
-        return scoring.rerank_scores(self.score(x, candidates), length_penalty)
+        return scoring.rerank_scores(self.score(x, candidates, frame_counts=frame_counts), length_penalty)
 
-    def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None):
+    def forward(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, frame_counts=None):
         """``forward(x, y)``: teacher-forced logits [B,T,V] (student signature, model.py:99-106).
-        ``forward(x)``: the teacher's form (``GenerativeImageTextTeacher.forward``, model.py:762-793)."""
+        ``forward(x)``: the teacher's form (``GenerativeImageTextTeacher.forward``, model.py:762-793).
+        frame_counts (or ``x`` as a list of clips): clips that differ in length, as in greedy_decode."""
         if y is None:
-            return self.teacher_forward(x)
+            return self.teacher_forward(x, frame_counts=frame_counts)
+        if frame_counts is not None or not isinstance(x, torch.Tensor):
+            self._drain()
+            x, rg = self._ragged_input(x, frame_counts)
+            if rg is not None:                   # the handle holds the packed batch: the text rows follow its tables
+                self._encode_ragged(*rg)
+                ids = self._ids(y)
+                B, T = ids.shape
+                if B != len(rg[1]):
+                    raise ValueError("x and y disagree on the number of clips")
+                logits = torch.empty((B, T, self.cfg.vocab_size), dtype=torch.float32, device=self._dev)
+                with torch.cuda.device(self._dev):
+                    self._call("gitcap_text_forward", _lib.ptr(ids), T, B, 1, 0, T, _lib.ptr(logits), 1, None, 0, self._stream())
+                return logits
         _, memory = self.forward_image_enc(x)
         return self.forward_decoder(y, memory)
 
     @torch.no_grad()
-    def teacher_forward(self, x: torch.Tensor, beam_size: int = 4, max_steps: int = 15, on_device: Optional[bool] = None) -> list:
+    def teacher_forward(self, x: torch.Tensor, beam_size: int = 4, max_steps: int = 15, on_device: Optional[bool] = None,
+                        frame_counts=None) -> list:
         """``GenerativeImageTextTeacher.forward`` (model.py:762-793): one dict per clip with the keys of
         ``infer`` (model.py:456-461) plus ``cap`` (decoded caption, :770) and ``output`` [1, n, V] = for each of
         the first n predicted words the logits of the beam that scores that word highest (:771-788).
@@ -832,7 +921,14 @@ class GitCaptioner(_NativeModule):
         Without a tokenizer ``cap`` is None and n counts the tokens before SEP."""
         if on_device is None:
             on_device = beam_size * 2 <= 16
-        fr, _ = self._check_frames(x)             # a CPU tensor stays where it is: every chunk is staged as it is submitted
+        rg = None
+        if frame_counts is not None or not isinstance(x, torch.Tensor):
+            x, rg = self._ragged_input(x, frame_counts)
+        if rg is not None:                        # clips that differ in length: fr = the list of clips, a chunk = a ragged batch
+            fr, nclips, rkw = rg[0], len(rg[1]), {"frame_counts": None}
+        else:
+            fr, _ = self._check_frames(x)         # a CPU tensor stays where it is: every chunk is staged as it is submitted
+            nclips, rkw = fr.shape[0], {}
         out = []
 
         def finish(pred, pred_h, logprobs, steps, vis):       # per-clip bookkeeping of one chunk; steps: [S, Bc * beams, V] on the device
@@ -859,7 +955,7 @@ class GitCaptioner(_NativeModule):
         if on_device:
             # a sliding window of submissions, each consumed (and its [max_steps - 1, B * beams, V] logits tensor dropped) before
             # the next is made: device memory is bounded by the window, not by the number of chunks
-            kw = dict(beam_size=beam_size, max_steps=max_steps, save_logits=True, visual_features=True)
+            kw = dict(beam_size=beam_size, max_steps=max_steps, save_logits=True, visual_features=True, **rkw)
             futs = []
 
             def take(f, b0):
@@ -873,15 +969,16 @@ class GitCaptioner(_NativeModule):
                     self.poll_errors()
                 finish(r["predictions"], pred_h, r["logprobs"], r["logits_dict"], r["visual_features"])
 
-            for b0 in range(0, fr.shape[0], self.max_batch):
+            for b0 in range(0, nclips, self.max_batch):
                 if len(futs) >= 3:
                     take(*futs.pop(0))
                 futs.append((self.infer_async(fr[b0:b0 + self.max_batch], **kw), b0))
             while futs:
                 take(*futs.pop(0))
         else:
-            for b0 in range(0, fr.shape[0], self.max_batch):
-                r = self.infer(fr[b0:b0 + self.max_batch], beam_size=beam_size, max_steps=max_steps, save_logits=True, on_device=False)
+            for b0 in range(0, nclips, 1 if rg is not None else self.max_batch):      # (ragged: clip by clip, as the reference, model.py:765)
+                xb = fr[b0][None] if rg is not None else fr[b0:b0 + self.max_batch]
+                r = self.infer(xb, beam_size=beam_size, max_steps=max_steps, save_logits=True, on_device=False)
                 steps = torch.from_numpy(np.stack([np.asarray(st) for st in r["logits_dict"]])).to(self._dev)
                 finish(r["predictions"], r["predictions"].cpu(), r["logprobs"], steps, r["visual_features"])
         return out
@@ -913,7 +1010,8 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
-                      prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None):
+                      prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+                      frame_counts=None):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
@@ -930,40 +1028,62 @@ class GitCaptioner(_NativeModule):
         and prompt included) may recur, SEP is banned while the row holds fewer than min_length tokens, the listed ids (a sequence
         or an int tensor, at most 256) are never emitted.  A banned column is -inf inside the vocabulary head, so the logprobs
         are those of the row renormalised over the allowed columns; a token a prompt forces is emitted even when banned.  With
-        the defaults nothing is attached."""
+        the defaults nothing is attached.
+        frame_counts: clips that differ in length -- ``src`` padded [B, Fmax, ...] with frame_counts [B] (frames beyond a clip's
+        count are ignored) or a list of B clips [F_b, ...] (counts inferred); fp32 or uint8 camera frames, host or device.  The
+        batch runs packed, without padding or masking (include/gitcap.h: gitcap_attach_frame_counts): every clip's ids and
+        logprobs are bit for bit those of the clip decoded alone.  Equal counts take the dense path."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
-        pr = self._prompt(prompt, prompt_lengths, src.shape[0], max_len, "max_len")
+        rg = None
+        if frame_counts is not None or not isinstance(src, torch.Tensor):
+            src, rg = self._ragged_input(src, frame_counts)
+        B, in_dev = (src.shape[0], src.device) if rg is None else (len(rg[1]), rg[0][0].device)
+        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
         co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
-        if src.device.type == "cpu":              # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr, co))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs, pr, co)
+        if in_dev.type == "cpu":                  # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr, co, rg))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, pr, co, rg)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None, co=None):
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None, co=None, rg=None):
+        """rg: the (clips, counts, raw) of a ragged batch (src is then unused): each chunk of at most max_batch clips is packed
+        and runs with its counts attached."""
         self._drain()
-        fr, raw = self._check_frames(src)         # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
-        B, F = fr.shape[:2]
+        if rg is None:
+            fr, raw = self._check_frames(src)     # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
+            B, F = fr.shape[:2]
+        else:
+            parts, counts, raw = rg
+            B, src = len(counts), parts[0]        # (src: where the results go)
         outs, steps_all, lps = [], [], []
         with torch.cuda.device(self._dev):
             for b0 in range(0, B, self.max_batch):
-                chunk = self._to_device(fr[b0:b0 + self.max_batch])      # (a CPU tensor: staged chunk by chunk, stream ordered)
-                ids = torch.empty((chunk.shape[0], max_len + 1), dtype=torch.int64, device=self._dev)
+                if rg is None:
+                    chunk = self._to_device(fr[b0:b0 + self.max_batch])      # (a CPU tensor: staged chunk by chunk, stream ordered)
+                    nb, (fh, fw) = chunk.shape[0], chunk.shape[2:4]
+                else:
+                    cc = counts[b0:b0 + self.max_batch]
+                    chunk = self._pack_to_device(parts[b0:b0 + self.max_batch], raw)
+                    nb, F, (fh, fw) = len(cc), max(cc), chunk.shape[1:3]
+                ids = torch.empty((nb, max_len + 1), dtype=torch.int64, device=self._dev)
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
                 if want_lp:                      # one-shot: consumed by the greedy call below
-                    lps.append(torch.empty((chunk.shape[0], max_len), dtype=torch.float32, device=self._dev))
+                    lps.append(torch.empty((nb, max_len), dtype=torch.float32, device=self._dev))
                     self._call("gitcap_attach_token_logprobs", _lib.ptr(lps[-1]), max_len)
                 if pr is not None:               # one-shot as well
-                    part = pr if B <= self.max_batch else pr.rows(b0, b0 + chunk.shape[0])
+                    part = pr if B <= self.max_batch else pr.rows(b0, b0 + nb)
                     part.attach(self)
                 if co is not None:               # one-shot as well
                     co.attach(self)
+                if rg is not None:               # one-shot as well
+                    self._attach_counts(cc)
                 if raw:
-                    self._call("gitcap_greedy_raw", _lib.ptr(chunk), chunk.shape[0], F, chunk.shape[2], chunk.shape[3], max_len, mode,
+                    self._call("gitcap_greedy_raw", _lib.ptr(chunk), nb, F, fh, fw, max_len, mode,
                                _lib.ptr(ids), _lib.ptr(steps), self._stream())
                 else:
-                    self._call("gitcap_greedy", _lib.ptr(chunk), chunk.shape[0], F, max_len, mode, _lib.ptr(ids), _lib.ptr(steps),
+                    self._call("gitcap_greedy", _lib.ptr(chunk), nb, F, max_len, mode, _lib.ptr(ids), _lib.ptr(steps),
                                self._stream())
                 outs.append(ids)
                 steps_all.append(steps)
@@ -988,7 +1108,7 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode_async(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                             coalesce: int = 1, prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                            suppress_tokens=None) -> "CaptionFuture":
+                            suppress_tokens=None, frame_counts=None) -> "CaptionFuture":
         """Pipelined greedy_decode for a stream of batches: returns immediately with a future; up to
         FOUR submissions may be in flight, so one batch's image pass (MFMA bound) overlaps the token
         loops (latency bound) of the batches before it on the handle's internal HIP streams.  Call
@@ -1005,11 +1125,16 @@ class GitCaptioner(_NativeModule):
         invariant); a ``result()`` on a batch that is still waiting for partners flushes it.  Needs
         max_batch >= k*B.  ``prompt`` / ``prompt_lengths`` as in greedy_decode; a prompted batch is submitted on its own (it does
         not coalesce).  no_repeat_ngram_size / min_length / suppress_tokens as in greedy_decode; a constrained batch coalesces
-        only with batches that carry equal constraints."""
+        only with batches that carry equal constraints.  frame_counts (or a list of clips) as in greedy_decode: a ragged batch is
+        packed once (host clips: in the staging ring's pinned buffer) and submitted on its own (it does not coalesce)."""
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
+        if frame_counts is not None or not isinstance(src, torch.Tensor):
+            src, rg = self._ragged_input(src, frame_counts)
+            if rg is not None:
+                return self._greedy_submit_ragged(rg, max_len, mode, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens)
         fr, raw = self._check_frames(src)         # nothing is copied yet: a CPU batch is staged when its group is submitted
         B = fr.shape[0]
         if B * max(1, coalesce) > self.max_batch:
@@ -1030,6 +1155,49 @@ class GitCaptioner(_NativeModule):
         self._pending_key = key
         if len(self._pending) >= max(1, coalesce):
             self._flush_pending()
+        return fut
+
+    def _greedy_submit_ragged(self, rg, max_len, mode, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens):
+        """greedy_decode_async of a ragged batch: one submission of its own, the counts attached beside prompt and constraints."""
+        parts, counts, raw = rg
+        B = len(counts)
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} > max_batch={self.max_batch}")
+        self._flush_pending()
+        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+        fut = CaptionFuture(self, None, mode, max_len, parts[0].device)
+        fut._prompt, fut._cons, fut._rg = pr, co, rg
+        while len(self._inflight) >= 4:
+            self._wait_submission(self._inflight[0])
+        with torch.cuda.device(self._dev):
+            entry = None
+            if parts[0].device.type == "cpu":
+                frames, entry, stream = self._stage_group(list(parts), raw)
+            else:
+                frames, stream = self._pack_to_device(parts, raw), self._stream()
+            ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
+            steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
+            ticket = ctypes.c_int(-1)
+
+            def before():
+                if pr is not None:
+                    pr.attach(self)
+                if co is not None:
+                    co.attach(self)
+                self._attach_counts(counts)
+            if raw:
+                self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, max(counts), frames.shape[1], frames.shape[2], max_len, mode,
+                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket), before=before)
+            else:
+                self._submit("gitcap_greedy_submit", _lib.ptr(frames), B, max(counts), max_len, mode, _lib.ptr(ids), _lib.ptr(steps), stream,
+                             ctypes.byref(ticket), before=before)
+        self._last_memory = None
+        sub = _Submission(ticket.value, frames, (ids, steps), False, parts=list(parts) if entry is not None else None)
+        if entry is not None:
+            entry["sub"] = sub
+        self._inflight.append(sub)
+        fut._attach(sub, 0, B)
         return fut
 
     def _stage_group(self, parts, raw):
@@ -1103,7 +1271,7 @@ class GitCaptioner(_NativeModule):
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
               on_device: Optional[bool] = None, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
               top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-              prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> dict:
+              prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, frame_counts=None) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
         reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
@@ -1132,18 +1300,44 @@ class GitCaptioner(_NativeModule):
         no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): every beam row's banned columns are -inf before
         the step ranks or samples, ahead of the log-softmax (where the reference edits its logits, :522-531), so the scores
         renormalise over the allowed columns -- unlike HF's beam search, which masks after normalising.  min_length counts CLS and
-        the prompt.  on_device=False applies the same rules in the host operator, on the raw logits next to its penalty."""
+        the prompt.  on_device=False applies the same rules in the host operator, on the raw logits next to its penalty.
+        frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length.  The device search runs the
+        batch packed, every clip's result bit for bit that of the clip alone; on_device=False runs the host operator clip by clip
+        (the reference's teacher loop, model.py:765).  ``visual_features`` comes padded with ``visual_features_valid``."""
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
         if max_steps > self.max_text_len:
             raise ValueError(f"max_steps {max_steps} > max_text_len={self.max_text_len}")
         self._drain()
-        fr, raw = self._check_frames(src)
-        B, F = fr.shape[:2]
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} > max_batch={self.max_batch}")
-        fr = self._to_device(fr)
+        rg = None
+        if frame_counts is not None or not isinstance(src, torch.Tensor):
+            src, rg = self._ragged_input(src, frame_counts)
+        if rg is not None:
+            parts, counts, raw = rg
+            B = len(counts)
+            if B > self.max_batch:
+                raise ValueError(f"batch {B} > max_batch={self.max_batch}")
+            if on_device is None:
+                on_device = (not save_logits and 1 <= num_keep_best <= beam_size * per_node_beam_size <= 16
+                             and per_node_beam_size >= 2)
+            if not on_device:                    # the host operator, one clip at a time
+                if prompt is not None:
+                    raise ValueError("infer(on_device=False, frame_counts=...) takes no prompt")
+                rs = [self.infer(p[None], beam_size, max_steps, length_penalty, per_node_beam_size, num_keep_best, save_logits, False,
+                                 repetition_penalty, do_sample, top_k, top_p, temperature, seed, None, None, no_repeat_ngram_size,
+                                 min_length, suppress_tokens) for p in parts]
+                N = self.cfg.tokens_per_frame
+                vis, valid = ragged.unpack_rows(torch.cat([r["visual_features"][0] for r in rs], 0), counts, N)
+                return {"predictions": torch.cat([r["predictions"] for r in rs], 0), "logprobs": torch.cat([r["logprobs"] for r in rs], 0),
+                        "logits_dict": [r["logits_dict"] for r in rs], "visual_features": vis, "visual_features_valid": valid}
+            fr = self._pack_to_device(parts, raw)
+        else:
+            fr, raw = self._check_frames(src)
+            B, F = fr.shape[:2]
+            if B > self.max_batch:
+                raise ValueError(f"batch {B} > max_batch={self.max_batch}")
+            fr = self._to_device(fr)
         if on_device is None:
             on_device = (not save_logits and 1 <= num_keep_best <= beam_size * per_node_beam_size <= 16
                          and per_node_beam_size >= 2)
@@ -1156,7 +1350,8 @@ class GitCaptioner(_NativeModule):
                                                                per_node_beam_size=per_node_beam_size, sync=True,
                                                                save_logits=save_logits, want_visual=False, raw=raw,
                                                                num_keep_best=num_keep_best, repetition_penalty=repetition_penalty,
-                                                               sampling=sampling, prompt=pr, constraints=co)
+                                                               sampling=sampling, prompt=pr, constraints=co,
+                                                               counts=None if rg is None else rg[1])
             out = {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
                    "visual_features": None}
             if sampling is not None:
@@ -1285,7 +1480,8 @@ class GitCaptioner(_NativeModule):
         return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
 
     def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None):
+                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None,
+                      counts=None):
         """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
         stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
         the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
@@ -1293,10 +1489,13 @@ class GitCaptioner(_NativeModule):
         if raw is None:
             raw = fr.dtype == torch.uint8
         B, F = fr.shape[:2]
+        fh, fw = fr.shape[2:4]
+        if counts is not None:                   # a ragged batch: fr holds the packed frames [sum(counts), ...], visual rows come packed
+            B, F, (fh, fw) = len(counts), max(counts), fr.shape[1:3]
         decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
         logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
         attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty, sampling)
-        if prompt is not None or constraints is not None:    # one-shot beside the options: every issue of the call attaches all
+        if prompt is not None or constraints is not None or counts is not None:    # one-shot beside the options: every issue of the call attaches all
             attach_options = attach
 
             def attach():
@@ -1305,6 +1504,8 @@ class GitCaptioner(_NativeModule):
                     prompt.attach(self)
                 if constraints is not None:
                     constraints.attach(self)
+                if counts is not None:
+                    self._attach_counts(counts)
         first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
         if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
             first, decoded, logprobs = rank0, nbest, nbest_lp
@@ -1317,14 +1518,15 @@ class GitCaptioner(_NativeModule):
                 self._last_memory = None
                 return decoded, logprobs, None, None
             steps = torch.empty((max_steps - 1, B * beam_size, self.cfg.vocab_size), dtype=torch.float32, device=self._dev) if save_logits else None
-            vis = torch.empty((B, F * self.cfg.tokens_per_frame, self.cfg.enc_width), dtype=torch.float32, device=self._dev) if want_visual else None
+            vis_shape = (B, F * self.cfg.tokens_per_frame) if counts is None else (sum(counts) * self.cfg.tokens_per_frame,)
+            vis = torch.empty(vis_shape + (self.cfg.enc_width,), dtype=torch.float32, device=self._dev) if want_visual else None
             while len(self._inflight) >= 4:
                 self._wait_submission(self._inflight[0])
             ticket = ctypes.c_int(-1)
             tail = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(first[0]),
                     _lib.ptr(first[1]), _lib.ptr(steps), stream if stream is not None else self._stream(), ctypes.byref(ticket))
             if raw:
-                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fr.shape[2], fr.shape[3], *tail, before=attach)
+                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fh, fw, *tail, before=attach)
             else:
                 self._submit("gitcap_beam_search_submit", _lib.ptr(fr), B, F, *tail, before=attach)
             self._last_memory = None
@@ -1338,7 +1540,8 @@ class GitCaptioner(_NativeModule):
                     per_node_beam_size: int = 2, save_logits: bool = False, visual_features: bool = False,
                     num_keep_best: int = 1, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                     top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-                    prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> "InferFuture":
+                    prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+                    frame_counts=None) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
@@ -1355,6 +1558,16 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"max_steps {max_steps} > max_text_len={self.max_text_len}")
         if self._pending:
             self._flush_pending()
+        rg = None
+        if frame_counts is not None or not isinstance(src, torch.Tensor):
+            src, rg = self._ragged_input(src, frame_counts)
+        if rg is not None:
+            return self._infer_submit_ragged(rg, save_logits, visual_features, dict(
+                beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
+                num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling,
+                prompt=self._prompt(prompt, prompt_lengths, len(rg[1]), max_steps - 1, "max_steps - 1"),
+                constraints=self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps, beam_size * per_node_beam_size),
+                counts=rg[1]))
         fr, raw = self._check_frames(src)
         if fr.shape[0] > self.max_batch:
             raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
@@ -1379,6 +1592,28 @@ class GitCaptioner(_NativeModule):
             entry["sub"] = sub
         self._inflight.append(sub)
         return InferFuture(self, sub, kw, src.device, save_logits)
+
+    def _infer_submit_ragged(self, rg, save_logits, visual_features, kw):
+        """infer_async of a ragged batch: packed once (host clips in the staging ring), submitted with its counts attached."""
+        parts, counts, raw = rg
+        if len(counts) > self.max_batch:
+            raise ValueError(f"batch {len(counts)} > max_batch={self.max_batch}")
+        held = entry = stream = None
+        if parts[0].device.type == "cpu":
+            while len(self._inflight) >= 4:
+                self._wait_submission(self._inflight[0])
+            held = list(parts)
+            with torch.cuda.device(self._dev):
+                fr, entry, stream = self._stage_group(held, raw)
+        else:
+            fr = self._pack_to_device(parts, raw)
+        decoded, logprobs, steps, vis, ticket = self._infer_device(fr, sync=False, save_logits=save_logits, want_visual=visual_features,
+                                                                   raw=raw, stream=stream, **kw)
+        sub = _Submission(ticket, fr, (decoded, logprobs, steps, vis), False, parts=held)
+        if entry is not None:
+            entry["sub"] = sub
+        self._inflight.append(sub)
+        return InferFuture(self, sub, kw, parts[0].device, save_logits)
 
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
