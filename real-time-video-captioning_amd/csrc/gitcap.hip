@@ -67,13 +67,6 @@ struct DecLayer {
 
 }  // namespace
 
-// Options of one device-resident search (gitcap_attach_search_options): hypotheses kept per clip, repetition penalty, n-best outputs.
-// smp: the sampling branch (gitcap_attach_sampling), pending beside the options above and consumed with them.
-struct SampleOpt { bool on = false; float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; uint64_t seed = 0; };
-// gitcap_attach_constraints: what a step may not emit (include/gitcap.h); on = false: none
-struct ConsOpt { bool on = false; int ngram = 0, min_length = 0; const int32_t* suppress = nullptr; int n_suppress = 0; };
-struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; SampleOpt smp{}; };
-
 struct gitcap : HandleCore {
     gitcap_config c;
     std::map<std::string, DevTensor> w;
@@ -169,20 +162,13 @@ struct gitcap : HandleCore {
     hipStream_t txt_streams[NSLOT] = {nullptr, nullptr, nullptr, nullptr};   // owned; slot i decodes on txt_streams[i % n_txt]
     int n_txt = NSLOT;
     bool pipelined = false; // the launches being issued belong to a gitcap_greedy_submit (other batches share the chip)
-    // gitcap_attach_token_logprobs: the pending one-shot attachment (device fp32 [B][lp_ld]); taken by the next greedy-family call
-    float* lp_attach = nullptr;
-    int lp_ld = 0;
-    // gitcap_attach_search_options: the pending one-shot attachment; taken by the next beam-family call (n = 1, rp = 1: none)
-    SearchOpt so_attach{};
-    // gitcap_attach_prompt: the pending one-shot attachment (ids == nullptr: none); taken by the next greedy- or beam-family call
-    PromptArgs pr_attach{};
-    // gitcap_attach_constraints: the pending one-shot attachment (on = false: none); taken by the next greedy- or beam-family call.
-    // cons_cur: the constraints of the call whose launches are being issued (as cur_slot / pipelined); ban_ld: words per mask row
-    ConsOpt cons_attach{}, cons_cur{};
+    // The one-shot attachments (CallOpts, host_logic.h).  pending: what the gitcap_attach_* setters wrote and no call has taken yet:
+    // log-probabilities go to the next greedy-family call, search options + sampling to the next beam-family call, prompt and
+    // constraints to the next call of either family, frame counts to the next call that runs an image pass (calls that cannot
+    // take them refuse).  call: the options of the call whose launches are being issued (as cur_slot / pipelined), installed by
+    // the entry point's CallScope and empty outside it.  ban_ld: words per row of the constraints' ban mask
+    CallOpts pending{}, call{};
     int ban_ld = 0;
-    // gitcap_attach_frame_counts: the pending one-shot attachment (B == 0: none); taken by the next call that runs an image pass.
-    // fc_cur: the counts of the call whose image pass is being issued (as cons_cur)
-    RaggedCounts fc_attach{}, fc_cur{};
 
     // gitcap_distill (first use): the dual head's seven partials [slot 0's Mt][ntiles], both models' target logits
     // ([2][Mt])
@@ -465,7 +451,7 @@ int ln_reduce(gitcap* h, hipStream_t s, const float* slabs, int nslab, const flo
 }
 
 // projected image tokens -> decoder layers over image rows only; fills kv_img (text independent)
-// ragged_rows > 0 (a ragged batch, h->fc_cur its counts): the packed rows of B clips whose tables the slot's off / len hold, S the
+// ragged_rows > 0 (a ragged batch, h->call.fc its counts): the packed rows of B clips whose tables the slot's off / len hold, S the
 // longest clip's -- every GEMM and row kernel sees the ragged_rows valid rows, the attention runs its variable-length form
 int image_prefix(gitcap* h, int B, int S, hipStream_t s, int ragged_rows = 0) {
     const gitcap_config& c = h->c;
@@ -475,7 +461,7 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s, int ragged_rows = 0) {
     double attn_pairs = (double)B * S * S;                   // (query, key) pairs per head
     if (ragged) {
         attn_pairs = 0.0;
-        for (int b = 0; b < h->fc_cur.B; ++b) attn_pairs += (double)h->fc_cur.n[b] * h->N * h->fc_cur.n[b] * h->N;
+        for (int b = 0; b < h->call.fc.B; ++b) attn_pairs += (double)h->call.fc.n[b] * h->N * h->call.fc.n[b] * h->N;
     }
     int rc;
     h->n_staged = 0;
@@ -697,19 +683,12 @@ struct FrameSrc { const float* f32; const uint8_t* u8; int H, W; };     // fp32 
 static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t stream);
 static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out, hipStream_t s);
 
-// gitcap_attach_frame_counts' pending attachment: taken, and with that consumed, by every entry point that runs an image pass
-// (take_fc; the entry point makes it fc_cur, the counts of the call being issued, around its body -- as cons_cur) and refused by
-// those that cannot take it (fc_refuse)
-static RaggedCounts take_fc(gitcap* h) {
-    const RaggedCounts fc = h->fc_attach;
-    h->fc_attach.B = 0; h->fc_cur.B = 0;
-    return fc;
-}
-static int fc_refuse(gitcap* h, const char* who) {
-    const bool pending = h->fc_attach.B != 0 || h->fc_cur.B != 0;
-    h->fc_attach.B = 0; h->fc_cur.B = 0;
-    return pending ? fail(h, GITCAP_ERR_ARG, std::string(who) + ": per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take") : 0;
-}
+// What the entry points take of the pending attachments (CallScope, host_logic.h): taken parts are consumed whatever becomes of
+// the call; a call without an image pass of its own frames refuses frame counts (REFUSE_FC: cleared, and the call fails).
+constexpr unsigned TAKE_GREEDY = OPT_LP | OPT_PR | OPT_CO, TAKE_BEAM = OPT_SO | OPT_PR | OPT_CO;
+#define REFUSE_FC(h, who)                                                                    \
+    CallScope opts_((h)->pending, (h)->call, 0, OPT_FC);                                     \
+    if (opts_.refused) return fail(h, GITCAP_ERR_ARG, refused_message(who))
 
 // Pipelined submission: the image pass on the encoder stream, `text_loop` on the slot's decode stream (see gitcap_greedy_submit).
 // A failure after the first enqueue must not leave the slot unordered (the next user of the slot waits on ev_dec only): from
@@ -1055,13 +1034,10 @@ int gitcap_finalize_weights(gitcap_t* h) {
 
 int gitcap_encode(gitcap_t* h, const float* frames, int B, int F, float* visual_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode: null handle");
-    const RaggedCounts fc = take_fc(h);
+    CallScope opts(h->pending, h->call, OPT_FC, 0);
     GUARD(h);
     POLL(h);
-    h->fc_cur = fc;
-    const int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
-    h->fc_cur.B = 0;
-    return rc;
+    return encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, visual_out, (hipStream_t)stream);
 }
 
 // The encoder half of the image pass: B x F frames (checked by the caller) through patch gather, the ViT blocks and ln_post.
@@ -1165,7 +1141,7 @@ static int encode_impl(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
     int rc = src.u8 ? check_frames(h, src.u8, B, F, true) : check_frames(h, src.f32, B, F);
     if (rc) return rc;
     cur(h).have = false;
-    if (const RaggedCounts& fc = h->fc_cur; fc.B != 0) {
+    if (const RaggedCounts& fc = h->call.fc; fc.B != 0) {
         // packed clips: `frames` holds sum(counts) frames, F is the largest count
         if (fc.B != B) return fail(h, GITCAP_ERR_ARG, "encode: B differs from the attached frame counts'");
         int total = 0, mx = 0, mn = 256;
@@ -1202,7 +1178,7 @@ static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
 
 int gitcap_set_visual(gitcap_t* h, const float* visual, int B, int S_img, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "set_visual: null handle");
-    if (int rc = fc_refuse(h, "set_visual")) return rc;
+    REFUSE_FC(h, "set_visual");
     GUARD(h);
     POLL(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
@@ -1229,17 +1205,18 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
 }
 
 // token steps t_first .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
-// lp (nullable, row pitch ld_lp): column t = the log-probability of the token step t emitted
-// prompt (nullable): steps that write a position inside a row's prompt take the prompt's token there (launch_argmax_final)
-static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, float* lp = nullptr, int ld_lp = 0,
-                       const PromptArgs* prompt = nullptr, int t_first = 0) {
+// The call's options (h->call): lp (row pitch lp.ld): column t = the log-probability of the token step t emitted; pr: steps that
+// write a position inside a row's prompt take the prompt's token there (launch_argmax_final); co: the constraints
+static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, int t_first = 0) {
+    const LpAttach& lp = h->call.lp;
+    const PromptArgs* prompt = h->call.pr.ids ? &h->call.pr : nullptr;
     const bool chain = text_chain_ok(h, rows, 1);
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
     // bits -- and measured nothing: 4.926 vs 4.912 ms per 20-token caption; tools/experiments/argmax_fold_rows.txt.)
     bool have_rows = false;                                  // the previous step's arg-max launch embedded this step's input rows
     // constraints attached: one small launch per step builds the rows' ban mask from the ids so far (prefix 0 .. t, CLS and prompt
     // included), and the head runs in its BAN form; a position a prompt forces takes the prompt's token whatever is banned
-    const ConsOpt& co = h->cons_cur;
+    const ConsOpt& co = h->call.co;
     const HeadBan bn{cur(h).ban_mask, h->ban_ld};
     for (int t = t_first; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
@@ -1248,7 +1225,7 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
             HIP_OK(h, launch_ban_mask(ids_out, ld, rows, t + 1, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress,
                                       h->c.vocab_size, cur(h).ban_mask, bn.ld, s));
         const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next,
-                                    lp ? lp + t : nullptr, ld_lp, nullptr, prompt, co.on ? &bn : nullptr);
+                                    lp.p ? lp.p + t : nullptr, lp.ld, nullptr, prompt, co.on ? &bn : nullptr);
         if (rc) return rc;
         have_rows = next;
     }
@@ -1259,8 +1236,9 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
 // clips are independent, every kernel is batch invariant, the captions were bitwise the same: 16 clips 323-325 / 580 / 600 us
 // per token step against 302 for one loop (profiles/r04_sync_call_split_token_loop.txt).  Chains of ~6 us launches on
 // different streams do not overlap each other the way one chain overlaps an image pass.  Removed.)
-static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s,
-                            LpAttach lp = LpAttach{nullptr, 0}, PromptArgs pr = PromptArgs{}) {
+static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
+    const LpAttach& lp = h->call.lp;
+    const PromptArgs& pr = h->call.pr;
     const int ld = max_len + 1;
     gitcap::Slot& sl = cur(h);
     int rc;
@@ -1268,7 +1246,7 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
     if (!pr.ids) {
         // CLS start tokens [B,1] (model.py:171)
         HIP_OK(h, launch_fill_i64(ids_out, ld, B, h->c.cls_token_id, s));
-        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld))) return rc;
+        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s))) return rc;
     } else {
         // the prompts [B, lengths[b]] in place of the lone CLS (model.py:432-437)
         HIP_OK(h, launch_fill_prompt(ids_out, ld, B, pr, s));
@@ -1276,7 +1254,7 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
         // slot's row workspace holds B x min_len rows; the token loop goes on behind it.  Steps that write a position below the
         // longest prompt run the forced arg-max.
         // (with constraints attached the prompt runs as forced steps: the one-pass plan is not combined with the ban mask)
-        const int P = (g_prompt_prefill && !h->cons_cur.on && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
+        const int P = (g_prompt_prefill && !h->call.co.on && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
         int t_first = 0;
         if (P > 1) {
             if (lp.p) HIP_OK(h, hipMemset2DAsync(lp.p, (size_t)lp.ld * 4, 0, (size_t)(P - 1) * 4, B, s));    // forced positions: 0.0f
@@ -1284,7 +1262,7 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
                                    lp.p ? lp.p + (P - 1) : nullptr, lp.ld, nullptr, &pr))) return rc;
             t_first = P;
         }
-        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, lp.p, lp.ld, &pr, t_first))) return rc;
+        if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, t_first))) return rc;
     }
     if (steps_out) HIP_OK(h, launch_finish_steps(sl.sep_cnt, B, max_len, stop, steps_out, s));
     return 0;
@@ -1292,71 +1270,53 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
 
 }  // extern "C"
 
-// gitcap_attach_prompt's pending attachment: taken, and with that consumed, by every greedy- and beam-family entry point
-static PromptArgs take_prompt(gitcap* h) {
-    const PromptArgs pr = h->pr_attach;
-    h->pr_attach = PromptArgs{};
-    return pr;
-}
-
-// gitcap_attach_constraints' pending attachment: taken like the prompt's.  cons_enter makes it the constraints of the call being
-// issued, or refuses a call whose rows could lose every column: each step bans at most n_suppress listed ids, one id per prefix
-// position and SEP.
-static ConsOpt take_cons(gitcap* h) {
-    const ConsOpt c = h->cons_attach;
-    h->cons_attach = ConsOpt{};
-    h->cons_cur = ConsOpt{};
-    return c;
-}
-static int cons_enter(gitcap* h, const ConsOpt& co, int max_len, int need, const char* who) {
-    if (!co.on) return 0;
-    if ((int64_t)co.n_suppress + max_len + need > h->c.vocab_size)
+// The call's constraints refuse a call whose rows could lose every column: each step bans at most n_suppress listed ids, one id per
+// prefix position and SEP.
+static int cons_check(gitcap* h, int max_len, int need, const char* who) {
+    const ConsOpt& co = h->call.co;
+    if (co.on && (int64_t)co.n_suppress + max_len + need > h->c.vocab_size)
         return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)");
-    h->cons_cur = co;
     return 0;
 }
 
-// The head of every greedy-family entry point: the null check (its message names the entry point), the pending log-probability
-// and prompt attachments are taken (a call refused below has consumed them), device, exchange health, the argument checks; then
-// body(lp, pr).
+// The head of every greedy-family entry point: the null check (its message names the entry point), the pending attachments in
+// `take` become the call's options (a call refused below has consumed them), device, exchange health, the argument checks; then
+// body().  refuse: the window call's OPT_FC -- it fails where its image prefix would start.
 template <typename Body>
-static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, int max_len, int stop, const int64_t* ids_out, Body body) {
+static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, unsigned take, unsigned refuse, int max_len, int stop,
+                        const int64_t* ids_out, Body body) {
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
-    const LpAttach lp = take_lp(h);
-    const PromptArgs pr = take_prompt(h);
-    const ConsOpt co = take_cons(h);
-    const RaggedCounts fc = take_fc(h);
+    CallScope opts(h->pending, h->call, take, refuse);
+    const LpAttach& lp = h->call.lp;
+    const PromptArgs& pr = h->call.pr;
     GUARD(h);
     POLL(h);
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, "greedy: bad arguments");
     if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "greedy: max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
     if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
-    int rc = lp_check(h, "greedy", lp, max_len);
-    if (!rc) rc = cons_enter(h, co, max_len, 1, "greedy");
-    h->fc_cur = fc;
-    if (!rc) rc = body(lp, pr);
-    h->cons_cur = ConsOpt{};
-    h->fc_cur.B = 0;
-    return rc;
+    if (int rc = lp_check(h, "greedy", lp, max_len)) return rc;
+    if (int rc = cons_check(h, max_len, 1, "greedy")) return rc;
+    if (opts.refused) return fail(h, GITCAP_ERR_ARG, refused_message("window"));
+    return body();
 }
 
 // synchronous: image pass and token loop on the caller's stream, slot 0 (a raw source is checked by the image pass alone)
 static int greedy_sync(gitcap* h, const char* null_msg, FrameSrc src, int B, int F, int max_len, int stop, int64_t* ids_out,
                        int32_t* steps_out, hipStream_t s) {
-    return greedy_entry(h, true, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
+    return greedy_entry(h, true, null_msg, TAKE_GREEDY | OPT_FC, 0, max_len, stop, ids_out, [&]() -> int {
         if (int rc = encode_sync(h, src, B, F, nullptr, s)) return rc;
-        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, pr);
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s);
     });
 }
 
 // submitted: lp's buffer stays valid until the wait, like ids_out; raw: camera frames, checked before the submission takes a slot
 static int greedy_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, int max_len, int stop, int64_t* ids_out,
                          int32_t* steps_out, hipStream_t stream, int* ticket) {
-    return greedy_entry(h, ticket != nullptr, null_msg, max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
+    return greedy_entry(h, ticket != nullptr, null_msg, TAKE_GREEDY | OPT_FC, 0, max_len, stop, ids_out, [&]() -> int {
         if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
         return submit_common(h, src, B, F, nullptr, stream, ticket, [&](hipStream_t s) {
-            return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, pr);
+            return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s);
         });
     });
 }
@@ -1369,13 +1329,10 @@ int gitcap_greedy(gitcap_t* h, const float* frames, int B, int F, int max_len, i
 
 int gitcap_encode_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, float* visual_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "encode_raw: null handle");
-    const RaggedCounts fc = take_fc(h);
+    CallScope opts(h->pending, h->call, OPT_FC, 0);
     GUARD(h);
     POLL(h);
-    h->fc_cur = fc;
-    const int rc = encode_sync(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
-    h->fc_cur.B = 0;
-    return rc;
+    return encode_sync(h, FrameSrc{nullptr, frames_hwc_bgr, H, W}, B, F, visual_out, (hipStream_t)stream);
 }
 
 int gitcap_greedy_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, int F, int H, int W, int max_len, int stop,
@@ -1410,12 +1367,14 @@ int gitcap_greedy_wait(gitcap_t* h, int ticket, void* stream) {
 
 // The search loop over the image K/V of the selected slot (its beam state, text K/V and row workspace), on stream s.
 // step_logits_out (nullable): [max_steps - 1][B * beams][V], the raw logits of every step (what model.py:521 saves).
-// so: the call's search options.  rp != 1: the candidates are ranked on the logits penalised at the columns of every row's prefix
+// so (h->call.so): the call's search options.  rp != 1: the candidates are ranked on the logits penalised at the columns of every row's prefix
 // (the saved step logits stay raw, model.py:521 comes before :522); n > 1: the bookkeeping keeps n hypotheses in the slot's nb_* state.
 // decoded_out / logprobs_out receive rank 0, the attached outputs all n ranks.
 static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_penalty, int per_node_beam_size,
-                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, const SearchOpt& so, const PromptArgs& pr,
-                     hipStream_t s) {
+                     int64_t* decoded_out, float* logprobs_out, float* step_logits_out, hipStream_t s) {
+    const SearchOpt& so = h->call.so;
+    const PromptArgs& pr = h->call.pr;
+    const ConsOpt& co = h->call.co;
     const PromptArgs* prompt = pr.ids ? &pr : nullptr;
     const int forced_all = prompt ? pr.min_len : 1;          // steps cur_len < forced_all rank nothing: every clip is inside its prompt
     const int rows = B * beams, K = beams * per_node_beam_size, V = h->c.vocab_size, L = max_steps;
@@ -1440,7 +1399,6 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
         if (rc) return rc;
         // constraints attached: the mask of the B * beams rows, each from the buffer that holds its current prefix
-        const ConsOpt& co = h->cons_cur;
         const HeadBan bn{sl.ban_mask, h->ban_ld};
         const HeadBan* ban = co.on ? &bn : nullptr;
         if (ranked && ban)
@@ -1465,17 +1423,15 @@ int gitcap_beam_search_wait(gitcap_t* h, int ticket, void* stream) { return gitc
 
 }  // extern "C"
 
-// The head of every beam-search entry point (as greedy_entry): the pending search options are taken (a call refused below has
-// consumed them), and so is the pending prompt; then `body(so, pr)`.
+// The head of every beam-search entry point (as greedy_entry): the pending attachments in `take` become the call's options (a call
+// refused below has consumed them); then `body()`.
 template <typename Body>
-static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, int max_steps, int per_node_beam_size,
-                      const int64_t* decoded_out, const float* logprobs_out, Body body) {
+static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, unsigned take, unsigned refuse, int beams, int max_steps,
+                      int per_node_beam_size, const int64_t* decoded_out, const float* logprobs_out, Body body) {
     if (!h || !args_ok) return fail(h, GITCAP_ERR_ARG, null_msg);
-    const SearchOpt so = h->so_attach;
-    h->so_attach = SearchOpt{};
-    const PromptArgs pr = take_prompt(h);
-    const ConsOpt co = take_cons(h);
-    const RaggedCounts fc = take_fc(h);
+    CallScope opts(h->pending, h->call, take, refuse);
+    const SearchOpt& so = h->call.so;
+    const PromptArgs& pr = h->call.pr;
     GUARD(h);
     POLL(h);
     if (!decoded_out || !logprobs_out || beams < 1 || per_node_beam_size < 1) return fail(h, GITCAP_ERR_ARG, "beam_search: bad arguments");
@@ -1494,22 +1450,19 @@ static int beam_entry(gitcap* h, bool args_ok, const char* null_msg, int beams, 
         return fail(h, GITCAP_ERR_ARG, "beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep");
     if (so.smp.on && h->c.vocab_size > 32768) return fail(h, GITCAP_ERR_ARG, "beam_search: sampling takes a vocabulary of at most 32768 columns");
     // (a beam row must keep at least beams * per_node_beam_size allowed columns: launch_beam_step is never handed a sentinel)
-    int rc = cons_enter(h, co, max_steps, beams * per_node_beam_size, "beam_search");
-    h->fc_cur = fc;
-    if (!rc) rc = body(so, pr);
-    h->cons_cur = ConsOpt{};
-    h->fc_cur.B = 0;
-    return rc;
+    if (int rc = cons_check(h, max_steps, beams * per_node_beam_size, "beam_search")) return rc;
+    if (opts.refused) return fail(h, GITCAP_ERR_ARG, refused_message("window"));
+    return body();
 }
 
 extern "C" {
 
 int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams, int max_steps, float length_penalty,
                        int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
+    return beam_entry(h, true, "beam_search: null handle", TAKE_BEAM | OPT_FC, 0, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s)) return rc;
-        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, pr, s);
+        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
     });
 }
 
@@ -1517,10 +1470,10 @@ int gitcap_beam_search(gitcap_t* h, const float* frames, int B, int F, int beams
 static int beam_submit(gitcap* h, const char* null_msg, FrameSrc src, bool raw, int B, int F, float* visual_out, int beams, int max_steps,
                        float length_penalty, int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, float* step_logits_out,
                        hipStream_t stream, int* ticket) {
-    return beam_entry(h, ticket != nullptr, null_msg, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
+    return beam_entry(h, ticket != nullptr, null_msg, TAKE_BEAM | OPT_FC, 0, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
         if (int rc = raw ? check_raw(h, src.u8, B, F, src.H, src.W) : 0) return rc;
         return submit_common(h, src, B, F, visual_out, stream, ticket, [&](hipStream_t s) {
-            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, so, pr, s);
+            return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, step_logits_out, s);
         });
     });
 }
@@ -1547,7 +1500,7 @@ int gitcap_beam_search_raw_submit(gitcap_t* h, const uint8_t* frames_hwc_bgr, in
 
 int gitcap_window_reset(gitcap_t* h, int B, int F) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "window_reset: null handle");
-    if (int rc = fc_refuse(h, "window_reset")) return rc;
+    REFUSE_FC(h, "window_reset");
     GUARD(h);
     if (B < 0 || (B > 0 && (B > h->c.max_batch || F < 1 || F > h->c.max_frames || (h->c.num_frames > 0 && F > h->c.num_frames))))
         return fail(h, GITCAP_ERR_ARG, "window_reset: B / F outside the sizes the handle was created for");
@@ -1573,7 +1526,7 @@ int gitcap_window_reset(gitcap_t* h, int B, int F) {
 
 // encode n new frames of each clip and append them to the ring: fp32 ln_post rows -> staging -> ring slots
 static int window_push(gitcap* h, FrameSrc src, int B, int n, hipStream_t s) {
-    if (int rc = fc_refuse(h, "window_push")) return rc;
+    REFUSE_FC(h, "window_push");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "window_push: no frame window (gitcap_window_reset first)");
     if (B != h->win_B || n < 1 || n > h->win.slots) return fail(h, GITCAP_ERR_ARG, "window_push: B differs from the reset's, or n outside [1, F]");
     int rc = src.u8 ? check_raw(h, src.u8, B, n, src.H, src.W) : check_frames(h, src.f32, B, n);
@@ -1610,7 +1563,6 @@ int gitcap_window_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, int B, in
 
 // the current window -> decoder input (+ visual features) -> image prefix on slot 0
 static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
-    if (int rc = fc_refuse(h, "window")) return rc;
     if (!h->win_ring || !h->win.full()) return fail(h, GITCAP_ERR_STATE, "window: fewer than F frames pushed since the reset");
     if (((uintptr_t)visual_out & 15) != 0) return fail(h, GITCAP_ERR_ARG, "window: visual_out must be 16-byte aligned");
     const int B = h->win_B, F = h->win.slots, N = h->N, Dv = h->Dv;
@@ -1631,19 +1583,19 @@ static int window_prefix(gitcap* h, float* visual_out, hipStream_t s) {
 }
 
 int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    return greedy_entry(h, true, "window_greedy: null handle", max_len, stop, ids_out, [&](const LpAttach& lp, const PromptArgs& pr) -> int {
+    return greedy_entry(h, true, "window_greedy: null handle", TAKE_GREEDY, OPT_FC, max_len, stop, ids_out, [&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = window_prefix(h, visual_out, s)) return rc;
-        return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s, lp, pr);
+        return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
     });
 }
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream) {
-    return beam_entry(h, true, "window_beam_search: null handle", beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&](const SearchOpt& so, const PromptArgs& pr) -> int {
+    return beam_entry(h, true, "window_beam_search: null handle", TAKE_BEAM, OPT_FC, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (int rc = window_prefix(h, visual_out, s)) return rc;
-        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, so, pr, s);
+        return beam_loop(h, h->win_B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
     });
 }
 
@@ -1657,11 +1609,11 @@ static int ensure_amax_sum(gitcap* h) {
 
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: null handle");
-    if (!logprobs_out) { h->lp_attach = nullptr; h->lp_ld = 0; return 0; }
+    if (!logprobs_out) { h->pending.lp = LpAttach{}; return 0; }
     if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_token_logprobs: ld < 1 or a misaligned pointer");
     GUARD(h);
     if (int rc = ensure_amax_sum(h)) return rc;
-    h->lp_attach = logprobs_out; h->lp_ld = ld;
+    h->pending.lp = LpAttach{logprobs_out, ld};
     return 0;
 }
 
@@ -1758,18 +1710,18 @@ int gitcap_distill(gitcap_t* h, gitcap_student_t* st, const int64_t* ids, int ld
 
 int gitcap_attach_prompt(gitcap_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_prompt: null handle");
-    h->pr_attach = PromptArgs{};
+    h->pending.pr = PromptArgs{};
     if (!prompt_ids && !lengths) return 0;                   // detach
     if (!prompt_ids || !lengths) return fail(h, GITCAP_ERR_ARG, "attach_prompt: prompt_ids and lengths are both required");
     if (((uintptr_t)prompt_ids & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return fail(h, GITCAP_ERR_ARG, "attach_prompt: a misaligned pointer");
     if (min_len < 1 || max_len < min_len || ld < max_len) return fail(h, GITCAP_ERR_ARG, "attach_prompt: need 1 <= min_len <= max_len <= ld");
-    h->pr_attach = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
+    h->pending.pr = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
     return 0;
 }
 
 int gitcap_attach_frame_counts(gitcap_t* h, const int32_t* counts, int B) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: null handle");
-    h->fc_attach.B = 0;
+    h->pending.fc.B = 0;
     if (!counts) return 0;                                   // detach
     if (B < 1 || B > h->c.max_batch || B > 256) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: B outside [1, min(max_batch, 256)]");
     const int limit = std::min(255, h->c.num_frames > 0 ? std::min(h->c.max_frames, h->c.num_frames) : h->c.max_frames);
@@ -1781,14 +1733,14 @@ int gitcap_attach_frame_counts(gitcap_t* h, const int32_t* counts, int B) {
         total += counts[b];
     }
     if (total > (int64_t)h->c.max_batch * h->c.max_frames) return fail(h, GITCAP_ERR_ARG, "attach_frame_counts: the counts sum beyond max_batch * max_frames");
-    for (int b = 0; b < B; ++b) h->fc_attach.n[b] = (unsigned char)counts[b];
-    h->fc_attach.B = B;
+    for (int b = 0; b < B; ++b) h->pending.fc.n[b] = (unsigned char)counts[b];
+    h->pending.fc.B = B;
     return 0;
 }
 
 int gitcap_attach_constraints(gitcap_t* h, const gitcap_constraints* c) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_constraints: null handle");
-    h->cons_attach = ConsOpt{};
+    h->pending.co = ConsOpt{};
     if (!c) return 0;                                        // detach
     if (c->no_repeat_ngram_size < 0 || c->min_length < 0 || c->n_suppress < 0) return fail(h, GITCAP_ERR_ARG, "attach_constraints: a negative field");
     if (c->n_suppress > 256) return fail(h, GITCAP_ERR_ARG, "attach_constraints: n_suppress > 256");
@@ -1801,14 +1753,14 @@ int gitcap_attach_constraints(gitcap_t* h, const gitcap_constraints* c) {
         for (auto& sl : h->slots)
             if (int rc = dev_alloc(h, &sl.ban_mask, (size_t)h->R * (size_t)h->ban_ld)) { h->slots[0].ban_mask = nullptr; return rc; }
     }
-    h->cons_attach = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
+    h->pending.co = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
     return 0;
 }
 
 int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_search_options: null handle");
-    const SampleOpt smp = h->so_attach.smp;                  // a pending gitcap_attach_sampling stays pending
-    if (!opt) { h->so_attach = SearchOpt{}; h->so_attach.smp = smp; return 0; }
+    const SampleOpt smp = h->pending.so.smp;                 // a pending gitcap_attach_sampling stays pending
+    if (!opt) { h->pending.so = SearchOpt{}; h->pending.so.smp = smp; return 0; }
     if (opt->num_keep_best < 1 || opt->num_keep_best > 16)
         return fail(h, GITCAP_ERR_ARG, "attach_search_options: num_keep_best outside [1, 16]");
     if (!(opt->repetition_penalty > 0.f) || !std::isfinite(opt->repetition_penalty))
@@ -1827,18 +1779,18 @@ int gitcap_attach_search_options(gitcap_t* h, const gitcap_search_options* opt) 
             if (rc) { h->slots[0].nb_len = nullptr; return rc; }
         }
     }
-    h->so_attach = SearchOpt{opt->num_keep_best, opt->repetition_penalty, opt->nbest_out, opt->nbest_logprobs_out, smp};
+    h->pending.so = SearchOpt{opt->num_keep_best, opt->repetition_penalty, opt->nbest_out, opt->nbest_logprobs_out, smp};
     return 0;
 }
 
 int gitcap_attach_sampling(gitcap_t* h, const gitcap_sampling_options* opt) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "attach_sampling: null handle");
-    if (!opt) { h->so_attach.smp = SampleOpt{}; return 0; }
+    if (!opt) { h->pending.so.smp = SampleOpt{}; return 0; }
     if (!(opt->temperature > 0.f) || !std::isfinite(opt->temperature))
         return fail(h, GITCAP_ERR_ARG, "attach_sampling: temperature must be finite and > 0");
     if (opt->top_k < 0) return fail(h, GITCAP_ERR_ARG, "attach_sampling: top_k must be >= 0");
     if (!(opt->top_p > 0.f) || !(opt->top_p <= 1.0f)) return fail(h, GITCAP_ERR_ARG, "attach_sampling: top_p outside (0, 1]");
-    h->so_attach.smp = SampleOpt{true, opt->temperature, opt->top_k, opt->top_p, opt->seed};
+    h->pending.so.smp = SampleOpt{true, opt->temperature, opt->top_k, opt->top_p, opt->seed};
     return 0;
 }
 

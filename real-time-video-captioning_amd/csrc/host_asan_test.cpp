@@ -9,6 +9,72 @@
 
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "host_asan_test: %s:%d: %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
 
+// Per-call options: what each family of entry points takes and refuses (the masks gitcap.hip states), on a record with every part
+// attached.  `early`: the call returns before its body, as one refused for its arguments does.
+static CallOpts all_attached(float* lp, int64_t* nb, const int64_t* ids, const int32_t* len) {
+    CallOpts o{};
+    o.lp = LpAttach{lp, 8};
+    o.so = SearchOpt{2, 1.5f, nb, lp, SampleOpt{true, 0.7f, 5, 1.0f, 9}};
+    o.pr = PromptArgs{ids, 4, len, 1, 3};
+    o.co = ConsOpt{true, 2, 3, len, 1};
+    o.fc.B = 3; o.fc.n[0] = 2; o.fc.n[1] = 255; o.fc.n[2] = 1;
+    return o;
+}
+static int entered(CallOpts& pending, CallOpts& call, unsigned take, unsigned refuse, bool early, unsigned* seen, unsigned* refused) {
+    CallScope scope(pending, call, take, refuse);
+    *seen = opts_set(call);
+    *refused = scope.refused;
+    if (early) return 1;
+    CHECK(&scope.call == &call);
+    return 0;
+}
+static int call_opts_test() {
+    float lp[1]; int64_t nb[1]; const int64_t ids[1] = {0}; const int32_t len[1] = {1};
+    const unsigned ALL = OPT_LP | OPT_SO | OPT_PR | OPT_CO | OPT_FC, GREEDY = OPT_LP | OPT_PR | OPT_CO, BEAM = OPT_SO | OPT_PR | OPT_CO;
+    { CallOpts none{}; CHECK(opts_set(none) == 0 && opts_set(all_attached(lp, nb, ids, len)) == ALL); }
+    struct Row { unsigned take, refuse; } rows[] = {
+        {GREEDY | OPT_FC, 0},       // gitcap_greedy, _raw, _submit, _raw_submit
+        {GREEDY, OPT_FC},           // gitcap_window_greedy
+        {BEAM | OPT_FC, 0},         // gitcap_beam_search, _submit, _raw_submit
+        {BEAM, OPT_FC},             // gitcap_window_beam_search
+        {OPT_FC, 0},                // gitcap_encode, gitcap_encode_raw
+        {0, OPT_FC},                // gitcap_set_visual, gitcap_window_reset, gitcap_window_push(_raw)
+        {0, 0},                     // score, distill, text_forward: everything stays pending
+    };
+    for (const Row& r : rows)
+        for (int early = 0; early < 2; ++early) {
+            CallOpts pending = all_attached(lp, nb, ids, len), call{};
+            unsigned seen = 0, refused = 0;
+            CHECK(entered(pending, call, r.take, r.refuse, early != 0, &seen, &refused) == early);
+            CHECK(seen == r.take && refused == r.refuse);                     // the body sees exactly the taken parts
+            CHECK(opts_set(call) == 0 && call.fc.B == 0);                     // the scope emptied `call`, on the early return too
+            CHECK(opts_set(pending) == (ALL & ~(r.take | r.refuse)));         // taken (even by a failed call) and refused: gone
+            // a second call finds nothing to take or refuse, and what stayed pending is intact
+            CHECK(entered(pending, call, r.take, r.refuse, false, &seen, &refused) == 0 && seen == 0 && refused == 0);
+            if (!(r.take & OPT_LP)) CHECK(pending.lp.p == lp && pending.lp.ld == 8);
+            if (!(r.take & OPT_SO)) CHECK(pending.so.n == 2 && pending.so.rp == 1.5f && pending.so.nbest == nb && pending.so.smp.on && pending.so.smp.seed == 9);
+            if (!(r.take & OPT_PR)) CHECK(pending.pr.ids == ids && pending.pr.lengths == len && pending.pr.max_len == 3);
+            if (!(r.take & OPT_CO)) CHECK(pending.co.on && pending.co.ngram == 2 && pending.co.n_suppress == 1);
+            if (!((r.take | r.refuse) & OPT_FC)) CHECK(pending.fc.B == 3 && pending.fc.n[1] == 255);
+        }
+    // the taken values arrive whole; nothing is refused where nothing is attached; sampling alone counts as search options
+    {
+        CallOpts pending = all_attached(lp, nb, ids, len);
+        unsigned refused = 7;
+        const CallOpts got = take_opts(pending, BEAM | OPT_FC, 0, &refused);
+        CHECK(refused == 0 && got.lp.p == nullptr && got.so.n == 2 && got.so.nbest_lp == lp && got.so.smp.top_k == 5 && got.pr.min_len == 1);
+        CHECK(got.co.suppress == len && got.fc.B == 3 && got.fc.n[0] == 2 && got.fc.n[2] == 1 && pending.lp.p == lp);
+        CHECK(pending.so.n == 1 && pending.so.rp == 1.0f && !pending.so.smp.on && !pending.pr.ids && !pending.co.on && pending.fc.B == 0);
+        (void)take_opts(pending, 0, OPT_FC, &refused);
+        CHECK(refused == 0);
+        CallOpts smp{};
+        smp.so.smp.on = true;
+        CHECK(opts_set(smp) == OPT_SO);
+    }
+    CHECK(refused_message("window") == "window: per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take");
+    return 0;
+}
+
 int main() {
     // e4m3: every finite code round-trips through value -> exact code
     for (int code = 0; code < 256; ++code) {
@@ -131,6 +197,7 @@ int main() {
         CHECK(!exchange_poll(hs, 0u) && hs.degraded && hs.trips == 1);          // the caller cleared the word: quiet again, still degraded
         CHECK(exchange_poll(hs, 7u) && hs.degraded && hs.trips == 2);
     }
+    if (int rc = call_opts_test()) return rc;
     CHECK(pad_to(18912, 256) == 18944 && pad_to(256, 256) == 256 && pad_to(1, 16) == 16);
     std::puts("host_asan_test ok");
     return 0;

@@ -166,6 +166,61 @@ struct RingCursor {
     void clear() { count = 0; }     // the entries may be undefined (a failed push, a failed exchange): pushed again by the caller
 };
 
+// ---- per-call options: the one-shot attachments of gitcap_attach_* --------------------------------------------------------
+// Each setter writes its part of the handle's `pending` record; an entry point states which parts it takes and which it refuses,
+// and the taken parts are the handle's `call` record -- the options of the call whose launches are being issued -- until it returns.
+// token log-probabilities (*_attach_token_logprobs): device fp32 [B][ld]; p == nullptr: none
+struct LpAttach { float* p = nullptr; int ld = 0; };
+// A batch of prompts (gitcap_attach_prompt): ids device int64 [rows][ld], lengths device int32 [rows] = valid tokens per row (the
+// kernels clamp them to [1, max_len]; max_len <= ld, so a wrong length reads no other row), min_len / max_len = the host's bounds.
+// ids == nullptr: none.  (Travels to the kernels by value, as RaggedCounts: plain members only.)
+struct PromptArgs { const int64_t* ids; int ld; const int32_t* lengths; int min_len, max_len; };
+// Ragged batches (gitcap_attach_frame_counts): clips of 1..255 frames each, packed clip-major; B == 0: none
+struct RaggedCounts { int B; unsigned char n[256]; };
+// Options of one device-resident search (gitcap_attach_search_options): hypotheses kept per clip, repetition penalty, n-best outputs
+// (n = 1, rp = 1: none).  smp: the sampling branch (gitcap_attach_sampling), pending beside the options above and consumed with them.
+struct SampleOpt { bool on = false; float temperature = 1.0f; int top_k = 0; float top_p = 1.0f; uint64_t seed = 0; };
+struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* nbest_lp = nullptr; SampleOpt smp{}; };
+// gitcap_attach_constraints: what a step may not emit (include/gitcap.h); on = false: none
+struct ConsOpt { bool on = false; int ngram = 0, min_length = 0; const int32_t* suppress = nullptr; int n_suppress = 0; };
+
+struct CallOpts { LpAttach lp{}; SearchOpt so{}; PromptArgs pr{}; ConsOpt co{}; RaggedCounts fc{}; };
+enum : unsigned { OPT_LP = 1, OPT_SO = 2, OPT_PR = 4, OPT_CO = 8, OPT_FC = 16 };
+
+inline unsigned opts_set(const CallOpts& o) {       // the parts that hold an attachment
+    return (o.lp.p ? OPT_LP : 0u) | (o.so.n != 1 || o.so.rp != 1.0f || o.so.smp.on ? OPT_SO : 0u) | (o.pr.ids ? OPT_PR : 0u) |
+           (o.co.on ? OPT_CO : 0u) | (o.fc.B != 0 ? OPT_FC : 0u);
+}
+inline void opts_clear(CallOpts& o, unsigned parts) {
+    if (parts & OPT_LP) o.lp = LpAttach{};
+    if (parts & OPT_SO) o.so = SearchOpt{};
+    if (parts & OPT_PR) o.pr = PromptArgs{};
+    if (parts & OPT_CO) o.co = ConsOpt{};
+    if (parts & OPT_FC) o.fc.B = 0;
+}
+// The parts in `take` move out of `pending` into the result (consumed, whatever becomes of the call); the parts in `refuse` are
+// cleared, *refused = those of them that held an attachment; every other part stays pending.
+inline CallOpts take_opts(CallOpts& pending, unsigned take, unsigned refuse, unsigned* refused) {
+    *refused = opts_set(pending) & refuse;
+    CallOpts out = pending;
+    opts_clear(out, ~take);
+    opts_clear(pending, take | refuse);
+    return out;
+}
+// An entry point's take: `call` holds the taken parts while the scope lives and is empty again on every exit.
+struct CallScope {
+    CallOpts& call;
+    unsigned refused = 0;
+    CallScope(CallOpts& pending, CallOpts& call_, unsigned take, unsigned refuse) : call(call_) { call = take_opts(pending, take, refuse, &refused); }
+    ~CallScope() { call = CallOpts{}; }
+    CallScope(const CallScope&) = delete;
+    CallScope& operator=(const CallScope&) = delete;
+};
+// the message of a call that refuses an attachment (only frame counts are ever refused)
+inline std::string refused_message(const char* who) {
+    return std::string(who) + ": per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take";
+}
+
 // ---- residual + LayerNorm GEMM: workgroup -> tile ----------------------------------------------------------------
 // The N/256 tiles of a 256-row block wait for each other (statistics exchange, gemm_epilogue.h), so they must be
 // consecutive workgroups of ONE XCD's dispatch sequence.  Workgroup b runs on XCD b % 8 as that XCD's (b / 8)-th

@@ -91,15 +91,8 @@ int upload_bf16_panel(H* h, DevTensor& t, const float* data, int64_t rows, int64
     return 0;
 }
 
-// The pending attachment of *_attach_token_logprobs (handle fields lp_attach / lp_ld): taken, and with that consumed, by every
-// greedy-family entry point before its argument checks.  `who` leads the message ("greedy", "student_greedy", ...).
-struct LpAttach { float* p; int ld; };
-template <class H>
-LpAttach take_lp(H* h) {
-    const LpAttach a{h->lp_attach, h->lp_ld};
-    h->lp_attach = nullptr; h->lp_ld = 0;
-    return a;
-}
+// The attachment of *_attach_token_logprobs (LpAttach, host_logic.h) is taken, and with that consumed, by every greedy-family
+// entry point before its argument checks.  `who` leads the message ("greedy", "student_greedy", ...).
 template <class H>
 int lp_check(H* h, const char* who, const LpAttach& lp, int max_len) {
     if (lp.p && lp.ld < max_len) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached token log-probability buffer has ld < max_len");

@@ -1,6 +1,7 @@
 // Launcher declarations for the gfx950 kernels behind libgitcap's C ABI.
 #pragma once
 #include "common.h"
+#include "host_logic.h"      // PromptArgs, RaggedCounts: the plain option structs that travel to kernels by value
 #include <atomic>
 #include <cstddef>
 
@@ -229,10 +230,7 @@ hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
 // emb->position -- word + position embedding -> LayerNorm -> xf / xb row r (rowln.h: the code of launch_embed_text) -- so
 // the next token step starts at its q|k|v projection.
 struct NextEmbed { const float *word, *pos, *gamma, *beta; float eps; int D, vocab, position; float* xf; bf16_t* xb; };
-// A batch of prompts (gitcap_attach_prompt): ids device int64 [rows][ld], lengths device int32 [rows] = valid tokens per row (the
-// kernels clamp them to [1, max_len]; max_len <= ld, so a wrong length reads no other row), min_len / max_len = the host's bounds.
-struct PromptArgs { const int64_t* ids; int ld; const int32_t* lengths; int min_len, max_len; };
-// prompt (nullable) + prompt_pos = the position the launch writes: a row with prompt_pos < lengths[r] takes ids[r][prompt_pos]
+// prompt (PromptArgs, host_logic.h; nullable) + prompt_pos = the position the launch writes: a row with prompt_pos < lengths[r] takes ids[r][prompt_pos]
 // instead of its arg-max (out, the embedded next row), leaves sep_cnt alone and gets lp 0.0f; with prompt_pos >= max_len the launch
 // is the one without a prompt.
 hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride,
@@ -340,10 +338,9 @@ hipError_t launch_window_scatter(const float* src, float* ring, int B, int n, in
 // [B*F*N][D] (the decoder input) and vis fp32 (nullable); the same bits as the ln_post epilogue that adds the embedding itself
 hipError_t launch_window_assemble(const float* ring, const float* temporal, bf16_t* out, float* vis, int B, int F, int head, int N, int D,
                                   hipStream_t s);
-// Ragged batches (gitcap_attach_frame_counts): clips of 1..255 frames each, packed clip-major.  RaggedCounts travels by value
-// (a stream-ordered launch captures it), launch_ragged_tables writes off[b] = N * sum_{i<b} n[i], len[b] = N * n[b] (int32 [B])
-// and pos[frame] = the frame's index inside its clip (int32 [sum n]).
-struct RaggedCounts { int B; unsigned char n[256]; };
+// Ragged batches (gitcap_attach_frame_counts): clips of 1..255 frames each, packed clip-major.  RaggedCounts (host_logic.h) travels
+// by value (a stream-ordered launch captures it), launch_ragged_tables writes off[b] = N * sum_{i<b} n[i], len[b] = N * n[b]
+// (int32 [B]) and pos[frame] = the frame's index inside its clip (int32 [sum n]).
 hipError_t launch_ragged_tables(const RaggedCounts& rc, int N, int32_t* off, int32_t* len, int32_t* pos, hipStream_t s);
 // row r (frame r / N) of the decoder input = bf16(ln[r] + temporal[pos[r / N]]), optionally also the fp32 sum (visual features):
 // window_assemble's add and rounding, i.e. the fused ln_post epilogue's, with the frame's position read from a table

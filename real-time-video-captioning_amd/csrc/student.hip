@@ -201,11 +201,11 @@ struct gitcap_student : HandleCore {
     unsigned* acc_ticket = nullptr;
     int32_t* acc_host = nullptr;
     hipEvent_t acc_ev = nullptr;
-    // token log-probabilities (gitcap_student_attach_token_logprobs): lp_attach / lp_ld = the pending one-shot attachment; the first
+    // token log-probabilities (gitcap_student_attach_token_logprobs): lp_attach = the pending one-shot attachment; the first
     // attach allocates amax_sum (the head's third partial, sized as amax_val), acc_lp (draft_accept_kernel's hand-over words) and
     // g_lp, the handle's own [B][max_len] rows the captured loops write (copied to the caller's buffer behind the replay, like g_ids)
-    float *lp_attach = nullptr, *amax_sum = nullptr, *g_lp = nullptr;
-    int lp_ld = 0;
+    LpAttach lp_attach{};
+    float *amax_sum = nullptr, *g_lp = nullptr;
     int* acc_lp = nullptr;
     float* score_buf = nullptr;         // gitcap_student_score (first use): [2][Mt] target logits, lp rows the caller did not ask for
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
@@ -771,7 +771,7 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
                  int64_t* ids_out, int32_t* steps_out, void* stream) {
     const std::string w(who);
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
-    const LpAttach lp = take_lp(h);
+    const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
@@ -898,7 +898,7 @@ int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft
 
 int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: null handle");
-    if (!logprobs_out) { h->lp_attach = nullptr; h->lp_ld = 0; return 0; }
+    if (!logprobs_out) { h->lp_attach = LpAttach{}; return 0; }
     if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: ld < 1 or a misaligned pointer");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_token_logprobs: weights not finalized");
     GUARD(h);
@@ -910,7 +910,7 @@ int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_ou
             return rc;
         }
     }
-    h->lp_attach = logprobs_out; h->lp_ld = ld;
+    h->lp_attach = LpAttach{logprobs_out, ld};
     return 0;
 }
 

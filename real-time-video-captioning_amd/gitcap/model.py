@@ -188,6 +188,68 @@ class _Constraints:
         model._call("gitcap_attach_constraints", ctypes.byref(self._c))
 
 
+class _CallOptions:
+    """Everything one decoding call attaches (include/gitcap.h: gitcap_attach_*): prompt, constraints, per-clip frame counts,
+    search options and sampling.  The attachments are one-shot: ``attach`` is made before every issue of the call, a repeat after
+    a failed statistics exchange and a future's re-run included; with all parts at their defaults it attaches nothing.  A future
+    holds the object until its result (the device reads the prompt, the suppress list and the n-best buffers)."""
+
+    def __init__(self, model, prompt=None, cons=None, counts=None, num_keep_best=1, repetition_penalty=1.0, sampling=None):
+        self._m, self.prompt, self.cons, self.counts = model, prompt, cons, counts
+        self.num_keep_best, self.repetition_penalty = int(num_keep_best), float(repetition_penalty)
+        self.sampling = sampling         # None | (temperature, top_k, top_p, seed)
+        self._so = self._smp = None
+        if sampling is not None:
+            self._smp = _lib.CSamplingOptions(sampling[0], sampling[1], sampling[2], sampling[3] & (2 ** 64 - 1))
+
+    @property
+    def key(self):
+        """What batches must share to coalesce: a prompted batch is alone with its key, constrained ones need equal constraints."""
+        return (None if self.prompt is None else id(self.prompt), None if self.cons is None else self.cons.key)
+
+    def rows(self, b0, b1):
+        """The options of clips [b0, b1): a chunk of a synchronous call over more than max_batch clips."""
+        n = len(self.counts) if self.counts is not None else len(self.prompt.host_lengths) if self.prompt is not None else None
+        if n is None or (b0 == 0 and b1 >= n):
+            return self
+        return _CallOptions(self._m, None if self.prompt is None else self.prompt.rows(b0, b1), self.cons,
+                            None if self.counts is None else self.counts[b0:b1], self.num_keep_best, self.repetition_penalty, self.sampling)
+
+    def search_outputs(self, B, max_steps):
+        """The output buffers of a search over B clips -> (own, decoded, logprobs): ``own`` = the (decoded, logprobs) pair the call
+        itself writes (rank 0), decoded / logprobs = what the caller gets: the same pair, or with num_keep_best > 1 the attached
+        n-best buffers [B, n, max_steps] / [B, n] (own is cut from the same two allocations: whoever holds the result keeps both alive)."""
+        dev, n = self._m._dev, self.num_keep_best
+        ids = torch.empty((B * (n + 1) * max_steps if n > 1 else B * max_steps,), dtype=torch.int64, device=dev)
+        lps = torch.empty((B * (n + 1) if n > 1 else B,), dtype=torch.float32, device=dev)
+        if n == 1:
+            own = decoded, logprobs = ids.view(B, max_steps), lps
+            nbest = nbest_lp = None
+        else:                            # [B, n, ...] with room for the call's own [B, ...] outputs behind it
+            decoded, logprobs = nbest, nbest_lp = ids[:B * n * max_steps].view(B, n, max_steps), lps[:B * n].view(B, n)
+            own = (ids[B * n * max_steps:].view(B, max_steps), lps[B * n:])
+        if n > 1 or self.repetition_penalty != 1.0:
+            self._so = _lib.CSearchOptions(n, self.repetition_penalty, None if nbest is None else nbest.data_ptr(),
+                                           None if nbest_lp is None else nbest_lp.data_ptr())
+        return own, decoded, logprobs
+
+    def attach(self, lp=None):
+        """lp: the token log-probability buffer [nb, max_len] of a greedy call (one per chunk)."""
+        m = self._m
+        if lp is not None:
+            m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), lp.shape[1])
+        if self._so is not None:
+            m._call("gitcap_attach_search_options", ctypes.byref(self._so))
+        if self._smp is not None:
+            m._call("gitcap_attach_sampling", ctypes.byref(self._smp))
+        if self.prompt is not None:
+            self.prompt.attach(m)
+        if self.cons is not None:
+            self.cons.attach(m)
+        if self.counts is not None:
+            m._attach_counts(self.counts)
+
+
 def _lp2d(logprobs):
     """The search's scores as the reference returns them, [B, num_keep_best] (the one-hypothesis call writes [B])."""
     return logprobs[:, None] if logprobs.dim() == 1 else logprobs
@@ -218,13 +280,11 @@ class _Future:
 class CaptionFuture(_Future):
     """Result handle of greedy_decode_async."""
 
-    def __init__(self, model, frames, mode, max_len, out_device):
+    def __init__(self, model, frames, mode, max_len, out_device, opts):
         self._m, self._frames, self._mode, self._max_len, self._out_device = model, frames, mode, max_len, out_device
         self._sub, self._r0, self._r1 = None, 0, 0
         self._done = None
-        self._prompt = None                      # greedy_decode_async(prompt=...): held until the result (the device reads it)
-        self._cons = None                        # _Constraints | None, held likewise
-        self._rg = None                          # greedy_decode_async(frame_counts=...): the (clips, counts, raw) a re-run decodes again
+        self._opts = opts                        # _CallOptions: held until the result (the device reads it; a re-run attaches it again)
 
     def _attach(self, sub, r0, r1):
         self._sub, self._r0, self._r1 = sub, r0, r1
@@ -251,8 +311,11 @@ class CaptionFuture(_Future):
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         def rerun():
-            ids = m._greedy_decode(None if self._rg is not None else sub.rows(self._r0, self._r1), self._max_len, self._mode, False,
-                                   self._prompt, self._cons, self._rg)
+            counts, rg = self._opts.counts, None
+            if counts is not None:               # a ragged batch: the callers' host clips again, or the packed device frames clip by clip
+                clips = sub.parts if sub.parts is not None else list(torch.split(sub.frames, counts))
+                rg = (clips, counts, clips[0].dtype == torch.uint8)
+            ids = m._greedy_decode(None if rg is not None else sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._opts, rg)
             return ids.to(self._out_device) if self._out_device != ids.device else ids
 
         synced = self._mode == STOP_ALL_SEP or self._out_device.type == "cpu"
@@ -263,8 +326,9 @@ class CaptionFuture(_Future):
 class InferFuture(_Future):
     """Result handle of infer_async: ``result()`` returns the dict of ``GitCaptioner.infer``."""
 
-    def __init__(self, model, sub, kw, out_device, save_logits):
-        self._m, self._sub, self._kw, self._out_device, self._save = model, sub, kw, out_device, save_logits
+    def __init__(self, model, sub, opts, search, out_device, save_logits):
+        self._m, self._sub, self._opts, self._out_device, self._save = model, sub, opts, out_device, save_logits
+        self._search = search                    # the search's plain arguments: beam_size, max_steps, length_penalty, per_node_beam_size
         self._done = None
 
     def result(self) -> dict:
@@ -278,24 +342,23 @@ class InferFuture(_Future):
             mv = lambda t: t if t is None or t.device == dev else t.to(dev)
             out = {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)),
                    "logits_dict": [] if steps is None else steps, "visual_features": mv(vis)}
-            if self._kw.get("sampling") is not None:
-                out["seed"] = self._kw["sampling"][3]
-            if self._kw.get("prompt") is not None:
-                out["prompt_lengths"] = mv(self._kw["prompt"].lengths)
-            counts = self._kw.get("counts")
+            opts = self._opts
+            if opts.sampling is not None:
+                out["seed"] = opts.sampling[3]
+            if opts.prompt is not None:
+                out["prompt_lengths"] = mv(opts.prompt.lengths)
+            counts = opts.counts
             if counts is not None and vis is not None:       # a ragged batch: packed rows -> the padded pair of the reference
                 pv, valid = ragged.unpack_rows(vis, counts, m.cfg.tokens_per_frame)
                 out["visual_features"], out["visual_features_valid"] = mv(pv), mv(valid)
             return out
 
         def rerun():
-            if self._kw.get("counts") is not None:           # the packed frames: on the device already, or the callers' host clips again
+            if self._opts.counts is not None:                # the packed frames: on the device already, or the callers' host clips again
                 fr = sub.frames if sub.parts is None else m._pack_to_device(sub.parts, sub.parts[0].dtype == torch.uint8)
             else:
                 fr = m._to_device(sub.rows(0, sub.outs[0].shape[0]))
-            r = m._infer_device(fr, sync=True, save_logits=self._save,
-                                want_visual=sub.outs[3] is not None, **self._kw)
-            sub.outs = r
+            sub.outs = m._infer_device(fr, self._opts, sync=True, save_logits=self._save, want_visual=sub.outs[3] is not None, **self._search)
             return extract()
 
         self._done = self._deliver(extract, self._out_device.type == "cpu", rerun)
@@ -310,11 +373,10 @@ class CaptionStream(_WindowStream):
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
                  gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None):
-        self._cons = constraints         # _Constraints | None: attached again for every caption
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
-        self._nbest, self._rp = int(num_keep_best), float(repetition_penalty)
         self._sampling = sampling        # (temperature, top_k, top_p, seed | None) of a do_sample stream
-        self._prompt = prompt            # _Prompt | None: the stream's per-clip prompt, attached again for every caption
+        # the stream's prompt (_Prompt | None), constraints (_Constraints | None) and search options: attached again for every caption
+        self._attached = (prompt, constraints, None, num_keep_best, repetition_penalty)
         self.last_seed = None            # do_sample: the seed of the caption the last push returned
         self._clear()
         super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
@@ -392,27 +454,16 @@ class CaptionStream(_WindowStream):
         with torch.cuda.device(m._dev):
             if self._beam is None:
                 ids, steps, lp = self._greedy_buffers(B)
-                if lp is not None:
-                    m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), self._max_len)
-                if self._prompt is not None:
-                    self._prompt.attach(m)
-                if self._cons is not None:
-                    self._cons.attach(m)
+                opts = _CallOptions(m, *self._attached)
+                opts.attach(lp)
                 m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
-                decoded = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
-                logprobs = torch.empty((B,), dtype=torch.float32, device=m._dev)
                 sampling = m._seeded(self._sampling)
-                attach, nbest, nbest_lp, _ = m._search_options(B, self._max_len, self._nbest, self._rp, sampling)
-                attach()                         # one-shot: consumed by the search below (a repeated caption attaches again)
-                if self._prompt is not None:
-                    self._prompt.attach(m)
-                if self._cons is not None:
-                    self._cons.attach(m)
+                opts = _CallOptions(m, *self._attached, sampling)
+                own, decoded, logprobs = opts.search_outputs(B, self._max_len)
+                opts.attach()                    # one-shot: consumed by the search below (a repeated caption attaches again)
                 m._call("gitcap_window_beam_search", self._beam, self._max_len, ctypes.c_float(self._lp), self._pnb, _lib.ptr(vis),
-                        _lib.ptr(decoded), _lib.ptr(logprobs), m._stream())
-                if nbest is not None:
-                    decoded, logprobs = nbest, nbest_lp
+                        _lib.ptr(own[0]), _lib.ptr(own[1]), m._stream())
                 if sampling is not None:
                     self.last_seed = sampling[3]
         m._last_memory = None
@@ -420,8 +471,8 @@ class CaptionStream(_WindowStream):
             return self._finish_greedy(ids, steps, lp, on_cpu)
         mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
         out = {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)), "logits_dict": [], "visual_features": mv(vis)}
-        if self._prompt is not None:
-            out["prompt_lengths"] = mv(self._prompt.lengths)
+        if opts.prompt is not None:
+            out["prompt_lengths"] = mv(opts.prompt.lengths)
         return out
 
 
@@ -1041,44 +1092,48 @@ class GitCaptioner(_NativeModule):
         if frame_counts is not None or not isinstance(src, torch.Tensor):
             src, rg = self._ragged_input(src, frame_counts)
         B, in_dev = (src.shape[0], src.device) if rg is None else (len(rg[1]), rg[0][0].device)
-        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
-        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+        opts = self._greedy_options(B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg)
         if in_dev.type == "cpu":                  # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, pr, co, rg))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs, pr, co, rg)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False, pr=None, co=None, rg=None):
+    def _greedy_options(self, B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg=None):
+        """The option arguments of the greedy calls (rg: the ragged batch, or None) -> _CallOptions"""
+        return _CallOptions(self, self._prompt(prompt, prompt_lengths, B, max_len, "max_len"),
+                            self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len), None if rg is None else rg[1])
+
+    def _chunks(self, fr, rg):
+        """A synchronous call's input in chunks of at most max_batch clips -> (first clip, nb, F, fh, fw, device frames) each: fr the
+        checked dense frames [B, F, ...] (a CPU tensor is staged chunk by chunk, stream ordered), or rg = (clips, counts, raw) of a
+        ragged batch, every chunk packed [sum(counts), ...] with F its largest count."""
+        step = self.max_batch
+        if rg is None:
+            for b0 in range(0, fr.shape[0], step):
+                chunk = self._to_device(fr[b0:b0 + step])
+                yield (b0,) + tuple(chunk.shape[:4]) + (chunk,)
+        else:
+            parts, counts, raw = rg
+            for b0 in range(0, len(counts), step):
+                chunk, cc = self._pack_to_device(parts[b0:b0 + step], raw), counts[b0:b0 + step]
+                yield (b0, len(cc), max(cc)) + tuple(chunk.shape[1:3]) + (chunk,)
+
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, opts=None, rg=None):
         """rg: the (clips, counts, raw) of a ragged batch (src is then unused): each chunk of at most max_batch clips is packed
         and runs with its counts attached."""
         self._drain()
+        opts = opts or _CallOptions(self)
         if rg is None:
             fr, raw = self._check_frames(src)     # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
-            B, F = fr.shape[:2]
         else:
-            parts, counts, raw = rg
-            B, src = len(counts), parts[0]        # (src: where the results go)
+            fr, raw, src = None, rg[2], rg[0][0]  # (src: where the results go)
         outs, steps_all, lps = [], [], []
         with torch.cuda.device(self._dev):
-            for b0 in range(0, B, self.max_batch):
-                if rg is None:
-                    chunk = self._to_device(fr[b0:b0 + self.max_batch])      # (a CPU tensor: staged chunk by chunk, stream ordered)
-                    nb, (fh, fw) = chunk.shape[0], chunk.shape[2:4]
-                else:
-                    cc = counts[b0:b0 + self.max_batch]
-                    chunk = self._pack_to_device(parts[b0:b0 + self.max_batch], raw)
-                    nb, F, (fh, fw) = len(cc), max(cc), chunk.shape[1:3]
+            for b0, nb, F, fh, fw, chunk in self._chunks(fr, rg):
                 ids = torch.empty((nb, max_len + 1), dtype=torch.int64, device=self._dev)
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
-                if want_lp:                      # one-shot: consumed by the greedy call below
+                if want_lp:
                     lps.append(torch.empty((nb, max_len), dtype=torch.float32, device=self._dev))
-                    self._call("gitcap_attach_token_logprobs", _lib.ptr(lps[-1]), max_len)
-                if pr is not None:               # one-shot as well
-                    part = pr if B <= self.max_batch else pr.rows(b0, b0 + nb)
-                    part.attach(self)
-                if co is not None:               # one-shot as well
-                    co.attach(self)
-                if rg is not None:               # one-shot as well
-                    self._attach_counts(cc)
+                opts.rows(b0, b0 + nb).attach(lps[-1] if want_lp else None)      # one-shot: consumed by the greedy call below
                 if raw:
                     self._call("gitcap_greedy_raw", _lib.ptr(chunk), nb, F, fh, fw, max_len, mode,
                                _lib.ptr(ids), _lib.ptr(steps), self._stream())
@@ -1133,8 +1188,16 @@ class GitCaptioner(_NativeModule):
             raise ValueError(f"max_len {max_len} > max_text_len={self.max_text_len} the handle was created for")
         if frame_counts is not None or not isinstance(src, torch.Tensor):
             src, rg = self._ragged_input(src, frame_counts)
-            if rg is not None:
-                return self._greedy_submit_ragged(rg, max_len, mode, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens)
+            if rg is not None:                    # one submission of its own, the counts attached beside prompt and constraints
+                parts, counts, raw = rg
+                if len(counts) > self.max_batch:
+                    raise ValueError(f"batch {len(counts)} > max_batch={self.max_batch}")
+                self._flush_pending()
+                opts = self._greedy_options(len(counts), max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg)
+                fut = CaptionFuture(self, None, mode, max_len, parts[0].device, opts)
+                fut._attach(self._greedy_submit(self._ragged_source(rg), raw, (len(counts), max(counts)) + tuple(parts[0].shape[1:3]),
+                                                max_len, mode, opts), 0, len(counts))
+                return fut
         fr, raw = self._check_frames(src)         # nothing is copied yet: a CPU batch is staged when its group is submitted
         B = fr.shape[0]
         if B * max(1, coalesce) > self.max_batch:
@@ -1142,12 +1205,10 @@ class GitCaptioner(_NativeModule):
         host = fr.device.type == "cpu"
         if not host:
             fr = self._to_device(fr)
-        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
-        fut = CaptionFuture(self, fr, mode, max_len, src.device)
-        fut._prompt = pr
-        fut._cons = co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
-        key = (tuple(fr.shape), max_len, mode, raw, host, None if pr is None else id(pr), None if co is None else co.key)
-        if pr is not None:
+        opts = self._greedy_options(B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens)
+        fut = CaptionFuture(self, fr, mode, max_len, src.device, opts)
+        key = (tuple(fr.shape), max_len, mode, raw, host) + opts.key
+        if opts.prompt is not None:
             coalesce = 1
         if self._pending and self._pending_key != key:
             self._flush_pending()
@@ -1157,48 +1218,11 @@ class GitCaptioner(_NativeModule):
             self._flush_pending()
         return fut
 
-    def _greedy_submit_ragged(self, rg, max_len, mode, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens):
-        """greedy_decode_async of a ragged batch: one submission of its own, the counts attached beside prompt and constraints."""
-        parts, counts, raw = rg
-        B = len(counts)
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} > max_batch={self.max_batch}")
-        self._flush_pending()
-        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
-        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
-        fut = CaptionFuture(self, None, mode, max_len, parts[0].device)
-        fut._prompt, fut._cons, fut._rg = pr, co, rg
-        while len(self._inflight) >= 4:
-            self._wait_submission(self._inflight[0])
-        with torch.cuda.device(self._dev):
-            entry = None
-            if parts[0].device.type == "cpu":
-                frames, entry, stream = self._stage_group(list(parts), raw)
-            else:
-                frames, stream = self._pack_to_device(parts, raw), self._stream()
-            ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
-            steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
-            ticket = ctypes.c_int(-1)
-
-            def before():
-                if pr is not None:
-                    pr.attach(self)
-                if co is not None:
-                    co.attach(self)
-                self._attach_counts(counts)
-            if raw:
-                self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, max(counts), frames.shape[1], frames.shape[2], max_len, mode,
-                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket), before=before)
-            else:
-                self._submit("gitcap_greedy_submit", _lib.ptr(frames), B, max(counts), max_len, mode, _lib.ptr(ids), _lib.ptr(steps), stream,
-                             ctypes.byref(ticket), before=before)
-        self._last_memory = None
-        sub = _Submission(ticket.value, frames, (ids, steps), False, parts=list(parts) if entry is not None else None)
-        if entry is not None:
-            entry["sub"] = sub
-        self._inflight.append(sub)
-        fut._attach(sub, 0, B)
-        return fut
+    def _ragged_source(self, rg):
+        """The clips of a ragged batch as _submit_frames takes them: host clips as they are (packed by the staging ring), device
+        clips packed."""
+        parts, _, raw = rg
+        return list(parts) if parts[0].device.type == "cpu" else self._pack_to_device(parts, raw)
 
     def _stage_group(self, parts, raw):
         """Host-fed submission: the callers' CPU tensors -> one ring entry (pinned staging unless the single tensor is already
@@ -1206,48 +1230,49 @@ class GitCaptioner(_NativeModule):
         dv, entry, st = self._staging().stage(self, parts, torch.uint8 if raw else torch.float32)
         return dv, entry, ctypes.c_void_p(st.cuda_stream)
 
+    def _submit_frames(self, kind, src, raw, dims, args, outs, opts, users=1):
+        """One pipelined submission, gitcap_<kind>[_raw]_submit (kind: "greedy" | "beam_search") -> its _Submission, in flight.
+        src: the device frames (dense [B, F, ...] or packed), or the list of the callers' CPU tensors, which go through the staging
+        ring (concatenated along dim 0) with the submission ordered behind their copy; dims = (B, F, fh, fw) as the call takes
+        them; args: the call's arguments between the frame sizes and the stream; outs: the buffers it writes."""
+        while len(self._inflight) >= 4:        # four slots: the oldest submission's slot is about to be reused (and, before the
+            self._wait_submission(self._inflight[0])                       # staging, its ring entry)
+        with torch.cuda.device(self._dev):
+            parts = entry = None
+            if isinstance(src, list):
+                parts = src
+                frames, entry, stream = self._stage_group(parts, raw)
+            else:
+                frames, stream = src, self._stream()
+            ticket = ctypes.c_int(-1)
+            self._submit(f"gitcap_{kind}_raw_submit" if raw else f"gitcap_{kind}_submit", _lib.ptr(frames), *(dims if raw else dims[:2]),
+                         *args, stream, ctypes.byref(ticket), before=opts.attach)
+        self._last_memory = None
+        sub = _Submission(ticket.value, frames, outs, users > 1, users=users, parts=parts)
+        if entry is not None:
+            entry["sub"] = sub
+        self._inflight.append(sub)
+        return sub
+
+    def _greedy_submit(self, src, raw, dims, max_len, stop, opts, users=1):
+        ids = torch.empty((dims[0], max_len + 1), dtype=torch.int64, device=self._dev)
+        steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
+        return self._submit_frames("greedy", src, raw, dims, (max_len, stop, _lib.ptr(ids), _lib.ptr(steps)), (ids, steps), opts, users)
+
     def _flush_pending(self):
         """Submit the waiting batches as one pass and hand each future its row range."""
         group, self._pending = self._pending, []
         if not group:
             return
         raw, host = self._pending_key[3], self._pending_key[4]
-        max_len, mode = group[0]._max_len, group[0]._mode
-        while len(self._inflight) >= 4:        # four slots: the oldest submission's slot is about to be reused
-            self._wait_submission(self._inflight[0])
-        with torch.cuda.device(self._dev):
-            parts = entry = None
-            if host:
-                parts = [f._frames for f in group]
-                frames, entry, stream = self._stage_group(parts, raw)
-            else:
-                frames = group[0]._frames if len(group) == 1 else torch.cat([f._frames for f in group], 0)
-                stream = self._stream()
-            B, F = frames.shape[:2]
-            ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
-            steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
-            ticket = ctypes.c_int(-1)
-            stop = STOP_NEVER if len(group) > 1 else mode       # the stop rule is per caller batch: applied in result()
-            pr = group[0]._prompt                # (a prompted batch is a group of one)
-            co = group[0]._cons                  # (every batch of a group carries equal constraints: the key holds them)
-            before = None
-            if pr is not None or co is not None:
-                def before():
-                    if pr is not None:
-                        pr.attach(self)
-                    if co is not None:
-                        co.attach(self)
-            if raw:
-                self._submit("gitcap_greedy_raw_submit", _lib.ptr(frames), B, F, frames.shape[2], frames.shape[3], max_len, stop,
-                             _lib.ptr(ids), _lib.ptr(steps), stream, ctypes.byref(ticket), before=before)
-            else:
-                self._submit("gitcap_greedy_submit", _lib.ptr(frames), B, F, max_len, stop, _lib.ptr(ids), _lib.ptr(steps), stream,
-                             ctypes.byref(ticket), before=before)
-        self._last_memory = None
-        shared = _Submission(ticket.value, frames, (ids, steps), len(group) > 1, users=len(group), parts=parts)
-        if entry is not None:
-            entry["sub"] = shared
-        self._inflight.append(shared)
+        frames = [f._frames for f in group]
+        dims = (sum(f.shape[0] for f in frames),) + tuple(frames[0].shape[1:4])
+        if not host:
+            frames = frames[0] if len(group) == 1 else torch.cat(frames, 0)
+        stop = STOP_NEVER if len(group) > 1 else group[0]._mode     # the stop rule is per caller batch: applied in result()
+        # the group's options are its first batch's: a prompted batch is a group of one, and every batch of a group carries equal
+        # constraints (the key holds them)
+        shared = self._greedy_submit(frames, raw, dims, group[0]._max_len, stop, group[0]._opts, users=len(group))
         r0 = 0
         for f in group:
             n = f._frames.shape[0]
@@ -1346,12 +1371,10 @@ class GitCaptioner(_NativeModule):
         co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps, beam_size * per_node_beam_size)
         if on_device:
             self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
-            decoded, logprobs, steps, vis = self._infer_device(fr, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
+            opts = _CallOptions(self, pr, co, None if rg is None else rg[1], num_keep_best, repetition_penalty, sampling)
+            decoded, logprobs, steps, vis = self._infer_device(fr, opts, beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty,
                                                                per_node_beam_size=per_node_beam_size, sync=True,
-                                                               save_logits=save_logits, want_visual=False, raw=raw,
-                                                               num_keep_best=num_keep_best, repetition_penalty=repetition_penalty,
-                                                               sampling=sampling, prompt=pr, constraints=co,
-                                                               counts=None if rg is None else rg[1])
+                                                               save_logits=save_logits, want_visual=False, raw=raw)
             out = {"predictions": decoded, "logprobs": _lp2d(logprobs), "logits_dict": [] if steps is None else steps,
                    "visual_features": None}
             if sampling is not None:
@@ -1452,88 +1475,42 @@ class GitCaptioner(_NativeModule):
             if (p < 1 and per_node_beam_size > 2) or (k > 0 and max(k, 2) < per_node_beam_size):
                 raise ValueError("beam_search: per_node_beam_size exceeds the columns the attached sampling filter is sure to keep")
 
-    def _search_options(self, B, max_steps, num_keep_best, repetition_penalty, sampling=None):
-        """-> (attach, nbest, nbest_logprobs, rank0): ``attach()`` makes the one-shot gitcap_attach_search_options call that the NEXT
-        beam-family call consumes (every issue of that call, a repeat after a failed statistics exchange included, needs its own);
-        the n-best output buffers and, cut from the same two allocations, (decoded, logprobs) buffers for the call's own outputs;
-        None for num_keep_best == 1.  With the defaults attach() does nothing at all.  ``sampling`` (temperature, top_k, top_p, seed):
-        attach() also makes the one-shot gitcap_attach_sampling call."""
-        if sampling is not None:
-            smp = _lib.CSamplingOptions(sampling[0], sampling[1], sampling[2], sampling[3] & (2 ** 64 - 1))
-            inner = self._search_options(B, max_steps, num_keep_best, repetition_penalty)
-
-            def attach():
-                inner[0]()
-                self._call("gitcap_attach_sampling", ctypes.byref(smp))
-            return (attach,) + inner[1:]
-        if num_keep_best == 1 and repetition_penalty == 1.0:
-            return (lambda: None), None, None, None
-        nbest = nbest_lp = rank0 = None
-        if num_keep_best > 1:                    # [B, n, ...] with room for the call's own [B, ...] outputs behind it
-            n = num_keep_best
-            ids = torch.empty((B * (n + 1) * max_steps,), dtype=torch.int64, device=self._dev)
-            lps = torch.empty((B * (n + 1),), dtype=torch.float32, device=self._dev)
-            nbest, nbest_lp = ids[:B * n * max_steps].view(B, n, max_steps), lps[:B * n].view(B, n)
-            rank0 = (ids[B * n * max_steps:].view(B, max_steps), lps[B * n:])
-        opt = _lib.CSearchOptions(int(num_keep_best), float(repetition_penalty), nbest.data_ptr() if nbest is not None else None,
-                                  nbest_lp.data_ptr() if nbest_lp is not None else None)
-        return (lambda: self._call("gitcap_attach_search_options", ctypes.byref(opt))), nbest, nbest_lp, rank0
-
-    def _infer_device(self, fr, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
-                      raw=None, stream=None, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None,
-                      counts=None):
-        """The device-resident search on frames already on the device (fp32 NCHW, or raw uint8 HWC): synchronously on the current
-        stream (sync=True; per-step logits are not available there) or as a pipelined submission ordered behind `stream` (default:
-        the current stream; a host-fed submission passes the copy stream).  Returns (decoded, logprobs, step logits | None,
-        visual | None) [+ the ticket when submitted]; with num_keep_best > 1 decoded is [B, n, max_steps] and logprobs [B, n]."""
+    def _infer_device(self, src, opts, *, beam_size, max_steps, length_penalty, per_node_beam_size, sync, save_logits, want_visual,
+                      raw=None, dims=None):
+        """The device-resident search with the options `opts` (_CallOptions): synchronously on the current stream (sync=True; src =
+        frames on the device, fp32 NCHW or raw uint8 HWC, packed for a ragged batch; per-step logits are not available from the
+        synchronous entry point, so a call that wants them submits and waits) or as a pipelined submission (src and dims as
+        _submit_frames takes them).  Returns (decoded, logprobs, step logits | None, visual | None), or when submitted the
+        _Submission that holds them as its outs; with num_keep_best > 1 decoded is [B, n, max_steps] and logprobs [B, n]."""
+        counts = opts.counts
         if raw is None:
-            raw = fr.dtype == torch.uint8
-        B, F = fr.shape[:2]
-        fh, fw = fr.shape[2:4]
-        if counts is not None:                   # a ragged batch: fr holds the packed frames [sum(counts), ...], visual rows come packed
-            B, F, (fh, fw) = len(counts), max(counts), fr.shape[1:3]
-        decoded = torch.empty((B, max_steps), dtype=torch.int64, device=self._dev)
-        logprobs = torch.empty((B,), dtype=torch.float32, device=self._dev)
-        attach, nbest, nbest_lp, rank0 = self._search_options(B, max_steps, num_keep_best, repetition_penalty, sampling)
-        if prompt is not None or constraints is not None or counts is not None:    # one-shot beside the options: every issue of the call attaches all
-            attach_options = attach
-
-            def attach():
-                attach_options()
-                if prompt is not None:
-                    prompt.attach(self)
-                if constraints is not None:
-                    constraints.attach(self)
-                if counts is not None:
-                    self._attach_counts(counts)
-        first = (decoded, logprobs)              # the call's own outputs: rank 0 of the n-best
-        if nbest is not None:                    # (they share the n-best's allocations: whoever holds the result keeps both alive)
-            first, decoded, logprobs = rank0, nbest, nbest_lp
+            raw = src.dtype == torch.uint8
+        if dims is None:                         # (a ragged batch: src holds the packed frames [sum(counts), ...], visual rows come packed)
+            dims = tuple(src.shape[:4]) if counts is None else (len(counts), max(counts)) + tuple(src.shape[1:3])
+        B, F = dims[:2]
+        own, decoded, logprobs = opts.search_outputs(B, max_steps)      # own: the call's outputs, rank 0 of the n-best
         with torch.cuda.device(self._dev):
             if sync and not save_logits and not want_visual and not raw:
                 self._drain()
-                attach()
-                self._call("gitcap_beam_search", _lib.ptr(fr), B, F, beam_size, max_steps, ctypes.c_float(length_penalty),
-                           per_node_beam_size, _lib.ptr(first[0]), _lib.ptr(first[1]), self._stream())
+                opts.attach()
+                self._call("gitcap_beam_search", _lib.ptr(src), B, F, beam_size, max_steps, ctypes.c_float(length_penalty),
+                           per_node_beam_size, _lib.ptr(own[0]), _lib.ptr(own[1]), self._stream())
                 self._last_memory = None
                 return decoded, logprobs, None, None
             steps = torch.empty((max_steps - 1, B * beam_size, self.cfg.vocab_size), dtype=torch.float32, device=self._dev) if save_logits else None
             vis_shape = (B, F * self.cfg.tokens_per_frame) if counts is None else (sum(counts) * self.cfg.tokens_per_frame,)
             vis = torch.empty(vis_shape + (self.cfg.enc_width,), dtype=torch.float32, device=self._dev) if want_visual else None
-            while len(self._inflight) >= 4:
-                self._wait_submission(self._inflight[0])
-            ticket = ctypes.c_int(-1)
-            tail = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(first[0]),
-                    _lib.ptr(first[1]), _lib.ptr(steps), stream if stream is not None else self._stream(), ctypes.byref(ticket))
-            if raw:
-                self._submit("gitcap_beam_search_raw_submit", _lib.ptr(fr), B, F, fh, fw, *tail, before=attach)
-            else:
-                self._submit("gitcap_beam_search_submit", _lib.ptr(fr), B, F, *tail, before=attach)
-            self._last_memory = None
-            if sync:                           # (a re-run, or a synchronous call that wants logits / visual features / takes raw frames)
-                self._call("gitcap_beam_search_wait", ticket.value, self._stream())
-                return decoded, logprobs, steps, vis
-        return decoded, logprobs, steps, vis, ticket.value
+        args = (_lib.ptr(vis), beam_size, max_steps, ctypes.c_float(length_penalty), per_node_beam_size, _lib.ptr(own[0]), _lib.ptr(own[1]),
+                _lib.ptr(steps))
+        sub = self._submit_frames("beam_search", src, raw, dims, args, (decoded, logprobs, steps, vis), opts)
+        if not sync:
+            return sub
+        try:                                     # (a re-run, or a synchronous call that wants logits / visual features / takes raw frames)
+            with torch.cuda.device(self._dev):
+                self._call("gitcap_beam_search_wait", sub.ticket, self._stream())
+        finally:
+            self._inflight.remove(sub)           # waited for here: no future holds it
+        return sub.outs
 
     @torch.no_grad()
     def infer_async(self, src: torch.Tensor, beam_size: int = 4, max_steps: int = 15, length_penalty: float = 0.6,
@@ -1561,59 +1538,24 @@ class GitCaptioner(_NativeModule):
         rg = None
         if frame_counts is not None or not isinstance(src, torch.Tensor):
             src, rg = self._ragged_input(src, frame_counts)
+        if rg is not None:                       # packed once (host clips in the staging ring), submitted with its counts attached
+            parts, counts, raw = rg
+            B, out_device, dims = len(counts), parts[0].device, (len(counts), max(counts)) + tuple(parts[0].shape[1:3])
+        else:
+            fr, raw = self._check_frames(src)
+            B, out_device, counts, dims = fr.shape[0], src.device, None, tuple(fr.shape[:4])
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} > max_batch={self.max_batch}")
+        opts = _CallOptions(self, self._prompt(prompt, prompt_lengths, B, max_steps - 1, "max_steps - 1"),
+                            self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps, beam_size * per_node_beam_size),
+                            counts, num_keep_best, repetition_penalty, sampling)
         if rg is not None:
-            return self._infer_submit_ragged(rg, save_logits, visual_features, dict(
-                beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
-                num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling,
-                prompt=self._prompt(prompt, prompt_lengths, len(rg[1]), max_steps - 1, "max_steps - 1"),
-                constraints=self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps, beam_size * per_node_beam_size),
-                counts=rg[1]))
-        fr, raw = self._check_frames(src)
-        if fr.shape[0] > self.max_batch:
-            raise ValueError(f"batch {fr.shape[0]} > max_batch={self.max_batch}")
-        kw = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size,
-                  num_keep_best=num_keep_best, repetition_penalty=repetition_penalty, sampling=sampling,
-                  prompt=self._prompt(prompt, prompt_lengths, fr.shape[0], max_steps - 1, "max_steps - 1"),
-                  constraints=self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_steps,
-                                                beam_size * per_node_beam_size))
-        parts = entry = stream = None
-        if fr.device.type == "cpu":
-            while len(self._inflight) >= 4:      # (before the staging: the entry about to be reused belongs to the oldest)
-                self._wait_submission(self._inflight[0])
-            parts = [fr]
-            with torch.cuda.device(self._dev):
-                fr, entry, stream = self._stage_group(parts, raw)
+            fr = self._ragged_source(rg)
         else:
-            fr = self._to_device(fr)
-        decoded, logprobs, steps, vis, ticket = self._infer_device(fr, sync=False, save_logits=save_logits, want_visual=visual_features,
-                                                                   raw=raw, stream=stream, **kw)
-        sub = _Submission(ticket, fr, (decoded, logprobs, steps, vis), False, parts=parts)
-        if entry is not None:
-            entry["sub"] = sub
-        self._inflight.append(sub)
-        return InferFuture(self, sub, kw, src.device, save_logits)
-
-    def _infer_submit_ragged(self, rg, save_logits, visual_features, kw):
-        """infer_async of a ragged batch: packed once (host clips in the staging ring), submitted with its counts attached."""
-        parts, counts, raw = rg
-        if len(counts) > self.max_batch:
-            raise ValueError(f"batch {len(counts)} > max_batch={self.max_batch}")
-        held = entry = stream = None
-        if parts[0].device.type == "cpu":
-            while len(self._inflight) >= 4:
-                self._wait_submission(self._inflight[0])
-            held = list(parts)
-            with torch.cuda.device(self._dev):
-                fr, entry, stream = self._stage_group(held, raw)
-        else:
-            fr = self._pack_to_device(parts, raw)
-        decoded, logprobs, steps, vis, ticket = self._infer_device(fr, sync=False, save_logits=save_logits, want_visual=visual_features,
-                                                                   raw=raw, stream=stream, **kw)
-        sub = _Submission(ticket, fr, (decoded, logprobs, steps, vis), False, parts=held)
-        if entry is not None:
-            entry["sub"] = sub
-        self._inflight.append(sub)
-        return InferFuture(self, sub, kw, parts[0].device, save_logits)
+            fr = [fr] if fr.device.type == "cpu" else self._to_device(fr)
+        search = dict(beam_size=beam_size, max_steps=max_steps, length_penalty=length_penalty, per_node_beam_size=per_node_beam_size)
+        sub = self._infer_device(fr, opts, sync=False, save_logits=save_logits, want_visual=visual_features, raw=raw, dims=dims, **search)
+        return InferFuture(self, sub, opts, search, out_device, save_logits)
 
     def caption_stream(self, batch: int = 1, window: Optional[int] = None, hop: int = 1, max_len: int = 20, stop: Optional[str] = None,
                        beam_size: Optional[int] = None, length_penalty: float = 0.6, per_node_beam_size: Optional[int] = None,
