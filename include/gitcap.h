@@ -1093,6 +1093,53 @@ int gitcap_tinyvit_encode_raw(gitcap_tinyvit_t* h, const uint8_t* frames_hwc_bgr
 int gitcap_frame_change(const uint8_t* frames_hwc_bgr, const uint8_t* ref_hwc_bgr, int B, int H, int W, int channel,
                         uint64_t* ssd, uint32_t* hist_frame, uint32_t* hist_ref, double* mse, double* chisq, void* stream);
 
+/* ---- frame sampling of whole videos (gitcap/sampling.py; csrc/framesample.hip) ----------------------------------------------
+ * Replaces: frame_mse_difference_sampling, scene_change_detection_sampling, clustered_sampling
+ *                                                         src/utils/frame_sampling_methods.py:135-297
+ * A decoded video is device uint8 [N][H][W][3] (BGR, any alignment).  The calls below choose its frames without a host decision:
+ * every step of a call is enqueued at once on `stream`, the steps are ordered by the stream alone (no kernel waits on another
+ * workgroup), and what a step needs from the one before -- the chain's reference frame, whether k-means has converged -- is a word
+ * in a stream-ordered allocation of the call.  Handle-free; nothing is synchronised.  Every call returns GITCAP_ERR_ARG before any
+ * launch for a null pointer (where not stated otherwise) or N <= 0, and for what its own paragraph lists.
+ *
+ * gitcap_frame_chain: the reference's two sequential samplers over a whole video.  Every `every`-th frame is looked at (frame 0
+ * included, as gitcap.framegate.FrameGate).  Frame 0 is kept.  A later looked-at frame i is compared with the last frame kept:
+ * dist[i] is, bit for bit, the mse (metric 0) or chisq (metric 1, channel `channel` of the BGR triple) gitcap_frame_change gives
+ * for that pair, keep[i] = dist[i] > threshold.  dist of frame 0 and of frames not looked at is NaN, their keep 0 (frame 0: 1).
+ * The two differences from the reference's arithmetic are gitcap_frame_change's (exact integer MSE, one channel order).
+ * GITCAP_ERR_ARG: H or W < 1, H*W*3 >= 2^31, metric outside 0..1, channel outside 0..2, every < 1. */
+int gitcap_frame_chain(const uint8_t* video_hwc_bgr, int N, int H, int W, int metric, int channel, double threshold, int every,
+                       uint8_t* keep, double* dist, void* stream);
+
+/* X[N][h2*w2*3] (fp32, element order y, x, channel): every frame resized to h2 x w2 by bilinear interpolation with half-pixel
+ * centres -- output row y samples source row ((2y + 1) H / h2 - 1) / 2, not below 0, the row beyond the last repeats it; columns
+ * alike.  Taps and weights come from integer quotients, the blend a w00 + b w01 + c w10 + d w11 is fp32, and nothing is rounded
+ * back to uint8 (the reference's cv2.resize works in fixed point and does; not reproduced).
+ * GITCAP_ERR_ARG: H, W, h2 or w2 < 1, h2 or w2 > 2^22. */
+int gitcap_frame_features(const uint8_t* video_hwc_bgr, int N, int H, int W, int h2, int w2, float* X, void* stream);
+
+/* Lloyd's algorithm on the rows of X[N][D] (fp32) with k clusters; the centroids start at the rows init_idx[k] (device int32; an
+ * index outside [0, N) is clamped).  An iteration assigns, then updates:
+ *   assign   labels[n] = arg min over c of sum_d (X[n][d] - centroids[c][d])^2, the direct difference in fp32 in a fixed order;
+ *            ties go to the lower c
+ *   update   centroids[c] = the mean of the rows labelled c, added in ascending n in fp32 (no atomics on floats: two runs are
+ *            bit-identical); a cluster without rows keeps its centroid (sklearn relocates it)
+ * All max_iter iterations are enqueued.  The first iteration whose assign changes no label is the last: its update and everything
+ * behind it return at once, and iters[0] is that iteration's number (max_iter if there is none).  labels[N], centroids[k][D] and
+ * iters[1] are device memory.  GITCAP_ERR_ARG: D < 1, k < 1, k > N, k > 65535, max_iter outside [1, 2^20]. */
+int gitcap_kmeans(const float* X, int N, int D, int k, const int32_t* init_idx, int max_iter, int32_t* labels, float* centroids,
+                  int32_t* iters, void* stream);
+/* One assign step alone: labels[N] in (any value; -1 = none) and out, changed[0] += the number of labels that changed. */
+int gitcap_dbg_kmeans_assign(const float* X, int N, int D, int k, const float* centroids, int32_t* labels, int32_t* changed, void* stream);
+/* One update step alone: centroids[k][D] in and out (a cluster without rows keeps its row). */
+int gitcap_dbg_kmeans_update(const float* X, int N, int D, int k, const int32_t* labels, float* centroids, void* stream);
+
+/* The kept frames' indices in ascending order: idx[0 .. count[0]), idx[count[0] .. N) = -1.  keep[N] non-null: frame i is kept iff
+ * keep[i] != 0; else labels[N]: frame 0 and every i with labels[i] != labels[i-1] (the reference's run-boundary rule, :186-192).
+ * With K kept frames and K > max_frames, the selection is thinned to kept[floor(j K / max_frames)], j = 0 .. max_frames - 1
+ * (a model's temporal embedding has a frame limit).  One workgroup.  GITCAP_ERR_ARG: keep and labels both null, max_frames < 1. */
+int gitcap_frame_select(const uint8_t* keep, const int32_t* labels, int N, int max_frames, int64_t* idx, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "distill_report":
         from .distill import distill_report
         return distill_report
+    if name in ("sample_frames", "caption_videos", "FrameSelection"):
+        from . import sampling
+        return getattr(sampling, name)
     raise AttributeError(name)
