@@ -1,0 +1,531 @@
+// libgitcap's handle-free test hooks: gitcap_dbg_* (but gitcap_dbg_config, which flips gitcap.hip's switches), gitcap_beam_topk*
+// and gitcap_sample_rows*.  None touches a handle: each checks its arguments -- what a launcher does not check itself and a wrong
+// value of which would index outside a buffer -- fills the launcher's record and calls ONE launcher on caller-owned device buffers.
+// Declarations: include/gitcap.h.
+#include "../../include/gitcap.h"
+#include "kernels.h"
+#include "host_logic.h"
+#include "host_util.h"
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+extern "C" {
+
+// ---- candidates of a search step (tests/test_selection_gpu.py, test_sampling_gpu.py, test_constraints_gpu.py) -----------------
+static bool ban_mask_ok(const uint16_t* mask, int ld_mask, int V) {
+    return mask && ((uintptr_t)mask & 3) == 0 && V > 0 && ld_mask >= (V + 15) / 16 && (ld_mask & 1) == 0;
+}
+
+// no handle here: the scratch of the two-stage top-k is a stream-ordered allocation
+static int beam_topk_hook(const CandArgs& c, int K, void* stream) {
+    if (!c.logits || !c.beam_scores || !c.out_scores || !c.out_idx || c.B <= 0 || c.beams <= 0 || c.V <= 0 || K <= 0) return GITCAP_ERR_ARG;
+    void* scratch = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(c.B, c.beams, c.V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
+    const hipError_t e = launch_beam_topk(c, K, scratch, s);
+    (void)hipFreeAsync(scratch, s);
+    return dbg_rc(e);
+}
+// the penalised forms: the penalty and its prefix, and the sizes before the scratch is sized
+static bool topk_penalty_ok(const CandArgs& c, int K) {
+    if (!(c.rp > 0.f) || !std::isfinite(c.rp)) return false;
+    if (c.rp != 1.0f && (!c.prefix_ids || c.cur_len < 1 || c.ld_ids < c.cur_len || ((uintptr_t)c.prefix_ids & 7) != 0)) return false;
+    return !(c.beams > 16 || K > 16 || (int64_t)K > (int64_t)c.beams * c.V || c.V > 131072);
+}
+
+int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
+                     float* out_scores, int32_t* out_idx, void* stream) {
+    return beam_topk_hook(CandArgs{logits, ld, beam_scores, nullptr, 0, 0, 1.0f, B, beams, V, out_scores, out_idx, nullptr}, K, stream);
+}
+
+int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                               float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
+    const CandArgs c{logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, out_scores, out_idx, nullptr};
+    return topk_penalty_ok(c, K) ? beam_topk_hook(c, K, stream) : GITCAP_ERR_ARG;
+}
+
+int gitcap_beam_topk_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                 float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx,
+                                 const uint16_t* mask, int ld_mask, void* stream) {
+    const HeadBan bn{mask, ld_mask};
+    const CandArgs c{logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, out_scores, out_idx, &bn};
+    return ban_mask_ok(mask, ld_mask, V) && topk_penalty_ok(c, K) ? beam_topk_hook(c, K, stream) : GITCAP_ERR_ARG;
+}
+
+static int sample_rows_hook(const CandArgs& c, int per_node, const SampleOpt& opt, const SampleStats& st, void* stream) {
+    if (!c.logits || !c.beam_scores || !c.out_scores || !c.out_idx || c.B <= 0 || c.beams <= 0 || c.V <= 0 || per_node <= 0) return GITCAP_ERR_ARG;
+    if (((uintptr_t)c.prefix_ids & 7) != 0 || ((uintptr_t)st.kept_out & 3) != 0 || ((uintptr_t)st.logz_out & 3) != 0) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_sample_rows(c, per_node, opt, st, (hipStream_t)stream));
+}
+
+int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream) {
+    const CandArgs c{logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, out_scores, out_idx, nullptr};
+    return sample_rows_hook(c, per_node, SampleOpt{true, temperature, top_k, top_p, seed}, SampleStats{kept_out, logz_out}, stream);
+}
+
+int gitcap_sample_rows_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
+                                   float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
+                                   uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out,
+                                   const uint16_t* mask, int ld_mask, void* stream) {
+    if (!ban_mask_ok(mask, ld_mask, V)) return GITCAP_ERR_ARG;
+    const HeadBan bn{mask, ld_mask};
+    const CandArgs c{logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, out_scores, out_idx, &bn};
+    return sample_rows_hook(c, per_node, SampleOpt{true, temperature, top_k, top_p, seed}, SampleStats{kept_out, logz_out}, stream);
+}
+
+// ---- constrained decoding (tests/test_constraints_gpu.py) ---------------------------------------------------------------------
+int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                        const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream) {
+    if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)suppress & 3) != 0) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ban_mask(prefix_ids, ld_ids, rows, cur_len, n, min_length, sep_id, suppress, n_suppress, V, mask_out, ld_mask,
+                                  (hipStream_t)stream));
+}
+
+int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
+                    int epi, int tile, void* stream) {
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.bias = bias; a.M = M; a.N = N; a.K = K;
+    a.out = out; a.ldo = N; a.resid = resid; a.ldr = N;
+    if (epi < 0 || epi > EPI_BIAS_F32) return GITCAP_ERR_ARG;
+    if (tile != 64 && tile != 128 && tile != 256) return GITCAP_ERR_ARG;
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
+    return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+// fp8 tile kernel (gemm256.hip) on caller-owned buffers: A8 [M][K], W8 [N][K] e4m3 codes, wscale [N], acc * ascale * wscale[n] + bias;
+// epi 4 -> out fp32 [M][N]; epi 0 -> bf16; epi 8 / 9 -> e4m3 codes of gelu(.) * out8_inv
+int gitcap_dbg_gemm_f8(const void* A8, const void* W8, const float* wscale, float ascale, const float* bias, void* out, int M, int N,
+                       int K, int epi, float out8_inv, void* stream) {
+    GemmArgs a{};
+    a.A = (const bf16_t*)A8; a.lda = K; a.W = (const bf16_t*)W8; a.wscale = wscale; a.ascale = ascale; a.bias = bias;
+    a.M = M; a.N = N; a.K = K; a.out = out; a.ldo = N; a.out8_inv = out8_inv;
+    if (epi != EPI_BIAS_F32 && epi != EPI_BIAS_BF16 && epi != EPI_BIAS_QGELU_F8 && epi != EPI_BIAS_GELU_F8) return GITCAP_ERR_ARG;
+    if (!gemm256f8_ok(a)) return GITCAP_ERR_ARG;
+    return launch_gemm256f8(a, epi, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+// GEMM + bias [+ resid] + LayerNorm: fused = 1 the EPI_RESID_LN_* epilogue of the 256x256 kernel, 0 = GEMM (tile) then the
+// row kernel; post as in gemm_ln (gitcap.hip).  out_f32: post ? LN(x) : x.  Scratch for the exchange is allocated here.
+int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const float* resid, const float* gamma,
+                       const float* beta, float eps, float* out_f32, void* out_bf16, int M, int N, int K, int post,
+                       int fused, int tile, void* stream) {
+    static float2* stats = nullptr; static unsigned* cnt = nullptr; static int cap = 0;
+    hipStream_t s = (hipStream_t)stream;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.bias = bias; a.M = M; a.N = N; a.K = K;
+    a.out = out_f32; a.ldo = N; a.resid = resid; a.ldr = N;
+    if (!fused) {
+        if (tile != 64 && tile != 128 && tile != 256) return GITCAP_ERR_ARG;
+        float* xo = out_f32;
+        float* tmp = nullptr;
+        if (post) { if (hipMalloc(&tmp, (size_t)M * N * 4) != hipSuccess) return GITCAP_ERR_NOMEM; xo = tmp; a.out = tmp; }
+        const int epi = resid ? EPI_BIAS_RESID_F32 : EPI_BIAS_F32;
+        hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
+        if (e == hipSuccess) {
+            LnArgs l{xo, N, gamma, beta, eps, M, N, post ? out_f32 : nullptr, N, (bf16_t*)out_bf16, N, nullptr, 1, 1, nullptr, nullptr, 0.f};
+            e = launch_layernorm(l, s);
+        }
+        if (tmp) { (void)hipStreamSynchronize(s); (void)hipFree(tmp); }
+        return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
+    }
+    if (M / 224 + 2 > cap) {
+        if (stats) { (void)hipFree(stats); (void)hipFree(cnt); }
+        cap = M / 224 + 2;
+        if (hipMalloc(&stats, (size_t)cap * 256 * 16 * sizeof(float2)) != hipSuccess || hipMalloc(&cnt, (size_t)cap * 8) != hipSuccess) return GITCAP_ERR_NOMEM;
+        if (hipMemset(cnt, 0, (size_t)cap * 8) != hipSuccess) return GITCAP_ERR_HIP;
+    }
+    a.ln_g = gamma; a.ln_b = beta; a.ln_eps = eps; a.ln_out = (bf16_t*)out_bf16; a.ld_ln = N; a.ln_stats = stats; a.ln_cnt = cnt;
+    a.ln_stats_rows = cap * 224;
+    const int epi = post ? EPI_RESID_LN_POST : EPI_RESID_LN_PRE;
+    if (!post && !resid) return GITCAP_ERR_ARG;
+    hipError_t e;
+    if (fused != 1 || !gemm256_ln_ok(a)) return GITCAP_ERR_ARG;          // the 256x256 kernel of gemm256.hip
+    e = launch_gemm256(a, epi, s);
+    return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+int gitcap_dbg_attn_full(const void* qkv, void* ctx, int G, int S, int H, void* stream) {
+    return launch_attn_full((const bf16_t*)qkv, (bf16_t*)ctx, G, S, H, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, float eps, int rows, int D,
+                         float* out_f32, void* out_bf16, void* stream) {
+    LnArgs a{x, D, gamma, beta, eps, rows, D, out_f32, D, (bf16_t*)out_bf16, D, nullptr, 1, 1, nullptr, nullptr, 0.f};
+    return launch_layernorm(a, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+// ---- token selection (tests/test_selection_gpu.py) --------------------------------------------------------------------------
+// launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
+static SkinnyArgs dbg_head_args(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum) {
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
+    a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
+    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
+    return a;
+}
+static int dbg_vocab_head(const SkinnyArgs& a, void* stream, const HeadTargets* tg = nullptr, const HeadBan* bn = nullptr) {
+    if (!a.X || !a.W || a.M <= 0 || a.N <= 0 || a.ldx < a.K || a.ldx % 8 || !skinny_full_ok(a.K) || (a.amax_val == nullptr) != (a.amax_idx == nullptr) ||
+        (!a.out && !a.amax_val) || (a.amax_sum && !a.amax_val))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream, tg, bn));
+}
+int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                          float* logits, float* amax_val, int32_t* amax_idx, void* stream) {
+    return dbg_vocab_head(dbg_head_args(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, nullptr), stream);
+}
+// the same launch with the third partial (amax_sum [M][ntiles], required)
+int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                              float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
+    if (!amax_sum) return GITCAP_ERR_ARG;
+    return dbg_vocab_head(dbg_head_args(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum), stream);
+}
+// the BAN forms of the same launch (mask uint16 [M][ld_mask], kernels.h: HeadBan); amax_sum NULL: the plain form, else the LSE form
+int gitcap_dbg_vocab_head_banned(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                 float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const uint16_t* mask, int ld_mask,
+                                 void* stream) {
+    if (!ban_mask_ok(mask, ld_mask, N)) return GITCAP_ERR_ARG;
+    const HeadBan bn{mask, ld_mask};
+    return dbg_vocab_head(dbg_head_args(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum), stream, nullptr, &bn);
+}
+// the scoring head: the _lse launch + the logit of each row's target column (targets int64 [M], tgt_logit fp32 [M])
+int gitcap_dbg_vocab_head_score(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
+                                float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const int64_t* targets, float* tgt_logit,
+                                void* stream) {
+    if (!amax_val || !amax_idx || !amax_sum || !targets || !tgt_logit) return GITCAP_ERR_ARG;
+    const HeadTargets tg{targets, M, M, 0, tgt_logit};
+    return dbg_vocab_head(dbg_head_args(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum), stream, &tg);
+}
+// launch_score_final on caller-owned buffers: partials [rows * T][ntiles], tgt_logit [rows * T], ids [rows][ld_ids]
+int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                           const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                           float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
+    if (!token_lp) return GITCAP_ERR_ARG;
+    const ScoreOut o{token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    return dbg_rc(launch_score_final(amax_val, amax_idx, amax_sum, ntiles, tgt_logit, ids, ld_ids, rows, T, lengths, ignore_id, V, o,
+                                     (hipStream_t)stream));
+}
+
+// launch_head_dual on caller-owned buffers, row-major weights; targets: one column per row (HeadTargets with T = ld = M, shift 0)
+int gitcap_dbg_vocab_head_dual(const void* Xt, int ldxt, const void* Wt, const float* wscale, const float* bias_t, int Kt, const void* Xs,
+                               int ldxs, const void* Ws, const float* bias_s, int Ks, int M, int N, float inv_temperature, float* t_max,
+                               int32_t* t_idx, float* t_sum, float* s_max, int32_t* s_idx, float* s_sum, float* cross,
+                               const int64_t* targets, float* t_logit, float* s_logit, void* stream) {
+    DualHeadArgs a{};
+    a.Xt = (const bf16_t*)Xt; a.ldxt = ldxt; a.Xs = (const bf16_t*)Xs; a.ldxs = ldxs;
+    a.wt = HeadWeight{Wt, nullptr, wscale, bias_t, N, Kt}; a.ws = HeadWeight{Ws, nullptr, nullptr, bias_s, N, Ks};
+    a.M = M; a.inv_temp = inv_temperature;
+    a.t_max = t_max; a.t_idx = t_idx; a.t_sum = t_sum; a.s_max = s_max; a.s_idx = s_idx; a.s_sum = s_sum; a.cross = cross;
+    if (targets) { a.tg = HeadTargets{targets, M, M, 0, t_logit}; a.s_logit = s_logit; }
+    return dbg_rc(launch_head_dual(a, (hipStream_t)stream));
+}
+int gitcap_dbg_distill_final(const float* t_max, const int32_t* t_idx, const float* t_sum, const float* s_max, const int32_t* s_idx,
+                             const float* s_sum, const float* cross, int ntiles, const float* t_logit, const float* s_logit,
+                             const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                             const gitcap_distill_out* out, void* stream) {
+    if (!out) return GITCAP_ERR_ARG;
+    const DistillOut o{out->kl, out->ld_kl, out->teacher_top1, out->student_top1, out->agree, out->teacher_lp, out->student_lp, out->ld_lp,
+                       out->row_kl_sum, out->row_cnt};
+    return dbg_rc(launch_distill_final(DistillPartials{t_max, t_idx, t_sum, s_max, s_idx, s_sum, cross}, ntiles, t_logit, s_logit, ids, ld_ids,
+                                       rows, T, lengths, ignore_id, V, o, (hipStream_t)stream));
+}
+
+// launch_argmax_final: the arguments every form shares; a form adds its own (sum / lp_out, prompt) before dbg_argmax_final
+static ArgmaxArgs dbg_argmax_args(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                  int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id) {
+    ArgmaxArgs a{};
+    a.val = amax_val; a.idx = amax_idx; a.ntiles = ntiles; a.rows = rows; a.row_stride = row_stride; a.row_off = row_off;
+    a.out = out; a.ld_out = ld_out; a.sep_cnt = sep_cnt; a.step = step; a.sep_id = sep_id;
+    a.prompt_pos = step + 1;              // the position a forced launch writes
+    return a;
+}
+static int dbg_argmax_final(ArgmaxArgs a, const gitcap_dbg_next_embed* emb, void* stream) {
+    if (!a.val || !a.idx || !a.out || a.ntiles <= 0 || a.rows <= 0 || a.row_stride <= 0 || a.row_off < 0 || a.ld_out <= 0 || a.step < 0)
+        return GITCAP_ERR_ARG;
+    NextEmbed ne{};
+    if (emb) {
+        if (emb->vocab <= 0 || emb->position < 0) return GITCAP_ERR_ARG;
+        ne = NextEmbed{emb->word, emb->pos, emb->gamma, emb->beta, emb->eps, emb->D, emb->vocab, emb->position, emb->xf, (bf16_t*)emb->xb};
+        a.emb = &ne;
+    }
+    return dbg_rc(launch_argmax_final(a, (hipStream_t)stream));
+}
+int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                            void* stream) {
+    return dbg_argmax_final(dbg_argmax_args(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id), emb, stream);
+}
+int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                               const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
+    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
+    ArgmaxArgs a = dbg_argmax_args(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id);
+    a.sum = amax_sum; a.lp_out = lp_out; a.ld_lp = ld_lp;
+    return dbg_argmax_final(a, emb, stream);
+}
+// the forced form (gitcap_attach_prompt): the launch writes position step + 1; amax_sum / lp_out both or neither
+int gitcap_dbg_argmax_final_forced(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                   int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                                   const float* amax_sum, float* lp_out, int ld_lp, const int64_t* prompt_ids, int ld_prompt,
+                                   const int32_t* lengths, int max_len, void* stream) {
+    if (!prompt_ids || !lengths || max_len < 1 || ld_prompt < max_len || (amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1))
+        return GITCAP_ERR_ARG;
+    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, max_len};
+    ArgmaxArgs a = dbg_argmax_args(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id);
+    a.sum = amax_sum; a.lp_out = lp_out; a.ld_lp = ld_lp; a.prompt = &pr;
+    return dbg_argmax_final(a, emb, stream);
+}
+
+// launch_draft_accept: the two words the kernel publishes go through a page-locked int32[2] this hook owns (made once, kept for
+// the process) and, with lp_out, the tokens through a device int[B * n] scratch this hook owns as well
+static int dbg_draft_accept(DraftAcceptArgs a, int32_t* host_out, void* stream) {
+    static std::mutex mu;
+    static int32_t* host = nullptr;
+    static int* lp_tok = nullptr;
+    static int64_t lp_cap = 0;
+    if (!host_out) return GITCAP_ERR_ARG;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!host && hipHostMalloc((void**)&host, 16, hipHostMallocMapped) != hipSuccess) { host = nullptr; return GITCAP_ERR_NOMEM; }
+    if (a.lp_out && a.B > 0 && a.n > 0 && (int64_t)a.B * a.n > lp_cap) {
+        if (lp_tok) { (void)hipDeviceSynchronize(); (void)hipFree(lp_tok); }
+        lp_cap = std::max<int64_t>((int64_t)a.B * a.n, 1024);
+        if (hipMalloc((void**)&lp_tok, (size_t)lp_cap * 4) != hipSuccess) { lp_tok = nullptr; lp_cap = 0; return GITCAP_ERR_NOMEM; }
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    ((volatile int32_t*)host)[0] = -1;
+    ((volatile int32_t*)host)[1] = -1;
+    a.host = host; a.lp_tok = a.lp_out ? lp_tok : nullptr;
+    const hipError_t e = launch_draft_accept(a, s);
+    if (e != hipSuccess) return dbg_rc(e);
+    if (hipStreamSynchronize(s) != hipSuccess) return GITCAP_ERR_HIP;
+    host_out[0] = ((volatile int32_t*)host)[0];
+    host_out[1] = ((volatile int32_t*)host)[1];
+    return 0;
+}
+int gitcap_dbg_draft_accept_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                               uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, const float* amax_sum, float* lp_out,
+                               int ld_lp, void* stream) {
+    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
+    DraftAcceptArgs a{};
+    a.val = amax_val; a.idx = amax_idx; a.sum = amax_sum; a.ntiles = ntiles; a.B = B; a.n = n; a.ids = ids; a.ld = ld; a.tok = tok;
+    a.ticket = ticket; a.sep_cnt = sep_cnt; a.sep_id = sep_id; a.lp_out = lp_out; a.ld_lp = ld_lp;
+    return dbg_draft_accept(a, host_out, stream);
+}
+int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
+                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream) {
+    DraftAcceptArgs a{};
+    a.val = amax_val; a.idx = amax_idx; a.ntiles = ntiles; a.B = B; a.n = n; a.ids = ids; a.ld = ld; a.tok = tok;
+    a.ticket = ticket; a.sep_cnt = sep_cnt; a.sep_id = sep_id;
+    return dbg_draft_accept(a, host_out, stream);
+}
+
+static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) {
+    if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len)
+        return false;
+    bb = BeamBuffers{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
+    return true;
+}
+
+// (gitcap_dbg_beam_buffers_nbest is gitcap_dbg_beam_buffers with the slot count n behind it)
+static bool dbg_beam_buffers_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamBuffers& bb) {
+    if (!b || b->n < 1 || b->n > 16) return false;
+    const gitcap_dbg_beam_buffers first{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
+    return dbg_beam_buffers(&first, bb);
+}
+
+int gitcap_dbg_beam_init(const gitcap_dbg_beam_buffers* b, int B, int beams, int max_len, int cls, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb) || B <= 0 || beams <= 0 || beams > 16 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_init(bb, B, beams, 1, max_len, cls, (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_finish(bb, 1, B, max_len, eos, BeamFinishOut{decoded, logprobs, nullptr, nullptr}, (hipStream_t)stream));
+}
+
+int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
+                                 void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_finish(bb, b->n, B, max_len, eos, BeamFinishOut{decoded, logprobs, nullptr, nullptr}, (hipStream_t)stream));
+}
+
+// launch_beam_step: one body for every form (the launcher refuses beams > 16 and K > 16 with the same status)
+static int dbg_beam_step(const BeamBuffers& bb, const BeamStepArgs& a, void* stream) {
+    if (!a.cand_scores || !a.cand_idx || a.B <= 0 || a.beams <= 0 || a.beams > 16 || a.K <= 0 || a.K > 16 || a.V <= 0 || a.cur_len < 1 ||
+        a.cur_len >= a.max_len || (a.cur != 0 && a.cur != 1))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_beam_step(bb, a, (hipStream_t)stream));
+}
+// the n-slot buffers' forms: a.n is the buffers'
+static int dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamStepArgs a, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers_nbest(b, bb)) return GITCAP_ERR_ARG;
+    a.n = b->n;
+    return dbg_beam_step(bb, a, stream);
+}
+
+int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams, int K,
+                         int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    BeamBuffers bb;
+    if (!dbg_beam_buffers(b, bb)) return GITCAP_ERR_ARG;
+    return dbg_beam_step(bb, BeamStepArgs{1, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, false, nullptr}, stream);
+}
+
+int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                               int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    return dbg_beam_step_nbest(b, BeamStepArgs{0, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, false, nullptr}, stream);
+}
+
+int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                                 int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
+    return dbg_beam_step_nbest(b, BeamStepArgs{0, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, true, nullptr}, stream);
+}
+
+// the forced forms (gitcap_attach_prompt): sampled = 0 and n = 1 runs beam_step_kernel, n > 1 the n-slot kernel, sampled != 0 its form
+// for draws; prompt_ids [B][ld_prompt], lengths [B], prompt_max_len < max_len
+int gitcap_dbg_beam_step_forced(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
+                                int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, int sampled,
+                                const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int prompt_max_len, void* stream) {
+    if (!prompt_ids || !lengths || prompt_max_len < 1 || prompt_max_len >= max_len || ld_prompt < prompt_max_len) return GITCAP_ERR_ARG;
+    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, prompt_max_len};
+    return dbg_beam_step_nbest(b, BeamStepArgs{0, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, sampled != 0, &pr}, stream);
+}
+
+// ---- text-row kernels of the token loop (tests/test_text_rows_gpu.py): each hook is ONE launcher on caller-owned device buffers,
+// no allocation, no handle; what a launcher does not check itself and a wrong value of which would index outside a buffer is
+// checked here
+int gitcap_dbg_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, void* stream) {
+    if (!src || !dst || K <= 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_pack_frags(src, dst, rows16, K, elem_bytes, (hipStream_t)stream));
+}
+
+int gitcap_dbg_kv_quant_v(const void* kv, void* v8, float* vs, int rows, int D, int H, int64_t pitch, void* stream) {
+    if (!kv || !v8 || !vs || H <= 0 || ((uintptr_t)kv & 15) || ((uintptr_t)v8 & 7)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_kv_quant_v((const bf16_t*)kv, (unsigned char*)v8, vs, rows, D, H, pitch, (hipStream_t)stream));
+}
+
+int gitcap_dbg_skinny(const gitcap_dbg_skinny_args* g, int epi, void* stream) {
+    if (!g || !g->W || !g->out || g->M <= 0 || g->N <= 0 || !skinny_full_ok(g->K) || g->ldo < g->N || g->T <= 0 || g->row_stride < 0 ||
+        g->row_off < 0 || ((uintptr_t)g->W & 15) || ((uintptr_t)g->Wpk & 15) || ((uintptr_t)g->out & 7) || (g->ldo & 3))
+        return GITCAP_ERR_ARG;
+    if (epi != SK_BIAS_BF16 && epi != SK_BIAS_GELU_BF16 && epi != SK_BIAS_RELU_BF16) return GITCAP_ERR_ARG;   // the head: gitcap_dbg_vocab_head
+    if (g->wscale && g->K != 128 && g->K != 768) return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)g->X; a.ldx = g->ldx; a.W = g->W; a.Wpk = g->Wpk; a.wscale = g->wscale; a.bias = g->bias;
+    a.M = g->M; a.N = g->N; a.K = g->K; a.out = g->out; a.ldo = g->ldo; a.T = g->T; a.row_stride = g->row_stride; a.row_off = g->row_off;
+    if (g->ln_kind) {
+        if ((g->ln_kind != 1 && g->ln_kind != 2) || !skinny_row_prologue_ok(g->M, g->K, g->wscale != nullptr) || epi == SK_BIAS_GELU_BF16 ||
+            !g->ln_g || !g->ln_b || !g->ln_xf)
+            return GITCAP_ERR_ARG;
+        if (g->ln_kind == 1 && (!g->ln_slabs || g->ln_nslab <= 0 || !g->ln_bias || !g->ln_resid || g->ln_resid == g->ln_xf)) return GITCAP_ERR_ARG;
+        if (g->ln_kind == 2 && (!g->ln_ids || g->ln_T <= 0 || g->ln_ld_ids < g->ln_T || g->ln_t0 < 0 || g->ln_vocab <= 0 || !g->ln_word || !g->ln_pos))
+            return GITCAP_ERR_ARG;
+        a.ln.kind = g->ln_kind; a.ln.slabs = g->ln_slabs; a.ln.nslab = g->ln_nslab; a.ln.bias = g->ln_bias; a.ln.resid = g->ln_resid;
+        a.ln.ids = g->ln_ids; a.ln.ld_ids = g->ln_ld_ids; a.ln.T = g->ln_T; a.ln.t0 = g->ln_t0; a.ln.vocab = g->ln_vocab;
+        a.ln.word = g->ln_word; a.ln.pos = g->ln_pos; a.ln.g = g->ln_g; a.ln.b = g->ln_b; a.ln.eps = g->ln_eps; a.ln.xf = g->ln_xf;
+    } else if (!g->X || g->ldx < g->K || (g->ldx & 7) || ((uintptr_t)g->X & 15)) {
+        return GITCAP_ERR_ARG;
+    }
+    return dbg_rc(launch_skinny(a, epi, (hipStream_t)stream));
+}
+
+int gitcap_dbg_skinny_splitk(const void* X, int ldx, const void* W, const void* Wpk, const float* wscale, int M, int N, int K, int ksplit,
+                             float* slabs, int ldo, void* stream) {
+    if (!X || !W || !slabs || M <= 0 || N <= 0 || K <= 0 || ksplit < 0 || ldx < K || (ldx & 7) || ldo < N || (ldo & 3) ||
+        ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || ((uintptr_t)Wpk & 15) || ((uintptr_t)slabs & 15))
+        return GITCAP_ERR_ARG;
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.Wpk = Wpk; a.wscale = wscale; a.M = M; a.N = N; a.K = K;
+    a.out = slabs; a.ldo = ldo; a.T = M; a.row_stride = M; a.ksplit = ksplit;
+    return dbg_rc(launch_skinny_splitk(a, (hipStream_t)stream));
+}
+
+int gitcap_dbg_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid, const float* gamma, const float* beta,
+                         float eps, int M, int D, float* xf, void* xb, void* stream) {
+    if (!slabs || !bias || !resid || !gamma || !beta || !xf || !xb || M <= 0 || D <= 0 || (D & 3) || nslab <= 0) return GITCAP_ERR_ARG;
+    if (((uintptr_t)slabs & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)resid & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15) ||
+        ((uintptr_t)xf & 15) || ((uintptr_t)xb & 7))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ln_reduce(slabs, nslab, bias, resid, gamma, beta, eps, M, D, xf, (bf16_t*)xb, (hipStream_t)stream));
+}
+
+int gitcap_dbg_ffn_txt(const void* X, int ldx, const void* W1pk, const void* W2pk, const float* w1scale, const float* w2scale,
+                       const float* b1, int M, int D, int F, float* slabs, void* stream) {
+    if (!X || !W1pk || !W2pk || !b1 || !slabs || M <= 0 || !ffn_txt_ok(D, F) || (w1scale != nullptr) != (w2scale != nullptr) || ldx < D ||
+        (ldx & 7) || ((uintptr_t)X & 15) || ((uintptr_t)W1pk & 15) || ((uintptr_t)W2pk & 15) || ((uintptr_t)slabs & 15))
+        return GITCAP_ERR_ARG;
+    FfnTxtArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.W1pk = W1pk; a.W2pk = W2pk; a.w1scale = w1scale; a.w2scale = w2scale; a.b1 = b1;
+    a.M = M; a.D = D; a.F = F; a.slabs = slabs;
+    return dbg_rc(launch_ffn_txt(a, (hipStream_t)stream));
+}
+
+// the tables of a variable-length hook (device int32 [n]) on the host: the stream is drained first (the caller may have
+// filled them on it)
+static bool dbg_read_tables(const int32_t* off, const int32_t* len, int n, hipStream_t s, std::vector<int32_t>& ho, std::vector<int32_t>& hl) {
+    if (!off || !len || n <= 0 || ((uintptr_t)off & 3) || ((uintptr_t)len & 3)) return false;
+    ho.resize(n); hl.resize(n);
+    return hipStreamSynchronize(s) == hipSuccess && hipMemcpy(ho.data(), off, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(hl.data(), len, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+int gitcap_dbg_attn_full_varlen(const void* qkv, void* ctx, int G, const int32_t* off, const int32_t* len, int H, void* stream) {
+    if (!qkv || !ctx || G <= 0 || H <= 0) return GITCAP_ERR_ARG;
+    std::vector<int32_t> ho, hl;
+    if (!dbg_read_tables(off, len, G, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
+    int mx = 0;
+    for (int g = 0; g < G; ++g) {
+        if (ho[g] < 0 || hl[g] < 1) return GITCAP_ERR_ARG;
+        mx = std::max(mx, hl[g]);
+    }
+    return launch_attn_full_varlen((const bf16_t*)qkv, (bf16_t*)ctx, G, off, len, mx, H, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
+}
+
+static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream);
+int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) { return dbg_txt_block(g, nullptr, nullptr, stream); }
+// variable-length form: off / len device int32 [clips], clips = ceil(rows / beams); S_img is not read
+int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
+    if (!g || g->rows <= 0 || g->beams <= 0) return GITCAP_ERR_ARG;
+    std::vector<int32_t> ho, hl;
+    const int clips = (g->rows - 1) / g->beams + 1;
+    if (!dbg_read_tables(off, len, clips, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
+    for (int c = 0; c < clips; ++c)
+        if (ho[c] < 0 || hl[c] < 0 || (g->v8_img && (int64_t)ho[c] + hl[c] > g->v8_pitch)) return GITCAP_ERR_ARG;
+    return dbg_txt_block(g, off, len, stream);
+}
+
+static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
+    if (!g || !g->kv_img || !g->kv_txt || !g->aow || !g->aob || !g->g1 || !g->b1 || !g->xin || !g->part || !g->cnt || !g->xs || !g->xsb)
+        return GITCAP_ERR_ARG;
+    if (g->rows <= 0 || g->beams <= 0 || g->T <= 0 || g->t0 < 0 || g->t0 + g->T > g->Tmax || g->S_img < 0 || !txt_block_ok(g->D) ||
+        g->H * 64 != g->D || (g->v8_img != nullptr) != (g->vs_img != nullptr) ||
+        (g->v8_img && !off && g->v8_pitch < (int64_t)((g->rows - 1) / g->beams + 1) * g->S_img))
+        return GITCAP_ERR_ARG;
+    // the widest access txt_block_kernel makes on each buffer: 16-byte rows of q / k / v and of the output dense (8 bytes of e4m3 codes),
+    // 8 bytes of V codes; everything else -- scales, bias, gamma / beta, residual, part, tickets, xs -- one float or word at a time, xsb
+    // one bf16 at a time
+    if (((uintptr_t)g->kv_img & 15) || ((uintptr_t)g->kv_txt & 15) || ((uintptr_t)g->aow & 15) || ((uintptr_t)g->aowpk & 15) ||
+        ((uintptr_t)g->v8_img & 7) || ((uintptr_t)g->vs_img & 3) || ((uintptr_t)g->aoscale & 3) || ((uintptr_t)g->aob & 3) ||
+        ((uintptr_t)g->g1 & 3) || ((uintptr_t)g->b1 & 3) || ((uintptr_t)g->xin & 3) || ((uintptr_t)g->part & 3) || ((uintptr_t)g->cnt & 3) ||
+        ((uintptr_t)g->xs & 3) || ((uintptr_t)g->xsb & 1))
+        return GITCAP_ERR_ARG;
+    TxtBlockArgs a{};
+    a.kv_img = (const bf16_t*)g->kv_img; a.kv_txt = (const bf16_t*)g->kv_txt;
+    a.rows = g->rows; a.beams = g->beams; a.t0 = g->t0; a.T = g->T; a.Tmax = g->Tmax; a.S_img = g->S_img; a.H = g->H; a.D = g->D;
+    a.aow = g->aow; a.aowpk = g->aoscale ? nullptr : g->aowpk; a.aoscale = g->aoscale; a.aob = g->aob; a.g1 = g->g1; a.b1 = g->b1;
+    a.xin = g->xin; a.eps = g->eps; a.part = g->part; a.cnt = g->cnt; a.xs = g->xs; a.xsb = (bf16_t*)g->xsb;
+    a.v8_img = (const unsigned char*)g->v8_img; a.vs_img = g->vs_img; a.v8_pitch = g->v8_pitch; a.nt_kv = g->nt_kv ? 1 : 0;
+    a.off = off; a.len = len;
+    return dbg_rc(launch_txt_block(a, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -536,11 +536,20 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
            !(g_row_prologue && skinny_row_prologue_ok(rows, h->D, h->dec[0].qkvw.scale != nullptr));
 }
 
-int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams, int t0, int T, float* logits_out,
-                 int all_positions, int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s,
-                 bool pre_embedded = false, bool embed_next = false, float* lp_out = nullptr, int ld_lp = 0, const ScoreReq* score = nullptr,
-                 const PromptArgs* prompt = nullptr, const HeadBan* ban = nullptr) {
+// A pass of the decoder over text rows (RowsReq, kernels.h) and what only this stack takes: rows = clips * beams; all_positions:
+// logits of every position instead of the last; the per-step modifiers pre_embedded / embed_next (above), prompt (the arg-max
+// launch's, nullable) and ban (the BAN form of the head, nullable).
+struct TextReq : RowsReq {
+    int beams = 1, all_positions = 0;
+    bool pre_embedded = false, embed_next = false;
+    const PromptArgs* prompt = nullptr;
+    const HeadBan* ban = nullptr;
+};
+
+int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
     const gitcap_config& c = h->c;
+    const int64_t* const ids = q.ids;
+    const int ld_ids = q.ld_ids, rows = q.rows, beams = q.beams, t0 = q.t0, T = q.T;
     gitcap::Slot& sl = cur(h);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
     if (!sl.have) return fail(h, GITCAP_ERR_STATE, "text_forward before encode/set_visual");
@@ -590,7 +599,7 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
             std::swap(xcur, xalt);
         } else {
             if (l == 0) {
-                if (!pre_embedded)
+                if (!q.pre_embedded)
                     HIP_OK(h, launch_embed_text(ids, ld_ids, rows, T, t0, h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D,
                                                 c.vocab_size, xcur, sl.xsb, s));
             } else {
@@ -633,31 +642,34 @@ int text_forward(gitcap* h, const int64_t* ids, int ld_ids, int rows, int beams,
         if ((rc = ln_reduce(h, s, sl.slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, sl.xsb))) return rc;
         HIP_OK(h, keep_txt(c.dec_layers));
     }
-    if (!logits_out && !argmax_out && !score) return 0;
+    if (!q.logits_out && !q.argmax_out && !q.score) return 0;
     // vocabulary head (+ arg-max partials per 16-column tile, reduced by argmax_final)
     const int V = c.vocab_size, ntiles = (V + 15) / 16;
-    if (score) {        // gitcap_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
+    if (q.score) {      // gitcap_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
         if (!sl.amax_sum || !sl.score_buf) return fail(h, GITCAP_ERR_STATE, "text_forward: scoring without its buffers");
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * M * V * D, (h->head_w.scale ? 1.0 : 2.0) * V * D);
         HIP_OK(h, launch_score(HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, ids, ld_ids, rows, T,
-                               sl.amax_val, sl.amax_idx, sl.amax_sum, sl.score_buf, *score, s));
+                               sl.amax_val, sl.amax_idx, sl.amax_sum, sl.score_buf, *q.score, s));
         return 0;
     }
-    if (lp_out && (!argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
+    if (q.lp_out && (!q.argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
     SkinnyArgs ha;      // amax_sum: the head's third partial -> the chosen token's log-probability (argmax_final)
     const HeadRows hr = vocab_head_args(ha, HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, rows, T,
-                                        all_positions && logits_out, logits_out, argmax_out ? sl.amax_val : nullptr,
-                                        argmax_out ? sl.amax_idx : nullptr, lp_out ? sl.amax_sum : nullptr);
+                                        q.all_positions && q.logits_out, q.logits_out, q.argmax_out ? sl.amax_val : nullptr,
+                                        q.argmax_out ? sl.amax_idx : nullptr, q.lp_out ? sl.amax_sum : nullptr);
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
-        HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s, nullptr, ban));     // ban (constrained greedy step): the BAN form of the head
+        HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s, nullptr, q.ban));     // ban (constrained greedy step): the BAN form of the head
     }
-    if (argmax_out) {
+    if (q.argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
-        // prompt (greedy loop): the token goes to position t0 + T, where a row's prompt may still stand
-        HIP_OK(h, launch_argmax_final(sl.amax_val, sl.amax_idx, ntiles, rows, hr.am_stride, hr.am_off, argmax_out, ld_argmax,
-                                      sep_cnt, step, c.sep_token_id, s, embed_next ? &ne : nullptr, lp_out ? sl.amax_sum : nullptr,
-                                      lp_out, ld_lp, prompt, t0 + T));
+        ArgmaxArgs a{};
+        a.val = sl.amax_val; a.idx = sl.amax_idx; a.sum = q.lp_out ? sl.amax_sum : nullptr; a.ntiles = ntiles;
+        a.rows = rows; a.row_stride = hr.am_stride; a.row_off = hr.am_off;
+        a.out = q.argmax_out; a.ld_out = q.ld_argmax; a.sep_cnt = q.sep_cnt; a.step = q.step; a.sep_id = c.sep_token_id;
+        a.lp_out = q.lp_out; a.ld_lp = q.ld_lp; a.emb = q.embed_next ? &ne : nullptr;
+        a.prompt = q.prompt; a.prompt_pos = t0 + T;       // (greedy loop): the token goes to position t0 + T, where a row's prompt may still stand
+        HIP_OK(h, launch_argmax_final(a, s));
     }
     return 0;
 }
@@ -1200,8 +1212,10 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
     POLL(h);
     select_slot(h, 0);
     HIP_OK(h, join_async(h, (hipStream_t)stream));
-    return text_forward(h, ids, ld_ids, rows, beams, t0, T, logits_out, all_positions, argmax_out, ld_argmax, nullptr, 0,
-                        (hipStream_t)stream);
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.beams = beams; q.t0 = t0; q.T = T;
+    q.logits_out = logits_out; q.all_positions = all_positions; q.argmax_out = argmax_out; q.ld_argmax = ld_argmax;
+    return text_forward(h, q, (hipStream_t)stream);
 }
 
 // token steps t_first .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
@@ -1218,15 +1232,18 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
     // included), and the head runs in its BAN form; a position a prompt forces takes the prompt's token whatever is banned
     const ConsOpt& co = h->call.co;
     const HeadBan bn{cur(h).ban_mask, h->ban_ld};
+    TextReq q;                                               // what every step shares; the position's part is filled per step
+    q.ld_ids = ld; q.rows = rows; q.T = 1; q.ld_argmax = ld; q.sep_cnt = cur(h).sep_cnt; q.ld_lp = lp.ld;
+    q.prompt = prompt; q.ban = co.on ? &bn : nullptr;
     for (int t = t_first; t < max_len; ++t) {
         // forward on the sequence so far, argmax of the last position, append (model.py:173-182)
         const bool next = chain && t + 1 < max_len && t + 1 < h->c.max_text_pos;
         if (co.on)
             HIP_OK(h, launch_ban_mask(ids_out, ld, rows, t + 1, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress,
                                       h->c.vocab_size, cur(h).ban_mask, bn.ld, s));
-        const int rc = text_forward(h, ids_out + t, ld, rows, 1, t, 1, nullptr, 0, ids_out + t + 1, ld, cur(h).sep_cnt, t, s, have_rows, next,
-                                    lp.p ? lp.p + t : nullptr, lp.ld, nullptr, prompt, co.on ? &bn : nullptr);
-        if (rc) return rc;
+        q.ids = ids_out + t; q.t0 = q.step = t; q.argmax_out = ids_out + t + 1; q.lp_out = lp.p ? lp.p + t : nullptr;
+        q.pre_embedded = have_rows; q.embed_next = next;
+        if (const int rc = text_forward(h, q, s)) return rc;
         have_rows = next;
     }
     return 0;
@@ -1258,8 +1275,11 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
         int t_first = 0;
         if (P > 1) {
             if (lp.p) HIP_OK(h, hipMemset2DAsync(lp.p, (size_t)lp.ld * 4, 0, (size_t)(P - 1) * 4, B, s));    // forced positions: 0.0f
-            if ((rc = text_forward(h, ids_out, ld, B, 1, 0, P, nullptr, 0, ids_out + P, ld, sl.sep_cnt, P - 1, s, false, false,
-                                   lp.p ? lp.p + (P - 1) : nullptr, lp.ld, nullptr, &pr))) return rc;
+            TextReq q;
+            q.ids = ids_out; q.ld_ids = ld; q.rows = B; q.T = P;
+            q.argmax_out = ids_out + P; q.ld_argmax = ld; q.sep_cnt = sl.sep_cnt; q.step = P - 1;
+            q.lp_out = lp.p ? lp.p + (P - 1) : nullptr; q.ld_lp = lp.ld; q.prompt = &pr;
+            if ((rc = text_forward(h, q, s))) return rc;
             t_first = P;
         }
         if ((rc = greedy_rows(h, B, max_len, ids_out, ld, s, t_first))) return rc;
@@ -1383,6 +1403,18 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
     BeamBuffers bb = sl.beam;
     if (so.n > 1) { bb.hyp_ids = sl.nb_ids; bb.hyp_score = sl.nb_score; bb.hyp_len = sl.nb_len; }
     HIP_OK(h, launch_beam_init(bb, B, beams, so.n, L, h->c.cls_token_id, s));
+    // constraints attached: the mask of the B * beams rows, each from the buffer that holds its current prefix
+    const HeadBan bn{sl.ban_mask, h->ban_ld};
+    const HeadBan* ban = co.on ? &bn : nullptr;
+    // the records of a step: what does not change from step to step is filled here
+    TextReq q;                  // one position of every beam row: logits only where the step ranks or the caller keeps them
+    q.ids = sl.beam.words; q.ld_ids = 1; q.rows = rows; q.beams = beams; q.T = 1;
+    CandArgs ca{};
+    ca.ld = V; ca.beam_scores = sl.beam.beam_scores; ca.ld_ids = L; ca.rp = so.rp; ca.B = B; ca.beams = beams; ca.V = V;
+    ca.out_scores = sl.cand_scores; ca.out_idx = sl.cand_idx; ca.bn = ban;
+    BeamStepArgs st{};
+    st.n = so.n; st.cand_scores = sl.cand_scores; st.cand_idx = sl.cand_idx; st.B = B; st.beams = beams; st.K = K; st.V = V;
+    st.max_len = L; st.eos = h->c.sep_token_id; st.length_penalty = length_penalty; st.sampled = so.smp.on; st.prompt = prompt;
     // while cur_len < max_length (model.py:518): the token at position cur_len-1 is decoded, candidates for
     // position cur_len are ranked, bookkept and the text K/V rows follow their beams -- no host round trip
     for (int cur_len = 1, cur = 0; cur_len < L; ++cur_len, cur ^= 1) {
@@ -1396,26 +1428,21 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         }
         // (an all-forced step needs the K/V append only: no vocabulary head unless the caller keeps the step logits)
         float* lg = step_logits_out ? step_logits_out + (size_t)t * rows * V : (ranked ? sl.beam_logits : nullptr);
-        rc = text_forward(h, sl.beam.words, 1, rows, beams, t, 1, lg, 0, nullptr, 0, nullptr, 0, s);
-        if (rc) return rc;
-        // constraints attached: the mask of the B * beams rows, each from the buffer that holds its current prefix
-        const HeadBan bn{sl.ban_mask, h->ban_ld};
-        const HeadBan* ban = co.on ? &bn : nullptr;
+        q.t0 = t; q.logits_out = lg;
+        if ((rc = text_forward(h, q, s))) return rc;
+        ca.logits = lg; ca.prefix_ids = cur ? sl.beam.ids1 : sl.beam.ids0; ca.cur_len = cur_len;
         if (ranked && ban)
-            HIP_OK(h, launch_ban_mask(cur ? sl.beam.ids1 : sl.beam.ids0, L, rows, cur_len, co.ngram, co.min_length, h->c.sep_token_id, co.suppress,
-                                      co.n_suppress, V, sl.ban_mask, bn.ld, s));
+            HIP_OK(h, launch_ban_mask(ca.prefix_ids, L, rows, cur_len, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress, V,
+                                      sl.ban_mask, bn.ld, s));
         if (!ranked) {
         } else if (so.smp.on)                                                       // model.py:532-554: K draws instead of the K best
-            HIP_OK(h, launch_sample_rows(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V,
-                                         per_node_beam_size, so.smp.temperature, so.smp.top_k, so.smp.top_p, so.smp.seed, sl.cand_scores,
-                                         sl.cand_idx, nullptr, nullptr, s, ban));
+            HIP_OK(h, launch_sample_rows(ca, per_node_beam_size, so.smp, SampleStats{}, s));
         else
-            HIP_OK(h, launch_beam_topk(lg, V, sl.beam.beam_scores, cur ? sl.beam.ids1 : sl.beam.ids0, L, cur_len, so.rp, B, beams, V, K,
-                                       sl.cand_scores, sl.cand_idx, sl.topk_scratch, s, ban));
-        HIP_OK(h, launch_beam_step(bb, so.n, sl.cand_scores, sl.cand_idx, B, beams, K, V, cur_len, L, h->c.sep_token_id, length_penalty, cur, s,
-                                   so.smp.on, prompt));
+            HIP_OK(h, launch_beam_topk(ca, K, sl.topk_scratch, s));
+        st.cur_len = cur_len; st.cur = cur;
+        HIP_OK(h, launch_beam_step(bb, st, s));
     }
-    HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, so.nbest, so.nbest_lp, decoded_out, logprobs_out, s));
+    HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, BeamFinishOut{so.nbest, so.nbest_lp, decoded_out, logprobs_out}, s));
     return 0;
 }
 
@@ -1632,8 +1659,10 @@ int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beam
     if ((rc = ensure_amax_sum(h))) return rc;
     if (!sl.score_buf && (rc = dev_alloc(h, &sl.score_buf, 2 * (size_t)sl.Mt))) return rc;
     HIP_OK(h, join_async(h, (hipStream_t)stream));
-    const ScoreReq q{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
-    return text_forward(h, ids, ld_ids, rows, beams, 0, T, nullptr, 1, nullptr, 0, nullptr, 0, (hipStream_t)stream, false, false, nullptr, 0, &q);
+    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.beams = beams; q.T = T; q.score = &sq;
+    return text_forward(h, q, (hipStream_t)stream);
 }
 
 int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream) {
@@ -1685,7 +1714,9 @@ int gitcap_distill(gitcap_t* h, gitcap_student_t* st, const int64_t* ids, int ld
     hipStream_t s = (hipStream_t)stream;
     HIP_OK(h, join_async(h, s));
     // both stacks up to their final LayerNorm rows (the "rows only, no head" request of the existing passes), then the two launches
-    if ((rc = text_forward(h, ids, ld_ids, rows, beams, 0, T, nullptr, 1, nullptr, 0, nullptr, 0, s))) return rc;
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.beams = beams; q.T = T;
+    if ((rc = text_forward(h, q, s))) return rc;
     StudentRows sr{};
     if ((rc = student_forward_rows(st, ids, ld_ids, rows, T, s, &sr, why))) return fail(h, rc, "distill: " + why);
     const gitcap::Distill& d = h->dist;
@@ -1846,145 +1877,6 @@ int gitcap_preprocess(const uint8_t* frames_hwc_bgr, int nf, int H, int W, float
     return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
 }
 
-// no handle here: the scratch of the two-stage top-k is a stream-ordered allocation
-static int beam_topk_hook(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
-                          int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream, const HeadBan* bn = nullptr) {
-    if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || K <= 0) return GITCAP_ERR_ARG;
-    void* scratch = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMallocAsync(&scratch, beam_topk_scratch_bytes(B, beams, V, K), s) != hipSuccess) return GITCAP_ERR_NOMEM;
-    const hipError_t e = launch_beam_topk(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, out_scores, out_idx, scratch, s, bn);
-    (void)hipFreeAsync(scratch, s);
-    return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
-}
-
-int gitcap_beam_topk(const float* logits, int ld, const float* beam_scores, int B, int beams, int V, int K,
-                     float* out_scores, int32_t* out_idx, void* stream) {
-    return beam_topk_hook(logits, ld, beam_scores, nullptr, 0, 0, 1.0f, B, beams, V, K, out_scores, out_idx, stream);
-}
-
-int gitcap_beam_topk_penalized(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                               float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx, void* stream) {
-    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty)) return GITCAP_ERR_ARG;
-    if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
-    if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
-    return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream);
-}
-
-static int sample_rows_hook(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                            float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
-                            uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream,
-                            const HeadBan* bn) {
-    if (!logits || !beam_scores || !out_scores || !out_idx || B <= 0 || beams <= 0 || V <= 0 || per_node <= 0) return GITCAP_ERR_ARG;
-    if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)kept_out & 3) != 0 || ((uintptr_t)logz_out & 3) != 0) return GITCAP_ERR_ARG;
-    const hipError_t e = launch_sample_rows(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node,
-                                            temperature, top_k, top_p, seed, out_scores, out_idx, kept_out, logz_out, (hipStream_t)stream, bn);
-    return e == hipSuccess ? 0 : (e == hipErrorInvalidValue ? GITCAP_ERR_ARG : GITCAP_ERR_HIP);
-}
-
-int gitcap_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                       float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
-                       uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out, void* stream) {
-    return sample_rows_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node, temperature, top_k,
-                            top_p, seed, out_scores, out_idx, kept_out, logz_out, stream, nullptr);
-}
-
-// ---- constrained decoding (tests/test_constraints_gpu.py): each hook is ONE launcher on caller-owned device buffers ----------------
-static bool ban_mask_ok(const uint16_t* mask, int ld_mask, int V) {
-    return mask && ((uintptr_t)mask & 3) == 0 && V > 0 && ld_mask >= (V + 15) / 16 && (ld_mask & 1) == 0;
-}
-
-int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
-                        const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream) {
-    if (((uintptr_t)prefix_ids & 7) != 0 || ((uintptr_t)suppress & 3) != 0) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_ban_mask(prefix_ids, ld_ids, rows, cur_len, n, min_length, sep_id, suppress, n_suppress, V, mask_out, ld_mask,
-                                  (hipStream_t)stream));
-}
-
-int gitcap_beam_topk_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                                 float repetition_penalty, int B, int beams, int V, int K, float* out_scores, int32_t* out_idx,
-                                 const uint16_t* mask, int ld_mask, void* stream) {
-    if (!(repetition_penalty > 0.f) || !std::isfinite(repetition_penalty) || !ban_mask_ok(mask, ld_mask, V)) return GITCAP_ERR_ARG;
-    if (repetition_penalty != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || ((uintptr_t)prefix_ids & 7) != 0)) return GITCAP_ERR_ARG;
-    if (beams > 16 || K > 16 || (int64_t)K > (int64_t)beams * V || V > 131072) return GITCAP_ERR_ARG;      // before the scratch is sized
-    const HeadBan bn{mask, ld_mask};
-    return beam_topk_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, K, out_scores, out_idx, stream, &bn);
-}
-
-int gitcap_sample_rows_constrained(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                                   float repetition_penalty, int B, int beams, int V, int per_node, float temperature, int top_k, float top_p,
-                                   uint64_t seed, float* out_scores, int32_t* out_idx, int32_t* kept_out, float* logz_out,
-                                   const uint16_t* mask, int ld_mask, void* stream) {
-    if (!ban_mask_ok(mask, ld_mask, V)) return GITCAP_ERR_ARG;
-    const HeadBan bn{mask, ld_mask};
-    return sample_rows_hook(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, repetition_penalty, B, beams, V, per_node, temperature, top_k,
-                            top_p, seed, out_scores, out_idx, kept_out, logz_out, stream, &bn);
-}
-
-int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
-                    int epi, int tile, void* stream) {
-    GemmArgs a{};
-    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.bias = bias; a.M = M; a.N = N; a.K = K;
-    a.out = out; a.ldo = N; a.resid = resid; a.ldr = N;
-    if (epi < 0 || epi > EPI_BIAS_F32) return GITCAP_ERR_ARG;
-    if (tile != 64 && tile != 128 && tile != 256) return GITCAP_ERR_ARG;
-    const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
-    return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
-// fp8 tile kernel (gemm256.hip) on caller-owned buffers: A8 [M][K], W8 [N][K] e4m3 codes, wscale [N], acc * ascale * wscale[n] + bias;
-// epi 4 -> out fp32 [M][N]; epi 0 -> bf16; epi 8 / 9 -> e4m3 codes of gelu(.) * out8_inv
-int gitcap_dbg_gemm_f8(const void* A8, const void* W8, const float* wscale, float ascale, const float* bias, void* out, int M, int N,
-                       int K, int epi, float out8_inv, void* stream) {
-    GemmArgs a{};
-    a.A = (const bf16_t*)A8; a.lda = K; a.W = (const bf16_t*)W8; a.wscale = wscale; a.ascale = ascale; a.bias = bias;
-    a.M = M; a.N = N; a.K = K; a.out = out; a.ldo = N; a.out8_inv = out8_inv;
-    if (epi != EPI_BIAS_F32 && epi != EPI_BIAS_BF16 && epi != EPI_BIAS_QGELU_F8 && epi != EPI_BIAS_GELU_F8) return GITCAP_ERR_ARG;
-    if (!gemm256f8_ok(a)) return GITCAP_ERR_ARG;
-    return launch_gemm256f8(a, epi, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
-// GEMM + bias [+ resid] + LayerNorm: fused = 1 the EPI_RESID_LN_* epilogue of the 256x256 kernel, 0 = GEMM (tile) then the
-// row kernel; post as in gemm_ln (gitcap.hip).  out_f32: post ? LN(x) : x.  Scratch for the exchange is allocated here.
-int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const float* resid, const float* gamma,
-                       const float* beta, float eps, float* out_f32, void* out_bf16, int M, int N, int K, int post,
-                       int fused, int tile, void* stream) {
-    static float2* stats = nullptr; static unsigned* cnt = nullptr; static int cap = 0;
-    hipStream_t s = (hipStream_t)stream;
-    GemmArgs a{};
-    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.bias = bias; a.M = M; a.N = N; a.K = K;
-    a.out = out_f32; a.ldo = N; a.resid = resid; a.ldr = N;
-    if (!fused) {
-        if (tile != 64 && tile != 128 && tile != 256) return GITCAP_ERR_ARG;
-        float* xo = out_f32;
-        float* tmp = nullptr;
-        if (post) { if (hipMalloc(&tmp, (size_t)M * N * 4) != hipSuccess) return GITCAP_ERR_NOMEM; xo = tmp; a.out = tmp; }
-        const int epi = resid ? EPI_BIAS_RESID_F32 : EPI_BIAS_F32;
-        hipError_t e = tile == 256 ? launch_gemm256(a, epi, s) : tile == 64 ? launch_gemm64(a, epi, s) : launch_gemm(a, epi, s);
-        if (e == hipSuccess) {
-            LnArgs l{xo, N, gamma, beta, eps, M, N, post ? out_f32 : nullptr, N, (bf16_t*)out_bf16, N, nullptr, 1, 1, nullptr, nullptr, 0.f};
-            e = launch_layernorm(l, s);
-        }
-        if (tmp) { (void)hipStreamSynchronize(s); (void)hipFree(tmp); }
-        return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
-    }
-    if (M / 224 + 2 > cap) {
-        if (stats) { (void)hipFree(stats); (void)hipFree(cnt); }
-        cap = M / 224 + 2;
-        if (hipMalloc(&stats, (size_t)cap * 256 * 16 * sizeof(float2)) != hipSuccess || hipMalloc(&cnt, (size_t)cap * 8) != hipSuccess) return GITCAP_ERR_NOMEM;
-        if (hipMemset(cnt, 0, (size_t)cap * 8) != hipSuccess) return GITCAP_ERR_HIP;
-    }
-    a.ln_g = gamma; a.ln_b = beta; a.ln_eps = eps; a.ln_out = (bf16_t*)out_bf16; a.ld_ln = N; a.ln_stats = stats; a.ln_cnt = cnt;
-    a.ln_stats_rows = cap * 224;
-    const int epi = post ? EPI_RESID_LN_POST : EPI_RESID_LN_PRE;
-    if (!post && !resid) return GITCAP_ERR_ARG;
-    hipError_t e;
-    if (fused != 1 || !gemm256_ln_ok(a)) return GITCAP_ERR_ARG;          // the 256x256 kernel of gemm256.hip
-    e = launch_gemm256(a, epi, s);
-    return e == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
 // Speed-only switches at run time (the same ones the GITCAP_* environment variables set once per process): lets ONE process
 // check that results do not depend on them.  key 0: GEMM + LayerNorm epilogue on/off, 1: one/two-row prologue on/off,
 // 2: 256-tile threshold (GITCAP_GEMM_SMALL_TILES), 3: 128-tile threshold (GITCAP_GEMM_TINY_TILES), 4: retired (no effect),
@@ -2014,376 +1906,6 @@ int gitcap_dbg_config(int key, int value) {
         default: return GITCAP_ERR_ARG;
     }
     return old;
-}
-
-int gitcap_dbg_attn_full(const void* qkv, void* ctx, int G, int S, int H, void* stream) {
-    return launch_attn_full((const bf16_t*)qkv, (bf16_t*)ctx, G, S, H, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
-int gitcap_dbg_layernorm(const float* x, const float* gamma, const float* beta, float eps, int rows, int D,
-                         float* out_f32, void* out_bf16, void* stream) {
-    LnArgs a{x, D, gamma, beta, eps, rows, D, out_f32, D, (bf16_t*)out_bf16, D, nullptr, 1, 1, nullptr, nullptr, 0.f};
-    return launch_layernorm(a, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
-// ---- token selection (tests/test_selection_gpu.py): each hook is ONE launcher on caller-owned device buffers --------------
-// launch_skinny with SK_BIAS_F32 under the identity row map: the vocabulary head of the token loops (switch 10 picks its form)
-static int dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                          float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream, const HeadBan* bn = nullptr) {
-    if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || (amax_val == nullptr) != (amax_idx == nullptr) ||
-        (!logits && !amax_val) || (amax_sum && !amax_val))
-        return GITCAP_ERR_ARG;
-    SkinnyArgs a{};
-    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
-    a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
-    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
-    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream, nullptr, bn));
-}
-// the BAN forms of the same launch (mask uint16 [M][ld_mask], kernels.h: HeadBan); amax_sum NULL: the plain form, else the LSE form
-int gitcap_dbg_vocab_head_banned(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                                 float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const uint16_t* mask, int ld_mask,
-                                 void* stream) {
-    if (!ban_mask_ok(mask, ld_mask, N)) return GITCAP_ERR_ARG;
-    const HeadBan bn{mask, ld_mask};
-    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum, stream, &bn);
-}
-int gitcap_dbg_vocab_head(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                          float* logits, float* amax_val, int32_t* amax_idx, void* stream) {
-    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, nullptr, stream);
-}
-// the same launch with the third partial (amax_sum [M][ntiles], required)
-int gitcap_dbg_vocab_head_lse(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                              float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, void* stream) {
-    if (!amax_sum) return GITCAP_ERR_ARG;
-    return dbg_vocab_head(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum, stream);
-}
-
-// the scoring head: the _lse launch + the logit of each row's target column (targets int64 [M], tgt_logit fp32 [M])
-int gitcap_dbg_vocab_head_score(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
-                                float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const int64_t* targets, float* tgt_logit,
-                                void* stream) {
-    if (!X || !W || M <= 0 || N <= 0 || ldx < K || ldx % 8 || !skinny_full_ok(K) || !amax_val || !amax_idx || !amax_sum || !targets || !tgt_logit)
-        return GITCAP_ERR_ARG;
-    SkinnyArgs a{};
-    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.wscale = wscale; a.bias = bias; a.M = M; a.N = N; a.K = K;
-    a.out = logits; a.ldo = N; a.T = M; a.row_stride = M; a.row_off = 0;
-    a.amax_val = amax_val; a.amax_idx = amax_idx; a.Wpk = nullptr; a.amax_sum = amax_sum;
-    const HeadTargets tg{targets, M, M, 0, tgt_logit};
-    return dbg_rc(launch_skinny(a, SK_BIAS_F32, (hipStream_t)stream, &tg));
-}
-// launch_score_final on caller-owned buffers: partials [rows * T][ntiles], tgt_logit [rows * T], ids [rows][ld_ids]
-int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
-                           const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
-                           float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
-    if (!token_lp) return GITCAP_ERR_ARG;
-    const ScoreOut o{token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
-    return dbg_rc(launch_score_final(amax_val, amax_idx, amax_sum, ntiles, tgt_logit, ids, ld_ids, rows, T, lengths, ignore_id, V, o,
-                                     (hipStream_t)stream));
-}
-
-// launch_head_dual on caller-owned buffers, row-major weights; targets: one column per row (HeadTargets with T = ld = M, shift 0)
-int gitcap_dbg_vocab_head_dual(const void* Xt, int ldxt, const void* Wt, const float* wscale, const float* bias_t, int Kt, const void* Xs,
-                               int ldxs, const void* Ws, const float* bias_s, int Ks, int M, int N, float inv_temperature, float* t_max,
-                               int32_t* t_idx, float* t_sum, float* s_max, int32_t* s_idx, float* s_sum, float* cross,
-                               const int64_t* targets, float* t_logit, float* s_logit, void* stream) {
-    DualHeadArgs a{};
-    a.Xt = (const bf16_t*)Xt; a.ldxt = ldxt; a.Xs = (const bf16_t*)Xs; a.ldxs = ldxs;
-    a.wt = HeadWeight{Wt, nullptr, wscale, bias_t, N, Kt}; a.ws = HeadWeight{Ws, nullptr, nullptr, bias_s, N, Ks};
-    a.M = M; a.inv_temp = inv_temperature;
-    a.t_max = t_max; a.t_idx = t_idx; a.t_sum = t_sum; a.s_max = s_max; a.s_idx = s_idx; a.s_sum = s_sum; a.cross = cross;
-    if (targets) { a.tg = HeadTargets{targets, M, M, 0, t_logit}; a.s_logit = s_logit; }
-    return dbg_rc(launch_head_dual(a, (hipStream_t)stream));
-}
-int gitcap_dbg_distill_final(const float* t_max, const int32_t* t_idx, const float* t_sum, const float* s_max, const int32_t* s_idx,
-                             const float* s_sum, const float* cross, int ntiles, const float* t_logit, const float* s_logit,
-                             const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
-                             const gitcap_distill_out* out, void* stream) {
-    if (!out) return GITCAP_ERR_ARG;
-    const DistillOut o{out->kl, out->ld_kl, out->teacher_top1, out->student_top1, out->agree, out->teacher_lp, out->student_lp, out->ld_lp,
-                       out->row_kl_sum, out->row_cnt};
-    return dbg_rc(launch_distill_final(DistillPartials{t_max, t_idx, t_sum, s_max, s_idx, s_sum, cross}, ntiles, t_logit, s_logit, ids, ld_ids,
-                                       rows, T, lengths, ignore_id, V, o, (hipStream_t)stream));
-}
-
-static int dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                            const float* amax_sum, float* lp_out, int ld_lp, void* stream, const PromptArgs* prompt = nullptr) {
-    if (!amax_val || !amax_idx || !out || ntiles <= 0 || rows <= 0 || row_stride <= 0 || row_off < 0 || ld_out <= 0 || step < 0)
-        return GITCAP_ERR_ARG;
-    NextEmbed ne{};
-    if (emb) {
-        if (emb->vocab <= 0 || emb->position < 0) return GITCAP_ERR_ARG;
-        ne = NextEmbed{emb->word, emb->pos, emb->gamma, emb->beta, emb->eps, emb->D, emb->vocab, emb->position, emb->xf, (bf16_t*)emb->xb};
-    }
-    return dbg_rc(launch_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id,
-                                      (hipStream_t)stream, emb ? &ne : nullptr, amax_sum, lp_out, ld_lp, prompt, step + 1));
-}
-int gitcap_dbg_argmax_final(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                            int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                            void* stream) {
-    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, nullptr, nullptr, 0, stream);
-}
-int gitcap_dbg_argmax_final_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                               const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
-    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
-    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, amax_sum, lp_out, ld_lp, stream);
-}
-
-// the forced form (gitcap_attach_prompt): the launch writes position step + 1; amax_sum / lp_out both or neither
-int gitcap_dbg_argmax_final_forced(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                                   int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
-                                   const float* amax_sum, float* lp_out, int ld_lp, const int64_t* prompt_ids, int ld_prompt,
-                                   const int32_t* lengths, int max_len, void* stream) {
-    if (!prompt_ids || !lengths || max_len < 1 || ld_prompt < max_len || (amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1))
-        return GITCAP_ERR_ARG;
-    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, max_len};
-    return dbg_argmax_final(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, emb, amax_sum, lp_out, ld_lp,
-                            stream, &pr);
-}
-
-// the two words the kernel publishes go through a page-locked int32[2] this hook owns (made once, kept for the process)
-// (and, with lp_out, through a device int[B * n] scratch this hook owns as well)
-static int dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
-                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, const float* amax_sum, float* lp_out,
-                            int ld_lp, void* stream) {
-    static std::mutex mu;
-    static int32_t* host = nullptr;
-    static int* lp_tok = nullptr;
-    static int64_t lp_cap = 0;
-    if (!host_out) return GITCAP_ERR_ARG;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!host && hipHostMalloc((void**)&host, 16, hipHostMallocMapped) != hipSuccess) { host = nullptr; return GITCAP_ERR_NOMEM; }
-    if (lp_out && B > 0 && n > 0 && (int64_t)B * n > lp_cap) {
-        if (lp_tok) { (void)hipDeviceSynchronize(); (void)hipFree(lp_tok); }
-        lp_cap = std::max<int64_t>((int64_t)B * n, 1024);
-        if (hipMalloc((void**)&lp_tok, (size_t)lp_cap * 4) != hipSuccess) { lp_tok = nullptr; lp_cap = 0; return GITCAP_ERR_NOMEM; }
-    }
-    const hipStream_t s = (hipStream_t)stream;
-    ((volatile int32_t*)host)[0] = -1;
-    ((volatile int32_t*)host)[1] = -1;
-    const hipError_t e = launch_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host, s, amax_sum,
-                                             lp_out ? lp_tok : nullptr, lp_out, ld_lp);
-    if (e != hipSuccess) return dbg_rc(e);
-    if (hipStreamSynchronize(s) != hipSuccess) return GITCAP_ERR_HIP;
-    host_out[0] = ((volatile int32_t*)host)[0];
-    host_out[1] = ((volatile int32_t*)host)[1];
-    return 0;
-}
-int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
-                            uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, void* stream) {
-    return dbg_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host_out, nullptr, nullptr, 0, stream);
-}
-int gitcap_dbg_draft_accept_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int32_t* tok,
-                               uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out, const float* amax_sum, float* lp_out,
-                               int ld_lp, void* stream) {
-    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
-    return dbg_draft_accept(amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket, sep_cnt, sep_id, host_out, amax_sum, lp_out, ld_lp, stream);
-}
-
-static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) {
-    if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len)
-        return false;
-    bb = BeamBuffers{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
-    return true;
-}
-
-// (gitcap_dbg_beam_buffers_nbest is gitcap_dbg_beam_buffers with the slot count n behind it)
-static bool dbg_beam_buffers_nbest(const gitcap_dbg_beam_buffers_nbest* b, BeamBuffers& bb) {
-    if (!b || b->n < 1 || b->n > 16) return false;
-    const gitcap_dbg_beam_buffers first{b->ids0, b->ids1, b->words, b->hyp_ids, b->beam_scores, b->hyp_score, b->src_rows, b->done, b->hyp_len};
-    return dbg_beam_buffers(&first, bb);
-}
-
-int gitcap_dbg_beam_init(const gitcap_dbg_beam_buffers* b, int B, int beams, int max_len, int cls, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers(b, bb) || B <= 0 || beams <= 0 || beams > 16 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_init(bb, B, beams, 1, max_len, cls, (hipStream_t)stream));
-}
-
-int gitcap_dbg_beam_step(const gitcap_dbg_beam_buffers* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams, int K,
-                         int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || K <= 0 || V <= 0 || cur_len < 1 ||
-        cur_len >= max_len || (cur != 0 && cur != 1))
-        return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_step(bb, 1, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur, (hipStream_t)stream));
-}
-
-int gitcap_dbg_beam_finish(const gitcap_dbg_beam_buffers* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_finish(bb, 1, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
-}
-
-int gitcap_dbg_beam_step_nbest(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
-                               int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
-        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
-        return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
-                                   (hipStream_t)stream));
-}
-
-int gitcap_dbg_beam_step_sampled(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
-                                 int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
-        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1))
-        return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
-                                   (hipStream_t)stream, true));
-}
-
-// the forced forms (gitcap_attach_prompt): sampled = 0 and n = 1 runs beam_step_kernel, n > 1 the n-slot kernel, sampled != 0 its form
-// for draws; prompt_ids [B][ld_prompt], lengths [B], prompt_max_len < max_len
-int gitcap_dbg_beam_step_forced(const gitcap_dbg_beam_buffers_nbest* b, const float* cand_scores, const int32_t* cand_idx, int B, int beams,
-                                int K, int V, int cur_len, int max_len, int eos, float length_penalty, int cur, int sampled,
-                                const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int prompt_max_len, void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers_nbest(b, bb) || !cand_scores || !cand_idx || B <= 0 || beams <= 0 || beams > 16 || K <= 0 ||
-        K > 16 || V <= 0 || cur_len < 1 || cur_len >= max_len || (cur != 0 && cur != 1) || !prompt_ids || !lengths ||
-        prompt_max_len < 1 || prompt_max_len >= max_len || ld_prompt < prompt_max_len)
-        return GITCAP_ERR_ARG;
-    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, prompt_max_len};
-    return dbg_rc(launch_beam_step(bb, b->n, cand_scores, cand_idx, B, beams, K, V, cur_len, max_len, eos, length_penalty, cur,
-                                   (hipStream_t)stream, sampled != 0, &pr));
-}
-
-int gitcap_dbg_beam_finish_nbest(const gitcap_dbg_beam_buffers_nbest* b, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
-                                 void* stream) {
-    BeamBuffers bb;
-    if (!dbg_beam_buffers_nbest(b, bb) || !decoded || !logprobs || B <= 0 || max_len < 2) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_beam_finish(bb, b->n, B, max_len, eos, decoded, logprobs, nullptr, nullptr, (hipStream_t)stream));
-}
-
-// ---- text-row kernels of the token loop (tests/test_text_rows_gpu.py): each hook is ONE launcher on caller-owned device buffers,
-// no allocation, no handle; what a launcher does not check itself and a wrong value of which would index outside a buffer is
-// checked here
-int gitcap_dbg_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, void* stream) {
-    if (!src || !dst || K <= 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_pack_frags(src, dst, rows16, K, elem_bytes, (hipStream_t)stream));
-}
-
-int gitcap_dbg_kv_quant_v(const void* kv, void* v8, float* vs, int rows, int D, int H, int64_t pitch, void* stream) {
-    if (!kv || !v8 || !vs || H <= 0 || ((uintptr_t)kv & 15) || ((uintptr_t)v8 & 7)) return GITCAP_ERR_ARG;
-    return dbg_rc(launch_kv_quant_v((const bf16_t*)kv, (unsigned char*)v8, vs, rows, D, H, pitch, (hipStream_t)stream));
-}
-
-int gitcap_dbg_skinny(const gitcap_dbg_skinny_args* g, int epi, void* stream) {
-    if (!g || !g->W || !g->out || g->M <= 0 || g->N <= 0 || !skinny_full_ok(g->K) || g->ldo < g->N || g->T <= 0 || g->row_stride < 0 ||
-        g->row_off < 0 || ((uintptr_t)g->W & 15) || ((uintptr_t)g->Wpk & 15) || ((uintptr_t)g->out & 7) || (g->ldo & 3))
-        return GITCAP_ERR_ARG;
-    if (epi != SK_BIAS_BF16 && epi != SK_BIAS_GELU_BF16 && epi != SK_BIAS_RELU_BF16) return GITCAP_ERR_ARG;   // the head: gitcap_dbg_vocab_head
-    if (g->wscale && g->K != 128 && g->K != 768) return GITCAP_ERR_ARG;
-    SkinnyArgs a{};
-    a.X = (const bf16_t*)g->X; a.ldx = g->ldx; a.W = g->W; a.Wpk = g->Wpk; a.wscale = g->wscale; a.bias = g->bias;
-    a.M = g->M; a.N = g->N; a.K = g->K; a.out = g->out; a.ldo = g->ldo; a.T = g->T; a.row_stride = g->row_stride; a.row_off = g->row_off;
-    if (g->ln_kind) {
-        if ((g->ln_kind != 1 && g->ln_kind != 2) || !skinny_row_prologue_ok(g->M, g->K, g->wscale != nullptr) || epi == SK_BIAS_GELU_BF16 ||
-            !g->ln_g || !g->ln_b || !g->ln_xf)
-            return GITCAP_ERR_ARG;
-        if (g->ln_kind == 1 && (!g->ln_slabs || g->ln_nslab <= 0 || !g->ln_bias || !g->ln_resid || g->ln_resid == g->ln_xf)) return GITCAP_ERR_ARG;
-        if (g->ln_kind == 2 && (!g->ln_ids || g->ln_T <= 0 || g->ln_ld_ids < g->ln_T || g->ln_t0 < 0 || g->ln_vocab <= 0 || !g->ln_word || !g->ln_pos))
-            return GITCAP_ERR_ARG;
-        a.ln.kind = g->ln_kind; a.ln.slabs = g->ln_slabs; a.ln.nslab = g->ln_nslab; a.ln.bias = g->ln_bias; a.ln.resid = g->ln_resid;
-        a.ln.ids = g->ln_ids; a.ln.ld_ids = g->ln_ld_ids; a.ln.T = g->ln_T; a.ln.t0 = g->ln_t0; a.ln.vocab = g->ln_vocab;
-        a.ln.word = g->ln_word; a.ln.pos = g->ln_pos; a.ln.g = g->ln_g; a.ln.b = g->ln_b; a.ln.eps = g->ln_eps; a.ln.xf = g->ln_xf;
-    } else if (!g->X || g->ldx < g->K || (g->ldx & 7) || ((uintptr_t)g->X & 15)) {
-        return GITCAP_ERR_ARG;
-    }
-    return dbg_rc(launch_skinny(a, epi, (hipStream_t)stream));
-}
-
-int gitcap_dbg_skinny_splitk(const void* X, int ldx, const void* W, const void* Wpk, const float* wscale, int M, int N, int K, int ksplit,
-                             float* slabs, int ldo, void* stream) {
-    if (!X || !W || !slabs || M <= 0 || N <= 0 || K <= 0 || ksplit < 0 || ldx < K || (ldx & 7) || ldo < N || (ldo & 3) ||
-        ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || ((uintptr_t)Wpk & 15) || ((uintptr_t)slabs & 15))
-        return GITCAP_ERR_ARG;
-    SkinnyArgs a{};
-    a.X = (const bf16_t*)X; a.ldx = ldx; a.W = W; a.Wpk = Wpk; a.wscale = wscale; a.M = M; a.N = N; a.K = K;
-    a.out = slabs; a.ldo = ldo; a.T = M; a.row_stride = M; a.ksplit = ksplit;
-    return dbg_rc(launch_skinny_splitk(a, (hipStream_t)stream));
-}
-
-int gitcap_dbg_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid, const float* gamma, const float* beta,
-                         float eps, int M, int D, float* xf, void* xb, void* stream) {
-    if (!slabs || !bias || !resid || !gamma || !beta || !xf || !xb || M <= 0 || D <= 0 || (D & 3) || nslab <= 0) return GITCAP_ERR_ARG;
-    if (((uintptr_t)slabs & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)resid & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15) ||
-        ((uintptr_t)xf & 15) || ((uintptr_t)xb & 7))
-        return GITCAP_ERR_ARG;
-    return dbg_rc(launch_ln_reduce(slabs, nslab, bias, resid, gamma, beta, eps, M, D, xf, (bf16_t*)xb, (hipStream_t)stream));
-}
-
-int gitcap_dbg_ffn_txt(const void* X, int ldx, const void* W1pk, const void* W2pk, const float* w1scale, const float* w2scale,
-                       const float* b1, int M, int D, int F, float* slabs, void* stream) {
-    if (!X || !W1pk || !W2pk || !b1 || !slabs || M <= 0 || !ffn_txt_ok(D, F) || (w1scale != nullptr) != (w2scale != nullptr) || ldx < D ||
-        (ldx & 7) || ((uintptr_t)X & 15) || ((uintptr_t)W1pk & 15) || ((uintptr_t)W2pk & 15) || ((uintptr_t)slabs & 15))
-        return GITCAP_ERR_ARG;
-    FfnTxtArgs a{};
-    a.X = (const bf16_t*)X; a.ldx = ldx; a.W1pk = W1pk; a.W2pk = W2pk; a.w1scale = w1scale; a.w2scale = w2scale; a.b1 = b1;
-    a.M = M; a.D = D; a.F = F; a.slabs = slabs;
-    return dbg_rc(launch_ffn_txt(a, (hipStream_t)stream));
-}
-
-// the tables of a variable-length hook (device int32 [n]) on the host: the stream is drained first (the caller may have
-// filled them on it)
-static bool dbg_read_tables(const int32_t* off, const int32_t* len, int n, hipStream_t s, std::vector<int32_t>& ho, std::vector<int32_t>& hl) {
-    if (!off || !len || n <= 0 || ((uintptr_t)off & 3) || ((uintptr_t)len & 3)) return false;
-    ho.resize(n); hl.resize(n);
-    return hipStreamSynchronize(s) == hipSuccess && hipMemcpy(ho.data(), off, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(hl.data(), len, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
-}
-
-int gitcap_dbg_attn_full_varlen(const void* qkv, void* ctx, int G, const int32_t* off, const int32_t* len, int H, void* stream) {
-    if (!qkv || !ctx || G <= 0 || H <= 0) return GITCAP_ERR_ARG;
-    std::vector<int32_t> ho, hl;
-    if (!dbg_read_tables(off, len, G, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
-    int mx = 0;
-    for (int g = 0; g < G; ++g) {
-        if (ho[g] < 0 || hl[g] < 1) return GITCAP_ERR_ARG;
-        mx = std::max(mx, hl[g]);
-    }
-    return launch_attn_full_varlen((const bf16_t*)qkv, (bf16_t*)ctx, G, off, len, mx, H, (hipStream_t)stream) == hipSuccess ? 0 : GITCAP_ERR_HIP;
-}
-
-static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream);
-int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* g, void* stream) { return dbg_txt_block(g, nullptr, nullptr, stream); }
-// variable-length form: off / len device int32 [clips], clips = ceil(rows / beams); S_img is not read
-int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
-    if (!g || g->rows <= 0 || g->beams <= 0) return GITCAP_ERR_ARG;
-    std::vector<int32_t> ho, hl;
-    const int clips = (g->rows - 1) / g->beams + 1;
-    if (!dbg_read_tables(off, len, clips, (hipStream_t)stream, ho, hl)) return GITCAP_ERR_ARG;
-    for (int c = 0; c < clips; ++c)
-        if (ho[c] < 0 || hl[c] < 0 || (g->v8_img && (int64_t)ho[c] + hl[c] > g->v8_pitch)) return GITCAP_ERR_ARG;
-    return dbg_txt_block(g, off, len, stream);
-}
-
-static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off, const int32_t* len, void* stream) {
-    if (!g || !g->kv_img || !g->kv_txt || !g->aow || !g->aob || !g->g1 || !g->b1 || !g->xin || !g->part || !g->cnt || !g->xs || !g->xsb)
-        return GITCAP_ERR_ARG;
-    if (g->rows <= 0 || g->beams <= 0 || g->T <= 0 || g->t0 < 0 || g->t0 + g->T > g->Tmax || g->S_img < 0 || !txt_block_ok(g->D) ||
-        g->H * 64 != g->D || (g->v8_img != nullptr) != (g->vs_img != nullptr) ||
-        (g->v8_img && !off && g->v8_pitch < (int64_t)((g->rows - 1) / g->beams + 1) * g->S_img))
-        return GITCAP_ERR_ARG;
-    // the widest access txt_block_kernel makes on each buffer: 16-byte rows of q / k / v and of the output dense (8 bytes of e4m3 codes),
-    // 8 bytes of V codes; everything else -- scales, bias, gamma / beta, residual, part, tickets, xs -- one float or word at a time, xsb
-    // one bf16 at a time
-    if (((uintptr_t)g->kv_img & 15) || ((uintptr_t)g->kv_txt & 15) || ((uintptr_t)g->aow & 15) || ((uintptr_t)g->aowpk & 15) ||
-        ((uintptr_t)g->v8_img & 7) || ((uintptr_t)g->vs_img & 3) || ((uintptr_t)g->aoscale & 3) || ((uintptr_t)g->aob & 3) ||
-        ((uintptr_t)g->g1 & 3) || ((uintptr_t)g->b1 & 3) || ((uintptr_t)g->xin & 3) || ((uintptr_t)g->part & 3) || ((uintptr_t)g->cnt & 3) ||
-        ((uintptr_t)g->xs & 3) || ((uintptr_t)g->xsb & 1))
-        return GITCAP_ERR_ARG;
-    TxtBlockArgs a{};
-    a.kv_img = (const bf16_t*)g->kv_img; a.kv_txt = (const bf16_t*)g->kv_txt;
-    a.rows = g->rows; a.beams = g->beams; a.t0 = g->t0; a.T = g->T; a.Tmax = g->Tmax; a.S_img = g->S_img; a.H = g->H; a.D = g->D;
-    a.aow = g->aow; a.aowpk = g->aoscale ? nullptr : g->aowpk; a.aoscale = g->aoscale; a.aob = g->aob; a.g1 = g->g1; a.b1 = g->b1;
-    a.xin = g->xin; a.eps = g->eps; a.part = g->part; a.cnt = g->cnt; a.xs = g->xs; a.xsb = (bf16_t*)g->xsb;
-    a.v8_img = (const unsigned char*)g->v8_img; a.vs_img = g->vs_img; a.v8_pitch = g->v8_pitch; a.nt_kv = g->nt_kv ? 1 : 0;
-    a.off = off; a.len = len;
-    return dbg_rc(launch_txt_block(a, (hipStream_t)stream));
 }
 
 // Threads a host-side copy may use: the affinity mask capped by the cgroup CPU quota (a 1-GPU box gives the job a share of the

@@ -167,6 +167,18 @@ inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int
     const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
     return launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
 }
+// One pass of a handle's decoder stack over text rows, and what its vocabulary head produces (host only; the request of both
+// handles' text_forward, gitcap.hip and student.hip -- the teacher's TextReq adds what only its stack takes).
+struct RowsReq {
+    // which rows and positions: ids [rows][ld_ids], query positions t0 .. t0 + T - 1 (K/V of earlier positions come from the cache)
+    const int64_t* ids = nullptr; int ld_ids = 0, rows = 0, t0 = 0, T = 0;
+    // what the head produces; none of logits_out / argmax_out / score: the stack's rows only, no head
+    float* logits_out = nullptr;                    // nullable: fp32 logits
+    int64_t* argmax_out = nullptr; int ld_argmax = 0;   // nullable: the last position's arg-max of every row (launch_argmax_final's out)
+    int32_t* sep_cnt = nullptr; int step = 0;       // launch_argmax_final's
+    float* lp_out = nullptr; int ld_lp = 0;         // nullable, needs argmax_out: the token's log-probability
+    const ScoreReq* score = nullptr;                // nullable: all positions through launch_score instead
+};
 // ---- teacher-student divergence (gitcap_distill): both vocabulary heads over the same tiles, then one merge -------------------
 // launch_head_dual (skinny.hip: skinny_head_dual_kernel): the teacher's rows Xt [M][ldxt] against wt (bf16, or e4m3 codes with
 // wscale) and the student's rows Xs [M][ldxs] against ws (bf16), (wt.D, ws.D) one of (768, 576), (1024, 576), (128, 64), equal V.
@@ -224,31 +236,49 @@ struct FfnTxtArgs {
 };
 bool ffn_txt_ok(int D, int F);
 hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
-// out[r*ld_out] = index of the max over the per-tile partials of row r*row_stride + row_off; lowest index wins ties (torch.argmax on
-// CPU), 0 when the winner is an empty tile's index 0x7fffffff (no logit above -inf in the row).  If sep_cnt != nullptr: sep_cnt[step] += 1 for every row whose token is sep_id (zero it per call).
+// ---- token selection (rowops.hip): host-only records, passed by const&; the kernels receive their scalars and pointers ---------
 // emb (nullable; greedy loop, one position per row): the kernel goes on to embed the token it just chose at text position
 // emb->position -- word + position embedding -> LayerNorm -> xf / xb row r (rowln.h: the code of launch_embed_text) -- so
 // the next token step starts at its q|k|v projection.
 struct NextEmbed { const float *word, *pos, *gamma, *beta; float eps; int D, vocab, position; float* xf; bf16_t* xb; };
-// prompt (PromptArgs, host_logic.h; nullable) + prompt_pos = the position the launch writes: a row with prompt_pos < lengths[r] takes ids[r][prompt_pos]
-// instead of its arg-max (out, the embedded next row), leaves sep_cnt alone and gets lp 0.0f; with prompt_pos >= max_len the launch
-// is the one without a prompt.
-hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride,
-                               int row_off, int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s,
-                               const NextEmbed* emb = nullptr, const float* amax_sum = nullptr, float* lp_out = nullptr, int ld_lp = 0,
-                               const PromptArgs* prompt = nullptr, int prompt_pos = 0);
-// amax_sum + lp_out (both or neither; SkinnyArgs::amax_sum of the same head launch): lp_out[r*ld_lp] = log_softmax(logits)[token]
-// of row r, natural log, -inf for a row with no logit above -inf.  Fixed summation order: bitwise independent of `rows`.
+struct ArgmaxArgs {
+    // the head's per-tile partials [head rows][ntiles] (SkinnyArgs::amax_val / amax_idx / amax_sum of the same head launch)
+    const float* val; const int* idx;
+    const float* sum;             // nullable, with lp_out (both or neither)
+    int ntiles;
+    // out[r*ld_out] = index of the max over the per-tile partials of row r*row_stride + row_off, r < rows; lowest index wins ties
+    // (torch.argmax on CPU), 0 when the winner is an empty tile's index 0x7fffffff (no logit above -inf in the row)
+    int rows, row_stride, row_off;
+    int64_t* out; int ld_out;
+    int32_t* sep_cnt; int step, sep_id;   // sep_cnt != nullptr: sep_cnt[step] += 1 for every row whose token is sep_id (zero it per call)
+    // lp_out[r*ld_lp] = log_softmax(logits)[token] of row r, natural log, -inf for a row with no logit above -inf.  Fixed summation
+    // order: bitwise independent of `rows`.
+    float* lp_out; int ld_lp;
+    const NextEmbed* emb;         // nullable (above)
+    // prompt (PromptArgs, host_logic.h; nullable) + prompt_pos = the position the launch writes: a row with prompt_pos < lengths[r]
+    // takes ids[r][prompt_pos] instead of its arg-max (out, the embedded next row), leaves sep_cnt alone and gets lp 0.0f; with
+    // prompt_pos >= max_len the launch is the one without a prompt.
+    const PromptArgs* prompt; int prompt_pos;
+};
+hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s);
 // Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
 // reduces them under launch_argmax_final's tie rule and compares with the draft tokens staged in ids [B][ld] (columns 1..n; -1 =
 // not a word).  a = the leading positions at which every row's token equals its draft token; ids columns 1..min(a + 1, n) and
-// sep_cnt[0 .. min(a + 1, n) - 1] become what the token loop would have written; host (page-locked int32[2]) = {a, all rows
-// emitted SEP in one of those steps}.  tok: int[B * n] scratch; ticket: one word, zero between launches.
-hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
-                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s,
-                               const float* amax_sum = nullptr, int* lp_tok = nullptr, float* lp_out = nullptr, int ld_lp = 0);
-// amax_sum + lp_out (both or neither; lp_tok: int[B * n] scratch, ld_lp >= n): lp_out[r*ld_lp + j] = the log-probability of the
-// token at position j (launch_argmax_final's value of that row) for the covered positions; columns behind them are not written.
+// sep_cnt[0 .. min(a + 1, n) - 1] become what the token loop would have written; host = {a, all rows emitted SEP in one of those steps}.
+struct DraftAcceptArgs {
+    const float* val; const int* idx;
+    const float* sum;             // nullable, with lp_out (both or neither)
+    int ntiles, B, n;
+    int64_t* ids; int ld;
+    int* tok;                     // int[B * n] scratch
+    unsigned* ticket;             // one word, zero between launches
+    int32_t* sep_cnt; int sep_id;
+    int32_t* host;                // page-locked int32[2]
+    // lp_out[r*ld_lp + j] = the log-probability of the token at position j (launch_argmax_final's value of that row) for the covered
+    // positions; columns behind them are not written.  lp_tok: int[B * n] scratch, ld_lp >= n.
+    int* lp_tok; float* lp_out; int ld_lp;
+};
+hipError_t launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s);
 
 // ---- attention ---------------------------------------------------------------------------
 // Full (unmasked) self-attention over groups of S rows: qkv [G*S][3*W] bf16 (q | k | v, head h
@@ -363,18 +393,35 @@ hipError_t launch_fill_i64(int64_t* p, int ld, int rows, int64_t v, hipStream_t 
 hipError_t launch_fill_prompt(int64_t* p, int ld, int rows, const PromptArgs& prompt, hipStream_t s);
 hipError_t launch_gather_txt_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_rows, int rows,
                                   int t_len, int Tmax, int width, int layers, size_t layer_stride, hipStream_t s);
+// The candidates of one search step, what launch_beam_topk (the K best) and launch_sample_rows (draws) have in common: B * beams rows
+// of logits [.][ld] (V columns) ranked under log_softmax + beam_scores; candidate slots out_scores / out_idx [B][K] (K = beams * pn
+// for draws).
+struct CandArgs {
+    const float* logits; int ld;
+    const float* beam_scores;
+    // rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
+    // prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
+    // often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
+    const int64_t* prefix_ids; int ld_ids, cur_len; float rp;
+    int B, beams, V;
+    float* out_scores; int* out_idx;
+    // bn (nullable): row b * beams + j of the mask bans columns of that beam row before the penalty, the chunk statistics and the
+    // chunk's top K (the BAN forms of the chunk kernel, combinable with the penalty): the log-softmax is that of the banned row;
+    // draws: banned columns are -inf before the penalty, the temperature and the filter -- the BAN form of the kernel.
+    const HeadBan* bn;
+};
 // top-K over (beam, vocab) of log_softmax(logits) + beam_scores per batch element: sorted descending, ties by smaller flat index
 // j*V + v.  Logits of -inf are no candidates; where a clip has fewer than K candidates the remaining slots hold the sentinel
 // (score -inf, index 0x7fffffff) -- launch_beam_step divides the index by V and must never be handed one.
 size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scratch launch_beam_topk needs (V <= 131072)
-// rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
-// prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
-// often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
-// bn (nullable): row b * beams + j of the mask bans columns of that beam row before the penalty, the chunk statistics and the
-// chunk's top K (the BAN forms of the chunk kernel, combinable with the penalty): the log-softmax is that of the banned row.
-hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
-                            const HeadBan* bn = nullptr);
+hipError_t launch_beam_topk(const CandArgs& c, int K, void* scratch, hipStream_t s);
+// the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
+// (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
+// candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (rowops.hip).
+// opt = the call's SampleOpt (host_logic.h; `on` is not read).
+// kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
+struct SampleStats { int* kept_out; float* logz_out; };
+hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& opt, const SampleStats& st, hipStream_t s);
 // uint8 HWC BGR frames [nf][H][W][3] -> CLIP-normalised fp32 NCHW [nf][3][crop][crop] (bicubic resize + centre crop)
 hipError_t launch_preprocess(const unsigned char* in, float* out, int nf, int H, int W, int crop, hipStream_t s);
 // the same transform fused with the patch gather: -> bf16 patch rows [nf*G*G][Kp] (layout of launch_im2col)
@@ -392,21 +439,20 @@ struct BeamBuffers {
 // slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes all B * n).  step: n = 1 runs beam_step_kernel, n > 1 the n-slot kernel.
 // finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_*: rank 0 again as [B][max_len] / [B]; all nullable.
 hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s);
-// sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates are
-// walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
-hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled = false,
-                            const PromptArgs* prompt = nullptr);
-// prompt (nullable; rows = clips): a clip with cur_len < lengths[b] is forced -- every beam keeps its prefix and appends
-// ids[b][cur_len], src_rows is the identity, beam_scores / done / the hypothesis slots are untouched, the candidates are not read;
-// with cur_len >= max_len (the prompt's) the launch is the one without a prompt.
-// the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
-// (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
-// candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (rowops.hip).
-// kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
-hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                              float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
-                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s, const HeadBan* bn = nullptr);
-// (bn, nullable: banned columns are -inf before the penalty, the temperature and the filter -- the BAN form of the kernel)
-hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
-                              int64_t* first_decoded, float* first_logprobs, hipStream_t s);
+struct BeamStepArgs {
+    int n;                                      // hypothesis slots per clip
+    const float* cand_scores; const int* cand_idx;   // [B][K]: launch_beam_topk's or launch_sample_rows'
+    int B, beams, K, V;
+    int cur_len, max_len, eos; float length_penalty;
+    int cur;                                    // which of ids0 / ids1 holds the current prefixes
+    // sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates
+    // are walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
+    bool sampled;
+    // prompt (nullable; rows = clips): a clip with cur_len < lengths[b] is forced -- every beam keeps its prefix and appends
+    // ids[b][cur_len], src_rows is the identity, beam_scores / done / the hypothesis slots are untouched, the candidates are not
+    // read; with cur_len >= max_len (the prompt's) the launch is the one without a prompt.
+    const PromptArgs* prompt;
+};
+hipError_t launch_beam_step(const BeamBuffers& bb, const BeamStepArgs& a, hipStream_t s);
+struct BeamFinishOut { int64_t* decoded; float* logprobs; int64_t* first_decoded; float* first_logprobs; };
+hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, const BeamFinishOut& o, hipStream_t s);

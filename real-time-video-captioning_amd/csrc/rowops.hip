@@ -1473,56 +1473,35 @@ hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int 
     return hipGetLastError();
 }
 
-hipError_t launch_argmax_final(const float* amax_val, const int* amax_idx, int ntiles, int rows, int row_stride, int row_off,
-                               int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, hipStream_t s, const NextEmbed* emb,
-                               const float* amax_sum, float* lp_out, int ld_lp, const PromptArgs* prompt, int prompt_pos) {
-    const NextEmbed e = emb ? *emb : NextEmbed{};
-    const int nv = emb ? (e.D + 255) / 256 : 0;
-    if (emb && (nv < 1 || nv > 4 || (e.D & 3) || !e.word || !e.pos || !e.gamma || !e.beta || !e.xf || !e.xb)) return hipErrorInvalidValue;
-    if ((amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1)) return hipErrorInvalidValue;
-    if (prompt) {
-        if (!prompt->ids || !prompt->lengths || prompt->max_len < 1 || prompt->ld < prompt->max_len || prompt_pos < 0) return hipErrorInvalidValue;
-        if (prompt_pos < prompt->max_len) {           // (behind the longest prompt the plain forms below choose the same tokens)
-            const PromptSel<true> pr{prompt->ids, prompt->lengths, prompt->ld, prompt->max_len, prompt_pos};
-#define AF_LAUNCH_F(NV, LP) hipLaunchKernelGGL((argmax_final_kernel<NV, LP, true>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, \
-                                               row_stride, row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp, pr)
-#define AF_SWITCH_F(LP)                                                                                                            \
-    switch (nv) {                                                                                                                  \
-        case 0: AF_LAUNCH_F(0, LP); break;                                                                                         \
-        case 1: AF_LAUNCH_F(1, LP); break;                                                                                         \
-        case 2: AF_LAUNCH_F(2, LP); break;                                                                                         \
-        case 3: AF_LAUNCH_F(3, LP); break;                                                                                         \
-        default: AF_LAUNCH_F(4, LP); break;                                                                                        \
-    }
-            if (lp_out) { AF_SWITCH_F(true) } else { AF_SWITCH_F(false) }
-#undef AF_SWITCH_F
-#undef AF_LAUNCH_F
-            return hipGetLastError();
-        }
-    }
-    if (lp_out) {
-#define AF_LAUNCH_LP(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, true>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, \
-                                            row_off, out, ld_out, sep_cnt, step, sep_id, e, amax_sum, lp_out, ld_lp, PromptSel<false>{})
-        switch (nv) {
-            case 0: AF_LAUNCH_LP(0); break;
-            case 1: AF_LAUNCH_LP(1); break;
-            case 2: AF_LAUNCH_LP(2); break;
-            case 3: AF_LAUNCH_LP(3); break;
-            default: AF_LAUNCH_LP(4); break;
-        }
-#undef AF_LAUNCH_LP
-        return hipGetLastError();
-    }
-#define AF_LAUNCH(NV) hipLaunchKernelGGL((argmax_final_kernel<NV, false>), dim3(rows), dim3(256), 0, s, amax_val, amax_idx, ntiles, row_stride, row_off, \
-                                         out, ld_out, sep_cnt, step, sep_id, e, (const float*)nullptr, (float*)nullptr, 0, PromptSel<false>{})
+// one launch form of argmax_final_kernel: without LP the kernel is handed null sum / lp, without FORCED the empty PromptSel
+template <int NV, bool LP, bool FORCED>
+static void argmax_final_launch(const ArgmaxArgs& a, const NextEmbed& e, const PromptSel<FORCED>& pr, hipStream_t s) {
+    hipLaunchKernelGGL((argmax_final_kernel<NV, LP, FORCED>), dim3(a.rows), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.row_stride, a.row_off,
+                       a.out, a.ld_out, a.sep_cnt, a.step, a.sep_id, e, LP ? a.sum : nullptr, LP ? a.lp_out : nullptr, LP ? a.ld_lp : 0, pr);
+}
+template <bool FORCED>
+static void argmax_final_dispatch(const ArgmaxArgs& a, int nv, const NextEmbed& e, const PromptSel<FORCED>& pr, hipStream_t s) {
+    const bool lp = a.lp_out != nullptr;
     switch (nv) {
-        case 0: AF_LAUNCH(0); break;
-        case 1: AF_LAUNCH(1); break;
-        case 2: AF_LAUNCH(2); break;
-        case 3: AF_LAUNCH(3); break;
-        default: AF_LAUNCH(4); break;
+        case 0: lp ? argmax_final_launch<0, true>(a, e, pr, s) : argmax_final_launch<0, false>(a, e, pr, s); break;
+        case 1: lp ? argmax_final_launch<1, true>(a, e, pr, s) : argmax_final_launch<1, false>(a, e, pr, s); break;
+        case 2: lp ? argmax_final_launch<2, true>(a, e, pr, s) : argmax_final_launch<2, false>(a, e, pr, s); break;
+        case 3: lp ? argmax_final_launch<3, true>(a, e, pr, s) : argmax_final_launch<3, false>(a, e, pr, s); break;
+        default: lp ? argmax_final_launch<4, true>(a, e, pr, s) : argmax_final_launch<4, false>(a, e, pr, s); break;
     }
-#undef AF_LAUNCH
+}
+
+hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s) {
+    const NextEmbed e = a.emb ? *a.emb : NextEmbed{};
+    const int nv = a.emb ? (e.D + 255) / 256 : 0;
+    if (a.emb && (nv < 1 || nv > 4 || (e.D & 3) || !e.word || !e.pos || !e.gamma || !e.beta || !e.xf || !e.xb)) return hipErrorInvalidValue;
+    if ((a.sum == nullptr) != (a.lp_out == nullptr) || (a.lp_out && a.ld_lp < 1)) return hipErrorInvalidValue;
+    const PromptArgs* p = a.prompt;
+    if (p && (!p->ids || !p->lengths || p->max_len < 1 || p->ld < p->max_len || a.prompt_pos < 0)) return hipErrorInvalidValue;
+    if (p && a.prompt_pos < p->max_len)             // (behind the longest prompt the plain forms choose the same tokens)
+        argmax_final_dispatch(a, nv, e, PromptSel<true>{p->ids, p->lengths, p->ld, p->max_len, a.prompt_pos}, s);
+    else
+        argmax_final_dispatch(a, nv, e, PromptSel<false>{}, s);
     return hipGetLastError();
 }
 
@@ -1555,18 +1534,17 @@ hipError_t launch_distill_final(const DistillPartials& p, int ntiles, const floa
     return hipGetLastError();
 }
 
-hipError_t launch_draft_accept(const float* amax_val, const int* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld, int* tok,
-                               unsigned* ticket, int32_t* sep_cnt, int sep_id, int32_t* host, hipStream_t s, const float* amax_sum,
-                               int* lp_tok, float* lp_out, int ld_lp) {
-    if (B <= 0 || n < 1 || n > 63 || ld < n + 1 || ntiles <= 0 || !amax_val || !amax_idx || !ids || !tok || !ticket || !sep_cnt || !host)
+hipError_t launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.n < 1 || a.n > 63 || a.ld < a.n + 1 || a.ntiles <= 0 || !a.val || !a.idx || !a.ids || !a.tok || !a.ticket || !a.sep_cnt ||
+        !a.host)
         return hipErrorInvalidValue;
-    if ((amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && (!lp_tok || ld_lp < n))) return hipErrorInvalidValue;
-    if (lp_out)
-        hipLaunchKernelGGL(draft_accept_kernel<true>, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket,
-                           sep_cnt, sep_id, host, amax_sum, lp_tok, lp_out, ld_lp);
+    if ((a.sum == nullptr) != (a.lp_out == nullptr) || (a.lp_out && (!a.lp_tok || a.ld_lp < a.n))) return hipErrorInvalidValue;
+    if (a.lp_out)
+        hipLaunchKernelGGL(draft_accept_kernel<true>, dim3(a.B * a.n), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.B, a.n, a.ids, a.ld, a.tok,
+                           a.ticket, a.sep_cnt, a.sep_id, a.host, a.sum, a.lp_tok, a.lp_out, a.ld_lp);
     else
-        hipLaunchKernelGGL(draft_accept_kernel<false>, dim3(B * n), dim3(256), 0, s, amax_val, amax_idx, ntiles, B, n, ids, ld, tok, ticket,
-                           sep_cnt, sep_id, host, (const float*)nullptr, (int*)nullptr, (float*)nullptr, 0);
+        hipLaunchKernelGGL(draft_accept_kernel<false>, dim3(a.B * a.n), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.B, a.n, a.ids, a.ld, a.tok,
+                           a.ticket, a.sep_cnt, a.sep_id, a.host, (const float*)nullptr, (int*)nullptr, (float*)nullptr, 0);
     return hipGetLastError();
 }
 
@@ -1576,60 +1554,58 @@ size_t beam_topk_scratch_bytes(int B, int beams, int V, int K) {
 }
 
 template <int KMAX>
-static void beam_topk_launch(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len, float rp,
-                             int B, int beams, int V, int K, int nch, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
-                             const HeadBan* bn) {
-    const size_t n = (size_t)B * beams * nch;
+static void beam_topk_launch(const CandArgs& c, int K, int nch, void* scratch, hipStream_t s) {
+    const size_t n = (size_t)c.B * c.beams * nch;
     float2* stats = (float2*)scratch;
     float* cval = (float*)(stats + n);
     int* cidx = (int*)(cval + n * K);
-    if (bn && rp != 1.0f)
-        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
-                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp}, BeamBan<true>{bn->mask, bn->ld});
-    else if (bn)
-        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
-                           BeamPenalty<false>{}, BeamBan<true>{bn->mask, bn->ld});
-    else if (rp != 1.0f)
-        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
-                           BeamPenalty<true>{prefix_ids, ld_ids, cur_len, rp}, BeamBan<false>{});
+    const BeamPenalty<true> pen{c.prefix_ids, c.ld_ids, c.cur_len, c.rp};
+    if (c.bn && c.rp != 1.0f)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true, true>), dim3((unsigned)n), dim3(256), 0, s, c.logits, c.ld, c.V, K, nch, stats, cval,
+                           cidx, pen, BeamBan<true>{c.bn->mask, c.bn->ld});
+    else if (c.bn)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false, true>), dim3((unsigned)n), dim3(256), 0, s, c.logits, c.ld, c.V, K, nch, stats, cval,
+                           cidx, BeamPenalty<false>{}, BeamBan<true>{c.bn->mask, c.bn->ld});
+    else if (c.rp != 1.0f)
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, true>), dim3((unsigned)n), dim3(256), 0, s, c.logits, c.ld, c.V, K, nch, stats, cval, cidx,
+                           pen, BeamBan<false>{});
     else
-        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false>), dim3((unsigned)n), dim3(256), 0, s, logits, ld, V, K, nch, stats, cval, cidx,
+        hipLaunchKernelGGL((beam_topk_chunks_kernel<KMAX, false>), dim3((unsigned)n), dim3(256), 0, s, c.logits, c.ld, c.V, K, nch, stats, cval, cidx,
                            BeamPenalty<false>{}, BeamBan<false>{});
-    hipLaunchKernelGGL(beam_topk_merge_kernel<KMAX>, dim3(B), dim3(64), 0, s, stats, cval, cidx, beam_scores, beams, V, K, nch, out_scores, out_idx);
+    hipLaunchKernelGGL(beam_topk_merge_kernel<KMAX>, dim3(c.B), dim3(64), 0, s, stats, cval, cidx, c.beam_scores, c.beams, c.V, K, nch, c.out_scores,
+                       c.out_idx);
 }
 
-hipError_t launch_beam_topk(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                            float rp, int B, int beams, int V, int K, float* out_scores, int* out_idx, void* scratch, hipStream_t s,
-                            const HeadBan* bn) {
-    const int nch = (V + BT_CHUNK - 1) / BT_CHUNK;
-    if (B <= 0 || beams <= 0 || beams > 16 || K <= 0 || K > 16 || K > beams * V || nch > 64 || !scratch) return hipErrorInvalidValue;
-    // rp == 1: the plain kernel, the prefix is neither checked nor read
-    if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
-    if (bn && (!bn->mask || bn->ld < (V + 15) / 16)) return hipErrorInvalidValue;
-    if (K <= 8) beam_topk_launch<8>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s, bn);
-    else beam_topk_launch<16>(logits, ld, beam_scores, prefix_ids, ld_ids, cur_len, rp, B, beams, V, K, nch, out_scores, out_idx, scratch, s, bn);
+// what launch_beam_topk and launch_sample_rows check alike: the penalty's prefix (rp == 1: neither checked nor read) and the ban mask
+static bool cand_args_ok(const CandArgs& c) {
+    if (c.rp != 1.0f && (!c.prefix_ids || c.cur_len < 1 || c.ld_ids < c.cur_len || !(c.rp > 0.f) || !std::isfinite(c.rp))) return false;
+    return !c.bn || (c.bn->mask && c.bn->ld >= (c.V + 15) / 16);
+}
+
+hipError_t launch_beam_topk(const CandArgs& c, int K, void* scratch, hipStream_t s) {
+    const int nch = (c.V + BT_CHUNK - 1) / BT_CHUNK;
+    if (c.B <= 0 || c.beams <= 0 || c.beams > 16 || K <= 0 || K > 16 || K > c.beams * c.V || nch > 64 || !scratch) return hipErrorInvalidValue;
+    if (!cand_args_ok(c)) return hipErrorInvalidValue;
+    if (K <= 8) beam_topk_launch<8>(c, K, nch, scratch, s);
+    else beam_topk_launch<16>(c, K, nch, scratch, s);
     return hipGetLastError();
 }
 
-hipError_t launch_sample_rows(const float* logits, int ld, const float* beam_scores, const int64_t* prefix_ids, int ld_ids, int cur_len,
-                              float rp, int B, int beams, int V, int pn, float temperature, int top_k, float top_p, uint64_t seed,
-                              float* out_scores, int* out_idx, int* kept_out, float* logz_out, hipStream_t s, const HeadBan* bn) {
-    if (B <= 0 || beams <= 0 || beams > 16 || pn <= 0 || beams * pn > 16 || pn > V || V > SR_MAX_V || ld < V || cur_len < 0) return hipErrorInvalidValue;
-    if (!(temperature > 0.f) || !std::isfinite(temperature) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f)) return hipErrorInvalidValue;
-    if (rp != 1.0f && (!prefix_ids || cur_len < 1 || ld_ids < cur_len || !(rp > 0.f) || !std::isfinite(rp))) return hipErrorInvalidValue;
-    if (bn) {
-        if (!bn->mask || bn->ld < (V + 15) / 16) return hipErrorInvalidValue;
-        if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel<true>>(SR_MAX_V * 4); e != hipSuccess) return e;
-        hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids,
-                           ld_ids, cur_len, rp, beams, pn, temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), out_scores,
-                           out_idx, kept_out, logz_out, BeamBan<true>{bn->mask, bn->ld});
-        return hipGetLastError();
-    }
-    if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel<false>>(SR_MAX_V * 4); e != hipSuccess) return e;
-    hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(B * beams), dim3(SR_THREADS), (size_t)V * 4, s, logits, ld, V, beam_scores, prefix_ids, ld_ids,
-                       cur_len, rp, beams, pn, temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), out_scores, out_idx,
-                       kept_out, logz_out, BeamBan<false>{});
+template <bool BAN>
+static hipError_t sample_rows_launch(const CandArgs& c, int pn, const SampleOpt& o, const SampleStats& st, const BeamBan<BAN>& ban, hipStream_t s) {
+    if (const hipError_t e = set_dynamic_lds_once<sample_rows_kernel<BAN>>(SR_MAX_V * 4); e != hipSuccess) return e;
+    hipLaunchKernelGGL(sample_rows_kernel<BAN>, dim3(c.B * c.beams), dim3(SR_THREADS), (size_t)c.V * 4, s, c.logits, c.ld, c.V, c.beam_scores,
+                       c.prefix_ids, c.ld_ids, c.cur_len, c.rp, c.beams, pn, o.temperature, o.top_k, o.top_p, (unsigned)o.seed,
+                       (unsigned)(o.seed >> 32), c.out_scores, c.out_idx, st.kept_out, st.logz_out, ban);
     return hipGetLastError();
+}
+
+hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& o, const SampleStats& st, hipStream_t s) {
+    if (c.B <= 0 || c.beams <= 0 || c.beams > 16 || pn <= 0 || c.beams * pn > 16 || pn > c.V || c.V > SR_MAX_V || c.ld < c.V || c.cur_len < 0)
+        return hipErrorInvalidValue;
+    if (!(o.temperature > 0.f) || !std::isfinite(o.temperature) || o.top_k < 0 || !(o.top_p > 0.f) || !(o.top_p <= 1.f)) return hipErrorInvalidValue;
+    if (!cand_args_ok(c)) return hipErrorInvalidValue;
+    return c.bn ? sample_rows_launch(c, pn, o, st, BeamBan<true>{c.bn->mask, c.bn->ld}, s) : sample_rows_launch(c, pn, o, st, BeamBan<false>{}, s);
 }
 
 hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
@@ -1652,42 +1628,35 @@ hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int 
     return hipGetLastError();
 }
 
-hipError_t launch_beam_step(const BeamBuffers& bb, int n, const float* cand_scores, const int* cand_idx, int B, int beams, int K,
-                            int V, int cur_len, int max_len, int eos, float length_penalty, int cur, hipStream_t s, bool sampled,
-                            const PromptArgs* prompt) {
-    if (beams > 16 || K > 16 || n < 1 || n > 16) return hipErrorInvalidValue;
-    if (prompt && (!prompt->ids || !prompt->lengths || prompt->max_len < 1 || prompt->ld < prompt->max_len || prompt->max_len >= max_len))
-        return hipErrorInvalidValue;
-    if (prompt && cur_len < prompt->max_len) {        // (behind the longest prompt no clip is forced: the plain forms below)
-        const PromptSel<true> pr{prompt->ids, prompt->lengths, prompt->ld, prompt->max_len, cur_len};
-        if (sampled)
-            hipLaunchKernelGGL((beam_step_nbest_kernel<true, true>), dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V,
-                               cur_len, max_len, eos, length_penalty, cur, pr);
-        else if (n == 1)
-            hipLaunchKernelGGL(beam_step_kernel<true>, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len,
-                               max_len, eos, length_penalty, cur, pr);
-        else
-            hipLaunchKernelGGL((beam_step_nbest_kernel<false, true>), dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V,
-                               cur_len, max_len, eos, length_penalty, cur, pr);
-        return hipGetLastError();
-    }
-    if (sampled)
-        hipLaunchKernelGGL(beam_step_nbest_kernel<true>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
-                           max_len, eos, length_penalty, cur, PromptSel<false>{});
-    else if (n == 1)
-        hipLaunchKernelGGL(beam_step_kernel<false>, dim3(B), dim3(64), 0, s, beam_state(bb), cand_scores, cand_idx, beams, K, V, cur_len, max_len, eos,
-                           length_penalty, cur, PromptSel<false>{});
+// the three kernels of a step, with or without a prompt: draws, one hypothesis slot, n slots
+template <bool FORCED>
+static void beam_step_launch(const BeamBuffers& bb, const BeamStepArgs& a, const PromptSel<FORCED>& pr, hipStream_t s) {
+    if (a.sampled)
+        hipLaunchKernelGGL((beam_step_nbest_kernel<true, FORCED>), dim3(a.B), dim3(64), 0, s, beam_state(bb), a.n, a.cand_scores, a.cand_idx, a.beams,
+                           a.K, a.V, a.cur_len, a.max_len, a.eos, a.length_penalty, a.cur, pr);
+    else if (a.n == 1)
+        hipLaunchKernelGGL(beam_step_kernel<FORCED>, dim3(a.B), dim3(64), 0, s, beam_state(bb), a.cand_scores, a.cand_idx, a.beams, a.K, a.V,
+                           a.cur_len, a.max_len, a.eos, a.length_penalty, a.cur, pr);
     else
-        hipLaunchKernelGGL(beam_step_nbest_kernel<false>, dim3(B), dim3(64), 0, s, beam_state(bb), n, cand_scores, cand_idx, beams, K, V, cur_len,
-                           max_len, eos, length_penalty, cur, PromptSel<false>{});
+        hipLaunchKernelGGL((beam_step_nbest_kernel<false, FORCED>), dim3(a.B), dim3(64), 0, s, beam_state(bb), a.n, a.cand_scores, a.cand_idx, a.beams,
+                           a.K, a.V, a.cur_len, a.max_len, a.eos, a.length_penalty, a.cur, pr);
+}
+
+hipError_t launch_beam_step(const BeamBuffers& bb, const BeamStepArgs& a, hipStream_t s) {
+    if (a.beams > 16 || a.K > 16 || a.n < 1 || a.n > 16) return hipErrorInvalidValue;
+    const PromptArgs* p = a.prompt;
+    if (p && (!p->ids || !p->lengths || p->max_len < 1 || p->ld < p->max_len || p->max_len >= a.max_len)) return hipErrorInvalidValue;
+    if (p && a.cur_len < p->max_len)                // (behind the longest prompt no clip is forced: the plain forms)
+        beam_step_launch(bb, a, PromptSel<true>{p->ids, p->lengths, p->ld, p->max_len, a.cur_len}, s);
+    else
+        beam_step_launch(bb, a, PromptSel<false>{}, s);
     return hipGetLastError();
 }
 
-hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, int64_t* decoded, float* logprobs,
-                              int64_t* first_decoded, float* first_logprobs, hipStream_t s) {
+hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, const BeamFinishOut& o, hipStream_t s) {
     if (n < 1 || n > 16) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(beam_finish_kernel, dim3(B, n), dim3(64), 0, s, beam_state(bb), n, max_len, eos, decoded, logprobs, first_decoded,
-                       first_logprobs);
+    hipLaunchKernelGGL(beam_finish_kernel, dim3(B, n), dim3(64), 0, s, beam_state(bb), n, max_len, eos, o.decoded, o.logprobs, o.first_decoded,
+                       o.first_logprobs);
     return hipGetLastError();
 }
 

@@ -276,11 +276,13 @@ int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx,
     return 0;
 }
 
-// model.py:128-154 for rows x T query positions t0..t0+T-1 (K/V of earlier positions come from the cache)
-int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int t0, int T, float* logits_out,
-                 int64_t* argmax_out, int ld_argmax, int32_t* sep_cnt, int step, hipStream_t s, float* lp_out = nullptr, int ld_lp = 0,
-                 const ScoreReq* score = nullptr) {
+// model.py:128-154 for rows x T query positions t0..t0+T-1 (K/V of earlier positions come from the cache); the request is the
+// part the two handles share (RowsReq, kernels.h): logits_out set = the logits of all positions
+using TextReq = RowsReq;
+int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
     const gitcap_student_config& c = h->c;
+    const int64_t* const ids = q.ids;
+    const int ld_ids = q.ld_ids, rows = q.rows, t0 = q.t0, T = q.T;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student: decoder called before set_memory");
     if (!ids || rows <= 0 || T <= 0 || t0 < 0) return fail(h, GITCAP_ERR_ARG, "student: bad arguments");
@@ -338,21 +340,26 @@ int text_forward(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, in
         if ((rc = proj(SK_BIAS_RELU_BF16, Ly.l1w, Ly.l1b, h->FF, h->ffn, h->FF, 1, 1, 0))) return rc;
         if ((rc = dense_ln(h->ffn, h->FF, Ly.l2w, Ly.l2b, Ly.n3w, Ly.n3b, l + 1 < h->L))) return rc;
     }
-    if (!logits_out && !argmax_out && !score) return 0;
-    if (score) {        // gitcap_student_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
+    if (!q.logits_out && !q.argmax_out && !q.score) return 0;
+    if (q.score) {      // gitcap_student_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
         if (!h->amax_sum || !h->score_buf) return fail(h, GITCAP_ERR_STATE, "student: scoring without its buffers");
-        HIP_OK(h, launch_score(head_weight(h), h->xb, ids, ld_ids, rows, T, h->amax_val, h->amax_idx, h->amax_sum, h->score_buf, *score, s));
+        HIP_OK(h, launch_score(head_weight(h), h->xb, ids, ld_ids, rows, T, h->amax_val, h->amax_idx, h->amax_sum, h->score_buf, *q.score, s));
         return 0;
     }
     // vocabulary head: all positions when logits are requested, else the last position of every row
-    if (lp_out && (!argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
+    if (q.lp_out && (!q.argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
     SkinnyArgs ha;
-    const HeadRows hr = vocab_head_args(ha, head_weight(h), h->xb, rows, T, logits_out != nullptr, logits_out, argmax_out ? h->amax_val : nullptr,
-                                        argmax_out ? h->amax_idx : nullptr, lp_out ? h->amax_sum : nullptr);
+    const HeadRows hr = vocab_head_args(ha, head_weight(h), h->xb, rows, T, q.logits_out != nullptr, q.logits_out,
+                                        q.argmax_out ? h->amax_val : nullptr, q.argmax_out ? h->amax_idx : nullptr, q.lp_out ? h->amax_sum : nullptr);
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
-    if (argmax_out)
-        HIP_OK(h, launch_argmax_final(h->amax_val, h->amax_idx, (h->V + 15) / 16, rows, hr.am_stride, hr.am_off, argmax_out, ld_argmax,
-                                        sep_cnt, step, c.sep_token_id, s, nullptr, lp_out ? h->amax_sum : nullptr, lp_out, ld_lp));
+    if (q.argmax_out) {
+        ArgmaxArgs a{};
+        a.val = h->amax_val; a.idx = h->amax_idx; a.sum = q.lp_out ? h->amax_sum : nullptr; a.ntiles = (h->V + 15) / 16;
+        a.rows = rows; a.row_stride = hr.am_stride; a.row_off = hr.am_off;
+        a.out = q.argmax_out; a.ld_out = q.ld_argmax; a.sep_cnt = q.sep_cnt; a.step = q.step; a.sep_id = c.sep_token_id;
+        a.lp_out = q.lp_out; a.ld_lp = q.ld_lp;
+        HIP_OK(h, launch_argmax_final(a, s));
+    }
     return 0;
 }
 
@@ -390,7 +397,9 @@ int student_rows_check(const gitcap_student* h, int rows, int T, std::string& wh
     return 0;
 }
 int student_forward_rows(gitcap_student* h, const int64_t* ids, int ld_ids, int rows, int T, hipStream_t s, StudentRows* out, std::string& why) {
-    const int rc = text_forward(h, ids, ld_ids, rows, 0, T, nullptr, nullptr, 0, nullptr, 0, s);
+    TextReq q;                  // the stack's rows only, no head
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.T = T;
+    const int rc = text_forward(h, q, s);
     if (rc) { why = h->err; return rc; }
     *out = StudentRows{h->xb, head_weight(h)};
     return 0;
@@ -523,7 +532,9 @@ int gitcap_student_forward_decoder(gitcap_student_t* h, const int64_t* ids, int 
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_forward_decoder: null handle");
     if (!logits) return fail(h, GITCAP_ERR_ARG, "student_forward_decoder: null logits");
     GUARD(h);
-    return text_forward(h, ids, ld_ids, B, 0, T, logits, nullptr, 0, nullptr, 0, (hipStream_t)stream);
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = B; q.T = T; q.logits_out = logits;
+    return text_forward(h, q, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -538,7 +549,11 @@ const bool g_use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP
 // want_lp, its log-probability as column t of g_lp).  The full loop, the captured tail steps and the un-graphed tail are this call.
 int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q) {
     const int ld = max_len + 1;
-    return text_forward(h, h->g_ids, ld, B, t, 1, nullptr, h->g_ids + t + 1, ld, h->sep_cnt, t, q, want_lp ? h->g_lp + t : nullptr, max_len);
+    TextReq r;
+    r.ids = h->g_ids; r.ld_ids = ld; r.rows = B; r.t0 = r.step = t; r.T = 1;
+    r.argmax_out = h->g_ids + t + 1; r.ld_argmax = ld; r.sep_cnt = h->sep_cnt;
+    r.lp_out = want_lp ? h->g_lp + t : nullptr; r.ld_lp = max_len;
+    return text_forward(h, r, q);
 }
 
 // What enqueue(cap_stream) launches -> one executable graph (replayed on the caller's stream).  A failed enqueue still ends the
@@ -653,16 +668,20 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
                        (int64_t)h->c.cls_token_id, h->g_ids, ld);
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
-    if ((rc = text_forward(h, h->g_ids, ld, B, 0, n, nullptr, nullptr, 0, nullptr, 0, s))) return rc;
+    TextReq q;
+    q.ids = h->g_ids; q.ld_ids = ld; q.rows = B; q.T = n;
+    if ((rc = text_forward(h, q, s))) return rc;
     const int ntiles = (h->V + 15) / 16;
     SkinnyArgs ha;      // want_lp: the covered positions' log-probabilities come from this pass (the same bits as the loop's)
     vocab_head_args(ha, head_weight(h), h->xb, B, n, true, nullptr, h->amax_val, h->amax_idx, want_lp ? h->amax_sum : nullptr);
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     // 2. accept
     *(volatile int32_t*)h->acc_host = -1;
-    HIP_OK(h, launch_draft_accept(h->amax_val, h->amax_idx, ntiles, B, n, h->g_ids, ld, h->acc_tok, h->acc_ticket, h->sep_cnt,
-                                  h->c.sep_token_id, h->acc_host, s, want_lp ? h->amax_sum : nullptr, want_lp ? h->acc_lp : nullptr,
-                                  want_lp ? h->g_lp : nullptr, max_len));
+    DraftAcceptArgs da{};
+    da.val = h->amax_val; da.idx = h->amax_idx; da.ntiles = ntiles; da.B = B; da.n = n; da.ids = h->g_ids; da.ld = ld;
+    da.tok = h->acc_tok; da.ticket = h->acc_ticket; da.sep_cnt = h->sep_cnt; da.sep_id = h->c.sep_token_id; da.host = h->acc_host;
+    if (want_lp) { da.sum = h->amax_sum; da.lp_tok = h->acc_lp; da.lp_out = h->g_lp; da.ld_lp = max_len; }
+    HIP_OK(h, launch_draft_accept(da, s));
     HIP_OK(h, hipEventRecord(h->acc_ev, s));
     HIP_OK(h, hipEventSynchronize(h->acc_ev));
     const int a = ((volatile int32_t*)h->acc_host)[0];
@@ -722,6 +741,11 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
     int64_t *cur = w.ids0, *nxt = w.ids1;
     bf16_t* const kvs_home = h->kvs;
     const size_t kv_layer = (size_t)h->R * h->Tmax * 3 * D;
+    TextReq q;                  // one position of every beam row -> its logits
+    q.ld_ids = ld; q.rows = rows; q.T = 1; q.logits_out = w.logits;
+    CandArgs ca{};              // the k best of every clip's k * V candidates, no penalty
+    ca.logits = w.logits; ca.ld = V; ca.beam_scores = w.scores; ca.rp = 1.0f; ca.B = B; ca.beams = k; ca.V = V;
+    ca.out_scores = w.cand_scores; ca.out_idx = w.cand_idx;
     for (int t = 0; t + 1 < max_len && !rc; ++t) {                      // the token at position t is decoded, position t + 1 chosen
         if (t > 0) {                                                    // rows continue beam src_rows[r]: positions 0 .. t-1, all layers
             bf16_t* other = h->kvs == kvs_home ? w.kvs2 : kvs_home;
@@ -729,9 +753,10 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
             if (eg != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: gather_txt_rows: ") + hipGetErrorString(eg)); break; }   // (h->kvs is restored below on every path)
             h->kvs = other;
         }
-        rc = text_forward(h, cur, ld, rows, t, 1, w.logits, nullptr, 0, nullptr, 0, s);
+        q.ids = cur; q.t0 = t;
+        rc = text_forward(h, q, s);
         if (rc) break;
-        hipError_t e = launch_beam_topk(w.logits, V, w.scores, nullptr, 0, 0, 1.0f, B, k, V, k, w.cand_scores, w.cand_idx, w.topk_scratch, s);
+        hipError_t e = launch_beam_topk(ca, k, w.topk_scratch, s);
         if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
         hipLaunchKernelGGL(student_beam_step_kernel, dim3(B), dim3(64), 0, s, w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, k, V, t, ld);
         if (hipGetLastError() != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
@@ -925,8 +950,10 @@ int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, in
     int rc;
     if (!h->amax_sum && (rc = dev_alloc(h, &h->amax_sum, (size_t)h->Mt * (((size_t)h->V + 15) / 16)))) return rc;
     if (!h->score_buf && (rc = dev_alloc(h, &h->score_buf, 2 * (size_t)h->Mt))) return rc;
-    const ScoreReq q{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
-    return text_forward(h, ids, ld_ids, rows, 0, T, nullptr, nullptr, 0, nullptr, 0, (hipStream_t)stream, nullptr, 0, &q);
+    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.T = T; q.score = &sq;
+    return text_forward(h, q, (hipStream_t)stream);
 }
 
 int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream) {
