@@ -291,6 +291,31 @@ int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out,
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream);
 
+/* Greedy decoding that verifies a draft caption in one pass, accepted row by row (the teacher's counterpart of
+ * gitcap_student_greedy_draft; the reference has none).  gitcap_greedy_draft = gitcap_greedy, gitcap_window_greedy_draft =
+ * gitcap_window_greedy: *steps_out, ids_out[b][0 .. *steps_out] and the attached log-probabilities of those steps are bit for bit
+ * those of the call without a draft, whatever the draft holds (with GITCAP_STOP_NEVER that is every column).  A cached token step
+ * equals the teacher-forced position bit for bit, so ONE pass over the draft's n_draft positions yields the token the loop would
+ * emit behind every draft prefix.  Each clip keeps its OWN leading matches plus the loop's token at its first mismatch (covered_b
+ * = min(a_b + 1, n_draft) steps); the token loop resumes at the first step some clip lacks (min_b covered_b), clips ahead of it keep
+ * the tokens they hold; it is skipped when nothing is left or all rows emitted SEP in a step every clip covers (GITCAP_STOP_ALL_SEP).
+ *   draft_ids     device int64 [B][ld_draft]: column 0 is ignored and taken as CLS, columns 1..n_draft are the guessed tokens,
+ *                 1 <= n_draft <= max_len, ld_draft >= n_draft + 1; any ids (an id outside [0, vocab) can only be rejected)
+ *   accepted_out  HOST int32 [B] (nullable): a_b, the leading draft tokens accepted for clip b
+ * Synchronous only: the call waits on the host once, for an event behind its verify pass (not for the tail).  Takes
+ * gitcap_attach_token_logprobs and (gitcap_greedy_draft) gitcap_attach_frame_counts; a pending prompt or pending constraints are
+ * consumed and the call fails with GITCAP_ERR_ARG.  n_draft > 63, or B * n_draft beyond the slot's text-row workspace: the call
+ * runs the plain loop, reports 0 accepted and counts as a call with nothing offered.
+ * Errors: GITCAP_ERR_ARG for a null handle, draft_ids or ids_out, n_draft < 1, n_draft > max_len, ld_draft < n_draft + 1, and
+ * the checks of gitcap_greedy / gitcap_window_greedy.
+ * gitcap_draft_stats: host int64[4] = draft calls, draft tokens offered (n_draft per clip, summed), tokens accepted (summed over
+ * the clips), tail steps run behind verify passes. */
+int gitcap_greedy_draft(gitcap_t* h, const float* frames, int B, int F, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len,
+                        int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream);
+int gitcap_window_greedy_draft(gitcap_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop, float* visual_out,
+                               int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream);
+int gitcap_draft_stats(const gitcap_t* h, int64_t* out4);
+
 /* Per-token log-probabilities of a greedy caption (no reference counterpart: the reference's greedy loop returns ids only).
  * A ONE-SHOT attachment: it applies to the NEXT greedy-family call or submission on the handle -- gitcap_greedy, gitcap_greedy_raw,
  * gitcap_greedy_submit, gitcap_greedy_raw_submit, gitcap_window_greedy -- and is consumed by it, whether that call succeeds or
@@ -697,6 +722,25 @@ int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int 
 int gitcap_dbg_draft_accept_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
                                int32_t* tok, uint32_t* ticket, int32_t* sep_cnt, int sep_id, int32_t* host_out,
                                const float* amax_sum, float* lp_out, int ld_lp, void* stream);
+/* draft_accept_rows (the accept step of gitcap_greedy_draft): partials and ids as draft_accept, but every caption r keeps its own
+ * a_r = leading positions whose token equals ids[r][j + 1]; covered_r = min(a_r + 1, n).  ids[r][1..covered_r] = the model's
+ * tokens; len[r] (device int32 [B]) = 1 + covered_r; sep_cnt[j] += 1 (atomic; not zeroed here) for every covered (r, j) whose token
+ * is sep_id; nothing behind a caption's covered part is touched.  tok int32 [B * n], row_res int32 [2 * B] scratch; ticket: 1 + B
+ * zero words, zero again when the launch has finished.  The call synchronises `stream` and writes host_out (HOST int32 [4 + B]) =
+ * min covered, max covered, sum of a_r, 1 when some j < min covered has sep_cnt[j] == B else 0, then a_r per caption.
+ * _lp: and lp_out[r * ld_lp + j] (fp32 [B][ld_lp], ld_lp >= n) = argmax_final_lp's value of partial row r * n + j for j < covered_r. */
+int gitcap_dbg_draft_accept_rows(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                                 int32_t* len, int32_t* tok, int32_t* row_res, uint32_t* ticket, int32_t* sep_cnt, int sep_id,
+                                 int32_t* host_out, void* stream);
+int gitcap_dbg_draft_accept_rows_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                                    int32_t* len, int32_t* tok, int32_t* row_res, uint32_t* ticket, int32_t* sep_cnt, int sep_id,
+                                    int32_t* host_out, const float* amax_sum, float* lp_out, int ld_lp, void* stream);
+/* argmax_final_keep: the launch of a verified draft's tail step that writes position p = step + 1: a row with p < len[r] (device
+ * int32 [rows], draft_accept_rows') keeps out[r] and lp_out[r] as they are, adds nothing to sep_cnt, and its emb row is embedded
+ * from the id already in out[r]; every other row is gitcap_dbg_argmax_final(_lp)'s, bit for bit.  amax_sum / lp_out: both or neither. */
+int gitcap_dbg_argmax_final_keep(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                 int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                                 const float* amax_sum, float* lp_out, int ld_lp, const int32_t* len, void* stream);
 /* The bookkeeping launches of the device-resident beam search over its nine state buffers (R = B * beams rows):
  * ids0 / ids1 int64 [R][max_len] (double buffered prefixes), words int64 [R], hyp_ids int64 [B][max_len], beam_scores fp32 [R],
  * hyp_score fp32 [B], src_rows int32 [R], done / hyp_len int32 [B].

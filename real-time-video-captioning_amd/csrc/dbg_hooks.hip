@@ -325,6 +325,67 @@ int gitcap_dbg_draft_accept(const float* amax_val, const int32_t* amax_idx, int 
     return dbg_draft_accept(a, host_out, stream);
 }
 
+// the kept form (a verified draft's tail): the launch writes position step + 1; amax_sum / lp_out both or neither
+int gitcap_dbg_argmax_final_keep(const float* amax_val, const int32_t* amax_idx, int ntiles, int rows, int row_stride, int row_off,
+                                 int64_t* out, int ld_out, int32_t* sep_cnt, int step, int sep_id, const gitcap_dbg_next_embed* emb,
+                                 const float* amax_sum, float* lp_out, int ld_lp, const int32_t* len, void* stream) {
+    if (!len || (amax_sum == nullptr) != (lp_out == nullptr) || (lp_out && ld_lp < 1)) return GITCAP_ERR_ARG;
+    ArgmaxArgs a = dbg_argmax_args(amax_val, amax_idx, ntiles, rows, row_stride, row_off, out, ld_out, sep_cnt, step, sep_id);
+    a.sum = amax_sum; a.lp_out = lp_out; a.ld_lp = ld_lp; a.keep_len = len;
+    return dbg_argmax_final(a, emb, stream);
+}
+
+// launch_draft_accept_rows: the words the kernel publishes go through a page-locked int32[4 + B] this hook owns and, with lp_out,
+// the log-probabilities through a device int[B * n] scratch this hook owns as well
+static int dbg_draft_accept_rows(DraftAcceptRowsArgs a, int32_t* host_out, void* stream) {
+    static std::mutex mu;
+    static int32_t* host = nullptr;
+    static int64_t host_cap = 0;
+    static int* lp_tok = nullptr;
+    static int64_t lp_cap = 0;
+    if (!host_out || a.B <= 0 || a.n <= 0) return GITCAP_ERR_ARG;
+    std::lock_guard<std::mutex> lock(mu);
+    if (4 + (int64_t)a.B > host_cap) {
+        if (host) { (void)hipDeviceSynchronize(); (void)hipHostFree(host); }
+        host_cap = std::max<int64_t>(4 + (int64_t)a.B, 1024);
+        if (hipHostMalloc((void**)&host, (size_t)host_cap * 4, hipHostMallocMapped) != hipSuccess) { host = nullptr; host_cap = 0; return GITCAP_ERR_NOMEM; }
+    }
+    if (a.lp_out && (int64_t)a.B * a.n > lp_cap) {
+        if (lp_tok) { (void)hipDeviceSynchronize(); (void)hipFree(lp_tok); }
+        lp_cap = std::max<int64_t>((int64_t)a.B * a.n, 1024);
+        if (hipMalloc((void**)&lp_tok, (size_t)lp_cap * 4) != hipSuccess) { lp_tok = nullptr; lp_cap = 0; return GITCAP_ERR_NOMEM; }
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < 4 + a.B; ++i) ((volatile int32_t*)host)[i] = -1;
+    a.host = host; a.host_rows = host + 4; a.lp_tok = a.lp_out ? lp_tok : nullptr;
+    const hipError_t e = launch_draft_accept_rows(a, s);
+    if (e != hipSuccess) return dbg_rc(e);
+    if (hipStreamSynchronize(s) != hipSuccess) return GITCAP_ERR_HIP;
+    for (int i = 0; i < 4 + a.B; ++i) host_out[i] = ((volatile int32_t*)host)[i];
+    return 0;
+}
+static DraftAcceptRowsArgs dbg_accept_rows_args(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                                                int32_t* len, int32_t* tok, int32_t* row_res, uint32_t* ticket, int32_t* sep_cnt, int sep_id) {
+    DraftAcceptRowsArgs a{};
+    a.val = amax_val; a.idx = amax_idx; a.ntiles = ntiles; a.B = B; a.n = n; a.ids = ids; a.ld = ld; a.len = len; a.tok = tok;
+    a.row_res = row_res; a.ticket = ticket; a.sep_cnt = sep_cnt; a.sep_id = sep_id;
+    return a;
+}
+int gitcap_dbg_draft_accept_rows(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                                 int32_t* len, int32_t* tok, int32_t* row_res, uint32_t* ticket, int32_t* sep_cnt, int sep_id,
+                                 int32_t* host_out, void* stream) {
+    return dbg_draft_accept_rows(dbg_accept_rows_args(amax_val, amax_idx, ntiles, B, n, ids, ld, len, tok, row_res, ticket, sep_cnt, sep_id),
+                                 host_out, stream);
+}
+int gitcap_dbg_draft_accept_rows_lp(const float* amax_val, const int32_t* amax_idx, int ntiles, int B, int n, int64_t* ids, int ld,
+                                    int32_t* len, int32_t* tok, int32_t* row_res, uint32_t* ticket, int32_t* sep_cnt, int sep_id,
+                                    int32_t* host_out, const float* amax_sum, float* lp_out, int ld_lp, void* stream) {
+    if (!amax_sum || !lp_out || ld_lp < 1) return GITCAP_ERR_ARG;
+    DraftAcceptRowsArgs a = dbg_accept_rows_args(amax_val, amax_idx, ntiles, B, n, ids, ld, len, tok, row_res, ticket, sep_cnt, sep_id);
+    a.sum = amax_sum; a.lp_out = lp_out; a.ld_lp = ld_lp;
+    return dbg_draft_accept_rows(a, host_out, stream);
+}
+
 static bool dbg_beam_buffers(const gitcap_dbg_beam_buffers* b, BeamBuffers& bb) {
     if (!b || !b->ids0 || !b->ids1 || !b->words || !b->hyp_ids || !b->beam_scores || !b->hyp_score || !b->src_rows || !b->done || !b->hyp_len)
         return false;

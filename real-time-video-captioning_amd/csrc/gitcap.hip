@@ -151,6 +151,12 @@ struct gitcap : HandleCore {
         bool ragged = false;
         bool have = false, used = false;
         int Mt = 0;             // text rows (rows x positions) the slot's row workspace holds
+        // draft verification (gitcap_greedy_draft; slot 0 only, first use): launch_draft_accept_rows' scratch -- tok / lp_tok int[Mt],
+        // row_res int[2 * max_batch], ticket [1 + max_batch] (zero between launches) -- and keep_len int32[max_batch], the rows'
+        // verified lengths the KEEP arg-max of the tail reads
+        int *acc_tok = nullptr, *acc_lp = nullptr, *acc_row = nullptr;
+        unsigned* acc_ticket = nullptr;
+        int32_t* keep_len = nullptr;
         hipEvent_t ev_in = nullptr, ev_enc = nullptr, ev_dec = nullptr;
         hipStream_t s_txt = nullptr;
     };
@@ -169,6 +175,11 @@ struct gitcap : HandleCore {
     // the entry point's CallScope and empty outside it.  ban_ld: words per row of the constraints' ban mask
     CallOpts pending{}, call{};
     int ban_ld = 0;
+    // gitcap_greedy_draft: acc_host = the accept launch's page-locked words (int32 [4 + max_batch]: min covered, max covered,
+    // accepted summed, fired, then accepted per row), acc_ev = the event the call waits for behind it; gitcap_draft_stats' counters
+    int32_t* acc_host = nullptr;
+    hipEvent_t acc_ev = nullptr;
+    int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
 
     // gitcap_distill (first use): the dual head's seven partials [slot 0's Mt][ntiles], both models' target logits
     // ([2][Mt])
@@ -538,12 +549,16 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 
 // A pass of the decoder over text rows (RowsReq, kernels.h) and what only this stack takes: rows = clips * beams; all_positions:
 // logits of every position instead of the last; the per-step modifiers pre_embedded / embed_next (above), prompt (the arg-max
-// launch's, nullable) and ban (the BAN form of the head, nullable).
+// launch's, nullable) and ban (the BAN form of the head, nullable).  keep_len (nullable): the KEEP form of the arg-max launch.
+// verify (a draft's verify pass): the head over ALL rows x T positions, arg-max partials only (+ the sum partial: verify_lp), no
+// logits and no arg-max launch -- launch_draft_accept_rows reduces them.
 struct TextReq : RowsReq {
     int beams = 1, all_positions = 0;
     bool pre_embedded = false, embed_next = false;
     const PromptArgs* prompt = nullptr;
     const HeadBan* ban = nullptr;
+    const int32_t* keep_len = nullptr;
+    bool verify = false, verify_lp = false;
 };
 
 int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
@@ -642,9 +657,18 @@ int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
         if ((rc = ln_reduce(h, s, sl.slabs, ks_f, P.fc2b, xcur, P.ln2w, P.ln2b, c.dec_ln_eps, M, D, xcur, sl.xsb))) return rc;
         HIP_OK(h, keep_txt(c.dec_layers));
     }
-    if (!q.logits_out && !q.argmax_out && !q.score) return 0;
+    if (!q.logits_out && !q.argmax_out && !q.score && !q.verify) return 0;
     // vocabulary head (+ arg-max partials per 16-column tile, reduced by argmax_final)
     const int V = c.vocab_size, ntiles = (V + 15) / 16;
+    if (q.verify) {     // gitcap_greedy_draft: the partials of all positions, what the token steps' heads would have left one by one
+        if (q.verify_lp && !sl.amax_sum) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
+        SkinnyArgs va;
+        vocab_head_args(va, HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, rows, T, true, nullptr,
+                        sl.amax_val, sl.amax_idx, q.verify_lp ? sl.amax_sum : nullptr);
+        ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * va.M * V * D, (va.wscale ? 1.0 : 2.0) * V * D);
+        HIP_OK(h, launch_skinny(va, SK_BIAS_F32, s));
+        return 0;
+    }
     if (q.score) {      // gitcap_score: all positions, no logits; the three partials + the given tokens' logits -> score_final
         if (!sl.amax_sum || !sl.score_buf) return fail(h, GITCAP_ERR_STATE, "text_forward: scoring without its buffers");
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * M * V * D, (h->head_w.scale ? 1.0 : 2.0) * V * D);
@@ -669,6 +693,7 @@ int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
         a.out = q.argmax_out; a.ld_out = q.ld_argmax; a.sep_cnt = q.sep_cnt; a.step = q.step; a.sep_id = c.sep_token_id;
         a.lp_out = q.lp_out; a.ld_lp = q.ld_lp; a.emb = q.embed_next ? &ne : nullptr;
         a.prompt = q.prompt; a.prompt_pos = t0 + T;       // (greedy loop): the token goes to position t0 + T, where a row's prompt may still stand
+        a.keep_len = q.keep_len;                          // (a draft's tail): or the row's verified part
         HIP_OK(h, launch_argmax_final(a, s));
     }
     return 0;
@@ -893,6 +918,8 @@ void gitcap_destroy(gitcap_t* h) {
     if (h->win_ring) (void)hipFree(h->win_ring);
     free_allocs(*h);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
+    if (h->acc_host) (void)hipHostFree(h->acc_host);
+    if (h->acc_ev) (void)hipEventDestroy(h->acc_ev);
     for (auto& kv : h->w)
         if (kv.second.p) (void)hipFree(kv.second.p);
     for (auto& kv : h->wscale)
@@ -1221,7 +1248,10 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
 // token steps t_first .. max_len-1 of `rows` text rows (the image K/V of their clips in the selected slot), ids at ids_out (row pitch ld)
 // The call's options (h->call): lp (row pitch lp.ld): column t = the log-probability of the token step t emitted; pr: steps that
 // write a position inside a row's prompt take the prompt's token there (launch_argmax_final); co: the constraints
-static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, int t_first = 0) {
+// tail (nullable; a verified draft's, host_logic.h): the steps that write a position some row holds already run the KEEP arg-max
+// against the slot's keep_len
+static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, int t_first = 0,
+                       const DraftTail* tail = nullptr) {
     const LpAttach& lp = h->call.lp;
     const PromptArgs* prompt = h->call.pr.ids ? &h->call.pr : nullptr;
     const bool chain = text_chain_ok(h, rows, 1);
@@ -1243,6 +1273,7 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
                                       h->c.vocab_size, cur(h).ban_mask, bn.ld, s));
         q.ids = ids_out + t; q.t0 = q.step = t; q.argmax_out = ids_out + t + 1; q.lp_out = lp.p ? lp.p + t : nullptr;
         q.pre_embedded = have_rows; q.embed_next = next;
+        q.keep_len = tail && draft_keep_step(*tail, t) ? cur(h).keep_len : nullptr;
         if (const int rc = text_forward(h, q, s)) return rc;
         have_rows = next;
     }
@@ -1288,6 +1319,71 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
     return 0;
 }
 
+// ---- greedy decoding that verifies a draft caption, accepted row by row ------------------------------------------------------
+// A cached token step is bit for bit the teacher-forced position (the prompt plan above relies on it) and a row does not depend on
+// the rows beside it.  So the tokens the loop emits after CLS, d_1 .. d_j are the head's arg-max at position j of ONE pass over the
+// draft, and every caption keeps its own leading matches (launch_draft_accept_rows; the first position that differs holds the
+// loop's own token).  The loop goes on at the first step some caption lacks; captions ahead of it keep their tokens (KEEP arg-max)
+// and recompute K/V from them.  The call's options: lp only (a prompt or constraints are refused by the entry points).
+struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
+static int ensure_draft(gitcap* h) {
+    gitcap::Slot& sl = h->slots[0];
+    const size_t Bm = (size_t)h->c.max_batch;
+    if (!h->acc_host) {
+        HIP_OK(h, hipHostMalloc((void**)&h->acc_host, (4 + Bm) * 4, hipHostMallocMapped));
+        HIP_OK(h, hipEventCreateWithFlags(&h->acc_ev, hipEventDisableTiming));
+    }
+    int rc = 0;
+    if (!sl.acc_tok) rc = dev_alloc(h, &sl.acc_tok, (size_t)sl.Mt);
+    if (!rc && !sl.acc_lp) rc = dev_alloc(h, &sl.acc_lp, (size_t)sl.Mt);
+    if (!rc && !sl.acc_row) rc = dev_alloc(h, &sl.acc_row, 2 * Bm);
+    if (!rc && !sl.acc_ticket) rc = dev_alloc(h, &sl.acc_ticket, 1 + Bm);
+    if (!rc && !sl.keep_len) rc = dev_alloc(h, &sl.keep_len, Bm);
+    return rc;
+}
+static int greedy_draft_loop(gitcap* h, int B, const Draft& d, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s) {
+    const LpAttach& lp = h->call.lp;
+    const int ld = max_len + 1, n = d.n;
+    gitcap::Slot& sl = cur(h);
+    int rc;
+    if (n > 63 || (int64_t)B * n > sl.Mt) {      // beyond the accept launch / the slot's row workspace: the plain loop, nothing offered
+        if ((rc = greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s))) return rc;
+        if (d.accepted_out) std::fill(d.accepted_out, d.accepted_out + B, 0);
+        ++h->draft_calls;
+        return 0;
+    }
+    if ((rc = ensure_draft(h))) return rc;
+    // 1. stage; 2. verify: one pass over positions 0 .. n-1 (their K/V rows -> the cache), the head's partials of all B * n rows
+    HIP_OK(h, hipMemsetAsync(sl.sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
+    HIP_OK(h, launch_draft_stage(d.ids, d.ld, n, B, h->c.vocab_size, h->c.cls_token_id, ids_out, ld, s));
+    {
+        TextReq q;
+        q.ids = ids_out; q.ld_ids = ld; q.rows = B; q.T = n; q.verify = true; q.verify_lp = lp.p != nullptr;
+        if ((rc = text_forward(h, q, s))) return rc;
+    }
+    // 3. accept, and the call's one host wait
+    volatile int32_t* host = h->acc_host;
+    host[0] = -1;
+    DraftAcceptRowsArgs da{};
+    da.val = sl.amax_val; da.idx = sl.amax_idx; da.ntiles = (h->V + 15) / 16; da.B = B; da.n = n; da.ids = ids_out; da.ld = ld;
+    da.len = sl.keep_len; da.tok = sl.acc_tok; da.row_res = sl.acc_row; da.ticket = sl.acc_ticket; da.sep_cnt = sl.sep_cnt;
+    da.sep_id = h->c.sep_token_id; da.host = h->acc_host; da.host_rows = h->acc_host + 4;
+    if (lp.p) { da.sum = sl.amax_sum; da.lp_tok = sl.acc_lp; da.lp_out = lp.p; da.ld_lp = lp.ld; }
+    HIP_OK(h, launch_draft_accept_rows(da, s));
+    HIP_OK(h, hipEventRecord(h->acc_ev, s));
+    HIP_OK(h, hipEventSynchronize(h->acc_ev));
+    const int cmin = host[0], cmax = host[1], asum = host[2];
+    if (cmin < 1 || cmin > cmax || cmax > n) return fail(h, GITCAP_ERR_HIP, "greedy_draft: the accept kernel published no count");
+    // 4. tail: the token steps some caption lacks; 5. finish
+    const DraftTail tail = draft_tail_plan(cmin, cmax, host[3] != 0, max_len, stop == GITCAP_STOP_ALL_SEP);
+    if (tail.run && (rc = greedy_rows(h, B, max_len, ids_out, ld, s, tail.t_first, &tail))) return rc;
+    if (steps_out) HIP_OK(h, launch_finish_steps(sl.sep_cnt, B, max_len, stop, steps_out, s));
+    if (d.accepted_out)
+        for (int r = 0; r < B; ++r) d.accepted_out[r] = host[4 + r];
+    ++h->draft_calls; h->draft_offered += (int64_t)n * B; h->draft_accepted += asum; h->draft_tail_steps += tail.steps;
+    return 0;
+}
+
 }  // extern "C"
 
 // The call's constraints refuse a call whose rows could lose every column: each step bans at most n_suppress listed ids, one id per
@@ -1317,8 +1413,23 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, unsigned 
     if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
     if (int rc = lp_check(h, "greedy", lp, max_len)) return rc;
     if (int rc = cons_check(h, max_len, 1, "greedy")) return rc;
-    if (opts.refused) return fail(h, GITCAP_ERR_ARG, refused_message("window"));
+    if (opts.refused & OPT_FC) return fail(h, GITCAP_ERR_ARG, refused_message("window"));
+    if (opts.refused) return fail(h, GITCAP_ERR_ARG, "greedy_draft: a prompt or constraints are attached, which a draft call does not take");
     return body();
+}
+
+// the draft forms: log-probabilities (and, with an image pass of their own, frame counts) are taken, a pending prompt or pending
+// constraints are consumed and the call fails; synchronous only (the accept step waits on the host).  prefix(): the image pass.
+template <typename Prefix>
+static int greedy_draft_entry(gitcap* h, const char* null_msg, unsigned take, unsigned refuse, const Draft& d, int max_len, int stop,
+                              int64_t* ids_out, int32_t* steps_out, hipStream_t s, Prefix prefix) {
+    return greedy_entry(h, true, null_msg, take, refuse | OPT_PR | OPT_CO, max_len, stop, ids_out, [&]() -> int {
+        if (!d.ids) return fail(h, GITCAP_ERR_ARG, "greedy_draft: null draft_ids");
+        if (d.n < 1 || d.n > max_len || d.ld < d.n + 1)
+            return fail(h, GITCAP_ERR_ARG, "greedy_draft: n_draft outside [1, max_len], or ld_draft < n_draft + 1");
+        if (int rc = prefix()) return rc;
+        return greedy_draft_loop(h, cur(h).B, d, max_len, stop, ids_out, steps_out, s);
+    });
 }
 
 // synchronous: image pass and token loop on the caller's stream, slot 0 (a raw source is checked by the image pass alone)
@@ -1615,6 +1726,26 @@ int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out, 
         if (int rc = window_prefix(h, visual_out, s)) return rc;
         return greedy_text_loop(h, h->win_B, max_len, stop, ids_out, steps_out, s);
     });
+}
+
+int gitcap_greedy_draft(gitcap_t* h, const float* frames, int B, int F, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len,
+                        int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return greedy_draft_entry(h, "greedy_draft: null handle", OPT_LP | OPT_FC, 0, Draft{draft_ids, ld_draft, n_draft, accepted_out}, max_len, stop,
+                              ids_out, steps_out, s, [&]() -> int { return encode_sync(h, FrameSrc{frames, nullptr, 0, 0}, B, F, nullptr, s); });
+}
+
+int gitcap_window_greedy_draft(gitcap_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop, float* visual_out,
+                               int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return greedy_draft_entry(h, "window_greedy_draft: null handle", OPT_LP, OPT_FC, Draft{draft_ids, ld_draft, n_draft, accepted_out}, max_len,
+                              stop, ids_out, steps_out, s, [&]() -> int { return window_prefix(h, visual_out, s); });
+}
+
+int gitcap_draft_stats(const gitcap_t* h, int64_t* out4) {
+    if (!h || !out4) return GITCAP_ERR_ARG;
+    out4[0] = h->draft_calls; out4[1] = h->draft_offered; out4[2] = h->draft_accepted; out4[3] = h->draft_tail_steps;
+    return 0;
 }
 
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,

@@ -221,6 +221,23 @@ inline std::string refused_message(const char* who) {
     return std::string(who) + ": per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take";
 }
 
+// ---- the tail of a draft verified row by row (gitcap_greedy_draft) ---------------------------------------------------------
+// The accept launch reports min / max over the captions of covered_r (the steps the verify pass settled for caption r) and whether
+// all rows emitted SEP in one of the steps every caption covers.  The token loop goes on at the first step some caption lacks,
+// t_first = min covered -- captions ahead of it recompute K/V from the tokens they already hold, the same bits -- unless nothing is
+// left (t_first >= max_len) or the stop rule (stop_all_sep) has fired.  keep_below: step t writes position t + 1, which a caption
+// holds already while t + 1 < 1 + covered_r: steps with t + 1 < keep_below = 1 + max covered run the KEEP arg-max, the rest the plain one.
+struct DraftTail { bool run; int t_first, keep_below, steps; };
+inline DraftTail draft_tail_plan(int min_covered, int max_covered, bool fired, int max_len, bool stop_all_sep) {
+    DraftTail p{};
+    p.t_first = min_covered;
+    p.keep_below = 1 + max_covered;
+    p.run = min_covered < max_len && !(stop_all_sep && fired);
+    p.steps = p.run ? max_len - min_covered : 0;
+    return p;
+}
+inline bool draft_keep_step(const DraftTail& p, int t) { return t + 1 < p.keep_below; }
+
 // ---- residual + LayerNorm GEMM: workgroup -> tile ----------------------------------------------------------------
 // The N/256 tiles of a 256-row block wait for each other (statistics exchange, gemm_epilogue.h), so they must be
 // consecutive workgroups of ONE XCD's dispatch sequence.  Workgroup b runs on XCD b % 8 as that XCD's (b / 8)-th

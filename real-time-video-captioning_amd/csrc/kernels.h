@@ -259,6 +259,10 @@ struct ArgmaxArgs {
     // takes ids[r][prompt_pos] instead of its arg-max (out, the embedded next row), leaves sep_cnt alone and gets lp 0.0f; with
     // prompt_pos >= max_len the launch is the one without a prompt.
     const PromptArgs* prompt; int prompt_pos;
+    // keep_len (nullable, device int32 [rows]; not with a prompt): the KEEP form -- a row with prompt_pos < keep_len[r] keeps
+    // out[r] and lp_out[r] as they stand, leaves sep_cnt alone and embeds its next row from the id already in out[r]
+    // (launch_draft_accept_rows wrote them); every other row is the plain launch's.
+    const int32_t* keep_len;
 };
 hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s);
 // Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
@@ -279,6 +283,28 @@ struct DraftAcceptArgs {
     int* lp_tok; float* lp_out; int ld_lp;
 };
 hipError_t launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s);
+// Draft verification of the teacher's greedy loop, accepted row by row.  launch_draft_stage: ids [rows][ld] column 0 = cls, columns
+// 1..n = draft [rows][ld_draft] columns 1..n, an id outside [0, vocab) as -1.  launch_draft_accept_rows: launch_draft_accept's
+// partials and tie rule, but per caption r: a_r = its leading matching positions, covered_r = min(a_r + 1, n); ids[r][1..covered_r],
+// len[r] = 1 + covered_r (ArgmaxArgs::keep_len), lp_out[r*ld_lp + j] for j < covered_r, sep_cnt[j] += 1 per covered SEP (atomic: the
+// caller zeroes sep_cnt), host_rows[r] = a_r; host = {min covered, max covered, sum of a_r, some j < min covered has sep_cnt[j] == B}.
+// Nothing behind a caption's covered part is written.
+struct DraftAcceptRowsArgs {
+    const float* val; const int* idx;
+    const float* sum;             // nullable, with lp_out (both or neither)
+    int ntiles, B, n;             // n <= 63
+    int64_t* ids; int ld;
+    int32_t* len;                 // device int32[B]
+    int* tok;                     // int[B * n] scratch
+    int* row_res;                 // int[2 * B] scratch
+    unsigned* ticket;             // 1 + B words, zero between launches
+    int32_t* sep_cnt; int sep_id;
+    int32_t* host;                // page-locked int32[4]
+    int32_t* host_rows;           // nullable: page-locked int32[B]
+    int* lp_tok; float* lp_out; int ld_lp;      // lp_tok: int[B * n] scratch, ld_lp >= n
+};
+hipError_t launch_draft_stage(const int64_t* draft, int ld_draft, int n, int rows, int vocab, int64_t cls, int64_t* ids, int ld, hipStream_t s);
+hipError_t launch_draft_accept_rows(const DraftAcceptRowsArgs& a, hipStream_t s);
 
 // ---- attention ---------------------------------------------------------------------------
 // Full (unmasked) self-attention over groups of S rows: qkv [G*S][3*W] bf16 (q | k | v, head h

@@ -443,19 +443,27 @@ __device__ __forceinline__ int prompt_len(const int32_t* __restrict__ lengths, c
 // stay the code they were.  FORCED (again a form of its own): a row whose prompt covers the position written (pr.pos <
 // lengths[r]) takes the prompt's token there instead of the arg-max -- into out, and into the next step's embedded row -- does not
 // count it in sep_cnt (the stop rule looks at what the model emitted) and writes 0.0f for its log-probability.
-template <int NV, bool LP = false, bool FORCED = false>
+// KEEP (a form of its own as well; the tail of a verified draft, gitcap.hip: greedy_draft_loop): a row whose verified part covers
+// the position written (kp.pos < kp.len[r], len = valid tokens, CLS included: draft_accept_rows_kernel's) keeps out[r] and
+// lp_out[r] as they are -- the accept kernel wrote the loop's own token and log-probability there -- leaves sep_cnt alone (the
+// accept kernel counted that position) and embeds the next step's input row from the id already stored.  Every other row is the
+// plain kernel.
+template <bool KEEP> struct KeepSel {};
+template <> struct KeepSel<true> { const int32_t* len; int pos; };
+template <int NV, bool LP = false, bool FORCED = false, bool KEEP = false>
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ val, const int* __restrict__ idx,
                                                            int ntiles, int row_stride, int row_off,
                                                            int64_t* __restrict__ out, int ld_out,
                                                            int32_t* __restrict__ sep_cnt, int step, int sep_id, NextEmbed emb,
                                                            const float* __restrict__ psum = nullptr, float* __restrict__ lp_out = nullptr,
-                                                           int ld_lp = 0, PromptSel<FORCED> pr = PromptSel<FORCED>{}) {
+                                                           int ld_lp = 0, PromptSel<FORCED> pr = PromptSel<FORCED>{},
+                                                           KeepSel<KEEP> kp = KeepSel<KEEP>{}) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ int chosen;
     __shared__ float vmax, ss[4];
     const int r = blockIdx.x, tid = threadIdx.x;
-    bool forced = false;                                                   // (thread 0's is the row's)
+    bool forced = false;                                                   // (thread 0's is the row's; a kept row counts as forced)
     const size_t base = (size_t)(r * row_stride + row_off) * ntiles;
     // gamma / beta of the next step's input row do not depend on the token chosen below: requested now (wave 0 uses them)
     f32x4 gv[NV > 0 ? NV : 1], bv[NV > 0 ? NV : 1];
@@ -476,6 +484,13 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
                 chosen = tok < 0 ? -1 : (tok > 0x7fffffff ? 0x7fffffff : (int)tok);   // (the embedding clamps into its table)
             }
         }
+        if constexpr (KEEP) {
+            forced = kp.pos < kp.len[r];
+            if (forced) {
+                const int64_t tok = out[(size_t)r * ld_out];
+                chosen = tok < 0 ? -1 : (tok > 0x7fffffff ? 0x7fffffff : (int)tok);
+            }
+        }
         if (!forced) {
             out[(size_t)r * ld_out] = bi;
             if (sep_cnt && bi == sep_id) atomicAdd(&sep_cnt[step], 1);
@@ -485,7 +500,11 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
     if (LP) {
         __syncthreads();
         const float lp = lp_partials(val, psum, base, ntiles, vmax, ss);
-        if (tid == 0) lp_out[(size_t)r * ld_lp] = forced ? 0.0f : lp;
+        if constexpr (KEEP) {
+            if (tid == 0 && !forced) lp_out[(size_t)r * ld_lp] = lp;
+        } else {
+            if (tid == 0) lp_out[(size_t)r * ld_lp] = forced ? 0.0f : lp;
+        }
     }
     if (NV > 0) {       // the next step's input row: embedding of the token just chosen + LayerNorm (one wave)
         __syncthreads();
@@ -564,6 +583,106 @@ __global__ __launch_bounds__(256) void draft_accept_kernel(const float* __restri
     if (j < covered) sep_cnt[j] = seps;
     const bool fired = __ballot(j < covered && seps == B) != 0ull;
     if (j == 0) { host[0] = a; host[1] = fired ? 1 : 0; }
+}
+
+// ---- draft verification of the teacher's greedy loop, accepted row by row (gitcap.hip: greedy_draft_loop) -------------------
+// column 0 = CLS whatever the draft holds, columns 1..n the draft's tokens, an id outside [0, vocab) as -1: the embedding clamps it
+// into its table, it equals no arg-max, so it can only be rejected
+__global__ void draft_stage_kernel(const int64_t* __restrict__ draft, int ld_draft, int n, int rows, int vocab, int64_t cls,
+                                   int64_t* __restrict__ ids, int ld) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * (n + 1)) return;
+    const int r = i / (n + 1), c = i % (n + 1);
+    const int64_t d = draft[(size_t)r * ld_draft + c];
+    ids[(size_t)r * ld + c] = c == 0 ? cls : (d >= 0 && d < vocab ? d : -1);
+}
+// draft_accept_kernel's pass (row m = r * n + j, one workgroup each, the same reduction, the same hand-off), but every caption
+// keeps what IT accepted: a batch's rows do not wait for its worst one.  Two tickets: the last workgroup of caption r to arrive
+// (ticket[1 + r]) does that caption's bookkeeping with its first wave, lane j = position j --
+//   a_r = leading positions whose token equals the draft's next token ids[r][j + 1] (-1 equals no token);
+//   covered_r = min(a_r + 1, n): the first differing position already holds the loop's own token;
+//   ids[r][1 .. covered_r] = the model's tokens, len[r] = 1 + covered_r (valid tokens, CLS included: what KeepSel reads);
+//   sep_cnt[j] += 1 for every covered j whose token is SEP (integer atomics: order independent);
+//   LP: lp_out[r * ld_lp + j] for j < covered_r; host_rows[r] = a_r (nullable, page-locked);
+//   row_res[2 r], [2 r + 1] = covered_r, a_r for the last caption
+// -- and the last caption to finish (ticket[0]) publishes host[0..3] = min covered, max covered, sum of a_r, fired (some step
+// j < min covered at which sep_cnt[j] == B: every row emitted SEP there).  Nothing behind a caption's covered part is written.
+// All ticket words are zero between launches.
+template <bool LP>
+__global__ __launch_bounds__(256) void draft_accept_rows_kernel(const float* __restrict__ val, const int* __restrict__ idx, int ntiles,
+                                                                int B, int n, int64_t* ids, int ld, int32_t* len, int* tok,
+                                                                int* row_res, unsigned* ticket, int32_t* sep_cnt, int sep_id,
+                                                                int32_t* host, int32_t* host_rows, const float* __restrict__ psum,
+                                                                int* lp_tok, float* lp_out, int ld_lp) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int last_flag;
+    __shared__ float vmax, ss[4];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int r = m / n;
+    float best;
+    int bi;
+    argmax_partials_waves(val, idx, (size_t)m * ntiles, ntiles, sv, si, best, bi);
+    if (tid == 0)
+        __hip_atomic_store(tok + m, argmax_partials_pick(sv, si, best, bi, LP ? &vmax : nullptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (LP) {
+        __syncthreads();
+        const float lp = lp_partials(val, psum, (size_t)m * ntiles, ntiles, vmax, ss);
+        if (tid == 0) __hip_atomic_store(lp_tok + m, __float_as_int(lp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned old = __hip_atomic_fetch_add(ticket + 1 + r, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = old == (unsigned)n - 1;
+        if (last) __hip_atomic_store(ticket + 1 + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+        last_flag = last;
+    }
+    __syncthreads();
+    if (!last_flag || tid >= 64) return;
+    // the caption's bookkeeping: one wave, no barrier from here on
+    const int j = tid;                                                      // n <= 63: one lane per position
+    const int t = j < n ? __hip_atomic_load(tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+    const bool match = j < n && (int64_t)t == ids[(size_t)r * ld + j + 1];
+    const unsigned long long miss = __ballot(!match);                       // lanes >= n miss: never zero
+    const int a = (int)__ffsll((long long)miss) - 1;
+    const int covered = a < n ? a + 1 : n;
+    if (j < covered) {
+        ids[(size_t)r * ld + j + 1] = t;
+        if (t == sep_id) atomicAdd(&sep_cnt[j], 1);
+        if (LP)
+            lp_out[(size_t)r * ld_lp + j] = __int_as_float(__hip_atomic_load(lp_tok + r * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    if (j == 0) {
+        len[r] = 1 + covered;
+        if (host_rows) host_rows[r] = a;
+        __hip_atomic_store(row_res + 2 * r, covered, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(row_res + 2 * r + 1, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // (the wave's stores and atomics have reached memory)
+    int last_row = 0;
+    if (j == 0) {
+        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_row = old == (unsigned)B - 1;
+        if (last_row) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!__shfl(last_row, 0)) return;
+    int cmin = n, cmax = 0, asum = 0;
+    for (int q = j; q < B; q += 64) {
+        const int c = __hip_atomic_load(row_res + 2 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cmin = min(cmin, c);
+        cmax = max(cmax, c);
+        asum += __hip_atomic_load(row_res + 2 * q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cmin = min(cmin, __shfl_xor(cmin, o));
+        cmax = max(cmax, __shfl_xor(cmax, o));
+        asum += __shfl_xor(asum, o);
+    }
+    const int cnt = j < cmin ? __hip_atomic_load(sep_cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+    const bool fired = __ballot(j < cmin && cnt == B) != 0ull;
+    if (j == 0) { host[0] = cmin; host[1] = cmax; host[2] = asum; host[3] = fired ? 1 : 0; }
 }
 
 // ---- scoring of given captions (gitcap_score; kernels.h: launch_score_final) ---------------------------------------------------
@@ -1473,21 +1592,23 @@ hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int 
     return hipGetLastError();
 }
 
-// one launch form of argmax_final_kernel: without LP the kernel is handed null sum / lp, without FORCED the empty PromptSel
-template <int NV, bool LP, bool FORCED>
-static void argmax_final_launch(const ArgmaxArgs& a, const NextEmbed& e, const PromptSel<FORCED>& pr, hipStream_t s) {
-    hipLaunchKernelGGL((argmax_final_kernel<NV, LP, FORCED>), dim3(a.rows), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.row_stride, a.row_off,
-                       a.out, a.ld_out, a.sep_cnt, a.step, a.sep_id, e, LP ? a.sum : nullptr, LP ? a.lp_out : nullptr, LP ? a.ld_lp : 0, pr);
+// one launch form of argmax_final_kernel: without LP the kernel is handed null sum / lp, without FORCED the empty PromptSel,
+// without KEEP the empty KeepSel
+template <int NV, bool LP, bool FORCED, bool KEEP>
+static void argmax_final_launch(const ArgmaxArgs& a, const NextEmbed& e, const PromptSel<FORCED>& pr, const KeepSel<KEEP>& kp, hipStream_t s) {
+    hipLaunchKernelGGL((argmax_final_kernel<NV, LP, FORCED, KEEP>), dim3(a.rows), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.row_stride, a.row_off,
+                       a.out, a.ld_out, a.sep_cnt, a.step, a.sep_id, e, LP ? a.sum : nullptr, LP ? a.lp_out : nullptr, LP ? a.ld_lp : 0, pr, kp);
 }
-template <bool FORCED>
-static void argmax_final_dispatch(const ArgmaxArgs& a, int nv, const NextEmbed& e, const PromptSel<FORCED>& pr, hipStream_t s) {
+template <bool FORCED, bool KEEP>
+static void argmax_final_dispatch(const ArgmaxArgs& a, int nv, const NextEmbed& e, const PromptSel<FORCED>& pr, const KeepSel<KEEP>& kp,
+                                  hipStream_t s) {
     const bool lp = a.lp_out != nullptr;
     switch (nv) {
-        case 0: lp ? argmax_final_launch<0, true>(a, e, pr, s) : argmax_final_launch<0, false>(a, e, pr, s); break;
-        case 1: lp ? argmax_final_launch<1, true>(a, e, pr, s) : argmax_final_launch<1, false>(a, e, pr, s); break;
-        case 2: lp ? argmax_final_launch<2, true>(a, e, pr, s) : argmax_final_launch<2, false>(a, e, pr, s); break;
-        case 3: lp ? argmax_final_launch<3, true>(a, e, pr, s) : argmax_final_launch<3, false>(a, e, pr, s); break;
-        default: lp ? argmax_final_launch<4, true>(a, e, pr, s) : argmax_final_launch<4, false>(a, e, pr, s); break;
+        case 0: lp ? argmax_final_launch<0, true>(a, e, pr, kp, s) : argmax_final_launch<0, false>(a, e, pr, kp, s); break;
+        case 1: lp ? argmax_final_launch<1, true>(a, e, pr, kp, s) : argmax_final_launch<1, false>(a, e, pr, kp, s); break;
+        case 2: lp ? argmax_final_launch<2, true>(a, e, pr, kp, s) : argmax_final_launch<2, false>(a, e, pr, kp, s); break;
+        case 3: lp ? argmax_final_launch<3, true>(a, e, pr, kp, s) : argmax_final_launch<3, false>(a, e, pr, kp, s); break;
+        default: lp ? argmax_final_launch<4, true>(a, e, pr, kp, s) : argmax_final_launch<4, false>(a, e, pr, kp, s); break;
     }
 }
 
@@ -1498,10 +1619,13 @@ hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s) {
     if ((a.sum == nullptr) != (a.lp_out == nullptr) || (a.lp_out && a.ld_lp < 1)) return hipErrorInvalidValue;
     const PromptArgs* p = a.prompt;
     if (p && (!p->ids || !p->lengths || p->max_len < 1 || p->ld < p->max_len || a.prompt_pos < 0)) return hipErrorInvalidValue;
-    if (p && a.prompt_pos < p->max_len)             // (behind the longest prompt the plain forms choose the same tokens)
-        argmax_final_dispatch(a, nv, e, PromptSel<true>{p->ids, p->lengths, p->ld, p->max_len, a.prompt_pos}, s);
+    if (a.keep_len && (p || a.prompt_pos < 0)) return hipErrorInvalidValue;      // (the kept form is not combined with a prompt)
+    if (a.keep_len)
+        argmax_final_dispatch(a, nv, e, PromptSel<false>{}, KeepSel<true>{a.keep_len, a.prompt_pos}, s);
+    else if (p && a.prompt_pos < p->max_len)        // (behind the longest prompt the plain forms choose the same tokens)
+        argmax_final_dispatch(a, nv, e, PromptSel<true>{p->ids, p->lengths, p->ld, p->max_len, a.prompt_pos}, KeepSel<false>{}, s);
     else
-        argmax_final_dispatch(a, nv, e, PromptSel<false>{}, s);
+        argmax_final_dispatch(a, nv, e, PromptSel<false>{}, KeepSel<false>{}, s);
     return hipGetLastError();
 }
 
@@ -1545,6 +1669,28 @@ hipError_t launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s) {
     else
         hipLaunchKernelGGL(draft_accept_kernel<false>, dim3(a.B * a.n), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.B, a.n, a.ids, a.ld, a.tok,
                            a.ticket, a.sep_cnt, a.sep_id, a.host, (const float*)nullptr, (int*)nullptr, (float*)nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_draft_stage(const int64_t* draft, int ld_draft, int n, int rows, int vocab, int64_t cls, int64_t* ids, int ld, hipStream_t s) {
+    if (!draft || !ids || n < 1 || rows < 1 || vocab < 1 || ld_draft < n + 1 || ld < n + 1 || (int64_t)rows * (n + 1) > 0x7fffffff)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(draft_stage_kernel, dim3((rows * (n + 1) + 255) / 256), dim3(256), 0, s, draft, ld_draft, n, rows, vocab, cls, ids, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_draft_accept_rows(const DraftAcceptRowsArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.n < 1 || a.n > 63 || (int64_t)a.B * a.n > 0x7fffffff || a.ld < a.n + 1 || a.ntiles <= 0 || !a.val || !a.idx || !a.ids ||
+        !a.len || !a.tok || !a.row_res || !a.ticket || !a.sep_cnt || !a.host)
+        return hipErrorInvalidValue;
+    if ((a.sum == nullptr) != (a.lp_out == nullptr) || (a.lp_out && (!a.lp_tok || a.ld_lp < a.n))) return hipErrorInvalidValue;
+    if (a.lp_out)
+        hipLaunchKernelGGL(draft_accept_rows_kernel<true>, dim3(a.B * a.n), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.B, a.n, a.ids, a.ld, a.len,
+                           a.tok, a.row_res, a.ticket, a.sep_cnt, a.sep_id, a.host, a.host_rows, a.sum, a.lp_tok, a.lp_out, a.ld_lp);
+    else
+        hipLaunchKernelGGL(draft_accept_rows_kernel<false>, dim3(a.B * a.n), dim3(256), 0, s, a.val, a.idx, a.ntiles, a.B, a.n, a.ids, a.ld, a.len,
+                           a.tok, a.row_res, a.ticket, a.sep_cnt, a.sep_id, a.host, a.host_rows, (const float*)nullptr, (int*)nullptr,
+                           (float*)nullptr, 0);
     return hipGetLastError();
 }
 

@@ -9,6 +9,9 @@ def __getattr__(name):
     if name == "GitCaptioner":
         from .model import GitCaptioner
         return GitCaptioner
+    if name == "draft_and_verify":
+        from .model import draft_and_verify
+        return draft_and_verify
     if name == "caption_confidence":
         from .confidence import caption_confidence
         return caption_confidence

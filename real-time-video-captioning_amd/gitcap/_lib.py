@@ -209,6 +209,18 @@ SYMBOLS = {
                                                c_void_p]),
     "gitcap_dbg_beam_step_forced": (c_int, [POINTER(CDbgBeamBuffersNbest), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_float, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    # greedy decoding that verifies a draft, accepted row by row (tests/test_draft_rows_gpu.py, test_teacher_draft_e2e_gpu.py)
+    "gitcap_greedy_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    POINTER(c_int32), c_void_p]),
+    "gitcap_window_greedy_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           POINTER(c_int32), c_void_p]),
+    "gitcap_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
+    "gitcap_dbg_draft_accept_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p]),
+    "gitcap_dbg_draft_accept_rows_lp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int, POINTER(c_int32), c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_argmax_final_keep": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                             POINTER(CDbgNextEmbed), c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     # constrained decoding: n-gram, length and token bans (tests/test_constraints_gpu.py)
     "gitcap_attach_constraints": (c_int, [c_void_p, POINTER(CConstraints)]),
     "gitcap_dbg_ban_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),

@@ -372,8 +372,12 @@ class CaptionStream(_WindowStream):
     (gitcap.framegate.FrameGate) only the camera frames it admits are encoded and counted."""
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
-                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None):
+                 gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None,
+                 carry=False):
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
+        # carry: the previous caption (on the device, truncated as it was returned) is the draft of the next window call
+        self._carry, self._prev = bool(carry), None
+        self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
         self._sampling = sampling        # (temperature, top_k, top_p, seed | None) of a do_sample stream
         # the stream's prompt (_Prompt | None), constraints (_Constraints | None) and search options: attached again for every caption
         self._attached = (prompt, constraints, None, num_keep_best, repetition_penalty)
@@ -388,6 +392,13 @@ class CaptionStream(_WindowStream):
     def _clear(self):
         self._kept = []                  # the last `window` frames per push order, [B, ...] each: what a recovery pushes again
         self._kind = None                # (raw, device) of the frames since the reset
+        self._prev = None                # carry: the next caption is a plain call
+
+    def stats(self) -> dict:
+        """Since the stream was opened (the student stream's keys): ``captions`` returned, ``draft_tokens`` offered to the verify
+        pass (per clip; 0 for a caption decoded by the plain call), ``accepted`` of them (summed over the clips: every clip keeps
+        its own), ``tail_steps`` decoded one by one behind a draft, and ``last`` = the same three numbers of the latest caption."""
+        return dict(self._stats)
 
     def _shape(self, frames):
         """[B,H,W,3] uint8 / [B,3,S,S] fp32 (one frame per clip) or [B,n,...] -> (5-D view, raw)."""
@@ -455,8 +466,12 @@ class CaptionStream(_WindowStream):
             if self._beam is None:
                 ids, steps, lp = self._greedy_buffers(B)
                 opts = _CallOptions(m, *self._attached)
-                opts.attach(lp)
-                m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
+                last = dict(draft_tokens=0, accepted=0, tail_steps=0)
+                if self._carry and self._prev is not None and self._prev.shape[1] >= 2:
+                    last = m._draft_call("gitcap_window_greedy_draft", (), (_lib.ptr(vis),), self._prev, self._max_len, self._mode, ids, steps, lp)
+                else:
+                    opts.attach(lp)
+                    m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
                 sampling = m._seeded(self._sampling)
                 opts = _CallOptions(m, *self._attached, sampling)
@@ -467,8 +482,15 @@ class CaptionStream(_WindowStream):
                 if sampling is not None:
                     self.last_seed = sampling[3]
         m._last_memory = None
+        self._stats["captions"] += 1
         if self._beam is None:
-            return self._finish_greedy(ids, steps, lp, on_cpu)
+            out = self._finish_greedy(ids, steps, lp, on_cpu)
+            if self._carry:
+                self._prev = ids[:, :out.shape[1]]
+            for k, v in last.items():
+                self._stats[k] += v
+            self._stats["last"] = last
+            return out
         mv = (lambda t: t if t is None else t.cpu()) if on_cpu else (lambda t: t)
         out = {"predictions": mv(decoded), "logprobs": mv(_lp2d(logprobs)), "logits_dict": [], "visual_features": mv(vis)}
         if opts.prompt is not None:
@@ -531,6 +553,7 @@ class GitCaptioner(_NativeModule):
         self._undelivered = set()                       # waited for, but a future has still to hand out (or re-run) its rows
         self._ring = None                               # _StagingRing, made when the first CPU tensor arrives
         self._window_owner = None                       # token of the one live CaptionStream (the handle has one frame window)
+        self.last_accepted: Optional[torch.Tensor] = None   # int32 [B]: draft tokens the last greedy_decode(draft=...) accepted per clip
         self._copy_stream = os.environ.get("GITCAP_COPY_STREAM", "caller")  # "caller" | "own" (A/B switch; see _StagingRing)
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
         self._open()
@@ -1062,7 +1085,7 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
                       prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                      frame_counts=None):
+                      frame_counts=None, draft: Optional[torch.Tensor] = None):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
@@ -1083,7 +1106,14 @@ class GitCaptioner(_NativeModule):
         frame_counts: clips that differ in length -- ``src`` padded [B, Fmax, ...] with frame_counts [B] (frames beyond a clip's
         count are ignored) or a list of B clips [F_b, ...] (counts inferred); fp32 or uint8 camera frames, host or device.  The
         batch runs packed, without padding or masking (include/gitcap.h: gitcap_attach_frame_counts): every clip's ids and
-        logprobs are bit for bit those of the clip decoded alone.  Equal counts take the dense path."""
+        logprobs are bit for bit those of the clip decoded alone.  Equal counts take the dense path.
+        draft: int64 [B, 1+n], a guess at the result (the previous caption of a live stream, the student's caption of the same
+        frames; column 0 is taken as CLS, any ids are allowed).  The result is the one without it, bit for bit: the draft is
+        verified in one pass, every clip keeps the leading tokens the loop would have produced anyway (``last_accepted`` [B] =
+        their numbers) and only the steps some clip still lacks are decoded one by one (include/gitcap.h: gitcap_greedy_draft).
+        The call waits on the host for the verify pass.  Not with prompt or the constraint arguments."""
+        if draft is not None and (prompt is not None or no_repeat_ngram_size or min_length or suppress_tokens is not None):
+            raise ValueError("draft= is not combined with prompt= or the constraint arguments")
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
@@ -1093,9 +1123,11 @@ class GitCaptioner(_NativeModule):
             src, rg = self._ragged_input(src, frame_counts)
         B, in_dev = (src.shape[0], src.device) if rg is None else (len(rg[1]), rg[0][0].device)
         opts = self._greedy_options(B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg)
+        if draft is not None and (draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] < 2 or draft.dtype != torch.int64):
+            raise ValueError(f"draft must be int64 [{B}, 1+n] with n >= 1, got {draft.dtype} {tuple(draft.shape)}")
         if in_dev.type == "cpu":                  # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft)
 
     def _greedy_options(self, B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg=None):
         """The option arguments of the greedy calls (rg: the ragged batch, or None) -> _CallOptions"""
@@ -1117,22 +1149,54 @@ class GitCaptioner(_NativeModule):
                 chunk, cc = self._pack_to_device(parts[b0:b0 + step], raw), counts[b0:b0 + step]
                 yield (b0, len(cc), max(cc)) + tuple(chunk.shape[1:3]) + (chunk,)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False, opts=None, rg=None):
+    def _draft_call(self, name, head, mid, draft, max_len, mode, ids, steps, lp=None, opts=None) -> dict:
+        """One of the two draft entry points (``head`` / ``mid`` = the arguments in front of the draft's / between the stop rule
+        and ids_out); ``draft`` int64 [B, 1+n] on either device, trimmed to max_len columns beyond CLS.  -> what the call
+        offered, accepted (summed over the clips) and decoded behind it; ``last_accepted`` = the clips' own numbers."""
+        B = ids.shape[0]
+        d = draft[:, :1 + max_len].to(self._dev).contiguous()
+        n = d.shape[1] - 1
+        acc = (ctypes.c_int32 * B)(*([-1] * B))
+        before = self.draft_stats()
+        (opts or _CallOptions(self)).attach(lp)
+        self._call(name, *head, _lib.ptr(d), n + 1, n, max_len, mode, *mid, _lib.ptr(ids), _lib.ptr(steps), acc, self._stream())
+        after = self.draft_stats()
+        self.last_accepted = torch.tensor(list(acc), dtype=torch.int32)
+        return dict(draft_tokens=after[1] - before[1], accepted=after[2] - before[2], tail_steps=after[3] - before[3])
+
+    def draft_stats(self):
+        """gitcap_draft_stats: (draft calls, tokens offered, tokens accepted -- both summed over the clips --, tail steps)."""
+        out = (ctypes.c_int64 * 4)()
+        self._call("gitcap_draft_stats", out)
+        return tuple(int(v) for v in out)
+
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, opts=None, rg=None, draft=None):
         """rg: the (clips, counts, raw) of a ragged batch (src is then unused): each chunk of at most max_batch clips is packed
-        and runs with its counts attached."""
+        and runs with its counts attached.  draft: greedy_decode's (fp32 frames; camera frames are decoded by the plain call)."""
         self._drain()
         opts = opts or _CallOptions(self)
         if rg is None:
             fr, raw = self._check_frames(src)     # raw: camera frames [B,F,H,W,3] uint8 BGR, transform fused into the patch gather
         else:
             fr, raw, src = None, rg[2], rg[0][0]  # (src: where the results go)
-        outs, steps_all, lps = [], [], []
+        if draft is not None and raw:
+            raise ValueError("draft= takes transformed fp32 frames (there is no draft form of the camera-frame call)")
+        outs, steps_all, lps, accepted = [], [], [], []
+        # (a batch of several chunks stops by the rule over the WHOLE batch, below: its chunks decode every step)
+        dmode = mode if draft is None or (len(rg[1]) if rg is not None else fr.shape[0]) <= self.max_batch else STOP_NEVER
         with torch.cuda.device(self._dev):
             for b0, nb, F, fh, fw, chunk in self._chunks(fr, rg):
                 ids = torch.empty((nb, max_len + 1), dtype=torch.int64, device=self._dev)
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
                 if want_lp:
                     lps.append(torch.empty((nb, max_len), dtype=torch.float32, device=self._dev))
+                if draft is not None:
+                    self._draft_call("gitcap_greedy_draft", (_lib.ptr(chunk), nb, F), (), draft[b0:b0 + nb], max_len, dmode, ids, steps,
+                                     lps[-1] if want_lp else None, opts.rows(b0, b0 + nb))
+                    accepted.append(self.last_accepted)
+                    outs.append(ids)
+                    steps_all.append(steps)
+                    continue
                 opts.rows(b0, b0 + nb).attach(lps[-1] if want_lp else None)      # one-shot: consumed by the greedy call below
                 if raw:
                     self._call("gitcap_greedy_raw", _lib.ptr(chunk), nb, F, fh, fw, max_len, mode,
@@ -1143,6 +1207,8 @@ class GitCaptioner(_NativeModule):
                 outs.append(ids)
                 steps_all.append(steps)
         self._last_memory = None
+        if accepted:
+            self.last_accepted = torch.cat(accepted)
         ids = torch.cat(outs, 0)
         if mode == STOP_ALL_SEP:
             if len(outs) == 1:
@@ -1562,7 +1628,8 @@ class GitCaptioner(_NativeModule):
                        visual_features: bool = False, gate=None, logprobs: bool = False, num_keep_best: int = 1,
                        repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                        top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-                       prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> CaptionStream:
+                       prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+                       carry: bool = False) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1575,7 +1642,13 @@ class GitCaptioner(_NativeModule):
         seed (beam streams only) as in infer: every caption samples with `seed` (seed=None: a fresh one per caption from torch's
         global CPU generator); ``stream.last_seed`` is the seed of the caption the last push returned.  prompt / prompt_lengths (as
         in greedy_decode / infer): the stream's prompt, one row per clip, attached again for every caption.  no_repeat_ngram_size /
-        min_length / suppress_tokens (as in greedy_decode / infer): the stream's constraints, attached again for every caption."""
+        min_length / suppress_tokens (as in greedy_decode / infer): the stream's constraints, attached again for every caption.
+        ``carry`` (greedy streams without prompt or constraints): the previous caption is the draft of the next window call
+        (greedy_decode's ``draft``): the same captions; ``stream.stats()`` tells how much of the drafts was accepted."""
+        if carry and beam_size is not None:
+            raise ValueError("carry=True is for greedy streams (beam_size=None)")
+        if carry and (prompt is not None or no_repeat_ngram_size or min_length or suppress_tokens is not None):
+            raise ValueError("carry=True is not combined with prompt= or the constraint arguments")
         if logprobs and beam_size is not None:
             raise ValueError("logprobs=True is for greedy streams (the beam-search dict carries its own sequence score)")
         window = int(window or max(1, self.cfg.num_frames))
@@ -1608,7 +1681,7 @@ class GitCaptioner(_NativeModule):
                                1 if beam_size is None else beam_size * per_node_beam_size)
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
                              logprobs, num_keep_best, repetition_penalty,
-                             sampling, pr, co)
+                             sampling, pr, co, carry)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip
@@ -1663,3 +1736,20 @@ class GitCaptioner(_NativeModule):
         n = ctypes.c_int64()
         self._lib.gitcap_workspace_bytes(self._handle, ctypes.byref(n))
         return n.value
+
+
+@torch.no_grad()
+def draft_and_verify(teacher: GitCaptioner, student, src: torch.Tensor, max_len: int = 20, student_src: Optional[torch.Tensor] = None,
+                     **greedy_kw) -> dict:
+    """Student drafts, teacher verifies: the student (a StudentCaptioner) captions ``src`` -- or ``student_src`` where its input
+    differs from the teacher's: frames of its encoder's size, or memory tokens [B, F, d_model] -- and the teacher's
+    greedy_decode(src, max_len, draft=that caption, **greedy_kw) verifies it.  -> dict(ids, draft, accepted[, logprobs]): ``ids``
+    (and ``logprobs`` with return_logprobs=True) are bit for bit the teacher's plain greedy_decode whatever the student wrote,
+    ``draft`` the student's caption, ``accepted`` int32 [B] the leading draft tokens the teacher kept per clip."""
+    draft = student.greedy_decode(src if student_src is None else student_src, max_len=min(max_len, student.max_text_len), stop="never")
+    out = teacher.greedy_decode(src, max_len=max_len, draft=draft, **greedy_kw)
+    ids, lp = out if isinstance(out, tuple) else (out, None)
+    res = dict(ids=ids, draft=draft, accepted=teacher.last_accepted)
+    if lp is not None:
+        res["logprobs"] = lp
+    return res
