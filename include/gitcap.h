@@ -334,6 +334,35 @@ int gitcap_draft_stats(const gitcap_t* h, int64_t* out4);
  * nothing and runs exactly the launches it ran before. */
 int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld);
 
+/* Top-k token alternatives per position (the `top_logprobs=k` of text-generation interfaces), without a logits tensor.  A ONE-SHOT
+ * attachment like gitcap_attach_token_logprobs: taken, and consumed whether the call succeeds or fails, by the next of gitcap_greedy,
+ * gitcap_greedy_raw, gitcap_greedy_submit, gitcap_greedy_raw_submit, gitcap_window_greedy and gitcap_score; k == 0 or a NULL pointer
+ * detaches.  The beam-search family leaves it pending.  gitcap_greedy_draft and gitcap_window_greedy_draft refuse it: the call
+ * consumes the attachment, launches nothing and returns GITCAP_ERR_ARG with a message that names it.
+ *   top_ids  device int64 [B][ld][k], top_lp device fp32 [B][ld][k], 1 <= k <= 32, ld >= max_len of a greedy call (ld >= T - 1 of
+ *            gitcap_score).  Entry [b][t][j] = the j-th best column of the distribution step t chose ids_out[b][t + 1] from, and its
+ *            natural-log probability; gitcap_score: position j of row r goes to [r][j][.] for j < T - 1, counted or not, like top1_ids.
+ *            Positions >= max_len (T - 1) are not written; positions >= *steps_out are unspecified.
+ * Order and ties: columns are ranked by (logit descending, column ascending), the arg-max launch's tie rule: rank 0 is the token
+ * the loop emitted (gitcap_score: top1_ids) and top_lp[..][0] compares == to its token log-probability (top1_lp).
+ * Padding: a rank the row cannot fill -- fewer than k columns with a logit above -inf (bans, a masked bias), or vocab_size < k --
+ *            holds id -1 and lp -inf.  NaN never appears for logits that are finite or -inf.
+ * With a prompt attached a forced position still reports the model's own ranks (and the prompt runs as forced steps); with
+ * constraints attached the step's banned columns never appear and the probabilities are those of the renormalised row; it
+ * combines with the frame-count and token log-probability attachments.  With or without it every id is the same.
+ * How: the head runs its three-partial form; a tile's arg-max partial is its best column, so the k best columns of a row lie in
+ * its k best tiles; one workgroup per row recomputes those k x 16 logits with the head's own MFMA chain (bit for bit the head's
+ * logits) and ranks them.  A row's values do not depend on the batch size or the entry point.
+ * Errors: GITCAP_ERR_ARG for k outside [1, 32], ld < 1, misaligned pointers; at the consuming call ld below the positions it
+ * writes gives GITCAP_ERR_ARG with nothing launched.  Memory: the first attach allocates the third partial per pipeline slot, as
+ * gitcap_attach_token_logprobs does, and nothing else; a handle that never attaches runs exactly the launches it ran before. */
+int gitcap_attach_top_logprobs(gitcap_t* h, int k, int64_t* top_ids, float* top_lp, int ld);
+/* debug hook (no handle): the three-partial head over X [M][ldx] (bf16) against W [ceil(V / 16) * 16][D] (bf16, or e4m3 codes with
+ * wscale; Wpk nullable: the fragment-major copy of gitcap_dbg_pack_frags), under ban_mask (nullable, uint16 [M][ld_mask]), then
+ * the k best columns of every row -> top_ids int64 / top_lp fp32 [M][k] as described above. */
+int gitcap_dbg_head_topk(const void* X, int ldx, int M, const void* W, const void* Wpk, const float* wscale, const float* bias, int V, int D,
+                         int k, const uint16_t* ban_mask, int ld_mask, int64_t* top_ids, float* top_lp, void* stream);
+
 /* Score GIVEN captions: the log-probability of every token of captions somebody else supplied (a ground truth, an n-best entry, a
  * sampled or carried caption), teacher-forced in one pass, without a logits tensor.
  *   ids   device int64 [rows][ld_ids], CLS first, T >= 2 columns used, ld_ids >= T; rows = B * beams, row r belongs to clip
@@ -1033,6 +1062,12 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4);
  * launched, attachment consumed).  The first attach allocates the third partial (sized as the arg-max partials, which covers
  * the verify pass's B * n_draft rows) and the handle's own [rows][max_len] staging the captured loops write. */
 int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld);
+/* gitcap_attach_top_logprobs for this handle: same layout ([B][ld][k]), order, tie rule and -1 / -inf padding.  One-shot; taken by
+ * the next of gitcap_student_greedy, gitcap_student_window_greedy and gitcap_student_score; gitcap_student_greedy_draft and
+ * gitcap_student_window_greedy_draft consume it and fail with GITCAP_ERR_ARG and a message that names it; beam search leaves it
+ * pending.  Needs finalized weights.  The captured token loop is keyed by k; the first attach allocates the third partial and the
+ * handle's own [rows][max_len][32] staging the captured loops write. */
+int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_ids, float* top_lp, int ld);
 /* gitcap_score over the student decoder's teacher-forced pass (the rows of gitcap_student_forward_decoder, after
  * gitcap_student_set_memory with `rows` rows): same semantics, outputs and ignore rules; no `beams` (candidates of one clip are
  * rows whose memory the caller repeated).  Checks: gitcap_student_forward_decoder's, plus T < 2, ld_ids < T, ld_lp < T - 1. */

@@ -202,6 +202,26 @@ int gitcap_dbg_vocab_head_score(const void* X, int ldx, const void* W, const flo
     const HeadTargets tg{targets, M, M, 0, tgt_logit};
     return dbg_vocab_head(dbg_head_args(X, ldx, W, wscale, bias, M, N, K, logits, amax_val, amax_idx, amax_sum), stream, &tg);
 }
+// launch_head_topk with its head (tests/test_top_logprobs_gpu.py): the LSE head over the M rows (ban_mask set: its BAN form), then
+// the k best columns of every row -> top_ids / top_lp [M][k].  W [ceil(V / 16) * 16][D] (bf16, or e4m3 codes with wscale), Wpk
+// nullable = its fragment-major copy.  No handle: the three partials are a stream-ordered allocation.
+int gitcap_dbg_head_topk(const void* X, int ldx, int M, const void* W, const void* Wpk, const float* wscale, const float* bias, int V, int D,
+                         int k, const uint16_t* ban_mask, int ld_mask, int64_t* top_ids, float* top_lp, void* stream) {
+    if (!X || !W || M <= 0 || V <= 0 || !head_topk_ok(D, wscale != nullptr) || (ban_mask && !ban_mask_ok(ban_mask, ld_mask, V)))
+        return GITCAP_ERR_ARG;
+    const size_t n = (size_t)M * ((V + 15) / 16);
+    float* part = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMallocAsync((void**)&part, 3 * n * 4, s) != hipSuccess) return GITCAP_ERR_NOMEM;
+    const HeadBan bn{ban_mask, ld_mask};
+    HeadTopkArgs a{};
+    a.X = (const bf16_t*)X; a.ldx = ldx; a.hw = HeadWeight{W, Wpk, wscale, bias, V, D};
+    a.val = part; a.idx = (int*)(part + n); a.sum = part + 2 * n; a.bn = ban_mask ? &bn : nullptr; a.run_head = true; a.M = M;
+    a.rows = M; a.T = 1; a.row_stride = 1; a.row_off = 0; a.k = k; a.top_ids = top_ids; a.top_lp = top_lp; a.ld = 1;
+    const hipError_t e = launch_head_topk(a, s);
+    (void)hipFreeAsync(part, s);
+    return dbg_rc(e);
+}
 // launch_score_final on caller-owned buffers: partials [rows * T][ntiles], tgt_logit [rows * T], ids [rows][ld_ids]
 int gitcap_dbg_score_final(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
                            const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,

@@ -676,14 +676,26 @@ int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
                                sl.amax_val, sl.amax_idx, sl.amax_sum, sl.score_buf, *q.score, s));
         return 0;
     }
-    if (q.lp_out && (!q.argmax_out || !sl.amax_sum)) return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities without their partials");
-    SkinnyArgs ha;      // amax_sum: the head's third partial -> the chosen token's log-probability (argmax_final)
-    const HeadRows hr = vocab_head_args(ha, HeadWeight{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D}, sl.xsb, rows, T,
-                                        q.all_positions && q.logits_out, q.logits_out, q.argmax_out ? sl.amax_val : nullptr,
-                                        q.argmax_out ? sl.amax_idx : nullptr, q.lp_out ? sl.amax_sum : nullptr);
+    if ((q.lp_out || q.topk.k) && (!q.argmax_out || !sl.amax_sum))
+        return fail(h, GITCAP_ERR_STATE, "text_forward: token log-probabilities or top-k alternatives without their partials");
+    SkinnyArgs ha;      // amax_sum: the head's third partial -> the chosen token's log-probability (argmax_final), the alternatives' (head_topk)
+    const HeadWeight hw{h->head_w.p, h->head_w.pk, h->head_w.scale, h->head_b, V, D};
+    const HeadRows hr = vocab_head_args(ha, hw, sl.xsb, rows, T, q.all_positions && q.logits_out, q.logits_out,
+                                        q.argmax_out ? sl.amax_val : nullptr, q.argmax_out ? sl.amax_idx : nullptr,
+                                        q.lp_out || q.topk.k ? sl.amax_sum : nullptr);
     {
         ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * ha.M * V * D, (ha.wscale ? 1.0 : 2.0) * V * D);
         HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s, nullptr, q.ban));     // ban (constrained greedy step): the BAN form of the head
+    }
+    // the model's own k best of the same row, whatever a prompt forces into the position: AHEAD of the arg-max launch, which may
+    // embed the next step's input rows over the head's (embed_next writes sl.xsb)
+    if (q.topk.k) {
+        HeadTopkArgs ta{};
+        ta.X = ha.X; ta.ldx = ha.ldx; ta.hw = hw; ta.val = sl.amax_val; ta.idx = sl.amax_idx; ta.sum = sl.amax_sum; ta.bn = q.ban;
+        ta.rows = rows; ta.T = 1; ta.row_stride = hr.am_stride; ta.row_off = hr.am_off;
+        ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
+        ProfScope ps(h, GITCAP_PROF_SKINNY, s, 2.0 * rows * q.topk.k * 16 * D, (hw.wscale ? 1.0 : 2.0) * rows * q.topk.k * 16 * D);
+        HIP_OK(h, launch_head_topk(ta, s));
     }
     if (q.argmax_out) {
         const NextEmbed ne{h->word, h->tpos, h->txt_lnw, h->txt_lnb, c.dec_ln_eps, D, c.vocab_size, t0 + 1, sl.xs, sl.xsb};
@@ -722,7 +734,7 @@ static int encode_sync(gitcap* h, FrameSrc src, int B, int F, float* visual_out,
 
 // What the entry points take of the pending attachments (CallScope, host_logic.h): taken parts are consumed whatever becomes of
 // the call; a call without an image pass of its own frames refuses frame counts (REFUSE_FC: cleared, and the call fails).
-constexpr unsigned TAKE_GREEDY = OPT_LP | OPT_PR | OPT_CO, TAKE_BEAM = OPT_SO | OPT_PR | OPT_CO;
+constexpr unsigned TAKE_GREEDY = OPT_LP | OPT_PR | OPT_CO | OPT_TK, TAKE_BEAM = OPT_SO | OPT_PR | OPT_CO;
 #define REFUSE_FC(h, who)                                                                    \
     CallScope opts_((h)->pending, (h)->call, 0, OPT_FC);                                     \
     if (opts_.refused) return fail(h, GITCAP_ERR_ARG, refused_message(who))
@@ -1253,6 +1265,7 @@ int gitcap_text_forward(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, i
 static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int ld, hipStream_t s, int t_first = 0,
                        const DraftTail* tail = nullptr) {
     const LpAttach& lp = h->call.lp;
+    const TopkAttach& tk = h->call.tk;                       // column t = the k best of the distribution step t chose from
     const PromptArgs* prompt = h->call.pr.ids ? &h->call.pr : nullptr;
     const bool chain = text_chain_ok(h, rows, 1);
     // (Round 6 folded the arg-max of step t into the q|k|v launch of step t + 1 for one / two rows -- one launch less per step, same
@@ -1272,6 +1285,7 @@ static int greedy_rows(gitcap* h, int rows, int max_len, int64_t* ids_out, int l
             HIP_OK(h, launch_ban_mask(ids_out, ld, rows, t + 1, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress,
                                       h->c.vocab_size, cur(h).ban_mask, bn.ld, s));
         q.ids = ids_out + t; q.t0 = q.step = t; q.argmax_out = ids_out + t + 1; q.lp_out = lp.p ? lp.p + t : nullptr;
+        if (tk.k) q.topk = TopkAttach{tk.k, tk.ids + (size_t)t * tk.k, tk.lp + (size_t)t * tk.k, tk.ld};
         q.pre_embedded = have_rows; q.embed_next = next;
         q.keep_len = tail && draft_keep_step(*tail, t) ? cur(h).keep_len : nullptr;
         if (const int rc = text_forward(h, q, s)) return rc;
@@ -1301,8 +1315,9 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
         // positions 0 .. min_len-1 are prompt in every row: one multi-position pass (its arg-max is step min_len-1's), where the
         // slot's row workspace holds B x min_len rows; the token loop goes on behind it.  Steps that write a position below the
         // longest prompt run the forced arg-max.
-        // (with constraints attached the prompt runs as forced steps: the one-pass plan is not combined with the ban mask)
-        const int P = (g_prompt_prefill && !h->call.co.on && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
+        // (with constraints attached the prompt runs as forced steps: the one-pass plan is not combined with the ban mask; with top-k
+        // alternatives attached too: every forced position reports the model's own ranks, which needs that position's head)
+        const int P = (g_prompt_prefill && !h->call.co.on && !h->call.tk.k && pr.min_len > 1 && (int64_t)B * pr.min_len <= sl.Mt) ? std::min(pr.min_len, max_len) : 1;
         int t_first = 0;
         if (P > 1) {
             if (lp.p) HIP_OK(h, hipMemset2DAsync(lp.p, (size_t)lp.ld * 4, 0, (size_t)(P - 1) * 4, B, s));    // forced positions: 0.0f
@@ -1412,8 +1427,11 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, unsigned 
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, "greedy: unknown stop rule");
     if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, "greedy: the attached prompt is longer than max_len");
     if (int rc = lp_check(h, "greedy", lp, max_len)) return rc;
+    if (int rc = tk_check(h, "greedy", h->call.tk, max_len)) return rc;
     if (int rc = cons_check(h, max_len, 1, "greedy")) return rc;
     if (opts.refused & OPT_FC) return fail(h, GITCAP_ERR_ARG, refused_message("window"));
+    if (opts.refused & OPT_TK)      // (the entry point's own name: what null_msg leads with, "greedy_draft" or "window_greedy_draft")
+        return fail(h, GITCAP_ERR_ARG, refused_message(std::string(null_msg, strcspn(null_msg, ":")).c_str(), OPT_TK));
     if (opts.refused) return fail(h, GITCAP_ERR_ARG, "greedy_draft: a prompt or constraints are attached, which a draft call does not take");
     return body();
 }
@@ -1423,7 +1441,7 @@ static int greedy_entry(gitcap* h, bool args_ok, const char* null_msg, unsigned 
 template <typename Prefix>
 static int greedy_draft_entry(gitcap* h, const char* null_msg, unsigned take, unsigned refuse, const Draft& d, int max_len, int stop,
                               int64_t* ids_out, int32_t* steps_out, hipStream_t s, Prefix prefix) {
-    return greedy_entry(h, true, null_msg, take, refuse | OPT_PR | OPT_CO, max_len, stop, ids_out, [&]() -> int {
+    return greedy_entry(h, true, null_msg, take, refuse | OPT_PR | OPT_CO | OPT_TK, max_len, stop, ids_out, [&]() -> int {
         if (!d.ids) return fail(h, GITCAP_ERR_ARG, "greedy_draft: null draft_ids");
         if (d.n < 1 || d.n > max_len || d.ld < d.n + 1)
             return fail(h, GITCAP_ERR_ARG, "greedy_draft: n_draft outside [1, max_len], or ld_draft < n_draft + 1");
@@ -1775,9 +1793,22 @@ int gitcap_attach_token_logprobs(gitcap_t* h, float* logprobs_out, int ld) {
     return 0;
 }
 
+int gitcap_attach_top_logprobs(gitcap_t* h, int k, int64_t* top_ids, float* top_lp, int ld) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attach_top_logprobs: null handle");
+    if (k == 0 || !top_ids || !top_lp) { h->pending.tk = TopkAttach{}; return 0; }
+    if (const char* bad = tk_attach_bad(k, top_ids, top_lp, ld)) return fail(h, GITCAP_ERR_ARG, std::string("attach_top_logprobs: ") + bad);
+    if (!head_topk_ok(h->c.dec_width, h->head_w.scale != nullptr)) return fail(h, GITCAP_ERR_ARG, "attach_top_logprobs: no top-k kernel for this decoder width");
+    GUARD(h);
+    if (int rc = ensure_amax_sum(h)) return rc;             // the head's third partial, per slot: all the feature allocates
+    h->pending.tk = TopkAttach{k, top_ids, top_lp, ld};
+    return 0;
+}
+
 int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beams, int T, const int32_t* lengths, int64_t ignore_id,
                  float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "score: null handle");
+    CallScope opts(h->pending, h->call, OPT_TK, 0);         // the top-k attachment is consumed, whatever becomes of the call
+    if (int rc = tk_check(h, "score", h->call.tk, T - 1)) return rc;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "score: weights not finalized");
     if (!h->slots[0].have) return fail(h, GITCAP_ERR_STATE, "score before encode/set_visual");
     if (T < 2 || ld_ids < T) return fail(h, GITCAP_ERR_ARG, "score: T < 2 (CLS and at least one token) or ld_ids < T");
@@ -1790,7 +1821,7 @@ int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beam
     if ((rc = ensure_amax_sum(h))) return rc;
     if (!sl.score_buf && (rc = dev_alloc(h, &sl.score_buf, 2 * (size_t)sl.Mt))) return rc;
     HIP_OK(h, join_async(h, (hipStream_t)stream));
-    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp, h->call.tk};
     TextReq q;
     q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.beams = beams; q.T = T; q.score = &sq;
     return text_forward(h, q, (hipStream_t)stream);

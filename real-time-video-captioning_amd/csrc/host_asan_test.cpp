@@ -75,7 +75,31 @@ static int call_opts_test() {
     return 0;
 }
 
+// top-k alternatives (OPT_TK): a part like the others -- taken by the greedy family and score, refused (and consumed) by a draft
+// call, left pending by the beam family
+static int topk_opts_test() {
+    float lp[1]; int64_t nb[1]; const int64_t ids[1] = {0}; const int32_t len[1] = {1};
+    const unsigned ALL = OPT_LP | OPT_SO | OPT_PR | OPT_CO | OPT_FC, GREEDY = OPT_LP | OPT_PR | OPT_CO, BEAM = OPT_SO | OPT_PR | OPT_CO;
+    {
+        int64_t tid[1]; float tlp[1];
+        CallOpts pending = all_attached(lp, nb, ids, len);
+        pending.tk = TopkAttach{8, tid, tlp, 20};
+        CHECK(opts_set(pending) == (ALL | OPT_TK));
+        unsigned refused = 0;
+        CallOpts got = take_opts(pending, BEAM, OPT_FC, &refused);                          // a window beam search
+        CHECK(refused == OPT_FC && got.tk.k == 0 && pending.tk.k == 8 && pending.tk.ids == tid && pending.tk.lp == tlp && pending.tk.ld == 20);
+        got = take_opts(pending, OPT_LP, OPT_PR | OPT_CO | OPT_TK, &refused);                // a draft call
+        CHECK(refused == OPT_TK && got.tk.k == 0 && got.lp.p == lp && pending.tk.k == 0 && opts_set(pending) == 0);
+        pending.tk = TopkAttach{2, tid, tlp, 4};
+        got = take_opts(pending, GREEDY | OPT_TK, 0, &refused);                              // a greedy call; score takes OPT_TK alone
+        CHECK(refused == 0 && got.tk.k == 2 && got.tk.ld == 4 && opts_set(pending) == 0);
+        CHECK(refused_message("greedy_draft", OPT_TK) == "greedy_draft: top-k alternatives are attached (gitcap_attach_top_logprobs), which this call does not take");
+    }
+    return 0;
+}
+
 int main() {
+    if (topk_opts_test()) return 1;
     // e4m3: every finite code round-trips through value -> exact code
     for (int code = 0; code < 256; ++code) {
         const float v = host_e4m3_value(code);

@@ -184,12 +184,15 @@ struct SearchOpt { int n = 1; float rp = 1.0f; int64_t* nbest = nullptr; float* 
 // gitcap_attach_constraints: what a step may not emit (include/gitcap.h); on = false: none
 struct ConsOpt { bool on = false; int ngram = 0, min_length = 0; const int32_t* suppress = nullptr; int n_suppress = 0; };
 
-struct CallOpts { LpAttach lp{}; SearchOpt so{}; PromptArgs pr{}; ConsOpt co{}; RaggedCounts fc{}; };
-enum : unsigned { OPT_LP = 1, OPT_SO = 2, OPT_PR = 4, OPT_CO = 8, OPT_FC = 16 };
+// top-k alternatives per position (*_attach_top_logprobs): device int64 / fp32 [B][ld][k]; k == 0: none
+struct TopkAttach { int k = 0; int64_t* ids = nullptr; float* lp = nullptr; int ld = 0; };
+
+struct CallOpts { LpAttach lp{}; SearchOpt so{}; PromptArgs pr{}; ConsOpt co{}; RaggedCounts fc{}; TopkAttach tk{}; };
+enum : unsigned { OPT_LP = 1, OPT_SO = 2, OPT_PR = 4, OPT_CO = 8, OPT_FC = 16, OPT_TK = 32 };
 
 inline unsigned opts_set(const CallOpts& o) {       // the parts that hold an attachment
     return (o.lp.p ? OPT_LP : 0u) | (o.so.n != 1 || o.so.rp != 1.0f || o.so.smp.on ? OPT_SO : 0u) | (o.pr.ids ? OPT_PR : 0u) |
-           (o.co.on ? OPT_CO : 0u) | (o.fc.B != 0 ? OPT_FC : 0u);
+           (o.co.on ? OPT_CO : 0u) | (o.fc.B != 0 ? OPT_FC : 0u) | (o.tk.k != 0 ? OPT_TK : 0u);
 }
 inline void opts_clear(CallOpts& o, unsigned parts) {
     if (parts & OPT_LP) o.lp = LpAttach{};
@@ -197,6 +200,7 @@ inline void opts_clear(CallOpts& o, unsigned parts) {
     if (parts & OPT_PR) o.pr = PromptArgs{};
     if (parts & OPT_CO) o.co = ConsOpt{};
     if (parts & OPT_FC) o.fc.B = 0;
+    if (parts & OPT_TK) o.tk = TopkAttach{};
 }
 // The parts in `take` move out of `pending` into the result (consumed, whatever becomes of the call); the parts in `refuse` are
 // cleared, *refused = those of them that held an attachment; every other part stays pending.
@@ -216,8 +220,11 @@ struct CallScope {
     CallScope(const CallScope&) = delete;
     CallScope& operator=(const CallScope&) = delete;
 };
-// the message of a call that refuses an attachment (only frame counts are ever refused)
-inline std::string refused_message(const char* who) {
+// the message of a call that refuses an attachment: frame counts (the default: what most refusals are about), or the top-k
+// alternatives a draft call does not carry; names the attachment and its setter
+inline std::string refused_message(const char* who, unsigned part = OPT_FC) {
+    if (part & OPT_TK)
+        return std::string(who) + ": top-k alternatives are attached (gitcap_attach_top_logprobs), which this call does not take";
     return std::string(who) + ": per-clip frame counts are attached (gitcap_attach_frame_counts), which this call does not take";
 }
 

@@ -99,6 +99,19 @@ int lp_check(H* h, const char* who, const LpAttach& lp, int max_len) {
     return 0;
 }
 
+// The attachment of *_attach_top_logprobs (TopkAttach, host_logic.h): the setter's argument check (0 = fine; a clearing call never
+// gets here), and the taking call's check of the row pitch against the positions it writes.
+inline const char* tk_attach_bad(int k, const int64_t* ids, const float* lp, int ld) {
+    if (k < 1 || k > 32) return "k outside [1, 32]";
+    if (ld < 1 || ((uintptr_t)ids & 7) != 0 || ((uintptr_t)lp & 3) != 0) return "ld < 1 or a misaligned pointer";
+    return nullptr;
+}
+template <class H>
+int tk_check(H* h, const char* who, const TopkAttach& tk, int positions) {
+    if (tk.k && tk.ld < positions) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": the attached top-k buffers have ld < the positions the call writes");
+    return 0;
+}
+
 // Ordering of a window ring's pushes and reads, whichever streams they are issued on: a push waits for the last read and the
 // last push (they share the staging rows) and records the ring event; a read waits for the ring event and records the read event.
 struct RingOrder {

@@ -143,6 +143,31 @@ inline HeadRows vocab_head_args(SkinnyArgs& ha, const HeadWeight& hw, const bf16
     }
     return r;
 }
+// ---- top-k alternatives of a head row (gitcap_attach_top_logprobs; skinny.hip: head_topk_kernel) --------------------------------
+// Columns are ordered by (logit descending, column ascending), launch_argmax_final's tie rule.  A tile's arg-max partial is its
+// best column under that order, the representatives of different tiles are different columns, and a column among the row's k best
+// has its tile's representative ahead of it: the k best columns lie in the k best tiles by (val, idx).  One workgroup per output
+// row picks those tiles from the row's partials, recomputes their 16 logits each with the head's own MFMA chain over the head's
+// operands (the head's bits; bias added, banned columns -inf, columns >= V no candidates) and ranks the candidates:
+//     top_ids[j] = the j-th best column, top_lp[j] = (logit - M) - log(z), M and z the row's maximum and merged sum as
+//     lp_partials forms them: rank 0 is launch_argmax_final's token and compares == to its log-probability.
+// Ranks the row cannot fill (fewer than k columns above -inf) hold id -1 and lp -inf.  1 <= k <= HEAD_TOPK_MAX.
+// Output row i < rows * T reads head row m = (i / T) * row_stride + row_off + i % T (X + m * ldx, partials and mask row m) and
+// writes k entries at ((i / T) * ld + i % T) * k: T = 1 with launch_argmax_final's row map for a token step, T = positions - 1
+// and row_stride = positions for a scoring pass.  A row's output does not depend on the rows beside it.
+// run_head: the launcher first runs the LSE head (with bn its BAN form) over the M head rows into val / idx / sum.
+constexpr int HEAD_TOPK_MAX = 32;
+struct HeadTopkArgs {
+    const bf16_t* X; int ldx;
+    HeadWeight hw;
+    float* val; int* idx; float* sum;       // [head rows][ceil(V / 16)]
+    const HeadBan* bn;                      // nullable: the mask the head ran under (head row m = mask row m)
+    bool run_head; int M;                   // run_head: the head rows of the launch
+    int rows, T, row_stride, row_off;
+    int k; int64_t* top_ids; float* top_lp; int ld;
+};
+bool head_topk_ok(int D, bool fp8);                          // widths the kernel is instantiated for (launch_skinny's)
+hipError_t launch_head_topk(const HeadTopkArgs& a, hipStream_t s);
 // Teacher-forced scoring of given captions ids [rows][ld_ids] (CLS first) from the head's partials of all rows x T positions
 // (row m = r * T + j) and the target logits the scoring head captured (HeadTargets with shift 1).  Position (r, j), j < T - 1,
 // is counted unless its target y = ids[r][j + 1] lies outside [0, V), equals ignore_id, or lengths (nullable, device) has
@@ -156,7 +181,9 @@ hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const 
                               const ScoreOut& o, hipStream_t s);
 // The scoring head over the bf16 rows xb [rows * T][D] + launch_score_final (host only; what gitcap_score / gitcap_student_score
 // run behind their decoder stacks).  scratch: fp32 [2][rows * T] = the target logits, then the lp rows where the caller wants none.
-struct ScoreReq { const int32_t* lengths; int64_t ignore_id; float* token_lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; };
+// topk (k != 0; gitcap_attach_top_logprobs): also the k best columns of positions 0 .. T - 2 of every row, counted or not, to
+// topk.ids / topk.lp [rows][topk.ld][k] (launch_head_topk over the same partials: rank 0 = top1_ids / top1_lp bit for bit).
+struct ScoreReq { const int32_t* lengths; int64_t ignore_id; float* token_lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; TopkAttach topk{}; };
 inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int64_t* ids, int ld_ids, int rows, int T, float* amax_val,
                                int* amax_idx, float* amax_sum, float* scratch, const ScoreReq& q, hipStream_t s) {
     SkinnyArgs ha;
@@ -165,7 +192,13 @@ inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int
     hipError_t e = launch_skinny(ha, SK_BIAS_F32, s, &tg);
     if (e != hipSuccess) return e;
     const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
-    return launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
+    e = launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
+    if (e != hipSuccess || !q.topk.k) return e;
+    HeadTopkArgs ta{};
+    ta.X = xb; ta.ldx = hw.D; ta.hw = hw; ta.val = amax_val; ta.idx = amax_idx; ta.sum = amax_sum;
+    ta.rows = rows; ta.T = T - 1; ta.row_stride = T; ta.row_off = 0;
+    ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
+    return launch_head_topk(ta, s);
 }
 // One pass of a handle's decoder stack over text rows, and what its vocabulary head produces (host only; the request of both
 // handles' text_forward, gitcap.hip and student.hip -- the teacher's TextReq adds what only its stack takes).
@@ -178,6 +211,9 @@ struct RowsReq {
     int32_t* sep_cnt = nullptr; int step = 0;       // launch_argmax_final's
     float* lp_out = nullptr; int ld_lp = 0;         // nullable, needs argmax_out: the token's log-probability
     const ScoreReq* score = nullptr;                // nullable: all positions through launch_score instead
+    // k != 0, needs argmax_out: the k best columns of the row the arg-max reads (launch_head_topk behind the arg-max launch; the head
+    // runs its LSE form); ids / lp point at this position's entries of row 0, ld = the row pitch in positions
+    TopkAttach topk{};
 };
 // ---- teacher-student divergence (gitcap_distill): both vocabulary heads over the same tiles, then one merge -------------------
 // launch_head_dual (skinny.hip: skinny_head_dual_kernel): the teacher's rows Xt [M][ldxt] against wt (bf16, or e4m3 codes with

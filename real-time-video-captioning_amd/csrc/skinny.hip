@@ -28,6 +28,7 @@
 // serial row loop cost more than the launch.)
 #include "kernels.h"
 #include "rowln.h"
+#include "lp_partials.h"
 
 namespace {
 
@@ -582,6 +583,134 @@ hipError_t launch_dual(const DualHeadArgs& a, const int ntiles, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- top-k alternatives of a head row (kernels.h: HeadTopkArgs) -----------------------------------------------------------------
+// One 256-thread workgroup per output row, behind the LSE head that left the row's three partials.
+//   1. the row's bf16 activations and (up to TOPK_PART tiles; beyond that they are read from L2 every round) its arg-max partials go
+//      to LDS; k rounds pick the k best tiles by (val descending, idx ascending): round r takes the best tile strictly behind round
+//      r - 1's pick -- the pairs of non-empty tiles are all different -- and the rounds end early where no tile is left.  Empty tiles
+//      (idx 0x7fffffff) are never picked.
+//   2. lp_partials: the row's -log(z) against M = round 0's val, the winner's logit.
+//   3. the four waves walk the picked tiles: load_wfrags, then skinny_head_body's chain -- the weight fragments in the A operand,
+//      the row in all 16 columns of the B operand (an MFMA output element depends on its own A row and B column alone: the head's
+//      bits, whatever the head's m-tile held beside this row) -- bias, the ban word of (row, tile), columns >= V as -inf; the lanes
+//      of B column 0 leave the 16 logits in LDS.
+//   4. every candidate above -inf counts the candidates ahead of it under (logit descending, column ascending); a rank below k
+//      writes its column and (logit - M) + (-log z).  Ranks nobody takes keep -1 / -inf.
+struct HeadTopkK {
+    const bf16_t* X; int ldx;
+    const void *W, *Wpk; const float *wscale, *bias; int V;
+    const float* val; const int* idx; const float* sum; int ntiles;
+    const uint16_t* mask; int ld_mask;
+    int T, row_stride, row_off, k;
+    int64_t* top_ids; float* top_lp; int ld;
+};
+constexpr int TOPK_PART = 2048;
+template <int K32, bool FP8>
+__global__ __launch_bounds__(256) void head_topk_kernel(const HeadTopkK a) {
+    __shared__ __attribute__((aligned(16))) bf16_t xrow[K32 * 32];
+    __shared__ float pv[TOPK_PART];
+    __shared__ int pi[TOPK_PART];
+    __shared__ float sv[2][4], ss[4], lpw_s, olp[HEAD_TOPK_MAX];
+    __shared__ int si[2][4], sel_col[HEAD_TOPK_MAX], oid[HEAD_TOPK_MAX];
+    __shared__ __attribute__((aligned(16))) float cand[HEAD_TOPK_MAX * 16];
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int orow = blockIdx.x / a.T, opos = blockIdx.x - orow * a.T;
+    const size_t m = (size_t)orow * a.row_stride + a.row_off + opos;
+    const size_t base = m * a.ntiles;
+    const int ntiles = a.ntiles, k = a.k;
+    if (tid < K32 * 4) *(u32x4*)(&xrow[tid * 8]) = *(const u32x4*)(a.X + m * a.ldx + tid * 8);
+    const bool part_lds = ntiles <= TOPK_PART;
+    if (part_lds)
+        for (int i = tid; i < ntiles; i += 256) { pv[i] = a.val[base + i]; pi[i] = a.idx[base + i]; }
+    if (tid < HEAD_TOPK_MAX) { oid[tid] = -1; olp[tid] = -INFINITY; }
+    __syncthreads();
+    // 1. the k best tiles
+    float pval = INFINITY, rowmax = -INFINITY;
+    int pidx = -1, nsel = 0;
+    for (int r = 0; r < k; ++r) {
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = tid; i < ntiles; i += 256) {
+            const float v = part_lds ? pv[i] : a.val[base + i];
+            const int c = part_lds ? pi[i] : a.idx[base + i];
+            const bool behind = v < pval || (v == pval && c > pidx);
+            if (c != 0x7fffffff && behind && (v > best || (v == best && c < bi))) { best = v; bi = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(best, o);
+            const int i2 = __shfl_xor(bi, o);
+            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+        }
+        if (lane == 0) { sv[r & 1][wave] = best; si[r & 1][wave] = bi; }
+        __syncthreads();                                         // (round r + 2 reuses this pair behind round r + 1's barrier)
+        best = sv[r & 1][0];
+        bi = si[r & 1][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (sv[r & 1][w] > best || (sv[r & 1][w] == best && si[r & 1][w] < bi)) { best = sv[r & 1][w]; bi = si[r & 1][w]; }
+        if (bi == 0x7fffffff) break;                             // (uniform) no tile left
+        pval = best;
+        pidx = bi;
+        if (r == 0) rowmax = best;
+        if (tid == 0) sel_col[r] = min(max(bi, 0) >> 4, ntiles - 1) << 4;     // (a partial is a column < V: the clamp never acts)
+        nsel = r + 1;
+    }
+    // 2. -log z of the row (one barrier inside: sel_col and xrow are visible behind it)
+    const float lpw0 = lp_partials(a.val, a.sum, base, ntiles, rowmax, ss);
+    if (tid == 0) lpw_s = lpw0;
+    // 3. the picked tiles' logits
+    for (int t = wave; t < nsel; t += 4) {
+        const int n0 = sel_col[t];
+        bf16x8 wf[K32];
+        load_wfrags<K32, FP8>(a.W, a.Wpk, a.wscale, (size_t)(n0 + frow), K32 * 32, fq * 8, wf);
+        const unsigned bw = a.mask ? a.mask[m * a.ld_mask + (n0 >> 4)] : 0u;
+        const int n = n0 + fq * 4;
+        float bias[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias[r] = (a.bias && n + r < a.V) ? a.bias[n + r] : 0.f;
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < K32; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kk], *(const bf16x8*)(&xrow[fq * 8 + kk * 32]), acc, 0, 0, 0);
+        f32x4 y;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) y[r] = (n + r >= a.V || ((bw >> (fq * 4 + r)) & 1u)) ? -INFINITY : acc[r] + bias[r];
+        if (frow == 0) *(f32x4*)(&cand[t * 16 + fq * 4]) = y;
+    }
+    __syncthreads();
+    // 4. rank the candidates
+    const int ncand = nsel * 16;
+    const float lpw = lpw_s;
+    for (int q = tid; q < ncand; q += 256) {
+        const float v = cand[q];
+        const int c = sel_col[q >> 4] + (q & 15);
+        if (!(v > -INFINITY)) continue;
+        int rank = 0;
+        for (int p = 0; p < ncand; p += 4) {
+            const f32x4 o = *(const f32x4*)(&cand[p]);
+            const int c0 = sel_col[p >> 4] + (p & 15);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) rank += (o[u] > v || (o[u] == v && c0 + u < c)) ? 1 : 0;
+        }
+        if (rank < k) { oid[rank] = c; olp[rank] = (v - rowmax) + lpw; }
+    }
+    __syncthreads();
+    if (tid < k) {
+        const size_t o = ((size_t)orow * a.ld + opos) * k + tid;
+        a.top_ids[o] = oid[tid];
+        a.top_lp[o] = olp[tid];
+    }
+}
+
+template <int K32, bool FP8>
+hipError_t launch_topk(const HeadTopkK& kk, int nrows, hipStream_t s) {
+    hipLaunchKernelGGL((head_topk_kernel<K32, FP8>), dim3(nrows), dim3(256), 0, s, kk);
+    return hipGetLastError();
+}
+
 // ---- one/two-row prologue over many slabs: three waves share the reduce ---------------------------------------------------
 // The fused FFN launch (ffn_txt.hip) leaves dec_ffn / 64 = 48 slabs; the single wave of skinny_full<LNR> walks them in three
 // dependent round trips (two 8-slab groups each) before it can normalise its row -- in every one of the 144 workgroups, 150
@@ -845,6 +974,44 @@ hipError_t launch_skinny_splitk(const SkinnyArgs& a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+bool head_topk_ok(int D, bool fp8) {
+    const int k32 = D / 32;
+    if (D % 32) return false;
+    return fp8 ? (k32 == 4 || k32 == 24) : skinny_full_ok(D);
+}
+
+hipError_t launch_head_topk(const HeadTopkArgs& a, hipStream_t s) {
+    const int V = a.hw.V, D = a.hw.D, ntiles = (V + 15) / 16;
+    const bool fp8 = a.hw.wscale != nullptr;
+    if (!a.X || !a.hw.W || !a.val || !a.idx || !a.sum || !a.top_ids || !a.top_lp || V <= 0 || !head_topk_ok(D, fp8) ||
+        a.k < 1 || a.k > HEAD_TOPK_MAX || a.rows <= 0 || a.T <= 0 || a.ld < a.T || a.row_stride < 0 || a.row_off < 0 ||
+        a.ldx < D || a.ldx % 8 || ((uintptr_t)a.X & 15) || ((uintptr_t)a.top_ids & 7) || ((uintptr_t)a.top_lp & 3))
+        return hipErrorInvalidValue;
+    if (a.bn && (!a.bn->mask || a.bn->ld < ntiles)) return hipErrorInvalidValue;
+    if (a.run_head) {
+        // the last head row an output row reads lies inside the launch
+        if (a.M <= 0 || (int64_t)(a.rows - 1) * a.row_stride + a.row_off + a.T - 1 >= a.M) return hipErrorInvalidValue;
+        SkinnyArgs ha{};
+        ha.X = a.X; ha.ldx = a.ldx; ha.W = a.hw.W; ha.Wpk = a.hw.Wpk; ha.wscale = a.hw.wscale; ha.bias = a.hw.bias;
+        ha.M = a.M; ha.N = V; ha.K = D; ha.ldo = V; ha.T = 1; ha.row_stride = 1;
+        ha.amax_val = a.val; ha.amax_idx = a.idx; ha.amax_sum = a.sum;
+        const hipError_t e = launch_skinny(ha, SK_BIAS_F32, s, nullptr, a.bn);
+        if (e != hipSuccess) return e;
+    }
+    const HeadTopkK kk{a.X, a.ldx, a.hw.W, a.hw.Wpk, a.hw.wscale, a.hw.bias, V, a.val, a.idx, a.sum, ntiles,
+                       a.bn ? a.bn->mask : nullptr, a.bn ? a.bn->ld : 0, a.T, a.row_stride, a.row_off, a.k, a.top_ids, a.top_lp, a.ld};
+    const int nrows = a.rows * a.T;
+    if (fp8) return D == 128 ? launch_topk<4, true>(kk, nrows, s) : launch_topk<24, true>(kk, nrows, s);
+    switch (D / 32) {
+        case 2: return launch_topk<2, false>(kk, nrows, s);
+        case 4: return launch_topk<4, false>(kk, nrows, s);
+        case 8: return launch_topk<8, false>(kk, nrows, s);
+        case 18: return launch_topk<18, false>(kk, nrows, s);
+        case 24: return launch_topk<24, false>(kk, nrows, s);
+        default: return launch_topk<32, false>(kk, nrows, s);
+    }
 }
 
 bool head_dual_ok(int Kt, int Ks) { return (Kt == 128 && Ks == 64) || ((Kt == 768 || Kt == 1024) && Ks == 576); }

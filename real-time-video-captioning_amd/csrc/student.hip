@@ -192,7 +192,7 @@ struct gitcap_student : HandleCore {
     // key: stop = a stop rule -> execs[0] the whole greedy loop; TAIL_STEPS -> execs[t - 1] token step t of the draft path, t >= 1
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; std::vector<hipGraphExec_t> execs; };
+    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none)
     static constexpr int TAIL_STEPS = -1;
     std::vector<Graphs> graphs;
     // draft verification (gitcap_student_*_greedy_draft): acc_tok / acc_ticket = draft_accept_kernel's scratch, acc_host = its
@@ -207,6 +207,11 @@ struct gitcap_student : HandleCore {
     LpAttach lp_attach{};
     float *amax_sum = nullptr, *g_lp = nullptr;
     int* acc_lp = nullptr;
+    // top-k alternatives (gitcap_student_attach_top_logprobs): tk_attach = the pending one-shot attachment; the first attach allocates
+    // amax_sum and g_tk_ids / g_tk_lp, the handle's own [B][max_len][k] rows the captured loops write (copied out like g_lp)
+    TopkAttach tk_attach{};
+    int64_t* g_tk_ids = nullptr;
+    float* g_tk_lp = nullptr;
     float* score_buf = nullptr;         // gitcap_student_score (first use): [2][Mt] target logits, lp rows the caller did not ask for
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
@@ -347,10 +352,12 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
         return 0;
     }
     // vocabulary head: all positions when logits are requested, else the last position of every row
-    if (q.lp_out && (!q.argmax_out || !h->amax_sum)) return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities without their partials");
+    if ((q.lp_out || q.topk.k) && (!q.argmax_out || !h->amax_sum))
+        return fail(h, GITCAP_ERR_STATE, "student: token log-probabilities or top-k alternatives without their partials");
     SkinnyArgs ha;
     const HeadRows hr = vocab_head_args(ha, head_weight(h), h->xb, rows, T, q.logits_out != nullptr, q.logits_out,
-                                        q.argmax_out ? h->amax_val : nullptr, q.argmax_out ? h->amax_idx : nullptr, q.lp_out ? h->amax_sum : nullptr);
+                                        q.argmax_out ? h->amax_val : nullptr, q.argmax_out ? h->amax_idx : nullptr,
+                                        q.lp_out || q.topk.k ? h->amax_sum : nullptr);
     HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
     if (q.argmax_out) {
         ArgmaxArgs a{};
@@ -359,6 +366,13 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
         a.out = q.argmax_out; a.ld_out = q.ld_argmax; a.sep_cnt = q.sep_cnt; a.step = q.step; a.sep_id = c.sep_token_id;
         a.lp_out = q.lp_out; a.ld_lp = q.ld_lp;
         HIP_OK(h, launch_argmax_final(a, s));
+    }
+    if (q.topk.k) {     // the k best of the row the arg-max read, from the same partials
+        HeadTopkArgs ta{};
+        ta.X = ha.X; ta.ldx = ha.ldx; ta.hw = head_weight(h); ta.val = h->amax_val; ta.idx = h->amax_idx; ta.sum = h->amax_sum;
+        ta.rows = rows; ta.T = 1; ta.row_stride = hr.am_stride; ta.row_off = hr.am_off;
+        ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
+        HIP_OK(h, launch_head_topk(ta, s));
     }
     return 0;
 }
@@ -546,13 +560,15 @@ namespace {
 const bool g_use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP_STUDENT_GRAPH")) == 0);
 
 // Token step t of the greedy loop (model.py:173-182) on the handle's id rows: position t in, the arg-max as token t + 1 (and, with
-// want_lp, its log-probability as column t of g_lp).  The full loop, the captured tail steps and the un-graphed tail are this call.
-int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q) {
+// want_lp, its log-probability as column t of g_lp; with tk != 0 the tk best of that distribution as entry t of g_tk_ids / g_tk_lp).
+// The full loop, the captured tail steps and the un-graphed tail are this call.
+int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q, int tk = 0) {
     const int ld = max_len + 1;
     TextReq r;
     r.ids = h->g_ids; r.ld_ids = ld; r.rows = B; r.t0 = r.step = t; r.T = 1;
     r.argmax_out = h->g_ids + t + 1; r.ld_argmax = ld; r.sep_cnt = h->sep_cnt;
     r.lp_out = want_lp ? h->g_lp + t : nullptr; r.ld_lp = max_len;
+    if (tk) r.topk = TopkAttach{tk, h->g_tk_ids + (size_t)t * tk, h->g_tk_lp + (size_t)t * tk, max_len};
     return text_forward(h, r, q);
 }
 
@@ -578,13 +594,13 @@ int capture(gitcap_student* h, const char* what, Enqueue enqueue, hipGraphExec_t
 // The executables of a key, captured by fill(execs) at the key's first use; a failed fill caches nothing.  Weight and workspace
 // pointers are baked into the nodes (destroy_graphs at every finalize).
 template <typename Fill>
-int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, Fill fill, const std::vector<hipGraphExec_t>** out) {
+int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, Fill fill, const std::vector<hipGraphExec_t>** out) {
     for (auto& g : h->graphs)
-        if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp) {
+        if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp && g.tk == tk) {
             *out = &g.execs;
             return 0;
         }
-    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, {}};
+    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, {}};
     if (int rc = fill(g.execs)) {
         for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
         return rc;
@@ -596,7 +612,13 @@ int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_l
 
 // the handle's ids [B][max_len + 1], steps and (lp.p set) log-probabilities [B][max_len] -> the caller's buffers; the columns of
 // lp.p behind max_len (row pitch lp.ld) are not touched
-int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* steps_out, const LpAttach& lp, hipStream_t s) {
+int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* steps_out, const LpAttach& lp, hipStream_t s,
+             const TopkAttach& tk = TopkAttach{}) {
+    if (tk.k) {         // [B][max_len][k] -> the caller's [B][tk.ld][k]; the positions behind max_len are not touched
+        const size_t w = (size_t)max_len * tk.k;
+        HIP_OK(h, hipMemcpy2DAsync(tk.ids, (size_t)tk.ld * tk.k * 8, h->g_tk_ids, w * 8, w * 8, (size_t)B, hipMemcpyDeviceToDevice, s));
+        HIP_OK(h, hipMemcpy2DAsync(tk.lp, (size_t)tk.ld * tk.k * 4, h->g_tk_lp, w * 4, w * 4, (size_t)B, hipMemcpyDeviceToDevice, s));
+    }
     HIP_OK(h, hipMemcpyAsync(ids_out, h->g_ids, (size_t)B * (max_len + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     if (steps_out) HIP_OK(h, hipMemcpyAsync(steps_out, h->g_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (lp.p)
@@ -606,20 +628,21 @@ int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* s
 
 // the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
 // lp.p set: the loop with token log-probabilities (a graph of its own; column t of g_lp = step t's)
-int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s, const LpAttach& lp) {
+int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s, const LpAttach& lp,
+                const TopkAttach& tk) {
     const bool want_lp = lp.p != nullptr;
     int rc;
     auto enqueue_loop = [&](hipStream_t q) -> int {
         HIP_OK(h, launch_fill_i64(h->g_ids, max_len + 1, B, h->c.cls_token_id, q));        // model.py:171
         HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
         for (int t = 0; t < max_len; ++t)                                                    // model.py:173-182
-            if (int r = token_step(h, B, t, max_len, want_lp, q)) return r;
+            if (int r = token_step(h, B, t, max_len, want_lp, q, tk.k)) return r;
         HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
         return 0;
     };
     if (g_use_graph) {
         const std::vector<hipGraphExec_t>* loop = nullptr;
-        rc = captured_graphs(h, B, max_len, stop, want_lp, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, stop, want_lp, tk.k, [&](std::vector<hipGraphExec_t>& execs) {
             execs.push_back(nullptr);
             return capture(h, "student greedy: capturing the token loop", enqueue_loop, &execs.back());
         }, &loop);
@@ -628,7 +651,7 @@ int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_ou
     } else if ((rc = enqueue_loop(s))) {
         return rc;
     }
-    return copy_out(h, B, max_len, ids_out, steps_out, lp, s);
+    return copy_out(h, B, max_len, ids_out, steps_out, lp, s, tk);
 }
 
 // ---- greedy decoding that verifies a draft caption ------------------------------------------------------------------------
@@ -652,7 +675,7 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
     const std::vector<hipGraphExec_t>* steps = nullptr;
     if (g_use_graph) {
-        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, 0, [&](std::vector<hipGraphExec_t>& execs) {
             for (int t = 1; t < max_len; ++t) {
                 execs.push_back(nullptr);
                 if (int r = capture(h, "student draft: capturing a token step", [&](hipStream_t q) { return token_step(h, B, t, max_len, want_lp, q); },
@@ -797,10 +820,13 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     const std::string w(who);
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
     const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});
+    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
+    if (draft && tk.k) return fail(h, GITCAP_ERR_ARG, refused_message(who, OPT_TK));       // (consumed above)
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
     if (int bad = lp_check(h, who, lp, max_len)) return bad;
+    if (int bad = tk_check(h, who, tk, max_len)) return bad;
     if (draft && !draft->ids) return fail(h, GITCAP_ERR_ARG, w + ": null draft_ids");
     if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
         return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
@@ -810,7 +836,7 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     if (int rc = window ? window_memory(h, who, 1, s) : set_memory(h, memory, B, s)) return rc;
     if (window) B = h->win_B;
     if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
 }
 
 }  // namespace
@@ -939,9 +965,30 @@ int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_ou
     return 0;
 }
 
+int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_ids, float* top_lp, int ld) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_top_logprobs: null handle");
+    if (k == 0 || !top_ids || !top_lp) { h->tk_attach = TopkAttach{}; return 0; }
+    if (const char* bad = tk_attach_bad(k, top_ids, top_lp, ld)) return fail(h, GITCAP_ERR_ARG, std::string("student_attach_top_logprobs: ") + bad);
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_top_logprobs: weights not finalized");
+    if (!head_topk_ok(h->D, false)) return fail(h, GITCAP_ERR_ARG, "student_attach_top_logprobs: no top-k kernel for this decoder width");
+    GUARD(h);
+    {   // first attach: the sum partial (sized as amax_val) and the loops' own rows at the largest k; each buffer on its own, so
+        // that an attach repeated after a failed allocation keeps what the first one got
+        const size_t Mt = (size_t)h->Mt, ntiles = ((size_t)h->V + 15) / 16;
+        int rc;
+        if (!h->amax_sum && (rc = dev_alloc(h, &h->amax_sum, Mt * ntiles))) { h->amax_sum = nullptr; return rc; }
+        if (!h->g_tk_ids && (rc = dev_alloc(h, &h->g_tk_ids, Mt * HEAD_TOPK_MAX))) { h->g_tk_ids = nullptr; return rc; }
+        if (!h->g_tk_lp && (rc = dev_alloc(h, &h->g_tk_lp, Mt * HEAD_TOPK_MAX))) { h->g_tk_lp = nullptr; return rc; }
+    }
+    h->tk_attach = TopkAttach{k, top_ids, top_lp, ld};
+    return 0;
+}
+
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
+    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});        // consumed, whatever becomes of the call
+    if (int bad = tk_check(h, "student_score", tk, T - 1)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_score: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student_score before set_memory");
     if (T < 2 || ld_ids < T) return fail(h, GITCAP_ERR_ARG, "student_score: T < 2 (CLS and at least one token) or ld_ids < T");
@@ -950,7 +997,7 @@ int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, in
     int rc;
     if (!h->amax_sum && (rc = dev_alloc(h, &h->amax_sum, (size_t)h->Mt * (((size_t)h->V + 15) / 16)))) return rc;
     if (!h->score_buf && (rc = dev_alloc(h, &h->score_buf, 2 * (size_t)h->Mt))) return rc;
-    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp};
+    const ScoreReq sq{lengths, ignore_id, token_lp, ld_lp, row_sum, row_cnt, top1_ids, top1_lp, tk};
     TextReq q;
     q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.T = T; q.score = &sq;
     return text_forward(h, q, (hipStream_t)stream);

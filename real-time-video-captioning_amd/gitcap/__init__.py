@@ -15,6 +15,9 @@ def __getattr__(name):
     if name == "caption_confidence":
         from .confidence import caption_confidence
         return caption_confidence
+    if name == "soft_labels":
+        from .scoring import soft_labels
+        return soft_labels
     if name == "distill_report":
         from .distill import distill_report
         return distill_report

@@ -178,6 +178,9 @@ SYMBOLS = {
     "gitcap_dbg_attn_small": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p]),
     "gitcap_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
+    "gitcap_attach_top_logprobs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "gitcap_dbg_head_topk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_void_p]),
     "gitcap_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
@@ -255,6 +258,7 @@ SYMBOLS = {
                                                    POINTER(c_int32), c_void_p]),
     "gitcap_student_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_student_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
+    "gitcap_student_attach_top_logprobs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "gitcap_student_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "gitcap_student_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -14,11 +14,14 @@ class _WindowStream:
     """A subclass gives ``_reset_lib()`` (empty the library's window), ``_clear()`` (forget what it keeps of the frames pushed so
     far) and ``_push(frames, to_cpu)`` (encode the frames; -> the caption when one is due, else None)."""
 
-    def __init__(self, model, sched, max_len, mode, gate, logprobs):
+    def __init__(self, model, sched, max_len, mode, gate, logprobs, top_logprobs=0):
         self._m, self._sched, self._gate = model, sched, gate
         self._max_len, self._mode = max_len, mode
         self._want_lp = logprobs
+        self._top_k = int(top_logprobs)
         self.last_logprobs = None        # logprobs=True: fp32 [B, steps] of the caption the last push returned (on the CPU when the frames were)
+        # top_logprobs=k: the k best tokens per step of that caption and their log-probabilities, [B, steps, k] each
+        self.last_top_ids = self.last_top_logprobs = None
         self._token = object()
         model._window_owner = self._token            # the handle has one window: this stream owns it until the next one is opened
         self._reset_lib()
@@ -55,10 +58,21 @@ class _WindowStream:
         lp = torch.empty((B, self._max_len), dtype=torch.float32, device=dev) if self._want_lp else None
         return ids, steps, lp
 
-    def _finish_greedy(self, ids, steps, lp, to_cpu):
-        """What the call left in the buffers -> the caption as greedy_decode returns it; keeps its log-probs in last_logprobs."""
+    def _topk_buffers(self, B):
+        """-> (top_ids int64, top_logprobs fp32) [B, max_len, k] for one greedy window call, or None"""
+        if not self._top_k:
+            return None
+        dev = self._m._dev
+        return (torch.empty((B, self._max_len, self._top_k), dtype=torch.int64, device=dev),
+                torch.empty((B, self._max_len, self._top_k), dtype=torch.float32, device=dev))
+
+    def _finish_greedy(self, ids, steps, lp, to_cpu, tk=None):
+        """What the call left in the buffers -> the caption as greedy_decode returns it; keeps its log-probs in last_logprobs and
+        its alternatives (tk = _topk_buffers') in last_top_ids / last_top_logprobs."""
         if self._mode == STOP_ALL_SEP:
             ids = ids[:, :1 + int(steps.item())]
+        if tk is not None:
+            self.last_top_ids, self.last_top_logprobs = ((t[:, :ids.shape[1] - 1].cpu() if to_cpu else t[:, :ids.shape[1] - 1]) for t in tk)
         if lp is not None:
             lp = lp[:, :ids.shape[1] - 1]
             self.last_logprobs = lp.cpu() if to_cpu else lp

@@ -10,10 +10,22 @@ def caption_confidence(ids, logprobs: torch.Tensor = None, sep_token_id: int = N
     its first SEP, or over all of them when the row has none.  ``ids`` int64 [B, 1+steps] starting with CLS, ``logprobs`` fp32
     [B, steps] (column t belongs to ids[:, t + 1]).  -> fp32 [B] in [0, 1], on ``logprobs``' device.  Plain torch ops.
     ``caption_confidence(d)`` with the dict of ``GitCaptioner.score`` / ``StudentCaptioner.score``: exp(sum / count) over the
-    positions that call counted, shaped as ``d["sum"]``; 1 where nothing was counted."""
+    positions that call counted, shaped as ``d["sum"]``; 1 where nothing was counted.  A dict that carries ``topk_logprobs``
+    (``score(top_k=k)``, k >= 2) or ``logprobs`` [.., k] (``soft_labels``) gives a dict instead: ``confidence`` (the number above;
+    absent without ``sum`` / ``count``) and ``margin`` fp32 [.., T-1], the per-token lp[.., 0] - lp[.., 1] in nats -- how far the
+    model's best token is ahead of its runner-up; +inf where there is no rank 1."""
     if isinstance(ids, dict):
-        cnt = ids["count"].to(torch.float32)
-        return torch.where(cnt > 0, torch.exp(ids["sum"].float() / cnt.clamp(min=1.0)), torch.ones_like(cnt))
+        conf = None
+        if "count" in ids:
+            cnt = ids["count"].to(torch.float32)
+            conf = torch.where(cnt > 0, torch.exp(ids["sum"].float() / cnt.clamp(min=1.0)), torch.ones_like(cnt))
+        top = ids.get("topk_logprobs", ids.get("logprobs") if "tail_logprob" in ids else None)
+        if top is None:
+            return conf
+        out = dict(margin=top_margin(top))
+        if conf is not None:
+            out["confidence"] = conf
+        return out
     if logprobs is None or sep_token_id is None:
         raise ValueError("caption_confidence takes (ids, logprobs, sep_token_id) or the dict score() returns")
     if ids.dim() != 2 or logprobs.dim() != 2 or ids.shape[0] != logprobs.shape[0] or ids.shape[1] != logprobs.shape[1] + 1:
@@ -27,3 +39,12 @@ def caption_confidence(ids, logprobs: torch.Tensor = None, sep_token_id: int = N
     keep = torch.arange(steps, device=logprobs.device)[None, :] < first[:, None]
     total = torch.where(keep, logprobs.float(), torch.zeros((), device=logprobs.device)).sum(dim=1)
     return torch.exp(total / first.to(torch.float32))
+
+
+def top_margin(top_logprobs: torch.Tensor) -> torch.Tensor:
+    """lp[..., 0] - lp[..., 1] of ranked log-probabilities [..., k]; +inf where rank 1 is missing (-inf padding, or k = 1)"""
+    first = top_logprobs[..., 0].float()
+    if top_logprobs.shape[-1] < 2:
+        return torch.full_like(first, float("inf"))
+    second = top_logprobs[..., 1].float()
+    return torch.where(torch.isneginf(second), torch.full_like(first, float("inf")), first - second)

@@ -199,21 +199,24 @@ class _CallOptions:
         self.num_keep_best, self.repetition_penalty = int(num_keep_best), float(repetition_penalty)
         self.sampling = sampling         # None | (temperature, top_k, top_p, seed)
         self._so = self._smp = None
+        self.top_k = 0                   # greedy calls: top_logprobs=k, the k best alternatives per position (0: none)
         if sampling is not None:
             self._smp = _lib.CSamplingOptions(sampling[0], sampling[1], sampling[2], sampling[3] & (2 ** 64 - 1))
 
     @property
     def key(self):
         """What batches must share to coalesce: a prompted batch is alone with its key, constrained ones need equal constraints."""
-        return (None if self.prompt is None else id(self.prompt), None if self.cons is None else self.cons.key)
+        return (None if self.prompt is None else id(self.prompt), None if self.cons is None else self.cons.key, self.top_k)
 
     def rows(self, b0, b1):
         """The options of clips [b0, b1): a chunk of a synchronous call over more than max_batch clips."""
         n = len(self.counts) if self.counts is not None else len(self.prompt.host_lengths) if self.prompt is not None else None
         if n is None or (b0 == 0 and b1 >= n):
             return self
-        return _CallOptions(self._m, None if self.prompt is None else self.prompt.rows(b0, b1), self.cons,
+        part = _CallOptions(self._m, None if self.prompt is None else self.prompt.rows(b0, b1), self.cons,
                             None if self.counts is None else self.counts[b0:b1], self.num_keep_best, self.repetition_penalty, self.sampling)
+        part.top_k = self.top_k
+        return part
 
     def search_outputs(self, B, max_steps):
         """The output buffers of a search over B clips -> (own, decoded, logprobs): ``own`` = the (decoded, logprobs) pair the call
@@ -233,11 +236,21 @@ class _CallOptions:
                                            None if nbest_lp is None else nbest_lp.data_ptr())
         return own, decoded, logprobs
 
-    def attach(self, lp=None):
-        """lp: the token log-probability buffer [nb, max_len] of a greedy call (one per chunk)."""
+    def topk_buffers(self, nb, max_len):
+        """-> (top_ids int64, top_logprobs fp32) [nb, max_len, top_k] for one greedy call, or None without top_logprobs"""
+        if not self.top_k:
+            return None
+        dev = self._m._dev
+        return (torch.empty((nb, max_len, self.top_k), dtype=torch.int64, device=dev),
+                torch.empty((nb, max_len, self.top_k), dtype=torch.float32, device=dev))
+
+    def attach(self, lp=None, tk=None):
+        """lp: the token log-probability buffer [nb, max_len] of a greedy call (one per chunk); tk: its topk_buffers()."""
         m = self._m
         if lp is not None:
             m._call("gitcap_attach_token_logprobs", _lib.ptr(lp), lp.shape[1])
+        if tk is not None:
+            m._call("gitcap_attach_top_logprobs", tk[0].shape[2], _lib.ptr(tk[0]), _lib.ptr(tk[1]), tk[0].shape[1])
         if self._so is not None:
             m._call("gitcap_attach_search_options", ctypes.byref(self._so))
         if self._smp is not None:
@@ -308,15 +321,19 @@ class CaptionFuture(_Future):
                 else:
                     n = int(sub.outs[1].item())
                 ids = ids[:, :1 + n]
-            return ids.to(self._out_device) if self._out_device != ids.device else ids
+            mv = lambda t: t.to(self._out_device) if self._out_device != t.device else t
+            if self._opts.top_k:                     # (ids, top_ids, top_logprobs), as greedy_decode(top_logprobs=k)
+                return (mv(ids),) + tuple(mv(t[self._r0:self._r1, :ids.shape[1] - 1]) for t in sub.outs[2:4])
+            return mv(ids)
 
         def rerun():
             counts, rg = self._opts.counts, None
             if counts is not None:               # a ragged batch: the callers' host clips again, or the packed device frames clip by clip
                 clips = sub.parts if sub.parts is not None else list(torch.split(sub.frames, counts))
                 rg = (clips, counts, clips[0].dtype == torch.uint8)
-            ids = m._greedy_decode(None if rg is not None else sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._opts, rg)
-            return ids.to(self._out_device) if self._out_device != ids.device else ids
+            out = m._greedy_decode(None if rg is not None else sub.rows(self._r0, self._r1), self._max_len, self._mode, False, self._opts, rg)
+            mv = lambda t: t.to(self._out_device) if self._out_device != t.device else t
+            return tuple(mv(t) for t in out) if isinstance(out, tuple) else mv(out)
 
         synced = self._mode == STOP_ALL_SEP or self._out_device.type == "cpu"
         self._done = self._deliver(extract, synced, rerun)
@@ -373,7 +390,7 @@ class CaptionStream(_WindowStream):
 
     def __init__(self, model, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features,
                  gate=None, logprobs=False, num_keep_best=1, repetition_penalty=1.0, sampling=None, prompt=None, constraints=None,
-                 carry=False):
+                 carry=False, top_logprobs=0):
         self._beam, self._lp, self._pnb, self._vis = beam_size, length_penalty, per_node_beam_size, visual_features
         # carry: the previous caption (on the device, truncated as it was returned) is the draft of the next window call
         self._carry, self._prev = bool(carry), None
@@ -383,7 +400,7 @@ class CaptionStream(_WindowStream):
         self._attached = (prompt, constraints, None, num_keep_best, repetition_penalty)
         self.last_seed = None            # do_sample: the seed of the caption the last push returned
         self._clear()
-        super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs)
+        super().__init__(model, WindowSchedule(batch, window, hop), max_len, mode, gate, logprobs, top_logprobs)
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -459,18 +476,19 @@ class CaptionStream(_WindowStream):
     def _caption(self, on_cpu):
         m = self._m
         B = self._sched.batch
-        vis = None
+        vis = tk = None
         if self._vis:
             vis = torch.empty((B, self._sched.window * m.cfg.tokens_per_frame, m.cfg.enc_width), dtype=torch.float32, device=m._dev)
         with torch.cuda.device(m._dev):
             if self._beam is None:
                 ids, steps, lp = self._greedy_buffers(B)
+                tk = self._topk_buffers(B)
                 opts = _CallOptions(m, *self._attached)
                 last = dict(draft_tokens=0, accepted=0, tail_steps=0)
                 if self._carry and self._prev is not None and self._prev.shape[1] >= 2:
                     last = m._draft_call("gitcap_window_greedy_draft", (), (_lib.ptr(vis),), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
-                    opts.attach(lp)
+                    opts.attach(lp, tk)
                     m._call("gitcap_window_greedy", self._max_len, self._mode, _lib.ptr(vis), _lib.ptr(ids), _lib.ptr(steps), m._stream())
             else:
                 sampling = m._seeded(self._sampling)
@@ -484,7 +502,7 @@ class CaptionStream(_WindowStream):
         m._last_memory = None
         self._stats["captions"] += 1
         if self._beam is None:
-            out = self._finish_greedy(ids, steps, lp, on_cpu)
+            out = self._finish_greedy(ids, steps, lp, on_cpu, tk)
             if self._carry:
                 self._prev = ids[:, :out.shape[1]]
             for k, v in last.items():
@@ -895,7 +913,7 @@ class GitCaptioner(_NativeModule):
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
-              ignore_id: Optional[int] = None, return_top1: bool = False, frame_counts=None) -> dict:
+              ignore_id: Optional[int] = None, return_top1: bool = False, frame_counts=None, top_k: int = 0) -> dict:
         """Log-probabilities of GIVEN captions, teacher-forced in one pass without a logits tensor (include/gitcap.h:
         gitcap_score).  ``x``: frames [B,F,3,S,S] or ``memory`` from forward_image_enc (treated as forward_decoder treats it);
         ``y``: CLS-first ids [B, T] or [B, n, T] -- n candidates per clip, run as n rows that share the clip's image K/V.
@@ -905,8 +923,12 @@ class GitCaptioner(_NativeModule):
         ``sum`` fp32 and ``count`` int32 [B, (n)]; with ``return_top1`` also ``top1_ids`` / ``top1_logprobs`` [B, (n,) T-1], the
         model's own arg-max at each position.  More clips than max_batch go through in chunks.  On ``x``'s device.
         frame_counts (or ``x`` as a list of clips; as in greedy_decode): frames of clips that differ in length; every clip's values
-        are bit for bit those of the clip scored alone."""
+        are bit for bit those of the clip scored alone.
+        top_k=k (1..32): also ``topk_ids`` int64 / ``topk_logprobs`` fp32 [B, (n,) T-1, k], the model's k best tokens at every
+        position (ignored ones included) ranked by (logit descending, id ascending): rank 0 is top1_ids / top1_logprobs bit for
+        bit, and the values are those of greedy_decode(top_logprobs=k) for the same prefix (gitcap_attach_top_logprobs)."""
         from . import scoring
+        top_k = scoring.check_top_k(top_k)
         self._drain()
         ids, had_n = scoring.candidates(y, self._dev)
         B, n, T = ids.shape
@@ -939,9 +961,10 @@ class GitCaptioner(_NativeModule):
                     if b0 == 0 and b1 == B:
                         self._remember_memory(x)
                 rows = (b1 - b0) * n
-                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1)
+                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1, top_k)
                 cid = ids[b0:b1].reshape(rows, T)
                 cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
+                buf.attach_topk(self._call, "gitcap_attach_top_logprobs")
                 self._call("gitcap_score", _lib.ptr(cid), T, rows, n, T, _lib.ptr(cl), -1 if ignore_id is None else int(ignore_id),
                            *buf.args(T), self._stream())
                 chunks.append(buf)
@@ -1085,7 +1108,7 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
                       prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                      frame_counts=None, draft: Optional[torch.Tensor] = None):
+                      frame_counts=None, draft: Optional[torch.Tensor] = None, top_logprobs: int = 0):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
@@ -1111,7 +1134,14 @@ class GitCaptioner(_NativeModule):
         frames; column 0 is taken as CLS, any ids are allowed).  The result is the one without it, bit for bit: the draft is
         verified in one pass, every clip keeps the leading tokens the loop would have produced anyway (``last_accepted`` [B] =
         their numbers) and only the steps some clip still lacks are decoded one by one (include/gitcap.h: gitcap_greedy_draft).
-        The call waits on the host for the verify pass.  Not with prompt or the constraint arguments."""
+        The call waits on the host for the verify pass.  Not with prompt or the constraint arguments.
+        top_logprobs=k (1..32): the result gains ``top_ids`` int64 and ``top_logprobs`` fp32 [B, steps, k] behind ids (and behind
+        logprobs with return_logprobs): the k best tokens of the distribution each step chose from and their log-probabilities,
+        ranked by (logit descending, id ascending); rank 0 is the emitted token (its value == the logprobs column) except at a
+        position a prompt forces, which reports the model's own ranks.  Ranks a row cannot fill (bans) hold -1 / -inf.  No
+        logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if draft is not None and (prompt is not None or no_repeat_ngram_size or min_length or suppress_tokens is not None):
             raise ValueError("draft= is not combined with prompt= or the constraint arguments")
         stop = stop or self.stop
@@ -1123,6 +1153,7 @@ class GitCaptioner(_NativeModule):
             src, rg = self._ragged_input(src, frame_counts)
         B, in_dev = (src.shape[0], src.device) if rg is None else (len(rg[1]), rg[0][0].device)
         opts = self._greedy_options(B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg)
+        opts.top_k = int(top_logprobs)
         if draft is not None and (draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] < 2 or draft.dtype != torch.int64):
             raise ValueError(f"draft must be int64 [{B}, 1+n] with n >= 1, got {draft.dtype} {tuple(draft.shape)}")
         if in_dev.type == "cpu":                  # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
@@ -1149,7 +1180,7 @@ class GitCaptioner(_NativeModule):
                 chunk, cc = self._pack_to_device(parts[b0:b0 + step], raw), counts[b0:b0 + step]
                 yield (b0, len(cc), max(cc)) + tuple(chunk.shape[1:3]) + (chunk,)
 
-    def _draft_call(self, name, head, mid, draft, max_len, mode, ids, steps, lp=None, opts=None) -> dict:
+    def _draft_call(self, name, head, mid, draft, max_len, mode, ids, steps, lp=None, opts=None, tk=None) -> dict:
         """One of the two draft entry points (``head`` / ``mid`` = the arguments in front of the draft's / between the stop rule
         and ids_out); ``draft`` int64 [B, 1+n] on either device, trimmed to max_len columns beyond CLS.  -> what the call
         offered, accepted (summed over the clips) and decoded behind it; ``last_accepted`` = the clips' own numbers."""
@@ -1158,7 +1189,7 @@ class GitCaptioner(_NativeModule):
         n = d.shape[1] - 1
         acc = (ctypes.c_int32 * B)(*([-1] * B))
         before = self.draft_stats()
-        (opts or _CallOptions(self)).attach(lp)
+        (opts or _CallOptions(self)).attach(lp, tk)          # (tk: the call refuses it and consumes it)
         self._call(name, *head, _lib.ptr(d), n + 1, n, max_len, mode, *mid, _lib.ptr(ids), _lib.ptr(steps), acc, self._stream())
         after = self.draft_stats()
         self.last_accepted = torch.tensor(list(acc), dtype=torch.int32)
@@ -1181,7 +1212,7 @@ class GitCaptioner(_NativeModule):
             fr, raw, src = None, rg[2], rg[0][0]  # (src: where the results go)
         if draft is not None and raw:
             raise ValueError("draft= takes transformed fp32 frames (there is no draft form of the camera-frame call)")
-        outs, steps_all, lps, accepted = [], [], [], []
+        outs, steps_all, lps, accepted, tks = [], [], [], [], []
         # (a batch of several chunks stops by the rule over the WHOLE batch, below: its chunks decode every step)
         dmode = mode if draft is None or (len(rg[1]) if rg is not None else fr.shape[0]) <= self.max_batch else STOP_NEVER
         with torch.cuda.device(self._dev):
@@ -1190,14 +1221,17 @@ class GitCaptioner(_NativeModule):
                 steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
                 if want_lp:
                     lps.append(torch.empty((nb, max_len), dtype=torch.float32, device=self._dev))
+                tk = opts.topk_buffers(nb, max_len)
+                if tk is not None:
+                    tks.append(tk)
                 if draft is not None:
                     self._draft_call("gitcap_greedy_draft", (_lib.ptr(chunk), nb, F), (), draft[b0:b0 + nb], max_len, dmode, ids, steps,
-                                     lps[-1] if want_lp else None, opts.rows(b0, b0 + nb))
+                                     lps[-1] if want_lp else None, opts.rows(b0, b0 + nb), tk)
                     accepted.append(self.last_accepted)
                     outs.append(ids)
                     steps_all.append(steps)
                     continue
-                opts.rows(b0, b0 + nb).attach(lps[-1] if want_lp else None)      # one-shot: consumed by the greedy call below
+                opts.rows(b0, b0 + nb).attach(lps[-1] if want_lp else None, tk)  # one-shot: consumed by the greedy call below
                 if raw:
                     self._call("gitcap_greedy_raw", _lib.ptr(chunk), nb, F, fh, fw, max_len, mode,
                                _lib.ptr(ids), _lib.ptr(steps), self._stream())
@@ -1218,18 +1252,20 @@ class GitCaptioner(_NativeModule):
                 nz = torch.nonzero(all_sep)
                 n = int(nz[0].item()) + 1 if nz.numel() else max_len
             ids = ids[:, :1 + n]
-        ids = ids.to(src.device) if src.device != ids.device else ids
-        if not want_lp:
-            return ids
-        lp = torch.cat(lps, 0)[:, :ids.shape[1] - 1]
-        return ids, (lp.to(src.device) if src.device != lp.device else lp)
+        mv = lambda t: t.to(src.device) if src.device != t.device else t
+        out = (mv(ids),)
+        if want_lp:
+            out += (mv(torch.cat(lps, 0)[:, :ids.shape[1] - 1]),)
+        if tks:
+            out += tuple(mv(torch.cat([t[i] for t in tks], 0)[:, :ids.shape[1] - 1]) for i in (0, 1))
+        return out if len(out) > 1 else out[0]
 
     generate = greedy_decode      # the name BASELINE.json's north_star uses for this entry point
 
     @torch.no_grad()
     def greedy_decode_async(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                             coalesce: int = 1, prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                            suppress_tokens=None, frame_counts=None) -> "CaptionFuture":
+                            suppress_tokens=None, frame_counts=None, top_logprobs: int = 0) -> "CaptionFuture":
         """Pipelined greedy_decode for a stream of batches: returns immediately with a future; up to
         FOUR submissions may be in flight, so one batch's image pass (MFMA bound) overlaps the token
         loops (latency bound) of the batches before it on the handle's internal HIP streams.  Call
@@ -1247,7 +1283,10 @@ class GitCaptioner(_NativeModule):
         max_batch >= k*B.  ``prompt`` / ``prompt_lengths`` as in greedy_decode; a prompted batch is submitted on its own (it does
         not coalesce).  no_repeat_ngram_size / min_length / suppress_tokens as in greedy_decode; a constrained batch coalesces
         only with batches that carry equal constraints.  frame_counts (or a list of clips) as in greedy_decode: a ragged batch is
-        packed once (host clips: in the staging ring's pinned buffer) and submitted on its own (it does not coalesce)."""
+        packed once (host clips: in the staging ring's pinned buffer) and submitted on its own (it does not coalesce).
+        top_logprobs=k as in greedy_decode: ``result()`` returns (ids, top_ids, top_logprobs); batches coalesce with equal k."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         stop = stop or self.stop
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop]
         if max_len > self.max_text_len:
@@ -1260,6 +1299,7 @@ class GitCaptioner(_NativeModule):
                     raise ValueError(f"batch {len(counts)} > max_batch={self.max_batch}")
                 self._flush_pending()
                 opts = self._greedy_options(len(counts), max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg)
+                opts.top_k = int(top_logprobs)
                 fut = CaptionFuture(self, None, mode, max_len, parts[0].device, opts)
                 fut._attach(self._greedy_submit(self._ragged_source(rg), raw, (len(counts), max(counts)) + tuple(parts[0].shape[1:3]),
                                                 max_len, mode, opts), 0, len(counts))
@@ -1272,6 +1312,7 @@ class GitCaptioner(_NativeModule):
         if not host:
             fr = self._to_device(fr)
         opts = self._greedy_options(B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens)
+        opts.top_k = int(top_logprobs)
         fut = CaptionFuture(self, fr, mode, max_len, src.device, opts)
         key = (tuple(fr.shape), max_len, mode, raw, host) + opts.key
         if opts.prompt is not None:
@@ -1296,7 +1337,7 @@ class GitCaptioner(_NativeModule):
         dv, entry, st = self._staging().stage(self, parts, torch.uint8 if raw else torch.float32)
         return dv, entry, ctypes.c_void_p(st.cuda_stream)
 
-    def _submit_frames(self, kind, src, raw, dims, args, outs, opts, users=1):
+    def _submit_frames(self, kind, src, raw, dims, args, outs, opts, users=1, before=None):
         """One pipelined submission, gitcap_<kind>[_raw]_submit (kind: "greedy" | "beam_search") -> its _Submission, in flight.
         src: the device frames (dense [B, F, ...] or packed), or the list of the callers' CPU tensors, which go through the staging
         ring (concatenated along dim 0) with the submission ordered behind their copy; dims = (B, F, fh, fw) as the call takes
@@ -1312,7 +1353,7 @@ class GitCaptioner(_NativeModule):
                 frames, stream = src, self._stream()
             ticket = ctypes.c_int(-1)
             self._submit(f"gitcap_{kind}_raw_submit" if raw else f"gitcap_{kind}_submit", _lib.ptr(frames), *(dims if raw else dims[:2]),
-                         *args, stream, ctypes.byref(ticket), before=opts.attach)
+                         *args, stream, ctypes.byref(ticket), before=before or opts.attach)
         self._last_memory = None
         sub = _Submission(ticket.value, frames, outs, users > 1, users=users, parts=parts)
         if entry is not None:
@@ -1323,7 +1364,9 @@ class GitCaptioner(_NativeModule):
     def _greedy_submit(self, src, raw, dims, max_len, stop, opts, users=1):
         ids = torch.empty((dims[0], max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros((1,), dtype=torch.int32, device=self._dev)
-        return self._submit_frames("greedy", src, raw, dims, (max_len, stop, _lib.ptr(ids), _lib.ptr(steps)), (ids, steps), opts, users)
+        tk = opts.topk_buffers(dims[0], max_len)          # held by the submission beside ids: the device writes them until the wait
+        return self._submit_frames("greedy", src, raw, dims, (max_len, stop, _lib.ptr(ids), _lib.ptr(steps)), (ids, steps) + (tk or ()), opts,
+                                   users, before=None if tk is None else (lambda: opts.attach(tk=tk)))
 
     def _flush_pending(self):
         """Submit the waiting batches as one pass and hand each future its row range."""
@@ -1629,7 +1672,7 @@ class GitCaptioner(_NativeModule):
                        repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                        top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
                        prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                       carry: bool = False) -> CaptionStream:
+                       carry: bool = False, top_logprobs: int = 0) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1644,7 +1687,13 @@ class GitCaptioner(_NativeModule):
         in greedy_decode / infer): the stream's prompt, one row per clip, attached again for every caption.  no_repeat_ngram_size /
         min_length / suppress_tokens (as in greedy_decode / infer): the stream's constraints, attached again for every caption.
         ``carry`` (greedy streams without prompt or constraints): the previous caption is the draft of the next window call
-        (greedy_decode's ``draft``): the same captions; ``stream.stats()`` tells how much of the drafts was accepted."""
+        (greedy_decode's ``draft``): the same captions; ``stream.stats()`` tells how much of the drafts was accepted.
+        ``top_logprobs=k`` (greedy streams without ``carry``): ``stream.last_top_ids`` / ``stream.last_top_logprobs`` [B, steps, k]
+        of the caption the last push returned (greedy_decode's top_logprobs)."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if top_logprobs and (beam_size is not None or carry):
+            raise ValueError("top_logprobs is for greedy streams without carry (a draft call does not carry alternatives)")
         if carry and beam_size is not None:
             raise ValueError("carry=True is for greedy streams (beam_size=None)")
         if carry and (prompt is not None or no_repeat_ngram_size or min_length or suppress_tokens is not None):
@@ -1681,7 +1730,7 @@ class GitCaptioner(_NativeModule):
                                1 if beam_size is None else beam_size * per_node_beam_size)
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
                              logprobs, num_keep_best, repetition_penalty,
-                             sampling, pr, co, carry)
+                             sampling, pr, co, carry, top_logprobs)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip

@@ -43,10 +43,10 @@ class StudentCaptionStream(_WindowStream):
     ``carry`` a greedy stream offers its previous caption as the draft of the next window call
     (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0):
         self._carry, self._prev, self._beams = bool(carry), None, beams
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
-        super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop), max_len, mode, gate, logprobs)
+        super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop), max_len, mode, gate, logprobs, top_logprobs)
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -91,13 +91,14 @@ class StudentCaptionStream(_WindowStream):
         with torch.cuda.device(m._dev):
             if self._beams is None:
                 ids, steps, lp = self._greedy_buffers(B)
+                tk = self._topk_buffers(B)
                 last = dict(draft_tokens=0, accepted=0, tail_steps=0)
                 if self._carry and self._prev is not None:
                     last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
-                    m._attach_logprobs(lp)
+                    m._attach_logprobs(lp, tk)
                     m._call("gitcap_student_window_greedy", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps), m._stream())
-                out = self._finish_greedy(ids, steps, lp, to_cpu)
+                out = self._finish_greedy(ids, steps, lp, to_cpu, tk)
                 if self._carry:
                     self._prev = ids[:, :out.shape[1]]       # stays on the device, truncated as the caption is
                 for k, v in last.items():
@@ -269,11 +270,12 @@ class StudentCaptioner(_NativeModule):
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
-              ignore_id: Optional[int] = None, return_top1: bool = False) -> dict:
+              ignore_id: Optional[int] = None, return_top1: bool = False, top_k: int = 0) -> dict:
         """GitCaptioner.score over the student decoder (include/gitcap.h: gitcap_student_score): ``x`` frames or memory [B,F,D],
         ``y`` CLS-first ids [B, T] or [B, n, T] (n candidates per clip: rows whose memory is repeated).  Same ignore rules and
-        the same dict; clips go through in chunks of max_batch // n."""
+        the same dict (``top_k`` included); clips go through in chunks of max_batch // n."""
         from . import scoring
+        top_k = scoring.check_top_k(top_k)
         ids, had_n = scoring.candidates(y, self._dev)
         B, n, T = ids.shape
         if x.shape[0] != B:
@@ -290,10 +292,11 @@ class StudentCaptioner(_NativeModule):
                 b1 = min(B, b0 + Bc)
                 mem = self._memory(self._src_memory(x[b0:b1])).repeat_interleave(n, dim=0) if n > 1 else self._memory(self._src_memory(x[b0:b1]))
                 rows = (b1 - b0) * n
-                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1)
+                buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1, top_k)
                 cid = ids[b0:b1].reshape(rows, T)
                 cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
                 self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
+                buf.attach_topk(self._call, "gitcap_student_attach_top_logprobs")
                 self._call("gitcap_student_score", _lib.ptr(cid), T, rows, T, _lib.ptr(cl), -1 if ignore_id is None else int(ignore_id),
                            *buf.args(T), self._stream())
                 chunks.append(buf)
@@ -304,13 +307,16 @@ class StudentCaptioner(_NativeModule):
         fmaps, memory = self.forward_image_enc(x)
         return list(fmaps) + [self.forward_decoder(y, memory)]
 
-    def _attach_logprobs(self, lp: Optional[torch.Tensor]):
-        """One-shot: the next greedy-family call writes its per-token log-probabilities to ``lp`` (fp32 [B, max_len], contiguous)."""
+    def _attach_logprobs(self, lp: Optional[torch.Tensor], tk=None):
+        """One-shot: the next greedy-family call writes its per-token log-probabilities to ``lp`` (fp32 [B, max_len], contiguous)
+        and the k best alternatives per step to ``tk`` = (int64, fp32) [B, max_len, k] (a draft call refuses these)."""
         if lp is not None:
             self._call("gitcap_student_attach_token_logprobs", _lib.ptr(lp), lp.shape[1])
+        if tk is not None:
+            self._call("gitcap_student_attach_top_logprobs", tk[0].shape[2], _lib.ptr(tk[0]), _lib.ptr(tk[1]), tk[0].shape[1])
 
     def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor,
-                    lp: Optional[torch.Tensor] = None) -> dict:
+                    lp: Optional[torch.Tensor] = None, tk=None) -> dict:
         """One of the two draft entry points (``head`` = the arguments in front of the draft's); ``draft`` int64 [B, 1+n] on
         either device, trimmed to max_len columns beyond CLS.  -> what the call offered, accepted and decoded behind it.
         ``lp``: see _attach_logprobs."""
@@ -321,7 +327,7 @@ class StudentCaptioner(_NativeModule):
         n = d.shape[1] - 1
         acc = ctypes.c_int32(-1)
         before = self._draft_stats()
-        self._attach_logprobs(lp)
+        self._attach_logprobs(lp, tk)
         self._call(name, *head, _lib.ptr(d), n + 1, n, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), ctypes.byref(acc), self._stream())
         self.last_accepted = int(acc.value)
         return dict(draft_tokens=n, accepted=self.last_accepted, tail_steps=self._draft_stats()[3] - before[3])
@@ -334,7 +340,7 @@ class StudentCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
-                      draft: Optional[torch.Tensor] = None, return_logprobs: bool = False):
+                      draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
@@ -343,7 +349,12 @@ class StudentCaptioner(_NativeModule):
         loop would have produced anyway are accepted (``last_accepted`` = their number) and only the rest is decoded step by
         step (include/gitcap.h: gitcap_student_greedy_draft).  The call waits on the host for the verify pass.
         ``return_logprobs``: -> (ids, logprobs), logprobs fp32 [B, steps] on ``src``'s device, column t =
-        log_softmax(step t's logits)[ids[:, t + 1]]; with a ``draft`` bit for bit the values without it."""
+        log_softmax(step t's logits)[ids[:, t + 1]]; with a ``draft`` bit for bit the values without it.
+        ``top_logprobs=k`` (1..32): the result gains ``top_ids`` int64 / ``top_logprobs`` fp32 [B, steps, k] behind ids (and
+        logprobs): every step's k best tokens by (logit descending, id ascending) and their log-probabilities; rank 0 is the
+        emitted token.  No logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
@@ -354,19 +365,25 @@ class StudentCaptioner(_NativeModule):
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
         lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
+        tk = None
+        if top_logprobs:
+            tk = (torch.empty((B, max_len, int(top_logprobs)), dtype=torch.int64, device=self._dev),
+                  torch.empty((B, max_len, int(top_logprobs)), dtype=torch.float32, device=self._dev))
         with torch.cuda.device(self._dev):
             if draft is not None:
-                self._draft_call("gitcap_student_greedy_draft", (_lib.ptr(mem), B), draft, max_len, mode, ids, steps, lp)
+                self._draft_call("gitcap_student_greedy_draft", (_lib.ptr(mem), B), draft, max_len, mode, ids, steps, lp, tk)
             else:
-                self._attach_logprobs(lp)
+                self._attach_logprobs(lp, tk)
                 self._call("gitcap_student_greedy", _lib.ptr(mem), B, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
-        ids = ids.to(out_dev) if out_dev != ids.device else ids
-        if lp is None:
-            return ids
-        lp = lp[:, :n]
-        return ids, (lp.to(out_dev) if out_dev != lp.device else lp)
+        mv = lambda t: t.to(out_dev) if out_dev != t.device else t
+        out = (mv(ids),)
+        if lp is not None:
+            out += (mv(lp[:, :n]),)
+        if tk is not None:
+            out += (mv(tk[0][:, :n]), mv(tk[1][:, :n]))
+        return out if len(out) > 1 else out[0]
 
     generate = greedy_decode
 
@@ -393,7 +410,7 @@ class StudentCaptioner(_NativeModule):
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
-                       logprobs: bool = False) -> StudentCaptionStream:
+                       logprobs: bool = False, top_logprobs: int = 0) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -405,7 +422,13 @@ class StudentCaptioner(_NativeModule):
         ``carry``: a greedy stream passes its previous caption as the draft of the next window call (greedy_decode's ``draft``):
         the same captions; ``stats()`` tells how much of the drafts was accepted.  Not with ``beams``.
         ``logprobs`` (greedy streams only): after a push that returned a caption, ``stream.last_logprobs`` holds its per-token
-        log-probabilities [B, steps] (greedy_decode's return_logprobs); works with ``gate`` and ``carry``."""
+        log-probabilities [B, steps] (greedy_decode's return_logprobs); works with ``gate`` and ``carry``.
+        ``top_logprobs=k`` (greedy streams without ``carry``: a draft call does not carry alternatives): ``stream.last_top_ids`` /
+        ``stream.last_top_logprobs`` [B, steps, k] of that caption (greedy_decode's top_logprobs)."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if top_logprobs and (beams is not None or carry):
+            raise ValueError("top_logprobs is for greedy streams without carry")
         if logprobs and beams is not None:
             raise ValueError("logprobs=True is for greedy streams: it cannot be combined with beams")
         if carry and beams is not None:
@@ -428,7 +451,7 @@ class StudentCaptioner(_NativeModule):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
