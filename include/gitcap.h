@@ -396,6 +396,45 @@ int gitcap_score(gitcap_t* h, const int64_t* ids, int ld_ids, int rows, int beam
  * keep whatever they held) -> out (device fp32 [n]) */
 int gitcap_dbg_score_target_logits(gitcap_t* h, float* out, int n, void* stream);
 
+/* Per-token attention maps over frames and patches: which image tokens every position of a caption attends to, read back from the
+ * q | k the LAST SYNCHRONOUS text pass of the handle left in its text cache (gitcap_greedy and its raw / window / draft forms,
+ * gitcap_score, gitcap_distill, gitcap_text_forward from position 0 and the calls that extended it).  Nothing is recomputed and no
+ * existing launch changes: two small launches over the cache.
+ * For row r (clip r / rows-per-clip of that pass), position j, decoder layer l and head h, p[l][h][r][j][.] is the softmax of
+ * q . k / sqrt(64) over the clip's image keys followed by the row's text keys 0 .. j (the mask the decoder applies).  The outputs are
+ * means over the heads and over the selected layers, layer = -1: all, layer = l: that one:
+ *   frame_mass  device fp32 [rows][T][ld_f]: column f = the mass on the image tokens of frame f of the row's clip (its class token
+ *               included); columns from the clip's frame count to the longest clip's hold 0; ld_f >= frames of the longest clip
+ *   text_mass   device fp32 [rows][T]: the mass on the row's own text keys; frame_mass summed over f + text_mass = 1 up to rounding
+ *   patch_map   nullable, device fp32 [rows][T][ld_s]: column s = the mean probability of image token s of the clip (frame-major),
+ *               0 from the clip's token count to the longest clip's; ld_s >= image tokens of the longest clip
+ *   lengths     nullable, device int32 [rows]: positions j >= lengths[r] are written as zeros
+ * Columns beyond the widths named above are not written.  Position j is the one whose head predicts token j + 1.  Sums run in a
+ * fixed order without float atomics: a row's values do not depend on the rows beside it and repeat bit for bit.
+ * Errors: GITCAP_ERR_STATE when there is no such pass (none yet, an image pass or a submitted call since), when the last pass was a
+ * beam search or gitcap_reorder_rows moved the rows (their rows are permuted: score the predictions, then ask), when T exceeds the
+ * positions that pass filled, or when the image prefix is not whole frames; GITCAP_ERR_ARG for rows != that pass's rows, a layer
+ * outside [-1, dec_layers), short leading dimensions, null outputs.  The first call allocates the scratch (2 floats per layer,
+ * head, row and position of the handle's sizes). */
+int gitcap_attention_map(gitcap_t* h, int rows, int T, int layer, const int32_t* lengths, float* frame_mass, int ld_f, float* text_mass,
+                         float* patch_map, int ld_s, void* stream);
+/* The same two launches on caller-built caches, no handle: kv_txt bf16 [L][rows][Tmax][3 D] (q | k | v of the text rows), kv_img bf16
+ * [L][img_rows][3 D]; clip c's image keys are rows c * S_img .. of kv_img (off == len == NULL, Smax == S_img), or rows off[c] ..
+ * off[c] + len[c] - 1 (device int32 [rows / rows_per_clip], len[c] a multiple of N and <= Smax).  N = image tokens per frame,
+ * D == 64 H.  The scratch is a stream-ordered allocation.  GITCAP_ERR_ARG for what would index outside a buffer. */
+typedef struct gitcap_dbg_attn_map_args {
+    const void *kv_txt, *kv_img;
+    int32_t L, H, D, rows, rows_per_clip, T, Tmax, N, S_img, Smax, img_rows;
+    const int32_t *off, *len;
+    int32_t layer;
+    const int32_t* lengths;
+    float* frame_mass;
+    int32_t ld_f;
+    float *text_mass, *patch_map;
+    int32_t ld_s;
+} gitcap_dbg_attn_map_args;
+int gitcap_dbg_attn_map(const gitcap_dbg_attn_map_args* a, void* stream);
+
 /* Prompted decoding: per-clip text prefixes for the greedy and the beam family -- the `prefix` branch of the reference's
  * GenerativeImageTextModel.infer (src/models/model.py:432-437, :453-455: the search starts from the given tokens instead of a lone
  * CLS; how a GIT model is asked a question, told how a caption begins, or made to continue one).  The reference takes one prefix
@@ -1074,6 +1113,21 @@ int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream);
 int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream);
+/* Per-token attention over the frames, for this handle.  The student's memory is one token per frame, so its cross-attention IS the
+ * per-frame attribution: a teacher-forced pass over `ids` against the memory set last -- the rows of gitcap_student_score, without
+ * the vocabulary head -- during which one small launch per layer writes the probabilities of the cross-attention (the q and memory
+ * K the attention launch reads, its own arithmetic), then their mean over the heads and over all layers (layer = -1) or one, in a
+ * fixed order.  frame_mass: device fp32 [rows][T][ld_f], column f = the mass on memory token f (each position's columns sum to 1),
+ * ld_f >= mem_tokens; position j is the one whose head predicts ids[r][j + 1]; lengths (nullable, device int32 [rows]): positions
+ * j >= lengths[r] are zeros.  Checks: gitcap_student_forward_decoder's, plus T < 1, ld_ids < T, ld_f < mem_tokens, a layer outside
+ * [-1, layers).  The first call allocates the probabilities' scratch; every other call of the handle runs the launches it ran. */
+int gitcap_student_attention(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, int layer, const int32_t* lengths,
+                             float* frame_mass, int ld_f, void* stream);
+/* The same read-out without a handle: q bf16 [rows * T][H * hd], memory keys k bf16 [rows][F][ldkv] (head h at columns h * hd) ->
+ * probs fp32 [rows * T][H][F] = softmax(q . k / sqrt(hd)) and frame_mass [rows][T][ld_f], their head mean.  F <= 64, hd % 8 == 0,
+ * hd <= 128, ldkv % 8 == 0. */
+int gitcap_dbg_cross_probs(const void* q, const void* k, int ldkv, int rows, int T, int H, int hd, int F, const int32_t* lengths, float* probs,
+                           float* frame_mass, int ld_f, void* stream);
 
 /* Teacher-student divergence of given captions, forward only: KL(teacher || student) of every position's next-token distribution
  * at a temperature -- LOSS 2 of DistillationTrainer.training_step (src/models/model.py:919-935: KLDivLoss('batchmean') of

@@ -78,6 +78,44 @@ int gitcap_sample_rows_constrained(const float* logits, int ld, const float* bea
     return sample_rows_hook(c, per_node, SampleOpt{true, temperature, top_k, top_p, seed}, SampleStats{kept_out, logz_out}, stream);
 }
 
+// ---- attention maps (tests/test_attention_map_gpu.py) -------------------------------------------------------------------------
+int gitcap_dbg_attn_map(const gitcap_dbg_attn_map_args* d, void* stream) {
+    if (!d || !d->kv_txt || !d->frame_mass || !d->text_mass) return GITCAP_ERR_ARG;
+    if (d->L <= 0 || d->H <= 0 || d->rows <= 0 || d->rows_per_clip <= 0 || d->rows % d->rows_per_clip != 0 || d->T <= 0 || d->T > d->Tmax ||
+        d->N < 0 || d->S_img < 0 || d->Smax < 0 || d->img_rows < 0)
+        return GITCAP_ERR_ARG;
+    if (!d->off && (int64_t)(d->rows / d->rows_per_clip) * d->S_img > d->img_rows) return GITCAP_ERR_ARG;
+    if ((((uintptr_t)d->off | (uintptr_t)d->len | (uintptr_t)d->lengths | (uintptr_t)d->frame_mass | (uintptr_t)d->text_mass | (uintptr_t)d->patch_map) & 3) != 0)
+        return GITCAP_ERR_ARG;
+    AttnMapArgs a{};
+    a.kv_img = (const bf16_t*)d->kv_img; a.img_layer_stride = (size_t)d->img_rows * 3 * d->D;
+    a.kv_txt = (const bf16_t*)d->kv_txt; a.txt_layer_stride = (size_t)d->rows * d->Tmax * 3 * d->D;
+    a.L = d->L; a.H = d->H; a.D = d->D; a.rows = d->rows; a.rows_per_clip = d->rows_per_clip; a.T = d->T; a.Tmax = d->Tmax;
+    a.N = d->N; a.S_img = d->S_img; a.Smax = d->Smax; a.off = d->off; a.len = d->len; a.layer = d->layer; a.lengths = d->lengths;
+    a.frame_mass = d->frame_mass; a.ld_f = d->ld_f; a.text_mass = d->text_mass; a.patch_map = d->patch_map; a.ld_s = d->ld_s;
+    hipStream_t s = (hipStream_t)stream;
+    void* scratch = nullptr;
+    if (hipMallocAsync(&scratch, attn_map_scratch_floats(d->L, d->H, d->rows, d->T, d->layer) * sizeof(float), s) != hipSuccess) return GITCAP_ERR_NOMEM;
+    a.stats = (float*)scratch;
+    const hipError_t e = launch_attn_map(a, s);
+    (void)hipFreeAsync(scratch, s);
+    return dbg_rc(e);
+}
+
+// the student's read-out: cross_probs_kernel on caller-built q [M][H * hd] and memory keys k [rows][F][ldkv] (M = rows * T), then the
+// head mean of that one layer -> frame_mass [rows][T][ld_f]; probs [M][H][F] is the caller's too
+int gitcap_dbg_cross_probs(const void* q, const void* k, int ldkv, int rows, int T, int H, int hd, int F, const int32_t* lengths, float* probs,
+                           float* frame_mass, int ld_f, void* stream) {
+    if (!q || !k || !probs || !frame_mass || rows <= 0 || T <= 0 || H <= 0 || hd <= 0 || F <= 0 || ldkv < H * hd || (ldkv & 7) != 0 || ld_f < F ||
+        (int64_t)rows * T * H * F > 0x7fffffff || (((uintptr_t)q | (uintptr_t)k) & 15) != 0 ||
+        (((uintptr_t)probs | (uintptr_t)frame_mass | (uintptr_t)lengths) & 3) != 0)
+        return GITCAP_ERR_ARG;
+    const CrossProbsArgs a{(const bf16_t*)q, H * hd, T, (const bf16_t*)k, ldkv, F, F, probs, rows * T, H, hd};
+    hipError_t e = launch_cross_probs(a, (hipStream_t)stream);
+    if (e == hipSuccess) e = launch_cross_mean(probs, 1, rows, T, H, F, 0, lengths, frame_mass, ld_f, (hipStream_t)stream);
+    return dbg_rc(e);
+}
+
 // ---- constrained decoding (tests/test_constraints_gpu.py) ---------------------------------------------------------------------
 int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
                         const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream) {

@@ -201,6 +201,12 @@ struct gitcap : HandleCore {
     struct ProfRec { hipEvent_t a, b; double flops, bytes; };
     struct ProfClass { std::vector<ProfRec> recs; size_t used = 0; };
     ProfClass prof[GITCAP_PROF_CLASSES];
+
+    // gitcap_attention_map: the text pass slot 0 ran last on the caller's stream -- its rows, rows per clip and the positions
+    // 0 .. T - 1 whose q | k the text cache holds (T == 0: none, or the image prefix changed since); permuted: a beam search or
+    // gitcap_reorder_rows moved the rows.  stats: launch_attn_map's scratch for max rows x max_text_len, first use.
+    struct AttnPass { int rows = 0, rows_per_clip = 0, T = 0; bool permuted = false; } att;
+    float* att_stats = nullptr;
 };
 
 namespace {
@@ -526,6 +532,7 @@ int image_prefix(gitcap* h, int B, int S, hipStream_t s, int ragged_rows = 0) {
         }
     }
     sl.B = B; sl.S = S; sl.S_tot = rows; sl.ragged = ragged; sl.have = true;
+    if (h->cur_slot == 0) h->att = gitcap::AttnPass{};      // the cached text rows were computed against another image prefix
     return 0;
 }
 
@@ -575,6 +582,13 @@ int text_forward(gitcap* h, const TextReq& q, hipStream_t s) {
     if (t0 + T > c.max_text_pos) return fail(h, GITCAP_ERR_ARG, "text_forward: position exceeds max_text_pos");
     const int D = h->D, M = rows * T, H = c.dec_heads;
     if (M > sl.Mt) return fail(h, GITCAP_ERR_STATE, "text_forward: more text rows than the slot's workspace holds");
+    if (h->cur_slot == 0) {     // what gitcap_attention_map may read back: a synchronous pass from position 0, and the steps that extend it
+        gitcap::AttnPass& ap = h->att;
+        if (h->pipelined) ap = gitcap::AttnPass{};
+        else if (t0 == 0) ap = gitcap::AttnPass{rows, beams, T, false};
+        else if (ap.rows == rows && ap.rows_per_clip == beams && t0 <= ap.T) ap.T = t0 + T;
+        else ap = gitcap::AttnPass{};
+    }
     int rc;
     const size_t kvi_layer = (size_t)h->Mi * 3 * D, kvt_layer = (size_t)h->R * h->Tmax * 3 * D;
     // FC1 -> GELU -> FC2 of the text rows: one launch over 64-wide hidden slices (ffn_txt.hip), leaving dec_ffn / 64 fp32
@@ -1572,6 +1586,7 @@ static int beam_loop(gitcap* h, int B, int beams, int max_steps, float length_pe
         HIP_OK(h, launch_beam_step(bb, st, s));
     }
     HIP_OK(h, launch_beam_finish(bb, so.n, B, L, h->c.sep_token_id, BeamFinishOut{so.nbest, so.nbest_lp, decoded_out, logprobs_out}, s));
+    if (h->cur_slot == 0) h->att.permuted = true;       // the text cache's rows followed their beams: no caption's positions in a row
     return 0;
 }
 
@@ -1999,6 +2014,43 @@ int gitcap_reorder_rows(gitcap_t* h, const int32_t* src_rows, int rows, int t_le
     HIP_OK(h, launch_gather_txt_rows(sl.kv_txt, sl.kv_txt2, src_rows, rows, t_len, h->Tmax, 3 * h->D, h->c.dec_layers,
                                      (size_t)h->R * h->Tmax * 3 * h->D, s));
     std::swap(sl.kv_txt, sl.kv_txt2);
+    h->att.permuted = true;
+    return 0;
+}
+
+// The maps of the text pass the handle ran last (attnmap.hip): two launches over the slot's cached q | k, nothing recomputed.
+int gitcap_attention_map(gitcap_t* h, int rows, int T, int layer, const int32_t* lengths, float* frame_mass, int ld_f, float* text_mass,
+                         float* patch_map, int ld_s, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "attention_map: null handle");
+    GUARD(h);
+    POLL(h);
+    select_slot(h, 0);
+    gitcap::Slot& sl = cur(h);
+    const gitcap::AttnPass& ap = h->att;
+    if (!h->finalized || !sl.have || ap.T == 0)
+        return fail(h, GITCAP_ERR_STATE, "attention_map: no synchronous text pass (greedy, score, text_forward) since the last image pass");
+    if (ap.permuted) return fail(h, GITCAP_ERR_STATE, "attention_map: the last text pass was a beam search (its rows are permuted): score the predictions, then ask");
+    if (!frame_mass || !text_mass || rows <= 0 || T <= 0) return fail(h, GITCAP_ERR_ARG, "attention_map: bad arguments");
+    if (rows != ap.rows) return fail(h, GITCAP_ERR_ARG, "attention_map: rows != the rows of the last text pass");
+    if (T > ap.T) return fail(h, GITCAP_ERR_STATE, "attention_map: T exceeds the positions the last text pass filled");
+    if (layer < -1 || layer >= h->c.dec_layers) return fail(h, GITCAP_ERR_ARG, "attention_map: layer outside [-1, dec_layers)");
+    if (h->N <= 0 || sl.S % h->N != 0) return fail(h, GITCAP_ERR_STATE, "attention_map: the image prefix is not whole frames (set_visual with another token count)");
+    if (ld_f < sl.S / h->N || (patch_map && ld_s < sl.S)) return fail(h, GITCAP_ERR_ARG, "attention_map: ld_f < frames or ld_s < image tokens of the longest clip");
+    if ((((uintptr_t)lengths | (uintptr_t)frame_mass | (uintptr_t)text_mass | (uintptr_t)patch_map) & 3) != 0)
+        return fail(h, GITCAP_ERR_ARG, "attention_map: misaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(h, join_async(h, s));
+    if (!h->att_stats)
+        if (int rc = dev_alloc(h, &h->att_stats, attn_map_scratch_floats(h->c.dec_layers, h->c.dec_heads, h->R, h->Tmax, -1))) return rc;
+    AttnMapArgs a{};
+    a.kv_img = sl.kv_img; a.img_layer_stride = (size_t)h->Mi * 3 * h->D;
+    a.kv_txt = sl.kv_txt; a.txt_layer_stride = (size_t)h->R * h->Tmax * 3 * h->D;
+    a.L = h->c.dec_layers; a.H = h->c.dec_heads; a.D = h->D; a.rows = rows; a.rows_per_clip = ap.rows_per_clip; a.T = T; a.Tmax = h->Tmax;
+    a.N = h->N; a.S_img = sl.S; a.Smax = sl.S;
+    if (sl.ragged) { a.off = sl.off; a.len = sl.len; }
+    a.layer = layer; a.lengths = lengths; a.stats = h->att_stats;
+    a.frame_mass = frame_mass; a.ld_f = ld_f; a.text_mass = text_mass; a.patch_map = patch_map; a.ld_s = ld_s;
+    HIP_OK(h, launch_attn_map(a, s));
     return 0;
 }
 

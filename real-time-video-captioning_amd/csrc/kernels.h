@@ -381,6 +381,28 @@ bool txt_block_ok(int D);
 extern std::atomic<bool> g_txt8;                                          // txtblock.hip: 8-wave workgroups where units > CUs (speed switch 9)
 hipError_t launch_txt_block(const TxtBlockArgs& a, hipStream_t s);
 
+// Per-token attention maps from the cached q | k of a text pass (attnmap.hip): two launches on `s`.  kv_txt [L][.][Tmax][3D] and
+// kv_img [L][.][3D] with their layer strides in elements; rows text rows of T filled positions (from position 0), rows_per_clip rows
+// per clip; N image tokens per frame; dense: clip c's S_img (== Smax) image rows at c * S_img; off / len (both or neither, device
+// int32 [clips]): rows off[c] .. off[c] + len[c] - 1, len[c] a multiple of N and <= Smax.  layer: -1 the mean over all L, or one.
+// lengths (nullable, device int32 [rows]): positions >= lengths[r] are written as zeros.  stats: attn_map_scratch_floats() floats.
+// Out: frame_mass [rows][T][ld_f] (columns 0 .. Smax / N - 1), text_mass [rows][T], patch_map (nullable) [rows][T][ld_s] (columns
+// 0 .. Smax - 1); columns beyond the widths are not written.
+struct AttnMapArgs {
+    const bf16_t* kv_img; size_t img_layer_stride;
+    const bf16_t* kv_txt; size_t txt_layer_stride;
+    int L, H, D, rows, rows_per_clip, T, Tmax, N, S_img, Smax;
+    const int32_t *off, *len;
+    int layer;
+    const int32_t* lengths;
+    float* stats;
+    float* frame_mass; int ld_f;
+    float* text_mass;
+    float* patch_map; int ld_s;
+};
+size_t attn_map_scratch_floats(int L, int H, int rows, int T, int layer);
+hipError_t launch_attn_map(const AttnMapArgs& a, hipStream_t s);
+
 // Small attention of the student decoder (student.hip): one wave per (query row, head), at most 64 keys,
 // any head_dim that is a multiple of 8 (<= 128).  Query m = (r, j), r = m / T: q at
 // q + (r*q_row_stride + q_row_off + j)*ldq + h*hd; key/value i of row r at k|v + (r*keys_stride + i)*ldkv + h*hd.
@@ -394,6 +416,21 @@ struct SmallAttnArgs {
     int M, H, hd;
 };
 hipError_t launch_attn_small(const SmallAttnArgs& a, hipStream_t s);
+// The probabilities of attn_small's cross-attention form (student.hip: cross_probs_kernel), the per-frame attribution of the student
+// (one memory token per frame): one wave per (query m, head), q row m of q (ldq), keys 0 .. F - 1 of row r = m / T at
+// k + (r * keys_stride + i) * ldkv, head h at columns h * hd: probs [M][H][F] fp32 = softmax(q . k / sqrt(hd)), attn_small's own
+// arithmetic.  F <= 64, hd % 8 == 0, hd <= 128.
+struct CrossProbsArgs {
+    const bf16_t* q; int ldq, T;
+    const bf16_t* k; int ldkv, keys_stride, F;
+    float* probs;
+    int M, H, hd;
+};
+hipError_t launch_cross_probs(const CrossProbsArgs& a, hipStream_t s);
+// frame_mass [rows][T][ld_f] (columns 0 .. F - 1) = the mean of probs [L][rows * T][H][F] over the heads and the selected layers
+// (layer = -1: all, ascending; heads ascending: a fixed order); zeros at positions j >= lengths[r] (nullable, device int32 [rows])
+hipError_t launch_cross_mean(const float* probs, int L, int rows, int T, int H, int F, int layer, const int32_t* lengths,
+                             float* frame_mass, int ld_f, hipStream_t s);
 // x[m] = (embed[ids[r*ld_ids + t0 + j]] + pe[t0 + j]) / sqrt(D), m = r*T + j  -> xf (fp32) and xb (bf16)
 hipError_t launch_student_embed(const int64_t* ids, int ld_ids, int rows, int T, int t0, const float* embed,
                                 const float* pe, int D, int vocab, float* xf, bf16_t* xb, hipStream_t s);

@@ -92,6 +92,48 @@ __global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a) {
     }
 }
 
+// attn_small_kernel's cross-attention scores and softmax for one (query, head) -- the same loads, the same order of the products,
+// the same butterflies, __expf and division --, written out instead of being multiplied into V: lane i owns memory token (frame) i
+__global__ __launch_bounds__(64) void cross_probs_kernel(CrossProbsArgs a) {
+    __shared__ float qs[128];
+    const int lane = threadIdx.x, m = blockIdx.x, h = blockIdx.y;
+    const int r = m / a.T;
+    const bf16_t* q = a.q + (size_t)m * a.ldq + h * a.hd;
+    for (int d = lane; d < a.hd; d += 64) qs[d] = bf2f(q[d]);
+    __syncthreads();
+    float s = -INFINITY;
+    if (lane < a.F) {
+        const bf16_t* k = a.k + (size_t)(r * a.keys_stride + lane) * a.ldkv + h * a.hd;
+        float acc = 0.f;
+        for (int c = 0; c < a.hd; c += 8) {
+            const bf16x8 kk = *(const bf16x8*)(k + c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc += qs[c + e] * bf2f((bf16_t)kk[e]);
+        }
+        s = acc * rsqrtf((float)a.hd);
+    }
+    const float mx = wave_max(s);
+    const float p = lane < a.F ? __expf(s - mx) : 0.f;
+    const float den = wave_sum(p);
+    if (lane < a.F) a.probs[((size_t)m * a.H + h) * a.F + lane] = p / den;
+}
+
+// one thread per (m, frame): layers, then heads, ascending
+__global__ void cross_mean_kernel(const float* __restrict__ probs, int L, int M, int T, int H, int F, int layer, const int32_t* __restrict__ lengths,
+                                  float* __restrict__ out, int ld_f) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M * F) return;
+    const int m = i / F, f = i - m * F, r = m / T, j = m - r * T;
+    float acc = 0.f;
+    if (!lengths || j < lengths[r]) {
+        const int l0 = layer < 0 ? 0 : layer, l1 = layer < 0 ? L : layer + 1;
+        for (int l = l0; l < l1; ++l)
+            for (int h = 0; h < H; ++h) acc += probs[(((size_t)l * M + m) * H + h) * F + f];
+        acc = acc / (float)((l1 - l0) * H);
+    }
+    out[(size_t)m * ld_f + f] = acc;
+}
+
 struct StuLayer {
     const bf16_t *sa_in_w, *sa_out_w, *ca_in_w, *ca_out_w, *l1w, *l2w;
     const float *sa_in_b, *sa_out_b, *ca_in_b, *ca_out_b, *l1b, *l2b, *n1w, *n1b, *n2w, *n2b, *n3w, *n3b;
@@ -102,6 +144,23 @@ struct StuLayer {
 hipError_t launch_attn_small(const SmallAttnArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.H <= 0 || a.hd % 8 || a.hd > 128 || a.nkeys > 64 || (a.nkeys == 0 && a.t0 + a.T > 64)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(attn_small_kernel, dim3(a.M, a.H), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cross_probs(const CrossProbsArgs& a, hipStream_t s) {
+    if (!a.q || !a.k || !a.probs || a.M <= 0 || a.T <= 0 || a.M % a.T || a.H <= 0 || a.hd <= 0 || a.hd % 8 || a.hd > 128 || a.F <= 0 || a.F > 64)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cross_probs_kernel, dim3(a.M, a.H), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cross_mean(const float* probs, int L, int rows, int T, int H, int F, int layer, const int32_t* lengths,
+                             float* frame_mass, int ld_f, hipStream_t s) {
+    if (!probs || !frame_mass || L <= 0 || rows <= 0 || T <= 0 || H <= 0 || F <= 0 || layer < -1 || layer >= L || ld_f < F ||
+        (int64_t)rows * T * F > 0x7fffffff)
+        return hipErrorInvalidValue;
+    const int n = rows * T * F;
+    hipLaunchKernelGGL(cross_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, s, probs, L, rows * T, T, H, F, layer, lengths, frame_mass, ld_f);
     return hipGetLastError();
 }
 
@@ -213,6 +272,10 @@ struct gitcap_student : HandleCore {
     int64_t* g_tk_ids = nullptr;
     float* g_tk_lp = nullptr;
     float* score_buf = nullptr;         // gitcap_student_score (first use): [2][Mt] target logits, lp rows the caller did not ask for
+    // gitcap_student_attention (first use): att_probs [L][Mt][H][F] cross-attention probabilities; att_on: the pass being issued
+    // writes them (one more launch per layer behind the cross-attention q projection), off for every other call
+    float* att_probs = nullptr;
+    bool att_on = false;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -339,6 +402,8 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
         if ((rc = proj(SK_BIAS_BF16, Ly.ca_in_w, Ly.ca_in_b, D, h->qc, D, 1, 1, 0))) return rc;
         const bf16_t* mkv = h->memkv + (size_t)l * mem_layer;
         SmallAttnArgs ca{h->qc, D, T, T, 0, mkv, mkv + D, 2 * D, h->F, h->F, 0, nullptr, 0, 0, h->ctx, D, M, h->H, h->hd};
+        if (h->att_on)      // gitcap_student_attention: the probabilities of the launch below, from the q and memory K it reads
+            HIP_OK(h, launch_cross_probs(CrossProbsArgs{h->qc, D, T, mkv, 2 * D, h->F, h->F, h->att_probs + (size_t)l * M * h->H * h->F, M, h->H, h->hd}, s));
         HIP_OK(h, launch_attn_small(ca, s));
         if ((rc = dense_ln(h->ctx, D, Ly.ca_out_w, Ly.ca_out_b, Ly.n2w, Ly.n2b, true))) return rc;
         // feed-forward (the last layer's LayerNorm is a launch: the vocabulary head reads its bf16 output)
@@ -1001,6 +1066,28 @@ int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, in
     TextReq q;
     q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.T = T; q.score = &sq;
     return text_forward(h, q, (hipStream_t)stream);
+}
+
+// The per-frame attribution of given captions: gitcap_student_score's pass without the head, its cross-attention probabilities kept
+int gitcap_student_attention(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, int layer, const int32_t* lengths,
+                             float* frame_mass, int ld_f, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attention: null handle");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attention: weights not finalized");
+    if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student_attention before set_memory");
+    if (!frame_mass || T < 1 || ld_ids < T || ld_f < h->F || layer < -1 || layer >= h->L || (((uintptr_t)frame_mass | (uintptr_t)lengths) & 3) != 0)
+        return fail(h, GITCAP_ERR_ARG, "student_attention: null or misaligned output, T < 1, ld_ids < T, ld_f < mem_tokens, or layer outside [-1, layers)");
+    if (rows <= 0 || (int64_t)rows * T > h->Mt) return fail(h, GITCAP_ERR_ARG, "student_attention: rows x T beyond the handle's row workspace");
+    GUARD(h);
+    int rc;
+    if (!h->att_probs && (rc = dev_alloc(h, &h->att_probs, (size_t)h->L * h->Mt * h->H * h->F))) return rc;
+    TextReq q;
+    q.ids = ids; q.ld_ids = ld_ids; q.rows = rows; q.T = T;
+    h->att_on = true;
+    rc = text_forward(h, q, (hipStream_t)stream);
+    h->att_on = false;
+    if (rc) return rc;
+    HIP_OK(h, launch_cross_mean(h->att_probs, h->L, rows, T, h->H, h->F, layer, lengths, frame_mass, ld_f, (hipStream_t)stream));
+    return 0;
 }
 
 int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int n, void* stream) {

@@ -15,6 +15,9 @@ def __getattr__(name):
     if name == "caption_confidence":
         from .confidence import caption_confidence
         return caption_confidence
+    if name == "frame_attribution":
+        from .confidence import frame_attribution
+        return frame_attribution
     if name == "soft_labels":
         from .scoring import soft_labels
         return soft_labels

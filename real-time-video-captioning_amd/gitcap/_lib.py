@@ -78,6 +78,14 @@ class CDbgAttnSmallArgs(ctypes.Structure):
                 ("hd", c_int32)]
 
 
+class CDbgAttnMapArgs(ctypes.Structure):
+    """struct gitcap_dbg_attn_map_args (include/gitcap.h)."""
+    _fields_ = [("kv_txt", c_void_p), ("kv_img", c_void_p), ("L", c_int32), ("H", c_int32), ("D", c_int32), ("rows", c_int32),
+                ("rows_per_clip", c_int32), ("T", c_int32), ("Tmax", c_int32), ("N", c_int32), ("S_img", c_int32), ("Smax", c_int32),
+                ("img_rows", c_int32), ("off", c_void_p), ("len", c_void_p), ("layer", c_int32), ("lengths", c_void_p),
+                ("frame_mass", c_void_p), ("ld_f", c_int32), ("text_mass", c_void_p), ("patch_map", c_void_p), ("ld_s", c_int32)]
+
+
 # every symbol include/gitcap.h declares (tests/test_cabi.py checks the list against the header)
 SYMBOLS = {
     "gitcap_abi_version": (c_int, []),
@@ -184,6 +192,9 @@ SYMBOLS = {
     "gitcap_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    # attention maps (GitCaptioner.attention; tests/test_attention_map_gpu.py)
+    "gitcap_attention_map": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_attn_map": (c_int, [POINTER(CDbgAttnMapArgs), c_void_p]),
     # teacher-student divergence (gitcap/distill.py; tests/test_distill_gpu.py): the call, the dual head, the merge
     "gitcap_distill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_float, POINTER(CDistillOut),
                                c_void_p]),
@@ -262,6 +273,9 @@ SYMBOLS = {
     "gitcap_student_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "gitcap_student_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_student_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_cross_probs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_void_p]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),

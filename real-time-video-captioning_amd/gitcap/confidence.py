@@ -48,3 +48,26 @@ def top_margin(top_logprobs: torch.Tensor) -> torch.Tensor:
         return torch.full_like(first, float("inf"))
     second = top_logprobs[..., 1].float()
     return torch.where(torch.isneginf(second), torch.full_like(first, float("inf")), first - second)
+
+
+def frame_attribution(result) -> dict:
+    """Which frame each token comes from, out of the dict ``GitCaptioner.attention`` / ``StudentCaptioner.attention`` returns (or a
+    ``frame_attention`` tensor [.., T-1, F] itself).  -> dict: ``frame`` int64 [.., T-1], the frame with the largest attention mass
+    per token (-1 at positions behind a row's length, whose masses are all zero); ``mean_mass`` fp32 [.., F], the caption-level
+    mean mass per frame over the row's live positions (zeros for a row without any) -- frames near 0 are frames the decoder
+    never looks at; ``image_share`` fp32 [..], the mean over the live positions of the mass on ALL frames (1 - the mass on the
+    caption's own tokens): low values are tokens that come from the language prior.  Plain torch ops."""
+    fa = result["frame_attention"] if isinstance(result, dict) else result
+    if fa.dim() < 2:
+        raise ValueError(f"expected frame_attention [.., T-1, F], got {tuple(fa.shape)}")
+    fa = fa.float()
+    total = fa.sum(dim=-1)
+    ta = result.get("text_attention") if isinstance(result, dict) else None
+    live = (total + ta.float() > 0) if ta is not None else (total > 0)
+    if fa.shape[-1] == 0:
+        frame = torch.full(fa.shape[:-1], -1, dtype=torch.int64, device=fa.device)
+    else:
+        frame = torch.where(live, fa.argmax(dim=-1), torch.full_like(total, -1, dtype=torch.int64))
+    cnt = live.sum(dim=-1).clamp(min=1).to(torch.float32)
+    mean_mass = torch.where(live[..., None], fa, torch.zeros_like(fa)).sum(dim=-2) / cnt[..., None]
+    return dict(frame=frame, mean_mass=mean_mass, image_share=torch.where(live, total, torch.zeros_like(total)).sum(dim=-1) / cnt)

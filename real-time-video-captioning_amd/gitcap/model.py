@@ -973,6 +973,64 @@ class GitCaptioner(_NativeModule):
         return scoring.result(chunks, B, n, had_n, return_top1, out_dev)
 
     @torch.no_grad()
+    def attention(self, x: torch.Tensor, y: torch.Tensor, *, layer: Optional[int] = None, patches: bool = False,
+                  lengths: Optional[torch.Tensor] = None, until_sep: bool = True, frame_counts=None) -> dict:
+        """Which frames and patches every token of GIVEN captions comes from: the decoder's attention probabilities, averaged over
+        the heads and over all layers (``layer=None``) or one (``layer=l``), read back from the K/V cache of score's pass
+        (include/gitcap.h: gitcap_attention_map).  ``x``, ``y``, ``lengths``, ``until_sep``, ``frame_counts`` as in score.
+        -> dict: ``frame_attention`` fp32 [B, (n,) T-1, Fmax], the probability mass on each frame's image tokens (0 for frames a
+        clip of a ragged batch does not have); ``text_attention`` fp32 [B, (n,) T-1], the mass on the caption's own tokens (the
+        two sum to 1); with ``patches`` also ``patch_attention`` fp32 [B, (n,) T-1, Fmax, N], the mean probability of every image
+        token (N per frame, the class token first).  Index j is the position that predicts y[..., j + 1], as in score; positions
+        behind a row's length hold zeros.  Every clip's values are bit for bit those of the clip alone, and those of
+        greedy_decode(return_attention=True) for the same tokens."""
+        from . import scoring
+        ids, had_n = scoring.candidates(y, self._dev)
+        B, n, T = ids.shape
+        if T < 2:
+            raise ValueError("attention needs CLS and at least one token")
+        lay = -1 if layer is None else int(layer)
+        if not -1 <= lay < self.cfg.dec_layers:
+            raise ValueError(f"layer={layer} outside 0..{self.cfg.dec_layers - 1}")
+        ln = scoring.row_lengths(ids, self.sep_token_id, until_sep, lengths)
+        Bc = min(B, self.max_batch)
+        N = (self.cfg.image_size // self.cfg.patch_size) ** 2 + 1
+        fms, tms, pms = [], [], []
+        # score's pass chunk by chunk (its outputs are not kept), the maps behind each chunk from the cache it filled
+        for b0 in range(0, B, Bc):
+            b1 = min(B, b0 + Bc)
+            xs = x[b0:b1] if isinstance(x, torch.Tensor) else x[b0:b1]
+            fc = None if frame_counts is None else frame_counts[b0:b1]
+            self.score(xs, ids[b0:b1] if had_n else ids[b0:b1, 0], lengths=None if ln is None else (ln[b0:b1] if had_n else ln[b0:b1, 0]),
+                       until_sep=False, frame_counts=fc)
+            rows = (b1 - b0) * n
+            with torch.cuda.device(self._dev):
+                if fc is not None:
+                    F = int(max(int(c) for c in fc))
+                elif not isinstance(x, torch.Tensor):
+                    F = max(int(c.shape[0]) for c in xs)
+                else:
+                    F = int(x.shape[1]) if x.dim() == 5 else int(x.shape[1]) // N
+                fm = torch.empty((rows, T - 1, F), dtype=torch.float32, device=self._dev)
+                tm = torch.empty((rows, T - 1), dtype=torch.float32, device=self._dev)
+                pm = torch.empty((rows, T - 1, F * N), dtype=torch.float32, device=self._dev) if patches else None
+                cl = None if ln is None else (ln[b0:b1].reshape(rows) - 1).clamp_(min=0).to(torch.int32).contiguous()
+                self._call("gitcap_attention_map", rows, T - 1, lay, _lib.ptr(cl), _lib.ptr(fm), F, _lib.ptr(tm), _lib.ptr(pm), F * N,
+                           self._stream())
+            fms.append(fm)
+            tms.append(tm)
+            pms.append(pm)
+        out_dev = x.device if isinstance(x, torch.Tensor) else x[0].device
+        Fmax = max(f.shape[2] for f in fms)
+        pad = lambda t, w: t if t.shape[2] == w else torch.nn.functional.pad(t, (0, w - t.shape[2]))
+        shape = (B, n) if had_n else (B,)
+        out = dict(frame_attention=torch.cat([pad(f, Fmax) for f in fms], 0).reshape(*shape, T - 1, Fmax).to(out_dev),
+                   text_attention=torch.cat(tms, 0).reshape(*shape, T - 1).to(out_dev))
+        if patches:
+            out["patch_attention"] = torch.cat([pad(p, Fmax * N) for p in pms], 0).reshape(*shape, T - 1, Fmax, N).to(out_dev)
+        return out
+
+    @torch.no_grad()
     def rerank(self, x: torch.Tensor, candidates: torch.Tensor, length_penalty: float = 0.6, frame_counts=None) -> dict:
         """Order n candidate captions per clip ([B, n, T], e.g. infer(num_keep_best=n), sampled captions, the student's beams)
         by this model's sum / count ** length_penalty, the BeamHypotheses score of the reference's search.  -> score()'s dict
@@ -1108,7 +1166,7 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None, return_logprobs: bool = False,
                       prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                      frame_counts=None, draft: Optional[torch.Tensor] = None, top_logprobs: int = 0):
+                      frame_counts=None, draft: Optional[torch.Tensor] = None, top_logprobs: int = 0, return_attention: bool = False):
         """CLS-prefixed greedy ids [B, 1+steps] (model.py:156-187).  stop='all_sep' is the
         reference rule (break when every row emits SEP in the same step, :184); 'never' always
         runs max_len steps.  The loop runs on the device without per-step host syncs; the
@@ -1139,9 +1197,15 @@ class GitCaptioner(_NativeModule):
         logprobs with return_logprobs): the k best tokens of the distribution each step chose from and their log-probabilities,
         ranked by (logit descending, id ascending); rank 0 is the emitted token (its value == the logprobs column) except at a
         position a prompt forces, which reports the model's own ranks.  Ranks a row cannot fill (bans) hold -1 / -inf.  No
-        logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it."""
+        logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it.
+        return_attention=True: the result gains, last, ``frame_attention`` fp32 [B, steps, Fmax] and ``text_attention`` fp32
+        [B, steps]: per emitted token the attention mass on each frame and on the caption so far, averaged over heads and
+        layers (see attention()), read from the K/V cache the loop just filled -- no extra pass; bit for bit attention(x, ids).
+        Not with ``draft``."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if return_attention and draft is not None:
+            raise ValueError("return_attention= is not combined with draft= (use attention(x, ids) on the result)")
         if draft is not None and (prompt is not None or no_repeat_ngram_size or min_length or suppress_tokens is not None):
             raise ValueError("draft= is not combined with prompt= or the constraint arguments")
         stop = stop or self.stop
@@ -1157,8 +1221,8 @@ class GitCaptioner(_NativeModule):
         if draft is not None and (draft.dim() != 2 or draft.shape[0] != B or draft.shape[1] < 2 or draft.dtype != torch.int64):
             raise ValueError(f"draft must be int64 [{B}, 1+n] with n >= 1, got {draft.dtype} {tuple(draft.shape)}")
         if in_dev.type == "cpu":                  # CPU tensor in -> CPU ids out (real_time_inference.py:57): the copy back is a
-            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft))    # synchronisation, so the result is vouched for
-        return self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft)
+            return self._vouched(lambda: self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft, return_attention))    # synchronisation, so the result is vouched for
+        return self._greedy_decode(src, max_len, mode, return_logprobs, opts, rg, draft, return_attention)
 
     def _greedy_options(self, B, max_len, prompt, prompt_lengths, no_repeat_ngram_size, min_length, suppress_tokens, rg=None):
         """The option arguments of the greedy calls (rg: the ragged batch, or None) -> _CallOptions"""
@@ -1201,7 +1265,7 @@ class GitCaptioner(_NativeModule):
         self._call("gitcap_draft_stats", out)
         return tuple(int(v) for v in out)
 
-    def _greedy_decode(self, src, max_len, mode, want_lp=False, opts=None, rg=None, draft=None):
+    def _greedy_decode(self, src, max_len, mode, want_lp=False, opts=None, rg=None, draft=None, want_att=False):
         """rg: the (clips, counts, raw) of a ragged batch (src is then unused): each chunk of at most max_batch clips is packed
         and runs with its counts attached.  draft: greedy_decode's (fp32 frames; camera frames are decoded by the plain call)."""
         self._drain()
@@ -1212,7 +1276,7 @@ class GitCaptioner(_NativeModule):
             fr, raw, src = None, rg[2], rg[0][0]  # (src: where the results go)
         if draft is not None and raw:
             raise ValueError("draft= takes transformed fp32 frames (there is no draft form of the camera-frame call)")
-        outs, steps_all, lps, accepted, tks = [], [], [], [], []
+        outs, steps_all, lps, accepted, tks, atts = [], [], [], [], [], []
         # (a batch of several chunks stops by the rule over the WHOLE batch, below: its chunks decode every step)
         dmode = mode if draft is None or (len(rg[1]) if rg is not None else fr.shape[0]) <= self.max_batch else STOP_NEVER
         with torch.cuda.device(self._dev):
@@ -1238,6 +1302,11 @@ class GitCaptioner(_NativeModule):
                 else:
                     self._call("gitcap_greedy", _lib.ptr(chunk), nb, F, max_len, mode, _lib.ptr(ids), _lib.ptr(steps),
                                self._stream())
+                if want_att:        # the maps of the positions the loop just cached (include/gitcap.h: gitcap_attention_map)
+                    fm = torch.empty((nb, max_len, F), dtype=torch.float32, device=self._dev)
+                    tm = torch.empty((nb, max_len), dtype=torch.float32, device=self._dev)
+                    self._call("gitcap_attention_map", nb, max_len, -1, None, _lib.ptr(fm), F, _lib.ptr(tm), None, 0, self._stream())
+                    atts.append((fm, tm))
                 outs.append(ids)
                 steps_all.append(steps)
         self._last_memory = None
@@ -1258,6 +1327,10 @@ class GitCaptioner(_NativeModule):
             out += (mv(torch.cat(lps, 0)[:, :ids.shape[1] - 1]),)
         if tks:
             out += tuple(mv(torch.cat([t[i] for t in tks], 0)[:, :ids.shape[1] - 1]) for i in (0, 1))
+        if atts:
+            Fm = max(a[0].shape[2] for a in atts)
+            fm = torch.cat([a[0] if a[0].shape[2] == Fm else torch.nn.functional.pad(a[0], (0, Fm - a[0].shape[2])) for a in atts], 0)
+            out += (mv(fm[:, :ids.shape[1] - 1]), mv(torch.cat([a[1] for a in atts], 0)[:, :ids.shape[1] - 1]))
         return out if len(out) > 1 else out[0]
 
     generate = greedy_decode      # the name BASELINE.json's north_star uses for this entry point
@@ -1265,7 +1338,7 @@ class GitCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode_async(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                             coalesce: int = 1, prompt=None, prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                            suppress_tokens=None, frame_counts=None, top_logprobs: int = 0) -> "CaptionFuture":
+                            suppress_tokens=None, frame_counts=None, top_logprobs: int = 0, return_attention: bool = False) -> "CaptionFuture":
         """Pipelined greedy_decode for a stream of batches: returns immediately with a future; up to
         FOUR submissions may be in flight, so one batch's image pass (MFMA bound) overlaps the token
         loops (latency bound) of the batches before it on the handle's internal HIP streams.  Call
@@ -1285,6 +1358,8 @@ class GitCaptioner(_NativeModule):
         only with batches that carry equal constraints.  frame_counts (or a list of clips) as in greedy_decode: a ragged batch is
         packed once (host clips: in the staging ring's pinned buffer) and submitted on its own (it does not coalesce).
         top_logprobs=k as in greedy_decode: ``result()`` returns (ids, top_ids, top_logprobs); batches coalesce with equal k."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by greedy_decode_async (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         stop = stop or self.stop
@@ -1405,7 +1480,7 @@ class GitCaptioner(_NativeModule):
               per_node_beam_size: int = 2, num_keep_best: int = 1, save_logits: bool = False,
               on_device: Optional[bool] = None, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
               top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
-              prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, frame_counts=None) -> dict:
+              prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, frame_counts=None, return_attention: bool = False) -> dict:
         """GIT inference with beam search = ``GenerativeImageTextModel.infer`` (model.py:426-462) driven by
         ``GeneratorWithBeamSearchV2.search`` (model.py:479-678; defaults of :702-708).  Returns the
         reference's output dict: predictions [B, max_steps] (CLS-prefixed, EOS padded; [B, num_keep_best, max_steps] by descending
@@ -1438,6 +1513,8 @@ class GitCaptioner(_NativeModule):
         frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length.  The device search runs the
         batch packed, every clip's result bit for bit that of the clip alone; on_device=False runs the host operator clip by clip
         (the reference's teacher loop, model.py:765).  ``visual_features`` comes padded with ``visual_features_valid``."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by the beam family (infer) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         from .search import GeneratorWithBeamSearch
         if beam_size > self.max_beams:
             raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
@@ -1627,7 +1704,7 @@ class GitCaptioner(_NativeModule):
                     num_keep_best: int = 1, repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                     top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
                     prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                    frame_counts=None) -> "InferFuture":
+                    frame_counts=None, return_attention: bool = False) -> "InferFuture":
         """Pipelined ``infer`` (the device-resident search) for a stream of batches: returns at once with a future; up to FOUR
         submissions (of this kind or of greedy_decode_async) may be in flight, so one batch's image pass overlaps the search loops
         of the batches before it.  ``result()`` returns ``infer``'s dict; with ``save_logits`` its ``logits_dict`` is one device
@@ -1636,6 +1713,8 @@ class GitCaptioner(_NativeModule):
         synchronous call, with do_sample too (its arguments as in ``infer``; the seed is fixed at submission and returned as
         ``seed``) and with prompt / prompt_lengths (as in ``infer``; the dict gains ``prompt_lengths``) and with no_repeat_ngram_size / min_length / suppress_tokens (as in ``infer``).
         `src` as in greedy_decode_async: fp32 frames or uint8 camera frames, on the device or in host memory (staged through the pinned ring)."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by the beam family (infer_async) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         sampling = self._seeded(self._sampling(do_sample, temperature, top_k, top_p, seed))
         self._check_device_search(beam_size, per_node_beam_size, num_keep_best, repetition_penalty, sampling)
         if beam_size > self.max_beams:
@@ -1672,7 +1751,7 @@ class GitCaptioner(_NativeModule):
                        repetition_penalty: float = 1.0, do_sample: bool = False, top_k: Optional[int] = None,
                        top_p: Optional[float] = None, temperature: float = 1.0, seed: Optional[int] = None, prompt=None,
                        prompt_lengths=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
-                       carry: bool = False, top_logprobs: int = 0) -> CaptionStream:
+                       carry: bool = False, top_logprobs: int = 0, return_attention: bool = False) -> CaptionStream:
         """A sliding caption window over live frames (the reference's real-time loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last `window` frames (default: the model's num_frames) once the
         window is full and `hop` frames have arrived since the last one, else None.  Each frame is encoded once.  Greedy by
@@ -1690,6 +1769,8 @@ class GitCaptioner(_NativeModule):
         (greedy_decode's ``draft``): the same captions; ``stream.stats()`` tells how much of the drafts was accepted.
         ``top_logprobs=k`` (greedy streams without ``carry``): ``stream.last_top_ids`` / ``stream.last_top_logprobs`` [B, steps, k]
         of the caption the last push returned (greedy_decode's top_logprobs)."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if top_logprobs and (beam_size is not None or carry):

@@ -302,6 +302,46 @@ class StudentCaptioner(_NativeModule):
                 chunks.append(buf)
         return scoring.result(chunks, B, n, had_n, return_top1, x.device)
 
+    @torch.no_grad()
+    def attention(self, x: torch.Tensor, y: torch.Tensor, *, layer: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
+                  until_sep: bool = True) -> dict:
+        """Which frame every token of GIVEN captions comes from (include/gitcap.h: gitcap_student_attention).  The student's memory
+        is one token per frame, so its cross-attention is the attribution: ``frame_attention`` fp32 [B, (n,) T-1, F], the
+        cross-attention probabilities averaged over the heads and over all layers (``layer=None``) or one; each position's F
+        values sum to 1.  ``x``, ``y``, ``lengths``, ``until_sep`` as in score; index j is the position that predicts
+        y[..., j + 1]; positions behind a row's length hold zeros.  One teacher-forced pass (score's, without the head)."""
+        from . import scoring
+        ids, had_n = scoring.candidates(y, self._dev)
+        B, n, T = ids.shape
+        if x.shape[0] != B:
+            raise ValueError("x and y disagree on the number of clips")
+        if T < 2 or T > self.max_text_len + 1:
+            raise ValueError(f"T={T} outside 2..max_text_len+1={self.max_text_len + 1}")
+        if n > self.max_batch:
+            raise ValueError(f"{n} candidates per clip > max_batch={self.max_batch} rows the handle was created for")
+        lay = -1 if layer is None else int(layer)
+        if not -1 <= lay < self.cfg.num_decoder_layers:
+            raise ValueError(f"layer={layer} outside 0..{self.cfg.num_decoder_layers - 1}")
+        ln = scoring.row_lengths(ids, self.cfg.sep_token_id, until_sep, lengths)
+        Bc = min(B, self.max_batch // n)
+        F = self.cfg.mem_tokens
+        outs = []
+        with torch.cuda.device(self._dev):
+            for b0 in range(0, B, Bc):
+                b1 = min(B, b0 + Bc)
+                mem = self._memory(self._src_memory(x[b0:b1]))
+                if n > 1:
+                    mem = mem.repeat_interleave(n, dim=0)
+                rows = (b1 - b0) * n
+                cid = ids[b0:b1].reshape(rows, T)
+                cl = None if ln is None else (ln[b0:b1].reshape(rows) - 1).clamp_(min=0).to(torch.int32).contiguous()
+                fm = torch.empty((rows, T - 1, F), dtype=torch.float32, device=self._dev)
+                self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
+                self._call("gitcap_student_attention", _lib.ptr(cid), T, rows, T - 1, lay, _lib.ptr(cl), _lib.ptr(fm), F, self._stream())
+                outs.append(fm)
+        shape = (B, n) if had_n else (B,)
+        return dict(frame_attention=torch.cat(outs, 0).reshape(*shape, T - 1, F).to(x.device))
+
     def forward(self, x: torch.Tensor, y: torch.Tensor):
         """model.py:99-106: feature maps + [logits]."""
         fmaps, memory = self.forward_image_enc(x)
@@ -340,7 +380,8 @@ class StudentCaptioner(_NativeModule):
 
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
-                      draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0):
+                      draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0,
+                      return_attention: bool = False):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
@@ -352,7 +393,9 @@ class StudentCaptioner(_NativeModule):
         log_softmax(step t's logits)[ids[:, t + 1]]; with a ``draft`` bit for bit the values without it.
         ``top_logprobs=k`` (1..32): the result gains ``top_ids`` int64 / ``top_logprobs`` fp32 [B, steps, k] behind ids (and
         logprobs): every step's k best tokens by (logit descending, id ascending) and their log-probabilities; rank 0 is the
-        emitted token.  No logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it."""
+        emitted token.  No logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it.
+        ``return_attention``: the result gains, last, ``frame_attention`` fp32 [B, steps, F] (see attention()), from one
+        teacher-forced pass over the result behind the loop: bit for bit attention(src, ids, until_sep=False)."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         out_dev = src.device
@@ -383,16 +426,25 @@ class StudentCaptioner(_NativeModule):
             out += (mv(lp[:, :n]),)
         if tk is not None:
             out += (mv(tk[0][:, :n]), mv(tk[1][:, :n]))
+        if return_attention:
+            fm = torch.empty((B, n, self.cfg.mem_tokens), dtype=torch.float32, device=self._dev)
+            if n:
+                with torch.cuda.device(self._dev):      # the memory of the loop is still the handle's
+                    self._call("gitcap_student_attention", _lib.ptr(ids), max_len + 1, B, n, -1, None, _lib.ptr(fm), self.cfg.mem_tokens,
+                               self._stream())
+            out += (mv(fm),)
         return out if len(out) > 1 else out[0]
 
     generate = greedy_decode
 
     @torch.no_grad()
-    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
+    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False) -> torch.Tensor:
         """model.py:189-318: k beams without end-of-sequence handling; returns the best beam [B, max_len].
         Runs on the device with the exact KV cache and no host round trip (``gitcap_student_beam_search``): the k beams
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by the beam family (beam_search) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
@@ -410,7 +462,7 @@ class StudentCaptioner(_NativeModule):
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
-                       logprobs: bool = False, top_logprobs: int = 0) -> StudentCaptionStream:
+                       logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -425,6 +477,8 @@ class StudentCaptioner(_NativeModule):
         log-probabilities [B, steps] (greedy_decode's return_logprobs); works with ``gate`` and ``carry``.
         ``top_logprobs=k`` (greedy streams without ``carry``: a draft call does not carry alternatives): ``stream.last_top_ids`` /
         ``stream.last_top_logprobs`` [B, steps, k] of that caption (greedy_decode's top_logprobs)."""
+        if return_attention:
+            raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if top_logprobs and (beams is not None or carry):
