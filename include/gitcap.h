@@ -974,6 +974,11 @@ typedef struct gitcap_dbg_attn_small_args {
     int32_t M, H, hd;
 } gitcap_dbg_attn_small_args;
 int gitcap_dbg_attn_small(const gitcap_dbg_attn_small_args* a, void* stream);
+/* The variable-length form the student's cross-attention takes for clips of different length (gitcap_student_attach_frame_counts):
+ * k | v are PACKED and the keys of text row r are rows key_off[r] .. key_off[r] + key_len[r] - 1 of them (device int32 [M / T] each,
+ * 1 <= key_len <= 64).  nkeys, keys_stride and t0 of the struct are not read; ids must be NULL.  A row with key_len = n holds the bits
+ * of gitcap_dbg_attn_small at nkeys = n on that row's keys.  Synchronises `stream` (the tables are checked on the host first). */
+int gitcap_dbg_attn_small_varlen(const gitcap_dbg_attn_small_args* a, const int32_t* key_off, const int32_t* key_len, void* stream);
 
 /* Residual stream of the ViT per block (tests/test_stress_layers_gpu.py: single-block checks on the device's own inputs).
  * While `buf` is non-NULL every SYNCHRONOUS image pass (gitcap_encode / _greedy / _beam_search and their _raw forms) copies
@@ -1128,6 +1133,37 @@ int gitcap_student_attention(gitcap_student_t* h, const int64_t* ids, int ld_ids
  * hd <= 128, ldkv % 8 == 0. */
 int gitcap_dbg_cross_probs(const void* q, const void* k, int ldkv, int rows, int T, int H, int hd, int F, const int32_t* lengths, float* probs,
                            float* frame_mass, int ld_f, void* stream);
+/* Its variable-length form: k is PACKED, row r's keys are rows key_off[r] .. key_off[r] + key_len[r] - 1 of it (device int32 [rows]
+ * each, 1 <= key_len <= F).  probs stays [rows * T][H][F]: columns from key_len[r] on hold 0, the others the bits of
+ * gitcap_dbg_cross_probs at F = key_len[r] on that row's keys.  Synchronises `stream` (the tables are checked on the host first). */
+int gitcap_dbg_cross_probs_varlen(const void* q, const void* k, int ldkv, int rows, int T, int H, int hd, int F, const int32_t* lengths, float* probs,
+                                  float* frame_mass, int ld_f, const int32_t* key_off, const int32_t* key_len, void* stream);
+
+/* Clips of different length on the student: gitcap_attach_frame_counts for this handle.  The decoder has no positional or temporal
+ * term on its memory (model.py:102 and :130-131 are commented out), so a clip of any number of frames is a well-defined input: its
+ * cross-attention runs over its own frames and nothing else.
+ *   counts  host int32 [B], 1 <= counts[b] <= mem_tokens, B <= max_rows; copied.  NULL detaches.
+ * One-shot: consumed by the next of gitcap_student_set_memory, gitcap_student_greedy, gitcap_student_beam_search and
+ * gitcap_student_greedy_draft (success or failure), whose B must be the counts' and whose `memory` is then PACKED: device fp32
+ * [sum(counts)][d_model], clip-major, no padding.  Exactly sum(counts) rows are cast and projected; the k beams of a clip share its
+ * rows (nothing is repeated).  The layout belongs to the memory set: gitcap_student_forward_decoder, _score, _attention and the student
+ * rows of gitcap_distill follow it until the next memory is set.  Every clip's results are bit for bit those of the clip run alone on
+ * a handle created with mem_tokens = counts[b]; counts that all equal mem_tokens run the dense call, launch for launch.
+ * gitcap_student_attention keeps ld_f >= mem_tokens; the columns from a clip's count on hold 0.  The captured token loops read the
+ * counts from two device tables at replay: one graph per (B, max_len, ...) serves every set of counts.
+ * The gitcap_student_window_* calls do not take counts: with counts attached they fail with GITCAP_ERR_ARG and a message that
+ * names the attachment, which they consume.
+ * Errors: GITCAP_ERR_ARG for a null handle, B outside [1, max_rows], a count outside [1, mem_tokens] (the message names the clip),
+ * and at the consuming call for a B that is not the counts'. */
+int gitcap_student_attach_frame_counts(gitcap_student_t* h, const int32_t* counts, int B);
+/* gitcap_student_window_greedy before the window is full: captions the n tokens pushed since the reset (1 <= n; n >= mem_tokens is
+ * gitcap_student_window_greedy itself), so a live stream shows a caption from its first admitted frame on.  All clips of a window
+ * share n.  Bit for bit gitcap_student_greedy on those n tokens per clip with counts = n attached.  frames_out (host int32,
+ * nullable) = the tokens the caption saw, min(n, mem_tokens).  Takes the log-probability and top-k attachments as
+ * gitcap_student_window_greedy does.  The beam and draft window calls have no partial form: they need a full window.
+ * GITCAP_ERR_STATE when nothing has been pushed since the reset. */
+int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* frames_out,
+                                         void* stream);
 
 /* Teacher-student divergence of given captions, forward only: KL(teacher || student) of every position's next-token distribution
  * at a temperature -- LOSS 2 of DistillationTrainer.training_step (src/models/model.py:919-935: KLDivLoss('batchmean') of

@@ -116,6 +116,28 @@ int gitcap_dbg_cross_probs(const void* q, const void* k, int ldkv, int rows, int
     return dbg_rc(e);
 }
 
+// its variable-length form (cross_probs_kernel<true>): k is PACKED, row r's keys are rows key_off[r] .. + key_len[r] - 1 of it (device
+// int32 [rows] each); probs stays [M][H][F], zeros from key_len[r] on.  The tables are read back first (the call synchronises
+// `stream`): a length outside [1, F] or a negative offset is refused before any launch.
+int gitcap_dbg_cross_probs_varlen(const void* q, const void* k, int ldkv, int rows, int T, int H, int hd, int F, const int32_t* lengths, float* probs,
+                                  float* frame_mass, int ld_f, const int32_t* key_off, const int32_t* key_len, void* stream) {
+    if (!q || !k || !probs || !frame_mass || !key_off || !key_len || rows <= 0 || T <= 0 || H <= 0 || hd <= 0 || F <= 0 || F > 64 || ldkv < H * hd ||
+        (ldkv & 7) != 0 || ld_f < F || (int64_t)rows * T * H * F > 0x7fffffff || (((uintptr_t)q | (uintptr_t)k) & 15) != 0 ||
+        (((uintptr_t)probs | (uintptr_t)frame_mass | (uintptr_t)lengths | (uintptr_t)key_off | (uintptr_t)key_len) & 3) != 0)
+        return GITCAP_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> tab(2 * (size_t)rows);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(tab.data(), key_off, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(tab.data() + rows, key_len, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return GITCAP_ERR_HIP;
+    for (int r = 0; r < rows; ++r)
+        if (tab[r] < 0 || tab[rows + r] < 1 || tab[rows + r] > F) return GITCAP_ERR_ARG;
+    const CrossProbsArgs a{(const bf16_t*)q, H * hd, T, (const bf16_t*)k, ldkv, F, F, probs, rows * T, H, hd};
+    hipError_t e = launch_cross_probs_varlen(a, key_off, key_len, s);
+    if (e == hipSuccess) e = launch_cross_mean(probs, 1, rows, T, H, F, 0, lengths, frame_mass, ld_f, s);
+    return dbg_rc(e);
+}
+
 // ---- constrained decoding (tests/test_constraints_gpu.py) ---------------------------------------------------------------------
 int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
                         const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream) {

@@ -427,6 +427,13 @@ struct CrossProbsArgs {
     int M, H, hd;
 };
 hipError_t launch_cross_probs(const CrossProbsArgs& a, hipStream_t s);
+// The variable-length forms of the two (clips of different length, gitcap_student_attach_frame_counts): the keys of decoder row r
+// are rows key_off[r] .. key_off[r] + key_len[r] - 1 (1 <= key_len <= 64) of the PACKED k | v -- device int32 tables of M / T
+// entries, read at run time -- in place of r * keys_stride .. + nkeys - 1; a.keys_stride, a.nkeys and a.t0 are not read, a.ids must
+// be null.  A row with key_len = n has the bits of the plain launch at nkeys = n.  cross_probs: probs stays [M][H][a.F], the
+// columns from key_len[r] on hold 0.
+hipError_t launch_attn_small_varlen(const SmallAttnArgs& a, const int32_t* key_off, const int32_t* key_len, hipStream_t s);
+hipError_t launch_cross_probs_varlen(const CrossProbsArgs& a, const int32_t* key_off, const int32_t* key_len, hipStream_t s);
 // frame_mass [rows][T][ld_f] (columns 0 .. F - 1) = the mean of probs [L][rows * T][H][F] over the heads and the selected layers
 // (layer = -1: all, ascending; heads ascending: a fixed order); zeros at positions j >= lengths[r] (nullable, device int32 [rows])
 hipError_t launch_cross_mean(const float* probs, int L, int rows, int T, int H, int F, int layer, const int32_t* lengths,

@@ -58,18 +58,27 @@ __global__ void student_draft_stage_kernel(const int64_t* __restrict__ draft, in
 }
 
 // one wave per (query, head); lane i owns key i for the scores and output column(s) lane, lane + 64 for P.V
-__global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a) {
+// VL (clips of different length, gitcap_student_attach_frame_counts): the keys of decoder row r are the key_len[r] (1..64) packed
+// memory rows from key_off[r] on -- device tables read at run time, so a captured loop follows the counts of the memory set last --
+// instead of rows r * keys_stride .. + nkeys - 1.  Nothing else differs: a row with key_len = n has the bits of the plain form at
+// nkeys = n.
+template <bool VL>
+__global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a, const int32_t* __restrict__ key_off, const int32_t* __restrict__ key_len) {
     __shared__ float qs[128];
     __shared__ float ps[64];
     const int lane = threadIdx.x, m = blockIdx.x, h = blockIdx.y;
     const int r = m / a.T, j = m % a.T;
-    const int nk = a.nkeys > 0 ? a.nkeys : a.t0 + j + 1;
+    int nk;
+    if constexpr (VL) nk = min(max(key_len[r], 0), 64);
+    else nk = a.nkeys > 0 ? a.nkeys : a.t0 + j + 1;
     const bf16_t* q = a.q + (size_t)(r * a.q_row_stride + a.q_row_off + j) * a.ldq + h * a.hd;
     for (int d = lane; d < a.hd; d += 64) qs[d] = bf2f(q[d]);
     __syncthreads();
     float s = -INFINITY;
     if (lane < nk) {
-        const bf16_t* k = a.k + (size_t)(r * a.keys_stride + lane) * a.ldkv + h * a.hd;
+        const bf16_t* k;
+        if constexpr (VL) k = a.k + (size_t)(key_off[r] + lane) * a.ldkv + h * a.hd;
+        else k = a.k + (size_t)(r * a.keys_stride + lane) * a.ldkv + h * a.hd;
         float acc = 0.f;
         for (int c = 0; c < a.hd; c += 8) {
             const bf16x8 kk = *(const bf16x8*)(k + c);
@@ -84,7 +93,9 @@ __global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a) {
     const float den = wave_sum(p);
     ps[lane] = p / den;
     __syncthreads();
-    const bf16_t* v = a.v + (size_t)r * a.keys_stride * a.ldkv + h * a.hd;
+    const bf16_t* v;
+    if constexpr (VL) v = a.v + (size_t)key_off[r] * a.ldkv + h * a.hd;
+    else v = a.v + (size_t)r * a.keys_stride * a.ldkv + h * a.hd;
     for (int d = lane; d < a.hd; d += 64) {
         float acc = 0.f;
         for (int i = 0; i < nk; ++i) acc += ps[i] * bf2f(v[(size_t)i * a.ldkv + d]);    // fixed order: batch invariant
@@ -93,17 +104,24 @@ __global__ __launch_bounds__(64) void attn_small_kernel(SmallAttnArgs a) {
 }
 
 // attn_small_kernel's cross-attention scores and softmax for one (query, head) -- the same loads, the same order of the products,
-// the same butterflies, __expf and division --, written out instead of being multiplied into V: lane i owns memory token (frame) i
-__global__ __launch_bounds__(64) void cross_probs_kernel(CrossProbsArgs a) {
+// the same butterflies, __expf and division --, written out instead of being multiplied into V: lane i owns memory token (frame) i.
+// VL: attn_small_kernel<true>'s keys; the row of probs keeps its a.F columns, those from key_len[r] on hold 0.
+template <bool VL>
+__global__ __launch_bounds__(64) void cross_probs_kernel(CrossProbsArgs a, const int32_t* __restrict__ key_off, const int32_t* __restrict__ key_len) {
     __shared__ float qs[128];
     const int lane = threadIdx.x, m = blockIdx.x, h = blockIdx.y;
     const int r = m / a.T;
+    int nk;
+    if constexpr (VL) nk = min(max(key_len[r], 0), a.F);
+    else nk = a.F;
     const bf16_t* q = a.q + (size_t)m * a.ldq + h * a.hd;
     for (int d = lane; d < a.hd; d += 64) qs[d] = bf2f(q[d]);
     __syncthreads();
     float s = -INFINITY;
-    if (lane < a.F) {
-        const bf16_t* k = a.k + (size_t)(r * a.keys_stride + lane) * a.ldkv + h * a.hd;
+    if (lane < nk) {
+        const bf16_t* k;
+        if constexpr (VL) k = a.k + (size_t)(key_off[r] + lane) * a.ldkv + h * a.hd;
+        else k = a.k + (size_t)(r * a.keys_stride + lane) * a.ldkv + h * a.hd;
         float acc = 0.f;
         for (int c = 0; c < a.hd; c += 8) {
             const bf16x8 kk = *(const bf16x8*)(k + c);
@@ -113,9 +131,13 @@ __global__ __launch_bounds__(64) void cross_probs_kernel(CrossProbsArgs a) {
         s = acc * rsqrtf((float)a.hd);
     }
     const float mx = wave_max(s);
-    const float p = lane < a.F ? __expf(s - mx) : 0.f;
+    const float p = lane < nk ? __expf(s - mx) : 0.f;
     const float den = wave_sum(p);
-    if (lane < a.F) a.probs[((size_t)m * a.H + h) * a.F + lane] = p / den;
+    if constexpr (VL) {
+        if (lane < a.F) a.probs[((size_t)m * a.H + h) * a.F + lane] = lane < nk ? p / den : 0.f;
+    } else {
+        if (lane < a.F) a.probs[((size_t)m * a.H + h) * a.F + lane] = p / den;
+    }
 }
 
 // one thread per (m, frame): layers, then heads, ascending
@@ -143,14 +165,29 @@ struct StuLayer {
 
 hipError_t launch_attn_small(const SmallAttnArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.H <= 0 || a.hd % 8 || a.hd > 128 || a.nkeys > 64 || (a.nkeys == 0 && a.t0 + a.T > 64)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_small_kernel, dim3(a.M, a.H), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(attn_small_kernel<false>, dim3(a.M, a.H), dim3(64), 0, s, a, nullptr, nullptr);
     return hipGetLastError();
 }
 
+hipError_t launch_attn_small_varlen(const SmallAttnArgs& a, const int32_t* key_off, const int32_t* key_len, hipStream_t s) {
+    if (!key_off || !key_len || a.M <= 0 || a.T <= 0 || a.H <= 0 || a.hd <= 0 || a.hd % 8 || a.hd > 128 || a.ids) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_small_kernel<true>, dim3(a.M, a.H), dim3(64), 0, s, a, key_off, key_len);
+    return hipGetLastError();
+}
+
+static bool cross_probs_ok(const CrossProbsArgs& a) {
+    return a.q && a.k && a.probs && a.M > 0 && a.T > 0 && a.M % a.T == 0 && a.H > 0 && a.hd > 0 && a.hd % 8 == 0 && a.hd <= 128 && a.F > 0 && a.F <= 64;
+}
+
 hipError_t launch_cross_probs(const CrossProbsArgs& a, hipStream_t s) {
-    if (!a.q || !a.k || !a.probs || a.M <= 0 || a.T <= 0 || a.M % a.T || a.H <= 0 || a.hd <= 0 || a.hd % 8 || a.hd > 128 || a.F <= 0 || a.F > 64)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cross_probs_kernel, dim3(a.M, a.H), dim3(64), 0, s, a);
+    if (!cross_probs_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cross_probs_kernel<false>, dim3(a.M, a.H), dim3(64), 0, s, a, nullptr, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_cross_probs_varlen(const CrossProbsArgs& a, const int32_t* key_off, const int32_t* key_len, hipStream_t s) {
+    if (!key_off || !key_len || !cross_probs_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cross_probs_kernel<true>, dim3(a.M, a.H), dim3(64), 0, s, a, key_off, key_len);
     return hipGetLastError();
 }
 
@@ -229,9 +266,10 @@ __global__ __launch_bounds__(256) void student_window_stage_kernel(const float* 
 }
 // window call: K|V rows of the ring [L][B][F slots][2D], oldest slot = head, -> memkv [L][R][F][2D] in window order; decoder row r
 // takes clip r / k (k beams per clip share its tokens).  blockIdx.x = (r, f), blockIdx.y = layer; n8 = 2D / 8 16-byte pieces per row.
+// n = the tokens copied per row, from slot `head` on: F of a full window, fewer of a partial one (rows keep their pitch of F slots).
 __global__ __launch_bounds__(64) void student_window_gather_kernel(const bf16_t* __restrict__ ring, bf16_t* __restrict__ memkv, int F, int head,
-                                                                   int k, int n8, size_t ring_layer, size_t mem_layer) {
-    const int r = blockIdx.x / F, f = blockIdx.x % F, l = blockIdx.y;
+                                                                   int k, int n8, size_t ring_layer, size_t mem_layer, int n) {
+    const int r = blockIdx.x / n, f = blockIdx.x % n, l = blockIdx.y;
     const uint4* src = (const uint4*)(ring + l * ring_layer) + ((size_t)(r / k) * F + (head + f) % F) * n8;
     uint4* dst = (uint4*)(memkv + l * mem_layer) + ((size_t)r * F + f) * n8;
     for (int i = threadIdx.x; i < n8; i += 64) dst[i] = src[i];
@@ -251,7 +289,7 @@ struct gitcap_student : HandleCore {
     // key: stop = a stop rule -> execs[0] the whole greedy loop; TAIL_STEPS -> execs[t - 1] token step t of the draft path, t >= 1
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none)
+    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; bool ragged; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none); ragged: the varlen cross-attention launches
     static constexpr int TAIL_STEPS = -1;
     std::vector<Graphs> graphs;
     // draft verification (gitcap_student_*_greedy_draft): acc_tok / acc_ticket = draft_accept_kernel's scratch, acc_host = its
@@ -276,6 +314,15 @@ struct gitcap_student : HandleCore {
     // writes them (one more launch per layer behind the cross-attention q projection), off for every other call
     float* att_probs = nullptr;
     bool att_on = false;
+    // clips of different length (gitcap_student_attach_frame_counts): fc_attach = the pending one-shot counts (empty: none).
+    // ragged = the memory currently set is packed: memkv holds one K|V row per frame, clip-major, and decoder row r reads rows
+    // key_off[r] .. + key_len[r] - 1 of it (key_tab: device int32 [2][R], offsets then lengths; the cross-attention launches of
+    // text_forward take the varlen forms).  The tables are written outside the captured loops, from key_host (page-locked, [2][R])
+    // behind key_ev = the previous copy has read it; the loops read them at replay, so one graph serves every set of counts.
+    std::vector<int32_t> fc_attach;
+    bool ragged = false;
+    int32_t *key_tab = nullptr, *key_host = nullptr;
+    hipEvent_t key_ev = nullptr;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -402,9 +449,13 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
         if ((rc = proj(SK_BIAS_BF16, Ly.ca_in_w, Ly.ca_in_b, D, h->qc, D, 1, 1, 0))) return rc;
         const bf16_t* mkv = h->memkv + (size_t)l * mem_layer;
         SmallAttnArgs ca{h->qc, D, T, T, 0, mkv, mkv + D, 2 * D, h->F, h->F, 0, nullptr, 0, 0, h->ctx, D, M, h->H, h->hd};
-        if (h->att_on)      // gitcap_student_attention: the probabilities of the launch below, from the q and memory K it reads
-            HIP_OK(h, launch_cross_probs(CrossProbsArgs{h->qc, D, T, mkv, 2 * D, h->F, h->F, h->att_probs + (size_t)l * M * h->H * h->F, M, h->H, h->hd}, s));
-        HIP_OK(h, launch_attn_small(ca, s));
+        // ragged: the memory rows are packed and row r's keys come through the tables (the varlen forms: same arithmetic)
+        const int32_t *key_off = h->key_tab, *key_len = h->ragged ? h->key_tab + h->R : nullptr;
+        if (h->att_on) {    // gitcap_student_attention: the probabilities of the launch below, from the q and memory K it reads
+            const CrossProbsArgs pa{h->qc, D, T, mkv, 2 * D, h->F, h->F, h->att_probs + (size_t)l * M * h->H * h->F, M, h->H, h->hd};
+            HIP_OK(h, h->ragged ? launch_cross_probs_varlen(pa, key_off, key_len, s) : launch_cross_probs(pa, s));
+        }
+        HIP_OK(h, h->ragged ? launch_attn_small_varlen(ca, key_off, key_len, s) : launch_attn_small(ca, s));
         if ((rc = dense_ln(h->ctx, D, Ly.ca_out_w, Ly.ca_out_b, Ly.n2w, Ly.n2b, true))) return rc;
         // feed-forward (the last layer's LayerNorm is a launch: the vocabulary head reads its bf16 output)
         if ((rc = proj(SK_BIAS_RELU_BF16, Ly.l1w, Ly.l1b, h->FF, h->ffn, h->FF, 1, 1, 0))) return rc;
@@ -442,10 +493,54 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
     return 0;
 }
 
-int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s) {
+// ---- clips of different length (gitcap_student_attach_frame_counts) -------------------------------------------------------------
+using Counts = std::vector<int32_t>;
+// the pending counts: consumed by the caller, whatever becomes of its call
+Counts take_counts(gitcap_student* h) { return std::exchange(h->fc_attach, Counts{}); }
+std::string counts_refused(const std::string& who) {
+    return who + ": per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take";
+}
+bool counts_dense(const gitcap_student* h, const Counts& fc) {
+    for (int32_t c : fc)
+        if (c != h->F) return false;
+    return true;
+}
+// Decoder rows 0 .. rows - 1 read the packed memory rows off(r) .. off(r) + len(r) - 1: the two device tables, written on `s`
+// (outside every captured loop).  The page-locked copy is reused once the previous call's transfer has read it.
+template <typename Row>
+int write_key_tables(gitcap_student* h, int rows, Row row, hipStream_t s) {
+    if (rows < 1 || rows > h->R) return fail(h, GITCAP_ERR_ARG, "student: rows outside [1, max_rows]");
+    if (!h->key_host) HIP_OK(h, hipHostMalloc((void**)&h->key_host, 2 * (size_t)h->R * sizeof(int32_t), hipHostMallocDefault));
+    if (!h->key_ev) HIP_OK(h, hipEventCreateWithFlags(&h->key_ev, hipEventDisableTiming));
+    if (!h->key_tab) {
+        if (int rc = dev_alloc(h, &h->key_tab, 2 * (size_t)h->R)) { h->key_tab = nullptr; return rc; }
+    }
+    HIP_OK(h, hipEventSynchronize(h->key_ev));      // (an event never recorded is complete)
+    for (int r = 0; r < rows; ++r) {
+        const std::pair<int, int> ol = row(r);
+        h->key_host[r] = ol.first;
+        h->key_host[h->R + r] = ol.second;
+    }
+    HIP_OK(h, hipMemcpyAsync(h->key_tab, h->key_host, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(h->key_tab + h->R, h->key_host + h->R, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipEventRecord(h->key_ev, s));
+    return 0;
+}
+
+// fc (non-null, not all mem_tokens): memory is the packed [sum(fc)][D] rows of B = fc.size() clips, and the k rows b * k .. b * k + k - 1
+// share clip b's K|V rows through the tables.  Otherwise memory is [B][mem_tokens][D], one clip per row.
+int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s, const Counts* fc = nullptr, int k = 1) {
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student: weights not finalized");
-    if (!memory || B <= 0 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student: set_memory: bad arguments / B exceeds max_rows");
-    const int D = h->D, Mm = B * h->F;
+    if (!memory || B <= 0 || k <= 0 || (int64_t)B * k > h->R) return fail(h, GITCAP_ERR_ARG, "student: set_memory: bad arguments / B exceeds max_rows");
+    const int D = h->D;
+    int Mm = B * h->F;
+    if (fc) {
+        Counts off(B);
+        Mm = 0;
+        for (int b = 0; b < B; ++b) { off[b] = Mm; Mm += (*fc)[b]; }
+        if (int rc = write_key_tables(h, B * k, [&](int r) { return std::make_pair((int)off[r / k], (int)(*fc)[r / k]); }, s)) return rc;
+    }
+    h->ragged = fc != nullptr;
     HIP_OK(h, launch_cast_bf16(memory, h->memb, (int64_t)Mm * D, s));
     const size_t mem_layer = (size_t)h->R * h->F * 2 * D;
     for (int l = 0; l < h->L; ++l) {
@@ -455,8 +550,18 @@ int set_memory(gitcap_student* h, const float* memory, int B, hipStream_t s) {
                          h->memkv + (size_t)l * mem_layer, 2 * D);
         if (rc) return rc;
     }
-    h->cur_B = B;
+    h->cur_B = B * k;
     h->have_memory = true;
+    return 0;
+}
+// The counts a memory-taking entry point took -> what set_memory gets: null for none and for all-mem_tokens counts (today's dense
+// path, launch for launch), else the counts; a B that is not theirs is refused.
+int counts_for_call(gitcap_student* h, const std::string& who, const Counts& fc, int B, const Counts** out) {
+    *out = nullptr;
+    if (fc.empty()) return 0;
+    if ((int)fc.size() != B)
+        return fail(h, GITCAP_ERR_ARG, who + ": B = " + std::to_string(B) + ", but frame counts of " + std::to_string(fc.size()) + " clips are attached");
+    if (!counts_dense(h, fc)) *out = &fc;
     return 0;
 }
 
@@ -529,6 +634,8 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->acc_host) (void)hipHostFree(h->acc_host);
     if (h->acc_ev) (void)hipEventDestroy(h->acc_ev);
+    if (h->key_host) (void)hipHostFree(h->key_host);
+    if (h->key_ev) (void)hipEventDestroy(h->key_ev);
     free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
@@ -603,8 +710,24 @@ int gitcap_student_finalize(gitcap_student_t* h) {
 
 int gitcap_student_set_memory(gitcap_student_t* h, const float* memory, int B, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_set_memory: null handle");
+    const Counts fc = take_counts(h);
+    const Counts* ragged = nullptr;
+    if (int bad = counts_for_call(h, "student_set_memory", fc, B, &ragged)) return bad;
     GUARD(h);
-    return set_memory(h, memory, B, (hipStream_t)stream);
+    return set_memory(h, memory, B, (hipStream_t)stream, ragged);
+}
+
+int gitcap_student_attach_frame_counts(gitcap_student_t* h, const int32_t* counts, int B) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: null handle");
+    h->fc_attach.clear();
+    if (!counts) return 0;                                   // detach
+    if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: B outside [1, max_rows]");
+    for (int b = 0; b < B; ++b)
+        if (counts[b] < 1 || counts[b] > h->F)
+            return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: clip " + std::to_string(b) + " has " + std::to_string(counts[b]) +
+                        " frames, outside [1, " + std::to_string(h->F) + "]");
+    h->fc_attach.assign(counts, counts + B);
+    return 0;
 }
 
 int gitcap_student_forward_decoder(gitcap_student_t* h, const int64_t* ids, int ld_ids, int B, int T, float* logits, void* stream) {
@@ -661,11 +784,12 @@ int capture(gitcap_student* h, const char* what, Enqueue enqueue, hipGraphExec_t
 template <typename Fill>
 int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, Fill fill, const std::vector<hipGraphExec_t>** out) {
     for (auto& g : h->graphs)
-        if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp && g.tk == tk) {
+        if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp && g.tk == tk &&
+            g.ragged == h->ragged) {
             *out = &g.execs;
             return 0;
         }
-    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, {}};
+    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, h->ragged, {}};
     if (int rc = fill(g.execs)) {
         for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
         return rc;
@@ -861,14 +985,22 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
 // A memory token is one frame's own stage-3 mean and its cross-attention K|V rows are W_kv . token + b, no positional term, from a
 // GEMM whose output rows do not depend on each other: everything per frame is computed once, at the push, and a caption of the
 // window only orders the F rows (student_window_gather_kernel) in front of the token loop of the full call.
-int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s) {
-    if (!h->win_ring || !h->win.full())
-        return fail(h, GITCAP_ERR_STATE, std::string(who) + ": fewer than mem_tokens tokens pushed since the reset");
-    const int rows = h->win_B * k, D = h->D;
+// partial (gitcap_student_window_greedy_partial): a window that is not full yet gives the n < mem_tokens tokens pushed since the reset,
+// oldest first, as slots 0 .. n - 1 of every row, and every row's key table entry says n: the varlen launches, a row of which is
+// bit for bit the plain launch at nkeys = n.  *frames = the tokens the caption sees.
+int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s, bool partial = false, int* frames = nullptr) {
+    if (!h->win_ring || (partial ? h->win.count < 1 : !h->win.full()))
+        return fail(h, GITCAP_ERR_STATE, std::string(who) + (partial ? ": no token pushed since the reset" : ": fewer than mem_tokens tokens pushed since the reset"));
+    const int rows = h->win_B * k, D = h->D, F = h->F, n = h->win.full() ? F : h->win.count;
+    if (frames) *frames = n;
     HIP_OK(h, h->win_order.before_read(s));
     h->have_memory = false;
-    hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * h->F, h->L), dim3(64), 0, s, h->win_ring, h->memkv, h->F, h->win.head, k,
-                       2 * D / 8, (size_t)h->win_B * h->F * 2 * D, (size_t)h->R * h->F * 2 * D);
+    if (n < F)
+        if (int rc = write_key_tables(h, rows, [&](int r) { return std::make_pair(r * F, n); }, s)) return rc;
+    h->ragged = n < F;
+    // the oldest token's slot: the head of a full ring, slot 0 of one that has not wrapped
+    hipLaunchKernelGGL(student_window_gather_kernel, dim3(rows * n, h->L), dim3(64), 0, s, h->win_ring, h->memkv, F, (h->win.head + F - n) % F, k,
+                       2 * D / 8, (size_t)h->win_B * F * 2 * D, (size_t)h->R * F * 2 * D, n);
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, h->win_order.after_read(s));
     h->cur_B = rows;
@@ -879,13 +1011,17 @@ int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s) {
 // The four greedy entry points.  who = the entry point's name in every message; window: the memory K|V come from the ring (win_B
 // clips) instead of the caller's `memory` (set_memory reads the caller's buffer: outside the graphs); draft set: the loop verifies
 // it.  The pending log-probability attachment is taken before the checks: a refused call has consumed it.
+// Attached frame counts are taken with them: the calls with `memory` follow them, the window calls refuse them.  partial: the window
+// need not be full (window_memory); *frames_out (host, nullable) = the tokens the caption saw.
 struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
 int greedy_entry(gitcap_student* h, const char* who, bool window, const float* memory, int B, const Draft* draft, int max_len, int stop,
-                 int64_t* ids_out, int32_t* steps_out, void* stream) {
+                 int64_t* ids_out, int32_t* steps_out, void* stream, bool partial = false, int32_t* frames_out = nullptr) {
     const std::string w(who);
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
     const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});
     const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
+    const Counts fc = take_counts(h);
+    if (window && !fc.empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));          // (consumed above)
     if (draft && tk.k) return fail(h, GITCAP_ERR_ARG, refused_message(who, OPT_TK));       // (consumed above)
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
@@ -896,9 +1032,13 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
         return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
     if (window && !h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
+    const Counts* ragged = nullptr;
+    if (int bad = counts_for_call(h, w, fc, B, &ragged)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = window ? window_memory(h, who, 1, s) : set_memory(h, memory, B, s)) return rc;
+    int frames = 0;
+    if (int rc = window ? window_memory(h, who, 1, s, partial, &frames) : set_memory(h, memory, B, s, ragged)) return rc;
+    if (frames_out) *frames_out = frames;
     if (window) B = h->win_B;
     if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
     return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
@@ -922,12 +1062,19 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
 // K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
+    const Counts fc = take_counts(h);
     if (!memory) return fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
     if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
+    const Counts* ragged = nullptr;
+    if (int bad = counts_for_call(h, "student_beam_search", fc, B, &ragged)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = beam_workspace(h);
     if (rc) return rc;
+    if (ragged) {       // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
+        if ((rc = set_memory(h, memory, B, s, ragged, k))) return rc;
+        return beam_loop(h, B, k, max_len, ids_out, s);
+    }
     const int rows = B * k;
     hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
     HIP_OK(h, hipGetLastError());
@@ -937,6 +1084,7 @@ int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, 
 
 int gitcap_student_window_reset(gitcap_student_t* h, int B) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_reset: null handle");
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_reset"));
     if (B < 0 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student_window_reset: B outside 0..max_rows");
     GUARD(h);
     if (h->win_ring && B != h->win_B) {
@@ -966,6 +1114,7 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B) {
 
 int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_push: null handle");
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_push"));
     if (!memory) return fail(h, GITCAP_ERR_ARG, "student_window_push: null memory");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_push: weights not finalized");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_push: no window (gitcap_student_window_reset first)");
@@ -998,6 +1147,11 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
 
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
     return greedy_entry(h, "student_window_greedy", true, nullptr, 0, nullptr, max_len, stop, ids_out, steps_out, stream);
+}
+
+int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* frames_out,
+                                         void* stream) {
+    return greedy_entry(h, "student_window_greedy_partial", true, nullptr, 0, nullptr, max_len, stop, ids_out, steps_out, stream, true, frames_out);
 }
 
 int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
@@ -1106,6 +1260,7 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_beam_search"));
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
     if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;

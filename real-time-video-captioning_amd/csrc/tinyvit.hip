@@ -764,4 +764,26 @@ int gitcap_dbg_attn_small(const gitcap_dbg_attn_small_args* g, void* stream) {
     return dbg_rc(launch_attn_small(a, (hipStream_t)stream));
 }
 
+// its variable-length form (attn_small_kernel<true>): key_off / key_len device int32 [M / T]; nkeys, keys_stride and t0 of the struct
+// are not read and ids must be null.  The tables are read back first (the call synchronises `stream`): a length outside [1, 64] or a
+// negative offset is refused before any launch.
+int gitcap_dbg_attn_small_varlen(const gitcap_dbg_attn_small_args* g, const int32_t* key_off, const int32_t* key_len, void* stream) {
+    if (!g || !g->q || !g->k || !g->v || !g->ctx || !key_off || !key_len || g->ids || g->T <= 0 || g->M <= 0 || g->M % g->T || g->H <= 0 ||
+        g->hd <= 0 || g->q_row_stride < 0 || g->q_row_off < 0 || g->ldq < g->H * g->hd || g->ldkv < g->H * g->hd || (g->ldkv & 7) ||
+        g->ldc < g->H * g->hd || misaligned(g->q, 2) || misaligned(g->k, 16) || misaligned(g->v, 2) || misaligned(g->ctx, 2) ||
+        misaligned(key_off, 4) || misaligned(key_len, 4))
+        return GITCAP_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = g->M / g->T;
+    std::vector<int32_t> tab(2 * (size_t)rows);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(tab.data(), key_off, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(tab.data() + rows, key_len, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return GITCAP_ERR_HIP;
+    for (int r = 0; r < rows; ++r)
+        if (tab[r] < 0 || tab[rows + r] < 1 || tab[rows + r] > 64) return GITCAP_ERR_ARG;
+    const SmallAttnArgs a{(const bf16_t*)g->q, g->ldq, g->T, g->q_row_stride, g->q_row_off, (const bf16_t*)g->k, (const bf16_t*)g->v,
+                          g->ldkv, 0, 0, 0, nullptr, 0, 0, (bf16_t*)g->ctx, g->ldc, g->M, g->H, g->hd};
+    return dbg_rc(launch_attn_small_varlen(a, key_off, key_len, s));
+}
+
 }  // extern "C"

@@ -276,6 +276,12 @@ SYMBOLS = {
     "gitcap_student_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "gitcap_dbg_cross_probs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                        c_void_p]),
+    # the student on clips of different length, and captions of a window that is not full yet (tests/test_student_ragged_*_gpu.py)
+    "gitcap_student_attach_frame_counts": (c_int, [c_void_p, POINTER(c_int32), c_int]),
+    "gitcap_student_window_greedy_partial": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "gitcap_dbg_attn_small_varlen": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_cross_probs_varlen": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_void_p, c_void_p]),
     # student image encoder (gitcap/tinyvit.py)
     "gitcap_tinyvit_create": (c_int, [POINTER(CTinyViTConfig), c_int, POINTER(c_void_p)]),
     "gitcap_tinyvit_destroy": (None, [c_void_p]),

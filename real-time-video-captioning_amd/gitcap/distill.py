@@ -38,7 +38,7 @@ FIELDS = ("kl", "kl_sum", "count", "teacher_top1", "student_top1", "agreement", 
 @torch.no_grad()
 def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temperature: float = 1.0,
                    lengths: Optional[torch.Tensor] = None, until_sep: bool = False, ignore_id: Optional[int] = None,
-                   student_x: Optional[torch.Tensor] = None) -> dict:
+                   student_x: Optional[torch.Tensor] = None, frame_counts=None) -> dict:
     """How far the student's next-token distributions are from the teacher's on given captions.
 
     ``x``: frames [B,F,3,S,S] or the teacher's ``memory``; ``student_x``: the student's frames or memory [B,F,D] (default: ``x``
@@ -50,7 +50,10 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
     score()'s bits), and two scalars: ``kl_loss`` = temperature^2 * kl.sum() / B -- the reference's LOSS 2
     (KLDivLoss('batchmean') * temperature^2) when nothing is ignored and n is 1 -- and ``ce_loss`` = the mean of -student_logprobs
     over the counted targets != 0, LOSS 3 (CrossEntropyLoss(ignore_index=0)).
-    Clips go through in chunks of the smaller of the two handles' max_batch // n."""
+    Clips go through in chunks of the smaller of the two handles' max_batch // n.
+    frame_counts (``x`` / ``student_x`` padded [B, Fmax, ...]), or ``x`` / ``student_x`` as lists of B clips [F_b, ...]: clips that
+    differ in length go to both models as they are (GitCaptioner.forward_image_enc, StudentCaptioner.score); a clip has at
+    most min(the teacher's frame limit, the student's mem_tokens) frames."""
     if not (isinstance(temperature, (int, float)) and math.isfinite(temperature) and temperature > 0):
         raise ValueError(f"temperature must be positive and finite, got {temperature}")
     if teacher._dev != student._dev:
@@ -61,14 +64,19 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
     teacher._drain()
     ids, had_n = scoring.candidates(y, dev)
     B, n, T = ids.shape
-    if x.shape[0] != B:
+    rg = frame_counts is not None or not isinstance(x, torch.Tensor)         # a ragged batch: x is frames, packed by each model
+    nclips = lambda v: v.shape[0] if isinstance(v, torch.Tensor) else len(v)
+    if nclips(x) != B:
         raise ValueError("x and y disagree on the number of clips")
     if student_x is None:
-        if not (x.dim() == 5 or x.dtype == torch.uint8):
+        if not (rg or x.dim() == 5 or x.dtype == torch.uint8):
             raise ValueError("x is the teacher's memory: pass student_x (the student's frames or memory)")
         student_x = x
-    if student_x.shape[0] != B:
+    if nclips(student_x) != B:
         raise ValueError("student_x and y disagree on the number of clips")
+    if not rg and not isinstance(student_x, torch.Tensor):
+        raise ValueError("student_x is a list of clips: pass x as one too, or frame_counts")
+    out_dev = x.device if isinstance(x, torch.Tensor) else x[0].device
     if T > min(teacher.max_text_len, student.max_text_len + 1):
         raise ValueError(f"T={T} exceeds what the handles were created for")
     Bc = min(B, teacher.max_batch, student.max_batch // n)
@@ -76,13 +84,16 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
         raise ValueError(f"{n} candidates per clip exceed the rows the handles were created for")
     ln = scoring.row_lengths(ids, teacher.sep_token_id, until_sep, lengths)
     ign = -1 if ignore_id is None else int(ignore_id)
-    frames = x.dim() == 5
+    frames = rg or x.dim() == 5
     chunks = []
     with torch.cuda.device(dev):
         for b0 in range(0, B, Bc):
             b1 = min(B, b0 + Bc)
             rows = (b1 - b0) * n
-            if frames:
+            fc = None if frame_counts is None else frame_counts[b0:b1]
+            if rg:
+                teacher.forward_image_enc(x[b0:b1], frame_counts=fc)
+            elif frames:
                 teacher.forward_image_enc(x[b0:b1])
             elif not (b0 == 0 and b1 == B and teacher._is_last_memory(x)):      # (as GitCaptioner.score: the handle may hold it already)
                 mem = x[b0:b1].to(device=dev, dtype=torch.float32).contiguous()
@@ -90,10 +101,7 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
                 teacher._last_memory = None
                 if b0 == 0 and b1 == B:
                     teacher._remember_memory(x)
-            smem = student._memory(student._src_memory(student_x[b0:b1]))
-            if n > 1:
-                smem = smem.repeat_interleave(n, dim=0)
-            student._call("gitcap_student_set_memory", _lib.ptr(smem), rows, student._stream())
+            student._set_memory(student_x[b0:b1], fc if rg else None, n)
             buf = _Buffers(rows, T, dev)
             cid = ids[b0:b1].reshape(rows, T)
             cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
@@ -107,7 +115,7 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
     def cat(field):
         t = torch.cat([getattr(c, field) for c in chunks], 0)
         t = t.view(B, n, *t.shape[1:]) if had_n else t
-        return t.to(x.device) if t.device != x.device else t
+        return t.to(out_dev) if t.device != out_dev else t
     res = {f: cat(f) for f in FIELDS}
     res["agreement"] = res["agreement"].bool()
     res["kl_loss"] = float(temperature) ** 2 * res["kl"].sum() / B
@@ -117,7 +125,7 @@ def distill_report(teacher, student, x: torch.Tensor, y: torch.Tensor, *, temper
     if ln is not None:
         j1 = torch.arange(1, T, device=dev)
         counted &= j1 < (ln if had_n else ln[:, 0])[..., None]
-    counted = counted.to(x.device)
+    counted = counted.to(out_dev)
     lp = res["student_logprobs"]
     res["ce_loss"] = -torch.where(counted, lp, torch.zeros_like(lp)).sum() / counted.sum().clamp(min=1)
     return res

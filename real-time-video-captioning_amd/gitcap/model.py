@@ -1875,8 +1875,11 @@ def draft_and_verify(teacher: GitCaptioner, student, src: torch.Tensor, max_len:
     differs from the teacher's: frames of its encoder's size, or memory tokens [B, F, d_model] -- and the teacher's
     greedy_decode(src, max_len, draft=that caption, **greedy_kw) verifies it.  -> dict(ids, draft, accepted[, logprobs]): ``ids``
     (and ``logprobs`` with return_logprobs=True) are bit for bit the teacher's plain greedy_decode whatever the student wrote,
-    ``draft`` the student's caption, ``accepted`` int32 [B] the leading draft tokens the teacher kept per clip."""
-    draft = student.greedy_decode(src if student_src is None else student_src, max_len=min(max_len, student.max_text_len), stop="never")
+    ``draft`` the student's caption, ``accepted`` int32 [B] the leading draft tokens the teacher kept per clip.
+    Clips that differ in length (``src`` / ``student_src`` as lists of clips, or padded with ``frame_counts=``) go to both models
+    as they are; a clip has at most min(the teacher's frame limit, the student's mem_tokens) frames."""
+    fc = {} if greedy_kw.get("frame_counts") is None else {"frame_counts": greedy_kw["frame_counts"]}
+    draft = student.greedy_decode(src if student_src is None else student_src, max_len=min(max_len, student.max_text_len), stop="never", **fc)
     out = teacher.greedy_decode(src, max_len=max_len, draft=draft, **greedy_kw)
     ids, lp = out if isinstance(out, tuple) else (out, None)
     res = dict(ids=ids, draft=draft, accepted=teacher.last_accepted)

@@ -23,7 +23,7 @@ from typing import Dict, Mapping, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from ._handle import _NativeModule
 from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
 from .framegate import FrameGate
@@ -43,10 +43,12 @@ class StudentCaptionStream(_WindowStream):
     ``carry`` a greedy stream offers its previous caption as the draft of the next window call
     (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0, partial=False):
         self._carry, self._prev, self._beams = bool(carry), None, beams
+        self._partial = bool(partial)
+        self.last_frames = None          # frames per clip the caption of the last push saw (mem_tokens unless partial=True)
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
-        super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop), max_len, mode, gate, logprobs, top_logprobs)
+        super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop, partial=self._partial), max_len, mode, gate, logprobs, top_logprobs)
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -97,7 +99,13 @@ class StudentCaptionStream(_WindowStream):
                     last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
                     m._attach_logprobs(lp, tk)
-                    m._call("gitcap_student_window_greedy", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps), m._stream())
+                    if self._partial:            # whatever the window holds; a full one is the plain call
+                        seen = ctypes.c_int32(0)
+                        m._call("gitcap_student_window_greedy_partial", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps),
+                                ctypes.byref(seen), m._stream())
+                        self.last_frames = int(seen.value)
+                    else:
+                        m._call("gitcap_student_window_greedy", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps), m._stream())
                 out = self._finish_greedy(ids, steps, lp, to_cpu, tk)
                 if self._carry:
                     self._prev = ids[:, :out.shape[1]]       # stays on the device, truncated as the caption is
@@ -108,6 +116,8 @@ class StudentCaptionStream(_WindowStream):
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 m._call("gitcap_student_window_beam_search", self._beams, self._max_len, _lib.ptr(ids), m._stream())
                 out = ids.cpu() if to_cpu else ids
+        if not self._partial:
+            self.last_frames = m.cfg.mem_tokens
         self._stats["captions"] += 1
         return out
 
@@ -216,6 +226,98 @@ class StudentCaptioner(_NativeModule):
         kw["image_enc_name"] = self.image_enc_name
         return _rebuild_student, (asdict(self.cfg), self._weights, kw, self.image_encoder)
 
+    # ------------------------------------------------------------------ clips of different length (gitcap/ragged.py)
+    def _frame_limit(self) -> int:
+        """The most frames a clip may have (what gitcap.sampling.caption_videos asks the sampler for)."""
+        return self.cfg.mem_tokens
+
+    @staticmethod
+    def _is_ragged(src, frame_counts) -> bool:
+        return frame_counts is not None or not isinstance(src, torch.Tensor)
+
+    @staticmethod
+    def _nclips(src) -> int:
+        return src.shape[0] if isinstance(src, torch.Tensor) else len(src)
+
+    def _encode_packed(self, frames: torch.Tensor) -> torch.Tensor:
+        """Packed frames [n,3,S,S] (or uint8 [n,H,W,3]) -> memory tokens [n, D] from one encode: no frame is padded."""
+        if self._native():
+            enc = self.image_encoder
+            return enc._encode(enc._frames(frames), False)[1]
+        if frames.dtype == torch.uint8:
+            raise _lib.GitcapError("uint8 camera frames need the native TinyViT encoder (image_encoder='native'): the frame "
+                                   "transform runs inside its first convolution")
+        if self.image_encoder is None:
+            raise _lib.GitcapError("StudentCaptioner was built without an image_encoder: pass image_encoder='native' (the "
+                                   "TinyViT encoder of libgitcap) or a module, or call the decoder with memory [F_b, d_model] per clip")
+        return torch.mean(self.image_encoder(frames.to(self._dev))[-1], dim=[2, 3])
+
+    def _clip_memories(self, src, frame_counts):
+        """The ragged input forms -> (memory tokens [F_b, D] fp32 on the device, one tensor per clip; the counts; src's device).
+        ``src``: a list of B clips -- frames [F_b,3,S,S], uint8 camera frames [F_b,H,W,3] or memory [F_b,D] -- or a padded tensor
+        [B,Fmax,...] of one of the three with ``frame_counts`` [B] (what lies beyond a clip's count is ignored).  1 <= F_b <=
+        mem_tokens.  Frames are encoded packed, sum(counts) of them in one pass."""
+        F, D = self.cfg.mem_tokens, self.cfg.d_model
+        padded = isinstance(src, torch.Tensor)
+        is_mem = (src.dim() == 3 if padded else bool(len(src)) and all(isinstance(p, torch.Tensor) and p.dim() == 2 for p in src))
+        if is_mem and (src.dtype if padded else src[0].dtype) != torch.uint8:
+            if padded:
+                if frame_counts is None:
+                    raise ValueError("a padded tensor needs frame_counts")
+                counts = ragged.check_counts(frame_counts, src.shape[0], min(F, src.shape[1]))
+                parts = [src[b, :n] for b, n in enumerate(counts)]
+            else:
+                parts = list(src)
+                counts = ragged.check_counts([p.shape[0] for p in parts], len(parts), F)
+                if frame_counts is not None and ragged.check_counts(frame_counts, len(parts), F) != counts:
+                    raise ValueError("frame_counts disagrees with the clips' own frame counts")
+            if any(p.shape[-1] != D or p.dtype == torch.uint8 for p in parts):
+                raise ValueError(f"expected memory tokens [F_b, {D}] per clip")
+            out_dev = parts[0].device
+            mems = [p.to(device=self._dev, dtype=torch.float32) for p in parts]
+        else:
+            size = self.image_encoder.cfg.img_size if self._native() else (src.shape[-1] if padded else src[0].shape[-1])
+            parts, counts, _ = ragged.clips(src, frame_counts, size, F)
+            out_dev = parts[0].device
+            mems = list(self._encode_packed(ragged.pack(parts)).split(counts, 0))
+        if len(counts) > self.max_batch:
+            raise ValueError(f"batch {len(counts)} outside 1..max_batch={self.max_batch}")
+        return mems, counts, out_dev
+
+    def _ragged_memory(self, src, frame_counts, n: int = 1):
+        """-> (memory for the library, rows, counts or None, src's device): n rows per clip (candidates: rows whose memory is
+        repeated).  Every clip of mem_tokens frames: the dense [rows, F, D] of the existing calls, counts None.  Else the packed
+        [sum, D] rows and the per-row counts gitcap_student_attach_frame_counts takes."""
+        mems, counts, out_dev = self._clip_memories(src, frame_counts)
+        if n > 1:
+            mems = [m for m in mems for _ in range(n)]
+            counts = [c for c in counts for _ in range(n)]
+        if all(c == self.cfg.mem_tokens for c in counts):
+            return torch.stack(mems, 0).contiguous(), len(counts), None, out_dev
+        return torch.cat(mems, 0).contiguous(), len(counts), counts, out_dev
+
+    def _attach_counts(self, counts):
+        """One-shot: the next call that takes memory reads it packed (gitcap_student_attach_frame_counts; the counts are copied)."""
+        if counts is not None:
+            self._call("gitcap_student_attach_frame_counts", (ctypes.c_int32 * len(counts))(*counts), len(counts))
+
+    def _set_memory(self, src, frame_counts=None, n: int = 1) -> int:
+        """``src`` (any input form, n rows per clip) becomes the handle's memory -> its rows."""
+        if self._is_ragged(src, frame_counts):
+            mem, rows, counts, _ = self._ragged_memory(src, frame_counts, n)
+        else:
+            mem, counts = self._memory(self._src_memory(src)), None
+            mem = mem.repeat_interleave(n, dim=0) if n > 1 else mem
+            rows = mem.shape[0]
+        self._attach_counts(counts)
+        self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
+        return rows
+
+    @staticmethod
+    def _clip_range(src, frame_counts, b0, b1):
+        """Clips b0 .. b1 - 1 of either input form."""
+        return src[b0:b1], None if frame_counts is None else frame_counts[b0:b1]
+
     # ------------------------------------------------------------------ reference API
     def _memory(self, memory: torch.Tensor) -> torch.Tensor:
         if memory.dim() != 3 or memory.shape[1] != self.cfg.mem_tokens or memory.shape[2] != self.cfg.d_model:
@@ -236,9 +338,25 @@ class StudentCaptioner(_NativeModule):
         return self._frames_memory(src) if src.dim() == 5 or src.dtype == torch.uint8 else src
 
     @torch.no_grad()
-    def forward_image_enc(self, x: torch.Tensor):
+    def forward_image_enc(self, x: torch.Tensor, frame_counts=None):
         """model.py:108-126: frames [B,F,C,H,W] -> (feature maps, memory [B,F,De]) through the image encoder.  The native
-        encoder also takes uint8 BGR camera frames [B,F,H,W,3]."""
+        encoder also takes uint8 BGR camera frames [B,F,H,W,3].
+        frame_counts (or ``x`` as a list of B clips [F_b, ...]): clips that differ in length, encoded packed -> (feature maps
+        [sum(counts),Ci,Hi,Wi], memory [B,Fmax,De] with zeros beyond a clip's frames, valid bool [B,Fmax])."""
+        if self._is_ragged(x, frame_counts):
+            size = self.image_encoder.cfg.img_size if self._native() else (x.shape[-1] if isinstance(x, torch.Tensor) else x[0].shape[-1])
+            parts, counts, _ = ragged.clips(x, frame_counts, size, self.cfg.mem_tokens)
+            packed = ragged.pack(parts)
+            if self._native():
+                enc = self.image_encoder
+                fmaps, mem = enc._encode(enc._frames(packed), True)
+            else:
+                if self.image_encoder is None or packed.dtype == torch.uint8:
+                    raise _lib.GitcapError("frames need an image_encoder (uint8 camera frames the native one)")
+                fmaps = self.image_encoder(packed.to(self._dev))
+                mem = torch.mean(fmaps[-1], dim=[2, 3])
+            memory, valid = ragged.unpack_rows(mem, counts, 1)
+            return fmaps, memory, valid
         if self._native():
             return self.image_encoder.forward_with_memory(x)
         if x.dtype == torch.uint8:
@@ -253,32 +371,40 @@ class StudentCaptioner(_NativeModule):
         return fmaps, memory
 
     @torch.no_grad()
-    def forward_decoder(self, y: torch.Tensor, memory: torch.Tensor) -> torch.Tensor:
-        """model.py:128-154: y [B,T] ids, memory [B,F,D] -> logits [B,T,V] (fp32, on the device)."""
-        mem = self._memory(memory)
+    def forward_decoder(self, y: torch.Tensor, memory: torch.Tensor, frame_counts=None) -> torch.Tensor:
+        """model.py:128-154: y [B,T] ids, memory [B,F,D] -> logits [B,T,V] (fp32, on the device).
+        frame_counts (memory padded [B,Fmax,D]), or memory as a list of B tensors [F_b,D]: clips that differ in length; row b
+        attends to its own F_b tokens only."""
+        counts = None
+        if self._is_ragged(memory, frame_counts):
+            mem, _, counts, _ = self._ragged_memory(memory, frame_counts)
+        else:
+            mem = self._memory(memory)
         ids = y.to(device=self._dev, dtype=torch.int64).contiguous()
         B, T = ids.shape
-        if B != mem.shape[0]:
+        if B != (mem.shape[0] if counts is None else len(counts)):
             raise ValueError("y and memory disagree on the batch size")
         if T < 1 or T > self.max_text_len + 1:
             raise ValueError(f"T={T} outside 1..max_text_len+1={self.max_text_len + 1}")
         logits = torch.empty((B, T, self.cfg.vocab_length), dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
+            self._attach_counts(counts)
             self._call("gitcap_student_set_memory", _lib.ptr(mem), B, self._stream())
             self._call("gitcap_student_forward_decoder", _lib.ptr(ids), T, B, T, _lib.ptr(logits), self._stream())
         return logits
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, y: torch.Tensor, *, lengths: Optional[torch.Tensor] = None, until_sep: bool = True,
-              ignore_id: Optional[int] = None, return_top1: bool = False, top_k: int = 0) -> dict:
+              ignore_id: Optional[int] = None, return_top1: bool = False, top_k: int = 0, frame_counts=None) -> dict:
         """GitCaptioner.score over the student decoder (include/gitcap.h: gitcap_student_score): ``x`` frames or memory [B,F,D],
         ``y`` CLS-first ids [B, T] or [B, n, T] (n candidates per clip: rows whose memory is repeated).  Same ignore rules and
-        the same dict (``top_k`` included); clips go through in chunks of max_batch // n."""
+        the same dict (``top_k`` included); clips go through in chunks of max_batch // n.
+        frame_counts (or ``x`` as a list of clips; as in greedy_decode): clips that differ in length."""
         from . import scoring
         top_k = scoring.check_top_k(top_k)
         ids, had_n = scoring.candidates(y, self._dev)
         B, n, T = ids.shape
-        if x.shape[0] != B:
+        if self._nclips(x) != B:
             raise ValueError("x and y disagree on the number of clips")
         if T > self.max_text_len + 1:
             raise ValueError(f"T={T} > max_text_len+1={self.max_text_len + 1}")
@@ -290,30 +416,30 @@ class StudentCaptioner(_NativeModule):
         with torch.cuda.device(self._dev):
             for b0 in range(0, B, Bc):
                 b1 = min(B, b0 + Bc)
-                mem = self._memory(self._src_memory(x[b0:b1])).repeat_interleave(n, dim=0) if n > 1 else self._memory(self._src_memory(x[b0:b1]))
-                rows = (b1 - b0) * n
+                rows = self._set_memory(*self._clip_range(x, frame_counts, b0, b1), n)
                 buf = scoring.ScoreBuffers(rows, T, self._dev, return_top1, top_k)
                 cid = ids[b0:b1].reshape(rows, T)
                 cl = None if ln is None else ln[b0:b1].reshape(rows).contiguous()
-                self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
                 buf.attach_topk(self._call, "gitcap_student_attach_top_logprobs")
                 self._call("gitcap_student_score", _lib.ptr(cid), T, rows, T, _lib.ptr(cl), -1 if ignore_id is None else int(ignore_id),
                            *buf.args(T), self._stream())
                 chunks.append(buf)
-        return scoring.result(chunks, B, n, had_n, return_top1, x.device)
+        return scoring.result(chunks, B, n, had_n, return_top1, x.device if isinstance(x, torch.Tensor) else x[0].device)
 
     @torch.no_grad()
     def attention(self, x: torch.Tensor, y: torch.Tensor, *, layer: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
-                  until_sep: bool = True) -> dict:
+                  until_sep: bool = True, frame_counts=None) -> dict:
         """Which frame every token of GIVEN captions comes from (include/gitcap.h: gitcap_student_attention).  The student's memory
         is one token per frame, so its cross-attention is the attribution: ``frame_attention`` fp32 [B, (n,) T-1, F], the
         cross-attention probabilities averaged over the heads and over all layers (``layer=None``) or one; each position's F
         values sum to 1.  ``x``, ``y``, ``lengths``, ``until_sep`` as in score; index j is the position that predicts
-        y[..., j + 1]; positions behind a row's length hold zeros.  One teacher-forced pass (score's, without the head)."""
+        y[..., j + 1]; positions behind a row's length hold zeros.  One teacher-forced pass (score's, without the head).
+        frame_counts (or ``x`` as a list of clips; as in greedy_decode): clips that differ in length; F stays mem_tokens and the
+        columns from a clip's count on hold 0."""
         from . import scoring
         ids, had_n = scoring.candidates(y, self._dev)
         B, n, T = ids.shape
-        if x.shape[0] != B:
+        if self._nclips(x) != B:
             raise ValueError("x and y disagree on the number of clips")
         if T < 2 or T > self.max_text_len + 1:
             raise ValueError(f"T={T} outside 2..max_text_len+1={self.max_text_len + 1}")
@@ -329,18 +455,14 @@ class StudentCaptioner(_NativeModule):
         with torch.cuda.device(self._dev):
             for b0 in range(0, B, Bc):
                 b1 = min(B, b0 + Bc)
-                mem = self._memory(self._src_memory(x[b0:b1]))
-                if n > 1:
-                    mem = mem.repeat_interleave(n, dim=0)
-                rows = (b1 - b0) * n
+                rows = self._set_memory(*self._clip_range(x, frame_counts, b0, b1), n)
                 cid = ids[b0:b1].reshape(rows, T)
                 cl = None if ln is None else (ln[b0:b1].reshape(rows) - 1).clamp_(min=0).to(torch.int32).contiguous()
                 fm = torch.empty((rows, T - 1, F), dtype=torch.float32, device=self._dev)
-                self._call("gitcap_student_set_memory", _lib.ptr(mem), rows, self._stream())
                 self._call("gitcap_student_attention", _lib.ptr(cid), T, rows, T - 1, lay, _lib.ptr(cl), _lib.ptr(fm), F, self._stream())
                 outs.append(fm)
         shape = (B, n) if had_n else (B,)
-        return dict(frame_attention=torch.cat(outs, 0).reshape(*shape, T - 1, F).to(x.device))
+        return dict(frame_attention=torch.cat(outs, 0).reshape(*shape, T - 1, F).to(x.device if isinstance(x, torch.Tensor) else x[0].device))
 
     def forward(self, x: torch.Tensor, y: torch.Tensor):
         """model.py:99-106: feature maps + [logits]."""
@@ -381,7 +503,7 @@ class StudentCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                       draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0,
-                      return_attention: bool = False):
+                      return_attention: bool = False, frame_counts=None):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
@@ -395,16 +517,24 @@ class StudentCaptioner(_NativeModule):
         logprobs): every step's k best tokens by (logit descending, id ascending) and their log-probabilities; rank 0 is the
         emitted token.  No logits tensor is written (include/gitcap.h: gitcap_attach_top_logprobs).  A ``draft`` call refuses it.
         ``return_attention``: the result gains, last, ``frame_attention`` fp32 [B, steps, F] (see attention()), from one
-        teacher-forced pass over the result behind the loop: bit for bit attention(src, ids, until_sep=False)."""
+        teacher-forced pass over the result behind the loop: bit for bit attention(src, ids, until_sep=False).
+        frame_counts: clips that differ in length -- ``src`` padded [B,Fmax,...] (frames, camera frames or memory) with
+        frame_counts [B], or ``src`` as a list of B clips [F_b,3,S,S] / uint8 [F_b,H,W,3] / memory [F_b,D], 1 <= F_b <=
+        mem_tokens.  The batch runs packed, without padding or masking (include/gitcap.h: gitcap_student_attach_frame_counts):
+        every clip's results are bit for bit those of the clip decoded alone by a model with mem_tokens = F_b."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
-        out_dev = src.device
-        memory = self._src_memory(src)
-        mem = self._memory(memory)
+        counts = None
+        if self._is_ragged(src, frame_counts):
+            mem, B, counts, out_dev = self._ragged_memory(src, frame_counts)
+        else:
+            out_dev = src.device
+            memory = self._src_memory(src)
+            mem = self._memory(memory)
+            B = mem.shape[0]
         if max_len < 1 or max_len > self.max_text_len:
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
-        B = mem.shape[0]
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
         lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
@@ -413,6 +543,7 @@ class StudentCaptioner(_NativeModule):
             tk = (torch.empty((B, max_len, int(top_logprobs)), dtype=torch.int64, device=self._dev),
                   torch.empty((B, max_len, int(top_logprobs)), dtype=torch.float32, device=self._dev))
         with torch.cuda.device(self._dev):
+            self._attach_counts(counts)
             if draft is not None:
                 self._draft_call("gitcap_student_greedy_draft", (_lib.ptr(mem), B), draft, max_len, mode, ids, steps, lp, tk)
             else:
@@ -438,17 +569,22 @@ class StudentCaptioner(_NativeModule):
     generate = greedy_decode
 
     @torch.no_grad()
-    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False) -> torch.Tensor:
+    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False, frame_counts=None) -> torch.Tensor:
         """model.py:189-318: k beams without end-of-sequence handling; returns the best beam [B, max_len].
         Runs on the device with the exact KV cache and no host round trip (``gitcap_student_beam_search``): the k beams
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
-        follow their beams."""
+        follow their beams.  frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length; the k
+        beams of a clip share its memory rows."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the beam family (beam_search) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
-        out_dev = src.device
-        memory = self._src_memory(src)
-        mem = self._memory(memory)
-        B = mem.shape[0]
+        counts = None
+        if self._is_ragged(src, frame_counts):
+            mem, B, counts, out_dev = self._ragged_memory(src, frame_counts)
+        else:
+            out_dev = src.device
+            memory = self._src_memory(src)
+            mem = self._memory(memory)
+            B = mem.shape[0]
         if B * k > self.max_batch:
             raise ValueError(f"B*k={B * k} rows > max_batch={self.max_batch}")
         if max_len - 1 > self.max_text_len:
@@ -457,12 +593,14 @@ class StudentCaptioner(_NativeModule):
             raise ValueError("beam_search needs max_len >= 2 and 1 <= k <= 16")
         best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
         with torch.cuda.device(self._dev):
+            self._attach_counts(counts)
             self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, _lib.ptr(best), self._stream())
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
-                       logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False) -> StudentCaptionStream:
+                       logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False,
+                       partial: bool = False) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -476,7 +614,12 @@ class StudentCaptioner(_NativeModule):
         ``logprobs`` (greedy streams only): after a push that returned a caption, ``stream.last_logprobs`` holds its per-token
         log-probabilities [B, steps] (greedy_decode's return_logprobs); works with ``gate`` and ``carry``.
         ``top_logprobs=k`` (greedy streams without ``carry``: a draft call does not carry alternatives): ``stream.last_top_ids`` /
-        ``stream.last_top_logprobs`` [B, steps, k] of that caption (greedy_decode's top_logprobs)."""
+        ``stream.last_top_logprobs`` [B, steps, k] of that caption (greedy_decode's top_logprobs).
+        ``partial``: a caption is due once ``hop`` frames have arrived, whether or not the window is full: the first captions
+        after a reset see the 1, 2, ... frames admitted so far (bit for bit greedy_decode on a list holding those frames), and
+        from mem_tokens frames on the stream is the ``partial=False`` one.  ``stream.last_frames`` = the frames the last
+        caption saw.  Works with ``gate``, ``logprobs`` and ``top_logprobs``; not with ``carry`` or ``beams``, whose window calls
+        need a full window (include/gitcap.h: gitcap_student_window_greedy_partial)."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
@@ -487,6 +630,8 @@ class StudentCaptioner(_NativeModule):
             raise ValueError("logprobs=True is for greedy streams: it cannot be combined with beams")
         if carry and beams is not None:
             raise ValueError("carry=True verifies the previous greedy caption: it cannot be combined with beams")
+        if partial and (carry or beams is not None):
+            raise ValueError("partial=True is for greedy streams without carry: the beam and draft window calls need a full window")
         if not self._native():
             raise _lib.GitcapError("caption_stream needs the native TinyViT encoder (image_encoder='native'): frames are "
                                    "encoded one at a time on the device")
@@ -505,7 +650,7 @@ class StudentCaptioner(_NativeModule):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:

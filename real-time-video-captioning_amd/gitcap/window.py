@@ -8,12 +8,13 @@ class WindowSchedule:
     """B clips advance in lockstep; each push appends n >= 1 frames per clip (n <= window).  A caption is due after a push once the
     window holds `window` frames and at least `hop` frames have arrived since the last caption (or since the reset).  hop = 1: a
     caption per new frame; hop = window: the reference's tumbling loop (src/real_time_inference.py:44-57: six frames, caption,
-    clear)."""
+    clear).  partial: a caption is due once `hop` frames have arrived, full window or not (StudentCaptioner.caption_stream)."""
 
-    def __init__(self, batch: int, window: int, hop: int = 1):
+    def __init__(self, batch: int, window: int, hop: int = 1, partial: bool = False):
         if batch < 1 or window < 1 or hop < 1:
             raise ValueError(f"batch, window and hop must be >= 1 (got {batch}, {window}, {hop})")
         self.batch, self.window, self.hop = int(batch), int(window), int(hop)
+        self.partial = bool(partial)
         self.reset()
 
     def reset(self):
@@ -32,7 +33,7 @@ class WindowSchedule:
         self.check(batch, n)
         self.pushed += n
         self.since += n
-        if self.pushed >= self.window and self.since >= self.hop:
+        if (self.partial or self.pushed >= self.window) and self.since >= self.hop:
             self.since = 0
             return True
         return False
