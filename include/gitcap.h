@@ -932,6 +932,56 @@ int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* a, void* stream);
  * gitcap_dbg_txt_block's with S_img = len[c] on that clip's keys. */
 int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* a, const int32_t* off, const int32_t* len, void* stream);
 
+/* The staging and layout kernels between those: csrc/preproc.hip and the plain row kernels at the top of csrc/rowops.hip, one launcher
+ * per hook on caller-owned device buffers (tests/test_staging_gpu.py; a plain fp64 statement of each: tests/staging_reference.py).
+ * No handle, no allocation; GITCAP_ERR_ARG, before any launch, for null pointers, misaligned pointers and sizes that would index
+ * outside a buffer.  (gitcap_preprocess is the fp32 form of the transform and needs no hook.)
+ *   preprocess_patches: gitcap_preprocess's transform fused with the patch gather -> bf16 rows [nf * (crop / p)^2][Kp], column
+ *                  c * p * p + py * p + px; columns >= 3 p^2 are NOT written.  crop % p == 0, Kp >= 3 p^2, Kp % 2 == 0.
+ *   preprocess_stem: the transform fused with the gather of a 3x3 stride-2 pad-1 convolution -> bf16 rows [nf * (crop / 2)^2][32],
+ *                  column ci * 9 + ky * 3 + kx, every column written (zero at taps outside the frame and at columns >= 27).  crop even,
+ *                  col 16-byte aligned.
+ *   im2col:        frames fp32 [nf][3][img][img] -> bf16 rows [nf * (img / p)^2][Kp], the same columns, zero from 3 p^2 on.  img % p == 0,
+ *                  p even, Kp >= 3 p^2; p % 4 == 0 and img % 4 == 0: Kp % 4 == 0, frames 16-byte and patches 8-byte aligned; else
+ *                  Kp % 2 == 0 and 4-byte alignment.
+ *   cast_bf16:     out bf16 [n] = in fp32 [n], round to nearest even; n % 4 == 0.
+ *   dequant_fp8:   out bf16 [rows][K] = e4m3 code w8[r][k] * scale[r] (a power of two: exact); K % 16 == 0.
+ *   dequant_fp8_batch: n <= 4 such matrices in one launch; the five arguments are HOST arrays of n entries.
+ *   embed_text:    row m = (r, j), r < rows, j < T: xf fp32 / xb bf16 [rows * T][D] = LayerNorm(word[id] + pos[t0 + j]) * gamma + beta,
+ *                  id = ids[r * ld_ids + j] clamped into [0, vocab).  Either of xf / xb may be NULL.  D % 4 == 0, D <= 1024, ld_ids >= T.
+ *   window_scatter: src fp32 [B][n][rows_per_frame][D] -> ring [B][F][rows_per_frame][D], frame j of clip b to slot (head + j) % F;
+ *                  no other slot is written.  n <= F, head < F, D % 4 == 0.
+ *   window_assemble: row (b, f, tok) of out bf16 [B * F * N][D] = ring[b][(head + f) % F][tok] + temporal[f] (fp32 add, then rounded);
+ *                  vis (nullable) = the fp32 sum; temporal (nullable) fp32 [F][D].  D % 4 == 0, D <= 1024.
+ *   ragged_tables: counts = HOST int32 [B], 1 .. 255 each, B <= 256: off[b] = N * sum_{i < b} counts[i], len[b] = N * counts[b],
+ *                  pos[frame] = the frame's index inside its clip; pos_cap = the entries pos holds (>= the sum of the counts).
+ *   ragged_temporal: row r of out bf16 [frames * N][D] = ln[r] + temporal[pos[r / N]], vis (nullable) the fp32 sum; pos is read back
+ *                  first: an entry outside [0, temporal_rows) is refused.
+ *   gather_hidden: out[b][e][s][:] = s < S_img ? img[e][b * S_img + s][:] : txt[e][b * T + s - S_img][:], e < n_entries, fp32 rows of D;
+ *                  entry e of img / txt starts e * the entry stride (in floats, % 4 == 0) behind the first.  D % 4 == 0.
+ *   gather_txt_rows: dst[l][r][t][:] = src[l][src_rows[r]][t][:], t < t_len, l < layers, bf16 rows of `width`, rows [.][Tmax][width],
+ *                  layers layer_stride elements apart; copied in pieces of 8 elements: t_len * width, Tmax * width and layer_stride
+ *                  are multiples of 8; t_len <= Tmax; src_rows (device int32 [rows], read back first) in [0, rows). */
+int gitcap_dbg_preprocess_patches(const uint8_t* frames_hwc_bgr, int nf, int H, int W, int crop, int p, int Kp, void* patches, void* stream);
+int gitcap_dbg_preprocess_stem(const uint8_t* frames_hwc_bgr, int nf, int H, int W, int crop, void* col, void* stream);
+int gitcap_dbg_im2col(const float* frames, int nf, int img, int p, int Kp, void* patches, void* stream);
+int gitcap_dbg_cast_bf16(const float* in, void* out, int64_t n, void* stream);
+int gitcap_dbg_dequant_fp8(const void* w8, const float* scale, void* out, int rows, int K, void* stream);
+int gitcap_dbg_dequant_fp8_batch(int n, const void* const* w8, const float* const* scale, void* const* out, const int32_t* rows,
+                                 const int32_t* K, void* stream);
+int gitcap_dbg_embed_text(const int64_t* ids, int ld_ids, int rows, int T, int t0, const float* word, const float* pos, const float* gamma,
+                          const float* beta, float eps, int D, int vocab, float* xf, void* xb, void* stream);
+int gitcap_dbg_window_scatter(const float* src, float* ring, int B, int n, int F, int head, int rows_per_frame, int D, void* stream);
+int gitcap_dbg_window_assemble(const float* ring, const float* temporal, void* out, float* vis, int B, int F, int head, int N, int D,
+                               void* stream);
+int gitcap_dbg_ragged_tables(const int32_t* counts, int B, int N, int32_t* off, int32_t* len, int32_t* pos, int pos_cap, void* stream);
+int gitcap_dbg_ragged_temporal(const float* ln, const float* temporal, int temporal_rows, const int32_t* pos, void* out, float* vis,
+                               int frames, int N, int D, void* stream);
+int gitcap_dbg_gather_hidden(const float* img, const float* txt, float* out, int n_entries, int B, int S_img, int T, int D,
+                             int64_t img_entry_stride, int64_t txt_entry_stride, void* stream);
+int gitcap_dbg_gather_txt_rows(const void* src, void* dst, const int32_t* src_rows, int rows, int t_len, int Tmax, int width, int layers,
+                               int64_t layer_stride, void* stream);
+
 /* The TinyViT encoder's kernels (csrc/tinyvit.hip) and the student decoder's attention (csrc/student.hip), one kernel per hook on
  * caller-owned device buffers (tests/test_encoder_kernels_gpu.py; a plain fp64 statement of each: tests/encoder_kernels_reference.py).
  * No handle, no weight upload; GITCAP_ERR_ARG for arguments the launcher refuses, before any launch.  Activations are bf16.

@@ -670,3 +670,134 @@ static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off,
 }
 
 }  // extern "C"
+
+// ---- staging and layout kernels (tests/test_staging_gpu.py): preproc.hip and the plain row kernels at the top of rowops.hip.  Each
+// hook is ONE launcher on caller-owned device buffers, no handle, no allocation; what the launcher does not check itself and a wrong
+// value of which would index outside a buffer (or fault on a misaligned vector access) is refused here, before any launch
+extern "C" {
+
+static bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int gitcap_dbg_preprocess_patches(const uint8_t* frames_hwc_bgr, int nf, int H, int W, int crop, int p, int Kp, void* patches, void* stream) {
+    if (!frames_hwc_bgr || !patches || !al(patches, 2) || Kp <= 0 || (Kp & 1)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_preprocess_patches(frames_hwc_bgr, (bf16_t*)patches, nf, H, W, crop, p, Kp, (hipStream_t)stream));
+}
+
+int gitcap_dbg_preprocess_stem(const uint8_t* frames_hwc_bgr, int nf, int H, int W, int crop, void* col, void* stream) {
+    if (!frames_hwc_bgr || !col || !al(col, 16)) return GITCAP_ERR_ARG;        // one row = four 16-byte stores
+    return dbg_rc(launch_preprocess_stem(frames_hwc_bgr, (bf16_t*)col, nf, H, W, crop, (hipStream_t)stream));
+}
+
+// launch_im2col checks nothing but the parity of p.  p % 4 == 0 and img % 4 == 0: 16-byte reads, 8-byte writes, Kp in pieces of 4;
+// else (p even): two floats, one 4-byte write, Kp in pieces of 2
+int gitcap_dbg_im2col(const float* frames, int nf, int img, int p, int Kp, void* patches, void* stream) {
+    if (!frames || !patches || nf <= 0 || img <= 0 || p <= 0 || img % p != 0 || (int64_t)Kp < 3 * (int64_t)p * p) return GITCAP_ERR_ARG;
+    const bool v4 = p % 4 == 0 && img % 4 == 0;
+    if (v4 ? (Kp % 4 != 0 || !al(frames, 16) || !al(patches, 8)) : (Kp % 2 != 0 || !al(frames, 4) || !al(patches, 4))) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_im2col(frames, (bf16_t*)patches, nf, img, p, Kp, (hipStream_t)stream));
+}
+
+int gitcap_dbg_cast_bf16(const float* in, void* out, int64_t n, void* stream) {
+    if (!in || !out || n <= 0 || !al(in, 16) || !al(out, 8)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_cast_bf16(in, (bf16_t*)out, n, (hipStream_t)stream));
+}
+
+int gitcap_dbg_dequant_fp8(const void* w8, const float* scale, void* out, int rows, int K, void* stream) {
+    if (!w8 || !scale || !out || !al(w8, 16) || !al(scale, 4) || !al(out, 16)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_dequant_fp8((const unsigned char*)w8, scale, (bf16_t*)out, rows, K, (hipStream_t)stream));
+}
+
+// the arrays are host arrays of n entries (n <= 4 is checked before they are read)
+int gitcap_dbg_dequant_fp8_batch(int n, const void* const* w8, const float* const* scale, void* const* out, const int32_t* rows,
+                                 const int32_t* K, void* stream) {
+    if (n <= 0 || n > 4 || !w8 || !scale || !out || !rows || !K) return GITCAP_ERR_ARG;
+    DequantBatch b{};
+    b.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] <= 0 || K[i] <= 0 || !al(w8[i], 16) || !al(scale[i], 4) || !al(out[i], 16)) return GITCAP_ERR_ARG;
+        b.w8[i] = (const unsigned char*)w8[i]; b.scale[i] = scale[i]; b.out[i] = (bf16_t*)out[i]; b.K[i] = K[i];
+        b.n16[i] = (int64_t)rows[i] * K[i] / 16;
+    }
+    return dbg_rc(launch_dequant_fp8_batch(b, (hipStream_t)stream));
+}
+
+// launch_embed_text checks nothing
+int gitcap_dbg_embed_text(const int64_t* ids, int ld_ids, int rows, int T, int t0, const float* word, const float* pos, const float* gamma,
+                          const float* beta, float eps, int D, int vocab, float* xf, void* xb, void* stream) {
+    if (!ids || !word || !pos || !gamma || !beta || (!xf && !xb) || rows <= 0 || T <= 0 || ld_ids < T || t0 < 0 || vocab <= 0 || D <= 0 ||
+        D > 1024 || (D & 3) || (int64_t)rows * T > 0x7fffffff)
+        return GITCAP_ERR_ARG;
+    if (!al(ids, 8) || !al(word, 16) || !al(pos, 16) || !al(gamma, 16) || !al(beta, 16) || !al(xf, 16) || !al(xb, 8)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_embed_text(ids, ld_ids, rows, T, t0, word, pos, gamma, beta, eps, D, vocab, xf, (bf16_t*)xb, (hipStream_t)stream));
+}
+
+int gitcap_dbg_window_scatter(const float* src, float* ring, int B, int n, int F, int head, int rows_per_frame, int D, void* stream) {
+    if (!src || !ring || !al(src, 16) || !al(ring, 16)) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_window_scatter(src, ring, B, n, F, head, rows_per_frame, D, (hipStream_t)stream));
+}
+
+int gitcap_dbg_window_assemble(const float* ring, const float* temporal, void* out, float* vis, int B, int F, int head, int N, int D,
+                               void* stream) {
+    if (!ring || !out || !al(ring, 16) || !al(temporal, 16) || !al(out, 8) || !al(vis, 16) || (int64_t)B * F * N > 0x7fffffff) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_window_assemble(ring, temporal, (bf16_t*)out, vis, B, F, head, N, D, (hipStream_t)stream));
+}
+
+// counts: HOST int32 [B], copied into the RaggedCounts the launch takes by value; pos_cap = the entries pos holds
+int gitcap_dbg_ragged_tables(const int32_t* counts, int B, int N, int32_t* off, int32_t* len, int32_t* pos, int pos_cap, void* stream) {
+    if (!counts || B <= 0 || B > 256 || N <= 0 || !off || !len || !pos || !al(off, 4) || !al(len, 4) || !al(pos, 4)) return GITCAP_ERR_ARG;
+    RaggedCounts rc{};
+    rc.B = B;
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 1 || counts[b] > 255) return GITCAP_ERR_ARG;
+        rc.n[b] = (unsigned char)counts[b];
+        total += counts[b];
+    }
+    if (total > pos_cap || total * N > 0x7fffffff) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ragged_tables(rc, N, off, len, pos, (hipStream_t)stream));
+}
+
+// pos (device int32 [frames]) is read back first (the call synchronises `stream`): an entry outside [0, temporal_rows) is refused
+int gitcap_dbg_ragged_temporal(const float* ln, const float* temporal, int temporal_rows, const int32_t* pos, void* out, float* vis,
+                               int frames, int N, int D, void* stream) {
+    if (!ln || !temporal || !pos || !out || frames <= 0 || N <= 0 || temporal_rows <= 0 || (int64_t)frames * N > 0x7fffffff || !al(ln, 16) ||
+        !al(temporal, 16) || !al(pos, 4) || !al(out, 8) || !al(vis, 16))
+        return GITCAP_ERR_ARG;
+    std::vector<int32_t> hp((size_t)frames);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(hp.data(), pos, (size_t)frames * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return GITCAP_ERR_HIP;
+    for (int f = 0; f < frames; ++f)
+        if (hp[f] < 0 || hp[f] >= temporal_rows) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ragged_temporal(ln, temporal, pos, (bf16_t*)out, vis, frames, N, D, (hipStream_t)stream));
+}
+
+// the entry strides are in floats; rows are copied 16 bytes at a time
+int gitcap_dbg_gather_hidden(const float* img, const float* txt, float* out, int n_entries, int B, int S_img, int T, int D,
+                             int64_t img_entry_stride, int64_t txt_entry_stride, void* stream) {
+    if (!img || !txt || !out || !al(img, 16) || !al(txt, 16) || !al(out, 16) || img_entry_stride < 0 || txt_entry_stride < 0 ||
+        (img_entry_stride & 3) || (txt_entry_stride & 3))
+        return GITCAP_ERR_ARG;
+    return dbg_rc(launch_gather_hidden(img, txt, out, n_entries, B, S_img, T, D, (size_t)img_entry_stride, (size_t)txt_entry_stride,
+                                       (hipStream_t)stream));
+}
+
+// gather_txt_rows_kernel copies a row's first t_len positions as t_len * width / 8 pieces of 16 bytes (8 bf16), from row bases at
+// multiples of Tmax * width behind layer bases at multiples of layer_stride: all three must be multiples of 8 elements.  src_rows
+// (device int32 [rows]) is read back first (the call synchronises `stream`): src and dst hold `rows` rows per layer
+int gitcap_dbg_gather_txt_rows(const void* src, void* dst, const int32_t* src_rows, int rows, int t_len, int Tmax, int width, int layers,
+                               int64_t layer_stride, void* stream) {
+    if (!src || !dst || src == dst || !src_rows || rows <= 0 || layers <= 0 || width <= 0 || Tmax <= 0 || t_len < 0 || t_len > Tmax ||
+        !al(src, 16) || !al(dst, 16) || !al(src_rows, 4))
+        return GITCAP_ERR_ARG;
+    const int64_t row = (int64_t)Tmax * width;
+    if (row > 0x7fffffff || (((int64_t)t_len * width) & 7) || (row & 7) || (layer_stride & 7) || layer_stride < (int64_t)rows * row) return GITCAP_ERR_ARG;
+    std::vector<int32_t> hr((size_t)rows);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(hr.data(), src_rows, (size_t)rows * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return GITCAP_ERR_HIP;
+    for (int r = 0; r < rows; ++r)
+        if (hr[r] < 0 || hr[r] >= rows) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_gather_txt_rows((const bf16_t*)src, (bf16_t*)dst, src_rows, rows, t_len, Tmax, width, layers, (size_t)layer_stride,
+                                         (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void embed_text_kernel(const int64_t* __restri
     f32x4 v[NV];
     const float s = row_load_embed<NV>(v, ids, ld_ids, T, t0, word, pos, D, vocab, m, lane);
     row_layernorm<NV>(v, s, lane, D, eps, gamma, beta);
-    row_store<NV>(v, lane, D, xf + (size_t)m * D, xb + (size_t)m * D);
+    row_store<NV>(v, lane, D, xf ? xf + (size_t)m * D : nullptr, xb ? xb + (size_t)m * D : nullptr);   // either may be null (row_store)
 }
 
 // ---- split-K reduce + bias + residual + LayerNorm (text rows) (rowln.h) ---------------------------------------------

@@ -300,6 +300,22 @@ SYMBOLS = {
     "gitcap_dbg_kmeans_assign": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_kmeans_update": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gitcap_frame_select": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    # staging and layout kernels, one launcher per hook (tests/test_staging_gpu.py)
+    "gitcap_dbg_preprocess_patches": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gitcap_dbg_preprocess_stem": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gitcap_dbg_im2col": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gitcap_dbg_cast_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "gitcap_dbg_dequant_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "gitcap_dbg_dequant_fp8_batch": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32),
+                                             POINTER(c_int32), c_void_p]),
+    "gitcap_dbg_embed_text": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p]),
+    "gitcap_dbg_window_scatter": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_window_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_ragged_tables": (c_int, [POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_ragged_temporal": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_gather_hidden": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p]),
+    "gitcap_dbg_gather_txt_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
 }
 
 _lib = None
