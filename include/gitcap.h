@@ -932,8 +932,8 @@ int gitcap_dbg_txt_block(const gitcap_dbg_txt_block_args* a, void* stream);
  * gitcap_dbg_txt_block's with S_img = len[c] on that clip's keys. */
 int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* a, const int32_t* off, const int32_t* len, void* stream);
 
-/* The staging and layout kernels between those: csrc/preproc.hip and the plain row kernels at the top of csrc/rowops.hip, one launcher
- * per hook on caller-owned device buffers (tests/test_staging_gpu.py; a plain fp64 statement of each: tests/staging_reference.py).
+/* The staging and layout kernels between those: csrc/preproc.hip, the plain row kernels of csrc/rowops.hip and the text embedding
+ * of csrc/select.hip, one launcher per hook on caller-owned device buffers (tests/test_staging_gpu.py; a plain fp64 statement of each: tests/staging_reference.py).
  * No handle, no allocation; GITCAP_ERR_ARG, before any launch, for null pointers, misaligned pointers and sizes that would index
  * outside a buffer.  (gitcap_preprocess is the fp32 form of the transform and needs no hook.)
  *   preprocess_patches: gitcap_preprocess's transform fused with the patch gather -> bf16 rows [nf * (crop / p)^2][Kp], column
@@ -1219,7 +1219,7 @@ int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int s
  * at a temperature -- LOSS 2 of DistillationTrainer.training_step (src/models/model.py:919-935: KLDivLoss('batchmean') of
  * log_softmax(student / t) against softmax(teacher / t)) -- without either model's [rows * T][V] logits: both vocabulary heads run
  * over the same 16-column tiles in one launch that keeps seven per-tile statistics, and one merge launch follows (csrc/skinny.hip:
- * skinny_head_dual_kernel, csrc/rowops.hip: distill_final_kernel).
+ * skinny_head_dual_kernel, csrc/select.hip: distill_final_kernel).
  * Preconditions: gitcap_score's on the teacher (after gitcap_encode / gitcap_set_visual; rows = encoded clips * beams) and
  * gitcap_student_score's on the student (after gitcap_student_set_memory with `rows` rows, a clip's rows repeating its memory);
  * both handles on one device, equal vocab_size, widths (768 | 1024, 576) or (128, 64), temperature > 0 and finite, T >= 1,

@@ -671,8 +671,8 @@ static int dbg_txt_block(const gitcap_dbg_txt_block_args* g, const int32_t* off,
 
 }  // extern "C"
 
-// ---- staging and layout kernels (tests/test_staging_gpu.py): preproc.hip and the plain row kernels at the top of rowops.hip.  Each
-// hook is ONE launcher on caller-owned device buffers, no handle, no allocation; what the launcher does not check itself and a wrong
+// ---- staging and layout kernels (tests/test_staging_gpu.py): preproc.hip, the plain row kernels of rowops.hip and the text
+// embedding of select.hip.  Each hook is ONE launcher on caller-owned device buffers, no handle, no allocation; what the launcher does not check itself and a wrong
 // value of which would index outside a buffer (or fault on a misaligned vector access) is refused here, before any launch
 extern "C" {
 

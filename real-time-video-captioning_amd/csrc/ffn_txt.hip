@@ -7,7 +7,7 @@
 // 16x16x32 MFMA chain of skinny_full_kernel), rounds to bf16 exactly where the FC1 launch did and leaves them in LDS;
 // after one barrier every wave multiplies the 16 x 64 tile of h into its quarter of the D output columns (two k-steps per
 // 16-column tile) and writes its fp32 partial.  The dec_ffn / 64 slabs are summed in a fixed order by ln_reduce_kernel
-// (rowops.hip) or by the row prologue of the next layer's q|k|v launch (rowln.h), with bias + residual + LayerNorm.
+// (select.hip) or by the row prologue of the next layer's q|k|v launch (rowln.h), with bias + residual + LayerNorm.
 //
 // What it replaces: the FC1 + GELU launch (192 single-wave workgroups, h through HBM) and the FC2 split-K launch (384):
 // one dependent stage (~5 us) of every decoder layer of every token step.  What makes it possible: the fragment-major

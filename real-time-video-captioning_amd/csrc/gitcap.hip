@@ -1354,7 +1354,6 @@ static int greedy_text_loop(gitcap* h, int B, int max_len, int stop, int64_t* id
 // draft, and every caption keeps its own leading matches (launch_draft_accept_rows; the first position that differs holds the
 // loop's own token).  The loop goes on at the first step some caption lacks; captions ahead of it keep their tokens (KEEP arg-max)
 // and recompute K/V from them.  The call's options: lp only (a prompt or constraints are refused by the entry points).
-struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
 static int ensure_draft(gitcap* h) {
     gitcap::Slot& sl = h->slots[0];
     const size_t Bm = (size_t)h->c.max_batch;

@@ -112,6 +112,9 @@ int tk_check(H* h, const char* who, const TopkAttach& tk, int positions) {
     return 0;
 }
 
+// The draft of the *_greedy_draft entry points of both handles: ids [B][ld], columns 1..n the draft's tokens; accepted_out nullable.
+struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
+
 // Ordering of a window ring's pushes and reads, whichever streams they are issued on: a push waits for the last read and the
 // last push (they share the staging rows) and records the ring event; a read waits for the ring event and records the read event.
 struct RingOrder {

@@ -5,7 +5,7 @@
 #include <atomic>
 #include <cstddef>
 
-// ---- big-tile bf16 MFMA GEMM:  C[m][n] = sum_k A[m][k] * W[n][k]  (+ epilogue) -------------
+// ---- big-tile bf16 MFMA GEMM:  C[m][n] = sum_k A[m][k] * W[n][k]  (+ epilogue) (gemm.hip, gemm256.hip) ----
 enum GemmEpi {
     EPI_BIAS_BF16 = 0,        // out bf16 = acc + bias
     EPI_BIAS_QGELU_BF16 = 1,  // out bf16 = quick_gelu(acc + bias)      (CLIP MLP)
@@ -61,7 +61,7 @@ bool gemm256_ln_ok(const GemmArgs& a);                                   // shap
 bool gemm256f8_ok(const GemmArgs& a);                                    // fp8 operands: K % 128 == 0, wscale / ascale set
 hipError_t launch_gemm256f8(const GemmArgs& a, int epi, hipStream_t s);  // the same tile kernel on e4m3 operands (gemm256.hip)
 
-// ---- skinny GEMMs (text rows; M = a few 16-row tiles): weight streaming, one wave per tile ----
+// ---- skinny GEMMs (text rows; M = a few 16-row tiles): weight streaming, one wave per tile (skinny.hip) ----
 enum SkinnyEpi { SK_BIAS_BF16 = 0, SK_BIAS_GELU_BF16 = 1, SK_BIAS_RELU_BF16 = 2, SK_BIAS_F32 = 3 };
 struct SkinnyArgs {
     const bf16_t* X; int ldx;     // bf16 activations, row m at X + m*ldx
@@ -108,21 +108,11 @@ struct HeadTargets { const int64_t* ids; int T, ld, shift; float* logit; };
 // Ban mask of the constrained vocabulary head (gitcap_attach_constraints; kernels of their own, skinny.hip "BAN"): uint16
 // [rows][ld], bit c & 15 of word c >> 4 of row m set = column c of head row m is banned; one word = one 16-column tile.
 // ld >= ceil(N / 16) and even (rows 4-byte aligned).  A banned column's logit is -inf before a.out, the arg-max partial and
-// the sum partial are formed.  Built by launch_ban_mask (rowops.hip).
+// the sum partial are formed.  Built by launch_ban_mask (search.hip).
 struct HeadBan { const uint16_t* mask; int ld; };
 // tg (nullable): SK_BIAS_F32 with all three partial buffers set; a.out stays nullable
 // bn (nullable; not with tg or a row prologue): SK_BIAS_F32, the BAN form of the head (plain, or with amax_sum the LSE form)
 hipError_t launch_skinny(const SkinnyArgs& a, int epi, hipStream_t s, const HeadTargets* tg = nullptr, const HeadBan* bn = nullptr);
-// One workgroup per row builds the row's ban mask from scratch (every word of the row is written: the buffer is reused every
-// step): the union of
-//   n-gram (n >= 1; HF NoRepeatNGramLogitsProcessor): prefix[i + n - 1] for every i in 0 .. cur_len - n whose n - 1 tokens
-//           prefix[i .. i + n - 2] equal the last n - 1 tokens of the prefix (n = 1: every token of the prefix);
-//   length: sep_id while cur_len < min_length (HF MinLengthLogitsProcessor);
-//   suppress: the n_suppress ids of the device list (int32, duplicates allowed).
-// prefix = ids[row * ld_ids + 0 .. cur_len - 1], compared as values; an id outside [0, V) bans nothing.  Bits of the last word
-// beyond V and the words behind ceil(V / 16) are 0.  V <= 131072 (the row's bitmap is built in LDS), n_suppress <= 256.
-hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
-                           const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s);
 // The vocabulary head's launch_skinny(SK_BIAS_F32) arguments over the bf16 rows xb [rows * T][D] (host only): every position
 // (all_positions) or the last position of every row.  The partial buffers are nullable.  Returns the row stride and offset at
 // which launch_argmax_final finds the last position of each row among the head's rows.
@@ -168,53 +158,6 @@ struct HeadTopkArgs {
 };
 bool head_topk_ok(int D, bool fp8);                          // widths the kernel is instantiated for (launch_skinny's)
 hipError_t launch_head_topk(const HeadTopkArgs& a, hipStream_t s);
-// Teacher-forced scoring of given captions ids [rows][ld_ids] (CLS first) from the head's partials of all rows x T positions
-// (row m = r * T + j) and the target logits the scoring head captured (HeadTargets with shift 1).  Position (r, j), j < T - 1,
-// is counted unless its target y = ids[r][j + 1] lies outside [0, V), equals ignore_id, or lengths (nullable, device) has
-// j + 1 >= lengths[r].  One workgroup per (r, j): top1_ids / top1_lp [rows][T - 1] (nullable) = launch_argmax_final's token and
-// log-probability of row m, bit for bit; lp[r * ld_lp + j] = (logit[m] - max) - log(total) of a counted position (-inf for a
-// -inf target logit, never NaN), 0 of an ignored one.  row_sum / row_cnt (nullable; a second launch, one thread per row) = the
-// sum of the counted positions' lp in ascending position order and their number.  lp is required (the caller's or a scratch).
-struct ScoreOut { float* lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; };
-hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
-                              const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
-                              const ScoreOut& o, hipStream_t s);
-// The scoring head over the bf16 rows xb [rows * T][D] + launch_score_final (host only; what gitcap_score / gitcap_student_score
-// run behind their decoder stacks).  scratch: fp32 [2][rows * T] = the target logits, then the lp rows where the caller wants none.
-// topk (k != 0; gitcap_attach_top_logprobs): also the k best columns of positions 0 .. T - 2 of every row, counted or not, to
-// topk.ids / topk.lp [rows][topk.ld][k] (launch_head_topk over the same partials: rank 0 = top1_ids / top1_lp bit for bit).
-struct ScoreReq { const int32_t* lengths; int64_t ignore_id; float* token_lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; TopkAttach topk{}; };
-inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int64_t* ids, int ld_ids, int rows, int T, float* amax_val,
-                               int* amax_idx, float* amax_sum, float* scratch, const ScoreReq& q, hipStream_t s) {
-    SkinnyArgs ha;
-    vocab_head_args(ha, hw, xb, rows, T, true, nullptr, amax_val, amax_idx, amax_sum);
-    const HeadTargets tg{ids, T, ld_ids, 1, scratch};
-    hipError_t e = launch_skinny(ha, SK_BIAS_F32, s, &tg);
-    if (e != hipSuccess) return e;
-    const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
-    e = launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
-    if (e != hipSuccess || !q.topk.k) return e;
-    HeadTopkArgs ta{};
-    ta.X = xb; ta.ldx = hw.D; ta.hw = hw; ta.val = amax_val; ta.idx = amax_idx; ta.sum = amax_sum;
-    ta.rows = rows; ta.T = T - 1; ta.row_stride = T; ta.row_off = 0;
-    ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
-    return launch_head_topk(ta, s);
-}
-// One pass of a handle's decoder stack over text rows, and what its vocabulary head produces (host only; the request of both
-// handles' text_forward, gitcap.hip and student.hip -- the teacher's TextReq adds what only its stack takes).
-struct RowsReq {
-    // which rows and positions: ids [rows][ld_ids], query positions t0 .. t0 + T - 1 (K/V of earlier positions come from the cache)
-    const int64_t* ids = nullptr; int ld_ids = 0, rows = 0, t0 = 0, T = 0;
-    // what the head produces; none of logits_out / argmax_out / score: the stack's rows only, no head
-    float* logits_out = nullptr;                    // nullable: fp32 logits
-    int64_t* argmax_out = nullptr; int ld_argmax = 0;   // nullable: the last position's arg-max of every row (launch_argmax_final's out)
-    int32_t* sep_cnt = nullptr; int step = 0;       // launch_argmax_final's
-    float* lp_out = nullptr; int ld_lp = 0;         // nullable, needs argmax_out: the token's log-probability
-    const ScoreReq* score = nullptr;                // nullable: all positions through launch_score instead
-    // k != 0, needs argmax_out: the k best columns of the row the arg-max reads (launch_head_topk behind the arg-max launch; the head
-    // runs its LSE form); ids / lp point at this position's entries of row 0, ld = the row pitch in positions
-    TopkAttach topk{};
-};
 // ---- teacher-student divergence (gitcap_distill): both vocabulary heads over the same tiles, then one merge -------------------
 // launch_head_dual (skinny.hip: skinny_head_dual_kernel): the teacher's rows Xt [M][ldxt] against wt (bf16, or e4m3 codes with
 // wscale) and the student's rows Xs [M][ldxs] against ws (bf16), (wt.D, ws.D) one of (768, 576), (1024, 576), (128, 64), equal V.
@@ -231,31 +174,9 @@ struct DualHeadArgs {
 };
 bool head_dual_ok(int Kt, int Ks);
 hipError_t launch_head_dual(const DualHeadArgs& a, hipStream_t s);
-// launch_distill_final (rowops.hip): one workgroup per (row r, position j < T) merges the partials of head row m = r * T + j in
-// launch_score_final's fixed order: each model's winner and log-sum-exp exactly as score_final_kernel forms them, C = sum over the
-// tiles of e^(t_max - Mt) (cross + t_sum ((t_max - Mt) - (s_max - Ms))), kl = C / Zt - log Zt + log Zs (a value in [-DISTILL_CLAMP,
-// 0) becomes 0, DISTILL_CLAMP = the two logs' share of the rounding bound: tests/distill_reference.py; +inf where the teacher puts mass on a column the
-// student excludes; 0 for a row the teacher gives no column at all).  A position j >= lengths[r] (nullable) gets kl 0 and is not
-// counted.  top1 / agree [rows][T] cover every position; t_lp / s_lp [rows][ld_lp] = the given next token's log-probability at
-// positions 0 .. T - 2 under launch_score_final's rules (0 where ignored), need t_logit / s_logit.  All outputs but kl nullable.
-// row_kl_sum / row_cnt (a second launch, one thread per row): the counted positions' kl in ascending order, and their number.
-constexpr float DISTILL_CLAMP = 4e-5f;                     // 2 x the 2e-5 nats of a merged log-sum-exp
-struct DistillOut {
-    float* kl; int ld_kl; int64_t *t_top1, *s_top1; uint8_t* agree; float *t_lp, *s_lp; int ld_lp; float* row_kl_sum; int32_t* row_cnt;
-};
-struct DistillPartials { const float* t_max; const int* t_idx; const float *t_sum, *s_max; const int* s_idx; const float *s_sum, *cross; };
-hipError_t launch_distill_final(const DistillPartials& p, int ntiles, const float* t_logit, const float* s_logit, const int64_t* ids,
-                                int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V, const DistillOut& o,
-                                hipStream_t s);
 bool skinny_full_ok(int K);                                 // K depths launch_skinny is instantiated for
 int skinny_ksplit(int K);                                    // number of K slabs launch_skinny_splitk writes
 hipError_t launch_skinny_splitk(const SkinnyArgs& a, hipStream_t s);
-// x = LayerNorm(sum_s slab[s][m][:] + bias + resid[m][:]) -> xf (fp32) and xb (bf16); one wave per row
-hipError_t launch_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid,
-                            const float* gamma, const float* beta, float eps, int M, int D,
-                            float* xf, bf16_t* xb, hipStream_t s);
-// fragment-major copy of a GEMM weight [rows16][K] (bf16: elem_bytes 2, e4m3 codes: 1) for the weight-streaming text kernels
-hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, hipStream_t s);
 
 // ---- fused FC1 -> GELU -> FC2 of the text rows over hidden slices (ffn_txt.hip) -----------------------------------------
 // Workgroup s owns hidden units 64 s .. 64 s + 63: h = GELU(X W1_s^T + b1_s) rounded to bf16 (exactly the FC1 launch's
@@ -272,7 +193,8 @@ struct FfnTxtArgs {
 };
 bool ffn_txt_ok(int D, int F);
 hipError_t launch_ffn_txt(const FfnTxtArgs& a, hipStream_t s);
-// ---- token selection (rowops.hip): host-only records, passed by const&; the kernels receive their scalars and pointers ---------
+// ---- the text rows' kernels around the decoder stack (select.hip) ------------------------------------------------------------------
+// token selection: host-only records, passed by const&; the kernels receive their scalars and pointers
 // emb (nullable; greedy loop, one position per row): the kernel goes on to embed the token it just chose at text position
 // emb->position -- word + position embedding -> LayerNorm -> xf / xb row r (rowln.h: the code of launch_embed_text) -- so
 // the next token step starts at its q|k|v projection.
@@ -301,6 +223,14 @@ struct ArgmaxArgs {
     const int32_t* keep_len;
 };
 hipError_t launch_argmax_final(const ArgmaxArgs& a, hipStream_t s);
+// text embedding + LN: row m=(r, j) -> token ids[r*ld_ids + j], position t0 + j
+hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, int t0,
+                             const float* word, const float* pos, const float* gamma, const float* beta,
+                             float eps, int D, int vocab, float* x_f32, bf16_t* x_bf16, hipStream_t s);
+// x = LayerNorm(sum_s slab[s][m][:] + bias + resid[m][:]) -> xf (fp32) and xb (bf16); one wave per row
+hipError_t launch_ln_reduce(const float* slabs, int nslab, const float* bias, const float* resid,
+                            const float* gamma, const float* beta, float eps, int M, int D,
+                            float* xf, bf16_t* xb, hipStream_t s);
 // Draft verification of the student's greedy loop: the partials hold B x n rows (row r * n + j = position j of caption r, n <= 63);
 // reduces them under launch_argmax_final's tie rule and compares with the draft tokens staged in ids [B][ld] (columns 1..n; -1 =
 // not a word).  a = the leading positions at which every row's token equals its draft token; ids columns 1..min(a + 1, n) and
@@ -341,8 +271,144 @@ struct DraftAcceptRowsArgs {
 };
 hipError_t launch_draft_stage(const int64_t* draft, int ld_draft, int n, int rows, int vocab, int64_t cls, int64_t* ids, int ld, hipStream_t s);
 hipError_t launch_draft_accept_rows(const DraftAcceptRowsArgs& a, hipStream_t s);
+// Teacher-forced scoring of given captions ids [rows][ld_ids] (CLS first) from the head's partials of all rows x T positions
+// (row m = r * T + j) and the target logits the scoring head captured (HeadTargets with shift 1).  Position (r, j), j < T - 1,
+// is counted unless its target y = ids[r][j + 1] lies outside [0, V), equals ignore_id, or lengths (nullable, device) has
+// j + 1 >= lengths[r].  One workgroup per (r, j): top1_ids / top1_lp [rows][T - 1] (nullable) = launch_argmax_final's token and
+// log-probability of row m, bit for bit; lp[r * ld_lp + j] = (logit[m] - max) - log(total) of a counted position (-inf for a
+// -inf target logit, never NaN), 0 of an ignored one.  row_sum / row_cnt (nullable; a second launch, one thread per row) = the
+// sum of the counted positions' lp in ascending position order and their number.  lp is required (the caller's or a scratch).
+struct ScoreOut { float* lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; };
+hipError_t launch_score_final(const float* amax_val, const int* amax_idx, const float* amax_sum, int ntiles, const float* tgt_logit,
+                              const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V,
+                              const ScoreOut& o, hipStream_t s);
+// launch_distill_final (select.hip): one workgroup per (row r, position j < T) merges the partials of head row m = r * T + j in
+// launch_score_final's fixed order: each model's winner and log-sum-exp exactly as score_final_kernel forms them, C = sum over the
+// tiles of e^(t_max - Mt) (cross + t_sum ((t_max - Mt) - (s_max - Ms))), kl = C / Zt - log Zt + log Zs (a value in [-DISTILL_CLAMP,
+// 0) becomes 0, DISTILL_CLAMP = the two logs' share of the rounding bound: tests/distill_reference.py; +inf where the teacher puts mass on a column the
+// student excludes; 0 for a row the teacher gives no column at all).  A position j >= lengths[r] (nullable) gets kl 0 and is not
+// counted.  top1 / agree [rows][T] cover every position; t_lp / s_lp [rows][ld_lp] = the given next token's log-probability at
+// positions 0 .. T - 2 under launch_score_final's rules (0 where ignored), need t_logit / s_logit.  All outputs but kl nullable.
+// row_kl_sum / row_cnt (a second launch, one thread per row): the counted positions' kl in ascending order, and their number.
+constexpr float DISTILL_CLAMP = 4e-5f;                     // 2 x the 2e-5 nats of a merged log-sum-exp
+struct DistillOut {
+    float* kl; int ld_kl; int64_t *t_top1, *s_top1; uint8_t* agree; float *t_lp, *s_lp; int ld_lp; float* row_kl_sum; int32_t* row_cnt;
+};
+struct DistillPartials { const float* t_max; const int* t_idx; const float *t_sum, *s_max; const int* s_idx; const float *s_sum, *cross; };
+hipError_t launch_distill_final(const DistillPartials& p, int ntiles, const float* t_logit, const float* s_logit, const int64_t* ids,
+                                int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id, int V, const DistillOut& o,
+                                hipStream_t s);
+hipError_t launch_finish_steps(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out, hipStream_t s);
+hipError_t launch_fill_i64(int64_t* p, int ld, int rows, int64_t v, hipStream_t s);
+// p[r][0 .. lengths[r] - 1] = prompt.ids[r][the same], r < rows (ld >= prompt.max_len): the start of a prompted greedy loop
+hipError_t launch_fill_prompt(int64_t* p, int ld, int rows, const PromptArgs& prompt, hipStream_t s);
+// ---- host-only composites of the launchers above, defined here -----------------------------------------------------------------
+// The scoring head over the bf16 rows xb [rows * T][D] + launch_score_final (host only; what gitcap_score / gitcap_student_score
+// run behind their decoder stacks).  scratch: fp32 [2][rows * T] = the target logits, then the lp rows where the caller wants none.
+// topk (k != 0; gitcap_attach_top_logprobs): also the k best columns of positions 0 .. T - 2 of every row, counted or not, to
+// topk.ids / topk.lp [rows][topk.ld][k] (launch_head_topk over the same partials: rank 0 = top1_ids / top1_lp bit for bit).
+struct ScoreReq { const int32_t* lengths; int64_t ignore_id; float* token_lp; int ld_lp; float* row_sum; int32_t* row_cnt; int64_t* top1_ids; float* top1_lp; TopkAttach topk{}; };
+inline hipError_t launch_score(const HeadWeight& hw, const bf16_t* xb, const int64_t* ids, int ld_ids, int rows, int T, float* amax_val,
+                               int* amax_idx, float* amax_sum, float* scratch, const ScoreReq& q, hipStream_t s) {
+    SkinnyArgs ha;
+    vocab_head_args(ha, hw, xb, rows, T, true, nullptr, amax_val, amax_idx, amax_sum);
+    const HeadTargets tg{ids, T, ld_ids, 1, scratch};
+    hipError_t e = launch_skinny(ha, SK_BIAS_F32, s, &tg);
+    if (e != hipSuccess) return e;
+    const ScoreOut o{q.token_lp ? q.token_lp : scratch + (size_t)rows * T, q.token_lp ? q.ld_lp : T - 1, q.row_sum, q.row_cnt, q.top1_ids, q.top1_lp};
+    e = launch_score_final(amax_val, amax_idx, amax_sum, (hw.V + 15) / 16, scratch, ids, ld_ids, rows, T, q.lengths, q.ignore_id, hw.V, o, s);
+    if (e != hipSuccess || !q.topk.k) return e;
+    HeadTopkArgs ta{};
+    ta.X = xb; ta.ldx = hw.D; ta.hw = hw; ta.val = amax_val; ta.idx = amax_idx; ta.sum = amax_sum;
+    ta.rows = rows; ta.T = T - 1; ta.row_stride = T; ta.row_off = 0;
+    ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
+    return launch_head_topk(ta, s);
+}
+// One pass of a handle's decoder stack over text rows, and what its vocabulary head produces (host only; the request of both
+// handles' text_forward, gitcap.hip and student.hip -- the teacher's TextReq adds what only its stack takes).
+struct RowsReq {
+    // which rows and positions: ids [rows][ld_ids], query positions t0 .. t0 + T - 1 (K/V of earlier positions come from the cache)
+    const int64_t* ids = nullptr; int ld_ids = 0, rows = 0, t0 = 0, T = 0;
+    // what the head produces; none of logits_out / argmax_out / score: the stack's rows only, no head
+    float* logits_out = nullptr;                    // nullable: fp32 logits
+    int64_t* argmax_out = nullptr; int ld_argmax = 0;   // nullable: the last position's arg-max of every row (launch_argmax_final's out)
+    int32_t* sep_cnt = nullptr; int step = 0;       // launch_argmax_final's
+    float* lp_out = nullptr; int ld_lp = 0;         // nullable, needs argmax_out: the token's log-probability
+    const ScoreReq* score = nullptr;                // nullable: all positions through launch_score instead
+    // k != 0, needs argmax_out: the k best columns of the row the arg-max reads (launch_head_topk behind the arg-max launch; the head
+    // runs its LSE form); ids / lp point at this position's entries of row 0, ld = the row pitch in positions
+    TopkAttach topk{};
+};
 
-// ---- attention ---------------------------------------------------------------------------
+// ---- candidate generation and the beam state of the search loops (search.hip) ------------------------------------------------------
+// The candidates of one search step, what launch_beam_topk (the K best) and launch_sample_rows (draws) have in common: B * beams rows
+// of logits [.][ld] (V columns) ranked under log_softmax + beam_scores; candidate slots out_scores / out_idx [B][K] (K = beams * pn
+// for draws).
+struct CandArgs {
+    const float* logits; int ld;
+    const float* beam_scores;
+    // rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
+    // prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
+    // often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
+    const int64_t* prefix_ids; int ld_ids, cur_len; float rp;
+    int B, beams, V;
+    float* out_scores; int* out_idx;
+    // bn (nullable): row b * beams + j of the mask bans columns of that beam row before the penalty, the chunk statistics and the
+    // chunk's top K (the BAN forms of the chunk kernel, combinable with the penalty): the log-softmax is that of the banned row;
+    // draws: banned columns are -inf before the penalty, the temperature and the filter -- the BAN form of the kernel.
+    const HeadBan* bn;
+};
+// top-K over (beam, vocab) of log_softmax(logits) + beam_scores per batch element: sorted descending, ties by smaller flat index
+// j*V + v.  Logits of -inf are no candidates; where a clip has fewer than K candidates the remaining slots hold the sentinel
+// (score -inf, index 0x7fffffff) -- launch_beam_step divides the index by V and must never be handed one.
+size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scratch launch_beam_topk needs (V <= 131072)
+hipError_t launch_beam_topk(const CandArgs& c, int K, void* scratch, hipStream_t s);
+// the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
+// (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
+// candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (search.hip).
+// opt = the call's SampleOpt (host_logic.h; `on` is not read).
+// kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
+struct SampleStats { int* kept_out; float* logz_out; };
+hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& opt, const SampleStats& st, hipStream_t s);
+// One workgroup per row builds the row's ban mask from scratch (every word of the row is written: the buffer is reused every
+// step): the union of
+//   n-gram (n >= 1; HF NoRepeatNGramLogitsProcessor): prefix[i + n - 1] for every i in 0 .. cur_len - n whose n - 1 tokens
+//           prefix[i .. i + n - 2] equal the last n - 1 tokens of the prefix (n = 1: every token of the prefix);
+//   length: sep_id while cur_len < min_length (HF MinLengthLogitsProcessor);
+//   suppress: the n_suppress ids of the device list (int32, duplicates allowed).
+// prefix = ids[row * ld_ids + 0 .. cur_len - 1], compared as values; an id outside [0, V) bans nothing.  Bits of the last word
+// beyond V and the words behind ceil(V / 16) are 0.  V <= 131072 (the row's bitmap is built in LDS), n_suppress <= 256.
+hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
+                           const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s);
+// device-resident beam search state + one bookkeeping step per decoder step
+struct BeamBuffers {
+    int64_t *ids0, *ids1, *words, *hyp_ids;
+    float *beam_scores, *hyp_score;
+    int32_t *src_rows, *done, *hyp_len;
+};
+// n finished hypotheses per clip (1 <= n <= 16): hyp_ids [B][n][max_len], hyp_score / hyp_len [B][n], stored in storage order in
+// slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes all B * n).  step: n = 1 runs beam_step_kernel, n > 1 the n-slot kernel.
+// finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_*: rank 0 again as [B][max_len] / [B]; all nullable.
+hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s);
+struct BeamStepArgs {
+    int n;                                      // hypothesis slots per clip
+    const float* cand_scores; const int* cand_idx;   // [B][K]: launch_beam_topk's or launch_sample_rows'
+    int B, beams, K, V;
+    int cur_len, max_len, eos; float length_penalty;
+    int cur;                                    // which of ids0 / ids1 holds the current prefixes
+    // sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates
+    // are walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
+    bool sampled;
+    // prompt (nullable; rows = clips): a clip with cur_len < lengths[b] is forced -- every beam keeps its prefix and appends
+    // ids[b][cur_len], src_rows is the identity, beam_scores / done / the hypothesis slots are untouched, the candidates are not
+    // read; with cur_len >= max_len (the prompt's) the launch is the one without a prompt.
+    const PromptArgs* prompt;
+};
+hipError_t launch_beam_step(const BeamBuffers& bb, const BeamStepArgs& a, hipStream_t s);
+struct BeamFinishOut { int64_t* decoded; float* logprobs; int64_t* first_decoded; float* first_logprobs; };
+hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, const BeamFinishOut& o, hipStream_t s);
+
+// ---- attention (attention.hip) ------------------------------------------------------------
 // Full (unmasked) self-attention over groups of S rows: qkv [G*S][3*W] bf16 (q | k | v, head h
 // at columns h*64), ctx [G*S][W] bf16.  Used for the ViT frames (S = N) and for the image
 // prefix of the decoder (S = F*N).
@@ -442,7 +508,7 @@ hipError_t launch_cross_mean(const float* probs, int L, int rows, int T, int H, 
 hipError_t launch_student_embed(const int64_t* ids, int ld_ids, int rows, int T, int t0, const float* embed,
                                 const float* pe, int D, int vocab, float* xf, bf16_t* xb, hipStream_t s);
 
-// ---- row ops -----------------------------------------------------------------------------
+// ---- row ops (rowops.hip) -----------------------------------------------------------------------------
 struct LnArgs {
     const float* x; int ldx;      // [rows][ldx]
     const float* gamma; const float* beta; float eps;
@@ -489,45 +555,12 @@ hipError_t launch_dequant_fp8(const unsigned char* w8, const float* scale, bf16_
 // up to four such matrices in ONE launch (the weights of a transformer layer); n16[i] = rows_i * K_i / 16
 struct DequantBatch { const unsigned char* w8[4]; const float* scale[4]; bf16_t* out[4]; int K[4]; int64_t n16[4]; int n; };
 hipError_t launch_dequant_fp8_batch(const DequantBatch& b, hipStream_t s);
-// text embedding + LN: row m=(r, j) -> token ids[r*ld_ids + j], position t0 + j
-hipError_t launch_embed_text(const int64_t* ids, int ld_ids, int rows, int T, int t0,
-                             const float* word, const float* pos, const float* gamma, const float* beta,
-                             float eps, int D, int vocab, float* x_f32, bf16_t* x_bf16, hipStream_t s);
-hipError_t launch_finish_steps(const int32_t* sep_cnt, int rows, int max_len, int stop, int32_t* steps_out, hipStream_t s);
-hipError_t launch_fill_i64(int64_t* p, int ld, int rows, int64_t v, hipStream_t s);
-// p[r][0 .. lengths[r] - 1] = prompt.ids[r][the same], r < rows (ld >= prompt.max_len): the start of a prompted greedy loop
-hipError_t launch_fill_prompt(int64_t* p, int ld, int rows, const PromptArgs& prompt, hipStream_t s);
+// fragment-major copy of a GEMM weight [rows16][K] (bf16: elem_bytes 2, e4m3 codes: 1) for the weight-streaming text kernels
+hipError_t launch_pack_frags(const void* src, void* dst, int rows16, int K, int elem_bytes, hipStream_t s);
 hipError_t launch_gather_txt_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_rows, int rows,
                                   int t_len, int Tmax, int width, int layers, size_t layer_stride, hipStream_t s);
-// The candidates of one search step, what launch_beam_topk (the K best) and launch_sample_rows (draws) have in common: B * beams rows
-// of logits [.][ld] (V columns) ranked under log_softmax + beam_scores; candidate slots out_scores / out_idx [B][K] (K = beams * pn
-// for draws).
-struct CandArgs {
-    const float* logits; int ld;
-    const float* beam_scores;
-    // rp != 1.0f: the same ranking under a repetition penalty (model.py:522-531): every logit whose column occurs in the row's prefix
-    // prefix_ids[row * ld_ids + 0 .. cur_len - 1] (int64; ids outside [0, V) are ignored) becomes x < 0 ? x * rp : x / rp, once however
-    // often the token occurs, and the log-softmax is that of the penalised row.  rp == 1.0f: the prefix is neither checked nor read.
-    const int64_t* prefix_ids; int ld_ids, cur_len; float rp;
-    int B, beams, V;
-    float* out_scores; int* out_idx;
-    // bn (nullable): row b * beams + j of the mask bans columns of that beam row before the penalty, the chunk statistics and the
-    // chunk's top K (the BAN forms of the chunk kernel, combinable with the penalty): the log-softmax is that of the banned row;
-    // draws: banned columns are -inf before the penalty, the temperature and the filter -- the BAN form of the kernel.
-    const HeadBan* bn;
-};
-// top-K over (beam, vocab) of log_softmax(logits) + beam_scores per batch element: sorted descending, ties by smaller flat index
-// j*V + v.  Logits of -inf are no candidates; where a clip has fewer than K candidates the remaining slots hold the sentinel
-// (score -inf, index 0x7fffffff) -- launch_beam_step divides the index by V and must never be handed one.
-size_t beam_topk_scratch_bytes(int B, int beams, int V, int K);   // device scratch launch_beam_topk needs (V <= 131072)
-hipError_t launch_beam_topk(const CandArgs& c, int K, void* scratch, hipStream_t s);
-// the sampling branch of the search (model.py:532-554) for B * beams rows: penalty, temperature, top-k / top-p filter
-// (min_tokens_to_keep = 2), pn draws without replacement per row from a counter-based Philox stream (seed, row, cur_len, column);
-// candidate p = j * pn + d of clip b = draw d of row b * beams + j, flat index (p % beams) * V + word, unsorted (rowops.hip).
-// opt = the call's SampleOpt (host_logic.h; `on` is not read).
-// kept_out (int [B*beams]) / logz_out (fp32 [B*beams]): columns the filter kept / log-sum-exp of the filtered row; nullable.
-struct SampleStats { int* kept_out; float* logz_out; };
-hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& opt, const SampleStats& st, hipStream_t s);
+
+// ---- preprocessing (preproc.hip) -----------------------------------------------------------------------------------------------
 // uint8 HWC BGR frames [nf][H][W][3] -> CLIP-normalised fp32 NCHW [nf][3][crop][crop] (bicubic resize + centre crop)
 hipError_t launch_preprocess(const unsigned char* in, float* out, int nf, int H, int W, int crop, hipStream_t s);
 // the same transform fused with the patch gather: -> bf16 patch rows [nf*G*G][Kp] (layout of launch_im2col)
@@ -535,30 +568,3 @@ hipError_t launch_preprocess_patches(const unsigned char* in, bf16_t* patches, i
 // the same transform fused with the gather of a 3x3 stride-2 pad-1 convolution over the cropped frame (TinyViT's first stem conv):
 // -> bf16 im2col rows [nf*(crop/2)^2][32], k = ci*9 + ky*3 + kx, every column written (zero at outside taps and k >= 27); crop even
 hipError_t launch_preprocess_stem(const unsigned char* in, bf16_t* col, int nf, int H, int W, int crop, hipStream_t s);
-// device-resident beam search state + one bookkeeping step per decoder step (rowops.hip)
-struct BeamBuffers {
-    int64_t *ids0, *ids1, *words, *hyp_ids;
-    float *beam_scores, *hyp_score;
-    int32_t *src_rows, *done, *hyp_len;
-};
-// n finished hypotheses per clip (1 <= n <= 16): hyp_ids [B][n][max_len], hyp_score / hyp_len [B][n], stored in storage order in
-// slots 0 .. cnt - 1, hyp_len 0 behind them (launch_beam_init zeroes all B * n).  step: n = 1 runs beam_step_kernel, n > 1 the n-slot kernel.
-// finish: decoded [B][n][max_len] / logprobs [B][n] by descending score; first_*: rank 0 again as [B][max_len] / [B]; all nullable.
-hipError_t launch_beam_init(const BeamBuffers& bb, int B, int beams, int n, int max_len, int cls, hipStream_t s);
-struct BeamStepArgs {
-    int n;                                      // hypothesis slots per clip
-    const float* cand_scores; const int* cand_idx;   // [B][K]: launch_beam_topk's or launch_sample_rows'
-    int B, beams, K, V;
-    int cur_len, max_len, eos; float length_penalty;
-    int cur;                                    // which of ids0 / ids1 holds the current prefixes
-    // sampled: the candidates are draws (launch_sample_rows), in no order: is_done takes the maximum of the K scores, the candidates
-    // are walked as given, and a clip left with 0 < kept < beams live beams pads only the missing ones with (0, eos, row 0); any n >= 1.
-    bool sampled;
-    // prompt (nullable; rows = clips): a clip with cur_len < lengths[b] is forced -- every beam keeps its prefix and appends
-    // ids[b][cur_len], src_rows is the identity, beam_scores / done / the hypothesis slots are untouched, the candidates are not
-    // read; with cur_len >= max_len (the prompt's) the launch is the one without a prompt.
-    const PromptArgs* prompt;
-};
-hipError_t launch_beam_step(const BeamBuffers& bb, const BeamStepArgs& a, hipStream_t s);
-struct BeamFinishOut { int64_t* decoded; float* logprobs; int64_t* first_decoded; float* first_logprobs; };
-hipError_t launch_beam_finish(const BeamBuffers& bb, int n, int B, int max_len, int eos, const BeamFinishOut& o, hipStream_t s);

@@ -1,5 +1,5 @@
 // The merge of the vocabulary head's three per-tile partials into a row's log-sum-exp, shared by the selection kernels
-// (rowops.hip: argmax_final, draft_accept, score_final, distill_final) and the top-k alternatives of a row (skinny.hip:
+// (select.hip: argmax_final, draft_accept, score_final, distill_final) and the top-k alternatives of a row (skinny.hip:
 // head_topk_kernel): the one statement of the add order, so that every kernel that reports a log-probability of a row reports
 // the same bits.
 #pragma once

@@ -1,4 +1,4 @@
-// Row LayerNorm of the text rows, shared by the stand-alone row kernels (rowops.hip) and by the q|k|v projection that
+// Row LayerNorm of the text rows, shared by the stand-alone row kernels (select.hip) and by the q|k|v projection that
 // computes its own input rows when there are only one or two of them (skinny.hip, "row prologue"): ONE wave per row, lane
 // holds NV float4 at columns 256 i + 4 lane, two-pass (mean, then centred variance) in registers, fp32 throughout.
 // The same inline code wherever a row is normalised, and every multiply-add spelled out (contraction off), so the result does

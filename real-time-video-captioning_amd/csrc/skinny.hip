@@ -16,7 +16,7 @@
 //   skinny_rows3 : the row-prologue form over the fused FFN's 48 slabs: three waves share the slab reduce (round 4).
 //   skinny_splitk: K split over blocks (more waves in flight for the K=3072 matrix and for the
 //                  N=768 ones that would otherwise use 48 waves); each wave writes its fp32
-//                  partial tile to a slab; ln_reduce_kernel (rowops.hip) sums the slabs in a fixed
+//                  partial tile to a slab; ln_reduce_kernel (select.hip) sums the slabs in a fixed
 //                  order, adds bias + residual and applies LayerNorm.  No atomics: results are
 //                  bitwise reproducible and independent of the batch size.
 //
@@ -117,7 +117,7 @@ __device__ __forceinline__ void logits_epilogue(const SkinnyArgs& a, const float
         }
         // third partial (token log-probabilities attached): sum of exp(logit - tile max) over the tile's valid columns, the lane's
         // own columns in ascending order, then the four column groups by the butterfly above; 0 for a tile with no logit above -inf
-        // (never -inf - -inf).  argmax_final / draft_accept (rowops.hip) merge the tiles in a fixed order.
+        // (never -inf - -inf).  argmax_final / draft_accept (select.hip) merge the tiles in a fixed order.
         if (LSE) {
             float se = 0.f;
             if (best != -INFINITY) {
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void skinny_head_ban_kernel(SkinnyArgs a, cons
 //     cross = sum exp(t - t_max) ((t - t_max) - (s - s_max))   over the columns with t > -inf; the exp is the very value summed
 //                                                    into t_sum.  +inf outright where such a column has s = -inf (never 0 * inf,
 //                                                    never -inf - -inf); 0 for a tile whose t_max is -inf.
-// launch_distill_final (rowops.hip) re-centres with the tile maxima and merges in a fixed order.
+// launch_distill_final (select.hip) re-centres with the tile maxima and merges in a fixed order.
 // LDS: 2 x 16 x ((KT + KS) * 64 + 32) bytes = 87 040 at 768 + 576, 103 424 at 1024 + 576, 13 312 at 128 + 64: one workgroup per CU
 // at the model sizes (160 KiB per CU), i.e. one wave per SIMD with the whole 512-register file to itself -- the fragments of both
 // weights (168 / 200 registers) stay resident across the m-tiles without scratch.  The launch streams both weights once (82 MB

@@ -45,18 +45,6 @@ __global__ __launch_bounds__(64) void student_embed_kernel(const int64_t* __rest
     }
 }
 
-// draft of gitcap_student_*_greedy_draft -> the handle's id rows: column 0 = CLS whatever the draft holds, columns 1..n the draft's
-// tokens, an id outside [0, vocab) as -1: the embedding clamps it to a table row, it equals no PAD key and no arg-max, so it can
-// only be rejected (draft_accept_kernel)
-__global__ void student_draft_stage_kernel(const int64_t* __restrict__ draft, int ld_draft, int n, int rows, int vocab, int64_t cls,
-                                           int64_t* __restrict__ ids, int ld) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * (n + 1)) return;
-    const int r = i / (n + 1), c = i % (n + 1);
-    const int64_t d = draft[(size_t)r * ld_draft + c];
-    ids[(size_t)r * ld + c] = c == 0 ? cls : (d >= 0 && d < vocab ? d : -1);
-}
-
 // one wave per (query, head); lane i owns key i for the scores and output column(s) lane, lane + 64 for P.V
 // VL (clips of different length, gitcap_student_attach_frame_counts): the keys of decoder row r are the key_len[r] (1..64) packed
 // memory rows from key_off[r] on -- device tables read at run time, so a captured loop follows the counts of the memory set last --
@@ -875,10 +863,10 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
         if (rc) return rc;
     }
     // 1. verify: one pass over positions 0 .. n-1 of the staged draft (K/V rows of those positions -> the cache), then the
-    //    vocabulary head over all B * n rows, arg-max partials only
-    hipLaunchKernelGGL(student_draft_stage_kernel, dim3((B * (n + 1) + 255) / 256), dim3(256), 0, s, draft, ld_draft, n, B, h->V,
-                       (int64_t)h->c.cls_token_id, h->g_ids, ld);
-    HIP_OK(h, hipGetLastError());
+    //    vocabulary head over all B * n rows, arg-max partials only.  Staging (select.hip: draft_stage_kernel) leaves an id outside
+    //    [0, vocab) as -1: the embedding clamps it to a table row, it equals no PAD key and no arg-max, so it can only be rejected.
+    //    greedy_entry has checked what the launcher checks: 1 <= n <= max_len (ld = max_len + 1), ld_draft >= n + 1, 1 <= B <= max_rows.
+    HIP_OK(h, launch_draft_stage(draft, ld_draft, n, B, h->V, (int64_t)h->c.cls_token_id, h->g_ids, ld, s));
     HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, s));
     TextReq q;
     q.ids = h->g_ids; q.ld_ids = ld; q.rows = B; q.T = n;
@@ -1013,7 +1001,6 @@ int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s, bool
 // it.  The pending log-probability attachment is taken before the checks: a refused call has consumed it.
 // Attached frame counts are taken with them: the calls with `memory` follow them, the window calls refuse them.  partial: the window
 // need not be full (window_memory); *frames_out (host, nullable) = the tokens the caption saw.
-struct Draft { const int64_t* ids; int ld, n; int32_t* accepted_out; };
 int greedy_entry(gitcap_student* h, const char* who, bool window, const float* memory, int B, const Draft* draft, int max_len, int stop,
                  int64_t* ids_out, int32_t* steps_out, void* stream, bool partial = false, int32_t* frames_out = nullptr) {
     const std::string w(who);

@@ -1,5 +1,5 @@
 """Plain numpy restatement, in fp64, of the teacher-student divergence pass (include/gitcap.h: gitcap_distill; csrc/skinny.hip:
-skinny_head_dual_kernel, csrc/rowops.hip: distill_final_kernel / distill_rows_kernel), built on tests/logprob_reference.py.
+skinny_head_dual_kernel, csrc/select.hip: distill_final_kernel / distill_rows_kernel), built on tests/logprob_reference.py.
 
 With t = teacher logit / temperature and s = student logit / temperature, per 16-column tile of a row:
     t_max, t_idx, t_sum and s_max, s_idx, s_sum     logprob_reference.tile_partials of each model

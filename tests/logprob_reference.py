@@ -1,5 +1,5 @@
 """Plain numpy restatement, in fp64, of how the greedy loops get the log-probability of the token they emit without a logits
-tensor (csrc/skinny.hip: logits_epilogue, csrc/rowops.hip: lp_partials):
+tensor (csrc/skinny.hip: logits_epilogue, csrc/lp_partials.h: lp_partials):
 
   the vocabulary head leaves three partials per 16-column tile of a row: the largest logit, the first column that holds it, and
   the sum of exp(logit - that maximum) over the tile's columns (0 for a tile with no logit above -inf);

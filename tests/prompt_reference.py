@@ -1,5 +1,5 @@
 """Restatement of prompted decoding (include/gitcap.h: gitcap_attach_prompt) in numpy / plain Python, written from the contracts of
-the forced forms of argmax_final_kernel and of the beam-step kernels (csrc/kernels.h, csrc/rowops.hip), for tests/test_prompt.py
+the forced forms of argmax_final_kernel and of the beam-step kernels (csrc/kernels.h, csrc/select.hip, csrc/search.hip), for tests/test_prompt.py
 and tests/test_prompt_gpu.py.  The free case of a selection is tests/selection_reference.py's.
 
 `fault=` builds the subtly wrong kernels tests/test_prompt.py must see caught by the inputs the GPU tests use:

@@ -177,7 +177,7 @@ def multinomial_from_philox(seed, cur_len=1):
 # ---- the bookkeeping for UNSORTED candidates (oracle/search_oracle.py:124-146), on the device's state, fp32 scores ----------------
 
 class Book:
-    """The beam state the device keeps (csrc/rowops.hip: BeamState) and one sampled step / the finish on it."""
+    """The beam state the device keeps (csrc/search.hip: BeamState) and one sampled step / the finish on it."""
 
     def __init__(self, B, beams, n, L, cls, eos, lp):
         self.B, self.beams, self.n, self.L, self.eos, self.lp = B, beams, n, L, eos, np.float32(lp)

@@ -1,5 +1,5 @@
 """Plain numpy restatement, in fp64, of how given captions are scored without a logits tensor (include/gitcap.h: gitcap_score;
-csrc/skinny.hip: logits_epilogue<true, true>, csrc/rowops.hip: score_final_kernel / score_rows_kernel), built on
+csrc/skinny.hip: logits_epilogue<true, true>, csrc/select.hip: score_final_kernel / score_rows_kernel), built on
 tests/logprob_reference.py:
 
   the scoring head leaves the three per-tile partials of every (row, position) and the one logit of the position's given next

@@ -1,5 +1,5 @@
 """Restatement of the token-selection kernels in numpy fp64 / plain Python, written from their contracts (csrc/kernels.h,
-the comments above the kernels in csrc/rowops.hip and csrc/skinny.hip), for tests/test_selection.py and
+the comments above the kernels in csrc/select.hip, csrc/search.hip and csrc/skinny.hip), for tests/test_selection.py and
 tests/test_selection_gpu.py.
 
 The rule everywhere: the largest value wins, the smallest index among equals.  Inputs must be free of NaN."""

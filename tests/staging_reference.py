@@ -1,5 +1,5 @@
-"""Plain fp64 / numpy statements of the teacher's staging and layout kernels (csrc/preproc.hip and the plain row kernels at the top
-of csrc/rowops.hip), and the inputs of tests/test_staging_gpu.py (kept honest on the CPU by tests/test_staging.py).
+"""Plain fp64 / numpy statements of the teacher's staging and layout kernels (csrc/preproc.hip, the plain row kernels of
+csrc/rowops.hip and the text embedding of csrc/select.hip), and the inputs of tests/test_staging_gpu.py (kept honest on the CPU by tests/test_staging.py).
 
 Nothing here imports the oracle or the library.  Number formats, LayerNorm and its bound come from text_rows_reference.
 

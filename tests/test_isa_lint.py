@@ -43,7 +43,7 @@ elif _state == "other":
 SCRATCH_ALLOWED = {"gemm256_kernelILi6ELb1E": 80, "gemm256_kernelILi7ELb1E": 32,
                    "gemm256f8_kernelILi6E": 40, "gemm256f8_kernelILi7E": 32}
 FILES = ["attention.hip", "ffn_txt.hip", "gemm.hip", "gemm256.hip", "preproc.hip", "rowops.hip",
-         "skinny.hip", "student.hip", "txtblock.hip"]
+         "search.hip", "select.hip", "skinny.hip", "student.hip", "txtblock.hip"]
 
 
 @pytest.fixture(scope="module")

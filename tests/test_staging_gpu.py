@@ -1,4 +1,5 @@
-"""The teacher's staging and layout kernels (csrc/preproc.hip, the plain row kernels at the top of csrc/rowops.hip), each through its
+"""The teacher's staging and layout kernels (csrc/preproc.hip, the plain row kernels of csrc/rowops.hip, the text embedding of
+csrc/select.hip), each through its
 handle-free gitcap_dbg_* hook on poisoned buffers, against tests/staging_reference.py: the fp32 frame transform under a counted
 bound, the text embedding under ln_bound, everything else bit for bit.  Every launch is a few KB to a few MB."""
 import ctypes

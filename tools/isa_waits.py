@@ -16,10 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "real-time-video-captioning_amd", "csrc")
 
 
-def product_flags():
+def product_flags(csrc=CSRC):
     """The compile flags of the product build, read from csrc/Makefile (CXXFLAGS with $(ARCH) / $(EXTRA) resolved to their defaults),
     so that what is linted is what is shipped."""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
+    mk = open(os.path.join(csrc, "Makefile")).read()
     var = lambda n: re.search(r"^%s[ \t]*\??=[ \t]*(.*)$" % n, mk, re.M).group(1).strip()
     flags = var("CXXFLAGS").replace("$(ARCH)", var("ARCH")).replace("$(EXTRA)", var("EXTRA"))
     return [f for f in flags.split() if f not in ("-fPIC", "-Wall", "-Wno-unused-function")]
@@ -32,15 +32,20 @@ def hipcc_version():
     return "%s.%s" % (m.group(1), m.group(2)) if m else "unknown"
 
 
-def kernel_listings(src, pat, extra_flags=()):
-    """[(mangled name, NumVgprs, ScratchSize in bytes, tokens)] of every kernel of `src` whose mangled name contains `pat`."""
-    src = src if os.path.exists(src) else os.path.join(CSRC, src)
+def device_asm(src, extra_flags=(), csrc=CSRC):
+    """The lines of the device assembly of `src` (a path, or a file of `csrc`) under the product flags of `csrc`."""
+    src = src if os.path.exists(src) else os.path.join(csrc, src)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        cmd = ["/opt/rocm/bin/hipcc"] + product_flags() + list(extra_flags) + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, "-S",
-                                                                             "--cuda-device-only", "-o", out, src]
+        cmd = ["/opt/rocm/bin/hipcc"] + product_flags(csrc) + list(extra_flags) + ["-I", os.path.join(csrc, "..", "..", "include"), "-I", csrc,
+                                                                                 "-S", "--cuda-device-only", "-o", out, src]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-        text = open(out).read().splitlines()
+        return open(out).read().splitlines()
+
+
+def kernel_listings(src, pat, extra_flags=()):
+    """[(mangled name, NumVgprs, ScratchSize in bytes, tokens)] of every kernel of `src` whose mangled name contains `pat`."""
+    text = device_asm(src, extra_flags)
     names = [l.split(":")[0] for l in text if re.match(r"^_Z\w+:", l)]
     res = []
     for name in [n for n in names if pat in n]:
