@@ -1215,6 +1215,53 @@ int gitcap_student_attach_frame_counts(gitcap_student_t* h, const int32_t* count
 int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* frames_out,
                                          void* stream);
 
+/* Stream pool: the memory-token window for several cameras on one handle.  The window above is ONE ring cursor: its clips advance
+ * in lockstep.  Cameras that start at different times, behind gates that admit different frames, are each at their own fill level
+ * and ring position; the pool keeps S independent windows (streams), takes tokens for any of them in any mix, and captions any
+ * subset of them as one ragged batch.  A token's K | V rows are computed once, at the push (the GEMM of gitcap_student_window_push
+ * over the n packed rows: a K | V row has the same bits whichever launch computed it, at every number of rows); a pool call copies
+ * each named stream's rows, oldest first, PACKED, to where gitcap_student_set_memory would have written them for clips of those
+ * lengths, writes the key tables of gitcap_student_attach_frame_counts and runs the token loop of the full call (its captured
+ * graphs, which read the tables at replay).  No host decision lies between the copy and the token loop.
+ * Contract: row r of gitcap_student_pool_greedy is bit for bit row r of gitcap_student_greedy with the streams' token counts attached
+ * (gitcap_student_attach_frame_counts) on the streams' current tokens, oldest first -- ids, log-probabilities and alternatives --
+ * and, as there, what the row would be alone.  When every named stream holds mem_tokens tokens the layout is the dense one and the
+ * call takes the dense launches, as gitcap_student_window_greedy on a full window does.
+ *   reset   n_streams = S, 1 <= S <= 4096: allocates (or, for the S of the last reset, reuses) the ring, bf16
+ *           [num_layers][S][mem_tokens][2 d_model], the staging of one push (max_rows * mem_tokens rows: the tokens cast to bf16, their
+ *           K | V rows of every layer, the slot table) and the table of one call; empties every stream.  S = 0 releases all of it;
+ *           so do gitcap_student_finalize (the rows came from the weights it replaces) and destroy.  A set-up step: a change of S
+ *           waits for the device.  A handle that never resets a pool allocates nothing and runs exactly the launches it ran before.
+ *           The pool is state of its own: gitcap_student_window_reset / _push / _greedy* neither read nor change it, nor the pool
+ *           calls the window.
+ *   push    memory: device fp32 [n][d_model], n tokens; stream_ids: HOST int32 [n], token i goes to stream stream_ids[i] behind
+ *           that stream's earlier tokens, this push's earlier ones included.  1 <= n <= max_rows * mem_tokens (the staging), and a
+ *           stream gets at most mem_tokens tokens in one push (more would write one ring slot twice in one launch: push twice).
+ *           The ids are checked on the host before anything is enqueued; a refused push changes nothing.  Work: one cast, one
+ *           K | V GEMM per layer over the n rows, one scatter launch for all layers.  Like a window push it writes neither the
+ *           decoder's memory nor the self-attention cache.
+ *   greedy  stream_ids: HOST int32 [B], 1 <= B <= max_rows, distinct; decoder row r is stream stream_ids[r], in the caller's order,
+ *           and sees its last n_r = min(tokens pushed, mem_tokens) tokens.  frames_out (host int32 [B], nullable) = n_r.  The other
+ *           arguments, the stop rule and the ids_out / steps_out layout as gitcap_student_greedy.  Takes the attachments of
+ *           gitcap_student_attach_token_logprobs and gitcap_student_attach_top_logprobs as gitcap_student_window_greedy does;
+ *           attached frame counts are refused (and consumed) with the window calls' message.  Leaves the handle as
+ *           gitcap_student_greedy with those counts would.  There is no draft and no beam form of the pool call.
+ *   drop    empties one stream (a camera that reconnected); the others are untouched.
+ *   counts  host int32 [S]: the tokens each stream holds, 0 .. mem_tokens.
+ * Pushes and pool calls may be issued on different streams: two events of the pool's own order a push behind the last pool call's
+ * copy and the last push, and a pool call behind the last push.  The two page-locked tables are reused behind an event each.
+ * Errors: GITCAP_ERR_ARG for a null handle or pointer, n_streams outside [0, 4096], n outside [1, max_rows * mem_tokens], a stream
+ * id outside [0, S), more than mem_tokens tokens for one stream in one push, B outside [1, max_rows], a stream named twice in a call,
+ * attached frame counts, and the length / stop-rule / attachment checks of gitcap_student_greedy; GITCAP_ERR_STATE for a call
+ * before any reset (or after the pool was released), a named stream that holds no token (nothing is launched), and weights not
+ * finalized.  gitcap_abi_version is unchanged: these are new symbols only. */
+int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams);
+int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int32_t* stream_ids, int n, void* stream);
+int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out,
+                               int32_t* steps_out, int32_t* frames_out, void* stream);
+int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id);
+int gitcap_student_pool_counts(const gitcap_student_t* h, int32_t* counts_out);
+
 /* Teacher-student divergence of given captions, forward only: KL(teacher || student) of every position's next-token distribution
  * at a temperature -- LOSS 2 of DistillationTrainer.training_step (src/models/model.py:919-935: KLDivLoss('batchmean') of
  * log_softmax(student / t) against softmax(teacher / t)) -- without either model's [rows * T][V] logits: both vocabulary heads run

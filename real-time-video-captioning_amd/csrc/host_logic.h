@@ -1,6 +1,7 @@
 // Host-only logic of libgitcap, free of any HIP dependency so that it also compiles for the CPU under
 // -fsanitize=address,undefined (`make asan`, tests/test_host_asan.py): numeric encodings of the weight loader, the
-// canonical tensor table, the pipeline's ticket -> slot bookkeeping, the window rings' cursor and the workgroup -> tile map of the residual +
+// canonical tensor table, the pipeline's ticket -> slot bookkeeping, the window rings' cursor, the stream pool's slot plan
+// (`make asan-pool`, host_pool_asan_test.cpp) and the workgroup -> tile map of the residual +
 // LayerNorm GEMM (shared with the kernel, which compiles the same function for the device).
 #pragma once
 #include <cmath>
@@ -164,7 +165,32 @@ struct RingCursor {
     void push(int n) { head = (head + n) % slots; count = count + n < slots ? count + n : slots; }
     bool full() const { return slots > 0 && count >= slots; }
     void clear() { count = 0; }     // the entries may be undefined (a failed push, a failed exchange): pushed again by the caller
+    int oldest() const { return (head + slots - count) % slots; }      // slot of the oldest entry held (count <= slots; 1 <= count)
 };
+
+// Stream pool (gitcap_student_pool_*): S independent rings in one buffer, one RingCursor per stream; ring row = stream * slots + slot.
+// One push holds tokens for any streams in any mix: token i goes to stream ids[i] behind that stream's earlier tokens, this
+// push's earlier ones included.  pool_push_slots writes slot[i] = the ring row of token i and changes nothing; a stream may get at
+// most `slots` tokens per push (more would write one row twice in one launch).  *bad = the first token refused.
+enum { POOL_PUSH_OK = 0, POOL_PUSH_BAD_ID = 1, POOL_PUSH_OVER = 2 };
+inline int pool_push_slots(const std::vector<RingCursor>& cur, const int32_t* ids, int n, int32_t* slot, int* bad) {
+    std::vector<int> seen(cur.size(), 0);
+    for (int i = 0; i < n; ++i) {
+        const int32_t id = ids[i];
+        *bad = i;
+        if (id < 0 || (size_t)id >= cur.size()) return POOL_PUSH_BAD_ID;
+        const RingCursor& c = cur[(size_t)id];
+        const int j = seen[(size_t)id]++;
+        if (j >= c.slots) return POOL_PUSH_OVER;
+        slot[i] = id * c.slots + (c.head + j) % c.slots;
+    }
+    *bad = -1;
+    return POOL_PUSH_OK;
+}
+// the cursors behind a push that pool_push_slots accepted
+inline void pool_push_commit(std::vector<RingCursor>& cur, const int32_t* ids, int n) {
+    for (int i = 0; i < n; ++i) cur[(size_t)ids[i]].push(1);
+}
 
 // ---- per-call options: the one-shot attachments of gitcap_attach_* --------------------------------------------------------
 // Each setter writes its part of the handle's `pending` record; an entry point states which parts it takes and which it refuses,

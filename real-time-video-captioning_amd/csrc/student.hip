@@ -263,6 +263,29 @@ __global__ __launch_bounds__(64) void student_window_gather_kernel(const bf16_t*
     for (int i = threadIdx.x; i < n8; i += 64) dst[i] = src[i];
 }
 
+// ---- stream pool (gitcap_student_pool_*) ------------------------------------------------------------------------------------
+// push: the packed K|V rows of one push, kv [L][cap][2D], -> the pool ring [L][S * F][2D]: row i of every layer goes to ring row
+// slot[i] (a table the host validated: stream * F + slot, no row twice).  blockIdx.x = i, blockIdx.y = layer; 16-byte pieces.
+__global__ __launch_bounds__(64) void student_pool_scatter_kernel(const bf16_t* __restrict__ kv, bf16_t* __restrict__ ring,
+                                                                  const int32_t* __restrict__ slot, int n8, size_t kv_layer, size_t ring_layer) {
+    const int i = blockIdx.x, l = blockIdx.y;
+    const uint4* src = (const uint4*)(kv + l * kv_layer) + (size_t)i * n8;
+    uint4* dst = (uint4*)(ring + l * ring_layer) + (size_t)slot[i] * n8;
+    for (int t = threadIdx.x; t < n8; t += 64) dst[t] = src[t];
+}
+// pool call: decoder row r's tokens, oldest first, -> memkv PACKED (row r starts where row r - 1 ended).  tab [rows][4] = {the
+// stream's first ring row, its oldest slot, the tokens it holds n_r, the first memkv row of r}.  blockIdx.x = (r, f), blockIdx.y =
+// layer; a block with f >= n_r has nothing to copy.
+__global__ __launch_bounds__(64) void student_pool_gather_kernel(const bf16_t* __restrict__ ring, bf16_t* __restrict__ memkv,
+                                                                 const int32_t* __restrict__ tab, int F, int n8, size_t ring_layer, size_t mem_layer) {
+    const int r = blockIdx.x / F, f = blockIdx.x % F, l = blockIdx.y;
+    const int4 t = ((const int4*)tab)[r];
+    if (f >= t.z) return;
+    const uint4* src = (const uint4*)(ring + l * ring_layer) + ((size_t)t.x + (t.y + f) % F) * n8;
+    uint4* dst = (uint4*)(memkv + l * mem_layer) + ((size_t)t.w + f) * n8;
+    for (int i = threadIdx.x; i < n8; i += 64) dst[i] = src[i];
+}
+
 struct gitcap_student : HandleCore {
     gitcap_student_config c;
     std::map<std::string, DevTensor> w;
@@ -328,6 +351,19 @@ struct gitcap_student : HandleCore {
     int win_B = 0;
     RingCursor win;
     RingOrder win_order;
+    // stream pool (gitcap_student_pool_*), allocated by pool_reset and state of its own beside the window: pool_ring = the K|V rows
+    // of pool_S independent streams, bf16 [L][pool_S][F slots][2D]; pool (one RingCursor per stream) = where a stream's next token
+    // goes and how many it holds.  One push: pool_stage = its tokens cast, packed [pool_cap][D]; pool_kv = their K|V rows, packed
+    // [L][pool_cap][2D]; pool_slot = the ring row of each (device [pool_cap], filled from the page-locked pool_slot_host behind
+    // pool_slot_ev).  One pool call: pool_tab = {ring row base, oldest slot, tokens, first packed memkv row} per decoder row
+    // (device [R][4], from pool_tab_host behind pool_tab_ev).  pool_order: win_order's discipline for the pool's ring.
+    bf16_t *pool_ring = nullptr, *pool_stage = nullptr, *pool_kv = nullptr;
+    int32_t *pool_slot = nullptr, *pool_tab = nullptr, *pool_slot_host = nullptr, *pool_tab_host = nullptr;
+    hipEvent_t pool_slot_ev = nullptr, pool_tab_ev = nullptr;
+    int pool_S = 0, pool_cap = 0;
+    int64_t pool_bytes = 0;
+    std::vector<RingCursor> pool;
+    RingOrder pool_order;
     // resolved weights
     const float *embed = nullptr, *pe = nullptr, *head_b = nullptr;
     const bf16_t* head_w = nullptr;
@@ -341,6 +377,20 @@ void destroy_graphs(gitcap_student* h) {
     for (auto& g : h->graphs)
         for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
     h->graphs.clear();
+}
+
+// the stream pool's buffers (the caller has made sure nothing in flight uses them); the events of pool_order stay for the next reset
+void pool_free(gitcap_student* h) {
+    for (void* p : {(void*)h->pool_ring, (void*)h->pool_stage, (void*)h->pool_kv, (void*)h->pool_slot, (void*)h->pool_tab})
+        if (p) (void)hipFree(p);
+    if (h->pool_slot_host) (void)hipHostFree(h->pool_slot_host);
+    if (h->pool_tab_host) (void)hipHostFree(h->pool_tab_host);
+    h->pool_ring = h->pool_stage = h->pool_kv = nullptr;
+    h->pool_slot = h->pool_tab = h->pool_slot_host = h->pool_tab_host = nullptr;
+    h->ws_bytes -= h->pool_bytes;
+    h->pool_bytes = 0;
+    h->pool_S = h->pool_cap = 0;
+    h->pool.clear();
 }
 
 bool student_is_gemm_weight(const std::string& n) {
@@ -628,6 +678,10 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
     h->win_order.destroy();
+    pool_free(h);
+    if (h->pool_slot_ev) (void)hipEventDestroy(h->pool_slot_ev);
+    if (h->pool_tab_ev) (void)hipEventDestroy(h->pool_tab_ev);
+    h->pool_order.destroy();
     delete h;
 }
 
@@ -662,6 +716,10 @@ int gitcap_student_finalize(gitcap_student_t* h) {
     auto Fp = [&](const std::string& n) { return (const float*)h->w[n].p; };
     auto Wt = [&](const std::string& n) { return (const bf16_t*)h->w[n].p; };
     destroy_graphs(h);
+    if (h->pool_ring) {         // the pool's K|V rows came from the weights being replaced: the pool goes, as at pool_reset(0)
+        HIP_OK(h, hipDeviceSynchronize());
+        pool_free(h);
+    }
     h->embed = Fp("embed.weight"); h->pe = Fp("pos_enc.pe"); h->head_w = Wt("linear.weight"); h->head_b = Fp("linear.bias");
     h->layers.resize(h->L);
     for (int i = 0; i < h->L; ++i) {
@@ -1031,6 +1089,42 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
 }
 
+// ---- stream pool ---------------------------------------------------------------------------------------------------------------
+// The memory K|V of a pool call: decoder row r = stream ids[r] (checked by the caller: in range, distinct, not empty), its last
+// n_r = min(count, F) tokens oldest first, rows packed as set_memory packs clips of different length -- the layout and the key
+// tables of gitcap_student_attach_frame_counts, so the token loop is that call's.  Every n_r == F: the packed layout is the dense
+// one and the loop takes the dense launches, as a full lockstep window's.  frames (host, nullable) = n_r.
+int pool_memory(gitcap_student* h, const int32_t* ids, int B, hipStream_t s, int32_t* frames) {
+    const int D = h->D, F = h->F;
+    HIP_OK(h, hipEventSynchronize(h->pool_tab_ev));         // the previous call's transfer has read the page-locked table
+    bool dense = true;
+    int off = 0;
+    for (int r = 0; r < B; ++r) {
+        const RingCursor& c = h->pool[(size_t)ids[r]];
+        int32_t* t = h->pool_tab_host + 4 * r;
+        t[0] = ids[r] * F; t[1] = c.oldest(); t[2] = c.count; t[3] = off;
+        off += c.count;
+        dense = dense && c.count == F;
+    }
+    HIP_OK(h, h->pool_order.before_read(s));
+    h->have_memory = false;
+    HIP_OK(h, hipMemcpyAsync(h->pool_tab, h->pool_tab_host, (size_t)B * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipEventRecord(h->pool_tab_ev, s));
+    if (!dense)
+        if (int rc = write_key_tables(h, B, [&](int r) { return std::make_pair((int)h->pool_tab_host[4 * r + 3], (int)h->pool_tab_host[4 * r + 2]); }, s))
+            return rc;
+    h->ragged = !dense;
+    hipLaunchKernelGGL(student_pool_gather_kernel, dim3(B * F, h->L), dim3(64), 0, s, h->pool_ring, h->memkv, h->pool_tab, F, 2 * D / 8,
+                       (size_t)h->pool_S * F * 2 * D, (size_t)h->R * F * 2 * D);
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, h->pool_order.after_read(s));
+    if (frames)
+        for (int r = 0; r < B; ++r) frames[r] = h->pool_tab_host[4 * r + 2];
+    h->cur_B = B;
+    h->have_memory = true;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1257,6 +1351,144 @@ int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, i
     if (rc) return rc;
     if ((rc = window_memory(h, "student_window_beam_search", k, s))) return rc;
     return beam_loop(h, h->win_B, k, max_len, ids_out, s);
+}
+
+// ---- stream pool ---------------------------------------------------------------------------------------------------------------
+int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_reset: null handle");
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_pool_reset"));
+    if (n_streams < 0 || n_streams > 4096) return fail(h, GITCAP_ERR_ARG, "student_pool_reset: n_streams outside 0..4096");
+    if (n_streams && !h->finalized) return fail(h, GITCAP_ERR_STATE, "student_pool_reset: weights not finalized");
+    GUARD(h);
+    if (h->pool_ring && n_streams != h->pool_S) {
+        HIP_OK(h, hipDeviceSynchronize());          // pushes or pool calls in flight may still use the buffers
+        pool_free(h);
+    }
+    if (n_streams == 0) return 0;
+    if (!h->pool_ring) {
+        const size_t S = (size_t)n_streams, F = (size_t)h->F, D = (size_t)h->D, L = (size_t)h->L, cap = (size_t)h->R * F;
+        HIP_OK(h, h->pool_order.ensure());
+        if (!h->pool_slot_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_slot_ev, hipEventDisableTiming));
+        if (!h->pool_tab_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_tab_ev, hipEventDisableTiming));
+        const size_t b_ring = L * S * F * 2 * D * sizeof(bf16_t), b_stage = cap * D * sizeof(bf16_t), b_kv = L * cap * 2 * D * sizeof(bf16_t),
+                     b_slot = cap * sizeof(int32_t), b_tab = (size_t)h->R * 4 * sizeof(int32_t);
+        hipError_t e = hipMalloc((void**)&h->pool_ring, b_ring);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->pool_stage, b_stage);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->pool_kv, b_kv);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->pool_slot, b_slot);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->pool_tab, b_tab);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_slot_host, b_slot, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_tab_host, b_tab, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            pool_free(h);
+            return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc stream pool: ") + hipGetErrorString(e));
+        }
+        h->pool_bytes = (int64_t)(b_ring + b_stage + b_kv + b_slot + b_tab);
+        h->ws_bytes += h->pool_bytes;
+        h->pool_S = n_streams;
+        h->pool_cap = (int)cap;
+        h->pool.resize(S);
+    }
+    for (RingCursor& c : h->pool) c.reset(h->F);
+    return 0;
+}
+
+int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int32_t* stream_ids, int n, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_push: null handle");
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_pool_push"));
+    if (!memory || !stream_ids) return fail(h, GITCAP_ERR_ARG, "student_pool_push: null memory or stream_ids");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_pool_push: weights not finalized");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "student_pool_push: no pool (gitcap_student_pool_reset first)");
+    if (n < 1 || n > h->pool_cap)
+        return fail(h, GITCAP_ERR_ARG, "student_pool_push: n outside [1, max_rows * mem_tokens = " + std::to_string(h->pool_cap) + "]");
+    std::vector<int32_t> slots((size_t)n);
+    int bad = -1;
+    if (const int why = pool_push_slots(h->pool, stream_ids, n, slots.data(), &bad))
+        return fail(h, GITCAP_ERR_ARG, "student_pool_push: token " + std::to_string(bad) + (why == POOL_PUSH_BAD_ID
+                    ? " names stream " + std::to_string(stream_ids[bad]) + ", outside [0, " + std::to_string(h->pool_S) + ")"
+                    : " is more than mem_tokens = " + std::to_string(h->F) + " for stream " + std::to_string(stream_ids[bad]) + " in one push"));
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    const int D = h->D;
+    HIP_OK(h, hipEventSynchronize(h->pool_slot_ev));        // the previous push's transfer has read the page-locked table
+    memcpy(h->pool_slot_host, slots.data(), (size_t)n * sizeof(int32_t));
+    HIP_OK(h, h->pool_order.before_push(s));
+    // From here on ring rows may be half written: a failure empties the streams this push names.
+    auto enqueue = [&]() -> int {
+        HIP_OK(h, hipMemcpyAsync(h->pool_slot, h->pool_slot_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_OK(h, hipEventRecord(h->pool_slot_ev, s));
+        HIP_OK(h, launch_cast_bf16(memory, h->pool_stage, (int64_t)n * D, s));         // the bf16 rows set_memory's GEMM reads
+        const size_t kv_layer = (size_t)h->pool_cap * 2 * D;
+        for (int l = 0; l < h->L; ++l) {
+            const StuLayer& Ly = h->layers[l];
+            // k | v of the n tokens: set_memory's GEMM.  skinny_full_kernel<K32, SK_BIAS_BF16, false, false> is what launch_skinny
+            // takes for this epilogue at every M (the head-sharing and row-prologue forms are for SK_BIAS_F32 and a pending
+            // LayerNorm), and in it output row m is one MFMA chain over X row m alone -- an m-tile's padding rows are clamped copies
+            // whose results are dropped -- so a row has the same bits at M = 1, 2, 17 or max_rows * mem_tokens.
+            if (int rc = sk_full(h, s, SK_BIAS_BF16, h->pool_stage, D, Ly.ca_in_w + (size_t)D * D, Ly.ca_in_b + D, n, 2 * D, D,
+                                 h->pool_kv + (size_t)l * kv_layer, 2 * D))
+                return rc;
+        }
+        hipLaunchKernelGGL(student_pool_scatter_kernel, dim3(n, h->L), dim3(64), 0, s, h->pool_kv, h->pool_ring, h->pool_slot, 2 * D / 8, kv_layer,
+                           (size_t)h->pool_S * h->F * 2 * D);
+        HIP_OK(h, hipGetLastError());
+        HIP_OK(h, h->pool_order.after_push(s));
+        return 0;
+    };
+    if (int rc = enqueue()) {
+        for (int i = 0; i < n; ++i) h->pool[(size_t)stream_ids[i]].reset(h->F);
+        return rc;
+    }
+    pool_push_commit(h->pool, stream_ids, n);
+    return 0;
+}
+
+int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out,
+                               int32_t* steps_out, int32_t* frames_out, void* stream) {
+    const char* who = "student_pool_greedy";
+    const std::string w(who);
+    if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
+    const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});           // consumed, whatever becomes of the call
+    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
+    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));
+    if (!stream_ids || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
+    if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
+    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
+    if (int bad = lp_check(h, who, lp, max_len)) return bad;
+    if (int bad = tk_check(h, who, tk, max_len)) return bad;
+    if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
+    for (int r = 0; r < B; ++r) {
+        if (stream_ids[r] < 0 || stream_ids[r] >= h->pool_S)
+            return fail(h, GITCAP_ERR_ARG, w + ": row " + std::to_string(r) + " names stream " + std::to_string(stream_ids[r]) + ", outside [0, " +
+                        std::to_string(h->pool_S) + ")");
+        for (int q = 0; q < r; ++q)
+            if (stream_ids[q] == stream_ids[r]) return fail(h, GITCAP_ERR_ARG, w + ": stream " + std::to_string(stream_ids[r]) + " is named twice");
+    }
+    for (int r = 0; r < B; ++r)
+        if (h->pool[(size_t)stream_ids[r]].count < 1)
+            return fail(h, GITCAP_ERR_STATE, w + ": stream " + std::to_string(stream_ids[r]) + " holds no token");
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = pool_memory(h, stream_ids, B, s, frames_out)) return rc;
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
+}
+
+int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_drop: null handle");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "student_pool_drop: no pool (gitcap_student_pool_reset first)");
+    if (stream_id < 0 || stream_id >= h->pool_S) return fail(h, GITCAP_ERR_ARG, "student_pool_drop: stream outside the pool");
+    h->pool[(size_t)stream_id].reset(h->F);         // (what is in flight was enqueued with the old cursor; pool_order orders the next push)
+    return 0;
+}
+
+int gitcap_student_pool_counts(const gitcap_student_t* h, int32_t* counts_out) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_counts: null handle");
+    if (!counts_out) return fail(h, GITCAP_ERR_ARG, "student_pool_counts: null counts_out");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "student_pool_counts: no pool (gitcap_student_pool_reset first)");
+    for (int i = 0; i < h->pool_S; ++i) counts_out[i] = h->pool[(size_t)i].count;
+    return 0;
 }
 
 }  // extern "C"

@@ -279,6 +279,11 @@ SYMBOLS = {
     # the student on clips of different length, and captions of a window that is not full yet (tests/test_student_ragged_*_gpu.py)
     "gitcap_student_attach_frame_counts": (c_int, [c_void_p, POINTER(c_int32), c_int]),
     "gitcap_student_window_greedy_partial": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "gitcap_student_pool_reset": (c_int, [c_void_p, c_int]),
+    "gitcap_student_pool_push": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_void_p]),
+    "gitcap_student_pool_greedy": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "gitcap_student_pool_drop": (c_int, [c_void_p, c_int]),
+    "gitcap_student_pool_counts": (c_int, [c_void_p, POINTER(c_int32)]),
     "gitcap_dbg_attn_small_varlen": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p, c_void_p, c_void_p]),
     "gitcap_dbg_cross_probs_varlen": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                               c_int, c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,153 @@
+"""``StudentStreamPool``: several live cameras on one StudentCaptioner (StudentCaptioner.stream_pool; include/gitcap.h:
+gitcap_student_pool_*).  Every camera (stream) has a window of ``mem_tokens`` frames of its own, at its own fill level and ring
+position; a push takes frames for any streams in any mix, encodes them once, packed, and the streams that are due are captioned
+as one ragged batch."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _lib
+from ._stream import STOP_ALL_SEP
+from .window import PoolSchedule
+
+
+def cut_at_sep(row, sep_id: int) -> int:
+    """Generated tokens of one caption row (CLS first) up to and including its own first SEP; all of them if it has none."""
+    hits = (row[1:] == sep_id).nonzero()
+    return int(hits[0]) + 1 if hits.numel() else row.shape[0] - 1
+
+
+class StudentStreamPool:
+    """``push(frames, streams)`` -> ``{stream: ids}`` for every stream that became due, ``caption(streams)`` for a caption now.  A
+    stream's caption is bit for bit ``greedy_decode`` on a list holding that stream's last (up to mem_tokens) frames, cut behind the
+    row's OWN first SEP when the stop rule is all_sep: it does not depend on which other streams were captioned with it.  After a
+    caption ``last_logprobs[stream]`` (logprobs=True), ``last_top_ids[stream]`` / ``last_top_logprobs[stream]`` (top_logprobs=k)
+    and ``last_frames[stream]`` (the frames it saw) hold that caption's, cut the same way.
+    Scene-change gates are not part of the pool: a caller puts one FrameGate per camera in front of ``push`` and pushes the frames
+    it admits; one launch for all the gates' decisions is left to a later change.  Nor does the pool carry drafts or run beams."""
+
+    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames):
+        self._m = model
+        self._sched = PoolSchedule(streams, model.cfg.mem_tokens, hop, min_frames)
+        self._max_len, self._mode = int(max_len), mode
+        self._want_lp, self._top_k = bool(logprobs), int(top_logprobs)
+        self.last_logprobs, self.last_top_ids, self.last_top_logprobs, self.last_frames = {}, {}, {}, {}
+        self._token = object()
+        model._pool_owner = self._token             # the handle has one pool: this object owns it until the next one is opened
+        self._reset_lib()
+
+    # ------------------------------------------------------------------ the library's side
+    def _check_live(self):
+        if self._m._pool_owner is not self._token:
+            raise _lib.GitcapError(f"this {type(self).__name__} was invalidated (another stream_pool() was opened, the model was moved or its weights were loaded again)")
+
+    def _reset_lib(self):
+        with torch.cuda.device(self._m._dev):
+            self._m._call("gitcap_student_pool_reset", self._sched.streams)
+
+    def _push_lib(self, mem, ids):
+        m = self._m
+        with torch.cuda.device(m._dev):
+            m._call("gitcap_student_pool_push", _lib.ptr(mem), (ctypes.c_int32 * len(ids))(*ids), len(ids), m._stream())
+
+    def _drop_lib(self, s):
+        self._m._call("gitcap_student_pool_drop", s)
+
+    def _counts_lib(self):
+        out = (ctypes.c_int32 * self._sched.streams)()
+        self._m._call("gitcap_student_pool_counts", out)
+        return list(out)
+
+    def _caption_lib(self, ids):
+        """One gitcap_student_pool_greedy on streams `ids` (at most max_batch) -> (ids [B, 1+max_len], log-probs or None, (top ids,
+        top log-probs) or None, frames seen per row), on the device."""
+        m, B, L = self._m, len(ids), self._max_len
+        out = torch.empty((B, L + 1), dtype=torch.int64, device=m._dev)
+        lp = torch.empty((B, L), dtype=torch.float32, device=m._dev) if self._want_lp else None
+        tk = None
+        if self._top_k:
+            tk = (torch.empty((B, L, self._top_k), dtype=torch.int64, device=m._dev),
+                  torch.empty((B, L, self._top_k), dtype=torch.float32, device=m._dev))
+        seen = (ctypes.c_int32 * B)()
+        with torch.cuda.device(m._dev):
+            m._attach_logprobs(lp, tk)
+            m._call("gitcap_student_pool_greedy", (ctypes.c_int32 * B)(*ids), B, L, self._mode, _lib.ptr(out), None, seen, m._stream())
+        return out, lp, tk, list(seen)
+
+    # ------------------------------------------------------------------ frames in, captions out
+    def _tokens(self, frames: torch.Tensor) -> torch.Tensor:
+        """uint8 [n,H,W,3] / fp32 [n,3,S,S] frames, or memory tokens [n,d_model] -> memory tokens [n,d_model] fp32 on the device."""
+        m = self._m
+        if frames.dtype != torch.uint8 and frames.dim() == 2:
+            if frames.shape[1] != m.cfg.d_model:
+                raise ValueError(f"expected memory tokens [n,{m.cfg.d_model}], got {tuple(frames.shape)}")
+            return frames.to(device=m._dev, dtype=torch.float32).contiguous()
+        if frames.dim() != 4:
+            raise ValueError(f"expected frames [n,H,W,3] uint8, [n,3,S,S] fp32 or tokens [n,d_model], got {tuple(frames.shape)}")
+        if not m._native():
+            raise _lib.GitcapError("stream_pool needs the native TinyViT encoder (image_encoder='native'): frames are "
+                                   "encoded one at a time on the device")
+        return m._encode_packed(frames).contiguous()
+
+    def push(self, frames: torch.Tensor, streams) -> dict:
+        """``frames``: n frames, uint8 camera frames [n,H,W,3], fp32 [n,3,S,S] or memory tokens [n,d_model], on the CPU or the device;
+        ``streams``: n ints, frame i belongs to stream streams[i] and is newer than that stream's earlier frames, this push's
+        included (at most mem_tokens per stream and push, at most max_batch * mem_tokens frames per push).  The frames are encoded
+        once, in one packed pass.  -> {stream: ids} for every stream that is due (possibly empty); ids int64 [1 + steps] with CLS
+        first, on the CPU when the frames were."""
+        self._check_live()
+        ids = self._sched.check(streams)
+        if frames.shape[0] != len(ids):
+            raise ValueError(f"{frames.shape[0]} frames for {len(ids)} stream ids")
+        cap = self._m.max_batch * self._m.cfg.mem_tokens
+        if len(ids) > cap:
+            raise ValueError(f"a push takes at most max_batch * mem_tokens = {cap} frames, got {len(ids)}")
+        self._push_lib(self._tokens(frames), ids)
+        return self._caption(self._sched.push(ids), frames.device.type == "cpu")
+
+    def caption(self, streams, to_cpu: bool = False) -> dict:
+        """Caption these streams now, whatever the schedule says -> {stream: ids}.  Every one of them must hold a frame."""
+        self._check_live()
+        ids = [int(s) for s in streams]
+        if len(set(ids)) != len(ids):
+            raise ValueError("a stream is named twice")
+        return self._caption(ids, to_cpu)
+
+    def _caption(self, due, to_cpu: bool) -> dict:
+        out = {}
+        B = self._m.max_batch
+        sep = self._m.cfg.sep_token_id
+        for c0 in range(0, len(due), B):
+            chunk = due[c0:c0 + B]
+            ids, lp, tk, seen = self._caption_lib(chunk)
+            if to_cpu:
+                ids, lp, tk = ids.cpu(), None if lp is None else lp.cpu(), None if tk is None else (tk[0].cpu(), tk[1].cpu())
+            host = ids if to_cpu or self._mode != STOP_ALL_SEP else ids.cpu()
+            for r, s in enumerate(chunk):
+                n = cut_at_sep(host[r], sep) if self._mode == STOP_ALL_SEP else self._max_len
+                out[s] = ids[r, :1 + n]
+                self.last_frames[s] = int(seen[r])
+                if lp is not None:
+                    self.last_logprobs[s] = lp[r, :n]
+                if tk is not None:
+                    self.last_top_ids[s], self.last_top_logprobs[s] = tk[0][r, :n], tk[1][r, :n]
+            self._sched.captioned(chunk)
+        return out
+
+    def drop(self, stream: int):
+        """Empty one stream (a camera that reconnected); the others keep their frames."""
+        self._check_live()
+        s = int(stream)
+        if not 0 <= s < self._sched.streams:
+            raise ValueError(f"stream {s} outside 0..{self._sched.streams - 1}")
+        self._drop_lib(s)
+        self._sched.drop(s)
+        for d in (self.last_logprobs, self.last_top_ids, self.last_top_logprobs, self.last_frames):
+            d.pop(s, None)
+
+    def counts(self) -> list:
+        """Frames held per stream, 0..mem_tokens (gitcap_student_pool_counts)."""
+        self._check_live()
+        return self._counts_lib()

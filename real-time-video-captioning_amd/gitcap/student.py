@@ -27,6 +27,7 @@ from . import _lib, ragged
 from ._handle import _NativeModule
 from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
 from .framegate import FrameGate
+from .streampool import StudentStreamPool
 from .student_config import (CStudentConfig, StudentConfig, check_student_shapes, positional_table, student_shapes)
 from .tinyvit import TinyViTEncoder, tinyvit_config
 from .window import WindowSchedule
@@ -158,6 +159,7 @@ class StudentCaptioner(_NativeModule):
         self._dev = torch.device(device)
         self._handle = None
         self._window_owner = None                       # token of the live StudentCaptionStream
+        self._pool_owner = None                         # token of the live StudentStreamPool (state of its own beside the window)
         self.last_accepted: Optional[int] = None        # draft tokens the last greedy_decode(draft=...) accepted
         self._weights: Optional[Dict[str, np.ndarray]] = None
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
@@ -172,6 +174,7 @@ class StudentCaptioner(_NativeModule):
 
     def _moved(self):
         self._window_owner = None                       # the window lived in the old handle
+        self._pool_owner = None                         # and so did the pool
 
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, *args, **kwargs):
@@ -215,6 +218,7 @@ class StudentCaptioner(_NativeModule):
         return self
 
     def _upload(self, w):
+        self._pool_owner = None                         # gitcap_student_finalize releases the pool: its K|V rows came from the old weights
         self._load_tensors((name, w[name]) for name in student_shapes(self.cfg))
 
     def __reduce__(self):
@@ -651,6 +655,33 @@ class StudentCaptioner(_NativeModule):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
         return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial)
+
+    def stream_pool(self, streams: int, hop: int = 1, max_len: int = 25, stop: Optional[str] = None, logprobs: bool = False,
+                    top_logprobs: int = 0, min_frames: int = 1) -> StudentStreamPool:
+        """Several live cameras on one model (the multi-camera loop): `streams` independent windows of
+        ``mem_tokens`` frames.  ``pool.push(frames, streams)`` takes n frames for any streams in any mix (frame i belongs to stream
+        streams[i]), encodes them once in one packed pass and returns ``{stream: ids}`` for every stream that is due: at least
+        `hop` of its frames have arrived since its last caption and it holds at least `min_frames` frames (1: a caption from a
+        camera's first frame on, as caption_stream(partial=True); mem_tokens: only full windows, as partial=False).  The due
+        streams are captioned as one ragged batch, in chunks of max_batch (include/gitcap.h: gitcap_student_pool_*).  A stream's
+        caption is bit for bit greedy_decode(max_len, stop) on a list holding that stream's last frames, cut behind the row's own
+        first SEP under the all_sep rule (not at the batch-wide step count): it does not depend on which other streams were due.
+        ``logprobs`` / ``top_logprobs=k``: ``pool.last_logprobs[stream]``, ``pool.last_top_ids[stream]`` /
+        ``pool.last_top_logprobs[stream]`` of a stream's latest caption, cut the same way; ``pool.last_frames[stream]`` = the frames
+        it saw.  ``pool.caption(streams)`` captions now, ``pool.drop(stream)`` empties one stream, ``pool.counts()`` = frames held
+        per stream.  Camera frames need the native encoder; memory tokens [n, d_model] can be pushed without one.
+        The pool and a caption_stream() of the same model live side by side: opening one does not invalidate the other.  Opening
+        another pool, moving the model or loading weights invalidates this one.
+        Out of scope: scene-change gates (put one FrameGate per camera in front of ``push``; deciding all cameras' gates in one
+        launch is a later change), ``carry`` / drafts and beams."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if streams < 1 or streams > 4096:
+            raise ValueError(f"streams={streams} outside 1..4096")
+        if max_len < 1 or max_len > self.max_text_len:
+            raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
+        mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        return StudentStreamPool(self, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:

@@ -46,3 +46,49 @@ class WindowSchedule:
         """Indices (0 = the first frame pushed since the reset) of the frames the library's ring holds, oldest first: the caption
         window once it is full."""
         return range(max(0, self.pushed - self.window), self.pushed)
+
+
+class PoolSchedule:
+    """`streams` independent windows of `window` frames (StudentCaptioner.stream_pool): a push names the stream of each of its frames,
+    any streams in any mix.  A stream is due once at least `hop` of its frames have arrived since its last caption (or since it was
+    emptied) and it holds at least `min_frames` frames; min_frames = window is WindowSchedule's full-window rule, min_frames = 1 its
+    partial one."""
+
+    def __init__(self, streams: int, window: int, hop: int = 1, min_frames: int = 1):
+        if streams < 1 or window < 1 or hop < 1:
+            raise ValueError(f"streams, window and hop must be >= 1 (got {streams}, {window}, {hop})")
+        if not 1 <= min_frames <= window:
+            raise ValueError(f"min_frames={min_frames} outside 1..{window}")
+        self.streams, self.window, self.hop, self.min_frames = int(streams), int(window), int(hop), int(min_frames)
+        self.reset()
+
+    def reset(self):
+        self.held = [0] * self.streams       # frames a stream's window holds, 0..window
+        self.since = [0] * self.streams      # frames arrived since the stream's last caption
+
+    def check(self, ids):
+        """Raises ValueError if a push whose frames go to streams `ids` is not one the pool takes."""
+        ids = [int(s) for s in ids]
+        if not ids:
+            raise ValueError("a push takes at least one frame")
+        for s in ids:
+            if not 0 <= s < self.streams:
+                raise ValueError(f"stream {s} outside 0..{self.streams - 1}")
+        worst = max(set(ids), key=ids.count)
+        if ids.count(worst) > self.window:
+            raise ValueError(f"a push takes at most {self.window} frames per stream, got {ids.count(worst)} for stream {worst}")
+        return ids
+
+    def push(self, ids) -> list:
+        """Record a push -> the streams that are due now, ascending.  They stay due until ``captioned`` says otherwise."""
+        for s in self.check(ids):
+            self.held[s] = min(self.held[s] + 1, self.window)
+            self.since[s] += 1
+        return [s for s in range(self.streams) if self.since[s] >= self.hop and self.held[s] >= self.min_frames]
+
+    def captioned(self, ids):
+        for s in ids:
+            self.since[s] = 0
+
+    def drop(self, s: int):
+        self.held[s] = self.since[s] = 0
