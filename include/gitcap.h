@@ -501,7 +501,8 @@ int gitcap_attach_frame_counts(gitcap_t* h, const int32_t* counts, int B);
  *   suppress (HF SuppressTokensLogitsProcessor): up to 256 ids banned at every step; duplicates allowed, ids outside the
  *       vocabulary ignored.
  * A position forced by a prompt (gitcap_attach_prompt) takes the prompt's token whatever is banned; under a repetition penalty -inf
- * stays -inf.  gitcap_score, gitcap_distill, gitcap_text_forward and the student model are not constrained.
+ * stays -inf.  gitcap_score, gitcap_distill and gitcap_text_forward are not constrained; the student model takes the same rules
+ * through an attachment of its own (gitcap_student_attach_constraints).
  * A ONE-SHOT attachment with the life cycle of gitcap_attach_prompt: the next call of the greedy family (gitcap_greedy,
  * gitcap_greedy_raw, their _submit forms, gitcap_window_greedy) or of the beam family (gitcap_beam_search, its _submit / _raw_submit
  * forms, gitcap_window_beam_search, sampled or not) consumes it, whichever comes first, whether that call succeeds or is refused;
@@ -536,6 +537,10 @@ int gitcap_attach_constraints(gitcap_t* h, const gitcap_constraints* c);   /* NU
  * that hold -inf at the banned columns, bit for bit. */
 int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
                         const int32_t* suppress, int n_suppress, int V, uint16_t* mask_out, int ld_mask, void* stream);
+/* gitcap_dbg_ban_mask with its rules read on the device when the kernel runs (tests/test_student_constraints_gpu.py): rec, device
+ * int32 [4 + 256] = {n, min_length, n_suppress, 0, the suppress ids}; n_suppress is clamped on the device to 0..256.  Same mask. */
+int gitcap_dbg_ban_mask_rec(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int sep_id, const int32_t* rec, int V,
+                            uint16_t* mask_out, int ld_mask, void* stream);
 int gitcap_dbg_vocab_head_banned(const void* X, int ldx, const void* W, const float* wscale, const float* bias, int M, int N, int K,
                                  float* logits, float* amax_val, int32_t* amax_idx, float* amax_sum, const uint16_t* mask, int ld_mask,
                                  void* stream);
@@ -1162,6 +1167,26 @@ int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_ou
  * pending.  Needs finalized weights.  The captured token loop is keyed by k; the first attach allocates the third partial and the
  * handle's own [rows][max_len][32] staging the captured loops write. */
 int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_ids, float* top_lp, int ld);
+/* Constrained decoding on the student: gitcap_attach_constraints for this handle -- the same struct (suppress is a device int32
+ * list), the same banned set per row and step (prefix = the row's ids so far, CLS included; the SEP of min_length is the handle's
+ * sep_token_id), banned columns -inf ahead of the arg-max, the log-probabilities, the alternatives and the log-softmax of the beam
+ * ranking.  The student's loops keep decoding behind a row's SEP, and the rules keep applying there.
+ * A ONE-SHOT attachment with the life cycle of gitcap_attach_constraints: the next call of the greedy family (gitcap_student_greedy,
+ * _window_greedy, _window_greedy_partial, _pool_greedy) or of the beam family (gitcap_student_beam_search, _window_beam_search)
+ * consumes it, whichever comes first, whether that call succeeds or is refused; gitcap_student_greedy_draft and
+ * _window_greedy_draft consume it and fail with GITCAP_ERR_ARG; gitcap_student_score, _attention, _forward_decoder, _set_memory, the
+ * pushes and gitcap_distill leave it pending; NULL detaches.  It combines with the log-probability, top-logprob and frame-count
+ * attachments.  In a pool call one set of rules applies to every stream named.
+ * The greedy loops are captured graphs, so the rules are no kernel arguments: the consuming call writes them to a device record
+ * (int32 [4 + 256]: n, min_length, n_suppress, 0, the ids) on the caller's stream ahead of the replay -- `suppress` is read by a
+ * device-to-device copy enqueued there, at the consuming call -- and every step's mask launch reads the record when it runs.  One
+ * captured loop per (B, max_len, ...) serves every set of rules; a call without constraints replays the unconstrained loop.
+ * The first attach allocates the mask (uint16 [max_rows][ld], ld even >= ceil(V / 16)), the record and a page-locked copy of its
+ * header; a handle that never attaches allocates nothing and runs exactly the launches it ran before.
+ * Errors, all GITCAP_ERR_ARG: a negative field; n_suppress > 256; n_suppress > 0 with a null or misaligned pointer; a vocabulary
+ * above 131072 columns; at the consuming call n_suppress + max_len >= vocab_size (greedy) or n_suppress + max_len + k > vocab_size
+ * (beam).  Nothing is launched then and the attachment is consumed all the same.  GITCAP_ERR_STATE before the weights are finalized. */
+int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constraints* c);
 /* gitcap_score over the student decoder's teacher-forced pass (the rows of gitcap_student_forward_decoder, after
  * gitcap_student_set_memory with `rows` rows): same semantics, outputs and ignore rules; no `beams` (candidates of one clip are
  * rows whose memory the caller repeated).  Checks: gitcap_student_forward_decoder's, plus T < 2, ld_ids < T, ld_lp < T - 1. */

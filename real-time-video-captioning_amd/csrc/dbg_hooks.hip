@@ -145,6 +145,12 @@ int gitcap_dbg_ban_mask(const int64_t* prefix_ids, int ld_ids, int rows, int cur
     return dbg_rc(launch_ban_mask(prefix_ids, ld_ids, rows, cur_len, n, min_length, sep_id, suppress, n_suppress, V, mask_out, ld_mask,
                                   (hipStream_t)stream));
 }
+// the form that reads its rules from a device record (kernels.h: launch_ban_mask_rec; tests/test_student_constraints_gpu.py)
+int gitcap_dbg_ban_mask_rec(const int64_t* prefix_ids, int ld_ids, int rows, int cur_len, int sep_id, const int32_t* rec, int V,
+                            uint16_t* mask_out, int ld_mask, void* stream) {
+    if (((uintptr_t)prefix_ids & 7) != 0) return GITCAP_ERR_ARG;
+    return dbg_rc(launch_ban_mask_rec(prefix_ids, ld_ids, rows, cur_len, sep_id, rec, V, mask_out, ld_mask, (hipStream_t)stream));
+}
 
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
                     int epi, int tile, void* stream) {

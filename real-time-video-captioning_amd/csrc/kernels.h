@@ -108,7 +108,7 @@ struct HeadTargets { const int64_t* ids; int T, ld, shift; float* logit; };
 // Ban mask of the constrained vocabulary head (gitcap_attach_constraints; kernels of their own, skinny.hip "BAN"): uint16
 // [rows][ld], bit c & 15 of word c >> 4 of row m set = column c of head row m is banned; one word = one 16-column tile.
 // ld >= ceil(N / 16) and even (rows 4-byte aligned).  A banned column's logit is -inf before a.out, the arg-max partial and
-// the sum partial are formed.  Built by launch_ban_mask (search.hip).
+// the sum partial are formed.  Built by launch_ban_mask / launch_ban_mask_rec (search.hip).
 struct HeadBan { const uint16_t* mask; int ld; };
 // tg (nullable): SK_BIAS_F32 with all three partial buffers set; a.out stays nullable
 // bn (nullable; not with tg or a row prologue): SK_BIAS_F32, the BAN form of the head (plain, or with amax_sum the LSE form)
@@ -380,6 +380,13 @@ hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& opt, c
 // beyond V and the words behind ceil(V / 16) are 0.  V <= 131072 (the row's bitmap is built in LDS), n_suppress <= 256.
 hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
                            const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s);
+// The same kernel body with the rules read on the device when the kernel runs, from rec int32 [BAN_REC_WORDS]: rec[0] = n, rec[1] =
+// min_length, rec[2] = n_suppress (clamped on the device to 0 .. BAN_REC_MAX_SUPPRESS: no value reads past the record), rec[3] = 0,
+// rec[4 ..] = the ids.  Nothing of the rules is a kernel argument, so a captured launch follows the record written last (the
+// student's token loops, student.hip); cur_len, sep_id, V and the id rows stay arguments.  The mask is launch_ban_mask's, bit for bit.
+constexpr int BAN_REC_HEADER = 4, BAN_REC_MAX_SUPPRESS = 256, BAN_REC_WORDS = BAN_REC_HEADER + BAN_REC_MAX_SUPPRESS;
+hipError_t launch_ban_mask_rec(const int64_t* ids, int ld_ids, int rows, int cur_len, int sep_id, const int32_t* rec, int V, uint16_t* mask,
+                               int ld_mask, hipStream_t s);
 // device-resident beam search state + one bookkeeping step per decoder step
 struct BeamBuffers {
     int64_t *ids0, *ids1, *words, *hyp_ids;

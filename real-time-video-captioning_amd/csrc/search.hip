@@ -468,13 +468,31 @@ hipError_t launch_sample_rows(const CandArgs& c, int pn, const SampleOpt& o, con
 //           tokens prefix[cur_len - n + 1 .. cur_len - 1] as int64 values and bans prefix[i + n - 1]; nothing while cur_len < n;
 //   length: sep_id while cur_len < min_length (HF MinLengthLogitsProcessor);   suppress: the listed ids.
 // An id outside [0, V) sets no bit, so the bits of the last word beyond V stay 0.
+// The rules (n, min_length, the suppress list) reach the body from the launch (BanRulesArgs: kernel arguments, the teacher's loops) or
+// from a device record read when the kernel runs (BanRulesRec; kernels.h: launch_ban_mask_rec), so that a captured token loop
+// follows whatever record was written last.  The record's list length is clamped to the record, so no value in it reads past it.
 namespace {
 constexpr int BM_MAX_V = 131072;
 
-__global__ __launch_bounds__(256) void ban_mask_kernel(const int64_t* __restrict__ ids, int ld_ids, int cur_len, int n, int min_length,
-                                                       int sep_id, const int32_t* __restrict__ suppress, int n_suppress, int V,
-                                                       unsigned* __restrict__ mask32, int ld32) {
+struct BanRules { int n, min_length; const int32_t* suppress; int n_suppress; };
+struct BanRulesArgs {
+    int n, min_length; const int32_t* suppress; int n_suppress;
+    __device__ __forceinline__ BanRules load() const { return BanRules{n, min_length, suppress, n_suppress}; }
+};
+struct BanRulesRec {
+    const int32_t* rec;     // int32 [BAN_REC_WORDS]: n, min_length, n_suppress, 0, the ids
+    __device__ __forceinline__ BanRules load() const {
+        return BanRules{rec[0], rec[1], rec + BAN_REC_HEADER, min(max(rec[2], 0), BAN_REC_MAX_SUPPRESS)};
+    }
+};
+
+template <typename Rules>
+__device__ __forceinline__ void ban_mask_body(const int64_t* __restrict__ ids, int ld_ids, int cur_len, const Rules rules, int sep_id, int V,
+                                              unsigned* __restrict__ mask32, int ld32) {
     __shared__ unsigned bits[BM_MAX_V / 32];
+    const BanRules ru = rules.load();
+    const int n = ru.n, min_length = ru.min_length, n_suppress = ru.n_suppress;
+    const int32_t* __restrict__ suppress = ru.suppress;
     const int row = blockIdx.x, tid = threadIdx.x;
     const int nw = (V + 31) >> 5;
     for (int w = tid; w < nw; w += 256) bits[w] = 0u;
@@ -496,14 +514,35 @@ __global__ __launch_bounds__(256) void ban_mask_kernel(const int64_t* __restrict
     unsigned* out = mask32 + (size_t)row * ld32;
     for (int w = tid; w < ld32; w += 256) out[w] = w < nw ? bits[w] : 0u;
 }
+
+__global__ __launch_bounds__(256) void ban_mask_kernel(const int64_t* __restrict__ ids, int ld_ids, int cur_len, int n, int min_length,
+                                                       int sep_id, const int32_t* __restrict__ suppress, int n_suppress, int V,
+                                                       unsigned* __restrict__ mask32, int ld32) {
+    ban_mask_body(ids, ld_ids, cur_len, BanRulesArgs{n, min_length, suppress, n_suppress}, sep_id, V, mask32, ld32);
+}
+__global__ __launch_bounds__(256) void ban_mask_rec_kernel(const int64_t* __restrict__ ids, int ld_ids, int cur_len, int sep_id,
+                                                           const int32_t* __restrict__ rec, int V, unsigned* __restrict__ mask32, int ld32) {
+    ban_mask_body(ids, ld_ids, cur_len, BanRulesRec{rec}, sep_id, V, mask32, ld32);
+}
+
+bool ban_mask_args_ok(const int64_t* ids, int ld_ids, int rows, int cur_len, int V, const uint16_t* mask, int ld_mask) {
+    return ids && mask && rows > 0 && cur_len >= 0 && ld_ids >= cur_len && V > 0 && V <= BM_MAX_V && ld_mask >= (V + 15) / 16 && !(ld_mask & 1) &&
+           !((uintptr_t)mask & 3);
+}
 }  // namespace
 hipError_t launch_ban_mask(const int64_t* ids, int ld_ids, int rows, int cur_len, int n, int min_length, int sep_id,
                            const int32_t* suppress, int n_suppress, int V, uint16_t* mask, int ld_mask, hipStream_t s) {
-    if (!ids || !mask || rows <= 0 || cur_len < 0 || ld_ids < cur_len || n < 0 || min_length < 0 || n_suppress < 0 || n_suppress > 256 ||
-        (n_suppress > 0 && !suppress) || V <= 0 || V > BM_MAX_V || ld_mask < (V + 15) / 16 || (ld_mask & 1) || ((uintptr_t)mask & 3))
+    if (!ban_mask_args_ok(ids, ld_ids, rows, cur_len, V, mask, ld_mask) || n < 0 || min_length < 0 || n_suppress < 0 ||
+        n_suppress > BAN_REC_MAX_SUPPRESS || (n_suppress > 0 && !suppress))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(ban_mask_kernel, dim3(rows), dim3(256), 0, s, ids, ld_ids, cur_len, n, min_length, sep_id, suppress, n_suppress, V,
                        (unsigned*)mask, ld_mask / 2);
+    return hipGetLastError();
+}
+hipError_t launch_ban_mask_rec(const int64_t* ids, int ld_ids, int rows, int cur_len, int sep_id, const int32_t* rec, int V, uint16_t* mask,
+                               int ld_mask, hipStream_t s) {
+    if (!ban_mask_args_ok(ids, ld_ids, rows, cur_len, V, mask, ld_mask) || !rec || ((uintptr_t)rec & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ban_mask_rec_kernel, dim3(rows), dim3(256), 0, s, ids, ld_ids, cur_len, sep_id, rec, V, (unsigned*)mask, ld_mask / 2);
     return hipGetLastError();
 }
 

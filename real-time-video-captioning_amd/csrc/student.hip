@@ -300,7 +300,7 @@ struct gitcap_student : HandleCore {
     // key: stop = a stop rule -> execs[0] the whole greedy loop; TAIL_STEPS -> execs[t - 1] token step t of the draft path, t >= 1
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; bool ragged; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none); ragged: the varlen cross-attention launches
+    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; bool ragged, cons; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none); ragged: the varlen cross-attention launches; cons: the constrained loop
     static constexpr int TAIL_STEPS = -1;
     std::vector<Graphs> graphs;
     // draft verification (gitcap_student_*_greedy_draft): acc_tok / acc_ticket = draft_accept_kernel's scratch, acc_host = its
@@ -334,6 +334,16 @@ struct gitcap_student : HandleCore {
     bool ragged = false;
     int32_t *key_tab = nullptr, *key_host = nullptr;
     hipEvent_t key_ev = nullptr;
+    // constrained decoding (gitcap_student_attach_constraints): co_attach = the pending one-shot rules.  The first attach allocates
+    // ban_mask (uint16 [R][ban_ld], the step's rows), ban_rec (device int32 [BAN_REC_WORDS]: n, min_length, n_suppress, 0, the ids) and
+    // ban_host, the page-locked copy of the record's header.  The constrained token loop is a graph of its own whose mask launches
+    // read ban_rec when they run: the consuming call writes it outside the graph (write_ban_record, behind ban_ev = the previous
+    // copy has read ban_host), so one captured loop serves every set of rules.
+    ConsOpt co_attach{};
+    uint16_t* ban_mask = nullptr;
+    int ban_ld = 0;
+    int32_t *ban_rec = nullptr, *ban_host = nullptr;
+    hipEvent_t ban_ev = nullptr;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -431,7 +441,8 @@ int sk_full(gitcap_student* h, hipStream_t s, int epi, const bf16_t* X, int ldx,
 
 // model.py:128-154 for rows x T query positions t0..t0+T-1 (K/V of earlier positions come from the cache); the request is the
 // part the two handles share (RowsReq, kernels.h): logits_out set = the logits of all positions
-using TextReq = RowsReq;
+// ban (nullable; a constrained greedy step): the BAN form of the head, mask row m = head row m
+struct TextReq : RowsReq { const HeadBan* ban = nullptr; };
 int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
     const gitcap_student_config& c = h->c;
     const int64_t* const ids = q.ids;
@@ -512,7 +523,7 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
     const HeadRows hr = vocab_head_args(ha, head_weight(h), h->xb, rows, T, q.logits_out != nullptr, q.logits_out,
                                         q.argmax_out ? h->amax_val : nullptr, q.argmax_out ? h->amax_idx : nullptr,
                                         q.lp_out || q.topk.k ? h->amax_sum : nullptr);
-    HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s));
+    HIP_OK(h, launch_skinny(ha, SK_BIAS_F32, s, nullptr, q.ban));
     if (q.argmax_out) {
         ArgmaxArgs a{};
         a.val = h->amax_val; a.idx = h->amax_idx; a.sum = q.lp_out ? h->amax_sum : nullptr; a.ntiles = (h->V + 15) / 16;
@@ -523,7 +534,7 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
     }
     if (q.topk.k) {     // the k best of the row the arg-max read, from the same partials
         HeadTopkArgs ta{};
-        ta.X = ha.X; ta.ldx = ha.ldx; ta.hw = head_weight(h); ta.val = h->amax_val; ta.idx = h->amax_idx; ta.sum = h->amax_sum;
+        ta.X = ha.X; ta.ldx = ha.ldx; ta.hw = head_weight(h); ta.val = h->amax_val; ta.idx = h->amax_idx; ta.sum = h->amax_sum; ta.bn = q.ban;
         ta.rows = rows; ta.T = 1; ta.row_stride = hr.am_stride; ta.row_off = hr.am_off;
         ta.k = q.topk.k; ta.top_ids = q.topk.ids; ta.top_lp = q.topk.lp; ta.ld = q.topk.ld;
         HIP_OK(h, launch_head_topk(ta, s));
@@ -674,6 +685,8 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     if (h->acc_ev) (void)hipEventDestroy(h->acc_ev);
     if (h->key_host) (void)hipHostFree(h->key_host);
     if (h->key_ev) (void)hipEventDestroy(h->key_ev);
+    if (h->ban_host) (void)hipHostFree(h->ban_host);
+    if (h->ban_ev) (void)hipEventDestroy(h->ban_ev);
     free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
@@ -796,14 +809,43 @@ const bool g_use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP
 // Token step t of the greedy loop (model.py:173-182) on the handle's id rows: position t in, the arg-max as token t + 1 (and, with
 // want_lp, its log-probability as column t of g_lp; with tk != 0 the tk best of that distribution as entry t of g_tk_ids / g_tk_lp).
 // The full loop, the captured tail steps and the un-graphed tail are this call.
-int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q, int tk = 0) {
+// cons: first the rows' ban mask from the ids so far (prefix 0 .. t) under the rules in ban_rec, then the BAN form of the head.
+int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q, int tk = 0, bool cons = false) {
     const int ld = max_len + 1;
+    const HeadBan bn{h->ban_mask, h->ban_ld};
     TextReq r;
+    if (cons) {
+        HIP_OK(h, launch_ban_mask_rec(h->g_ids, ld, B, t + 1, h->c.sep_token_id, h->ban_rec, h->V, h->ban_mask, h->ban_ld, q));
+        r.ban = &bn;
+    }
     r.ids = h->g_ids; r.ld_ids = ld; r.rows = B; r.t0 = r.step = t; r.T = 1;
     r.argmax_out = h->g_ids + t + 1; r.ld_argmax = ld; r.sep_cnt = h->sep_cnt;
     r.lp_out = want_lp ? h->g_lp + t : nullptr; r.ld_lp = max_len;
     if (tk) r.topk = TopkAttach{tk, h->g_tk_ids + (size_t)t * tk, h->g_tk_lp + (size_t)t * tk, max_len};
     return text_forward(h, r, q);
+}
+
+// ---- constrained decoding (gitcap_student_attach_constraints) --------------------------------------------------------------------
+// the pending rules: consumed by the caller, whatever becomes of its call
+ConsOpt take_constraints(gitcap_student* h) { return std::exchange(h->co_attach, ConsOpt{}); }
+// A call whose rows could lose every column is refused: each step bans at most n_suppress listed ids, one id per prefix position and
+// SEP; need = the columns the call must still find (1: the arg-max; k: the candidates a clip's ranking keeps).
+int cons_check(gitcap_student* h, const std::string& who, const ConsOpt& co, int max_len, int need) {
+    if (co.on && (int64_t)co.n_suppress + max_len + need > h->V)
+        return fail(h, GITCAP_ERR_ARG, who + ": the attached constraints could ban every column of a row (n_suppress + max_len" +
+                    (need > 1 ? " + k > vocab_size)" : " >= vocab_size)"));
+    return 0;
+}
+// The rules of the call -> ban_rec, on `s` and outside every captured loop: the header through the page-locked copy (reused once the
+// previous call's transfer has read it), the list by a device-to-device copy of the caller's `suppress`.
+int write_ban_record(gitcap_student* h, const ConsOpt& co, hipStream_t s) {
+    HIP_OK(h, hipEventSynchronize(h->ban_ev));      // (an event never recorded is complete)
+    h->ban_host[0] = co.ngram; h->ban_host[1] = co.min_length; h->ban_host[2] = co.n_suppress; h->ban_host[3] = 0;
+    HIP_OK(h, hipMemcpyAsync(h->ban_rec, h->ban_host, BAN_REC_HEADER * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipEventRecord(h->ban_ev, s));
+    if (co.n_suppress)
+        HIP_OK(h, hipMemcpyAsync(h->ban_rec + BAN_REC_HEADER, co.suppress, (size_t)co.n_suppress * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 // What enqueue(cap_stream) launches -> one executable graph (replayed on the caller's stream).  A failed enqueue still ends the
@@ -828,14 +870,14 @@ int capture(gitcap_student* h, const char* what, Enqueue enqueue, hipGraphExec_t
 // The executables of a key, captured by fill(execs) at the key's first use; a failed fill caches nothing.  Weight and workspace
 // pointers are baked into the nodes (destroy_graphs at every finalize).
 template <typename Fill>
-int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, Fill fill, const std::vector<hipGraphExec_t>** out) {
+int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, bool cons, Fill fill, const std::vector<hipGraphExec_t>** out) {
     for (auto& g : h->graphs)
         if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp && g.tk == tk &&
-            g.ragged == h->ragged) {
+            g.ragged == h->ragged && g.cons == cons) {
             *out = &g.execs;
             return 0;
         }
-    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, h->ragged, {}};
+    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, h->ragged, cons, {}};
     if (int rc = fill(g.execs)) {
         for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
         return rc;
@@ -863,21 +905,23 @@ int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* s
 
 // the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
 // lp.p set: the loop with token log-probabilities (a graph of its own; column t of g_lp = step t's)
+// co.on: the constrained loop (a graph of its own, whatever the rules: they are written to ban_rec here, ahead of the replay)
 int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s, const LpAttach& lp,
-                const TopkAttach& tk) {
+                const TopkAttach& tk, const ConsOpt& co) {
     const bool want_lp = lp.p != nullptr;
     int rc;
+    if (co.on && (rc = write_ban_record(h, co, s))) return rc;
     auto enqueue_loop = [&](hipStream_t q) -> int {
         HIP_OK(h, launch_fill_i64(h->g_ids, max_len + 1, B, h->c.cls_token_id, q));        // model.py:171
         HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
         for (int t = 0; t < max_len; ++t)                                                    // model.py:173-182
-            if (int r = token_step(h, B, t, max_len, want_lp, q, tk.k)) return r;
+            if (int r = token_step(h, B, t, max_len, want_lp, q, tk.k, co.on)) return r;
         HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
         return 0;
     };
     if (g_use_graph) {
         const std::vector<hipGraphExec_t>* loop = nullptr;
-        rc = captured_graphs(h, B, max_len, stop, want_lp, tk.k, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, stop, want_lp, tk.k, co.on, [&](std::vector<hipGraphExec_t>& execs) {
             execs.push_back(nullptr);
             return capture(h, "student greedy: capturing the token loop", enqueue_loop, &execs.back());
         }, &loop);
@@ -910,7 +954,7 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
     const std::vector<hipGraphExec_t>* steps = nullptr;
     if (g_use_graph) {
-        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, 0, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, 0, false, [&](std::vector<hipGraphExec_t>& execs) {
             for (int t = 1; t < max_len; ++t) {
                 execs.push_back(nullptr);
                 if (int r = capture(h, "student draft: capturing a token step", [&](hipStream_t q) { return token_step(h, B, t, max_len, want_lp, q); },
@@ -989,7 +1033,9 @@ int beam_workspace(gitcap_student* h) {
 }
 
 // the token loop of beam_search against the memory K|V of B * k rows in h->memkv (set_memory of the repeated rows, or the window's gather)
-int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s) {
+// co.on: every step first builds the mask of the B * k rows from the buffer that holds their current prefixes (positions 0 .. t), and
+// the ranking runs its BAN form: banned columns are -inf ahead of the log-softmax
+int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s, const ConsOpt& co) {
     const int rows = B * k, D = h->D, V = h->V, ld = h->Tmax + 1;
     int rc = 0;
     gitcap_student::BeamWs& w = h->bw;
@@ -1004,6 +1050,8 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
     CandArgs ca{};              // the k best of every clip's k * V candidates, no penalty
     ca.logits = w.logits; ca.ld = V; ca.beam_scores = w.scores; ca.rp = 1.0f; ca.B = B; ca.beams = k; ca.V = V;
     ca.out_scores = w.cand_scores; ca.out_idx = w.cand_idx;
+    const HeadBan bn{h->ban_mask, h->ban_ld};
+    if (co.on) ca.bn = &bn;
     for (int t = 0; t + 1 < max_len && !rc; ++t) {                      // the token at position t is decoded, position t + 1 chosen
         if (t > 0) {                                                    // rows continue beam src_rows[r]: positions 0 .. t-1, all layers
             bf16_t* other = h->kvs == kvs_home ? w.kvs2 : kvs_home;
@@ -1014,6 +1062,11 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
         q.ids = cur; q.t0 = t;
         rc = text_forward(h, q, s);
         if (rc) break;
+        if (co.on) {
+            const hipError_t eb = launch_ban_mask(cur, ld, rows, t + 1, co.ngram, co.min_length, h->c.sep_token_id, co.suppress, co.n_suppress, V,
+                                                  h->ban_mask, h->ban_ld, s);
+            if (eb != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: ban_mask: ") + hipGetErrorString(eb)); break; }
+        }
         hipError_t e = launch_beam_topk(ca, k, w.topk_scratch, s);
         if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
         hipLaunchKernelGGL(student_beam_step_kernel, dim3(B), dim3(64), 0, s, w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, k, V, t, ld);
@@ -1066,13 +1119,17 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});
     const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
     const Counts fc = take_counts(h);
+    const ConsOpt co = take_constraints(h);
     if (window && !fc.empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));          // (consumed above)
+    if (draft && co.on)
+        return fail(h, GITCAP_ERR_ARG, w + ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take");
     if (draft && tk.k) return fail(h, GITCAP_ERR_ARG, refused_message(who, OPT_TK));       // (consumed above)
     if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
     if (int bad = lp_check(h, who, lp, max_len)) return bad;
     if (int bad = tk_check(h, who, tk, max_len)) return bad;
+    if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
     if (draft && !draft->ids) return fail(h, GITCAP_ERR_ARG, w + ": null draft_ids");
     if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
         return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
@@ -1086,7 +1143,7 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     if (frames_out) *frames_out = frames;
     if (window) B = h->win_B;
     if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1144,8 +1201,10 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
     const Counts fc = take_counts(h);
+    const ConsOpt co = take_constraints(h);
     if (!memory) return fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
     if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
+    if (int bad = cons_check(h, "student_beam_search", co, max_len, k)) return bad;
     const Counts* ragged = nullptr;
     if (int bad = counts_for_call(h, "student_beam_search", fc, B, &ragged)) return bad;
     GUARD(h);
@@ -1154,13 +1213,13 @@ int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, 
     if (rc) return rc;
     if (ragged) {       // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
         if ((rc = set_memory(h, memory, B, s, ragged, k))) return rc;
-        return beam_loop(h, B, k, max_len, ids_out, s);
+        return beam_loop(h, B, k, max_len, ids_out, s, co);
     }
     const int rows = B * k;
     hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
     HIP_OK(h, hipGetLastError());
     if ((rc = set_memory(h, h->bw.memrep, rows, s))) return rc;
-    return beam_loop(h, B, k, max_len, ids_out, s);
+    return beam_loop(h, B, k, max_len, ids_out, s, co);
 }
 
 int gitcap_student_window_reset(gitcap_student_t* h, int B) {
@@ -1284,6 +1343,30 @@ int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_
     return 0;
 }
 
+int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constraints* c) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: null handle");
+    h->co_attach = ConsOpt{};
+    if (!c) return 0;                                        // detach
+    if (c->no_repeat_ngram_size < 0 || c->min_length < 0 || c->n_suppress < 0) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: a negative field");
+    if (c->n_suppress > BAN_REC_MAX_SUPPRESS) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: n_suppress > 256");
+    if (c->n_suppress > 0 && (!c->suppress || ((uintptr_t)c->suppress & 3) != 0))
+        return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: n_suppress > 0 with a null or misaligned suppress pointer");
+    if (h->V > 131072) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: the ban mask takes a vocabulary of at most 131072 columns");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_constraints: weights not finalized");
+    GUARD(h);
+    {   // first attach: the mask of the step's rows (ld even, >= ceil(V / 16)), the record and its page-locked header; each on its
+        // own, so that an attach repeated after a failed allocation keeps what the first one got
+        int rc;
+        h->ban_ld = (((h->V + 15) / 16) + 1) & ~1;
+        if (!h->ban_mask && (rc = dev_alloc(h, &h->ban_mask, (size_t)h->R * (size_t)h->ban_ld))) { h->ban_mask = nullptr; return rc; }
+        if (!h->ban_rec && (rc = dev_alloc(h, &h->ban_rec, (size_t)BAN_REC_WORDS))) { h->ban_rec = nullptr; return rc; }
+        if (!h->ban_host) HIP_OK(h, hipHostMalloc((void**)&h->ban_host, BAN_REC_HEADER * sizeof(int32_t), hipHostMallocDefault));
+        if (!h->ban_ev) HIP_OK(h, hipEventCreateWithFlags(&h->ban_ev, hipEventDisableTiming));
+    }
+    h->co_attach = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
+    return 0;
+}
+
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
@@ -1341,16 +1424,18 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
+    const ConsOpt co = take_constraints(h);         // consumed, whatever becomes of the call
     if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_beam_search"));
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
     if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;
+    if (int bad = cons_check(h, "student_window_beam_search", co, max_len, k)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = beam_workspace(h);
     if (rc) return rc;
     if ((rc = window_memory(h, "student_window_beam_search", k, s))) return rc;
-    return beam_loop(h, h->win_B, k, max_len, ids_out, s);
+    return beam_loop(h, h->win_B, k, max_len, ids_out, s, co);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1450,12 +1535,14 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
     const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});           // consumed, whatever becomes of the call
     const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
+    const ConsOpt co = take_constraints(h);
     if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));
     if (!stream_ids || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
     if (int bad = lp_check(h, who, lp, max_len)) return bad;
     if (int bad = tk_check(h, who, tk, max_len)) return bad;
+    if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
     if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
     if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
@@ -1472,7 +1559,7 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = pool_memory(h, stream_ids, B, s, frames_out)) return rc;
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co);
 }
 
 int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id) {

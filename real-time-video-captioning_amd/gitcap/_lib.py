@@ -238,6 +238,7 @@ SYMBOLS = {
     # constrained decoding: n-gram, length and token bans (tests/test_constraints_gpu.py)
     "gitcap_attach_constraints": (c_int, [c_void_p, POINTER(CConstraints)]),
     "gitcap_dbg_ban_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "gitcap_dbg_ban_mask_rec": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gitcap_dbg_vocab_head_banned": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gitcap_beam_topk_constrained": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int,
@@ -270,6 +271,7 @@ SYMBOLS = {
     "gitcap_student_draft_stats": (c_int, [c_void_p, POINTER(c_int64)]),
     "gitcap_student_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     "gitcap_student_attach_top_logprobs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "gitcap_student_attach_constraints": (c_int, [c_void_p, POINTER(CConstraints)]),
     "gitcap_student_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "gitcap_student_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -26,10 +26,13 @@ class StudentStreamPool:
     caption ``last_logprobs[stream]`` (logprobs=True), ``last_top_ids[stream]`` / ``last_top_logprobs[stream]`` (top_logprobs=k)
     and ``last_frames[stream]`` (the frames it saw) hold that caption's, cut the same way.
     Scene-change gates are not part of the pool: a caller puts one FrameGate per camera in front of ``push`` and pushes the frames
-    it admits; one launch for all the gates' decisions is left to a later change.  Nor does the pool carry drafts or run beams."""
+    it admits; one launch for all the gates' decisions is left to a later change.  Nor does the pool carry drafts or run beams.
+    ``constraints`` (StudentCaptioner.stream_pool's constraint arguments, or None): one set of rules for every stream, attached
+    again for every pool call."""
 
-    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames):
+    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None):
         self._m = model
+        self._co = constraints
         self._sched = PoolSchedule(streams, model.cfg.mem_tokens, hop, min_frames)
         self._max_len, self._mode = int(max_len), mode
         self._want_lp, self._top_k = bool(logprobs), int(top_logprobs)
@@ -73,6 +76,8 @@ class StudentStreamPool:
         seen = (ctypes.c_int32 * B)()
         with torch.cuda.device(m._dev):
             m._attach_logprobs(lp, tk)
+            if self._co is not None:
+                self._co.attach(m)
             m._call("gitcap_student_pool_greedy", (ctypes.c_int32 * B)(*ids), B, L, self._mode, _lib.ptr(out), None, seen, m._stream())
         return out, lp, tk, list(seen)
 

@@ -35,6 +35,24 @@ from .window import WindowSchedule
 ENC_PREFIX = "image_encoder.model."
 
 
+class _StudentConstraints:
+    """Hard constraints of a student decoding call (include/gitcap.h: gitcap_student_attach_constraints): the n-gram size, the
+    minimum length and the suppress list as a device int32 tensor (read by the consuming call, on its stream)."""
+
+    def __init__(self, model, n, min_length, suppress):
+        self.n, self.min_length, self.suppress = n, min_length, tuple(suppress)
+        self._ids = torch.tensor(suppress, dtype=torch.int32, device=model._dev) if suppress else None
+        self._c = _lib.CConstraints(n, min_length, None if self._ids is None else self._ids.data_ptr(), len(suppress))
+
+    def attach(self, model):
+        """The one-shot attachment the NEXT greedy- or beam-family call consumes (a repeated call attaches again)."""
+        model._call("gitcap_student_attach_constraints", ctypes.byref(self._c))
+
+
+def _constrained(no_repeat_ngram_size, min_length, suppress_tokens) -> bool:
+    return bool(no_repeat_ngram_size or min_length or suppress_tokens is not None)
+
+
 class StudentCaptionStream(_WindowStream):
     """Live captioning on the student over a sliding window of ``mem_tokens`` frames (StudentCaptioner.caption_stream;
     include/gitcap.h: gitcap_student_window_*).  A frame is encoded once, when it is pushed, and its cross-attention K|V rows
@@ -42,10 +60,13 @@ class StudentCaptionStream(_WindowStream):
     greedy_decode / beam_search on the window's frames.  With a ``gate`` (gitcap.framegate.FrameGate) only the frames it admits
     are encoded and counted; a push of camera frames with none admitted returns None and costs one distance launch.  With
     ``carry`` a greedy stream offers its previous caption as the draft of the next window call
-    (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop."""
+    (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop.
+    ``constraints`` (a _StudentConstraints or None): the stream's hard constraints, attached again for every caption."""
 
-    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0, partial=False):
+    def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0, partial=False,
+                 constraints=None):
         self._carry, self._prev, self._beams = bool(carry), None, beams
+        self._co = constraints
         self._partial = bool(partial)
         self.last_frames = None          # frames per clip the caption of the last push saw (mem_tokens unless partial=True)
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
@@ -100,6 +121,8 @@ class StudentCaptionStream(_WindowStream):
                     last = m._draft_call("gitcap_student_window_greedy_draft", (), self._prev, self._max_len, self._mode, ids, steps, lp)
                 else:
                     m._attach_logprobs(lp, tk)
+                    if self._co is not None:
+                        self._co.attach(m)
                     if self._partial:            # whatever the window holds; a full one is the plain call
                         seen = ctypes.c_int32(0)
                         m._call("gitcap_student_window_greedy_partial", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps),
@@ -115,6 +138,8 @@ class StudentCaptionStream(_WindowStream):
                 self._stats["last"] = last
             else:
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
+                if self._co is not None:
+                    self._co.attach(m)
                 m._call("gitcap_student_window_beam_search", self._beams, self._max_len, _lib.ptr(ids), m._stream())
                 out = ids.cpu() if to_cpu else ids
         if not self._partial:
@@ -481,6 +506,20 @@ class StudentCaptioner(_NativeModule):
         if tk is not None:
             self._call("gitcap_student_attach_top_logprobs", tk[0].shape[2], _lib.ptr(tk[0]), _lib.ptr(tk[1]), tk[0].shape[1])
 
+    def _constraints(self, no_repeat_ngram_size, min_length, suppress_tokens, max_len, need=1):
+        """The constraint arguments of the decoding calls -> _StudentConstraints or None (the defaults: nothing is attached).
+        ValueError for what the library would refuse (include/gitcap.h: gitcap_student_attach_constraints), before anything is
+        launched.  need: the columns a row must keep (1: the arg-max; k: a clip's beam candidates)."""
+        from .search import check_constraints
+        n, m, sup = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
+        if not (n or m or sup):
+            return None
+        if len(sup) + max_len + need > self.cfg.vocab_length:
+            raise ValueError(f"{len(sup)} suppressed ids over {max_len} steps could ban every column of a row (vocab_size {self.cfg.vocab_length})")
+        if self.cfg.vocab_length > 131072:
+            raise ValueError("the constraints' ban mask takes a vocabulary of at most 131072 columns")
+        return _StudentConstraints(self, n, m, sup)
+
     def _draft_call(self, name, head, draft: torch.Tensor, max_len: int, mode: int, ids: torch.Tensor, steps: torch.Tensor,
                     lp: Optional[torch.Tensor] = None, tk=None) -> dict:
         """One of the two draft entry points (``head`` = the arguments in front of the draft's); ``draft`` int64 [B, 1+n] on
@@ -507,7 +546,8 @@ class StudentCaptioner(_NativeModule):
     @torch.no_grad()
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                       draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0,
-                      return_attention: bool = False, frame_counts=None):
+                      return_attention: bool = False, frame_counts=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                      suppress_tokens=None):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
@@ -525,9 +565,16 @@ class StudentCaptioner(_NativeModule):
         frame_counts: clips that differ in length -- ``src`` padded [B,Fmax,...] (frames, camera frames or memory) with
         frame_counts [B], or ``src`` as a list of B clips [F_b,3,S,S] / uint8 [F_b,H,W,3] / memory [F_b,D], 1 <= F_b <=
         mem_tokens.  The batch runs packed, without padding or masking (include/gitcap.h: gitcap_student_attach_frame_counts):
-        every clip's results are bit for bit those of the clip decoded alone by a model with mem_tokens = F_b."""
+        every clip's results are bit for bit those of the clip decoded alone by a model with mem_tokens = F_b.
+        no_repeat_ngram_size / min_length / suppress_tokens: hard constraints on what a step may emit (include/gitcap.h:
+        gitcap_student_attach_constraints; HF's NoRepeatNGram / MinLength / SuppressTokens processors): no n-gram of the row so far
+        (CLS included) twice, no SEP while the row is shorter than min_length (CLS counts), and up to 256 ids never.  Banned columns
+        are -inf before the arg-max, so ``return_logprobs`` / ``top_logprobs`` are those of the renormalised row and never name a
+        banned id.  The loop keeps decoding behind a row's SEP and the rules keep applying there.  Not combined with ``draft``."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if draft is not None and _constrained(no_repeat_ngram_size, min_length, suppress_tokens):
+            raise ValueError("draft= is not combined with prompt= or the constraint arguments")
         counts = None
         if self._is_ragged(src, frame_counts):
             mem, B, counts, out_dev = self._ragged_memory(src, frame_counts)
@@ -539,6 +586,7 @@ class StudentCaptioner(_NativeModule):
         if max_len < 1 or max_len > self.max_text_len:
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
         lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
@@ -552,6 +600,8 @@ class StudentCaptioner(_NativeModule):
                 self._draft_call("gitcap_student_greedy_draft", (_lib.ptr(mem), B), draft, max_len, mode, ids, steps, lp, tk)
             else:
                 self._attach_logprobs(lp, tk)
+                if co is not None:
+                    co.attach(self)
                 self._call("gitcap_student_greedy", _lib.ptr(mem), B, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
@@ -573,12 +623,15 @@ class StudentCaptioner(_NativeModule):
     generate = greedy_decode
 
     @torch.no_grad()
-    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False, frame_counts=None) -> torch.Tensor:
+    def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False, frame_counts=None,
+                    no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> torch.Tensor:
         """model.py:189-318: k beams without end-of-sequence handling; returns the best beam [B, max_len].
         Runs on the device with the exact KV cache and no host round trip (``gitcap_student_beam_search``): the k beams
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams.  frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length; the k
-        beams of a clip share its memory rows."""
+        beams of a clip share its memory rows.
+        no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): every beam row's banned columns are -inf ahead of
+        the log-softmax, so the scores renormalise over the allowed columns."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the beam family (beam_search) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         counts = None
@@ -595,16 +648,20 @@ class StudentCaptioner(_NativeModule):
             raise ValueError(f"max_len={max_len} exceeds max_text_len+1={self.max_text_len + 1}")
         if max_len < 2 or k < 1 or k > 16:
             raise ValueError("beam_search needs max_len >= 2 and 1 <= k <= 16")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, k)
         best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
         with torch.cuda.device(self._dev):
             self._attach_counts(counts)
+            if co is not None:
+                co.attach(self)
             self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, _lib.ptr(best), self._stream())
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
                        logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False,
-                       partial: bool = False) -> StudentCaptionStream:
+                       partial: bool = False, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                       suppress_tokens=None) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -623,7 +680,9 @@ class StudentCaptioner(_NativeModule):
         after a reset see the 1, 2, ... frames admitted so far (bit for bit greedy_decode on a list holding those frames), and
         from mem_tokens frames on the stream is the ``partial=False`` one.  ``stream.last_frames`` = the frames the last
         caption saw.  Works with ``gate``, ``logprobs`` and ``top_logprobs``; not with ``carry`` or ``beams``, whose window calls
-        need a full window (include/gitcap.h: gitcap_student_window_greedy_partial)."""
+        need a full window (include/gitcap.h: gitcap_student_window_greedy_partial).
+        no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode / beam_search): the stream's constraints, attached
+        again for every caption, greedy or ``beams``; not with ``carry`` (a draft call does not take them)."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
@@ -634,6 +693,8 @@ class StudentCaptioner(_NativeModule):
             raise ValueError("logprobs=True is for greedy streams: it cannot be combined with beams")
         if carry and beams is not None:
             raise ValueError("carry=True verifies the previous greedy caption: it cannot be combined with beams")
+        if carry and _constrained(no_repeat_ngram_size, min_length, suppress_tokens):
+            raise ValueError("carry=True is not combined with prompt= or the constraint arguments")
         if partial and (carry or beams is not None):
             raise ValueError("partial=True is for greedy streams without carry: the beam and draft window calls need a full window")
         if not self._native():
@@ -654,10 +715,12 @@ class StudentCaptioner(_NativeModule):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial)
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, 1 if beams is None else beams)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial, co)
 
     def stream_pool(self, streams: int, hop: int = 1, max_len: int = 25, stop: Optional[str] = None, logprobs: bool = False,
-                    top_logprobs: int = 0, min_frames: int = 1) -> StudentStreamPool:
+                    top_logprobs: int = 0, min_frames: int = 1, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                    suppress_tokens=None) -> StudentStreamPool:
         """Several live cameras on one model (the multi-camera loop): `streams` independent windows of
         ``mem_tokens`` frames.  ``pool.push(frames, streams)`` takes n frames for any streams in any mix (frame i belongs to stream
         streams[i]), encodes them once in one packed pass and returns ``{stream: ids}`` for every stream that is due: at least
@@ -673,7 +736,9 @@ class StudentCaptioner(_NativeModule):
         The pool and a caption_stream() of the same model live side by side: opening one does not invalidate the other.  Opening
         another pool, moving the model or loading weights invalidates this one.
         Out of scope: scene-change gates (put one FrameGate per camera in front of ``push``; deciding all cameras' gates in one
-        launch is a later change), ``carry`` / drafts and beams."""
+        launch is a later change), ``carry`` / drafts and beams.
+        no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): one set of rules for every camera's captions,
+        attached again for every pool call; rules per camera are out of scope."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if streams < 1 or streams > 4096:
@@ -681,12 +746,29 @@ class StudentCaptioner(_NativeModule):
         if max_len < 1 or max_len > self.max_text_len:
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
-        return StudentStreamPool(self, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames)
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+        return StudentStreamPool(self, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, co)
 
     @torch.no_grad()
-    def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
+    def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                         suppress_tokens=None) -> torch.Tensor:
         """The same search driven from the host the way the reference writes it (every step recomputes the whole prefix
-        through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests."""
+        through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests.  The constraint
+        arguments (as in beam_search) set every row's banned logits to -inf ahead of the log_softmax."""
+        from .search import banned_tokens, check_constraints
+        cn, cm, sup = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
+        V, sep = self.cfg.vocab_length, self.cfg.sep_token_id
+
+        def rule(logits, prefixes):         # logits [rows, V] of the rows whose ids so far are prefixes [rows, L]
+            if not (cn or cm or sup):
+                return logits
+            logits = logits.clone()
+            for r, pre in enumerate(prefixes.tolist()):
+                cols = banned_tokens(pre, cn, cm, sep, sup, V)
+                if cols:
+                    logits[r, cols] = float("-inf")
+            return logits
+
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
@@ -696,12 +778,13 @@ class StudentCaptioner(_NativeModule):
         if max_len - 1 > self.max_text_len:
             raise ValueError(f"max_len={max_len} exceeds max_text_len+1={self.max_text_len + 1}")
         tgt = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev)
-        logp = torch.log_softmax(self.forward_decoder(tgt, mem)[:, -1], dim=-1)            # model.py:221-225
+        logp = torch.log_softmax(rule(self.forward_decoder(tgt, mem)[:, -1], tgt), dim=-1)  # model.py:221-225
         scores, top = logp.topk(k, dim=-1)
         seqs = torch.cat([tgt.unsqueeze(1).expand(-1, k, -1), top.unsqueeze(-1)], dim=-1)  # [B, k, 2]
         mem_rep = mem.repeat_interleave(k, dim=0)                                          # row b*k + i = beam i of clip b
         for _ in range(2, max_len):                                                        # model.py:230
-            lp = torch.log_softmax(self.forward_decoder(seqs.reshape(B * k, -1), mem_rep)[:, -1], dim=-1)
+            rows = seqs.reshape(B * k, -1)
+            lp = torch.log_softmax(rule(self.forward_decoder(rows, mem_rep)[:, -1], rows), dim=-1)
             ts, ti = lp.view(B, k, -1).topk(k, dim=-1)                                     # each beam's top-k
             cand = (scores.unsqueeze(-1) + ts).view(B, k * k)                              # beam-major, as all_candidates
             sel = cand.sort(dim=1, descending=True).indices[:, :k]                         # model.py:252-256
