@@ -291,6 +291,56 @@ int gitcap_window_greedy(gitcap_t* h, int max_len, int stop, float* visual_out,
 int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float length_penalty, int per_node_beam_size,
                               float* visual_out, int64_t* decoded_out, float* logprobs_out, void* stream);
 
+/* Stream pool: the frame window for several cameras on one handle.  The window above is ONE ring cursor: its B clips receive the same
+ * n frames per push and no caption comes before all of them hold F frames.  Cameras behind scene-change gates of their own admit
+ * frames at different times: each is at its own fill level and ring position.  The pool keeps n_streams independent windows
+ * (streams) of F frames over a ring of the same rows (fp32 ln_post, temporal embedding NOT added), takes frames for any of them in
+ * any mix -- every frame is encoded once -- and captions any subset of them as one ragged batch.
+ * Contract: row r of gitcap_pool_greedy / gitcap_pool_beam_search is bit for bit row r of gitcap_greedy / gitcap_beam_search with
+ * the streams' frame counts attached (gitcap_attach_frame_counts) on the streams' current frames, oldest first, and so, as there,
+ * what the stream's frames give alone: ids, log-probabilities, alternatives, scores.  When every named stream holds the same
+ * number of frames the layout is the dense one and the call takes the dense launches, as equal attached counts do.
+ *   reset   1 <= n_streams <= 4096 with a ring of n_streams * F * tokens_per_frame * enc_width * 4 bytes <= 8 GiB (3.6 MB per stream
+ *           at F = 6 on GIT-base); 1 <= F <= max_frames, F <= 255 (and <= num_frames when num_frames > 0).  Allocates the ring and
+ *           three int32 tables of max_batch * max_frames entries (or, for the sizes of the last reset, reuses them) and empties every
+ *           stream.  n_streams = 0 releases all of it.  A set-up step: a change of sizes waits for the device.  The pool is state of
+ *           its own: gitcap_window_* neither read nor change it, nor the pool calls the window; a handle that never resets a pool
+ *           allocates nothing and runs exactly the launches it ran before.
+ *   push    frames: device fp32 [n][3][S][S], 16-byte aligned (_raw: uint8 BGR [n][H][W][3]); stream_ids: HOST int32 [n]: frame i
+ *           goes to stream stream_ids[i] behind that stream's earlier frames, this push's earlier ones included.  1 <= n <=
+ *           max_batch * max_frames, and a stream gets at most F frames in one push (more would write one ring frame twice in one
+ *           launch: push twice).  The ids are checked on the host before anything is enqueued; a refused push changes nothing.
+ *           Work: the encoder pass of n one-frame clips (the ragged path's, without the temporal add) and one scatter launch.  Like
+ *           a window push it writes neither slot 0's image K/V nor the text cache.
+ *   greedy / beam_search   stream_ids: HOST int32 [B], 1 <= B <= min(max_batch, 256), distinct; decoder row r is stream
+ *           stream_ids[r], in the caller's order, and sees its last n_r = min(frames pushed, F) frames; the named streams hold at
+ *           most max_batch * max_frames frames together.  frames_out (host int32 [B], nullable) = n_r.  The other arguments and the
+ *           outputs as gitcap_window_greedy / gitcap_window_beam_search without visual_out.  Work: one assemble launch (each frame's
+ *           temporal embedding at its position in its OWN clip), the image prefix, the token loop.  Attachments: what the window
+ *           calls take (token log-probabilities, top-k alternatives, prompt, constraints; search options and sampling); attached
+ *           frame counts are refused (and consumed) with the window calls' message.  There is no draft form, no visual_out, no
+ *           attention map and no _submit form of the pool calls.
+ *   drop    empties one stream (a camera that reconnected); the others are untouched.
+ *   counts  host int32 [n_streams]: the frames each stream holds, 0 .. F.
+ * Pushes and pool calls may be issued on different streams (two events order a push behind the last pool call's image prefix and
+ * the last push, and a pool call behind the last push); pushes of the pool and of the window, which share the encoder workspace,
+ * wait for each other's events too.  The two page-locked tables are reused behind an event each.
+ * Errors: GITCAP_ERR_ARG for a null handle or pointer, misaligned frames, sizes outside the bounds above, a stream id outside
+ * [0, n_streams), more than F frames for one stream in one push, a stream named twice in a call, attached frame counts, and the
+ * checks of gitcap_greedy / gitcap_beam_search; GITCAP_ERR_STATE for a call before any reset (or after the release), a named stream
+ * that holds no frame (nothing is launched) and weights not finalized; GITCAP_ERR_EXCHANGE as for the window: every stream is
+ * emptied and the error is returned once -- push again.  Workspace: gitcap_workspace_bytes counts the ring and the tables while they
+ * are allocated.  gitcap_abi_version is unchanged: these are new symbols only. */
+int gitcap_pool_reset(gitcap_t* h, int n_streams, int F);
+int gitcap_pool_push(gitcap_t* h, const float* frames, const int32_t* stream_ids, int n, void* stream);
+int gitcap_pool_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, const int32_t* stream_ids, int n, int H, int W, void* stream);
+int gitcap_pool_greedy(gitcap_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out,
+                       int32_t* frames_out, void* stream);
+int gitcap_pool_beam_search(gitcap_t* h, const int32_t* stream_ids, int B, int beams, int max_steps, float length_penalty,
+                            int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream);
+int gitcap_pool_drop(gitcap_t* h, int stream_id);
+int gitcap_pool_counts(const gitcap_t* h, int32_t* counts_out);
+
 /* Greedy decoding that verifies a draft caption in one pass, accepted row by row (the teacher's counterpart of
  * gitcap_student_greedy_draft; the reference has none).  gitcap_greedy_draft = gitcap_greedy, gitcap_window_greedy_draft =
  * gitcap_window_greedy: *steps_out, ids_out[b][0 .. *steps_out] and the attached log-probabilities of those steps are bit for bit
@@ -962,7 +1012,24 @@ int gitcap_dbg_txt_block_varlen(const gitcap_dbg_txt_block_args* a, const int32_
  *                  pos[frame] = the frame's index inside its clip; pos_cap = the entries pos holds (>= the sum of the counts).
  *   ragged_temporal: row r of out bf16 [frames * N][D] = ln[r] + temporal[pos[r / N]], vis (nullable) the fp32 sum; pos is read back
  *                  first: an entry outside [0, temporal_rows) is refused.
- *   gather_hidden: out[b][e][s][:] = s < S_img ? img[e][b * S_img + s][:] : txt[e][b * T + s - S_img][:], e < n_entries, fp32 rows of D;
+ *   pool_plan:     touches no device.  The stream pool's host plan (csrc/host_logic.h: pool_plan) on n_streams cursors of F slots,
+ *                  heads / counts HOST int32 [n_streams] (in and out: the push advances them).  First the push: frame i of push_ids
+ *                  [n_push] -> ring frame dst[i] = stream * F + slot.  Then the call on the cursors behind it: row r = stream
+ *                  cap_ids[r] [B]; src / pos [sum of the rows' counts] = each packed frame's ring frame and index inside its own
+ *                  clip, off / len [B] = each row's first packed frame and frame count; out3 = {packed frames, longest row, dense}.
+ *                  n_push = 0 / B = 0 leave a half out (its pointers may be NULL).  GITCAP_ERR_ARG: a stream id out of range, more
+ *                  than F frames for one stream, a stream named twice; GITCAP_ERR_STATE: a named stream holds nothing.  A refused
+ *                  plan writes nothing.
+ *   pool_scatter:  frame i of stage fp32 [frames][N][D] -> ring frame dst[i] of ring [ring_frames][N][D]; no other row is written.
+ *                  dst (device int32 [frames]) is read back first: an entry outside [0, ring_frames) or one that repeats is refused.
+ *   pool_assemble: row (g, tok) of out bf16 [frames * N][D] = ring[src[g]][tok] + temporal[pos[g]] (temporal nullable: no add, pos
+ *                  unused); src / pos (device int32 [frames]) are read back first and checked against ring_frames / temporal_rows. */
+int gitcap_dbg_pool_plan(int n_streams, int F, int32_t* heads, int32_t* counts, const int32_t* push_ids, int n_push, int32_t* dst,
+                         const int32_t* cap_ids, int B, int32_t* src, int32_t* pos, int32_t* off, int32_t* len, int32_t* out3);
+int gitcap_dbg_pool_scatter(const float* stage, float* ring, int ring_frames, const int32_t* dst, int frames, int N, int D, void* stream);
+int gitcap_dbg_pool_assemble(const float* ring, int ring_frames, const float* temporal, int temporal_rows, const int32_t* src,
+                             const int32_t* pos, void* out, int frames, int N, int D, void* stream);
+/*   gather_hidden: out[b][e][s][:] = s < S_img ? img[e][b * S_img + s][:] : txt[e][b * T + s - S_img][:], e < n_entries, fp32 rows of D;
  *                  entry e of img / txt starts e * the entry stride (in floats, % 4 == 0) behind the first.  D % 4 == 0.
  *   gather_txt_rows: dst[l][r][t][:] = src[l][src_rows[r]][t][:], t < t_len, l < layers, bf16 rows of `width`, rows [.][Tmax][width],
  *                  layers layer_stride elements apart; copied in pieces of 8 elements: t_len * width, Tmax * width and layer_stride

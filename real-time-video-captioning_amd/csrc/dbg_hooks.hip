@@ -777,6 +777,67 @@ int gitcap_dbg_ragged_temporal(const float* ln, const float* temporal, int tempo
     return dbg_rc(launch_ragged_temporal(ln, temporal, pos, (bf16_t*)out, vis, frames, N, D, (hipStream_t)stream));
 }
 
+// the stream pool's host plan on cursors given as heads / counts (touches no device; a refused plan writes nothing)
+int gitcap_dbg_pool_plan(int n_streams, int F, int32_t* heads, int32_t* counts, const int32_t* push_ids, int n_push, int32_t* dst,
+                         const int32_t* cap_ids, int B, int32_t* src, int32_t* pos, int32_t* off, int32_t* len, int32_t* out3) {
+    if (n_streams < 1 || n_streams > 4096 || F < 1 || F > 255 || !heads || !counts || n_push < 0 || B < 0 || n_push > (1 << 20) || B > n_streams ||
+        (n_push > 0 && (!push_ids || !dst)) || (B > 0 && (!cap_ids || !src || !pos || !off || !len)) || !out3)
+        return GITCAP_ERR_ARG;
+    std::vector<RingCursor> cur((size_t)n_streams);
+    for (int i = 0; i < n_streams; ++i) {
+        if (heads[i] < 0 || heads[i] >= F || counts[i] < 0 || counts[i] > F) return GITCAP_ERR_ARG;
+        cur[(size_t)i].slots = F; cur[(size_t)i].head = heads[i]; cur[(size_t)i].count = counts[i];
+    }
+    std::vector<int32_t> d((size_t)n_push), sp((size_t)B * F * 2), ol((size_t)B * 2);
+    PoolPlan plan;
+    int bad = -1;
+    const int why = pool_plan(cur, push_ids, n_push, d.data(), cap_ids, B, sp.data(), sp.data() + (size_t)B * F, ol.data(), ol.data() + B, &plan, &bad);
+    if (why) return why == POOL_PLAN_EMPTY ? GITCAP_ERR_STATE : GITCAP_ERR_ARG;
+    for (int i = 0; i < n_streams; ++i) { heads[i] = cur[(size_t)i].head; counts[i] = cur[(size_t)i].count; }
+    for (int i = 0; i < n_push; ++i) dst[i] = d[(size_t)i];
+    for (int g = 0; g < plan.total; ++g) { src[g] = sp[(size_t)g]; pos[g] = sp[(size_t)B * F + g]; }
+    for (int r = 0; r < B; ++r) { off[r] = ol[(size_t)r]; len[r] = ol[(size_t)B + r]; }
+    out3[0] = plan.total; out3[1] = plan.maxn; out3[2] = plan.dense ? 1 : 0;
+    return 0;
+}
+
+// a device int32 table read back (the call synchronises `stream`): false when it cannot be read or an entry is outside [0, limit)
+static bool dbg_table_ok(const int32_t* tab, int n, int limit, void* stream, std::vector<int32_t>& host, int* rc) {
+    host.resize((size_t)n);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(host.data(), tab, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        *rc = GITCAP_ERR_HIP;
+        return false;
+    }
+    *rc = GITCAP_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (host[(size_t)i] < 0 || host[(size_t)i] >= limit) return false;
+    return true;
+}
+
+int gitcap_dbg_pool_scatter(const float* stage, float* ring, int ring_frames, const int32_t* dst, int frames, int N, int D, void* stream) {
+    if (!stage || !ring || !dst || ring_frames <= 0 || frames <= 0 || frames > ring_frames || !al(stage, 16) || !al(ring, 16) || !al(dst, 4))
+        return GITCAP_ERR_ARG;
+    std::vector<int32_t> hd;
+    int rc = 0;
+    if (!dbg_table_ok(dst, frames, ring_frames, stream, hd, &rc)) return rc;
+    std::vector<char> seen((size_t)ring_frames, 0);
+    for (int32_t d : hd)
+        if (seen[(size_t)d]++) return GITCAP_ERR_ARG;        // one writer per ring frame
+    return dbg_rc(launch_pool_scatter(PoolScatterArgs{stage, ring, dst, frames, N, D}, (hipStream_t)stream));
+}
+
+int gitcap_dbg_pool_assemble(const float* ring, int ring_frames, const float* temporal, int temporal_rows, const int32_t* src,
+                             const int32_t* pos, void* out, int frames, int N, int D, void* stream) {
+    if (!ring || !src || !out || ring_frames <= 0 || frames <= 0 || (temporal && (!pos || temporal_rows <= 0)) || !al(ring, 16) ||
+        !al(temporal, 16) || !al(src, 4) || !al(pos, 4) || !al(out, 8))
+        return GITCAP_ERR_ARG;
+    std::vector<int32_t> ht;
+    int rc = 0;
+    if (!dbg_table_ok(src, frames, ring_frames, stream, ht, &rc)) return rc;
+    if (temporal && !dbg_table_ok(pos, frames, temporal_rows, stream, ht, &rc)) return rc;
+    return dbg_rc(launch_pool_assemble(PoolAssembleArgs{ring, temporal, src, pos, (bf16_t*)out, frames, N, D}, (hipStream_t)stream));
+}
+
 // the entry strides are in floats; rows are copied 16 bytes at a time
 int gitcap_dbg_gather_hidden(const float* img, const float* txt, float* out, int n_entries, int B, int S_img, int T, int D,
                              int64_t img_entry_stride, int64_t txt_entry_stride, void* stream) {

@@ -196,6 +196,19 @@ struct gitcap : HandleCore {
     RingCursor win;
     RingOrder win_order;
 
+    // Stream pool (gitcap_pool_reset / _push / _greedy / _beam_search), allocated by pool_reset and state of its own beside the
+    // window: pool_ring = the fp32 ln_post rows (no temporal embedding) of pool_S independent streams, [pool_S][F][N][Dv]; pool (one
+    // RingCursor per stream) = where a stream's next frame goes and how many it holds.  pool_tab (device int32 [3][pool_cap]): the
+    // ring frame of each packed frame of one push, then src / pos of each packed frame of one pool call (host_logic.h: pool_plan),
+    // filled from the page-locked pool_push_host / pool_call_host behind an event each.  pool_order: win_order's discipline.
+    float* pool_ring = nullptr;
+    int32_t *pool_tab = nullptr, *pool_push_host = nullptr, *pool_call_host = nullptr;
+    hipEvent_t pool_push_ev = nullptr, pool_call_ev = nullptr;
+    int pool_S = 0, pool_F = 0, pool_cap = 0;
+    int64_t pool_bytes = 0;
+    std::vector<RingCursor> pool;
+    RingOrder pool_order;
+
     // instrumentation (bench.py): HIP-event brackets per kernel class, on the launch stream
     bool prof_on = false;
     struct ProfRec { hipEvent_t a, b; double flops, bytes; };
@@ -231,6 +244,19 @@ std::atomic<int> g_tiny_tiles{getenv("GITCAP_GEMM_TINY_TILES") ? atoi(getenv("GI
 std::atomic<unsigned> g_ln_spin_limit{0};
 
 void select_slot(gitcap* h, int i) { h->cur_slot = i; }
+
+// the stream pool's buffers (the caller has made sure nothing in flight uses them); the events stay for the next reset
+void pool_free(gitcap* h) {
+    if (h->pool_ring) (void)hipFree(h->pool_ring);
+    if (h->pool_tab) (void)hipFree(h->pool_tab);
+    if (h->pool_push_host) (void)hipHostFree(h->pool_push_host);
+    if (h->pool_call_host) (void)hipHostFree(h->pool_call_host);
+    h->pool_ring = nullptr;
+    h->pool_tab = h->pool_push_host = h->pool_call_host = nullptr;
+    h->pool_bytes = 0;
+    h->pool_S = h->pool_F = h->pool_cap = 0;
+    h->pool.clear();
+}
 gitcap::Slot& cur(gitcap* h) { return h->slots[h->cur_slot]; }      // the selected slot: every use of slot state goes through here
 
 // Synchronous entry points (slot 0, caller's stream) share the image-row workspace with the submissions that
@@ -258,6 +284,7 @@ int poll_exchange(gitcap* h) {
     *(volatile unsigned*)h->ln_fail = 0;
     if (h->ln_cnt) (void)hipMemset(h->ln_cnt, 0, h->ln_cnt_words * sizeof(unsigned));
     h->win.clear();         // the frame window's rows may be undefined too: it is emptied, the caller pushes its frames again
+    for (RingCursor& c : h->pool) c.reset(h->pool_F);       // and so is every stream of the pool
     return fail(h, GITCAP_ERR_EXCHANGE, "a GEMM + LayerNorm launch timed out waiting for its sibling tiles (CUs held by another "
                 "process or a CU-masked stream?): results since the last call are undefined -- re-run them; this handle now uses "
                 "separate LayerNorm launches");
@@ -942,6 +969,10 @@ void gitcap_destroy(gitcap_t* h) {
     if (h->s_enc) (void)hipStreamDestroy(h->s_enc);
     h->win_order.destroy();
     if (h->win_ring) (void)hipFree(h->win_ring);
+    pool_free(h);
+    if (h->pool_push_ev) (void)hipEventDestroy(h->pool_push_ev);
+    if (h->pool_call_ev) (void)hipEventDestroy(h->pool_call_ev);
+    h->pool_order.destroy();
     free_allocs(*h);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
     if (h->acc_host) (void)hipHostFree(h->acc_host);
@@ -1704,6 +1735,7 @@ static int window_push(gitcap* h, FrameSrc src, int B, int n, hipStream_t s) {
     select_slot(h, 0);
     HIP_OK(h, join_async(h, s));
     HIP_OK(h, h->win_order.before_push(s));
+    HIP_OK(h, h->pool_order.before_push(s));        // (the pool's pushes and calls use the same encoder workspace; nothing without a pool)
     // staging: the q|k|v buffer of the image rows (bf16 [Mi][3 Dv], 1.5x the bytes of fp32 [Mi][Dv]) is dead once the last block's
     // attention has read it, and only the final FC2 + ln_post launch and the scatter run after that
     float* stage = (float*)h->qkv;
@@ -1790,6 +1822,202 @@ int gitcap_window_beam_search(gitcap_t* h, int beams, int max_steps, float lengt
 }
 
 // first use by gitcap_attach_token_logprobs or gitcap_score: the third head partial beside amax_val, one buffer per slot
+// ---- stream pool ---------------------------------------------------------------------------------------------------------------
+// The window above is ONE cursor: its clips advance in lockstep.  The pool keeps one cursor per stream over a ring of the same
+// rows; a push encodes its frames as one packed pass of one-frame clips (the ragged path's encoder pass) and scatters them to ring
+// frames the host planned; a pool call assembles the named streams' frames, oldest first, PACKED -- the layout of
+// gitcap_attach_frame_counts -- and runs the image prefix and the token loop of that call.
+
+int gitcap_pool_reset(gitcap_t* h, int n_streams, int F) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "pool_reset: null handle");
+    REFUSE_FC(h, "pool_reset");
+    GUARD(h);
+    if (n_streams < 0 || n_streams > 4096) return fail(h, GITCAP_ERR_ARG, "pool_reset: n_streams outside 0..4096");
+    if (n_streams > 0 && (F < 1 || F > 255 || F > h->c.max_frames || (h->c.num_frames > 0 && F > h->c.num_frames)))
+        return fail(h, GITCAP_ERR_ARG, "pool_reset: F outside the sizes the handle was created for");
+    const int64_t ring_bytes = n_streams > 0 ? (int64_t)n_streams * F * h->N * h->Dv * 4 : 0;
+    if (ring_bytes > ((int64_t)8 << 30)) return fail(h, GITCAP_ERR_ARG, "pool_reset: the ring (n_streams * F * tokens * enc_width * 4 bytes) would exceed 8 GiB");
+    if (n_streams > 0 && !h->finalized) return fail(h, GITCAP_ERR_STATE, "pool_reset: weights not finalized");
+    if (h->pool_ring && (n_streams != h->pool_S || F != h->pool_F)) {
+        HIP_OK(h, hipDeviceSynchronize());          // pushes or pool calls in flight may still use the buffers
+        pool_free(h);
+    }
+    if (n_streams == 0) return 0;
+    if (!h->pool_ring) {
+        const size_t cap = (size_t)h->c.max_batch * h->c.max_frames;
+        HIP_OK(h, h->pool_order.ensure());
+        if (!h->pool_push_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_push_ev, hipEventDisableTiming));
+        if (!h->pool_call_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_call_ev, hipEventDisableTiming));
+        hipError_t e = hipMalloc((void**)&h->pool_ring, (size_t)ring_bytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->pool_tab, 3 * cap * sizeof(int32_t));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_push_host, cap * sizeof(int32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_call_host, 2 * cap * sizeof(int32_t), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            pool_free(h);
+            return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc stream pool: ") + hipGetErrorString(e));
+        }
+        h->pool_bytes = ring_bytes + (int64_t)(3 * cap * sizeof(int32_t));
+        h->pool_S = n_streams; h->pool_F = F; h->pool_cap = (int)cap;
+        h->pool.resize((size_t)n_streams);
+    }
+    for (RingCursor& c : h->pool) c.reset(F);
+    return 0;
+}
+
+// the message of a plan the host refused (host_logic.h: pool_plan); unit = "frame" (a push) or "row" (a pool call)
+static std::string pool_refused(const gitcap* h, const char* who, const char* unit, int why, int bad, int32_t id) {
+    const std::string head = std::string(who) + ": " + unit + " " + std::to_string(bad);
+    switch (why) {
+        case POOL_PLAN_BAD_ID: return head + " names stream " + std::to_string(id) + ", outside [0, " + std::to_string(h->pool_S) + ")";
+        case POOL_PLAN_OVER: return head + " is more than F = " + std::to_string(h->pool_F) + " for stream " + std::to_string(id) + " in one push";
+        case POOL_PLAN_TWICE: return std::string(who) + ": stream " + std::to_string(id) + " is named twice";
+        default: return std::string(who) + ": stream " + std::to_string(id) + " holds no frame";
+    }
+}
+
+// encode the n frames as n one-frame clips (no temporal add) and copy each to the ring frame the plan gave it
+static int pool_push(gitcap* h, const char* who, FrameSrc src, const int32_t* stream_ids, int n, hipStream_t s) {
+    REFUSE_FC(h, who);
+    const std::string w(who);
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_pool_reset first)");
+    if (!stream_ids) return fail(h, GITCAP_ERR_ARG, w + ": null stream_ids");
+    if (n < 1 || n > h->pool_cap) return fail(h, GITCAP_ERR_ARG, w + ": n outside [1, max_batch * max_frames = " + std::to_string(h->pool_cap) + "]");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "weights not finalized");
+    if (!src.u8 && !src.f32) return fail(h, GITCAP_ERR_ARG, w + ": null frames");
+    if (src.u8 ? (src.H <= 0 || src.W <= 0 || (int64_t)n * src.H * src.W * 3 > ((int64_t)1 << 40)) : ((uintptr_t)src.f32 & 15) != 0)
+        return fail(h, GITCAP_ERR_ARG, w + ": empty or oversized camera frames, or fp32 frames not 16-byte aligned");
+    std::vector<RingCursor> after = h->pool;
+    std::vector<int32_t> dst((size_t)n);
+    PoolPlan plan;
+    int bad = -1;
+    if (const int why = pool_plan(after, stream_ids, n, dst.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, &plan, &bad))
+        return fail(h, GITCAP_ERR_ARG, pool_refused(h, who, "frame", why, bad, stream_ids[bad]));
+    select_slot(h, 0);
+    HIP_OK(h, hipEventSynchronize(h->pool_push_ev));        // the previous push's transfer has read the page-locked table
+    memcpy(h->pool_push_host, dst.data(), (size_t)n * sizeof(int32_t));
+    HIP_OK(h, join_async(h, s));
+    HIP_OK(h, h->pool_order.before_push(s));
+    HIP_OK(h, h->win_order.before_push(s));         // (the window's pushes and calls use the same encoder workspace)
+    // From here on ring frames may be half written: a failure empties the streams this push names.
+    auto enqueue = [&]() -> int {
+        HIP_OK(h, hipMemcpyAsync(h->pool_tab, h->pool_push_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_OK(h, hipEventRecord(h->pool_push_ev, s));
+        float* stage = (float*)h->qkv;              // window_push's staging: dead behind the last block's attention
+        if (int rc = encode_frames(h, src, n, 1, stage, nullptr, false, s)) return rc;
+        ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, 8.0 * n * (double)h->N * h->Dv);
+        HIP_OK(h, launch_pool_scatter(PoolScatterArgs{stage, h->pool_ring, h->pool_tab, n, h->N, h->Dv}, s));
+        return 0;
+    };
+    int rc = enqueue();
+    if (!rc) {
+        const hipError_t e = h->pool_order.after_push(s);
+        if (e != hipSuccess) rc = fail(h, GITCAP_ERR_HIP, std::string("pool push: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        for (int i = 0; i < n; ++i) h->pool[(size_t)stream_ids[i]].reset(h->pool_F);
+        return rc;
+    }
+    h->pool.swap(after);
+    return 0;
+}
+
+int gitcap_pool_push(gitcap_t* h, const float* frames, const int32_t* stream_ids, int n, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "pool_push: null handle");
+    GUARD(h);
+    POLL(h);
+    return pool_push(h, "pool_push", FrameSrc{frames, nullptr, 0, 0}, stream_ids, n, (hipStream_t)stream);
+}
+
+int gitcap_pool_push_raw(gitcap_t* h, const uint8_t* frames_hwc_bgr, const int32_t* stream_ids, int n, int H, int W, void* stream) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "pool_push_raw: null handle");
+    GUARD(h);
+    POLL(h);
+    if (!frames_hwc_bgr) return fail(h, GITCAP_ERR_ARG, "pool_push_raw: null frames");
+    return pool_push(h, "pool_push_raw", FrameSrc{nullptr, frames_hwc_bgr, H, W}, stream_ids, n, (hipStream_t)stream);
+}
+
+// the named streams' frames -> decoder input -> image prefix on slot 0; frames_out (host, nullable) = the frames each row saw
+static int pool_prefix(gitcap* h, const char* who, const int32_t* stream_ids, int B, int32_t* frames_out, hipStream_t s) {
+    const std::string w(who);
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_pool_reset first)");
+    if (!stream_ids || B < 1 || B > h->c.max_batch || B > 256) return fail(h, GITCAP_ERR_ARG, w + ": null stream_ids, or B outside [1, min(max_batch, 256)]");
+    const int N = h->N, cap = h->pool_cap;
+    std::vector<RingCursor> cursors = h->pool;
+    std::vector<int32_t> tab((size_t)B * h->pool_F * 2 + 2 * (size_t)B);
+    int32_t *src = tab.data(), *pos = src + (size_t)B * h->pool_F, *off = pos + (size_t)B * h->pool_F, *len = off + B;
+    PoolPlan plan;
+    int bad = -1;
+    if (const int why = pool_plan(cursors, nullptr, 0, nullptr, stream_ids, B, src, pos, off, len, &plan, &bad))
+        return fail(h, why == POOL_PLAN_EMPTY ? GITCAP_ERR_STATE : GITCAP_ERR_ARG, pool_refused(h, who, "row", why, bad, stream_ids[bad]));
+    if (plan.total > cap) return fail(h, GITCAP_ERR_ARG, w + ": the named streams hold more than max_batch * max_frames frames");
+    select_slot(h, 0);
+    HIP_OK(h, hipEventSynchronize(h->pool_call_ev));        // the previous call's transfer has read the page-locked table
+    memcpy(h->pool_call_host, src, (size_t)plan.total * sizeof(int32_t));
+    memcpy(h->pool_call_host + cap, pos, (size_t)plan.total * sizeof(int32_t));
+    HIP_OK(h, join_async(h, s));
+    HIP_OK(h, h->pool_order.before_read(s));
+    cur(h).have = false;
+    int32_t *d_src = h->pool_tab + cap, *d_pos = h->pool_tab + 2 * (size_t)cap;
+    HIP_OK(h, hipMemcpyAsync(d_src, h->pool_call_host, (size_t)plan.total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(d_pos, h->pool_call_host + cap, (size_t)plan.total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(h, hipEventRecord(h->pool_call_ev, s));
+    {
+        ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, (double)plan.total * N * h->Dv * (4.0 + 2.0));
+        HIP_OK(h, launch_pool_assemble(PoolAssembleArgs{h->pool_ring, h->c.num_frames > 0 ? h->temporal : nullptr, d_src, d_pos, h->hb,
+                                                        plan.total, N, h->Dv}, s));
+    }
+    int rc;
+    if (plan.dense) {
+        rc = image_prefix(h, B, plan.maxn * N, s);          // equal counts: the dense layout [B][n][N][Dv], launch for launch
+    } else {
+        RaggedCounts& fc = h->call.fc;                       // (image_prefix reads the counts; the entry's CallScope empties them)
+        fc.B = B;
+        for (int r = 0; r < B; ++r) fc.n[r] = (unsigned char)len[r];
+        gitcap::Slot& sl = cur(h);
+        HIP_OK(h, launch_ragged_tables(fc, N, sl.off, sl.len, sl.fpos, s));
+        rc = image_prefix(h, B, plan.maxn * N, s, plan.total * N);
+    }
+    if (rc) return rc;
+    HIP_OK(h, h->pool_order.after_read(s));
+    if (frames_out)
+        for (int r = 0; r < B; ++r) frames_out[r] = len[r];
+    return 0;
+}
+
+int gitcap_pool_greedy(gitcap_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out,
+                       int32_t* frames_out, void* stream) {
+    return greedy_entry(h, true, "pool_greedy: null handle", TAKE_GREEDY, OPT_FC, max_len, stop, ids_out, [&]() -> int {
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc = pool_prefix(h, "pool_greedy", stream_ids, B, frames_out, s)) return rc;
+        return greedy_text_loop(h, B, max_len, stop, ids_out, steps_out, s);
+    });
+}
+
+int gitcap_pool_beam_search(gitcap_t* h, const int32_t* stream_ids, int B, int beams, int max_steps, float length_penalty,
+                            int per_node_beam_size, int64_t* decoded_out, float* logprobs_out, void* stream) {
+    return beam_entry(h, true, "pool_beam_search: null handle", TAKE_BEAM, OPT_FC, beams, max_steps, per_node_beam_size, decoded_out, logprobs_out, [&]() -> int {
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc = pool_prefix(h, "pool_beam_search", stream_ids, B, nullptr, s)) return rc;
+        return beam_loop(h, B, beams, max_steps, length_penalty, per_node_beam_size, decoded_out, logprobs_out, nullptr, s);
+    });
+}
+
+int gitcap_pool_drop(gitcap_t* h, int stream_id) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "pool_drop: null handle");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "pool_drop: no pool (gitcap_pool_reset first)");
+    if (stream_id < 0 || stream_id >= h->pool_S) return fail(h, GITCAP_ERR_ARG, "pool_drop: stream outside the pool");
+    h->pool[(size_t)stream_id].reset(h->pool_F);     // (what is in flight was enqueued with the old cursor; pool_order orders the next push)
+    return 0;
+}
+
+int gitcap_pool_counts(const gitcap_t* h, int32_t* counts_out) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "pool_counts: null handle");
+    if (!counts_out) return fail(h, GITCAP_ERR_ARG, "pool_counts: null counts_out");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "pool_counts: no pool (gitcap_pool_reset first)");
+    for (int i = 0; i < h->pool_S; ++i) counts_out[i] = h->pool[(size_t)i].count;
+    return 0;
+}
+
 static int ensure_amax_sum(gitcap* h) {
     if (h->slots[0].amax_sum) return 0;
     for (auto& sl : h->slots)
@@ -2291,7 +2519,7 @@ int gitcap_weight_bytes(const gitcap_t* h, int64_t* bytes) {
 
 int gitcap_workspace_bytes(const gitcap_t* h, int64_t* bytes) {
     if (!h || !bytes) return GITCAP_ERR_ARG;
-    *bytes = h->ws_bytes + h->win_bytes;
+    *bytes = h->ws_bytes + h->win_bytes + h->pool_bytes;
     return 0;
 }
 

@@ -192,6 +192,44 @@ inline void pool_push_commit(std::vector<RingCursor>& cur, const int32_t* ids, i
     for (int i = 0; i < n; ++i) cur[(size_t)ids[i]].push(1);
 }
 
+// The teacher's stream pool (gitcap_pool_*): the ring holds FRAMES (ring frame = stream * slots + slot), and one plan maps the
+// cursors to every table a push and a pool call need.  First the push: frame i of `push_ids` [n_push] goes to ring frame dst[i]
+// (pool_push_slots' rule) and the cursors advance.  Then the call on the cursors behind that push: decoder row r = stream
+// cap_ids[r], its last len[r] = count frames, oldest first, packed behind row r - 1's from packed frame off[r] on; packed frame g
+// is ring frame src[g] and the pos[g]-th frame of its own clip (the temporal embedding it gets).  total = packed frames, maxn =
+// the longest row's, dense = every row holds the same number (the packed layout is then [B][n] and the call takes the dense
+// launches).  n_push == 0 / B == 0 leave that half out.  A refused plan changes nothing: *bad = the push frame or the row refused.
+enum { POOL_PLAN_OK = 0, POOL_PLAN_BAD_ID = 1, POOL_PLAN_OVER = 2, POOL_PLAN_TWICE = 3, POOL_PLAN_EMPTY = 4 };
+struct PoolPlan { int total = 0, maxn = 0; bool dense = true; };
+inline int pool_plan(std::vector<RingCursor>& cur, const int32_t* push_ids, int n_push, int32_t* dst, const int32_t* cap_ids, int B,
+                     int32_t* src, int32_t* pos, int32_t* off, int32_t* len, PoolPlan* plan, int* bad) {
+    *plan = PoolPlan{};
+    if (n_push > 0)
+        if (const int why = pool_push_slots(cur, push_ids, n_push, dst, bad)) return why;      // (the two enums agree on 0, 1, 2)
+    std::vector<RingCursor> after = cur;
+    if (n_push > 0) pool_push_commit(after, push_ids, n_push);
+    for (int r = 0; r < B; ++r) {
+        const int32_t id = cap_ids[r];
+        *bad = r;
+        if (id < 0 || (size_t)id >= after.size()) return POOL_PLAN_BAD_ID;
+        for (int q = 0; q < r; ++q)
+            if (cap_ids[q] == id) return POOL_PLAN_TWICE;
+        if (after[(size_t)id].count < 1) return POOL_PLAN_EMPTY;
+    }
+    int g = 0;
+    for (int r = 0; r < B; ++r) {
+        const RingCursor& c = after[(size_t)cap_ids[r]];
+        off[r] = g; len[r] = c.count;
+        for (int f = 0; f < c.count; ++f, ++g) { src[g] = cap_ids[r] * c.slots + (c.oldest() + f) % c.slots; pos[g] = f; }
+        plan->maxn = c.count > plan->maxn ? c.count : plan->maxn;
+        plan->dense = plan->dense && c.count == len[0];
+    }
+    plan->total = g;
+    cur.swap(after);
+    *bad = -1;
+    return POOL_PLAN_OK;
+}
+
 // ---- per-call options: the one-shot attachments of gitcap_attach_* --------------------------------------------------------
 // Each setter writes its part of the handle's `pending` record; an entry point states which parts it takes and which it refuses,
 // and the taken parts are the handle's `call` record -- the options of the call whose launches are being issued -- until it returns.

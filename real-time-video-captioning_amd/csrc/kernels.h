@@ -555,6 +555,16 @@ hipError_t launch_ragged_tables(const RaggedCounts& rc, int N, int32_t* off, int
 // window_assemble's add and rounding, i.e. the fused ln_post epilogue's, with the frame's position read from a table
 hipError_t launch_ragged_temporal(const float* ln, const float* temporal, const int32_t* pos, bf16_t* out, float* vis, int frames, int N,
                                   int D, hipStream_t s);
+// Stream pool (gitcap_pool_*): ring = fp32 ln_post rows of n_streams independent windows, [ring_frames][N][D] (no temporal
+// embedding), ring frame = stream * F + slot.  The tables are device int32 the host planned (host_logic.h: pool_plan): every entry
+// in range, no destination twice.
+// scatter: packed frame i of stage [frames][N][D] -> ring frame dst[i]
+struct PoolScatterArgs { const float* stage; float* ring; const int32_t* dst; int frames, N, D; };
+hipError_t launch_pool_scatter(const PoolScatterArgs& a, hipStream_t s);
+// assemble: row (g, tok) of out bf16 [frames * N][D] = ring[src[g]][tok] + temporal[pos[g]] (temporal nullable: no add);
+// window_assemble's / ragged_temporal's add and rounding
+struct PoolAssembleArgs { const float* ring; const float* temporal; const int32_t *src, *pos; bf16_t* out; int frames, N, D; };
+hipError_t launch_pool_assemble(const PoolAssembleArgs& a, hipStream_t s);
 // f32 -> bf16 copy
 hipError_t launch_cast_bf16(const float* in, bf16_t* out, int64_t n, hipStream_t s);
 // e4m3 weight rows [rows][K] (+ per-row power-of-two scale) -> bf16 [rows][K] (exact); K % 16 == 0

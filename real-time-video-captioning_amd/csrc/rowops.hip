@@ -346,6 +346,61 @@ hipError_t launch_ragged_temporal(const float* ln, const float* temporal, const 
     return hipGetLastError();
 }
 
+// ---- stream pool (gitcap_pool_*) -----------------------------------------------------------------
+// The window kernels with the frame's ring slot read from a table the host planned (host_logic.h: pool_plan), so streams at
+// different fill levels and ring positions share one launch.  Both: one wave per row, lane = 4 consecutive columns (16-byte reads
+// and writes of consecutive lanes), grid = rows / 4; every destination row has one writer.
+namespace {
+// push: row (i, tok) of the packed staging rows [frames][N][D] -> ring frame dst[i], a plain copy
+__global__ __launch_bounds__(256) void pool_scatter_kernel(const float* __restrict__ stage, float* __restrict__ ring,
+                                                           const int32_t* __restrict__ dst, int rows, int N, int D) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* s = stage + (size_t)row * D;
+    float* d = ring + ((size_t)dst[row / N] * N + row % N) * D;
+    for (int c = lane * 4; c < D; c += 256) *(f32x4*)(d + c) = *(const f32x4*)(s + c);
+}
+
+// caption: row (g, tok) of the decoder input = bf16(ring[src[g]][tok] + temporal[pos[g]]): ragged_temporal_kernel's lone fp32 add
+// (no contraction) and pack_bf2, i.e. the fused ln_post epilogue's bits; temporal == nullptr (a model without the table): no add
+__global__ __launch_bounds__(256) void pool_assemble_kernel(const float* __restrict__ ring, const float* __restrict__ temporal,
+                                                            const int32_t* __restrict__ src, const int32_t* __restrict__ pos,
+                                                            bf16_t* __restrict__ out, int rows, int N, int D) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int g = row / N;
+    const float* x = ring + ((size_t)src[g] * N + row % N) * D;
+    const float* t = temporal ? temporal + (size_t)pos[g] * D : nullptr;
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 y = *(const f32x4*)(x + c);
+        if (t) y += *(const f32x4*)(t + c);
+        uint2 o;
+        o.x = pack_bf2(y[0], y[1]);
+        o.y = pack_bf2(y[2], y[3]);
+        *(uint2*)(out + (size_t)row * D + c) = o;
+    }
+}
+}  // namespace
+hipError_t launch_pool_scatter(const PoolScatterArgs& a, hipStream_t s) {
+    if (!a.stage || !a.ring || !a.dst || a.frames <= 0 || a.N <= 0 || a.D <= 0 || a.D % 4 || (int64_t)a.frames * a.N > 0x7fffffff)
+        return hipErrorInvalidValue;
+    const int rows = a.frames * a.N;
+    hipLaunchKernelGGL(pool_scatter_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a.stage, a.ring, a.dst, rows, a.N, a.D);
+    return hipGetLastError();
+}
+
+hipError_t launch_pool_assemble(const PoolAssembleArgs& a, hipStream_t s) {
+    if (!a.ring || !a.src || !a.out || (a.temporal && !a.pos) || a.frames <= 0 || a.N <= 0 || a.D <= 0 || a.D % 4 || a.D > 1024 ||
+        (int64_t)a.frames * a.N > 0x7fffffff)
+        return hipErrorInvalidValue;
+    const int rows = a.frames * a.N;
+    hipLaunchKernelGGL(pool_assemble_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a.ring, a.temporal, a.src, a.pos, a.out,
+                       rows, a.N, a.D);
+    return hipGetLastError();
+}
+
 // e4m3 weight panel -> bf16 staging panel for the big-tile GEMMs (16 values per thread: 16-B read, 32-B write)
 namespace {
 __global__ __launch_bounds__(256) void dequant_fp8_kernel(const unsigned char* __restrict__ w8, const float* __restrict__ scale,

@@ -27,4 +27,7 @@ def __getattr__(name):
     if name in ("sample_frames", "caption_videos", "FrameSelection"):
         from . import sampling
         return getattr(sampling, name)
+    if name in ("TeacherStreamPool", "StudentStreamPool"):
+        from . import streampool
+        return getattr(streampool, name)
     raise AttributeError(name)

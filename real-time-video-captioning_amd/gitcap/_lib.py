@@ -120,6 +120,14 @@ SYMBOLS = {
     "gitcap_window_push_raw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gitcap_window_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gitcap_window_beam_search": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the teacher's stream pool (tests/test_teacher_pool*.py)
+    "gitcap_pool_reset": (c_int, [c_void_p, c_int, c_int]),
+    "gitcap_pool_push": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_void_p]),
+    "gitcap_pool_push_raw": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p]),
+    "gitcap_pool_greedy": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    "gitcap_pool_beam_search": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "gitcap_pool_drop": (c_int, [c_void_p, c_int]),
+    "gitcap_pool_counts": (c_int, [c_void_p, POINTER(c_int32)]),
     "gitcap_dbg_enc_tap": (c_int, [c_void_p, c_void_p]),
     "gitcap_host_copy": (c_int, [c_void_p, c_void_p, c_int64]),
     "gitcap_poll_errors": (c_int, [c_void_p]),
@@ -321,6 +329,9 @@ SYMBOLS = {
     "gitcap_dbg_window_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gitcap_dbg_ragged_tables": (c_int, [POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gitcap_dbg_ragged_temporal": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_pool_plan": (c_int, [c_int, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_int, POINTER(c_int32), POINTER(c_int32), c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "gitcap_dbg_pool_scatter": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gitcap_dbg_pool_assemble": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gitcap_dbg_gather_hidden": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p]),
     "gitcap_dbg_gather_txt_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
 }

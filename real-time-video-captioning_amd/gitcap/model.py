@@ -32,6 +32,7 @@ from .framegate import FrameGate
 from . import weights as W
 from ._handle import _NativeModule
 from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
+from .streampool import TeacherStreamPool
 from .window import WindowSchedule
 
 
@@ -571,6 +572,7 @@ class GitCaptioner(_NativeModule):
         self._undelivered = set()                       # waited for, but a future has still to hand out (or re-run) its rows
         self._ring = None                               # _StagingRing, made when the first CPU tensor arrives
         self._window_owner = None                       # token of the one live CaptionStream (the handle has one frame window)
+        self._pool_owner = None                         # token of the live TeacherStreamPool (state of its own beside the window)
         self.last_accepted: Optional[torch.Tensor] = None   # int32 [B]: draft tokens the last greedy_decode(draft=...) accepted per clip
         self._copy_stream = os.environ.get("GITCAP_COPY_STREAM", "caller")  # "caller" | "own" (A/B switch; see _StagingRing)
         self._lib = _lib.load()                         # raises if libgitcap.so is missing
@@ -682,6 +684,7 @@ class GitCaptioner(_NativeModule):
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, *args, **kwargs):
         self._window_owner = None                       # a CaptionStream does not follow the model
+        self._pool_owner = None                         # nor does a TeacherStreamPool
         return super().to(*args, **kwargs)
 
     def cuda(self, device=None):
@@ -707,6 +710,7 @@ class GitCaptioner(_NativeModule):
         return self
 
     def _upload(self, w: Mapping[str, np.ndarray]):
+        self._pool_owner = None                         # the pool's rows came from the old encoder weights
         self._load_tensors((name, w[name]) for name in W.canonical_shapes(self.cfg))
 
     def __reduce__(self):
@@ -1812,6 +1816,59 @@ class GitCaptioner(_NativeModule):
         return CaptionStream(self, batch, window, hop, max_len, mode, beam_size, length_penalty, per_node_beam_size, visual_features, gate,
                              logprobs, num_keep_best, repetition_penalty,
                              sampling, pr, co, carry, top_logprobs)
+
+    def stream_pool(self, streams: int, frames: Optional[int] = None, hop: int = 1, min_frames: int = 1, max_len: int = 20,
+                    stop: Optional[str] = None, beam_size: Optional[int] = None, logprobs: bool = False, top_logprobs: int = 0,
+                    prompt=None, no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None,
+                    length_penalty: float = 0.6, per_node_beam_size: int = 2) -> TeacherStreamPool:
+        """Several live cameras on one model (the multi-camera loop): `streams` independent windows of `frames`
+        frames (default: the model's num_frames).  ``pool.push(frames, streams)`` takes n frames for any streams in any mix (frame i
+        belongs to stream streams[i]) -- uint8 camera frames [n,H,W,3] or transformed fp32 frames [n,3,S,S], on the host or the
+        device --, encodes them once in one packed pass and returns ``{stream: ids}`` for every stream that is due: at least `hop`
+        of its frames have arrived since its last caption and it holds at least `min_frames` frames (1: a caption from a camera's
+        first frame on; `frames`: only full windows).  The due streams are captioned as one ragged batch, in chunks of max_batch
+        (include/gitcap.h: gitcap_pool_*).  A stream's caption is bit for bit greedy_decode(max_len, stop) on a list holding that
+        stream's last frames, cut behind the row's own first SEP under the all_sep rule (not at the batch-wide step count): it
+        does not depend on which other streams were due.  ``logprobs`` / ``top_logprobs=k``: ``pool.last_logprobs[stream]``,
+        ``pool.last_top_ids[stream]`` / ``pool.last_top_logprobs[stream]`` of a stream's latest caption, cut the same way;
+        ``pool.last_frames[stream]`` = the frames it saw.  ``beam_size=k`` (with length_penalty / per_node_beam_size as in infer):
+        a caption is the device search's best hypothesis [max_len] (max_len = infer's max_steps; EOS padded, not cut) and
+        ``pool.last_scores[stream]`` its score, bit for bit infer on a one-clip list of the stream's frames.  prompt (one row of
+        token ids: every stream's captions start from it) and no_repeat_ngram_size / min_length / suppress_tokens (as in
+        greedy_decode / infer) hold for every stream and are attached again for every pool call; per-camera prompts or rules are
+        not part of the pool.  ``pool.caption(streams)`` captions now, ``pool.drop(stream)`` empties one stream,
+        ``pool.counts()`` = frames held per stream.
+        The pool and a caption_stream() of the same model live side by side: opening one does not invalidate the other.  Opening
+        another pool, moving the model or loading weights invalidates this one.
+        Out of scope: scene-change gates (put one FrameGate per camera in front of ``push``), ``carry`` / drafts, visual
+        features and attention maps, pipelined submission."""
+        if not 0 <= int(top_logprobs) <= 32:
+            raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
+        if streams < 1 or streams > 4096:
+            raise ValueError(f"streams={streams} outside 1..4096")
+        window = int(frames or max(1, self.cfg.num_frames))
+        if window < 1 or window > self._frame_limit():
+            raise ValueError(f"frames={window} outside 1..{self._frame_limit()} (max_frames / num_frames)")
+        if max_len < 1 or max_len > self.max_text_len:
+            raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
+        mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
+        beam = None
+        if beam_size is not None:
+            if logprobs or top_logprobs:
+                raise ValueError("logprobs / top_logprobs are for greedy pools (a search carries its own sequence score)")
+            self._check_device_search(beam_size, per_node_beam_size)
+            if beam_size > self.max_beams:
+                raise ValueError(f"beam_size {beam_size} > max_beams={self.max_beams} the handle was created for")
+            if max_len < 2:
+                raise ValueError("a search takes max_len >= 2")
+            beam = (int(beam_size), float(length_penalty), int(per_node_beam_size))
+        pr = None
+        if prompt is not None:          # one row for every stream: max_batch copies, a pool call attaches the rows it needs
+            row = torch.as_tensor(prompt).detach().to("cpu", torch.int64).reshape(-1)
+            pr = self._prompt([row] * self.max_batch, None, self.max_batch, max_len if beam is None else max_len - 1,
+                              "max_len" if beam is None else "max_len - 1")
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, 1 if beam is None else beam[0] * beam[2])
+        return TeacherStreamPool(self, streams, window, hop, max_len, mode, logprobs, top_logprobs, min_frames, (pr, co), beam)
 
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3) -> torch.Tensor:
         """Signature of StudentCandidateV1.beam_search (model.py:189): best sequence per clip

@@ -1,7 +1,9 @@
-"""``StudentStreamPool``: several live cameras on one StudentCaptioner (StudentCaptioner.stream_pool; include/gitcap.h:
-gitcap_student_pool_*).  Every camera (stream) has a window of ``mem_tokens`` frames of its own, at its own fill level and ring
-position; a push takes frames for any streams in any mix, encodes them once, packed, and the streams that are due are captioned
-as one ragged batch."""
+"""Stream pools: several live cameras on one model (StudentCaptioner.stream_pool -> ``StudentStreamPool``, include/gitcap.h:
+gitcap_student_pool_*; GitCaptioner.stream_pool -> ``TeacherStreamPool``, gitcap_pool_*).  Every camera (stream) has a window of
+frames of its own, at its own fill level and ring position; a push takes frames for any streams in any mix, encodes them once,
+packed, and the streams that are due are captioned as one ragged batch.  ``_StreamPool`` holds what the two share -- ownership
+token, schedule, chunks of max_batch, the cut behind a row's own first SEP, the ``last_*`` dicts; the subclasses differ in their
+library calls only."""
 from __future__ import annotations
 
 import ctypes
@@ -19,21 +21,22 @@ def cut_at_sep(row, sep_id: int) -> int:
     return int(hits[0]) + 1 if hits.numel() else row.shape[0] - 1
 
 
-class StudentStreamPool:
+class _StreamPool:
     """``push(frames, streams)`` -> ``{stream: ids}`` for every stream that became due, ``caption(streams)`` for a caption now.  A
-    stream's caption is bit for bit ``greedy_decode`` on a list holding that stream's last (up to mem_tokens) frames, cut behind the
+    stream's caption is bit for bit ``greedy_decode`` on a list holding that stream's last (up to `window`) frames, cut behind the
     row's OWN first SEP when the stop rule is all_sep: it does not depend on which other streams were captioned with it.  After a
     caption ``last_logprobs[stream]`` (logprobs=True), ``last_top_ids[stream]`` / ``last_top_logprobs[stream]`` (top_logprobs=k)
     and ``last_frames[stream]`` (the frames it saw) hold that caption's, cut the same way.
     Scene-change gates are not part of the pool: a caller puts one FrameGate per camera in front of ``push`` and pushes the frames
-    it admits; one launch for all the gates' decisions is left to a later change.  Nor does the pool carry drafts or run beams.
-    ``constraints`` (StudentCaptioner.stream_pool's constraint arguments, or None): one set of rules for every stream, attached
-    again for every pool call."""
+    it admits; one launch for all the gates' decisions is left to a later change.  Nor does a pool carry drafts.
+    A subclass supplies ``_WHAT`` (the name of the window size in messages) and the library's side: _reset_lib, _prepare, _push_lib,
+    _drop_lib, _counts_lib, _caption_lib."""
 
-    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None):
+    _WHAT = "window"
+
+    def __init__(self, model, streams, window, hop, max_len, mode, logprobs, top_logprobs, min_frames):
         self._m = model
-        self._co = constraints
-        self._sched = PoolSchedule(streams, model.cfg.mem_tokens, hop, min_frames)
+        self._sched = PoolSchedule(streams, window, hop, min_frames)
         self._max_len, self._mode = int(max_len), mode
         self._want_lp, self._top_k = bool(logprobs), int(top_logprobs)
         self.last_logprobs, self.last_top_ids, self.last_top_logprobs, self.last_frames = {}, {}, {}, {}
@@ -41,10 +44,101 @@ class StudentStreamPool:
         model._pool_owner = self._token             # the handle has one pool: this object owns it until the next one is opened
         self._reset_lib()
 
-    # ------------------------------------------------------------------ the library's side
     def _check_live(self):
         if self._m._pool_owner is not self._token:
             raise _lib.GitcapError(f"this {type(self).__name__} was invalidated (another stream_pool() was opened, the model was moved or its weights were loaded again)")
+
+    def _last_dicts(self):
+        return (self.last_logprobs, self.last_top_ids, self.last_top_logprobs, self.last_frames)
+
+    def _buffers(self, B):
+        """The outputs of one greedy pool call over B rows -> (ids [B, 1+max_len], log-probs or None, (top ids, top log-probs) or None)"""
+        dev, L = self._m._dev, self._max_len
+        out = torch.empty((B, L + 1), dtype=torch.int64, device=dev)
+        lp = torch.empty((B, L), dtype=torch.float32, device=dev) if self._want_lp else None
+        tk = None
+        if self._top_k:
+            tk = (torch.empty((B, L, self._top_k), dtype=torch.int64, device=dev),
+                  torch.empty((B, L, self._top_k), dtype=torch.float32, device=dev))
+        return out, lp, tk
+
+    # ------------------------------------------------------------------ frames in, captions out
+    def push(self, frames: torch.Tensor, streams) -> dict:
+        """``frames``: n frames (what the pool's model takes: see its stream_pool), on the CPU or the device; ``streams``: n ints,
+        frame i belongs to stream streams[i] and is newer than that stream's earlier frames, this push's included (at most `window`
+        per stream and push, at most max_batch * `window` frames per push).  The frames are encoded once, in one packed pass.
+        -> {stream: ids} for every stream that is due (possibly empty); ids int64 [1 + steps] with CLS first, on the CPU when the
+        frames were."""
+        self._check_live()
+        ids = self._sched.check(streams)
+        if frames.shape[0] != len(ids):
+            raise ValueError(f"{frames.shape[0]} frames for {len(ids)} stream ids")
+        cap = self._m.max_batch * self._sched.window
+        if len(ids) > cap:
+            raise ValueError(f"a push takes at most max_batch * {self._WHAT} = {cap} frames, got {len(ids)}")
+        self._push_lib(self._prepare(frames), ids)
+        return self._caption(self._sched.push(ids), frames.device.type == "cpu")
+
+    def caption(self, streams, to_cpu: bool = False) -> dict:
+        """Caption these streams now, whatever the schedule says -> {stream: ids}.  Every one of them must hold a frame."""
+        self._check_live()
+        ids = [int(s) for s in streams]
+        if len(set(ids)) != len(ids):
+            raise ValueError("a stream is named twice")
+        return self._caption(ids, to_cpu)
+
+    def _caption(self, due, to_cpu: bool) -> dict:
+        out = {}
+        B = self._m.max_batch
+        sep = self._m.cfg.sep_token_id
+        for c0 in range(0, len(due), B):
+            chunk = due[c0:c0 + B]
+            ids, lp, tk, seen = self._caption_lib(chunk)
+            if to_cpu:
+                ids = tuple(t.cpu() for t in ids) if isinstance(ids, tuple) else ids.cpu()       # (a tuple: a search's predictions and scores)
+                lp, tk = None if lp is None else lp.cpu(), None if tk is None else (tk[0].cpu(), tk[1].cpu())
+            self._deliver(out, chunk, ids, lp, tk, seen, to_cpu, sep)
+            self._sched.captioned(chunk)
+        return out
+
+    def _deliver(self, out, chunk, ids, lp, tk, seen, to_cpu, sep):
+        """One chunk's rows into `out` and the last_* dicts, each cut behind its own first SEP under all_sep."""
+        host = ids if to_cpu or self._mode != STOP_ALL_SEP else ids.cpu()
+        for r, s in enumerate(chunk):
+            n = cut_at_sep(host[r], sep) if self._mode == STOP_ALL_SEP else self._max_len
+            out[s] = ids[r, :1 + n]
+            self.last_frames[s] = int(seen[r])
+            if lp is not None:
+                self.last_logprobs[s] = lp[r, :n]
+            if tk is not None:
+                self.last_top_ids[s], self.last_top_logprobs[s] = tk[0][r, :n], tk[1][r, :n]
+
+    def drop(self, stream: int):
+        """Empty one stream (a camera that reconnected); the others keep their frames."""
+        self._check_live()
+        s = int(stream)
+        if not 0 <= s < self._sched.streams:
+            raise ValueError(f"stream {s} outside 0..{self._sched.streams - 1}")
+        self._drop_lib(s)
+        self._sched.drop(s)
+        for d in self._last_dicts():
+            d.pop(s, None)
+
+    def counts(self) -> list:
+        """Frames held per stream, 0..`window` (the library's *_pool_counts)."""
+        self._check_live()
+        return self._counts_lib()
+
+
+class StudentStreamPool(_StreamPool):
+    """The pool of StudentCaptioner.stream_pool: windows of ``mem_tokens`` frames; greedy captions only.  ``constraints``
+    (stream_pool's constraint arguments, or None): one set of rules for every stream, attached again for every pool call."""
+
+    _WHAT = "mem_tokens"
+
+    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None):
+        self._co = constraints
+        super().__init__(model, streams, model.cfg.mem_tokens, hop, max_len, mode, logprobs, top_logprobs, min_frames)
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -66,23 +160,17 @@ class StudentStreamPool:
     def _caption_lib(self, ids):
         """One gitcap_student_pool_greedy on streams `ids` (at most max_batch) -> (ids [B, 1+max_len], log-probs or None, (top ids,
         top log-probs) or None, frames seen per row), on the device."""
-        m, B, L = self._m, len(ids), self._max_len
-        out = torch.empty((B, L + 1), dtype=torch.int64, device=m._dev)
-        lp = torch.empty((B, L), dtype=torch.float32, device=m._dev) if self._want_lp else None
-        tk = None
-        if self._top_k:
-            tk = (torch.empty((B, L, self._top_k), dtype=torch.int64, device=m._dev),
-                  torch.empty((B, L, self._top_k), dtype=torch.float32, device=m._dev))
+        m, B = self._m, len(ids)
+        out, lp, tk = self._buffers(B)
         seen = (ctypes.c_int32 * B)()
         with torch.cuda.device(m._dev):
             m._attach_logprobs(lp, tk)
             if self._co is not None:
                 self._co.attach(m)
-            m._call("gitcap_student_pool_greedy", (ctypes.c_int32 * B)(*ids), B, L, self._mode, _lib.ptr(out), None, seen, m._stream())
+            m._call("gitcap_student_pool_greedy", (ctypes.c_int32 * B)(*ids), B, self._max_len, self._mode, _lib.ptr(out), None, seen, m._stream())
         return out, lp, tk, list(seen)
 
-    # ------------------------------------------------------------------ frames in, captions out
-    def _tokens(self, frames: torch.Tensor) -> torch.Tensor:
+    def _prepare(self, frames: torch.Tensor) -> torch.Tensor:
         """uint8 [n,H,W,3] / fp32 [n,3,S,S] frames, or memory tokens [n,d_model] -> memory tokens [n,d_model] fp32 on the device."""
         m = self._m
         if frames.dtype != torch.uint8 and frames.dim() == 2:
@@ -96,63 +184,111 @@ class StudentStreamPool:
                                    "encoded one at a time on the device")
         return m._encode_packed(frames).contiguous()
 
-    def push(self, frames: torch.Tensor, streams) -> dict:
-        """``frames``: n frames, uint8 camera frames [n,H,W,3], fp32 [n,3,S,S] or memory tokens [n,d_model], on the CPU or the device;
-        ``streams``: n ints, frame i belongs to stream streams[i] and is newer than that stream's earlier frames, this push's
-        included (at most mem_tokens per stream and push, at most max_batch * mem_tokens frames per push).  The frames are encoded
-        once, in one packed pass.  -> {stream: ids} for every stream that is due (possibly empty); ids int64 [1 + steps] with CLS
-        first, on the CPU when the frames were."""
-        self._check_live()
-        ids = self._sched.check(streams)
-        if frames.shape[0] != len(ids):
-            raise ValueError(f"{frames.shape[0]} frames for {len(ids)} stream ids")
-        cap = self._m.max_batch * self._m.cfg.mem_tokens
-        if len(ids) > cap:
-            raise ValueError(f"a push takes at most max_batch * mem_tokens = {cap} frames, got {len(ids)}")
-        self._push_lib(self._tokens(frames), ids)
-        return self._caption(self._sched.push(ids), frames.device.type == "cpu")
 
-    def caption(self, streams, to_cpu: bool = False) -> dict:
-        """Caption these streams now, whatever the schedule says -> {stream: ids}.  Every one of them must hold a frame."""
-        self._check_live()
-        ids = [int(s) for s in streams]
-        if len(set(ids)) != len(ids):
-            raise ValueError("a stream is named twice")
-        return self._caption(ids, to_cpu)
+class TeacherStreamPool(_StreamPool):
+    """The pool of GitCaptioner.stream_pool (include/gitcap.h: gitcap_pool_*): windows of ``frames`` frames over a ring of the
+    encoder's fp32 ln_post rows, so a pushed frame runs the CLIP-ViT once and a caption re-runs only the temporal add, the decoder's
+    image prefix and the token loop.  ``opts`` = (prompt, constraints) as _CallOptions takes them, one set for every stream, attached
+    again for every pool call.  ``beam`` = None (greedy) or (beam_size, length_penalty, per_node_beam_size): a caption is then the
+    search's best hypothesis [max_len] (CLS first, EOS padded, not cut) and ``last_scores[stream]`` its score; log-probabilities and
+    alternatives belong to the greedy pool.
+    A failed statistics exchange (GitcapExchangeTimeout, raised once) leaves the ring's rows undefined: the library empties every
+    stream, and so does the pool -- push the cameras' frames again."""
+
+    _WHAT = "frames"
+
+    def __init__(self, model, streams, window, hop, max_len, mode, logprobs, top_logprobs, min_frames, opts=(None, None), beam=None):
+        self._opts, self._beam = opts, beam
+        if beam is not None:
+            self.last_scores = {}
+        super().__init__(model, streams, window, hop, max_len, mode, logprobs, top_logprobs, min_frames)
+
+    def _last_dicts(self):
+        return super()._last_dicts() + ((self.last_scores,) if self._beam is not None else ())
+
+    def _emptied(self):
+        """The library emptied every stream (a failed exchange): the schedule and the last_* dicts follow."""
+        self._sched.reset()
+        for d in self._last_dicts():
+            d.clear()
+
+    def _reset_lib(self):
+        with torch.cuda.device(self._m._dev):
+            self._m._call("gitcap_pool_reset", self._sched.streams, self._sched.window)
+
+    def _prepare(self, frames: torch.Tensor):
+        """uint8 camera frames [n,H,W,3] or transformed fp32 frames [n,3,S,S], host or device -> (device frames, raw)"""
+        m, S = self._m, self._m.cfg.image_size
+        raw = frames.dtype == torch.uint8
+        if frames.dim() != 4 or (frames.shape[3] != 3 or min(frames.shape[1:3]) < 1 if raw else tuple(frames.shape[1:]) != (3, S, S)):
+            raise ValueError(f"expected frames [n,H,W,3] uint8 or [n,3,{S},{S}] fp32, got {frames.dtype} {tuple(frames.shape)}")
+        return m._to_device(frames), raw
+
+    def _push_lib(self, prepared, ids):
+        m = self._m
+        fr, raw = prepared
+        sid = (ctypes.c_int32 * len(ids))(*ids)
+        m._drain()
+        try:
+            with torch.cuda.device(m._dev):
+                if raw:
+                    m._call("gitcap_pool_push_raw", _lib.ptr(fr), sid, len(ids), fr.shape[1], fr.shape[2], m._stream())
+                else:
+                    m._call("gitcap_pool_push", _lib.ptr(fr), sid, len(ids), m._stream())
+        except _lib.GitcapExchangeTimeout:
+            self._emptied()
+            raise
+
+    def _drop_lib(self, s):
+        self._m._call("gitcap_pool_drop", s)
+
+    def _counts_lib(self):
+        out = (ctypes.c_int32 * self._sched.streams)()
+        self._m._call("gitcap_pool_counts", out)
+        return list(out)
+
+    def _caption_lib(self, ids):
+        """One gitcap_pool_greedy (or _beam_search) on streams `ids` (at most max_batch) -> (ids [B, 1+max_len] or the search's
+        (predictions [B, max_len], scores [B]), log-probs or None, (top ids, top log-probs) or None, frames seen per row)."""
+        from .model import _CallOptions
+        m, B = self._m, len(ids)
+        sid = (ctypes.c_int32 * B)(*ids)
+        prompt, cons = self._opts
+        opts = _CallOptions(m, None if prompt is None else prompt.rows(0, B), cons)
+        m._drain()
+        try:
+            with torch.cuda.device(m._dev):
+                if self._beam is None:
+                    out, lp, tk = self._buffers(B)
+                    seen = (ctypes.c_int32 * B)()
+                    opts.attach(lp, tk)
+                    m._call("gitcap_pool_greedy", sid, B, self._max_len, self._mode, _lib.ptr(out), None, seen, m._stream())
+                    seen = list(seen)
+                else:
+                    k, length_penalty, per_node = self._beam
+                    own, decoded, scores = opts.search_outputs(B, self._max_len)
+                    lp = tk = None
+                    opts.attach()
+                    m._call("gitcap_pool_beam_search", sid, B, k, self._max_len, ctypes.c_float(length_penalty), per_node, _lib.ptr(own[0]),
+                            _lib.ptr(own[1]), m._stream())
+                    out = (decoded, scores)
+                    held = self._counts_lib()
+                    seen = [held[s] for s in ids]
+        except _lib.GitcapExchangeTimeout:
+            self._emptied()
+            raise
+        m._last_memory = None
+        return out, lp, tk, seen
 
     def _caption(self, due, to_cpu: bool) -> dict:
-        out = {}
-        B = self._m.max_batch
-        sep = self._m.cfg.sep_token_id
-        for c0 in range(0, len(due), B):
-            chunk = due[c0:c0 + B]
-            ids, lp, tk, seen = self._caption_lib(chunk)
-            if to_cpu:
-                ids, lp, tk = ids.cpu(), None if lp is None else lp.cpu(), None if tk is None else (tk[0].cpu(), tk[1].cpu())
-            host = ids if to_cpu or self._mode != STOP_ALL_SEP else ids.cpu()
-            for r, s in enumerate(chunk):
-                n = cut_at_sep(host[r], sep) if self._mode == STOP_ALL_SEP else self._max_len
-                out[s] = ids[r, :1 + n]
-                self.last_frames[s] = int(seen[r])
-                if lp is not None:
-                    self.last_logprobs[s] = lp[r, :n]
-                if tk is not None:
-                    self.last_top_ids[s], self.last_top_logprobs[s] = tk[0][r, :n], tk[1][r, :n]
-            self._sched.captioned(chunk)
+        out = super()._caption(due, to_cpu)
+        if to_cpu and due:
+            self._m.poll_errors()           # CPU results are vouched for, as caption_stream's
         return out
 
-    def drop(self, stream: int):
-        """Empty one stream (a camera that reconnected); the others keep their frames."""
-        self._check_live()
-        s = int(stream)
-        if not 0 <= s < self._sched.streams:
-            raise ValueError(f"stream {s} outside 0..{self._sched.streams - 1}")
-        self._drop_lib(s)
-        self._sched.drop(s)
-        for d in (self.last_logprobs, self.last_top_ids, self.last_top_logprobs, self.last_frames):
-            d.pop(s, None)
-
-    def counts(self) -> list:
-        """Frames held per stream, 0..mem_tokens (gitcap_student_pool_counts)."""
-        self._check_live()
-        return self._counts_lib()
+    def _deliver(self, out, chunk, ids, lp, tk, seen, to_cpu, sep):
+        if self._beam is None:
+            return super()._deliver(out, chunk, ids, lp, tk, seen, to_cpu, sep)
+        decoded, scores = ids
+        for r, s in enumerate(chunk):
+            out[s], self.last_scores[s], self.last_frames[s] = decoded[r], scores[r], int(seen[r])
