@@ -494,7 +494,8 @@ int gitcap_dbg_attn_map(const gitcap_dbg_attn_map_args* a, void* stream);
  * their _submit forms, gitcap_window_greedy) or of the beam family (gitcap_beam_search, its _submit / _raw_submit forms,
  * gitcap_window_beam_search), whichever comes first, and is consumed by it whether that call succeeds or is refused; every other
  * entry point leaves it pending; prompt_ids == NULL and lengths == NULL detach.  A pipelined submission captures the two pointers:
- * the buffers stay valid and unchanged until the wait.  The student model takes no prompt.
+ * the buffers stay valid and unchanged until the wait.  The student model takes its prompts through an attachment of its own
+ * (gitcap_student_attach_prompt).
  *   prompt_ids  device int64 [B][ld], CLS at column 0 (the beam family starts every row from the handle's CLS whatever column 0 says).
  *   lengths     device int32 [B]: valid tokens per clip, CLS included, 1 <= lengths[b] <= ld; 1 = no prompt for that clip.
  *   min_len, max_len  the host's minimum and maximum of lengths (launches are planned without a round trip).  The kernels clamp
@@ -758,8 +759,8 @@ int gitcap_dbg_gemm_ln(const void* A, const void* W, const float* bias, const fl
  * FC1 -> GELU -> FC2 as one launch over hidden slices on/off; 8: fragment-major copies of the text-path weights at the next
  * gitcap_finalize_weights on/off; 9: 8-wave workgroups for text-attention launches of more (row, head) units than CUs on/off;
  * 10: the vocabulary head's four-tile workgroups that share the activation rows through LDS on/off; 11: three-wave workgroups
- * that share the slab reduce of the one/two-row prologue on/off; 20: a prompted greedy loop (gitcap_attach_prompt) runs the
- * positions every row's prompt covers as one multi-position pass on/off (off: as forced token steps).  Returns the previous value (< 0: bad key).  The switches are process-wide atomics: a call on another thread sees either value,
+ * that share the slab reduce of the one/two-row prologue on/off; 20: a prompted greedy loop (gitcap_attach_prompt,
+ * gitcap_student_attach_prompt) runs the positions every row's prompt covers as one multi-position pass on/off (off: as forced token steps).  Returns the previous value (< 0: bad key).  The switches are process-wide atomics: a call on another thread sees either value,
  * and either value gives the same bits. */
 int gitcap_dbg_config(int key, int value);
 /* attn_full: qkv [G*S][3*H*64] bf16 -> ctx [G*S][H*64] bf16 */
@@ -1254,6 +1255,54 @@ int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_
  * above 131072 columns; at the consuming call n_suppress + max_len >= vocab_size (greedy) or n_suppress + max_len + k > vocab_size
  * (beam).  Nothing is launched then and the attachment is consumed all the same.  GITCAP_ERR_STATE before the weights are finalized. */
 int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constraints* c);
+/* Prompted decoding on the student: gitcap_attach_prompt for this handle -- the same arguments (prompt_ids device int64 [B][ld] with
+ * CLS at column 0, lengths device int32 [B] = valid tokens per clip, CLS included, 1 = no prompt for that clip; min_len / max_len
+ * the host's minimum and maximum of lengths; NULL / NULL detaches), the same clamp (the kernels clamp lengths[b] to [1, max_len] of
+ * the consuming call, so a mismatch reads nothing outside a table row) and the same treatment of ids outside the vocabulary.
+ * A ONE-SHOT attachment with the life cycle of gitcap_attach_prompt: the next call of the greedy family (gitcap_student_greedy,
+ * _window_greedy, _window_greedy_partial, _pool_greedy) or of the beam family (gitcap_student_beam_search, _window_beam_search)
+ * consumes it, whichever comes first, whether that call succeeds or is refused; gitcap_student_greedy_draft and
+ * _window_greedy_draft consume it and fail with GITCAP_ERR_ARG; every other entry point leaves it pending.  It combines with the
+ * log-probability, top-logprob, frame-count and constraint attachments.  In a window call row b is clip b of the window, in a pool
+ * call row r is the stream stream_ids[r] names.
+ * The greedy loops are captured graphs, so the prompt is no kernel argument: the consuming call copies the caller's rows (max_len
+ * columns each, and the lengths) into tables the handle owns -- int64 [max_rows][max_text_len + 2] and int32 [max_rows] --, device to
+ * device on the caller's stream ahead of the replay, and the captured nodes name only those tables.  The caller's buffers are read
+ * by those copies and may be reused once they have run.
+ * Greedy: a small staging launch takes the place of the CLS fill: row r = CLS, the prompt's tokens 1 .. lengths[r] - 1, CLS behind
+ * them -- the whole prompt stands in the id rows before the first position runs, because the self-attention masks PAD keys by id.
+ * Every step then runs the forced form of the arg-max against the tables: a row whose prompt covers the position written takes
+ * the prompt's token (for the output and the next step's input), the token is not counted by the stop rule, 0.0f is written for
+ * its log-probability, and it is emitted even when a constraint bans it; attached top-k alternatives still report the model's own
+ * ranks there.  Positions 0 .. min_len - 1 are prompt in every row: with min_len >= 2 they run as ONE pass (the head on its last
+ * position only, the arg-max forced at position min_len) unless constraints or top-k alternatives are attached, which need every
+ * position's step; the prompt then runs as forced token steps (same ids: a cached step is bit for bit the teacher-forced
+ * position).  The captured loop is keyed by that plan -- 0 unprompted, 1 forced steps, min_len for one pass -- so one graph serves
+ * every prompt of its plan, and a call without a prompt replays the loop it replayed before.  ids_out includes the prompt.
+ * Beam: the rows start from the staged prompts (clip b's row for its k beams); while t + 1 < lengths[b] the bookkeeping step does
+ * not rank clip b: every one of its k rows keeps its own prefix and appends prompt_ids[b][t + 1], src_rows is the identity and the
+ * scores stay untouched, so a clip leaves its prompt with [0, -1e9, ..] as it leaves CLS.  max_len counts the prompt; the search
+ * keeps its semantics otherwise (no end-of-sequence handling).  The beam rows take no multi-position pass.
+ * Errors: GITCAP_ERR_ARG for one null pointer, a misaligned pointer, min_len < 1, max_len < min_len, ld < max_len or max_len >
+ * max_text_len + 1; GITCAP_ERR_STATE before the weights are finalized; at the consuming call max_len > the call's max_len (greedy) or
+ * > max_len - 1 (beam: at least one free position) gives GITCAP_ERR_ARG with nothing launched (the attachment is consumed all the
+ * same).  The first attach allocates the two tables; a handle that never attaches allocates nothing and makes the launches it made. */
+int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len);
+/* gitcap_workspace_bytes for this handle: the device bytes of its workspace, attachments' buffers and the stream pool (weights, the
+ * window's ring and page-locked memory not counted).  What an attachment's first use adds shows here. */
+int gitcap_student_workspace_bytes(const gitcap_student_t* h, int64_t* bytes);
+/* test hooks of the two kernels behind it, on caller-owned device buffers.  prompt_stage: ids [rows][ld] row r = cls, tokens
+ * 1 .. len - 1 of prompt_ids [rows / k][ld_prompt] row r / k, cls behind them, len = lengths[r / k] clamped to [1, max_len] (max_len <=
+ * ld_prompt, max_len <= ld); lp (nullable, fp32 [rows][ld_lp]): columns 0 .. pmin - 2 = 0.0f (1 <= pmin <= ld_lp + 1).
+ * student_beam_step: candidates [B][k] (flat index = beam * V + token, best first) -> ids_next rows (prefix 0 .. t of the source row
+ * of ids_cur [B * k][ld], the token at t + 1), scores, src_rows; prompt_ids NULL: the plain kernel; else (lengths required,
+ * prompt_max_len <= ld_prompt) the forced form where t + 1 < prompt_max_len: a clip with t + 1 < lengths[b] appends
+ * prompt_ids[b][t + 1] to every row's own prefix, src_rows the identity, scores and candidates untouched. */
+int gitcap_dbg_student_prompt_stage(const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int rows, int k, int max_len, int64_t cls,
+                                    int64_t* ids, int ld, float* lp, int ld_lp, int pmin, void* stream);
+int gitcap_dbg_student_beam_step(const float* cand_scores, const int32_t* cand_idx, const int64_t* ids_cur, int64_t* ids_next, float* scores,
+                                 int32_t* src_rows, int B, int k, int V, int t, int ld, const int64_t* prompt_ids, int ld_prompt,
+                                 const int32_t* lengths, int prompt_max_len, void* stream);
 /* gitcap_score over the student decoder's teacher-forced pass (the rows of gitcap_student_forward_decoder, after
  * gitcap_student_set_memory with `rows` rows): same semantics, outputs and ignore rules; no `beams` (candidates of one clip are
  * rows whose memory the caller repeated).  Checks: gitcap_student_forward_decoder's, plus T < 2, ld_ids < T, ld_lp < T - 1. */

@@ -152,6 +152,23 @@ int gitcap_dbg_ban_mask_rec(const int64_t* prefix_ids, int ld_ids, int rows, int
     return dbg_rc(launch_ban_mask_rec(prefix_ids, ld_ids, rows, cur_len, sep_id, rec, V, mask_out, ld_mask, (hipStream_t)stream));
 }
 
+// ---- the student's prompted loops (tests/test_student_prompt_gpu.py) ---------------------------------------------------------------
+int gitcap_dbg_student_prompt_stage(const int64_t* prompt_ids, int ld_prompt, const int32_t* lengths, int rows, int k, int max_len, int64_t cls,
+                                    int64_t* ids, int ld, float* lp, int ld_lp, int pmin, void* stream) {
+    if ((((uintptr_t)prompt_ids | (uintptr_t)ids) & 7) != 0 || (((uintptr_t)lengths | (uintptr_t)lp) & 3) != 0) return GITCAP_ERR_ARG;
+    const StudentPromptStageArgs a{prompt_ids, ld_prompt, lengths, rows, k, max_len, cls, ids, ld, lp, ld_lp, pmin};
+    return dbg_rc(launch_student_prompt_stage(a, (hipStream_t)stream));
+}
+// plain (prompt_ids null) and forced
+int gitcap_dbg_student_beam_step(const float* cand_scores, const int32_t* cand_idx, const int64_t* ids_cur, int64_t* ids_next, float* scores,
+                                 int32_t* src_rows, int B, int k, int V, int t, int ld, const int64_t* prompt_ids, int ld_prompt,
+                                 const int32_t* lengths, int prompt_max_len, void* stream) {
+    if ((((uintptr_t)ids_cur | (uintptr_t)ids_next | (uintptr_t)prompt_ids) & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return GITCAP_ERR_ARG;
+    const PromptArgs pr{prompt_ids, ld_prompt, lengths, 1, prompt_max_len};
+    const StudentBeamStepArgs a{cand_scores, cand_idx, ids_cur, ids_next, scores, src_rows, B, k, V, t, ld, prompt_ids ? &pr : nullptr};
+    return dbg_rc(launch_student_beam_step(a, (hipStream_t)stream));
+}
+
 int gitcap_dbg_gemm(const void* A, const void* W, const float* bias, const float* resid, void* out, int M, int N, int K,
                     int epi, int tile, void* stream) {
     GemmArgs a{};

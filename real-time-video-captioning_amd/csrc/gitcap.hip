@@ -26,6 +26,9 @@
 // g_row_prologue is shared with student.hip.
 std::atomic<bool> g_row_prologue{!env_flag("GITCAP_NO_ROW_PROLOGUE")};
 std::atomic<bool> g_head_share{!env_flag("GITCAP_NO_HEAD_SHARE")};        // kernels.h; gitcap_dbg_config(10, .)
+// a prompted greedy loop runs the positions every row's prompt covers as ONE multi-position pass (gitcap_dbg_config(20, 0): as
+// forced token steps, the plan of a ragged batch whose shortest prompt is the lone CLS; same ids either way)
+std::atomic<bool> g_prompt_prefill{true};         // kernels.h: shared with student.hip, as g_row_prologue is
 std::atomic<bool> g_rows3{!env_flag("GITCAP_NO_ROWS3")};                  // kernels.h; gitcap_dbg_config(11, .)
 
 // compute units of the current device, cached per device (the workgroup -> tile maps and the tile-height choice depend on it)
@@ -572,9 +575,6 @@ std::atomic<bool> g_chain_steps{!env_flag("GITCAP_NO_STEP_CHAIN")};       // git
 // the kernels read the row-major originals; same bits, slower; the FFN then runs as two launches)
 std::atomic<bool> g_wpack{!env_flag("GITCAP_NO_WPACK")};
 std::atomic<bool> g_ffn_fuse{!env_flag("GITCAP_NO_FFN_FUSE")};            // gitcap_dbg_config(7, .): ffn_txt.hip vs FC1 + split-K FC2 launches
-// a prompted greedy loop runs the positions every row's prompt covers as ONE multi-position pass (gitcap_dbg_config(20, 0): as
-// forced token steps, the plan of a ragged batch whose shortest prompt is the lone CLS; same ids either way)
-std::atomic<bool> g_prompt_prefill{true};
 
 bool text_chain_ok(gitcap* h, int rows, int T) {
     return g_chain_steps && T == 1 && !(h->want_hidden && h->cur_slot == 0 && !h->pipelined) &&
@@ -582,14 +582,12 @@ bool text_chain_ok(gitcap* h, int rows, int T) {
 }
 
 // A pass of the decoder over text rows (RowsReq, kernels.h) and what only this stack takes: rows = clips * beams; all_positions:
-// logits of every position instead of the last; the per-step modifiers pre_embedded / embed_next (above), prompt (the arg-max
-// launch's, nullable) and ban (the BAN form of the head, nullable).  keep_len (nullable): the KEEP form of the arg-max launch.
+// logits of every position instead of the last; the per-step modifiers pre_embedded / embed_next (above) and ban (the BAN form of the head, nullable).  keep_len (nullable): the KEEP form of the arg-max launch.
 // verify (a draft's verify pass): the head over ALL rows x T positions, arg-max partials only (+ the sum partial: verify_lp), no
 // logits and no arg-max launch -- launch_draft_accept_rows reduces them.
 struct TextReq : RowsReq {
     int beams = 1, all_positions = 0;
     bool pre_embedded = false, embed_next = false;
-    const PromptArgs* prompt = nullptr;
     const HeadBan* ban = nullptr;
     const int32_t* keep_len = nullptr;
     bool verify = false, verify_lp = false;

@@ -97,6 +97,8 @@ extern std::atomic<bool> g_row_prologue;                                 // gitc
 // vocabulary head: four 16-column tiles per workgroup share the activation rows through LDS (skinny.hip: skinny_head_kernel);
 // GITCAP_NO_HEAD_SHARE / gitcap_dbg_config(10, 0): one single-wave workgroup per tile.  Same bits either way.
 extern std::atomic<bool> g_head_share;
+// gitcap.hip, gitcap_dbg_config(20, .): a prompted greedy loop of either handle runs the positions every row's prompt covers as one pass
+extern std::atomic<bool> g_prompt_prefill;
 // one/two-row prologue over more than 16 slabs: three-wave workgroups that share the reduce (skinny.hip: skinny_rows3_kernel);
 // GITCAP_NO_ROWS3 / gitcap_dbg_config(11, 0): the single-wave form.  Same bits either way.
 extern std::atomic<bool> g_rows3;
@@ -338,6 +340,8 @@ struct RowsReq {
     // k != 0, needs argmax_out: the k best columns of the row the arg-max reads (launch_head_topk behind the arg-max launch; the head
     // runs its LSE form); ids / lp point at this position's entries of row 0, ld = the row pitch in positions
     TopkAttach topk{};
+    // nullable, needs argmax_out (a prompted greedy loop): the arg-max launch's prompt; it writes position t0 + T
+    const PromptArgs* prompt = nullptr;
 };
 
 // ---- candidate generation and the beam state of the search loops (search.hip) ------------------------------------------------------
@@ -514,6 +518,30 @@ hipError_t launch_cross_mean(const float* probs, int L, int rows, int T, int H, 
 // x[m] = (embed[ids[r*ld_ids + t0 + j]] + pe[t0 + j]) / sqrt(D), m = r*T + j  -> xf (fp32) and xb (bf16)
 hipError_t launch_student_embed(const int64_t* ids, int ld_ids, int rows, int T, int t0, const float* embed,
                                 const float* pe, int D, int vocab, float* xf, bf16_t* xb, hipStream_t s);
+// The start of a prompted student loop (gitcap_student_attach_prompt; student.hip: student_prompt_stage_kernel): ids [rows][ld] row r =
+// CLS, tokens 1 .. len - 1 of prm_ids [rows / k][ld_prm] row r / k, CLS behind them; len = prm_len[r / k] clamped to [1, max_len]
+// (max_len <= ld_prm and <= ld: no read leaves a table row, every column of a row is written).  lp (nullable, [rows][ld_lp]):
+// columns 0 .. pmin - 2 = 0.0f (1 <= pmin <= ld_lp + 1).  k = 1: the greedy loop's rows; k beams of a clip share its prompt.
+struct StudentPromptStageArgs {
+    const int64_t* prm_ids; int ld_prm; const int32_t* prm_len;
+    int rows, k, max_len; int64_t cls;
+    int64_t* ids; int ld;
+    float* lp; int ld_lp, pmin;
+};
+hipError_t launch_student_prompt_stage(const StudentPromptStageArgs& a, hipStream_t s);
+// The bookkeeping step of the student's beam search (student.hip: student_beam_step_kernel): the candidates [B][k] (flat index =
+// beam * V + token, best first) of the step that decoded position t become rows b * k + j of ids_next (prefix 0 .. t of the source row
+// of ids_cur, the token at t + 1; ld >= t + 2), scores and src_rows.  prompt (nullable; rows = clips): a clip with t + 1 < lengths[b]
+// keeps every row's own prefix, appends ids[b][t + 1], src_rows the identity, scores untouched, candidates unread; with
+// t + 1 >= max_len (the prompt's) the launch is the one without a prompt.
+struct StudentBeamStepArgs {
+    const float* cand_scores; const int* cand_idx;
+    const int64_t* ids_cur; int64_t* ids_next;
+    float* scores; int32_t* src_rows;
+    int B, k, V, t, ld;
+    const PromptArgs* prompt;
+};
+hipError_t launch_student_beam_step(const StudentBeamStepArgs& a, hipStream_t s);
 
 // ---- row ops (rowops.hip) -----------------------------------------------------------------------------
 struct LnArgs {

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "host_util.h"
 #include "student_internal.h"
+#include "prompt_sel.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -212,11 +213,30 @@ __global__ void beam_scores_init_kernel(float* scores, int rows, int k) {
 }
 // one step of model.py:252-287: candidate j of clip b (sorted best first by beam_topk; flat index = beam * V + token) becomes
 // row b * k + j: its prefix is the prefix of row b * k + beam, its new token the candidate's, its score the candidate's
+// FORCED (gitcap_student_attach_prompt; pr indexed by clip, pr.pos = t + 1 = the position written): a clip still inside its prompt
+// (t + 1 < len_b) is not ranked -- every one of its k rows keeps its OWN prefix and appends the prompt's token, src_rows is the
+// identity, scores stay as they are (a clip leaves its prompt with [0, -1e9, ..], as it leaves CLS) and its candidates are not read.
+// <false> is the kernel as it was before it became a template.
+template <bool FORCED>
 __global__ __launch_bounds__(64) void student_beam_step_kernel(const float* __restrict__ cand_scores, const int* __restrict__ cand_idx,
                                                                const int64_t* __restrict__ ids_cur, int64_t* __restrict__ ids_next,
                                                                float* __restrict__ scores, int32_t* __restrict__ src_rows,
-                                                               int k, int V, int t, int ld) {
+                                                               int k, int V, int t, int ld, PromptSel<FORCED> pr) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    if constexpr (FORCED) {
+        if (pr.pos < prompt_len(pr.lengths, b, pr.max_len)) {
+            const int64_t tok = pr.ids[(size_t)b * pr.ld + pr.pos];
+            for (int j = 0; j < k; ++j) {
+                const int row = b * k + j;
+                for (int i = lane; i <= t; i += 64) ids_next[(size_t)row * ld + i] = ids_cur[(size_t)row * ld + i];
+                if (lane == 0) {
+                    ids_next[(size_t)row * ld + t + 1] = tok;
+                    src_rows[row] = row;
+                }
+            }
+            return;
+        }
+    }
     for (int j = 0; j < k; ++j) {
         const int idx = cand_idx[b * k + j];
         const int beam = idx / V, tok = idx - beam * V;
@@ -229,10 +249,48 @@ __global__ __launch_bounds__(64) void student_beam_step_kernel(const float* __re
         }
     }
 }
+// The start of a prompted loop (gitcap_student_attach_prompt), in the place of launch_fill_i64: row r of ids [rows][ld] = CLS, the
+// tokens 1 .. len - 1 of prompt row r / k (k beams of a clip share its prompt; k = 1: the greedy loop's rows), CLS in the columns
+// behind them (what the fill writes).  len = lengths[r / k] clamped to [1, max_len] (prompt_len: no read leaves a table row).
+// lp (nullable, [rows][ld_lp]): its columns 0 .. pmin - 2 become 0.0f, the forced positions a one-pass plan never visits.
+// The tables are the handle's and are read when the launch runs: inside a captured loop, at replay.
+__global__ __launch_bounds__(64) void student_prompt_stage_kernel(const int64_t* __restrict__ prm_ids, int ld_prm, const int32_t* __restrict__ prm_len,
+                                                                  int k, int max_len, int64_t cls, int64_t* __restrict__ ids, int ld,
+                                                                  float* __restrict__ lp, int ld_lp, int pmin) {
+    const int r = blockIdx.x, c = r / k;
+    const int len = prompt_len(prm_len, c, max_len);
+    for (int i = threadIdx.x; i < ld; i += 64) ids[(size_t)r * ld + i] = (i >= 1 && i < len) ? prm_ids[(size_t)c * ld_prm + i] : cls;
+    if (lp)
+        for (int i = threadIdx.x; i + 1 < pmin; i += 64) lp[(size_t)r * ld_lp + i] = 0.0f;
+}
 // the best beam of every clip (row b * k: the candidates arrive sorted) -> out [B][max_len]
 __global__ void student_beam_finish_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ out, int k, int ld, int max_len) {
     const int b = blockIdx.x;
     for (int i = threadIdx.x; i < max_len; i += 64) out[(size_t)b * max_len + i] = ids[(size_t)b * k * ld + i];
+}
+
+hipError_t launch_student_prompt_stage(const StudentPromptStageArgs& a, hipStream_t s) {
+    if (!a.prm_ids || !a.prm_len || !a.ids || a.rows < 1 || a.k < 1 || a.max_len < 1 || a.ld_prm < a.max_len || a.ld < a.max_len || a.pmin < 1 ||
+        (a.lp && a.ld_lp + 1 < a.pmin))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(student_prompt_stage_kernel, dim3(a.rows), dim3(64), 0, s, a.prm_ids, a.ld_prm, a.prm_len, a.k, a.max_len, a.cls, a.ids, a.ld,
+                       a.lp, a.ld_lp, a.pmin);
+    return hipGetLastError();
+}
+
+hipError_t launch_student_beam_step(const StudentBeamStepArgs& a, hipStream_t s) {
+    if (!a.cand_scores || !a.cand_idx || !a.ids_cur || !a.ids_next || !a.scores || !a.src_rows || a.B < 1 || a.k < 1 || a.V < 1 || a.t < 0 ||
+        a.ld < a.t + 2)
+        return hipErrorInvalidValue;
+    const PromptArgs* p = a.prompt;
+    if (p && (!p->ids || !p->lengths || p->max_len < 1 || p->ld < p->max_len)) return hipErrorInvalidValue;
+    if (p && a.t + 1 < p->max_len)                  // (behind the longest prompt no clip is forced: the plain form)
+        hipLaunchKernelGGL(student_beam_step_kernel<true>, dim3(a.B), dim3(64), 0, s, a.cand_scores, a.cand_idx, a.ids_cur, a.ids_next, a.scores,
+                           a.src_rows, a.k, a.V, a.t, a.ld, PromptSel<true>{p->ids, p->lengths, p->ld, p->max_len, a.t + 1});
+    else
+        hipLaunchKernelGGL(student_beam_step_kernel<false>, dim3(a.B), dim3(64), 0, s, a.cand_scores, a.cand_idx, a.ids_cur, a.ids_next, a.scores,
+                           a.src_rows, a.k, a.V, a.t, a.ld, PromptSel<false>{});
+    return hipGetLastError();
 }
 
 // ---- memory-token window (gitcap_student_window_*) -------------------------------------------------------------------------
@@ -300,7 +358,9 @@ struct gitcap_student : HandleCore {
     // key: stop = a stop rule -> execs[0] the whole greedy loop; TAIL_STEPS -> execs[t - 1] token step t of the draft path, t >= 1
     int64_t* g_ids = nullptr;
     int32_t* g_steps = nullptr;
-    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; bool ragged, cons; std::vector<hipGraphExec_t> execs; };     // tk: top-k alternatives per step (0: none); ragged: the varlen cross-attention launches; cons: the constrained loop
+    // tk: top-k alternatives per step (0: none); ragged: the varlen cross-attention launches; cons: the constrained loop; plan: 0 the
+    // unprompted loop, 1 a prompted loop of forced token steps, p >= 2 a prompted loop whose positions 0 .. p - 1 run as one pass
+    struct Graphs { int B, max_len, stop; bool rows_pro, head_share, lp; int tk; bool ragged, cons; int plan; std::vector<hipGraphExec_t> execs; };
     static constexpr int TAIL_STEPS = -1;
     std::vector<Graphs> graphs;
     // draft verification (gitcap_student_*_greedy_draft): acc_tok / acc_ticket = draft_accept_kernel's scratch, acc_host = its
@@ -344,6 +404,13 @@ struct gitcap_student : HandleCore {
     int ban_ld = 0;
     int32_t *ban_rec = nullptr, *ban_host = nullptr;
     hipEvent_t ban_ev = nullptr;
+    // prompted decoding (gitcap_student_attach_prompt): pr_attach = the pending one-shot attachment (the caller's device tables).  The
+    // first attach allocates prm_ids (int64 [R][Tmax + 1]) and prm_len (int32 [R]), the handle's own tables: the consuming call copies
+    // the caller's rows into them on its stream, outside every captured loop (write_prompt_tables), and the loops' nodes -- the stage
+    // kernel, the forced arg-max -- name only these, so one captured loop serves every prompt of its plan.
+    PromptArgs pr_attach{};
+    int64_t* prm_ids = nullptr;
+    int32_t* prm_len = nullptr;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
     hipStream_t cap_stream = nullptr;   // capture only (the legacy default stream cannot be captured); replays run on the caller's stream
     // device-resident beam search (gitcap_student_beam_search), allocated on first use
@@ -530,6 +597,7 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
         a.rows = rows; a.row_stride = hr.am_stride; a.row_off = hr.am_off;
         a.out = q.argmax_out; a.ld_out = q.ld_argmax; a.sep_cnt = q.sep_cnt; a.step = q.step; a.sep_id = c.sep_token_id;
         a.lp_out = q.lp_out; a.ld_lp = q.ld_lp;
+        a.prompt = q.prompt; a.prompt_pos = t0 + T;         // (a prompted greedy loop): the token goes to position t0 + T
         HIP_OK(h, launch_argmax_final(a, s));
     }
     if (q.topk.k) {     // the k best of the row the arg-max read, from the same partials
@@ -810,7 +878,8 @@ const bool g_use_graph = !(getenv("GITCAP_STUDENT_GRAPH") && atoi(getenv("GITCAP
 // want_lp, its log-probability as column t of g_lp; with tk != 0 the tk best of that distribution as entry t of g_tk_ids / g_tk_lp).
 // The full loop, the captured tail steps and the un-graphed tail are this call.
 // cons: first the rows' ban mask from the ids so far (prefix 0 .. t) under the rules in ban_rec, then the BAN form of the head.
-int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q, int tk = 0, bool cons = false) {
+// prompt (the handle's tables): a row whose prompt covers position t + 1 takes the prompt's token there (the forced arg-max).
+int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipStream_t q, int tk = 0, bool cons = false, const PromptArgs* prompt = nullptr) {
     const int ld = max_len + 1;
     const HeadBan bn{h->ban_mask, h->ban_ld};
     TextReq r;
@@ -822,6 +891,7 @@ int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipSt
     r.argmax_out = h->g_ids + t + 1; r.ld_argmax = ld; r.sep_cnt = h->sep_cnt;
     r.lp_out = want_lp ? h->g_lp + t : nullptr; r.ld_lp = max_len;
     if (tk) r.topk = TopkAttach{tk, h->g_tk_ids + (size_t)t * tk, h->g_tk_lp + (size_t)t * tk, max_len};
+    r.prompt = prompt;
     return text_forward(h, r, q);
 }
 
@@ -848,6 +918,23 @@ int write_ban_record(gitcap_student* h, const ConsOpt& co, hipStream_t s) {
     return 0;
 }
 
+// ---- prompted decoding (gitcap_student_attach_prompt) ---------------------------------------------------------------------------
+// the pending prompt: consumed by the caller, whatever becomes of its call
+PromptArgs take_prompt(gitcap_student* h) { return std::exchange(h->pr_attach, PromptArgs{}); }
+// The caller's prompts of `rows` clips -> the handle's tables, on `s` and outside every captured loop: pr.max_len columns of every row
+// and the lengths, device to device (the caller's buffers are read when these copies run, ahead of the loop on the same stream).
+int write_prompt_tables(gitcap_student* h, const PromptArgs& pr, int rows, hipStream_t s) {
+    HIP_OK(h, hipMemcpy2DAsync(h->prm_ids, ((size_t)h->Tmax + 1) * sizeof(int64_t), pr.ids, (size_t)pr.ld * sizeof(int64_t),
+                               (size_t)pr.max_len * sizeof(int64_t), (size_t)rows, hipMemcpyDeviceToDevice, s));
+    HIP_OK(h, hipMemcpyAsync(h->prm_len, pr.lengths, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// the handle's tables as the forced launches take them: lengths are clamped to the CALL's max_len (>= the prompt's), which fits a
+// table row (ld = Tmax + 1)
+PromptArgs table_prompt(const gitcap_student* h, const PromptArgs& pr, int call_max_len) {
+    return PromptArgs{h->prm_ids, h->Tmax + 1, h->prm_len, pr.min_len, call_max_len};
+}
+
 // What enqueue(cap_stream) launches -> one executable graph (replayed on the caller's stream).  A failed enqueue still ends the
 // capture and its own status is returned; whatever fails, the hipGraph_t is destroyed and *exec stays null.
 template <typename Enqueue>
@@ -870,14 +957,14 @@ int capture(gitcap_student* h, const char* what, Enqueue enqueue, hipGraphExec_t
 // The executables of a key, captured by fill(execs) at the key's first use; a failed fill caches nothing.  Weight and workspace
 // pointers are baked into the nodes (destroy_graphs at every finalize).
 template <typename Fill>
-int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, bool cons, Fill fill, const std::vector<hipGraphExec_t>** out) {
+int captured_graphs(gitcap_student* h, int B, int max_len, int stop, bool want_lp, int tk, bool cons, int plan, Fill fill, const std::vector<hipGraphExec_t>** out) {
     for (auto& g : h->graphs)
         if (g.B == B && g.max_len == max_len && g.stop == stop && g.rows_pro == g_row_prologue && g.head_share == g_head_share && g.lp == want_lp && g.tk == tk &&
-            g.ragged == h->ragged && g.cons == cons) {
+            g.ragged == h->ragged && g.cons == cons && g.plan == plan) {
             *out = &g.execs;
             return 0;
         }
-    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, h->ragged, cons, {}};
+    gitcap_student::Graphs g{B, max_len, stop, g_row_prologue, g_head_share, want_lp, tk, h->ragged, cons, plan, {}};
     if (int rc = fill(g.execs)) {
         for (hipGraphExec_t e : g.execs) (void)hipGraphExecDestroy(e);
         return rc;
@@ -906,22 +993,49 @@ int copy_out(gitcap_student* h, int B, int max_len, int64_t* ids_out, int32_t* s
 // the token loop of greedy_decode (model.py:171-184) against the memory K|V in h->memkv (set_memory, or the window's gather)
 // lp.p set: the loop with token log-probabilities (a graph of its own; column t of g_lp = step t's)
 // co.on: the constrained loop (a graph of its own, whatever the rules: they are written to ban_rec here, ahead of the replay)
+// pr.ids set: the prompted loop (graphs of their own, one per plan, whatever the prompts: they are copied to the handle's tables here,
+// ahead of the replay).  The stage kernel puts every row's prompt into g_ids before the first position runs -- the self-attention masks
+// PAD keys by id --, and every step runs the forced arg-max against the tables: the device lengths decide row by row.  Positions
+// 0 .. pmin - 1 are prompt in every row: where pmin >= 2 they run as ONE pass (T = pmin, the head on its last position, the arg-max
+// forced at position pmin), except under constraints or top-k alternatives, which need every position's step.
 int greedy_loop(gitcap_student* h, int B, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, hipStream_t s, const LpAttach& lp,
-                const TopkAttach& tk, const ConsOpt& co) {
+                const TopkAttach& tk, const ConsOpt& co, const PromptArgs& pr) {
     const bool want_lp = lp.p != nullptr;
     int rc;
     if (co.on && (rc = write_ban_record(h, co, s))) return rc;
+    int plan = 0;
+    if (pr.ids) {
+        std::string why;
+        plan = g_prompt_prefill && pr.min_len >= 2 && !co.on && !tk.k && student_rows_check(h, B, pr.min_len, why) == 0 ? pr.min_len : 1;
+        if ((rc = write_prompt_tables(h, pr, B, s))) return rc;
+    }
+    const PromptArgs tab = table_prompt(h, pr, max_len);
+    const PromptArgs* const prompt = plan ? &tab : nullptr;
     auto enqueue_loop = [&](hipStream_t q) -> int {
-        HIP_OK(h, launch_fill_i64(h->g_ids, max_len + 1, B, h->c.cls_token_id, q));        // model.py:171
+        if (plan) {
+            const StudentPromptStageArgs sa{h->prm_ids, h->Tmax + 1, h->prm_len, B, 1, max_len, h->c.cls_token_id, h->g_ids, max_len + 1,
+                                            want_lp ? h->g_lp : nullptr, max_len, plan};
+            HIP_OK(h, launch_student_prompt_stage(sa, q));
+        } else {
+            HIP_OK(h, launch_fill_i64(h->g_ids, max_len + 1, B, h->c.cls_token_id, q));    // model.py:171
+        }
         HIP_OK(h, hipMemsetAsync(h->sep_cnt, 0, ((size_t)h->Tmax + 1) * 4, q));
-        for (int t = 0; t < max_len; ++t)                                                    // model.py:173-182
-            if (int r = token_step(h, B, t, max_len, want_lp, q, tk.k, co.on)) return r;
+        if (plan >= 2) {                            // positions 0 .. plan - 1 in one pass: its arg-max is step plan - 1's
+            TextReq r;
+            r.ids = h->g_ids; r.ld_ids = max_len + 1; r.rows = B; r.t0 = 0; r.T = plan; r.step = plan - 1;
+            r.argmax_out = h->g_ids + plan; r.ld_argmax = max_len + 1; r.sep_cnt = h->sep_cnt;
+            r.lp_out = want_lp ? h->g_lp + (plan - 1) : nullptr; r.ld_lp = max_len;
+            r.prompt = prompt;
+            if (int e = text_forward(h, r, q)) return e;
+        }
+        for (int t = plan >= 2 ? plan : 0; t < max_len; ++t)                                 // model.py:173-182
+            if (int r = token_step(h, B, t, max_len, want_lp, q, tk.k, co.on, prompt)) return r;
         HIP_OK(h, launch_finish_steps(h->sep_cnt, B, max_len, stop, h->g_steps, q));       // model.py:184
         return 0;
     };
     if (g_use_graph) {
         const std::vector<hipGraphExec_t>* loop = nullptr;
-        rc = captured_graphs(h, B, max_len, stop, want_lp, tk.k, co.on, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, stop, want_lp, tk.k, co.on, plan, [&](std::vector<hipGraphExec_t>& execs) {
             execs.push_back(nullptr);
             return capture(h, "student greedy: capturing the token loop", enqueue_loop, &execs.back());
         }, &loop);
@@ -954,7 +1068,7 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     // every token step this key can need is captured now: how many of them run depends on the data, a capture must not
     const std::vector<hipGraphExec_t>* steps = nullptr;
     if (g_use_graph) {
-        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, 0, false, [&](std::vector<hipGraphExec_t>& execs) {
+        rc = captured_graphs(h, B, max_len, gitcap_student::TAIL_STEPS, want_lp, 0, false, 0, [&](std::vector<hipGraphExec_t>& execs) {
             for (int t = 1; t < max_len; ++t) {
                 execs.push_back(nullptr);
                 if (int r = capture(h, "student draft: capturing a token step", [&](hipStream_t q) { return token_step(h, B, t, max_len, want_lp, q); },
@@ -1035,11 +1149,20 @@ int beam_workspace(gitcap_student* h) {
 // the token loop of beam_search against the memory K|V of B * k rows in h->memkv (set_memory of the repeated rows, or the window's gather)
 // co.on: every step first builds the mask of the B * k rows from the buffer that holds their current prefixes (positions 0 .. t), and
 // the ranking runs its BAN form: banned columns are -inf ahead of the log-softmax
-int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s, const ConsOpt& co) {
+// pr.ids set (max_len counts the prompt): the rows start from the staged prompts, clip b's row for its k beams, and while a clip is
+// inside its prompt the bookkeeping step appends the prompt's token to every one of its rows instead of ranking (the FORCED form)
+int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s, const ConsOpt& co, const PromptArgs& pr) {
     const int rows = B * k, D = h->D, V = h->V, ld = h->Tmax + 1;
     int rc = 0;
     gitcap_student::BeamWs& w = h->bw;
-    HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
+    const PromptArgs tab = table_prompt(h, pr, max_len - 1);        // (at least one free position)
+    if (pr.ids) {
+        if ((rc = write_prompt_tables(h, pr, B, s))) return rc;
+        const StudentPromptStageArgs sa{h->prm_ids, h->Tmax + 1, h->prm_len, rows, k, max_len - 1, h->c.cls_token_id, w.ids0, ld, nullptr, 0, 1};
+        HIP_OK(h, launch_student_prompt_stage(sa, s));
+    } else {
+        HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
+    }
     hipLaunchKernelGGL(beam_scores_init_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, w.scores, rows, k);
     HIP_OK(h, hipGetLastError());
     int64_t *cur = w.ids0, *nxt = w.ids1;
@@ -1069,8 +1192,8 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
         }
         hipError_t e = launch_beam_topk(ca, k, w.topk_scratch, s);
         if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL(student_beam_step_kernel, dim3(B), dim3(64), 0, s, w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, k, V, t, ld);
-        if (hipGetLastError() != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
+        const StudentBeamStepArgs st{w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, B, k, V, t, ld, pr.ids ? &tab : nullptr};
+        if (launch_student_beam_step(st, s) != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
         std::swap(cur, nxt);
     }
     h->kvs = kvs_home;                                                  // (the captured greedy graphs hold this pointer)
@@ -1120,7 +1243,10 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
     const Counts fc = take_counts(h);
     const ConsOpt co = take_constraints(h);
+    const PromptArgs pr = take_prompt(h);
     if (window && !fc.empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));          // (consumed above)
+    if (draft && pr.ids)
+        return fail(h, GITCAP_ERR_ARG, w + ": a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take");
     if (draft && co.on)
         return fail(h, GITCAP_ERR_ARG, w + ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take");
     if (draft && tk.k) return fail(h, GITCAP_ERR_ARG, refused_message(who, OPT_TK));       // (consumed above)
@@ -1130,6 +1256,7 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     if (int bad = lp_check(h, who, lp, max_len)) return bad;
     if (int bad = tk_check(h, who, tk, max_len)) return bad;
     if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
+    if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len");
     if (draft && !draft->ids) return fail(h, GITCAP_ERR_ARG, w + ": null draft_ids");
     if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
         return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
@@ -1143,7 +1270,7 @@ int greedy_entry(gitcap_student* h, const char* who, bool window, const float* m
     if (frames_out) *frames_out = frames;
     if (window) B = h->win_B;
     if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co, pr);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1202,9 +1329,11 @@ int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, 
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
     const Counts fc = take_counts(h);
     const ConsOpt co = take_constraints(h);
+    const PromptArgs pr = take_prompt(h);
     if (!memory) return fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
     if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
     if (int bad = cons_check(h, "student_beam_search", co, max_len, k)) return bad;
+    if (pr.ids && pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, "student_beam_search: the attached prompt is longer than max_len - 1");
     const Counts* ragged = nullptr;
     if (int bad = counts_for_call(h, "student_beam_search", fc, B, &ragged)) return bad;
     GUARD(h);
@@ -1213,13 +1342,13 @@ int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, 
     if (rc) return rc;
     if (ragged) {       // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
         if ((rc = set_memory(h, memory, B, s, ragged, k))) return rc;
-        return beam_loop(h, B, k, max_len, ids_out, s, co);
+        return beam_loop(h, B, k, max_len, ids_out, s, co, pr);
     }
     const int rows = B * k;
     hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
     HIP_OK(h, hipGetLastError());
     if ((rc = set_memory(h, h->bw.memrep, rows, s))) return rc;
-    return beam_loop(h, B, k, max_len, ids_out, s, co);
+    return beam_loop(h, B, k, max_len, ids_out, s, co, pr);
 }
 
 int gitcap_student_window_reset(gitcap_student_t* h, int B) {
@@ -1367,6 +1496,25 @@ int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constrai
     return 0;
 }
 
+int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: null handle");
+    h->pr_attach = PromptArgs{};
+    if (!prompt_ids && !lengths) return 0;                   // detach
+    if (!prompt_ids || !lengths) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: prompt_ids and lengths are both required");
+    if (((uintptr_t)prompt_ids & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: a misaligned pointer");
+    if (min_len < 1 || max_len < min_len || ld < max_len) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: need 1 <= min_len <= max_len <= ld");
+    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: max_len exceeds max_text_len + 1");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_prompt: weights not finalized");
+    GUARD(h);
+    {   // first attach: the handle's own tables, each on its own (an attach repeated after a failed allocation keeps what the first got)
+        int rc;
+        if (!h->prm_ids && (rc = dev_alloc(h, &h->prm_ids, (size_t)h->R * ((size_t)h->Tmax + 1)))) { h->prm_ids = nullptr; return rc; }
+        if (!h->prm_len && (rc = dev_alloc(h, &h->prm_len, (size_t)h->R))) { h->prm_len = nullptr; return rc; }
+    }
+    h->pr_attach = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
+    return 0;
+}
+
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
@@ -1416,6 +1564,12 @@ int gitcap_student_dbg_score_target_logits(gitcap_student_t* h, float* out, int 
     return 0;
 }
 
+int gitcap_student_workspace_bytes(const gitcap_student_t* h, int64_t* bytes) {
+    if (!h || !bytes) return fail(h, GITCAP_ERR_ARG, "student_workspace_bytes: null argument");
+    *bytes = h->ws_bytes;
+    return 0;
+}
+
 int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
     if (!h || !out4) return fail(h, GITCAP_ERR_ARG, "student_draft_stats: null argument");
     out4[0] = h->draft_calls; out4[1] = h->draft_offered; out4[2] = h->draft_accepted; out4[3] = h->draft_tail_steps;
@@ -1425,17 +1579,19 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
     const ConsOpt co = take_constraints(h);         // consumed, whatever becomes of the call
+    const PromptArgs pr = take_prompt(h);
     if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_beam_search"));
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
     if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;
     if (int bad = cons_check(h, "student_window_beam_search", co, max_len, k)) return bad;
+    if (pr.ids && pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: the attached prompt is longer than max_len - 1");
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     int rc = beam_workspace(h);
     if (rc) return rc;
     if ((rc = window_memory(h, "student_window_beam_search", k, s))) return rc;
-    return beam_loop(h, h->win_B, k, max_len, ids_out, s, co);
+    return beam_loop(h, h->win_B, k, max_len, ids_out, s, co, pr);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1536,6 +1692,7 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});           // consumed, whatever becomes of the call
     const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
     const ConsOpt co = take_constraints(h);
+    const PromptArgs pr = take_prompt(h);
     if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));
     if (!stream_ids || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
@@ -1543,6 +1700,7 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     if (int bad = lp_check(h, who, lp, max_len)) return bad;
     if (int bad = tk_check(h, who, tk, max_len)) return bad;
     if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
+    if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len");
     if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
     if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
@@ -1559,7 +1717,7 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = pool_memory(h, stream_ids, B, s, frames_out)) return rc;
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co, pr);
 }
 
 int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id) {

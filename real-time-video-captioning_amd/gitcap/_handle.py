@@ -13,6 +13,22 @@ from torch import nn
 from . import _lib
 
 
+class _Prompt:
+    """A batch of per-clip text prefixes on the device (include/gitcap.h: gitcap_attach_prompt, gitcap_student_attach_prompt): ids
+    int64 [B, P] with CLS at column 0, lengths int32 [B] (valid tokens per clip, CLS included), and the host's copy of the lengths."""
+
+    def __init__(self, ids, lengths, host_lengths):
+        self.ids, self.lengths, self.host_lengths = ids, lengths, host_lengths
+        self.min_len, self.max_len = min(host_lengths), max(host_lengths)
+
+    def rows(self, r0, r1):
+        return _Prompt(self.ids[r0:r1].contiguous(), self.lengths[r0:r1].contiguous(), self.host_lengths[r0:r1])
+
+    def attach(self, model):
+        """The one-shot attachment the NEXT greedy- or beam-family call consumes (a repeated call attaches again)."""
+        model._call(model._PREFIX + "_attach_prompt", _lib.ptr(self.ids), self.ids.shape[1], _lib.ptr(self.lengths), self.min_len, self.max_len)
+
+
 class _NativeModule(nn.Module):
     """The constructor of a subclass sets ``_lib``, ``_dev``, ``_handle = None`` and ``_weights = None``, then calls ``_open()``."""
     _PREFIX = None       # "gitcap" | "gitcap_student" | "gitcap_tinyvit"
@@ -32,6 +48,39 @@ class _NativeModule(nn.Module):
 
     def _moved(self):
         """Runs after ``to()`` has really changed the device (new handle, weights loaded again)."""
+
+    # ------------------------------------------------------------------ prompts (GitCaptioner and StudentCaptioner: `cls_token_id`)
+    def _prompt(self, prompt, prompt_lengths, B, limit, what):
+        """The ``prompt=`` argument of the decoding calls -> _Prompt or None.  prompt: int64 [B, P] (every row P tokens, or
+        ``prompt_lengths`` [B] valid tokens per row) or a list of B 1-D tensors (ragged).  CLS is prepended to a row that does not
+        start with it (the lengths then count it).  A set-up step: the lengths are read on the host."""
+        if prompt is None:
+            if prompt_lengths is not None:
+                raise ValueError("prompt_lengths without prompt")
+            return None
+        if isinstance(prompt, torch.Tensor):
+            if prompt.dim() != 2:
+                raise ValueError(f"prompt must be [B, P] or a list of B 1-D tensors, got {tuple(prompt.shape)}")
+            lens = [prompt.shape[1]] * prompt.shape[0] if prompt_lengths is None else [int(v) for v in torch.as_tensor(prompt_lengths).tolist()]
+            if len(lens) != prompt.shape[0] or any(not 0 <= n <= prompt.shape[1] for n in lens):
+                raise ValueError("prompt_lengths must hold one length in [0, P] per row of prompt")
+            host = prompt.detach().to("cpu", torch.int64)
+            rows = [host[b, :n] for b, n in enumerate(lens)]
+        else:
+            if prompt_lengths is not None:
+                raise ValueError("prompt_lengths goes with a [B, P] tensor; a list of rows carries its own lengths")
+            rows = [torch.as_tensor(r).detach().to("cpu", torch.int64).reshape(-1) for r in prompt]
+        if len(rows) != B:
+            raise ValueError(f"prompt has {len(rows)} rows for a batch of {B} clips")
+        cls = self.cls_token_id
+        rows = [r if r.numel() and int(r[0]) == cls else torch.cat([torch.tensor([cls], dtype=torch.int64), r]) for r in rows]
+        lens = [int(r.numel()) for r in rows]
+        if max(lens) > limit:
+            raise ValueError(f"a prompt of {max(lens)} tokens (CLS included) exceeds {what} = {limit}")
+        ids = torch.full((B, max(lens)), cls, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            ids[b, :lens[b]] = r
+        return _Prompt(ids.to(self._dev), torch.tensor(lens, dtype=torch.int32).to(self._dev), lens)
 
     # ------------------------------------------------------------------ handle
     def _open(self):

@@ -280,6 +280,13 @@ SYMBOLS = {
     "gitcap_student_attach_token_logprobs": (c_int, [c_void_p, c_void_p, c_int]),
     "gitcap_student_attach_top_logprobs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "gitcap_student_attach_constraints": (c_int, [c_void_p, POINTER(CConstraints)]),
+    # the student's prompted decoding (tests/test_student_prompt_gpu.py, tests/test_student_prompt_e2e_gpu.py)
+    "gitcap_student_attach_prompt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "gitcap_student_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
+    "gitcap_dbg_student_prompt_stage": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                c_void_p]),
+    "gitcap_dbg_student_beam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gitcap_student_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "gitcap_student_dbg_score_target_logits": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),

@@ -30,7 +30,7 @@ from . import _lib, ragged
 from .config import CGitCapConfig, GitCapConfig, git_base
 from .framegate import FrameGate
 from . import weights as W
-from ._handle import _NativeModule
+from ._handle import _NativeModule, _Prompt  # noqa: F401  (_Prompt: the prompts _CallOptions carries)
 from ._stream import STOP_ALL_SEP, STOP_NEVER, _WindowStream
 from .streampool import TeacherStreamPool
 from .window import WindowSchedule
@@ -156,22 +156,6 @@ class _StagingRing:
             ev.record(st)
         e["ev"] = ev
         return dview, e, st
-
-
-class _Prompt:
-    """A batch of per-clip text prefixes on the device (include/gitcap.h: gitcap_attach_prompt): ids int64 [B, P] with CLS at
-    column 0, lengths int32 [B] (valid tokens per clip, CLS included), and the host's copy of the lengths."""
-
-    def __init__(self, ids, lengths, host_lengths):
-        self.ids, self.lengths, self.host_lengths = ids, lengths, host_lengths
-        self.min_len, self.max_len = min(host_lengths), max(host_lengths)
-
-    def rows(self, r0, r1):
-        return _Prompt(self.ids[r0:r1].contiguous(), self.lengths[r0:r1].contiguous(), self.host_lengths[r0:r1])
-
-    def attach(self, model):
-        """The one-shot attachment the NEXT greedy- or beam-family call consumes (a repeated call attaches again)."""
-        model._call("gitcap_attach_prompt", _lib.ptr(self.ids), self.ids.shape[1], _lib.ptr(self.lengths), self.min_len, self.max_len)
 
 
 class _Constraints:
@@ -778,38 +762,6 @@ class GitCaptioner(_NativeModule):
         if len(sup) + max_len + need > self.cfg.vocab_size:
             raise ValueError(f"{len(sup)} suppressed ids over {max_len} steps could ban every column of a row (vocab_size {self.cfg.vocab_size})")
         return _Constraints(self, n, m, sup)
-
-    def _prompt(self, prompt, prompt_lengths, B, limit, what):
-        """The ``prompt=`` argument of the decoding calls -> _Prompt or None.  prompt: int64 [B, P] (every row P tokens, or
-        ``prompt_lengths`` [B] valid tokens per row) or a list of B 1-D tensors (ragged).  CLS is prepended to a row that does not
-        start with it (the lengths then count it).  A set-up step: the lengths are read on the host."""
-        if prompt is None:
-            if prompt_lengths is not None:
-                raise ValueError("prompt_lengths without prompt")
-            return None
-        if isinstance(prompt, torch.Tensor):
-            if prompt.dim() != 2:
-                raise ValueError(f"prompt must be [B, P] or a list of B 1-D tensors, got {tuple(prompt.shape)}")
-            lens = [prompt.shape[1]] * prompt.shape[0] if prompt_lengths is None else [int(v) for v in torch.as_tensor(prompt_lengths).tolist()]
-            if len(lens) != prompt.shape[0] or any(not 0 <= n <= prompt.shape[1] for n in lens):
-                raise ValueError("prompt_lengths must hold one length in [0, P] per row of prompt")
-            host = prompt.detach().to("cpu", torch.int64)
-            rows = [host[b, :n] for b, n in enumerate(lens)]
-        else:
-            if prompt_lengths is not None:
-                raise ValueError("prompt_lengths goes with a [B, P] tensor; a list of rows carries its own lengths")
-            rows = [torch.as_tensor(r).detach().to("cpu", torch.int64).reshape(-1) for r in prompt]
-        if len(rows) != B:
-            raise ValueError(f"prompt has {len(rows)} rows for a batch of {B} clips")
-        cls = self.cls_token_id
-        rows = [r if r.numel() and int(r[0]) == cls else torch.cat([torch.tensor([cls], dtype=torch.int64), r]) for r in rows]
-        lens = [int(r.numel()) for r in rows]
-        if max(lens) > limit:
-            raise ValueError(f"a prompt of {max(lens)} tokens (CLS included) exceeds {what} = {limit}")
-        ids = torch.full((B, max(lens)), cls, dtype=torch.int64)
-        for b, r in enumerate(rows):
-            ids[b, :lens[b]] = r
-        return _Prompt(ids.to(self._dev), torch.tensor(lens, dtype=torch.int32).to(self._dev), lens)
 
     def _ids(self, y: torch.Tensor) -> torch.Tensor:
         return y.to(device=self._dev, dtype=torch.int64).contiguous()

@@ -132,13 +132,59 @@ class _StreamPool:
 
 class StudentStreamPool(_StreamPool):
     """The pool of StudentCaptioner.stream_pool: windows of ``mem_tokens`` frames; greedy captions only.  ``constraints``
-    (stream_pool's constraint arguments, or None): one set of rules for every stream, attached again for every pool call."""
+    (stream_pool's constraint arguments, or None): one set of rules for every stream, attached again for every pool call.
+    ``set_prompt(stream, ids)``: a standing text prefix per camera (include/gitcap.h: gitcap_student_attach_prompt); a pool call
+    attaches the ragged table of the cameras it captions, a camera without one being the row of CLS alone, and
+    ``last_prompt_lengths[stream]`` holds the prompt tokens (CLS included) of that camera's latest caption."""
 
     _WHAT = "mem_tokens"
 
     def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None):
         self._co = constraints
+        self._prompts = {}                  # stream -> its prompt, int64 1-D on the CPU, CLS first
+        self.last_prompt_lengths = {}
         super().__init__(model, streams, model.cfg.mem_tokens, hop, max_len, mode, logprobs, top_logprobs, min_frames)
+
+    def _last_dicts(self):
+        return super()._last_dicts() + (self.last_prompt_lengths,)
+
+    def set_prompt(self, stream: int, ids):
+        """The prompt of one camera from its next caption on: ``ids`` 1-D token ids (CLS is prepended where missing; at most max_len
+        tokens with it), or None for no prompt.  It stays until replaced; ``drop(stream)`` does not remove it."""
+        self._check_live()
+        s = int(stream)
+        if not 0 <= s < self._sched.streams:
+            raise ValueError(f"stream {s} outside 0..{self._sched.streams - 1}")
+        if ids is None:
+            self._prompts.pop(s, None)
+            return
+        row = torch.as_tensor(ids)
+        if row.dim() != 1:
+            raise ValueError(f"a camera's prompt is 1-D token ids, got {tuple(row.shape)}")
+        pr = self._m._prompt([row], None, 1, self._max_len, "max_len")          # the shared normaliser: CLS, the length limit
+        self._prompts[s] = pr.ids[0].cpu()
+
+    def _chunk_prompt(self, ids):
+        """The ragged prompt table of one pool call over streams `ids`, or None when none of them has a prompt"""
+        if not any(s in self._prompts for s in ids):
+            return None
+        cls = torch.tensor([self._m.cls_token_id], dtype=torch.int64)
+        return self._m._prompt([self._prompts.get(s, cls) for s in ids], None, len(ids), self._max_len, "max_len")
+
+    def _deliver(self, out, chunk, ids, lp, tk, seen, to_cpu, sep):
+        """The cut behind a row's own first SEP looks at what the model emitted: a SEP inside a camera's prompt does not end its row."""
+        if self._mode != STOP_ALL_SEP or all(self.last_prompt_lengths.get(s, 1) == 1 for s in chunk):
+            return super()._deliver(out, chunk, ids, lp, tk, seen, to_cpu, sep)
+        host = ids.cpu()
+        for r, s in enumerate(chunk):
+            p = self.last_prompt_lengths[s]
+            n = p - 1 + cut_at_sep(host[r, p - 1:], sep)
+            out[s] = ids[r, :1 + n]
+            self.last_frames[s] = int(seen[r])
+            if lp is not None:
+                self.last_logprobs[s] = lp[r, :n]
+            if tk is not None:
+                self.last_top_ids[s], self.last_top_logprobs[s] = tk[0][r, :n], tk[1][r, :n]
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -167,7 +213,12 @@ class StudentStreamPool(_StreamPool):
             m._attach_logprobs(lp, tk)
             if self._co is not None:
                 self._co.attach(m)
+            pr = self._chunk_prompt(ids)
+            if pr is not None:
+                pr.attach(m)
             m._call("gitcap_student_pool_greedy", (ctypes.c_int32 * B)(*ids), B, self._max_len, self._mode, _lib.ptr(out), None, seen, m._stream())
+        for r, s in enumerate(ids):
+            self.last_prompt_lengths[s] = 1 if pr is None else pr.host_lengths[r]
         return out, lp, tk, list(seen)
 
     def _prepare(self, frames: torch.Tensor) -> torch.Tensor:

@@ -61,16 +61,39 @@ class StudentCaptionStream(_WindowStream):
     are encoded and counted; a push of camera frames with none admitted returns None and costs one distance launch.  With
     ``carry`` a greedy stream offers its previous caption as the draft of the next window call
     (gitcap_student_window_greedy_draft): same captions, and a caption that repeats costs one pass instead of a token loop.
-    ``constraints`` (a _StudentConstraints or None): the stream's hard constraints, attached again for every caption."""
+    ``constraints`` (a _StudentConstraints or None): the stream's hard constraints, attached again for every caption.
+    ``prompt`` (caption_stream's ``prompt=``, or None): one text prefix per stream row, attached again for every caption; the
+    ``prompt`` property replaces it (None: no prompt from the next caption on) and ``prompt_lengths`` [batch] tells how many leading
+    tokens of every caption row are the prompt's (CLS included; None without a prompt)."""
 
     def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0, partial=False,
-                 constraints=None):
+                 constraints=None, prompt=None):
         self._carry, self._prev, self._beams = bool(carry), None, beams
         self._co = constraints
+        self._batch = int(batch)
+        self._pr = None
+        self._m, self._max_len = model, max_len          # (the prompt setter needs them; the base class sets them again)
+        self.prompt = prompt
         self._partial = bool(partial)
         self.last_frames = None          # frames per clip the caption of the last push saw (mem_tokens unless partial=True)
         self._stats = dict(captions=0, draft_tokens=0, accepted=0, tail_steps=0)
         super().__init__(model, WindowSchedule(batch, model.cfg.mem_tokens, hop, partial=self._partial), max_len, mode, gate, logprobs, top_logprobs)
+
+    @property
+    def prompt(self):
+        """The stream's prompt as normalised ids int64 [batch, P] on the device (CLS first; rows padded with CLS), or None."""
+        return None if self._pr is None else self._pr.ids
+
+    @prompt.setter
+    def prompt(self, value):
+        if value is not None and self._carry:
+            raise ValueError("carry=True is not combined with prompt= or the constraint arguments")
+        limit = self._max_len if self._beams is None else self._max_len - 1
+        self._pr = self._m._prompt(value, None, self._batch, limit, "max_len" if self._beams is None else "max_len - 1")
+
+    @property
+    def prompt_lengths(self):
+        return None if self._pr is None else self._pr.lengths
 
     def _reset_lib(self):
         with torch.cuda.device(self._m._dev):
@@ -123,6 +146,8 @@ class StudentCaptionStream(_WindowStream):
                     m._attach_logprobs(lp, tk)
                     if self._co is not None:
                         self._co.attach(m)
+                    if self._pr is not None:
+                        self._pr.attach(m)
                     if self._partial:            # whatever the window holds; a full one is the plain call
                         seen = ctypes.c_int32(0)
                         m._call("gitcap_student_window_greedy_partial", self._max_len, self._mode, _lib.ptr(ids), _lib.ptr(steps),
@@ -140,6 +165,8 @@ class StudentCaptionStream(_WindowStream):
                 ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 if self._co is not None:
                     self._co.attach(m)
+                if self._pr is not None:
+                    self._pr.attach(m)
                 m._call("gitcap_student_window_beam_search", self._beams, self._max_len, _lib.ptr(ids), m._stream())
                 out = ids.cpu() if to_cpu else ids
         if not self._partial:
@@ -547,7 +574,7 @@ class StudentCaptioner(_NativeModule):
     def greedy_decode(self, src: torch.Tensor, max_len: int = 10, stop: Optional[str] = None,
                       draft: Optional[torch.Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0,
                       return_attention: bool = False, frame_counts=None, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                      suppress_tokens=None):
+                      suppress_tokens=None, prompt=None, prompt_lengths=None):
         """model.py:156-187.  ``src``: frames [B,F,C,H,W] (needs ``image_encoder``; a native one keeps the memory on the
         device and also takes uint8 camera frames [B,F,H,W,3]) or memory [B,F,D].
         Returns int64 [B, 1+steps] starting with CLS, on ``src``'s device.
@@ -570,10 +597,16 @@ class StudentCaptioner(_NativeModule):
         gitcap_student_attach_constraints; HF's NoRepeatNGram / MinLength / SuppressTokens processors): no n-gram of the row so far
         (CLS included) twice, no SEP while the row is shorter than min_length (CLS counts), and up to 256 ids never.  Banned columns
         are -inf before the arg-max, so ``return_logprobs`` / ``top_logprobs`` are those of the renormalised row and never name a
-        banned id.  The loop keeps decoding behind a row's SEP and the rules keep applying there.  Not combined with ``draft``."""
+        banned id.  The loop keeps decoding behind a row's SEP and the rules keep applying there.  Not combined with ``draft``.
+        prompt / prompt_lengths: a text prefix per clip (include/gitcap.h: gitcap_student_attach_prompt; GitCaptioner.greedy_decode's
+        argument): int64 [B, P], optionally with prompt_lengths [B], or a list of B 1-D tensors of different lengths; CLS is
+        prepended where missing, and a row of CLS alone has no prompt.  The result includes the prompt: row b starts with its
+        lengths[b] prompt tokens and the model's tokens follow; log-probabilities are 0.0 at a prompt's positions, ``top_logprobs``
+        reports the model's own ranks there, a prompt token is emitted even when a constraint bans it and does not count for the
+        stop rule.  At most max_len tokens (CLS included).  Not combined with ``draft``."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
-        if draft is not None and _constrained(no_repeat_ngram_size, min_length, suppress_tokens):
+        if draft is not None and (prompt is not None or _constrained(no_repeat_ngram_size, min_length, suppress_tokens)):
             raise ValueError("draft= is not combined with prompt= or the constraint arguments")
         counts = None
         if self._is_ragged(src, frame_counts):
@@ -587,6 +620,7 @@ class StudentCaptioner(_NativeModule):
             raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
         co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+        pr = self._prompt(prompt, prompt_lengths, B, max_len, "max_len")
         ids = torch.empty((B, max_len + 1), dtype=torch.int64, device=self._dev)
         steps = torch.zeros(1, dtype=torch.int32, device=self._dev)
         lp = torch.empty((B, max_len), dtype=torch.float32, device=self._dev) if return_logprobs else None
@@ -602,6 +636,8 @@ class StudentCaptioner(_NativeModule):
                 self._attach_logprobs(lp, tk)
                 if co is not None:
                     co.attach(self)
+                if pr is not None:
+                    pr.attach(self)
                 self._call("gitcap_student_greedy", _lib.ptr(mem), B, max_len, mode, _lib.ptr(ids), _lib.ptr(steps), self._stream())
         n = int(steps.item()) if mode == STOP_ALL_SEP else max_len
         ids = ids[:, :1 + n]
@@ -624,14 +660,18 @@ class StudentCaptioner(_NativeModule):
 
     @torch.no_grad()
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False, frame_counts=None,
-                    no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None) -> torch.Tensor:
+                    no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, prompt=None,
+                    prompt_lengths=None) -> torch.Tensor:
         """model.py:189-318: k beams without end-of-sequence handling; returns the best beam [B, max_len].
         Runs on the device with the exact KV cache and no host round trip (``gitcap_student_beam_search``): the k beams
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams.  frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length; the k
         beams of a clip share its memory rows.
         no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): every beam row's banned columns are -inf ahead of
-        the log-softmax, so the scores renormalise over the allowed columns."""
+        the log-softmax, so the scores renormalise over the allowed columns.
+        prompt / prompt_lengths (as in greedy_decode; at most max_len - 1 tokens, CLS included): every beam of clip b starts from its
+        prompt -- the search ranks nothing while the clip is inside it and the scores start behind it as they start behind CLS --
+        and max_len counts the prompt; the result includes it."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the beam family (beam_search) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         counts = None
@@ -649,11 +689,14 @@ class StudentCaptioner(_NativeModule):
         if max_len < 2 or k < 1 or k > 16:
             raise ValueError("beam_search needs max_len >= 2 and 1 <= k <= 16")
         co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, k)
+        pr = self._prompt(prompt, prompt_lengths, B, max_len - 1, "max_len - 1")
         best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
         with torch.cuda.device(self._dev):
             self._attach_counts(counts)
             if co is not None:
                 co.attach(self)
+            if pr is not None:
+                pr.attach(self)
             self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, _lib.ptr(best), self._stream())
         return best.to(out_dev) if out_dev != best.device else best
 
@@ -661,7 +704,7 @@ class StudentCaptioner(_NativeModule):
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
                        logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False,
                        partial: bool = False, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                       suppress_tokens=None) -> StudentCaptionStream:
+                       suppress_tokens=None, prompt=None) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -682,7 +725,10 @@ class StudentCaptioner(_NativeModule):
         caption saw.  Works with ``gate``, ``logprobs`` and ``top_logprobs``; not with ``carry`` or ``beams``, whose window calls
         need a full window (include/gitcap.h: gitcap_student_window_greedy_partial).
         no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode / beam_search): the stream's constraints, attached
-        again for every caption, greedy or ``beams``; not with ``carry`` (a draft call does not take them)."""
+        again for every caption, greedy or ``beams``; not with ``carry`` (a draft call does not take them).
+        ``prompt`` (as in greedy_decode: [batch, P] or a list of `batch` 1-D tensors): one text prefix per stream row, kept for the
+        stream's life and attached again for every caption, greedy or ``beams``; ``stream.prompt = ...`` replaces it,
+        ``stream.prompt_lengths`` tells what of a caption row is prompt.  Not with ``carry``."""
         if return_attention:
             raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
@@ -693,7 +739,7 @@ class StudentCaptioner(_NativeModule):
             raise ValueError("logprobs=True is for greedy streams: it cannot be combined with beams")
         if carry and beams is not None:
             raise ValueError("carry=True verifies the previous greedy caption: it cannot be combined with beams")
-        if carry and _constrained(no_repeat_ngram_size, min_length, suppress_tokens):
+        if carry and (prompt is not None or _constrained(no_repeat_ngram_size, min_length, suppress_tokens)):
             raise ValueError("carry=True is not combined with prompt= or the constraint arguments")
         if partial and (carry or beams is not None):
             raise ValueError("partial=True is for greedy streams without carry: the beam and draft window calls need a full window")
@@ -716,7 +762,7 @@ class StudentCaptioner(_NativeModule):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
         co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, 1 if beams is None else beams)
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial, co)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial, co, prompt)
 
     def stream_pool(self, streams: int, hop: int = 1, max_len: int = 25, stop: Optional[str] = None, logprobs: bool = False,
                     top_logprobs: int = 0, min_frames: int = 1, no_repeat_ngram_size: int = 0, min_length: int = 0,
@@ -738,7 +784,10 @@ class StudentCaptioner(_NativeModule):
         Out of scope: scene-change gates (put one FrameGate per camera in front of ``push``; deciding all cameras' gates in one
         launch is a later change), ``carry`` / drafts and beams.
         no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): one set of rules for every camera's captions,
-        attached again for every pool call; rules per camera are out of scope."""
+        attached again for every pool call; rules per camera are out of scope.
+        ``pool.set_prompt(stream, ids)``: a standing text prefix for one camera (ids 1-D, CLS prepended where missing; None removes
+        it), kept until replaced; every pool call attaches the ragged table of the cameras it captions, and a camera's caption is
+        greedy_decode(prompt=[ids]) on its frames.  ``pool.last_prompt_lengths[stream]`` = the prompt tokens of its latest caption."""
         if not 0 <= int(top_logprobs) <= 32:
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if streams < 1 or streams > 4096:
@@ -751,10 +800,12 @@ class StudentCaptioner(_NativeModule):
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None) -> torch.Tensor:
+                         suppress_tokens=None, prompt=None, prompt_lengths=None) -> torch.Tensor:
         """The same search driven from the host the way the reference writes it (every step recomputes the whole prefix
         through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests.  The constraint
-        arguments (as in beam_search) set every row's banned logits to -inf ahead of the log_softmax."""
+        arguments (as in beam_search) set every row's banned logits to -inf ahead of the log_softmax.
+        prompt / prompt_lengths (as in beam_search): the search of every clip starts from its own prefix instead of the lone CLS;
+        prompts of different lengths are searched clip by clip (the reference's loop advances all rows in lockstep)."""
         from .search import banned_tokens, check_constraints
         cn, cm, sup = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
         V, sep = self.cfg.vocab_length, self.cfg.sep_token_id
@@ -777,12 +828,18 @@ class StudentCaptioner(_NativeModule):
             raise ValueError(f"B*k={B * k} rows > max_batch={self.max_batch}")
         if max_len - 1 > self.max_text_len:
             raise ValueError(f"max_len={max_len} exceeds max_text_len+1={self.max_text_len + 1}")
-        tgt = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev)
+        pr = self._prompt(prompt, prompt_lengths, B, max_len - 1, "max_len - 1")
+        if pr is not None and pr.min_len != pr.max_len:
+            rows = [self.beam_search_host(mem[b:b + 1], max_len, k, no_repeat_ngram_size, min_length, suppress_tokens,
+                                          prompt=pr.ids[b:b + 1, :pr.host_lengths[b]]) for b in range(B)]
+            best = torch.cat(rows, 0)
+            return best.to(out_dev) if out_dev != best.device else best
+        tgt = torch.full((B, 1), self.cls_token_id, dtype=torch.long, device=self._dev) if pr is None else pr.ids[:, :pr.max_len]
         logp = torch.log_softmax(rule(self.forward_decoder(tgt, mem)[:, -1], tgt), dim=-1)  # model.py:221-225
         scores, top = logp.topk(k, dim=-1)
-        seqs = torch.cat([tgt.unsqueeze(1).expand(-1, k, -1), top.unsqueeze(-1)], dim=-1)  # [B, k, 2]
+        seqs = torch.cat([tgt.unsqueeze(1).expand(-1, k, -1), top.unsqueeze(-1)], dim=-1)  # [B, k, 2] (a prompt: [B, k, P + 1])
         mem_rep = mem.repeat_interleave(k, dim=0)                                          # row b*k + i = beam i of clip b
-        for _ in range(2, max_len):                                                        # model.py:230
+        for _ in range(tgt.shape[1] + 1, max_len):                                         # model.py:230
             rows = seqs.reshape(B * k, -1)
             lp = torch.log_softmax(rule(self.forward_decoder(rows, mem_rep)[:, -1], rows), dim=-1)
             ts, ti = lp.view(B, k, -1).topk(k, dim=-1)                                     # each beam's top-k
