@@ -203,10 +203,10 @@ struct gitcap : HandleCore {
     // window: pool_ring = the fp32 ln_post rows (no temporal embedding) of pool_S independent streams, [pool_S][F][N][Dv]; pool (one
     // RingCursor per stream) = where a stream's next frame goes and how many it holds.  pool_tab (device int32 [3][pool_cap]): the
     // ring frame of each packed frame of one push, then src / pos of each packed frame of one pool call (host_logic.h: pool_plan),
-    // filled from the page-locked pool_push_host / pool_call_host behind an event each.  pool_order: win_order's discipline.
+    // staged in pool_push_host / pool_call_host.  pool_order: win_order's discipline.
     float* pool_ring = nullptr;
-    int32_t *pool_tab = nullptr, *pool_push_host = nullptr, *pool_call_host = nullptr;
-    hipEvent_t pool_push_ev = nullptr, pool_call_ev = nullptr;
+    int32_t* pool_tab = nullptr;
+    HostStage pool_push_host, pool_call_host;
     int pool_S = 0, pool_F = 0, pool_cap = 0;
     int64_t pool_bytes = 0;
     std::vector<RingCursor> pool;
@@ -248,14 +248,14 @@ std::atomic<unsigned> g_ln_spin_limit{0};
 
 void select_slot(gitcap* h, int i) { h->cur_slot = i; }
 
-// the stream pool's buffers (the caller has made sure nothing in flight uses them); the events stay for the next reset
+// the stream pool's buffers (the caller has made sure nothing in flight uses them); pool_order's events stay for the next reset
 void pool_free(gitcap* h) {
     if (h->pool_ring) (void)hipFree(h->pool_ring);
     if (h->pool_tab) (void)hipFree(h->pool_tab);
-    if (h->pool_push_host) (void)hipHostFree(h->pool_push_host);
-    if (h->pool_call_host) (void)hipHostFree(h->pool_call_host);
+    h->pool_push_host.destroy();
+    h->pool_call_host.destroy();
     h->pool_ring = nullptr;
-    h->pool_tab = h->pool_push_host = h->pool_call_host = nullptr;
+    h->pool_tab = nullptr;
     h->pool_bytes = 0;
     h->pool_S = h->pool_F = h->pool_cap = 0;
     h->pool.clear();
@@ -968,8 +968,6 @@ void gitcap_destroy(gitcap_t* h) {
     h->win_order.destroy();
     if (h->win_ring) (void)hipFree(h->win_ring);
     pool_free(h);
-    if (h->pool_push_ev) (void)hipEventDestroy(h->pool_push_ev);
-    if (h->pool_call_ev) (void)hipEventDestroy(h->pool_call_ev);
     h->pool_order.destroy();
     free_allocs(*h);
     if (h->ln_fail) (void)hipHostFree(h->ln_fail);
@@ -1844,12 +1842,10 @@ int gitcap_pool_reset(gitcap_t* h, int n_streams, int F) {
     if (!h->pool_ring) {
         const size_t cap = (size_t)h->c.max_batch * h->c.max_frames;
         HIP_OK(h, h->pool_order.ensure());
-        if (!h->pool_push_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_push_ev, hipEventDisableTiming));
-        if (!h->pool_call_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_call_ev, hipEventDisableTiming));
         hipError_t e = hipMalloc((void**)&h->pool_ring, (size_t)ring_bytes);
         if (e == hipSuccess) e = hipMalloc((void**)&h->pool_tab, 3 * cap * sizeof(int32_t));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_push_host, cap * sizeof(int32_t), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_call_host, 2 * cap * sizeof(int32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = h->pool_push_host.ensure(cap);
+        if (e == hipSuccess) e = h->pool_call_host.ensure(2 * cap);
         if (e != hipSuccess) {
             pool_free(h);
             return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc stream pool: ") + hipGetErrorString(e));
@@ -1891,15 +1887,15 @@ static int pool_push(gitcap* h, const char* who, FrameSrc src, const int32_t* st
     if (const int why = pool_plan(after, stream_ids, n, dst.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, &plan, &bad))
         return fail(h, GITCAP_ERR_ARG, pool_refused(h, who, "frame", why, bad, stream_ids[bad]));
     select_slot(h, 0);
-    HIP_OK(h, hipEventSynchronize(h->pool_push_ev));        // the previous push's transfer has read the page-locked table
-    memcpy(h->pool_push_host, dst.data(), (size_t)n * sizeof(int32_t));
+    HIP_OK(h, h->pool_push_host.wait());
+    memcpy(h->pool_push_host.p, dst.data(), (size_t)n * sizeof(int32_t));
     HIP_OK(h, join_async(h, s));
     HIP_OK(h, h->pool_order.before_push(s));
     HIP_OK(h, h->win_order.before_push(s));         // (the window's pushes and calls use the same encoder workspace)
     // From here on ring frames may be half written: a failure empties the streams this push names.
     auto enqueue = [&]() -> int {
-        HIP_OK(h, hipMemcpyAsync(h->pool_tab, h->pool_push_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_OK(h, hipEventRecord(h->pool_push_ev, s));
+        HIP_OK(h, h->pool_push_host.copy(h->pool_tab, 0, (size_t)n, s));
+        HIP_OK(h, h->pool_push_host.mark(s));
         float* stage = (float*)h->qkv;              // window_push's staging: dead behind the last block's attention
         if (int rc = encode_frames(h, src, n, 1, stage, nullptr, false, s)) return rc;
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, 8.0 * n * (double)h->N * h->Dv);
@@ -1949,16 +1945,16 @@ static int pool_prefix(gitcap* h, const char* who, const int32_t* stream_ids, in
         return fail(h, why == POOL_PLAN_EMPTY ? GITCAP_ERR_STATE : GITCAP_ERR_ARG, pool_refused(h, who, "row", why, bad, stream_ids[bad]));
     if (plan.total > cap) return fail(h, GITCAP_ERR_ARG, w + ": the named streams hold more than max_batch * max_frames frames");
     select_slot(h, 0);
-    HIP_OK(h, hipEventSynchronize(h->pool_call_ev));        // the previous call's transfer has read the page-locked table
-    memcpy(h->pool_call_host, src, (size_t)plan.total * sizeof(int32_t));
-    memcpy(h->pool_call_host + cap, pos, (size_t)plan.total * sizeof(int32_t));
+    HIP_OK(h, h->pool_call_host.wait());
+    memcpy(h->pool_call_host.p, src, (size_t)plan.total * sizeof(int32_t));
+    memcpy(h->pool_call_host.p + cap, pos, (size_t)plan.total * sizeof(int32_t));
     HIP_OK(h, join_async(h, s));
     HIP_OK(h, h->pool_order.before_read(s));
     cur(h).have = false;
     int32_t *d_src = h->pool_tab + cap, *d_pos = h->pool_tab + 2 * (size_t)cap;
-    HIP_OK(h, hipMemcpyAsync(d_src, h->pool_call_host, (size_t)plan.total * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipMemcpyAsync(d_pos, h->pool_call_host + cap, (size_t)plan.total * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipEventRecord(h->pool_call_ev, s));
+    HIP_OK(h, h->pool_call_host.copy(d_src, 0, (size_t)plan.total, s));
+    HIP_OK(h, h->pool_call_host.copy(d_pos, (size_t)cap, (size_t)plan.total, s));
+    HIP_OK(h, h->pool_call_host.mark(s));
     {
         ProfScope ps(h, GITCAP_PROF_ROWOPS, s, 0.0, (double)plan.total * N * h->Dv * (4.0 + 2.0));
         HIP_OK(h, launch_pool_assemble(PoolAssembleArgs{h->pool_ring, h->c.num_frames > 0 ? h->temporal : nullptr, d_src, d_pos, h->hb,

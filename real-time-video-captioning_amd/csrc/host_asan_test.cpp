@@ -98,8 +98,52 @@ static int topk_opts_test() {
     return 0;
 }
 
+// The student's record (StudentOpts) under the same take_opts: one row per family of gitcap_student_* entry points -- what it takes,
+// what it refuses, what of five attachments is reported as refused and what stays pending behind it.
+static int student_opts_test() {
+    float lp[1], tlp[1]; int64_t tid[1]; const int64_t ids[1] = {0}; const int32_t len[1] = {1};
+    const unsigned ALL = OPT_LP | OPT_TK | OPT_CO | OPT_PR | OPT_FC, GREEDY = OPT_LP | OPT_TK | OPT_CO | OPT_PR, DRAFT = OPT_PR | OPT_CO | OPT_TK;
+    struct Row { unsigned take, refuse, refused, left; } rows[] = {
+        {GREEDY | OPT_FC, 0, 0, 0},                         // student_greedy
+        {GREEDY, OPT_FC, OPT_FC, 0},                        // student_window_greedy, _partial
+        {OPT_LP | OPT_FC, DRAFT, DRAFT, 0},                 // student_greedy_draft
+        {OPT_LP, OPT_FC | DRAFT, OPT_FC | DRAFT, 0},        // student_window_greedy_draft
+        {GREEDY, OPT_FC, OPT_FC, 0},                        // student_pool_greedy
+        {OPT_FC | OPT_CO | OPT_PR, 0, 0, OPT_LP | OPT_TK},  // student_beam_search
+        {OPT_CO | OPT_PR, OPT_FC, OPT_FC, OPT_LP | OPT_TK}, // student_window_beam_search
+        {OPT_TK, 0, 0, ALL & ~OPT_TK},                      // student_score
+        {OPT_FC, 0, 0, ALL & ~OPT_FC},                      // student_set_memory
+        {0, OPT_FC, OPT_FC, ALL & ~OPT_FC},                 // student_window_reset, _push, student_pool_reset, _push
+        {0, 0, 0, ALL},                                     // student_pool_drop, _counts, _attention, _forward_decoder
+    };
+    for (const Row& r : rows) {
+        StudentOpts pending;
+        CHECK(opts_set(pending) == 0);
+        pending.lp = LpAttach{lp, 8};
+        pending.tk = TopkAttach{8, tid, tlp, 20};
+        pending.co = ConsOpt{true, 2, 0, len, 1};
+        pending.pr = PromptArgs{ids, 4, len, 1, 3};
+        pending.fc.assign(300, 7);                          // more clips than RaggedCounts holds
+        CHECK(opts_set(pending) == ALL);
+        unsigned refused = 99;
+        const StudentOpts got = take_opts(pending, r.take, r.refuse, &refused);
+        CHECK(refused == r.refused && opts_set(got) == r.take && opts_set(pending) == r.left);
+        if (r.take & OPT_FC) CHECK(got.fc.size() == 300 && got.fc[299] == 7);
+        if (r.take & OPT_TK) CHECK(got.tk.k == 8 && got.tk.ids == tid && got.tk.lp == tlp && got.tk.ld == 20);
+        if (r.left & OPT_LP) CHECK(pending.lp.p == lp && pending.lp.ld == 8);
+        if (r.left & OPT_TK) CHECK(pending.tk.k == 8 && pending.tk.ld == 20);
+        if (r.left & OPT_CO) CHECK(pending.co.on && pending.co.ngram == 2 && pending.co.suppress == len);
+        if (r.left & OPT_PR) CHECK(pending.pr.ids == ids && pending.pr.max_len == 3);
+        if (r.left & OPT_FC) CHECK(pending.fc.size() == 300 && pending.fc[0] == 7);
+        // a second call finds nothing to take or refuse, and what stayed pending is intact
+        (void)take_opts(pending, r.take, r.refuse, &refused);
+        CHECK(refused == 0 && opts_set(pending) == r.left);
+    }
+    return 0;
+}
+
 int main() {
-    if (topk_opts_test()) return 1;
+    if (topk_opts_test() || student_opts_test()) return 1;
     // e4m3: every finite code round-trips through value -> exact code
     for (int code = 0; code < 256; ++code) {
         const float v = host_e4m3_value(code);

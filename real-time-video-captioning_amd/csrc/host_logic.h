@@ -266,11 +266,25 @@ inline void opts_clear(CallOpts& o, unsigned parts) {
     if (parts & OPT_FC) o.fc.B = 0;
     if (parts & OPT_TK) o.tk = TopkAttach{};
 }
+// The student's record (gitcap_student_attach_*): the same parts without search options, and counts that are a vector -- its max_rows
+// may exceed the 256 clips RaggedCounts holds (empty: none; an empty vector is copied without an allocation).
+struct StudentOpts { LpAttach lp{}; TopkAttach tk{}; ConsOpt co{}; PromptArgs pr{}; std::vector<int32_t> fc; };
+inline unsigned opts_set(const StudentOpts& o) {
+    return (o.lp.p ? OPT_LP : 0u) | (o.pr.ids ? OPT_PR : 0u) | (o.co.on ? OPT_CO : 0u) | (!o.fc.empty() ? OPT_FC : 0u) | (o.tk.k != 0 ? OPT_TK : 0u);
+}
+inline void opts_clear(StudentOpts& o, unsigned parts) {
+    if (parts & OPT_LP) o.lp = LpAttach{};
+    if (parts & OPT_PR) o.pr = PromptArgs{};
+    if (parts & OPT_CO) o.co = ConsOpt{};
+    if (parts & OPT_FC) o.fc.clear();
+    if (parts & OPT_TK) o.tk = TopkAttach{};
+}
 // The parts in `take` move out of `pending` into the result (consumed, whatever becomes of the call); the parts in `refuse` are
-// cleared, *refused = those of them that held an attachment; every other part stays pending.
-inline CallOpts take_opts(CallOpts& pending, unsigned take, unsigned refuse, unsigned* refused) {
+// cleared, *refused = those of them that held an attachment; every other part stays pending.  (CallOpts or StudentOpts.)
+template <class Opts>
+Opts take_opts(Opts& pending, unsigned take, unsigned refuse, unsigned* refused) {
     *refused = opts_set(pending) & refuse;
-    CallOpts out = pending;
+    Opts out = pending;
     opts_clear(out, ~take);
     opts_clear(pending, take | refuse);
     return out;

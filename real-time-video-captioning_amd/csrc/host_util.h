@@ -137,3 +137,19 @@ struct RingOrder {
         ev_ring = ev_read = nullptr;
     }
 };
+
+// A table the host plans for a launch, on its way to the device: one page-locked int32 buffer and the event "the previous transfer
+// has read it".  Every use is wait(), fill p, copy() once or more, mark(); the device buffer is the user's.
+struct HostStage {
+    int32_t* p = nullptr;
+    hipEvent_t ev = nullptr;
+    hipError_t ensure(size_t words) {       // lazy create
+        const hipError_t e = p ? hipSuccess : hipHostMalloc((void**)&p, words * sizeof(int32_t), hipHostMallocDefault);
+        return e != hipSuccess || ev ? e : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    }
+    hipError_t wait() { return ev ? hipEventSynchronize(ev) : hipSuccess; }        // (an event never recorded is complete)
+    // words o .. o + n - 1 -> dev
+    hipError_t copy(int32_t* dev, size_t o, size_t n, hipStream_t s) { return hipMemcpyAsync(dev, p + o, n * sizeof(int32_t), hipMemcpyHostToDevice, s); }
+    hipError_t mark(hipStream_t s) { return hipEventRecord(ev, s); }
+    void destroy() { if (p) (void)hipHostFree(p); if (ev) (void)hipEventDestroy(ev); p = nullptr; ev = nullptr; }
+};

@@ -15,6 +15,7 @@
 #include "student_internal.h"
 #include "prompt_sel.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -369,15 +370,14 @@ struct gitcap_student : HandleCore {
     unsigned* acc_ticket = nullptr;
     int32_t* acc_host = nullptr;
     hipEvent_t acc_ev = nullptr;
-    // token log-probabilities (gitcap_student_attach_token_logprobs): lp_attach = the pending one-shot attachment; the first
-    // attach allocates amax_sum (the head's third partial, sized as amax_val), acc_lp (draft_accept_kernel's hand-over words) and
-    // g_lp, the handle's own [B][max_len] rows the captured loops write (copied to the caller's buffer behind the replay, like g_ids)
-    LpAttach lp_attach{};
+    StudentOpts pending;        // the one-shot attachments of gitcap_student_attach_* (host_logic.h); entry points take them through take()
+    // token log-probabilities (gitcap_student_attach_token_logprobs): the first attach allocates amax_sum (the head's third partial,
+    // sized as amax_val), acc_lp (draft_accept_kernel's hand-over words) and g_lp, the handle's own [B][max_len] rows the captured
+    // loops write (copied to the caller's buffer behind the replay, like g_ids)
     float *amax_sum = nullptr, *g_lp = nullptr;
     int* acc_lp = nullptr;
-    // top-k alternatives (gitcap_student_attach_top_logprobs): tk_attach = the pending one-shot attachment; the first attach allocates
-    // amax_sum and g_tk_ids / g_tk_lp, the handle's own [B][max_len][k] rows the captured loops write (copied out like g_lp)
-    TopkAttach tk_attach{};
+    // top-k alternatives (gitcap_student_attach_top_logprobs): the first attach allocates amax_sum and g_tk_ids / g_tk_lp, the
+    // handle's own [B][max_len][k] rows the captured loops write (copied out like g_lp)
     int64_t* g_tk_ids = nullptr;
     float* g_tk_lp = nullptr;
     float* score_buf = nullptr;         // gitcap_student_score (first use): [2][Mt] target logits, lp rows the caller did not ask for
@@ -385,30 +385,25 @@ struct gitcap_student : HandleCore {
     // writes them (one more launch per layer behind the cross-attention q projection), off for every other call
     float* att_probs = nullptr;
     bool att_on = false;
-    // clips of different length (gitcap_student_attach_frame_counts): fc_attach = the pending one-shot counts (empty: none).
-    // ragged = the memory currently set is packed: memkv holds one K|V row per frame, clip-major, and decoder row r reads rows
-    // key_off[r] .. + key_len[r] - 1 of it (key_tab: device int32 [2][R], offsets then lengths; the cross-attention launches of
-    // text_forward take the varlen forms).  The tables are written outside the captured loops, from key_host (page-locked, [2][R])
-    // behind key_ev = the previous copy has read it; the loops read them at replay, so one graph serves every set of counts.
-    std::vector<int32_t> fc_attach;
+    // clips of different length (gitcap_student_attach_frame_counts): ragged = the memory currently set is packed: memkv holds one
+    // K|V row per frame, clip-major, and decoder row r reads rows key_off[r] .. + key_len[r] - 1 of it (key_tab: device int32 [2][R],
+    // offsets then lengths; the cross-attention launches of text_forward take the varlen forms).  The tables are written outside the
+    // captured loops, from key_host ([2][R]); the loops read them at replay, so one graph serves every set of counts.
     bool ragged = false;
-    int32_t *key_tab = nullptr, *key_host = nullptr;
-    hipEvent_t key_ev = nullptr;
-    // constrained decoding (gitcap_student_attach_constraints): co_attach = the pending one-shot rules.  The first attach allocates
-    // ban_mask (uint16 [R][ban_ld], the step's rows), ban_rec (device int32 [BAN_REC_WORDS]: n, min_length, n_suppress, 0, the ids) and
-    // ban_host, the page-locked copy of the record's header.  The constrained token loop is a graph of its own whose mask launches
-    // read ban_rec when they run: the consuming call writes it outside the graph (write_ban_record, behind ban_ev = the previous
-    // copy has read ban_host), so one captured loop serves every set of rules.
-    ConsOpt co_attach{};
+    int32_t* key_tab = nullptr;
+    HostStage key_host;
+    // constrained decoding (gitcap_student_attach_constraints): the first attach allocates ban_mask (uint16 [R][ban_ld], the step's
+    // rows), ban_rec (device int32 [BAN_REC_WORDS]: n, min_length, n_suppress, 0, the ids) and ban_host, the staging of the record's
+    // header.  The constrained token loop is a graph of its own whose mask launches read ban_rec when they run: the consuming call
+    // writes it outside the graph (write_ban_record), so one captured loop serves every set of rules.
     uint16_t* ban_mask = nullptr;
     int ban_ld = 0;
-    int32_t *ban_rec = nullptr, *ban_host = nullptr;
-    hipEvent_t ban_ev = nullptr;
-    // prompted decoding (gitcap_student_attach_prompt): pr_attach = the pending one-shot attachment (the caller's device tables).  The
-    // first attach allocates prm_ids (int64 [R][Tmax + 1]) and prm_len (int32 [R]), the handle's own tables: the consuming call copies
-    // the caller's rows into them on its stream, outside every captured loop (write_prompt_tables), and the loops' nodes -- the stage
-    // kernel, the forced arg-max -- name only these, so one captured loop serves every prompt of its plan.
-    PromptArgs pr_attach{};
+    int32_t* ban_rec = nullptr;
+    HostStage ban_host;
+    // prompted decoding (gitcap_student_attach_prompt; the attachment names the caller's device tables): the first attach allocates
+    // prm_ids (int64 [R][Tmax + 1]) and prm_len (int32 [R]), the handle's own tables: the consuming call copies the caller's rows
+    // into them on its stream, outside every captured loop (write_prompt_tables), and the loops' nodes -- the stage kernel, the
+    // forced arg-max -- name only these, so one captured loop serves every prompt of its plan.
     int64_t* prm_ids = nullptr;
     int32_t* prm_len = nullptr;
     int64_t draft_calls = 0, draft_offered = 0, draft_accepted = 0, draft_tail_steps = 0;
@@ -431,12 +426,12 @@ struct gitcap_student : HandleCore {
     // stream pool (gitcap_student_pool_*), allocated by pool_reset and state of its own beside the window: pool_ring = the K|V rows
     // of pool_S independent streams, bf16 [L][pool_S][F slots][2D]; pool (one RingCursor per stream) = where a stream's next token
     // goes and how many it holds.  One push: pool_stage = its tokens cast, packed [pool_cap][D]; pool_kv = their K|V rows, packed
-    // [L][pool_cap][2D]; pool_slot = the ring row of each (device [pool_cap], filled from the page-locked pool_slot_host behind
-    // pool_slot_ev).  One pool call: pool_tab = {ring row base, oldest slot, tokens, first packed memkv row} per decoder row
-    // (device [R][4], from pool_tab_host behind pool_tab_ev).  pool_order: win_order's discipline for the pool's ring.
+    // [L][pool_cap][2D]; pool_slot = the ring row of each (device [pool_cap], staged in pool_slot_host).  One pool call: pool_tab =
+    // {ring row base, oldest slot, tokens, first packed memkv row} per decoder row (device [R][4], staged in pool_tab_host).
+    // pool_order: win_order's discipline for the pool's ring.
     bf16_t *pool_ring = nullptr, *pool_stage = nullptr, *pool_kv = nullptr;
-    int32_t *pool_slot = nullptr, *pool_tab = nullptr, *pool_slot_host = nullptr, *pool_tab_host = nullptr;
-    hipEvent_t pool_slot_ev = nullptr, pool_tab_ev = nullptr;
+    int32_t *pool_slot = nullptr, *pool_tab = nullptr;
+    HostStage pool_slot_host, pool_tab_host;
     int pool_S = 0, pool_cap = 0;
     int64_t pool_bytes = 0;
     std::vector<RingCursor> pool;
@@ -460,10 +455,10 @@ void destroy_graphs(gitcap_student* h) {
 void pool_free(gitcap_student* h) {
     for (void* p : {(void*)h->pool_ring, (void*)h->pool_stage, (void*)h->pool_kv, (void*)h->pool_slot, (void*)h->pool_tab})
         if (p) (void)hipFree(p);
-    if (h->pool_slot_host) (void)hipHostFree(h->pool_slot_host);
-    if (h->pool_tab_host) (void)hipHostFree(h->pool_tab_host);
+    h->pool_slot_host.destroy();
+    h->pool_tab_host.destroy();
     h->pool_ring = h->pool_stage = h->pool_kv = nullptr;
-    h->pool_slot = h->pool_tab = h->pool_slot_host = h->pool_tab_host = nullptr;
+    h->pool_slot = h->pool_tab = nullptr;
     h->ws_bytes -= h->pool_bytes;
     h->pool_bytes = 0;
     h->pool_S = h->pool_cap = 0;
@@ -612,35 +607,36 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
 
 // ---- clips of different length (gitcap_student_attach_frame_counts) -------------------------------------------------------------
 using Counts = std::vector<int32_t>;
-// the pending counts: consumed by the caller, whatever becomes of its call
-Counts take_counts(gitcap_student* h) { return std::exchange(h->fc_attach, Counts{}); }
-std::string counts_refused(const std::string& who) {
-    return who + ": per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take";
-}
-bool counts_dense(const gitcap_student* h, const Counts& fc) {
-    for (int32_t c : fc)
-        if (c != h->F) return false;
-    return true;
+// An entry point's take (host_logic.h: take_opts): the parts in `parts` go to *o, consumed whatever becomes of the call; of the parts in
+// `refuse`, cleared, the first that held an attachment is the call's error: counts, prompt, constraints, top-k, as ever reported.
+int take(gitcap_student* h, const std::string& who, unsigned parts, unsigned refuse, StudentOpts* o = nullptr) {
+    unsigned refused = 0;
+    StudentOpts taken = take_opts(h->pending, parts, refuse, &refused);
+    if (o) *o = std::move(taken);
+    const char* what = refused & OPT_FC ? ": per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take"
+                     : refused & OPT_PR ? ": a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take"
+                     : refused & OPT_CO ? ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take" : nullptr;
+    if (what) return fail(h, GITCAP_ERR_ARG, who + what);
+    return refused & OPT_TK ? fail(h, GITCAP_ERR_ARG, refused_message(who.c_str(), OPT_TK)) : 0;
 }
 // Decoder rows 0 .. rows - 1 read the packed memory rows off(r) .. off(r) + len(r) - 1: the two device tables, written on `s`
-// (outside every captured loop).  The page-locked copy is reused once the previous call's transfer has read it.
+// (outside every captured loop).
 template <typename Row>
 int write_key_tables(gitcap_student* h, int rows, Row row, hipStream_t s) {
     if (rows < 1 || rows > h->R) return fail(h, GITCAP_ERR_ARG, "student: rows outside [1, max_rows]");
-    if (!h->key_host) HIP_OK(h, hipHostMalloc((void**)&h->key_host, 2 * (size_t)h->R * sizeof(int32_t), hipHostMallocDefault));
-    if (!h->key_ev) HIP_OK(h, hipEventCreateWithFlags(&h->key_ev, hipEventDisableTiming));
+    HIP_OK(h, h->key_host.ensure(2 * (size_t)h->R));
     if (!h->key_tab) {
         if (int rc = dev_alloc(h, &h->key_tab, 2 * (size_t)h->R)) { h->key_tab = nullptr; return rc; }
     }
-    HIP_OK(h, hipEventSynchronize(h->key_ev));      // (an event never recorded is complete)
+    HIP_OK(h, h->key_host.wait());
     for (int r = 0; r < rows; ++r) {
         const std::pair<int, int> ol = row(r);
-        h->key_host[r] = ol.first;
-        h->key_host[h->R + r] = ol.second;
+        h->key_host.p[r] = ol.first;
+        h->key_host.p[h->R + r] = ol.second;
     }
-    HIP_OK(h, hipMemcpyAsync(h->key_tab, h->key_host, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipMemcpyAsync(h->key_tab + h->R, h->key_host + h->R, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipEventRecord(h->key_ev, s));
+    HIP_OK(h, h->key_host.copy(h->key_tab, 0, (size_t)rows, s));
+    HIP_OK(h, h->key_host.copy(h->key_tab + h->R, (size_t)h->R, (size_t)rows, s));
+    HIP_OK(h, h->key_host.mark(s));
     return 0;
 }
 
@@ -678,7 +674,7 @@ int counts_for_call(gitcap_student* h, const std::string& who, const Counts& fc,
     if (fc.empty()) return 0;
     if ((int)fc.size() != B)
         return fail(h, GITCAP_ERR_ARG, who + ": B = " + std::to_string(B) + ", but frame counts of " + std::to_string(fc.size()) + " clips are attached");
-    if (!counts_dense(h, fc)) *out = &fc;
+    if (!std::all_of(fc.begin(), fc.end(), [&](int32_t c) { return c == h->F; })) *out = &fc;
     return 0;
 }
 
@@ -751,17 +747,13 @@ void gitcap_student_destroy(gitcap_student_t* h) {
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->acc_host) (void)hipHostFree(h->acc_host);
     if (h->acc_ev) (void)hipEventDestroy(h->acc_ev);
-    if (h->key_host) (void)hipHostFree(h->key_host);
-    if (h->key_ev) (void)hipEventDestroy(h->key_ev);
-    if (h->ban_host) (void)hipHostFree(h->ban_host);
-    if (h->ban_ev) (void)hipEventDestroy(h->ban_ev);
+    h->key_host.destroy();
+    h->ban_host.destroy();
     free_allocs(*h);
     if (h->win_ring) (void)hipFree(h->win_ring);
     if (h->win_stage) (void)hipFree(h->win_stage);
     h->win_order.destroy();
     pool_free(h);
-    if (h->pool_slot_ev) (void)hipEventDestroy(h->pool_slot_ev);
-    if (h->pool_tab_ev) (void)hipEventDestroy(h->pool_tab_ev);
     h->pool_order.destroy();
     delete h;
 }
@@ -837,23 +829,24 @@ int gitcap_student_finalize(gitcap_student_t* h) {
 
 int gitcap_student_set_memory(gitcap_student_t* h, const float* memory, int B, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_set_memory: null handle");
-    const Counts fc = take_counts(h);
+    StudentOpts o;
+    (void)take(h, "student_set_memory", OPT_FC, 0, &o);
     const Counts* ragged = nullptr;
-    if (int bad = counts_for_call(h, "student_set_memory", fc, B, &ragged)) return bad;
+    if (int bad = counts_for_call(h, "student_set_memory", o.fc, B, &ragged)) return bad;
     GUARD(h);
     return set_memory(h, memory, B, (hipStream_t)stream, ragged);
 }
 
 int gitcap_student_attach_frame_counts(gitcap_student_t* h, const int32_t* counts, int B) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: null handle");
-    h->fc_attach.clear();
+    h->pending.fc.clear();
     if (!counts) return 0;                                   // detach
     if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: B outside [1, max_rows]");
     for (int b = 0; b < B; ++b)
         if (counts[b] < 1 || counts[b] > h->F)
             return fail(h, GITCAP_ERR_ARG, "student_attach_frame_counts: clip " + std::to_string(b) + " has " + std::to_string(counts[b]) +
                         " frames, outside [1, " + std::to_string(h->F) + "]");
-    h->fc_attach.assign(counts, counts + B);
+    h->pending.fc.assign(counts, counts + B);
     return 0;
 }
 
@@ -896,8 +889,6 @@ int token_step(gitcap_student* h, int B, int t, int max_len, bool want_lp, hipSt
 }
 
 // ---- constrained decoding (gitcap_student_attach_constraints) --------------------------------------------------------------------
-// the pending rules: consumed by the caller, whatever becomes of its call
-ConsOpt take_constraints(gitcap_student* h) { return std::exchange(h->co_attach, ConsOpt{}); }
 // A call whose rows could lose every column is refused: each step bans at most n_suppress listed ids, one id per prefix position and
 // SEP; need = the columns the call must still find (1: the arg-max; k: the candidates a clip's ranking keeps).
 int cons_check(gitcap_student* h, const std::string& who, const ConsOpt& co, int max_len, int need) {
@@ -906,21 +897,19 @@ int cons_check(gitcap_student* h, const std::string& who, const ConsOpt& co, int
                     (need > 1 ? " + k > vocab_size)" : " >= vocab_size)"));
     return 0;
 }
-// The rules of the call -> ban_rec, on `s` and outside every captured loop: the header through the page-locked copy (reused once the
-// previous call's transfer has read it), the list by a device-to-device copy of the caller's `suppress`.
+// The rules of the call -> ban_rec, on `s` and outside every captured loop: the header through its staging, the list by a
+// device-to-device copy of the caller's `suppress`.
 int write_ban_record(gitcap_student* h, const ConsOpt& co, hipStream_t s) {
-    HIP_OK(h, hipEventSynchronize(h->ban_ev));      // (an event never recorded is complete)
-    h->ban_host[0] = co.ngram; h->ban_host[1] = co.min_length; h->ban_host[2] = co.n_suppress; h->ban_host[3] = 0;
-    HIP_OK(h, hipMemcpyAsync(h->ban_rec, h->ban_host, BAN_REC_HEADER * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipEventRecord(h->ban_ev, s));
+    HIP_OK(h, h->ban_host.wait());
+    h->ban_host.p[0] = co.ngram; h->ban_host.p[1] = co.min_length; h->ban_host.p[2] = co.n_suppress; h->ban_host.p[3] = 0;
+    HIP_OK(h, h->ban_host.copy(h->ban_rec, 0, BAN_REC_HEADER, s));
+    HIP_OK(h, h->ban_host.mark(s));
     if (co.n_suppress)
         HIP_OK(h, hipMemcpyAsync(h->ban_rec + BAN_REC_HEADER, co.suppress, (size_t)co.n_suppress * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
 // ---- prompted decoding (gitcap_student_attach_prompt) ---------------------------------------------------------------------------
-// the pending prompt: consumed by the caller, whatever becomes of its call
-PromptArgs take_prompt(gitcap_student* h) { return std::exchange(h->pr_attach, PromptArgs{}); }
 // The caller's prompts of `rows` clips -> the handle's tables, on `s` and outside every captured loop: pr.max_len columns of every row
 // and the lengths, device to device (the caller's buffers are read when these copies run, ahead of the loop on the same stream).
 int write_prompt_tables(gitcap_student* h, const PromptArgs& pr, int rows, hipStream_t s) {
@@ -1117,15 +1106,6 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     return 0;
 }
 
-// argument checks shared by gitcap_student_beam_search and gitcap_student_window_beam_search
-int beam_check(gitcap_student* h, const char* who, int B, int k, int max_len, const int64_t* ids_out) {
-    if (!ids_out || B <= 0 || k <= 0 || max_len < 2) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": bad arguments");
-    if (k > 16) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": at most 16 beams");
-    if ((int64_t)B * k > h->R) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": B * k exceeds max_rows");
-    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, std::string(who) + ": max_len exceeds max_text_len + 1");
-    return 0;
-}
-
 int beam_workspace(gitcap_student* h) {
     gitcap_student::BeamWs& w = h->bw;
     if (w.memrep) return 0;
@@ -1209,12 +1189,11 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
 // window only orders the F rows (student_window_gather_kernel) in front of the token loop of the full call.
 // partial (gitcap_student_window_greedy_partial): a window that is not full yet gives the n < mem_tokens tokens pushed since the reset,
 // oldest first, as slots 0 .. n - 1 of every row, and every row's key table entry says n: the varlen launches, a row of which is
-// bit for bit the plain launch at nkeys = n.  *frames = the tokens the caption sees.
+// bit for bit the plain launch at nkeys = n.  *frames (nullable, written when the call succeeds) = the tokens the caption sees.
 int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s, bool partial = false, int* frames = nullptr) {
     if (!h->win_ring || (partial ? h->win.count < 1 : !h->win.full()))
         return fail(h, GITCAP_ERR_STATE, std::string(who) + (partial ? ": no token pushed since the reset" : ": fewer than mem_tokens tokens pushed since the reset"));
     const int rows = h->win_B * k, D = h->D, F = h->F, n = h->win.full() ? F : h->win.count;
-    if (frames) *frames = n;
     HIP_OK(h, h->win_order.before_read(s));
     h->have_memory = false;
     if (n < F)
@@ -1225,85 +1204,126 @@ int window_memory(gitcap_student* h, const char* who, int k, hipStream_t s, bool
                        2 * D / 8, (size_t)h->win_B * F * 2 * D, (size_t)h->R * F * 2 * D, n);
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, h->win_order.after_read(s));
+    if (frames) *frames = n;
     h->cur_B = rows;
     h->have_memory = true;
     return 0;
 }
 
-// The four greedy entry points.  who = the entry point's name in every message; window: the memory K|V come from the ring (win_B
-// clips) instead of the caller's `memory` (set_memory reads the caller's buffer: outside the graphs); draft set: the loop verifies
-// it.  The pending log-probability attachment is taken before the checks: a refused call has consumed it.
-// Attached frame counts are taken with them: the calls with `memory` follow them, the window calls refuse them.  partial: the window
-// need not be full (window_memory); *frames_out (host, nullable) = the tokens the caption saw.
-int greedy_entry(gitcap_student* h, const char* who, bool window, const float* memory, int B, const Draft* draft, int max_len, int stop,
-                 int64_t* ids_out, int32_t* steps_out, void* stream, bool partial = false, int32_t* frames_out = nullptr) {
+// The greedy entry points.  who = the entry point's name in every message; parts / refuse = the attachments it takes -- before the
+// checks: a refused call has consumed them -- and refuses (take); draft set: the loop verifies it.  source(opts, stream, &B) does the
+// checks of the entry point's own arguments and state and provides the memory K|V of its B rows: from the caller's `memory`
+// (memory_source; set_memory reads the caller's buffer: outside the graphs), the window's ring or the pool's.  early_bad: a fault in
+// the source's arguments that is reported as the family's first "bad arguments".
+template <typename Source>
+int greedy_entry(gitcap_student* h, const char* who, unsigned parts, unsigned refuse, const Draft* draft, int max_len, int stop, int64_t* ids_out,
+                 int32_t* steps_out, void* stream, Source source, bool early_bad = false) {
     const std::string w(who);
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
-    const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});
-    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
-    const Counts fc = take_counts(h);
-    const ConsOpt co = take_constraints(h);
-    const PromptArgs pr = take_prompt(h);
-    if (window && !fc.empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));          // (consumed above)
-    if (draft && pr.ids)
-        return fail(h, GITCAP_ERR_ARG, w + ": a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take");
-    if (draft && co.on)
-        return fail(h, GITCAP_ERR_ARG, w + ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take");
-    if (draft && tk.k) return fail(h, GITCAP_ERR_ARG, refused_message(who, OPT_TK));       // (consumed above)
-    if (!ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
+    StudentOpts o;
+    if (int bad = take(h, w, parts, refuse, &o)) return bad;
+    if (early_bad || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
-    if (int bad = lp_check(h, who, lp, max_len)) return bad;
-    if (int bad = tk_check(h, who, tk, max_len)) return bad;
-    if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
-    if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len");
+    if (int bad = lp_check(h, who, o.lp, max_len)) return bad;
+    if (int bad = tk_check(h, who, o.tk, max_len)) return bad;
+    if (int bad = cons_check(h, w, o.co, max_len, 1)) return bad;
+    if (o.pr.ids && o.pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len");
     if (draft && !draft->ids) return fail(h, GITCAP_ERR_ARG, w + ": null draft_ids");
     if (draft && (draft->n < 1 || draft->n > max_len || draft->ld < draft->n + 1))
         return fail(h, GITCAP_ERR_ARG, w + ": n_draft outside [1, max_len], or ld_draft < n_draft + 1");
-    if (window && !h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
-    const Counts* ragged = nullptr;
-    if (int bad = counts_for_call(h, w, fc, B, &ragged)) return bad;
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
-    int frames = 0;
-    if (int rc = window ? window_memory(h, who, 1, s, partial, &frames) : set_memory(h, memory, B, s, ragged)) return rc;
-    if (frames_out) *frames_out = frames;
-    if (window) B = h->win_B;
-    if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, lp);
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co, pr);
+    int B = 0;
+    if (int rc = source(o, w, s, &B)) return rc;
+    if (draft) return greedy_draft_core(h, B, draft->ids, draft->ld, draft->n, max_len, stop, ids_out, steps_out, draft->accepted_out, s, o.lp);
+    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, o.lp, o.tk, o.co, o.pr);
+}
+constexpr unsigned GREEDY_PARTS = OPT_LP | OPT_TK | OPT_CO | OPT_PR, DRAFT_REFUSES = OPT_PR | OPT_CO | OPT_TK;
+// the caller's memory of B clips, following the counts the call took
+auto memory_source(gitcap_student* h, const float* memory, int B) {
+    return [=](const StudentOpts& o, const std::string& who, hipStream_t s, int* rows) -> int {
+        const Counts* ragged = nullptr;
+        if (int bad = counts_for_call(h, who, o.fc, B, &ragged)) return bad;
+        *rows = B;
+        return set_memory(h, memory, B, s, ragged);
+    };
+}
+// the window's win_B clips; partial: the window need not be full (window_memory), *frames_out (host, nullable) = the tokens the caption saw
+auto window_source(gitcap_student* h, bool partial = false, int32_t* frames_out = nullptr) {
+    return [=](const StudentOpts&, const std::string& who, hipStream_t s, int* rows) -> int {
+        if (!h->finalized) return fail(h, GITCAP_ERR_STATE, who + ": weights not finalized");
+        *rows = h->win_B;
+        return window_memory(h, who.c_str(), 1, s, partial, frames_out);
+    };
+}
+
+// The two beam entry points, in greedy_entry's shape.  early(&B): the source's checks that come ahead of the family's, and its clips;
+// source(opts, stream): its other checks, then beam_workspace and the memory K|V of the B * k rows.
+template <typename Early, typename Source>
+int beam_entry(gitcap_student* h, const char* who, unsigned parts, unsigned refuse, int k, int max_len, int64_t* ids_out, void* stream, Early early,
+               Source source) {
+    const std::string w(who);
+    if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
+    StudentOpts o;
+    int B = 0, bad = take(h, w, parts, refuse, &o);
+    if (bad || (bad = early(&B))) return bad;
+    if (!ids_out || B <= 0 || k <= 0 || max_len < 2) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
+    if (k > 16) return fail(h, GITCAP_ERR_ARG, w + ": at most 16 beams");
+    if ((int64_t)B * k > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B * k exceeds max_rows");
+    if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len + 1");
+    if ((bad = cons_check(h, w, o.co, max_len, k))) return bad;
+    if (o.pr.ids && o.pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len - 1");
+    GUARD(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = source(o, s)) return rc;
+    return beam_loop(h, B, k, max_len, ids_out, s, o.co, o.pr);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
-// The memory K|V of a pool call: decoder row r = stream ids[r] (checked by the caller: in range, distinct, not empty), its last
-// n_r = min(count, F) tokens oldest first, rows packed as set_memory packs clips of different length -- the layout and the key
+// The memory K|V of a pool call: decoder row r = stream ids[r] (non-null: greedy_entry's early_bad; in range, distinct, not empty), its
+// last n_r = min(count, F) tokens oldest first, rows packed as set_memory packs clips of different length -- the layout and the key
 // tables of gitcap_student_attach_frame_counts, so the token loop is that call's.  Every n_r == F: the packed layout is the dense
 // one and the loop takes the dense launches, as a full lockstep window's.  frames (host, nullable) = n_r.
-int pool_memory(gitcap_student* h, const int32_t* ids, int B, hipStream_t s, int32_t* frames) {
+// (The teacher's pool_plan checks a row's id, duplicate and emptiness in one pass: the two report different faults first.)
+int pool_memory(gitcap_student* h, const std::string& w, const int32_t* ids, int B, hipStream_t s, int32_t* frames) {
+    if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
+    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
+    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
+    for (int r = 0; r < B; ++r) {
+        if (ids[r] < 0 || ids[r] >= h->pool_S)
+            return fail(h, GITCAP_ERR_ARG, w + ": row " + std::to_string(r) + " names stream " + std::to_string(ids[r]) + ", outside [0, " +
+                        std::to_string(h->pool_S) + ")");
+        for (int q = 0; q < r; ++q)
+            if (ids[q] == ids[r]) return fail(h, GITCAP_ERR_ARG, w + ": stream " + std::to_string(ids[r]) + " is named twice");
+    }
+    for (int r = 0; r < B; ++r)
+        if (h->pool[(size_t)ids[r]].count < 1) return fail(h, GITCAP_ERR_STATE, w + ": stream " + std::to_string(ids[r]) + " holds no token");
     const int D = h->D, F = h->F;
-    HIP_OK(h, hipEventSynchronize(h->pool_tab_ev));         // the previous call's transfer has read the page-locked table
+    int32_t* const tab = h->pool_tab_host.p;
+    HIP_OK(h, h->pool_tab_host.wait());
     bool dense = true;
     int off = 0;
     for (int r = 0; r < B; ++r) {
         const RingCursor& c = h->pool[(size_t)ids[r]];
-        int32_t* t = h->pool_tab_host + 4 * r;
+        int32_t* t = tab + 4 * r;
         t[0] = ids[r] * F; t[1] = c.oldest(); t[2] = c.count; t[3] = off;
         off += c.count;
         dense = dense && c.count == F;
     }
     HIP_OK(h, h->pool_order.before_read(s));
     h->have_memory = false;
-    HIP_OK(h, hipMemcpyAsync(h->pool_tab, h->pool_tab_host, (size_t)B * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(h, hipEventRecord(h->pool_tab_ev, s));
+    HIP_OK(h, h->pool_tab_host.copy(h->pool_tab, 0, (size_t)B * 4, s));
+    HIP_OK(h, h->pool_tab_host.mark(s));
     if (!dense)
-        if (int rc = write_key_tables(h, B, [&](int r) { return std::make_pair((int)h->pool_tab_host[4 * r + 3], (int)h->pool_tab_host[4 * r + 2]); }, s))
-            return rc;
+        if (int rc = write_key_tables(h, B, [&](int r) { return std::make_pair((int)tab[4 * r + 3], (int)tab[4 * r + 2]); }, s)) return rc;
     h->ragged = !dense;
     hipLaunchKernelGGL(student_pool_gather_kernel, dim3(B * F, h->L), dim3(64), 0, s, h->pool_ring, h->memkv, h->pool_tab, F, 2 * D / 8,
                        (size_t)h->pool_S * F * 2 * D, (size_t)h->R * F * 2 * D);
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, h->pool_order.after_read(s));
     if (frames)
-        for (int r = 0; r < B; ++r) frames[r] = h->pool_tab_host[4 * r + 2];
+        for (int r = 0; r < B; ++r) frames[r] = tab[4 * r + 2];
     h->cur_B = B;
     h->have_memory = true;
     return 0;
@@ -1315,7 +1335,7 @@ extern "C" {
 
 int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int max_len, int stop, int64_t* ids_out,
                           int32_t* steps_out, void* stream) {
-    return greedy_entry(h, "student_greedy", false, memory, B, nullptr, max_len, stop, ids_out, steps_out, stream);
+    return greedy_entry(h, "student_greedy", GREEDY_PARTS | OPT_FC, 0, nullptr, max_len, stop, ids_out, steps_out, stream, memory_source(h, memory, B));
 }
 
 // StudentCandidateV1.beam_search (model.py:189-318) on the device with the exact KV cache: k beams per clip as rows
@@ -1326,34 +1346,23 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
 // -1e9), so the k rows start as the top k of the single prefix [CLS] (model.py:221-227).  After every step the self-attention
 // K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_beam_search: null handle");
-    const Counts fc = take_counts(h);
-    const ConsOpt co = take_constraints(h);
-    const PromptArgs pr = take_prompt(h);
-    if (!memory) return fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments");
-    if (int bad = beam_check(h, "student_beam_search", B, k, max_len, ids_out)) return bad;
-    if (int bad = cons_check(h, "student_beam_search", co, max_len, k)) return bad;
-    if (pr.ids && pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, "student_beam_search: the attached prompt is longer than max_len - 1");
-    const Counts* ragged = nullptr;
-    if (int bad = counts_for_call(h, "student_beam_search", fc, B, &ragged)) return bad;
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = beam_workspace(h);
-    if (rc) return rc;
-    if (ragged) {       // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
-        if ((rc = set_memory(h, memory, B, s, ragged, k))) return rc;
-        return beam_loop(h, B, k, max_len, ids_out, s, co, pr);
-    }
-    const int rows = B * k;
-    hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, rows), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
-    HIP_OK(h, hipGetLastError());
-    if ((rc = set_memory(h, h->bw.memrep, rows, s))) return rc;
-    return beam_loop(h, B, k, max_len, ids_out, s, co, pr);
+    const char* who = "student_beam_search";
+    return beam_entry(h, who, OPT_FC | OPT_CO | OPT_PR, 0, k, max_len, ids_out, stream,
+        [&](int* clips) { *clips = B; return memory ? 0 : fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments"); },
+        [&](const StudentOpts& o, hipStream_t s) -> int {
+            const Counts* ragged = nullptr;
+            if (int bad = counts_for_call(h, who, o.fc, B, &ragged)) return bad;
+            if (int rc = beam_workspace(h)) return rc;
+            if (ragged) return set_memory(h, memory, B, s, ragged, k);      // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
+            hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, B * k), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
+            HIP_OK(h, hipGetLastError());
+            return set_memory(h, h->bw.memrep, B * k, s);
+        });
 }
 
 int gitcap_student_window_reset(gitcap_student_t* h, int B) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_reset: null handle");
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_reset"));
+    if (int bad = take(h, "student_window_reset", 0, OPT_FC)) return bad;
     if (B < 0 || B > h->R) return fail(h, GITCAP_ERR_ARG, "student_window_reset: B outside 0..max_rows");
     GUARD(h);
     if (h->win_ring && B != h->win_B) {
@@ -1383,7 +1392,7 @@ int gitcap_student_window_reset(gitcap_student_t* h, int B) {
 
 int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, int n, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_push: null handle");
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_push"));
+    if (int bad = take(h, "student_window_push", 0, OPT_FC)) return bad;
     if (!memory) return fail(h, GITCAP_ERR_ARG, "student_window_push: null memory");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_push: weights not finalized");
     if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_push: no window (gitcap_student_window_reset first)");
@@ -1415,29 +1424,30 @@ int gitcap_student_window_push(gitcap_student_t* h, const float* memory, int B, 
 }
 
 int gitcap_student_window_greedy(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, void* stream) {
-    return greedy_entry(h, "student_window_greedy", true, nullptr, 0, nullptr, max_len, stop, ids_out, steps_out, stream);
+    return greedy_entry(h, "student_window_greedy", GREEDY_PARTS, OPT_FC, nullptr, max_len, stop, ids_out, steps_out, stream, window_source(h));
 }
 
 int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* frames_out,
                                          void* stream) {
-    return greedy_entry(h, "student_window_greedy_partial", true, nullptr, 0, nullptr, max_len, stop, ids_out, steps_out, stream, true, frames_out);
+    return greedy_entry(h, "student_window_greedy_partial", GREEDY_PARTS, OPT_FC, nullptr, max_len, stop, ids_out, steps_out, stream,
+                        window_source(h, true, frames_out));
 }
 
 int gitcap_student_greedy_draft(gitcap_student_t* h, const float* memory, int B, const int64_t* draft_ids, int ld_draft, int n_draft,
                                 int max_len, int stop, int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
     const Draft d{draft_ids, ld_draft, n_draft, accepted_out};
-    return greedy_entry(h, "student_greedy_draft", false, memory, B, &d, max_len, stop, ids_out, steps_out, stream);
+    return greedy_entry(h, "student_greedy_draft", OPT_LP | OPT_FC, DRAFT_REFUSES, &d, max_len, stop, ids_out, steps_out, stream, memory_source(h, memory, B));
 }
 
 int gitcap_student_window_greedy_draft(gitcap_student_t* h, const int64_t* draft_ids, int ld_draft, int n_draft, int max_len, int stop,
                                        int64_t* ids_out, int32_t* steps_out, int32_t* accepted_out, void* stream) {
     const Draft d{draft_ids, ld_draft, n_draft, accepted_out};
-    return greedy_entry(h, "student_window_greedy_draft", true, nullptr, 0, &d, max_len, stop, ids_out, steps_out, stream);
+    return greedy_entry(h, "student_window_greedy_draft", OPT_LP, OPT_FC | DRAFT_REFUSES, &d, max_len, stop, ids_out, steps_out, stream, window_source(h));
 }
 
 int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_out, int ld) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: null handle");
-    if (!logprobs_out) { h->lp_attach = LpAttach{}; return 0; }
+    if (!logprobs_out) { h->pending.lp = LpAttach{}; return 0; }
     if (ld < 1 || ((uintptr_t)logprobs_out & 3) != 0) return fail(h, GITCAP_ERR_ARG, "student_attach_token_logprobs: ld < 1 or a misaligned pointer");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_token_logprobs: weights not finalized");
     GUARD(h);
@@ -1449,13 +1459,13 @@ int gitcap_student_attach_token_logprobs(gitcap_student_t* h, float* logprobs_ou
             return rc;
         }
     }
-    h->lp_attach = LpAttach{logprobs_out, ld};
+    h->pending.lp = LpAttach{logprobs_out, ld};
     return 0;
 }
 
 int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_ids, float* top_lp, int ld) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_top_logprobs: null handle");
-    if (k == 0 || !top_ids || !top_lp) { h->tk_attach = TopkAttach{}; return 0; }
+    if (k == 0 || !top_ids || !top_lp) { h->pending.tk = TopkAttach{}; return 0; }
     if (const char* bad = tk_attach_bad(k, top_ids, top_lp, ld)) return fail(h, GITCAP_ERR_ARG, std::string("student_attach_top_logprobs: ") + bad);
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attach_top_logprobs: weights not finalized");
     if (!head_topk_ok(h->D, false)) return fail(h, GITCAP_ERR_ARG, "student_attach_top_logprobs: no top-k kernel for this decoder width");
@@ -1468,13 +1478,13 @@ int gitcap_student_attach_top_logprobs(gitcap_student_t* h, int k, int64_t* top_
         if (!h->g_tk_ids && (rc = dev_alloc(h, &h->g_tk_ids, Mt * HEAD_TOPK_MAX))) { h->g_tk_ids = nullptr; return rc; }
         if (!h->g_tk_lp && (rc = dev_alloc(h, &h->g_tk_lp, Mt * HEAD_TOPK_MAX))) { h->g_tk_lp = nullptr; return rc; }
     }
-    h->tk_attach = TopkAttach{k, top_ids, top_lp, ld};
+    h->pending.tk = TopkAttach{k, top_ids, top_lp, ld};
     return 0;
 }
 
 int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constraints* c) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: null handle");
-    h->co_attach = ConsOpt{};
+    h->pending.co = ConsOpt{};
     if (!c) return 0;                                        // detach
     if (c->no_repeat_ngram_size < 0 || c->min_length < 0 || c->n_suppress < 0) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: a negative field");
     if (c->n_suppress > BAN_REC_MAX_SUPPRESS) return fail(h, GITCAP_ERR_ARG, "student_attach_constraints: n_suppress > 256");
@@ -1489,16 +1499,15 @@ int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constrai
         h->ban_ld = (((h->V + 15) / 16) + 1) & ~1;
         if (!h->ban_mask && (rc = dev_alloc(h, &h->ban_mask, (size_t)h->R * (size_t)h->ban_ld))) { h->ban_mask = nullptr; return rc; }
         if (!h->ban_rec && (rc = dev_alloc(h, &h->ban_rec, (size_t)BAN_REC_WORDS))) { h->ban_rec = nullptr; return rc; }
-        if (!h->ban_host) HIP_OK(h, hipHostMalloc((void**)&h->ban_host, BAN_REC_HEADER * sizeof(int32_t), hipHostMallocDefault));
-        if (!h->ban_ev) HIP_OK(h, hipEventCreateWithFlags(&h->ban_ev, hipEventDisableTiming));
+        HIP_OK(h, h->ban_host.ensure(BAN_REC_HEADER));
     }
-    h->co_attach = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
+    h->pending.co = ConsOpt{true, c->no_repeat_ngram_size, c->min_length, c->n_suppress ? c->suppress : nullptr, c->n_suppress};
     return 0;
 }
 
 int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: null handle");
-    h->pr_attach = PromptArgs{};
+    h->pending.pr = PromptArgs{};
     if (!prompt_ids && !lengths) return 0;                   // detach
     if (!prompt_ids || !lengths) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: prompt_ids and lengths are both required");
     if (((uintptr_t)prompt_ids & 7) != 0 || ((uintptr_t)lengths & 3) != 0) return fail(h, GITCAP_ERR_ARG, "student_attach_prompt: a misaligned pointer");
@@ -1511,14 +1520,16 @@ int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids,
         if (!h->prm_ids && (rc = dev_alloc(h, &h->prm_ids, (size_t)h->R * ((size_t)h->Tmax + 1)))) { h->prm_ids = nullptr; return rc; }
         if (!h->prm_len && (rc = dev_alloc(h, &h->prm_len, (size_t)h->R))) { h->prm_len = nullptr; return rc; }
     }
-    h->pr_attach = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
+    h->pending.pr = PromptArgs{prompt_ids, ld, lengths, min_len, max_len};
     return 0;
 }
 
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
-    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});        // consumed, whatever becomes of the call
+    StudentOpts o;
+    (void)take(h, "student_score", OPT_TK, 0, &o);
+    const TopkAttach& tk = o.tk;
     if (int bad = tk_check(h, "student_score", tk, T - 1)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_score: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student_score before set_memory");
@@ -1577,27 +1588,20 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
 }
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
-    if (!h) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: null handle");
-    const ConsOpt co = take_constraints(h);         // consumed, whatever becomes of the call
-    const PromptArgs pr = take_prompt(h);
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_window_beam_search"));
-    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
-    if (!h->win_ring) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
-    if (int bad = beam_check(h, "student_window_beam_search", h->win_B, k, max_len, ids_out)) return bad;
-    if (int bad = cons_check(h, "student_window_beam_search", co, max_len, k)) return bad;
-    if (pr.ids && pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, "student_window_beam_search: the attached prompt is longer than max_len - 1");
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = beam_workspace(h);
-    if (rc) return rc;
-    if ((rc = window_memory(h, "student_window_beam_search", k, s))) return rc;
-    return beam_loop(h, h->win_B, k, max_len, ids_out, s, co, pr);
+    const char* who = "student_window_beam_search";
+    return beam_entry(h, who, OPT_CO | OPT_PR, OPT_FC, k, max_len, ids_out, stream,
+        [&](int* clips) {
+            *clips = h->win_B;
+            if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
+            return h->win_ring ? 0 : fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
+        },
+        [&](const StudentOpts&, hipStream_t s) { const int rc = beam_workspace(h); return rc ? rc : window_memory(h, who, k, s); });
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
 int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_reset: null handle");
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_pool_reset"));
+    if (int bad = take(h, "student_pool_reset", 0, OPT_FC)) return bad;
     if (n_streams < 0 || n_streams > 4096) return fail(h, GITCAP_ERR_ARG, "student_pool_reset: n_streams outside 0..4096");
     if (n_streams && !h->finalized) return fail(h, GITCAP_ERR_STATE, "student_pool_reset: weights not finalized");
     GUARD(h);
@@ -1609,8 +1613,6 @@ int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams) {
     if (!h->pool_ring) {
         const size_t S = (size_t)n_streams, F = (size_t)h->F, D = (size_t)h->D, L = (size_t)h->L, cap = (size_t)h->R * F;
         HIP_OK(h, h->pool_order.ensure());
-        if (!h->pool_slot_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_slot_ev, hipEventDisableTiming));
-        if (!h->pool_tab_ev) HIP_OK(h, hipEventCreateWithFlags(&h->pool_tab_ev, hipEventDisableTiming));
         const size_t b_ring = L * S * F * 2 * D * sizeof(bf16_t), b_stage = cap * D * sizeof(bf16_t), b_kv = L * cap * 2 * D * sizeof(bf16_t),
                      b_slot = cap * sizeof(int32_t), b_tab = (size_t)h->R * 4 * sizeof(int32_t);
         hipError_t e = hipMalloc((void**)&h->pool_ring, b_ring);
@@ -1618,8 +1620,8 @@ int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams) {
         if (e == hipSuccess) e = hipMalloc((void**)&h->pool_kv, b_kv);
         if (e == hipSuccess) e = hipMalloc((void**)&h->pool_slot, b_slot);
         if (e == hipSuccess) e = hipMalloc((void**)&h->pool_tab, b_tab);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_slot_host, b_slot, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h->pool_tab_host, b_tab, hipHostMallocDefault);
+        if (e == hipSuccess) e = h->pool_slot_host.ensure(cap);
+        if (e == hipSuccess) e = h->pool_tab_host.ensure((size_t)h->R * 4);
         if (e != hipSuccess) {
             pool_free(h);
             return fail(h, GITCAP_ERR_NOMEM, std::string("hipMalloc stream pool: ") + hipGetErrorString(e));
@@ -1636,7 +1638,7 @@ int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams) {
 
 int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int32_t* stream_ids, int n, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_pool_push: null handle");
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused("student_pool_push"));
+    if (int bad = take(h, "student_pool_push", 0, OPT_FC)) return bad;
     if (!memory || !stream_ids) return fail(h, GITCAP_ERR_ARG, "student_pool_push: null memory or stream_ids");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_pool_push: weights not finalized");
     if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, "student_pool_push: no pool (gitcap_student_pool_reset first)");
@@ -1651,13 +1653,13 @@ int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     const int D = h->D;
-    HIP_OK(h, hipEventSynchronize(h->pool_slot_ev));        // the previous push's transfer has read the page-locked table
-    memcpy(h->pool_slot_host, slots.data(), (size_t)n * sizeof(int32_t));
+    HIP_OK(h, h->pool_slot_host.wait());
+    memcpy(h->pool_slot_host.p, slots.data(), (size_t)n * sizeof(int32_t));
     HIP_OK(h, h->pool_order.before_push(s));
     // From here on ring rows may be half written: a failure empties the streams this push names.
     auto enqueue = [&]() -> int {
-        HIP_OK(h, hipMemcpyAsync(h->pool_slot, h->pool_slot_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_OK(h, hipEventRecord(h->pool_slot_ev, s));
+        HIP_OK(h, h->pool_slot_host.copy(h->pool_slot, 0, (size_t)n, s));
+        HIP_OK(h, h->pool_slot_host.mark(s));
         HIP_OK(h, launch_cast_bf16(memory, h->pool_stage, (int64_t)n * D, s));         // the bf16 rows set_memory's GEMM reads
         const size_t kv_layer = (size_t)h->pool_cap * 2 * D;
         for (int l = 0; l < h->L; ++l) {
@@ -1686,38 +1688,9 @@ int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int
 
 int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out,
                                int32_t* steps_out, int32_t* frames_out, void* stream) {
-    const char* who = "student_pool_greedy";
-    const std::string w(who);
-    if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
-    const LpAttach lp = std::exchange(h->lp_attach, LpAttach{});           // consumed, whatever becomes of the call
-    const TopkAttach tk = std::exchange(h->tk_attach, TopkAttach{});
-    const ConsOpt co = take_constraints(h);
-    const PromptArgs pr = take_prompt(h);
-    if (!take_counts(h).empty()) return fail(h, GITCAP_ERR_ARG, counts_refused(w));
-    if (!stream_ids || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
-    if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
-    if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
-    if (int bad = lp_check(h, who, lp, max_len)) return bad;
-    if (int bad = tk_check(h, who, tk, max_len)) return bad;
-    if (int bad = cons_check(h, w, co, max_len, 1)) return bad;
-    if (pr.ids && pr.max_len > max_len) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len");
-    if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
-    if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
-    if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
-    for (int r = 0; r < B; ++r) {
-        if (stream_ids[r] < 0 || stream_ids[r] >= h->pool_S)
-            return fail(h, GITCAP_ERR_ARG, w + ": row " + std::to_string(r) + " names stream " + std::to_string(stream_ids[r]) + ", outside [0, " +
-                        std::to_string(h->pool_S) + ")");
-        for (int q = 0; q < r; ++q)
-            if (stream_ids[q] == stream_ids[r]) return fail(h, GITCAP_ERR_ARG, w + ": stream " + std::to_string(stream_ids[r]) + " is named twice");
-    }
-    for (int r = 0; r < B; ++r)
-        if (h->pool[(size_t)stream_ids[r]].count < 1)
-            return fail(h, GITCAP_ERR_STATE, w + ": stream " + std::to_string(stream_ids[r]) + " holds no token");
-    GUARD(h);
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = pool_memory(h, stream_ids, B, s, frames_out)) return rc;
-    return greedy_loop(h, B, max_len, stop, ids_out, steps_out, s, lp, tk, co, pr);
+    return greedy_entry(h, "student_pool_greedy", GREEDY_PARTS, OPT_FC, nullptr, max_len, stop, ids_out, steps_out, stream,
+        [=](const StudentOpts&, const std::string& who, hipStream_t s, int* rows) { *rows = B; return pool_memory(h, who, stream_ids, B, s, frames_out); },
+        !stream_ids);
 }
 
 int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id) {

@@ -8,7 +8,11 @@ checks the submitted one runs, the window forms check the window behind the argu
 tables were recorded on the commit before the entry points were folded.  No arithmetic: a refused call launches nothing.  The
 "sizes overflow" case is driven through the submitted raw paths only: the synchronous raw path has no such check and would launch.
 
-An attachment (gitcap_attach_token_logprobs and its student twin) is consumed by a call that then fails its argument check."""
+An attachment (gitcap_attach_token_logprobs and its student twin) is consumed by a call that then fails its argument check.
+
+STUDENT_MORE_EXPECTED does the same for gitcap_student_pool_greedy, gitcap_student_beam_search and
+gitcap_student_window_beam_search, and adds, for every student entry point, which of the five one-shot attachments (token
+log-probabilities, top-k, constraints, prompt, frame counts) are still pending behind a valid and behind a refused call: seen()."""
 import ctypes
 
 import pytest
@@ -293,6 +297,225 @@ def _student_observed():
     return t.rows + u.rows
 
 
+# ---- student: the pool call, the two beam searches, and what every entry point leaves pending ------------------------------------
+
+MORE = ("gitcap_student_pool_greedy", "gitcap_student_beam_search", "gitcap_student_window_beam_search")
+TOK, BAN = 5, 80        # the attached prompt is [CLS, TOK] for both clips; the attached constraints suppress the ids 0 .. BAN - 1
+
+
+class _StudentMore(_Student):
+    def __init__(self, weights=True):
+        super().__init__(weights)
+        F, V = self.cfg.mem_tokens, self.cfg.vocab_length
+        self.sid = (ctypes.c_int32 * 2)(0, 1)
+        self.frames = (ctypes.c_int32 * 2)()
+        self.counts = (ctypes.c_int32 * 2)(F, F)
+        self.tki = torch.full((2, S_LEN, 2), -1, dtype=torch.int64, device="cuda")
+        self.tkl = torch.full((2, S_LEN, 2), POISON, device="cuda")
+        self.sup = torch.arange(V - 2, dtype=torch.int32, device="cuda")
+        self.prm = torch.tensor([[self.cfg.cls_token_id] + [TOK] * L] * 2, dtype=torch.int64, device="cuda")
+        self.plen = torch.full((2,), 2, dtype=torch.int32, device="cuda")
+        self.bout = torch.full((2, L + 2), -1, dtype=torch.int64, device="cuda")
+        self.logits = torch.zeros((2, S_LEN, V), device="cuda")
+        self.mass = torch.zeros((2 * S_LEN, F), device="cuda")
+        self.pool_tokens = self.mem.reshape(2 * F, -1).contiguous()
+        self.pool_ids = (ctypes.c_int32 * (2 * F))(*([0] * F + [1] * F))
+
+    def more(self, name, h=True, sid="own", mem="own", B=2, k=1, max_len=S_LEN, stop=0, ids="own"):
+        hh = self.h if h else None
+        if name == MORE[0]:
+            return self.lib.gitcap_student_pool_greedy(hh, self.sid if sid == "own" else sid, B, max_len, stop,
+                                                       _p(self.ids) if ids == "own" else ids, _p(self.steps), self.frames, stream())
+        out = _p(self.bout) if ids == "own" else ids
+        if name == MORE[1]:
+            return self.lib.gitcap_student_beam_search(hh, _p(self.mem) if mem == "own" else mem, B, k, max_len, out, stream())
+        return self.lib.gitcap_student_window_beam_search(hh, k, max_len, out, stream())
+
+    def attach_tk(self, ld=S_LEN):
+        assert self.lib.gitcap_student_attach_top_logprobs(self.h, 2, _p(self.tki), _p(self.tkl), ld) == 0
+
+    def attach_co(self, n=BAN):
+        from gitcap._lib import CConstraints
+        c = CConstraints(0, 0, self.sup.data_ptr(), n)
+        assert self.lib.gitcap_student_attach_constraints(self.h, ctypes.byref(c)) == 0
+
+    def attach_pr(self, max_len=2):
+        assert self.lib.gitcap_student_attach_prompt(self.h, _p(self.prm), L + 1, _p(self.plen), 2, max_len) == 0
+
+    def attach_fc(self, B=2):
+        assert self.lib.gitcap_student_attach_frame_counts(self.h, self.counts, B) == 0
+
+    def fill_window(self):
+        assert self.lib.gitcap_student_window_reset(self.h, 2) == 0
+        assert self.lib.gitcap_student_window_push(self.h, _p(self.mem), 2, self.cfg.mem_tokens, stream()) == 0
+
+    def fill_pool(self):
+        assert self.lib.gitcap_student_pool_reset(self.h, 2) == 0
+        assert self.lib.gitcap_student_pool_push(self.h, _p(self.pool_tokens), self.pool_ids, 2 * self.cfg.mem_tokens, stream()) == 0
+
+    def seen(self):
+        """Which attachments are still pending: the counts by the message of a window push that is refused either way (it refuses and
+        clears them, and takes nothing else), the other four by what the gitcap_student_greedy behind it does with them."""
+        self.lib.gitcap_student_window_push(self.h, None, 2, 1, stream())
+        fc = b"frame counts are attached" in self.lib.gitcap_student_last_error(self.h)
+        self.lp.fill_(POISON)
+        self.tkl.fill_(POISON)
+        self.ids.fill_(-1)
+        rc = self.call("gitcap_student_greedy")
+        torch.cuda.synchronize()
+        return "greedy=%d fc=%d lp=%d tk=%d co=%d pr=%d" % (rc, fc, bool((self.lp != POISON).any()), bool((self.tkl != POISON).any()),
+                                                             bool((self.ids[:, 2:] >= BAN).all()), bool((self.ids[:, 1] == TOK).all()))
+
+    def pending(self, label, valid, bad, restore=None):
+        for what, fn, fc in (("all five, valid arguments", valid, True), ("all five, a bad argument", bad, True),
+                             ("all but the counts, valid arguments", valid, False)):
+            self.attach(S_LEN)
+            self.attach_tk()
+            self.attach_co()
+            self.attach_pr()
+            if fc:
+                self.attach_fc()
+            self.rec(f"{label}: {what}", fn())
+            torch.cuda.synchronize()
+            self.rows.append((f"{label}: {what}, then", 0, self.seen()))
+            if restore:
+                restore()
+
+
+def _student_more_observed():
+    t = _StudentMore()
+    pool, beam, wbeam = MORE
+    for name in MORE:
+        t.rec(f"{name}: null handle", t.more(name, h=False), h=False)
+    t.rec(f"{pool}: no pool", t.more(pool))
+    t.rec(f"{pool}: no pool, max_len 0", t.more(pool, max_len=0))
+    t.rec(f"{pool}: no pool, B 0", t.more(pool, B=0))
+    t.rec(f"{wbeam}: no window", t.more(wbeam))
+    t.rec(f"{wbeam}: no window, k 0", t.more(wbeam, k=0))
+    assert t.lib.gitcap_student_window_reset(t.h, 2) == 0
+    t.rec(f"{wbeam}: empty window", t.more(wbeam))
+    assert t.lib.gitcap_student_pool_reset(t.h, 2) == 0
+    t.rec(f"{pool}: empty streams", t.more(pool))
+    t.rec(f"{pool}: empty streams, stream 5", t.more(pool, sid=(ctypes.c_int32 * 2)(0, 5)))
+    t.fill_window()
+    t.fill_pool()
+    assert t.lib.gitcap_student_pool_drop(t.h, 1) == 0
+    t.rec(f"{pool}: stream 1 empty", t.more(pool))
+    t.rec(f"{pool}: stream 1 empty, named twice", t.more(pool, sid=(ctypes.c_int32 * 2)(1, 1)))
+    t.fill_pool()
+    for name in MORE:
+        c = lambda **kw: t.more(name, **kw)                                         # noqa: E731
+        t.rec(f"{name}: null ids_out", c(ids=None))
+        t.rec(f"{name}: max_len 0", c(max_len=0))
+        t.rec(f"{name}: max_len 1", c(max_len=1))
+        t.rec(f"{name}: max_len 9", c(max_len=L + 1))
+        t.rec(f"{name}: max_len 10", c(max_len=L + 2))
+        if name == pool:
+            t.rec(f"{name}: stop 7", c(stop=7))
+            t.rec(f"{name}: null stream_ids", c(sid=None))
+            t.rec(f"{name}: null stream_ids, max_len 0", c(sid=None, max_len=0))
+            t.rec(f"{name}: stream 2", c(sid=(ctypes.c_int32 * 2)(0, 2)))
+            t.rec(f"{name}: stream -1", c(sid=(ctypes.c_int32 * 2)(-1, 1)))
+            t.rec(f"{name}: stream 0 twice", c(sid=(ctypes.c_int32 * 2)(0, 0)))
+            t.rec(f"{name}: B 0, stop 7", c(B=0, stop=7))
+            t.attach(S_LEN - 1)
+            t.rec(f"{name}: attached ld 5", c())
+            t.attach(S_LEN - 1)
+            t.rec(f"{name}: attached ld 5 and stop 7", c(stop=7))
+            t.attach(S_LEN - 1)
+            t.rec(f"{name}: attached ld 5 and B 0", c(B=0))
+            t.attach(S_LEN - 1)
+            t.rec(f"{name}: attached ld 5 and null stream_ids", c(sid=None))
+            t.attach_tk(S_LEN - 1)
+            t.rec(f"{name}: attached top-k ld 5", c())
+            t.attach_tk(S_LEN - 1)
+            t.rec(f"{name}: attached top-k ld 5 and stream 2", c(sid=(ctypes.c_int32 * 2)(0, 2)))
+        else:
+            t.rec(f"{name}: k 0", c(k=0))
+            t.rec(f"{name}: k 17", c(k=17))
+            t.rec(f"{name}: k 2", c(k=2))
+            t.rec(f"{name}: k 17, max_len 10", c(k=17, max_len=L + 2))
+            # a log-probability buffer with a short ld is not this call's: it stays for the greedy call behind it
+            t.attach(S_LEN - 1)
+            t.rec(f"{name}: attached ld 5", c())
+            t.rec(f"{name}: attached ld 5, then k 0", c(k=0))
+            t.rec(f"{name}: attached ld 5, then gitcap_student_greedy", t.call("gitcap_student_greedy"))
+        if name != wbeam:
+            t.rec(f"{name}: B 0", c(B=0))
+            t.rec(f"{name}: B 3", c(B=3))
+        if name == beam:
+            t.rec(f"{name}: null memory", c(mem=None))
+            t.rec(f"{name}: null memory, k 0", c(mem=None, k=0))
+            t.attach_fc(1)
+            t.rec(f"{name}: attached counts of 1 clip", c())
+            t.attach_fc(1)
+            t.rec(f"{name}: attached counts of 1 clip and k 0", c(k=0))
+        else:
+            t.attach_fc()
+            t.rec(f"{name}: attached counts", c())
+            t.attach_fc()
+            t.rec(f"{name}: attached counts and max_len 0", c(max_len=0))
+        t.attach_co(t.cfg.vocab_length - 2)
+        t.rec(f"{name}: attached constraints ban every column", c())
+        t.attach_co(t.cfg.vocab_length - 2)
+        t.rec(f"{name}: attached constraints ban every column and max_len 10", c(max_len=L + 2))
+        t.attach_pr(S_LEN + 1)
+        t.rec(f"{name}: attached prompt of 7", c())
+        t.attach_pr(S_LEN + 1)
+        t.attach_co(t.cfg.vocab_length - 2)
+        t.rec(f"{name}: attached prompt of 7 and constraints ban every column", c())
+        rc = c()
+        torch.cuda.synchronize()
+        t.rec(f"{name}: valid call", rc)
+    t.rec(f"{beam}: 1 clip x 2 beams", t.more(beam, B=1, k=2))
+    torch.cuda.synchronize()
+
+    # what stays pending: one block per entry point, the attachments set before it and seen() behind it
+    lib, h, F, part = t.lib, t.h, t.cfg.mem_tokens, t.mem[:, :1].contiguous()
+    one = (ctypes.c_int32 * 1)(0)
+    cnt = (ctypes.c_int32 * 2)()
+    for name in STUDENT:
+        t.pending(name, lambda: t.call(name), lambda: t.call(name, max_len=0))
+    t.pending("gitcap_student_window_greedy_partial",
+              lambda: lib.gitcap_student_window_greedy_partial(h, S_LEN, 0, _p(t.ids), _p(t.steps), t.frames, stream()),
+              lambda: lib.gitcap_student_window_greedy_partial(h, 0, 0, _p(t.ids), _p(t.steps), t.frames, stream()))
+    t.pending(pool, lambda: t.more(pool), lambda: t.more(pool, max_len=0))
+    t.pending(beam, lambda: t.more(beam), lambda: t.more(beam, k=0))
+    t.pending(wbeam, lambda: t.more(wbeam), lambda: t.more(wbeam, k=0))
+    score = lambda T: lib.gitcap_student_score(h, _p(t.d), S_LEN + 1, 2, T, None, -1, None, 0, None, None, None, None, stream())   # noqa: E731
+    t.pending("gitcap_student_score", lambda: score(S_LEN + 1), lambda: score(1))
+    t.pending("gitcap_student_set_memory", lambda: lib.gitcap_student_set_memory(h, _p(t.mem), 2, stream()),
+              lambda: lib.gitcap_student_set_memory(h, _p(t.mem), 0, stream()))
+    t.pending("gitcap_student_window_reset", lambda: lib.gitcap_student_window_reset(h, 2), lambda: lib.gitcap_student_window_reset(h, -1),
+              restore=t.fill_window)
+    t.pending("gitcap_student_window_push", lambda: lib.gitcap_student_window_push(h, _p(part), 2, 1, stream()),
+              lambda: lib.gitcap_student_window_push(h, _p(part), 2, F + 1, stream()))
+    t.pending("gitcap_student_pool_reset", lambda: lib.gitcap_student_pool_reset(h, 2), lambda: lib.gitcap_student_pool_reset(h, -1),
+              restore=t.fill_pool)
+    t.pending("gitcap_student_pool_push", lambda: lib.gitcap_student_pool_push(h, _p(part), one, 1, stream()),
+              lambda: lib.gitcap_student_pool_push(h, _p(part), one, 0, stream()))
+    t.pending("gitcap_student_pool_drop", lambda: lib.gitcap_student_pool_drop(h, 0), lambda: lib.gitcap_student_pool_drop(h, 7), restore=t.fill_pool)
+    t.pending("gitcap_student_pool_counts", lambda: lib.gitcap_student_pool_counts(h, cnt), lambda: lib.gitcap_student_pool_counts(h, None))
+    att = lambda T: lib.gitcap_student_attention(h, _p(t.d), S_LEN + 1, 2, T, -1, None, _p(t.mass), F, stream())                    # noqa: E731
+    t.pending("gitcap_student_attention", lambda: att(S_LEN), lambda: att(0))
+    fwd = lambda out: lib.gitcap_student_forward_decoder(h, _p(t.d), S_LEN + 1, 2, S_LEN, out, stream())                             # noqa: E731
+    t.pending("gitcap_student_forward_decoder", lambda: fwd(_p(t.logits)), lambda: fwd(None))
+
+    # before gitcap_student_finalize
+    u = _StudentMore(weights=False)
+    for name in MORE:
+        u.rec(f"{name}: not finalized", u.more(name))
+        u.rec(f"{name}: not finalized, max_len 0", u.more(name, max_len=0))
+    u.rec(f"{pool}: not finalized, B 0", u.more(pool, B=0))
+    u.rec(f"{pool}: not finalized, stop 7", u.more(pool, stop=7))
+    u.rec(f"{beam}: not finalized, k 0", u.more(beam, k=0))
+    u.rec(f"{wbeam}: not finalized, k 0", u.more(wbeam, k=0))
+    assert u.lib.gitcap_student_window_reset(u.h, 2) == 0
+    u.rec(f"{wbeam}: not finalized, empty window", u.more(wbeam))
+    torch.cuda.synchronize()
+    return t.rows + u.rows
+
+
 TEACHER_EXPECTED = [
     ('gitcap_greedy: null handle', -1, 'greedy: null handle'),
     ('gitcap_greedy: null ids_out', -1, 'greedy: bad arguments'),
@@ -555,6 +778,314 @@ STUDENT_EXPECTED = [
     ('gitcap_student_window_greedy_draft: not finalized, empty window', -2, 'student_window_greedy_draft: weights not finalized'),
 ]
 
+# recorded on the commit before the student got one pending record and one greedy / beam entry (see _student_more_observed)
+STUDENT_MORE_EXPECTED = [('gitcap_student_pool_greedy: null handle', -1, 'student_pool_greedy: null handle'),
+ ('gitcap_student_beam_search: null handle', -1, 'student_beam_search: null handle'),
+ ('gitcap_student_window_beam_search: null handle', -1, 'student_window_beam_search: null handle'),
+ ('gitcap_student_pool_greedy: no pool', -2, 'student_pool_greedy: no pool (gitcap_student_pool_reset first)'),
+ ('gitcap_student_pool_greedy: no pool, max_len 0', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: no pool, B 0', -1, 'student_pool_greedy: B outside [1, max_rows]'),
+ ('gitcap_student_window_beam_search: no window', -2, 'student_window_beam_search: no window (gitcap_student_window_reset first)'),
+ ('gitcap_student_window_beam_search: no window, k 0', -2, 'student_window_beam_search: no window (gitcap_student_window_reset first)'),
+ ('gitcap_student_window_beam_search: empty window', -2, 'student_window_beam_search: fewer than mem_tokens tokens pushed since the reset'),
+ ('gitcap_student_pool_greedy: empty streams', -2, 'student_pool_greedy: stream 0 holds no token'),
+ ('gitcap_student_pool_greedy: empty streams, stream 5', -1, 'student_pool_greedy: row 1 names stream 5, outside [0, 2)'),
+ ('gitcap_student_pool_greedy: stream 1 empty', -2, 'student_pool_greedy: stream 1 holds no token'),
+ ('gitcap_student_pool_greedy: stream 1 empty, named twice', -1, 'student_pool_greedy: stream 1 is named twice'),
+ ('gitcap_student_pool_greedy: null ids_out', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: max_len 0', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: max_len 1', 0, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: max_len 9', -1, 'student_pool_greedy: max_len exceeds max_text_len'),
+ ('gitcap_student_pool_greedy: max_len 10', -1, 'student_pool_greedy: max_len exceeds max_text_len'),
+ ('gitcap_student_pool_greedy: stop 7', -1, 'student_pool_greedy: unknown stop rule'),
+ ('gitcap_student_pool_greedy: null stream_ids', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: null stream_ids, max_len 0', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: stream 2', -1, 'student_pool_greedy: row 1 names stream 2, outside [0, 2)'),
+ ('gitcap_student_pool_greedy: stream -1', -1, 'student_pool_greedy: row 0 names stream -1, outside [0, 2)'),
+ ('gitcap_student_pool_greedy: stream 0 twice', -1, 'student_pool_greedy: stream 0 is named twice'),
+ ('gitcap_student_pool_greedy: B 0, stop 7', -1, 'student_pool_greedy: unknown stop rule'),
+ ('gitcap_student_pool_greedy: attached ld 5', -1, 'student_pool_greedy: the attached token log-probability buffer has ld < max_len'),
+ ('gitcap_student_pool_greedy: attached ld 5 and stop 7', -1, 'student_pool_greedy: unknown stop rule'),
+ ('gitcap_student_pool_greedy: attached ld 5 and B 0',
+  -1,
+  'student_pool_greedy: the attached token log-probability buffer has ld < max_len'),
+ ('gitcap_student_pool_greedy: attached ld 5 and null stream_ids', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_pool_greedy: attached top-k ld 5',
+  -1,
+  'student_pool_greedy: the attached top-k buffers have ld < the positions the call writes'),
+ ('gitcap_student_pool_greedy: attached top-k ld 5 and stream 2',
+  -1,
+  'student_pool_greedy: the attached top-k buffers have ld < the positions the call writes'),
+ ('gitcap_student_pool_greedy: B 0', -1, 'student_pool_greedy: B outside [1, max_rows]'),
+ ('gitcap_student_pool_greedy: B 3', -1, 'student_pool_greedy: B outside [1, max_rows]'),
+ ('gitcap_student_pool_greedy: attached counts',
+  -1,
+  'student_pool_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_greedy: attached counts and max_len 0',
+  -1,
+  'student_pool_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_greedy: attached constraints ban every column',
+  -1,
+  'student_pool_greedy: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_pool_greedy: attached constraints ban every column and max_len 10',
+  -1,
+  'student_pool_greedy: max_len exceeds max_text_len'),
+ ('gitcap_student_pool_greedy: attached prompt of 7', -1, 'student_pool_greedy: the attached prompt is longer than max_len'),
+ ('gitcap_student_pool_greedy: attached prompt of 7 and constraints ban every column',
+  -1,
+  'student_pool_greedy: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_pool_greedy: valid call',
+  0,
+  'student_pool_greedy: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_beam_search: null ids_out', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: max_len 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: max_len 1', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: max_len 9', 0, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: max_len 10', -1, 'student_beam_search: max_len exceeds max_text_len + 1'),
+ ('gitcap_student_beam_search: k 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: k 17', -1, 'student_beam_search: at most 16 beams'),
+ ('gitcap_student_beam_search: k 2', -1, 'student_beam_search: B * k exceeds max_rows'),
+ ('gitcap_student_beam_search: k 17, max_len 10', -1, 'student_beam_search: at most 16 beams'),
+ ('gitcap_student_beam_search: attached ld 5', 0, 'student_beam_search: at most 16 beams'),
+ ('gitcap_student_beam_search: attached ld 5, then k 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: attached ld 5, then gitcap_student_greedy',
+  -1,
+  'student_greedy: the attached token log-probability buffer has ld < max_len'),
+ ('gitcap_student_beam_search: B 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: B 3', -1, 'student_beam_search: B * k exceeds max_rows'),
+ ('gitcap_student_beam_search: null memory', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: null memory, k 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: attached counts of 1 clip', -1, 'student_beam_search: B = 2, but frame counts of 1 clips are attached'),
+ ('gitcap_student_beam_search: attached counts of 1 clip and k 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: attached constraints ban every column',
+  -1,
+  'student_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_beam_search: attached constraints ban every column and max_len 10',
+  -1,
+  'student_beam_search: max_len exceeds max_text_len + 1'),
+ ('gitcap_student_beam_search: attached prompt of 7', -1, 'student_beam_search: the attached prompt is longer than max_len - 1'),
+ ('gitcap_student_beam_search: attached prompt of 7 and constraints ban every column',
+  -1,
+  'student_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_beam_search: valid call',
+  0,
+  'student_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_window_beam_search: null ids_out', -1, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: max_len 0', -1, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: max_len 1', -1, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: max_len 9', 0, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: max_len 10', -1, 'student_window_beam_search: max_len exceeds max_text_len + 1'),
+ ('gitcap_student_window_beam_search: k 0', -1, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: k 17', -1, 'student_window_beam_search: at most 16 beams'),
+ ('gitcap_student_window_beam_search: k 2', -1, 'student_window_beam_search: B * k exceeds max_rows'),
+ ('gitcap_student_window_beam_search: k 17, max_len 10', -1, 'student_window_beam_search: at most 16 beams'),
+ ('gitcap_student_window_beam_search: attached ld 5', 0, 'student_window_beam_search: at most 16 beams'),
+ ('gitcap_student_window_beam_search: attached ld 5, then k 0', -1, 'student_window_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: attached ld 5, then gitcap_student_greedy',
+  -1,
+  'student_greedy: the attached token log-probability buffer has ld < max_len'),
+ ('gitcap_student_window_beam_search: attached counts',
+  -1,
+  'student_window_beam_search: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_beam_search: attached counts and max_len 0',
+  -1,
+  'student_window_beam_search: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_beam_search: attached constraints ban every column',
+  -1,
+  'student_window_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_window_beam_search: attached constraints ban every column and max_len 10',
+  -1,
+  'student_window_beam_search: max_len exceeds max_text_len + 1'),
+ ('gitcap_student_window_beam_search: attached prompt of 7',
+  -1,
+  'student_window_beam_search: the attached prompt is longer than max_len - 1'),
+ ('gitcap_student_window_beam_search: attached prompt of 7 and constraints ban every column',
+  -1,
+  'student_window_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_window_beam_search: valid call',
+  0,
+  'student_window_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_beam_search: 1 clip x 2 beams',
+  0,
+  'student_window_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_greedy: all five, valid arguments',
+  0,
+  'student_window_beam_search: the attached constraints could ban every column of a row (n_suppress + max_len >= vocab_size)'),
+ ('gitcap_student_greedy: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_greedy: all five, a bad argument', -1, 'student_greedy: bad arguments'),
+ ('gitcap_student_greedy: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_greedy: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_greedy: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy: all five, valid arguments',
+  -1,
+  'student_window_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy: all five, a bad argument',
+  -1,
+  'student_window_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_window_greedy: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_greedy_draft: all five, valid arguments',
+  -1,
+  'student_greedy_draft: a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take'),
+ ('gitcap_student_greedy_draft: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_greedy_draft: all five, a bad argument',
+  -1,
+  'student_greedy_draft: a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take'),
+ ('gitcap_student_greedy_draft: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_greedy_draft: all but the counts, valid arguments',
+  -1,
+  'student_greedy_draft: a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take'),
+ ('gitcap_student_greedy_draft: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_draft: all five, valid arguments',
+  -1,
+  'student_window_greedy_draft: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy_draft: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_draft: all five, a bad argument',
+  -1,
+  'student_window_greedy_draft: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy_draft: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_draft: all but the counts, valid arguments',
+  -1,
+  'student_window_greedy_draft: a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take'),
+ ('gitcap_student_window_greedy_draft: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_partial: all five, valid arguments',
+  -1,
+  'student_window_greedy_partial: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy_partial: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_partial: all five, a bad argument',
+  -1,
+  'student_window_greedy_partial: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_greedy_partial: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_window_greedy_partial: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_window_greedy_partial: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_pool_greedy: all five, valid arguments',
+  -1,
+  'student_pool_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_greedy: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_pool_greedy: all five, a bad argument',
+  -1,
+  'student_pool_greedy: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_greedy: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_pool_greedy: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_pool_greedy: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=0 tk=0 co=0 pr=0'),
+ ('gitcap_student_beam_search: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_beam_search: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_beam_search: all five, a bad argument', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_beam_search: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_beam_search: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_beam_search: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_window_beam_search: all five, valid arguments',
+  -1,
+  'student_window_beam_search: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_beam_search: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_window_beam_search: all five, a bad argument',
+  -1,
+  'student_window_beam_search: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_beam_search: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_window_beam_search: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_window_beam_search: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=0 pr=0'),
+ ('gitcap_student_score: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_score: all five, valid arguments, then', 0, 'greedy=0 fc=1 lp=1 tk=0 co=1 pr=1'),
+ ('gitcap_student_score: all five, a bad argument', -1, 'student_score: T < 2 (CLS and at least one token) or ld_ids < T'),
+ ('gitcap_student_score: all five, a bad argument, then', 0, 'greedy=0 fc=1 lp=1 tk=0 co=1 pr=1'),
+ ('gitcap_student_score: all but the counts, valid arguments',
+  0,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_score: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=0 co=1 pr=1'),
+ ('gitcap_student_set_memory: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_set_memory: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_set_memory: all five, a bad argument', -1, 'student_set_memory: B = 0, but frame counts of 2 clips are attached'),
+ ('gitcap_student_set_memory: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_set_memory: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_set_memory: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_reset: all five, valid arguments',
+  -1,
+  'student_window_reset: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_reset: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_reset: all five, a bad argument',
+  -1,
+  'student_window_reset: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_reset: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_reset: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_window_reset: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_push: all five, valid arguments',
+  -1,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_push: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_push: all five, a bad argument',
+  -1,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_window_push: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_window_push: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_window_push: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_reset: all five, valid arguments',
+  -1,
+  'student_pool_reset: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_reset: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_reset: all five, a bad argument',
+  -1,
+  'student_pool_reset: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_reset: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_reset: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_pool_reset: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_push: all five, valid arguments',
+  -1,
+  'student_pool_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_push: all five, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_push: all five, a bad argument',
+  -1,
+  'student_pool_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_push: all five, a bad argument, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_push: all but the counts, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_pool_push: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_drop: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_pool_drop: all five, valid arguments, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_drop: all five, a bad argument', -1, 'student_pool_drop: stream outside the pool'),
+ ('gitcap_student_pool_drop: all five, a bad argument, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_drop: all but the counts, valid arguments',
+  0,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_drop: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_counts: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_pool_counts: all five, valid arguments, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_counts: all five, a bad argument', -1, 'student_pool_counts: null counts_out'),
+ ('gitcap_student_pool_counts: all five, a bad argument, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_counts: all but the counts, valid arguments',
+  0,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_pool_counts: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_attention: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_attention: all five, valid arguments, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_attention: all five, a bad argument',
+  -1,
+  'student_attention: null or misaligned output, T < 1, ld_ids < T, ld_f < mem_tokens, or layer outside [-1, layers)'),
+ ('gitcap_student_attention: all five, a bad argument, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_attention: all but the counts, valid arguments',
+  0,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_attention: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_forward_decoder: all five, valid arguments', 0, 'student_window_push: null memory'),
+ ('gitcap_student_forward_decoder: all five, valid arguments, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_forward_decoder: all five, a bad argument', -1, 'student_forward_decoder: null logits'),
+ ('gitcap_student_forward_decoder: all five, a bad argument, then', 0, 'greedy=0 fc=1 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_forward_decoder: all but the counts, valid arguments',
+  0,
+  'student_window_push: per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take'),
+ ('gitcap_student_forward_decoder: all but the counts, valid arguments, then', 0, 'greedy=0 fc=0 lp=1 tk=1 co=1 pr=1'),
+ ('gitcap_student_pool_greedy: not finalized', -2, 'student_pool_greedy: weights not finalized'),
+ ('gitcap_student_pool_greedy: not finalized, max_len 0', -1, 'student_pool_greedy: bad arguments'),
+ ('gitcap_student_beam_search: not finalized', -2, 'student: weights not finalized'),
+ ('gitcap_student_beam_search: not finalized, max_len 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: not finalized', -2, 'student_window_beam_search: weights not finalized'),
+ ('gitcap_student_window_beam_search: not finalized, max_len 0', -2, 'student_window_beam_search: weights not finalized'),
+ ('gitcap_student_pool_greedy: not finalized, B 0', -1, 'student_pool_greedy: B outside [1, max_rows]'),
+ ('gitcap_student_pool_greedy: not finalized, stop 7', -1, 'student_pool_greedy: unknown stop rule'),
+ ('gitcap_student_beam_search: not finalized, k 0', -1, 'student_beam_search: bad arguments'),
+ ('gitcap_student_window_beam_search: not finalized, k 0', -2, 'student_window_beam_search: weights not finalized'),
+ ('gitcap_student_window_beam_search: not finalized, empty window', -2, 'student_window_beam_search: weights not finalized')]
+
 
 def _compare(got, want):
     for g, w in zip(got, want):
@@ -568,3 +1099,7 @@ def test_teacher_entry_point_errors():
 
 def test_student_entry_point_errors():
     _compare(_student_observed(), STUDENT_EXPECTED)
+
+
+def test_student_pool_beam_errors_and_pending_attachments():
+    _compare(_student_more_observed(), STUDENT_MORE_EXPECTED)
