@@ -1288,6 +1288,40 @@ int gitcap_student_attach_constraints(gitcap_student_t* h, const gitcap_constrai
  * > max_len - 1 (beam: at least one free position) gives GITCAP_ERR_ARG with nothing launched (the attachment is consumed all the
  * same).  The first attach allocates the two tables; a handle that never attaches allocates nothing and makes the launches it made. */
 int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids, int ld, const int32_t* lengths, int min_len, int max_len);
+/* Beam search that ends hypotheses at SEP: the search of gitcap_beam_search (GeneratorWithBeamSearchV2, model.py:479-678) on the
+ * student, in the place of the reference's unfinished loop (model.py:189-318, end-of-sequence handling commented out).  With this
+ * attachment a call of the beam family (gitcap_student_beam_search, _window_beam_search, _pool_beam_search) ranks k *
+ * per_node_beam_size candidates per clip and step; a candidate that is SEP, or any candidate of the last step, finishes the
+ * hypothesis ids[0 .. cur_len) with score = sum of log-probabilities (the finishing token's included) / cur_len^length_penalty; a
+ * clip keeps its num_keep_best best and is done once its worst kept score >= the best candidate sum / (max_len - 1)^length_penalty.
+ * A done clip's rows are padded (SEP, score 0, row 0) and its hypotheses frozen; the loop still runs its max_len - 1 steps, with
+ * no host decision.  repetition_penalty (model.py:522-531) rewrites the logits of the columns in a row's prefix before the
+ * log-softmax; with constraints attached, banned columns are -inf first.  A prompt's forced steps finish nothing.
+ *   num_keep_best        1 .. k: hypotheses kept and returned per clip
+ *   length_penalty       the exponent above (finite)
+ *   per_node_beam_size   0 = k; else 2 .. k, and k * per_node_beam_size <= 16 (with 1 a SEP candidate would leave a clip short of k
+ *                        live beams, which the reference asserts against, model.py:606; so the attachment needs k >= 2)
+ *   repetition_penalty   > 0 and finite, 1 = off
+ *   scores_out           device fp32 [B][num_keep_best]: the scores, best first; a rank without a hypothesis holds -1e5
+ *   lengths_out          device int32 [B][num_keep_best], nullable: tokens of each hypothesis, CLS included, SEP not; 0 = none
+ * While it is attached ids_out of the consuming call is [B][num_keep_best][max_len]: rank 0 first, every row filled with SEP
+ * behind its hypothesis.  A ONE-SHOT attachment: the next call of the beam family consumes it, whether that call succeeds or is
+ * refused; every greedy, draft, score and attention entry point consumes it and fails with GITCAP_ERR_ARG; NULL detaches.  It
+ * combines with the frame-count, constraint and prompt attachments.  The options are copied at the attach; the two pointers are
+ * written by the consuming call on its stream.  The first consuming call adds the hypothesis store to the beam workspace
+ * (gitcap_student_workspace_bytes); a handle that never attaches allocates nothing and makes the launches it made.
+ * Errors, GITCAP_ERR_ARG: a field outside the ranges above that do not depend on k, a null or misaligned scores_out, a misaligned
+ * lengths_out; at the consuming call num_keep_best > k, per_node_beam_size > k or 1 (k = 1 included), k * per_node_beam_size > 16,
+ * and under constraints n_suppress + max_len + k * per_node_beam_size > vocab_size.  Nothing is launched then. */
+typedef struct gitcap_student_search_options {
+    int32_t num_keep_best;
+    float length_penalty;
+    int32_t per_node_beam_size;
+    float repetition_penalty;
+    float* scores_out;
+    int32_t* lengths_out;
+} gitcap_student_search_options;
+int gitcap_student_attach_search(gitcap_student_t* h, const gitcap_student_search_options* o);
 /* gitcap_workspace_bytes for this handle: the device bytes of its workspace, attachments' buffers and the stream pool (weights, the
  * window's ring and page-locked memory not counted).  What an attachment's first use adds shows here. */
 int gitcap_student_workspace_bytes(const gitcap_student_t* h, int64_t* bytes);
@@ -1386,7 +1420,13 @@ int gitcap_student_window_greedy_partial(gitcap_student_t* h, int max_len, int s
  *           arguments, the stop rule and the ids_out / steps_out layout as gitcap_student_greedy.  Takes the attachments of
  *           gitcap_student_attach_token_logprobs and gitcap_student_attach_top_logprobs as gitcap_student_window_greedy does;
  *           attached frame counts are refused (and consumed) with the window calls' message.  Leaves the handle as
- *           gitcap_student_greedy with those counts would.  There is no draft and no beam form of the pool call.
+ *           gitcap_student_greedy with those counts would.  There is no draft form of the pool call.
+ *   beam    gitcap_student_pool_beam_search: the beam form of the pool call, k beams per named stream (B * k <= max_rows, k <= 16).
+ *           The streams' K|V rows are copied packed, once per stream, and the k rows of stream r read them through the key tables
+ *           (gitcap_student_attach_frame_counts' scheme for beams: nothing is repeated), so row r is bit for bit row r of
+ *           gitcap_student_beam_search with the streams' token counts attached.  ids_out as gitcap_student_beam_search; takes the
+ *           constraint, prompt and search attachments (gitcap_student_attach_search) as that call does; stream_ids / B are checked
+ *           as by the greedy form, with its errors.  Leaves the handle with B * k rows.
  *   drop    empties one stream (a camera that reconnected); the others are untouched.
  *   counts  host int32 [S]: the tokens each stream holds, 0 .. mem_tokens.
  * Pushes and pool calls may be issued on different streams: two events of the pool's own order a push behind the last pool call's
@@ -1400,6 +1440,7 @@ int gitcap_student_pool_reset(gitcap_student_t* h, int n_streams);
 int gitcap_student_pool_push(gitcap_student_t* h, const float* memory, const int32_t* stream_ids, int n, void* stream);
 int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, int B, int max_len, int stop, int64_t* ids_out,
                                int32_t* steps_out, int32_t* frames_out, void* stream);
+int gitcap_student_pool_beam_search(gitcap_student_t* h, const int32_t* stream_ids, int B, int k, int max_len, int64_t* ids_out, void* stream);
 int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id);
 int gitcap_student_pool_counts(const gitcap_student_t* h, int32_t* counts_out);
 

@@ -139,6 +139,39 @@ static int student_opts_test() {
         (void)take_opts(pending, r.take, r.refuse, &refused);
         CHECK(refused == 0 && opts_set(pending) == r.left);
     }
+    // the search part (gitcap_student_attach_search, OPT_SO): the beam family takes it, the greedy family, the drafts, score and
+    // attention refuse and consume it, everything else leaves it pending; it combines with counts, constraints and a prompt
+    float sc[1]; int32_t ln[1];
+    struct SoRow { unsigned take, refuse, refused; bool left; } so_rows[] = {
+        {OPT_FC | OPT_CO | OPT_PR | OPT_SO, 0, 0, false},           // student_beam_search
+        {OPT_CO | OPT_PR | OPT_SO, OPT_FC, OPT_FC, false},          // student_window_beam_search, student_pool_beam_search
+        {GREEDY | OPT_FC, OPT_SO, OPT_SO, false},                   // student_greedy
+        {GREEDY, OPT_FC | OPT_SO, OPT_FC | OPT_SO, false},          // student_window_greedy, _partial, student_pool_greedy
+        {OPT_LP | OPT_FC, DRAFT | OPT_SO, OPT_PR | OPT_CO | OPT_SO, false},     // student_greedy_draft
+        {OPT_TK, OPT_SO, OPT_SO, false},                            // student_score
+        {0, OPT_SO, OPT_SO, false},                                 // student_attention
+        {OPT_FC, 0, 0, true},                                       // student_set_memory
+        {0, OPT_FC, OPT_FC, true},                                  // the resets and pushes
+    };
+    for (const SoRow& r : so_rows) {
+        StudentOpts pending;
+        pending.se = StudentSearch{true, 2, 0.6f, 3, 1.3f, sc, ln};
+        pending.co = ConsOpt{true, 2, 0, len, 1};
+        pending.pr = PromptArgs{ids, 4, len, 1, 3};
+        pending.fc.assign(3, 2);
+        CHECK(opts_set(pending) == (OPT_SO | OPT_CO | OPT_PR | OPT_FC));
+        unsigned refused = 99;
+        const StudentOpts got = take_opts(pending, r.take, r.refuse, &refused);
+        CHECK(refused == r.refused && ((opts_set(pending) & OPT_SO) != 0) == r.left);
+        if (r.take & OPT_SO)
+            CHECK(got.se.on && got.se.n == 2 && got.se.length_penalty == 0.6f && got.se.pn == 3 && got.se.rp == 1.3f && got.se.scores == sc &&
+                  got.se.lengths == ln && got.co.on && got.pr.ids == ids);
+        else
+            CHECK(!got.se.on && got.se.scores == nullptr);
+        if (r.left) CHECK(pending.se.on && pending.se.n == 2 && pending.se.scores == sc && pending.se.lengths == ln);
+        (void)take_opts(pending, r.take, r.refuse, &refused);      // one-shot: nothing of it is found again
+        CHECK((refused & OPT_SO) == 0 && ((opts_set(pending) & OPT_SO) != 0) == r.left);
+    }
     return 0;
 }
 

@@ -266,13 +266,19 @@ inline void opts_clear(CallOpts& o, unsigned parts) {
     if (parts & OPT_FC) o.fc.B = 0;
     if (parts & OPT_TK) o.tk = TopkAttach{};
 }
-// The student's record (gitcap_student_attach_*): the same parts without search options, and counts that are a vector -- its max_rows
-// may exceed the 256 clips RaggedCounts holds (empty: none; an empty vector is copied without an allocation).
-struct StudentOpts { LpAttach lp{}; TopkAttach tk{}; ConsOpt co{}; PromptArgs pr{}; std::vector<int32_t> fc; };
+// The student's record (gitcap_student_attach_*): the same parts with search options of its own, and counts that are a vector -- its
+// max_rows may exceed the 256 clips RaggedCounts holds (empty: none; an empty vector is copied without an allocation).
+// se (gitcap_student_attach_search, part OPT_SO): the beam family's search that ends hypotheses at SEP -- n hypotheses kept per clip,
+// the length penalty, pn candidates per beam (resolved: 0 never gets here), the repetition penalty, and where the n scores and
+// lengths per clip go (device [B][n]; lengths nullable).  on = false: none.
+struct StudentSearch { bool on = false; int n = 1; float length_penalty = 1.0f; int pn = 0; float rp = 1.0f; float* scores = nullptr; int32_t* lengths = nullptr; };
+struct StudentOpts { LpAttach lp{}; TopkAttach tk{}; ConsOpt co{}; PromptArgs pr{}; std::vector<int32_t> fc; StudentSearch se{}; };
 inline unsigned opts_set(const StudentOpts& o) {
-    return (o.lp.p ? OPT_LP : 0u) | (o.pr.ids ? OPT_PR : 0u) | (o.co.on ? OPT_CO : 0u) | (!o.fc.empty() ? OPT_FC : 0u) | (o.tk.k != 0 ? OPT_TK : 0u);
+    return (o.lp.p ? OPT_LP : 0u) | (o.pr.ids ? OPT_PR : 0u) | (o.co.on ? OPT_CO : 0u) | (!o.fc.empty() ? OPT_FC : 0u) | (o.tk.k != 0 ? OPT_TK : 0u) |
+           (o.se.on ? OPT_SO : 0u);
 }
 inline void opts_clear(StudentOpts& o, unsigned parts) {
+    if (parts & OPT_SO) o.se = StudentSearch{};
     if (parts & OPT_LP) o.lp = LpAttach{};
     if (parts & OPT_PR) o.pr = PromptArgs{};
     if (parts & OPT_CO) o.co = ConsOpt{};

@@ -270,6 +270,25 @@ __global__ void student_beam_finish_kernel(const int64_t* __restrict__ ids, int6
     for (int i = threadIdx.x; i < max_len; i += 64) out[(size_t)b * max_len + i] = ids[(size_t)b * k * ld + i];
 }
 
+// gitcap_student_attach_search's lengths_out: the stored hypotheses' lengths [B][n] by rank, as search.hip's beam_finish_kernel ranks
+// the slots (descending score, equal scores in storage order); a rank without a hypothesis holds 0.  One thread per (clip, slot).
+__global__ void student_hyp_lengths_kernel(const float* __restrict__ hyp_score, const int32_t* __restrict__ hyp_len, int n, int total,
+                                           int32_t* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= total) return;
+    const int b = i / n, slot = i - b * n, len = hyp_len[i];
+    int rank = slot;                            // an empty slot: behind every stored one, in slot order
+    if (len > 0) {
+        rank = 0;
+        for (int j = 0; j < n; ++j) {
+            if (j == slot || hyp_len[b * n + j] <= 0) continue;
+            const float sj = hyp_score[b * n + j];
+            rank += sj > hyp_score[i] || (sj == hyp_score[i] && j < slot);
+        }
+    }
+    out[b * n + rank] = len > 0 ? len : 0;
+}
+
 hipError_t launch_student_prompt_stage(const StudentPromptStageArgs& a, hipStream_t s) {
     if (!a.prm_ids || !a.prm_len || !a.ids || a.rows < 1 || a.k < 1 || a.max_len < 1 || a.ld_prm < a.max_len || a.ld < a.max_len || a.pmin < 1 ||
         (a.lp && a.ld_lp + 1 < a.pmin))
@@ -414,6 +433,13 @@ struct gitcap_student : HandleCore {
         int* cand_idx = nullptr; int32_t* src_rows = nullptr;
         int64_t *ids0 = nullptr, *ids1 = nullptr;
         bf16_t* kvs2 = nullptr; char* topk_scratch = nullptr;
+        // the search that ends hypotheses at SEP (gitcap_student_attach_search), allocated by its first call: what search.hip's
+        // bookkeeping keeps beside the buffers above -- words [R], done / hyp_len / hyp_score [R] (B * n <= B * k), hyp_ids
+        // [R][Tmax] -- and candidate slots for k * per_node_beam_size <= 16 per clip ([R][16]: B <= R clips)
+        int64_t *words = nullptr, *hyp_ids = nullptr;
+        int32_t *done = nullptr, *hyp_len = nullptr;
+        float *hyp_score = nullptr, *cand16_scores = nullptr;
+        int* cand16_idx = nullptr;
     } bw;
     // memory-token window (gitcap_student_window_*), allocated by window_reset: ring = the cross-attention K|V rows of the last F
     // tokens of win_B clips, bf16 [L][win_B][F slots][2D]; win (RingCursor) = where the next token goes and how many have been
@@ -608,14 +634,16 @@ int text_forward(gitcap_student* h, const TextReq& q, hipStream_t s) {
 // ---- clips of different length (gitcap_student_attach_frame_counts) -------------------------------------------------------------
 using Counts = std::vector<int32_t>;
 // An entry point's take (host_logic.h: take_opts): the parts in `parts` go to *o, consumed whatever becomes of the call; of the parts in
-// `refuse`, cleared, the first that held an attachment is the call's error: counts, prompt, constraints, top-k, as ever reported.
+// `refuse`, cleared, the first that held an attachment is the call's error: counts, prompt, constraints, search options, top-k, as
+// ever reported.
 int take(gitcap_student* h, const std::string& who, unsigned parts, unsigned refuse, StudentOpts* o = nullptr) {
     unsigned refused = 0;
     StudentOpts taken = take_opts(h->pending, parts, refuse, &refused);
     if (o) *o = std::move(taken);
     const char* what = refused & OPT_FC ? ": per-clip frame counts are attached (gitcap_student_attach_frame_counts), which this call does not take"
                      : refused & OPT_PR ? ": a prompt is attached (gitcap_student_attach_prompt), which a draft call does not take"
-                     : refused & OPT_CO ? ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take" : nullptr;
+                     : refused & OPT_CO ? ": constraints are attached (gitcap_student_attach_constraints), which a draft call does not take"
+                     : refused & OPT_SO ? ": search options are attached (gitcap_student_attach_search), which only the beam family takes" : nullptr;
     if (what) return fail(h, GITCAP_ERR_ARG, who + what);
     return refused & OPT_TK ? fail(h, GITCAP_ERR_ARG, refused_message(who.c_str(), OPT_TK)) : 0;
 }
@@ -1106,24 +1134,35 @@ int greedy_draft_core(gitcap_student* h, int B, const int64_t* draft, int ld_dra
     return 0;
 }
 
-int beam_workspace(gitcap_student* h) {
+// search: the call took search options (gitcap_student_attach_search) -- the hypothesis store joins the workspace at the first such
+// call, each buffer on its own (a call repeated after a failed allocation keeps what the first one got)
+int beam_workspace(gitcap_student* h, bool search = false) {
     gitcap_student::BeamWs& w = h->bw;
-    if (w.memrep) return 0;
     const size_t R = h->R, ld = (size_t)h->Tmax + 1;
-    const int D = h->D, V = h->V;
     int rc = 0;
-    rc = rc ? rc : dev_alloc(h, &w.memrep, R * h->F * D);
-    rc = rc ? rc : dev_alloc(h, &w.scores, R);
-    rc = rc ? rc : dev_alloc(h, &w.cand_scores, R);
-    rc = rc ? rc : dev_alloc(h, &w.cand_idx, R);
-    rc = rc ? rc : dev_alloc(h, &w.src_rows, R);
-    rc = rc ? rc : dev_alloc(h, &w.ids0, R * ld);
-    rc = rc ? rc : dev_alloc(h, &w.ids1, R * ld);
-    rc = rc ? rc : dev_alloc(h, &w.logits, R * (size_t)V);
-    rc = rc ? rc : dev_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
-    rc = rc ? rc : dev_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
-    if (rc) w = gitcap_student::BeamWs{};
-    return rc;
+    if (!w.memrep) {
+        const int D = h->D, V = h->V;
+        rc = rc ? rc : dev_alloc(h, &w.memrep, R * h->F * D);
+        rc = rc ? rc : dev_alloc(h, &w.scores, R);
+        rc = rc ? rc : dev_alloc(h, &w.cand_scores, R);
+        rc = rc ? rc : dev_alloc(h, &w.cand_idx, R);
+        rc = rc ? rc : dev_alloc(h, &w.src_rows, R);
+        rc = rc ? rc : dev_alloc(h, &w.ids0, R * ld);
+        rc = rc ? rc : dev_alloc(h, &w.ids1, R * ld);
+        rc = rc ? rc : dev_alloc(h, &w.logits, R * (size_t)V);
+        rc = rc ? rc : dev_alloc(h, &w.kvs2, (size_t)h->L * h->R * h->Tmax * 3 * D);
+        rc = rc ? rc : dev_alloc(h, &w.topk_scratch, beam_topk_scratch_bytes(h->R, 1, V, 16));     // rows x chunks, whatever the split into clips x beams
+        if (rc) w = gitcap_student::BeamWs{};
+    }
+    if (rc || !search) return rc;
+    if (!w.words && (rc = dev_alloc(h, &w.words, R))) { w.words = nullptr; return rc; }
+    if (!w.done && (rc = dev_alloc(h, &w.done, R))) { w.done = nullptr; return rc; }
+    if (!w.hyp_len && (rc = dev_alloc(h, &w.hyp_len, R))) { w.hyp_len = nullptr; return rc; }
+    if (!w.hyp_score && (rc = dev_alloc(h, &w.hyp_score, R))) { w.hyp_score = nullptr; return rc; }
+    if (!w.hyp_ids && (rc = dev_alloc(h, &w.hyp_ids, R * h->Tmax))) { w.hyp_ids = nullptr; return rc; }
+    if (!w.cand16_scores && (rc = dev_alloc(h, &w.cand16_scores, R * 16))) { w.cand16_scores = nullptr; return rc; }
+    if (!w.cand16_idx && (rc = dev_alloc(h, &w.cand16_idx, R * 16))) { w.cand16_idx = nullptr; return rc; }
+    return 0;
 }
 
 // the token loop of beam_search against the memory K|V of B * k rows in h->memkv (set_memory of the repeated rows, or the window's gather)
@@ -1131,10 +1170,20 @@ int beam_workspace(gitcap_student* h) {
 // the ranking runs its BAN form: banned columns are -inf ahead of the log-softmax
 // pr.ids set (max_len counts the prompt): the rows start from the staged prompts, clip b's row for its k beams, and while a clip is
 // inside its prompt the bookkeeping step appends the prompt's token to every one of its rows instead of ranking (the FORCED form)
-int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s, const ConsOpt& co, const PromptArgs& pr) {
-    const int rows = B * k, D = h->D, V = h->V, ld = h->Tmax + 1;
+// se.on (gitcap_student_attach_search): the bookkeeping is the teacher's (search.hip: launch_beam_init / _step / _finish over this
+// workspace), step t being its cur_len = t + 1.  Those kernels take id rows whose pitch is the call's max_len, so the two id buffers
+// are used at that pitch (they hold Tmax + 1 columns per row) and every launch that reads them is told so.  K = k * se.pn candidates
+// are ranked under se.rp; ids_out is [B][se.n][max_len].  A done clip's k rows are padded by the step kernel -- SEP appended to a
+// copy of row 0's prefix, src_rows = 0, so the K/V rows the gather gives them are row 0's as well: ids and cache stay consistent,
+// the PAD-key mask (by id) sees row 0's ids.  Whatever those rows compute is read by nobody else: a row attends to its own cache and
+// its clip's memory only, its logits rank among its own clip's candidates only, and the step kernel reads no candidate of a done
+// clip and leaves its hypotheses frozen.  No host decision: all max_len - 1 steps run.
+int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hipStream_t s, const ConsOpt& co, const PromptArgs& pr,
+              const StudentSearch& se) {
+    const int rows = B * k, D = h->D, V = h->V, ld = se.on ? max_len : h->Tmax + 1, K = se.on ? k * se.pn : k;
     int rc = 0;
     gitcap_student::BeamWs& w = h->bw;
+    const BeamBuffers bb{w.ids0, w.ids1, w.words, w.hyp_ids, w.scores, w.hyp_score, w.src_rows, w.done, w.hyp_len};
     const PromptArgs tab = table_prompt(h, pr, max_len - 1);        // (at least one free position)
     if (pr.ids) {
         if ((rc = write_prompt_tables(h, pr, B, s))) return rc;
@@ -1143,18 +1192,25 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
     } else {
         HIP_OK(h, launch_fill_i64(w.ids0, ld, rows, h->c.cls_token_id, s));
     }
-    hipLaunchKernelGGL(beam_scores_init_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, w.scores, rows, k);
-    HIP_OK(h, hipGetLastError());
+    if (se.on) {            // scores [0, -1e9, ..], src_rows the identity, no clip done, no hypothesis stored (column 0 is CLS already)
+        HIP_OK(h, launch_beam_init(bb, B, k, se.n, max_len, h->c.cls_token_id, s));
+    } else {
+        hipLaunchKernelGGL(beam_scores_init_kernel, dim3((rows + 63) / 64), dim3(64), 0, s, w.scores, rows, k);
+        HIP_OK(h, hipGetLastError());
+    }
     int64_t *cur = w.ids0, *nxt = w.ids1;
     bf16_t* const kvs_home = h->kvs;
     const size_t kv_layer = (size_t)h->R * h->Tmax * 3 * D;
     TextReq q;                  // one position of every beam row -> its logits
     q.ld_ids = ld; q.rows = rows; q.T = 1; q.logits_out = w.logits;
-    CandArgs ca{};              // the k best of every clip's k * V candidates, no penalty
-    ca.logits = w.logits; ca.ld = V; ca.beam_scores = w.scores; ca.rp = 1.0f; ca.B = B; ca.beams = k; ca.V = V;
-    ca.out_scores = w.cand_scores; ca.out_idx = w.cand_idx;
+    CandArgs ca{};              // the K best of every clip's k * V candidates (without search options: K = k, no penalty)
+    ca.logits = w.logits; ca.ld = V; ca.beam_scores = w.scores; ca.ld_ids = ld; ca.rp = se.on ? se.rp : 1.0f; ca.B = B; ca.beams = k; ca.V = V;
+    ca.out_scores = se.on ? w.cand16_scores : w.cand_scores; ca.out_idx = se.on ? w.cand16_idx : w.cand_idx;
     const HeadBan bn{h->ban_mask, h->ban_ld};
     if (co.on) ca.bn = &bn;
+    BeamStepArgs bs{};
+    bs.n = se.n; bs.cand_scores = ca.out_scores; bs.cand_idx = ca.out_idx; bs.B = B; bs.beams = k; bs.K = K; bs.V = V; bs.max_len = max_len;
+    bs.eos = h->c.sep_token_id; bs.length_penalty = se.length_penalty; bs.sampled = false; bs.prompt = pr.ids ? &tab : nullptr;
     for (int t = 0; t + 1 < max_len && !rc; ++t) {                      // the token at position t is decoded, position t + 1 chosen
         if (t > 0) {                                                    // rows continue beam src_rows[r]: positions 0 .. t-1, all layers
             bf16_t* other = h->kvs == kvs_home ? w.kvs2 : kvs_home;
@@ -1170,14 +1226,28 @@ int beam_loop(gitcap_student* h, int B, int k, int max_len, int64_t* ids_out, hi
                                                   h->ban_mask, h->ban_ld, s);
             if (eb != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: ban_mask: ") + hipGetErrorString(eb)); break; }
         }
-        hipError_t e = launch_beam_topk(ca, k, w.topk_scratch, s);
+        ca.prefix_ids = cur; ca.cur_len = t + 1;                        // (read under a penalty only)
+        hipError_t e = launch_beam_topk(ca, K, w.topk_scratch, s);
         if (e != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, std::string("student_beam_search: beam_topk: ") + hipGetErrorString(e)); break; }
-        const StudentBeamStepArgs st{w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, B, k, V, t, ld, pr.ids ? &tab : nullptr};
-        if (launch_student_beam_step(st, s) != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
+        if (se.on) {
+            bs.cur_len = t + 1; bs.cur = cur == w.ids0 ? 0 : 1;
+            if (launch_beam_step(bb, bs, s) != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
+        } else {
+            const StudentBeamStepArgs st{w.cand_scores, w.cand_idx, cur, nxt, w.scores, w.src_rows, B, k, V, t, ld, pr.ids ? &tab : nullptr};
+            if (launch_student_beam_step(st, s) != hipSuccess) { rc = fail(h, GITCAP_ERR_HIP, "student_beam_search: beam step launch"); break; }
+        }
         std::swap(cur, nxt);
     }
     h->kvs = kvs_home;                                                  // (the captured greedy graphs hold this pointer)
     if (rc) return rc;
+    if (se.on) {            // the n hypotheses of every clip by rank -> the caller's buffers
+        HIP_OK(h, launch_beam_finish(bb, se.n, B, max_len, h->c.sep_token_id, BeamFinishOut{ids_out, se.scores, nullptr, nullptr}, s));
+        if (se.lengths) {
+            hipLaunchKernelGGL(student_hyp_lengths_kernel, dim3((B * se.n + 63) / 64), dim3(64), 0, s, w.hyp_score, w.hyp_len, se.n, B * se.n, se.lengths);
+            HIP_OK(h, hipGetLastError());
+        }
+        return 0;
+    }
     hipLaunchKernelGGL(student_beam_finish_kernel, dim3(B), dim3(64), 0, s, cur, ids_out, k, ld, max_len);
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1221,7 +1291,7 @@ int greedy_entry(gitcap_student* h, const char* who, unsigned parts, unsigned re
     const std::string w(who);
     if (!h) return fail(h, GITCAP_ERR_ARG, w + ": null handle");
     StudentOpts o;
-    if (int bad = take(h, w, parts, refuse, &o)) return bad;
+    if (int bad = take(h, w, parts, refuse | OPT_SO, &o)) return bad;         // (search options are the beam family's)
     if (early_bad || !ids_out || max_len <= 0) return fail(h, GITCAP_ERR_ARG, w + ": bad arguments");
     if (max_len + 1 > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len");
     if (stop != GITCAP_STOP_NEVER && stop != GITCAP_STOP_ALL_SEP) return fail(h, GITCAP_ERR_ARG, w + ": unknown stop rule");
@@ -1272,12 +1342,21 @@ int beam_entry(gitcap_student* h, const char* who, unsigned parts, unsigned refu
     if (k > 16) return fail(h, GITCAP_ERR_ARG, w + ": at most 16 beams");
     if ((int64_t)B * k > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B * k exceeds max_rows");
     if (max_len > h->Tmax) return fail(h, GITCAP_ERR_ARG, w + ": max_len exceeds max_text_len + 1");
-    if ((bad = cons_check(h, w, o.co, max_len, k))) return bad;
+    StudentSearch& se = o.se;
+    if (se.on) {
+        if (se.pn == 0) se.pn = k;
+        if (se.n > k) return fail(h, GITCAP_ERR_ARG, w + ": the attached num_keep_best exceeds k");
+        if (se.pn > k || k * se.pn > 16) return fail(h, GITCAP_ERR_ARG, w + ": the attached per_node_beam_size exceeds k, or k * per_node_beam_size > 16 candidates");
+        // with one candidate per beam a SEP candidate leaves a clip short of k live beams, which the reference asserts against
+        // (model.py:606); the device bookkeeping has no way to report it, so refuse up front
+        if (se.pn < 2) return fail(h, GITCAP_ERR_ARG, w + ": the attached search needs per_node_beam_size >= 2, so k >= 2 (model.py:606)");
+    }
+    if ((bad = cons_check(h, w, o.co, max_len, se.on ? k * se.pn : k))) return bad;
     if (o.pr.ids && o.pr.max_len > max_len - 1) return fail(h, GITCAP_ERR_ARG, w + ": the attached prompt is longer than max_len - 1");
     GUARD(h);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = source(o, s)) return rc;
-    return beam_loop(h, B, k, max_len, ids_out, s, o.co, o.pr);
+    return beam_loop(h, B, k, max_len, ids_out, s, o.co, o.pr, se);
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1286,7 +1365,10 @@ int beam_entry(gitcap_student* h, const char* who, unsigned parts, unsigned refu
 // tables of gitcap_student_attach_frame_counts, so the token loop is that call's.  Every n_r == F: the packed layout is the dense
 // one and the loop takes the dense launches, as a full lockstep window's.  frames (host, nullable) = n_r.
 // (The teacher's pool_plan checks a row's id, duplicate and emptiness in one pass: the two report different faults first.)
-int pool_memory(gitcap_student* h, const std::string& w, const int32_t* ids, int B, hipStream_t s, int32_t* frames) {
+// k > 1 (gitcap_student_pool_beam_search): decoder rows r * k .. r * k + k - 1 are the beams of stream ids[r].  The gather is the same
+// launch -- every stream's rows are copied once -- and the k rows read them through the key tables, as set_memory(.., ragged, k) has
+// them: nothing is repeated, so the tables are written whether or not every stream is full.
+int pool_memory(gitcap_student* h, const std::string& w, const int32_t* ids, int B, hipStream_t s, int32_t* frames, int k = 1) {
     if (B < 1 || B > h->R) return fail(h, GITCAP_ERR_ARG, w + ": B outside [1, max_rows]");
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, w + ": weights not finalized");
     if (!h->pool_ring) return fail(h, GITCAP_ERR_STATE, w + ": no pool (gitcap_student_pool_reset first)");
@@ -1315,16 +1397,17 @@ int pool_memory(gitcap_student* h, const std::string& w, const int32_t* ids, int
     h->have_memory = false;
     HIP_OK(h, h->pool_tab_host.copy(h->pool_tab, 0, (size_t)B * 4, s));
     HIP_OK(h, h->pool_tab_host.mark(s));
-    if (!dense)
-        if (int rc = write_key_tables(h, B, [&](int r) { return std::make_pair((int)tab[4 * r + 3], (int)tab[4 * r + 2]); }, s)) return rc;
-    h->ragged = !dense;
+    const bool ragged = !dense || k > 1;
+    if (ragged)
+        if (int rc = write_key_tables(h, B * k, [&](int r) { return std::make_pair((int)tab[4 * (r / k) + 3], (int)tab[4 * (r / k) + 2]); }, s)) return rc;
+    h->ragged = ragged;
     hipLaunchKernelGGL(student_pool_gather_kernel, dim3(B * F, h->L), dim3(64), 0, s, h->pool_ring, h->memkv, h->pool_tab, F, 2 * D / 8,
                        (size_t)h->pool_S * F * 2 * D, (size_t)h->R * F * 2 * D);
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, h->pool_order.after_read(s));
     if (frames)
         for (int r = 0; r < B; ++r) frames[r] = tab[4 * r + 2];
-    h->cur_B = B;
+    h->cur_B = B * k;
     h->have_memory = true;
     return 0;
 }
@@ -1347,12 +1430,12 @@ int gitcap_student_greedy(gitcap_student_t* h, const float* memory, int B, int m
 // K/V rows follow their beams (gather into the second cache buffer) and so do the id rows the PAD-key mask reads.
 int gitcap_student_beam_search(gitcap_student_t* h, const float* memory, int B, int k, int max_len, int64_t* ids_out, void* stream) {
     const char* who = "student_beam_search";
-    return beam_entry(h, who, OPT_FC | OPT_CO | OPT_PR, 0, k, max_len, ids_out, stream,
+    return beam_entry(h, who, OPT_FC | OPT_CO | OPT_PR | OPT_SO, 0, k, max_len, ids_out, stream,
         [&](int* clips) { *clips = B; return memory ? 0 : fail(h, GITCAP_ERR_ARG, "student_beam_search: bad arguments"); },
         [&](const StudentOpts& o, hipStream_t s) -> int {
             const Counts* ragged = nullptr;
             if (int bad = counts_for_call(h, who, o.fc, B, &ragged)) return bad;
-            if (int rc = beam_workspace(h)) return rc;
+            if (int rc = beam_workspace(h, o.se.on)) return rc;
             if (ragged) return set_memory(h, memory, B, s, ragged, k);      // the k beams of a clip read its packed K|V rows through the tables: nothing is repeated
             hipLaunchKernelGGL(repeat_rows_kernel, dim3(4, B * k), dim3(256), 0, s, memory, h->bw.memrep, k, h->F * h->D / 4);
             HIP_OK(h, hipGetLastError());
@@ -1524,11 +1607,25 @@ int gitcap_student_attach_prompt(gitcap_student_t* h, const int64_t* prompt_ids,
     return 0;
 }
 
+int gitcap_student_attach_search(gitcap_student_t* h, const gitcap_student_search_options* o) {
+    if (!h) return fail(h, GITCAP_ERR_ARG, "student_attach_search: null handle");
+    h->pending.se = StudentSearch{};
+    if (!o) return 0;                                        // detach
+    if (o->num_keep_best < 1 || o->num_keep_best > 16 || o->per_node_beam_size < 0 || o->per_node_beam_size == 1 || o->per_node_beam_size > 16)
+        return fail(h, GITCAP_ERR_ARG, "student_attach_search: num_keep_best outside [1, 16], or per_node_beam_size not 0 or in [2, 16]");
+    if (!std::isfinite(o->length_penalty) || !(o->repetition_penalty > 0.f) || !std::isfinite(o->repetition_penalty))
+        return fail(h, GITCAP_ERR_ARG, "student_attach_search: length_penalty must be finite, repetition_penalty > 0 and finite");
+    if (!o->scores_out || (((uintptr_t)o->scores_out | (uintptr_t)o->lengths_out) & 3) != 0)
+        return fail(h, GITCAP_ERR_ARG, "student_attach_search: null scores_out or a misaligned pointer");
+    h->pending.se = StudentSearch{true, o->num_keep_best, o->length_penalty, o->per_node_beam_size, o->repetition_penalty, o->scores_out, o->lengths_out};
+    return 0;
+}
+
 int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, const int32_t* lengths, int64_t ignore_id,
                          float* token_lp, int ld_lp, float* row_sum, int32_t* row_cnt, int64_t* top1_ids, float* top1_lp, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_score: null handle");
     StudentOpts o;
-    (void)take(h, "student_score", OPT_TK, 0, &o);
+    if (int bad = take(h, "student_score", OPT_TK, OPT_SO, &o)) return bad;
     const TopkAttach& tk = o.tk;
     if (int bad = tk_check(h, "student_score", tk, T - 1)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_score: weights not finalized");
@@ -1549,6 +1646,7 @@ int gitcap_student_score(gitcap_student_t* h, const int64_t* ids, int ld_ids, in
 int gitcap_student_attention(gitcap_student_t* h, const int64_t* ids, int ld_ids, int rows, int T, int layer, const int32_t* lengths,
                              float* frame_mass, int ld_f, void* stream) {
     if (!h) return fail(h, GITCAP_ERR_ARG, "student_attention: null handle");
+    if (int bad = take(h, "student_attention", 0, OPT_SO)) return bad;
     if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_attention: weights not finalized");
     if (!h->have_memory) return fail(h, GITCAP_ERR_STATE, "student_attention before set_memory");
     if (!frame_mass || T < 1 || ld_ids < T || ld_f < h->F || layer < -1 || layer >= h->L || (((uintptr_t)frame_mass | (uintptr_t)lengths) & 3) != 0)
@@ -1589,13 +1687,13 @@ int gitcap_student_draft_stats(const gitcap_student_t* h, int64_t* out4) {
 
 int gitcap_student_window_beam_search(gitcap_student_t* h, int k, int max_len, int64_t* ids_out, void* stream) {
     const char* who = "student_window_beam_search";
-    return beam_entry(h, who, OPT_CO | OPT_PR, OPT_FC, k, max_len, ids_out, stream,
+    return beam_entry(h, who, OPT_CO | OPT_PR | OPT_SO, OPT_FC, k, max_len, ids_out, stream,
         [&](int* clips) {
             *clips = h->win_B;
             if (!h->finalized) return fail(h, GITCAP_ERR_STATE, "student_window_beam_search: weights not finalized");
             return h->win_ring ? 0 : fail(h, GITCAP_ERR_STATE, "student_window_beam_search: no window (gitcap_student_window_reset first)");
         },
-        [&](const StudentOpts&, hipStream_t s) { const int rc = beam_workspace(h); return rc ? rc : window_memory(h, who, k, s); });
+        [&](const StudentOpts& o, hipStream_t s) { const int rc = beam_workspace(h, o.se.on); return rc ? rc : window_memory(h, who, k, s); });
 }
 
 // ---- stream pool ---------------------------------------------------------------------------------------------------------------
@@ -1691,6 +1789,19 @@ int gitcap_student_pool_greedy(gitcap_student_t* h, const int32_t* stream_ids, i
     return greedy_entry(h, "student_pool_greedy", GREEDY_PARTS, OPT_FC, nullptr, max_len, stop, ids_out, steps_out, stream,
         [=](const StudentOpts&, const std::string& who, hipStream_t s, int* rows) { *rows = B; return pool_memory(h, who, stream_ids, B, s, frames_out); },
         !stream_ids);
+}
+
+// The beam form of the pool call: beam_entry over the pool's memory.  stream_ids and B are checked as gitcap_student_pool_greedy checks
+// them (a null stream_ids is the family's "bad arguments"; B's range comes ahead of the family's checks so that it keeps its message).
+int gitcap_student_pool_beam_search(gitcap_student_t* h, const int32_t* stream_ids, int B, int k, int max_len, int64_t* ids_out, void* stream) {
+    const std::string who = "student_pool_beam_search";
+    return beam_entry(h, who.c_str(), OPT_CO | OPT_PR | OPT_SO, OPT_FC, k, max_len, ids_out, stream,
+        [&](int* clips) {
+            *clips = B;
+            if (!stream_ids) return fail(h, GITCAP_ERR_ARG, who + ": bad arguments");
+            return B < 1 || B > h->R ? fail(h, GITCAP_ERR_ARG, who + ": B outside [1, max_rows]") : 0;
+        },
+        [&](const StudentOpts& o, hipStream_t s) { const int rc = beam_workspace(h, o.se.on); return rc ? rc : pool_memory(h, who, stream_ids, B, s, nullptr, k); });
 }
 
 int gitcap_student_pool_drop(gitcap_student_t* h, int stream_id) {

@@ -40,6 +40,12 @@ class CSamplingOptions(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int32), ("top_p", c_float), ("seed", ctypes.c_uint64)]
 
 
+class CStudentSearchOptions(ctypes.Structure):
+    """struct gitcap_student_search_options (include/gitcap.h)."""
+    _fields_ = [("num_keep_best", c_int32), ("length_penalty", c_float), ("per_node_beam_size", c_int32), ("repetition_penalty", c_float),
+                ("scores_out", c_void_p), ("lengths_out", c_void_p)]
+
+
 class CConstraints(ctypes.Structure):
     """struct gitcap_constraints (include/gitcap.h)."""
     _fields_ = [("no_repeat_ngram_size", c_int32), ("min_length", c_int32), ("suppress", c_void_p), ("n_suppress", c_int32)]
@@ -299,6 +305,9 @@ SYMBOLS = {
     "gitcap_student_pool_reset": (c_int, [c_void_p, c_int]),
     "gitcap_student_pool_push": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_void_p]),
     "gitcap_student_pool_greedy": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    # the student's search that ends hypotheses at SEP, and the pool's beam form (tests/test_student_search_e2e_gpu.py)
+    "gitcap_student_attach_search": (c_int, [c_void_p, POINTER(CStudentSearchOptions)]),
+    "gitcap_student_pool_beam_search": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p]),
     "gitcap_student_pool_drop": (c_int, [c_void_p, c_int]),
     "gitcap_student_pool_counts": (c_int, [c_void_p, POINTER(c_int32)]),
     "gitcap_dbg_attn_small_varlen": (c_int, [POINTER(CDbgAttnSmallArgs), c_void_p, c_void_p, c_void_p]),

@@ -86,6 +86,102 @@ def banned_tokens(prefix: List[int], n: int, min_length: int, sep_id: int, suppr
     return sorted(c for c in out if 0 <= c < V)
 
 
+def eos_beam_search(step: Callable[[torch.Tensor], torch.Tensor], start: List[List[int]], *, k: int, max_len: int, sep_id: int,
+                    length_penalty: float = 1.0, num_keep_best: int = 1, per_node_beam_size: Optional[int] = None,
+                    repetition_penalty: float = 1.0, rule: Optional[Callable] = None, stats: Optional[dict] = None) -> dict:
+    """The search of gitcap_student_attach_search (include/gitcap.h) over given logits, device free: the operator of
+    GeneratorWithBeamSearchV2.search (model.py:479-678; oracle/search_oracle.py restates it) with what the device loop adds -- a
+    forced prompt, banned columns, and all max_len - 1 steps run with done clips padded (SEP, score 0, row 0).
+    ``step(ids [B * k, cur_len]) -> logits [B * k, V]`` (fp32, CPU) of the last position; ``start``: one list of token ids per clip,
+    CLS first (a prompt: longer lists; a clip inside its prompt is not ranked, every beam appends the prompt's token).
+    ``rule(logits, ids) -> logits`` (nullable): the constraints' -inf columns, ahead of the penalty.  Candidates are ranked by
+    score descending, ties to the smaller beam-major index.  ``stats`` (nullable dict) receives ``min_gap``, the smallest
+    difference between two scores whose order decided anything (the last candidate a clip's walk took against the first it left,
+    a hypothesis kept or displaced, is_done, the final ranks), ``done_step`` per clip (the first step at which it was done, or None), ``sep_hyps`` per clip
+    (hypotheses stored because a candidate was SEP) and ``displaced`` per clip (stored hypotheses thrown out by a better one).
+    -> predictions int64 [B, n, max_len] (SEP behind every hypothesis), scores fp32 [B, n] (-1e5: no hypothesis), lengths int32
+    [B, n], last_tokens int64 [B, n] (the candidate that finished each hypothesis: SEP, or any token at the last step)."""
+    B, n = len(start), int(num_keep_best)
+    pn = k if per_node_beam_size is None else int(per_node_beam_size)
+    K = k * pn
+    plen = [len(p) for p in start]
+    ids = torch.tensor([[p[0]] for p in start for _ in range(k)], dtype=torch.long)
+    beam_scores = torch.zeros(B, k)
+    beam_scores[:, 1:] = -1e9
+    beam_scores = beam_scores.view(-1)
+    hyps = [[] for _ in range(B)]           # storage order: (score, ids list, finishing token)
+    done = [False] * B
+    gaps = []
+    st = dict(done_step=[None] * B, sep_hyps=[0] * B, displaced=[0] * B)
+    for cur_len in range(1, max_len):
+        logits = step(ids).float().clone()
+        V = logits.shape[-1]
+        if rule is not None:
+            logits = rule(logits, ids)
+        if repetition_penalty != 1.0:
+            for r in range(B * k):
+                for tok in set(t for t in ids[r].tolist() if 0 <= t < V):
+                    logits[r, tok] = logits[r, tok] * repetition_penalty if logits[r, tok] < 0 else logits[r, tok] / repetition_penalty
+        cand = (torch.log_softmax(logits, dim=-1) + beam_scores[:, None]).view(B, k * V)
+        order = torch.sort(-cand, dim=1, stable=True).indices
+        nxt = []
+        for b in range(B):
+            if cur_len < plen[b]:                                                   # forced: nothing is ranked, stored or tested
+                nxt += [(float(beam_scores[b * k + j]), start[b][cur_len], b * k + j) for j in range(k)]
+                continue
+            cs = cand[b, order[b, :K + 1]].tolist()
+            if not done[b] and len(hyps[b]) == n:
+                worst = min(h[0] for h in hyps[b])
+                limit = cs[0] / (max_len - 1) ** length_penalty                     # (Python floats, as the reference container)
+                done[b] = worst >= limit
+                gaps.append(abs(worst - limit))
+                if done[b]:
+                    st["done_step"][b] = cur_len
+            if done[b]:
+                nxt += [(0.0, sep_id, 0)] * k
+                continue
+            live = []
+            for c in range(K):
+                idx = int(order[b, c])
+                beam, word = idx // V, idx % V
+                if word == sep_id or cur_len + 1 == max_len:
+                    score = cs[c] / cur_len ** length_penalty
+                    hyp = (score, ids[b * k + beam].tolist(), word)
+                    if len(hyps[b]) < n:
+                        hyps[b].append(hyp)
+                        st["sep_hyps"][b] += word == sep_id
+                    else:
+                        e = min(range(n), key=lambda i: (hyps[b][i][0], i))          # the earliest stored of equal minima
+                        gaps.append(abs(score - hyps[b][e][0]))
+                        if score > hyps[b][e][0]:
+                            del hyps[b][e]
+                            hyps[b].append(hyp)
+                            st["displaced"][b] += 1
+                            st["sep_hyps"][b] += word == sep_id
+                else:
+                    live.append((cs[c], word, b * k + beam))
+                if len(live) == k:
+                    break
+            gaps.append(cs[c] - cs[c + 1])          # the walk's end: the order inside it changes neither what is stored nor what lives
+            nxt += live if len(live) == k else [(0.0, sep_id, 0)] * k                # the last step, or too few live beams: pad
+        beam_scores = torch.tensor([x[0] for x in nxt])
+        ids = torch.cat([ids[torch.tensor([x[2] for x in nxt])], torch.tensor([[x[1]] for x in nxt], dtype=torch.long)], dim=1)
+    pred = torch.full((B, n, max_len), sep_id, dtype=torch.long)
+    scores = torch.full((B, n), -1e5)
+    lengths = torch.zeros((B, n), dtype=torch.int32)
+    last = torch.full((B, n), sep_id, dtype=torch.long)
+    for b in range(B):
+        ranked = sorted(range(len(hyps[b])), key=lambda i: (-hyps[b][i][0], i))      # equal scores in storage order
+        gaps += [hyps[b][ranked[i]][0] - hyps[b][ranked[i + 1]][0] for i in range(len(ranked) - 1)]
+        for r, i in enumerate(ranked):
+            s, toks, word = hyps[b][i]
+            pred[b, r, :len(toks)] = torch.tensor(toks)
+            scores[b, r], lengths[b, r], last[b, r] = s, len(toks), word
+    if stats is not None:
+        stats.update(st, min_gap=min(gaps) if gaps else float("inf"))
+    return dict(predictions=pred, scores=scores, lengths=lengths, last_tokens=last)
+
+
 class GeneratorWithBeamSearch:
     def __init__(self, eos_index: int, max_steps: int, beam_size: int, per_node_beam_size: int = 2,
                  length_penalty: float = 1.0, repetition_penalty: float = 1.0, temperature: float = 1.0,

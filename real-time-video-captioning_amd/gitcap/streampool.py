@@ -89,7 +89,7 @@ class _StreamPool:
 
     def _caption(self, due, to_cpu: bool) -> dict:
         out = {}
-        B = self._m.max_batch
+        B = self._chunk_rows()
         sep = self._m.cfg.sep_token_id
         for c0 in range(0, len(due), B):
             chunk = due[c0:c0 + B]
@@ -100,6 +100,10 @@ class _StreamPool:
             self._deliver(out, chunk, ids, lp, tk, seen, to_cpu, sep)
             self._sched.captioned(chunk)
         return out
+
+    def _chunk_rows(self) -> int:
+        """Streams captioned per library call."""
+        return self._m.max_batch
 
     def _deliver(self, out, chunk, ids, lp, tk, seen, to_cpu, sep):
         """One chunk's rows into `out` and the last_* dicts, each cut behind its own first SEP under all_sep."""
@@ -131,22 +135,33 @@ class _StreamPool:
 
 
 class StudentStreamPool(_StreamPool):
-    """The pool of StudentCaptioner.stream_pool: windows of ``mem_tokens`` frames; greedy captions only.  ``constraints``
+    """The pool of StudentCaptioner.stream_pool: windows of ``mem_tokens`` frames.  ``constraints``
     (stream_pool's constraint arguments, or None): one set of rules for every stream, attached again for every pool call.
+    ``beams`` = None (greedy) or k: a caption is then the best beam [max_len] of gitcap_student_pool_beam_search (CLS first, not
+    cut), max_batch // k streams per call; with ``search`` (a gitcap.student._StudentSearch) it is rank 0 of the search that ends
+    hypotheses at SEP, and ``last_scores[stream]`` [n], ``last_predictions[stream]`` [n, max_len] and ``last_lengths[stream]`` [n]
+    hold all ranks.  A prompt of a pool with beams takes at most max_len - 1 tokens.
     ``set_prompt(stream, ids)``: a standing text prefix per camera (include/gitcap.h: gitcap_student_attach_prompt); a pool call
     attaches the ragged table of the cameras it captions, a camera without one being the row of CLS alone, and
     ``last_prompt_lengths[stream]`` holds the prompt tokens (CLS included) of that camera's latest caption."""
 
     _WHAT = "mem_tokens"
 
-    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None):
-        self._co = constraints
+    def __init__(self, model, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, constraints=None, beams=None, search=None):
+        self._co, self._beams, self._se = constraints, beams, search
+        self._plimit = (max_len, "max_len") if beams is None else (max_len - 1, "max_len - 1")
+        if search is not None:
+            self.last_scores, self.last_predictions, self.last_lengths = {}, {}, {}
         self._prompts = {}                  # stream -> its prompt, int64 1-D on the CPU, CLS first
         self.last_prompt_lengths = {}
         super().__init__(model, streams, model.cfg.mem_tokens, hop, max_len, mode, logprobs, top_logprobs, min_frames)
 
     def _last_dicts(self):
-        return super()._last_dicts() + (self.last_prompt_lengths,)
+        own = (self.last_scores, self.last_predictions, self.last_lengths) if self._se is not None else ()
+        return super()._last_dicts() + (self.last_prompt_lengths,) + own
+
+    def _chunk_rows(self) -> int:
+        return self._m.max_batch // (self._beams or 1)
 
     def set_prompt(self, stream: int, ids):
         """The prompt of one camera from its next caption on: ``ids`` 1-D token ids (CLS is prepended where missing; at most max_len
@@ -161,7 +176,7 @@ class StudentStreamPool(_StreamPool):
         row = torch.as_tensor(ids)
         if row.dim() != 1:
             raise ValueError(f"a camera's prompt is 1-D token ids, got {tuple(row.shape)}")
-        pr = self._m._prompt([row], None, 1, self._max_len, "max_len")          # the shared normaliser: CLS, the length limit
+        pr = self._m._prompt([row], None, 1, *self._plimit)          # the shared normaliser: CLS, the length limit
         self._prompts[s] = pr.ids[0].cpu()
 
     def _chunk_prompt(self, ids):
@@ -169,10 +184,18 @@ class StudentStreamPool(_StreamPool):
         if not any(s in self._prompts for s in ids):
             return None
         cls = torch.tensor([self._m.cls_token_id], dtype=torch.int64)
-        return self._m._prompt([self._prompts.get(s, cls) for s in ids], None, len(ids), self._max_len, "max_len")
+        return self._m._prompt([self._prompts.get(s, cls) for s in ids], None, len(ids), *self._plimit)
 
     def _deliver(self, out, chunk, ids, lp, tk, seen, to_cpu, sep):
         """The cut behind a row's own first SEP looks at what the model emitted: a SEP inside a camera's prompt does not end its row."""
+        if self._beams is not None:         # beam captions are whole rows: the best beam, or rank 0 of (predictions, scores, lengths)
+            for r, s in enumerate(chunk):
+                self.last_frames[s] = int(seen[r])
+                if self._se is None:
+                    out[s] = ids[r]
+                else:
+                    out[s], self.last_predictions[s], self.last_scores[s], self.last_lengths[s] = ids[0][r, 0], ids[0][r], ids[1][r], ids[2][r]
+            return
         if self._mode != STOP_ALL_SEP or all(self.last_prompt_lengths.get(s, 1) == 1 for s in chunk):
             return super()._deliver(out, chunk, ids, lp, tk, seen, to_cpu, sep)
         host = ids.cpu()
@@ -207,6 +230,8 @@ class StudentStreamPool(_StreamPool):
         """One gitcap_student_pool_greedy on streams `ids` (at most max_batch) -> (ids [B, 1+max_len], log-probs or None, (top ids,
         top log-probs) or None, frames seen per row), on the device."""
         m, B = self._m, len(ids)
+        if self._beams is not None:
+            return self._beam_lib(ids)
         out, lp, tk = self._buffers(B)
         seen = (ctypes.c_int32 * B)()
         with torch.cuda.device(m._dev):
@@ -220,6 +245,29 @@ class StudentStreamPool(_StreamPool):
         for r, s in enumerate(ids):
             self.last_prompt_lengths[s] = 1 if pr is None else pr.host_lengths[r]
         return out, lp, tk, list(seen)
+
+    def _beam_lib(self, ids):
+        """One gitcap_student_pool_beam_search on streams `ids` (at most max_batch // beams) -> (the best beams [B, max_len], or the
+        search's (predictions [B, n, max_len], scores [B, n], lengths [B, n]); None; None; frames seen per row), on the device."""
+        m, B = self._m, len(ids)
+        sid = (ctypes.c_int32 * B)(*ids)
+        call = lambda ptr: m._call("gitcap_student_pool_beam_search", sid, B, self._beams, self._max_len, ptr, m._stream())
+        with torch.cuda.device(m._dev):
+            if self._co is not None:
+                self._co.attach(m)
+            pr = self._chunk_prompt(ids)
+            if pr is not None:
+                pr.attach(m)
+            if self._se is not None:
+                res = self._se.run(m, B, self._max_len, call)
+                out = (res["predictions"], res["scores"], res["lengths"])
+            else:
+                out = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
+                call(_lib.ptr(out))
+        held = self._counts_lib()
+        for r, s in enumerate(ids):
+            self.last_prompt_lengths[s] = 1 if pr is None else pr.host_lengths[r]
+        return out, None, None, [held[s] for s in ids]
 
     def _prepare(self, frames: torch.Tensor) -> torch.Tensor:
         """uint8 [n,H,W,3] / fp32 [n,3,S,S] frames, or memory tokens [n,d_model] -> memory tokens [n,d_model] fp32 on the device."""

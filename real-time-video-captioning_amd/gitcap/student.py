@@ -49,6 +49,45 @@ class _StudentConstraints:
         model._call("gitcap_student_attach_constraints", ctypes.byref(self._c))
 
 
+class _StudentSearch:
+    """The options of a beam-family call that ends hypotheses at SEP (include/gitcap.h: gitcap_student_attach_search), checked as the
+    library checks them, before anything is launched.  ``run`` allocates the outputs, attaches and makes the call."""
+
+    def __init__(self, k, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty):
+        pn = k if per_node_beam_size is None else int(per_node_beam_size)
+        n = int(num_keep_best)
+        if not 1 <= n <= k:
+            raise ValueError(f"num_keep_best={num_keep_best} outside 1..k={k}")
+        if not 2 <= pn <= k or k * pn > 16:
+            raise ValueError(f"per_node_beam_size={pn} must be in 2..k={k} with k * per_node_beam_size <= 16 (eos=True needs k >= 2)")
+        rp, lp = float(repetition_penalty), float(length_penalty)
+        if not (rp > 0 and np.isfinite(rp) and np.isfinite(lp)):
+            raise ValueError("repetition_penalty must be > 0 and finite, length_penalty finite")
+        self.k, self.n, self.pn, self.rp, self.lp = int(k), n, pn, rp, lp
+
+    def run(self, model, B, max_len, call) -> dict:
+        """``call(ids_ptr)`` makes the library call that consumes the attachment -> predictions [B, n, max_len], scores and
+        lengths [B, n], on the device."""
+        dev = model._dev
+        pred = torch.empty((B, self.n, max_len), dtype=torch.int64, device=dev)
+        scores = torch.empty((B, self.n), dtype=torch.float32, device=dev)
+        lengths = torch.empty((B, self.n), dtype=torch.int32, device=dev)
+        c = _lib.CStudentSearchOptions(self.n, self.lp, self.pn, self.rp, scores.data_ptr(), lengths.data_ptr())
+        model._call("gitcap_student_attach_search", ctypes.byref(c))
+        call(_lib.ptr(pred))
+        return dict(predictions=pred, scores=scores, lengths=lengths)
+
+
+def _search_options(eos, k, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty):
+    """The search arguments of the beam-family calls -> _StudentSearch, or None for today's search (eos=False and the defaults)."""
+    if eos:
+        return _StudentSearch(k, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty)
+    if length_penalty != 1.0 or num_keep_best != 1 or per_node_beam_size is not None or repetition_penalty != 1.0:
+        raise ValueError("length_penalty, num_keep_best, per_node_beam_size and repetition_penalty belong to the search that ends "
+                         "hypotheses at SEP: pass eos=True")
+    return None
+
+
 def _constrained(no_repeat_ngram_size, min_length, suppress_tokens) -> bool:
     return bool(no_repeat_ngram_size or min_length or suppress_tokens is not None)
 
@@ -64,11 +103,15 @@ class StudentCaptionStream(_WindowStream):
     ``constraints`` (a _StudentConstraints or None): the stream's hard constraints, attached again for every caption.
     ``prompt`` (caption_stream's ``prompt=``, or None): one text prefix per stream row, attached again for every caption; the
     ``prompt`` property replaces it (None: no prompt from the next caption on) and ``prompt_lengths`` [batch] tells how many leading
-    tokens of every caption row are the prompt's (CLS included; None without a prompt)."""
+    tokens of every caption row are the prompt's (CLS included; None without a prompt).
+    ``search`` (a _StudentSearch or None; streams with ``beams``): the search that ends hypotheses at SEP -- a push returns rank 0
+    [batch, max_len] and ``last_predictions`` [batch, n, max_len], ``last_scores`` / ``last_lengths`` [batch, n] hold all ranks."""
 
     def __init__(self, model, batch, hop, max_len, mode, beams, gate=None, carry=False, logprobs=False, top_logprobs=0, partial=False,
-                 constraints=None, prompt=None):
+                 constraints=None, prompt=None, search=None):
         self._carry, self._prev, self._beams = bool(carry), None, beams
+        self._se = search
+        self.last_predictions = self.last_scores = self.last_lengths = None
         self._co = constraints
         self._batch = int(batch)
         self._pr = None
@@ -162,13 +205,21 @@ class StudentCaptionStream(_WindowStream):
                     self._stats[k] += v
                 self._stats["last"] = last
             else:
-                ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
                 if self._co is not None:
                     self._co.attach(m)
                 if self._pr is not None:
                     self._pr.attach(m)
-                m._call("gitcap_student_window_beam_search", self._beams, self._max_len, _lib.ptr(ids), m._stream())
-                out = ids.cpu() if to_cpu else ids
+                call = lambda ptr: m._call("gitcap_student_window_beam_search", self._beams, self._max_len, ptr, m._stream())
+                if self._se is not None:
+                    res = self._se.run(m, B, self._max_len, call)
+                    if to_cpu:
+                        res = {name: t.cpu() for name, t in res.items()}
+                    self.last_predictions, self.last_scores, self.last_lengths = res["predictions"], res["scores"], res["lengths"]
+                    out = self.last_predictions[:, 0]
+                else:
+                    ids = torch.empty((B, self._max_len), dtype=torch.int64, device=m._dev)
+                    call(_lib.ptr(ids))
+                    out = ids.cpu() if to_cpu else ids
         if not self._partial:
             self.last_frames = m.cfg.mem_tokens
         self._stats["captions"] += 1
@@ -661,8 +712,17 @@ class StudentCaptioner(_NativeModule):
     @torch.no_grad()
     def beam_search(self, src: torch.Tensor, max_len: int = 10, k: int = 3, return_attention: bool = False, frame_counts=None,
                     no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=None, prompt=None,
-                    prompt_lengths=None) -> torch.Tensor:
+                    prompt_lengths=None, eos: bool = False, length_penalty: float = 1.0, num_keep_best: int = 1,
+                    per_node_beam_size: Optional[int] = None, repetition_penalty: float = 1.0):
         """model.py:189-318: k beams without end-of-sequence handling; returns the best beam [B, max_len].
+        ``eos=True``: the search that ends hypotheses at SEP instead (include/gitcap.h: gitcap_student_attach_search; the teacher's
+        search rules): each step ranks k * per_node_beam_size candidates (default k per beam; 2..k, at most 16 in all, so k >= 2), a
+        SEP candidate finishes its hypothesis with score = sum of log-probabilities / length ** length_penalty, a clip keeps its
+        num_keep_best (1..k) best and stops extending once no live beam can beat them; ``repetition_penalty`` rewrites the logits
+        of the tokens a row already holds.  Returns a dict: ``predictions`` int64 [B, n, max_len] (rank 0 best, SEP behind every
+        hypothesis), ``scores`` fp32 [B, n] (-1e5 for a rank without a hypothesis) and ``lengths`` int32 [B, n] (tokens, CLS
+        included, SEP not).  Combines with frame_counts, the constraint arguments and prompts.  Without ``eos=True`` the four
+        search arguments must keep their defaults, and the call is today's, launch for launch.
         Runs on the device with the exact KV cache and no host round trip (``gitcap_student_beam_search``): the k beams
         of a clip are rows b*k+i (B*k <= max_batch), candidates are ranked by the beam top-k kernel, the cached K/V rows
         follow their beams.  frame_counts (or ``src`` as a list of clips; as in greedy_decode): clips that differ in length; the k
@@ -688,23 +748,29 @@ class StudentCaptioner(_NativeModule):
             raise ValueError(f"max_len={max_len} exceeds max_text_len+1={self.max_text_len + 1}")
         if max_len < 2 or k < 1 or k > 16:
             raise ValueError("beam_search needs max_len >= 2 and 1 <= k <= 16")
-        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, k)
+        se = _search_options(eos, k, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty)
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, k if se is None else k * se.pn)
         pr = self._prompt(prompt, prompt_lengths, B, max_len - 1, "max_len - 1")
-        best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
+        call = lambda out: self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, out, self._stream())
         with torch.cuda.device(self._dev):
             self._attach_counts(counts)
             if co is not None:
                 co.attach(self)
             if pr is not None:
                 pr.attach(self)
-            self._call("gitcap_student_beam_search", _lib.ptr(mem), B, k, max_len, _lib.ptr(best), self._stream())
+            if se is not None:
+                res = se.run(self, B, max_len, call)
+                return {name: t.to(out_dev) if out_dev != t.device else t for name, t in res.items()}
+            best = torch.empty((B, max_len), dtype=torch.int64, device=self._dev)
+            call(_lib.ptr(best))
         return best.to(out_dev) if out_dev != best.device else best
 
     def caption_stream(self, batch: int = 1, hop: int = 1, max_len: int = 25, stop: Optional[str] = None,
                        beams: Optional[int] = None, gate: Optional[FrameGate] = None, carry: bool = False,
                        logprobs: bool = False, top_logprobs: int = 0, return_attention: bool = False,
                        partial: bool = False, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                       suppress_tokens=None, prompt=None) -> StudentCaptionStream:
+                       suppress_tokens=None, prompt=None, eos: bool = False, length_penalty: float = 1.0, num_keep_best: int = 1,
+                       per_node_beam_size: Optional[int] = None, repetition_penalty: float = 1.0) -> StudentCaptionStream:
         """A sliding caption window over live frames (the reference's webcam loop): ``push(frames)`` appends
         frames of `batch` clips and returns the caption of the last ``mem_tokens`` frames once the window is full and `hop`
         frames have arrived since the last one, else None.  hop = mem_tokens is the reference's tumbling loop
@@ -728,7 +794,13 @@ class StudentCaptioner(_NativeModule):
         again for every caption, greedy or ``beams``; not with ``carry`` (a draft call does not take them).
         ``prompt`` (as in greedy_decode: [batch, P] or a list of `batch` 1-D tensors): one text prefix per stream row, kept for the
         stream's life and attached again for every caption, greedy or ``beams``; ``stream.prompt = ...`` replaces it,
-        ``stream.prompt_lengths`` tells what of a caption row is prompt.  Not with ``carry``."""
+        ``stream.prompt_lengths`` tells what of a caption row is prompt.  Not with ``carry``.
+        ``eos`` / length_penalty / num_keep_best / per_node_beam_size / repetition_penalty (streams with ``beams``; as in
+        beam_search): with ``eos=True`` a push returns the best hypothesis of every clip [batch, max_len], and
+        ``stream.last_predictions`` [batch, n, max_len], ``stream.last_scores`` / ``stream.last_lengths`` [batch, n] hold all ranks:
+        bit for bit beam_search(eos=True) on the window's frames."""
+        if beams is None and (eos or length_penalty != 1.0 or num_keep_best != 1 or per_node_beam_size is not None or repetition_penalty != 1.0):
+            raise ValueError("eos= and the search arguments are for streams with beams")
         if return_attention:
             raise ValueError("return_attention= is not taken by the window streams (caption_stream) (its cache rows are not a caption's positions in order, or not the caller's to read yet): use attention(x, predictions) on the result")
         if not 0 <= int(top_logprobs) <= 32:
@@ -761,12 +833,16 @@ class StudentCaptioner(_NativeModule):
             if not isinstance(gate, FrameGate):
                 raise ValueError(f"gate must be a gitcap.framegate.FrameGate, got {type(gate).__name__}")
             gate.reset()
-        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, 1 if beams is None else beams)
-        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial, co, prompt)
+        se = None if beams is None else _search_options(eos, beams, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty)
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len,
+                               1 if beams is None else beams if se is None else beams * se.pn)
+        return StudentCaptionStream(self, batch, hop, max_len, mode, beams, gate, carry, logprobs, top_logprobs, partial, co, prompt, se)
 
     def stream_pool(self, streams: int, hop: int = 1, max_len: int = 25, stop: Optional[str] = None, logprobs: bool = False,
                     top_logprobs: int = 0, min_frames: int = 1, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                    suppress_tokens=None) -> StudentStreamPool:
+                    suppress_tokens=None, beams: Optional[int] = None, eos: bool = False, length_penalty: float = 1.0,
+                    num_keep_best: int = 1, per_node_beam_size: Optional[int] = None,
+                    repetition_penalty: float = 1.0) -> StudentStreamPool:
         """Several live cameras on one model (the multi-camera loop): `streams` independent windows of
         ``mem_tokens`` frames.  ``pool.push(frames, streams)`` takes n frames for any streams in any mix (frame i belongs to stream
         streams[i]), encodes them once in one packed pass and returns ``{stream: ids}`` for every stream that is due: at least
@@ -782,7 +858,14 @@ class StudentCaptioner(_NativeModule):
         The pool and a caption_stream() of the same model live side by side: opening one does not invalidate the other.  Opening
         another pool, moving the model or loading weights invalidates this one.
         Out of scope: scene-change gates (put one FrameGate per camera in front of ``push``; deciding all cameras' gates in one
-        launch is a later change), ``carry`` / drafts and beams.
+        launch is a later change) and ``carry`` / drafts.
+        ``beams=k`` (include/gitcap.h: gitcap_student_pool_beam_search): the due cameras are captioned by beam search, max_batch // k
+        of them per call, the k beam rows of a camera reading its K|V rows through the key tables (nothing is repeated).  A caption is
+        then the best beam [max_len] (not cut; max_len counts CLS, as in beam_search), bit for bit beam_search(max_len, k) on a list
+        holding the camera's frames.  With ``eos=True`` (and length_penalty / num_keep_best / per_node_beam_size /
+        repetition_penalty, as in beam_search) it is rank 0 of the search that ends hypotheses at SEP, ``pool.last_scores[stream]``
+        [n] holds its scores and ``pool.last_predictions[stream]`` [n, max_len] / ``pool.last_lengths[stream]`` [n] all ranks.  One
+        set of search rules for every camera; log-probabilities and alternatives belong to the greedy pool.
         no_repeat_ngram_size / min_length / suppress_tokens (as in greedy_decode): one set of rules for every camera's captions,
         attached again for every pool call; rules per camera are out of scope.
         ``pool.set_prompt(stream, ids)``: a standing text prefix for one camera (ids 1-D, CLS prepended where missing; None removes
@@ -792,21 +875,37 @@ class StudentCaptioner(_NativeModule):
             raise ValueError(f"top_logprobs={top_logprobs} outside 0..32")
         if streams < 1 or streams > 4096:
             raise ValueError(f"streams={streams} outside 1..4096")
-        if max_len < 1 or max_len > self.max_text_len:
-            raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
         mode = {"all_sep": STOP_ALL_SEP, "never": STOP_NEVER}[stop or self.stop]
-        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
-        return StudentStreamPool(self, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, co)
+        if beams is None:
+            if eos or length_penalty != 1.0 or num_keep_best != 1 or per_node_beam_size is not None or repetition_penalty != 1.0:
+                raise ValueError("eos= and the search arguments are for pools with beams")
+            if max_len < 1 or max_len > self.max_text_len:
+                raise ValueError(f"max_len={max_len} outside 1..max_text_len={self.max_text_len}")
+            co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len)
+            return StudentStreamPool(self, streams, hop, max_len, mode, logprobs, top_logprobs, min_frames, co)
+        if logprobs or top_logprobs:
+            raise ValueError("logprobs / top_logprobs are for greedy pools: they cannot be combined with beams")
+        if max_len < 2 or max_len - 1 > self.max_text_len or beams < 1 or beams > min(16, self.max_batch):
+            raise ValueError(f"a pool with beams needs 2 <= max_len <= max_text_len+1={self.max_text_len + 1} and 1 <= beams <= min(16, max_batch)")
+        se = _search_options(eos, beams, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty)
+        co = self._constraints(no_repeat_ngram_size, min_length, suppress_tokens, max_len, beams if se is None else beams * se.pn)
+        return StudentStreamPool(self, streams, hop, max_len, mode, False, 0, min_frames, co, beams, se)
 
     @torch.no_grad()
     def beam_search_host(self, src: torch.Tensor, max_len: int = 10, k: int = 3, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                         suppress_tokens=None, prompt=None, prompt_lengths=None) -> torch.Tensor:
+                         suppress_tokens=None, prompt=None, prompt_lengths=None, eos: bool = False, length_penalty: float = 1.0,
+                         num_keep_best: int = 1, per_node_beam_size: Optional[int] = None, repetition_penalty: float = 1.0,
+                         frame_counts=None, stats: Optional[dict] = None):
         """The same search driven from the host the way the reference writes it (every step recomputes the whole prefix
         through ``forward_decoder``, one host sync per step): the cross-check of ``beam_search`` in the tests.  The constraint
         arguments (as in beam_search) set every row's banned logits to -inf ahead of the log_softmax.
         prompt / prompt_lengths (as in beam_search): the search of every clip starts from its own prefix instead of the lone CLS;
-        prompts of different lengths are searched clip by clip (the reference's loop advances all rows in lockstep)."""
-        from .search import banned_tokens, check_constraints
+        prompts of different lengths are searched clip by clip (the reference's loop advances all rows in lockstep).
+        ``eos=True`` and the search arguments (as in beam_search): gitcap.search.eos_beam_search -- the teacher's search operator as
+        host logic -- over ``forward_decoder`` on the growing prefix: the yardstick of beam_search(eos=True), with its dict plus
+        ``last_tokens`` [B, n], the candidate that finished each hypothesis.  This form also takes frame_counts (or ``src`` as a
+        list of clips) and fills ``stats`` (eos_beam_search's)."""
+        from .search import banned_tokens, check_constraints, eos_beam_search
         cn, cm, sup = check_constraints(no_repeat_ngram_size, min_length, suppress_tokens)
         V, sep = self.cfg.vocab_length, self.cfg.sep_token_id
 
@@ -820,6 +919,23 @@ class StudentCaptioner(_NativeModule):
                     logits[r, cols] = float("-inf")
             return logits
 
+        se = _search_options(eos, k, length_penalty, num_keep_best, per_node_beam_size, repetition_penalty)
+        if se is not None:
+            if self._is_ragged(src, frame_counts):
+                mems, _, out_dev = self._clip_memories(src, frame_counts)
+            else:
+                out_dev = src.device
+                mems = list(self._memory(self._src_memory(src)))
+            B = len(mems)
+            if B * k > self.max_batch or max_len - 1 > self.max_text_len or max_len < 2:
+                raise ValueError(f"B*k={B * k} rows > max_batch={self.max_batch}, or max_len={max_len} outside 2..max_text_len+1")
+            pr = self._prompt(prompt, prompt_lengths, B, max_len - 1, "max_len - 1")
+            start = [[self.cls_token_id]] * B if pr is None else [pr.ids[b, :n].tolist() for b, n in enumerate(pr.host_lengths)]
+            mem_rep = [m for m in mems for _ in range(k)]                               # row b*k + i = beam i of clip b
+            res = eos_beam_search(lambda ids: self.forward_decoder(ids, mem_rep)[:, -1].cpu(), start, k=k, max_len=max_len, sep_id=sep,
+                                  length_penalty=se.lp, num_keep_best=se.n, per_node_beam_size=se.pn, repetition_penalty=se.rp,
+                                  rule=rule, stats=stats)
+            return {name: t.to(out_dev) for name, t in res.items()}
         out_dev = src.device
         memory = self._src_memory(src)
         mem = self._memory(memory)
